@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- end-to-end frames/s of the detect -> encode -> track hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config {2,3,5}] [--streams S]
+    python bench.py --gpus N --steps K --warmup W [--config {2,3,5}] [--streams S] [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input: one BGR frame from each of the S
 independent video streams this rank owns (detector forward + post-process on the frame, NMS + MARS encoder over
 ~20 synthetic detections per frame, deep_sort predict/update, count-line logic).  Frames and detections are
-generated before the timed region and the frames are resident in HBM when it starts.
+generated before the timed region and the frames are resident in HBM when it starts: at most FRAME_PERIOD distinct frames
+per stream, later steps replay them in order, so any --steps fits.
 
 --gpus N > 1: when this process was not started by a launcher (no RANK in the environment) it starts N ranks of
 itself with `python -m torch.distributed.run` (one per GPU, rendezvous on 127.0.0.1) BEFORE anything touches the
@@ -17,7 +18,10 @@ vector after the timed region (deepdish_amd/multistream.py).
 --config picks the BASELINE.json configuration (1-based): 2 = SSD-MobileNet-v1 + MARS + deep_sort on 640x480 frames
 (the headline; default), 3 = YOLOv5s-f16 detector on 640x640 frames, 5 = 1280x720 streams, one per GPU.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for the roofline / cpu_baseline fields).
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for the roofline / cpu_baseline fields).  A plain run sets up, warms
+up, times the K steps and prints the line; --full adds the passes that take runs of their own after the timed region (roofline of
+the dominant kernel, CPU baseline, parity samples against the oracle).  --dump-outputs DIR writes what the last timed step computed
+as DIR/*.npy (see dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import json
@@ -33,6 +37,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 N_OBJ = 20
+FRAME_PERIOD = 50                   # distinct frames per stream resident in HBM (142 GB at 3 072 streams, the default steps + warmup); later steps replay them in order
+RENDER_CHUNK = 8                    # streams rendered per device pass (~7 GB of temporaries at 50 frames)
 DEFAULT_DETECTOR_DTYPE = 'i8'       # the reference's own detector arithmetic (its ssdmobilenetv1.tflite is uint8-quantised); --detector-dtype f16 = the float model
 CONFIGS = {
     # 3 072 streams in 4 worker groups = 768 frames and ~15 000 crops per launch: with the crop-resident encoder kernels of round 5 bigger launches pay
@@ -56,7 +62,7 @@ CONFIGS = {
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=40)          # (steps + warmup) x streams x 0.92 MB of frames are resident in HBM: 141 GB at the defaults
+    ap.add_argument('--steps', type=int, default=40)          # min(steps + warmup, FRAME_PERIOD) x streams x 0.92 MB of frames are resident in HBM: 141 GB at the defaults
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--config', type=int, default=2, choices=sorted(CONFIGS),
                     help='BASELINE.json configuration (1-based): 2 headline, 3 YOLOv5s detector, 5 one 1280x720 stream per GPU')
@@ -68,7 +74,13 @@ def parse():
     ap.add_argument('--detector-dtype', choices=('f16', 'i8'), default=DEFAULT_DETECTOR_DTYPE,
                     help='SSD-MobileNet arithmetic (configs 2 and 5): i8 = the uint8-quantised model the reference ships '
                          '(tools/ssd_mobilenet.py:102), integer kernels bit-exact against the TFLite restatement; f16 = the float model')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also the extra passes: roofline of the dominant kernel, CPU baseline and the parity '
+                         'samples against the oracle (a plain run only sets up, warms up, times the steps and prints the line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64): every '
+                         'stream\'s track table and counts, the detector\'s decoded rows of the first frames of each worker group')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline and the parity samples')
     ap.add_argument('--ingest-host', action='store_true',
                     help='secondary figure (never the headline value): frames start in pinned host memory and cross PCIe '
                          'inside the timed region through the ingest ring (deepdish_amd/ingest.py), one step ahead of the compute')
@@ -76,7 +88,7 @@ def parse():
                     help='secondary figure (never the headline value): run with the reference\'s default background subtraction '
                          '(MOG2 on every frame + motion test on the detector boxes, deepdish.py:920-924,957; the reference uses '
                          'RATIO 0.25).  BASELINE.json\'s configurations run with --disable-background-subtraction')
-    ap.add_argument('--cpu-frames', type=int, default=40, help='frames per seed of the CPU baseline sample (3 seeds)')
+    ap.add_argument('--cpu-frames', type=int, default=40, help='frames per seed of the CPU baseline sample (3 seeds; --full)')
     ap.add_argument('--rehearse-cpu', action='store_true',
                     help='launcher / rendezvous / count-reduction rehearsal over gloo on the CPU: no frames are processed and no '
                          'throughput is reported (what tests/test_bench_launcher.py runs where there is no GPU)')
@@ -127,6 +139,65 @@ def _gen_stream(job):
     return frames, per
 
 
+def _scene_spec(job):
+    """What deepdish_amd.synth.Scene draws for one stream, without rendering: the background's coarse grid, the textures, every
+    frame's rectangles (Scene.frame's integer positions) and the injected detections.  render_frames() paints the frames from it
+    on the device with Scene.frame's arithmetic, so only ~1 MB per stream leaves a worker instead of every rendered frame."""
+    seed, n_frames, W, H = job
+    from deepdish_amd.synth import Scene
+
+    class SpecScene(Scene):
+        def _background(self, rng):                   # the same draw as Scene._background; the interpolation runs on the device
+            self.bg_lo = rng.integers(40, 200, (self.H // 32 + 2, self.W // 32 + 2, 3))
+
+    sc = SpecScene(seed=seed, n_obj=N_OBJ, width=W, height=H, n_frames=n_frames)
+    f = np.arange(n_frames)[:, None]
+    alive = (sc.t0[None] <= f) & (f < sc.t1[None])                       # Scene.alive, [F, n_obj]
+    xy = np.rint(sc.xy).astype(np.int32)                                 # int(round(.)): both round half to even
+    wh = np.stack([sc.w, sc.h], axis=1).astype(np.int32)
+    per = []
+    for k in range(n_frames):
+        boxes, scores, who, _ = sc.detections(k)
+        per.append(([tuple(int(v) for v in b) for b in boxes], ['person'] * len(boxes), [float(x) for x in scores]))
+    return (sc.bg_lo.astype(np.float32), sc.tex, xy, wh, alive), per
+
+
+def render_frames(specs, W, H, device):
+    """Scene.frame(f) of every frame of C streams at once, bit for bit: u8 [F, C, H, W, 3].  The background is Scene._background's
+    bilinear stretch in float64 (the same operations in the same order), the rectangles are pasted in object order (a later object
+    covers an earlier one) with the texture lookup (row * 16 // h, column * 8 // w)."""
+    import torch
+    lo = torch.from_numpy(np.stack([s[0] for s in specs])).to(device)                  # [C, H/32+2, W/32+2, 3] f32
+    tex = torch.from_numpy(np.stack([s[1] for s in specs])).to(device)                 # [C, n, 16, 8, 3] u8
+    xy = torch.from_numpy(np.stack([s[2] for s in specs])).to(device).long()           # [C, F, n, 2]
+    wh = torch.from_numpy(np.stack([s[3] for s in specs])).to(device).long()           # [C, n, 2]
+    alive = torch.from_numpy(np.stack([s[4] for s in specs])).to(device)               # [C, F, n]
+    C, F, n = alive.shape
+    yy = torch.arange(H, dtype=torch.float64, device=device)[:, None] / 32.0
+    xx = torch.arange(W, dtype=torch.float64, device=device)[None, :] / 32.0
+    y0, x0 = torch.floor(yy).long(), torch.floor(xx).long()
+    fy, fx = (yy - y0)[..., None], (xx - x0)[..., None]
+    bg = (lo[:, y0, x0] * (1 - fy) * (1 - fx) + lo[:, y0 + 1, x0] * fy * (1 - fx)
+          + lo[:, y0, x0 + 1] * (1 - fy) * fx + lo[:, y0 + 1, x0 + 1] * fy * fx)
+    bg = bg.clamp(0, 255).to(torch.uint8)                                              # [C, H, W, 3]
+    Y = torch.arange(H, device=device).view(1, 1, H, 1)
+    X = torch.arange(W, device=device).view(1, 1, 1, W)
+    owner = torch.full((C, F, H, W), -1, dtype=torch.int8, device=device)
+    for i in range(n):
+        x, y = xy[:, :, i, 0].view(C, F, 1, 1), xy[:, :, i, 1].view(C, F, 1, 1)
+        w, h = wh[:, i, 0].view(C, 1, 1, 1), wh[:, i, 1].view(C, 1, 1, 1)
+        rows = alive[:, :, i].view(C, F, 1, 1) & (Y >= y) & (Y < y + h)
+        owner.masked_fill_(rows & (X >= x) & (X < x + w), i)
+    inside = owner >= 0
+    o = owner.long().clamp_(min=0)
+    pick = lambda v: torch.gather(v.unsqueeze(2).expand(C, F, H, n), 3, o)          # noqa: E731 -- v [C, F, n] at each pixel's owner
+    ty = ((Y - pick(xy[..., 1])) * 16 // pick(wh[:, None, :, 1].expand(C, F, n))).clamp_(0, 15)
+    tx = ((X - pick(xy[..., 0])) * 8 // pick(wh[:, None, :, 0].expand(C, F, n))).clamp_(0, 7)
+    flat = (torch.arange(C, device=device).view(C, 1, 1, 1) * n + o) * 128 + ty * 8 + tx
+    texel = tex.reshape(C * n * 128, 3)[flat]                                          # [C, F, H, W, 3]
+    return torch.where(inside[..., None], texel, bg[:, None]).transpose(0, 1)
+
+
 def gen_workers(world, streams):
     """Generator processes of this rank: the ranks of one node share its cores, each rank takes its share of half of them."""
     workers = max(1, min(16, (os.cpu_count() or 2) // (2 * max(1, world)), streams))
@@ -160,6 +231,28 @@ def make_inputs(pool, rank, streams, n_frames, W, H, sink):
     for s, (fr, per) in enumerate(it):
         sink(s, fr)
         dets[s] = per
+    if pool is not None:
+        pool.close()
+        pool.join()
+    return dets
+
+
+def make_inputs_rendered(pool, rank, streams, n_frames, W, H, dev_frames, bounds, device):
+    """make_inputs for frames resident in HBM: the workers send each stream's scene draws (_scene_spec) and the frames are
+    painted straight into dev_frames[g] [F, S_g, H, W, 3] (render_frames), RENDER_CHUNK streams per pass."""
+    dets = [None] * streams
+    seed_rank = int(os.environ.get('DD_BENCH_SEED_RANK', rank))
+    jobs = [(1000 * seed_rank + s, n_frames, W, H) for s in range(streams)]
+    it = pool.imap(_scene_spec, jobs, chunksize=4) if pool is not None else map(_scene_spec, jobs)
+    specs = []
+    for s, (spec, per) in enumerate(it):
+        dets[s] = per
+        specs.append(spec)
+        g = max(k for k in range(len(bounds) - 1) if bounds[k] <= s)
+        if len(specs) == RENDER_CHUNK or s + 1 == streams or s + 1 == bounds[g + 1]:
+            a = s + 1 - len(specs) - bounds[g]
+            dev_frames[g][:, a:a + len(specs)] = render_frames(specs, W, H, device)
+            specs = []
     if pool is not None:
         pool.close()
         pool.join()
@@ -360,6 +453,53 @@ def detector_sample_check(model, sc, device, W, H, streams):
                 chain='Pillow Lanczos -> nets_quant.ssd_quant_forward -> ssd_quant_decode -> nets_torch.ssd_postprocess_decoded -> detectors_np tail')
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_DETECTOR_BYTES = 32 << 20          # the detector sample's share of the dump (the whole dump stays under 64 MB)
+
+
+def dump_outputs(out_dir, pipes, prefix=''):
+    """What the last timed step left for a caller of the pipelines, as .npy files (float64 / float32):
+    track_table  [T, 15] f64: stream, id, state, time_since_update, hits, age, last detection, Kalman mean (8) -- every live track of every stream;
+    counts       [S, labels, 4] f64: (pos, neg, int, del) per stream;
+    detector_*   f32: the detector's decoded rows (SSD: boxes, scores, classes, keys per anchor; YOLOv5: boxes, confidence, classes per row)
+                 of the first frames of every worker group -- the same number of frames per group, chosen by the size alone."""
+    from deepdish_amd._lib import lib, check
+    from deepdish_amd.runtime import ptr
+    os.makedirs(out_dir, exist_ok=True)
+    rows, s0 = [], 0
+    for p in pipes:
+        for z in range(p.S):
+            ints, means = p.tracker(z).table()
+            rows.append(np.concatenate([np.full((len(ints), 1), s0 + z, np.float64), ints.astype(np.float64), means], axis=1))
+        s0 += p.S
+    files = {'track_table': np.concatenate(rows).reshape(-1, 15),
+             'counts': np.concatenate([p.counts() for p in pipes]).astype(np.float64)}
+    det = [p.det for p in pipes]
+    if all(d is not None for d in det):
+        meta = det[0].program.meta
+        if 'anchors' in meta and os.environ.get('DD_SSD_DEC', '1') != '0':
+            A = len(meta['anchors'])
+            names, widths, read = ('boxes', 'scores', 'classes', 'keys'), (4, 1, 1, 1), lib().dd_net_ssd_decoded_read
+        elif 'rows' in meta and os.environ.get('DD_YOLO_DEC', '1') != '0':
+            A = int(meta['rows'])
+            names, widths, read = ('boxes', 'confidence', 'classes'), (4, 1, 1), lib().dd_net_yolo_decoded_read
+        else:
+            A = 0
+        if A:
+            n = max(1, min(min(p.S for p in pipes), DUMP_DETECTOR_BYTES // (len(pipes) * A * sum(widths) * 4)))
+            parts = {k: [] for k in names}
+            for d in det:
+                bufs = [np.zeros((n, A, w), np.int32 if k == 'classes' else np.float32) for k, w in zip(names, widths)]
+                check(read(d._h, n, *[ptr(b) for b in bufs]), read.__name__)
+                for k, b in zip(names, bufs):
+                    parts[k].append(b.astype(np.float32))
+            for k in names:
+                files['detector_' + k] = np.concatenate(parts[k])
+    for k, v in files.items():
+        np.save(os.path.join(out_dir, prefix + k + '.npy'), v)
+    return sorted(files)
+
+
 # ------------------------------------------------------------------------------------------------ rehearsal
 def rehearse(args, rank, world, real_stdout):
     """No GPU: the launcher, the rendezvous, the barrier / max-over-ranks timing protocol and the count reduction,
@@ -462,14 +602,16 @@ def main():
     from deepdish_amd.multistream import reduce_counts
     from deepdish_amd.runtime import Context
     n_frames = args.warmup + args.steps
-    # every step's frames are resident before the timed region (HBM, or pinned host memory + the ring's device slots with --ingest-host):
-    # say so before allocating rather than dying inside an allocation (engines: ~14 MB per stream at these launch sizes)
-    need = n_frames * args.streams * H * W * 3
+    # frames resident in HBM: at most FRAME_PERIOD distinct frames per stream, steps beyond them replay them in order (step f takes
+    # frame f % period), so any --steps fits; --ingest-host keeps one pinned slot per step.  Say so before allocating rather than dying
+    # inside an allocation (engines: ~14 MB per stream at these launch sizes)
+    period = n_frames if args.ingest_host else min(n_frames, FRAME_PERIOD)
+    need = period * args.streams * H * W * 3
     free_b, total_b = torch.cuda.mem_get_info(local_rank)
     engines = args.streams * 14 * (1 << 20)
     if need + engines > free_b:
         sys.stderr.write('bench.py: %d steps x %d streams of %dx%d frames = %.1f GB resident (+ ~%.1f GB of engines), %.1f GB free on the device: '
-                         'lower --steps / --warmup / --streams\n' % (n_frames, args.streams, W, H, need / 1e9, engines / 1e9, free_b / 1e9))
+                         'lower --steps / --warmup / --streams\n' % (period, args.streams, W, H, need / 1e9, engines / 1e9, free_b / 1e9))
         sys.exit(2)
     bounds = [round(g * args.streams / G) for g in range(G + 1)]
     ctxs = [Context(local_rank) for _ in range(G)]
@@ -488,15 +630,14 @@ def main():
             for f in range(n_frames):
                 ings[g].host(f)[s - bounds[g]] = fr[f]
     else:
-        # frames resident in HBM before the timed region: per group [F][S_g][H][W][3]
-        dev_frames = [torch.empty((n_frames, bounds[g + 1] - bounds[g], H, W, 3), dtype=torch.uint8, device=f'cuda:{local_rank}')
+        # frames resident in HBM before the timed region: per group [period][S_g][H][W][3], rendered on the device from the scenes' draws
+        dev_frames = [torch.empty((period, bounds[g + 1] - bounds[g], H, W, 3), dtype=torch.uint8, device=f'cuda:{local_rank}')
                       for g in range(G)]
-
-        def sink(s, fr):
-            g = group_of[s]
-            dev_frames[g][:, s - bounds[g]] = torch.from_numpy(fr).to(f'cuda:{local_rank}')
-    dets = make_inputs(gen_pool, rank, args.streams, n_frames, W, H, sink)
-    injected = [[pipes[g].pack_injected([dets[s][f] for s in range(bounds[g], bounds[g + 1])]) for f in range(n_frames)]
+    if ings is not None:
+        dets = make_inputs(gen_pool, rank, args.streams, n_frames, W, H, sink)
+    else:
+        dets = make_inputs_rendered(gen_pool, rank, args.streams, period, W, H, dev_frames, bounds, f'cuda:{local_rank}')
+    injected = [[pipes[g].pack_injected([dets[s][f] for s in range(bounds[g], bounds[g + 1])]) for f in range(period)]
                 for g in range(G)]
     torch.cuda.synchronize()
 
@@ -518,8 +659,8 @@ def main():
             return
         ahead = os.environ.get('DD_BENCH_NO_LOOKAHEAD') is None
         for f in range(f0, f1):                                   # blocking C call, releases the GIL; the detector of
-            pipes[g].step(dev_frames[g][f], injected[g][f],       # frame f+1 is queued behind this step's own detections
-                          dev_frames[g][f + 1] if ahead and f + 1 < f1 else None)
+            pipes[g].step(dev_frames[g][f % period], injected[g][f % period],       # frame f+1 is queued behind this step's own detections
+                          dev_frames[g][(f + 1) % period] if ahead and f + 1 < f1 else None)
             if step_times is not None:
                 step_times[g].append(time.perf_counter())
 
@@ -572,6 +713,8 @@ def main():
     counts = reduce_counts(local_counts, device=red_dev)                  # RCCL: the only exchange step of the path
     dt = float(tmax.item())
     total_frames = args.steps * args.streams * world
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pipes, 'rank%d_' % rank if world > 1 else '')
 
     if rank == 0:
         out = {
@@ -613,10 +756,10 @@ def main():
                            'note': 'PCIe Gen5 x16 spec 63 GB/s (MI355X_MICROARCH.md): the most a host can feed one GPU at %dx%d BGR; copy_ceiling_measured = pinned '
                                    'host -> device copies alone on an idle GPU of this pool (scripts/experiments/pcie_rates.py, 2 streams x 708 MB, either NUMA node)' % (W, H)}
             extra_only = True
-        if not extra_only:
+        if args.full and not extra_only:
             try:
                 from deepdish_amd.profile import dominant_kernel_roofline
-                out['roofline'] = dominant_kernel_roofline(pipes, lambda g, f: pipes[g].step(dev_frames[g][f], injected[g][f]), args)
+                out['roofline'] = dominant_kernel_roofline(pipes, lambda g, f: pipes[g].step(dev_frames[g][f % period], injected[g][f % period]), args)
             except Exception as e:                            # never let the extra pass hide the headline number
                 out['roofline'] = None
                 out['roofline_error'] = repr(e)
