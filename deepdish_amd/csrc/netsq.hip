@@ -1437,16 +1437,32 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
             DD_REQUIRE(td->w >= 16, DD_E_ARG, "dd_net_forward: uint8 first layer: output narrower than a fragment");
             DD_REQUIRE(td->pad == 1 && td->cs == 32 && o[11] == 32 && (reinterpret_cast<uintptr_t>(input) & 3) == 0 && (P.total_bytes & 3) == 0 && !P.R.linear && P.R.e >= 1,
                        DD_E_ARG, "dd_net_forward: uint8 first layer: 32 channels into a bordered tensor from a 4-byte aligned batch");
-            const int n_frags = dd_ceil_div(P.m, 16);
-            DD_REQUIRE(o[46] != 0 && P.total_bytes < (1ll << 31) - 16 && P.out_bytes < (1ll << 31) - 16, DD_E_ARG, "dd_net_forward: uint8 first layer: no folded requantisation constants in the program, or a batch beyond 31-bit offsets");
+            DD_REQUIRE(o[46] != 0, DD_E_ARG, "dd_net_forward: uint8 first layer: no folded requantisation constants in the program");
+            // The kernel's source and destination are 31-bit buffer ranges (2 904 frames of 300x300: 0.74 MB of bordered output each).  A bigger
+            // batch runs as launches over chunks of frames -- the frames are independent, so a chunk is the same kernel on other base pointers.
+            const long long in_img = (long long)P.H * P.W * 3, out_img = (long long)(P.ho + 2) * 2 * (P.wo + 2) * 16, lim31 = (1ll << 31) - 17;
+            long long lim = std::min(lim31 / in_img, lim31 / out_img);
+            if (in_img % 4) lim &= ~3ll;                                  // (chunks of whole 4-frame groups keep every chunk's source 4-byte aligned)
+            DD_REQUIRE(lim >= 1, DD_E_CAPACITY, "dd_net_forward: uint8 first layer: one frame beyond 31-bit offsets");
+            const long long n_chunks = (nimg + lim - 1) / lim;
+            long long chunk = (nimg + n_chunks - 1) / n_chunks;
+            if (in_img % 4) chunk = std::min(lim, (chunk + 3) & ~3ll);
             const int sat0 = P.R.lo == 0 && P.R.hi == 255 ? (P.R.e <= 8 ? 2 : 1) : 0;
-            const dim3 grid0(dd_ceil_div(n_frags, 4 * C0F));
+            const uint8_t *const src0 = P.src;
+            uint8_t *const out0 = P.out;
+            for (long long c0 = 0; c0 < nimg; c0 += chunk) {
+                const int nc = (int)std::min(chunk, nimg - c0);
+                P.src = src0 + c0 * in_img; P.out = out0 + c0 * out_img;
+                P.total_bytes = nc * in_img; P.out_bytes = nc * out_img; P.m = nc * P.ho * P.wo;
+                const int n_frags = dd_ceil_div(P.m, 16);
+                const dim3 grid0(dd_ceil_div(n_frags, 4 * C0F));
 #define DD_Q0(H_) do { if (sat0 == 2) hipLaunchKernelGGL((q_conv0_k<H_, 2>), grid0, dim3(256), 0, s, P, n_frags); \
                        else if (sat0 == 1) hipLaunchKernelGGL((q_conv0_k<H_, 1>), grid0, dim3(256), 0, s, P, n_frags); \
                        else hipLaunchKernelGGL((q_conv0_k<H_, 0>), grid0, dim3(256), 0, s, P, n_frags); } while (0)
-            if (P.w2) DD_Q0(true); else DD_Q0(false);
+                if (P.w2) DD_Q0(true); else DD_Q0(false);
 #undef DD_Q0
-            DD_LAUNCH_CHECK();
+                DD_LAUNCH_CHECK();
+            }
             return DD_OK;
         }
         case OP_QCONV: {
@@ -1570,20 +1586,29 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
             DD_REQUIRE(P.total < (1ll << 31) * 256, DD_E_CAPACITY, "dd_net_forward: uint8 depthwise %d: too many items", i);
             static const bool no_mfma = getenv("DD_Q_DW_VALU") && atoi(getenv("DD_Q_DW_VALU")) != 0;       // A/B switch: the vector-ALU form
             if (o[20] && P.R.e >= 1 && !no_mfma) {                  // o[20], o[21]: the block-diagonal operand table and its constants (netsq.pack_dw_mfma)
-                QDwmP Q;
-                Q.in = P.in; Q.H = P.H; Q.W = P.W; Q.c16 = P.c16; Q.stride = P.stride; Q.off_y = P.off_y; Q.off_x = P.off_x; Q.ho = P.ho; Q.wo = P.wo;
-                Q.m = nimg * P.ho * P.wo; Q.out = P.out; Q.R = P.R;
-                Q.dw_a = reinterpret_cast<const uint2 *>(W + (size_t)(uint32_t)o[20]);
-                Q.dw_cb = reinterpret_cast<const int *>(W + (size_t)(uint32_t)o[21]);
-                const long long n_items = (long long)P.c16 * dd_ceil_div(Q.m, 64);
-                DD_REQUIRE(n_items < (1ll << 31), DD_E_CAPACITY, "dd_net_forward: uint8 depthwise %d: %lld wave items", i, n_items);
-                Q.hw_magic = (unsigned)((1ull << 32) / (unsigned)(P.ho * P.wo)) + 1u; Q.wo_magic = (unsigned)((1ull << 32) / (unsigned)P.wo) + 1u; Q.c16_magic = (unsigned)((1ull << 32) / (unsigned)P.c16) + 1u;
-                if ((long long)Q.m * (P.ho * P.wo) >= (1ll << 32) || P.wo < 2 || P.c16 < 2) Q.hw_magic = 0;       // (a divisor of 1 has no 32-bit magic)
-                DD_REQUIRE(n_items * P.c16 < (1ll << 32) && (long long)(nimg + 1) * (P.H + 2) * P.c16 * (P.W + 2) * 16 < (1ll << 32) &&
-                           (long long)(nimg + 1) * (P.ho + 2) * P.c16 * (P.wo + 2) * 16 < (1ll << 32), DD_E_CAPACITY, "dd_net_forward: uint8 depthwise %d: beyond 32-bit offsets", i);
-                if (P.R.lo == 0 && P.R.hi == 255) hipLaunchKernelGGL((q_dwm_k<true>), dim3((unsigned)((n_items + 3) / 4)), dim3(256), 0, s, Q, (int)n_items);
-                else hipLaunchKernelGGL((q_dwm_k<false>), dim3((unsigned)((n_items + 3) / 4)), dim3(256), 0, s, Q, (int)n_items);
-                DD_LAUNCH_CHECK();
+                // q_dwm_k's offsets are 32-bit ((n + 1) frames of source and of output; block 2's depthwise reads 1 478 656 bytes a frame:
+                // 2 903 frames).  A bigger batch runs as launches over chunks of frames on other base pointers (the frames are independent).
+                const long long in_img = (long long)(P.H + 2) * P.c16 * (P.W + 2) * 16, out_img = (long long)(P.ho + 2) * P.c16 * (P.wo + 2) * 16;
+                auto items = [&](long long nc) { return (long long)P.c16 * ((nc * P.ho * P.wo + 63) / 64); };
+                auto fits = [&](long long nc) { return items(nc) < (1ll << 31) && items(nc) * P.c16 < (1ll << 32) && (nc + 1) * in_img < (1ll << 32) && (nc + 1) * out_img < (1ll << 32); };
+                DD_REQUIRE(fits(1), DD_E_CAPACITY, "dd_net_forward: uint8 depthwise %d: one frame beyond 32-bit offsets", i);
+                long long n_chunks = 1;
+                while (!fits((nimg + n_chunks - 1) / n_chunks)) ++n_chunks;
+                const long long chunk = (nimg + n_chunks - 1) / n_chunks;
+                for (long long c0 = 0; c0 < nimg; c0 += chunk) {
+                    const int nc = (int)std::min(chunk, nimg - c0);
+                    QDwmP Q;
+                    Q.in = P.in + c0 * in_img; Q.H = P.H; Q.W = P.W; Q.c16 = P.c16; Q.stride = P.stride; Q.off_y = P.off_y; Q.off_x = P.off_x; Q.ho = P.ho; Q.wo = P.wo;
+                    Q.m = nc * P.ho * P.wo; Q.out = P.out + c0 * out_img; Q.R = P.R;
+                    Q.dw_a = reinterpret_cast<const uint2 *>(W + (size_t)(uint32_t)o[20]);
+                    Q.dw_cb = reinterpret_cast<const int *>(W + (size_t)(uint32_t)o[21]);
+                    const long long n_items = items(nc);
+                    Q.hw_magic = (unsigned)((1ull << 32) / (unsigned)(P.ho * P.wo)) + 1u; Q.wo_magic = (unsigned)((1ull << 32) / (unsigned)P.wo) + 1u; Q.c16_magic = (unsigned)((1ull << 32) / (unsigned)P.c16) + 1u;
+                    if ((long long)Q.m * (P.ho * P.wo) >= (1ll << 32) || P.wo < 2 || P.c16 < 2) Q.hw_magic = 0;       // (a divisor of 1 has no 32-bit magic)
+                    if (P.R.lo == 0 && P.R.hi == 255) hipLaunchKernelGGL((q_dwm_k<true>), dim3((unsigned)((n_items + 3) / 4)), dim3(256), 0, s, Q, (int)n_items);
+                    else hipLaunchKernelGGL((q_dwm_k<false>), dim3((unsigned)((n_items + 3) / 4)), dim3(256), 0, s, Q, (int)n_items);
+                    DD_LAUNCH_CHECK();
+                }
                 if (i < (int)net->op_launch.size()) net->op_launch[i] = 17;      // dd_net_op_launches: q_dwm_k ran (a layer table prints the kernel that ran, not the op's default)
                 return DD_OK;
             }
@@ -1612,22 +1637,31 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
             DD_REQUIRE(cin == ts->cs && cout == td->cs && P.Rd.e >= 1 && P.Rp.e >= 1 && !P.Rd.linear && !P.Rp.linear && P.off_y >= 0 && P.off_x >= 0 &&
                        (P.ho - 1) * stride + 2 + P.off_y <= P.H + 1 && (P.wo - 1) * stride + 2 + P.off_x <= P.W + 1, DD_E_ARG,
                        "dd_net_forward: uint8 block %d: shapes / multipliers the fused kernel does not take", i);
-            DD_REQUIRE((double)nimg * (P.ho + 2) * (P.wo + 2) * td->cs < 4294967296.0, DD_E_CAPACITY, "dd_net_forward: uint8 block %d: output beyond 32-bit offsets", i);
-            bool ok = false;
-            int rc = DD_OK;
+            // The kernel's output offsets are 32-bit (block 1: 2 904 frames of 152 x 152 x 64 bordered bytes).  A bigger batch runs as launches
+            // over chunks of frames on other base pointers (the frames are independent; the source offsets are 64-bit anyway).
+            const long long in_img = (long long)(P.H + 2) * (P.W + 2) * ts->cs, out_img = (long long)(P.ho + 2) * (P.wo + 2) * td->cs;
+            const long long lim = 4294967295ll / out_img, n_chunks = (nimg + lim - 1) / lim, chunk = (nimg + n_chunks - 1) / n_chunks;
+            DD_REQUIRE(lim >= 1, DD_E_CAPACITY, "dd_net_forward: uint8 block %d: one frame's output beyond 32-bit offsets", i);
             const int dev = net->ctx->device;
-#define DD_QB(CIN_, COUT_, WP_, S_, LPT_) launch_q_dwpw<CIN_, COUT_, WP_, S_, LPT_>(s, P, nimg, dev, &ok)
             static const int qt128 = getenv("DD_Q_QT128") ? atoi(getenv("DD_Q_QT128")) : 1;   // block 1: 128-pixel tiles, four waves (0: 64-pixel tiles, two waves)
-            if (cin == 32 && cout == 64 && stride == 1) rc = qt128 ? launch_q_dwpw<32, 64, 4, 1, 6, 0, 4, 128>(s, P, nimg, dev, &ok) : DD_QB(32, 64, 2, 1, 8);
-            else if (cin == 64 && cout == 128 && stride == 2) rc = DD_QB(64, 128, 2, 2, 8);
-            else if (cin == 128 && cout == 128 && stride == 1) rc = DD_QB(128, 128, 2, 1, 8);
-            else if (cin == 128 && cout == 256 && stride == 2) rc = DD_QB(128, 256, 2, 2, 8);
-            else if (cin == 256 && cout == 256 && stride == 1) rc = DD_QB(256, 256, 2, 1, 6);
-            else if (cin == 256 && cout == 512 && stride == 2) rc = DD_QB(256, 512, 1, 2, 12);
-            else if (cin == 512 && cout == 512 && stride == 1) rc = DD_QB(512, 512, 1, 1, 8);
+            for (long long c0 = 0; c0 < nimg; c0 += chunk) {
+                const int nc = (int)std::min(chunk, nimg - c0);
+                QDwpwP Q = P;
+                Q.in = P.in + c0 * in_img; Q.out = P.out + c0 * out_img;
+                bool ok = false;
+                int rc = DD_OK;
+#define DD_QB(CIN_, COUT_, WP_, S_, LPT_) launch_q_dwpw<CIN_, COUT_, WP_, S_, LPT_>(s, Q, nc, dev, &ok)
+                if (cin == 32 && cout == 64 && stride == 1) rc = qt128 ? launch_q_dwpw<32, 64, 4, 1, 6, 0, 4, 128>(s, Q, nc, dev, &ok) : DD_QB(32, 64, 2, 1, 8);
+                else if (cin == 64 && cout == 128 && stride == 2) rc = DD_QB(64, 128, 2, 2, 8);
+                else if (cin == 128 && cout == 128 && stride == 1) rc = DD_QB(128, 128, 2, 1, 8);
+                else if (cin == 128 && cout == 256 && stride == 2) rc = DD_QB(128, 256, 2, 2, 8);
+                else if (cin == 256 && cout == 256 && stride == 1) rc = DD_QB(256, 256, 2, 1, 6);
+                else if (cin == 256 && cout == 512 && stride == 2) rc = DD_QB(256, 512, 1, 2, 12);
+                else if (cin == 512 && cout == 512 && stride == 1) rc = DD_QB(512, 512, 1, 1, 8);
 #undef DD_QB
-            if (rc != DD_OK) return rc;
-            DD_REQUIRE(ok, DD_E_ARG, "dd_net_forward: uint8 block %d (%d -> %d, stride %d, %d x %d): no fused kernel for this shape -- compile the program with the two-op form", i, cin, cout, stride, P.H, P.W);
+                if (rc != DD_OK) return rc;
+                DD_REQUIRE(ok, DD_E_ARG, "dd_net_forward: uint8 block %d (%d -> %d, stride %d, %d x %d): no fused kernel for this shape -- compile the program with the two-op form", i, cin, cout, stride, P.H, P.W);
+            }
             return DD_OK;
         }
         case OP_QSSD_DECODE: {

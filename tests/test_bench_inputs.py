@@ -44,3 +44,16 @@ def test_streams_land_in_their_groups_slots(monkeypatch):
         want, per = _scene(s, F, W, H)
         assert dets[s] == per
         np.testing.assert_array_equal(dev[g][:, s - bounds[g]].numpy(), want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('W,H,n_frames,seeds', [(640, 480, 6, (0, 1000, 3071)), (640, 640, 4, (5,)), (1280, 720, 3, (0, 2))])
+def test_rendered_frames_on_the_device_are_scene_frames(W, H, n_frames, seeds):
+    """bench.py paints on 'cuda' (render_frames' float64 background stretch and the pasted rectangles on the GPU): the same
+    bytes as synth.Scene.frame, as the CPU-backend test above holds for torch's CPU kernels."""
+    out = [bench._scene_spec((s, n_frames, W, H)) for s in seeds]
+    frames = bench.render_frames([o[0] for o in out], W, H, 'cuda').cpu().numpy()
+    for c, s in enumerate(seeds):
+        want, per = _scene(s, n_frames, W, H)
+        assert out[c][1] == per
+        np.testing.assert_array_equal(frames[:, c], want, err_msg='%dx%d seed %d' % (W, H, s))

@@ -202,3 +202,35 @@ def test_stage_gpu_ms_and_detections_getter():
     mp.step(torch.stack([fr, fr]))                                      # no injection: the detector's own rows, the same for both slots
     a, b = mp.detections(0), mp.detections(1)
     assert a[1] == b[1] and np.array_equal(a[0], b[0]) and np.array_equal(a[2], b[2])
+
+
+def test_batched_uint8_pipeline_at_1536_streams_with_64_detections(plugin):
+    """No injection, the headline's worker group: 1 536 streams through the uint8 detector (row pipelines, ssd_finish_k over 1 536
+    frames, nms_batched_small over 1 536 problems) with the post-process op's max_detections at its bound of 64
+    (MAX_DET_CAP, csrc/pipeline.hip:53): up to 1 536 x 64 = 98 304 boxes may reach one crop launch, whose box index is gridDim.y
+    (65 535 and beyond: test_gpu_image.py runs such a launch).  Streams 0, 1, 768 and 1 535, two frames: mp.detections(z) against this
+    file's oracle chain with max_det=64 (the plugin cannot be given the option)."""
+    from deepdish_amd._lib import lib, check
+    from deepdish_amd.multipipe import MultiStreamPipeline
+    from deepdish_amd.synth import Scene
+    det, _ = plugin
+    qm = det.ssdm.weights
+    wanted = sorted({l for l in _labels().values() if l and l != '???'})
+    S, F = 1536, 2
+    scenes = [Scene(seed=z, n_obj=20, n_frames=F) for z in range(S)]
+    mp = MultiStreamPipeline(S, model=MODEL, wanted_labels=wanted)
+    assert mp.det_dtype == 'u8'
+    check(lib().dd_pipeline_ssd_options(mp._h, 64, 1e-8, 0.6), 'dd_pipeline_ssd_options')
+    n_rows = 0
+    for f in range(F):
+        frames = np.stack([sc.frame(f) for sc in scenes])
+        mp.step(torch.from_numpy(frames).cuda())
+        for z in (0, 1, S // 2, S - 1):
+            want = _oracle_detect(qm, frames[z], wanted, max_det=64)
+            assert want[3][3] > 10, want[3][3]                             # the op kept more rows than the stock 10
+            _same_detections(mp.detections(z), want[:3], 'frame %d stream %d' % (f, z))
+            n_rows += len(want[1])
+    from deepdish_amd.profile import net_op_launches, OPK_NAMES
+    ran = {OPK_NAMES.get(int(c)) for c in net_op_launches(mp.det)}
+    assert {'q_front_k', 'q_mid_k'} <= ran, ran
+    assert n_rows > 0

@@ -117,3 +117,43 @@ def test_lanczos_batch_one_launch_vs_pillow(ctx):
             rgba = np.dstack([frames[i][..., ::-1], np.full((H, W, 1), 255, np.uint8)])
             want = np.asarray(Image.fromarray(rgba, 'RGBA').convert('RGB').resize((w, h), Image.LANCZOS))
             np.testing.assert_array_equal(got[i], want, err_msg=f'{H}x{W}->{h}x{w} frame {i}')
+
+
+def test_crop_resize_of_a_bench_sized_launch_vs_oracle(ctx):
+    """98 304 boxes in one dd_crop_resize launch (the pipeline's bound at 1 536 streams: dd_pipeline_ssd_options takes max_detections up to
+    64, 1 536 x 64 = 98 304).  crop_resize4_k / crop_resize_k put the box index in gridDim.y, so boxes 65 535 / 65 536 straddle the
+    16-bit grid row count and box n-1 is far above it; the output (6 144 bytes a crop, 604 MB) stays below 2^31 bytes.  Boxes: the
+    synthetic scenes' detections (bench.N_OBJ objects a frame, bilinear path), exact 2x boxes (64 x 128: the decimation path) and the
+    edge boxes of test_crop_resize_vs_oracle, repeated.  Against oracle/image_np.extract_image_patch: a fixed stratified sample of 8 192
+    crops (one from every run of 12), the last 1 000, and boxes 65 530 .. 65 545."""
+    import bench
+    from deepdish_amd.synth import Scene
+    from deepdish_amd.tools.generate_detections import crop_patches_device
+    from oracle import image_np
+    n = 98304
+    sc = Scene(seed=7, n_obj=bench.N_OBJ, n_frames=40)
+    img = sc.frame(0)
+    scene_boxes = np.concatenate([sc.detections(f)[0] for f in range(40)]).astype(np.int64)
+    rng = np.random.default_rng(98304)
+    x2 = np.c_[rng.integers(0, 576, 64), rng.integers(0, 352, 64), np.full(64, 64), np.full(64, 128)]
+    extra = np.array([[100, 50, 41, 90], [100, 50, 40, 91], [10, 10, 64, 128], [0, 0, 640, 480], [639, 479, 5, 5],
+                      [700, 10, 20, 40], [-50, -50, 20, 40], [5, 5, 1, 2], [300, 200, 16, 32]])
+    pool = np.concatenate([scene_boxes, x2, extra]).astype(np.int64)
+    boxes = pool[np.arange(n) % len(pool)]
+    boxes[65530:65546] = pool[len(scene_boxes):len(scene_boxes) + 16]      # 2x boxes across gridDim.y = 65 536
+    boxes[n - len(extra):] = extra
+    out, valid = crop_patches_device(ctx, ctx.to_device(img), 480, 640, boxes, 64, 32)
+    out = ctx.to_host(out)
+    picks = sorted(set(range(0, n, 12)) | set(range(n - 1000, n)) | set(range(65530, 65546)))
+    assert len(picks) >= 9000
+    n_valid = n_x2 = 0
+    for i in picks:
+        want = image_np.extract_image_patch(img, boxes[i], (64, 32))
+        assert bool(valid[i]) == (want is not None), (i, boxes[i])
+        if want is None:
+            assert not out[i].any(), i
+            continue
+        n_valid += 1
+        n_x2 += int(boxes[i][2] == 64 and boxes[i][3] == 128)
+        np.testing.assert_array_equal(out[i], want, err_msg='box %d %s' % (i, boxes[i]))
+    assert n_valid > 0.9 * len(picks) and n_x2 > 20 and not valid[n - 4]           # (n - 4: [700, 10, 20, 40], outside the frame)

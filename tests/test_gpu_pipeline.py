@@ -624,3 +624,54 @@ def test_bench_two_ranks_on_two_gpus():
     if torch.cuda.device_count() < 2:
         pytest.skip('needs 2 GPUs')
     _bench_two_ranks({})
+
+
+@pytest.mark.parametrize('S', [1536, 3072])
+def test_multistream_pipeline_at_bench_scale_matches_oracle_per_stream(S):
+    """The batched pipeline at the bench's shapes: S = 1 536 streams (one worker group of the headline; encoder engine 32 x S = 49 152
+    crops) and 3 072 (--groups 1; 98 304), bench.N_OBJ objects a scene, injected detections, 5 frames.  The step's frame buffer is
+    921 600 bytes a stream, so the crops of streams from 2 331 on read above byte 2^31 (stream 2 330 straddles it); the encoder's
+    launch holds ~20 x S crops, and NMS runs over S problems at once.  Streams 0, 1, S/2, 2 330, 2 331, S-1: track tables and counts
+    of test_multistream_pipeline_matches_oracle_per_stream's oracle chain."""
+    import bench
+    from deepdish_amd.multipipe import MultiStreamPipeline
+    from deepdish_amd.synth import Scene
+    from oracle import deepsort_np as ds, countline_np as cl, image_np, nets_torch
+    F = 5
+    scenes = [Scene(seed=z, n_obj=bench.N_OBJ, n_frames=F) for z in range(S)]
+    picks = sorted({z for z in (0, 1, S // 2, 2330, 2331, S - 1) if z < S})
+    mp = MultiStreamPipeline(S, run_detector=False)
+    assert mp.enc.max_batch == 32 * S
+    otrk = {z: ds.Tracker(ds.Metric(0.2), max_iou_distance=0.7, max_age=60) for z in picks}
+    ocnt = {z: cl.CountLine(scenes[z].countline()) for z in picks}
+    n_crops = seen = 0
+    for f in range(F):
+        frames = torch.from_numpy(np.stack([sc.frame(f) for sc in scenes])).cuda()
+        per = []
+        for z, sc in enumerate(scenes):
+            boxes, scores, _, _ = sc.detections(f)
+            per.append(([tuple(int(v) for v in b) for b in boxes], ['person'] * len(boxes), [float(s) for s in scores]))
+            n_crops += len(boxes)
+            if z in otrk:
+                frame = frames[z].cpu().numpy()
+                keep = ds.non_max_suppression(boxes, 0.6, scores)
+                patches = np.stack([image_np.extract_image_patch(frame, boxes[i], (64, 32)) for i in keep])
+                feats = nets_torch.mars_forward(mp.enc_weights, patches)
+                otrk[z].predict()
+                otrk[z].update([ds.Det(boxes[i], 'person', scores[i], feats[j]) for j, i in enumerate(keep)])
+                ocnt[z].step(otrk[z])
+        mp.step(frames, mp.pack_injected(per))
+        del frames
+        for z in picks:
+            ints, means = mp.tracker(z).table()
+            want = np.array([[t.track_id, t.state, t.time_since_update, t.hits, t.age] for t in otrk[z].tracks],
+                            dtype=np.int64).reshape(-1, 5)
+            np.testing.assert_array_equal(ints[:, :5], want, err_msg=f'frame {f} stream {z}')
+            if len(want):
+                seen += 1
+                np.testing.assert_allclose(means, np.array([t.mean for t in otrk[z].tracks]), rtol=1e-6, atol=1e-6)
+    got = mp.counts()
+    for z in picks:
+        np.testing.assert_array_equal(got[z], ocnt[z].vector())
+    assert mp.stage_ms()['steps'] == F
+    assert n_crops > 15 * S * F and seen >= 3 * len(picks)             # ~bench.N_OBJ crops a stream and frame went through one launch

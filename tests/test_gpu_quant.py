@@ -211,12 +211,14 @@ def test_decoded_arrays(qnet):
         net.ssd_decode(None, 0.0, enable=False)
 
 
-@pytest.mark.parametrize('n_frames, symmetric', [(1536, False), (768, False), (384, False), (91, False), (91, True), (23, False)])
+@pytest.mark.parametrize('n_frames, symmetric', [(1536, False), (768, False), (384, False), (91, False), (91, True), (23, False), (3072, False), (1533, False)])
 def test_launch_of_many_frames_is_bit_exact(n_frames, symmetric):
     """The bench's launch shape (one worker group = 1 536 frames per forward since round 6, 768 in round 5, 384 before) and odd ones: picked slots against the integer oracle, every
     other slot against the slot that holds the same frame (persistent blocks, tiles that straddle frames, the last tile of a frame).
     91 frames: the register-filter pointwise kernel (from 8 192 pixels per launch) with a partly filled last tile on every map it takes,
-    merged predictors included; 23 frames: the same layers on the generic kernel, the 19x19 predictors still merged (8 303 pixels)."""
+    merged predictors included; 23 frames: the same layers on the generic kernel, the 19x19 predictors still merged (8 303 pixels).
+    3 072 frames: the bench with --groups 1 (the row pipelines' source is 829 MB, block 1's bordered output would be 4.5 GB); 1 533: an
+    odd count at the headline's size (rows and tiles of the last frames split unevenly over the persistent blocks)."""
     from deepdish_amd import quantize, netsq
     from deepdish_amd.engine import Net
     from oracle import nets_quant
@@ -234,6 +236,36 @@ def test_launch_of_many_frames_is_bit_exact(n_frames, symmetric):
     box_w, cls_w, _ = nets_quant.ssd_quant_forward(qm, base)
     for z in range(n_frames):
         assert (box[z] == box_w[idx[z]]).all() and (cls[z] == cls_w[idx[z]]).all(), 'slot %d (frame %d)' % (z, idx[z])
+
+
+def test_three_launch_front_end_beyond_2904_frames(monkeypatch):
+    """The front end as three launches (DD_Q_FRONT=0, and wherever q_front_k declines: a linear requantisation, a shift below 1, a
+    misaligned batch) at the bench's --groups 1 shape.  q_conv0_k addresses its source and its bordered output as 31-bit buffer ranges
+    (csrc/netsq.hip, OP_QCONV0: 152 x 2 x 152 x 16 = 739 328 output bytes a frame, 2^31 - 17 bytes hold 2 904 frames), q_dwpw_k
+    writes block 1 with 32-bit offsets (OP_QDWPW: 152 x 152 x 64 = 1 478 656 bytes a frame, 2^32 - 1 bytes hold 2 904 frames).  Both
+    used to refuse such a batch (DD_E_ARG / DD_E_CAPACITY); they now run over chunks of frames -- 2 x 1 536 here, so slots 1 535 / 1 536
+    and 2 903 / 2 904 / 2 905 straddle a chunk boundary and the old limit.  Every slot against the integer oracle.  DD_Q_FRONT is read on
+    every forward: one engine, the row pipeline first, then the three launches."""
+    from deepdish_amd import quantize, netsq
+    from deepdish_amd.engine import Net
+    from deepdish_amd.profile import net_op_launches
+    from oracle import nets_quant
+    n = 3072
+    qm = quantize.synthetic_ssd_quant_model(1234)
+    prog = netsq.compile_ssd_mobilenet_quant(qm)
+    net = Net(prog, max_batch=n)
+    base = _frames(4, 21)
+    idx = np.arange(n) % 4
+    idx[[0, 1, 1535, 1536, 2903, 2904, 2905, n - 1]] = [3, 2, 1, 0, 3, 2, 1, 0]
+    box_w, cls_w, _ = nets_quant.ssd_quant_forward(qm, base)
+    for front, launches in (('1', [1, 1, 19, 1, 20]), ('0', [0, 0, 0, 1, 20])):
+        monkeypatch.setenv('DD_Q_FRONT', front)
+        net.forward(base[idx])
+        assert list(net_op_launches(net)[:5]) == launches, (front, net_op_launches(net)[:5])
+        box = net.read(tensor=prog.meta['box_tensor'])[:, :, 0, :]
+        cls = net.read(tensor=prog.meta['cls_tensor'])[:, :, 0, :prog.meta['n_classes']]
+        for z in range(n):
+            assert (box[z] == box_w[idx[z]]).all() and (cls[z] == cls_w[idx[z]]).all(), 'DD_Q_FRONT=%s slot %d (frame %d)' % (front, z, idx[z])
 
 
 @pytest.mark.parametrize('zero_point_of', ['box', 'cls'])
