@@ -59,6 +59,8 @@ struct QConvP {
     int n_frag_a, groups_a;                       // 0: one layer
     uint8_t *out_b; long long img_bytes_b; int row_bytes_b, base_off_b, cout_store_b, zwc_b;
     QReq Rb;
+    // QEPI_Q16N with a residual operand (MobileNet-v2 blocks): the projection's bytes ADDed to the block input's at the same pixel and channel
+    const uint8_t *res; QAdd A;                   // res: Q16 of the output's geometry, or null
 };
 
 // One wave item = MQ 16-channel fragments x NPF (2 or 4) 16-pixel fragments; operands straight from L2 / HBM in fragment shape (Q16 is
@@ -66,7 +68,8 @@ struct QConvP {
 // SPLIT = 3 (3x3 layers with few wave items: the SSD extras): the block is ONE item, wave w sums the k steps of filter row w, the partial
 // accumulators meet in LDS and wave 0 runs the epilogue -- three times the waves to cover the L2 round trips of a 36-step chain
 // (the 10x10 -> 5x5 extra layer has 1 200 items for 1 024 SIMDs).  Integer sums: the same bits in any order.
-template <int MQ, bool ROWSUM, int NPF, bool PIPE, int SPLIT = 1>
+// Q16N (MobileNet-v2: any multiple of 16 output channels, linear projections, the residual ADD): the epilogue of QEPI_Q16N, MQ < 4.
+template <int MQ, bool ROWSUM, int NPF, bool PIPE, int SPLIT = 1, bool Q16N = false>
 __global__ __launch_bounds__(256) void q_conv_k(const QConvP P, const int n_items, const int n_mgroups) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int fr = lane & 15, fq = lane >> 4;
@@ -196,7 +199,38 @@ __global__ __launch_bounds__(256) void q_conv_k(const QConvP P, const int n_item
             rs[j] *= is_b ? P.zwc_b : P.zwc;
         }
     }
-    if (P.epi == QEPI_Q16) {
+    if constexpr (Q16N) {
+        // filter rows in natural order, MQ < 4 fragments per group: fragment m is plane frag0 + m, this lane holds its channels 4 fq .. 4 fq + 3 --
+        // four bytes per pixel.  Any multiple of 16 channels; the requantisation with or without activation (q_requant: the literal two-step form
+        // for a linear projection), clamped to the layer's range as TFLite materialises the tensor.  With a residual operand, that byte and the
+        // residual's are the two inputs of TFLite's uint8 ADD, and only the sum is stored.
+        static_assert(MQ < 4, "Q16N: one to three planes per wave item");
+        const size_t PPo = (size_t)(P.Wo + 2) * 16;
+#pragma unroll
+        for (int m = 0; m < MQ; ++m) {
+            const int plane = frag0 + m;
+            if (plane >= frag_end) continue;
+            const i4v c = *reinterpret_cast<const i4v *>(P.cbias + 16 * plane + 4 * fq);
+#pragma unroll
+            for (int j = 0; j < NPF; ++j) {
+                int z[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) z[r] = q_requant(acc[m][j][r] + rs[j] + c[r], P.R);
+                if (live[j]) {
+                    const size_t off = (((size_t)qn[j] * (P.Ho + 2) + qy[j] + 1) * P.c16_out + plane) * PPo + (size_t)(qx[j] + 1) * 16 + 4 * fq;
+                    if (P.res) {
+                        const unsigned rv = *reinterpret_cast<const unsigned *>(P.res + off) ^ 0x80808080u;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) z[r] = q_add_u8(z[r], (int)((rv >> (8 * r)) & 0xffu), P.A);
+                    }
+                    unsigned wv = 0;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) wv |= (unsigned)z[r] << (8 * r);
+                    *reinterpret_cast<unsigned *>(P.out + off) = wv ^ 0x80808080u;
+                }
+            }
+        }
+    } else if (P.epi == QEPI_Q16) {
         // the host packed fragment m's row 4g + r with channel 64 mg + 16 g + 4 m + r: this lane holds the 16 consecutive channels of plane 4 mg + fq
         if constexpr (MQ == 4) {
             const i4v *cb = reinterpret_cast<const i4v *>(P.cbias + 64 * mg + 16 * fq);
@@ -1412,13 +1446,42 @@ int launch_q_pws(hipStream_t s, QPwsP &P, int nimg, int device, bool *ok) {
     return DD_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ residual ADD
+// TFLite's uint8 ADD of two Q16 tensors of one geometry (the unfused form of a MobileNet-v2 block's residual, and the cross-check of the fused
+// one): one lane per 16 bytes of a pixel's plane, interior only (the borders keep the output's zero point).  Item = ((n H + y) c16 + p) W + x,
+// below 2^31 per launch (the host runs bigger batches as chunks of frames); byte offsets are 64-bit.
+struct QAddP {
+    const uint8_t *a, *b; uint8_t *out;
+    int H, W, c16, n_items;
+    QAdd A;
+};
+
+__global__ __launch_bounds__(256) void q_add_k(const QAddP P) {
+    const int it = blockIdx.x * 256 + threadIdx.x;
+    if (it >= P.n_items) return;
+    const unsigned u = (unsigned)it, w = (unsigned)P.W, c = (unsigned)P.c16, h = (unsigned)P.H;
+    const unsigned x = u % w, q1 = u / w, p = q1 % c, q2 = q1 / c, y = q2 % h, n = q2 / h;
+    const size_t off = (((size_t)n * (P.H + 2) + y + 1) * P.c16 + p) * (size_t)(P.W + 2) * 16 + (size_t)(x + 1) * 16;
+    const u4v a = *reinterpret_cast<const u4v *>(P.a + off), b = *reinterpret_cast<const u4v *>(P.b + off);
+    u4v o;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        const unsigned av = a[d] ^ 0x80808080u, bv = b[d] ^ 0x80808080u;      // stored as a - 128
+        unsigned wv = 0;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) wv |= (unsigned)q_add_u8((int)((av >> (8 * r)) & 0xffu), (int)((bv >> (8 * r)) & 0xffu), P.A) << (8 * r);
+        o[d] = wv ^ 0x80808080u;
+    }
+    *reinterpret_cast<u4v *>(P.out + off) = o;
+}
+
 }  // namespace
 
 int netq_prepare(dd_net *) { return DD_OK; }
 
 int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int nimg, hipStream_t s, int *handled) {
     const int kind = o[0], src = o[1], dst = o[2];
-    *handled = kind >= OP_QCONV0 && kind <= OP_QSSD_DECODE;
+    *handled = kind >= OP_QCONV0 && kind <= OP_QADD;
     if (!*handled) return DD_OK;
     auto base = [&](int t) -> uint8_t * { return static_cast<uint8_t *>(net->bufs[net->tensors[t].buf]); };
     const TensorDesc *ts = src >= 0 ? &net->tensors[src] : nullptr;
@@ -1486,10 +1549,26 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
             }
             DD_REQUIRE(P.off_y >= 0 && P.off_x >= 0 && (P.ho - 1) * P.stride + P.kh - 1 + P.off_y <= P.H + 1 && (P.wo - 1) * P.stride + P.kw - 1 + P.off_x <= P.W + 1,
                        DD_E_ARG, "dd_net_forward: uint8 conv %d reaches outside the one-pixel border", i);
+            DD_REQUIRE(o[3] < 0 || P.epi == QEPI_Q16N, DD_E_ARG, "dd_net_forward: uint8 conv %d: a residual operand needs the natural bordered epilogue", i);
             if (P.epi == QEPI_Q16) {
                 DD_REQUIRE(td->pad == 1 && td->h == P.ho && td->w == P.wo && o[12] % 64 == 0 && td->cs == o[12] && !P.R.linear, DD_E_ARG,
                            "dd_net_forward: uint8 conv %d: bordered output needs a multiple of 64 channels and an activation", i);
                 P.Ho = td->h; P.Wo = td->w; P.c16_out = td->cs / 16; P.mq = 4;
+            } else if (P.epi == QEPI_Q16N) {
+                // any multiple of 16 channels, with or without activation: one to three planes per wave item (natural filter order)
+                DD_REQUIRE(td->pad == 1 && td->h == P.ho && td->w == P.wo && o[12] % 16 == 0 && td->cs == o[12] && n_frag_a == 0 && (P.R.linear || P.R.lo >= P.R.zo) &&
+                           P.R.e >= 0 && P.R.e <= 30 && P.R.lo >= 0 && P.R.lo <= P.R.hi && P.R.hi <= 255, DD_E_ARG,
+                           "dd_net_forward: uint8 conv %d: natural bordered output geometry / requantisation", i);
+                P.Ho = td->h; P.Wo = td->w; P.c16_out = td->cs / 16;
+                P.mq = P.n_mfrag % 3 == 0 ? 3 : P.n_mfrag % 2 == 0 ? 2 : std::min(3, P.n_mfrag);
+                if (o[3] >= 0) {
+                    DD_REQUIRE(o[3] < (int)net->tensors.size(), DD_E_ARG, "dd_net_forward: uint8 conv %d: residual tensor %d out of range", i, o[3]);
+                    const TensorDesc *tr = &net->tensors[o[3]];
+                    P.res = base(o[3]); P.A = make_add(o);
+                    DD_REQUIRE(tr->pad == 1 && tr->h == td->h && tr->w == td->w && tr->cs == td->cs && o[3] != dst && add_ok(P.A) && P.R.lo == 0 && P.R.hi == 255, DD_E_ARG,
+                               "dd_net_forward: uint8 conv %d: residual operand geometry / ADD parameters", i);
+                    if (i < (int)net->op_launch.size()) net->op_launch[i] = 21;      // dd_net_op_launches: q_conv_k with the residual ADD in its epilogue
+                }
             } else {
                 P.img_bytes_out = (long long)td->h * td->w * td->cs; P.row_bytes = o[42]; P.base_off = o[43]; P.cout_store = o[44];
                 DD_REQUIRE(!td->pad && P.row_bytes % 4 == 0 && P.base_off % 4 == 0 && P.cout_store % 4 == 0 && P.cout_store <= P.row_bytes &&
@@ -1498,7 +1577,7 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
             }
             // 1x1 stride-1 layers with 512 / 1024 input channels and pixels enough: the filter in registers, the pixels through LDS (q_pws_k)
             static const int pws_env = getenv("DD_Q_PWS") ? atoi(getenv("DD_Q_PWS")) : 1;
-            if (pws_env && P.kh == 1 && P.kw == 1 && P.stride == 1 && P.off_y == 1 && P.off_x == 1 && (ts->cs == 512 || ts->cs == 1024) && P.m >= 8192 && P.n_mfrag >= 8 &&
+            if (pws_env && P.epi != QEPI_Q16N && P.kh == 1 && P.kw == 1 && P.stride == 1 && P.off_y == 1 && P.off_x == 1 && (ts->cs == 512 || ts->cs == 1024) && P.m >= 8192 && P.n_mfrag >= 8 &&
                 o[46] != 0 && (P.epi == QEPI_ROWS || (!P.R.linear && P.R.e >= 1))) {
                 QPwsP Q;
                 memset(&Q, 0, sizeof(Q));
@@ -1538,13 +1617,14 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
                 static const int split_env = getenv("DD_Q_SPLITK") ? atoi(getenv("DD_Q_SPLITK")) : 1;
                 const bool split = split_env && P.kh * P.kw == 9 && n_items < 1024;       // (3x3: the k steps divide by the three filter rows; at 1 200 items the split costs: 40 -> 51 us)
                 const dim3 grid(split ? (unsigned)n_items : (unsigned)((n_items + 3) / 4)), block(split ? 192 : 256);
-#define DD_QC2(MQ_, R_) do { if (npf == 4 && split) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 4, false, 3>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
-                             else if (npf == 4) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 4, false>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
-                             else if (split) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 2, true, 3>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
-                             else if (pipe) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 2, true>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
-                             else hipLaunchKernelGGL((q_conv_k<MQ_, R_, 2, false>), grid, block, 0, s, P, (int)n_items, n_mgroups); } while (0)
-#define DD_QC(MQ_) do { if (rsum) DD_QC2(MQ_, true); else DD_QC2(MQ_, false); } while (0)
-                if (P.mq == 4) DD_QC(4); else if (P.mq == 3) DD_QC(3); else if (P.mq == 2) DD_QC(2); else DD_QC(1);
+#define DD_QC2(MQ_, R_, N_) do { if (npf == 4 && split) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 4, false, 3, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
+                                 else if (npf == 4) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 4, false, 1, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
+                                 else if (split) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 2, true, 3, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
+                                 else if (pipe) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 2, true, 1, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
+                                 else hipLaunchKernelGGL((q_conv_k<MQ_, R_, 2, false, 1, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); } while (0)
+#define DD_QC(MQ_, N_) do { if (rsum) DD_QC2(MQ_, true, N_); else DD_QC2(MQ_, false, N_); } while (0)
+                if (P.epi == QEPI_Q16N) { if (P.mq == 3) DD_QC(3, true); else if (P.mq == 2) DD_QC(2, true); else DD_QC(1, true); }
+                else if (P.mq == 4) DD_QC(4, false); else if (P.mq == 3) DD_QC(3, false); else if (P.mq == 2) DD_QC(2, false); else DD_QC(1, false);
 #undef DD_QC2
 #undef DD_QC
                 DD_LAUNCH_CHECK();
@@ -1662,6 +1742,28 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
                 if (rc != DD_OK) return rc;
                 DD_REQUIRE(ok, DD_E_ARG, "dd_net_forward: uint8 block %d (%d -> %d, stride %d, %d x %d): no fused kernel for this shape -- compile the program with the two-op form", i, cin, cout, stride, P.H, P.W);
             }
+            return DD_OK;
+        }
+        case OP_QADD: {
+            DD_REQUIRE(ts && td && o[3] >= 0 && o[3] < (int)net->tensors.size(), DD_E_ARG, "dd_net_forward: uint8 ADD %d: operands", i);
+            const TensorDesc *tb = &net->tensors[o[3]];
+            QAddP P;
+            P.A = make_add(o);
+            DD_REQUIRE(ts->pad == 1 && td->pad == 1 && tb->pad == 1 && ts->h == td->h && ts->w == td->w && ts->cs == td->cs && tb->h == td->h && tb->w == td->w &&
+                       tb->cs == td->cs && td->cs % 16 == 0 && dst != src && dst != o[3] && add_ok(P.A), DD_E_ARG, "dd_net_forward: uint8 ADD %d: tensor layouts / parameters", i);
+            P.H = td->h; P.W = td->w; P.c16 = td->cs / 16;
+            // items below 2^31 per launch: a bigger batch runs as launches over chunks of frames on other base pointers (the frames are independent)
+            const long long per_img = (long long)P.H * P.c16 * P.W, img_bytes = (long long)(P.H + 2) * (P.W + 2) * td->cs;
+            DD_REQUIRE(per_img < (1ll << 31) - 256, DD_E_CAPACITY, "dd_net_forward: uint8 ADD %d: one frame beyond 31-bit items", i);
+            const long long chunk = ((1ll << 31) - 256) / per_img;
+            for (long long c0 = 0; c0 < nimg; c0 += chunk) {
+                const long long nc = std::min(chunk, nimg - c0);
+                P.a = base(src) + c0 * img_bytes; P.b = base(o[3]) + c0 * img_bytes; P.out = base(dst) + c0 * img_bytes;
+                P.n_items = (int)(nc * per_img);
+                hipLaunchKernelGGL(q_add_k, dim3((unsigned)dd_ceil_div(P.n_items, 256)), dim3(256), 0, s, P);
+                DD_LAUNCH_CHECK();
+            }
+            if (i < (int)net->op_launch.size()) net->op_launch[i] = 22;          // dd_net_op_launches: q_add_k
             return DD_OK;
         }
         case OP_QSSD_DECODE: {

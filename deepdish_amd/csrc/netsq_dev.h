@@ -11,8 +11,8 @@ typedef unsigned u4v __attribute__((ext_vector_type(4)));
 typedef short s2v __attribute__((ext_vector_type(2)));
 typedef const __attribute__((address_space(4))) int cint;      // read-only data at a wave-uniform address: s_load
 
-enum { OP_QCONV0 = 16, OP_QCONV = 17, OP_QDW = 18, OP_QDWPW = 19, OP_QSSD_DECODE = 20 };
-enum { QEPI_Q16 = 0, QEPI_ROWS = 1 };
+enum { OP_QCONV0 = 16, OP_QCONV = 17, OP_QDW = 18, OP_QDWPW = 19, OP_QSSD_DECODE = 20, OP_QADD = 21 };
+enum { QEPI_Q16 = 0, QEPI_ROWS = 1, QEPI_Q16N = 2 };     // Q16N: bordered output, filter rows in natural channel order (netsq.py QEPI_Q16N)
 
 struct QReq {            // requantisation of one layer (per-tensor parameters)
     int M;               // quantized multiplier, [2^30, 2^31)
@@ -115,6 +115,39 @@ __device__ __forceinline__ unsigned q_requant_linear_pack4(int x0, int x1, int x
     asm("v_ashr_pk_u8_i32 %0, %1, %2, %3" : "=v"(r) : "v"(z[0]), "v"(z[1]), "v"(e));
     asm("v_ashr_pk_u8_i32 %0, %1, %2, %3 op_sel:[0,0,0,1]" : "+v"(r) : "v"(z[2]), "v"(z[3]), "v"(e));
     return r;
+}
+
+// TFLite's uint8 ADD (kernels/add.cc Prepare, kernels/internal/reference/add.h AddElementwise): left_shift 20, one multiplier per input and
+// one for the sum, each applied as MultiplyByQuantizedMultiplierSmallerThanOneExp, the output offset, the clamp.
+struct QAdd {
+    int M1, e1, M2, e2, Mo, eo;   // quantized multipliers in [2^30, 2^31) and right shifts (>= 0)
+    int z1, z2, zo, lo, hi;       // input zero points, output zero point, clamp
+};
+
+// MultiplyByQuantizedMultiplierSmallerThanOneExp: SaturatingRoundingDoublingHighMul (M > 0: never the saturating case; the truncating division
+// and its sign-dependent nudge are the floor of x M + 2^30 over 2^31), then RoundingDivideByPOT (halves away from zero).
+__device__ __forceinline__ int q_mul_lt1(int x, int M, int e) {
+    const int y = (int)(((long long)x * M + (1ll << 30)) >> 31);
+    return e > 0 ? (y + (1 << (e - 1)) + (y >> 31)) >> e : y;
+}
+
+__device__ __forceinline__ int q_add_u8(int a, int b, const QAdd &A) {      // a, b: the two input bytes (0 .. 255)
+    const int s1 = q_mul_lt1((a - A.z1) * (1 << 20), A.M1, A.e1);
+    const int s2 = q_mul_lt1((b - A.z2) * (1 << 20), A.M2, A.e2);
+    return min(max(q_mul_lt1(s1 + s2, A.Mo, A.eo) + A.zo, A.lo), A.hi);
+}
+
+inline QAdd make_add(const int32_t *o) {      // the op words of netsq.add_words
+    QAdd A;
+    A.M1 = o[20]; A.e1 = o[21]; A.M2 = o[22]; A.e2 = o[23]; A.Mo = o[24]; A.eo = o[25];
+    A.z1 = o[28]; A.z2 = o[29]; A.zo = o[31]; A.lo = o[34]; A.hi = o[35];
+    return A;
+}
+
+inline bool add_ok(const QAdd &A) {
+    auto m = [](int M, int e) { return M >= (1 << 30) && e >= 0 && e <= 31; };
+    return m(A.M1, A.e1) && m(A.M2, A.e2) && m(A.Mo, A.eo) && A.z1 >= 0 && A.z1 <= 255 && A.z2 >= 0 && A.z2 <= 255 && A.zo >= 0 && A.zo <= 255 &&
+           A.lo >= 0 && A.lo <= A.hi && A.hi <= 255;
 }
 
 __device__ __forceinline__ int sdot4(int a, int b, int c) {

@@ -13,9 +13,10 @@ import numpy as np
 from . import nets, quantize
 from .nets import Program, same_pad, DT_U8
 
-OP_QCONV0, OP_QCONV, OP_QDW, OP_QDWPW, OP_QSSD_DECODE = 16, 17, 18, 19, 20
-QEPI_Q16, QEPI_ROWS = 0, 1
+OP_QCONV0, OP_QCONV, OP_QDW, OP_QDWPW, OP_QSSD_DECODE, OP_QADD = 16, 17, 18, 19, 20, 21
+QEPI_Q16, QEPI_ROWS, QEPI_Q16N = 0, 1, 2         # Q16N: a bordered output from filters packed in natural channel order (any multiple of 16 channels)
 FUSE_BLOCKS = os.environ.get('DD_Q_FUSE', '1') != '0'      # MobileNet blocks as one launch each (q_dwpw_k); 0: depthwise and pointwise ops
+ADD_FUSE = os.environ.get('DD_Q_ADD_FUSE', '1') != '0'      # MobileNet-v2 residual ADD in the projection's epilogue; 0: an OP_QADD of its own
 SPLIT_PW = os.environ.get('DD_Q_SPLIT_PW', '1') != '0'      # pointwise filters of the blocks with <= SPLIT_PW_MAX_CIN input channels as hi + lo parts (no row sums)
 SPLIT_PW_MAX_CIN = int(os.environ.get('DD_Q_SPLIT_PW_MAX_CIN', '128'))
 SPLIT_PW_MIN_CIN = int(os.environ.get('DD_Q_SPLIT_PW_MIN_CIN', '64'))       # block 1 (32 channels) measured slower split: 308 vs 294 us
@@ -145,17 +146,20 @@ def pack_dw_mfma(L):
     return tab.reshape(c // 16, 64, 8).view(np.uint32).reshape(c // 16, 64, 2), cb.astype(np.int32)
 
 
-def _model_need(cond, what):
+def _model_need(cond, what, model='uint8 SSD-MobileNet-v1'):
     """A property of the MODEL (as opposed to an internal invariant): raised as tools.tflite_reader.UnsupportedModel, never an assert
     (python -O strips those, and a file that misses one would run with wrong arithmetic)."""
     if not cond:
         from .tools.tflite_reader import UnsupportedModel
-        raise UnsupportedModel('uint8 SSD-MobileNet-v1: %s' % what)
+        raise UnsupportedModel('%s: %s' % (model, what))
 
 
 def compile_ssd_mobilenet_quant(qm):
     """u8 RGB [n,300,300,3] -> box encodings u8 [n,1917,4] and class logits u8 [n,1917,96] (91 used per row), both in the
-    tensors' own quantisation; dd_net_ssd_decode adds the post-process op's first stage (per-anchor arrays)."""
+    tensors' own quantisation; dd_net_ssd_decode adds the post-process op's first stage (per-anchor arrays).  A v2 model
+    (kind 'ssd_mobilenet_v2_uint8') goes to compile_ssd_mobilenet_v2_quant."""
+    if qm.get('kind') == 'ssd_mobilenet_v2_uint8':
+        return compile_ssd_mobilenet_v2_quant(qm)
     size = int(qm['input']['size'])
     P = Program(size, size)
     Ls = qm['layers']
@@ -330,6 +334,177 @@ def compile_ssd_mobilenet_quant(qm):
     P.out_tensor = cls_t
     P.meta = dict(kind='ssd_mobilenet_v1_uint8', anchors=anchors, n_classes=n_cls, box_tensor=box_t, cls_tensor=cls_t, cls_row=cls_row,
                   feats=feats, quant=True)
+    return P
+
+
+def add_words(a):
+    """Op words of a uint8 ADD (OP_QADD, or OP_QCONV with a residual operand): 20..25 the three multipliers and right shifts
+    (quantize.add_multipliers), 28 / 29 the two input zero points, 31 the output zero point, 34 / 35 the clamp."""
+    m1, e1, m2, e2, mo, eo = quantize.add_multipliers(a)
+    return {20: m1, 21: e1, 22: m2, 23: e2, 24: mo, 25: eo, 28: int(a['in1_zp']), 29: int(a['in2_zp']), 31: int(a['out_zp']),
+            34: int(a['lo']), 35: int(a['hi'])}
+
+
+def pad_channels(L, cin=None, cout=None):
+    """A layer with phantom channels appended: input channels (consumers of a tensor stored wider than the model's) and output rows get
+    weights = the weight zero point and bias 0, so (a - za)(w - zw) = 0 on them and a phantom output row stores the output zero point."""
+    w = L['w']
+    pads = [(0, 0)] * 4
+    if cin is not None:
+        pads[2] = (0, cin - w.shape[2])
+    if cout is not None:
+        pads[3] = (0, cout - w.shape[3])
+    if not any(p[1] for p in pads):
+        return L
+    w = np.pad(w, pads, constant_values=int(L['w_zp']))
+    return dict(L, w=w, bias=np.pad(L['bias'], (0, w.shape[3] - len(L['bias']))))
+
+
+def compile_ssd_mobilenet_v2_quant(qm):
+    """uint8 SSD-MobileNet-v2 (quantize.py: kind 'ssd_mobilenet_v2_uint8') -> the same head tensors, decode op and meta keys as
+    v1's program, op by op: first layer (q_conv0_k), 1x1 expansions and projections (q_conv_k), depthwise layers (q_dwm_k / q_dw_k),
+    the residual ADDs in the projections' epilogues (DD_Q_ADD_FUSE=0: OP_QADD, q_add_k).  Tensors of 24 channels are stored as 32
+    (pad_channels: the phantom channels hold the zero point)."""
+    need = lambda cond, what: _model_need(cond, what, 'uint8 SSD-MobileNet-v2')
+    size = int(qm['input']['size'])
+    P = Program(size, size)
+    Ls = qm['layers']
+    anchors, maps = nets.ssd_anchors(size)
+    if qm.get('anchors') is not None:
+        need(tuple(qm['anchors'].shape) == tuple(anchors.shape), 'anchors %s (this input size gives %s)' % (tuple(qm['anchors'].shape), tuple(anchors.shape)))
+        anchors = np.ascontiguousarray(qm['anchors'], dtype=np.float32)
+    n_anchors = len(anchors)
+
+    def geom(t, k, stride):
+        d = P.T(t)
+        ho, pt = same_pad(d['h'], k, stride)
+        wo, pl = same_pad(d['w'], k, stride)
+        return ho, wo, pt, pl
+
+    def info(kernel, flops, nbytes, wbytes, src_bytes=0):
+        P.info[-1] = dict(kernel=kernel, flops=flops, bytes=nbytes, wbytes=wbytes, src_bytes=src_bytes)
+
+    layer_t = {}                                             # layer (or block: its ADD's output) -> the tensor it writes
+
+    L = Ls['conv0']
+    ho, pt = same_pad(size, 3, L['stride'])
+    wo, pl = same_pad(size, 3, L['stride'])
+    need(L['w'].shape == (3, 3, 3, 32) and L['act'] == 'relu6', 'conv0: a 3x3 layer of 32 channels with ReLU6')
+    x = layer_t['conv0'] = P.qtensor(ho, wo, 32, L['out_zp'])
+    wp, wl, cb = pack_conv0(L)
+    raw = _req_words(L)
+    P.add_blob(np.zeros(16, np.uint8))
+    raw.update({38: 0 if wl is not None else 128 - int(L['w_zp']), 39: int(L['in_zp']), 46: P.add_blob(folded_addends(cb, raw))})
+    P._op(OP_QCONV0, dst=x, kh=3, kw=3, stride=L['stride'], pad_t=pt, pad_l=pl, cin=3, cout=32, cout_pad=32,
+          w_off=P.add_blob(wp), b_off=P.add_blob(cb), aff_off=P.add_blob(wl) if wl is not None else 0, ho=ho, wo=wo, raw=raw)
+    info('q_conv0_k', 2 * ho * wo * 27 * 32, 3 * size * size + ho * wo * 32, 27 * 32 + 4 * 32, 3 * size * size)
+
+    def conv(src, name, epi=None, res=-1, add=None, chan_map=None, cout_pad=None, dst=None, row_bytes=0, base_off=0, cout_store=0):
+        s = P.T(src)
+        L0 = Ls[name]
+        cout = L0['w'].shape[3]
+        L = pad_channels(L0, cin=s['c'], cout=(cout + 15) // 16 * 16 if epi != QEPI_ROWS else None)
+        kh = L['w'].shape[0]
+        ho, wo, pt, pl = geom(src, kh, L['stride'])
+        need(s['zp'] == L['in_zp'] and L0['w'].shape[2] <= s['c'] and L['w'].shape[2] == s['c'],
+                    '%s: input zero point %s / channels %s, its producer writes %s / %s' % (name, L['in_zp'], L0['w'].shape[2], s['zp'], s['c']))
+        if epi is None:                                      # bordered output: the 64-channel interleave where it fits (ReLU6, C % 64 == 0), else natural
+            epi = QEPI_Q16 if L['act'] == 'relu6' and res < 0 and L['w'].shape[3] % 64 == 0 else QEPI_Q16N
+        wp, cb, kcpt = pack_conv(L, epi, chan_map, cout_pad)
+        raw = _req_words(L)
+        if epi != QEPI_ROWS:
+            dst = P.qtensor(ho, wo, L['w'].shape[3], add['out_zp'] if add is not None else L['out_zp'])
+        raw.update({38: 128 - int(L['w_zp']), 39: int(L['in_zp']), 42: row_bytes, 43: base_off, 44: cout_store})
+        raw[46] = P.add_blob(folded_addends(cb, raw) if not raw[41] else np.array([int(v) * int(raw[32]) + (1 << 30) for v in cb], dtype=np.int64))
+        if add is not None:
+            r = P.T(res)
+            need(r['zp'] == add['in2_zp'] and L['out_zp'] == add['in1_zp'] and (r['h'], r['w'], r['c']) == (ho, wo, L['w'].shape[3]),
+                        '%s: the residual ADD reads tensors of other geometry or zero points' % name)
+            raw.update(add_words(add))
+        if epi != QEPI_ROWS and add is None:
+            layer_t[name] = dst
+        P._op(OP_QCONV, src=src, dst=dst, res=res, kh=kh, kw=kh, stride=L['stride'], pad_t=pt, pad_l=pl, cin=s['c'], cout=L['w'].shape[3],
+              cout_pad=len(cb), kpad=kcpt, epi=epi, w_off=P.add_blob(wp), b_off=P.add_blob(cb), ho=ho, wo=wo, raw=raw)
+        cin, cout = L0['w'].shape[2:]
+        info('q_conv_k', 2 * ho * wo * kh * kh * cin * cout, s['h'] * s['w'] * cin + ho * wo * cout, kh * kh * cin * cout + 4 * cout)
+        return dst
+
+    def dw(src, name):
+        L = Ls[name]
+        ho, wo, pt, pl = geom(src, 3, L['stride'])
+        s = P.T(src)
+        need(s['zp'] == L['in_zp'] and L['w'].shape[2] == s['c'], '%s: input zero point %s / channels %s, its producer writes %s / %s' % (name, L['in_zp'], L['w'].shape[2], s['zp'], s['c']))
+        w16, cb = pack_dw(L)
+        dst = layer_t[name] = P.qtensor(ho, wo, s['c'], L['out_zp'])
+        mf = pack_dw_mfma(L)
+        P._op(OP_QDW, src=src, dst=dst, kh=3, kw=3, stride=L['stride'], pad_t=pt, pad_l=pl, cin=s['c'], cout=s['c'], cout_pad=s['c'],
+              w_off=P.add_blob(w16), b_off=P.add_blob(cb), ho=ho, wo=wo, raw=_req_words(L),
+              p=[P.add_blob(mf[0]), P.add_blob(mf[1])] if mf is not None else [0, 0])
+        info('q_dw_k', 2 * ho * wo * 9 * s['c'], s['h'] * s['w'] * s['c'] + ho * wo * s['c'], 9 * s['c'] + 4 * s['c'])
+        return dst
+
+    def add_op(a_t, b_t, add):
+        t1, t2 = P.T(a_t), P.T(b_t)
+        need(t1['zp'] == add['in1_zp'] and t2['zp'] == add['in2_zp'] and (t1['h'], t1['w'], t1['c']) == (t2['h'], t2['w'], t2['c']),
+                    'ADD of tensors with other geometry or zero points')
+        dst = P.qtensor(t1['h'], t1['w'], t1['c'], add['out_zp'])
+        P._op(OP_QADD, src=a_t, dst=dst, res=b_t, cin=t1['c'], cout=t1['c'], ho=t1['h'], wo=t1['w'], raw=add_words(add))
+        nb = t1['h'] * t1['w'] * t1['c']
+        info('q_add_k', 0, 3 * nb, 0, 2 * nb)
+        return dst
+
+    feats = {}
+    blocks = []
+    while 'b%d_dw' % len(blocks) in Ls:
+        blocks.append('b%d' % len(blocks))
+    need(len(blocks) == 17, '%d inverted-residual blocks (MobileNet-v2 has 17)' % len(blocks))
+    for b in blocks:
+        h = x
+        if b + '_expand' in Ls:
+            h = conv(x, b + '_expand')
+            feats[b + '_expand'] = h
+        h = dw(h, b + '_dw')
+        add = qm.get('add', {}).get(b)
+        if add is None:
+            x = conv(h, b + '_project')
+        elif ADD_FUSE:
+            x = layer_t[b] = conv(h, b + '_project', res=x, add=add)
+        else:
+            x = layer_t[b] = add_op(conv(h, b + '_project'), x, add)
+        feats[b] = x
+    x = conv(x, 'conv_last')
+    feats['conv_last'] = x
+    for j in range(1, 5):
+        x = conv(conv(x, f'extra{j}_1'), f'extra{j}_2')
+        feats[f'extra{j}_2'] = x
+    n_cls = Ls['cls0']['w'].shape[3] // nets.SSD_ANCHORS_PER_MAP[0]
+    cls_row = (n_cls + 15) // 16 * 16
+    box_t = P.tensor(n_anchors, 1, 4, cs=4, dtype=DT_U8)
+    cls_t = P.tensor(n_anchors, 1, n_cls, cs=cls_row, dtype=DT_U8)
+    base = 0
+    for k, (fname, a) in enumerate(zip(quantize.V2_FEATURE_LAYERS, nets.SSD_ANCHORS_PER_MAP)):
+        ft = feats[fname]
+        fm = P.T(ft)['h']
+        need(fm == maps[k], 'feature map %d is %dx%d (the anchors are laid out for %d)' % (k, fm, fm, maps[k]))
+        for other in (f'box{k}', f'cls{k}'):
+            need((Ls[other]['out_scale'], Ls[other]['out_zp']) == (Ls[other[:3] + '0']['out_scale'], Ls[other[:3] + '0']['out_zp']),
+                        'the six %s tensors are concatenated: they need one (scale, zero point)' % other[:3])
+        cmap = np.full(a * cls_row, -1, np.int64)
+        for an in range(a):
+            cmap[an * cls_row:an * cls_row + n_cls] = an * n_cls + np.arange(n_cls)
+        conv(ft, f'box{k}', epi=QEPI_ROWS, dst=box_t, row_bytes=4 * a, base_off=4 * base, cout_store=4 * a)
+        conv(ft, f'cls{k}', epi=QEPI_ROWS, dst=cls_t, chan_map=cmap, cout_pad=(a * cls_row + 15) // 16 * 16, row_bytes=a * cls_row,
+             base_off=cls_row * base, cout_store=a * cls_row)
+        base += fm * fm * a
+    need(base == n_anchors, '%d anchors for predictors that emit %d rows' % (n_anchors, base))
+    Lb, Lc = Ls['box0'], Ls['cls0']
+    lut = quantize.logistic_table(Lc['out_scale'], Lc['out_zp'], qm['logistic']['out_scale'], qm['logistic']['out_zp'])
+    P._op(OP_QSSD_DECODE, src=box_t, res=cls_t, w_off=P.add_blob(lut), p=[n_cls, n_anchors],
+          rawf={32: float(Lb['out_scale']), 33: float(Lb['out_zp']), 34: float(qm['logistic']['out_scale']), 35: float(qm['logistic']['out_zp'])})
+    info('q_ssd_decode_k', 0, n_anchors * (4 + cls_row + 24), 256)
+    P.out_tensor = cls_t
+    P.meta = dict(kind='ssd_mobilenet_v2_uint8', anchors=anchors, n_classes=n_cls, box_tensor=box_t, cls_tensor=cls_t, cls_row=cls_row,
+                  feats=feats, quant=True, layer_tensors=layer_t)
     return P
 
 

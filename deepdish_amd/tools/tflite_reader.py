@@ -259,6 +259,8 @@ def load_ssd_mobilenet(path):
         layers[f'box{k}'], _ = _conv_layer(g, bh)
         layers[f'cls{k}'], _ = _conv_layer(g, ch)
         feats.append(bh.inputs[0])
+    if any(op.kind == 'ADD' for op in g.ops):                       # residual blocks: MobileNet-v2
+        return _load_ssd_mobilenet_v2(g, path, post, popts, anc, layers, feats, logi)
     # the backbone: from the last feature map back to the graph input
     chain, t = [], feats[-1]
     while g.made_by(t) is not None:
@@ -297,6 +299,110 @@ def load_ssd_mobilenet(path):
     wd['anchors'] = anc
     wd['__post__'] = popts                                            # not an array: nets.compile_ssd_mobilenet ignores it, the plugins read it
     return 'f32', wd
+
+
+def _load_ssd_mobilenet_v2(g, path, post, popts, anc, layers, feats, logi):
+    """uint8 SSD-MobileNet-v2 (TF-slim MobileNet-v2 + the TF Object Detection API SSD head; the export is absent, so this pattern is a
+    reconstruction).  The backbone is walked back from the last feature map; an ADD is a residual: one input is the block's projection,
+    whose chain (project <- depthwise <- [expand]) starts at the other input."""
+    from .. import quantize
+    for k in range(6):
+        for kind in ('box', 'cls'):
+            L = layers[f'{kind}{k}']
+            _need(L['w'].shape[:2] == (1, 1), g.made_by(feats[k]) or post, '%s%d: a %dx%d predictor (1x1 predictors are built)' % (kind, k, *L['w'].shape[:2]))
+    seq, t, residual_of = [], feats[-1], {}
+    while g.made_by(t) is not None:
+        op = g.made_by(t)
+        if op.kind == 'ADD':
+            _need(op.options.get('act', 'none') == 'none', op, 'fused activation %s on ADD (NONE is built)' % op.options.get('act'))
+            _need(len(op.inputs) == 2, op, 'ADD of %d inputs' % len(op.inputs))
+
+            def block_input(p):                                          # the tensor the projection p's block starts at, or None
+                chain = []
+                for _ in range(3):
+                    c = g.made_by(p)
+                    if c is None or c.kind not in ('CONV_2D', 'DEPTHWISE_CONV_2D'):
+                        return None
+                    chain.append(c)
+                    p = c.inputs[0]
+                    if c.kind == 'DEPTHWISE_CONV_2D':
+                        e = g.made_by(p)
+                        if e is not None and e.kind == 'CONV_2D' and len(chain) == 2:
+                            return e.inputs[0]
+                        return p
+                return None
+            a, b = op.inputs
+            if block_input(a) == b:
+                proj, res = a, b
+            elif block_input(b) == a:
+                proj, res = b, a
+            else:
+                raise UnsupportedModel('operator %s: neither input of the ADD is a projection of the block that starts at the other one' % (op,))
+            seq.append(op)
+            residual_of[op.index] = res
+            t = proj
+            continue
+        seq.append(op)
+        t = op.inputs[0]
+    _need(t in g.inputs, seq[-1] if seq else post, 'the backbone does not start at a graph input')
+    seq.reverse()
+    x = g.tensors[t]
+    _need(x.dtype == np.uint8, seq[0], 'a float MobileNet-v2 is not built (uint8 only)')
+    _need(len(x.shape) == 4 and x.shape[1] == x.shape[2] and x.shape[3] == 3, seq[0], 'input %s (expected [1, s, s, 3])' % (x.shape,))
+    names, adds, out_of = [], {}, {}
+    pending = list(seq)
+
+    def take(name, kind):
+        op = pending.pop(0) if pending else None
+        _need(op is not None, post, 'the backbone ends before %s' % name)
+        want = 'DEPTHWISE_CONV_2D' if kind == 'dw' else 'CONV_2D'
+        _need(op.kind == want, op, 'expected %s for %s (%s)' % (want, name, 'depthwise extras are SSDLite, not built' if name.startswith('extra') else 'MobileNet-v2 layout'))
+        layers[name], _ = _conv_layer(g, op)
+        _need(quantize.conv_multiplier(layers[name])[1] <= 0, op, '%s: requantisation multiplier >= 1 (not built)' % name)
+        names.append(name)
+        out_of[op.outputs[0]] = name
+        return op
+    take('conv0', 'conv')
+    for bname, _, t_, _, _, res in quantize.v2_blocks():
+        start = pending[0].inputs[0] if pending else None
+        if t_ != 1:
+            take(bname + '_expand', 'conv')
+        take(bname + '_dw', 'dw')
+        take(bname + '_project', 'conv')
+        if pending and pending[0].kind == 'ADD':
+            op = pending.pop(0)
+            _need(res, op, '%s: a residual ADD on a block that changes stride or channels' % bname)
+            _need(residual_of[op.index] == start, op, '%s: the ADD does not read the block input' % bname)
+            s1, s2, so = (g.tensors[k] for k in (op.inputs[0], op.inputs[1], op.outputs[0]))
+            if op.inputs[0] == start:
+                s1, s2 = s2, s1
+            _need(s1.per_tensor and s2.per_tensor and so.per_tensor and so.dtype == np.uint8, op, 'uint8 ADD with per-tensor parameters')
+            a = dict(in1_scale=np.float32(s1.scale[0]), in1_zp=int(s1.zero_point[0]), in2_scale=np.float32(s2.scale[0]), in2_zp=int(s2.zero_point[0]),
+                     out_scale=np.float32(so.scale[0]), out_zp=int(so.zero_point[0]), lo=0, hi=255)
+            try:
+                quantize.add_multipliers(a)
+            except ValueError as e:
+                raise UnsupportedModel('operator %s: %s' % (op, e))
+            adds[bname] = a
+            out_of[op.outputs[0]] = bname
+        else:
+            _need(not res, pending[0] if pending else post, '%s: the block has no residual ADD' % bname)
+    take('conv_last', 'conv')
+    for j in range(1, 5):
+        take(f'extra{j}_1', 'conv')
+        take(f'extra{j}_2', 'conv')
+    _need(not pending, pending[0] if pending else post, 'operators behind the last extra layer')
+    want_feats = list(quantize.V2_FEATURE_LAYERS)
+    _need([out_of.get(f) for f in feats] == want_feats, post, 'feature maps come from %s (expected %s)' % ([out_of.get(f) for f in feats], want_feats))
+    order = names + [n for k in range(6) for n in (f'box{k}', f'cls{k}')]
+    per_anchor = layers['cls0']['w'].shape[3] // 3
+    _need(popts['num_classes'] + 1 == per_anchor, post, 'num_classes = %d, but the class predictors emit %d values per anchor (classes + background)'
+          % (popts['num_classes'], per_anchor))
+    lt = g.tensors[logi.outputs[0]]
+    qm = dict(kind='ssd_mobilenet_v2_uint8', input=dict(scale=np.float32(x.scale[0]), zp=int(x.zero_point[0]), size=int(x.shape[1])),
+              layers=layers, add=adds, logistic=dict(out_scale=np.float32(lt.scale[0]), out_zp=int(lt.zero_point[0])), order=order, anchors=anc,
+              post=popts, source=str(path))
+    return 'uint8', qm
 
 
 # ------------------------------------------------------------------------------------------- MARS encoder

@@ -191,10 +191,14 @@ def ssd_mobilenet_graph(model, anchors=None, post=None):
     for name in names:
         t, hw = conv(name, t, hw)
         out_of[name] = (t, hw)
+    return _ssd_tail(W, model, quant, layer, conv, [out_of[f] for f in ['pw11', 'pw13', 'extra1_2', 'extra2_2', 'extra3_2', 'extra4_2']], anchors, adt, qp, post)
+
+
+def _ssd_tail(W, model, quant, layer, conv, feats, anchors, adt, qp, post):
+    """The predictors on the six (feature tensor, map size) pairs, RESHAPE / CONCATENATION fans, LOGISTIC and the post-process op."""
     boxes, classes = [], []
     n_cls = (model['layers']['cls0']['w'].shape[3] if quant else model['cls0/weights'].shape[3]) // nets.SSD_ANCHORS_PER_MAP[0]
-    for k, (f, a) in enumerate(zip(['pw11', 'pw13', 'extra1_2', 'extra2_2', 'extra3_2', 'extra4_2'], nets.SSD_ANCHORS_PER_MAP)):
-        ft, fm = out_of[f]
+    for k, ((ft, fm), a) in enumerate(zip(feats, nets.SSD_ANCHORS_PER_MAP)):
         for kind, per, acc in (('box', 4, boxes), ('cls', n_cls, classes)):
             c, _ = conv(f'{kind}{k}', ft, fm)
             L = layer(f'{kind}{k}')
@@ -337,6 +341,63 @@ def write_ssd_mobilenet(model, path, anchors=None, post=None, metadata=None):
     if metadata is not None:
         g.set_metadata(**metadata)
     data = g.tobytes()
+    with open(path, 'wb') as f:
+        f.write(data)
+    return len(data)
+
+
+def ssd_mobilenet_v2_graph(qm, anchors=None, post=None):
+    """uint8 SSD-MobileNet-v2 QModel (deepdish_amd/quantize.py) -> GraphWriter of the graph the TF Object Detection API exports: CONV_2D
+    (fused RELU6 / NONE), DEPTHWISE_CONV_2D, ADD (the residual: projection + block input), the predictors on b13's expansion output,
+    conv_last and the four extras, then the same fans, LOGISTIC and post-process op as v1."""
+    W = GraphWriter('SSD-MobileNet-v2 (uint8), written by deepdish_amd')
+    size = int(qm['input']['size'])
+    if anchors is None:
+        anchors = qm.get('anchors') if qm.get('anchors') is not None else nets.ssd_anchors(size)[0]
+    layer = lambda name: qm['layers'][name]
+    qp = lambda scale, zp: (scale, zp)
+
+    def conv(name, src, hw):
+        L = layer(name)
+        if L['kind'] == 'conv':
+            wt, cout = np.transpose(L['w'], (3, 0, 1, 2)), L['w'].shape[3]
+        else:
+            wt, cout = L['w'][None], L['w'].shape[2]
+        ho = -(-hw // L['stride'])
+        fw = W.tensor(name + '/weights', wt.shape, np.uint8, wt, L['w_scale'], L['w_zp'])
+        bs = W.tensor(name + '/bias', [cout], np.int32, L['bias'], np.float32(L['in_scale']) * np.float32(L['w_scale']), 0)
+        out = W.tensor(name, [1, ho, ho, cout], np.uint8, None, L['out_scale'], L['out_zp'])
+        W.op('CONV_2D' if L['kind'] == 'conv' else 'DEPTHWISE_CONV_2D', [src, fw, bs], [out], dict(stride=L['stride'], act=L['act']))
+        return out, ho
+
+    x = W.tensor('normalized_input_image_tensor', [1, size, size, 3], np.uint8, None, qm['input']['scale'], qm['input']['zp'])
+    W.inputs = [x]
+    t, hw = conv('conv0', x, size)
+    out_of = {}
+    b = 0
+    while 'b%d_dw' % b in qm['layers']:
+        name = 'b%d' % b
+        h, hh = t, hw
+        if name + '_expand' in qm['layers']:
+            h, hh = out_of[name + '_expand'] = conv(name + '_expand', h, hh)
+        h, hh = conv(name + '_project', *conv(name + '_dw', h, hh))
+        a = qm['add'].get(name)
+        if a is not None:
+            s = W.tensor(name + '/add', [1, hh, hh, layer(name + '_project')['w'].shape[3]], np.uint8, None, a['out_scale'], a['out_zp'])
+            W.op('ADD', [h, t], [s])
+            h = s
+        t, hw = h, hh
+        b += 1
+    t, hw = out_of['conv_last'] = conv('conv_last', t, hw)
+    for j in range(1, 5):
+        t, hw = out_of[f'extra{j}_2'] = conv(f'extra{j}_2', *conv(f'extra{j}_1', t, hw))
+    return _ssd_tail(W, qm, True, layer, conv, [out_of[f] for f in ('b13_expand', 'conv_last', 'extra1_2', 'extra2_2', 'extra3_2', 'extra4_2')],
+                     anchors, np.uint8, qp, post)
+
+
+def write_ssd_mobilenet_v2(qm, path, anchors=None, post=None):
+    """A uint8 SSD-MobileNet-v2 QModel as a .tflite file (post: overrides of the post-process options, as write_ssd_mobilenet)."""
+    data = ssd_mobilenet_v2_graph(qm, anchors, post=post).tobytes()
     with open(path, 'wb') as f:
         f.write(data)
     return len(data)

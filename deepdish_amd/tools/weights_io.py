@@ -9,7 +9,8 @@ tools/graphdef.py; other graphs are an explicit error.
 
 `load_ssd_model` is what the SSD-MobileNet plugins call: it returns ('uint8', QModel) for the reference's own kind
 of file -- a uint8-quantised model (tools/ssd_mobilenet.py:102 upstream; `synthetic...uint8` names build one from
-the seeded f32 weights with deepdish_amd/quantize.py, `...sym...` pins the weight zero points at 128) -- and
+the seeded f32 weights with deepdish_amd/quantize.py, `...sym...` pins the weight zero points at 128, and a name that also holds
+`mobilenet_v2` builds the v2 network) -- and
 ('f32', named weights) otherwise.
 """
 import os
@@ -73,6 +74,8 @@ def load_ssd_model(model_file):
     m = re.search(r'synthetic(?::|-seed)?(\d+)?', name)
     if m and ('uint8' in name or 'quant' in name):
         seed = int(m.group(1)) if m.group(1) else 1234
+        if 'mobilenet_v2' in name or 'mobilenetv2' in name:      # synthetic-ssd_mobilenet_v2-uint8[-sym]: the v2 network (quantize.py)
+            return 'uint8', quantize.synthetic_ssd_v2_quant_model(seed, symmetric_weights='sym' in name)
         return 'uint8', quantize.synthetic_ssd_quant_model(seed, symmetric_weights='sym' in name)
     return 'f32', load_named_weights(model_file, nets.synthetic_ssd_weights)
 
@@ -83,7 +86,7 @@ def ssd_post_options(model):
     nms_iou_threshold 0.6 -- the values synthetic models and .npz weights run with)."""
     from .tflite_reader import SSD_POST_DEFAULTS
     post = dict(SSD_POST_DEFAULTS)
-    src = model.get('post') if isinstance(model, dict) and model.get('kind') == 'ssd_mobilenet_v1_uint8' else model.get('__post__') if isinstance(model, dict) else None
+    src = model.get('post') if isinstance(model, dict) and model.get('kind') in ('ssd_mobilenet_v1_uint8', 'ssd_mobilenet_v2_uint8') else model.get('__post__') if isinstance(model, dict) else None
     if src:
         post.update({k: src[k] for k in SSD_POST_DEFAULTS if k in src})
     return post

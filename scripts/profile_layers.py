@@ -16,6 +16,9 @@ if kind == 'ssd':
 elif kind in ('ssd_i8', 'ssd_i8_sym'):                                    # the uint8 model (csrc/netsq.hip); _sym: weight zero points at 128
     from deepdish_amd import quantize, netsq
     prog = netsq.compile_ssd_mobilenet_quant(quantize.synthetic_ssd_quant_model(symmetric_weights=kind.endswith('sym'))); shape = (300, 300)
+elif kind == 'ssd_v2_i8':                                                # the uint8 SSD-MobileNet-v2 (op by op: q_conv_k with the residual ADD, q_dwm_k)
+    from deepdish_amd import quantize, netsq
+    prog = netsq.compile_ssd_mobilenet_quant(quantize.synthetic_ssd_v2_quant_model()); shape = (300, 300)
 elif kind == 'mars':
     prog = nets.compile_mars(nets.synthetic_mars_weights()); shape = (64, 32)
 else:
@@ -23,7 +26,7 @@ else:
 net = Net(prog, max_batch=batch)
 if kind.startswith('ssd') and os.environ.get('DD_SSD_DEC', '1') != '0':      # as the pipeline runs it: the heads decode in their epilogue
     net.ssd_decode(prog.meta['anchors'], 1e-8)
-if kind not in ('ssd', 'ssd_i8', 'ssd_i8_sym', 'mars') and os.environ.get('DD_YOLO_DEC', '1') != '0':      # as the pipeline runs it: the Detect heads reduce their rows
+if kind not in ('ssd', 'ssd_i8', 'ssd_i8_sym', 'ssd_v2_i8', 'mars') and os.environ.get('DD_YOLO_DEC', '1') != '0':      # as the pipeline runs it: the Detect heads reduce their rows
     net.yolo_decode(True)
 x = torch.randint(0, 256, (batch,) + shape + (3,), dtype=torch.uint8, device='cuda')
 check(lib().dd_net_profile(net._h, 1))

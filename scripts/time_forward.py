@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Whole-forward device time of a network (HIP events on the launch stream), no per-op instrumentation.
-Usage: python scripts/time_forward.py ssd|ssd_i8|mars|yolo BATCH [kernels] [reps=N]   (kernels: also print which special launches ran;
+Usage: python scripts/time_forward.py ssd|ssd_i8|ssd_v2_i8|mars|yolo BATCH [kernels] [reps=N]   (kernels: also print which special launches ran;
 reps=N: N timed forwards after min(5, N) untimed ones instead of 30 after 5 -- for launches of thousands of frames)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,6 +17,9 @@ if kind == 'ssd':
 elif kind == 'ssd_i8':
     from deepdish_amd import quantize, netsq
     prog = netsq.compile_ssd_mobilenet_quant(quantize.synthetic_ssd_quant_model()); shape = (300, 300)
+elif kind == 'ssd_v2_i8':                                 # uint8 SSD-MobileNet-v2 (synthetic weights)
+    from deepdish_amd import quantize, netsq
+    prog = netsq.compile_ssd_mobilenet_quant(quantize.synthetic_ssd_v2_quant_model()); shape = (300, 300)
 elif kind == 'mars':
     prog = nets.compile_mars(nets.synthetic_mars_weights()); shape = (64, 32)
 else:
@@ -35,7 +38,7 @@ for r in range(reps):
 net.ctx.sync()
 us = np.array([ev[r].elapsed_time(ev[r + 1]) * 1e3 for r in range(reps)])
 ref = net.read().copy()
-if kind == 'ssd_i8':                                       # the class rows are the output tensor; the box rows belong to the digest too
+if kind in ('ssd_i8', 'ssd_v2_i8'):                         # the class rows are the output tensor; the box rows belong to the digest too
     ref = np.concatenate([np.asarray(ref).reshape(-1), np.asarray(net.read(tensor=prog.meta['box_tensor'])).reshape(-1)])
 import hashlib
 print(f'{kind} batch {batch}: mean {us.mean():.1f} us  min {us.min():.1f} us  checksum {float(np.abs(ref).sum()):.6e}  sha {hashlib.sha256(np.ascontiguousarray(ref).tobytes()).hexdigest()[:16]}')
