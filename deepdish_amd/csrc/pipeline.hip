@@ -138,6 +138,14 @@ struct dd_pipeline {
     long long motion_rejected = 0;
     std::vector<int> off, doff;                // per-step prefix sums (candidates, kept detections) over the streams
     std::vector<double> tlwh;
+    // --object-detector-skip-frames (deepdish.py:892-893,929-938,1003-1014; dd_pipeline_detector_skip_frames): a skip step reuses the
+    // last detector step's adaptor output (StreamState::boxes0/scores0/cls0) and its feature rows (d_feats, per-stream offsets foff)
+    int skip_n = 0;                            // N; <= 0 = every step a detector step
+    int skip_rem = 0;                          // skip steps left before the next detector step (the reference's skip_rem)
+    std::vector<int> foff;                     // row offsets of the last encoder run's features in d_feats, [S + 1]
+    DevBuf d_feats_skip, d_gather;             // a skip step's tracker input rows; their per-stream offsets on the device
+    PinBuf h_gather;
+    hipEvent_t skip_mark = nullptr;            // a skip step's main stream waits here for what the detector stream holds at step entry
 };
 
 namespace {
@@ -227,6 +235,7 @@ int dd_pipeline_create(dd_ctx *ctx, int n_streams, int frame_h, int frame_w, dd_
         }
         DD_HIP(hipEventCreateWithFlags(&p->det_done, hipEventDisableTiming));
         DD_HIP(hipEventCreateWithFlags(&p->main_mark, hipEventDisableTiming));
+        DD_HIP(hipEventCreateWithFlags(&p->skip_mark, hipEventDisableTiming));
         for (hipEvent_t &e : p->ev_det) DD_HIP(hipEventCreate(&e));
         const size_t S = n_streams;
         if ((rc = p->d_resized.reserve(S * p->det_in * p->det_in_w * 3)) != DD_OK) return rc;
@@ -266,6 +275,7 @@ int dd_pipeline_create(dd_ctx *ctx, int n_streams, int frame_h, int frame_w, dd_
     { const char *e = getenv("DD_DET_LATE"); p->det_late = e ? atoi(e) != 0 : n_streams >= 64; }
     p->st.resize(n_streams);
     p->trks.resize(n_streams);
+    p->foff.assign(n_streams + 1, 0);
     if ((rc = ddk::tracker_group_create(ctx, n_streams, max_cosine_distance, max_iou_distance, max_age, n_init, 0,
                                         track_capacity, gallery_capacity, p->trks.data())) != DD_OK) return rc;
     for (int z = 0; z < n_streams; ++z) {
@@ -284,12 +294,13 @@ int dd_pipeline_destroy(dd_pipeline *p) {
     if (p->det_stream) { (void)hipStreamSynchronize(p->det_stream); (void)hipStreamDestroy(p->det_stream); }
     if (p->det_done) (void)hipEventDestroy(p->det_done);
     if (p->main_mark) (void)hipEventDestroy(p->main_mark);
+    if (p->skip_mark) (void)hipEventDestroy(p->skip_mark);
     for (auto &s : p->st) dd_tracker_destroy(s.trk);
     (void)hipFree(p->d_anchors);
     dd_mog2_destroy(p->mog2);
     for (DevBuf *b : {&p->d_resized, &p->d_tmp, &p->d_post, &p->d_det, &p->d_fin, &p->d_pack, &p->d_tfl_boxes, &p->d_nms, &p->d_crop, &p->d_patches, &p->d_feats,
-                      &p->d_mask, &p->d_masked, &p->d_mbox}) b->release();
-    for (PinBuf *b : {&p->h_fin, &p->h_nms, &p->h_crop, &p->h_mbox}) b->release();
+                      &p->d_mask, &p->d_masked, &p->d_mbox, &p->d_feats_skip, &p->d_gather}) b->release();
+    for (PinBuf *b : {&p->h_fin, &p->h_nms, &p->h_crop, &p->h_mbox, &p->h_gather}) b->release();
     delete p;
     return DD_OK;
 }
@@ -331,6 +342,20 @@ int dd_pipeline_detector_adaptor(dd_pipeline *p, int adaptor) {
         if ((rc = p->d_tfl_boxes.reserve(hb.size() * sizeof(int))) != DD_OK) return rc;
         DD_HIP(hipMemcpy(p->d_tfl_boxes.p, hb.data(), hb.size() * sizeof(int), hipMemcpyHostToDevice));
     }
+    return DD_OK;
+}
+
+// --object-detector-skip-frames N (deepdish.py:892-893,929-938,1003-1014): the detector and the encoder run on one step in N + 1 --
+// steps 0, N + 1, 2 (N + 1), ... counted from the first step; n <= 0 = every step (the default).  All streams step together, so a step
+// is either a detector step or a skip step.  A skip step runs no detector chain (resize, forward, post-process, adaptor tail, host copy)
+// and no crops / encoder: every stream keeps the adaptor output of the last detector step (what dd_pipeline_detections returns; injected
+// detections passed on a skip step are ignored), and its boxes -- through this step's box hygiene, motion test and NMS -- pair with
+// that step's feature rows as zip() does: the first min(kept boxes now, feature rows then) of each.  Call before the first step.
+int dd_pipeline_detector_skip_frames(dd_pipeline *p, int n) {
+    DD_REQUIRE(p, DD_E_ARG, "dd_pipeline_detector_skip_frames: NULL pipeline");
+    DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, "dd_pipeline_detector_skip_frames: call before the first step");
+    p->skip_n = n;
+    p->skip_rem = 0;
     return DD_OK;
 }
 
@@ -513,6 +538,18 @@ int enqueue_detector(dd_pipeline *p, const uint8_t *frames) {
     return DD_OK;
 }
 
+// A skip step's tracker input (deepdish.py:1003-1014: zip(boxes, labels, scores, features) with the last encoder run's features):
+// row j < n_z = dst_off[z + 1] - dst_off[z] of stream z is feature row src_off[z] + j of that run; the host has truncated n_z to the
+// rows stream z had then, so every read stays inside them.  One block per stream; a 128-f32 row moves as 32 float4.
+__global__ void __launch_bounds__(256) skip_gather_rows_k(const float4 *__restrict__ src, float4 *__restrict__ dst,
+                                                          const int *__restrict__ dst_off, const int *__restrict__ src_off) {
+    const int z = blockIdx.x;
+    const int a = dst_off[z], n = dst_off[z + 1] - a;
+    const float4 *sp = src + (size_t)src_off[z] * 32;
+    float4 *dp = dst + (size_t)a * 32;
+    for (int i = threadIdx.x; i < n * 32; i += blockDim.x) dp[i] = sp[i];
+}
+
 // Count-line logic of one stream after its tracker update (deepdish.py:1035-1114, 1303-1312); host only.
 void count_line_one_stream(dd_pipeline *p, StreamState &st) {
     int nd = 0, nl = 0;
@@ -586,6 +623,8 @@ extern "C" {
 // scores, class ids, stream s owns rows [inj_offsets[s], inj_offsets[s+1]).
 // frames_next (optional): the frames of the following step; their detector run is queued on the detector
 // stream as soon as this step has read its own detections, and overlaps this step's NMS / encoder / tracker.
+// With dd_pipeline_detector_skip_frames a skip step ignores inj_* (they stand for the detector's output, and it does not run), and
+// frames_next is queued only when the next step is a detector step.
 int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames, const uint8_t *frames_next, const double *inj_boxes_host,
                       const double *inj_scores_host, const int *inj_cls_host, const int *inj_offsets_host);
 
@@ -606,8 +645,18 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
     const int S = p->S, MAX_DET = p->max_det;
     int rc;
     if ((rc = flush_stage_events(p)) != DD_OK) return rc;
+    // deepdish.py:929-938: the first step detects; then N skip steps follow every detector step
+    const bool skip = p->skip_rem > 0 && p->steps > 0;
+    const int skip_rem_next = skip ? p->skip_rem - 1 : p->skip_n;
+    if (skip_rem_next > 0) frames_next = nullptr;          // the next step is a skip step: no detector run to queue for its frames
     const double t0 = now_s();
     p->step_wait = 0;
+    if (skip && p->det) {
+        // no detector run reads these frames: the main stream takes over what the detector stream holds for them (the wait an ingest
+        // ring queued there for their upload, dd_pipeline_detector_stream) before MOG2 reads them
+        DD_HIP(hipEventRecord(p->skip_mark, p->det_stream));
+        DD_HIP(hipStreamWaitEvent(s, p->skip_mark, 0));
+    }
     DD_STAGE_BEGIN(0);
     if ((rc = ddk::trackers_predict(p->trks.data(), S)) != DD_OK) return rc;            // deepdish.py:1028
     DD_STAGE_END(0);
@@ -621,7 +670,10 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
     // (host phases below: one parallel_for over the streams each -- they share nothing; hostpool.h)
     constexpr int GRAIN = 16;
     std::vector<StreamState> &st = p->st;
-    if (p->det) {
+    if (skip) {
+        // every stream keeps the adaptor output of the last detector step; the early look-ahead form queues the next frames here
+        if (p->det && frames_next && !p->det_late && (rc = enqueue_detector(p, frames_next)) != DD_OK) return rc;
+    } else if (p->det) {
         if (p->det_pending != frames && (rc = enqueue_detector(p, frames)) != DD_OK) return rc;       // not queued ahead: run it now
         DD_TIMED_WAIT(hipEventSynchronize(p->det_done));                                               // round trip 1
         p->det_pending = nullptr;
@@ -734,7 +786,7 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
     ddk::parallel_for(S, GRAIN, [&](int z0, int z1) {
         for (int z = z0; z < z1; ++z) {
             StreamState &q = st[z];
-            if (inj_offsets_host) {
+            if (inj_offsets_host && !skip) {
                 const int a = inj_offsets_host[z], b = inj_offsets_host[z + 1];
                 q.boxes0.assign(inj_boxes_host + (size_t)a * 4, inj_boxes_host + (size_t)b * 4);
                 q.scores0.assign(inj_scores_host + a, inj_scores_host + b);
@@ -821,53 +873,74 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
     }
     const double t2 = now_s();
 
-    // ---------------- crops + MARS for every kept box of every stream (deepdish.py:1008)
+    // ---------------- crops + MARS for every kept box of every stream (deepdish.py:1008).  A skip step runs neither (:1003-1014): stream
+    // z's first n_z = min(kept boxes, feature rows of the last encoder run) boxes pair with those rows, as zip() truncates
     std::vector<int> &doff = p->doff;
     doff.assign(S + 1, 0);
-    for (int z = 0; z < S; ++z) doff[z + 1] = doff[z] + (int)st[z].keep.size();
+    for (int z = 0; z < S; ++z)
+        doff[z + 1] = doff[z] + (skip ? std::min((int)st[z].keep.size(), p->foff[z + 1] - p->foff[z]) : (int)st[z].keep.size());
     const int D = doff[S];
     std::vector<double> &tlwh = p->tlwh;
     tlwh.resize((size_t)D * 4);
     if (D > 0) {
-        if ((rc = p->h_crop.reserve((size_t)D * 32)) != DD_OK) return rc;
-        if ((rc = p->d_crop.reserve((size_t)D * 32)) != DD_OK) return rc;
-        if ((rc = p->d_patches.reserve((size_t)D * 64 * 32 * 3)) != DD_OK) return rc;
-        if ((rc = p->d_feats.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
-        int *hc = p->h_crop.as<int>();
+        if (!skip) {
+            if ((rc = p->h_crop.reserve((size_t)D * 32)) != DD_OK) return rc;
+            if ((rc = p->d_crop.reserve((size_t)D * 32)) != DD_OK) return rc;
+            if ((rc = p->d_patches.reserve((size_t)D * 64 * 32 * 3)) != DD_OK) return rc;
+            if ((rc = p->d_feats.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
+        }
+        int *hc = skip ? nullptr : p->h_crop.as<int>();
         ddk::parallel_for(S, GRAIN, [&](int z0, int z1) {
             for (int z = z0; z < z1; ++z) {
                 StreamState &q = st[z];
                 q.det_cls.clear(); q.det_conf.clear();
-                for (size_t j = 0; j < q.keep.size(); ++j) {
+                for (int j = 0; j < doff[z + 1] - doff[z]; ++j) {
                     const int i = q.keep[j];
                     const int64_t *b = q.ib.data() + (size_t)i * 4;
-                    int *c = hc + (size_t)(doff[z] + j) * 8;
-                    ddk::crop_box_host(b, 64, 32, p->H, p->W, c, c + 1, c + 2, c + 3);     // generate_detections.py:63-80
-                    c[4] = z; c[5] = c[6] = c[7] = 0;
+                    if (hc) {
+                        int *c = hc + (size_t)(doff[z] + j) * 8;
+                        ddk::crop_box_host(b, 64, 32, p->H, p->W, c, c + 1, c + 2, c + 3);     // generate_detections.py:63-80
+                        c[4] = z; c[5] = c[6] = c[7] = 0;
+                    }
                     for (int c4 = 0; c4 < 4; ++c4) tlwh[(size_t)(doff[z] + j) * 4 + c4] = (double)b[c4];
                     q.det_cls.push_back(q.ic[i]);
                     q.det_conf.push_back(q.is[i]);
                 }
             }
         });
-        DD_STAGE_BEGIN(2);
-        DD_HIP(hipMemcpyAsync(p->d_crop.p, hc, (size_t)D * 32, hipMemcpyHostToDevice, s));
-        if ((rc = ddk::crop_resize(s, frames, p->H, p->W, p->d_crop.p, D, 64, 32, p->d_patches.as<uint8_t>())) != DD_OK) return rc;
-        for (int a = 0; a < D; a += p->enc_batch) {
-            const int n = std::min(p->enc_batch, D - a);
-            if ((rc = dd_net_forward(p->enc, p->d_patches.as<uint8_t>() + (size_t)a * 64 * 32 * 3, n, s)) != DD_OK) return rc;
-            if ((rc = dd_net_read(p->enc, -1, n, p->d_feats.as<float>() + (size_t)a * 128, 1, s)) != DD_OK) return rc;
+        if (!skip) {
+            DD_STAGE_BEGIN(2);
+            DD_HIP(hipMemcpyAsync(p->d_crop.p, hc, (size_t)D * 32, hipMemcpyHostToDevice, s));
+            if ((rc = ddk::crop_resize(s, frames, p->H, p->W, p->d_crop.p, D, 64, 32, p->d_patches.as<uint8_t>())) != DD_OK) return rc;
+            for (int a = 0; a < D; a += p->enc_batch) {
+                const int n = std::min(p->enc_batch, D - a);
+                if ((rc = dd_net_forward(p->enc, p->d_patches.as<uint8_t>() + (size_t)a * 64 * 32 * 3, n, s)) != DD_OK) return rc;
+                if ((rc = dd_net_read(p->enc, -1, n, p->d_feats.as<float>() + (size_t)a * 128, 1, s)) != DD_OK) return rc;
+            }
+            DD_STAGE_END(2);
         }
-        DD_STAGE_END(2);
     } else {
         for (auto &q : st) { q.det_cls.clear(); q.det_conf.clear(); }
     }
+    if (!skip) p->foff = doff;                      // the rows d_feats now holds: what the skip steps up to the next detector step pair with
     const double t3 = now_s();
 
     // ---------------- deep_sort update, phase-split so all streams share two round trips (:1029)
     DD_STAGE_BEGIN(3);
-    if ((rc = ddk::trackers_update_begin(p->trks.data(), S, tlwh.data(), D ? p->d_feats.as<float>() : nullptr, 1,
-                                         doff.data())) != DD_OK) return rc;
+    if (skip && D > 0) {                            // the skip step's tracker input rows, gathered on the device (the trak stage)
+        if ((rc = p->h_gather.reserve((size_t)(2 * S + 1) * sizeof(int))) != DD_OK) return rc;
+        if ((rc = p->d_gather.reserve((size_t)(2 * S + 1) * sizeof(int))) != DD_OK) return rc;
+        if ((rc = p->d_feats_skip.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
+        int *hg = p->h_gather.as<int>();           // the previous step's copy out of it completed at that step's last stream wait
+        memcpy(hg, doff.data(), (size_t)(S + 1) * sizeof(int));
+        memcpy(hg + S + 1, p->foff.data(), (size_t)S * sizeof(int));
+        DD_HIP(hipMemcpyAsync(p->d_gather.p, hg, (size_t)(2 * S + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+        const int *dg = p->d_gather.as<int>();
+        hipLaunchKernelGGL(skip_gather_rows_k, dim3(S), dim3(256), 0, s, p->d_feats.as<float4>(), p->d_feats_skip.as<float4>(), dg, dg + S + 1);
+        DD_LAUNCH_CHECK();
+    }
+    const float *feats = D == 0 ? nullptr : skip ? p->d_feats_skip.as<float>() : p->d_feats.as<float>();
+    if ((rc = ddk::trackers_update_begin(p->trks.data(), S, tlwh.data(), feats, 1, doff.data())) != DD_OK) return rc;
     DD_STAGE_END(3);
     // Look-ahead, late form (default): the detector run of the next frames is queued HERE, behind this step's NMS / crops / encoder /
     // association kernels (enqueue_detector orders the detector stream after what the main stream holds so far).  Queued at the
@@ -891,6 +964,7 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
     p->g_wall += 1e3 * (t4 - t0); p->g_host += 1e3 * ((t4 - t0) - p->step_wait);
     p->ev_pending = true;
     p->steps += 1;
+    p->skip_rem = skip_rem_next;
     return DD_OK;
 }
 

@@ -40,7 +40,7 @@ class MultiStreamPipeline:
                  labels=None, wanted_labels=('person',), input_size=(640, 480), line=None, max_cosine_distance=0.2,
                  nms_max_overlap=0.6, max_iou_distance=0.7, max_age=60, n_init=3, context=None, run_detector=True,
                  encoder_max_batch=None, track_capacity=512, gallery_capacity=256, background_subtraction_ratio=None,
-                 background_masking=False, graph=None):
+                 background_masking=False, graph=None, object_detector_skip_frames=None):
         self.ctx = context or default_context()
         self.S = int(n_streams)
         self.W, self.H = input_size
@@ -116,6 +116,10 @@ class MultiStreamPipeline:
         self._class_id = {name: i - off for i, name in enumerate(self.label_lines) if i >= off}
         if background_subtraction_ratio is not None:
             self.background_subtraction(background_subtraction_ratio, background_masking)
+        # --object-detector-skip-frames (deepdish.py:892-893,929-938,1003-1014): detector + encoder on one step in N + 1 (None: every step)
+        self.object_detector_skip_frames = object_detector_skip_frames
+        if object_detector_skip_frames is not None:
+            check(lib().dd_pipeline_detector_skip_frames(self._h, int(object_detector_skip_frames)), 'dd_pipeline_detector_skip_frames')
 
     def background_subtraction(self, ratio, masking=False):
         """deepdish.py:512,889,957: ratio = --background-subtraction-ratio (reference default 0.25); None or a negative
@@ -153,7 +157,9 @@ class MultiStreamPipeline:
     def step(self, frames_dev, injected=None, frames_next=None):
         """frames_dev: u8 [S, H, W, 3] BGR torch tensor in HBM; injected: pack_injected(...) or None.
         frames_next: the frames of the following step (same shape): their detector run is queued on the
-        detector stream and overlaps this step's NMS / encoder / tracker; the next step() must receive them."""
+        detector stream and overlaps this step's NMS / encoder / tracker; the next step() must receive them.
+        With object_detector_skip_frames, a skip step ignores `injected` (it stands for the detector's output, and the
+        detector does not run), and frames_next is queued only when the next step is a detector step."""
         assert tuple(frames_dev.shape) == (self.S, self.H, self.W, 3)
         assert frames_next is None or tuple(frames_next.shape) == (self.S, self.H, self.W, 3)
         b, sc, cl, off = injected if injected is not None else (None, None, None, None)
@@ -163,7 +169,8 @@ class MultiStreamPipeline:
     def detector_stream(self):
         """The stream the look-ahead detector run is queued on (None without a detector): the consumer to name when acquiring the NEXT
         step's frames from an ingest ring (`ring.frames(slot, stream=pipe.detector_stream())`), so that their upload is waited for by
-        their own detector run and not by this step's kernels."""
+        their own detector run and not by this step's kernels.  A skip step (object_detector_skip_frames) has no detector run: its
+        main stream waits at step entry for what this stream holds, so frames acquired for it are uploaded before MOG2 reads them."""
         h = P()
         check(lib().dd_pipeline_detector_stream(self._h, ctypes.byref(h)), 'dd_pipeline_detector_stream')
         return h if h.value else None
@@ -195,7 +202,8 @@ class MultiStreamPipeline:
 
     def detections(self, stream):
         """The detector adaptor's output for one stream in the last step: what the reference's detect_image(...) returns
-        (tools/ssd_mobilenet.py:198-213) -- (boxes tlwh f64 [n, 4], label names, scores f64 [n])."""
+        (tools/ssd_mobilenet.py:198-213) -- (boxes tlwh f64 [n, 4], label names, scores f64 [n]); on a skip step, the last
+        detector step's."""
         n = ctypes.c_int()
         check(lib().dd_pipeline_detections(self._h, int(stream), None, None, None, 0, ctypes.byref(n)), 'dd_pipeline_detections')
         b, sc, cl = np.zeros((n.value, 4), np.float64), np.zeros(n.value, np.float64), np.zeros(n.value, np.int32)

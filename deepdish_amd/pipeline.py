@@ -73,7 +73,7 @@ class HotPath:
                  nms_max_overlap=0.6, max_iou_distance=0.7, max_age=60, encoder_batch_size=32, num_threads=4,
                  context=None, run_detector=True, disable_background_subtraction=True, background_subtraction_ratio=0.25,
                  enable_background_masking=False, log=None, restore_from_log=False, mqtt_publish=None, mqtt_topic='default/topic',
-                 mqtt_acp_id=None, mqtt_verbosity=1, cpu_temp=None, annotations=None):
+                 mqtt_acp_id=None, mqtt_verbosity=1, cpu_temp=None, annotations=None, object_detector_skip_frames=None):
         self.ctx = context or default_context()
         self.input_size = tuple(input_size)
         # deepdish.py:512,889: the reference defaults to background subtraction ON; its benchmarks (and this class)
@@ -95,6 +95,12 @@ class HotPath:
         self.counter = CountLine(np.asarray(line, dtype=float), self.wanted_labels)
         self.frame_count = 0
         self.timings = {}
+        # --object-detector-skip-frames (deepdish.py:892-893,929-938,1003-1014): the detector and the encoder run on one frame in N + 1,
+        # counted from this object's first step (a restored frame_count does not shift it); the frames between reuse their last results
+        self.object_detector_skip_frames = object_detector_skip_frames
+        self._skip_rem = 0
+        self._prev_objd = None                 # (boxes0, labels0, scores0) of the last detector run
+        self._prev_feats = None                # (device features [rows, 128] or None, rows) of the last encoder run
         # frame records (deepdish.py:613-641): always present upstream, a pass-through unless CVAT annotations are given
         # (--input-cvat-dir; `annotations` = the parsed annotations.xml)
         det_labels = getattr(self.object_detector, 'labels', None) or {i: l for i, l in enumerate(self.wanted_labels)}
@@ -113,7 +119,8 @@ class HotPath:
     def step(self, frame_dev, injected=None, t_frame=None):
         """frame_dev: u8 [H, W, 3] BGR torch tensor in HBM.  injected = (boxes tlwh, labels, scores)
         replaces the detector's OUTPUT (the detector still runs) -- how bench.py feeds synthetic
-        detections, since random weights detect nothing meaningful."""
+        detections, since random weights detect nothing meaningful.  On a frame that object_detector_skip_frames
+        skips there is no detector output to replace: `injected` is ignored, the last detector run's output is used."""
         H, W = int(frame_dev.shape[0]), int(frame_dev.shape[1])
         t0 = time()
         if self.background_subtraction:                                                           # :920-924
@@ -121,12 +128,19 @@ class HotPath:
             self.backSub.apply_device(frame_dev[None], masked_out=masked[None] if masked is not None else None)
             if masked is not None:
                 frame_dev = masked
-        if self.object_detector is not None:
-            boxes0, labels0, scores0 = self.object_detector.detect_frame_device(frame_dev, H, W)   # :883
+        skipped = self._skip_rem > 0 and self._prev_objd is not None                             # :929-938
+        if skipped:
+            boxes0, labels0, scores0 = self._prev_objd
+            self._skip_rem -= 1
         else:
-            boxes0, labels0, scores0 = [], [], []
-        if injected is not None:
-            boxes0, labels0, scores0 = injected
+            if self.object_detector is not None:
+                boxes0, labels0, scores0 = self.object_detector.detect_frame_device(frame_dev, H, W)   # :883
+            else:
+                boxes0, labels0, scores0 = [], [], []
+            if injected is not None:
+                boxes0, labels0, scores0 = injected
+            self._prev_objd = (boxes0, labels0, scores0)
+            self._skip_rem = self.object_detector_skip_frames or 0
         boxes, labels, scores = clean_boxes(boxes0, labels0, scores0, self.input_size[0], self.input_size[1],
                                             (self.backSub, self.background_subtraction_ratio) if self.background_subtraction else None)
         t1 = time()
@@ -141,10 +155,17 @@ class HotPath:
             boxesA1 = np.array(boxes2, dtype=np.float64).reshape(-1, 4)
             scoresA1 = np.array(scores2, dtype=np.float64)
             indices = list(range(len(labels1)))
-        if len(indices):
-            feats_dev, _valid = self.encoder.encode_device(frame_dev, H, W, boxesA1)                    # :1008
+        if skipped:                                                                                     # :1003-1006, 1014
+            feats_dev, rows = self._prev_feats      # zip(): the first min(boxes, rows) boxes pair with the last encoder run's rows
+            n = min(len(boxesA1), rows)
+            boxesA1, labels1, scoresA1 = boxesA1[:n], labels1[:n], scoresA1[:n]
+            feats_dev = feats_dev[:n] if n else None
         else:
-            feats_dev = None
+            if len(indices):
+                feats_dev, _valid = self.encoder.encode_device(frame_dev, H, W, boxesA1)                # :1008
+            else:
+                feats_dev = None
+            self._prev_feats = (feats_dev, len(boxesA1) if feats_dev is not None else 0)
         t2 = time()
         detections = [Detection(b, l, s, _NOFEAT) for b, l, s in zip(boxesA1, labels1, scoresA1)]        # :1014
         self.tracker.predict()                                                                          # :1028
@@ -161,6 +182,8 @@ class HotPath:
         if self.sink is not None:
             self.sink.crossings(events, t0 if t_frame is None else t_frame, self.frame_count)            # :1116-1123
         self.timings = dict(objd=t1 - t0, feat=t2 - t1, trak=t3 - t2, proc=t4 - t3, e2e=t4 - t0)
+        if skipped:                                                                                     # :980, :1019
+            del self.timings['objd'], self.timings['feat']
         return events
 
     def _attach_features(self, detections, feats_dev):

@@ -93,7 +93,8 @@ def initialisation_payload(now, acp_id, hot_path, model, encoder_model, input_na
             'background_subtraction': bs,
             'powersaving': a.get('powersaving'),
             'cpu_governor': a.get('cpu_governor'),
-            'object_detector_skip_frames': a.get('object_detector_skip_frames'),
+            'object_detector_skip_frames': (a['object_detector_skip_frames'] if a.get('object_detector_skip_frames') is not None
+                                            else getattr(hot_path, 'object_detector_skip_frames', None)),
             'interframe_interval': a.get('interframe_interval'),
             'simulate_camera': a.get('simulate_camera')}
 

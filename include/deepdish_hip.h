@@ -354,6 +354,13 @@ int dd_pipeline_detector_adaptor(dd_pipeline *p, int adaptor);
  * Above 16 rows the ORDER of equal-score rows of one class is the reference's only up to its NumPy's unstable sort (tools/ssd_mobilenet.py:73
  * `s.argsort()[::-1]`: stable for <= 16 elements, unspecified beyond) -- INTEGRATION.md, "Ties inside a class". */
 int dd_pipeline_ssd_options(dd_pipeline *p, int max_detections, float nms_score_threshold, float nms_iou_threshold);
+/* --object-detector-skip-frames n (deepdish.py:892-893,929-938,1003-1014): the detector and the encoder run on one step in n + 1 --
+ * steps 0, n + 1, 2 (n + 1), ... counted from the first step; n <= 0 = every step (the default).  A skip step runs no detector chain
+ * (resize, forward, post-process, adaptor tail, host copy), no crops and no encoder: each stream reuses the last detector step's adaptor
+ * output (dd_pipeline_detections returns it; injected detections passed on a skip step are ignored) through this step's box hygiene,
+ * motion test and NMS, and its first min(kept boxes, feature rows of that step) boxes pair with those feature rows in order, as the
+ * reference's zip() does.  Stage events add nothing to objd / feat on a skip step.  Before the first step. */
+int dd_pipeline_detector_skip_frames(dd_pipeline *p, int n);
 /* frames: device u8 [n_streams][H][W][3] BGR.  inj_*: optional detections that REPLACE the detector's
  * output (it still runs): tlwh f64 rows, scores, class ids; stream s owns rows
  * [inj_offsets[s], inj_offsets[s+1]).  Blocks until the step is complete. */
@@ -370,7 +377,9 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames, const uint8_t *fram
 /* The stream the look-ahead detector run of dd_pipeline_step2 is queued on (NULL for a pipeline without a detector).  A caller whose
  * `frames_next` are still on their way to the device hands it to dd_ingest_acquire as the consumer of THAT slot: the upload of frame
  * t + 1 is then waited for by the detector run of frame t + 1 alone, not by step t's own kernels -- the reference's capture thread fills
- * the next frame while the stages work on the current one the same way (deepdish.py:837-878, FreshQueue :192-203). */
+ * the next frame while the stages work on the current one the same way (deepdish.py:837-878, FreshQueue :192-203).  A skip step
+ * (dd_pipeline_detector_skip_frames) has no detector run: its main stream waits at step entry for what this stream holds, so frames
+ * acquired for it are still uploaded before the step's MOG2 update reads them. */
 int dd_pipeline_detector_stream(dd_pipeline *p, void **stream_out);
 /* counts_host: int64 [n_streams][n_wanted][4] = poscount, negcount, intcount, delcount */
 /* Background subtraction for every stream of the pipeline (deepdish.py:512,889,920-924,957): ratio =
