@@ -31,7 +31,7 @@ enum { OP_INPUT = 1, OP_CONV = 2, OP_DWCONV = 3, OP_MAXPOOL = 4, OP_UPSAMPLE = 5
 enum { ACT_NONE = 0, ACT_RELU6 = 1, ACT_ELU = 2, ACT_SILU = 3, ACT_RELU = 4, ACT_SIGMOID = 5 };
 enum { EPI_F16 = 0, EPI_F32 = 1, EPI_SSD_HEAD = 2, EPI_YOLO = 3 };
 // dd_net_op_launches: 0 = the op's own kernel, 1 = no launch (folded into the next op's), else the fused / special kernel
-enum { OPK_DEFAULT = 0, OPK_FOLDED = 1, OPK_POOL_ROWS = 2, OPK_POOL_ROWS_STEM = 3, OPK_RES_UNIT = 4, OPK_SSD_FRONT = 5, OPK_C64_ROWS = 6, OPK_S2_ROWS = 7, OPK_CONV_WS = 8, OPK_WS_DW = 9, OPK_DWPW_ROWS = 10, OPK_SSD_HEAD_DEC = 11, OPK_RES_PAIR = 12, OPK_YOLO_HEAD_DEC = 13, OPK_MARS_WS = 14, OPK_FOLDED_PREV = 15, OPK_MARS_PAIR = 16, OPK_C64_STRIPS = 18, OPK_Q_FRONT = 19, OPK_Q_MID = 20 };   // (17: q_dwm_k, csrc/netsq.hip; 19: q_front_k, csrc/netsq_front.hip; 20: q_mid_k, csrc/netsq_mid.hip)
+enum { OPK_DEFAULT = 0, OPK_FOLDED = 1, OPK_POOL_ROWS = 2, OPK_POOL_ROWS_STEM = 3, OPK_RES_UNIT = 4, OPK_SSD_FRONT = 5, OPK_C64_ROWS = 6, OPK_S2_ROWS = 7, OPK_CONV_WS = 8, OPK_WS_DW = 9, OPK_DWPW_ROWS = 10, OPK_SSD_HEAD_DEC = 11, OPK_RES_PAIR = 12, OPK_YOLO_HEAD_DEC = 13, OPK_MARS_WS = 14, OPK_FOLDED_PREV = 15, OPK_MARS_PAIR = 16, OPK_C64_STRIPS = 18, OPK_Q_FRONT = 19, OPK_Q_MID = 20, OPK_STEM_WIDE = 23 };   // (17, 21, 22: q_dwm_k, q_conv_k<add>, q_add_k, csrc/netsq.hip; 19: q_front_k, csrc/netsq_front.hip; 20: q_mid_k, csrc/netsq_mid.hip)
 enum { DT_F16 = 0, DT_F32 = 1, DT_U8 = 2 };
 
 constexpr int OP_WORDS = 48;       // int32 words per op record (see deepdish_amd/nets.py)
@@ -1427,6 +1427,243 @@ __global__ __launch_bounds__(256, 2) void conv3x3_pool_rows_k(const ConvP P, con
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the look-ahead DMAs of the last rounds
 #endif
+}
+
+// ---------------------------------------------------------------------------------------------------
+// conv3x3_pool_rows_k<STEM> for crops 64 and 128 pixels wide (the 128 x 64 and 256 x 128 MARS encoders): first layer from the u8 crop, 3x3
+// 32->32 layer, ELU and the VALID 3x3 stride-2 max pool in one launch; neither 32-channel full-resolution tensor is written.
+//   * One wave per 32-column strip of a crop, streaming down the rows exactly as the 32-wide kernel does (same k slots, same order bias ->
+//     taps 0..8, activation and f16 rounding on the pooled maximum: the bits of stem_conv3_k + conv3x3_rw_k + maxpool_k).  The strips of a
+//     crop are waves of ONE workgroup: 4 strips of one crop (width 128) or 2 strips of 2 crops (width 64).
+//   * A strip needs first-layer columns -1 and 32 of its own numbering.  They are recomputed: a third first-layer fragment per row whose lanes
+//     0 / 1 make the two columns (a column outside the crop is the second layer's zero padding).  A row slot is [64 even][64 odd][4 left halo]
+//     [4 right halo] chunks of 16 B; the lane of pixel 0 / 31 points its left / right tap at its plane's halo chunk.  (The halo chunks sit at bank
+//     phases 0..7 behind the slot, so the one lane that reads one shares a phase with another lane of its 16: a two-way conflict in two of the four
+//     reads of a row, accepted -- a phase-exact place for eight chunks per slot would cost 6 KB per wave and the second workgroup of the CU.)
+//   * Pooled column 16 s + 15 of strip s reads second-layer column 32 (s + 1): the even fragment of lane 0 of the next strip.  Each round the
+//     lanes fr = 0 leave their 16 raw sums in a double-buffered LDS mailbox, the workgroup meets at one barrier, and lane 15 of the strip to the
+//     left takes them as its third operand of the horizontal maximum (max is exact, so the order of the three does not matter).  The waves of
+//     a workgroup do the same rounds on the same rows, so the barrier costs the spread between four waves, once per 72 MFMAs.
+//   * The row ring has six slots and the crop ring six rows (+ rows 0, 1 a second time), the round loop is unrolled by three: every slot index
+//     is a literal as in the 32-wide kernel, and a wave takes 16.1 KB of LDS, 64.5 KB per workgroup: two workgroups per CU.
+//   * All image and tensor offsets are size_t: the pooled tensor passes 2^31 bytes at crop 17 180 (128 x 64) / 4 194 (256 x 128).
+constexpr int SW_SLOTS = 6, SW_SLOT_HALVES = 1088, SW_CROP_PITCH = 160, SW_CROP_ROWS = 8, SW_MAIL_HALVES = 256;
+// The kernel has not been timed against the three launches it replaces (nor against the parent's): until scripts/time_mars_sizes.py has priced it
+// and its crossover, the default dispatch keeps the three launches and the kernel runs on request (DD_STEM_WIDE=1, from DD_STEM_WIDE_MIN crops).
+constexpr bool STEM_WIDE_DEFAULT = false;
+constexpr int STEM_WIDE_MIN_CROPS = 64;   // an unmeasured placeholder for the crossover
+constexpr int sw_wave_halves() { return SW_SLOTS * SW_SLOT_HALVES + SW_CROP_ROWS * SW_CROP_PITCH + SW_MAIL_HALVES; }
+
+template <int ACT>
+__global__ __launch_bounds__(256, 2) void stem_conv_pool_wide_k(const ConvP P, const int nimg, const int n_units, const int split) {
+    extern __shared__ __attribute__((aligned(16))) _Float16 lds[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fr = lane & 15, fq = lane >> 4;
+    _Float16 *ring = lds + (size_t)wave * sw_wave_halves();
+    _Float16 *crop = ring + SW_SLOTS * SW_SLOT_HALVES;
+    float *mail = reinterpret_cast<float *>(crop + SW_CROP_ROWS * SW_CROP_PITCH);          // [2][4 fq][16]
+    typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+    const h8 zero8 = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+
+    h8 wf[9][2];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+            wf[t][a] = *reinterpret_cast<const h8 *>(P.w + (size_t)rw_weight_row(a, fr) * P.kpad + t * 32 + fq * 8);
+    const f4 bias0 = *reinterpret_cast<const f4 *>(P.bias + fq * 8), bias1 = *reinterpret_cast<const f4 *>(P.bias + fq * 8 + 4);
+    h8 ws[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) ws[a] = *reinterpret_cast<const h8 *>(P.dw_w + rw_weight_row(a, fr) * 32 + fq * 8);
+    const f4 sb0 = *reinterpret_cast<const f4 *>(P.dw_bias + fq * 8), sb1 = *reinterpret_cast<const f4 *>(P.dw_bias + fq * 8 + 4);
+
+    const int ph = P.p[0], pw = P.p[1];
+    const int H = P.H, W = P.W, w3 = W * 3;
+    const int strips = W >> 5, cpw = 4 / strips;                  // 2 or 4 strips per crop, 2 or 1 crops per workgroup
+    const int strip = wave % strips, c0 = strip * 32;
+    const bool halo_l = c0 > 0, halo_r = c0 + 32 < W;             // first-layer columns c0 - 1 / c0 + 32 exist
+    // fragment addresses inside a row slot (halves): B = even[fr], C = odd[fr], A = odd[fr-1], D = even[fr+1]
+    const _Float16 *pB = ring + (fq * 16 + fr) * 8, *pC = pB + 512;
+    const _Float16 *pA = fr ? pC - 8 : ring + (128 + fq) * 8, *pD = fr < 15 ? pB + 8 : ring + (132 + fq) * 8;
+    // crop rows: two per step, one aligned dword per lane; half h of a crop-ring row is byte 96 strip - 8 + h of the image row, so pixel x of
+    // the strip (x = -2 .. 33) starts at half 8 + 3 x
+    const int crow = lane >> 5, cdw = lane & 31;
+    const int cbyte = 96 * strip - 8 + 4 * cdw;
+    const bool col_ok = cdw < 28 && cbyte >= 0 && cbyte < w3;     // an aligned dword lies entirely inside or outside the row (w3 % 4 == 0)
+    const int cx = 5 + 6 * fr;                                    // window start (x - 1) of the even pixel x = 2 fr
+    const _Float16 *gPb = crop + (fq < 3 ? fq : 2) * SW_CROP_PITCH + cx;
+    const _Float16 *gA0 = fq == 3 ? crop + cx + 8 : gPb, *gA1 = fq == 3 ? crop + SW_CROP_PITCH + cx + 7 : gPb, *gA2 = fq == 3 ? crop + 2 * SW_CROP_PITCH + cx + 6 : gPb;
+    const int hx = fr == 1 ? 101 : 2;                             // halo fragment: lane 0 = column -1, lane 1 = column 32 (the others repeat lane 0)
+    const _Float16 *gHb = crop + (fq < 3 ? fq : 2) * SW_CROP_PITCH + hx;
+    const _Float16 *gH0 = fq == 3 ? crop + hx + 8 : gHb, *gH1 = fq == 3 ? crop + SW_CROP_PITCH + hx + 7 : gHb, *gH2 = fq == 3 ? crop + 2 * SW_CROP_PITCH + hx + 6 : gHb;
+    _Float16 *cW = crop + cdw * 4;
+    const float *mail_next = reinterpret_cast<const float *>(reinterpret_cast<const _Float16 *>(mail) + sw_wave_halves()) + fq * 16;   // the next wave's
+    const bool has_next = strip + 1 < strips;
+    // crop-ring columns no row fill reaches are read by the gathers of strips at the crop's edge: zero once
+    for (int i = lane * 8; i < SW_CROP_ROWS * SW_CROP_PITCH; i += 64 * 8) *reinterpret_cast<h8 *>(crop + i) = zero8;
+
+    for (int u = blockIdx.x; u < n_units; u += gridDim.x) {       // unit = pooled rows [j0, j1) of the workgroup's crops
+        const int g = u / split, part = u - g * split;
+        const int j0 = part * ph / split, j1 = (part + 1) * ph / split;
+        const int n_raw = g * cpw + wave / strips;
+        const bool live = n_raw < nimg;                           // a crop past the end: same rounds (the barriers), no stores
+        const int n = live ? n_raw : nimg - 1;
+        const uint8_t *img8 = P.src8 + (size_t)n * H * w3;
+        auto load_raw = [&](int r0) -> unsigned {                 // image rows r0, r0+1 (a select between addresses, not values)
+            const int r = r0 + crow;
+            const bool ok = (unsigned)r < (unsigned)H && col_ok;
+            return *reinterpret_cast<const unsigned *>(ok ? img8 + (size_t)r * w3 + cbyte : reinterpret_cast<const uint8_t *>(P.zero));
+        };
+        auto put_crop = [&](int r0, int row_lo, int row_hi, unsigned raw) {   // normalise image rows r0, r0+1 into crop-ring rows (r + 1) mod 6
+            const int r = r0 + crow;
+            const bool ok = (unsigned)r < (unsigned)H && col_ok;  // outside the image: the zero padding
+            h4 o;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) o[q] = (_Float16)(ok ? ((float)((raw >> (8 * q)) & 255u) - P.in_mean) * P.in_scale : 0.f);
+            const int row = crow ? row_hi : row_lo;
+            if (cdw < 28) {
+                *reinterpret_cast<h4 *>(cW + row * SW_CROP_PITCH) = o;
+                if (row < 2) *reinterpret_cast<h4 *>(cW + (row + 6) * SW_CROP_PITCH) = o;     // rows 0, 1 a second time behind row 5
+            }
+        };
+        auto stem_row = [&](int y, int slot, int c) {             // first-layer row y -> ring slot (y + 1) mod 6 (wave-uniform y); c = y mod 6
+            _Float16 *dst = ring + slot * SW_SLOT_HALVES;
+            if ((unsigned)y >= (unsigned)H) {                     // the second layer's zero padding
+                *reinterpret_cast<h8 *>(dst + lane * 8) = zero8;
+                *reinterpret_cast<h8 *>(dst + 512 + lane * 8) = zero8;
+                if (lane < 8) *reinterpret_cast<h8 *>(dst + 1024 + lane * 8) = zero8;
+                return;
+            }
+            const int co = c * SW_CROP_PITCH;
+#pragma unroll
+            for (int par = 0; par < 3; ++par) {                   // even pixels, odd pixels, the two halo columns
+                h8 xf;
+                if (par < 2) {
+                    xf[0] = gA0[co + 3 * par]; xf[1] = gA1[co + 1 + 3 * par]; xf[2] = gA2[co + 2 + 3 * par];
+#pragma unroll
+                    for (int j = 3; j < 8; ++j) xf[j] = gPb[co + j + 3 * par];
+                } else {
+                    xf[0] = gH0[co]; xf[1] = gH1[co + 1]; xf[2] = gH2[co + 2];
+#pragma unroll
+                    for (int j = 3; j < 8; ++j) xf[j] = gHb[co + j];
+                }
+                const f4 a0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ws[0], xf, sb0, 0, 0, 0);       // onto the bias, as stem_conv3_k
+                const f4 a1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ws[1], xf, sb1, 0, 0, 0);
+                h8 o;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { o[r] = (_Float16)apply_act(a0[r], ACT); o[4 + r] = (_Float16)apply_act(a1[r], ACT); }
+                if (par < 2) *reinterpret_cast<h8 *>(dst + par * 512 + (fq * 16 + fr) * 8) = o;
+                else if (fr < 2) *reinterpret_cast<h8 *>(dst + (128 + fr * 4 + fq) * 8) = (fr ? halo_r : halo_l) ? o : zero8;
+            }
+        };
+        const int kbeg = j0 - 2;                                  // >= -2
+        __syncthreads();                                          // the mailboxes of the previous unit have been read
+        put_crop(2 * j0 - 2, (2 * j0 + 5) % 6, (2 * j0 + 6) % 6, load_raw(2 * j0 - 2));
+        unsigned raw = load_raw(2 * j0);
+        f4 carry[2];
+        _Float16 *out_img = static_cast<_Float16 *>(P.out) + (size_t)n * ph * pw * P.cs_out + P.coff_out + fq * 8;
+        const int pcol = strip * 16 + fr;
+        const bool store = live && pcol < pw;
+        for (int kk = (kbeg + 3) / 3 * 3 - 3; kk <= j1; kk += 3) {
+#pragma unroll
+            for (int kq = 0; kq < 3; ++kq) {
+                const int k = kk + kq;                            // 2 k = 2 kq (mod 6): every slot index below is a literal
+                if (k < kbeg || k > j1) continue;                 // wave-uniform, and the same in every wave of the workgroup
+                // step k makes first-layer rows 2k+3 and 2k+4 (round k+1's new rows) from image rows 2k+2 .. 2k+5
+                if (k < j1) {
+                    put_crop(2 * k + 4, (2 * kq + 5) % 6, (2 * kq + 6) % 6, raw);
+                    raw = load_raw(2 * k + 6);
+                    stem_row(2 * k + 3, (2 * kq + 4) % 6, (2 * kq + 3) % 6);
+                    stem_row(2 * k + 4, (2 * kq + 5) % 6, (2 * kq + 4) % 6);
+                }
+                if (k < j0) continue;
+                f4 acc[2][2][2];                                  // [conv row][parity][channel half], from the bias
+#pragma unroll
+                for (int cr = 0; cr < 2; ++cr)
+#pragma unroll
+                    for (int par = 0; par < 2; ++par) { acc[cr][par][0] = bias0; acc[cr][par][1] = bias1; }
+                h8 X[2][4];
+                auto read_row = [&](int i, h8 (&x)[4]) {
+                    const int so = ((2 * kq + i) % SW_SLOTS) * SW_SLOT_HALVES;          // slot of input row 2k-1+i
+                    x[0] = *reinterpret_cast<const h8 *>(pA + so);
+                    x[1] = *reinterpret_cast<const h8 *>(pB + so);
+                    x[2] = *reinterpret_cast<const h8 *>(pC + so);
+                    x[3] = *reinterpret_cast<const h8 *>(pD + so);
+                };
+                read_row(0, X[0]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    h8 (&x)[4] = X[i & 1];
+#if defined(__HIP_DEVICE_COMPILE__)
+                    __builtin_amdgcn_sched_barrier(0);
+#endif
+                    if (i + 1 < 4) read_row(i + 1, X[(i + 1) & 1]);
+#if defined(__HIP_DEVICE_COMPILE__)
+                    __builtin_amdgcn_sched_barrier(0);
+#endif
+#pragma unroll
+                    for (int dx = 0; dx < 3; ++dx)
+#pragma unroll
+                        for (int cr = 0; cr < 2; ++cr) {
+                            const int dy = i - cr;                // filter row of conv row 2k+cr that meets input row 2k-1+i
+                            if (dy < 0 || dy > 2) continue;
+#pragma unroll
+                            for (int par = 0; par < 2; ++par)
+#pragma unroll
+                                for (int a = 0; a < 2; ++a)
+                                    acc[cr][par][a] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[dy * 3 + dx][a], x[dx + par], acc[cr][par][a], 0, 0, 0);
+                        }
+#if defined(__HIP_DEVICE_COMPILE__)
+                    __builtin_amdgcn_sched_barrier(0);
+#endif
+                }
+                // column 0 of this strip is column 32 of the strip to the left: into the mailbox of this round's parity
+                float *mb = mail + (k & 1) * 64 + fq * 16;
+                if (fr == 0) {
+#pragma unroll
+                    for (int cr = 0; cr < 2; ++cr)
+#pragma unroll
+                        for (int a = 0; a < 2; ++a) *reinterpret_cast<f4 *>(mb + (cr * 2 + a) * 4) = acc[cr][0][a];
+                }
+                __syncthreads();
+                f4 nb[2][2];
+#pragma unroll
+                for (int cr = 0; cr < 2; ++cr)
+#pragma unroll
+                    for (int a = 0; a < 2; ++a) nb[cr][a] = *reinterpret_cast<const f4 *>((has_next ? mail_next : mail + fq * 16) + (k & 1) * 64 + (cr * 2 + a) * 4);
+                // horizontal 3-max of each conv row: x = 2fr, 2fr+1 and 2fr+2 (the even fragment of lane fr+1, or of the next strip's lane 0)
+                f4 hm[2][2];
+#pragma unroll
+                for (int cr = 0; cr < 2; ++cr)
+#pragma unroll
+                    for (int a = 0; a < 2; ++a)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float e = acc[cr][0][a][r];
+                            float nx = e;
+#if defined(__HIP_DEVICE_COMPILE__)
+                            nx = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, e), 0x101 /* row_shl:1 */, 0xf, 0xf, true));
+#endif
+                            if (fr == 15) nx = nb[cr][a][r];      // (the last strip's lane 15 is pooled column pw: never stored)
+                            hm[cr][a][r] = pool_max(pool_max(e, acc[cr][1][a][r]), nx);
+                        }
+                if (k > j0) {                                     // pooled row k-1 = rows 2k-2, 2k-1 (carried) and 2k
+                    h8 pooled;
+#pragma unroll
+                    for (int a = 0; a < 2; ++a)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            pooled[a * 4 + r] = (_Float16)apply_act(pool_max(carry[a][r], hm[0][a][r]), ACT);
+                    if (store) *reinterpret_cast<h8 *>(out_img + ((size_t)(k - 1) * pw + pcol) * P.cs_out) = pooled;
+                }
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) carry[a][r] = pool_max(hm[0][a][r], hm[1][a][r]);
+            }
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -3700,6 +3937,34 @@ bool pool_rows_fusable(const ConvP &P, int nimg) {
            P.pad_t == 1 && P.pad_l == 1 && P.cin == 32 && P.cout == 32 && P.act == ACT_ELU;
 }
 
+// First layer + 3x3 32->32 layer + ELU + VALID 3x3/2 max pool of a 64- or 128-pixel-wide crop as one launch (stem_conv_pool_wide_k).  P = the
+// 3x3 layer with the first layer in src8 / dw_w / dw_bias and the POOLED tensor as its output (P.p[0..1] = pooled height, width).
+bool stem_wide_geometry(int H, int W) { return (W == 64 || W == 128) && H % 2 == 0 && H >= 6; }
+
+int launch_stem_wide(hipStream_t s, ConvP &P, int nimg, int device) {
+    DD_REQUIRE(stem_wide_geometry(P.H, P.W) && P.wo == P.W && P.ho == P.H && P.p[0] == P.H / 2 - 1 && P.p[1] == P.W / 2 - 1 && P.act == ACT_ELU &&
+               P.dw_act == ACT_ELU && !P.res && !P.out2 && P.src8 && (reinterpret_cast<uintptr_t>(P.src8) & 3) == 0, DD_E_ARG,
+               "stem_wide: %d x %d is not a layer pair this launch takes", P.H, P.W);
+    const size_t lds_bytes = (size_t)4 * sw_wave_halves() * sizeof(_Float16);
+    static DevOnce once;
+    const int rc = once.run(device, [&]() -> int {
+        DD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&stem_conv_pool_wide_k<ACT_ELU>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        return DD_OK;
+    });
+    if (rc != DD_OK) return rc;
+    const int strips = P.W / 32, cpw = 4 / strips;
+    const int groups = dd_ceil_div(nimg, cpw);                     // workgroups' worth of crops
+    // few crops: split the rows of a crop over several workgroups (a unit's first two steps only build its rings: ~2 recomputed rounds per extra unit)
+    static const int force_split = getenv("DD_STEM_WIDE_SPLIT") ? atoi(getenv("DD_STEM_WIDE_SPLIT")) : 0;
+    const int split = force_split > 0 ? force_split : groups >= 512 ? 1 : groups >= 256 ? 2 : 4;
+    const long long n_units = (long long)groups * split;
+    DD_REQUIRE(n_units < (1ll << 31), DD_E_CAPACITY, "stem_wide: %lld units", n_units);
+    const int grid = (int)std::min<long long>(n_units, 2 * 256);  // persistent: two workgroups per CU (LDS)
+    hipLaunchKernelGGL((stem_conv_pool_wide_k<ACT_ELU>), dim3((unsigned)grid), dim3(256), lds_bytes, s, P, nimg, (int)n_units, split);
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
 int launch_conv3x3_rw(hipStream_t s, ConvP &P, int nimg, bool pool, int device) {
     if (pool) {                                                  // 8 pooled rows per tile = 17 conv rows, full width
         P.tw = P.wo; P.th = 17; P.tiles_x = 1; P.tiles_y = dd_ceil_div(P.p[0], 8);
@@ -4667,6 +4932,7 @@ static int net_run_ops(dd_net *net, const uint8_t *input, int nimg, hipStream_t 
     net->op_launch.assign((size_t)net->n_ops, OPK_DEFAULT);
     ConvP stem_p;                                                 // a first layer waiting to be folded into the next op's launch
     bool stem_pending = false;
+    bool wide_pending = false, wide_ready = false;               // ... into the launch of the NEXT TWO ops (3x3 layer, then max pool: stem_conv_pool_wide_k, launched at the pool op)
     bool input_pending = false;                                   // a space-to-depth input op waiting to be folded into the 3x3 layer behind it
     float input_mean = 0.f, input_scale = 1.f;
     int input_op = -1;
@@ -4747,6 +5013,7 @@ static int net_run_ops(dd_net *net, const uint8_t *input, int nimg, hipStream_t 
             if (rc != DD_OK) return rc;
             if (ran) { net->op_launch[i] = OPK_FOLDED; net->op_launch[i + 1] = OPK_Q_MID; ++i; continue; }
         }
+        DD_REQUIRE((!wide_pending || kind == OP_CONV) && (!wide_ready || kind == OP_MAXPOOL), DD_E_STATE, "dd_net_forward: op %d does not take the first layer folded into it", i);
         if (pair_pending && kind != OP_CONV) { const int rc = flush_pair(); if (rc != DD_OK) return rc; }
         if (pw_pending && kind != OP_DWCONV) {
             pw_pending = false; net->op_launch[i - 1] = OPK_CONV_WS;
@@ -4902,6 +5169,16 @@ static int net_run_ops(dd_net *net, const uint8_t *input, int nimg, hipStream_t 
                     // whole filter in registers, input patch staged once (see conv3x3_rw_k)
                     if (input_pending) { input_pending = false; P.src8 = input; P.in_mean = input_mean; P.in_scale = input_scale; }
                     if (o[29]) { P.p[0] = td->h; P.p[1] = td->w; }      // fused 3x3/2 max pool: dst is the pooled tensor
+                    if (wide_pending) {                        // first layer + this layer + the max pool behind it: one launch at the pool op (checked at the first layer's op)
+                        wide_pending = false;
+                        const int32_t *r = o + OP_WORDS;
+                        const TensorDesc &tp = net->tensors[r[2]];
+                        P.src8 = stem_p.src8; P.in_mean = stem_p.in_mean; P.in_scale = stem_p.in_scale;
+                        P.dw_w = stem_p.w; P.dw_bias = stem_p.bias; P.dw_act = stem_p.act;
+                        P.out = base(r[2]); P.cs_out = tp.cs; P.coff_out = tp.coff; P.p[0] = tp.h; P.p[1] = tp.w;
+                        stem_p = P; wide_ready = true; net->op_launch[i] = OPK_FOLDED;
+                        break;
+                    }
                     if (stem_pending) {
                         stem_pending = false;
                         if (o[29] && pool_rows_fusable(P, nimg) && stem_p.out == static_cast<const void *>(P.in) && !P.coff_in) {
@@ -5005,6 +5282,33 @@ static int net_run_ops(dd_net *net, const uint8_t *input, int nimg, hipStream_t 
                     stem_p = P; stem_pending = true; net->op_launch[i] = OPK_FOLDED;
                     break;
                 }
+                // widths 64 / 128 (the 128 x 64 and 256 x 128 encoders): the next two ops are the 3x3 layer and its VALID 3x3/2 max pool, each the only
+                // reader of the tensor in front of it (o[30] here; the 3x3 layer's output is looked up in the op list) -- from DD_STEM_WIDE_MIN crops the three run as one launch
+                // (stem_conv_pool_wide_k) and neither full-resolution tensor is written.  DD_STEM_WIDE=1 / 0: the one launch / always the three launches
+                // (default: STEM_WIDE_DEFAULT).  Read on every forward: a test flips them between two forwards of one process.
+                auto sole_reader = [&](int t, int reader) {       // no op but `reader` reads tensor t's buffer, and it is not the network's output
+                    if (t < 0 || t == net->out_tensor) return false;
+                    for (int k = 0; k < net->n_ops; ++k) {
+                        const int32_t *w = net->prog.data() + net->ops_off + (size_t)k * OP_WORDS;
+                        for (int a : {w[1], w[3]})
+                            if (k != reader && a >= 0 && net->tensors[a].buf == net->tensors[t].buf) return false;
+                    }
+                    return true;
+                };
+                const char *wide_env = getenv("DD_STEM_WIDE"), *wide_min_env = getenv("DD_STEM_WIDE_MIN");
+                const bool wide_off = wide_env ? atoi(wide_env) == 0 : !STEM_WIDE_DEFAULT;
+                const int wide_min = wide_min_env ? atoi(wide_min_env) : STEM_WIDE_MIN_CROPS;
+                if (o[30] && !wide_off && nimg >= wide_min && i + 2 < net->n_ops && net->use_rw && stem_wide_geometry(P.H, P.W) && P.stride == 1 &&
+                    P.pad_t == 1 && P.pad_l == 1 && P.cout == 32 && P.act == ACT_ELU && !td->coff && (reinterpret_cast<uintptr_t>(input) & 3) == 0) {
+                    const int32_t *q = o + OP_WORDS, *r = o + 2 * OP_WORDS;
+                    if (q[0] == OP_CONV && q[1] == dst && q[5] == 3 && q[6] == 3 && q[7] == 1 && q[8] == 1 && q[9] == 1 && q[10] == 32 && q[11] == 32 && q[12] == 32 &&
+                        q[14] == ACT_ELU && q[15] == EPI_F16 && q[3] < 0 && q[4] < 0 && !q[29] && !q[30] &&
+                        r[0] == OP_MAXPOOL && r[1] == q[2] && r[5] == 3 && r[6] <= 1 && r[7] == 2 && r[8] == 0 && r[2] >= 0 && sole_reader(q[2], i + 2) &&
+                        net->tensors[r[2]].h == P.H / 2 - 1 && net->tensors[r[2]].w == P.W / 2 - 1 && net->tensors[r[2]].c == 32) {
+                        stem_p = P; wide_pending = true; net->op_launch[i] = OPK_FOLDED;
+                        break;
+                    }
+                }
                 if (o[30] && i + 1 < net->n_ops && P.stride == 2) {       // followed by the first MobileNet block (ssd_front_k)
                     stem_p = P; stem_p.zero = net->d_zero; stem_pending = true; net->op_launch[i] = OPK_FOLDED;
                     break;
@@ -5092,6 +5396,13 @@ static int net_run_ops(dd_net *net, const uint8_t *input, int nimg, hipStream_t 
                 break;
             }
             case OP_MAXPOOL: {
+                if (wide_ready) {                                // the first layer and the 3x3 layer in front of this pool were held back for this launch
+                    wide_ready = false;
+                    const int rc = launch_stem_wide(s, stem_p, nimg, net->ctx->device);
+                    if (rc != DD_OK) return rc;
+                    net->op_launch[i] = OPK_STEM_WIDE;
+                    break;
+                }
                 PoolP P;
                 P.in = reinterpret_cast<const _Float16 *>(base(src)); P.H = ts->h; P.W = ts->w; P.cs_in = ts->cs; P.coff_in = ts->coff;
                 P.k = o[5]; P.stride = o[7]; P.pad = o[8]; P.ho = td->h; P.wo = td->w; P.c = o[12];

@@ -92,7 +92,7 @@ struct dd_pipeline {
     dd_ctx *ctx = nullptr;
     int S = 0, H = 0, W = 0;
     dd_net *det = nullptr, *enc = nullptr;
-    int det_kind = DET_SSD, det_in = 300, det_in_w = 300, n_anchors = 0, n_classes = 0, enc_batch = 0;
+    int det_kind = DET_SSD, det_in = 300, det_in_w = 300, n_anchors = 0, n_classes = 0, enc_batch = 0, enc_h = 64, enc_w = 32;   // enc_h x enc_w: the encoder's crop size (its engine's input)
     int label_offset = 1;                      // class id c is line c + label_offset of the label file (SSD 1, YOLOv5 0)
     float *d_anchors = nullptr;
     double nms_overlap = 0.6, det_conf = 0.5;
@@ -219,6 +219,7 @@ int dd_pipeline_create(dd_ctx *ctx, int n_streams, int frame_h, int frame_w, dd_
     DD_HIP(hipSetDevice(ctx->device));
     int rc;
     if ((rc = dd_net_max_batch(encoder, &p->enc_batch)) != DD_OK) return rc;
+    if ((rc = dd_net_input_size(encoder, &p->enc_h, &p->enc_w)) != DD_OK) return rc;
     if (detector) {
         int db = 0;
         if ((rc = dd_net_max_batch(detector, &db)) != DD_OK) return rc;
@@ -886,7 +887,7 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
         if (!skip) {
             if ((rc = p->h_crop.reserve((size_t)D * 32)) != DD_OK) return rc;
             if ((rc = p->d_crop.reserve((size_t)D * 32)) != DD_OK) return rc;
-            if ((rc = p->d_patches.reserve((size_t)D * 64 * 32 * 3)) != DD_OK) return rc;
+            if ((rc = p->d_patches.reserve((size_t)D * p->enc_h * p->enc_w * 3)) != DD_OK) return rc;
             if ((rc = p->d_feats.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
         }
         int *hc = skip ? nullptr : p->h_crop.as<int>();
@@ -899,7 +900,7 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
                     const int64_t *b = q.ib.data() + (size_t)i * 4;
                     if (hc) {
                         int *c = hc + (size_t)(doff[z] + j) * 8;
-                        ddk::crop_box_host(b, 64, 32, p->H, p->W, c, c + 1, c + 2, c + 3);     // generate_detections.py:63-80
+                        ddk::crop_box_host(b, p->enc_h, p->enc_w, p->H, p->W, c, c + 1, c + 2, c + 3);     // generate_detections.py:63-80
                         c[4] = z; c[5] = c[6] = c[7] = 0;
                     }
                     for (int c4 = 0; c4 < 4; ++c4) tlwh[(size_t)(doff[z] + j) * 4 + c4] = (double)b[c4];
@@ -911,10 +912,10 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
         if (!skip) {
             DD_STAGE_BEGIN(2);
             DD_HIP(hipMemcpyAsync(p->d_crop.p, hc, (size_t)D * 32, hipMemcpyHostToDevice, s));
-            if ((rc = ddk::crop_resize(s, frames, p->H, p->W, p->d_crop.p, D, 64, 32, p->d_patches.as<uint8_t>())) != DD_OK) return rc;
+            if ((rc = ddk::crop_resize(s, frames, p->H, p->W, p->d_crop.p, D, p->enc_h, p->enc_w, p->d_patches.as<uint8_t>())) != DD_OK) return rc;
             for (int a = 0; a < D; a += p->enc_batch) {
                 const int n = std::min(p->enc_batch, D - a);
-                if ((rc = dd_net_forward(p->enc, p->d_patches.as<uint8_t>() + (size_t)a * 64 * 32 * 3, n, s)) != DD_OK) return rc;
+                if ((rc = dd_net_forward(p->enc, p->d_patches.as<uint8_t>() + (size_t)a * p->enc_h * p->enc_w * 3, n, s)) != DD_OK) return rc;
                 if ((rc = dd_net_read(p->enc, -1, n, p->d_feats.as<float>() + (size_t)a * 128, 1, s)) != DD_OK) return rc;
             }
             DD_STAGE_END(2);

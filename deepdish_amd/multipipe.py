@@ -82,10 +82,18 @@ class MultiStreamPipeline:
             ssd_post = ssd_post_options(wd)                         # the post-process op's options as the model file states them
         wd = load_mars_weights(encoder_model)                       # a mars .tflite file on disk goes through tools/tflite_reader.load_mars
         self.enc_weights = wd
-        if tuple(wd.get('__in_hw__', (64, 32))) != (64, 32):
-            raise ValueError('%s takes %s crops: the batched pipeline is built for the 64 x 32 encoder (mars-64x32x3, deepdish.py:505-510)' % (encoder_model, wd['__in_hw__']))
+        self.enc_hw = tuple(int(v) for v in wd.get('__in_hw__', (64, 32)))      # the crop size the weights state (deepdish.py:505-510: ImageEncoder reads it off the graph)
+        if self.enc_hw not in nets.MARS_SIZES:
+            raise ValueError('%s takes %d x %d crops: the batched pipeline runs the 64 x 32, 128 x 64 and 256 x 128 encoders '
+                             '(mars-64x32x3, mars-128x64x3, mars-256x128x3)' % (encoder_model, self.enc_hw[0], self.enc_hw[1]))
+        # crops per encoder forward: the activation arena per crop grows 4.8 x / 19 x with the crop (nets.MARS_ARENA_BYTES_PER_CROP), so the default
+        # shrinks by that much -- the arena stays within what 64 x 32 takes at the same stream count (never below 16 crops).
+        # The pipeline forwards in chunks of this many and the forward is crop-independent: the same bits at any chunk size
+        if not encoder_max_batch:
+            per_crop = nets.MARS_ARENA_BYTES_PER_CROP
+            encoder_max_batch = max(16, max(64, 32 * self.S) * per_crop[(64, 32)] // per_crop[self.enc_hw])
         # the pipeline never reads an intermediate encoder tensor: its activation buffers share memory by lifetime (6.2 -> ~2 GB at 12 288 crops)
-        self.enc = Net(nets.compile_mars(wd), max_batch=encoder_max_batch or max(64, 32 * self.S), context=self.ctx,
+        self.enc = Net(nets.compile_mars(wd, *self.enc_hw), max_batch=encoder_max_batch, context=self.ctx,
                        shared=os.environ.get('DD_NET_SHARED', '1') != '0')
         # latency mode: with a handful of streams a forward is a train of 20-75 kernels of a few microseconds each;
         # replaying it as one hipGraph takes the per-launch host cost out of the frame latency (DD_GRAPH=0/1 overrides)

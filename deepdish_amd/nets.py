@@ -373,10 +373,21 @@ MARS_BLOCKS = [('conv2_1', 32, False, True), ('conv2_3', 32, False, False), ('co
                ('conv3_3', 64, False, False), ('conv4_1', 128, True, False), ('conv4_3', 128, False, False)]
 
 
-def synthetic_mars_weights(seed=1234):
-    """Seeded weights with the variable names/shapes of tools/freeze_model.py:88-157."""
+MARS_SIZES = ((64, 32), (128, 64), (256, 128))      # the crop sizes of the encoders the reference ships (encoders/mars-*.pb)
+# activation arena of the encoder engine per crop, buffers overlaid by lifetime (dd_net_create_shared): at 64 x 32 conv1_1
+# (128 KB) beside the pooled tensor and conv2_1's, at the larger sizes the two full-resolution tensors of the three-launch front
+MARS_ARENA_BYTES_PER_CROP = {(64, 32): 220352, (128, 64): 1048576, (256, 128): 4194304}
+
+
+def synthetic_mars_weights(seed=1234, in_hw=(64, 32)):
+    """Seeded weights with the variable names/shapes of tools/freeze_model.py:88-157.  in_hw: the crop size (h, w), multiples of 8; every
+    array is drawn in the same order at any size, only fc1 (h/8 * w/8 * 128 rows) differs in shape.  Sizes other than 64 x 32 state
+    theirs under '__in_hw__' (what a model file's `images` placeholder states)."""
     rng = np.random.default_rng(seed)
     wd = {}
+    h, w = (int(v) for v in in_hw)
+    assert h % 8 == 0 and w % 8 == 0 and h > 0 and w > 0
+    fc_k = (h // 8) * (w // 8) * 128
 
     def conv(scope, kh, cin, cout, gain=1.0, bias=False, bn=True):
         wd[scope + '/weights'] = (rng.standard_normal((kh, kh, cin, cout)) * gain * math.sqrt(2.0 / (kh * kh * cin))).astype(np.float32)
@@ -401,14 +412,22 @@ def synthetic_mars_weights(seed=1234):
         if inc:
             wd[name + '/projection/weights'] = (rng.standard_normal((1, 1, cin, c)) * math.sqrt(1.0 / cin)).astype(np.float32)
         cin = c
-    wd['fc1/weights'] = (rng.standard_normal((4096, 128)) * math.sqrt(2.0 / 4096)).astype(np.float32)
+    wd['fc1/weights'] = (rng.standard_normal((fc_k, 128)) * math.sqrt(2.0 / fc_k)).astype(np.float32)
     bnp('fc1/bn', 128)
     bnp('ball', 128)
+    if (h, w) != (64, 32):
+        wd['__in_hw__'] = (h, w)
     return wd
 
 
 def compile_mars(wd, in_h=64, in_w=32):
-    """tools/freeze_model.py:88-157 as an op program; input u8 BGR [n,64,32,3] -> f32 [n,128]."""
+    """tools/freeze_model.py:88-157 as an op program; input u8 BGR [n,in_h,in_w,3] -> f32 [n,128].  The reference ships the network at three
+    crop sizes (64 x 32, 128 x 64, 256 x 128: MARS_SIZES); any size whose fc1 has (in_h/8)(in_w/8)128 rows compiles.
+    Front of the network: at width 32 conv1_1 is marked foldable and conv1_2 carries the pool (conv3x3_pool_rows_k<STEM>, one launch).  At widths
+    64 and 128 the three ops stay in the program -- conv1_1 (marked foldable), conv1_2, the max pool -- and
+    the engine runs them as three launches by default and as one (stem_conv_pool_wide_k) with DD_STEM_WIDE=1 from DD_STEM_WIDE_MIN crops (the
+    kernel is bit-identical but not timed yet); the two
+    full-resolution tensors keep their place in the arena for that path.  conv2_x .. conv4_x run on the generic kernels at the larger sizes."""
     P = Program(in_h, in_w)
     w, b = fold_conv_bn(wd, 'conv1_1')
     x = c11 = P.stem(w, b, 1, ACT_ELU, swap_rb=bool(wd.get('__swap_rb__', True)))   # :175-177 BGR -> RGB, :101-105 (a .tflite graph says whether it reverses the channels)
@@ -417,8 +436,10 @@ def compile_mars(wd, in_h=64, in_w=32):
     w, b = fold_conv_bn(wd, 'conv1_2')
     if in_w == 32:
         x = pool = P.conv(x, w, b, act=ACT_ELU, pool=True)                     # :106-110 + :116 VALID pool, one launch (the fused kernel is 32 wide)
-    else:                                                                      # other crop sizes (mars-small128.pb: 128 x 64): pool as its own op
-        P.ops[-1][30] = 0
+    else:                                                                      # other crop sizes: the pool as its own op
+        wide = Program.STEM_POOL_FUSE and in_w in (64, 128) and in_h % 2 == 0   # stem_conv_pool_wide_k takes the three ops
+        if not wide:
+            P.ops[-1][30] = 0
         x = pool = P.maxpool(P.conv(x, w, b, act=ACT_ELU), 3, 2, 0)
     raw, pre = x, x                  # raw = block input (skip path), pre = what conv "1" reads
     for i, (name, c, inc, first) in enumerate(MARS_BLOCKS):

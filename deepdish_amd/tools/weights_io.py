@@ -41,7 +41,8 @@ def load_named_weights(model_file, synthetic_fn):
 
 def load_mars_weights(model_file):
     """What the encoder constructors call: a `.tflite` file on disk goes through tools/tflite_reader.load_mars (the reference's
-    `mars-64x32x3.tflite`, generate_detections.py:151-162), anything else through load_named_weights."""
+    `mars-64x32x3.tflite`, generate_detections.py:151-162), anything else through load_named_weights.  A synthetic name that holds
+    `128x64` or `256x128` (synthetic-mars-128x64x3) yields the weights of that crop size, with the size under '__in_hw__'."""
     from .. import nets
     name = str(model_file)
     if name.endswith('.tflite') and os.path.exists(name):
@@ -50,7 +51,9 @@ def load_mars_weights(model_file):
     if name.endswith('.pb') and os.path.exists(name):            # a frozen graph (generate_detections.py:118-148,187-189: ImageEncoder)
         from . import graphdef
         return graphdef.load_mars(name)[0]                       # '__in_hw__' carries the crop size its placeholder states
-    return load_named_weights(model_file, nets.synthetic_mars_weights)
+    # a synthetic name states the crop size the way the reference's files do (mars-128x64x3, mars-256x128x3); none stated: 64 x 32
+    in_hw = (128, 64) if '128x64' in name else (256, 128) if '256x128' in name else (64, 32)
+    return load_named_weights(model_file, lambda seed: nets.synthetic_mars_weights(seed, in_hw))
 
 
 def load_yolov5_weights(model_file):

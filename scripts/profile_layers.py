@@ -21,12 +21,15 @@ elif kind == 'ssd_v2_i8':                                                # the u
     prog = netsq.compile_ssd_mobilenet_quant(quantize.synthetic_ssd_v2_quant_model()); shape = (300, 300)
 elif kind == 'mars':
     prog = nets.compile_mars(nets.synthetic_mars_weights()); shape = (64, 32)
+elif kind.startswith('mars-'):                                           # mars-128x64, mars-256x128: the larger encoders the reference ships
+    shape = tuple(int(v) for v in kind[5:].split('x')[:2])
+    prog = nets.compile_mars(nets.synthetic_mars_weights(1234, shape), *shape)
 else:
     prog = nets.compile_yolov5s(nets.synthetic_yolov5s_weights()); shape = (640, 640)
 net = Net(prog, max_batch=batch)
 if kind.startswith('ssd') and os.environ.get('DD_SSD_DEC', '1') != '0':      # as the pipeline runs it: the heads decode in their epilogue
     net.ssd_decode(prog.meta['anchors'], 1e-8)
-if kind not in ('ssd', 'ssd_i8', 'ssd_i8_sym', 'ssd_v2_i8', 'mars') and os.environ.get('DD_YOLO_DEC', '1') != '0':      # as the pipeline runs it: the Detect heads reduce their rows
+if kind not in ('ssd', 'ssd_i8', 'ssd_i8_sym', 'ssd_v2_i8') and not kind.startswith('mars') and os.environ.get('DD_YOLO_DEC', '1') != '0':      # as the pipeline runs it: the Detect heads reduce their rows
     net.yolo_decode(True)
 x = torch.randint(0, 256, (batch,) + shape + (3,), dtype=torch.uint8, device='cuda')
 check(lib().dd_net_profile(net._h, 1))
