@@ -31,11 +31,13 @@ SIGNATURES = {
     'dd_kf_gate': [P, P, P, P, c_int, P, c_int, c_int, P, P],
     'dd_iou_cost': [P, P, P, c_int, P, c_int, P, P],
     'dd_cosine_nn_cost': [P, P, P, c_int, P, c_int, P, P],
+    'dd_euclidean_nn_cost': [P, P, P, c_int, P, c_int, P, P],
     'dd_nms': [P, P, P, c_int, c_double, P, P, P],
     'dd_nms_ssd': [P, P, P, c_int, c_double, P, P, P],
     'dd_lsap_host': [P, c_int, c_int, P, P],
     'dd_pyset_difference_order_host': [P, c_int, P, c_int, P, POINTER(c_int)],
     'dd_tracker_create': [P, c_double, c_double, c_int, c_int, c_int, c_int, c_int, POINTER(P)],
+    'dd_tracker_create_metric': [P, c_int, c_double, c_double, c_int, c_int, c_int, c_int, c_int, POINTER(P)],
     'dd_tracker_destroy': [P],
     'dd_tracker_predict': [P],
     'dd_tracker_update': [P, P, P, c_int, c_int],
@@ -98,6 +100,7 @@ SIGNATURES = {
     'dd_pipeline_detector_adaptor': [P, c_int],
     'dd_pipeline_ssd_options': [P, c_int, c_float, c_float],
     'dd_pipeline_detector_skip_frames': [P, c_int],
+    'dd_pipeline_metric': [P, c_int],
     'dd_pipeline_step': [P, P, P, P, P, P],
     'dd_pipeline_step2': [P, P, P, P, P, P, P],
     'dd_pipeline_background_subtraction': [P, c_double, c_int],

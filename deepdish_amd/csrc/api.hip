@@ -127,20 +127,21 @@ int dd_iou_cost(dd_ctx *ctx, const double *tlwh_t, const int *tsu, int n_t, cons
     return ddk::iou_cost(dd_pick_stream(ctx, stream), tlwh_t, tsu, n_t, tlwh_d, n_d, out);
 }
 
-int dd_cosine_nn_cost(dd_ctx *ctx, const float *gallery, const int *offsets_host, int n_t, const float *feats,
-                      int n_d, double *out, void *stream) {
-    DD_REQUIRE(ctx && n_t >= 0 && n_d >= 0, DD_E_ARG, "dd_cosine_nn_cost: bad argument");
+// Shared host side of dd_cosine_nn_cost / dd_euclidean_nn_cost: per-target row ranges to the device, then the metric's launch.
+static int nn_cost_common(dd_ctx *ctx, const float *gallery, const int *offsets_host, int n_t, const float *feats, int n_d,
+                          double *out, void *stream, bool euclidean, const char *who) {
+    DD_REQUIRE(ctx && n_t >= 0 && n_d >= 0, DD_E_ARG, "%s: bad argument", who);
     DD_DEVICE(ctx);
     if (n_t == 0 || n_d == 0) return DD_OK;
-    DD_REQUIRE(gallery && offsets_host && feats && out, DD_E_ARG, "dd_cosine_nn_cost: NULL argument");
+    DD_REQUIRE(gallery && offsets_host && feats && out, DD_E_ARG, "%s: NULL argument", who);
     hipStream_t s = dd_pick_stream(ctx, stream);
     const int g = offsets_host[n_t];
     for (int t = 0; t < n_t; ++t)
-        DD_REQUIRE(offsets_host[t + 1] > offsets_host[t], DD_E_ARG, "dd_cosine_nn_cost: target %d has no samples", t);
+        DD_REQUIRE(offsets_host[t + 1] > offsets_host[t], DD_E_ARG, "%s: target %d has no samples", who, t);
     int rc;
     const size_t nbytes = ((size_t)g + n_d) * 128 * sizeof(float);
     const size_t ibytes = (size_t)n_t * (sizeof(long long) + sizeof(int));
-    if ((rc = ctx->scratch[0].reserve(nbytes)) != DD_OK) return rc;
+    if (!euclidean && (rc = ctx->scratch[0].reserve(nbytes)) != DD_OK) return rc;
     if ((rc = ctx->scratch[1].reserve(ibytes)) != DD_OK) return rc;
     if ((rc = ctx->pin[0].reserve(ibytes)) != DD_OK) return rc;
     long long *h_start = ctx->pin[0].as<long long>();
@@ -150,12 +151,23 @@ int dd_cosine_nn_cost(dd_ctx *ctx, const float *gallery, const int *offsets_host
         h_count[t] = offsets_host[t + 1] - offsets_host[t];
     }
     if ((rc = upload(ctx, s, ctx->scratch[1].p, h_start, ibytes)) != DD_OK) return rc;
+    const long long *d_start = ctx->scratch[1].as<long long>();
+    const int *d_count = reinterpret_cast<const int *>(d_start + n_t);
+    if (euclidean) return ddk::euclidean_nn_cost(s, gallery, d_start, d_count, n_t, feats, n_d, out, n_d);   // raw rows, no copy
     float *gal_n = ctx->scratch[0].as<float>(), *feat_n = gal_n + (size_t)g * 128;
     if ((rc = ddk::normalize_rows(s, gallery, gal_n, g)) != DD_OK) return rc;
     if ((rc = ddk::normalize_rows(s, feats, feat_n, n_d)) != DD_OK) return rc;
-    const long long *d_start = ctx->scratch[1].as<long long>();
-    const int *d_count = reinterpret_cast<const int *>(d_start + n_t);
     return ddk::cosine_nn_cost(s, gal_n, d_start, d_count, n_t, feat_n, n_d, out, n_d);
+}
+
+int dd_cosine_nn_cost(dd_ctx *ctx, const float *gallery, const int *offsets_host, int n_t, const float *feats,
+                      int n_d, double *out, void *stream) {
+    return nn_cost_common(ctx, gallery, offsets_host, n_t, feats, n_d, out, stream, false, "dd_cosine_nn_cost");
+}
+
+int dd_euclidean_nn_cost(dd_ctx *ctx, const float *gallery, const int *offsets_host, int n_t, const float *feats,
+                         int n_d, double *out, void *stream) {
+    return nn_cost_common(ctx, gallery, offsets_host, n_t, feats, n_d, out, stream, true, "dd_euclidean_nn_cost");
 }
 
 static int nms_common(dd_ctx *ctx, const double *boxes, const double *keys, int k, double thr, int mode,

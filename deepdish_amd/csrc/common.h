@@ -131,6 +131,8 @@ int normalize_rows(hipStream_t s, const float *in, float *out, int n);   // rows
 // gallery rows are pre-normalised; target t owns rows [row_start[t], row_start[t]+row_count[t])
 int cosine_nn_cost(hipStream_t s, const float *gallery_n, const long long *row_start, const int *row_count,
                    int n_t, const float *feats_n, int n_d, double *out, int ld_out);
+int euclidean_nn_cost(hipStream_t s, const float *gallery, const long long *row_start, const int *row_count,
+                      int n_t, const float *feats, int n_d, double *out, int ld_out);   // rows NOT normalised
 int nms(hipStream_t s, const double *boxes, const double *keys, int k, double thr, int mode,
         int *out_idx, int *out_n, void *scratch, size_t scratch_bytes);
 size_t nms_scratch_bytes(int k);

@@ -1,7 +1,7 @@
-// Association cost matrices: IoU (f64) and nearest-neighbour cosine appearance cost (f32 -> f64).
+// Association cost matrices: IoU (f64) and nearest-neighbour cosine / euclidean appearance cost (f32 -> f64).
 //
-// Reference (upstream paths): deep_sort/iou_matching.py:7-81, deep_sort/nn_matching.py:31-54,
-// 78-96, 156-177.  The cosine cost is a [G_t x 128] . [128 x D] contraction per target followed by
+// Reference (upstream paths): deep_sort/iou_matching.py:7-81, deep_sort/nn_matching.py:5-28, 31-54,
+// 57-96, 156-177.  The cosine cost is a [G_t x 128] . [128 x D] contraction per target followed by
 // a column min; it runs on the exact-f32 MFMA (v_mfma_f32_16x16x4_f32, a k-ordered fmaf chain)
 // so the values stay f32-faithful to the reference's float32 GEMM.
 #include "common.h"
@@ -51,6 +51,19 @@ __global__ __launch_bounds__(256) void cosine_nn_k(const float *__restrict__ gal
     if ((lane >> 4) == 0 && d0 + c < n_d) out[(size_t)t * ld_out + d0 + c] = (double)(1.0f - best);
 }
 
+// Same grid and wave layout as cosine_nn_k on un-normalised rows: min squared euclidean distance (nn_matching.py:57-75).
+__global__ __launch_bounds__(256) void euclidean_nn_k(const float *__restrict__ gal, const long long *__restrict__ row_start,
+                                                      const int *__restrict__ row_count, const float *__restrict__ feats,
+                                                      int n_d, double *__restrict__ out, int ld_out) {
+    const int t = blockIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int d0 = blockIdx.y * 64 + wave * 16;
+    if (d0 >= n_d) return;                                    // wave-uniform, no barriers below
+    const float best = nn_min_sqdist(FlatRows{gal + (size_t)row_start[t] * 128}, row_count[t], feats, d0, n_d, lane);
+    const int c = lane & 15;
+    if ((lane >> 4) == 0 && d0 + c < n_d) out[(size_t)t * ld_out + d0 + c] = (double)best;
+}
+
 }  // namespace
 
 namespace ddk {
@@ -75,6 +88,15 @@ int cosine_nn_cost(hipStream_t s, const float *gallery_n, const long long *row_s
     if (n_t <= 0 || n_d <= 0) return DD_OK;
     hipLaunchKernelGGL(cosine_nn_k, dim3(n_t, dd_ceil_div(n_d, 64)), dim3(256), 0, s, gallery_n, row_start, row_count,
                        feats_n, n_d, out, ld_out);
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
+int euclidean_nn_cost(hipStream_t s, const float *gallery, const long long *row_start, const int *row_count,
+                      int n_t, const float *feats, int n_d, double *out, int ld_out) {
+    if (n_t <= 0 || n_d <= 0) return DD_OK;
+    hipLaunchKernelGGL(euclidean_nn_k, dim3(n_t, dd_ceil_div(n_d, 64)), dim3(256), 0, s, gallery, row_start, row_count,
+                       feats, n_d, out, ld_out);
     DD_LAUNCH_CHECK();
     return DD_OK;
 }

@@ -75,4 +75,52 @@ __device__ __forceinline__ float nn_max_dot(const Rows rows, int count,
     return best;
 }
 
+// min over `count` gallery rows of max(0, |row[g]|^2 + |feats[d]|^2 - 2 <row[g], feats[d]>) for the 16 detections
+// d0..d0+15 of this wave, all f32 (deep_sort/nn_matching.py:5-28 _pdist, :57-75 _nn_euclidean_distance); operands are
+// NOT normalised.  Same sweep as nn_max_dot: 16 rows per tile through the MFMA, last partial tile clamped.  The squared
+// norms ride on the fragments the lanes already hold -- no second pass over HBM, no norms kept in the gallery: lane
+// (c, q) sums the squares of its 32 elements of query d0 + c (once) and of row g + c (per tile), the four q add up
+// across the wave; D[reg] of lane (c, q) is row 4 q + reg, whose norm sits in the lanes with lane & 15 == 4 q + reg.
+template <class Rows>
+__device__ __forceinline__ float nn_min_sqdist(const Rows rows, int count,
+                                               const float *__restrict__ feats, int d0, int n_d, int lane) {
+    const int c = lane & 15, q = lane >> 4;
+    const int dd = min(d0 + c, n_d - 1);
+    f32x4 b[8];
+    const float *fp = feats + (size_t)dd * 128 + 4 * q;
+    f32x4 b2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        b[s] = *reinterpret_cast<const f32x4 *>(fp + 16 * s);
+        b2 += b[s] * b[s];
+    }
+    float qn = (b2[0] + b2[1]) + (b2[2] + b2[3]);
+    qn += __shfl_xor(qn, 16, 64);
+    qn += __shfl_xor(qn, 32, 64);                            // |feats[d0 + c]|^2 in every q
+    float best = __builtin_inff();
+    for (int g = 0; g < count; g += 16) {
+        const int r = min(g + c, count - 1);                 // clamp: a repeated row cannot change the min
+        const float *ap = rows.row(r) + 4 * q;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, a2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const f32x4 a = *reinterpret_cast<const f32x4 *>(ap + 16 * s);
+            a2 += a * a;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[s][j], acc, 0, 0, 0);
+        }
+        float rn = (a2[0] + a2[1]) + (a2[2] + a2[3]);
+        rn += __shfl_xor(rn, 16, 64);
+        rn += __shfl_xor(rn, 32, 64);                        // |row[g + c]|^2 in every q
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float gn = __shfl(rn, 4 * q + j, 64);
+            best = fminf(best, fmaxf(0.f, (-2.f * acc[j] + gn) + qn));   // nn_matching.py:26-27
+        }
+    }
+    best = fminf(best, __shfl_xor(best, 16, 64));
+    best = fminf(best, __shfl_xor(best, 32, 64));
+    return best;
+}
+
 }  // namespace costdev

@@ -34,6 +34,7 @@ int ssd_finish(hipStream_t s, const float *boxes, const float *cls, const float 
                double iou_thr, double img_w, double img_h, double *out_boxes, int *out_cls, double *out_scores, int *out_n);
 int tracker_group_create(dd_ctx *ctx, int n, double max_cos, double max_iou, int max_age, int n_init, int budget, int tcap,
                          int gcap, dd_tracker **out);
+int tracker_group_set_metric(dd_tracker *any, int metric);
 int trackers_predict(dd_tracker **ts, int S);
 int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const float *feats, int feats_on_device,
                           const int *det_off);
@@ -358,6 +359,17 @@ int dd_pipeline_detector_skip_frames(dd_pipeline *p, int n) {
     p->skip_n = n;
     p->skip_rem = 0;
     return DD_OK;
+}
+
+// NearestNeighborDistanceMetric("euclidean", ...) for the pipeline's tracker group (nn_matching.py:5-28,57-75,126-132): metric 0 =
+// cosine (the default, deepdish.py:515-516), 1 = euclidean -- the encoder's rows are then associated and stored as they come, and the
+// max_cosine_distance given to dd_pipeline_create is the matching_threshold on the squared distance, as the reference passes
+// --max-cosine-distance for either metric.  Call before the first step.
+int dd_pipeline_metric(dd_pipeline *p, int metric) {
+    DD_REQUIRE(p, DD_E_ARG, "dd_pipeline_metric: NULL pipeline");
+    DD_REQUIRE(metric == 0 || metric == 1, DD_E_ARG, "dd_pipeline_metric: metric must be 0 (cosine) or 1 (euclidean), got %d", metric);
+    DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, "dd_pipeline_metric: call before the first step");
+    return ddk::tracker_group_set_metric(p->trks[0], metric);
 }
 
 // deepdish.py:512,889: background subtraction on (ratio = --background-subtraction-ratio, default 0.25) or off

@@ -8,16 +8,16 @@
 // of one): per step the device does a handful of launches for ALL streams together and the host
 // two round trips:
 //   predict : 1 kernel over every live track of every stream
-//   update  : normalise all detection features (1 launch);
-//             K1 "assoc"  -- for every (track row, detection of the SAME stream): gated cosine NN cost
-//                            (exact-f32 MFMA + f64 Mahalanobis gate) and the IoU cost, ALL cascade
+//   update  : normalise all detection features (1 launch; the euclidean metric keeps them raw: a plain copy);
+//             K1 "assoc"  -- for every (track row, detection of the SAME stream): gated cosine (or squared euclidean)
+//                            NN cost (exact-f32 MFMA + f64 Mahalanobis gate) and the IoU cost, ALL cascade
 //                            levels at once (the cost of a pair does not depend on the level);
 //             host        -- per stream: matching cascade + LSAP on the small cost matrices;
 //             K2 "apply"  -- Kalman update / initiate + gallery append for the decided pairs;
 //             gather      -- means of all live / just-deleted tracks back to the host.
 // Layout: means[slot][8] f64, covs[slot][64] f64; a stream owns the slot range [slot_base, slot_base + tcap) of
 // a pool, slots recycled through a per-stream free list.  Appearance gallery: rows of 128 f32 (already
-// L2-normalised) in 32-row chunks drawn from 64 MiB arenas shared by the group; a track owns a chunk LIST (device
+// L2-normalised under the cosine metric, as the encoder produced them under the euclidean one) in 32-row chunks drawn from 64 MiB arenas shared by the group; a track owns a chunk LIST (device
 // table tab[slot][stride]), extended whenever the track is matched -- nn_budget=None upstream keeps every sample
 // (deepdish.py:515, nn_matching.py:137-154), so a gallery has no fixed capacity here either; with nn_budget = B
 // the last B samples are kept (a ring over ceil(B / 32) chunks).  Chunks return to the pool with the track's slot.
@@ -36,6 +36,7 @@ using namespace costdev;
 constexpr double GATE_4DOF = 9.4877;      // kalman_filter.py:14
 constexpr double INFTY_COST = 1e5;        // linear_assignment.py:8
 enum { TENTATIVE = 1, CONFIRMED = 2, DELETED = 3 };   // track.py:15-17
+enum { METRIC_COSINE = 0, METRIC_EUCLIDEAN = 1 };     // nn_matching.py:126-132
 
 // detection.py:43-50
 __device__ __forceinline__ void tlwh_to_xyah(const double *b, double z[4]) {
@@ -46,7 +47,9 @@ __device__ __forceinline__ void tlwh_to_xyah(const double *b, double z[4]) {
 }
 
 // grid (R rows of all streams, ceil(max n_det / 64)); 4 waves, 16 detections per wave.  Row r belongs to
-// one stream and sees only that stream's detections [det_off, det_off + n_det).
+// one stream and sees only that stream's detections [det_off, det_off + n_det).  Metric: the appearance half --
+// METRIC_COSINE 1 - max dot of normalised rows, METRIC_EUCLIDEAN min squared distance of raw rows; gate and IoU half are shared.
+template <int Metric>
 __global__ __launch_bounds__(256) void tracker_assoc_k(
     const double *__restrict__ means, const double *__restrict__ covs, float *const *__restrict__ arenas,
     const int *__restrict__ tab, int tab_stride, const int *__restrict__ row_slot, const int *__restrict__ row_state,
@@ -62,9 +65,14 @@ __global__ __launch_bounds__(256) void tracker_assoc_k(
     const int det_off = row_det_off[row];
     const bool confirmed = row_state[row] == CONFIRMED;
     float best = 0.f;
-    if (confirmed)                                            // wave-uniform branch around the MFMAs
-        best = nn_max_dot(ChunkRows{arenas, tab + (size_t)slot * tab_stride}, row_gcount[row],
-                          feats_n + (size_t)det_off * 128, d0, n_det, lane);
+    if (confirmed) {                                          // wave-uniform branch around the MFMAs
+        if constexpr (Metric == METRIC_EUCLIDEAN)
+            best = nn_min_sqdist(ChunkRows{arenas, tab + (size_t)slot * tab_stride}, row_gcount[row],
+                                 feats_n + (size_t)det_off * 128, d0, n_det, lane);
+        else
+            best = nn_max_dot(ChunkRows{arenas, tab + (size_t)slot * tab_stride}, row_gcount[row],
+                              feats_n + (size_t)det_off * 128, d0, n_det, lane);
+    }
     const int d = d0 + (lane & 15);
     if ((lane >> 4) != 0 || d >= n_det) return;
     const double *m = means + (size_t)slot * 8;
@@ -77,7 +85,8 @@ __global__ __launch_bounds__(256) void tracker_assoc_k(
         tlwh_to_xyah(b, z);
         const double mm[4] = {m[0], m[1], m[2], m[3]};
         const double d2 = maha2(c, mm, z, 0);
-        cost[o] = d2 > GATE_4DOF ? INFTY_COST : (double)(1.0f - best);   // linear_assignment.py:181-189
+        if constexpr (Metric == METRIC_EUCLIDEAN) cost[o] = d2 > GATE_4DOF ? INFTY_COST : (double)best;
+        else cost[o] = d2 > GATE_4DOF ? INFTY_COST : (double)(1.0f - best);   // linear_assignment.py:181-189
     }
     double ci = INFTY_COST;                                   // iou_matching.py:74-76
     if (row_tsu[row] <= 1) {
@@ -128,6 +137,7 @@ constexpr int GAL_MAX_ARENAS = 4096;                      // x 64 MiB = 256 GiB:
 struct TrackerPool {
     dd_ctx *ctx = nullptr;
     int slots = 0, refs = 0;
+    int metric = 0;                                       // METRIC_*: one per group; d_feats_n then holds normalised / raw rows
     double *d_means = nullptr, *d_covs = nullptr;
     // gallery: arenas of GAL_ARENA_CHUNKS chunks, per-slot chunk lists (host) mirrored in d_tab[slot][tab_stride]
     std::vector<float *> arenas;
@@ -344,6 +354,17 @@ int tracker_group_create(dd_ctx *ctx, int n, double max_cos, double max_iou, int
     return DD_OK;
 }
 
+// nn_matching.py:126-132: the metric of the whole group (its trackers share the gallery and the association launch).  Only while the
+// group has seen no detection: the gallery rows of the two metrics are not interchangeable.
+int tracker_group_set_metric(dd_tracker *any, int metric) {
+    DD_REQUIRE(any && (metric == METRIC_COSINE || metric == METRIC_EUCLIDEAN), DD_E_ARG,
+               "tracker metric must be 0 (cosine) or 1 (euclidean), got %d", metric);
+    TrackerPool *p = any->pool;
+    DD_REQUIRE(p->arenas.empty() || p->metric == metric, DD_E_STATE, "tracker metric: the group already holds gallery rows");
+    p->metric = metric;
+    return DD_OK;
+}
+
 // tracker.py:51-57 + track.py:113-125 for every tracker of the group: one copy, one launch, no sync.
 int trackers_predict(dd_tracker **ts, int S) {
     if (S <= 0) return DD_OK;
@@ -429,19 +450,26 @@ int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const
     }
     char *d = p->d_in.as<char>();
     DD_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
-    const float *raw = feats;
-    if (!feats_on_device) {
-        if ((rc = p->d_feats_raw.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
-        DD_HIP(hipMemcpyAsync(p->d_feats_raw.p, feats, (size_t)D * 128 * sizeof(float), hipMemcpyHostToDevice, s));
-        raw = p->d_feats_raw.as<float>();
-    }
+    const bool euclid = p->metric == METRIC_EUCLIDEAN;
     if ((rc = p->d_feats_n.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
-    if ((rc = ddk::normalize_rows(s, raw, p->d_feats_n.as<float>(), D)) != DD_OK) return rc;
+    if (euclid) {                                               // nn_matching.py:57-75 works on the features as they come: no normalisation
+        DD_HIP(hipMemcpyAsync(p->d_feats_n.p, feats, (size_t)D * 128 * sizeof(float),
+                              feats_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    } else {
+        const float *raw = feats;
+        if (!feats_on_device) {
+            if ((rc = p->d_feats_raw.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
+            DD_HIP(hipMemcpyAsync(p->d_feats_raw.p, feats, (size_t)D * 128 * sizeof(float), hipMemcpyHostToDevice, s));
+            raw = p->d_feats_raw.as<float>();
+        }
+        if ((rc = ddk::normalize_rows(s, raw, p->d_feats_n.as<float>(), D)) != DD_OK) return rc;
+    }
     if (R > 0 && cost_total > 0) {
         if ((rc = p->d_cost.reserve(cost_total * sizeof(double))) != DD_OK) return rc;
         if ((rc = p->h_cost.reserve(cost_total * sizeof(double))) != DD_OK) return rc;
         const int *dr = reinterpret_cast<const int *>(d + off_rows);
-        hipLaunchKernelGGL(tracker_assoc_k, dim3(R, dd_ceil_div(maxn, 64)), dim3(256), 0, s, p->d_means, p->d_covs,
+        hipLaunchKernelGGL(euclid ? tracker_assoc_k<METRIC_EUCLIDEAN> : tracker_assoc_k<METRIC_COSINE>, dim3(R, dd_ceil_div(maxn, 64)),
+                           dim3(256), 0, s, p->d_means, p->d_covs,
                            p->d_arenas, p->d_tab, p->tab_stride, dr, dr + R, dr + 2 * R, dr + 3 * R, dr + 4 * R, dr + 5 * R,
                            dr + 6 * R, dr + 7 * R, reinterpret_cast<const double *>(d), p->d_feats_n.as<float>(),
                            p->d_cost.as<double>());
@@ -656,6 +684,17 @@ int dd_tracker_create(dd_ctx *ctx, double max_cosine_distance, double max_iou_di
                                      track_capacity, gallery_capacity, out);
 }
 
+// nn_matching.py:5-28,57-75,126-132: the same tracker under either metric.  metric 0 = "cosine" (dd_tracker_create), 1 = "euclidean":
+// matching_threshold then bounds the minimum SQUARED distance of the raw features, which are associated and stored un-normalised.
+int dd_tracker_create_metric(dd_ctx *ctx, int metric, double matching_threshold, double max_iou_distance, int max_age, int n_init,
+                             int nn_budget, int track_capacity, int gallery_capacity, dd_tracker **out) {
+    DD_REQUIRE(metric == METRIC_COSINE || metric == METRIC_EUCLIDEAN, DD_E_ARG,
+               "dd_tracker_create_metric: metric must be 0 (cosine) or 1 (euclidean), got %d", metric);
+    int rc = dd_tracker_create(ctx, matching_threshold, max_iou_distance, max_age, n_init, nn_budget, track_capacity, gallery_capacity, out);
+    if (rc != DD_OK) return rc;
+    return ddk::tracker_group_set_metric(*out, metric);
+}
+
 int dd_tracker_destroy(dd_tracker *t) {
     if (!t) return DD_OK;
     pool_release(t->pool);
@@ -727,7 +766,8 @@ int find_live(const dd_tracker *t, int64_t id) {
 
 // Track.update(kf, detection) (track.py:127-152) for ONE live track: Kalman update with the detection's box, feature
 // appended to the track's gallery, hits += 1, time_since_update = 0, Tentative -> Confirmed once hits >= n_init.
-// The mirrored mean of the track is refreshed.  feat: 128 f32 (host or device), normalised here like every feature.
+// The mirrored mean of the track is refreshed.  feat: 128 f32 (host or device), normalised here like every feature (cosine metric;
+// stored as it is under the euclidean one).
 int dd_tracker_track_update(dd_tracker *t, int64_t track_id, const double *tlwh_host, const float *feat, int feat_on_device) {
     DD_REQUIRE(t && tlwh_host && feat, DD_E_ARG, "dd_tracker_track_update: NULL argument");
     DD_DEVICE(t->pool->ctx);
@@ -752,8 +792,12 @@ int dd_tracker_track_update(dd_tracker *t, int64_t track_id, const double *tlwh_
     if ((rc = gallery_place(p, tr.slot, t->budget, &grow)) != DD_OK) return rc;
     hp[0] = tr.slot; hp[1] = 0; hp[2] = grow;
     DD_HIP(hipMemcpyAsync(d, h, 32 + 3 * sizeof(int), hipMemcpyHostToDevice, s));
-    DD_HIP(hipMemcpyAsync(p->d_feats_raw.p, feat, 128 * sizeof(float), feat_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    if ((rc = ddk::normalize_rows(s, p->d_feats_raw.as<float>(), p->d_feats_n.as<float>(), 1)) != DD_OK) return rc;
+    if (p->metric == METRIC_EUCLIDEAN) {                          // the raw row is what the gallery keeps
+        DD_HIP(hipMemcpyAsync(p->d_feats_n.p, feat, 128 * sizeof(float), feat_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    } else {
+        DD_HIP(hipMemcpyAsync(p->d_feats_raw.p, feat, 128 * sizeof(float), feat_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        if ((rc = ddk::normalize_rows(s, p->d_feats_raw.as<float>(), p->d_feats_n.as<float>(), 1)) != DD_OK) return rc;
+    }
     const int *dp = reinterpret_cast<const int *>(d + 32);
     hipLaunchKernelGGL(tracker_apply_k, dim3(1), dim3(256), 0, s, p->d_means, p->d_covs, p->d_arenas, dp, dp + 1, dp + 2, 1, 0,
                        reinterpret_cast<const double *>(d), p->d_feats_n.as<float>());

@@ -24,9 +24,10 @@ class Tracker:
         self._by_id = {}
         budget = metric.budget if getattr(metric, 'budget', None) else 0
         h = P()
-        check(lib().dd_tracker_create(self.ctx.handle, float(metric.matching_threshold), float(max_iou_distance),
-                                      int(max_age), int(n_init), int(budget), int(track_capacity),
-                                      int(gallery_capacity), ctypes.byref(h)), 'dd_tracker_create')
+        kind = int(getattr(metric, 'kind', 0))      # 0 cosine, 1 euclidean (nn_matching.py:126-132)
+        check(lib().dd_tracker_create_metric(self.ctx.handle, kind, float(metric.matching_threshold), float(max_iou_distance),
+                                             int(max_age), int(n_init), int(budget), int(track_capacity),
+                                             int(gallery_capacity), ctypes.byref(h)), 'dd_tracker_create_metric')
         self._h = h
 
     def __del__(self):

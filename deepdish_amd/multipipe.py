@@ -10,6 +10,7 @@ from .runtime import default_context, ptr
 from . import nets, netsq
 from .engine import Net
 from .pipeline import DEFAULT_LABELS, DEFAULT_YOLO_LABELS
+from .deep_sort.nn_matching import metric_kind as _metric_kind
 from .tools.weights_io import load_named_weights, load_ssd_model, load_mars_weights, load_yolov5_weights, ssd_post_options
 
 
@@ -40,7 +41,9 @@ class MultiStreamPipeline:
                  labels=None, wanted_labels=('person',), input_size=(640, 480), line=None, max_cosine_distance=0.2,
                  nms_max_overlap=0.6, max_iou_distance=0.7, max_age=60, n_init=3, context=None, run_detector=True,
                  encoder_max_batch=None, track_capacity=512, gallery_capacity=256, background_subtraction_ratio=None,
-                 background_masking=False, graph=None, object_detector_skip_frames=None):
+                 background_masking=False, graph=None, object_detector_skip_frames=None, metric='cosine'):
+        self.metric = metric
+        metric_kind = _metric_kind(metric)   # 'cosine' or 'euclidean' (nn_matching.py:126-132), else ValueError -- before anything is built
         self.ctx = context or default_context()
         self.S = int(n_streams)
         self.W, self.H = input_size
@@ -115,6 +118,8 @@ class MultiStreamPipeline:
                                        int(max_age), int(n_init), ptr(self.line), int(track_capacity),
                                        int(gallery_capacity), ctypes.byref(h)), 'dd_pipeline_create')
         self._h = h
+        if metric_kind:         # NearestNeighborDistanceMetric("euclidean", max_cosine_distance, None) for every stream's tracker
+            check(lib().dd_pipeline_metric(self._h, metric_kind), 'dd_pipeline_metric')
         if self.det is not None and self.kind != 'yolov5':
             check(lib().dd_pipeline_ssd_options(self._h, int(ssd_post['max_detections']), float(ssd_post['nms_score_threshold']),
                                                 float(ssd_post['nms_iou_threshold'])), 'dd_pipeline_ssd_options')

@@ -73,7 +73,9 @@ class HotPath:
                  nms_max_overlap=0.6, max_iou_distance=0.7, max_age=60, encoder_batch_size=32, num_threads=4,
                  context=None, run_detector=True, disable_background_subtraction=True, background_subtraction_ratio=0.25,
                  enable_background_masking=False, log=None, restore_from_log=False, mqtt_publish=None, mqtt_topic='default/topic',
-                 mqtt_acp_id=None, mqtt_verbosity=1, cpu_temp=None, annotations=None, object_detector_skip_frames=None):
+                 mqtt_acp_id=None, mqtt_verbosity=1, cpu_temp=None, annotations=None, object_detector_skip_frames=None,
+                 metric='cosine'):
+        nn_matching.metric_kind(metric)              # 'cosine' or 'euclidean' (nn_matching.py:126-132), else ValueError -- before anything is built
         self.ctx = context or default_context()
         self.input_size = tuple(input_size)
         # deepdish.py:512,889: the reference defaults to background subtraction ON; its benchmarks (and this class)
@@ -87,7 +89,8 @@ class HotPath:
         self.object_detector = make_detector(model, labels, wanted_labels, num_threads, self.ctx) if run_detector else None
         self.encoder = gdet.create_box_encoder(encoder_model, batch_size=encoder_batch_size, num_threads=num_threads,
                                                context=self.ctx)
-        metric = nn_matching.NearestNeighborDistanceMetric("cosine", max_cosine_distance, None)   # deepdish.py:515-516
+        # deepdish.py:515-516 asks for "cosine"; with 'euclidean' the same threshold bounds the squared distance of the encoder's rows
+        metric = nn_matching.NearestNeighborDistanceMetric(metric, max_cosine_distance, None)
         self.tracker = Tracker(metric, max_iou_distance=max_iou_distance, max_age=max_age, context=self.ctx)
         w, h = self.input_size
         if line is None:                                                                          # :739-741

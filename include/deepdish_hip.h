@@ -83,6 +83,12 @@ int dd_iou_cost(dd_ctx *ctx, const double *tlwh_t, const int *tsu, int n_t,
 int dd_cosine_nn_cost(dd_ctx *ctx, const float *gallery, const int *offsets_host, int n_t,
                       const float *feats, int n_d, double *out, void *stream);
 
+/* deep_sort/nn_matching.py:5-28,57-75: the "euclidean" metric -- per target t, min over its gallery rows g of
+ * max(0, |g|^2 + |q|^2 - 2 g.q) in f32 (a SQUARED distance), widened to f64.  Same contract as dd_cosine_nn_cost;
+ * gallery and feats are used as they are, NOT normalised. */
+int dd_euclidean_nn_cost(dd_ctx *ctx, const float *gallery, const int *offsets_host, int n_t,
+                         const float *feats, int n_d, double *out, void *stream);
+
 /* deep_sort/preprocessing.py:6-73 non_max_suppression (greedy, +1 pixel, inter/area_other > thr).
  * `keys` is the sort key (scores, or y2 when the reference is called with scores=None).
  * out_idx[k] receives the surviving indices in pick order, *out_n their number (both device). */
@@ -117,6 +123,12 @@ int dd_pyset_difference_order_host(const int *a_host, int na, const int *b_host,
 int dd_tracker_create(dd_ctx *ctx, double max_cosine_distance, double max_iou_distance,
                       int max_age, int n_init, int nn_budget /* <=0: None */,
                       int track_capacity, int gallery_capacity, dd_tracker **out);
+/* deep_sort/nn_matching.py:5-28,57-75 (metric chosen at :126-132): dd_tracker_create with the metric named -- 0 = "cosine"
+ * (what dd_tracker_create means), 1 = "euclidean"; any other value is DD_E_ARG.  Under the euclidean metric matching_threshold bounds
+ * the minimum squared distance, and features are associated and stored in the gallery as given (no L2 normalisation anywhere). */
+int dd_tracker_create_metric(dd_ctx *ctx, int metric, double matching_threshold, double max_iou_distance,
+                             int max_age, int n_init, int nn_budget /* <=0: None */,
+                             int track_capacity, int gallery_capacity, dd_tracker **out);
 int dd_tracker_destroy(dd_tracker *trk);
 /* tracker.py:51-57 */
 int dd_tracker_predict(dd_tracker *trk);
@@ -362,6 +374,10 @@ int dd_pipeline_ssd_options(dd_pipeline *p, int max_detections, float nms_score_
  * motion test and NMS, and its first min(kept boxes, feature rows of that step) boxes pair with those feature rows in order, as the
  * reference's zip() does.  Stage events add nothing to objd / feat on a skip step.  Before the first step. */
 int dd_pipeline_detector_skip_frames(dd_pipeline *p, int n);
+/* deep_sort/nn_matching.py:5-28,57-75: the metric of the pipeline's trackers, 0 = cosine (default), 1 = euclidean (other values:
+ * DD_E_ARG).  The threshold stays the max_cosine_distance given to dd_pipeline_create, as the reference hands --max-cosine-distance to
+ * NearestNeighborDistanceMetric as matching_threshold whatever the metric (deepdish.py:515-516).  Before the first step (DD_E_STATE after). */
+int dd_pipeline_metric(dd_pipeline *p, int metric);
 /* frames: device u8 [n_streams][H][W][3] BGR.  inj_*: optional detections that REPLACE the detector's
  * output (it still runs): tlwh f64 rows, scores, class ids; stream s owns rows
  * [inj_offsets[s], inj_offsets[s+1]).  Blocks until the step is complete. */
