@@ -86,6 +86,10 @@ SIGNATURES = {
     'dd_ssd_postprocess': [P, P, P, c_int, c_int, c_int, c_float, c_float, P, P, P, P, P],
     'dd_ssd_decode': [P, P, P, c_int, c_int, c_float, P, P, P, P, c_int, P],
     'dd_ssd_postprocess_decoded': [P, P, P, P, P, c_int, c_int, c_float, c_float, P, P, P, P, c_int, P],
+    'dd_ssd_regular_nms_decoded': [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P, P, c_int, P],
+    'dd_ssd_postprocess_regular': [P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P, P, c_int, P],
+    'dd_ssd_postprocess_regular_u8': [P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, P, P, P, P, c_int, P],
+    'dd_net_ssd_heads_u8': [P, POINTER(P), POINTER(P), POINTER(c_int), POINTER(P), P, POINTER(c_int), POINTER(c_int)],
     'dd_net_ssd_decode': [P, P, c_int, c_float, c_int],
     'dd_net_ssd_decoded': [P, POINTER(P), POINTER(P), POINTER(P), POINTER(P)],
     'dd_net_ssd_decoded_read': [P, c_int, P, P, P, P],
@@ -99,6 +103,7 @@ SIGNATURES = {
     'dd_pipeline_destroy': [P],
     'dd_pipeline_detector_adaptor': [P, c_int],
     'dd_pipeline_ssd_options': [P, c_int, c_float, c_float],
+    'dd_pipeline_ssd_regular_nms': [P, c_int],
     'dd_pipeline_detector_skip_frames': [P, c_int],
     'dd_pipeline_metric': [P, c_int],
     'dd_pipeline_step': [P, P, P, P, P, P],

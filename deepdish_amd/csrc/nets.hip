@@ -4881,6 +4881,30 @@ int dd_net_ssd_decoded(dd_net *net, float **boxes, float **scores, int **classes
     return DD_OK;
 }
 
+// The uint8 program's head tensors (the inputs of its OP_QSSD_DECODE) where the last forward left them, for the consumers that score
+// every class of an anchor (csrc/post_regular.hip): a uint8 engine keeps one buffer per tensor, so they outlive the forward.
+int dd_net_ssd_heads_u8(dd_net *net, const uint8_t **box_q, const uint8_t **cls_q, int *cls_stride, const uint8_t **lut, float *quant4_host,
+                        int *n_anchors, int *n_classes) {
+    DD_REQUIRE(net && box_q && cls_q && cls_stride && lut && quant4_host && n_anchors && n_classes, DD_E_ARG, "dd_net_ssd_heads_u8: NULL argument");
+    DD_REQUIRE(!net->arena, DD_E_STATE, "dd_net_ssd_heads_u8: the engine's buffers share memory by lifetime (dd_net_create_shared): the head "
+               "tensors do not outlive the forward");
+    for (int i = 0; i < net->n_ops; ++i) {
+        const int32_t *o = net->prog.data() + net->ops_off + (size_t)i * OP_WORDS;
+        if (o[0] != 20) continue;                              // OP_QSSD_DECODE
+        DD_REQUIRE(o[1] >= 0 && o[1] < (int)net->tensors.size() && o[3] >= 0 && o[3] < (int)net->tensors.size(), DD_E_ARG, "dd_net_ssd_heads_u8: head tensors out of range");
+        const TensorDesc &tb = net->tensors[o[1]], &tc = net->tensors[o[3]];
+        DD_REQUIRE(tb.cs == 4 && tb.h == o[21] && tc.h == o[21] && tb.w == 1 && tc.w == 1 && o[20] <= tc.cs && !tb.pad && !tc.pad && !tb.coff && !tc.coff, DD_E_ARG,
+                   "dd_net_ssd_heads_u8: head tensors of %d anchors are not [anchors][4] / [anchors][>= %d] bytes", o[21], o[20]);
+        *box_q = static_cast<const uint8_t *>(net->bufs[tb.buf]); *cls_q = static_cast<const uint8_t *>(net->bufs[tc.buf]);
+        *cls_stride = tc.cs; *n_anchors = o[21]; *n_classes = o[20];
+        *lut = reinterpret_cast<const uint8_t *>(net->d_weights + (size_t)(uint32_t)o[16]);
+        const float *of = reinterpret_cast<const float *>(o);
+        for (int q = 0; q < 4; ++q) quant4_host[q] = of[32 + q];
+        return DD_OK;
+    }
+    DD_REQUIRE(false, DD_E_ARG, "dd_net_ssd_heads_u8: the program has no uint8 SSD head");
+}
+
 int dd_net_ssd_decoded_read(dd_net *net, int n, float *boxes_host, float *scores_host, int *classes_host, float *keys_host) {
     DD_REQUIRE(net && net->ssd_dec && n >= 0 && n <= net->max_batch, DD_E_STATE, "dd_net_ssd_decoded_read: decode is off or n out of range");
     DD_DEVICE(net->ctx);

@@ -30,6 +30,11 @@ int ssd_postprocess_decoded(hipStream_t s, const float *d_boxes, const float *d_
                             int n_anchors, int max_det, float score_thr, float iou_thr, float *boxes, float *classes, float *scores,
                             int *count, int batch, void *scratch, size_t scratch_bytes);
 int yolov5_pack(hipStream_t s, const float *boxes, const float *scores, const int *cls, const int *n_rows, int cap, int batch, float *packed);
+int ssd_regular_nms_raw(hipStream_t s, const float *raw, const float *anchors, int n_anchors, int n_classes, int max_det, int per_class,
+                        float score_thr, float iou_thr, float *boxes, float *classes, float *scores, int *count, int batch);
+int ssd_regular_nms_u8(hipStream_t s, const uint8_t *box_q, const uint8_t *cls_q, int cls_stride, const uint8_t *lut, const float *quant4,
+                       const float *anchors, int n_anchors, int n_classes, int max_det, int per_class, float score_thr, float iou_thr,
+                       float *boxes, float *classes, float *scores, int *count, int batch);
 int ssd_finish(hipStream_t s, const float *boxes, const float *cls, const float *scores, int batch, int max_det, double conf,
                double iou_thr, double img_w, double img_h, double *out_boxes, int *out_cls, double *out_scores, int *out_n);
 int tracker_group_create(dd_ctx *ctx, int n, double max_cos, double max_iou, int max_age, int n_init, int budget, int tcap,
@@ -45,6 +50,8 @@ int tracker_read_host(dd_tracker *t, int which, int64_t *ints6_host, double *mea
 extern "C" int dd_net_max_batch(dd_net *net, int *out_host);
 extern "C" int dd_net_ssd_decode(dd_net *net, const float *anchors_host, int n_anchors, float score_thr, int enable);
 extern "C" int dd_net_ssd_decoded(dd_net *net, float **boxes, float **scores, int **classes, float **keys);
+extern "C" int dd_net_ssd_heads_u8(dd_net *net, const uint8_t **box_q, const uint8_t **cls_q, int *cls_stride, const uint8_t **lut, float *quant4_host,
+                                   int *n_anchors, int *n_classes);
 extern "C" int dd_net_yolo_decode(dd_net *net, int enable);
 extern "C" int dd_net_yolo_decoded(dd_net *net, float **boxes, float **conf, int **classes, int *rows);
 extern "C" int dd_net_input_size(dd_net *net, int *h_host, int *w_host);
@@ -108,6 +115,8 @@ struct dd_pipeline {
     std::vector<std::string> tfl_labels;       // its label list: the label file's lines after the first, empty lines dropped (tflite.py:22, tflite_object_detector.py)
     bool det_late = true;                      // where the look-ahead detector run is queued (dd_pipeline_step2)
     bool ssd_dec = false;                      // SSD: the head layers decode in their epilogue (dd_net_ssd_decode)
+    int ssd_per_class = 0;                     // > 0: the model file states use_regular_nms -- per-class NMS with this detections_per_class (dd_pipeline_ssd_regular_nms)
+    struct { const uint8_t *box = nullptr, *cls = nullptr, *lut = nullptr; int stride = 0, n_classes = 0; float quant[4] = {0, 0, 0, 0}; } q8;   // uint8 engine: its head tensors
     bool yolo_dec = false;                     // YOLOv5: the Detect layers reduce their rows in their epilogue (dd_net_yolo_decode)
     size_t yolo_host_rows = 0;                 // YOLOv5: packed rows the first copy of a step brings to the host
     std::vector<size_t> ybase;
@@ -329,6 +338,27 @@ int dd_pipeline_ssd_options(dd_pipeline *p, int max_detections, float nms_score_
     return DD_OK;
 }
 
+int dd_pipeline_ssd_regular_nms(dd_pipeline *p, int detections_per_class) {
+    DD_REQUIRE(p && p->det && p->det_kind != DET_YOLOV5, DD_E_ARG, "dd_pipeline_ssd_regular_nms: needs a pipeline with an SSD-type detector");
+    DD_REQUIRE(detections_per_class >= 1, DD_E_ARG, "dd_pipeline_ssd_regular_nms: detections_per_class %d (>= 1)", detections_per_class);
+    DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, "dd_pipeline_ssd_regular_nms: call before the first step");
+    DD_DEVICE(p->ctx);
+    int rc, dtype = 0;
+    if ((rc = dd_net_output(p->det, -1, nullptr, nullptr, nullptr, nullptr, nullptr, &dtype)) != DD_OK) return rc;
+    if (dtype == 2) {                          // uint8 engine: the op reads the quantised head tensors where the forward leaves them
+        int na = 0;
+        if ((rc = dd_net_ssd_heads_u8(p->det, &p->q8.box, &p->q8.cls, &p->q8.stride, &p->q8.lut, p->q8.quant, &na, &p->q8.n_classes)) != DD_OK) return rc;
+        DD_REQUIRE(na == p->n_anchors && p->q8.n_classes == p->n_classes, DD_E_ARG, "dd_pipeline_ssd_regular_nms: the engine's head has %d anchors x %d columns, the pipeline %d x %d",
+                   na, p->q8.n_classes, p->n_anchors, p->n_classes);
+    }
+    // the decode epilogue keeps the best class of an anchor only: off (the f32 engine then writes its head matrix, as under DD_SSD_DEC=0).
+    // The op needs no scratch: d_post stays as it is.
+    if ((rc = dd_net_ssd_decode(p->det, nullptr, 0, 0.f, 0)) != DD_OK) return rc;
+    p->ssd_dec = false;
+    p->ssd_per_class = detections_per_class;
+    return DD_OK;
+}
+
 int dd_pipeline_detector_adaptor(dd_pipeline *p, int adaptor) {
     DD_REQUIRE(p && p->det && p->det_kind != DET_YOLOV5 && (adaptor == DET_SSD || adaptor == DET_TFLITE), DD_E_ARG,
                "dd_pipeline_detector_adaptor: needs a pipeline with an SSD-type detector; adaptor 0 (ssd_mobilenet) or 2 (tflite)");
@@ -523,7 +553,13 @@ int enqueue_detector(dd_pipeline *p, const uint8_t *frames) {
     }
     float *db = p->d_det.as<float>(), *dc = db + (size_t)S * MAX_DET * 4, *ds = dc + (size_t)S * MAX_DET;
     int *dn = reinterpret_cast<int *>(ds + (size_t)S * MAX_DET);
-    if (p->ssd_dec) {
+    if (p->ssd_per_class > 0) {                                 // use_regular_nms = true: per-class NMS, straight from the head
+        if (p->q8.cls) rc = ddk::ssd_regular_nms_u8(s, p->q8.box, p->q8.cls, p->q8.stride, p->q8.lut, p->q8.quant, p->d_anchors, p->n_anchors, p->n_classes,
+                                                    MAX_DET, p->ssd_per_class, p->ssd_score_thr, p->ssd_iou_thr, db, dc, ds, dn, S);
+        else rc = ddk::ssd_regular_nms_raw(s, static_cast<const float *>(raw), p->d_anchors, p->n_anchors, p->n_classes, MAX_DET, p->ssd_per_class,
+                                           p->ssd_score_thr, p->ssd_iou_thr, db, dc, ds, dn, S);
+        if (rc != DD_OK) return rc;
+    } else if (p->ssd_dec) {
         float *eb = nullptr, *es = nullptr, *ek = nullptr;
         int *ec = nullptr;
         if ((rc = dd_net_ssd_decoded(p->det, &eb, &es, &ec, &ek)) != DD_OK) return rc;

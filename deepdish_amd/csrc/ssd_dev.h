@@ -8,6 +8,13 @@
 
 namespace ssddev {
 
+// The class score of a logit: decode_anchor's own expression, for the callers that score every class of an anchor (the regular,
+// per-class NMS of csrc/post_regular.hip) -- the same bits as decode_anchor returns for that logit.
+__device__ __forceinline__ float sigmoid(float x) {
+#pragma clang fp contract(off)
+    return 1.f / (1.f + expf(-x));
+}
+
 // r = the four box encodings (ty, tx, th, tw) of the anchor, an = its (yc, xc, h, w); best = the largest class logit
 // (background excluded).  Writes ymin, xmin, ymax, xmax and returns the score.
 __device__ __forceinline__ float decode_anchor(const float r[4], const float an[4], float best, float box[4]) {

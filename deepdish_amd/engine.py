@@ -54,6 +54,17 @@ class Net:
         check(lib().dd_net_ssd_decode(self._h, ptr(a), len(a), float(score_thr), int(bool(enable))), 'dd_net_ssd_decode')
         self._dec_anchors = len(a) if enable else 0
 
+    def ssd_heads_u8(self):
+        """uint8 SSD engine: where the last forward left the post-process op's two inputs -- dict(box, cls, lut: device pointers,
+        cls_stride, n_anchors, n_classes (with the background column), quant: f32 [4] box scale, box zero point, score scale, score
+        zero point).  What dd_ssd_postprocess_regular_u8 takes."""
+        box, cls, lut = P(), P(), P()
+        stride, na, nc = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        quant = np.zeros(4, np.float32)
+        check(lib().dd_net_ssd_heads_u8(self._h, ctypes.byref(box), ctypes.byref(cls), ctypes.byref(stride), ctypes.byref(lut), ptr(quant),
+                                        ctypes.byref(na), ctypes.byref(nc)), 'dd_net_ssd_heads_u8')
+        return dict(box=box.value, cls=cls.value, lut=lut.value, cls_stride=stride.value, n_anchors=na.value, n_classes=nc.value, quant=quant)
+
     def ssd_decoded(self, n=None):
         """(boxes [n, A, 4] f32, scores [n, A] f32, classes [n, A] i32, keys [n, A] f32) of the last forward, on the host."""
         n = self._last_n if n is None else n

@@ -123,6 +123,8 @@ class MultiStreamPipeline:
         if self.det is not None and self.kind != 'yolov5':
             check(lib().dd_pipeline_ssd_options(self._h, int(ssd_post['max_detections']), float(ssd_post['nms_score_threshold']),
                                                 float(ssd_post['nms_iou_threshold'])), 'dd_pipeline_ssd_options')
+            if ssd_post.get('use_regular_nms'):                     # the file asks for the op's per-class NMS (csrc/post_regular.hip)
+                check(lib().dd_pipeline_ssd_regular_nms(self._h, int(ssd_post['detections_per_class'])), 'dd_pipeline_ssd_regular_nms')
         if self.kind == 'tflite' and self.det is not None:          # tools/tflite.py's adaptor instead of tools/ssd_mobilenet.py's
             check(lib().dd_pipeline_detector_adaptor(self._h, 2), 'dd_pipeline_detector_adaptor')
         off = 0 if self.kind == 'yolov5' else 1                     # yolov5.py:134 labels[idx]; ssd_mobilenet.py:142-147 labels[idx + 1]

@@ -3,8 +3,8 @@
 `detect_image(img) -> (boxes tlwh, labels, scores)`.
 
 Device side: Lanczos stretch resize (csrc/image.hip) -> MobileNet-v1 SSD forward (csrc/nets.hip, f16
-MFMA) -> anchor decode / sigmoid / fast NMS / top-10 (csrc/post.hip) -> per-class NMS
-(csrc/nms.hip mode 1).  Host side: the dozen-element list handling of predict / detect_image.
+MFMA) -> anchor decode / sigmoid / fast NMS / top-10 (csrc/post.hip; a model file that states
+use_regular_nms: the op's per-class NMS, csrc/post_regular.hip) -> per-class NMS (csrc/nms.hip mode 1).  Host side: the dozen-element list handling of predict / detect_image.
 """
 import ctypes
 import os
@@ -38,10 +38,13 @@ class SSDMobileNet:
         post = ssd_post_options(wd)
         self.MAX_DET = int(post['max_detections'])
         self.nms_score_threshold, self.nms_iou_threshold = float(post['nms_score_threshold']), float(post['nms_iou_threshold'])
+        # use_regular_nms = true in the file: the op's per-class NMS with its detections_per_class (None: the fast class-agnostic NMS)
+        self.detections_per_class = int(post['detections_per_class']) if post.get('use_regular_nms') else None
         prog = netsq.compile_ssd_mobilenet_quant(wd) if self.quantized else nets.compile_ssd_mobilenet(wd)
         self.net = Net(prog, max_batch=max_batch, context=self.ctx)
-        if self.quantized:                           # integer heads: the post-process op's first stage reads the quantised tensors (csrc/netsq.hip)
+        if self.quantized and self.detections_per_class is None:   # integer heads: the post-process op's first stage reads the quantised tensors (csrc/netsq.hip)
             self.net.ssd_decode(prog.meta['anchors'], self.nms_score_threshold)
+        self._heads_u8 = self.net.ssd_heads_u8() if self.quantized and self.detections_per_class is not None else None
         self.height = self.width = prog.in_h
         self.anchors = prog.meta['anchors']
         self.n_classes = prog.meta['n_classes']
@@ -68,7 +71,19 @@ class SSDMobileNet:
     def invoke_device(self, resized_dev, read=True):
         """ssd_mobilenet.py:102-109: interpreter.invoke() and its four output tensors (read=False leaves them in HBM)."""
         self.net.forward(resized_dev)
-        if self.quantized:
+        if self.detections_per_class is not None:    # every class of every anchor is a candidate: straight from the head (csrc/post_regular.hip)
+            outs = (ptr(self._boxes), ptr(self._classes), ptr(self._scores), ptr(self._count), 1, None)
+            if self.quantized:
+                h = self._heads_u8
+                check(lib().dd_ssd_postprocess_regular_u8(self.ctx.handle, h['box'], h['cls'], h['cls_stride'], h['lut'], ptr(h['quant']),
+                                                          ptr(self._anchors_dev), len(self.anchors), self.n_classes, self.MAX_DET,
+                                                          self.detections_per_class, self.nms_score_threshold, self.nms_iou_threshold, *outs),
+                      'dd_ssd_postprocess_regular_u8')
+            else:
+                check(lib().dd_ssd_postprocess_regular(self.ctx.handle, self.net.output_ptr(), ptr(self._anchors_dev), len(self.anchors),
+                                                       self.n_classes, self.MAX_DET, self.detections_per_class, self.nms_score_threshold,
+                                                       self.nms_iou_threshold, *outs), 'dd_ssd_postprocess_regular')
+        elif self.quantized:
             P4 = [ctypes.c_void_p() for _ in range(4)]
             check(lib().dd_net_ssd_decoded(self.net._h, *[ctypes.byref(q) for q in P4]), 'dd_net_ssd_decoded')
             check(lib().dd_ssd_postprocess_decoded(self.ctx.handle, P4[0], P4[1], P4[2], P4[3], len(self.anchors), self.MAX_DET,

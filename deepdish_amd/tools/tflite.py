@@ -59,6 +59,7 @@ class ObjectDetector:
         post = ssd_post_options(wd)                           # the post-process op's own options (its file's, else the stock export's)
         self.MAX_DET = int(post['max_detections'])
         self._score_thr, self._iou_thr = float(post['nms_score_threshold']), float(post['nms_iou_threshold'])
+        self._per_class = int(post['detections_per_class']) if post.get('use_regular_nms') else None     # the op's per-class NMS (csrc/post_regular.hip)
         # tflite_object_detector.py:117-137: mean / std and the label list come from the model file's own metadata.  A model WITHOUT metadata
         # (the reference's MetadataDisplayer raises on one) is taken with a label_file and the defaults: an extension for this build's
         # synthetic / .npz models, never consulted when the file carries metadata (the reference ignores its label_file argument, tflite.py:16-23).
@@ -103,9 +104,14 @@ class ObjectDetector:
         check(lib().dd_resize_bilinear(self.ctx.handle, ptr(self.ctx.to_device(img)), image_height, image_width, 3,
                                        ptr(self._resized), h, w, None), 'dd_resize_bilinear')      # :211 cv2.resize
         self.net.forward(self._resized)
-        check(lib().dd_ssd_postprocess(self.ctx.handle, self.net.output_ptr(), ptr(self._anchors_dev), len(self._anchors),
-                                       self._n_classes, self.MAX_DET, self._score_thr, self._iou_thr, ptr(self._boxes), ptr(self._classes),
-                                       ptr(self._scores), ptr(self._count), None), 'dd_ssd_postprocess')
+        if self._per_class is not None:
+            check(lib().dd_ssd_postprocess_regular(self.ctx.handle, self.net.output_ptr(), ptr(self._anchors_dev), len(self._anchors),
+                                                   self._n_classes, self.MAX_DET, self._per_class, self._score_thr, self._iou_thr, ptr(self._boxes),
+                                                   ptr(self._classes), ptr(self._scores), ptr(self._count), 1, None), 'dd_ssd_postprocess_regular')
+        else:
+            check(lib().dd_ssd_postprocess(self.ctx.handle, self.net.output_ptr(), ptr(self._anchors_dev), len(self._anchors),
+                                           self._n_classes, self.MAX_DET, self._score_thr, self._iou_thr, ptr(self._boxes), ptr(self._classes),
+                                           ptr(self._scores), ptr(self._count), None), 'dd_ssd_postprocess')
         self.ctx.sync()
         return self._postprocess(self._boxes.cpu().numpy(), self._classes.cpu().numpy(), self._scores.cpu().numpy(),
                                  int(self._count.cpu().numpy()[0]), image_width, image_height)

@@ -197,8 +197,12 @@ def _conv_layer(g, op):
 
 # TFLite_Detection_PostProcess options this build runs (tools/ssd_mobilenet.py:100-109 upstream: the interpreter applies whatever the file
 # says).  Passed on: max_detections, nms_score_threshold, nms_iou_threshold (SSDMobileNet, dd_pipeline_ssd_options).  Checked: the four
-# box-coder scales the decode is built for must be PRESENT and equal 10 / 10 / 5 / 5; max_classes_per_detection 1; the fast
-# (class-agnostic) NMS -- `use_regular_nms` true selects a per-class NMS with `detections_per_class`, which is not built: refused by name.
+# box-coder scales the decode is built for must be PRESENT and equal 10 / 10 / 5 / 5; max_classes_per_detection 1.  `use_regular_nms`
+# false (or absent) is the fast class-agnostic NMS; true selects the per-class NMS (csrc/post_regular.hip: greedy NMS inside every class,
+# at most `detections_per_class` survivors each, merged by score -- equal scores: lower class, then lower anchor, first) and is accepted
+# when the file also states `detections_per_class` >= 1 (the Object Detection API's exporter always writes it; the same strictness as
+# for the coder scales).  The options dict then carries `use_regular_nms` and `detections_per_class`; a fast-NMS file's has neither key.
+# Both modes are restated from the op's published behaviour (TensorFlow Lite is absent here): parity unpinned.
 SSD_POST_DEFAULTS = dict(max_detections=10, nms_score_threshold=1e-8, nms_iou_threshold=0.6)
 MAX_DETECTIONS_BUILT = 64                                          # csrc/post.hip: one wave lane per row of the op's output
 
@@ -210,14 +214,19 @@ def ssd_post_options(post):
         _need(abs(float(o[k]) - v) < 1e-6, post, '%s = %s (the decode is built for %s)' % (k, o[k], v))
     for k in ('max_detections', 'nms_score_threshold', 'nms_iou_threshold', 'num_classes'):
         _need(k in o, post, 'option %s is missing' % k)
-    _need(not bool(o.get('use_regular_nms', False)), post, 'use_regular_nms = true (per-class NMS with detections_per_class = %s): only the fast '
-          'class-agnostic NMS is built' % o.get('detections_per_class', 100))
+    regular = bool(o.get('use_regular_nms', False))
+    if regular:
+        _need('detections_per_class' in o, post, 'use_regular_nms = true without detections_per_class (the per-class NMS needs the option stated)')
+        _need(int(o['detections_per_class']) >= 1, post, 'detections_per_class = %s with use_regular_nms = true (>= 1)' % o['detections_per_class'])
     _need(int(o.get('max_classes_per_detection', 1)) == 1, post, 'max_classes_per_detection = %s (one class per detection is built)' % o.get('max_classes_per_detection'))
     md = int(o['max_detections'])
     _need(1 <= md <= MAX_DETECTIONS_BUILT, post, 'max_detections = %d (1 .. %d are built)' % (md, MAX_DETECTIONS_BUILT))
     iou, thr = float(o['nms_iou_threshold']), float(o['nms_score_threshold'])
     _need(0.0 < iou <= 1.0, post, 'nms_iou_threshold = %s' % iou)            # the op itself rejects values outside (0, 1]
-    return dict(max_detections=md, nms_score_threshold=thr, nms_iou_threshold=iou, num_classes=int(o['num_classes']))
+    out = dict(max_detections=md, nms_score_threshold=thr, nms_iou_threshold=iou, num_classes=int(o['num_classes']))
+    if regular:
+        out.update(use_regular_nms=True, detections_per_class=int(o['detections_per_class']))
+    return out
 
 
 def load_ssd_mobilenet(path):

@@ -86,10 +86,14 @@ def load_ssd_model(model_file):
 def ssd_post_options(model):
     """TFLite_Detection_PostProcess options of a model load_ssd_model returned: what its .tflite file states (tools/tflite_reader.
     ssd_post_options has validated them), else the stock SSD-MobileNet-v1 export's (max_detections 10, nms_score_threshold 1e-8,
-    nms_iou_threshold 0.6 -- the values synthetic models and .npz weights run with)."""
+    nms_iou_threshold 0.6 -- the values synthetic models and .npz weights run with).  A file that states use_regular_nms = true adds two
+    keys, `use_regular_nms` (True) and `detections_per_class`: the plugins then run the per-class NMS (csrc/post_regular.hip); every other
+    model gives exactly the three keys."""
     from .tflite_reader import SSD_POST_DEFAULTS
     post = dict(SSD_POST_DEFAULTS)
     src = model.get('post') if isinstance(model, dict) and model.get('kind') in ('ssd_mobilenet_v1_uint8', 'ssd_mobilenet_v2_uint8') else model.get('__post__') if isinstance(model, dict) else None
     if src:
         post.update({k: src[k] for k in SSD_POST_DEFAULTS if k in src})
+        if src.get('use_regular_nms'):
+            post.update(use_regular_nms=True, detections_per_class=int(src['detections_per_class']))
     return post

@@ -308,6 +308,42 @@ int dd_net_ssd_decoded(dd_net *net, float **boxes_dev, float **scores_dev, int *
 /* the same arrays of the first n images of the last forward copied to host memory (any pointer may be NULL) */
 int dd_net_ssd_decoded_read(dd_net *net, int n, float *boxes_host, float *scores_host, int *classes_host, float *keys_host);
 
+/* TFLite_Detection_PostProcess as a model file with use_regular_nms = true runs it (the interpreter applies the op's options,
+ * tools/ssd_mobilenet.py:100-109; kernels/detection_postprocess.cc NonMaxSuppressionMultiClassRegularHelper): for every class in
+ * ascending id the anchors with score >= score_thr by descending score (equal scores: the lower anchor first), greedy NMS inside the
+ * class (IoU > iou_thr suppresses, the f32 expressions of the fast path), at most detections_per_class survivors; the classes'
+ * survivors merged by descending score (equal scores: the lower class first, inside a class the keep order), the first max_det rows.
+ * One anchor can come out under several classes; boxes of different classes never suppress each other.  TensorFlow Lite is absent
+ * from this image: restated from the op's published behaviour, parity unpinned.  Outputs as dd_ssd_postprocess for `batch` images:
+ * boxes f32 [batch][max_det][4], classes f32 (id - 1), scores f32 [batch][max_det], count int32 [batch]; rows past count are zero.
+ * 64 < n_anchors <= 4096, 1 <= max_det <= 64, detections_per_class >= 1, at most 256 score columns per anchor (255 classes behind a
+ * background column, 256 for _decoded); anything else is DD_E_ARG.  One
+ * kernel (csrc/post_regular.hip) behind three front ends:
+ *   _decoded: dec_boxes f32 [batch][n_anchors][4] (ymin,xmin,ymax,xmax; 16-byte aligned) and a ready score matrix f32
+ *     [batch][n_anchors][score_ld] whose column first_class_col + c holds class c (n_classes = classes, no background column);
+ *   dd_ssd_postprocess_regular: the f32 head matrix raw [batch][n_anchors][4 + n_classes] (n_classes counts the background column,
+ *     as in dd_ssd_postprocess); a row's box has the bits dd_ssd_decode gives its anchor, every class logit goes through the sigmoid;
+ *   _u8: the uint8 head tensors of a quantised model (dd_net_ssd_heads_u8): box bytes [batch][n_anchors][4], class bytes
+ *     [batch][n_anchors][cls_stride] (background first) through the graph's LOGISTIC as a 256-byte table (device), quant4_host =
+ *     box scale, box zero point, score scale, score zero point: scale * (q - zero point), what dd_net_ssd_decode's uint8 stage reads. */
+int dd_ssd_regular_nms_decoded(dd_ctx *ctx, const float *dec_boxes, const float *scores_in, int score_ld, int first_class_col,
+                               int n_anchors, int n_classes, int max_det, int detections_per_class, float score_thr, float iou_thr,
+                               float *boxes, float *classes, float *scores, int *count, int batch, void *stream);
+int dd_ssd_postprocess_regular(dd_ctx *ctx, const float *raw, const float *anchors, int n_anchors, int n_classes, int max_det,
+                               int detections_per_class, float score_thr, float iou_thr, float *boxes, float *classes, float *scores,
+                               int *count, int batch, void *stream);
+int dd_ssd_postprocess_regular_u8(dd_ctx *ctx, const uint8_t *box_q, const uint8_t *cls_q, int cls_stride, const uint8_t *logistic_table,
+                                  const float *quant4_host, const float *anchors, int n_anchors, int n_classes, int max_det,
+                                  int detections_per_class, float score_thr, float iou_thr, float *boxes, float *classes, float *scores,
+                                  int *count, int batch, void *stream);
+/* The quantised head tensors of a uint8 SSD engine where the last forward left them (tools/ssd_mobilenet.py:102-109: the two inputs of
+ * the post-process op): device pointers to the box bytes [n][n_anchors][4], the class bytes [n][n_anchors][cls_stride] and the 256-byte
+ * logistic table, quant4_host[4] = box scale, box zero point, score scale, score zero point, n_classes with the background column.
+ * DD_E_STATE for an engine whose buffers share memory by lifetime (the tensors do not outlive the forward), DD_E_ARG for a program
+ * without the uint8 SSD head. */
+int dd_net_ssd_heads_u8(dd_net *net, const uint8_t **box_q_dev, const uint8_t **cls_q_dev, int *cls_stride_host,
+                        const uint8_t **logistic_table_dev, float *quant4_host, int *n_anchors_host, int *n_classes_host);
+
 /* YOLOv5 detector: tools/yolov5.py:126-128 (cls *= obj, np.argmax, confidence) inside the Detect layers' epilogues -- per row of the
  * head the decoded box (x, y, w, h: the matrix's first four columns), the confidence and the class; the f32 [rows][5 + C] matrix
  * (yolov5.py:109 `pred`) is then never written and dd_net_read of it is an error.  Needs a program compiled with the per-anchor
@@ -367,6 +403,12 @@ int dd_pipeline_detector_adaptor(dd_pipeline *p, int adaptor);
  * Above 16 rows the ORDER of equal-score rows of one class is the reference's only up to its NumPy's unstable sort (tools/ssd_mobilenet.py:73
  * `s.argsort()[::-1]`: stable for <= 16 elements, unspecified beyond) -- INTEGRATION.md, "Ties inside a class". */
 int dd_pipeline_ssd_options(dd_pipeline *p, int max_detections, float nms_score_threshold, float nms_iou_threshold);
+/* A model file whose post-process op states use_regular_nms = true (tools/ssd_mobilenet.py:100-109: the interpreter runs what the file
+ * says): the detector stage calls the per-class NMS (dd_ssd_postprocess_regular / _u8) with this detections_per_class (>= 1) instead of
+ * the fast class-agnostic one; max_detections and the two thresholds stay dd_pipeline_ssd_options'.  The head layers' decode epilogue
+ * keeps only the best class of an anchor, so it is switched off (dd_net_ssd_decode enable = 0): the f32 engine writes its head matrix,
+ * the uint8 engine's head tensors are read where they lie.  Before the first step. */
+int dd_pipeline_ssd_regular_nms(dd_pipeline *p, int detections_per_class);
 /* --object-detector-skip-frames n (deepdish.py:892-893,929-938,1003-1014): the detector and the encoder run on one step in n + 1 --
  * steps 0, n + 1, 2 (n + 1), ... counted from the first step; n <= 0 = every step (the default).  A skip step runs no detector chain
  * (resize, forward, post-process, adaptor tail, host copy), no crops and no encoder: each stream reuses the last detector step's adaptor
