@@ -56,7 +56,9 @@ SIGNATURES = {
     'dd_resize_lanczos': [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, P],
     'dd_resize_lanczos_batch': [P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P],
     'dd_resize_bilinear': [P, P, c_int, c_int, c_int, P, c_int, c_int, P],
+    'dd_yuv420_to_bgr': [P, P, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, P, P],
     'dd_ingest_create': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
+    'dd_ingest_create_format': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
     'dd_ingest_destroy': [P],
     'dd_ingest_host_slot': [P, c_int, P, P],
     'dd_ingest_submit': [P, c_int],

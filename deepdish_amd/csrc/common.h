@@ -145,6 +145,11 @@ int crop_box_host(const int64_t *b, int ph, int pw, int H, int W, int *sx, int *
 int crop_box_host_f64(const double *b, int ph, int pw, int H, int W, int *sx, int *sy, int *cw, int *ch);
 // d_boxes: device array of {sx, sy, cw, ch, frame, 0, 0, 0} int32 records
 int crop_resize(hipStream_t s, const uint8_t *frames, int H, int W, const void *d_boxes, int n, int oh, int ow, uint8_t *out);
+// 4:2:0 YUV -> BGR (yuv.hip); layout 1 NV12, 2 I420; pitch / chroma_offset / frame_stride 0 = dense
+int yuv420_to_bgr(hipStream_t s, const uint8_t *src, int batch, int H, int W, int layout, int pitch, int64_t chroma_offset,
+                  int64_t frame_stride, uint8_t *dst);
+// the same + cv2.flip(frame, 0) + INTER_LINEAR stretch of n dense frames in one launch: the bytes of yuv420_to_bgr then crop_resize
+int yuv420_resize(hipStream_t s, const uint8_t *src, int n, int H, int W, int layout, int flip, int oh, int ow, uint8_t *out);
 int resize_lanczos(hipStream_t s, int device, const uint8_t *src, int H, int W, int src_c, int swap_rb, uint8_t *dst,
                    int h, int w, uint8_t *tmp, int batch);
 size_t ssd_post_scratch_bytes(int n_anchors, int batch);

@@ -1,0 +1,298 @@
+// 4:2:0 YUV (NV12 / I420) -> BGR u8, what a decoder hands out -> what the pipeline reads (u8, integer arithmetic, HBM-bound):
+//   * yuv420_to_bgr_k   the stand-alone converter, cv2.cvtColor(frame, COLOR_YUV2BGR_NV12 / COLOR_YUV2BGR_I420)
+//   * yuv420_resize_k   convert + cv2.flip(frame, 0) + cv2.resize(frame, input_size) in one launch (the ingest ring's transform)
+// The arithmetic is OpenCV's published BT.601 fixed-point form (20 fractional bits), restated -- OpenCV itself is absent, so parity with
+// it is unpinned like every other cv2 arithmetic here; tests/yuv_ref.py is the numpy restatement the kernels are held to bit for bit.
+//   NV12: H rows of luma, then H/2 rows of interleaved U,V pairs.   I420: H rows of luma, then the U plane, then the V plane.
+// The chroma sample of pixel (x, y) is that of block (x >> 1, y >> 1): no chroma interpolation.
+#include <cstdlib>
+#include "common.h"
+#include "resize_dev.h"
+
+namespace {
+
+constexpr int YUV_NV12 = 1, YUV_I420 = 2;
+constexpr int YUV_SHIFT = 20;
+constexpr int YUV_CY = 1220542, YUV_CVR = 1673527, YUV_CVG = -852492, YUV_CUG = -409993, YUV_CUB = 2116026;
+// rounding term and the -128 of both chroma samples folded into one constant per channel: R = (c + CVR * V + KR) >> 20 ...
+constexpr int YUV_KR = (1 << (YUV_SHIFT - 1)) - 128 * YUV_CVR;
+constexpr int YUV_KG = (1 << (YUV_SHIFT - 1)) - 128 * YUV_CVG - 128 * YUV_CUG;
+constexpr int YUV_KB = (1 << (YUV_SHIFT - 1)) - 128 * YUV_CUB;
+
+// Four values -> sat8(v >> 20) each, packed into a word: two v_ashr_pk_u8_i32 (D[7:0] = sat_u8(S0 >> S2), D[15:8] = sat_u8(S1 >> S2) into the
+// half of D that op_sel[3] names, the other half kept) instead of twelve shift / min / max / shift / or.  Written out because hipcc's own use of
+// the instruction assumes zeros in the half it keeps (image.hip, lanczos_v4_k).  Operands are ordinary VALU results: no wait states needed.
+__device__ __forceinline__ uint32_t yuv_pack4(int v0, int v1, int v2, int v3) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t r;
+    asm("v_ashr_pk_u8_i32 %0, %1, %2, %3" : "=v"(r) : "v"(v0), "v"(v1), "v"(YUV_SHIFT));
+    asm("v_ashr_pk_u8_i32 %0, %1, %2, %3 op_sel:[0,0,0,1]" : "+v"(r) : "v"(v2), "v"(v3), "v"(YUV_SHIFT));
+    return r;
+#else
+    return 0;
+#endif
+}
+
+// The chroma part of a 2x2 block's three channels (every product fits the 24-bit multiplier: coefficients < 2^23, samples < 2^8).
+struct YuvChroma { int r, g, b; };
+__device__ __forceinline__ YuvChroma yuv_chroma(int U, int V) {
+    YuvChroma t;
+    t.r = __mul24(V, YUV_CVR) + YUV_KR;
+    t.g = __mul24(V, YUV_CVG) + __mul24(U, YUV_CUG) + YUV_KG;
+    t.b = __mul24(U, YUV_CUB) + YUV_KB;
+    return t;
+}
+__device__ __forceinline__ int yuv_luma(int Y) { return __mul24(max(Y - 16, 0), YUV_CY); }
+
+// One pixel -> B | G << 8 | R << 16 (saturated bytes).
+__device__ __forceinline__ uint32_t yuv_bgr(int Y, int U, int V) {
+    const YuvChroma t = yuv_chroma(U, V);
+    const int c = yuv_luma(Y);
+    return yuv_pack4(c + t.b, c + t.g, c + t.r, 0);
+}
+
+typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+typedef uint16_t u16u __attribute__((aligned(1)));
+typedef uint32_t u32u __attribute__((aligned(1)));
+
+// grid (ceil(items / 256), batch).  WIDE: W % 16 == 0 and every row 16-byte aligned (the launcher checks) -- an item is 16 pixels of two
+// rows: two 16-byte luma loads, 16 bytes of chroma (NV12: one load, I420: 8 + 8), 2 x three 16-byte stores; 4.5 bytes of traffic per pixel
+// and nothing else.  Otherwise an item is one 2x2 block, byte by byte: any even W and H.
+template <int LAYOUT, bool WIDE>
+__global__ __launch_bounds__(256) void yuv420_to_bgr_k(const uint8_t *__restrict__ src, int H, int W, int pitch, int64_t chroma_offset,
+                                                       int64_t frame_stride, uint8_t *__restrict__ dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int ipr = WIDE ? W >> 4 : W >> 1;                      // items per row pair
+    if (i >= (H >> 1) * ipr) return;
+    const int by = i / ipr, bx = i - by * ipr;
+    const uint8_t *f = src + (size_t)blockIdx.y * (size_t)frame_stride;
+    const uint8_t *ch = f + chroma_offset;
+    const int cpitch = pitch >> 1;                               // I420 chroma rows
+    uint8_t *o = dst + (((size_t)blockIdx.y * H + 2 * by) * W) * 3;
+    if constexpr (WIDE) {
+        const uint8_t *yp = f + (size_t)(2 * by) * pitch + 16 * bx;
+        const u4v y0 = *reinterpret_cast<const u4v *>(yp), y1 = *reinterpret_cast<const u4v *>(yp + pitch);
+        uint32_t uw[4], vw[4];                                   // NV12: uw[j] = U V U V of pairs 2j, 2j + 1; I420: uw / vw[j] = four samples
+        if constexpr (LAYOUT == YUV_NV12) {
+            const u4v c = *reinterpret_cast<const u4v *>(ch + (size_t)by * pitch + 16 * bx);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) uw[j] = c[j];
+        } else {
+            const uint8_t *up = ch + (size_t)by * cpitch + 8 * bx;
+            const u2v u = *reinterpret_cast<const u2v *>(up), v = *reinterpret_cast<const u2v *>(up + (size_t)cpitch * (H >> 1));
+            uw[0] = u[0]; uw[1] = u[1]; vw[0] = v[0]; vw[1] = v[1];
+        }
+        YuvChroma t[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            int U, V;
+            if constexpr (LAYOUT == YUV_NV12) {
+                U = (int)((uw[k >> 1] >> (16 * (k & 1))) & 255u);
+                V = (int)((uw[k >> 1] >> (16 * (k & 1) + 8)) & 255u);
+            } else {
+                U = (int)((uw[k >> 2] >> (8 * (k & 3))) & 255u);
+                V = (int)((vw[k >> 2] >> (8 * (k & 3))) & 255u);
+            }
+            t[k] = yuv_chroma(U, V);
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const u4v y = r ? y1 : y0;
+            int val[48];                                         // the row's 48 output values before the shift, in byte order
+#pragma unroll
+            for (int x = 0; x < 16; ++x) {
+                const int c = yuv_luma((int)((y[x >> 2] >> (8 * (x & 3))) & 255u));
+                val[3 * x] = c + t[x >> 1].b; val[3 * x + 1] = c + t[x >> 1].g; val[3 * x + 2] = c + t[x >> 1].r;
+            }
+            u4v *op = reinterpret_cast<u4v *>(o + (size_t)r * W * 3 + 48 * bx);
+#pragma unroll
+            for (int w = 0; w < 3; ++w) {
+                u4v q;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int b = 16 * w + 4 * j;
+                    q[j] = yuv_pack4(val[b], val[b + 1], val[b + 2], val[b + 3]);
+                }
+                op[w] = q;
+            }
+        }
+    } else {
+        const uint8_t *yp = f + (size_t)(2 * by) * pitch + 2 * bx;
+        int U, V;
+        if constexpr (LAYOUT == YUV_NV12) {
+            const uint8_t *cp = ch + (size_t)by * pitch + 2 * bx;
+            U = cp[0]; V = cp[1];
+        } else {
+            const uint8_t *up = ch + (size_t)by * cpitch + bx;
+            U = up[0]; V = up[(size_t)cpitch * (H >> 1)];
+        }
+        const YuvChroma t = yuv_chroma(U, V);
+        o += (size_t)(2 * bx) * 3;
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int x = 0; x < 2; ++x) {
+                const int c = yuv_luma(yp[(size_t)r * pitch + x]);
+                const uint32_t p = yuv_pack4(c + t.b, c + t.g, c + t.r, 0);
+                uint8_t *q = o + ((size_t)r * W + x) * 3;
+                q[0] = (uint8_t)p; q[1] = (uint8_t)(p >> 8); q[2] = (uint8_t)(p >> 16);
+            }
+    }
+}
+
+// Pixels (sx, r) and (sx + 1, r) of a dense W x H frame at `f`, converted: t0, t1 = B | G << 8 | R << 16.  `second` false: the right edge,
+// both taps are pixel sx.  Two adjacent pixels are two adjacent luma bytes and at most two adjacent chroma blocks: one load each where the
+// row has the bytes, never one past the row's end.
+template <int LAYOUT>
+__device__ __forceinline__ void yuv_tap_pair(const uint8_t *__restrict__ f, int H, int W, int r, int sx, bool second, uint32_t &t0, uint32_t &t1) {
+    const uint8_t *yp = f + (size_t)r * W + sx;
+    int Y0, Y1;
+    if (second) { const uint32_t y = *reinterpret_cast<const u16u *>(yp); Y0 = (int)(y & 255u); Y1 = (int)(y >> 8); }
+    else Y0 = Y1 = yp[0];
+    int U0, V0, U1, V1;
+    const uint8_t *ch = f + (size_t)H * W;
+    if constexpr (LAYOUT == YUV_NV12) {
+        const int cx = sx & ~1;
+        const uint8_t *cp = ch + (size_t)(r >> 1) * W + cx;
+        uint32_t c;
+        if (cx + 4 <= W) c = *reinterpret_cast<const u32u *>(cp);
+        else { c = *reinterpret_cast<const u16u *>(cp); c |= c << 16; }
+        U0 = (int)(c & 255u); V0 = (int)((c >> 8) & 255u);
+        U1 = (sx & 1) ? (int)((c >> 16) & 255u) : U0; V1 = (sx & 1) ? (int)(c >> 24) : V0;
+    } else {
+        const int cw = W >> 1, cx = sx >> 1;
+        const uint8_t *up = ch + (size_t)(r >> 1) * cw + cx, *vp = up + (size_t)cw * (H >> 1);
+        uint32_t u, v;
+        if (cx + 2 <= cw) { u = *reinterpret_cast<const u16u *>(up); v = *reinterpret_cast<const u16u *>(vp); }
+        else { u = up[0]; u |= u << 8; v = vp[0]; v |= v << 8; }
+        U0 = (int)(u & 255u); V0 = (int)(v & 255u);
+        U1 = (sx & 1) ? (int)(u >> 8) : U0; V1 = (sx & 1) ? (int)(v >> 8) : V0;
+    }
+    t0 = yuv_bgr(Y0, U0, V0);
+    t1 = second ? yuv_bgr(Y1, U1, V1) : t0;
+}
+
+// Convert + flip + stretch of whole dense frames: every source tap is converted to saturated BGR bytes first, then the arithmetic of
+// crop_resize_k / crop_resize4_k (image.hip) runs on those bytes -- lin_coeff, 11-bit coefficients, the exact-2x INTER_AREA shortcut --
+// so the result is what yuv420_to_bgr_k followed by crop_resize gives, byte for byte, without the BGR frame ever reaching HBM.
+// grid (ceil(oh * (ow / NPX) / 256), n); a lane owns NPX (4: ow % 4 == 0, twelve bytes leave as three dwords; or 1) output pixels of a row.
+template <int LAYOUT, int NPX>
+__global__ __launch_bounds__(256) void yuv420_resize_k(const uint8_t *__restrict__ src, int H, int W, int flip, int oh, int ow,
+                                                       uint8_t *__restrict__ out) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    const int qpr = ow / NPX;
+    if (q >= oh * qpr) return;
+    const int dy = q / qpr, dx0 = (q - dy * qpr) * NPX;
+    const uint8_t *f = src + (size_t)blockIdx.y * ((size_t)H * W * 3 / 2);
+    uint8_t *o = out + (((size_t)blockIdx.y * oh + dy) * ow + dx0) * 3;
+    const bool area = W == 2 * ow && H == 2 * oh;                // exact 2x decimation: INTER_AREA shortcut
+    int sy, ya0 = 0, ya1 = 0, sy1;
+    if (area) { sy = 2 * dy; sy1 = sy + 1; }
+    else { lin_coeff(dy, oh, H, sy, ya0, ya1); sy1 = min(sy + 1, H - 1); }
+    // flip: row y of the (virtually) flipped BGR frame is stored row H-1-y, whose chroma is that of the STORED row (convert, then flip)
+    const int r0 = flip ? H - 1 - sy : sy, r1 = flip ? H - 1 - sy1 : sy1;
+    uint8_t px[NPX][3];
+#pragma unroll
+    for (int i = 0; i < NPX; ++i) {
+        int sx, xa0 = 0, xa1 = 0;
+        bool second = true;
+        if (area) sx = 2 * (dx0 + i);
+        else { lin_coeff(dx0 + i, ow, W, sx, xa0, xa1); second = sx + 1 <= W - 1; }      // at the right edge both taps are pixel sx
+        uint32_t t00, t01, t10, t11;
+        yuv_tap_pair<LAYOUT>(f, H, W, r0, sx, second, t00, t01);
+        yuv_tap_pair<LAYOUT>(f, H, W, r1, sx, second, t10, t11);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int p00 = (int)((t00 >> (8 * c)) & 255u), p01 = (int)((t01 >> (8 * c)) & 255u);
+            const int p10 = (int)((t10 >> (8 * c)) & 255u), p11 = (int)((t11 >> (8 * c)) & 255u);
+            if (area) {
+                px[i][c] = (uint8_t)((p00 + p01 + p10 + p11 + 2) >> 2);
+            } else {
+                const int h0 = p00 * xa0 + p01 * xa1;            // scale 2^11
+                const int h1 = p10 * xa0 + p11 * xa1;
+                const int v = (((ya0 * (h0 >> 4)) >> 16) + ((ya1 * (h1 >> 4)) >> 16) + 2) >> 2;
+                px[i][c] = (uint8_t)min(max(v, 0), 255);
+            }
+        }
+    }
+    if constexpr (NPX == 4) {
+        const uint8_t *b = &px[0][0];
+        uint32_t *ow32 = reinterpret_cast<uint32_t *>(o);
+#pragma unroll
+        for (int w = 0; w < 3; ++w)
+            ow32[w] = (uint32_t)b[4 * w] | ((uint32_t)b[4 * w + 1] << 8) | ((uint32_t)b[4 * w + 2] << 16) | ((uint32_t)b[4 * w + 3] << 24);
+    } else {
+        o[0] = px[0][0]; o[1] = px[0][1]; o[2] = px[0][2];
+    }
+}
+
+}  // namespace
+
+namespace ddk {
+
+// pitch / chroma_offset / frame_stride: 0 means dense (see dd_yuv420_to_bgr).  The caller has checked layout, even sizes and pitch.
+int yuv420_to_bgr(hipStream_t s, const uint8_t *src, int batch, int H, int W, int layout, int pitch, int64_t chroma_offset,
+                  int64_t frame_stride, uint8_t *dst) {
+    if (batch <= 0) return DD_OK;
+    if (pitch == 0) pitch = W;
+    if (chroma_offset == 0) chroma_offset = (int64_t)pitch * H;
+    if (frame_stride == 0) frame_stride = chroma_offset + (layout == YUV_NV12 ? (int64_t)pitch : (int64_t)(pitch / 2) * 2) * (H / 2);
+    const bool wide = W % 16 == 0 && pitch % 16 == 0 && chroma_offset % 16 == 0 && frame_stride % 16 == 0 &&
+                      ((int64_t)(pitch / 2) * (H / 2)) % 8 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
+                      (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+    const dim3 grid(dd_ceil_div((H / 2) * (wide ? W / 16 : W / 2), 256), batch), block(256);
+    if (layout == YUV_NV12) {
+        if (wide) hipLaunchKernelGGL((yuv420_to_bgr_k<YUV_NV12, true>), grid, block, 0, s, src, H, W, pitch, chroma_offset, frame_stride, dst);
+        else hipLaunchKernelGGL((yuv420_to_bgr_k<YUV_NV12, false>), grid, block, 0, s, src, H, W, pitch, chroma_offset, frame_stride, dst);
+    } else {
+        if (wide) hipLaunchKernelGGL((yuv420_to_bgr_k<YUV_I420, true>), grid, block, 0, s, src, H, W, pitch, chroma_offset, frame_stride, dst);
+        else hipLaunchKernelGGL((yuv420_to_bgr_k<YUV_I420, false>), grid, block, 0, s, src, H, W, pitch, chroma_offset, frame_stride, dst);
+    }
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
+// n dense frames [H * 3 / 2][W] -> BGR [n][oh][ow][3], rows read bottom-up when `flip`.
+int yuv420_resize(hipStream_t s, const uint8_t *src, int n, int H, int W, int layout, int flip, int oh, int ow, uint8_t *out) {
+    if (n <= 0) return DD_OK;
+    const bool quad = ow % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0;
+    const dim3 grid(dd_ceil_div(oh * (quad ? ow / 4 : ow), 256), n), block(256);
+    if (layout == YUV_NV12) {
+        if (quad) hipLaunchKernelGGL((yuv420_resize_k<YUV_NV12, 4>), grid, block, 0, s, src, H, W, flip, oh, ow, out);
+        else hipLaunchKernelGGL((yuv420_resize_k<YUV_NV12, 1>), grid, block, 0, s, src, H, W, flip, oh, ow, out);
+    } else {
+        if (quad) hipLaunchKernelGGL((yuv420_resize_k<YUV_I420, 4>), grid, block, 0, s, src, H, W, flip, oh, ow, out);
+        else hipLaunchKernelGGL((yuv420_resize_k<YUV_I420, 1>), grid, block, 0, s, src, H, W, flip, oh, ow, out);
+    }
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
+}  // namespace ddk
+
+extern "C" {
+
+int dd_yuv420_to_bgr(dd_ctx *ctx, const uint8_t *src, int batch, int H, int W, int layout, int pitch, int64_t chroma_offset,
+                     int64_t frame_stride, uint8_t *dst, void *stream) {
+    DD_REQUIRE(ctx, DD_E_ARG, "dd_yuv420_to_bgr: NULL ctx");
+    DD_REQUIRE(layout == YUV_NV12 || layout == YUV_I420, DD_E_ARG, "dd_yuv420_to_bgr: layout %d is neither 1 (NV12) nor 2 (I420)", layout);
+    DD_REQUIRE(batch >= 0 && batch <= 65535, DD_E_ARG, "dd_yuv420_to_bgr: batch %d outside 0..65535", batch);
+    DD_REQUIRE(W >= 2 && W % 2 == 0, DD_E_ARG, "dd_yuv420_to_bgr: W %d must be even and positive (4:2:0 chroma)", W);
+    DD_REQUIRE(H >= 2 && H % 2 == 0, DD_E_ARG, "dd_yuv420_to_bgr: H %d must be even and positive (4:2:0 chroma)", H);
+    DD_REQUIRE(pitch == 0 || pitch >= W, DD_E_ARG, "dd_yuv420_to_bgr: pitch %d below W %d", pitch, W);
+    DD_REQUIRE(layout != YUV_I420 || pitch % 2 == 0, DD_E_ARG, "dd_yuv420_to_bgr: pitch %d must be even for I420 (chroma rows use pitch / 2)", pitch);
+    const int64_t p = pitch ? pitch : W;
+    DD_REQUIRE(chroma_offset == 0 || chroma_offset >= p * (H - 1) + W, DD_E_ARG, "dd_yuv420_to_bgr: chroma_offset %lld inside the luma plane",
+               (long long)chroma_offset);
+    const int64_t co = chroma_offset ? chroma_offset : p * H;
+    const int64_t extent = layout == YUV_NV12 ? co + p * (H / 2 - 1) + W : co + (p / 2) * (H / 2) + (p / 2) * (H / 2 - 1) + W / 2;
+    DD_REQUIRE(frame_stride == 0 || frame_stride >= extent, DD_E_ARG, "dd_yuv420_to_bgr: frame_stride %lld below a frame's %lld bytes",
+               (long long)frame_stride, (long long)extent);
+    DD_DEVICE(ctx);
+    if (batch == 0) return DD_OK;
+    DD_REQUIRE(src && dst, DD_E_ARG, "dd_yuv420_to_bgr: NULL argument");
+    return ddk::yuv420_to_bgr(dd_pick_stream(ctx, stream), src, batch, H, W, layout, pitch, chroma_offset, frame_stride, dst);
+}
+
+}  // extern "C"

@@ -3,31 +3,49 @@
 A decoder thread writes raw BGR frames of S streams into a pinned slot (`host(slot)` is a numpy view of
 it), `submit(slot)` queues upload + cv2.flip(frame, 0) + cv2.resize(frame, input_size) on a private copy
 stream, and `acquire(slot)` hands the device frames to the hot path once its stream has been told to wait
-for them -- the host never blocks on a copy."""
+for them -- the host never blocks on a copy.
+
+With `pixel_format='nv12'` or `'i420'` a slot holds what a decoder produces itself (4:2:0 YUV, 1.5 bytes per pixel): half the bytes
+cross the host link, and the conversion to BGR (csrc/yuv.hip, OpenCV's BT.601 fixed-point arithmetic restated) runs on the copy
+stream in front of the flip + resize.  `yuv420_to_bgr` is the same conversion for frames that are already in device memory."""
 import ctypes
 import numpy as np
 
 from ._lib import lib, check, P
-from .runtime import default_context
+from .runtime import default_context, ptr
+
+PIXEL_FORMATS = {'bgr': 0, 'nv12': 1, 'i420': 2}
 
 
 class FrameIngest:
-    def __init__(self, n_streams, src_size, dst_size=None, slots=2, flip=False, context=None):
-        """src_size / dst_size: (width, height) like the reference's `input_size`; dst defaults to src."""
-        self.ctx = context or default_context()
-        self.S, self.slots = int(n_streams), int(slots)
+    def __init__(self, n_streams, src_size, dst_size=None, slots=2, flip=False, context=None, pixel_format='bgr'):
+        """src_size / dst_size: (width, height) like the reference's `input_size`; dst defaults to src.
+        pixel_format: what a slot holds, 'bgr' | 'nv12' | 'i420' (YUV needs an even width and height); the consumer always gets BGR."""
+        self._h = None
+        if pixel_format not in PIXEL_FORMATS:
+            raise ValueError("pixel_format %r is none of 'bgr', 'nv12', 'i420'" % (pixel_format,))
+        self.pixel_format = pixel_format
         self.sw, self.sh = src_size
         self.dw, self.dh = dst_size or src_size
+        if pixel_format != 'bgr' and (self.sw % 2 or self.sh % 2):
+            raise ValueError('%s frames need an even width and height, got %dx%d' % (pixel_format, self.sw, self.sh))
+        self.ctx = context or default_context()
+        self.S, self.slots = int(n_streams), int(slots)
         h = P()
-        check(lib().dd_ingest_create(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
-                                     ctypes.byref(h)), 'dd_ingest_create')
+        if pixel_format == 'bgr':
+            check(lib().dd_ingest_create(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
+                                         ctypes.byref(h)), 'dd_ingest_create')
+        else:
+            check(lib().dd_ingest_create_format(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
+                                                PIXEL_FORMATS[pixel_format], ctypes.byref(h)), 'dd_ingest_create_format')
         self._h = h
         self._host = []
         for i in range(self.slots):
             p, n = ctypes.c_void_p(), ctypes.c_int64()
             check(lib().dd_ingest_host_slot(self._h, i, ctypes.byref(p), ctypes.byref(n)), 'dd_ingest_host_slot')
             buf = (ctypes.c_uint8 * n.value).from_address(p.value)
-            self._host.append(np.frombuffer(buf, dtype=np.uint8).reshape(self.S, self.sh, self.sw, 3))
+            shape = (self.S, self.sh, self.sw, 3) if pixel_format == 'bgr' else (self.S, self.sh * 3 // 2, self.sw)
+            self._host.append(np.frombuffer(buf, dtype=np.uint8).reshape(shape))
 
     def __del__(self):
         try:
@@ -39,8 +57,8 @@ class FrameIngest:
             pass
 
     def host(self, slot):
-        """Pinned numpy view [S, src_h, src_w, 3] of a slot: fill it, then submit(slot).  Blocks until the slot's
-        previous upload has left the host buffer."""
+        """Pinned numpy view of a slot, [S, src_h, src_w, 3] for BGR and [S, src_h * 3 // 2, src_w] for NV12 / I420 (the shape cv2 gives
+        such frames): fill it, then submit(slot).  Blocks until the slot's previous upload has left the host buffer."""
         check(lib().dd_ingest_wait_uploaded(self._h, slot), 'dd_ingest_wait_uploaded')
         return self._host[slot]
 
@@ -69,3 +87,36 @@ class _DevView:
 
     def data_ptr(self):
         return self._addr
+
+
+def yuv420_to_bgr(src, height, width, layout, pitch=0, chroma_offset=0, frame_stride=0, out=None, context=None, stream=None):
+    """NV12 / I420 frames in device memory -> u8 [batch, height, width, 3] BGR device tensor (cv2.cvtColor COLOR_YUV2BGR_NV12 / _I420
+    restated).  src: u8 device tensor, [batch, height * 3 // 2, width] when dense; a decoder's padded surfaces are described by
+    pitch (bytes per luma row), chroma_offset (frame start -> chroma) and frame_stride, 0 meaning dense -- the batch is then what
+    fits.  out: a tensor to write into (the batch is then its first dimension).  The launch is queued on the context's stream (or
+    `stream`): `context.sync()` before torch reads the result on another stream."""
+    import torch
+    if layout not in ('nv12', 'i420'):
+        raise ValueError("layout %r is neither 'nv12' nor 'i420'" % (layout,))
+    ctx = context or default_context()
+    p = pitch or width
+    co = chroma_offset or p * height
+    if layout == 'nv12':
+        extent, dense = co + p * (height // 2 - 1) + width, co + p * (height // 2)
+    else:
+        extent, dense = co + (p // 2) * (height - 1) + width // 2, co + (p // 2) * height
+    stride = frame_stride or dense
+    if out is not None:
+        batch = out.shape[0]
+    else:
+        batch = max(0, (src.numel() - extent) // stride + 1)
+        out = torch.empty((batch, height, width, 3), dtype=torch.uint8, device=src.device)
+    if tuple(out.shape[1:]) != (height, width, 3) or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError('out must be a contiguous u8 [batch, %d, %d, 3] tensor' % (height, width))
+    if src.dtype != torch.uint8 or not src.is_contiguous():
+        raise ValueError('src must be a contiguous u8 tensor')
+    if batch > 0 and src.numel() < (batch - 1) * stride + extent:
+        raise ValueError('src holds %d bytes, %d frames need %d' % (src.numel(), batch, (batch - 1) * stride + extent))
+    check(lib().dd_yuv420_to_bgr(ctx.handle, ptr(src), batch, height, width, PIXEL_FORMATS[layout], pitch, chroma_offset, frame_stride,
+                                 ptr(out), stream), 'dd_yuv420_to_bgr')
+    return out

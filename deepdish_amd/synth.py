@@ -115,3 +115,31 @@ def tracker_scene(seed=0, n_obj=256, n_frames=60):
     """Config 4: T = D = 256 on a 4000x3000 canvas so boxes rarely overlap."""
     return Scene(seed=seed, n_obj=n_obj, width=4000, height=3000, n_frames=n_frames,
                  p_miss=0.02, churn=False, n_dup=0.0)
+
+
+def to_yuv420(frame_bgr, layout):
+    """BGR u8 [H, W, 3] (H, W even) -> NV12 / I420 u8 [H * 3 // 2, W], the shape cv2 gives such frames.  For synthetic inputs only: a
+    plain BT.601 studio-range forward transform in float, chroma averaged over each 2x2 block -- it pins nothing, the decoder side
+    (csrc/yuv.hip) is what the tests hold to the last bit."""
+    if layout not in ('nv12', 'i420'):
+        raise ValueError("layout %r is neither 'nv12' nor 'i420'" % (layout,))
+    f = np.asarray(frame_bgr, dtype=np.float64)
+    H, W = f.shape[:2]
+    if H % 2 or W % 2 or f.shape[2:] != (3,):
+        raise ValueError('to_yuv420 needs a BGR frame of even height and width, got %r' % (f.shape,))
+    b, g, r = f[..., 0], f[..., 1], f[..., 2]
+    y = 16.0 + (65.481 * r + 128.553 * g + 24.966 * b) / 255.0
+    u = 128.0 + (-37.797 * r - 74.203 * g + 112.0 * b) / 255.0
+    v = 128.0 + (112.0 * r - 93.786 * g - 18.214 * b) / 255.0
+    sub = lambda p: p.reshape(H // 2, 2, W // 2, 2).mean(axis=(1, 3))
+    q = lambda p: np.clip(np.rint(p), 0, 255).astype(np.uint8)
+    out = np.empty((H * 3 // 2, W), dtype=np.uint8)
+    out[:H] = q(y)
+    cu, cv = q(sub(u)), q(sub(v))
+    if layout == 'nv12':
+        c = out[H:].reshape(H // 2, W // 2, 2)
+        c[..., 0], c[..., 1] = cu, cv
+    else:
+        c = out[H:].reshape(2, H // 2, W // 2)
+        c[0], c[1] = cu, cv
+    return out

@@ -195,6 +195,19 @@ int dd_resize_lanczos_batch(dd_ctx *ctx, const uint8_t *src, int batch, int H, i
 int dd_resize_bilinear(dd_ctx *ctx, const uint8_t *src, int H, int W, int c,
                        uint8_t *dst, int h, int w, void *stream);
 
+/* 4:2:0 YUV -> BGR: cv2.cvtColor(frame, COLOR_YUV2BGR_NV12 / COLOR_YUV2BGR_I420) for frames already on the device (a hardware decoder's
+ * surfaces).  OpenCV's published BT.601 fixed-point arithmetic restated (csrc/yuv.hip; parity with OpenCV itself is unpinned, the library
+ * is absent): per pixel c = max(0, Y - 16) * 1220542, R = sat8((c + 524288 + 1673527 (V - 128)) >> 20), G = sat8((c + 524288
+ * - 852492 (V - 128) - 409993 (U - 128)) >> 20), B = sat8((c + 524288 + 2116026 (U - 128)) >> 20); the chroma of pixel (x, y) is that of
+ * block (x >> 1, y >> 1), no interpolation.
+ * src: `batch` frames of W x H (both even) u8.  layout 1 = NV12: H rows of luma, then H/2 rows of interleaved U,V pairs; layout 2 = I420: H
+ * rows of luma, then H/2 rows of U, then H/2 rows of V.  pitch: bytes per luma row, 0 = W; NV12 chroma rows use pitch, I420 chroma rows
+ * pitch / 2 (pitch even).  chroma_offset: bytes from a frame's start to its chroma, 0 = pitch * H (the I420 V plane follows the U plane's
+ * H/2 rows).  frame_stride: bytes between frames, 0 = dense.  dst: u8 dense [batch][H][W][3] BGR.
+ * DD_E_ARG (the message names the argument) for another layout, an odd or non-positive size, a pitch below W. */
+int dd_yuv420_to_bgr(dd_ctx *ctx, const uint8_t *src, int batch, int H, int W, int layout, int pitch, int64_t chroma_offset,
+                     int64_t frame_stride, uint8_t *dst, void *stream);
+
 /* ---------------------------------------------------------------- frame ingest
  * The CPU side of Pipeline.capture (deepdish.py:837-878): cv2.flip(frame, 0) (:864) + cv2.resize(frame,
  * input_size) (:867) on frames that a decoder put in host memory.  A ring of `slots` pinned host buffers,
@@ -205,6 +218,14 @@ int dd_resize_bilinear(dd_ctx *ctx, const uint8_t *src, int H, int W, int c,
 typedef struct dd_ingest dd_ingest;
 int dd_ingest_create(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip,
                      dd_ingest **out);
+/* The same ring for slots that hold what a decoder produces: pixel_format 0 = BGR (exactly dd_ingest_create), 1 = NV12, 2 = I420 (layouts
+ * as dd_yuv420_to_bgr, dense; src_h and src_w even, else DD_E_ARG naming the value).  A YUV slot and its device twin are
+ * n_streams * src_h * src_w * 3 / 2 bytes -- half the bytes per frame on the host link and in pinned memory; dd_ingest_submit converts on
+ * the copy stream, then flips and stretches the BGR frame as above (one launch for all three; DD_INGEST_YUV_FUSED=0, read here, selects
+ * convert-into-a-staging-buffer + the BGR ring's resize launch: the same bytes).  The consumer still receives BGR
+ * [n_streams][dst_h][dst_w][3]; submit / acquire / release are unchanged. */
+int dd_ingest_create_format(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip,
+                            int pixel_format, dd_ingest **out);
 int dd_ingest_destroy(dd_ingest *g);
 int dd_ingest_host_slot(dd_ingest *g, int slot, uint8_t **host_ptr, int64_t *n_bytes);
 int dd_ingest_wait_uploaded(dd_ingest *g, int slot);    /* host may overwrite the pinned slot after this returns */

@@ -1,0 +1,246 @@
+"""GPU: NV12 / I420 frames through the converter (csrc/yuv.hip) and the ingest ring, against tests/yuv_ref.py -- equality only.
+The ring's flip + resize is held to the oracle's restatement of cv2 INTER_LINEAR applied to the converted frame (OpenCV itself is
+absent: unpinned), once fused (one launch) and once, in a fresh child process with DD_INGEST_YUV_FUSED=0, as convert + resize.
+
+Run as a script (`python tests/test_gpu_ingest_yuv.py out.npz`) this file is that child: it pushes every ring case through a
+FrameIngest and saves what came out."""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
+import yuv_ref  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+LAYOUTS = ('nv12', 'i420')
+S = 3
+# the geometries of test_gpu_ingest.py::test_ingest_flip_resize_vs_oracle, plus one whose output width is no multiple of 4
+RING_GEOMETRIES = [((1280, 720), (640, 480), False), ((1280, 960), (640, 480), True), ((480, 360), (640, 480), True),
+                   ((640, 480), (640, 480), False), ((640, 480), (640, 480), True), ((70, 34), (30, 22), True)]
+RING_CASES = [(layout,) + g for layout in LAYOUTS for g in RING_GEOMETRIES]
+
+
+def _read(ctx, addr, shape):
+    """Device bytes at `addr` -> numpy (after the context's stream has drained)."""
+    import torch
+    ctx.sync()
+    out = torch.empty(shape, dtype=torch.uint8, device=f'cuda:{ctx.device}')
+    hip = ctypes.CDLL('libamdhip64.so')
+    rc = hip.hipMemcpy(ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(addr), ctypes.c_size_t(int(np.prod(shape))), 3)      # device -> device
+    assert rc == 0
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+def _ring_input(i):
+    _, src, _, _ = RING_CASES[i]
+    return np.random.default_rng(100 + i).integers(0, 256, (S, src[1] * 3 // 2, src[0]), dtype=np.uint8)
+
+
+def _run_ring(i):
+    from deepdish_amd.ingest import FrameIngest
+    layout, src, dst, flip = RING_CASES[i]
+    ing = FrameIngest(S, src, dst, slots=2, flip=flip, pixel_format=layout)
+    ing.host(1)[...] = _ring_input(i)
+    ing.submit(1)
+    got = _read(ing.ctx, ing.acquire(1), (S, dst[1], dst[0], 3))
+    ing.release(1)
+    return got
+
+
+# ------------------------------------------------------------------ converter vs yuv_ref
+def _convert(raw, H, W, layout, n, **kw):
+    """raw (flat u8) -> BGR through yuv420_to_bgr, written into the middle of a sentinel-filled buffer that must stay intact around it."""
+    import torch
+    from deepdish_amd.ingest import yuv420_to_bgr
+    from deepdish_amd.runtime import default_context
+    ctx = default_context()
+    lead, tail, nb = 64, 256, n * H * W * 3
+    buf = torch.full((lead + nb + tail,), 0xA5, dtype=torch.uint8, device='cuda')
+    torch.cuda.synchronize()
+    out = buf[lead:lead + nb].view(n, H, W, 3)
+    src = torch.from_numpy(raw).cuda()
+    torch.cuda.synchronize()                                      # the upload ran on torch's stream, the conversion runs on the context's
+    r = yuv420_to_bgr(src, H, W, layout, out=out, context=ctx, **kw)
+    assert r is out
+    ctx.sync()
+    host = buf.cpu().numpy()
+    assert (host[:lead] == 0xA5).all() and (host[lead + nb:] == 0xA5).all(), 'bytes outside the frames were written'
+    return host[lead:lead + nb].reshape(n, H, W, 3)
+
+
+@pytest.mark.parametrize('layout', LAYOUTS)
+@pytest.mark.parametrize('W,H', [(2, 2), (18, 6), (70, 34), (640, 480)])
+def test_converter_vs_ref(layout, W, H):
+    """Random bytes, dense frames: (2, 2) one block, (18, 6) an odd number of chroma rows, (70, 34) the block-per-lane kernel over
+    more than one workgroup, (640, 480) the 16-pixels-per-lane kernel."""
+    raw = np.random.default_rng(W * 1000 + H).integers(0, 256, (S, H * 3 // 2, W), dtype=np.uint8)
+    got = _convert(raw.reshape(-1), H, W, layout, S)
+    for z in range(S):
+        np.testing.assert_array_equal(got[z], yuv_ref.yuv420_to_bgr(raw[z], H, W, layout))
+
+
+@pytest.mark.parametrize('layout', LAYOUTS)
+@pytest.mark.parametrize('W,H,pad,co_extra,fs_extra', [(70, 34, 14, 10, 33), (640, 480, 16, 32, 64)])
+def test_converter_padded_surfaces(layout, W, H, pad, co_extra, fs_extra):
+    """pitch = W + pad with the chroma and the next frame further away than dense: a decoder's padded surfaces.  W + 14 takes the
+    block-per-lane kernel, 640 + 16 with 16-byte multiples everywhere the wide one."""
+    pitch = W + pad
+    co = pitch * H + co_extra
+    plane = pitch * (H // 2) if layout == 'nv12' else (pitch // 2) * H
+    stride = co + plane + fs_extra
+    raw = np.random.default_rng(7 + W).integers(0, 256, S * stride, dtype=np.uint8)
+    got = _convert(raw, H, W, layout, S, pitch=pitch, chroma_offset=co, frame_stride=stride)
+    for z in range(S):
+        np.testing.assert_array_equal(got[z], yuv_ref.yuv420_to_bgr(raw[z * stride:(z + 1) * stride], H, W, layout, pitch, co))
+
+
+@pytest.fixture(scope='module')
+def every_triple():
+    """One 4096 x 4096 frame whose 2x2 blocks enumerate all 2^24 (Y, U, V) triples: block k = by * 2048 + bx has U = k & 255,
+    V = (k >> 8) & 255 and luma 4 ((k >> 16) & 63) + {0, 1, 2, 3}.  -> (Y, U, V planes, the reference's BGR)."""
+    k = np.arange(2048 * 2048, dtype=np.int64).reshape(2048, 2048)
+    U, V = (k & 255).astype(np.uint8), ((k >> 8) & 255).astype(np.uint8)
+    Y = np.empty((4096, 4096), np.uint8)
+    base = (4 * ((k >> 16) & 63)).astype(np.uint8)
+    Y[0::2, 0::2], Y[0::2, 1::2], Y[1::2, 0::2], Y[1::2, 1::2] = base, base + 1, base + 2, base + 3
+    up = lambda c: np.repeat(np.repeat(c, 2, axis=0), 2, axis=1)
+    want = yuv_ref.yuv_to_bgr(Y, up(U), up(V))
+    return Y, U, V, want
+
+
+@pytest.mark.parametrize('layout', LAYOUTS)
+def test_every_input_once(layout, every_triple):
+    Y, U, V, want = every_triple
+    chroma = np.stack([U, V], axis=-1).reshape(2048, 4096) if layout == 'nv12' else np.concatenate([U.reshape(1024, 4096), V.reshape(1024, 4096)])
+    raw = np.concatenate([Y, chroma])
+    got = _convert(raw.reshape(-1), 4096, 4096, layout, 1)
+    assert np.array_equal(got[0], want)
+
+
+# ------------------------------------------------------------------ the ring
+@pytest.fixture(scope='module')
+def two_launch_outputs(tmp_path_factory):
+    """Every ring case once more in ONE fresh child process with DD_INGEST_YUV_FUSED=0 (read when a ring is created)."""
+    path = str(tmp_path_factory.mktemp('yuv') / 'two_launch.npz')
+    env = dict(os.environ, DD_INGEST_YUV_FUSED='0')
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), path], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    with np.load(path) as z:
+        return {name: z[name] for name in z.files}
+
+
+@pytest.mark.parametrize('i', range(len(RING_CASES)), ids=['%s-%dx%d-%dx%d-%s' % (c[0], *c[1], *c[2], 'flip' if c[3] else 'noflip') for c in RING_CASES])
+def test_ring_flip_resize_vs_oracle(i, two_launch_outputs):
+    from oracle import image_np
+    layout, src, dst, flip = RING_CASES[i]
+    raw = _ring_input(i)
+    assert os.environ.get('DD_INGEST_YUV_FUSED', '1') != '0'
+    got = _run_ring(i)
+    for z in range(S):
+        img = yuv_ref.yuv420_to_bgr(raw[z], src[1], src[0], layout)
+        if flip:
+            img = img[::-1]                                       # convert, then cv2.flip(frame, 0), deepdish.py:864
+        want = image_np.resize_linear_u8(np.ascontiguousarray(img), dst[0], dst[1]) if src != dst else img
+        np.testing.assert_array_equal(got[z], want)
+    np.testing.assert_array_equal(two_launch_outputs['case%d' % i], got)
+
+
+@pytest.mark.parametrize('layout', LAYOUTS)
+def test_ring_feeds_the_pipeline(layout):
+    """The look-ahead loop of test_gpu_ingest.py::test_ingest_ring_with_detector_look_ahead with YUV slots: the detector's own rows (uint8
+    synthetic SSD, every label wanted), the tracks and the counts are those of a run that is handed yuv_ref's BGR of the same buffers."""
+    import torch
+    from deepdish_amd.ingest import FrameIngest
+    from deepdish_amd.multipipe import MultiStreamPipeline
+    from deepdish_amd.pipeline import DEFAULT_LABELS
+    from deepdish_amd.synth import Scene, to_yuv420
+    F = 7
+    labels = [l.strip() for l in open(DEFAULT_LABELS)][1:]
+    wanted = [l for l in labels if l and l != '???']
+    scenes = [Scene(seed=40 + z, n_obj=6, n_frames=F) for z in range(S)]
+    yuv = [np.stack([to_yuv420(sc.frame(f), layout) for sc in scenes]) for f in range(F)]
+    bgr = [np.stack([yuv_ref.yuv420_to_bgr(y, 480, 640, layout) for y in fr]) for fr in yuv]
+    res = []
+    for mode in ('direct', 'ring'):
+        mp = MultiStreamPipeline(S, model='synthetic-ssd_mobilenet_v1-uint8', wanted_labels=wanted)
+        rows = []
+        if mode == 'direct':
+            dev = [torch.from_numpy(fr).cuda() for fr in bgr]
+            for f in range(F):
+                mp.step(dev[f], None, dev[f + 1] if f + 1 < F else None)
+                rows.append([mp.detections(z) for z in range(S)])
+        else:
+            ing = FrameIngest(S, (640, 480), slots=F, context=mp.ctx, pixel_format=layout)
+            assert ing.host(0).shape == (S, 720, 640)
+            for f in range(F):
+                ing.host(f)[...] = yuv[f]
+            ing.submit(0)
+            for f in range(F):
+                if f + 1 < F:
+                    ing.submit(f + 1)
+                nxt = ing.frames(f + 1, stream=mp.detector_stream()) if f + 1 < F else None
+                mp.step(ing.frames(f), None, nxt)
+                ing.release(f)
+                rows.append([mp.detections(z) for z in range(S)])
+        res.append((rows, [mp.tracker(z).table() for z in range(S)], mp.counts()))
+    n_rows = 0
+    for f in range(F):
+        for z in range(S):
+            a, b = res[0][0][f][z], res[1][0][f][z]
+            assert list(a[1]) == list(b[1])
+            np.testing.assert_array_equal(np.asarray(a[0], np.float64), np.asarray(b[0], np.float64))
+            np.testing.assert_array_equal(np.asarray(a[2], np.float64), np.asarray(b[2], np.float64))
+            n_rows += len(a[1])
+    assert n_rows > 0
+    for z in range(S):
+        np.testing.assert_array_equal(res[0][1][z][0], res[1][1][z][0])
+        np.testing.assert_array_equal(res[0][1][z][1], res[1][1][z][1])
+    np.testing.assert_array_equal(res[0][2], res[1][2])
+
+
+@pytest.mark.parametrize('layout', LAYOUTS)
+def test_slot_size(layout):
+    from deepdish_amd.ingest import FrameIngest
+    H, W = 34, 70
+    ing = FrameIngest(S, (W, H), slots=2, pixel_format=layout)
+    for slot in range(2):
+        assert ing.host(slot).nbytes == S * H * W * 3 // 2
+        assert ing.host(slot).shape == (S, H * 3 // 2, W)
+    assert ing.frames(0).shape == (S, H, W, 3)
+
+
+def test_bad_arguments_raise_before_anything_is_allocated():
+    from deepdish_amd._lib import lib, P
+    from deepdish_amd.ingest import FrameIngest
+    from deepdish_amd.runtime import default_context
+    with pytest.raises(ValueError, match='yuyv'):
+        FrameIngest(S, (640, 480), pixel_format='yuyv')
+    with pytest.raises(ValueError, match='641'):
+        FrameIngest(S, (641, 480), pixel_format='nv12')
+    with pytest.raises(ValueError, match='479'):
+        FrameIngest(S, (640, 479), pixel_format='i420')
+    # the C entry itself: a code, the message names the value, and no handle comes back
+    ctx = default_context()
+    h = P()
+    assert lib().dd_ingest_create_format(ctx.handle, 2, S, 480, 641, 480, 641, 0, 1, ctypes.byref(h)) < 0
+    assert b'src_w 641' in lib().dd_last_error() and not h.value
+    assert lib().dd_ingest_create_format(ctx.handle, 2, S, 480, 640, 480, 640, 0, 3, ctypes.byref(h)) < 0
+    assert b'pixel_format 3' in lib().dd_last_error() and not h.value
+    assert lib().dd_yuv420_to_bgr(ctx.handle, None, 1, 480, 641, 1, 0, 0, 0, None, None) < 0
+    assert b'W 641' in lib().dd_last_error()
+    assert lib().dd_yuv420_to_bgr(ctx.handle, None, 1, 480, 640, 1, 600, 0, 0, None, None) < 0
+    assert b'pitch 600' in lib().dd_last_error()
+    assert lib().dd_yuv420_to_bgr(ctx.handle, None, 1, 480, 640, 5, 0, 0, 0, None, None) < 0
+    assert b'layout 5' in lib().dd_last_error()
+
+
+if __name__ == '__main__':
+    np.savez(sys.argv[1], **{'case%d' % i: _run_ring(i) for i in range(len(RING_CASES))})
