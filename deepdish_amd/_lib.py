@@ -55,6 +55,8 @@ SIGNATURES = {
     'dd_fake_encode': [P, P, c_int, c_int, P, P],
     'dd_resize_lanczos': [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, P],
     'dd_resize_lanczos_batch': [P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P],
+    'dd_resize_lanczos_plan': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                               POINTER(c_int)],
     'dd_resize_bilinear': [P, P, c_int, c_int, c_int, P, c_int, c_int, P],
     'dd_yuv420_to_bgr': [P, P, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, P, P],
     'dd_ingest_create': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],

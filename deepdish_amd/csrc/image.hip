@@ -649,12 +649,18 @@ struct LanczosTable {
 double sinc_(double x) { if (x == 0.0) return 1.0; x *= M_PI; return sin(x) / x; }
 double lanczos_(double x) { return (-3.0 <= x && x < 3.0) ? sinc_(x) * sinc_(x / 3) : 0.0; }
 
+int lanczos_ksize(int in_size, int out_size) {                // taps per output, Pillow precompute_coeffs
+    double filterscale = (double)in_size / out_size;
+    if (filterscale < 1.0) filterscale = 1.0;
+    return (int)ceil(3.0 * filterscale) * 2 + 1;
+}
+
 LanczosTable make_table(int in_size, int out_size) {
     LanczosTable t;
     double scale = (double)in_size / out_size, filterscale = scale;
     if (filterscale < 1.0) filterscale = 1.0;
     const double support = 3.0 * filterscale;
-    t.ksize = (int)ceil(support) * 2 + 1;
+    t.ksize = lanczos_ksize(in_size, out_size);
     t.bounds.assign((size_t)out_size * 2, 0);
     t.kk.assign((size_t)out_size * t.ksize, 0);
     const double ss = 1.0 / filterscale;
@@ -705,7 +711,8 @@ int get_table(int device, int in_size, int out_size, DevTable *out) {
 // pairs of output column `col`; pitch = bytes per source row (the window of a column group must fit).
 struct BandTable { int n_groups = 0, ksteps = 0, n_cols = 0; int *start = nullptr; void *coef = nullptr; int *bias = nullptr; bool ok = false;
                    int *slab_u0 = nullptr; int n_slabs = 0, slab_width = 0; };     // lanczos_fused_k: first window byte of every 4 groups, widest union
-std::map<std::tuple<int, int, int, int, int, int, int>, BandTable> g_bands;     // (device, in, out, mode, src_c, swap, pitch)
+struct BandEntry { BandTable t; bool uploaded = false; std::vector<int> start, bias, u0; std::vector<int8_t> coef; };      // host copy until the first launch
+std::map<std::tuple<int, int, int, int, int, int, int>, BandEntry> g_bands;     // (device, in, out, mode, src_c, swap, pitch)
 
 template <class TapFn>
 bool build_band(int n_cols, int pitch, TapFn taps, std::vector<int> &start, std::vector<int8_t> &coef, std::vector<int> &bias, int &ksteps) {
@@ -753,15 +760,16 @@ bool build_band(int n_cols, int pitch, TapFn taps, std::vector<int> &start, std:
 }
 
 // mode 0: horizontal (in = W, out = w, columns (x, c), source bytes x*src_c + channel); mode 1: vertical (in = H, out = h).
-int get_band(int device, int in_size, int out_size, int mode, int src_c, int swap_rb, int pitch, BandTable *out) {
+// The table is built on the host and cached; it goes to the device the first time a caller asks for it with `upload` (a launch):
+// lanczos_plan only needs ok / ksteps / n_groups / slab_width and touches no device.
+int get_band(int device, int in_size, int out_size, int mode, int src_c, int swap_rb, int pitch, bool upload, BandTable *out) {
     std::lock_guard<std::mutex> lk(g_tab_mu);
     auto key = std::make_tuple(device, in_size, out_size, mode, src_c, swap_rb, pitch);
     auto it = g_bands.find(key);
     if (it == g_bands.end()) {
         const LanczosTable t = make_table(in_size, out_size);
-        BandTable b;
-        std::vector<int> start, bias;
-        std::vector<int8_t> coef;
+        BandEntry e;
+        BandTable &b = e.t;
         int ksteps = 0;
         const int n_cols = mode == 0 ? out_size * 3 : out_size;
         auto taps = [&](int c, std::vector<std::pair<int, int>> &v) {
@@ -773,37 +781,49 @@ int get_band(int device, int in_size, int out_size, int mode, int src_c, int swa
                 v.emplace_back(mode == 0 ? (lo + x) * src_c + (swap_rb ? 2 - ch : ch) : lo + x, k);
             }
         };
-        b.ok = build_band(n_cols, pitch, taps, start, coef, bias, ksteps);
+        b.ok = build_band(n_cols, pitch, taps, e.start, e.coef, e.bias, ksteps);
         if (b.ok) {
-            b.n_groups = (int)start.size(); b.ksteps = ksteps; b.n_cols = n_cols;
-            DD_HIP(hipMalloc(&b.start, start.size() * sizeof(int)));
-            DD_HIP(hipMalloc(&b.coef, coef.size()));
-            DD_HIP(hipMalloc(&b.bias, bias.size() * sizeof(int)));
-            DD_HIP(hipMemcpy(b.start, start.data(), start.size() * sizeof(int), hipMemcpyHostToDevice));
-            DD_HIP(hipMemcpy(b.coef, coef.data(), coef.size(), hipMemcpyHostToDevice));
-            DD_HIP(hipMemcpy(b.bias, bias.data(), bias.size() * sizeof(int), hipMemcpyHostToDevice));
+            b.n_groups = (int)e.start.size(); b.ksteps = ksteps; b.n_cols = n_cols;
             b.n_slabs = (b.n_groups + 3) / 4;
-            std::vector<int> u0(b.n_slabs);
+            e.u0.resize(b.n_slabs);
             for (int sl = 0; sl < b.n_slabs; ++sl) {
                 int lo = INT32_MAX, hi = 0;
-                for (int g = sl * 4; g < std::min(b.n_groups, sl * 4 + 4); ++g) { lo = std::min(lo, start[g]); hi = std::max(hi, start[g] + ksteps * 64); }
-                u0[sl] = lo;
+                for (int g = sl * 4; g < std::min(b.n_groups, sl * 4 + 4); ++g) { lo = std::min(lo, e.start[g]); hi = std::max(hi, e.start[g] + ksteps * 64); }
+                e.u0[sl] = lo;
                 b.slab_width = std::max(b.slab_width, hi - lo);
             }
-            DD_HIP(hipMalloc(&b.slab_u0, u0.size() * sizeof(int)));
-            DD_HIP(hipMemcpy(b.slab_u0, u0.data(), u0.size() * sizeof(int), hipMemcpyHostToDevice));
         }
-        it = g_bands.emplace(key, b).first;
+        it = g_bands.emplace(key, std::move(e)).first;
     }
-    *out = it->second;
+    BandEntry &e = it->second;
+    if (upload && e.t.ok && !e.uploaded) {
+        BandTable b = e.t;
+        DD_HIP(hipMalloc(&b.start, e.start.size() * sizeof(int)));
+        DD_HIP(hipMalloc(&b.coef, e.coef.size()));
+        DD_HIP(hipMalloc(&b.bias, e.bias.size() * sizeof(int)));
+        DD_HIP(hipMalloc(&b.slab_u0, e.u0.size() * sizeof(int)));
+        DD_HIP(hipMemcpy(b.start, e.start.data(), e.start.size() * sizeof(int), hipMemcpyHostToDevice));
+        DD_HIP(hipMemcpy(b.coef, e.coef.data(), e.coef.size(), hipMemcpyHostToDevice));
+        DD_HIP(hipMemcpy(b.bias, e.bias.data(), e.bias.size() * sizeof(int), hipMemcpyHostToDevice));
+        DD_HIP(hipMemcpy(b.slab_u0, e.u0.data(), e.u0.size() * sizeof(int), hipMemcpyHostToDevice));
+        e.t = b;
+        e.uploaded = true;
+        e.start = {}; e.bias = {}; e.u0 = {}; e.coef = {};
+    }
+    *out = e.t;
     return DD_OK;
 }
 
-int launch_band(hipStream_t s, const BandTable &b, const uint8_t *src, size_t src_img_stride, int R, int pitch_s, uint8_t *outT,
+// band_resample_wide_k's 16-byte / 4-byte stores of four rows at a time: what its output must allow
+bool band_wide_ok(int R, const void *outT, size_t out_img_stride, int pitch_o) {
+    return R % 4 == 0 && pitch_o % 4 == 0 && (reinterpret_cast<uintptr_t>(outT) & 3) == 0 && out_img_stride % 4 == 0;
+}
+
+// `wide`: lanczos_plan's choice between band_resample_wide_k and band_resample_k
+int launch_band(hipStream_t s, const BandTable &b, bool wide, const uint8_t *src, size_t src_img_stride, int R, int pitch_s, uint8_t *outT,
                 size_t out_img_stride, int pitch_o, int batch) {
     const i4v *cf = static_cast<const i4v *>(b.coef);
-    static const bool no_wide = getenv("DD_LANCZOS_NO_WIDE") != nullptr;
-    if (!no_wide && R % 4 == 0 && pitch_o % 4 == 0 && (reinterpret_cast<uintptr_t>(outT) & 3) == 0 && out_img_stride % 4 == 0) {
+    if (wide) {
         const int tiles = dd_ceil_div(R, 64);                     // 64-row iterations, 16-byte stores
         const int chunks = std::max(1, std::min(tiles, dd_ceil_div(8192, std::max(1, b.n_groups * batch))));
         const int tpc = dd_ceil_div(tiles, chunks);
@@ -863,6 +883,8 @@ int launch_lanczos_fused(hipStream_t s, int device, const BandTable &bh, const B
 
 namespace ddk {
 
+struct LanczosPlan { int h_step = DD_LANCZOS_H_NONE, v_step = DD_LANCZOS_V_NONE, h_ksteps = 0, v_ksteps = 0; };     // the DD_LANCZOS_H_* / _V_* of deepdish_hip.h
+
 // tools/generate_detections.py:63-80 on the host: int64 tlwh -> clipped crop rectangle.
 // Returns 1 when the reference would extract a patch, 0 when it returns None.
 int crop_box_host(const int64_t *b, int ph, int pw, int H, int W, int *sx, int *sy, int *cw, int *ch) {
@@ -914,71 +936,124 @@ int crop_resize(hipStream_t s, const uint8_t *frames, int H, int W, const void *
     return DD_OK;
 }
 
+// The one decision of resize_lanczos: which kernels turn src [H][W][src_c] into dst [h][w][3], from the geometry, the pointers'
+// alignment and the process's DD_LANCZOS_* switches.  Host only: the band tables are built and cached but not uploaded.
+int lanczos_plan(int device, const void *src, int H, int W, int src_c, int swap_rb, const void *dst, int h, int w, const void *tmp,
+                 int batch, LanczosPlan *pl) {
+    (void)batch;                                                  // no path depends on it today
+    static const int dbg = getenv("DD_LANCZOS_DEBUG") ? atoi(getenv("DD_LANCZOS_DEBUG")) : 0;      // 4: no matrix cores, 1: no lanczos_h_row_k, 2: no lanczos_v4_k
+    static const bool fused_off = getenv("DD_LANCZOS_FUSED") && atoi(getenv("DD_LANCZOS_FUSED")) == 0;
+    static const bool no_wide = getenv("DD_LANCZOS_NO_WIDE") != nullptr;
+    const uintptr_t a_src = reinterpret_cast<uintptr_t>(src), a_dst = reinterpret_cast<uintptr_t>(dst), a_tmp = reinterpret_cast<uintptr_t>(tmp);
+    *pl = LanczosPlan();
+    // ---- matrix-core path: both passes as banded i8 products through a transposed intermediate [w*3][H]
+    if (!(dbg & 4) && w != W && h != H && (src_c == 3 || src_c == 4) && (W * src_c) % 16 == 0 && H % 16 == 0 &&
+        (w * 3) % 4 == 0 && (a_src & 15) == 0 && (a_tmp & 15) == 0 && (a_dst & 3) == 0 && ((size_t)H * W * src_c) % 16 == 0) {
+        BandTable bh, bv;
+        int rc = get_band(device, W, w, 0, src_c, swap_rb, W * src_c, false, &bh);
+        if (rc != DD_OK) return rc;
+        rc = get_band(device, H, h, 1, 1, 0, H, false, &bv);
+        if (rc != DD_OK) return rc;
+        if (bh.ok && bv.ok) {
+            pl->h_ksteps = bh.ksteps;
+            pl->v_ksteps = bv.ksteps;
+            if (!fused_off && bh.ksteps <= 2 && bv.ksteps == 1 && bv.n_groups <= 4 * LF_NVG && H <= 512 && bh.slab_width <= 256 && W * src_c >= 256) {
+                pl->h_step = DD_LANCZOS_H_FUSED;
+                pl->v_step = DD_LANCZOS_V_FUSED;
+            } else {
+                pl->h_step = !no_wide && band_wide_ok(H, tmp, (size_t)w * 3 * H, H) ? DD_LANCZOS_H_BAND_WIDE : DD_LANCZOS_H_BAND_NARROW;
+                pl->v_step = !no_wide && band_wide_ok(w * 3, dst, (size_t)h * w * 3, w * 3) ? DD_LANCZOS_V_BAND_WIDE : DD_LANCZOS_V_BAND_NARROW;
+            }
+            return DD_OK;
+        }
+    }
+    const void *mid = src;
+    if (w != W) {
+        pl->h_step = (!(dbg & 1) && (W * src_c) % 16 == 0 && (a_src & 15) == 0 && W * src_c <= 6144 && lanczos_ksize(W, w) <= HTAPS) ? DD_LANCZOS_H_ROW
+                                                                                                                       : DD_LANCZOS_H_SCALAR;
+        mid = (h != H) ? tmp : dst;
+    } else if (src_c != 3 || swap_rb) {
+        const void *o = (h != H) ? tmp : dst;
+        pl->h_step = (src_c == 3 && swap_rb && (H * W) % 4 == 0 && ((a_src | reinterpret_cast<uintptr_t>(o)) & 3) == 0) ? DD_LANCZOS_H_SWAP_COPY
+                                                                                                                        : DD_LANCZOS_H_COPY;
+        mid = o;
+    }
+    if (h != H)
+        pl->v_step = (!(dbg & 2) && (w * 3) % 4 == 0 && (reinterpret_cast<uintptr_t>(mid) & 3) == 0 && (a_dst & 3) == 0) ? DD_LANCZOS_V_V4
+                                                                                                                         : DD_LANCZOS_V_SCALAR;
+    else if (mid != dst)
+        pl->v_step = DD_LANCZOS_V_MEMCPY;
+    return DD_OK;
+}
+
 // `batch` images of identical geometry, densely packed; tmp must hold batch*H*w*3 bytes.
 int resize_lanczos(hipStream_t s, int device, const uint8_t *src, int H, int W, int src_c, int swap_rb,
                    uint8_t *dst, int h, int w, uint8_t *tmp, int batch) {
-    // ---- matrix-core path: both passes as banded i8 products through a transposed intermediate [w*3][H]
-    static const int dbg_band = getenv("DD_LANCZOS_DEBUG") ? atoi(getenv("DD_LANCZOS_DEBUG")) : 0;
-    if (!(dbg_band & 4) && w != W && h != H && (src_c == 3 || src_c == 4) && (W * src_c) % 16 == 0 && H % 16 == 0 &&
-        (w * 3) % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(tmp) & 15) == 0 &&
-        (reinterpret_cast<uintptr_t>(dst) & 3) == 0 && ((size_t)H * W * src_c) % 16 == 0) {
+    LanczosPlan pl;
+    int rc = lanczos_plan(device, src, H, W, src_c, swap_rb, dst, h, w, tmp, batch, &pl);
+    if (rc != DD_OK) return rc;
+    if (pl.h_step == DD_LANCZOS_H_FUSED || pl.h_step == DD_LANCZOS_H_BAND_WIDE || pl.h_step == DD_LANCZOS_H_BAND_NARROW) {
         BandTable bh, bv;
-        int rc = get_band(device, W, w, 0, src_c, swap_rb, W * src_c, &bh);
-        if (rc != DD_OK) return rc;
-        rc = get_band(device, H, h, 1, 1, 0, H, &bv);
-        if (rc != DD_OK) return rc;
-        static const bool fused_off = getenv("DD_LANCZOS_FUSED") && atoi(getenv("DD_LANCZOS_FUSED")) == 0;
-        if (bh.ok && bv.ok && !fused_off && bh.ksteps <= 2 && bv.ksteps == 1 && bv.n_groups <= 4 * LF_NVG && H <= 512 && bh.slab_width <= 256 && W * src_c >= 256)
+        if ((rc = get_band(device, W, w, 0, src_c, swap_rb, W * src_c, true, &bh)) != DD_OK) return rc;
+        if ((rc = get_band(device, H, h, 1, 1, 0, H, true, &bv)) != DD_OK) return rc;
+        if (pl.h_step == DD_LANCZOS_H_FUSED)
             return launch_lanczos_fused(s, device, bh, bv, src, (size_t)H * W * src_c, H, W * src_c, dst, (size_t)h * w * 3, h, batch);
-        if (bh.ok && bv.ok) {
-            rc = launch_band(s, bh, src, (size_t)H * W * src_c, H, W * src_c, tmp, (size_t)w * 3 * H, H, batch);
-            if (rc != DD_OK) return rc;
-            return launch_band(s, bv, tmp, (size_t)w * 3 * H, w * 3, H, dst, (size_t)h * w * 3, w * 3, batch);
-        }
+        rc = launch_band(s, bh, pl.h_step == DD_LANCZOS_H_BAND_WIDE, src, (size_t)H * W * src_c, H, W * src_c, tmp, (size_t)w * 3 * H, H, batch);
+        if (rc != DD_OK) return rc;
+        return launch_band(s, bv, pl.v_step == DD_LANCZOS_V_BAND_WIDE, tmp, (size_t)w * 3 * H, w * 3, H, dst, (size_t)h * w * 3, w * 3, batch);
     }
     const uint8_t *mid = src;
     int mid_c = src_c;
-    if (w != W) {
-        DevTable th;
-        int rc = get_table(device, W, w, &th);
-        if (rc != DD_OK) return rc;
-        uint8_t *o = (h != H) ? tmp : dst;
-        static const int dbg = getenv("DD_LANCZOS_DEBUG") ? atoi(getenv("DD_LANCZOS_DEBUG")) : 0;
-        if (!(dbg & 1) && (W * src_c) % 16 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && W * src_c <= 6144 &&
-            th.ksize <= HTAPS)
-            hipLaunchKernelGGL(lanczos_h_row_k, dim3(dd_ceil_div(H, HROWS), batch), dim3(320), (size_t)HROWS * W * src_c, s, src,
-                               H, W, src_c, swap_rb, th.bounds, th.kk, th.ksize, w, o);
-        else
-            hipLaunchKernelGGL(lanczos_h_k, dim3(dd_ceil_div(H * w, 256), batch), dim3(256), 0, s, src, H, W, src_c, swap_rb,
-                               th.bounds, th.kk, th.ksize, w, o);
-        DD_LAUNCH_CHECK();
-        mid = o;
-        mid_c = 3;
-    } else if (src_c != 3 || swap_rb) {
-        uint8_t *o = (h != H) ? tmp : dst;
-        if (src_c == 3 && swap_rb && (H * W) % 4 == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(o)) & 3) == 0)
-            hipLaunchKernelGGL(copy_swap_rb4_k, dim3(dd_ceil_div(H * W / 4, 256), batch), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(src),
-                               H * W / 4, reinterpret_cast<uint32_t *>(o));
-        else
-            hipLaunchKernelGGL(copy_rgb_k, dim3(dd_ceil_div(H * W, 256), batch), dim3(256), 0, s, src, H * W, src_c, swap_rb, o);
-        DD_LAUNCH_CHECK();
-        mid = o;
-        mid_c = 3;
+    uint8_t *o = (h != H) ? tmp : dst;                            // where the horizontal step writes
+    switch (pl.h_step) {
+        case DD_LANCZOS_H_ROW:
+        case DD_LANCZOS_H_SCALAR: {
+            DevTable th;
+            if ((rc = get_table(device, W, w, &th)) != DD_OK) return rc;
+            if (pl.h_step == DD_LANCZOS_H_ROW)
+                hipLaunchKernelGGL(lanczos_h_row_k, dim3(dd_ceil_div(H, HROWS), batch), dim3(320), (size_t)HROWS * W * src_c, s, src,
+                                   H, W, src_c, swap_rb, th.bounds, th.kk, th.ksize, w, o);
+            else
+                hipLaunchKernelGGL(lanczos_h_k, dim3(dd_ceil_div(H * w, 256), batch), dim3(256), 0, s, src, H, W, src_c, swap_rb,
+                                   th.bounds, th.kk, th.ksize, w, o);
+            DD_LAUNCH_CHECK();
+            mid = o;
+            mid_c = 3;
+            break;
+        }
+        case DD_LANCZOS_H_SWAP_COPY:
+        case DD_LANCZOS_H_COPY:
+            if (pl.h_step == DD_LANCZOS_H_SWAP_COPY)
+                hipLaunchKernelGGL(copy_swap_rb4_k, dim3(dd_ceil_div(H * W / 4, 256), batch), dim3(256), 0, s, reinterpret_cast<const uint32_t *>(src),
+                                   H * W / 4, reinterpret_cast<uint32_t *>(o));
+            else
+                hipLaunchKernelGGL(copy_rgb_k, dim3(dd_ceil_div(H * W, 256), batch), dim3(256), 0, s, src, H * W, src_c, swap_rb, o);
+            DD_LAUNCH_CHECK();
+            mid = o;
+            mid_c = 3;
+            break;
+        default:
+            break;
     }
-    if (h != H) {
-        DevTable tv;
-        int rc = get_table(device, H, h, &tv);
-        if (rc != DD_OK) return rc;
-        static const int dbg2 = getenv("DD_LANCZOS_DEBUG") ? atoi(getenv("DD_LANCZOS_DEBUG")) : 0;
-        if (!(dbg2 & 2) && (w * 3) % 4 == 0 && (reinterpret_cast<uintptr_t>(mid) & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 3) == 0)
-            hipLaunchKernelGGL(lanczos_v4_k, dim3(dd_ceil_div(h * (w * 3 / 4), 256), batch), dim3(256), 0, s, mid, H, w * 3,
-                               tv.bounds, tv.kk, tv.ksize, h, dst);
-        else
-            hipLaunchKernelGGL(lanczos_v_k, dim3(dd_ceil_div(h * w * 3, 256), batch), dim3(256), 0, s, mid, H, w * 3, tv.bounds,
-                               tv.kk, tv.ksize, h, dst);
-        DD_LAUNCH_CHECK();
-    } else if (mid != dst) {
-        DD_HIP(hipMemcpyAsync(dst, mid, (size_t)batch * H * w * mid_c, hipMemcpyDeviceToDevice, s));
+    switch (pl.v_step) {
+        case DD_LANCZOS_V_V4:
+        case DD_LANCZOS_V_SCALAR: {
+            DevTable tv;
+            if ((rc = get_table(device, H, h, &tv)) != DD_OK) return rc;
+            if (pl.v_step == DD_LANCZOS_V_V4)
+                hipLaunchKernelGGL(lanczos_v4_k, dim3(dd_ceil_div(h * (w * 3 / 4), 256), batch), dim3(256), 0, s, mid, H, w * 3,
+                                   tv.bounds, tv.kk, tv.ksize, h, dst);
+            else
+                hipLaunchKernelGGL(lanczos_v_k, dim3(dd_ceil_div(h * w * 3, 256), batch), dim3(256), 0, s, mid, H, w * 3, tv.bounds,
+                                   tv.kk, tv.ksize, h, dst);
+            DD_LAUNCH_CHECK();
+            break;
+        }
+        case DD_LANCZOS_V_MEMCPY:
+            DD_HIP(hipMemcpyAsync(dst, mid, (size_t)batch * H * w * mid_c, hipMemcpyDeviceToDevice, s));
+            break;
+        default:
+            break;
     }
     return DD_OK;
 }
@@ -1050,6 +1125,26 @@ int dd_resize_lanczos(dd_ctx *ctx, const uint8_t *src, int H, int W, int src_c, 
     if ((rc = ctx->scratch[3].reserve((size_t)H * w * 3 + 64)) != DD_OK) return rc;
     return ddk::resize_lanczos(dd_pick_stream(ctx, stream), ctx->device, src, H, W, src_c, swap_rb, dst, h, w,
                                ctx->scratch[3].as<uint8_t>(), 1);
+}
+
+int dd_resize_lanczos_plan(dd_ctx *ctx, int H, int W, int src_c, int swap_rb, int h, int w, int batch, const void *src, const void *dst,
+                           const void *tmp, int *h_step, int *v_step, int *h_ksteps, int *v_ksteps) {
+    DD_REQUIRE((ctx || tmp) && batch > 0 && H > 0 && W > 0 && h > 0 && w > 0, DD_E_ARG, "dd_resize_lanczos_plan: bad argument");
+    DD_REQUIRE(src_c == 3 || src_c == 4, DD_E_ARG, "dd_resize_lanczos_plan: src_c must be 3 or 4");
+    if (!tmp) {                                                   // the intermediate the real call would use
+        DD_DEVICE(ctx);
+        int rc;
+        if ((rc = ctx->scratch[3].reserve((size_t)batch * H * w * 3 + 64)) != DD_OK) return rc;
+        tmp = ctx->scratch[3].p;
+    }
+    ddk::LanczosPlan pl;
+    const int rc = ddk::lanczos_plan(ctx ? ctx->device : 0, src, H, W, src_c, swap_rb, dst, h, w, tmp, batch, &pl);
+    if (rc != DD_OK) return rc;
+    if (h_step) *h_step = pl.h_step;
+    if (v_step) *v_step = pl.v_step;
+    if (h_ksteps) *h_ksteps = pl.h_ksteps;
+    if (v_ksteps) *v_ksteps = pl.v_ksteps;
+    return DD_OK;
 }
 
 int dd_resize_lanczos_batch(dd_ctx *ctx, const uint8_t *src, int batch, int H, int W, int src_c, int swap_rb, uint8_t *dst,

@@ -191,6 +191,29 @@ int dd_resize_lanczos(dd_ctx *ctx, const uint8_t *src, int H, int W, int src_c, 
  * does with a step's frames: one launch, both passes through LDS when the geometry allows). */
 int dd_resize_lanczos_batch(dd_ctx *ctx, const uint8_t *src, int batch, int H, int W, int src_c, int swap_rb,
                             uint8_t *dst, int h, int w, void *stream);
+/* Which kernels dd_resize_lanczos / dd_resize_lanczos_batch run for a geometry: the decision those calls themselves switch on (and the
+ * DD_LANCZOS_* switches of the process), answered without launching anything.  src / dst: the pointers the real call would be given (only
+ * their alignment, and whether they are the same, matters); tmp: the intermediate, NULL = the context's own scratch as the real call
+ * reserves it (ctx may be NULL when tmp is given: nothing touches the device).  Any out pointer may be NULL.
+ * *h_step: what turns src [H][W][src_c] into 3-channel rows of w pixels; *v_step: what turns those into h rows.
+ * *h_ksteps / *v_ksteps: 64-byte window steps of the banded tables (1..4) for the band and fused steps, 0 for the others. */
+#define DD_LANCZOS_H_NONE 0        /* w == W, 3 channels, no swap: the vertical step reads src */
+#define DD_LANCZOS_H_COPY 1        /* w == W: copy_rgb_k (4 -> 3 channels and / or red-blue swap, a byte at a time) */
+#define DD_LANCZOS_H_SWAP_COPY 2   /* w == W: copy_swap_rb4_k (3 channels, red-blue swap, four pixels per thread) */
+#define DD_LANCZOS_H_ROW 3         /* lanczos_h_row_k (source rows staged in LDS) */
+#define DD_LANCZOS_H_SCALAR 4      /* lanczos_h_k */
+#define DD_LANCZOS_H_BAND_WIDE 5   /* band_resample_wide_k into the transposed intermediate */
+#define DD_LANCZOS_H_BAND_NARROW 6 /* band_resample_k into the transposed intermediate */
+#define DD_LANCZOS_H_FUSED 7       /* lanczos_fused_k: both passes in one launch */
+#define DD_LANCZOS_V_NONE 0        /* h == H and the horizontal step wrote dst (or src is dst) */
+#define DD_LANCZOS_V_MEMCPY 1      /* h == H, w == W, nothing to convert: device-to-device copy */
+#define DD_LANCZOS_V_V4 2          /* lanczos_v4_k (four bytes per thread) */
+#define DD_LANCZOS_V_SCALAR 3      /* lanczos_v_k */
+#define DD_LANCZOS_V_BAND_WIDE 4   /* band_resample_wide_k out of the transposed intermediate */
+#define DD_LANCZOS_V_BAND_NARROW 5 /* band_resample_k out of the transposed intermediate */
+#define DD_LANCZOS_V_FUSED 6       /* lanczos_fused_k */
+int dd_resize_lanczos_plan(dd_ctx *ctx, int H, int W, int src_c, int swap_rb, int h, int w, int batch, const void *src,
+                           const void *dst, const void *tmp, int *h_step, int *v_step, int *h_ksteps, int *v_ksteps);
 /* cv2.resize INTER_LINEAR stretch as tools/tflite_object_detector.py:211 */
 int dd_resize_bilinear(dd_ctx *ctx, const uint8_t *src, int H, int W, int c,
                        uint8_t *dst, int h, int w, void *stream);

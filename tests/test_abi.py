@@ -29,6 +29,32 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert l.dd_version() >= 100
 
 
+def test_lanczos_plan_is_declared_and_answers_without_a_device():
+    """dd_resize_lanczos_plan is in the header, the binary and the binding, and -- given the intermediate's address -- decides from the
+    geometry and the alignments alone: no context, no GPU.  640x480 -> 300x300 is the one-launch form; 1080 rows are no multiple of 16, so
+    a 1080p frame takes the scalar kernels (41 taps: not the LDS-row one); an odd row length takes the byte-wise vertical kernel."""
+    import ctypes
+    from deepdish_amd._lib import lib, SIGNATURES
+    assert 'dd_resize_lanczos_plan' in _declared() and 'dd_resize_lanczos_plan' in SIGNATURES
+    assert len(_declared()) >= 100
+
+    def plan(H, W, c, swap, h, w, src=0x10000, dst=0x20040, tmp=0x30000):
+        out = [ctypes.c_int(-1) for _ in range(4)]
+        assert lib().dd_resize_lanczos_plan(None, H, W, c, swap, h, w, 1, src, dst, tmp, *[ctypes.byref(o) for o in out]) == 0
+        return tuple(o.value for o in out)
+    assert plan(480, 640, 3, 1, 300, 300) == (7, 6, 2, 1)          # DD_LANCZOS_H_FUSED, DD_LANCZOS_V_FUSED
+    assert plan(720, 1280, 3, 1, 300, 300)[:2] == (5, 4)           # band wide, both passes
+    assert plan(1080, 1920, 3, 1, 300, 300) == (4, 2, 0, 0)        # lanczos_h_k, lanczos_v4_k
+    assert plan(1080, 1920, 3, 1, 640, 640) == (3, 2, 0, 0)        # lanczos_h_row_k
+    assert plan(480, 640, 3, 1, 150, 150) == (4, 3, 0, 0)          # lanczos_v_k: 450-byte rows
+    assert plan(480, 640, 3, 1, 300, 300, dst=0x20041) == (3, 3, 0, 0)      # a destination that is not 4-byte aligned: no dword stores
+    assert plan(480, 640, 3, 0, 480, 640) == (0, 1, 0, 0) and plan(480, 640, 3, 0, 480, 640, dst=0x10000) == (0, 0, 0, 0)
+    assert lib().dd_resize_lanczos_plan(None, 480, 640, 3, 1, 300, 300, 1, None, None, None, None, None, None, None) < 0      # neither a context nor tmp
+    assert b'dd_resize_lanczos_plan' in lib().dd_last_error()
+    assert lib().dd_resize_lanczos_plan(None, 480, 640, 2, 1, 300, 300, 1, None, None, 0x30000, None, None, None, None) < 0
+    assert b'src_c' in lib().dd_last_error()
+
+
 def test_errors_are_codes_not_exceptions():
     from deepdish_amd._lib import lib
     l = lib()
