@@ -36,6 +36,9 @@ SIGNATURES = {
     'dd_nms_ssd': [P, P, P, c_int, c_double, P, P, P],
     'dd_lsap_host': [P, c_int, c_int, P, P],
     'dd_pyset_difference_order_host': [P, c_int, P, c_int, P, POINTER(c_int)],
+    'dd_lsap_batch': [P, P, P, P, P, c_int, P, P],
+    'dd_match_cascade': [P, c_int, P, P, c_int, c_int, P, P, c_double, c_double, c_int, P, POINTER(c_int), P, POINTER(c_int), P,
+                         POINTER(c_int)],
     'dd_tracker_create': [P, c_double, c_double, c_int, c_int, c_int, c_int, c_int, POINTER(P)],
     'dd_tracker_create_metric': [P, c_int, c_double, c_double, c_int, c_int, c_int, c_int, c_int, POINTER(P)],
     'dd_tracker_destroy': [P],
@@ -50,6 +53,9 @@ SIGNATURES = {
     'dd_tracker_next_id': [P, POINTER(c_int64)],
     'dd_tracker_last_cost': [P, P, P, c_int, POINTER(c_int), POINTER(c_int)],
     'dd_tracker_last_matches': [P, P, c_int, POINTER(c_int)],
+    'dd_tracker_set_association': [P, c_int],
+    'dd_tracker_association_stats': [P, POINTER(ctypes.c_longlong), POINTER(ctypes.c_longlong), POINTER(ctypes.c_longlong),
+                                     POINTER(ctypes.c_longlong)],
     'dd_crop_resize': [P, P, c_int, c_int, P, c_int, c_int, c_int, P, P, P],
     'dd_crop_resize_f64': [P, P, c_int, c_int, P, c_int, c_int, c_int, P, P, P],
     'dd_fake_encode': [P, P, c_int, c_int, P, P],
@@ -110,6 +116,7 @@ SIGNATURES = {
     'dd_pipeline_ssd_regular_nms': [P, c_int],
     'dd_pipeline_detector_skip_frames': [P, c_int],
     'dd_pipeline_metric': [P, c_int],
+    'dd_pipeline_association': [P, c_int],
     'dd_pipeline_step': [P, P, P, P, P, P],
     'dd_pipeline_step2': [P, P, P, P, P, P, P],
     'dd_pipeline_background_subtraction': [P, c_double, c_int],

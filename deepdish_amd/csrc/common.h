@@ -160,4 +160,11 @@ void pyset_difference_order(const std::vector<int> &a, const std::vector<int> &b
 int lsap(const double *cost, int nr, int nc, int *rows, int *cols);   // host; returns pair count or -1
 int gather_state(hipStream_t s, const double *means, const double *covs, const int *slots, int n,
                  double *out_means, double *out_covs);
+// the association decision of one stream (tracker.py:95-133 _match): host form (tracker.hip) and one wave per stream (assoc.hip).
+// matches: (row, det) pairs flattened.  app / iou: [T][n] row-major; state / tsu: per row.
+void match_decide_host(const double *app, const double *iou, int T, int n, const int *state, const int *tsu, double max_cos,
+                       double max_iou, int max_age, std::vector<int> &matches, std::vector<int> &un_rows, std::vector<int> &un_dets);
+size_t assoc_out_ints(int T, int n);   // ints one stream's decision takes in assoc_match's output
+int assoc_match(hipStream_t s, const double *cost, const int *row_state, const int *row_tsu, const int *desc, int n_streams,
+                double max_cos, double max_iou, int max_age, int *out);
 }  // namespace ddk

@@ -40,6 +40,7 @@ int ssd_finish(hipStream_t s, const float *boxes, const float *cls, const float 
 int tracker_group_create(dd_ctx *ctx, int n, double max_cos, double max_iou, int max_age, int n_init, int budget, int tcap,
                          int gcap, dd_tracker **out);
 int tracker_group_set_metric(dd_tracker *any, int metric);
+int tracker_group_set_association(dd_tracker *any, int where);
 int trackers_predict(dd_tracker **ts, int S);
 int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const float *feats, int feats_on_device,
                           const int *det_off);
@@ -400,6 +401,14 @@ int dd_pipeline_metric(dd_pipeline *p, int metric) {
     DD_REQUIRE(metric == 0 || metric == 1, DD_E_ARG, "dd_pipeline_metric: metric must be 0 (cosine) or 1 (euclidean), got %d", metric);
     DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, "dd_pipeline_metric: call before the first step");
     return ddk::tracker_group_set_metric(p->trks[0], metric);
+}
+
+// Where the pipeline's tracker group decides its association (dd_tracker_set_association for every stream's tracker at once): 0 = on the
+// host from the cost matrices (the default), 1 = on the device (csrc/assoc.hip), the decisions being the same.  Between steps only.
+int dd_pipeline_association(dd_pipeline *p, int where) {
+    DD_REQUIRE(p, DD_E_ARG, "dd_pipeline_association: NULL pipeline");
+    DD_REQUIRE(where == 0 || where == 1, DD_E_ARG, "dd_pipeline_association: where must be 0 (host) or 1 (device), got %d", where);
+    return ddk::tracker_group_set_association(p->trks[0], where);
 }
 
 // deepdish.py:512,889: background subtraction on (ratio = --background-subtraction-ratio, default 0.25) or off

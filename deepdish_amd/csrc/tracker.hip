@@ -13,6 +13,8 @@
 //                            NN cost (exact-f32 MFMA + f64 Mahalanobis gate) and the IoU cost, ALL cascade
 //                            levels at once (the cost of a pair does not depend on the level);
 //             host        -- per stream: matching cascade + LSAP on the small cost matrices;
+//                            (under device association, csrc/assoc.hip: one more launch decides every stream, one wave each, and only
+//                            the three lists of each decision come to the host, which keeps the book-keeping);
 //             K2 "apply"  -- Kalman update / initiate + gallery append for the decided pairs;
 //             gather      -- means of all live / just-deleted tracks back to the host.
 // Layout: means[slot][8] f64, covs[slot][64] f64; a stream owns the slot range [slot_base, slot_base + tcap) of
@@ -37,6 +39,7 @@ constexpr double GATE_4DOF = 9.4877;      // kalman_filter.py:14
 constexpr double INFTY_COST = 1e5;        // linear_assignment.py:8
 enum { TENTATIVE = 1, CONFIRMED = 2, DELETED = 3 };   // track.py:15-17
 enum { METRIC_COSINE = 0, METRIC_EUCLIDEAN = 1 };     // nn_matching.py:126-132
+enum { ASSOC_HOST = 0, ASSOC_DEVICE = 1 };            // where the cascade and the assignment run
 
 // detection.py:43-50
 __device__ __forceinline__ void tlwh_to_xyah(const double *b, double z[4]) {
@@ -151,9 +154,17 @@ struct TrackerPool {
                                                           // (tab_stride always describes the d_tab the device holds, also on an error path)
     DevBuf d_tabupd;
     PinBuf h_tabupd;
-    DevBuf d_pred, d_in, d_feats_raw, d_feats_n, d_cost, d_pairs, d_gather;
-    PinBuf h_pred, h_in, h_cost, h_pairs, h_gather;
+    DevBuf d_pred, d_in, d_feats_raw, d_feats_n, d_cost, d_pairs, d_gather, d_assoc;
+    PinBuf h_pred, h_in, h_cost, h_pairs, h_gather, h_assoc;
     bool pred_inflight = false;
+    // where the association is decided (ASSOC_*), one setting per group, and what became of the group's updates so far
+    int assoc = 0;
+    bool upd_inflight = false;                            // between trackers_update_begin and trackers_update_end
+    bool dev_decided = false;                             // the current update's decisions come from assoc_match_k (h_assoc)
+    bool cost_on_host = false;                            // h_cost holds the current update's matrices (all of them)
+    std::vector<int> assoc_base;                          // per stream: where its decision sits in h_assoc, -1 = none (T or n is 0)
+    long long n_dev_updates = 0, n_host_updates = 0, n_fallback_streams = 0;
+    long long assoc_d2h_bytes = 0;                        // what the decisions brought to the host: cost matrices, or lists + handed-back matrices
     // phase state of the current group update
     std::vector<dd_tracker *> cur;
     std::vector<int> det_off, cost_base;
@@ -323,8 +334,8 @@ void pool_release(TrackerPool *p) {
     (void)hipFree(p->d_means); (void)hipFree(p->d_covs);
     for (float *a : p->arenas) (void)hipFree(a);
     (void)hipFree(p->d_arenas); (void)hipFree(p->d_tab);
-    for (DevBuf *b : {&p->d_pred, &p->d_in, &p->d_feats_raw, &p->d_feats_n, &p->d_cost, &p->d_pairs, &p->d_gather, &p->d_tabupd}) b->release();
-    for (PinBuf *b : {&p->h_pred, &p->h_in, &p->h_cost, &p->h_pairs, &p->h_gather, &p->h_tabupd}) b->release();
+    for (DevBuf *b : {&p->d_pred, &p->d_in, &p->d_feats_raw, &p->d_feats_n, &p->d_cost, &p->d_pairs, &p->d_gather, &p->d_tabupd, &p->d_assoc}) b->release();
+    for (PinBuf *b : {&p->h_pred, &p->h_in, &p->h_cost, &p->h_pairs, &p->h_gather, &p->h_tabupd, &p->h_assoc}) b->release();
     delete p;
 }
 
@@ -362,6 +373,16 @@ int tracker_group_set_metric(dd_tracker *any, int metric) {
     TrackerPool *p = any->pool;
     DD_REQUIRE(p->arenas.empty() || p->metric == metric, DD_E_STATE, "tracker metric: the group already holds gallery rows");
     p->metric = metric;
+    return DD_OK;
+}
+
+// Where the group's updates decide their association: ASSOC_HOST (cost matrices to the host, cascade + LSAP on the host pool) or
+// ASSOC_DEVICE (assoc_match_k behind tracker_assoc_k, the three lists to the host).  Same decisions either way.
+int tracker_group_set_association(dd_tracker *any, int where) {
+    DD_REQUIRE(any && (where == ASSOC_HOST || where == ASSOC_DEVICE), DD_E_ARG,
+               "tracker association must be 0 (host) or 1 (device), got %d", where);
+    DD_REQUIRE(!any->pool->upd_inflight, DD_E_STATE, "tracker association: an update of the group is in flight");
+    any->pool->assoc = where;
     return DD_OK;
 }
 
@@ -423,10 +444,22 @@ int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const
         maxn = std::max(maxn, t->ph_n);
     }
     p->D = D; p->R = R; p->have_cost = false;
-    if (D == 0) return DD_OK;
-    // ---- stage inputs: [det tlwh f64 D*4][8 int arrays of R rows]
+    // the device decides only when every stream of the group fits its solver: decided here, before anything is launched
+    bool use_dev = p->assoc == ASSOC_DEVICE;
+    for (int z = 0; z < S && use_dev; ++z) use_dev = ts[z]->ph_T <= DD_ASSOC_DEVICE_MAX && ts[z]->ph_n <= DD_ASSOC_DEVICE_MAX;
+    p->dev_decided = use_dev; p->cost_on_host = false;
+    p->assoc_base.assign(S, -1);
+    // an update counts, and is in flight, once this phase has succeeded: on both ways out below
+    long long &n_updates = use_dev ? p->n_dev_updates : p->n_host_updates;
+    if (D == 0) {
+        n_updates += 1;
+        p->upd_inflight = true;
+        return DD_OK;
+    }
+    // ---- stage inputs: [det tlwh f64 D*4][8 int arrays of R rows][5 ints per stream the device decides]
     const size_t off_rows = (size_t)D * 4 * sizeof(double);
-    const size_t in_bytes = off_rows + (size_t)8 * R * sizeof(int);
+    const size_t off_desc = off_rows + (size_t)8 * R * sizeof(int);
+    const size_t in_bytes = off_desc + (use_dev ? (size_t)5 * S * sizeof(int) : 0);
     if ((rc = p->h_in.reserve(in_bytes + 64)) != DD_OK) return rc;
     if ((rc = p->d_in.reserve(in_bytes + 64)) != DD_OK) return rc;
     char *h = p->h_in.as<char>();
@@ -448,6 +481,22 @@ int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const
             h_gcnt[r] = gallery_count(p, t->tracks[i].slot, t->budget);
         }
     }
+    int n_dec = 0;
+    size_t out_ints = 0;
+    if (use_dev) {                                              // (row base, T, n, cost base, output base) per stream with T > 0 && n > 0
+        int *hd = reinterpret_cast<int *>(h + off_desc);
+        int row_base = 0;
+        for (int z = 0; z < S; ++z) {
+            const dd_tracker *t = ts[z];
+            if (t->ph_T > 0 && t->ph_n > 0) {
+                int *e = hd + 5 * n_dec++;
+                e[0] = row_base; e[1] = t->ph_T; e[2] = t->ph_n; e[3] = p->cost_base[z]; e[4] = (int)out_ints;
+                p->assoc_base[z] = (int)out_ints;
+                out_ints += ddk::assoc_out_ints(t->ph_T, t->ph_n);
+            }
+            row_base += t->ph_T;
+        }
+    }
     char *d = p->d_in.as<char>();
     DD_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, s));
     const bool euclid = p->metric == METRIC_EUCLIDEAN;
@@ -466,7 +515,7 @@ int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const
     }
     if (R > 0 && cost_total > 0) {
         if ((rc = p->d_cost.reserve(cost_total * sizeof(double))) != DD_OK) return rc;
-        if ((rc = p->h_cost.reserve(cost_total * sizeof(double))) != DD_OK) return rc;
+        if (!use_dev && (rc = p->h_cost.reserve(cost_total * sizeof(double))) != DD_OK) return rc;
         const int *dr = reinterpret_cast<const int *>(d + off_rows);
         hipLaunchKernelGGL(euclid ? tracker_assoc_k<METRIC_EUCLIDEAN> : tracker_assoc_k<METRIC_COSINE>, dim3(R, dd_ceil_div(maxn, 64)),
                            dim3(256), 0, s, p->d_means, p->d_covs,
@@ -474,9 +523,22 @@ int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const
                            dr + 6 * R, dr + 7 * R, reinterpret_cast<const double *>(d), p->d_feats_n.as<float>(),
                            p->d_cost.as<double>());
         DD_LAUNCH_CHECK();
-        DD_HIP(hipMemcpyAsync(p->h_cost.p, p->d_cost.p, cost_total * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (use_dev) {                                          // the decision itself; its lists and status words come back, the matrices stay
+            if ((rc = p->d_assoc.reserve(out_ints * sizeof(int))) != DD_OK) return rc;
+            if ((rc = p->h_assoc.reserve(out_ints * sizeof(int))) != DD_OK) return rc;
+            if ((rc = ddk::assoc_match(s, p->d_cost.as<double>(), dr + R, dr + 2 * R, reinterpret_cast<const int *>(d + off_desc), n_dec,
+                                       ts[0]->max_cos, ts[0]->max_iou, ts[0]->max_age, p->d_assoc.as<int>())) != DD_OK) return rc;
+            DD_HIP(hipMemcpyAsync(p->h_assoc.p, p->d_assoc.p, out_ints * sizeof(int), hipMemcpyDeviceToHost, s));
+            p->assoc_d2h_bytes += (long long)(out_ints * sizeof(int));
+        } else {
+            DD_HIP(hipMemcpyAsync(p->h_cost.p, p->d_cost.p, cost_total * sizeof(double), hipMemcpyDeviceToHost, s));
+            p->cost_on_host = true;
+            p->assoc_d2h_bytes += (long long)(cost_total * sizeof(double));
+        }
         p->have_cost = true;
     }
+    n_updates += 1;
+    p->upd_inflight = true;
     return DD_OK;
 }
 
@@ -485,57 +547,37 @@ int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const
 // ONE gather of the means.  The per-stream part touches only that stream's tracker, so the streams are spread over
 // the host pool (hostpool.h); gallery chunks are then handed out serially in stream order, as a single thread would.
 namespace {
-// tracker.py:59-93 for one stream: decisions + integer book-keeping.  Fills t->m_upd / t->m_new with (slot, detection) pairs.
+// tracker.py:59-93 for one stream: the decision (from the device's lists, or made here) + integer book-keeping.  Fills t->m_upd /
+// t->m_new with (slot, detection) pairs.
 int match_one_stream(TrackerPool *p, dd_tracker *t, int z) {
     const int n = t->ph_n, T = t->ph_T, doff = p->det_off[z];
-    std::vector<std::pair<int, int>> matches;
-    std::vector<int> un_rows_final, un_dets, lvl_rows, tmp_rows, tmp_dets, confirmed, unconfirmed;
+    std::vector<int> matches, un_rows_final, un_dets;         // matches: (row, det) pairs flattened
     t->m_upd.clear(); t->m_new.clear();
     t->ph_cost_base = (n > 0 && T > 0 && p->have_cost) ? p->cost_base[z] : -1;   // parity aid (dd_tracker_last_cost)
-    if (n > 0 && T > 0) {
-        const double *app = p->h_cost.as<double>() + p->cost_base[z], *iou = app + (size_t)T * n;
-        // ---- tracker.py:95-133 _match
-        for (int i = 0; i < T; ++i) (t->tracks[i].state == CONFIRMED ? confirmed : unconfirmed).push_back(i);
-        un_dets.resize(n);
-        std::iota(un_dets.begin(), un_dets.end(), 0);
-        for (int level = 0; level < t->max_age; ++level) {            // linear_assignment.py:78-141
-            if (un_dets.empty()) break;
-            lvl_rows.clear();
-            for (int k : confirmed) if (t->tracks[k].tsu == 1 + level) lvl_rows.push_back(k);
-            if (lvl_rows.empty()) continue;
-            min_cost_matching(app, n, t->max_cos, lvl_rows, un_dets, matches, tmp_rows, tmp_dets);
-            un_dets = tmp_dets;
-        }
-        // unmatched_tracks_a = list(set(track_indices) - set(k for k, _ in matches)) (linear_assignment.py:140):
-        // the reference's order is CPython's set iteration order, reproduced by csrc/pyset.cpp, because it
-        // becomes the row order of the IoU assignment below (tracker.py:120-123).
-        std::vector<int> matched_rows, un_a_all;
-        for (auto &m : matches) matched_rows.push_back(m.first);
-        ddk::pyset_difference_order(confirmed, matched_rows, un_a_all);
-        std::vector<int> iou_rows = unconfirmed, un_rows_a;
-        for (int k : un_a_all) {
-            if (t->tracks[k].tsu == 1) iou_rows.push_back(k); else un_rows_a.push_back(k);
-        }
-        std::vector<int> un_rows_b;
-        min_cost_matching(iou, n, t->max_iou, iou_rows, un_dets, matches, un_rows_b, tmp_dets);
-        un_dets = tmp_dets;
-        un_rows_final = un_rows_a;
-        un_rows_final.insert(un_rows_final.end(), un_rows_b.begin(), un_rows_b.end());
-    } else {
-        un_dets.resize(n);
-        std::iota(un_dets.begin(), un_dets.end(), 0);
-        for (int i = 0; i < T; ++i) un_rows_final.push_back(i);
+    const int *dev = (p->dev_decided && n > 0 && T > 0 && p->assoc_base[z] >= 0) ? p->h_assoc.as<int>() + p->assoc_base[z] : nullptr;
+    if (dev && dev[0] == 0) {                                  // decided by assoc_match_k
+        const int *pm = dev + 4, *pr = pm + 2 * std::min(T, n), *pd = pr + T;
+        matches.assign(pm, pm + 2 * dev[1]);
+        un_rows_final.assign(pr, pr + dev[2]);
+        un_dets.assign(pd, pd + dev[3]);
+    } else {                                                   // host association, or a stream the device handed back (its matrices were fetched)
+        std::vector<int> state(T), tsu(T);
+        for (int i = 0; i < T; ++i) { state[i] = t->tracks[i].state; tsu[i] = t->tracks[i].tsu; }
+        const double *app = (n > 0 && T > 0) ? p->h_cost.as<double>() + p->cost_base[z] : nullptr;
+        ddk::match_decide_host(app, app ? app + (size_t)T * n : nullptr, T, n, state.data(), tsu.data(), t->max_cos, t->max_iou, t->max_age,
+                               matches, un_rows_final, un_dets);
     }
     // ---- tracker.py:70-79 apply to the integer book-keeping
-    for (auto &m : matches) {                                  // track.py:127-152
-        TrackRec &tr = t->tracks[m.first];
+    for (size_t k = 0; k + 1 < matches.size(); k += 2) {       // track.py:127-152
+        const int row = matches[k], det = matches[k + 1];
+        TrackRec &tr = t->tracks[row];
         tr.hits += 1;
         tr.tsu = 0;
-        tr.last_det = m.second;
+        tr.last_det = det;
         if (tr.state == TENTATIVE && tr.hits >= t->n_init) tr.state = CONFIRMED;
-        t->m_upd.push_back(tr.slot); t->m_upd.push_back(doff + m.second);
-        t->last_pairs.push_back(m.first);
-        t->last_pairs.push_back(m.second);
+        t->m_upd.push_back(tr.slot); t->m_upd.push_back(doff + det);
+        t->last_pairs.push_back(row);
+        t->last_pairs.push_back(det);
     }
     for (int r : un_rows_final) {                              // track.py:190-196
         TrackRec &tr = t->tracks[r];
@@ -564,12 +606,82 @@ int match_one_stream(TrackerPool *p, dd_tracker *t, int z) {
 }
 }  // namespace
 
+// tracker.py:95-133 _match for one stream on host matrices: the matching cascade over the confirmed tracks, then the IoU stage.
+void match_decide_host(const double *app, const double *iou, int T, int n, const int *state, const int *tsu, double max_cos,
+                       double max_iou, int max_age, std::vector<int> &matches_flat, std::vector<int> &un_rows_final, std::vector<int> &un_dets) {
+    std::vector<std::pair<int, int>> matches;
+    std::vector<int> lvl_rows, tmp_rows, tmp_dets, confirmed, unconfirmed;
+    matches_flat.clear(); un_rows_final.clear(); un_dets.clear();
+    if (n > 0 && T > 0) {
+        for (int i = 0; i < T; ++i) (state[i] == CONFIRMED ? confirmed : unconfirmed).push_back(i);
+        un_dets.resize(n);
+        std::iota(un_dets.begin(), un_dets.end(), 0);
+        for (int level = 0; level < max_age; ++level) {            // linear_assignment.py:78-141
+            if (un_dets.empty()) break;
+            lvl_rows.clear();
+            for (int k : confirmed) if (tsu[k] == 1 + level) lvl_rows.push_back(k);
+            if (lvl_rows.empty()) continue;
+            min_cost_matching(app, n, max_cos, lvl_rows, un_dets, matches, tmp_rows, tmp_dets);
+            un_dets = tmp_dets;
+        }
+        // unmatched_tracks_a = list(set(track_indices) - set(k for k, _ in matches)) (linear_assignment.py:140):
+        // the reference's order is CPython's set iteration order, reproduced by csrc/pyset.cpp, because it
+        // becomes the row order of the IoU assignment below (tracker.py:120-123).
+        std::vector<int> matched_rows, un_a_all;
+        for (auto &m : matches) matched_rows.push_back(m.first);
+        ddk::pyset_difference_order(confirmed, matched_rows, un_a_all);
+        std::vector<int> iou_rows = unconfirmed, un_rows_a;
+        for (int k : un_a_all) {
+            if (tsu[k] == 1) iou_rows.push_back(k); else un_rows_a.push_back(k);
+        }
+        std::vector<int> un_rows_b;
+        min_cost_matching(iou, n, max_iou, iou_rows, un_dets, matches, un_rows_b, tmp_dets);
+        un_dets = tmp_dets;
+        un_rows_final = un_rows_a;
+        un_rows_final.insert(un_rows_final.end(), un_rows_b.begin(), un_rows_b.end());
+    } else {
+        un_dets.resize(n);
+        std::iota(un_dets.begin(), un_dets.end(), 0);
+        for (int i = 0; i < T; ++i) un_rows_final.push_back(i);
+    }
+    for (auto &m : matches) { matches_flat.push_back(m.first); matches_flat.push_back(m.second); }
+}
+
+namespace {
+int update_match(dd_tracker **ts, int S);
+}
+
+// (an update that fails here is over: trackers_update_end will not be called for it)
 int trackers_update_match(dd_tracker **ts, int S) {
+    const int rc = update_match(ts, S);
+    if (rc != DD_OK) ts[0]->pool->upd_inflight = false;
+    return rc;
+}
+
+namespace {
+int update_match(dd_tracker **ts, int S) {
     TrackerPool *p = ts[0]->pool;
     hipStream_t s = p->ctx->stream;
     p->pred_inflight = false;                                   // the caller synchronised before this phase
     int rc;
     const int D = p->D;
+    if (p->dev_decided && p->have_cost) {
+        // a stream whose status word is set (NaN / -inf cost, a bound hit) is decided by the host code: its two matrices come over now
+        // (here, not on the pool's threads, which make no device call)
+        size_t total = 0;
+        for (int z = 0; z < S; ++z) total += (size_t)2 * ts[z]->ph_T * ts[z]->ph_n;
+        int n_back = 0;
+        for (int z = 0; z < S; ++z) {
+            if (p->assoc_base[z] < 0 || p->h_assoc.as<int>()[p->assoc_base[z]] == 0) continue;
+            if (n_back++ == 0 && (rc = p->h_cost.reserve(total * sizeof(double))) != DD_OK) return rc;
+            const size_t bytes = (size_t)2 * ts[z]->ph_T * ts[z]->ph_n * sizeof(double);
+            DD_HIP(hipMemcpyAsync(p->h_cost.as<double>() + p->cost_base[z], p->d_cost.as<double>() + p->cost_base[z], bytes,
+                                  hipMemcpyDeviceToHost, s));
+            p->assoc_d2h_bytes += (long long)bytes;
+        }
+        if (n_back) DD_HIP(hipStreamSynchronize(s));
+        p->n_fallback_streams += n_back;
+    }
     size_t max_pairs = (size_t)p->R + D;
     if ((rc = p->h_pairs.reserve(max_pairs * 3 * sizeof(int) + 64)) != DD_OK) return rc;
     if ((rc = p->d_pairs.reserve(max_pairs * 3 * sizeof(int) + 64)) != DD_OK) return rc;
@@ -637,10 +749,12 @@ int trackers_update_match(dd_tracker **ts, int S) {
     }
     return DD_OK;
 }
+}  // namespace
 
 // phase 3 (the means have landed): mirror them for dd_tracker_read.
 int trackers_update_end(dd_tracker **ts, int S) {
     TrackerPool *p = ts[0]->pool;
+    p->upd_inflight = false;
     const double *hg = p->h_gather.as<double>();
     size_t k = 0;
     for (int z = 0; z < S; ++z) {
@@ -885,9 +999,35 @@ int dd_tracker_last_cost(dd_tracker *t, double *app_host, double *iou_host, int 
     if (!have || (!app_host && !iou_host)) return DD_OK;
     const size_t tn = (size_t)t->ph_T * t->ph_n;
     DD_REQUIRE((size_t)cap >= tn, DD_E_ARG, "dd_tracker_last_cost: cap %d < %zu", cap, tn);
-    const double *c0 = t->pool->h_cost.as<double>() + t->ph_cost_base;
+    TrackerPool *p = t->pool;
+    if (!p->cost_on_host) {                                       // device association: the matrices stayed in HBM, fetch them now
+        DD_DEVICE(p->ctx);
+        DD_HIP(hipStreamSynchronize(p->ctx->stream));
+        const double *d0 = p->d_cost.as<double>() + t->ph_cost_base;
+        if (app_host) DD_HIP(hipMemcpy(app_host, d0, tn * sizeof(double), hipMemcpyDeviceToHost));
+        if (iou_host) DD_HIP(hipMemcpy(iou_host, d0 + tn, tn * sizeof(double), hipMemcpyDeviceToHost));
+        return DD_OK;
+    }
+    const double *c0 = p->h_cost.as<double>() + t->ph_cost_base;
     if (app_host) memcpy(app_host, c0, tn * sizeof(double));
     if (iou_host) memcpy(iou_host, c0 + tn, tn * sizeof(double));
+    return DD_OK;
+}
+
+// Where the updates of the tracker's group decide their association: 0 host (the default), 1 device.  Refused while an update is in flight.
+int dd_tracker_set_association(dd_tracker *t, int where) {
+    DD_REQUIRE(t, DD_E_ARG, "dd_tracker_set_association: NULL tracker");
+    return ddk::tracker_group_set_association(t, where);
+}
+
+int dd_tracker_association_stats(dd_tracker *t, long long *device_updates_host, long long *host_updates_host, long long *fallback_streams_host,
+                                 long long *d2h_bytes_host) {
+    DD_REQUIRE(t, DD_E_ARG, "dd_tracker_association_stats: NULL tracker");
+    const TrackerPool *p = t->pool;
+    if (device_updates_host) *device_updates_host = p->n_dev_updates;
+    if (host_updates_host) *host_updates_host = p->n_host_updates;
+    if (fallback_streams_host) *fallback_streams_host = p->n_fallback_streams;
+    if (d2h_bytes_host) *d2h_bytes_host = p->assoc_d2h_bytes;
     return DD_OK;
 }
 

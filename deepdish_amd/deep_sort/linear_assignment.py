@@ -3,16 +3,40 @@
 import numpy as np
 
 from .._lib import lib, check
-from ..runtime import ptr
+from ..runtime import ptr, default_context
 from . import kalman_filter
 
 INFTY_COST = 1e+5
 
 
-def linear_sum_assignment(cost_matrix):
+def linear_sum_assignment_batch(costs, device=True, context=None):
+    """[(row_ind, col_ind)] for a list of cost matrices.  device=True: every problem in ONE launch, one wave per problem
+    (dd_lsap_batch; shapes up to 256 x 256, no empty ones); device=False: the host solver, problem by problem.  Same pairs either way."""
+    if not device:
+        return [linear_sum_assignment(c) for c in costs]
+    cs = [np.ascontiguousarray(c, dtype=np.float64) for c in costs]
+    if not cs:
+        return []
+    nr = np.array([c.shape[0] for c in cs], dtype=np.int32)
+    nc = np.array([c.shape[1] for c in cs], dtype=np.int32)
+    sizes = nr.astype(np.int64) * nc
+    off = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.int64)
+    k = np.minimum(nr, nc).astype(np.int64)
+    ctx = context or default_context()
+    flat = np.concatenate([c.ravel() for c in cs]) if sizes.sum() else np.zeros(1)
+    dev = ctx.to_device(flat)
+    rows, cols = np.zeros(max(1, int(k.sum())), dtype=np.int32), np.zeros(max(1, int(k.sum())), dtype=np.int32)
+    check(lib().dd_lsap_batch(ctx.handle, ptr(dev), ptr(nr), ptr(nc), ptr(off), len(cs), ptr(rows), ptr(cols)), 'dd_lsap_batch')
+    ends = np.cumsum(k)
+    return [(rows[e - n:e].astype(np.int64), cols[e - n:e].astype(np.int64)) for e, n in zip(ends.tolist(), k.tolist())]
+
+
+def linear_sum_assignment(cost_matrix, device=False):
     c = np.ascontiguousarray(cost_matrix, dtype=np.float64)
     nr, nc = c.shape
     k = min(nr, nc)
+    if device and k > 0:
+        return linear_sum_assignment_batch([c], device=True)[0]
     rows, cols = np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.int32)
     check(lib().dd_lsap_host(ptr(c), nr, nc, ptr(rows), ptr(cols)), 'dd_lsap_host')
     return rows.astype(np.int64), cols.astype(np.int64)

@@ -10,9 +10,26 @@ from . import kalman_filter
 from .track import Track
 
 
+def association_kind(name):
+    """'host' / 'device' -> the C ABI's number for where Tracker._match is decided; anything else is a ValueError."""
+    if name not in ('host', 'device'):
+        raise ValueError("Invalid association; must be either 'host' or 'device'")
+    return 1 if name == 'device' else 0
+
+
+def _association_stats(handle, d2h_bytes=False):
+    v = [ctypes.c_longlong() for _ in range(4)]
+    check(lib().dd_tracker_association_stats(handle, *[ctypes.byref(x) for x in v]), 'dd_tracker_association_stats')
+    if d2h_bytes:               # what the decisions copied device-to-host so far (scripts/time_association.py)
+        return v[3].value
+    return dict(zip(('device_updates', 'host_updates', 'fallback_streams'), (x.value for x in v[:3])))
+
+
 class Tracker:
     def __init__(self, metric, max_iou_distance=0.7, max_age=30, n_init=3, context=None,
-                 track_capacity=1024, gallery_capacity=256):
+                 track_capacity=1024, gallery_capacity=256, association='host'):
+        where = association_kind(association)       # before anything is built
+        self.association = association
         self.metric = metric
         self.max_iou_distance = max_iou_distance
         self.max_age = max_age
@@ -29,6 +46,22 @@ class Tracker:
                                              int(max_age), int(n_init), int(budget), int(track_capacity),
                                              int(gallery_capacity), ctypes.byref(h)), 'dd_tracker_create_metric')
         self._h = h
+        if where:                                   # the cascade and the assignments on the device (csrc/assoc.hip): the same decisions
+            check(lib().dd_tracker_set_association(self._h, where), 'dd_tracker_set_association')
+
+    def association_stats(self):
+        """{'device_updates', 'host_updates', 'fallback_streams'}: updates decided on the device / on the host so far, and streams of
+        device-decided updates whose decision the host code had to make (a NaN cost)."""
+        return _association_stats(self._h)
+
+    def last_matches(self):
+        """[(track row before the update, detection)] of the last update(), in the order they were applied."""
+        m = ctypes.c_int()
+        check(lib().dd_tracker_last_matches(self._h, None, 0, ctypes.byref(m)), 'dd_tracker_last_matches')
+        pairs = np.zeros((m.value, 2), dtype=np.int32)
+        if m.value:
+            check(lib().dd_tracker_last_matches(self._h, ptr(pairs), m.value, ctypes.byref(m)), 'dd_tracker_last_matches')
+        return [tuple(r) for r in pairs.tolist()]
 
     def __del__(self):
         try:

@@ -11,6 +11,7 @@ from . import nets, netsq
 from .engine import Net
 from .pipeline import DEFAULT_LABELS, DEFAULT_YOLO_LABELS
 from .deep_sort.nn_matching import metric_kind as _metric_kind
+from .deep_sort.tracker import association_kind as _association_kind, _association_stats
 from .tools.weights_io import load_named_weights, load_ssd_model, load_mars_weights, load_yolov5_weights, ssd_post_options
 
 
@@ -41,9 +42,12 @@ class MultiStreamPipeline:
                  labels=None, wanted_labels=('person',), input_size=(640, 480), line=None, max_cosine_distance=0.2,
                  nms_max_overlap=0.6, max_iou_distance=0.7, max_age=60, n_init=3, context=None, run_detector=True,
                  encoder_max_batch=None, track_capacity=512, gallery_capacity=256, background_subtraction_ratio=None,
-                 background_masking=False, graph=None, object_detector_skip_frames=None, metric='cosine'):
+                 background_masking=False, graph=None, object_detector_skip_frames=None, metric='cosine',
+                 association='host'):
         self.metric = metric
         metric_kind = _metric_kind(metric)   # 'cosine' or 'euclidean' (nn_matching.py:126-132), else ValueError -- before anything is built
+        self.association = association
+        association_where = _association_kind(association)       # 'host' or 'device', else ValueError -- likewise
         self.ctx = context or default_context()
         self.S = int(n_streams)
         self.W, self.H = input_size
@@ -120,6 +124,8 @@ class MultiStreamPipeline:
         self._h = h
         if metric_kind:         # NearestNeighborDistanceMetric("euclidean", max_cosine_distance, None) for every stream's tracker
             check(lib().dd_pipeline_metric(self._h, metric_kind), 'dd_pipeline_metric')
+        if association_where:   # every stream's matching cascade and assignments on the device, one wave per stream (csrc/assoc.hip)
+            check(lib().dd_pipeline_association(self._h, association_where), 'dd_pipeline_association')
         if self.det is not None and self.kind != 'yolov5':
             check(lib().dd_pipeline_ssd_options(self._h, int(ssd_post['max_detections']), float(ssd_post['nms_score_threshold']),
                                                 float(ssd_post['nms_iou_threshold'])), 'dd_pipeline_ssd_options')
@@ -199,6 +205,11 @@ class MultiStreamPipeline:
         h = P()
         check(lib().dd_pipeline_tracker(self._h, stream, ctypes.byref(h)), 'dd_pipeline_tracker')
         return _TrackerView(h)
+
+    def association_stats(self):
+        """Tracker.association_stats() for the pipeline's tracker group: group updates decided on the device / on the host, and streams
+        that fell back to the host code."""
+        return _association_stats(self.tracker(0)._h)
 
     def stage_ms(self):
         """Per step: the stages' GPU milliseconds under the reference's timer names (deepdish.py:975-981 objd, :1018-1021 feat, :1031-1032

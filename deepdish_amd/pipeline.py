@@ -14,7 +14,7 @@ import torch
 from .background import createBackgroundSubtractorMOG2, motion_filter
 from .deep_sort import nn_matching, preprocessing
 from .deep_sort.detection import Detection
-from .deep_sort.tracker import Tracker
+from .deep_sort.tracker import Tracker, association_kind
 from .tools import generate_detections as gdet
 from .tools.countline import CountLine
 from .runtime import default_context
@@ -74,8 +74,9 @@ class HotPath:
                  context=None, run_detector=True, disable_background_subtraction=True, background_subtraction_ratio=0.25,
                  enable_background_masking=False, log=None, restore_from_log=False, mqtt_publish=None, mqtt_topic='default/topic',
                  mqtt_acp_id=None, mqtt_verbosity=1, cpu_temp=None, annotations=None, object_detector_skip_frames=None,
-                 metric='cosine'):
+                 metric='cosine', association='host'):
         nn_matching.metric_kind(metric)              # 'cosine' or 'euclidean' (nn_matching.py:126-132), else ValueError -- before anything is built
+        association_kind(association)                # 'host' or 'device', else ValueError -- likewise
         self.ctx = context or default_context()
         self.input_size = tuple(input_size)
         # deepdish.py:512,889: the reference defaults to background subtraction ON; its benchmarks (and this class)
@@ -91,7 +92,7 @@ class HotPath:
                                                context=self.ctx)
         # deepdish.py:515-516 asks for "cosine"; with 'euclidean' the same threshold bounds the squared distance of the encoder's rows
         metric = nn_matching.NearestNeighborDistanceMetric(metric, max_cosine_distance, None)
-        self.tracker = Tracker(metric, max_iou_distance=max_iou_distance, max_age=max_age, context=self.ctx)
+        self.tracker = Tracker(metric, max_iou_distance=max_iou_distance, max_age=max_age, context=self.ctx, association=association)
         w, h = self.input_size
         if line is None:                                                                          # :739-741
             line = np.array([[w / 2, 0], [w / 2, h]], dtype=int)

@@ -111,6 +111,27 @@ int dd_lsap_host(const double *cost_host, int nr, int nc, int *row_ind_host, int
 int dd_pyset_difference_order_host(const int *a_host, int na, const int *b_host, int nb, int *out_host,
                                    int *out_n_host);
 
+/* The same solver on the device, one wave64 per problem, all problems in ONE launch: scipy.optimize.linear_sum_assignment as called at
+ * deep_sort/linear_assignment.py:58, with dd_lsap_host's choices under ties (pair for pair the same result).  cost_dev: device memory;
+ * problem p is the row-major nr_host[p] x nc_host[p] matrix at element offset offset_host[p].  rows_host / cols_host receive the
+ * min(nr, nc) pairs of every problem, sorted by row, problem after problem.  A shape above DD_ASSOC_DEVICE_MAX in either dimension, an
+ * empty shape, an infeasible matrix or a NaN / -inf cost is DD_E_ARG, the message naming the first such problem. */
+#define DD_ASSOC_DEVICE_MAX 256
+int dd_lsap_batch(dd_ctx *ctx, const double *cost_dev, const int *nr_host, const int *nc_host, const int64_t *offset_host,
+                  int n_problems, int *rows_host, int *cols_host);
+
+/* The association decision of one tracker update, for parity tests: deep_sort/tracker.py:95-133 _match, i.e. matching_cascade over the
+ * confirmed tracks (deep_sort/linear_assignment.py:78-141; each level min_cost_matching, :11-75, costs above the threshold clamped to
+ * threshold + 1e-5 at :57), then min_cost_matching on the IoU costs for the unconfirmed tracks and the confirmed ones missed once
+ * (tracker.py:117-123).  app / iou: [T][n] f64 row-major, the appearance cost after gating and the IoU cost; state_host / tsu_host: per
+ * track row, state (1 Tentative, 2 Confirmed) and time_since_update.  where = 0: the host code on HOST matrices (no GPU, ctx may be NULL);
+ * where = 1: the device code (csrc/assoc.hip) on DEVICE matrices, T and n at most DD_ASSOC_DEVICE_MAX.  Out, in the order the reference
+ * builds them: matches_host [min(T, n)][2] (track row, detection), un_rows_host [T] (unmatched tracks), un_dets_host [n] (unmatched
+ * detections) and their counts. */
+int dd_match_cascade(dd_ctx *ctx, int where, const double *app, const double *iou, int T, int n, const int *state_host,
+                     const int *tsu_host, double max_cos, double max_iou, int max_age, int *matches_host, int *n_matches_host,
+                     int *un_rows_host, int *n_un_rows_host, int *un_dets_host, int *n_un_dets_host);
+
 /* ---------------------------------------------------------------- tracker (state in HBM)
  * deep_sort/tracker.py:40-138 Tracker + track.py:67-196 Track state machine +
  * linear_assignment.py:11-190 (threshold, LSAP, cascade, gating) + nn_matching.py:137-154
@@ -163,6 +184,17 @@ int dd_tracker_next_id(dd_tracker *trk, int64_t *out_host);
 int dd_tracker_last_cost(dd_tracker *trk, double *app_host, double *iou_host, int cap, int *rows_host, int *cols_host);
 /* matches[m][2] = (track row, detection), in update order */
 int dd_tracker_last_matches(dd_tracker *trk, int *pairs_host, int cap, int *out_m_host);
+/* Where Tracker._match (deep_sort/tracker.py:95-133: matching cascade, linear_assignment.py:78-141, and the assignments it solves, :11-75)
+ * is decided for the tracker's GROUP (the trackers of a pipeline share it): 0 = on the host from the cost matrices (the default), 1 = on
+ * the device, one wave per stream behind the association kernel, only the three lists coming back.  The decisions are the same.  A group
+ * update in which any stream has more than DD_ASSOC_DEVICE_MAX tracks or detections runs whole on the host path; a stream whose device
+ * decision stops (NaN / -inf cost) is decided by the host code.  DD_E_STATE while an update of the group is in flight. */
+int dd_tracker_set_association(dd_tracker *trk, int where);
+/* Group-wide counts since creation (any pointer may be NULL): group updates decided on the device, group updates decided on the host,
+ * streams of device-decided updates that fell back to the host code, and the bytes the decisions copied device-to-host (the cost matrices
+ * under host association; the lists, plus the matrices of streams that fell back, under device association). */
+int dd_tracker_association_stats(dd_tracker *trk, long long *device_updates_host, long long *host_updates_host,
+                                 long long *fallback_streams_host, long long *d2h_bytes_host);
 
 /* ---------------------------------------------------------------- crops
  * tools/generate_detections.py:40-84 extract_image_patch for every box (integer box math on the
@@ -464,6 +496,9 @@ int dd_pipeline_detector_skip_frames(dd_pipeline *p, int n);
  * DD_E_ARG).  The threshold stays the max_cosine_distance given to dd_pipeline_create, as the reference hands --max-cosine-distance to
  * NearestNeighborDistanceMetric as matching_threshold whatever the metric (deepdish.py:515-516).  Before the first step (DD_E_STATE after). */
 int dd_pipeline_metric(dd_pipeline *p, int metric);
+/* dd_tracker_set_association for the pipeline's tracker group (deep_sort/tracker.py:95-133, deep_sort/linear_assignment.py:11-141 decided on
+ * the host, 0, the default, or on the device, 1; other values: DD_E_ARG).  Between steps. */
+int dd_pipeline_association(dd_pipeline *p, int where);
 /* frames: device u8 [n_streams][H][W][3] BGR.  inj_*: optional detections that REPLACE the detector's
  * output (it still runs): tlwh f64 rows, scores, class ids; stream s owns rows
  * [inj_offsets[s], inj_offsets[s+1]).  Blocks until the step is complete. */
