@@ -63,6 +63,9 @@ SIGNATURES = {
     'dd_resize_lanczos_batch': [P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P],
     'dd_resize_lanczos_plan': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                POINTER(c_int)],
+    'dd_letterbox_geometry': [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int)],
+    'dd_resize_lanczos_letterbox': [P, P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P],
+    'dd_resize_lanczos_letterbox_plan': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)],
     'dd_resize_bilinear': [P, P, c_int, c_int, c_int, P, c_int, c_int, P],
     'dd_yuv420_to_bgr': [P, P, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, P, P],
     'dd_ingest_create': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
@@ -108,6 +111,7 @@ SIGNATURES = {
     'dd_net_yolo_decoded_read': [P, c_int, P, P, P],
     'dd_ssd_detections': [P, P, P, P, c_int, c_int, c_double, c_double, c_double, c_double, P, P, P, P, P],
     'dd_yolov5_decode': [P, P, c_int, c_int, c_float, c_float, c_float, P, P, P, c_int, P, P],
+    'dd_yolov5_decode_letterbox': [P, P, c_int, c_int, c_float, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P],
     'dd_pipeline_create': [P, c_int, c_int, c_int, P, P, c_int, c_int, P, c_char_p, c_char_p, c_double, c_double,
                            c_double, c_int, c_int, P, c_int, c_int, POINTER(P)],
     'dd_pipeline_destroy': [P],
@@ -115,6 +119,7 @@ SIGNATURES = {
     'dd_pipeline_ssd_options': [P, c_int, c_float, c_float],
     'dd_pipeline_ssd_regular_nms': [P, c_int],
     'dd_pipeline_detector_skip_frames': [P, c_int],
+    'dd_pipeline_detector_letterbox': [P, c_int],
     'dd_pipeline_metric': [P, c_int],
     'dd_pipeline_association': [P, c_int],
     'dd_pipeline_step': [P, P, P, P, P, P],

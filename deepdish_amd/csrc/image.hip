@@ -14,6 +14,7 @@
 #include <cstdint>
 #include "common.h"
 #include "resize_dev.h"
+#include "lanczos_tab.h"
 
 namespace {
 
@@ -640,11 +641,11 @@ __global__ __launch_bounds__(256) void fake_encode_k(const uint8_t *__restrict__
 }
 
 // Host: Pillow precompute_coeffs + normalize_coeffs_8bpc (double math on the host so that sin()
-// is the same libm the reference's Pillow uses; the device only sees integers).
-struct LanczosTable {
-    int ksize = 0;
-    std::vector<int> bounds, kk;
-};
+// is the same libm the reference's Pillow uses; the device only sees integers).  LanczosTable, DevTable and the three functions
+// letterbox.hip shares are declared in lanczos_tab.h.
+}  // namespace
+
+namespace ddk {
 
 double sinc_(double x) { if (x == 0.0) return 1.0; x *= M_PI; return sin(x) / x; }
 double lanczos_(double x) { return (-3.0 <= x && x < 3.0) ? sinc_(x) * sinc_(x / 3) : 0.0; }
@@ -685,11 +686,20 @@ LanczosTable make_table(int in_size, int out_size) {
     return t;
 }
 
-struct DevTable { int ksize; int *bounds; int *kk; };
+}  // namespace ddk
+
+namespace {
+
+using ddk::LanczosTable;
+using ddk::DevTable;
+using ddk::lanczos_ksize;
+using ddk::make_table;
 std::mutex g_tab_mu;
 std::map<std::tuple<int, int, int>, DevTable> g_tabs;     // (device, in, out) -> device-resident table
 
-int get_table(int device, int in_size, int out_size, DevTable *out) {
+}  // namespace
+
+int ddk::get_table(int device, int in_size, int out_size, DevTable *out) {
     std::lock_guard<std::mutex> lk(g_tab_mu);
     auto key = std::make_tuple(device, in_size, out_size);
     auto it = g_tabs.find(key);
@@ -706,6 +716,10 @@ int get_table(int device, int in_size, int out_size, DevTable *out) {
     *out = it->second;
     return DD_OK;
 }
+
+namespace {
+
+using ddk::get_table;
 
 // Banded-product tables for band_resample_k.  `taps(col)` yields (source byte index, coefficient)
 // pairs of output column `col`; pitch = bytes per source row (the window of a column group must fit).

@@ -25,6 +25,12 @@ int yolov5_decode(hipStream_t s, const float *raw, int n_rows, int n_cls, float 
                   float *out_scores, int *out_cls, int cap, int *out_n, int batch, void *scratch);
 int yolov5_select(hipStream_t s, const float *boxes4, const float *conf, const int *cls, int n_rows, float thr, float img_w, float img_h,
                   float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch);
+int yolov5_decode_letterbox(hipStream_t s, const float *raw, int n_rows, int n_cls, float thr, int img_w, int img_h, int net_w, int net_h,
+                            float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch, void *scratch);
+int yolov5_select_letterbox(hipStream_t s, const float *boxes4, const float *conf, const int *cls, int n_rows, float thr, int img_w, int img_h,
+                            int net_w, int net_h, float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch);
+int resize_lanczos_letterbox(hipStream_t s, int device, const uint8_t *src, int batch, int H, int W, int src_c, int swap_rb, uint8_t *dst, int h, int w,
+                             int pad, uint8_t *tmp);
 size_t ssd_post_decoded_scratch_bytes(int n_anchors, int batch);
 int ssd_postprocess_decoded(hipStream_t s, const float *d_boxes, const float *d_score, const int *d_cls, const float *d_keys,
                             int n_anchors, int max_det, float score_thr, float iou_thr, float *boxes, float *classes, float *scores,
@@ -120,6 +126,7 @@ struct dd_pipeline {
     struct { const uint8_t *box = nullptr, *cls = nullptr, *lut = nullptr; int stride = 0, n_classes = 0; float quant[4] = {0, 0, 0, 0}; } q8;   // uint8 engine: its head tensors
     bool yolo_dec = false;                     // YOLOv5: the Detect layers reduce their rows in their epilogue (dd_net_yolo_decode)
     size_t yolo_host_rows = 0;                 // YOLOv5: packed rows the first copy of a step brings to the host
+    int letterbox_pad = -1;                    // YOLOv5: >= 0 = the detector sees the frame letterboxed on this pad value (dd_pipeline_detector_letterbox)
     std::vector<size_t> ybase;
     PinBuf h_fin, h_nms, h_crop;
     int crop_cap = 0;
@@ -392,6 +399,18 @@ int dd_pipeline_detector_skip_frames(dd_pipeline *p, int n) {
     return DD_OK;
 }
 
+// YOLOv5 on aspect-preserving, padded input (csrc/letterbox.hip) instead of the reference adaptor's stretch (tools/yolov5.py:99): the
+// step's resize becomes the letterbox launch and both decode forms un-map their boxes from the canvas.  Call before the first step.
+int dd_pipeline_detector_letterbox(dd_pipeline *p, int pad) {
+    DD_REQUIRE(p && p->det && p->det_kind == DET_YOLOV5, DD_E_ARG, "dd_pipeline_detector_letterbox: needs a pipeline with a YOLOv5 detector");
+    DD_REQUIRE(pad >= 0 && pad <= 255, DD_E_ARG, "dd_pipeline_detector_letterbox: pad %d (0 .. 255)", pad);
+    DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, "dd_pipeline_detector_letterbox: call before the first step");
+    int rc;
+    if ((rc = dd_letterbox_geometry(p->W, p->H, p->det_in_w, p->det_in, nullptr, nullptr, nullptr, nullptr)) != DD_OK) return rc;
+    p->letterbox_pad = pad;
+    return DD_OK;
+}
+
 // NearestNeighborDistanceMetric("euclidean", ...) for the pipeline's tracker group (nn_matching.py:5-28,57-75,126-132): metric 0 =
 // cosine (the default, deepdish.py:515-516), 1 = euclidean -- the encoder's rows are then associated and stored as they come, and the
 // max_cosine_distance given to dd_pipeline_create is the matching_threshold on the squared distance, as the reference passes
@@ -532,6 +551,9 @@ int enqueue_detector(dd_pipeline *p, const uint8_t *frames) {
     if (g_stage_events) DD_HIP(hipEventRecord(p->ev_det[0], s));
     if (p->det_kind == DET_TFLITE) {                           // tflite_object_detector.py:207-211: cv2.resize (INTER_LINEAR) of the RGB frame
         if ((rc = ddk::crop_resize(s, frames, p->H, p->W, p->d_tfl_boxes.p, S, p->det_in, p->det_in_w, p->d_resized.as<uint8_t>())) != DD_OK) return rc;
+    } else if (p->letterbox_pad >= 0) {                        // dd_pipeline_detector_letterbox: d_tmp holds S * H * det_in_w * 3 >= S * H * new_w * 3 bytes
+        if ((rc = ddk::resize_lanczos_letterbox(s, p->ctx->device, frames, S, p->H, p->W, 3, 1, p->d_resized.as<uint8_t>(), p->det_in, p->det_in_w,
+                                                p->letterbox_pad, p->d_tmp.as<uint8_t>())) != DD_OK) return rc;
     } else if ((rc = ddk::resize_lanczos(s, p->ctx->device, frames, p->H, p->W, 3, 1, p->d_resized.as<uint8_t>(), p->det_in,
                                          p->det_in_w, p->d_tmp.as<uint8_t>(), S)) != DD_OK) return rc;    // ssd_mobilenet.py:54-57, yolov5.py:99
     if ((rc = dd_net_forward(p->det, p->d_resized.as<uint8_t>(), S, s)) != DD_OK) return rc;       // :102-103 / yolov5.py:107-109
@@ -544,8 +566,15 @@ int enqueue_detector(dd_pipeline *p, const uint8_t *frames) {
         if (p->yolo_dec) {                                       // :126-128 ran in the Detect layers' epilogues
             float *b4 = nullptr, *cf = nullptr; int *cl = nullptr;
             if ((rc = dd_net_yolo_decoded(p->det, &b4, &cf, &cl, nullptr)) != DD_OK) return rc;
+            if (p->letterbox_pad >= 0) {
+                if ((rc = ddk::yolov5_select_letterbox(s, b4, cf, cl, p->n_anchors, (float)p->det_conf, p->W, p->H, p->det_in_w, p->det_in, yb, ys, yc,
+                                                       p->n_anchors, yn, S)) != DD_OK) return rc;
+            } else
             if ((rc = ddk::yolov5_select(s, b4, cf, cl, p->n_anchors, (float)p->det_conf, (float)p->W, (float)p->H, yb, ys, yc,
                                          p->n_anchors, yn, S)) != DD_OK) return rc;
+        } else if (p->letterbox_pad >= 0) {
+            if ((rc = ddk::yolov5_decode_letterbox(s, static_cast<const float *>(raw), p->n_anchors, p->n_classes, (float)p->det_conf, p->W, p->H,
+                                                   p->det_in_w, p->det_in, yb, ys, yc, p->n_anchors, yn, S, p->d_post.p)) != DD_OK) return rc;
         } else
         if ((rc = ddk::yolov5_decode(s, static_cast<const float *>(raw), p->n_anchors, p->n_classes, (float)p->det_conf, (float)p->W,
                                      (float)p->H, yb, ys, yc, p->n_anchors, yn, S, p->d_post.p)) != DD_OK) return rc;

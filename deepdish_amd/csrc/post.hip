@@ -222,12 +222,21 @@ __global__ __launch_bounds__(256) void yolo_conf_k(const float *__restrict__ raw
     }
 }
 
-// second half: ordered compaction of rows with conf >= thr (ascending row order, like np.where)
+// Letterboxed input (csrc/letterbox.hip): the network's corners are normalised to the padded canvas; back to frame pixels they go as
+//     X = (x - off_x / net_w) / (new_w / net_w) * W,   Y = (y - off_y / net_h) / (new_h / net_h) * H
+// in f64, in this order, un-fused, rounded once to f32 on store -- the shape of tools/yolo.py:78-86 (correct_yolo_boxes).  One deviation:
+// the offset is the integer paste offset (net - new) // 2, where the pixels are; the reference's un-mapping uses (net - new) / 2. there.
+// No int() (that is the YOLOv3 plugin's) and no clipping: a box in the padding comes out negative and the box hygiene clips it like any
+// detector's.  With off = 0 and new = net every term is exact and the result is x * W, the stretch form's bits.
+struct YoloLetterbox { double ax, bx, ay, by; };      // off_x / net_w, new_w / net_w, off_y / net_h, new_h / net_h
+
+// second half: ordered compaction of rows with conf >= thr (ascending row order, like np.where).  LB = false: today's stretch arithmetic.
+template <bool LB>
 __global__ __launch_bounds__(1024) void yolo_compact_k(const float *__restrict__ raw, const float *__restrict__ conf,
                                                        const int *__restrict__ cls, int n_rows, int row_floats, float thr,
                                                        float img_w, float img_h, float *__restrict__ out_boxes,
                                                        float *__restrict__ out_scores, int *__restrict__ out_cls,
-                                                       int cap, int *__restrict__ out_n) {
+                                                       int cap, int *__restrict__ out_n, const YoloLetterbox g) {
     __shared__ int wave_cnt[16];
     __shared__ int base;
     {   // blockIdx.x = image of a batch: rows, per-row confidences and outputs of that image
@@ -250,10 +259,17 @@ __global__ __launch_bounds__(1024) void yolo_compact_k(const float *__restrict__
         if (ok && pos < cap) {
             const float *x = raw + (size_t)r * row_floats;
             const float x1 = x[0] - x[2] / 2, y1 = x[1] - x[3] / 2, x2 = x[0] + x[2] / 2, y2 = x[1] + x[3] / 2;
+            if constexpr (LB) {
+                out_boxes[pos * 4 + 0] = (float)((((double)x1 - g.ax) / g.bx) * (double)img_w);
+                out_boxes[pos * 4 + 1] = (float)((((double)y1 - g.ay) / g.by) * (double)img_h);
+                out_boxes[pos * 4 + 2] = (float)((((double)x2 - g.ax) / g.bx) * (double)img_w);
+                out_boxes[pos * 4 + 3] = (float)((((double)y2 - g.ay) / g.by) * (double)img_h);
+            } else {
             out_boxes[pos * 4 + 0] = (float)((double)x1 * (double)img_w);
             out_boxes[pos * 4 + 1] = (float)((double)y1 * (double)img_h);
             out_boxes[pos * 4 + 2] = (float)((double)x2 * (double)img_w);
             out_boxes[pos * 4 + 3] = (float)((double)y2 * (double)img_h);
+            }
             out_scores[pos] = conf[r];
             out_cls[pos] = cls[r];
         }
@@ -383,8 +399,47 @@ int yolov5_decode(hipStream_t s, const float *raw, int n_rows, int n_cls, float 
     DD_REQUIRE(total < (1LL << 31), DD_E_CAPACITY, "yolov5_decode: %lld rows exceed 32-bit indexing", total);
     hipLaunchKernelGGL(yolo_conf_k, dim3((unsigned)std::min<long long>((total + 7) / 8, 256 * 32)), dim3(256), 0, s, raw, (int)total, n_cls, conf, cls);
     DD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(yolo_compact_k, dim3(batch), dim3(1024), 0, s, raw, conf, cls, n_rows, 5 + n_cls, thr, img_w, img_h, out_boxes,
-                       out_scores, out_cls, cap, out_n);
+    hipLaunchKernelGGL(yolo_compact_k<false>, dim3(batch), dim3(1024), 0, s, raw, conf, cls, n_rows, 5 + n_cls, thr, img_w, img_h, out_boxes,
+                       out_scores, out_cls, cap, out_n, YoloLetterbox{0, 1, 0, 1});
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
+static int yolo_letterbox_terms(int img_w, int img_h, int net_w, int net_h, YoloLetterbox *g) {
+    int nw, nh, ox, oy;
+    const int rc = dd_letterbox_geometry(img_w, img_h, net_w, net_h, &nw, &nh, &ox, &oy);
+    if (rc != DD_OK) return rc;
+    g->ax = (double)ox / (double)net_w; g->bx = (double)nw / (double)net_w;
+    g->ay = (double)oy / (double)net_h; g->by = (double)nh / (double)net_h;
+    return DD_OK;
+}
+
+// yolov5_decode for frames of img_w x img_h that went through the letterbox into a net_w x net_h canvas
+int yolov5_decode_letterbox(hipStream_t s, const float *raw, int n_rows, int n_cls, float thr, int img_w, int img_h, int net_w, int net_h,
+                            float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch, void *scratch) {
+    YoloLetterbox g;
+    const int rc = yolo_letterbox_terms(img_w, img_h, net_w, net_h, &g);
+    if (rc != DD_OK) return rc;
+    float *conf = static_cast<float *>(scratch);
+    int *cls = reinterpret_cast<int *>(conf + (size_t)batch * n_rows);
+    const long long total = (long long)batch * n_rows;
+    DD_REQUIRE(total < (1LL << 31), DD_E_CAPACITY, "yolov5_decode_letterbox: %lld rows exceed 32-bit indexing", total);
+    hipLaunchKernelGGL(yolo_conf_k, dim3((unsigned)std::min<long long>((total + 7) / 8, 256 * 32)), dim3(256), 0, s, raw, (int)total, n_cls, conf, cls);
+    DD_LAUNCH_CHECK();
+    hipLaunchKernelGGL(yolo_compact_k<true>, dim3(batch), dim3(1024), 0, s, raw, conf, cls, n_rows, 5 + n_cls, thr, (float)img_w, (float)img_h,
+                       out_boxes, out_scores, out_cls, cap, out_n, g);
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
+// yolov5_select likewise
+int yolov5_select_letterbox(hipStream_t s, const float *boxes4, const float *conf, const int *cls, int n_rows, float thr, int img_w, int img_h,
+                            int net_w, int net_h, float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch) {
+    YoloLetterbox g;
+    const int rc = yolo_letterbox_terms(img_w, img_h, net_w, net_h, &g);
+    if (rc != DD_OK) return rc;
+    hipLaunchKernelGGL(yolo_compact_k<true>, dim3(batch), dim3(1024), 0, s, boxes4, conf, cls, n_rows, 4, thr, (float)img_w, (float)img_h, out_boxes,
+                       out_scores, out_cls, cap, out_n, g);
     DD_LAUNCH_CHECK();
     return DD_OK;
 }
@@ -393,8 +448,8 @@ int yolov5_decode(hipStream_t s, const float *raw, int n_rows, int n_cls, float 
 // [batch][n_rows][4] (x, y, w, h), conf, cls [batch][n_rows].
 int yolov5_select(hipStream_t s, const float *boxes4, const float *conf, const int *cls, int n_rows, float thr, float img_w, float img_h,
                   float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch) {
-    hipLaunchKernelGGL(yolo_compact_k, dim3(batch), dim3(1024), 0, s, boxes4, conf, cls, n_rows, 4, thr, img_w, img_h, out_boxes,
-                       out_scores, out_cls, cap, out_n);
+    hipLaunchKernelGGL(yolo_compact_k<false>, dim3(batch), dim3(1024), 0, s, boxes4, conf, cls, n_rows, 4, thr, img_w, img_h, out_boxes,
+                       out_scores, out_cls, cap, out_n, YoloLetterbox{0, 1, 0, 1});
     DD_LAUNCH_CHECK();
     return DD_OK;
 }
@@ -479,6 +534,19 @@ int dd_yolov5_decode(dd_ctx *ctx, const float *raw, int n_rows, int n_cls, float
     if ((rc = ctx->scratch[2].reserve((size_t)n_rows * 8 + 256)) != DD_OK) return rc;
     return ddk::yolov5_decode(s, raw, n_rows, n_cls, thr, img_w, img_h, out_boxes, out_scores, out_cls, cap, out_n, 1,
                               ctx->scratch[2].p);
+}
+
+int dd_yolov5_decode_letterbox(dd_ctx *ctx, const float *raw, int n_rows, int n_cls, float thr, int img_w, int img_h, int net_w, int net_h,
+                               float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, void *stream) {
+    DD_REQUIRE(ctx && raw && out_boxes && out_scores && out_cls && out_n && n_rows >= 0 && n_cls > 0 && cap >= 0,
+               DD_E_ARG, "dd_yolov5_decode_letterbox: bad argument");
+    DD_DEVICE(ctx);
+    hipStream_t s = dd_pick_stream(ctx, stream);
+    if (n_rows == 0) { DD_HIP(hipMemsetAsync(out_n, 0, sizeof(int), s)); return DD_OK; }
+    int rc;
+    if ((rc = ctx->scratch[2].reserve((size_t)n_rows * 8 + 256)) != DD_OK) return rc;
+    return ddk::yolov5_decode_letterbox(s, raw, n_rows, n_cls, thr, img_w, img_h, net_w, net_h, out_boxes, out_scores, out_cls, cap, out_n, 1,
+                                        ctx->scratch[2].p);
 }
 
 int dd_counts_accumulate(dd_ctx *ctx, int64_t *acc, const int64_t *counts_host, int n, void *stream) {

@@ -43,7 +43,11 @@ class MultiStreamPipeline:
                  nms_max_overlap=0.6, max_iou_distance=0.7, max_age=60, n_init=3, context=None, run_detector=True,
                  encoder_max_batch=None, track_capacity=512, gallery_capacity=256, background_subtraction_ratio=None,
                  background_masking=False, graph=None, object_detector_skip_frames=None, metric='cosine',
-                 association='host'):
+                 association='host', detector_letterbox=False):
+        from .tools.yolov5 import letterbox_pad
+        self.detector_letterbox = letterbox_pad(detector_letterbox)      # None, or the pad value of the YOLOv5 detector's letterboxed input
+        if self.detector_letterbox is not None and 'yolov5' not in model:      # before anything is built
+            raise ValueError('%s: detector_letterbox is the YOLOv5 detector\'s option; the other detectors are trained on stretched input' % model)
         self.metric = metric
         metric_kind = _metric_kind(metric)   # 'cosine' or 'euclidean' (nn_matching.py:126-132), else ValueError -- before anything is built
         self.association = association
@@ -131,6 +135,8 @@ class MultiStreamPipeline:
                                                 float(ssd_post['nms_iou_threshold'])), 'dd_pipeline_ssd_options')
             if ssd_post.get('use_regular_nms'):                     # the file asks for the op's per-class NMS (csrc/post_regular.hip)
                 check(lib().dd_pipeline_ssd_regular_nms(self._h, int(ssd_post['detections_per_class'])), 'dd_pipeline_ssd_regular_nms')
+        if self.detector_letterbox is not None and self.det is not None:      # the step's stretch becomes the letterbox launch (csrc/letterbox.hip)
+            check(lib().dd_pipeline_detector_letterbox(self._h, self.detector_letterbox), 'dd_pipeline_detector_letterbox')
         if self.kind == 'tflite' and self.det is not None:          # tools/tflite.py's adaptor instead of tools/ssd_mobilenet.py's
             check(lib().dd_pipeline_detector_adaptor(self._h, 2), 'dd_pipeline_detector_adaptor')
         off = 0 if self.kind == 'yolov5' else 1                     # yolov5.py:134 labels[idx]; ssd_mobilenet.py:142-147 labels[idx + 1]

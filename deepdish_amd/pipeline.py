@@ -26,13 +26,16 @@ DEFAULT_LABELS = os.path.join(HERE, 'assets', 'coco_labels_ssd.txt')
 DEFAULT_YOLO_LABELS = os.path.join(HERE, 'assets', 'coco_classes.txt')
 
 
-def make_detector(model, labels=None, wanted_labels=('person',), num_threads=4, context=None):
-    """Plugin selection by substring of --model, as deepdish.py:482-502."""
+def make_detector(model, labels=None, wanted_labels=('person',), num_threads=4, context=None, letterbox=False):
+    """Plugin selection by substring of --model, as deepdish.py:482-502.  letterbox: YOLOv5 only (tools/yolov5.py here) -- the other
+    detectors are trained on stretched input, so the option set for them is a ValueError before anything is built."""
     wanted = list(wanted_labels)
     if 'yolov5' in model:
         from .tools.yolov5 import YOLOV5
         return YOLOV5(wanted_labels=wanted, model_file=model, label_file=labels or DEFAULT_YOLO_LABELS,
-                      num_threads=num_threads, context=context)
+                      num_threads=num_threads, context=context, letterbox=letterbox)
+    if letterbox is not False and letterbox is not None:
+        raise ValueError('%s: letterboxed input is the YOLOv5 detector\'s option; SSD-MobileNet and the TFLite adaptor resize by stretching' % model)
     if 'yolo' in model or 'saved_model' in model:
         raise ValueError('%s: the Keras YOLOv3 / SavedModel detectors are outside the hot path of this build' % model)
     if 'mobilenet' in model:
@@ -74,7 +77,9 @@ class HotPath:
                  context=None, run_detector=True, disable_background_subtraction=True, background_subtraction_ratio=0.25,
                  enable_background_masking=False, log=None, restore_from_log=False, mqtt_publish=None, mqtt_topic='default/topic',
                  mqtt_acp_id=None, mqtt_verbosity=1, cpu_temp=None, annotations=None, object_detector_skip_frames=None,
-                 metric='cosine', association='host'):
+                 metric='cosine', association='host', detector_letterbox=False):
+        if detector_letterbox is not False and detector_letterbox is not None and 'yolov5' not in model:      # before anything is built
+            raise ValueError('%s: detector_letterbox is the YOLOv5 detector\'s option; the other detectors are trained on stretched input' % model)
         nn_matching.metric_kind(metric)              # 'cosine' or 'euclidean' (nn_matching.py:126-132), else ValueError -- before anything is built
         association_kind(association)                # 'host' or 'device', else ValueError -- likewise
         self.ctx = context or default_context()
@@ -87,7 +92,7 @@ class HotPath:
         self.backSub = createBackgroundSubtractorMOG2(context=self.ctx) if self.background_subtraction else None
         self.wanted_labels = list(wanted_labels)
         self.nms_max_overlap = nms_max_overlap
-        self.object_detector = make_detector(model, labels, wanted_labels, num_threads, self.ctx) if run_detector else None
+        self.object_detector = make_detector(model, labels, wanted_labels, num_threads, self.ctx, letterbox=detector_letterbox) if run_detector else None
         self.encoder = gdet.create_box_encoder(encoder_model, batch_size=encoder_batch_size, num_threads=num_threads,
                                                context=self.ctx)
         # deepdish.py:515-516 asks for "cosine"; with 'euclidean' the same threshold bounds the squared distance of the encoder's rows

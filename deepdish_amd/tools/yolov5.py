@@ -1,6 +1,6 @@
 """YOLOv5 detector plugin with the reference's surface (tools/yolov5.py:37-146 upstream).
 
-Device side: Lanczos stretch resize -> YOLOv5s forward with the Detect decode fused into the head
+Device side: Lanczos stretch resize (or, with letterbox=..., the aspect-preserving padded canvas of csrc/letterbox.hip) -> YOLOv5s forward with the Detect decode fused into the head
 convs (csrc/nets.hip) -> score/argmax/threshold/scale compaction (csrc/post.hip).  No NMS here, as in
 the reference: every candidate flows on to deep_sort's non_max_suppression.
 """
@@ -15,11 +15,25 @@ from ..engine import Net
 from .weights_io import load_named_weights, load_yolov5_weights
 
 
+def letterbox_pad(letterbox):
+    """The `letterbox` option -> None (off: the reference adaptor's stretch, tools/yolov5.py:99) or the canvas's pad value.  True = 114, the
+    grey YOLOv5's own pre-processing pads with (external to the reference tree: quoted from general knowledge of that project); an int
+    0..255 is that value (128 is the canvas of the reference's YOLOv3 letterbox_image)."""
+    if letterbox is False or letterbox is None:
+        return None
+    if letterbox is True:
+        return 114
+    if isinstance(letterbox, (int, np.integer)) and 0 <= int(letterbox) <= 255:
+        return int(letterbox)
+    raise ValueError('letterbox must be False, True (pad 114) or a pad value 0..255, got %r' % (letterbox,))
+
+
 class YOLOV5:
     MAX_ROWS = 4096
 
     def __init__(self, wanted_labels=None, model_file=None, label_file=None, num_threads=None, edgetpu=False,
-                 libedgetpu=None, score_threshold=0.25, context=None):
+                 libedgetpu=None, score_threshold=0.25, context=None, letterbox=False):
+        self.letterbox = letterbox_pad(letterbox)                # None = stretch (the reference); else the pad value of the letterboxed input
         basedir = os.getenv('DEEPDISHHOME', '.')
         if model_file is None:
             model_file = os.path.join(basedir, 'detectors/yolov5/yolov5s-int8.tflite')
@@ -56,6 +70,8 @@ class YOLOV5:
             return {i: line.strip() for i, line in enumerate(f.readlines())}
 
     def _run_device(self, img_dev, H, W, src_c, swap_rb):
+        if self.letterbox is not None:
+            return self._run_device_letterbox(img_dev, H, W, src_c, swap_rb)
         check(lib().dd_resize_lanczos(self.ctx.handle, ptr(img_dev), H, W, src_c, int(swap_rb), ptr(self._resized),
                                       self.height, self.width, None), 'dd_resize_lanczos')       # yolov5.py:99
         self.net.forward(self._resized)                                                          # :107-109
@@ -63,6 +79,20 @@ class YOLOV5:
                                      float(self.score_threshold), float(W), float(H), ptr(self._boxes),
                                      ptr(self._scores), ptr(self._cls), self.MAX_ROWS, ptr(self._n), None),
               'dd_yolov5_decode')                                                                # :120-131
+        self.ctx.sync()
+        n = min(int(self._n.cpu().numpy()[0]), self.MAX_ROWS)
+        return self._boxes[:n].cpu().numpy(), self._scores[:n].cpu().numpy(), self._cls[:n].cpu().numpy()
+
+    def _run_device_letterbox(self, img_dev, H, W, src_c, swap_rb):
+        """The same three steps on aspect-preserving input: Pillow's Lanczos resize pasted into a padded canvas in one launch, the forward,
+        and the decode with the boxes mapped back from the canvas to the frame."""
+        check(lib().dd_resize_lanczos_letterbox(self.ctx.handle, ptr(img_dev), 1, H, W, src_c, int(swap_rb), ptr(self._resized),
+                                                self.height, self.width, self.letterbox, None), 'dd_resize_lanczos_letterbox')
+        self.net.forward(self._resized)
+        check(lib().dd_yolov5_decode_letterbox(self.ctx.handle, self.net.output_ptr(), self.n_rows, self.n_cls,
+                                               float(self.score_threshold), int(W), int(H), self.width, self.height, ptr(self._boxes),
+                                               ptr(self._scores), ptr(self._cls), self.MAX_ROWS, ptr(self._n), None),
+              'dd_yolov5_decode_letterbox')
         self.ctx.sync()
         n = min(int(self._n.cpu().numpy()[0]), self.MAX_ROWS)
         return self._boxes[:n].cpu().numpy(), self._scores[:n].cpu().numpy(), self._cls[:n].cpu().numpy()

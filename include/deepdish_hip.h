@@ -246,6 +246,24 @@ int dd_resize_lanczos_batch(dd_ctx *ctx, const uint8_t *src, int batch, int H, i
 #define DD_LANCZOS_V_FUSED 6       /* lanczos_fused_k */
 int dd_resize_lanczos_plan(dd_ctx *ctx, int H, int W, int src_c, int swap_rb, int h, int w, int batch, const void *src,
                            const void *dst, const void *tmp, int *h_step, int *v_step, int *h_ksteps, int *v_ksteps);
+/* Aspect-preserving geometry of a W x H frame in a net_w x net_h canvas, as the reference's letterbox_image computes it (yolo3/utils.py:18-28 =
+ * tools/yolo.py:141-151): s = min(net_w * 1.0 / W, net_h * 1.0 / H), new = int(W s) x int(H s), pasted at ((net_w - new_w) // 2,
+ * (net_h - new_h) // 2) -- the same double arithmetic and truncation (49 x 7 into 64 x 64 is 63 x 9 at (0, 27)).  Host only: no context, no
+ * device.  A picture of zero width or height (Pillow raises ValueError there) is DD_E_ARG.  Any out pointer may be NULL. */
+int dd_letterbox_geometry(int W, int H, int net_w, int net_h, int *new_w, int *new_h, int *off_x, int *off_y);
+/* Letterboxed detector input, `batch` frames in one launch: dst u8 [batch][h][w][3] = for the RGB view of each frame
+ *     Image.new('RGB', (w, h), (pad,) * 3).paste(Image.fromarray(rgb).resize((new_w, new_h), Image.LANCZOS), (off_x, off_y))
+ * byte for byte, with dd_letterbox_geometry(W, H, w, h)'s numbers; src_c / swap_rb as in dd_resize_lanczos.  An axis whose size does not
+ * change is copied (640 x 480 into 640 x 640 is swap + paste + pad).  Every canvas byte is written once, nothing outside it.  The reference
+ * letterboxes for its YOLOv3 plugin only and with bicubic; Lanczos (its YOLOv5 adaptor's filter) is this build's choice.
+ * DD_LETTERBOX_FUSED=0 (read once per process) runs the two-launch form for every geometry. */
+int dd_resize_lanczos_letterbox(dd_ctx *ctx, const uint8_t *src, int batch, int H, int W, int src_c, int swap_rb, uint8_t *dst, int h, int w,
+                                int pad, void *stream);
+/* The decision dd_resize_lanczos_letterbox switches on, answered without a device (ctx may be NULL).  *path: 0 = neither axis is
+ * resampled (one copy launch), 1 = letterbox_lanczos_k (both passes through LDS, one launch), 2 = two launches (the dense horizontal pass,
+ * then letterbox_v_pad_k): a geometry whose one-row vertical window exceeds the kernel's 64 KiB LDS budget, or DD_LETTERBOX_FUSED=0.
+ * *rows_per_block: canvas rows a workgroup of the last launch owns. */
+int dd_resize_lanczos_letterbox_plan(dd_ctx *ctx, int H, int W, int src_c, int swap_rb, int h, int w, int batch, int *path, int *rows_per_block);
 /* cv2.resize INTER_LINEAR stretch as tools/tflite_object_detector.py:211 */
 int dd_resize_bilinear(dd_ctx *ctx, const uint8_t *src, int H, int W, int c,
                        uint8_t *dst, int h, int w, void *stream);
@@ -449,6 +467,13 @@ int dd_yolov5_decode(dd_ctx *ctx, const float *raw, int n_rows, int n_cls, float
                      float img_w, float img_h, float *out_boxes, float *out_scores,
                      int *out_cls, int cap, int *out_n, void *stream);
 
+/* dd_yolov5_decode for an img_w x img_h frame that reached the net_w x net_h network through dd_resize_lanczos_letterbox: the corners,
+ * normalised to the canvas, go back to frame pixels as X = (x - off_x / net_w) / (new_w / net_w) * img_w (Y likewise) in f64, rounded once
+ * to f32 -- the shape of tools/yolo.py:78-86, with the integer paste offset where the reference divides by 2. (that is where the pixels
+ * are).  No int(), no clipping: boxes in the padding come out negative.  A frame with the canvas's aspect gives dd_yolov5_decode's bits. */
+int dd_yolov5_decode_letterbox(dd_ctx *ctx, const float *raw, int n_rows, int n_cls, float thr, int img_w, int img_h, int net_w, int net_h,
+                               float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, void *stream);
+
 /* ---------------------------------------------------------------- multi-stream hot path
  * The per-frame call sequence of the reference's Pipeline (deepdish.py:880-885 run_object_detector,
  * :940-960 box hygiene, :995 NMS, :1008 encoder, :1028-1029 tracker, :1035-1114 count line) for
@@ -492,6 +517,11 @@ int dd_pipeline_ssd_regular_nms(dd_pipeline *p, int detections_per_class);
  * motion test and NMS, and its first min(kept boxes, feature rows of that step) boxes pair with those feature rows in order, as the
  * reference's zip() does.  Stage events add nothing to objd / feat on a skip step.  Before the first step. */
 int dd_pipeline_detector_skip_frames(dd_pipeline *p, int n);
+/* Letterboxed detector input for a YOLOv5 pipeline (other detectors: DD_E_ARG -- SSD-MobileNet is trained on stretched input): the step's
+ * Lanczos stretch becomes dd_resize_lanczos_letterbox with this pad value (0 .. 255; 114 is YOLOv5's own, 128 the reference's YOLOv3 canvas)
+ * on the detector stream, and both decode forms un-map their boxes as dd_yolov5_decode_letterbox does.  Everything downstream sees frame
+ * pixels as before.  Before the first step (DD_E_STATE after). */
+int dd_pipeline_detector_letterbox(dd_pipeline *p, int pad);
 /* deep_sort/nn_matching.py:5-28,57-75: the metric of the pipeline's trackers, 0 = cosine (default), 1 = euclidean (other values:
  * DD_E_ARG).  The threshold stays the max_cosine_distance given to dd_pipeline_create, as the reference hands --max-cosine-distance to
  * NearestNeighborDistanceMetric as matching_threshold whatever the metric (deepdish.py:515-516).  Before the first step (DD_E_STATE after). */
