@@ -132,6 +132,11 @@ SIGNATURES = {
     'dd_pipeline_stage_gpu_ms': [P, P, POINTER(ctypes.c_longlong)],
     'dd_pipeline_detector_stream': [P, POINTER(P)],
     'dd_pipeline_detections': [P, c_int, P, P, P, c_int, POINTER(c_int)],
+    'dd_pipeline_overlay': [P, P, c_int, P, P, P, P, P, P, P, P, P],
+    'dd_render_create': [P, c_int, c_int, POINTER(P)],
+    'dd_render_destroy': [P],
+    'dd_render_put_mask': [P, P, c_int, c_int, POINTER(c_int)],
+    'dd_render_draw': [P, P, c_int, P, c_int, P, P, P, P],
     'dd_counts_accumulate': [P, P, P, c_int, P],
 }
 _RESTYPE = {'dd_last_error': c_char_p}

@@ -505,6 +505,78 @@ int dd_pipeline_detections(dd_pipeline *p, int stream, double *boxes_host, doubl
     return DD_OK;
 }
 
+// The overlay elements of the last step, read off the state the step left: the tracker's host mirror, StreamState::db and votes, the
+// tracker input rows (tlwh, doff) and the counters.  Nothing here is kept by the step for this call's sake.
+int dd_pipeline_overlay(dd_pipeline *p, const int *streams_host, int n, int *sizes_host, const int *caps_host, int64_t *track_ints_host,
+                        double *track_tlbr_host, double *points_host, double *cross_host, double *det_tlbr_host, int64_t *counts_host,
+                        double *line_host) {
+    DD_REQUIRE(p && streams_host && sizes_host && n > 0, DD_E_ARG, "dd_pipeline_overlay: bad argument");
+    for (int i = 0; i < n; ++i)
+        DD_REQUIRE(streams_host[i] >= 0 && streams_host[i] < p->S, DD_E_ARG, "dd_pipeline_overlay: stream %d of %d", streams_host[i], p->S);
+    const bool fill = track_ints_host && track_tlbr_host && points_host && cross_host && det_tlbr_host && counts_host && line_host;
+    DD_REQUIRE(!fill || caps_host, DD_E_ARG, "dd_pipeline_overlay: arrays without their capacities");
+    const bool stepped = p->steps > 0 && (int)p->doff.size() == p->S + 1;
+    size_t nt = 0, np = 0, nc = 0, nd = 0;
+    std::vector<int64_t> ints;
+    std::vector<double> means;
+    for (int i = 0; i < n; ++i) {
+        const int z = streams_host[i];
+        StreamState &st = p->st[z];
+        int nl = 0, rc;
+        if ((rc = dd_tracker_count(st.trk, 0, &nl)) != DD_OK) return rc;
+        ints.resize((size_t)nl * 6); means.resize((size_t)nl * 8);
+        if (nl && stepped && (rc = ddk::tracker_read_host(st.trk, 0, ints.data(), means.data())) != DD_OK) return rc;
+        int *sz = sizes_host + (size_t)i * 4;
+        sz[0] = sz[1] = sz[2] = 0;
+        sz[3] = stepped ? p->doff[z + 1] - p->doff[z] : 0;
+        for (int k = 0; stepped && k < nl; ++k) {
+            const int64_t *r = ints.data() + (size_t)k * 6;
+            if (r[1] != CONFIRMED || r[2] > 1) continue;                // deepdish.py:1053
+            const auto it = st.db.find(r[0]);
+            const size_t npts = it == st.db.end() ? 0 : it->second.size();
+            bool crossed = false;
+            if (npts > 1) {                                               // :1071-1078
+                const double a[2] = {it->second[npts - 1].first, it->second[npts - 1].second};
+                const double b[2] = {it->second[npts - 2].first, it->second[npts - 2].second};
+                crossed = seg_intersect(p->line, p->line + 2, a, b);
+            }
+            if (fill) {
+                DD_REQUIRE(nt < (size_t)caps_host[0] && np + npts <= (size_t)caps_host[1] && nc + crossed <= (size_t)caps_host[2], DD_E_CAPACITY,
+                           "dd_pipeline_overlay: more rows than the arrays have room for");
+                const auto vt = st.votes.find(r[0]);
+                const std::string lbl = vt == st.votes.end() ? std::string() : vote_label(p, vt->second);
+                int64_t line_no = -1;
+                for (size_t li = 0; li < p->labels.size() && line_no < 0 && !lbl.empty(); ++li) if (p->labels[li] == lbl) line_no = (int64_t)li;
+                int64_t *ti = track_ints_host + nt * 3;
+                ti[0] = r[0]; ti[1] = line_no; ti[2] = (int64_t)npts;
+                const double *m = means.data() + (size_t)k * 8;
+                const double w = m[2] * m[3];                            // track.py:84-111 to_tlbr
+                double *tb = track_tlbr_host + nt * 4;
+                tb[0] = m[0] - w / 2; tb[1] = m[1] - m[3] / 2; tb[2] = tb[0] + w; tb[3] = tb[1] + m[3];
+                for (size_t q = 0; q < npts; ++q) { points_host[(np + q) * 2] = it->second[q].first; points_host[(np + q) * 2 + 1] = it->second[q].second; }
+                if (crossed) {
+                    double *c = cross_host + nc * 4;
+                    c[0] = it->second[npts - 2].first; c[1] = it->second[npts - 2].second; c[2] = it->second[npts - 1].first; c[3] = it->second[npts - 1].second;
+                }
+            }
+            ++nt; ++sz[0]; np += npts; sz[1] += (int)npts; nc += crossed; sz[2] += crossed;
+        }
+        if (fill) {
+            DD_REQUIRE(nd + sz[3] <= (size_t)caps_host[3], DD_E_CAPACITY, "dd_pipeline_overlay: more detections than the array has room for");
+            for (int j = 0; j < sz[3]; ++j) {                            // detection.py to_tlbr
+                const double *b = p->tlwh.data() + (size_t)(p->doff[z] + j) * 4;
+                double *o = det_tlbr_host + (nd + j) * 4;
+                o[0] = b[0]; o[1] = b[1]; o[2] = b[0] + b[2]; o[3] = b[1] + b[3];
+            }
+            const size_t nw = p->wanted.size() * 4;
+            memcpy(counts_host + (size_t)i * nw, st.counts.data(), nw * sizeof(int64_t));
+        }
+        nd += sz[3];
+    }
+    if (fill) for (int i = 0; i < 4; ++i) line_host[i] = p->line[i];
+    return DD_OK;
+}
+
 int dd_pipeline_stage_seconds(dd_pipeline *p, double *out4_host, long long *steps_host) {
     DD_REQUIRE(p && out4_host, DD_E_ARG, "dd_pipeline_stage_seconds: NULL argument");
     out4_host[0] = p->t_det; out4_host[1] = p->t_nms; out4_host[2] = p->t_enc; out4_host[3] = p->t_trk;

@@ -232,6 +232,52 @@ class MultiStreamPipeline:
         return dict(objd=g[0] / k, nms=g[1] / k, feat=g[2] / k, trak=g[3] / k, host=g[4] / k, wall=g[5] / k, steps=n.value,
                     host_wall=dict(objd=1e3 * t[0] / k, nms=1e3 * t[1] / k, feat=1e3 * t[2] / k, trak=1e3 * t[3] / k))
 
+    def overlay(self, streams=None):
+        """The overlay elements of the last step (dd_pipeline_overlay) for `streams` (default: all): a list with one dict per stream --
+        line f64 [4]; track_ids int64 [t], track_labels (voted label names), track_tlbr f64 [t, 4] and path_counts int64 [t] for the
+        confirmed tracks with time_since_update <= 1 in track order; points f64 [sum(path_counts), 2], their bottom-centre paths behind
+        one another; crossings f64 [c, 4], the segments that crossed the line in this step; det_tlbr f64 [d, 4], the detections that
+        went into the tracker; counts int64 [n_wanted, 4] = pos, neg, int, del."""
+        streams = np.arange(self.S, dtype=np.int32) if streams is None else np.ascontiguousarray(list(streams), dtype=np.int32)
+        n = len(streams)
+        sizes = np.zeros((n, 4), dtype=np.int32)
+        none = P(None)
+        check(lib().dd_pipeline_overlay(self._h, ptr(streams), n, ptr(sizes), none, none, none, none, none, none, none, none), 'dd_pipeline_overlay')
+        caps = np.ascontiguousarray(sizes.sum(axis=0), dtype=np.int32)
+        ti, tb = np.zeros((caps[0], 3), np.int64), np.zeros((caps[0], 4), np.float64)
+        pts, cr, dt = np.zeros((caps[1], 2), np.float64), np.zeros((caps[2], 4), np.float64), np.zeros((caps[3], 4), np.float64)
+        counts, line = np.zeros((n, len(self.wanted), 4), np.int64), np.zeros(4, np.float64)
+        check(lib().dd_pipeline_overlay(self._h, ptr(streams), n, ptr(sizes), ptr(caps), ptr(ti), ptr(tb), ptr(pts), ptr(cr), ptr(dt), ptr(counts),
+                                        ptr(line)), 'dd_pipeline_overlay')
+        end = np.concatenate([np.zeros((1, 4), np.int64), np.cumsum(sizes, axis=0)])
+        out = []
+        for i in range(n):
+            (t0, p0, c0, d0), (t1, p1, c1, d1) = end[i], end[i + 1]
+            out.append(dict(line=line, track_ids=ti[t0:t1, 0], track_labels=[self.label_lines[k] if k >= 0 else '' for k in ti[t0:t1, 1]],
+                            track_tlbr=tb[t0:t1], path_counts=ti[t0:t1, 2], points=pts[p0:p1], crossings=cr[c0:c1], det_tlbr=dt[d0:d1],
+                            counts=counts[i]))
+        return out
+
+    def render(self, frames_dev, streams=None, annotation='label', out=None, font=None):
+        """The reference's annotated output frame (deepdish.py:295-408, 1187-1207) of `streams` (default: all) after the last step, painted
+        over frames_dev (the frames that step received) in one launch (csrc/render.hip) -> u8 [n, H, W, 3] BGR on the device, in the order
+        of `streams`.  annotation = --object-annotation: 'label', 'id' or 'none'.  font: a PIL font (default: Pillow's default face at
+        int(24 / 640 * W)).  Nothing of this runs unless it is called."""
+        from . import render as rd
+        rd.annotation_kind(annotation)
+        assert tuple(frames_dev.shape) == (self.S, self.H, self.W, 3)
+        streams = list(range(self.S)) if streams is None else [int(z) for z in streams]
+        if not hasattr(self, '_renderers'):
+            self._renderers = {}
+        key = id(font) if font is not None else None
+        if key not in self._renderers:
+            self._renderers[key] = (rd.Renderer(self.H, self.W, font=font, context=self.ctx), font)      # (the font is kept alive with its id)
+        r = self._renderers[key][0]
+        prims = [rd.overlay_primitives(r, o['line'], o['track_ids'], o['track_labels'], o['track_tlbr'], o['points'], o['path_counts'], o['crossings'],
+                                       o['det_tlbr'], [(l, int(c[1]), int(c[0])) for l, c in zip(self.wanted, o['counts'])], annotation)
+                 for o in self.overlay(streams)]
+        return r.draw(frames_dev, prims, streams=streams, out=out)
+
     def detections(self, stream):
         """The detector adaptor's output for one stream in the last step: what the reference's detect_image(...) returns
         (tools/ssd_mobilenet.py:198-213) -- (boxes tlwh f64 [n, 4], label names, scores f64 [n]); on a skip step, the last

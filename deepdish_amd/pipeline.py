@@ -186,6 +186,7 @@ class HotPath:
             self.tracker.tracks = self.framerec.process_tracking(framenum, self.tracker)                # :1047
         t3 = time()
         events = self.counter.step(self.tracker)                                                         # :1035-1114
+        self._overlay = (detections, events)          # what render() draws of this step besides the tracker's and the counter's state
         t4 = time()
         self.frame_count += 1
         if self.sink is not None:
@@ -194,6 +195,31 @@ class HotPath:
         if skipped:                                                                                     # :980, :1019
             del self.timings['objd'], self.timings['feat']
         return events
+
+    def render(self, frame_dev, annotation='label', font=None):
+        """The reference's annotated output frame (deepdish.py:295-408, 1187-1207) after the last step, painted over frame_dev (the frame
+        that step received) by csrc/render.hip -> u8 [1, H, W, 3] BGR on the device; MultiStreamPipeline.render for one stream, built from
+        this class's Python tracker objects.  annotation = --object-annotation: 'label', 'id' or 'none'."""
+        from . import render as rd
+        rd.annotation_kind(annotation)
+        H, W = int(frame_dev.shape[0]), int(frame_dev.shape[1])
+        if not hasattr(self, '_renderers'):
+            self._renderers = {}
+        key = (H, W, id(font) if font is not None else None)
+        if key not in self._renderers:
+            self._renderers[key] = (rd.Renderer(H, W, font=font, context=self.ctx), font)
+        r = self._renderers[key][0]
+        detections, events = getattr(self, '_overlay', ([], []))
+        drawn = [t for t in self.tracker.tracks if t.is_confirmed() and t.time_since_update <= 1]      # :1053
+        paths = [self.counter.db.get(t.track_id, []) for t in drawn]
+        points = np.array([p for path in paths for p in path], dtype=np.float64).reshape(-1, 2)
+        crossings = [tuple(self.counter.db[tid][-2]) + tuple(self.counter.db[tid][-1]) for _, _, tid in events]      # :1078 pts[-4:]
+        prims = rd.overlay_primitives(r, np.asarray(self.counter.line, np.float64).reshape(4), [t.track_id for t in drawn],
+                                      [t.get_label() for t in drawn], np.array([t.to_tlbr() for t in drawn], dtype=np.float64).reshape(-1, 4),
+                                      points, [len(p) for p in paths], np.array(crossings, dtype=np.float64).reshape(-1, 4),
+                                      np.array([d.to_tlbr() for d in detections], dtype=np.float64).reshape(-1, 4),
+                                      [(l, self.counter.negcount[l], self.counter.poscount[l]) for l in self.counter.labels], annotation)
+        return r.draw(frame_dev, [prims])
 
     def _attach_features(self, detections, feats_dev):
         """With annotations a track may be extended from a detection later (framerecords.process_tracking): give the

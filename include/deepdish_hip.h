@@ -574,6 +574,37 @@ int dd_pipeline_stage_gpu_ms(dd_pipeline *p, double *out6_host, long long *steps
  * adaptor's label offset); with injected detections, those.  cap rows of room; n_host always gets the row count. */
 int dd_pipeline_detections(dd_pipeline *p, int stream, double *boxes_host, double *scores_host, int *classes_host, int cap, int *n_host);
 
+/* The overlay elements of the last step for `n` streams (deepdish.py:971-974,1066-1086,1122-1134: what the reference hands its renderer),
+ * packed over the streams in the order of streams_host.  sizes_host int32 [n][4] is always filled: per stream the number of drawn tracks
+ * (confirmed, time_since_update <= 1, in track order), of their path points together, of this step's crossing segments and of the
+ * detections that went into the tracker.  The other arrays are filled when every one of them is given, with room for caps_host[4] rows
+ * of each kind in all (DD_E_CAPACITY otherwise): track_ints int64 rows {track id, line of the label file that holds the voted label or
+ * -1, points of its path}; track_tlbr f64 [tracks][4] (to_tlbr()); points f64 [points][2], the bottom-centre path of each track in turn;
+ * cross f64 [crossings][4], the last two path points of a track that crossed the line in this step; det_tlbr f64 [detections][4];
+ * counts int64 [n][n_wanted][4] as dd_pipeline_counts; line f64 [4].  Host work only; between steps. */
+int dd_pipeline_overlay(dd_pipeline *p, const int *streams_host, int n, int *sizes_host, const int *caps_host, int64_t *track_ints_host,
+                        double *track_tlbr_host, double *points_host, double *cross_host, double *det_tlbr_host, int64_t *counts_host,
+                        double *line_host);
+
+/* ---------------------------------------------------------------- renderer (csrc/render.hip)
+ * Paints primitive records over BGR frames in HBM, out of place, one launch for all requested frames.  A record is 8 int32:
+ *   {0, x0, y0, x1, y1, 0, ink, 0}        rectangle outline, Pillow's ImageDraw.rectangle byte for byte (x1 >= x0, y1 >= y0)
+ *   {1, ax, ay, bx, by, width, ink, 0}    line segment: the pixels within width / 2 of it (a capsule; exact integers; width odd, 1 .. 15)
+ *   {2, x, y, w, h, offset, ink, 0}       mask blit: u8 coverage [h][w] at `offset` of the atlas, blended as Pillow's draw_bitmap does
+ * ink = B | G << 8 | R << 16; coordinates lie in -8192 .. 8191 and a canvas is at most 8192 either way (DD_E_ARG otherwise).  Records
+ * are painted in the order given: a later one overwrites an earlier one. */
+typedef struct dd_render dd_render;
+int dd_render_create(dd_ctx *ctx, int frame_h, int frame_w, dd_render **out);
+int dd_render_destroy(dd_render *r);
+/* Appends a coverage mask (host u8 [h][w]) to the atlas; offset_out is what a mask record names.  Complete on return. */
+int dd_render_put_mask(dd_render *r, const uint8_t *mask_host, int w, int h, int *offset_out);
+/* frames_dev: u8 [n_frames][H][W][3].  Output frame i of n is frame streams_host[i] under records prim_off_host[i] ..
+ * prim_off_host[i + 1] - 1 of prims_host (prim_off_host: int32 [n + 1], from 0); a frame without records is a copy.  out_dev: u8
+ * [n][H][W][3], sharing no byte with frames_dev.  Every record is checked before the launch (DD_E_ARG names the first bad one).  Queued on
+ * `stream` (NULL: the context's); draws of one renderer go to one stream at a time. */
+int dd_render_draw(dd_render *r, const uint8_t *frames_dev, int n_frames, const int *streams_host, int n, const int32_t *prims_host,
+                   const int *prim_off_host, uint8_t *out_dev, void *stream);
+
 /* ---------------------------------------------------------------- multi-GPU
  * Sum of the per-stream count vectors (pos, neg, int, del per label; deepdish.py:1141-1145).
  * The collective itself is issued by the host through torch.distributed (RCCL); this entry
