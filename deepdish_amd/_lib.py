@@ -137,6 +137,11 @@ SIGNATURES = {
     'dd_render_destroy': [P],
     'dd_render_put_mask': [P, P, c_int, c_int, POINTER(c_int)],
     'dd_render_draw': [P, P, c_int, P, c_int, P, P, P, P],
+    'dd_jpeg_create': [P, c_int, c_int, c_int, c_int, POINTER(P)],
+    'dd_jpeg_destroy': [P],
+    'dd_jpeg_header': [P, P, c_int, POINTER(c_int)],
+    'dd_jpeg_plan': [c_int, c_int, c_int, POINTER(c_int)],
+    'dd_jpeg_encode': [P, P, c_int, P, c_int64, P, P],
     'dd_counts_accumulate': [P, P, P, c_int, P],
 }
 _RESTYPE = {'dd_last_error': c_char_p}

@@ -278,6 +278,19 @@ class MultiStreamPipeline:
                  for o in self.overlay(streams)]
         return r.draw(frames_dev, prims, streams=streams, out=out)
 
+    def render_jpeg(self, frames_dev, streams=None, annotation='label', quality=95, font=None):
+        """render(...) and then csrc/jpeg.hip: the annotated output frames of `streams` as JPEG files, a list of bytes in the order of
+        `streams` -- what the reference makes of its output frame with cv2.imencode(".jpg", frame) (deepdish.py:168) for the web stream,
+        --output-cvat-dir and --stream-path, but for the restart markers (jpeg.py).  The raw frames never leave the device."""
+        from .jpeg import JpegEncoder
+        frames = self.render(frames_dev, streams=streams, annotation=annotation, font=font)
+        if not hasattr(self, '_jpeg_encoders'):
+            self._jpeg_encoders = {}
+        key = (self.H, self.W, int(quality))
+        if key not in self._jpeg_encoders:
+            self._jpeg_encoders[key] = JpegEncoder(self.H, self.W, quality=quality, context=self.ctx)
+        return self._jpeg_encoders[key].encode_to_host(frames)
+
     def detections(self, stream):
         """The detector adaptor's output for one stream in the last step: what the reference's detect_image(...) returns
         (tools/ssd_mobilenet.py:198-213) -- (boxes tlwh f64 [n, 4], label names, scores f64 [n]); on a skip step, the last

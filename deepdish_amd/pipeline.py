@@ -221,6 +221,18 @@ class HotPath:
                                       [(l, self.counter.negcount[l], self.counter.poscount[l]) for l in self.counter.labels], annotation)
         return r.draw(frame_dev, [prims])
 
+    def render_jpeg(self, frame_dev, annotation='label', quality=95):
+        """render(...) and then csrc/jpeg.hip: the annotated output frame as one JPEG file (bytes) -- the reference's
+        cv2.imencode(".jpg", frame) (deepdish.py:168), but for the restart markers (jpeg.py)."""
+        from .jpeg import JpegEncoder
+        frame = self.render(frame_dev, annotation=annotation)
+        if not hasattr(self, '_jpeg_encoders'):
+            self._jpeg_encoders = {}
+        key = (int(frame.shape[1]), int(frame.shape[2]), int(quality))
+        if key not in self._jpeg_encoders:
+            self._jpeg_encoders[key] = JpegEncoder(key[0], key[1], quality=quality, context=self.ctx)
+        return self._jpeg_encoders[key].encode_to_host(frame)[0]
+
     def _attach_features(self, detections, feats_dev):
         """With annotations a track may be extended from a detection later (framerecords.process_tracking): give the
         detections their feature rows (one small device-to-host copy per frame, only in this mode)."""

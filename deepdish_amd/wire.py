@@ -189,3 +189,9 @@ class ResultSink:
             self.publish(self.topic, json.dumps(heartbeat_mqtt_payload(now, self.acp_id, temp, self.counter)))
         if self.log is not None:
             self.log.write(heartbeat_log_record(now, self.frame_count, temp, self.counter))
+
+
+def mjpeg_part(jpeg_bytes):
+    """deepdish.py:178-179: one part of the multipart/x-mixed-replace web stream, around one JPEG file (jpeg.JpegEncoder,
+    MultiStreamPipeline.render_jpeg)."""
+    return b'--frame\r\n' b'Content-Type: image/jpeg\r\n\r\n' + bytes(jpeg_bytes) + b'\r\n'

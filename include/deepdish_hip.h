@@ -605,6 +605,33 @@ int dd_render_put_mask(dd_render *r, const uint8_t *mask_host, int w, int h, int
 int dd_render_draw(dd_render *r, const uint8_t *frames_dev, int n_frames, const int *streams_host, int n, const int32_t *prims_host,
                    const int *prim_off_host, uint8_t *out_dev, void *stream);
 
+/* ---------------------------------------------------------------- JPEG encoder (csrc/jpeg.hip)
+ * The exit of the render path: BGR frames in HBM -> whole baseline JFIF files in HBM, with no raw download and no CPU encode.  It serves
+ * the three places the reference turns an output frame into JPEG: cv2.imencode(".jpg", frame) for the MJPEG web stream
+ * (deepdish.py:155-181), frame_%06d.jpg under --output-cvat-dir (:764-766) and the file --stream-path names.  The bytes are libjpeg's
+ * for 8-bit YCbCr 4:2:0 with the Annex K tables at `quality` -- Pillow's Image.save(f, 'JPEG', quality=q, subsampling='4:2:0',
+ * restart_marker_rows=r), byte for byte, header included.  The one deviation from cv2.imencode is the DRI segment and the RSTn markers
+ * (an interval is restart_rows MCU rows); every decoder honours them.  Parity with OpenCV's own bytes is not pinned. */
+typedef struct dd_jpeg dd_jpeg;
+#define DD_JPEG_LDS     0   /* an interval's samples and coefficients stay in LDS */
+#define DD_JPEG_STREAM  1   /* an interval too large for LDS: blocks are transformed again from the frame where they are needed */
+/* deepdish.py:168 cv2.imencode(".jpg", frame): one encoder per frame size, quality (1 .. 100; cv2's default is 95) and restart_rows
+ * (>= 1, at most 65535 MCUs in an interval); sides 1 .. 8192.  DD_E_ARG names the bad argument.  ctx may be NULL: such an encoder
+ * answers dd_jpeg_header only.  No device work happens before the first dd_jpeg_encode. */
+int dd_jpeg_create(dd_ctx *ctx, int h, int w, int quality, int restart_rows, dd_jpeg **out);
+int dd_jpeg_destroy(dd_jpeg *enc);
+/* deepdish.py:168: everything cv2.imencode writes before the scan (SOI, JFIF APP0, two DQT, SOF0, four DHT), then DRI and SOS; the same
+ * for every frame of this encoder.  len_host always gets its length; buf_host (may be NULL) gets the bytes when cap suffices
+ * (DD_E_CAPACITY otherwise).  Host only. */
+int dd_jpeg_header(dd_jpeg *enc, uint8_t *buf_host, int cap, int *len_host);
+/* Which kernel path (DD_JPEG_*) a geometry takes (deepdish.py:168 at any frame size); decided from the sizes alone, needs no device. */
+int dd_jpeg_plan(int h, int w, int restart_rows, int *path_host);
+/* deepdish.py:168,178-179,764-766: frames_dev u8 [n][H][W][3] BGR -> out_dev u8 [n][cap], file i at out_dev + i * cap, and lengths_dev
+ * int32 [n].  lengths[i] is always the true length of file i; a file with lengths[i] <= cap is complete in its slot; one that does not
+ * fit writes nothing at all, and the call returns DD_E_CAPACITY after the other frames are done.  Two launches on `stream` (NULL: the
+ * context's); the call then waits for them, because the lengths decide its return value. */
+int dd_jpeg_encode(dd_jpeg *enc, const uint8_t *frames_dev, int n, uint8_t *out_dev, int64_t cap, int *lengths_dev, void *stream);
+
 /* ---------------------------------------------------------------- multi-GPU
  * Sum of the per-stream count vectors (pos, neg, int, del per label; deepdish.py:1141-1145).
  * The collective itself is issued by the host through torch.distributed (RCCL); this entry
