@@ -70,6 +70,9 @@ SIGNATURES = {
     'dd_yuv420_to_bgr': [P, P, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, P, P],
     'dd_ingest_create': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
     'dd_ingest_create_format': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
+    'dd_ingest_create_jpeg': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, P],
+    'dd_ingest_jpeg_put': [P, c_int, c_int, P, c_int64],
+    'dd_ingest_status': [P, c_int, P],
     'dd_ingest_destroy': [P],
     'dd_ingest_host_slot': [P, c_int, P, P],
     'dd_ingest_submit': [P, c_int],
@@ -142,6 +145,13 @@ SIGNATURES = {
     'dd_jpeg_header': [P, P, c_int, POINTER(c_int)],
     'dd_jpeg_plan': [c_int, c_int, c_int, POINTER(c_int)],
     'dd_jpeg_encode': [P, P, c_int, P, c_int64, P, P],
+    'dd_jpeg_parse': [P, c_int64, P],
+    'dd_jpegdec_plan': [c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)],
+    'dd_jpegdec_create': [P, c_int, c_int, c_int, c_int64, POINTER(P)],
+    'dd_jpegdec_destroy': [P],
+    'dd_jpegdec_decode': [P, P, P, P, c_int, P, P, P],
+    'dd_jpegdec_profile': [P, c_int],
+    'dd_jpegdec_profile_read': [P, P],
     'dd_counts_accumulate': [P, P, P, c_int, P],
 }
 _RESTYPE = {'dd_last_error': c_char_p}

@@ -12,14 +12,21 @@
 // the link, and the conversion to BGR (csrc/yuv.hip) happens on the copy stream -- fused with the flip + resize in one launch
 // (yuv420_resize_k), or, with DD_INGEST_YUV_FUSED=0, as convert-into-a-staging-buffer then crop_resize (the same bytes, for A/B runs).
 // The consumer always receives BGR.
+//
+// A slot may also hold baseline JPEG files, what a camera or the reference's frame_%06d.jpg sequence delivers (a tenth or less of the raw
+// bytes): put() copies a stream's file into the slot's pinned arena and parses its header on the calling thread, submit() uploads the
+// bytes in use and the records and decodes on the copy stream (csrc/jpeg_dec.hip) -- into the slot's output, or into a staging buffer
+// in front of crop_resize when a flip or a resize is asked.  Each stream carries a status; a bad file costs its neighbours nothing.
+#include <cstddef>
 #include <cstdlib>
+#include <mutex>
 #include <vector>
 #include "common.h"
 
 struct dd_ingest {
     dd_ctx *ctx = nullptr;
     int slots = 0, S = 0, sh = 0, sw = 0, dh = 0, dw = 0, flip = 0;
-    int format = 0;                         // 0 BGR, 1 NV12, 2 I420
+    int format = 0;                         // 0 BGR, 1 NV12, 2 I420, 3 JPEG files
     bool transform = false, own_out = false, fused = true;
     uint8_t *d_stage = nullptr;             // YUV, two-launch form only: the converted BGR frames [S][sh][sw][3]
     hipStream_t copy = nullptr;
@@ -28,14 +35,24 @@ struct dd_ingest {
     std::vector<char> used, submitted;      // done[slot] / ready[slot] has been recorded at least once
     void *d_boxes = nullptr;                // S full-frame CropBox records
     size_t raw_bytes = 0, out_bytes = 0;
+    // JPEG slots: h_raw[slot] is the arena; per slot the records and the status in pinned memory, the status on the device, the arena's
+    // fill and whether the slot was submitted since it was last reset
+    dd_jpegdec *dec = nullptr;
+    std::vector<dd_jpeg_info *> h_recs;
+    std::vector<int *> h_status, d_status;
+    std::vector<size_t> fill;
+    std::vector<char> stale;
+    std::mutex mu;
 };
 
+constexpr int INGEST_JPEG = 3;
+
 static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip,
-                         int pixel_format, dd_ingest **out) {
+                         int pixel_format, dd_ingest **out, size_t jpeg_slot_bytes = 0) {
     DD_REQUIRE(ctx && out && slots > 0 && n_streams > 0 && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0, DD_E_ARG,
                "%s: bad argument", who);
-    DD_REQUIRE(pixel_format >= 0 && pixel_format <= 2, DD_E_ARG, "%s: pixel_format %d is none of 0 (BGR), 1 (NV12), 2 (I420)", who, pixel_format);
-    if (pixel_format != 0) {
+    DD_REQUIRE((pixel_format >= 0 && pixel_format <= 2) || (pixel_format == INGEST_JPEG && jpeg_slot_bytes), DD_E_ARG, "%s: pixel_format %d is none of 0 (BGR), 1 (NV12), 2 (I420)", who, pixel_format);
+    if (pixel_format == 1 || pixel_format == 2) {
         DD_REQUIRE(src_w % 2 == 0, DD_E_ARG, "%s: src_w %d must be even for 4:2:0 frames", who, src_w);
         DD_REQUIRE(src_h % 2 == 0, DD_E_ARG, "%s: src_h %d must be even for 4:2:0 frames", who, src_h);
         DD_REQUIRE(n_streams <= 65535, DD_E_ARG, "%s: n_streams %d above 65535", who, n_streams);
@@ -47,14 +64,16 @@ static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams,
     g->transform = g->flip || src_h != dst_h || src_w != dst_w;
     g->format = pixel_format;
     g->raw_bytes = pixel_format ? (size_t)n_streams * src_h * src_w * 3 / 2 : (size_t)n_streams * src_h * src_w * 3;
+    if (pixel_format == INGEST_JPEG) g->raw_bytes = jpeg_slot_bytes;
     g->own_out = g->transform || pixel_format != 0;          // BGR without a transform: the uploaded frames are the output
     g->fused = !(getenv("DD_INGEST_YUV_FUSED") && atoi(getenv("DD_INGEST_YUV_FUSED")) == 0);
+    if (pixel_format == INGEST_JPEG) g->fused = false;      // decode into the staging buffer, then crop_resize
     g->out_bytes = (size_t)n_streams * dst_h * dst_w * 3;
     DD_HIP(hipStreamCreateWithFlags(&g->copy, hipStreamNonBlocking));
     for (int i = 0; i < slots; ++i) {
         uint8_t *h = nullptr, *d = nullptr, *o = nullptr;
         DD_HIP(hipHostMalloc(reinterpret_cast<void **>(&h), g->raw_bytes, hipHostMallocDefault));
-        DD_HIP(hipMalloc(reinterpret_cast<void **>(&d), g->raw_bytes + 64));
+        if (pixel_format != INGEST_JPEG) DD_HIP(hipMalloc(reinterpret_cast<void **>(&d), g->raw_bytes + 64));       // the decoder holds the files' device twin
         if (g->own_out) DD_HIP(hipMalloc(reinterpret_cast<void **>(&o), g->out_bytes + 64));
         else o = d;
         hipEvent_t r, dn;
@@ -74,11 +93,74 @@ static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams,
         DD_HIP(hipMalloc(&g->d_boxes, boxes.size() * sizeof(int)));
         DD_HIP(hipMemcpy(g->d_boxes, boxes.data(), boxes.size() * sizeof(int), hipMemcpyHostToDevice));
     }
+    if (pixel_format == INGEST_JPEG) {
+        if (int rc = dd_jpegdec_create(ctx, src_h, src_w, n_streams, (int64_t)jpeg_slot_bytes, &g->dec)) return rc;
+        for (int i = 0; i < slots; ++i) {
+            dd_jpeg_info *r = nullptr;
+            int *hs = nullptr, *ds = nullptr;
+            DD_HIP(hipHostMalloc(reinterpret_cast<void **>(&r), (size_t)n_streams * sizeof(dd_jpeg_info), hipHostMallocDefault));
+            DD_HIP(hipHostMalloc(reinterpret_cast<void **>(&hs), (size_t)n_streams * sizeof(int), hipHostMallocDefault));
+            DD_HIP(hipMalloc(reinterpret_cast<void **>(&ds), (size_t)n_streams * sizeof(int)));
+            g->h_recs.push_back(r); g->h_status.push_back(hs); g->d_status.push_back(ds);
+            g->fill.push_back(0); g->stale.push_back(1);
+        }
+    }
     *out = g;
     return DD_OK;
 }
 
+// A JPEG slot before its first put after a submit: wait until the last upload has left it, then empty it.  Caller holds g->mu.
+static int ingest_jpeg_reset(dd_ingest *g, int slot) {
+    if (!g->stale[slot]) return DD_OK;
+    if (g->submitted[slot]) DD_HIP(hipEventSynchronize(g->ready[slot]));
+    for (int z = 0; z < g->S; ++z) {
+        memset(&g->h_recs[slot][z], 0, offsetof(dd_jpeg_info, quant));      // the scalar fields; the next parse rewrites the tables
+        g->h_recs[slot][z].status = DD_JPEG_ST_NO_FRAME;
+    }
+    g->fill[slot] = 0;
+    g->stale[slot] = 0;
+    return DD_OK;
+}
+
 extern "C" {
+
+int dd_ingest_create_jpeg(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip, int64_t slot_bytes,
+                          dd_ingest **out) {
+    DD_REQUIRE(slot_bytes >= 1, DD_E_ARG, "dd_ingest_create_jpeg: slot_bytes %lld", (long long)slot_bytes);
+    return ingest_create("dd_ingest_create_jpeg", ctx, slots, n_streams, src_h, src_w, dst_h, dst_w, flip, INGEST_JPEG, out, (size_t)slot_bytes);
+}
+
+int dd_ingest_jpeg_put(dd_ingest *g, int slot, int stream, const uint8_t *data_host, int64_t n) {
+    DD_REQUIRE(g && data_host && slot >= 0 && slot < g->slots && stream >= 0 && stream < g->S && n >= 1 && n <= 0x7fffffffll, DD_E_ARG,
+               "dd_ingest_jpeg_put: bad argument");
+    DD_REQUIRE(g->format == INGEST_JPEG, DD_E_STATE, "dd_ingest_jpeg_put: the ring does not hold JPEG files");
+    DD_DEVICE(g->ctx);
+    size_t at;
+    {
+        std::lock_guard<std::mutex> lk(g->mu);
+        if (int rc = ingest_jpeg_reset(g, slot)) return rc;
+        at = (g->fill[slot] + 63) & ~(size_t)63;
+        DD_REQUIRE(at + (size_t)n <= g->raw_bytes, DD_E_CAPACITY, "dd_ingest_jpeg_put: a file of %lld bytes at offset %zu of a slot of %zu bytes", (long long)n, at,
+                   g->raw_bytes);
+        g->fill[slot] = at + (size_t)n;
+    }
+    // the copy and the parse run outside the lock: decoder threads share that work.  A stream's record belongs to the thread that puts it.
+    memcpy(g->h_raw[slot] + at, data_host, (size_t)n);
+    dd_jpeg_info *rec = &g->h_recs[slot][stream];
+    ddk::jpegdec_parse(g->h_raw[slot] + at, (size_t)n, g->sh, g->sw, rec);
+    rec->file_offset = (int64_t)at;
+    return DD_OK;
+}
+
+int dd_ingest_status(dd_ingest *g, int slot, int *status_host) {
+    DD_REQUIRE(g && status_host && slot >= 0 && slot < g->slots, DD_E_ARG, "dd_ingest_status: bad argument");
+    DD_REQUIRE(g->format == INGEST_JPEG, DD_E_STATE, "dd_ingest_status: the ring does not hold JPEG files");
+    DD_REQUIRE(g->submitted[slot], DD_E_STATE, "dd_ingest_status: slot %d was never submitted", slot);
+    DD_DEVICE(g->ctx);
+    DD_HIP(hipEventSynchronize(g->ready[slot]));
+    memcpy(status_host, g->h_status[slot], (size_t)g->S * sizeof(int));
+    return DD_OK;
+}
 
 int dd_ingest_create(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip,
                      dd_ingest **out) {
@@ -96,12 +178,18 @@ int dd_ingest_destroy(dd_ingest *g) {
     for (int i = 0; i < g->slots; ++i) {
         (void)hipHostFree(g->h_raw[i]);
         if (g->own_out) (void)hipFree(g->d_out[i]);
-        (void)hipFree(g->d_raw[i]);
+        if (g->d_raw[i]) (void)hipFree(g->d_raw[i]);
         (void)hipEventDestroy(g->ready[i]);
         (void)hipEventDestroy(g->done[i]);
     }
     if (g->d_boxes) (void)hipFree(g->d_boxes);
     if (g->d_stage) (void)hipFree(g->d_stage);
+    for (size_t i = 0; i < g->h_recs.size(); ++i) {
+        (void)hipHostFree(g->h_recs[i]);
+        (void)hipHostFree(g->h_status[i]);
+        (void)hipFree(g->d_status[i]);
+    }
+    if (g->dec) (void)dd_jpegdec_destroy(g->dec);
     (void)hipStreamDestroy(g->copy);
     delete g;
     return DD_OK;
@@ -109,6 +197,7 @@ int dd_ingest_destroy(dd_ingest *g) {
 
 int dd_ingest_host_slot(dd_ingest *g, int slot, uint8_t **host_ptr, int64_t *n_bytes) {
     DD_REQUIRE(g && host_ptr && slot >= 0 && slot < g->slots, DD_E_ARG, "dd_ingest_host_slot: bad argument");
+    DD_REQUIRE(g->format != INGEST_JPEG, DD_E_STATE, "dd_ingest_host_slot: a JPEG ring's slots are filled through dd_ingest_jpeg_put");
     *host_ptr = g->h_raw[slot];
     if (n_bytes) *n_bytes = (int64_t)g->raw_bytes;
     return DD_OK;
@@ -125,6 +214,20 @@ int dd_ingest_wait_uploaded(dd_ingest *g, int slot) {
 int dd_ingest_submit(dd_ingest *g, int slot) {
     DD_REQUIRE(g && slot >= 0 && slot < g->slots, DD_E_ARG, "dd_ingest_submit: bad slot");
     DD_DEVICE(g->ctx);
+    if (g->format == INGEST_JPEG) {
+        std::lock_guard<std::mutex> lk(g->mu);
+        if (int rc = ingest_jpeg_reset(g, slot)) return rc;                         // a submit without a put: every stream reports "no frame"
+        if (g->used[slot]) DD_HIP(hipStreamWaitEvent(g->copy, g->done[slot], 0));
+        uint8_t *dst = g->transform ? g->d_stage : g->d_out[slot];
+        int rc = ddk::jpegdec_launch(g->dec, g->h_recs[slot], g->h_raw[slot], g->fill[slot], g->S, dst, g->d_status[slot], g->copy, nullptr);
+        if (rc == DD_OK && g->transform) rc = ddk::crop_resize(g->copy, g->d_stage, g->sh, g->sw, g->d_boxes, g->S, g->dh, g->dw, g->d_out[slot]);
+        if (rc != DD_OK) return rc;
+        DD_HIP(hipMemcpyAsync(g->h_status[slot], g->d_status[slot], (size_t)g->S * sizeof(int), hipMemcpyDeviceToHost, g->copy));
+        DD_HIP(hipEventRecord(g->ready[slot], g->copy));
+        g->submitted[slot] = 1;
+        g->stale[slot] = 1;
+        return DD_OK;
+    }
     if (g->used[slot]) DD_HIP(hipStreamWaitEvent(g->copy, g->done[slot], 0));       // the previous consumer of this slot
     DD_HIP(hipMemcpyAsync(g->d_raw[slot], g->h_raw[slot], g->raw_bytes, hipMemcpyHostToDevice, g->copy));
     if (g->format) {

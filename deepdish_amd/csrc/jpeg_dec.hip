@@ -1,0 +1,533 @@
+// Baseline JPEG decoder for files that arrive in host memory: BGR frames in HBM, byte for byte what libjpeg gives for them (Pillow's
+// Image.open(f).convert('RGB'), channels swapped; tests/jpeg_dec_ref.py is the definition).  Serves the frame_%06d.jpg sequence the
+// reference reads under --input-cvat-dir (deepdish.py:685-689, :727) and MJPEG cameras, through the ingest ring (csrc/ingest.hip) or on
+// its own.  All integer arithmetic.
+//
+// The host parses each header (csrc/jpeg_parse.h, bounded by the header) and uploads the records and the file bytes; then
+//   jpeg_markers_k   one workgroup per file finds the RSTn markers in its scan bytes and writes each restart interval's start and end;
+//   jpeg_entropy_k   one lane per restart interval decodes it (csrc/jpeg_dec_dev.h; Huffman decoding is serial inside an interval) and
+//                    stores the non-zero quantised coefficients, int16, natural order, into a zeroed buffer in HBM;
+//   jpeg_pixels_k    one workgroup per band (one MCU row) of a frame: dequantisation and the IDCT, one 8x8 block per thread, into sample
+//                    planes in LDS; then fancy up-sampling and colour conversion, BGR rows stored in order.  The h2v2 filter's one
+//                    chroma row above and below the band comes from transforming those neighbouring chroma blocks again.
+// A band too wide for LDS (DD_JPEGDEC_PLANES) takes its planes through HBM: jpeg_planes_k transforms, jpeg_pixels_k reads them back.
+// Files of one call may differ in tables, sampling and restart interval; a file that is refused or damaged sets its own status and
+// writes nothing outside its own frame.
+#include "common.h"
+#include "jpeg_dec_dev.h"
+#include <cstdlib>
+#include <new>
+
+namespace {
+
+constexpr int JD_T = 256;                      // threads per workgroup (markers, pixels)
+constexpr int JD_CHUNK = 16;                   // scan bytes per thread and pass of jpeg_markers_k
+constexpr int JD_LDS_MAX = 64 * 1024;          // a band's planes; what every kernel may use without asking
+
+struct JdGeom {
+    int H, W, max_bands;
+    long long coef_stride;                     // int16 per frame: the largest accepted sampling's blocks
+    long long plane_stride;                    // bytes per frame of the HBM planes
+};
+
+struct JdBand {
+    int Wy, Wc, yrows, crows, halo;
+    size_t lds;
+};
+
+__host__ __device__ inline JdBand jd_band(int W, int ncomp, int hs, int vs) {
+    JdBand b;
+    const int mx = (W + 8 * hs - 1) / (8 * hs);
+    b.Wy = mx * 8 * hs, b.Wc = mx * 8;
+    b.yrows = 8 * vs;
+    b.halo = ncomp == 3 && vs == 2 ? 1 : 0;
+    b.crows = ncomp == 3 ? 8 + 2 * b.halo : 0;
+    b.lds = (size_t)b.yrows * b.Wy + 2 * (size_t)b.crows * b.Wc;
+    return b;
+}
+
+// ------------------------------------------------------------------------------------------------ device
+
+// Exclusive prefix sum over the workgroup's threads; total: the sum.  sc: 4 words of LDS.
+__device__ __forceinline__ int jd_scan(int v, int *sc, int &total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(x, o);
+        if (lane >= o) x += y;
+    }
+    __syncthreads();
+    if (lane == 63) sc[w] = x;
+    __syncthreads();
+    int base = 0, t = 0;
+#pragma unroll
+    for (int i = 0; i < JD_T / 64; ++i) {
+        const int s = sc[i];
+        if (i < w) base += s;
+        t += s;
+    }
+    total = t;
+    return base + x - v;
+}
+
+// One workgroup per file.  iv_start / iv_end: per restart interval, offsets into the file's scan bytes.  mark[f]: the status the
+// later kernels go by (the host's, or DD_JPEG_ST_DATA for a wrong marker count or sequence); status[f]: the caller's copy.
+__global__ __launch_bounds__(JD_T) void jpeg_markers_k(const dd_jpeg_info *__restrict__ recs, const uint8_t *__restrict__ bytes, uint32_t *__restrict__ iv_start,
+                                                       uint32_t *__restrict__ iv_end, int *__restrict__ mark, int *__restrict__ status) {
+    __shared__ int sc[4];
+    __shared__ int bad;
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const dd_jpeg_info &r = recs[f];
+    if (r.status != DD_JPEG_ST_OK) {
+        if (tid == 0) mark[f] = r.status, status[f] = r.status;
+        return;
+    }
+    const uint8_t *scan = bytes + r.file_offset + r.scan_offset;
+    const uint32_t len = (uint32_t)r.scan_length;
+    const int n_int = r.n_intervals;
+    uint32_t *st = iv_start + r.interval_base, *en = iv_end + r.interval_base;
+    if (tid == 0) bad = 0, st[0] = 0;
+    int found = 0;                                              // markers in front of this pass
+    for (uint32_t w0 = 0; w0 + 1 < len; w0 += JD_T * JD_CHUNK) {
+        const uint32_t p0 = w0 + (uint32_t)tid * JD_CHUNK;
+        int cnt = 0;
+        for (uint32_t p = p0; p < p0 + JD_CHUNK && p + 1 < len; ++p) cnt += jpd_rst_at(scan, p) >= 0 ? 1 : 0;
+        int all;
+        int k = found + jd_scan(cnt, sc, all);
+        if (cnt)
+            for (uint32_t p = p0; p < p0 + JD_CHUNK && p + 1 < len; ++p) {
+                const int m = jpd_rst_at(scan, p);
+                if (m < 0) continue;
+                if (m != (k & 7) || k + 1 >= n_int) bad = 1;    // RSTn out of sequence, or more markers than intervals
+                else en[k] = p, st[k + 1] = p + 2;
+                ++k;
+            }
+        found += all;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        en[n_int - 1] = len;
+        const int s = bad || found != n_int - 1 ? DD_JPEG_ST_DATA : DD_JPEG_ST_OK;
+        mark[f] = s, status[f] = s;
+    }
+}
+
+// One lane per restart interval, `per` of them in a wave.  Intervals of frames whose status is set are not decoded.
+__global__ __launch_bounds__(64) void jpeg_entropy_k(const dd_jpeg_info *__restrict__ recs, int n, int total, int per, const uint8_t *__restrict__ bytes,
+                                                     const uint32_t *__restrict__ iv_start, const uint32_t *__restrict__ iv_end, const int *__restrict__ mark,
+                                                     int16_t *__restrict__ coef, long long coef_stride, int *__restrict__ status) {
+    if ((int)threadIdx.x >= per) return;
+    const long long idx = (long long)blockIdx.x * per + threadIdx.x;
+    if (idx >= total) return;
+    int lo = 0, hi = n - 1;                                     // the last frame whose first interval is at or before idx
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (recs[mid].interval_base <= idx) lo = mid;
+        else hi = mid - 1;
+    }
+    const int f = lo;
+    const dd_jpeg_info &r = recs[f];
+    const int iv = (int)(idx - r.interval_base);
+    if (iv >= r.n_intervals || mark[f] != DD_JPEG_ST_OK) return;
+    const int mcus = r.mcus_x * r.mcus_y, ri = r.restart_interval ? r.restart_interval : mcus;
+    const int m0 = iv * ri, nm = min(ri, mcus - m0);
+    const uint8_t *scan = bytes + r.file_offset + r.scan_offset;
+    const uint32_t len = (uint32_t)r.scan_length;
+    const uint32_t s = min(iv_start[idx], len), e = min(iv_end[idx], len);
+    if (jpd_decode_interval(r, scan, s, e, m0, nm, coef + (size_t)f * coef_stride) != DD_JPEG_ST_OK) status[f] = DD_JPEG_ST_DATA;
+}
+
+// Block `blk` of a frame: dequantise and transform.  rows: -1 all eight to dst (stride bytes apart), else that one row to dst.
+__device__ __forceinline__ void jd_block(const int16_t *__restrict__ coef, size_t blk, const uint16_t *__restrict__ q, uint8_t *dst, int stride, int row) {
+    int32_t d[64];
+    const uint4 *c4 = reinterpret_cast<const uint4 *>(coef + blk * 64);
+    const uint4 *q4 = reinterpret_cast<const uint4 *>(q);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint4 c = c4[i], v = q4[i];
+        const uint32_t cw[4] = {c.x, c.y, c.z, c.w}, qw[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            d[8 * i + 2 * j] = (int32_t)(int16_t)(cw[j] & 0xffffu) * (int32_t)(qw[j] & 0xffffu);
+            d[8 * i + 2 * j + 1] = (int32_t)(int16_t)(cw[j] >> 16) * (int32_t)(qw[j] >> 16);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) jpd_idct8<8, 11>(&d[c]);
+    if (row < 0) {
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            jpd_idct8<1, 18>(&d[8 * r]);
+            uint32_t lo = 0, hi = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                lo |= (uint32_t)jpd_range_limit(d[8 * r + i]) << (8 * i);
+                hi |= (uint32_t)jpd_range_limit(d[8 * r + 4 + i]) << (8 * i);
+            }
+            *reinterpret_cast<uint2 *>(dst + (size_t)r * stride) = make_uint2(lo, hi);
+        }
+    } else {
+        int32_t e[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) e[i] = row == 0 ? d[i] : d[56 + i];            // the halo rows: a block's first or last
+        jpd_idct8<1, 18>(e);
+        uint32_t lo = 0, hi = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            lo |= (uint32_t)jpd_range_limit(e[i]) << (8 * i);
+            hi |= (uint32_t)jpd_range_limit(e[4 + i]) << (8 * i);
+        }
+        *reinterpret_cast<uint2 *>(dst) = make_uint2(lo, hi);
+    }
+}
+
+// The blocks of MCU row `band` into planes Y [.. ][Wy], Cb and Cr [.. ][Wc]: Y's row 0 is the band's first luma row; the chroma planes'
+// row 0 is the band's first chroma row when halo is 0, else the last chroma row of the band above, and row 9 the first of the band below.
+__device__ __forceinline__ void jd_transform_band(const dd_jpeg_info &r, const int16_t *__restrict__ coef, int band, const JdBand &b, uint8_t *Y, uint8_t *Cb, uint8_t *Cr,
+                                                  bool halo) {
+    const int mx = r.mcus_x, bpm = r.blocks_per_mcu, ny = bpm == 1 ? 1 : bpm - 2, hs = r.hmax;
+    const int per_mcu = bpm + (halo ? 4 : 0);
+    for (int t = threadIdx.x; t < mx * per_mcu; t += JD_T) {
+        const int m = t / per_mcu, k = t - m * per_mcu;
+        const size_t mcu = (size_t)band * mx + m;
+        if (k < ny) {
+            jd_block(coef, mcu * bpm + k, r.quant[r.tq[0]], Y + (size_t)(k / hs) * 8 * b.Wy + (size_t)(m * hs + k % hs) * 8, b.Wy, -1);
+        } else if (k < bpm) {
+            const int c = k - ny + 1;
+            jd_block(coef, mcu * bpm + k, r.quant[r.tq[c]], (c == 1 ? Cb : Cr) + (size_t)(halo ? 1 : 0) * b.Wc + (size_t)m * 8, b.Wc, -1);
+        } else {
+            const int h = k - bpm, c = 1 + (h & 1), below = h >> 1;
+            if (below ? band + 1 >= r.mcus_y : band == 0) continue;          // the frame's edge: the filter repeats the band's own row
+            const size_t nb = ((size_t)(below ? band + 1 : band - 1) * mx + m) * bpm + ny + (c - 1);
+            jd_block(coef, nb, r.quant[r.tq[c]], (c == 1 ? Cb : Cr) + (size_t)(below ? 9 : 0) * b.Wc + (size_t)m * 8, b.Wc, below ? 0 : 7);
+        }
+    }
+}
+
+// Pixel (y, x) of the frame from planes whose row 0 is luma row y0 / chroma row c0: libjpeg's fancy up-sampling over the component's
+// true size cw x ch (plain replication at cw <= 2, as jdsample.c chooses), then jdcolor.c.  Packed B | G << 8 | R << 16.
+__device__ __forceinline__ uint32_t jd_pixel(const dd_jpeg_info &r, const JdBand &b, const uint8_t *Y, const uint8_t *Cb, const uint8_t *Cr, int y0, int c0, int y, int x,
+                                             int cw, int ch) {
+    const int yy = Y[(size_t)(y - y0) * b.Wy + x];
+    if (r.ncomp == 1) return (uint32_t)yy * 0x010101u;
+    int cb, cr;
+    if (r.hmax == 1) {
+        const size_t o = (size_t)(y - c0) * b.Wc + x;
+        cb = Cb[o], cr = Cr[o];
+    } else {
+        const int cx = x >> 1, cy = r.vmax == 2 ? y >> 1 : y;
+        const size_t near = (size_t)(cy - c0) * b.Wc;
+        if (cw <= 2) {
+            cb = Cb[near + cx], cr = Cr[near + cx];
+        } else {
+            const int nx = (x & 1) ? min(cx + 1, cw - 1) : max(cx - 1, 0);
+            if (r.vmax == 1) {
+                const int bias = (x & 1) ? 2 : 1;
+                cb = (3 * Cb[near + cx] + Cb[near + nx] + bias) >> 2;
+                cr = (3 * Cr[near + cx] + Cr[near + nx] + bias) >> 2;
+            } else {
+                const int fy = (y & 1) ? min(cy + 1, ch - 1) : max(cy - 1, 0);
+                const size_t far = (size_t)(fy - c0) * b.Wc;
+                const int bias = (x & 1) ? 7 : 8;
+                cb = (3 * (3 * Cb[near + cx] + Cb[far + cx]) + 3 * Cb[near + nx] + Cb[far + nx] + bias) >> 4;
+                cr = (3 * (3 * Cr[near + cx] + Cr[far + cx]) + 3 * Cr[near + nx] + Cr[far + nx] + bias) >> 4;
+            }
+        }
+    }
+    return jpd_bgr(yy, cb, cr);
+}
+
+// Rows [y_first, y_first + rows) of frame `out` from the planes.  Four pixels a thread, three dword stores, where rows are dword-aligned.
+__device__ __forceinline__ void jd_paint(const dd_jpeg_info &r, const JdBand &b, const uint8_t *Y, const uint8_t *Cb, const uint8_t *Cr, int y0, int c0, int y_first, int rows,
+                                         uint8_t *__restrict__ out, bool vec) {
+    const int W = r.width, H = r.height;
+    const int cw = (W + r.hmax - 1) / r.hmax, ch = (H + r.vmax - 1) / r.vmax;
+    if (vec) {
+        const int qw = W >> 2;
+        for (int i = threadIdx.x; i < rows * qw; i += JD_T) {
+            const int row = i / qw, x = (i - row * qw) * 4, y = y_first + row;
+            uint32_t p[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) p[j] = jd_pixel(r, b, Y, Cb, Cr, y0, c0, y, x + j, cw, ch);
+            uint32_t *o = reinterpret_cast<uint32_t *>(out + ((size_t)y * W + x) * 3);
+            o[0] = p[0] | (p[1] << 24);
+            o[1] = (p[1] >> 8) | (p[2] << 16);
+            o[2] = (p[2] >> 16) | (p[3] << 8);
+        }
+    } else {
+        for (int i = threadIdx.x; i < rows * W; i += JD_T) {
+            const int row = i / W, x = i - row * W, y = y_first + row;
+            const uint32_t p = jd_pixel(r, b, Y, Cb, Cr, y0, c0, y, x, cw, ch);
+            uint8_t *o = out + ((size_t)y * W + x) * 3;
+            o[0] = (uint8_t)p, o[1] = (uint8_t)(p >> 8), o[2] = (uint8_t)(p >> 16);
+        }
+    }
+}
+
+// DD_JPEGDEC_PLANES only: one workgroup per band transforms it into the frame's planes in HBM.
+__global__ __launch_bounds__(JD_T) void jpeg_planes_k(const dd_jpeg_info *__restrict__ recs, JdGeom g, const int *__restrict__ mark, const int16_t *__restrict__ coef,
+                                                      uint8_t *__restrict__ planes) {
+    const int f = blockIdx.x / g.max_bands, band = blockIdx.x - f * g.max_bands;
+    const dd_jpeg_info &r = recs[f];
+    if (mark[f] != DD_JPEG_ST_OK || r.path != DD_JPEGDEC_PLANES || band >= r.mcus_y) return;
+    const JdBand b = jd_band(r.width, r.ncomp, r.hmax, r.vmax);
+    uint8_t *Y = planes + (size_t)f * g.plane_stride, *Cb = Y + (size_t)r.mcus_y * b.yrows * b.Wy, *Cr = Cb + (size_t)r.mcus_y * 8 * b.Wc;
+    jd_transform_band(r, coef + (size_t)f * g.coef_stride, band, b, Y + (size_t)band * b.yrows * b.Wy, Cb + (size_t)band * 8 * b.Wc, Cr + (size_t)band * 8 * b.Wc, false);
+}
+
+// One workgroup per band of a frame.
+__global__ __launch_bounds__(JD_T) void jpeg_pixels_k(const dd_jpeg_info *__restrict__ recs, JdGeom g, const int *__restrict__ mark, const int16_t *__restrict__ coef,
+                                                      const uint8_t *__restrict__ planes, uint8_t *__restrict__ out, int vec) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t jd_lds[];
+    const int f = blockIdx.x / g.max_bands, band = blockIdx.x - f * g.max_bands;
+    const dd_jpeg_info &r = recs[f];
+    if (mark[f] != DD_JPEG_ST_OK || band >= r.mcus_y) return;
+    const JdBand b = jd_band(r.width, r.ncomp, r.hmax, r.vmax);
+    const int y_first = band * b.yrows, rows = min(b.yrows, r.height - y_first);
+    uint8_t *frame = out + (size_t)f * g.H * g.W * 3;
+    if (r.path == DD_JPEGDEC_LDS) {
+        uint8_t *Y = jd_lds, *Cb = Y + (size_t)b.yrows * b.Wy, *Cr = Cb + (size_t)b.crows * b.Wc;
+        jd_transform_band(r, coef + (size_t)f * g.coef_stride, band, b, Y, Cb, Cr, b.halo != 0);
+        __syncthreads();
+        jd_paint(r, b, Y, Cb, Cr, y_first, band * 8 - b.halo, y_first, rows, frame, vec != 0);
+    } else {
+        const uint8_t *Y = planes + (size_t)f * g.plane_stride, *Cb = Y + (size_t)r.mcus_y * b.yrows * b.Wy, *Cr = Cb + (size_t)r.mcus_y * 8 * b.Wc;
+        jd_paint(r, b, Y, Cb, Cr, 0, 0, y_first, rows, frame, vec != 0);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host
+
+int jd_geometry(int h, int w, const char *who, JdGeom *g) {
+    DD_REQUIRE(h >= 1 && w >= 1 && h <= JPD_MAX_SIDE && w <= JPD_MAX_SIDE, DD_E_ARG, "%s: a %d x %d frame (h, w: 1 .. %d either way)", who, w, h, JPD_MAX_SIDE);
+    g->H = h, g->W = w;
+    g->max_bands = (h + 7) / 8;
+    const long long b8w = (w + 7) / 8, b8h = (h + 7) / 8, b16w = (w + 15) / 16, b16h = (h + 15) / 16;
+    long long blocks = 3 * b8w * b8h;                                            // 4:4:4
+    if (4 * b16w * b8h > blocks) blocks = 4 * b16w * b8h;                       // 4:2:2
+    if (6 * b16w * b16h > blocks) blocks = 6 * b16w * b16h;                     // 4:2:0
+    g->coef_stride = blocks * 64;
+    g->plane_stride = 3 * (16 * b16w) * (16 * b16h);                            // every sampling's planes fit in three padded ones
+    return DD_OK;
+}
+
+}  // namespace
+
+struct dd_jpegdec {
+    dd_ctx *ctx = nullptr;
+    JdGeom g{};
+    int max_frames = 0, lanes = 0;
+    size_t max_bytes = 0;
+    DevBuf recs, bytes, coef, starts, mark, planes;
+    PinBuf recs_host;
+    hipEvent_t uploaded = nullptr;
+    bool profile = false, profiled = false;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};       // profile: call start, uploads done, markers, entropy, pixels
+};
+
+namespace ddk {
+
+// The header of one file into *rec, with the status a decoder of h x w gives it (a NULL or empty file: DD_JPEG_ST_NO_FRAME).
+int jpegdec_parse(const uint8_t *file, size_t n, int h, int w, dd_jpeg_info *rec) {
+    char msg[320];
+    if (!file || n == 0) {
+        memset(rec, 0, sizeof(*rec));
+        rec->status = DD_JPEG_ST_NO_FRAME;
+        return rec->status;
+    }
+    if (jpd_parse(file, n, rec, msg, sizeof(msg)) != DD_JPEG_R_OK) {
+        dd_set_error("%s", msg);
+        rec->status = DD_JPEG_ST_HEADER;
+    } else if (rec->height != h || rec->width != w) {
+        dd_set_error("jpeg decoder: a %d x %d file for a decoder of %d x %d", rec->width, rec->height, w, h);
+        rec->status = DD_JPEG_ST_SIZE;
+    }
+    return rec->status;
+}
+
+// recs_host: n records from jpegdec_parse, in memory that stays as it is until the stream has run the upload (pinned: the copy is then
+// asynchronous); file i lies at bytes_host + recs_host[i].file_offset, all within n_bytes.  Fills the records' decoder fields, uploads
+// records and bytes in one copy each (then records `uploaded`, if given), and queues the kernels on s.  No host wait.
+int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, const uint8_t *bytes_host, size_t n_bytes, int n, uint8_t *out_dev, int *status_dev, hipStream_t s,
+                   hipEvent_t uploaded) {
+    DD_REQUIRE(n >= 1 && n <= d->max_frames, DD_E_CAPACITY, "jpeg decoder: %d frames in a call (1 .. %d)", n, d->max_frames);
+    DD_REQUIRE(n_bytes <= d->max_bytes, DD_E_CAPACITY, "jpeg decoder: %zu bytes of files in a call (at most %zu)", n_bytes, d->max_bytes);
+    const JdGeom &g = d->g;
+    long long total = 0;
+    size_t lds = 0;
+    bool any = false, any_planes = false;
+    for (int i = 0; i < n; ++i) {
+        dd_jpeg_info &r = recs_host[i];
+        r.interval_base = (int32_t)total;
+        if (r.status != DD_JPEG_ST_OK) {
+            r.n_intervals = 0;
+            continue;
+        }
+        DD_REQUIRE(r.file_offset >= 0 && (size_t)r.file_offset + (size_t)r.scan_offset + (size_t)r.scan_length <= n_bytes, DD_E_ARG,
+                   "jpeg decoder: file %d lies outside the %zu bytes given", i, n_bytes);
+        const JdBand b = jd_band(r.width, r.ncomp, r.hmax, r.vmax);
+        r.path = b.lds <= (size_t)JD_LDS_MAX ? DD_JPEGDEC_LDS : DD_JPEGDEC_PLANES;
+        if (r.path == DD_JPEGDEC_LDS) lds = b.lds > lds ? b.lds : lds;
+        else any_planes = true;
+        total += r.n_intervals;
+        any = true;
+        DD_REQUIRE(total <= 0x7fffffffll, DD_E_CAPACITY, "jpeg decoder: more than 2^31 restart intervals in a call");
+    }
+    if (int rc = d->starts.reserve((size_t)(total + 1) * 2 * sizeof(uint32_t))) return rc;
+    if (any_planes)
+        if (int rc = d->planes.reserve((size_t)n * (size_t)g.plane_stride)) return rc;
+    dd_jpeg_info *recs = d->recs.as<dd_jpeg_info>();
+    uint8_t *bytes = d->bytes.as<uint8_t>();
+    int16_t *coef = d->coef.as<int16_t>();
+    uint32_t *iv_start = d->starts.as<uint32_t>(), *iv_end = iv_start + total + 1;
+    int *mark = d->mark.as<int>();
+    d->profiled = false;
+    if (d->profile) DD_HIP(hipEventRecord(d->ev[0], s));
+    DD_HIP(hipMemcpyAsync(recs, recs_host, (size_t)n * sizeof(dd_jpeg_info), hipMemcpyHostToDevice, s));
+    if (n_bytes) DD_HIP(hipMemcpyAsync(bytes, bytes_host, n_bytes, hipMemcpyHostToDevice, s));
+    if (uploaded) DD_HIP(hipEventRecord(uploaded, s));
+    if (d->profile) DD_HIP(hipEventRecord(d->ev[1], s));
+    hipLaunchKernelGGL(jpeg_markers_k, dim3((unsigned)n), dim3(JD_T), 0, s, recs, bytes, iv_start, iv_end, mark, status_dev);
+    DD_LAUNCH_CHECK();
+    if (d->profile) DD_HIP(hipEventRecord(d->ev[2], s));
+    if (!any) return DD_OK;
+    DD_HIP(hipMemsetAsync(coef, 0, (size_t)n * (size_t)g.coef_stride * sizeof(int16_t), s));
+    // intervals per wave: a lane decodes serially, so few intervals are spread over many waves (one per SIMD and more: 256 CUs of 4 SIMDs),
+    // and only a call with very many intervals fills its waves
+    int per = 64;
+    while (per > 1 && total / per < 2048) per >>= 1;
+    if (d->lanes) per = d->lanes;
+    hipLaunchKernelGGL(jpeg_entropy_k, dim3((unsigned)((total + per - 1) / per)), dim3(64), 0, s, recs, n, (int)total, per, bytes, iv_start, iv_end, mark, coef,
+                       g.coef_stride, status_dev);
+    DD_LAUNCH_CHECK();
+    if (d->profile) DD_HIP(hipEventRecord(d->ev[3], s));
+    const unsigned grid = (unsigned)n * (unsigned)g.max_bands;
+    if (any_planes) {
+        hipLaunchKernelGGL(jpeg_planes_k, dim3(grid), dim3(JD_T), 0, s, recs, g, mark, coef, d->planes.as<uint8_t>());
+        DD_LAUNCH_CHECK();
+    }
+    const int vec = (g.W & 3) == 0 && (reinterpret_cast<uintptr_t>(out_dev) & 3) == 0;
+    hipLaunchKernelGGL(jpeg_pixels_k, dim3(grid), dim3(JD_T), lds, s, recs, g, mark, coef, d->planes.as<uint8_t>(), out_dev, vec);
+    DD_LAUNCH_CHECK();
+    if (d->profile) {
+        DD_HIP(hipEventRecord(d->ev[4], s));
+        d->profiled = true;
+    }
+    return DD_OK;
+}
+
+}  // namespace ddk
+
+extern "C" {
+
+int dd_jpeg_parse(const uint8_t *file_host, int64_t n, dd_jpeg_info *info) {
+    DD_REQUIRE(file_host && info && n >= 0, DD_E_ARG, "dd_jpeg_parse: NULL argument or a negative length");
+    char msg[320];
+    if (jpd_parse(file_host, (size_t)n, info, msg, sizeof(msg)) != DD_JPEG_R_OK) {
+        dd_set_error("%s", msg);
+        return DD_E_FORMAT;
+    }
+    return DD_OK;
+}
+
+int dd_jpegdec_plan(int h, int w, int ncomp, int hs, int vs, int *path_host, int *band_rows_host, int *bands_host) {
+    JdGeom g;
+    if (int rc = jd_geometry(h, w, "dd_jpegdec_plan", &g)) return rc;
+    DD_REQUIRE((ncomp == 1 && hs == 1 && vs == 1) || (ncomp == 3 && ((hs == 1 && vs == 1) || (hs == 2 && (vs == 1 || vs == 2)))), DD_E_ARG,
+               "dd_jpegdec_plan: %d components with luma sampling %dx%d (1 component, or 3 with 1x1, 2x1 or 2x2)", ncomp, hs, vs);
+    const JdBand b = jd_band(w, ncomp, hs, vs);
+    if (path_host) *path_host = b.lds <= (size_t)JD_LDS_MAX ? DD_JPEGDEC_LDS : DD_JPEGDEC_PLANES;
+    if (band_rows_host) *band_rows_host = b.yrows;
+    if (bands_host) *bands_host = (h + b.yrows - 1) / b.yrows;
+    return DD_OK;
+}
+
+int dd_jpegdec_create(dd_ctx *ctx, int h, int w, int max_frames, int64_t max_bytes, dd_jpegdec **out) {
+    DD_REQUIRE(ctx && out, DD_E_ARG, "dd_jpegdec_create: NULL argument");
+    JdGeom g;
+    if (int rc = jd_geometry(h, w, "dd_jpegdec_create", &g)) return rc;
+    DD_REQUIRE(max_frames >= 1 && (long long)max_frames * g.max_bands <= 0x7fffffffll, DD_E_ARG, "dd_jpegdec_create: max_frames %d", max_frames);
+    DD_REQUIRE(max_bytes >= 1, DD_E_ARG, "dd_jpegdec_create: max_bytes %lld", (long long)max_bytes);
+    DD_DEVICE(ctx);
+    dd_jpegdec *d = new (std::nothrow) dd_jpegdec();
+    DD_REQUIRE(d, DD_E_HIP, "dd_jpegdec_create: out of host memory");
+    d->ctx = ctx, d->g = g, d->max_frames = max_frames, d->max_bytes = (size_t)max_bytes;
+    const char *lanes = getenv("DD_JPEGDEC_LANES");                 // intervals per wave of jpeg_entropy_k, for A/B runs: 1 .. 64
+    if (lanes && atoi(lanes) >= 1 && atoi(lanes) <= 64) d->lanes = atoi(lanes);
+    int rc = d->recs.reserve((size_t)max_frames * sizeof(dd_jpeg_info));
+    if (rc == DD_OK) rc = d->bytes.reserve((size_t)max_bytes + 16);
+    if (rc == DD_OK) rc = d->coef.reserve((size_t)max_frames * (size_t)g.coef_stride * sizeof(int16_t));
+    if (rc == DD_OK) rc = d->mark.reserve((size_t)max_frames * sizeof(int));
+    if (rc == DD_OK) rc = d->recs_host.reserve((size_t)max_frames * sizeof(dd_jpeg_info));
+    if (rc == DD_OK && hipEventCreateWithFlags(&d->uploaded, hipEventDisableTiming) != hipSuccess) {
+        dd_set_error("dd_jpegdec_create: hipEventCreateWithFlags failed");
+        rc = DD_E_HIP;
+    }
+    if (rc != DD_OK) {
+        dd_jpegdec_destroy(d);
+        return rc;
+    }
+    *out = d;
+    return DD_OK;
+}
+
+int dd_jpegdec_destroy(dd_jpegdec *d) {
+    if (!d) return DD_OK;
+    if (d->ctx) (void)hipSetDevice(d->ctx->device);
+    d->recs.release(), d->bytes.release(), d->coef.release(), d->starts.release(), d->mark.release(), d->planes.release();
+    d->recs_host.release();
+    if (d->uploaded) (void)hipEventDestroy(d->uploaded);
+    for (hipEvent_t e : d->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete d;
+    return DD_OK;
+}
+
+int dd_jpegdec_profile(dd_jpegdec *d, int on) {
+    DD_REQUIRE(d, DD_E_ARG, "dd_jpegdec_profile: NULL decoder");
+    DD_DEVICE(d->ctx);
+    if (on)
+        for (hipEvent_t &e : d->ev)
+            if (!e) DD_HIP(hipEventCreate(&e));
+    d->profile = on != 0;
+    d->profiled = false;
+    return DD_OK;
+}
+
+int dd_jpegdec_profile_read(dd_jpegdec *d, float *ms_host) {
+    DD_REQUIRE(d && ms_host, DD_E_ARG, "dd_jpegdec_profile_read: NULL argument");
+    DD_REQUIRE(d->profiled, DD_E_STATE, "dd_jpegdec_profile_read: no profiled decode (dd_jpegdec_profile(dec, 1), then a decode with a frame to decode)");
+    DD_DEVICE(d->ctx);
+    DD_HIP(hipEventSynchronize(d->ev[4]));
+    for (int i = 0; i < 4; ++i) DD_HIP(hipEventElapsedTime(&ms_host[i], d->ev[i], d->ev[i + 1]));
+    return DD_OK;
+}
+
+int dd_jpegdec_decode(dd_jpegdec *d, const uint8_t *files_host, const int64_t *offsets, const int64_t *lengths, int n, uint8_t *out_dev, int *status_dev, void *stream) {
+    DD_REQUIRE(d && files_host && offsets && lengths && out_dev && status_dev, DD_E_ARG, "dd_jpegdec_decode: NULL argument");
+    DD_REQUIRE(n >= 1 && n <= d->max_frames, DD_E_CAPACITY, "dd_jpegdec_decode: %d frames (1 .. %d)", n, d->max_frames);
+    DD_DEVICE(d->ctx);
+    hipStream_t s = dd_pick_stream(d->ctx, stream);
+    dd_jpeg_info *recs = d->recs_host.as<dd_jpeg_info>();
+    size_t n_bytes = 0;
+    for (int i = 0; i < n; ++i) {
+        DD_REQUIRE(offsets[i] >= 0 && lengths[i] >= 0 && lengths[i] <= 0x7fffffffll, DD_E_ARG, "dd_jpegdec_decode: file %d at offset %lld, length %lld", i,
+                   (long long)offsets[i], (long long)lengths[i]);
+        const size_t end = (size_t)offsets[i] + (size_t)lengths[i];
+        DD_REQUIRE(end <= d->max_bytes, DD_E_CAPACITY, "dd_jpegdec_decode: file %d ends at byte %zu, the decoder holds %zu", i, end, d->max_bytes);
+        ddk::jpegdec_parse(files_host + offsets[i], (size_t)lengths[i], d->g.H, d->g.W, &recs[i]);
+        recs[i].file_offset = offsets[i];
+        if (lengths[i] && end > n_bytes) n_bytes = end;
+    }
+    const int rc = ddk::jpegdec_launch(d, recs, files_host, n_bytes, n, out_dev, status_dev, s, d->uploaded);
+    // the records' staging and the caller's bytes are free again once the two copies have run
+    if (rc != DD_OK) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    DD_HIP(hipEventSynchronize(d->uploaded));
+    return DD_OK;
+}
+
+}  // extern "C"

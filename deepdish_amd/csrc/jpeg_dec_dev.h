@@ -1,0 +1,206 @@
+// The statements of the baseline JPEG decoder that run on the card, as __host__ __device__ code: the bit reader, the Huffman decoder,
+// one restart interval's MCUs, and jidctint.c's accurate-integer IDCT.  csrc/jpeg_dec.hip runs them in its kernels;
+// scripts/jpeg_decode_check.cpp runs the same statements on the host under the address and undefined-behaviour sanitizers, over
+// truncated and damaged files, before the card sees any.
+//
+// The bounds are part of the design:
+//   - the bit reader never reads at or beyond the interval's end: it yields zero bits there and counts them (`phantom`);
+//   - the coefficient index is checked against 63 before every store, and every store lands in the block being decoded;
+//   - a code that is not in the table ends the interval;
+//   - the MCU loop runs the interval's MCU count, the block loop the MCU's block count, and every pass of the coefficient loop advances
+//     the index: no input can make a lane loop without end.
+// Arithmetic is 32-bit; what can wrap on hostile coefficients is computed in uint32_t.
+#pragma once
+#include <cstdint>
+#include "jpeg_parse.h"
+
+#if defined(__HIPCC__)
+#define JPD_HD __host__ __device__ __forceinline__
+#else
+#define JPD_HD inline
+#endif
+
+struct JpdBits {
+    const uint8_t *p;
+    uint32_t pos, end;       // next byte, one past the interval's last
+    uint64_t acc;            // the low n bits are unread
+    int n, phantom;          // phantom: how many of them were made up past the end (they are the lowest)
+};
+
+JPD_HD void jpd_bits_open(JpdBits &b, const uint8_t *p, uint32_t start, uint32_t end) {
+    b.p = p, b.pos = start < end ? start : end, b.end = end, b.acc = 0, b.n = 0, b.phantom = 0;
+}
+
+// At least 33 unread bits afterwards.  A 0xFF followed by 0x00 is a stuffed 0xFF; followed by anything else, or by the end, it is a
+// marker, and the interval's data ends in front of it.  Four bytes that lie inside the interval and hold no 0xFF are taken in one load
+// (a lane's time is the latency of its dependent loads); everything else goes byte by byte.
+JPD_HD void jpd_bits_fill(JpdBits &b) {
+    while (b.n <= 32) {
+        if (b.pos + 4 <= b.end && b.pos + 4 > b.pos) {
+            uint32_t w;
+            __builtin_memcpy(&w, b.p + b.pos, 4);
+            w = __builtin_bswap32(w);
+            if (((~w - 0x01010101u) & w & 0x80808080u) == 0) {          // no byte of w is 0xFF
+                b.acc = (b.acc << 32) | w;
+                b.n += 32;
+                b.pos += 4;
+                continue;
+            }
+        }
+        uint32_t v = 0;
+        if (b.pos < b.end) {
+            v = b.p[b.pos];
+            if (v == 0xFF) {
+                if (b.pos + 1 < b.end && b.p[b.pos + 1] == 0) b.pos += 2;
+                else {
+                    b.pos = b.end;
+                    v = 0;
+                    b.phantom += 8;
+                }
+            } else
+                ++b.pos;
+        } else
+            b.phantom += 8;
+        b.acc = (b.acc << 8) | v;
+        b.n += 8;
+    }
+}
+
+JPD_HD uint32_t jpd_peek16(const JpdBits &b) { return (uint32_t)(b.acc >> (b.n - 16)) & 0xFFFFu; }          // n >= 16
+
+JPD_HD uint32_t jpd_take(JpdBits &b, int s) {                                                     // 1 <= s <= 16 <= n
+    b.n -= s;
+    return (uint32_t)(b.acc >> b.n) & ((1u << s) - 1);
+}
+
+// The next symbol, or -1 for a code the table does not hold.
+JPD_HD int jpd_symbol(JpdBits &b, const dd_jpeg_huff &h) {
+    if (b.n < 16) jpd_bits_fill(b);
+    const uint32_t w = jpd_peek16(b);
+    const uint32_t e = h.look[w >> 8];
+    if (e) {
+        b.n -= (int)(e >> 8);
+        return (int)(e & 255);
+    }
+    for (int l = 9; l <= 16; ++l) {
+        const int code = (int)(w >> (16 - l));
+        if (code <= h.maxcode[l]) {
+            const int k = h.valoff[l] + code;
+            if (k < 0 || k >= h.nvals) return -1;
+            b.n -= l;
+            return h.vals[k];
+        }
+    }
+    return -1;
+}
+
+// A coefficient of category s (1 .. 15) from its s bits (Annex F's EXTEND).
+JPD_HD int jpd_extend(JpdBits &b, int s) {
+    if (b.n < 16) jpd_bits_fill(b);
+    const uint32_t v = jpd_take(b, s);
+    return v < (1u << (s - 1)) ? (int)v - (int)((1u << s) - 1) : (int)v;
+}
+
+// The MCUs [mcu0, mcu0 + n_mcu) of one restart interval, whose bytes are scan[start .. end): quantised coefficients, natural order, into
+// coef[(mcu * blocks_per_mcu + k) * 64 ..], which the caller has zeroed.  Returns DD_JPEG_ST_OK or DD_JPEG_ST_DATA.
+JPD_HD int jpd_decode_interval(const dd_jpeg_info &r, const uint8_t *scan, uint32_t start, uint32_t end, int mcu0, int n_mcu, int16_t *coef) {
+    JpdBits b;
+    jpd_bits_open(b, scan, start, end);
+    uint32_t pred[3] = {0, 0, 0};
+    const int bpm = r.blocks_per_mcu, ny = bpm == 1 ? 1 : bpm - 2;
+    for (int m = 0; m < n_mcu; ++m) {
+        for (int k = 0; k < bpm; ++k) {
+            const int c = k < ny ? 0 : k - ny + 1;
+            int16_t *blk = coef + ((size_t)(mcu0 + m) * bpm + k) * 64;
+            const int s = jpd_symbol(b, r.huff[r.td[c] & 1]);
+            if (s < 0 || s > 11) return DD_JPEG_ST_DATA;
+            if (s) pred[c] += (uint32_t)jpd_extend(b, s);
+            blk[0] = (int16_t)(uint16_t)pred[c];
+            const dd_jpeg_huff &ac = r.huff[2 + (r.ta[c] & 1)];
+            for (int j = 1; j < 64; ++j) {
+                const int rs = jpd_symbol(b, ac);
+                if (rs < 0) return DD_JPEG_ST_DATA;
+                const int run = rs >> 4, sz = rs & 15;
+                if (sz == 0) {
+                    if (run != 15) break;
+                    j += 15;
+                    continue;
+                }
+                j += run;
+                const int v = jpd_extend(b, sz);
+                if (j > 63) return DD_JPEG_ST_DATA;
+                blk[JPD_ZIGZAG[j]] = (int16_t)v;
+            }
+            if (b.n < b.phantom) return DD_JPEG_ST_DATA;          // bits were taken from beyond the interval's end
+        }
+    }
+    // what is left must be the padding of the last byte, and behind it a marker or the end
+    if (b.n - b.phantom >= 8) return DD_JPEG_ST_DATA;
+    if (b.pos < b.end && !(b.p[b.pos] == 0xFF && (b.pos + 1 >= b.end || b.p[b.pos + 1] != 0))) return DD_JPEG_ST_DATA;
+    return DD_JPEG_ST_OK;
+}
+
+// The RSTn marker (0 .. 7) at scan[p], p + 1 < len, or -1.
+JPD_HD int jpd_rst_at(const uint8_t *scan, uint32_t p) { return scan[p] == 0xFF && scan[p + 1] >= 0xD0 && scan[p + 1] <= 0xD7 ? scan[p + 1] - 0xD0 : -1; }
+
+// ---- jidctint.c (jpeg_idct_islow): 13-bit constants, the column pass descaled by 11, the row pass by 18.
+
+JPD_HD int32_t jpd_sar(uint32_t x, int n) { return (int32_t)x >> n; }
+
+template <int S, int SHIFT>
+JPD_HD void jpd_idct8(int32_t *d) {
+    typedef uint32_t U;
+    const U c0 = (U)d[0], c1 = (U)d[S], c2 = (U)d[2 * S], c3 = (U)d[3 * S], c4 = (U)d[4 * S], c5 = (U)d[5 * S], c6 = (U)d[6 * S], c7 = (U)d[7 * S];
+    U z1 = (c2 + c6) * 4433u;
+    const U t2 = z1 - c6 * 15137u, t3 = z1 + c2 * 6270u;
+    const U t0 = (c0 + c4) << 13, t1 = (c0 - c4) << 13;
+    const U t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+    U a0 = c7, a1 = c5, a2 = c3, a3 = c1;
+    z1 = a0 + a3;
+    U z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3;
+    const U z5 = (z3 + z4) * 9633u;
+    a0 *= 2446u, a1 *= 16819u, a2 *= 25172u, a3 *= 12299u;
+    z1 *= (U)-7373, z2 *= (U)-20995;
+    z3 = z3 * (U)-16069 + z5;
+    z4 = z4 * (U)-3196 + z5;
+    a0 += z1 + z3, a1 += z2 + z4, a2 += z2 + z3, a3 += z1 + z4;
+    const U r = 1u << (SHIFT - 1);
+    d[0] = jpd_sar(t10 + a3 + r, SHIFT), d[7 * S] = jpd_sar(t10 - a3 + r, SHIFT);
+    d[S] = jpd_sar(t11 + a2 + r, SHIFT), d[6 * S] = jpd_sar(t11 - a2 + r, SHIFT);
+    d[2 * S] = jpd_sar(t12 + a1 + r, SHIFT), d[5 * S] = jpd_sar(t12 - a1 + r, SHIFT);
+    d[3 * S] = jpd_sar(t13 + a0 + r, SHIFT), d[4 * S] = jpd_sar(t13 - a0 + r, SHIFT);
+}
+
+// libjpeg's range-limit table behind the IDCT, addressed through & 1023: the sample + 128, clamped, with the table's wrap.
+JPD_HD int jpd_range_limit(int32_t v) {
+    const int i = v & 1023;
+    return i < 128 ? 128 + i : i < 512 ? 255 : i < 896 ? 0 : i - 896;
+}
+
+// 64 dequantised coefficients (natural order) in d -> 64 samples 0 .. 255 in d.
+JPD_HD void jpd_idct(int32_t (&d)[64]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int c = 0; c < 8; ++c) jpd_idct8<8, 11>(&d[c]);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int r = 0; r < 8; ++r) jpd_idct8<1, 18>(&d[8 * r]);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 64; ++i) d[i] = jpd_range_limit(d[i]);
+}
+
+// jdcolor.c: YCbCr -> B, G, R with FIX(x) = int(x * 65536 + 0.5), packed B | G << 8 | R << 16.
+JPD_HD uint32_t jpd_bgr(int y, int cb, int cr) {
+    cb -= 128, cr -= 128;
+    int r = y + ((91881 * cr + 32768) >> 16);
+    int b = y + ((116130 * cb + 32768) >> 16);
+    int g = y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
+    r = r < 0 ? 0 : r > 255 ? 255 : r;
+    g = g < 0 ? 0 : g > 255 ? 255 : g;
+    b = b < 0 ? 0 : b > 255 ? 255 : b;
+    return (uint32_t)b | ((uint32_t)g << 8) | ((uint32_t)r << 16);
+}

@@ -7,27 +7,33 @@ for them -- the host never blocks on a copy.
 
 With `pixel_format='nv12'` or `'i420'` a slot holds what a decoder produces itself (4:2:0 YUV, 1.5 bytes per pixel): half the bytes
 cross the host link, and the conversion to BGR (csrc/yuv.hip, OpenCV's BT.601 fixed-point arithmetic restated) runs on the copy
-stream in front of the flip + resize.  `yuv420_to_bgr` is the same conversion for frames that are already in device memory."""
+stream in front of the flip + resize.  `yuv420_to_bgr` is the same conversion for frames that are already in device memory.
+
+With `pixel_format='jpeg'` a slot holds baseline JPEG files, what an IP camera's MJPEG stream or the reference's frame_%06d.jpg sequence
+(--input-cvat-dir) delivers -- a tenth or less of the raw bytes: `put(slot, stream, file)` copies a file into the slot's pinned arena and
+parses its header on the calling thread, `submit(slot)` uploads the bytes in use and decodes on the copy stream (csrc/jpeg_dec.hip,
+libjpeg's arithmetic restated), and `status(slot)` tells per stream whether its frame is good (deepdish_amd.jpeg.ST_*)."""
 import ctypes
 import numpy as np
 
 from ._lib import lib, check, P
 from .runtime import default_context, ptr
 
-PIXEL_FORMATS = {'bgr': 0, 'nv12': 1, 'i420': 2}
+PIXEL_FORMATS = {'bgr': 0, 'nv12': 1, 'i420': 2, 'jpeg': 3}
 
 
 class FrameIngest:
-    def __init__(self, n_streams, src_size, dst_size=None, slots=2, flip=False, context=None, pixel_format='bgr'):
+    def __init__(self, n_streams, src_size, dst_size=None, slots=2, flip=False, context=None, pixel_format='bgr', jpeg_slot_bytes=None):
         """src_size / dst_size: (width, height) like the reference's `input_size`; dst defaults to src.
-        pixel_format: what a slot holds, 'bgr' | 'nv12' | 'i420' (YUV needs an even width and height); the consumer always gets BGR."""
+        pixel_format: what a slot holds, 'bgr' | 'nv12' | 'i420' (YUV needs an even width and height) | 'jpeg'; the consumer always gets
+        BGR.  jpeg_slot_bytes: the size of a JPEG slot's arena, by default n_streams * width * height * 3 // 8."""
         self._h = None
         if pixel_format not in PIXEL_FORMATS:
-            raise ValueError("pixel_format %r is none of 'bgr', 'nv12', 'i420'" % (pixel_format,))
+            raise ValueError("pixel_format %r is none of 'bgr', 'nv12', 'i420', 'jpeg'" % (pixel_format,))
         self.pixel_format = pixel_format
         self.sw, self.sh = src_size
         self.dw, self.dh = dst_size or src_size
-        if pixel_format != 'bgr' and (self.sw % 2 or self.sh % 2):
+        if pixel_format in ('nv12', 'i420') and (self.sw % 2 or self.sh % 2):
             raise ValueError('%s frames need an even width and height, got %dx%d' % (pixel_format, self.sw, self.sh))
         self.ctx = context or default_context()
         self.S, self.slots = int(n_streams), int(slots)
@@ -35,12 +41,16 @@ class FrameIngest:
         if pixel_format == 'bgr':
             check(lib().dd_ingest_create(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
                                          ctypes.byref(h)), 'dd_ingest_create')
+        elif pixel_format == 'jpeg':
+            self.jpeg_slot_bytes = int(jpeg_slot_bytes) if jpeg_slot_bytes else self.S * self.sw * self.sh * 3 // 8
+            check(lib().dd_ingest_create_jpeg(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
+                                              self.jpeg_slot_bytes, ctypes.byref(h)), 'dd_ingest_create_jpeg')
         else:
             check(lib().dd_ingest_create_format(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
                                                 PIXEL_FORMATS[pixel_format], ctypes.byref(h)), 'dd_ingest_create_format')
         self._h = h
         self._host = []
-        for i in range(self.slots):
+        for i in range(self.slots if pixel_format != 'jpeg' else 0):
             p, n = ctypes.c_void_p(), ctypes.c_int64()
             check(lib().dd_ingest_host_slot(self._h, i, ctypes.byref(p), ctypes.byref(n)), 'dd_ingest_host_slot')
             buf = (ctypes.c_uint8 * n.value).from_address(p.value)
@@ -59,8 +69,25 @@ class FrameIngest:
     def host(self, slot):
         """Pinned numpy view of a slot, [S, src_h, src_w, 3] for BGR and [S, src_h * 3 // 2, src_w] for NV12 / I420 (the shape cv2 gives
         such frames): fill it, then submit(slot).  Blocks until the slot's previous upload has left the host buffer."""
+        if self.pixel_format == 'jpeg':
+            raise ValueError("a 'jpeg' ring has no raw slot to fill: hand each stream's file to put(slot, stream, data)")
         check(lib().dd_ingest_wait_uploaded(self._h, slot), 'dd_ingest_wait_uploaded')
         return self._host[slot]
+
+    def put(self, slot, stream, data):
+        """'jpeg' rings: stream `stream`'s next frame as a baseline JPEG file (bytes).  Blocks until the slot's previous upload has left
+        it, copies the file into the slot's arena and parses its header here, on the calling thread (several threads may put into one
+        slot at once).  A full arena raises (DD_E_CAPACITY, -4).  A file that is refused or of another size is accepted here and shows
+        in status(slot)."""
+        data = bytes(data)
+        check(lib().dd_ingest_jpeg_put(self._h, int(slot), int(stream), data, len(data)), 'dd_ingest_jpeg_put')
+
+    def status(self, slot):
+        """'jpeg' rings: int32 [S], deepdish_amd.jpeg.ST_* per stream of the slot's last submit (waits for it).  A stream with a
+        non-zero status has unspecified pixels in its own frame and costs the others nothing."""
+        out = np.empty(self.S, np.int32)
+        check(lib().dd_ingest_status(self._h, int(slot), out.ctypes.data_as(P)), 'dd_ingest_status')
+        return out
 
     def submit(self, slot):
         check(lib().dd_ingest_submit(self._h, slot), 'dd_ingest_submit')

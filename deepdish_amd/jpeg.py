@@ -10,7 +10,11 @@ frame_%06d.jpg under --output-cvat-dir (:764-766) and to the file --stream-path 
 The bytes are libjpeg's for 8-bit YCbCr 4:2:0 with the ITU-T T.81 Annex K tables: Pillow's
 Image.save(f, 'JPEG', quality=q, subsampling='4:2:0', restart_marker_rows=r) byte for byte, header included (tests/test_jpeg_ref.py,
 tests/test_gpu_jpeg.py).  The one deviation from cv2.imencode is the DRI segment and the RSTn markers, which cv2 does not write and every
-decoder honours: a restart interval is the unit of parallel work.  Parity with OpenCV's own bytes is not pinned."""
+decoder honours: a restart interval is the unit of parallel work.  Parity with OpenCV's own bytes is not pinned.
+
+The way in is the mirror (csrc/jpeg_parse.h, csrc/jpeg_dec.hip): `parse(file)` reads a baseline file's header on the host, and
+`JpegDecoder(H, W).decode(files)` turns files in host memory into BGR frames in HBM, byte for byte libjpeg's pixels (tests/jpeg_dec_ref.py,
+tests/test_gpu_jpeg_decode.py); the ingest ring's `pixel_format='jpeg'` slots (deepdish_amd/ingest.py) are built on it."""
 import ctypes
 
 import numpy as np
@@ -110,3 +114,121 @@ class JpegEncoder:
         flat = torch.cat(pieces).cpu().numpy().tobytes()
         ends = np.cumsum(lens)
         return [flat[int(e - l):int(e)] for e, l in zip(ends, lens)]
+
+
+# ------------------------------------------------------------------------------------------------ decoder (csrc/jpeg_dec.hip)
+DEC_PATH_LDS, DEC_PATH_PLANES = 0, 1
+E_FORMAT = -5
+ST_OK, ST_HEADER, ST_SIZE, ST_DATA, ST_NO_FRAME = 0, 1, 2, 3, 4
+REASONS = {0: 'ok', 1: 'truncated', 2: 'progressive', 3: 'arithmetic', 4: 'lossless', 5: 'precision', 6: 'components', 7: 'sampling',
+           8: 'scans', 9: 'huffman', 10: 'undefined', 11: 'size', 12: 'segment'}
+
+
+class _Huff(ctypes.Structure):
+    _fields_ = [('bits', ctypes.c_uint8 * 16), ('vals', ctypes.c_uint8 * 256), ('look', ctypes.c_uint16 * 256), ('maxcode', ctypes.c_int32 * 18),
+                ('valoff', ctypes.c_int32 * 18), ('nvals', ctypes.c_int32), ('defined', ctypes.c_int32)]
+
+
+class JpegInfo(ctypes.Structure):
+    """dd_jpeg_info of include/deepdish_hip.h."""
+    _fields_ = ([('reason', ctypes.c_int32), ('height', ctypes.c_int32), ('width', ctypes.c_int32), ('ncomp', ctypes.c_int32), ('sof', ctypes.c_int32)]
+                + [(k, ctypes.c_int32 * 3) for k in ('hs', 'vs', 'tq', 'td', 'ta')]
+                + [(k, ctypes.c_int32) for k in ('hmax', 'vmax', 'mcus_x', 'mcus_y', 'blocks_per_mcu', 'restart_interval', 'n_intervals', 'scan_offset',
+                                                 'scan_length')]
+                + [('quant_defined', ctypes.c_int32 * 4)]
+                + [(k, ctypes.c_int32) for k in ('status', 'path', 'interval_base', 'reserved')]
+                + [('file_offset', ctypes.c_int64), ('quant', (ctypes.c_uint16 * 64) * 4), ('huff', _Huff * 4)])
+
+
+def parse(file):
+    """The header of a baseline JPEG file, SOI .. the first SOS, as dd_jpeg_parse reads it -> dict.  Needs no device.  A file that is
+    refused raises DeepDishHipError with .reason (a word of REASONS) and the reason spelt out in the message."""
+    data = bytes(file)
+    info = JpegInfo()
+    rc = lib().dd_jpeg_parse(data, len(data), ctypes.byref(info))
+    if rc != 0:
+        msg = lib().dd_last_error()
+        err = DeepDishHipError('dd_jpeg_parse failed (%d): %s' % (rc, msg.decode() if msg else '?'))
+        err.code, err.reason = rc, REASONS.get(info.reason, '?') if rc == E_FORMAT else None
+        raise err
+    nc = info.ncomp
+    out = {k: getattr(info, k) for k in ('height', 'width', 'ncomp', 'sof', 'hmax', 'vmax', 'mcus_x', 'mcus_y', 'blocks_per_mcu', 'restart_interval',
+                                          'n_intervals', 'scan_offset', 'scan_length')}
+    out['comps'] = [(info.hs[c], info.vs[c], info.tq[c]) for c in range(nc)]
+    out['td'], out['ta'] = list(info.td[:nc]), list(info.ta[:nc])
+    out['quant'] = {t: np.array(info.quant[t][:], np.int64) for t in range(4) if info.quant_defined[t]}
+    out['huff'] = {(t >> 1, t & 1): (list(info.huff[t].bits), list(info.huff[t].vals[:info.huff[t].nvals])) for t in range(4) if info.huff[t].defined}
+    return out
+
+
+def decoder_plan(H, W, ncomp=3, hs=2, vs=2):
+    """-> (path, rows of a band, bands): DEC_PATH_LDS keeps a band's sample planes in LDS, DEC_PATH_PLANES takes them through HBM.
+    Needs no device."""
+    path, rows, bands = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
+    check(lib().dd_jpegdec_plan(int(H), int(W), int(ncomp), int(hs), int(vs), ctypes.byref(path), ctypes.byref(rows), ctypes.byref(bands)), 'dd_jpegdec_plan')
+    return path.value, rows.value, bands.value
+
+
+class JpegDecoder:
+    """Baseline JPEG files of one frame size, H x W, in host memory -> BGR frames in HBM, byte for byte libjpeg's (Pillow's
+    Image.open(f).convert('RGB') with the channels swapped; parity with OpenCV's decode is not pinned).  Files of one call may differ
+    in sampling (4:2:0, 4:2:2, 4:4:4, greyscale), tables and restart interval.
+
+        dec = JpegDecoder(480, 640, max_frames=64)
+        frames, status = dec.decode(files)           # u8 [n, 480, 640, 3] and int32 [n] on the device
+
+    status: ST_OK; ST_HEADER (refused: parse(file) says why) and ST_SIZE (not H x W) leave the frame untouched; ST_DATA (corrupt or
+    truncated entropy data) leaves unspecified bytes in that frame alone; ST_NO_FRAME for an empty file."""
+
+    def __init__(self, H, W, max_frames=16, max_bytes=None, context=None):
+        from .runtime import default_context
+        self.ctx = context or default_context()
+        self.H, self.W, self.max_frames = int(H), int(W), int(max_frames)
+        self.max_bytes = int(max_bytes) if max_bytes else self.max_frames * (self.H * self.W * 3 + 4096)
+        self._h = None
+        h = P()
+        check(lib().dd_jpegdec_create(self.ctx.handle, self.H, self.W, self.max_frames, self.max_bytes, ctypes.byref(h)), 'dd_jpegdec_create')
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().dd_jpegdec_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def profile(self, on=True):
+        """Record device events around the parts of every decode; read them with kernel_ms()."""
+        check(lib().dd_jpegdec_profile(self._h, int(bool(on))), 'dd_jpegdec_profile')
+
+    def kernel_ms(self):
+        """-> {'upload', 'markers', 'entropy', 'pixels'}: milliseconds of the last profiled decode (waits for it)."""
+        ms = (ctypes.c_float * 4)()
+        check(lib().dd_jpegdec_profile_read(self._h, ms), 'dd_jpegdec_profile_read')
+        return dict(zip(('upload', 'markers', 'entropy', 'pixels'), (float(v) for v in ms)))
+
+    def decode(self, files, out=None, status=None, stream=None):
+        """files: a list of bytes objects.  out / status: tensors to write instead of new ones.  Queued on the context's stream (or
+        `stream`): `context.sync()` before torch reads the result on another stream."""
+        import torch
+        n = len(files)
+        lens = np.array([len(f) for f in files], np.int64)
+        offs = np.zeros(n, np.int64)
+        if n > 1:
+            offs[1:] = np.cumsum((lens[:-1] + 63) & ~63)
+        blob = bytearray(int(offs[-1] + lens[-1]) if n else 0)
+        for f, o in zip(files, offs):
+            blob[int(o):int(o) + len(f)] = f
+        buf = (ctypes.c_uint8 * max(1, len(blob))).from_buffer(blob)
+        dev = torch.device('cuda', self.ctx.device)
+        if out is None:
+            out = torch.empty((n, self.H, self.W, 3), dtype=torch.uint8, device=dev)
+        if status is None:
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+        assert tuple(out.shape) == (n, self.H, self.W, 3) and out.dtype == torch.uint8 and out.is_contiguous()
+        assert tuple(status.shape) == (n,) and status.dtype == torch.int32
+        torch.cuda.current_stream(out.device).synchronize()
+        check(lib().dd_jpegdec_decode(self._h, buf, offs.ctypes.data_as(P), lens.ctypes.data_as(P), n, P(out.data_ptr()), P(status.data_ptr()), stream),
+              'dd_jpegdec_decode')
+        return out, status

@@ -289,6 +289,7 @@ int dd_yuv420_to_bgr(dd_ctx *ctx, const uint8_t *src, int batch, int H, int W, i
  * wait for that slot (no host wait) and returns the device frames [n_streams][dst_h][dst_w][3];
  * dd_ingest_release marks the consumer's last use so the slot can be refilled. */
 typedef struct dd_ingest dd_ingest;
+typedef struct dd_jpegdec dd_jpegdec;
 int dd_ingest_create(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip,
                      dd_ingest **out);
 /* The same ring for slots that hold what a decoder produces: pixel_format 0 = BGR (exactly dd_ingest_create), 1 = NV12, 2 = I420 (layouts
@@ -299,6 +300,19 @@ int dd_ingest_create(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w
  * [n_streams][dst_h][dst_w][3]; submit / acquire / release are unchanged. */
 int dd_ingest_create_format(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip,
                             int pixel_format, dd_ingest **out);
+/* The same ring for slots that hold baseline JPEG files (see the JPEG decoder below): a slot is one pinned arena of slot_bytes, into which
+ * dd_ingest_jpeg_put copies stream `stream`'s file at the next 64-byte-aligned offset (after waiting for the slot's previous upload, as
+ * dd_ingest_wait_uploaded does) and parses its header on the calling thread; it may be called from several threads at once.  A full arena
+ * is DD_E_CAPACITY.  dd_ingest_submit uploads the bytes in use and the records in one copy each and decodes on the copy stream, straight
+ * into the slot's output when neither flip nor resize is asked, otherwise into one staging buffer followed by the ring's crop_resize
+ * launch.  dd_ingest_status gives the slot's int32 [n_streams] DD_JPEG_ST_* once the slot's work has run (it waits for it): a stream
+ * with a non-zero status costs the others nothing, and one for which nothing was put since the last submit reports DD_JPEG_ST_NO_FRAME.
+ * dd_ingest_host_slot on such a ring is DD_E_STATE.  The consumer always receives BGR [n_streams][dst_h][dst_w][3].  Every put into a slot
+ * must have returned before that slot's submit; a second put for a stream replaces the first (its bytes stay in the arena until the submit). */
+int dd_ingest_create_jpeg(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip, int64_t slot_bytes,
+                          dd_ingest **out);
+int dd_ingest_jpeg_put(dd_ingest *g, int slot, int stream, const uint8_t *data_host, int64_t n);
+int dd_ingest_status(dd_ingest *g, int slot, int *status_host);
 int dd_ingest_destroy(dd_ingest *g);
 int dd_ingest_host_slot(dd_ingest *g, int slot, uint8_t **host_ptr, int64_t *n_bytes);
 int dd_ingest_wait_uploaded(dd_ingest *g, int slot);    /* host may overwrite the pinned slot after this returns */
@@ -631,6 +645,86 @@ int dd_jpeg_plan(int h, int w, int restart_rows, int *path_host);
  * fit writes nothing at all, and the call returns DD_E_CAPACITY after the other frames are done.  Two launches on `stream` (NULL: the
  * context's); the call then waits for them, because the lengths decide its return value. */
 int dd_jpeg_encode(dd_jpeg *enc, const uint8_t *frames_dev, int n, uint8_t *out_dev, int64_t cap, int *lengths_dev, void *stream);
+
+/* ---------------------------------------------------------------- JPEG decoder (csrc/jpeg_parse.h, csrc/jpeg_dec.hip)
+ * The entry of the ingest path for what a camera host usually holds: the frame_%06d.jpg files the reference reads under --input-cvat-dir
+ * (deepdish.py:685-689, cv2.VideoCapture at :727) or an MJPEG stream.  Baseline files are decoded in HBM to BGR, libjpeg's arithmetic
+ * restated (Annex F Huffman decoding, jidctint.c's accurate-integer IDCT, fancy up-sampling, jdcolor.c's YCbCr -> RGB): Pillow's
+ * Image.open(f).convert('RGB') with the channels swapped, byte for byte (tests/jpeg_dec_ref.py).  Parity with OpenCV's own decode is
+ * not pinned.
+ * Accepted: SOF0, and SOF1 at 8 bits; 1 component, or 3 with luma sampled 1x1, 2x1 or 2x2 over 1x1 chroma; one interleaved scan; DC / AC
+ * tables 0 and 1; any DRI.  Everything else is refused by name (DD_JPEG_R_*). */
+#define DD_E_FORMAT     -5   /* input data (a file) is malformed or of a kind that is refused; the message names the reason */
+/* why dd_jpeg_parse refused a file (dd_jpeg_info.reason) */
+#define DD_JPEG_R_OK           0
+#define DD_JPEG_R_TRUNCATED    1   /* no SOI, a segment length past the file, no SOS before the end */
+#define DD_JPEG_R_PROGRESSIVE  2   /* SOF2 / SOF6, or a scan with Ss, Se, Ah, Al other than 0, 63, 0, 0 */
+#define DD_JPEG_R_ARITHMETIC   3   /* SOF9 and above */
+#define DD_JPEG_R_LOSSLESS     4   /* SOF3 / SOF7, and hierarchical SOF5 */
+#define DD_JPEG_R_PRECISION    5   /* sample precision other than 8 bits, or a 16-bit quant table */
+#define DD_JPEG_R_COMPONENTS   6   /* neither 1 nor 3 components; an Adobe transform other than YCbCr on 3 */
+#define DD_JPEG_R_SAMPLING     7   /* 4:4:0, 4:1:1, sub-sampled luma ... */
+#define DD_JPEG_R_SCANS        8   /* a scan that does not hold every component in order */
+#define DD_JPEG_R_HUFFMAN      9   /* a DHT that over-subscribes the code space, names more than 256 symbols or a table id above 1 */
+#define DD_JPEG_R_UNDEFINED   10   /* a component references a table the file does not define */
+#define DD_JPEG_R_SIZE        11   /* height or width of 0 or above 8192 */
+#define DD_JPEG_R_SEGMENT     12   /* a segment whose content contradicts its length */
+/* per-frame status of a decode (int32) */
+#define DD_JPEG_ST_OK          0
+#define DD_JPEG_ST_HEADER      1   /* the header was refused (dd_jpeg_parse says why); nothing is written for the frame */
+#define DD_JPEG_ST_SIZE        2   /* the SOF size is not the decoder's H x W; nothing is written */
+#define DD_JPEG_ST_DATA        3   /* corrupt or truncated entropy-coded data: the frame holds unspecified bytes, inside its own H x W x 3 */
+#define DD_JPEG_ST_NO_FRAME    4   /* ingest ring: no file was put for this stream since the last submit; nothing is written */
+/* One Huffman table: Annex C's bits / vals, and what the kernel reads: look[b] = length << 8 | symbol for the code of at most 8 bits that
+ * prefixes byte b (0: none); for longer codes maxcode[l] (-1: no code of length l) and valoff[l] = index of the first symbol of length l
+ * minus its code. */
+typedef struct dd_jpeg_huff {
+    uint8_t bits[16], vals[256];
+    uint16_t look[256];
+    int32_t maxcode[18], valoff[18], nvals, defined;
+} dd_jpeg_huff;
+/* The header of one file, SOI .. the first SOS.  Fixed size, no pointers: the decoder uploads these records as they are. */
+typedef struct dd_jpeg_info {
+    int32_t reason;                              /* DD_JPEG_R_* */
+    int32_t height, width, ncomp, sof;           /* sof: 0xC0 or 0xC1 */
+    int32_t hs[3], vs[3], tq[3], td[3], ta[3];   /* per component: sampling factors, quant table, DC and AC table */
+    int32_t hmax, vmax, mcus_x, mcus_y, blocks_per_mcu;
+    int32_t restart_interval;                    /* MCUs, 0: none */
+    int32_t n_intervals;                         /* ceil(MCUs / interval), 1 without DRI */
+    int32_t scan_offset, scan_length;            /* the entropy-coded bytes: from behind the SOS segment to the end of the file */
+    int32_t quant_defined[4];
+    /* filled by the decoder for its kernels; 0 from dd_jpeg_parse */
+    int32_t status, path, interval_base, reserved;
+    int64_t file_offset;
+    uint16_t quant[4][64];                       /* natural order */
+    dd_jpeg_huff huff[4];                        /* DC 0, DC 1, AC 0, AC 1 */
+} dd_jpeg_info;
+/* Host only, no device: parse `n` bytes of a file into *info.  DD_E_FORMAT with info->reason and a dd_last_error() text that names the
+ * reason when the file is refused.  The work is bounded by the header; the entropy-coded bytes are not walked.  Every read is checked
+ * against n. */
+int dd_jpeg_parse(const uint8_t *file_host, int64_t n, dd_jpeg_info *info);
+
+#define DD_JPEGDEC_LDS     0   /* jpeg_pixels_k keeps a band (one MCU row) of sample planes in LDS */
+#define DD_JPEGDEC_PLANES  1   /* a band too wide for that: jpeg_planes_k writes the sample planes to HBM first */
+/* Which path a frame of h x w with `ncomp` components and luma sampling hs x vs takes, how many pixel rows a band of jpeg_pixels_k holds
+ * and how many bands the frame has.  Needs no device. */
+int dd_jpegdec_plan(int h, int w, int ncomp, int hs, int vs, int *path_host, int *band_rows_host, int *bands_host);
+/* A decoder for up to max_frames files of h x w per call, max_bytes of file data in all (sides 1 .. 8192).  It owns the coefficient
+ * buffer (int16, the largest accepted sampling's blocks per frame) and the staging for records and bytes. */
+int dd_jpegdec_create(dd_ctx *ctx, int h, int w, int max_frames, int64_t max_bytes, dd_jpegdec **out);
+int dd_jpegdec_destroy(dd_jpegdec *dec);
+/* File i is files_host[offsets[i] .. offsets[i] + lengths[i]) (a length of 0: DD_JPEG_ST_NO_FRAME).  Parses each header, uploads the
+ * records and the bytes in one copy each, then launches jpeg_markers_k, jpeg_entropy_k and jpeg_pixels_k (jpeg_planes_k in front of the
+ * last when a frame takes DD_JPEGDEC_PLANES) on `stream` (NULL: the context's).  out_dev u8 [n][h][w][3] BGR, status_dev int32 [n]
+ * (DD_JPEG_ST_*), both valid once the stream has run.  Files may differ in tables, sampling and restart interval.  A frame with a
+ * non-zero status costs its neighbours nothing.  The call returns once the uploads have left the host buffers. */
+int dd_jpegdec_decode(dd_jpegdec *dec, const uint8_t *files_host, const int64_t *offsets, const int64_t *lengths, int n, uint8_t *out_dev,
+                      int *status_dev, void *stream);
+/* Device-event times of a decode's parts (scripts/time_ingest_jpeg.py): after dd_jpegdec_profile(dec, 1) every decode records events, and
+ * dd_jpegdec_profile_read waits for the last decode and gives ms_host[4] = the two uploads, jpeg_markers_k, clearing the coefficients +
+ * jpeg_entropy_k, jpeg_planes_k + jpeg_pixels_k.  DD_E_STATE without a profiled decode. */
+int dd_jpegdec_profile(dd_jpegdec *dec, int on);
+int dd_jpegdec_profile_read(dd_jpegdec *dec, float *ms_host);
 
 /* ---------------------------------------------------------------- multi-GPU
  * Sum of the per-stream count vectors (pos, neg, int, del per label; deepdish.py:1141-1145).
