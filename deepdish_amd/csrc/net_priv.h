@@ -35,6 +35,7 @@ struct dd_net {
     int tile_mode = 0;                       // DD_TILE_MODE=1 forces the 64 x 64 tile everywhere (A/B measurements)
     std::vector<hipEvent_t> events;           // n_ops + 1 when profiling
     std::vector<int32_t> op_launch;           // per op of the last forward: DD_OPK_* (which launch ran it)
+    std::vector<int32_t> op_variant;          // per op of the last forward: tile / fill mode / K split of the generic conv launcher, 0 = another kernel
     // Latency mode (dd_net_use_graph): the launch train of one forward -- 20 to 75 short kernels at batch 1 -- captured
     // once per (input pointer, batch) and replayed as one hipGraph launch; the first call of a key runs eagerly (it may
     // still allocate split-K slabs and set function attributes), the second captures.

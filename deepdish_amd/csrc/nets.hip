@@ -3822,11 +3822,16 @@ int conv_splitk(int ho, int wo, int cout_pad, int ksteps, int max_batch) {
     return splitk;
 }
 
+// dd_net_op_variants: what the generic launcher used for an op, packed (include/deepdish_hip.h)
+inline int32_t conv_variant_code(int wm, int wn, int mi, int ni, int bk, int mode, int splitk) {
+    return wm | wn << 4 | mi << 8 | ni << 12 | (bk >> 4) << 16 | mode << 20 | splitk << 24;
+}
+
 // Few blocks and a long K axis: split K over blockIdx.z so the chip is busy and each block's serial
 // chain of (load -> barrier -> MFMA) steps is short; partial sums go through an f32 slab.
 // GLDS selects the direct-to-LDS kernel (needs padded Cin % 64 == 0 and BK == 64).
 template <int WM, int WN, int MI, int NI, int BK, bool GLDS>
-int launch_conv(hipStream_t s, ConvP &P, DevBuf &slab, int max_batch, int device, bool *slab_moved = nullptr) {
+int launch_conv(hipStream_t s, ConvP &P, DevBuf &slab, int max_batch, int device, bool *slab_moved = nullptr, int32_t *variant = nullptr) {
     constexpr int BM = WM * MI * 16, BN = WN * NI * 16;
     const int gx = dd_ceil_div(P.m, BM), gy = dd_ceil_div(P.cout_pad, BN);
     const int ksteps = P.kpad / BK;
@@ -3878,8 +3883,11 @@ int launch_conv(hipStream_t s, ConvP &P, DevBuf &slab, int max_batch, int device
         if (pw) hipLaunchKernelGGL((conv_glds_k<WM, WN, MI, NI, 1>), dim3(gx, gy, splitk), dim3(WM * WN * 64), lds_bytes, s, P);
         else if (tapu) hipLaunchKernelGGL((conv_glds_k<WM, WN, MI, NI, 2>), dim3(gx, gy, splitk), dim3(WM * WN * 64), lds_bytes, s, P);
         else hipLaunchKernelGGL((conv_glds_k<WM, WN, MI, NI, 0>), dim3(gx, gy, splitk), dim3(WM * WN * 64), lds_bytes, s, P);
-    } else
+        if (variant) *variant = conv_variant_code(WM, WN, MI, NI, BK, pw ? 1 : tapu ? 2 : 0, splitk);
+    } else {
         hipLaunchKernelGGL((conv_mfma_k<WM, WN, MI, NI, BK>), dim3(gx, gy, splitk), dim3(WM * WN * 64), lds_bytes, s, P);
+        if (variant) *variant = conv_variant_code(WM, WN, MI, NI, BK, 3, splitk);
+    }
     DD_LAUNCH_CHECK();
     if (splitk > 1) {
         const long long total = (long long)P.m * (P.cout_pad >> 2);
@@ -3968,7 +3976,7 @@ int launch_stem_wide(hipStream_t s, ConvP &P, int nimg, int device) {
 int launch_conv3x3_rw(hipStream_t s, ConvP &P, int nimg, bool pool, int device) {
     if (pool) {                                                  // 8 pooled rows per tile = 17 conv rows, full width
         P.tw = P.wo; P.th = 17; P.tiles_x = 1; P.tiles_y = dd_ceil_div(P.p[0], 8);
-        DD_REQUIRE(P.wo == 32 && P.act == ACT_ELU && !P.res && !P.out2, DD_E_ARG, "conv3x3_rw: fused pooling needs a 32-wide ELU layer");
+        DD_REQUIRE(!P.res && !P.out2 && P.ho >= 3 && P.wo >= 3, DD_E_ARG, "conv3x3_rw: fused pooling takes no residual and no second output");
         // one wave per image, rows streamed (conv3x3_pool_rows_k); DD_POOL_TILED=1 keeps the tiled kernel (same bits)
         // (measured at 3840 / 1024 / 256 / 64 images: rows 136 / 41 / 17 / 9.3 us, tiled 251 / 75 / 23 / 9.0 us; below
         // ~160 images the tiled kernel's 16 waves per image win, profiles/r02_pool_rows_sweep.txt)
@@ -4005,16 +4013,24 @@ int launch_conv3x3_rw(hipStream_t s, ConvP &P, int nimg, bool pool, int device) 
     const int total = nimg * P.tiles_x * P.tiles_y;
     const int grid = std::min(total, 2 * 256);                   // persistent: 2 blocks per CU (register-bound), multiple of 8
     if (pool) {
+        // the largest tile either form takes: 17 rows of the widest map whose patch fits (19 x 37 patch pixels)
+        constexpr int pool_lds_max = 4 * ((RW_MAX_PATCH * 16 + 255) & ~255) + 17 * 35 * 32 * (int)sizeof(_Float16);
+        DD_REQUIRE(lds_bytes <= (size_t)pool_lds_max, DD_E_ARG, "conv3x3_rw: pooled tile of %d columns", P.tw);
         static DevOnce once;
         const int rc = once.run(device, [&]() -> int {
             DD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_rw_k<2, 32, ACT_ELU, true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, pool_lds_max));
+            DD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv3x3_rw_k<2, 0, -1, true>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, pool_lds_max));
             return DD_OK;
         });
         if (rc != DD_OK) return rc;
     }
     if (pool) {
-        hipLaunchKernelGGL((conv3x3_rw_k<2, 32, ACT_ELU, true>), dim3((unsigned)grid), dim3(256), lds_bytes, s, P, total);
+        // 32 columns and ELU (the MARS front): tile width and activation known at compile time; any other width whose patch fits, any activation:
+        // the same kernel with both read from P
+        if (P.tw == 32 && P.act == ACT_ELU) hipLaunchKernelGGL((conv3x3_rw_k<2, 32, ACT_ELU, true>), dim3((unsigned)grid), dim3(256), lds_bytes, s, P, total);
+        else hipLaunchKernelGGL((conv3x3_rw_k<2, 0, -1, true>), dim3((unsigned)grid), dim3(256), lds_bytes, s, P, total);
         DD_LAUNCH_CHECK();
         return DD_OK;
     }
@@ -4732,6 +4748,14 @@ int dd_net_op_launches(dd_net *n, int32_t *codes_host, int cap, int *n_ops_host)
     return DD_OK;
 }
 
+int dd_net_op_variants(dd_net *n, int32_t *codes_host, int cap, int *n_ops_host) {
+    DD_REQUIRE(n && codes_host && n_ops_host, DD_E_ARG, "dd_net_op_variants: NULL argument");
+    DD_REQUIRE(cap >= n->n_ops, DD_E_ARG, "dd_net_op_variants: cap %d < %d ops", cap, n->n_ops);
+    for (int i = 0; i < n->n_ops; ++i) codes_host[i] = i < (int)n->op_variant.size() ? n->op_variant[i] : 0;
+    *n_ops_host = n->n_ops;
+    return DD_OK;
+}
+
 int dd_net_read(dd_net *n, int tensor, int n_img, void *dst, int dst_on_device, void *stream) {
     DD_REQUIRE(n && dst && n_img >= 0 && n_img <= n->max_batch, DD_E_ARG, "dd_net_read: bad argument");
     DD_DEVICE(n->ctx);
@@ -4954,6 +4978,7 @@ static int net_run_ops(dd_net *net, const uint8_t *input, int nimg, hipStream_t 
         return static_cast<char *>(net->bufs[d.buf]);
     };
     net->op_launch.assign((size_t)net->n_ops, OPK_DEFAULT);
+    net->op_variant.assign((size_t)net->n_ops, 0);
     ConvP stem_p;                                                 // a first layer waiting to be folded into the next op's launch
     bool stem_pending = false;
     bool wide_pending = false, wide_ready = false;               // ... into the launch of the NEXT TWO ops (3x3 layer, then max pool: stem_conv_pool_wide_k, launched at the pool op)
@@ -5255,10 +5280,10 @@ static int net_run_ops(dd_net *net, const uint8_t *input, int nimg, hipStream_t 
                     rc = P.cin == 256 ? launch_conv_ws<4>(s, P, net->ctx->device) : launch_conv_ws<8>(s, P, net->ctx->device);
                 } else if (P.cout_pad <= 32) {
                     // 32 output channels: 128 pixels per block (each wave 32 px x 32 ch) once there are enough pixels
-                    rc = bk32 ? launch_conv<4, 1, 1, 2, 32, false>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved)
-                       : (glds && P.m >= 16384) ? launch_conv<4, 1, 2, 2, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved)
-                       : glds ? launch_conv<4, 1, 1, 2, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved)
-                              : launch_conv<4, 1, 1, 2, 64, false>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved);
+                    rc = bk32 ? launch_conv<4, 1, 1, 2, 32, false>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i])
+                       : (glds && P.m >= 16384) ? launch_conv<4, 1, 2, 2, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i])
+                       : glds ? launch_conv<4, 1, 1, 2, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i])
+                              : launch_conv<4, 1, 1, 2, 64, false>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i]);
                 } else if (glds && net->tile_mode != 1 && P.m >= 16384 && P.cout_pad >= 128) {
                     // plenty of pixels: 128 x 128 with 8 waves -- a third less L2->LDS traffic per FLOP than 64 x 128
                     // (24.3 us vs 26.6 us for 19x19x512 -> 512 at 64 frames; at 10x10 it halves the block count and loses).
@@ -5269,19 +5294,19 @@ static int net_run_ops(dd_net *net, const uint8_t *input, int nimg, hipStream_t 
                     const int c128 = dd_ceil_div(dd_ceil_div(P.m, 128) * gy128, 512) * 128;
                     const int c192 = dd_ceil_div(dd_ceil_div(P.m, 192) * gy128, 512) * 192;
                     if (P.epi == EPI_F16 && c192 <= c128 && net->tile_mode != 2)
-                        rc = launch_conv<4, 2, 3, 4, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved);
+                        rc = launch_conv<4, 2, 3, 4, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i]);
                     else
-                        rc = launch_conv<4, 2, 2, 4, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved);
+                        rc = launch_conv<4, 2, 2, 4, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i]);
                 } else if (glds && net->tile_mode != 1 && P.m >= 16384 && P.cout_pad == 64) {
-                    rc = launch_conv<4, 2, 2, 2, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved);      // 128 x 64, 8 waves
+                    rc = launch_conv<4, 2, 2, 2, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i]);      // 128 x 64, 8 waves
                 } else if (glds && net->tile_mode != 1 && P.m >= 4096 && P.cout_pad >= 128) {
                     // 64 pixels x 128 channels: each staged pixel row feeds twice the MFMAs; measured 31 us vs 38 us
                     // for 19x19x512 -> 512 at 64 frames (128 x 64 gave nothing, 128 x 128 was 2.5x slower: 2 blocks/CU)
-                    rc = launch_conv<2, 2, 2, 4, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved);
+                    rc = launch_conv<2, 2, 2, 4, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i]);
                 } else {
-                    rc = bk32 ? launch_conv<2, 2, 2, 2, 32, false>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved)
-                       : glds ? launch_conv<2, 2, 2, 2, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved)
-                              : launch_conv<2, 2, 2, 2, 64, false>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved);
+                    rc = bk32 ? launch_conv<2, 2, 2, 2, 32, false>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i])
+                       : glds ? launch_conv<2, 2, 2, 2, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i])
+                              : launch_conv<2, 2, 2, 2, 64, false>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i]);
                 }
                 if (rc != DD_OK) return rc;
                 break;

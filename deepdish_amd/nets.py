@@ -142,7 +142,7 @@ class Program:
         wp[:cout, STEM_K_SLOT] = np.transpose(w, (3, 0, 1, 2)).reshape(cout, 27).astype(np.float16)
         bp = np.zeros(32, dtype=np.float32)
         bp[:cout] = bias
-        dst = self.tensor(ho, wo, cout)
+        dst = self.tensor(ho, wo, cout, cs=32)       # the kernel stores all 32 packed channels of a pixel (zeros behind cout)
         self._op(OP_STEM, dst=dst, stride=stride, pad_t=pt, pad_l=pl, cout=cout, cout_pad=32, act=act,
                  w_off=self.add_blob(wp), b_off=self.add_blob(bp), ho=ho, wo=wo, f=[mean, scale])
         self.info[-1] = dict(kernel='stem_conv3_k', flops=2 * ho * wo * 27 * cout,

@@ -42,6 +42,20 @@ def net_op_launches(net):
     return codes
 
 
+CONV_MODES = {0: 'conv_glds_k<general>', 1: 'conv_glds_k<pointwise>', 2: 'conv_glds_k<taps>', 3: 'conv_mfma_k'}
+
+
+def net_op_variants(net):
+    """Per op of the last forward: (WM, WN, MI, NI, BK, mode, splitk) of the generic convolution launcher (mode: CONV_MODES), or None for
+    an op that took any other kernel (dd_net_op_variants, include/deepdish_hip.h)."""
+    n = len(net.program.ops)
+    codes = np.zeros(n, dtype=np.int32)
+    cnt = ctypes.c_int(0)
+    check(lib().dd_net_op_variants(net._h, ptr(codes), n, ctypes.byref(cnt)), 'dd_net_op_variants')
+    return [None if not c else (c & 15, c >> 4 & 15, c >> 8 & 15, c >> 12 & 15, (c >> 16 & 15) * 16, c >> 20 & 15, c >> 24 & 127)
+            for c in (int(v) for v in codes)]
+
+
 def launches_of(net, ms, batch):
     """[(kernel, ms, flops, bytes)] per LAUNCH of the last forward: an op folded into the next op's launch adds its FLOPs
     and the bytes it reads to that launch, and the tensor between the two (never written) is not counted."""

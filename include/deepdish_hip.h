@@ -390,6 +390,11 @@ int dd_net_profile_read(dd_net *net, float *ms_host, int cap, int *n_ops_host);
  * 21 q_conv_k with a residual ADD in its epilogue, 22 q_add_k, 23 stem_conv_pool_wide_k (first layer + 3x3 layer + max pool of a 64- or
  * 128-wide crop, reported on the pool op) -- so that a per-kernel time table attributes a fused launch to the kernel that ran. */
 int dd_net_op_launches(dd_net *net, int32_t *codes_host, int cap, int *n_ops_host);
+/* Which variant of the generic convolution launcher ran each op of the last forward (read-only, beside dd_net_op_launches, which reports 0
+ * for all of them): WM | WN << 4 | MI << 8 | NI << 12 | (BK / 16) << 16 | mode << 20 | splitk << 24 -- the block tile is WM*MI*16 pixels x
+ * WN*NI*16 channels in steps of BK along K; mode 0 / 1 / 2 = conv_glds_k with the general / pointwise / whole-tap fill, 3 = conv_mfma_k;
+ * splitk = slices of the K axis (1 = none; > 1: conv_splitk_finish_k ran behind it).  0 for an op that took any other kernel. */
+int dd_net_op_variants(dd_net *net, int32_t *codes_host, int cap, int *n_ops_host);
 
 /* TFLite_Detection_PostProcess (inside the reference's .tflite graph, tools/ssd_mobilenet.py:103-109):
  * anchor decode, sigmoid, per-class NMS, top max_det.  raw f32 [n_anchors][4+n_classes] ->
