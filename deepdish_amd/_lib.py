@@ -100,6 +100,7 @@ SIGNATURES = {
     'dd_net_profile_read': [P, P, c_int, POINTER(c_int)],
     'dd_net_op_launches': [P, P, c_int, POINTER(c_int)],
     'dd_net_op_variants': [P, P, c_int, POINTER(c_int)],
+    'dd_netq_dwpw_fits': [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int)],
     'dd_ssd_postprocess': [P, P, P, c_int, c_int, c_int, c_float, c_float, P, P, P, P, P],
     'dd_ssd_decode': [P, P, P, c_int, c_int, c_float, P, P, P, P, c_int, P],
     'dd_ssd_postprocess_decoded': [P, P, P, P, P, c_int, c_int, c_float, c_float, P, P, P, P, c_int, P],

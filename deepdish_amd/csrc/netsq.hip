@@ -301,9 +301,12 @@ __global__ __launch_bounds__(256) void q_conv0_k(const QConv0P P, const int n_fr
     if (f0 >= n_frags) return;
     const unsigned zp4 = (unsigned)P.in_zp * 0x01010101u;
     const int hw = P.ho * P.wo;
-    // Range-checked buffer accesses: a window that starts before the batch (column -1 of the first row) or ends past it reads zeros instead of
-    // faulting -- those bytes are replaced by the zero point below anyway -- and a pixel past the last one stores nothing; no clamps, no
-    // 64-bit address arithmetic (the host checked that both tensors stay below 2^31 / 2^32 bytes).
+    // Range-checked buffer accesses: a dword past the end of the batch reads zeros instead of faulting -- bytes the zero point replaces below
+    // anyway -- and a pixel past the last one stores nothing; no 64-bit address arithmetic (the host checked that both tensors stay below
+    // 2^31 / 2^32 bytes).  A window that starts BEFORE the batch is another matter: with pad_l = 1, frame 0's first pixel starts at byte -3,
+    // the compiler merges a lane's three dword loads into one dwordx3, and one that begins before the buffer comes back as zeros in ALL its
+    // dwords -- bytes 0 .. 5 of the batch with it.  Hence the first dword's offset is clamped to 0 below (it holds only bytes of column -1
+    // then, which the zero point replaces: any address does) and the other two stay a load of their own.
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(P.src), 0, (int)P.total_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rdst = __builtin_amdgcn_make_buffer_rsrc(P.out, 0, (int)P.out_bytes, 0x00020000);
     unsigned w[C0F][3]; int o_[C0F]; bool rowok[C0F]; int px[C0F]; unsigned so[C0F];
@@ -322,8 +325,9 @@ __global__ __launch_bounds__(256) void q_conv0_k(const QConv0P P, const int n_fr
         const int a = ((qn * P.H + row) * P.W + col) * 3;      // (< 0 or past the end only for rows / pixels whose bytes are not used)
         const int a4 = a & ~3;
         o_[j] = a - a4;
+        w[j][0] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, max(a4, 0), 0, 0);      // (see above: never a load that begins before the buffer)
 #pragma unroll
-        for (int i = 0; i < 3; ++i) w[j][i] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, a4 + 4 * i, 0, 0);
+        for (int i = 1; i < 3; ++i) w[j][i] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, a4 + 4 * i, 0, 0);
         // a pixel past the end of the batch: an offset outside the tensor (the store is dropped)
         so[j] = (f0 + j) * 16 + fr < P.m ? (unsigned)((((qn * (P.ho + 2) + qy + 1) * 2 + (fq >> 1)) * PPo) + (qx + 1) * 16 + (fq & 1) * 8) : 0xfffffff0u;
         qx += 16;                                                   // (wo >= 16: at most one row step per fragment)
@@ -1102,6 +1106,9 @@ __global__ __launch_bounds__((COUT / (16 * MW)) * WP * 64, (COUT / (16 * MW)) * 
 
 
 
+// dd_net_op_variants of the uint8 ops (include/deepdish_hip.h): bits 0..3 name the kernel, the rest its template arguments and launch form
+enum { QV_CONV = 1, QV_PWS = 2, QV_DW = 3, QV_DWM = 4, QV_DWPW = 5, QV_CONV0 = 6, QV_ADD = 7, QV_DECODE = 8 };
+
 // Ring rows and prefetch depth of q_dwpw_k for this geometry (tiles of one frame and the step into the next frame).
 void dwpw_plan(int H, int W, int ho, int wo, int stride, int off_y, int cin, int nt, int qt, int *NR, int *lpt) {
     const int hw = ho * wo, tpf = dd_ceil_div(hw, qt), RB = (W + 2) * cin;
@@ -1118,8 +1125,10 @@ void dwpw_plan(int H, int W, int ho, int wo, int stride, int off_y, int cin, int
     *lpt = (int)(((long long)mx * RB + (long long)nt * 16 - 1) / ((long long)nt * 16));
 }
 
+// dry: decide only (*ok; dry_split: for a pointwise filter packed as hi + lo parts), no device call -- the rule below is the one statement of which geometries the fused kernel takes
+// (dd_netq_dwpw_fits asks it for the compiler).  *variant: dd_net_op_variants' word of the launch (QV_* above).
 template <int CIN, int COUT, int WP, int STRIDE, int LPT, int EXTRA = 0, int MW = 4, int QTT = QT>
-int launch_q_dwpw(hipStream_t s, QDwpwP &P, int nimg, int device, bool *ok) {
+int launch_q_dwpw(hipStream_t s, QDwpwP &P, int nimg, int device, bool *ok, bool dry = false, int *variant = nullptr, bool dry_split = false) {
     constexpr int NW = (COUT / (16 * MW)) * WP, NT = NW * 64, CINP = (CIN + 63) / 64 * 64;
     int lpt = 0;
     P.tiles_per_frame = dd_ceil_div(P.hw, QTT);
@@ -1138,14 +1147,16 @@ int launch_q_dwpw(hipStream_t s, QDwpwP &P, int nimg, int device, bool *ok) {
           RB < lim24 && (long long)P.c16_out * (P.wo + 2) * 16 < lim24 && (long long)(nimg + 1) * (P.ho + 2) < lim24 && P.hw < lim24;
     if (!*ok) return DD_OK;
     constexpr bool CAN_HL = CIN <= 128;                                // split pointwise filters are packed for the narrow blocks only
-    const bool hl = P.w2 != nullptr;
+    const bool hl = dry ? dry_split : P.w2 != nullptr;            // (a dry run has no filter: it is told the filter's form)
     if (hl && !CAN_HL) { *ok = false; return DD_OK; }
+    if (dry) return DD_OK;
     const bool rsum = P.zwc != 0 && !hl;
     // both clamps are the byte range: saturating packs (1); both shifts <= 8 as well: the packed 16-bit shift (2)
     const int sat = P.Rd.lo == 0 && P.Rd.hi == 255 && P.Rp.lo == 0 && P.Rp.hi == 255 ? (P.Rd.e <= 8 && P.Rp.e <= 8 ? 2 : 1) : 0;
 #define DD_QK(R_, S_, H_) q_dwpw_k<CIN, COUT, WP, STRIDE, LPT, R_, MW, S_, (H_) && CAN_HL, QTT>
 #define DD_QS(R_, H_) (sat == 2 ? &DD_QK(R_, 2, H_) : sat == 1 ? &DD_QK(R_, 1, H_) : &DD_QK(R_, 0, H_))
     void (*kern)(const QDwpwP, const int, const int) = hl ? DD_QS(false, true) : rsum ? DD_QS(true, false) : DD_QS(false, false);
+    if (variant) *variant = QV_DWPW | (CIN / 32) << 4 | (COUT / 64) << 9 | STRIDE << 13 | (QTT / 64) << 15 | (hl ? 2 : rsum ? 1 : P.dup ? 3 : 0) << 17 | sat << 19;
     static DevOnce once;
     const int rc = once.run(device, [&]() -> int {
         for (const void *f : {reinterpret_cast<const void *>(&DD_QK(false, 0, true)), reinterpret_cast<const void *>(&DD_QK(false, 1, true)), reinterpret_cast<const void *>(&DD_QK(false, 2, true)),
@@ -1187,6 +1198,22 @@ int launch_q_dwpw(hipStream_t s, QDwpwP &P, int nimg, int device, bool *ok) {
         fprintf(stderr, "q_dwpw_k<%d,%d,%d> %d blocks/CU %d tiles/block: cycles per wave and tile: depthwise %.0f  barrier A %.0f  matrix stage %.0f  ring write %.0f  barrier B %.0f\n",
                 CIN, COUT, STRIDE, per_cu, tpb, sum[0] / nw, sum[1] / nw, sum[2] / nw, sum[3] / nw, sum[4] / nw);
     }
+    return DD_OK;
+}
+
+// The fused kernels there are: (cin, cout, stride) -> instantiation.  *ok = false: none, or its launcher does not take the geometry.
+int dwpw_dispatch(hipStream_t s, QDwpwP &Q, int nc, int dev, int cin, int cout, int stride, bool *ok, bool dry, int *variant, bool dry_split = false) {
+    static const int qt128 = getenv("DD_Q_QT128") ? atoi(getenv("DD_Q_QT128")) : 1;   // block 1: 128-pixel tiles, four waves (0: 64-pixel tiles, two waves)
+    *ok = false;
+#define DD_QB(CIN_, COUT_, WP_, S_, LPT_) launch_q_dwpw<CIN_, COUT_, WP_, S_, LPT_>(s, Q, nc, dev, ok, dry, variant, dry_split)
+    if (cin == 32 && cout == 64 && stride == 1) return qt128 ? launch_q_dwpw<32, 64, 4, 1, 6, 0, 4, 128>(s, Q, nc, dev, ok, dry, variant, dry_split) : DD_QB(32, 64, 2, 1, 8);
+    if (cin == 64 && cout == 128 && stride == 2) return DD_QB(64, 128, 2, 2, 8);
+    if (cin == 128 && cout == 128 && stride == 1) return DD_QB(128, 128, 2, 1, 8);
+    if (cin == 128 && cout == 256 && stride == 2) return DD_QB(128, 256, 2, 2, 8);
+    if (cin == 256 && cout == 256 && stride == 1) return DD_QB(256, 256, 2, 1, 6);
+    if (cin == 256 && cout == 512 && stride == 2) return DD_QB(256, 512, 1, 2, 12);
+    if (cin == 512 && cout == 512 && stride == 1) return DD_QB(512, 512, 1, 1, 8);
+#undef DD_QB
     return DD_OK;
 }
 
@@ -1396,7 +1423,7 @@ __global__ __launch_bounds__(512, 2) void q_pws_k(const QPwsP P, const int n_til
 
 // Shapes q_pws_k takes; *ok = false leaves the layer to q_conv_k.
 template <int K, int MW>
-int launch_q_pws(hipStream_t s, QPwsP &P, int nimg, int device, bool *ok) {
+int launch_q_pws(hipStream_t s, QPwsP &P, int nimg, int device, bool *ok, int *variant) {
     const int n_tiles = dd_ceil_div(P.m, QT);
     const int waves = std::min(8, dd_ceil_div(P.n_mfrag, MW));         // per block; the fragments split evenly over the groups
     const int groups = dd_ceil_div(P.n_mfrag, waves * MW);
@@ -1427,6 +1454,7 @@ int launch_q_pws(hipStream_t s, QPwsP &P, int nimg, int device, bool *ok) {
         else kern = rsum ? &DD_PW(QEPI_Q16, true, 0) : &DD_PW(QEPI_Q16, false, 0);
     }
     if (!kern) { *ok = false; return DD_OK; }
+    *variant = QV_PWS | (K / 512) << 4 | MW << 6 | (rows ? QEPI_ROWS : QEPI_Q16) << 9 | (int)rsum << 11 | sat << 12 | (P.n_frag_a ? 1 : 0) << 14;
     static DevOnce once;
     const int rc = once.run(device, [&]() -> int {
         DD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&DD_PW(QEPI_ROWS, true, 0)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -1479,6 +1507,25 @@ __global__ __launch_bounds__(256) void q_add_k(const QAddP P) {
 
 int netq_prepare(dd_net *) { return DD_OK; }
 
+// Host only: whether OP_QDWPW of this shape on an h x w source (TensorFlow SAME padding, one frame) finds a fused kernel whose launcher takes the
+// geometry -- launch_q_dwpw's own rule, so the compiler (netsq.py dwpw_fits) and dd_net_forward cannot disagree.
+int dd_netq_dwpw_fits(int cin, int cout, int stride, int h, int w, int split_filter, int *fits_host) {
+    DD_REQUIRE(fits_host && cin > 0 && cout > 0 && (stride == 1 || stride == 2) && h > 0 && w > 0 && h < (1 << 20) && w < (1 << 20), DD_E_ARG,
+               "dd_netq_dwpw_fits: %d -> %d channels, stride %d, %d x %d", cin, cout, stride, h, w);
+    // (the kernel's 24-bit multiplies take maps below 2^23 pixels: a larger one never fits, and the plan's loop over its tiles is not run)
+    if ((long long)((h + stride - 1) / stride) * ((w + stride - 1) / stride) >= (1ll << 23)) { *fits_host = 0; return DD_OK; }
+    QDwpwP Q;
+    memset(&Q, 0, sizeof(Q));
+    Q.H = h; Q.W = w; Q.ho = (h + stride - 1) / stride; Q.wo = (w + stride - 1) / stride; Q.hw = Q.ho * Q.wo;
+    Q.off_y = 1 - std::max((Q.ho - 1) * stride + 3 - h, 0) / 2; Q.off_x = 1 - std::max((Q.wo - 1) * stride + 3 - w, 0) / 2;
+    Q.c16_out = cout / 16;
+    bool ok = false;
+    const int rc = dwpw_dispatch(nullptr, Q, 1, 0, cin, cout, stride, &ok, true, nullptr, split_filter != 0);
+    if (rc != DD_OK) return rc;
+    *fits_host = ok ? 1 : 0;
+    return DD_OK;
+}
+
 int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int nimg, hipStream_t s, int *handled) {
     const int kind = o[0], src = o[1], dst = o[2];
     *handled = kind >= OP_QCONV0 && kind <= OP_QADD;
@@ -1487,6 +1534,8 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
     const TensorDesc *ts = src >= 0 ? &net->tensors[src] : nullptr;
     const TensorDesc *td = dst >= 0 ? &net->tensors[dst] : nullptr;
     char *W = net->d_weights;
+    int variant_none = 0;
+    int *const variant = i < (int)net->op_variant.size() ? &net->op_variant[i] : &variant_none;      // dd_net_op_variants: the kernel that runs this op (QV_*)
     switch (kind) {
         case OP_QCONV0: {
             QConv0P P;
@@ -1513,6 +1562,7 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
             const int sat0 = P.R.lo == 0 && P.R.hi == 255 ? (P.R.e <= 8 ? 2 : 1) : 0;
             const uint8_t *const src0 = P.src;
             uint8_t *const out0 = P.out;
+            *variant = QV_CONV0 | (P.w2 ? 1 : 0) << 4 | sat0 << 5 | (int)std::min(n_chunks, 255ll) << 8;
             for (long long c0 = 0; c0 < nimg; c0 += chunk) {
                 const int nc = (int)std::min(chunk, nimg - c0);
                 P.src = src0 + c0 * in_img; P.out = out0 + c0 * out_img;
@@ -1592,8 +1642,8 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
                 }
                 bool ok = false;
                 // (the 19x19 class predictor has 18 fragments: six waves of three load the SIMDs 6 / 6 / 3 / 3, five of four 8 / 4 / 4 / 2)
-                const int rc = ts->cs == 512 ? (P.epi == QEPI_ROWS && (P.n_mfrag + 2) / 3 <= 8 && P.n_mfrag % 4 != 0 ? launch_q_pws<512, 3>(s, Q, nimg, net->ctx->device, &ok) : launch_q_pws<512, 4>(s, Q, nimg, net->ctx->device, &ok))
-                                             : launch_q_pws<1024, 2>(s, Q, nimg, net->ctx->device, &ok);
+                const int rc = ts->cs == 512 ? (P.epi == QEPI_ROWS && (P.n_mfrag + 2) / 3 <= 8 && P.n_mfrag % 4 != 0 ? launch_q_pws<512, 3>(s, Q, nimg, net->ctx->device, &ok, variant) : launch_q_pws<512, 4>(s, Q, nimg, net->ctx->device, &ok, variant))
+                                             : launch_q_pws<1024, 2>(s, Q, nimg, net->ctx->device, &ok, variant);
                 if (rc != DD_OK) return rc;
                 if (ok) return DD_OK;
             }
@@ -1617,6 +1667,9 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
                 static const int split_env = getenv("DD_Q_SPLITK") ? atoi(getenv("DD_Q_SPLITK")) : 1;
                 const bool split = split_env && P.kh * P.kw == 9 && n_items < 1024;       // (3x3: the k steps divide by the three filter rows; at 1 200 items the split costs: 40 -> 51 us)
                 const dim3 grid(split ? (unsigned)n_items : (unsigned)((n_items + 3) / 4)), block(split ? 192 : 256);
+                // (two launches of one op -- DD_Q_HEADS_ONE=0 -- report the second one's kernel and count 2 in bits 18..19)
+                *variant = QV_CONV | P.mq << 4 | (int)rsum << 7 | npf << 8 | (int)(npf != 4 && (split || pipe)) << 11 | (split ? 3 : 1) << 12 | (P.epi == QEPI_Q16N ? 1 : 0) << 14 |
+                           (P.n_frag_a ? 1 : 0) << 15 | (P.hw_magic ? 1 : 0) << 16 | (P.res ? 1 : 0) << 17 | (((*variant & 15) == QV_CONV ? (*variant >> 18 & 3) : 0) + 1) << 18;
 #define DD_QC2(MQ_, R_, N_) do { if (npf == 4 && split) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 4, false, 3, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
                                  else if (npf == 4) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 4, false, 1, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
                                  else if (split) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 2, true, 3, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
@@ -1683,8 +1736,10 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
                     Q.dw_a = reinterpret_cast<const uint2 *>(W + (size_t)(uint32_t)o[20]);
                     Q.dw_cb = reinterpret_cast<const int *>(W + (size_t)(uint32_t)o[21]);
                     const long long n_items = items(nc);
+                    *variant = QV_DWM | (P.R.lo == 0 && P.R.hi == 255 ? 1 : 0) << 4 | 0 << 5 | (int)std::min(n_chunks, 255ll) << 8;
                     Q.hw_magic = (unsigned)((1ull << 32) / (unsigned)(P.ho * P.wo)) + 1u; Q.wo_magic = (unsigned)((1ull << 32) / (unsigned)P.wo) + 1u; Q.c16_magic = (unsigned)((1ull << 32) / (unsigned)P.c16) + 1u;
                     if ((long long)Q.m * (P.ho * P.wo) >= (1ll << 32) || P.wo < 2 || P.c16 < 2) Q.hw_magic = 0;       // (a divisor of 1 has no 32-bit magic)
+                    *variant |= (Q.hw_magic ? 1 : 0) << 5;
                     if (P.R.lo == 0 && P.R.hi == 255) hipLaunchKernelGGL((q_dwm_k<true>), dim3((unsigned)((n_items + 3) / 4)), dim3(256), 0, s, Q, (int)n_items);
                     else hipLaunchKernelGGL((q_dwm_k<false>), dim3((unsigned)((n_items + 3) / 4)), dim3(256), 0, s, Q, (int)n_items);
                     DD_LAUNCH_CHECK();
@@ -1692,6 +1747,7 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
                 if (i < (int)net->op_launch.size()) net->op_launch[i] = 17;      // dd_net_op_launches: q_dwm_k ran (a layer table prints the kernel that ran, not the op's default)
                 return DD_OK;
             }
+            *variant = QV_DW | 1 << 8;
             hipLaunchKernelGGL(q_dw_k, dim3((unsigned)((P.total + 255) / 256)), dim3(256), 0, s, P);
             DD_LAUNCH_CHECK();
             return DD_OK;
@@ -1723,23 +1779,15 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
             const long long lim = 4294967295ll / out_img, n_chunks = (nimg + lim - 1) / lim, chunk = (nimg + n_chunks - 1) / n_chunks;
             DD_REQUIRE(lim >= 1, DD_E_CAPACITY, "dd_net_forward: uint8 block %d: one frame's output beyond 32-bit offsets", i);
             const int dev = net->ctx->device;
-            static const int qt128 = getenv("DD_Q_QT128") ? atoi(getenv("DD_Q_QT128")) : 1;   // block 1: 128-pixel tiles, four waves (0: 64-pixel tiles, two waves)
             for (long long c0 = 0; c0 < nimg; c0 += chunk) {
                 const int nc = (int)std::min(chunk, nimg - c0);
                 QDwpwP Q = P;
                 Q.in = P.in + c0 * in_img; Q.out = P.out + c0 * out_img;
                 bool ok = false;
-                int rc = DD_OK;
-#define DD_QB(CIN_, COUT_, WP_, S_, LPT_) launch_q_dwpw<CIN_, COUT_, WP_, S_, LPT_>(s, Q, nc, dev, &ok)
-                if (cin == 32 && cout == 64 && stride == 1) rc = qt128 ? launch_q_dwpw<32, 64, 4, 1, 6, 0, 4, 128>(s, Q, nc, dev, &ok) : DD_QB(32, 64, 2, 1, 8);
-                else if (cin == 64 && cout == 128 && stride == 2) rc = DD_QB(64, 128, 2, 2, 8);
-                else if (cin == 128 && cout == 128 && stride == 1) rc = DD_QB(128, 128, 2, 1, 8);
-                else if (cin == 128 && cout == 256 && stride == 2) rc = DD_QB(128, 256, 2, 2, 8);
-                else if (cin == 256 && cout == 256 && stride == 1) rc = DD_QB(256, 256, 2, 1, 6);
-                else if (cin == 256 && cout == 512 && stride == 2) rc = DD_QB(256, 512, 1, 2, 12);
-                else if (cin == 512 && cout == 512 && stride == 1) rc = DD_QB(512, 512, 1, 1, 8);
-#undef DD_QB
+                int v = 0;
+                const int rc = dwpw_dispatch(s, Q, nc, dev, cin, cout, stride, &ok, false, &v);
                 if (rc != DD_OK) return rc;
+                if (ok) *variant = v | (int)std::min(n_chunks, 127ll) << 21;
                 DD_REQUIRE(ok, DD_E_ARG, "dd_net_forward: uint8 block %d (%d -> %d, stride %d, %d x %d): no fused kernel for this shape -- compile the program with the two-op form", i, cin, cout, stride, P.H, P.W);
             }
             return DD_OK;
@@ -1760,6 +1808,7 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
                 const long long nc = std::min(chunk, nimg - c0);
                 P.a = base(src) + c0 * img_bytes; P.b = base(o[3]) + c0 * img_bytes; P.out = base(dst) + c0 * img_bytes;
                 P.n_items = (int)(nc * per_img);
+                *variant = QV_ADD | (int)std::min((nimg + chunk - 1) / chunk, 255ll) << 8;
                 hipLaunchKernelGGL(q_add_k, dim3((unsigned)dd_ceil_div(P.n_items, 256)), dim3(256), 0, s, P);
                 DD_LAUNCH_CHECK();
             }
@@ -1779,6 +1828,7 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
             P.box_scale = of[32]; P.box_zp = of[33]; P.sc_scale = of[34]; P.sc_zp = of[35]; P.thr = net->dec_thr;
             P.anchors = net->d_anchors; P.boxes = net->dec_boxes; P.score = net->dec_score; P.keys = net->dec_keys; P.cls_out = net->dec_cls;
             DD_REQUIRE(P.cls_stride % 16 == 0 && P.n_classes <= 128, DD_E_ARG, "dd_net_forward: uint8 decode: %d classes in rows of %d bytes", P.n_classes, P.cls_stride);
+            *variant = QV_DECODE;
             hipLaunchKernelGGL(q_ssd_decode_k, dim3(dd_ceil_div(P.n_anchors * 8, 256), nimg), dim3(256), 0, s, P);
             DD_LAUNCH_CHECK();
             return DD_OK;

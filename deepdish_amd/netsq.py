@@ -43,7 +43,7 @@ def folded_addends(cb, rw):
     m, e, zo = int(rw[32]), int(rw[33]), int(rw[40])
     c = (1 << 30) + ((1 << (30 + e)) if e > 0 else 0) + (zo << (31 + e))
     out = [int(v) * m + c for v in np.asarray(cb).reshape(-1)]
-    assert all(-(1 << 62) < v < (1 << 62) for v in out)
+    _model_need(all(-(1 << 62) < v < (1 << 62) for v in out), 'a requantisation addend (folded bias x multiplier + zero point << %d) leaves 62 bits' % (31 + e), 'uint8 layer')
     return np.array(out, dtype=np.int64)
 
 
@@ -71,7 +71,7 @@ def pack_conv(L, epi, chan_map=None, cout_pad=None):
     wk[valid, :, :cin] = src[cmap[valid]]
     cb = np.zeros(cout_pad, np.int64)
     cb[valid] = _cbias(L, src.reshape(cout, -1))[cmap[valid]]
-    assert np.abs(cb).max() < 2 ** 31
+    _model_need(np.abs(cb).max() < 2 ** 31, 'a folded bias (bias - za * sum w + K za zw) leaves 32 bits', 'uint8 layer')
     n_mfrag = cout_pad // 16
     ksteps = kh * kw * kcpt
     # rows: natural (ROWS) or fragment m of group mg holds row 4g + r = channel 64 mg + 16 g + 4 m + r (Q16)
@@ -101,7 +101,7 @@ def pack_conv0(L):
         chan = 8 * (row // 4) + 4 * f + (row % 4)
         return np.transpose(wk[chan], (0, 2, 1, 3)).reshape(2, 64, 16).astype(np.int8)    # wk[chan]: [2][16][4][16]
     w = L['w'].astype(np.int64)
-    assert w.shape == (3, 3, 3, 32)
+    _model_need(w.shape == (3, 3, 3, 32), 'first layer with a filter of shape %s (3x3 over 3 colours into 32 channels is built)' % (tuple(w.shape),), 'uint8 layer')
     x = w - int(L['w_zp'])
     hi = np.clip(x, -128, 127)
     if int(L['w_zp']) != 128 and (x - hi).max() <= 127:
@@ -154,75 +154,127 @@ def _model_need(cond, what, model='uint8 SSD-MobileNet-v1'):
         raise UnsupportedModel('%s: %s' % (model, what))
 
 
-def compile_ssd_mobilenet_quant(qm):
-    """u8 RGB [n,300,300,3] -> box encodings u8 [n,1917,4] and class logits u8 [n,1917,96] (91 used per row), both in the
-    tensors' own quantisation; dd_net_ssd_decode adds the post-process op's first stage (per-anchor arrays).  A v2 model
-    (kind 'ssd_mobilenet_v2_uint8') goes to compile_ssd_mobilenet_v2_quant."""
-    if qm.get('kind') == 'ssd_mobilenet_v2_uint8':
-        return compile_ssd_mobilenet_v2_quant(qm)
-    size = int(qm['input']['size'])
-    P = Program(size, size)
-    Ls = qm['layers']
-    anchors, maps = nets.ssd_anchors(size)
-    if qm.get('anchors') is not None:                       # a model file carries its own (the post-process op's third input)
-        _model_need(tuple(qm['anchors'].shape) == tuple(anchors.shape), 'anchors %s (this input size gives %s)' % (tuple(qm['anchors'].shape), tuple(anchors.shape)))
-        anchors = np.ascontiguousarray(qm['anchors'], dtype=np.float32)
-    n_anchors = len(anchors)
+def add_words(a):
+    """Op words of a uint8 ADD (OP_QADD, or OP_QCONV with a residual operand): 20..25 the three multipliers and right shifts
+    (quantize.add_multipliers), 28 / 29 the two input zero points, 31 the output zero point, 34 / 35 the clamp."""
+    m1, e1, m2, e2, mo, eo = quantize.add_multipliers(a)
+    return {20: m1, 21: e1, 22: m2, 23: e2, 24: mo, 25: eo, 28: int(a['in1_zp']), 29: int(a['in2_zp']), 31: int(a['out_zp']),
+            34: int(a['lo']), 35: int(a['hi'])}
 
-    def geom(t, k, stride):
-        d = P.T(t)
+
+def pad_channels(L, cin=None, cout=None):
+    """A layer with phantom channels appended: input channels (consumers of a tensor stored wider than the model's) and output rows get
+    weights = the weight zero point and bias 0, so (a - za)(w - zw) = 0 on them and a phantom output row stores the output zero point."""
+    w = L['w']
+    pads = [(0, 0)] * 4
+    if cin is not None:
+        pads[2] = (0, cin - w.shape[2])
+    if cout is not None:
+        pads[3] = (0, cout - w.shape[3])
+    if not any(p[1] for p in pads):
+        return L
+    w = np.pad(w, pads, constant_values=int(L['w_zp']))
+    return dict(L, w=w, bias=np.pad(L['bias'], (0, w.shape[3] - len(L['bias']))))
+
+
+def dwpw_fits(cin, cout, stride, h, w, split_filter=False):
+    """Whether csrc/netsq.hip runs a MobileNet block of this shape on an h x w map as one launch of q_dwpw_k.  The rule (ring rows a tile
+    step requests against the instantiation's prefetch depth, LDS, the 24-bit multiplies) is stated once, in launch_q_dwpw; this asks the
+    library (host code: no device), so that a program never holds an OP_QDWPW that dd_net_forward would refuse.  The rule is asked for one
+    frame.  Its terms that grow with the frames of a launch (n tiles^2 < 2^32, (n + 1)(H + 2) NR < 2^32, (n + 1)(ho + 2) < 2^23) cannot decide
+    otherwise for maps below 2^18 pixels: forward launches chunks of frames whose bordered output stays below 4 GiB (at least 64 bytes a
+    pixel), which bounds n ho wo by 2^26.  A larger map in a batch that large is still refused at forward, as before."""
+    import ctypes
+    from ._lib import lib, check
+    ok = ctypes.c_int(0)
+    check(lib().dd_netq_dwpw_fits(int(cin), int(cout), int(stride), int(h), int(w), int(bool(split_filter)), ctypes.byref(ok)), 'dd_netq_dwpw_fits')
+    return bool(ok.value)
+
+
+class QBuilder:
+    """The ops of a uint8 program, one method per op: each takes a layer dict (a QModel layer: w, w_zp, bias, in_zp, in_scale, w_scale,
+    out_scale, out_zp, act, stride) and tensor ids of `P`, appends the op and returns the tensor it writes.  The two model compilers below
+    and one-op programs (tests/test_gpu_q_ops.py) emit their ops through it.  `name` only labels messages and `layer_t`."""
+
+    def __init__(self, P, model='uint8 SSD-MobileNet-v1', pad=False):
+        """pad: tensors may be stored wider than the model's channel counts (MobileNet-v2's 24 as 32): conv() appends phantom channels
+        (pad_channels) and picks the bordered epilogue from the layer."""
+        self.P, self.model, self.pad = P, model, pad
+        self.layer_t = {}                                       # layer name -> the tensor it writes (pad=True programs)
+
+    def need(self, cond, what):
+        _model_need(cond, what, self.model)
+
+    def geom(self, t, k, stride):
+        d = self.P.T(t)
         ho, pt = same_pad(d['h'], k, stride)
         wo, pl = same_pad(d['w'], k, stride)
         return ho, wo, pt, pl
 
-    def info(kernel, flops, nbytes, wbytes, src_bytes=0):
-        P.info[-1] = dict(kernel=kernel, flops=flops, bytes=nbytes, wbytes=wbytes, src_bytes=src_bytes)     # src_bytes: what the op reads (a folded op's share of its launch: profile.launches_of)
+    def info(self, kernel, flops, nbytes, wbytes, src_bytes=0):
+        self.P.info[-1] = dict(kernel=kernel, flops=flops, bytes=nbytes, wbytes=wbytes, src_bytes=src_bytes)     # src_bytes: what the op reads (a folded op's share of its launch: profile.launches_of)
 
-    # first layer
-    L = Ls['conv0']
-    ho, pt = same_pad(size, 3, L['stride'])
-    wo, pl = same_pad(size, 3, L['stride'])
-    x = P.qtensor(ho, wo, 32, L['out_zp'])
-    wp, wl, cb = pack_conv0(L)
-    raw = _req_words(L)
-    P.add_blob(np.zeros(16, np.uint8))                      # (offset 0 means "absent" in the op words)
-    raw.update({38: 0 if wl is not None else 128 - int(L['w_zp']), 39: int(L['in_zp']), 46: P.add_blob(folded_addends(cb, raw))})
-    P._op(OP_QCONV0, dst=x, kh=3, kw=3, stride=L['stride'], pad_t=pt, pad_l=pl, cin=3, cout=32, cout_pad=32,
-          w_off=P.add_blob(wp), b_off=P.add_blob(cb), aff_off=P.add_blob(wl) if wl is not None else 0, ho=ho, wo=wo, raw=raw)
-    info('q_conv0_k', 2 * ho * wo * 27 * 32, 3 * size * size + ho * wo * 32, 27 * 32 + 4 * 32, 3 * size * size)
+    def conv0(self, L):
+        """First layer: u8 frames [n][in_h][in_w][3] -> 32 channels (q_conv0_k)."""
+        P = self.P
+        ho, pt = same_pad(P.in_h, 3, L['stride'])
+        wo, pl = same_pad(P.in_w, 3, L['stride'])
+        x = P.qtensor(ho, wo, 32, L['out_zp'])
+        wp, wl, cb = pack_conv0(L)
+        raw = _req_words(L)
+        P.add_blob(np.zeros(16, np.uint8))                      # (offset 0 means "absent" in the op words)
+        raw.update({38: 0 if wl is not None else 128 - int(L['w_zp']), 39: int(L['in_zp']), 46: P.add_blob(folded_addends(cb, raw))})
+        P._op(OP_QCONV0, dst=x, kh=3, kw=3, stride=L['stride'], pad_t=pt, pad_l=pl, cin=3, cout=32, cout_pad=32,
+              w_off=P.add_blob(wp), b_off=P.add_blob(cb), aff_off=P.add_blob(wl) if wl is not None else 0, ho=ho, wo=wo, raw=raw)
+        self.info('q_conv0_k', 2 * ho * wo * 27 * 32, 3 * P.in_h * P.in_w + ho * wo * 32, 27 * 32 + 4 * 32, 3 * P.in_h * P.in_w)
+        return x
 
-    def conv(src, name, epi=QEPI_Q16, dst=None, chan_map=None, cout_pad=None, row_bytes=0, base_off=0, cout_store=0):
-        L = Ls[name]
-        kh = L['w'].shape[0]
-        ho, wo, pt, pl = geom(src, kh, L['stride'])
+    def conv(self, src, L0, name='?', epi=None, res=-1, add=None, dst=None, chan_map=None, cout_pad=None, row_bytes=0, base_off=0, cout_store=0):
+        """epi None: QEPI_Q16, or with pad=True the 64-channel interleave where it fits (ReLU6, C % 64 == 0) and the natural order otherwise.
+        res / add: the block input and the parameters of the residual ADD in this layer's epilogue (QEPI_Q16N)."""
+        P = self.P
         s = P.T(src)
-        _model_need(s['zp'] == L['in_zp'] and L['w'].shape[2] == s['c'], '%s: input zero point %s / channels %s, its producer writes %s / %s' % (name, L['in_zp'], L['w'].shape[2], s['zp'], s['c']))
+        # pad: the layer as the tensors store it (phantom input channels and, for a bordered output, phantom output rows)
+        L = pad_channels(L0, cin=s['c'], cout=(L0['w'].shape[3] + 15) // 16 * 16 if epi != QEPI_ROWS else None) if self.pad else L0
+        kh = L['w'].shape[0]
+        ho, wo, pt, pl = self.geom(src, kh, L['stride'])
+        self.need(s['zp'] == L['in_zp'] and L0['w'].shape[2] <= s['c'] and L['w'].shape[2] == s['c'],
+                  '%s: input zero point %s / channels %s, its producer writes %s / %s' % (name, L['in_zp'], L0['w'].shape[2], s['zp'], s['c']))
+        if epi is None:
+            epi = QEPI_Q16 if not self.pad or (L['act'] == 'relu6' and res < 0 and L['w'].shape[3] % 64 == 0) else QEPI_Q16N
         wp, cb, kcpt = pack_conv(L, epi, chan_map, cout_pad)
-        if dst is None:
-            dst = P.qtensor(ho, wo, L['w'].shape[3], L['out_zp'])
+        if epi != QEPI_ROWS:                                 # a bordered output is this op's own tensor (the ADD's, where it has one); rows go to `dst`
+            dst = P.qtensor(ho, wo, L['w'].shape[3], add['out_zp'] if add is not None else L['out_zp'])
         raw = _req_words(L)
         raw.update({38: 128 - int(L['w_zp']), 39: int(L['in_zp']), 42: row_bytes, 43: base_off, 44: cout_store})
         # the per-channel 64-bit requantisation addends (q_pws_k): cbias * M + C of the ReLU form, or + 2^30 (the first rounding) without activation
         raw[46] = P.add_blob(folded_addends(cb, raw) if not raw[41] else np.array([int(v) * int(raw[32]) + (1 << 30) for v in cb], dtype=np.int64))
-        P._op(OP_QCONV, src=src, dst=dst, kh=kh, kw=kh, stride=L['stride'], pad_t=pt, pad_l=pl, cin=s['c'], cout=L['w'].shape[3],
+        if add is not None:
+            r = P.T(res)
+            self.need(r['zp'] == add['in2_zp'] and L['out_zp'] == add['in1_zp'] and (r['h'], r['w'], r['c']) == (ho, wo, L['w'].shape[3]),
+                      '%s: the residual ADD reads tensors of other geometry or zero points' % name)
+            raw.update(add_words(add))
+        if self.pad and epi != QEPI_ROWS and add is None:
+            self.layer_t[name] = dst
+        P._op(OP_QCONV, src=src, dst=dst, res=res, kh=kh, kw=kh, stride=L['stride'], pad_t=pt, pad_l=pl, cin=s['c'], cout=L['w'].shape[3],
               cout_pad=len(cb), kpad=kcpt, epi=epi, w_off=P.add_blob(wp), b_off=P.add_blob(cb), ho=ho, wo=wo, raw=raw)
-        cin, cout = L['w'].shape[2:]
+        cin, cout = L0['w'].shape[2:]
         # (label: the kernel that runs the layer at the bench's 384 frames per launch -- csrc/netsq.hip picks q_pws_k from 8 192 pixels up)
-        pws = kh == 1 and L['stride'] == 1 and cin in (512, 1024) and len(cb) >= 128
-        info('q_pws_k' if pws else 'q_conv_k', 2 * ho * wo * kh * kh * cin * cout, s['h'] * s['w'] * cin + ho * wo * cout, kh * kh * cin * cout + 4 * cout)
+        pws = not self.pad and kh == 1 and L['stride'] == 1 and cin in (512, 1024) and len(cb) >= 128
+        self.info('q_pws_k' if pws else 'q_conv_k', 2 * ho * wo * kh * kh * cin * cout, s['h'] * s['w'] * cin + ho * wo * cout, kh * kh * cin * cout + 4 * cout)
         return dst
 
-    def conv_heads(src, cname, bname, cls_args, box_args):
+    def conv_heads(self, src, Lc, Lb, cls_args, box_args, name='?'):
         """The class and box predictors of one feature map as ONE op (they read the same pixels; csrc/netsq.hip q_pws_k stores both, small
-        batches run two launches of q_conv_k): fragments of the class layer first, then the box layer's; its parameters in words 20..25, 28."""
-        Lc, Lb = Ls[cname], Ls[bname]
+        batches run one launch of q_conv_k): fragments of the class layer first, then the box layer's; its parameters in words 20..25, 28."""
+        P = self.P
         s = P.T(src)
-        ho, wo, pt, pl = geom(src, 1, 1)
-        _model_need(s['zp'] == Lc['in_zp'] == Lb['in_zp'] and Lc['w'].shape[:3] == Lb['w'].shape[:3] == (1, 1, s['c']), '%s / %s: 1x1 predictors on one feature map with one input zero point' % (cname, bname))
+        ho, wo, pt, pl = self.geom(src, 1, 1)
+        self.need(s['zp'] == Lc['in_zp'] == Lb['in_zp'] and Lc['w'].shape[:3] == Lb['w'].shape[:3] == (1, 1, s['c']), '%s: 1x1 predictors on one feature map with one input zero point' % name)
         wc, cbc, kcpt = pack_conv(Lc, QEPI_ROWS, cls_args['chan_map'], cls_args['cout_pad'])
         wb, cbb, _ = pack_conv(Lb, QEPI_ROWS, None, None)
         rc, rb = _req_words(Lc), _req_words(Lb)
-        _model_need(rc[41] and rb[41], '%s / %s: predictors carry no activation' % (cname, bname))
+        self.need(rc[41] and rb[41], '%s: predictors carry no activation' % name)
         lin = lambda cb, r: np.array([int(v) * int(r[32]) + (1 << 30) for v in cb], dtype=np.int64)
         raw = dict(rc)
         raw.update({38: 128 - int(Lc['w_zp']), 39: int(Lc['in_zp']), 42: cls_args['row_bytes'], 43: cls_args['base_off'], 44: cls_args['cout_store'],
@@ -233,35 +285,47 @@ def compile_ssd_mobilenet_quant(qm):
               ho=ho, wo=wo, raw=raw)
         cin = s['c']
         cout = Lc['w'].shape[3] + Lb['w'].shape[3]
-        info('q_pws_k', 2 * ho * wo * cin * cout, s['h'] * s['w'] * cin + ho * wo * cout, cin * cout + 4 * cout)
+        self.info('q_pws_k', 2 * ho * wo * cin * cout, s['h'] * s['w'] * cin + ho * wo * cout, cin * cout + 4 * cout)
 
-    def dw(src, name):
-        L = Ls[name]
-        ho, wo, pt, pl = geom(src, 3, L['stride'])
+    def dw(self, src, L, name='?'):
+        P = self.P
+        ho, wo, pt, pl = self.geom(src, 3, L['stride'])
         s = P.T(src)
-        _model_need(s['zp'] == L['in_zp'] and L['w'].shape[2] == s['c'], '%s: input zero point %s / channels %s, its producer writes %s / %s' % (name, L['in_zp'], L['w'].shape[2], s['zp'], s['c']))
+        self.need(s['zp'] == L['in_zp'] and L['w'].shape[2] == s['c'], '%s: input zero point %s / channels %s, its producer writes %s / %s' % (name, L['in_zp'], L['w'].shape[2], s['zp'], s['c']))
         w16, cb = pack_dw(L)
         dst = P.qtensor(ho, wo, s['c'], L['out_zp'])
+        if self.pad:
+            self.layer_t[name] = dst
         mf = pack_dw_mfma(L)                                    # the matrix-pipe form's operand table (None: a weight needs w - zw = 255)
         P._op(OP_QDW, src=src, dst=dst, kh=3, kw=3, stride=L['stride'], pad_t=pt, pad_l=pl, cin=s['c'], cout=s['c'], cout_pad=s['c'],
               w_off=P.add_blob(w16), b_off=P.add_blob(cb), ho=ho, wo=wo, raw=_req_words(L),
               p=[P.add_blob(mf[0]), P.add_blob(mf[1])] if mf is not None else [0, 0])
-        info('q_dw_k', 2 * ho * wo * 9 * s['c'], s['h'] * s['w'] * s['c'] + ho * wo * s['c'], 9 * s['c'] + 4 * s['c'])
+        self.info('q_dw_k', 2 * ho * wo * 9 * s['c'], s['h'] * s['w'] * s['c'] + ho * wo * s['c'], 9 * s['c'] + 4 * s['c'])
         return dst
 
-    def dwpw(src, dname, pname):
-        """MobileNet block as one launch (csrc/netsq.hip q_dwpw_k) where a fused kernel exists for the shape, else two ops."""
-        Ld, Lp = Ls[dname], Ls[pname]
+    def dwpw_fused(self, src, Ld, Lp):
+        """Whether dwpw() emits the block as one OP_QDWPW: a fused kernel exists for (cin, cout, stride), the map is wide enough to pay
+        (wo >= 19: the 10 x 10 blocks are q_conv_k's) and the launcher takes the geometry (dwpw_fits).  The gate knows no model input size."""
+        s = self.P.T(src)
+        cin, cout, stride = s['c'], Lp['w'].shape[3], Ld['stride']
+        ho, wo, pt, pl = self.geom(src, 3, stride)
+        if not FUSE_BLOCKS or (cin, cout, stride) not in FUSED_SHAPES or wo < 19:
+            return False
+        return dwpw_fits(cin, cout, stride, s['h'], s['w'], SPLIT_PW and SPLIT_PW_MIN_CIN <= cin <= SPLIT_PW_MAX_CIN)
+
+    def dwpw(self, src, Ld, Lp, dname='?', pname='?'):
+        """MobileNet block as one launch (csrc/netsq.hip q_dwpw_k) where a fused kernel takes the shape (dwpw_fused), else two ops."""
+        P = self.P
         s = P.T(src)
         cin, cout, stride = s['c'], Lp['w'].shape[3], Ld['stride']
-        ho, wo, pt, pl = geom(src, 3, stride)
-        if not FUSE_BLOCKS or (cin, cout, stride) not in FUSED_SHAPES or wo < 19:
-            return conv(dw(src, dname), pname)
-        _model_need(s['zp'] == Ld['in_zp'] and Ld['out_zp'] == Lp['in_zp'] and Ld['w'].shape[2] == cin and Lp['w'].shape[2] == cin, '%s / %s: zero points and channel counts along the block do not agree' % (dname, pname))
+        ho, wo, pt, pl = self.geom(src, 3, stride)
+        if not self.dwpw_fused(src, Ld, Lp):
+            return self.conv(self.dw(src, Ld, dname), Lp, pname)
+        self.need(s['zp'] == Ld['in_zp'] and Ld['out_zp'] == Lp['in_zp'] and Ld['w'].shape[2] == cin and Lp['w'].shape[2] == cin, '%s / %s: zero points and channel counts along the block do not agree' % (dname, pname))
         packed_dw = pack_dw_mfma(Ld)
         rd, rp = _req_words(Ld), _req_words(Lp)
         if packed_dw is None or rd[33] < 1 or rp[33] < 1:
-            return conv(dw(src, dname), pname)                             # w - zw = 255, or a multiplier >= 0.5: the two-op form handles it
+            return self.conv(self.dw(src, Ld, dname), Lp, pname)           # w - zw = 255, or a multiplier >= 0.5: the two-op form handles it
         dwa, dcb = packed_dw
         wp, cb, kcpt = pack_conv(Lp, QEPI_Q16)
         zwc = 128 - int(Lp['w_zp'])
@@ -292,72 +356,94 @@ def compile_ssd_mobilenet_quant(qm):
         P._op(OP_QDWPW, src=src, dst=dst, kh=1, kw=1, stride=stride, pad_t=pt, pad_l=pl, cin=cin, cout=cout, cout_pad=cout, kpad=kcpt,
               w_off=P.add_blob(wp), b_off=P.add_blob(cb), aff_off=w_lo, ho=ho, wo=wo,
               p=[P.add_blob(dwa), P.add_blob(dcb), rd[32], rd[33], rd[36], rd[37]], bk=rd[40], raw=raw)
-        info('q_dwpw_k', 2 * ho * wo * cin * (9 + cout), s['h'] * s['w'] * cin + ho * wo * cout, cin * (9 + cout) + 4 * (cin + cout), s['h'] * s['w'] * cin)
+        self.info('q_dwpw_k', 2 * ho * wo * cin * (9 + cout), s['h'] * s['w'] * cin + ho * wo * cout, cin * (9 + cout) + 4 * (cin + cout), s['h'] * s['w'] * cin)
         return dst
 
-    feats = {}
-    for i in range(1, 14):
-        x = dwpw(x, f'dw{i}', f'pw{i}')
-        feats[f'pw{i}'] = x
-    for j in range(1, 5):
-        x = conv(conv(x, f'extra{j}_1'), f'extra{j}_2')
-        feats[f'extra{j}_2'] = x
-    n_cls = Ls['cls0']['w'].shape[3] // nets.SSD_ANCHORS_PER_MAP[0]
-    cls_row = (n_cls + 15) // 16 * 16                        # 91 -> 96 bytes per anchor
-    box_t = P.tensor(n_anchors, 1, 4, cs=4, dtype=DT_U8)
-    cls_t = P.tensor(n_anchors, 1, n_cls, cs=cls_row, dtype=DT_U8)
-    base = 0
-    for k, (fname, a) in enumerate(zip(FEATURE_LAYERS, nets.SSD_ANCHORS_PER_MAP)):
-        ft = feats[fname]
-        fm = P.T(ft)['h']
-        _model_need(fm == maps[k], 'feature map %d is %dx%d (the anchors are laid out for %d)' % (k, fm, fm, maps[k]))
-        for other in (f'box{k}', f'cls{k}'):
-            _model_need((Ls[other]['out_scale'], Ls[other]['out_zp']) == (Ls[other[:3] + '0']['out_scale'], Ls[other[:3] + '0']['out_zp']),
-                        'the six %s tensors are concatenated: they need one (scale, zero point)' % other[:3])
+    def add_op(self, a_t, b_t, add):
+        P = self.P
+        t1, t2 = P.T(a_t), P.T(b_t)
+        self.need(t1['zp'] == add['in1_zp'] and t2['zp'] == add['in2_zp'] and (t1['h'], t1['w'], t1['c']) == (t2['h'], t2['w'], t2['c']),
+                  'ADD of tensors with other geometry or zero points')
+        dst = P.qtensor(t1['h'], t1['w'], t1['c'], add['out_zp'])
+        P._op(OP_QADD, src=a_t, dst=dst, res=b_t, cin=t1['c'], cout=t1['c'], ho=t1['h'], wo=t1['w'], raw=add_words(add))
+        nb = t1['h'] * t1['w'] * t1['c']
+        self.info('q_add_k', 0, 3 * nb, 0, 2 * nb)
+        return dst
+
+    def rows_tensors(self, n_anchors, n_cls):
+        """The two head tensors (plain rows): boxes [n_anchors][4], class logits [n_anchors][n_cls in rows of a multiple of 16 bytes]."""
+        cls_row = (n_cls + 15) // 16 * 16                        # 91 -> 96 bytes per anchor
+        box_t = self.P.tensor(n_anchors, 1, 4, cs=4, dtype=DT_U8)
+        cls_t = self.P.tensor(n_anchors, 1, n_cls, cs=cls_row, dtype=DT_U8)
+        return box_t, cls_t, cls_row
+
+    @staticmethod
+    def head_args(box_t, cls_t, a, n_cls, cls_row, base):
+        """Row geometry of a feature map's two predictors (a anchors per pixel, rows from anchor `base` on): (box_args, cls_args) for
+        conv(epi=QEPI_ROWS, **args) or conv_heads."""
         cmap = np.full(a * cls_row, -1, np.int64)
         for an in range(a):
             cmap[an * cls_row:an * cls_row + n_cls] = an * n_cls + np.arange(n_cls)
         box_args = dict(dst=box_t, row_bytes=4 * a, base_off=4 * base, cout_store=4 * a)
         cls_args = dict(dst=cls_t, chan_map=cmap, cout_pad=(a * cls_row + 15) // 16 * 16, row_bytes=a * cls_row, base_off=cls_row * base, cout_store=a * cls_row)
+        return box_args, cls_args
+
+    def decode(self, box_t, cls_t, Lb, Lc, logistic, n_cls, n_anchors, cls_row):
+        P = self.P
+        lut = quantize.logistic_table(Lc['out_scale'], Lc['out_zp'], logistic['out_scale'], logistic['out_zp'])
+        P._op(OP_QSSD_DECODE, src=box_t, res=cls_t, w_off=P.add_blob(lut), p=[n_cls, n_anchors],
+              rawf={32: float(Lb['out_scale']), 33: float(Lb['out_zp']), 34: float(logistic['out_scale']), 35: float(logistic['out_zp'])})
+        self.info('q_ssd_decode_k', 0, n_anchors * (4 + cls_row + 24), 256)
+
+
+def compile_ssd_mobilenet_quant(qm):
+    """u8 RGB [n,300,300,3] -> box encodings u8 [n,1917,4] and class logits u8 [n,1917,96] (91 used per row), both in the
+    tensors' own quantisation; dd_net_ssd_decode adds the post-process op's first stage (per-anchor arrays).  A v2 model
+    (kind 'ssd_mobilenet_v2_uint8') goes to compile_ssd_mobilenet_v2_quant.
+    Needs the built library (no device): whether a MobileNet block becomes one fused op is the launcher's own rule (dwpw_fits)."""
+    if qm.get('kind') == 'ssd_mobilenet_v2_uint8':
+        return compile_ssd_mobilenet_v2_quant(qm)
+    size = int(qm['input']['size'])
+    P = Program(size, size)
+    B = QBuilder(P)
+    Ls = qm['layers']
+    anchors, maps = nets.ssd_anchors(size)
+    if qm.get('anchors') is not None:                       # a model file carries its own (the post-process op's third input)
+        B.need(tuple(qm['anchors'].shape) == tuple(anchors.shape), 'anchors %s (this input size gives %s)' % (tuple(qm['anchors'].shape), tuple(anchors.shape)))
+        anchors = np.ascontiguousarray(qm['anchors'], dtype=np.float32)
+    n_anchors = len(anchors)
+    x = B.conv0(Ls['conv0'])
+    conv = lambda src, name, **kw: B.conv(src, Ls[name], name, **kw)
+    feats = {}
+    for i in range(1, 14):
+        x = B.dwpw(x, Ls[f'dw{i}'], Ls[f'pw{i}'], f'dw{i}', f'pw{i}')
+        feats[f'pw{i}'] = x
+    for j in range(1, 5):
+        x = conv(conv(x, f'extra{j}_1'), f'extra{j}_2')
+        feats[f'extra{j}_2'] = x
+    n_cls = Ls['cls0']['w'].shape[3] // nets.SSD_ANCHORS_PER_MAP[0]
+    box_t, cls_t, cls_row = B.rows_tensors(n_anchors, n_cls)
+    base = 0
+    for k, (fname, a) in enumerate(zip(FEATURE_LAYERS, nets.SSD_ANCHORS_PER_MAP)):
+        ft = feats[fname]
+        fm = P.T(ft)['h']
+        B.need(fm == maps[k], 'feature map %d is %dx%d (the anchors are laid out for %d)' % (k, fm, fm, maps[k]))
+        for other in (f'box{k}', f'cls{k}'):
+            B.need((Ls[other]['out_scale'], Ls[other]['out_zp']) == (Ls[other[:3] + '0']['out_scale'], Ls[other[:3] + '0']['out_zp']),
+                   'the six %s tensors are concatenated: they need one (scale, zero point)' % other[:3])
+        box_args, cls_args = B.head_args(box_t, cls_t, a, n_cls, cls_row, base)
         if MERGE_HEADS and P.T(ft)['c'] in (512, 1024):
-            conv_heads(ft, f'cls{k}', f'box{k}', cls_args, box_args)
+            B.conv_heads(ft, Ls[f'cls{k}'], Ls[f'box{k}'], cls_args, box_args, f'cls{k} / box{k}')
         else:
             conv(ft, f'box{k}', epi=QEPI_ROWS, **box_args)
             conv(ft, f'cls{k}', epi=QEPI_ROWS, **cls_args)
         base += fm * fm * a
-    _model_need(base == n_anchors, '%d anchors for predictors that emit %d rows' % (n_anchors, base))
-    Lb, Lc = Ls['box0'], Ls['cls0']
-    lut = quantize.logistic_table(Lc['out_scale'], Lc['out_zp'], qm['logistic']['out_scale'], qm['logistic']['out_zp'])
-    P._op(OP_QSSD_DECODE, src=box_t, res=cls_t, w_off=P.add_blob(lut), p=[n_cls, n_anchors],
-          rawf={32: float(Lb['out_scale']), 33: float(Lb['out_zp']), 34: float(qm['logistic']['out_scale']), 35: float(qm['logistic']['out_zp'])})
-    info('q_ssd_decode_k', 0, n_anchors * (4 + cls_row + 24), 256)
+    B.need(base == n_anchors, '%d anchors for predictors that emit %d rows' % (n_anchors, base))
+    B.decode(box_t, cls_t, Ls['box0'], Ls['cls0'], qm['logistic'], n_cls, n_anchors, cls_row)
     P.out_tensor = cls_t
     P.meta = dict(kind='ssd_mobilenet_v1_uint8', anchors=anchors, n_classes=n_cls, box_tensor=box_t, cls_tensor=cls_t, cls_row=cls_row,
                   feats=feats, quant=True)
     return P
-
-
-def add_words(a):
-    """Op words of a uint8 ADD (OP_QADD, or OP_QCONV with a residual operand): 20..25 the three multipliers and right shifts
-    (quantize.add_multipliers), 28 / 29 the two input zero points, 31 the output zero point, 34 / 35 the clamp."""
-    m1, e1, m2, e2, mo, eo = quantize.add_multipliers(a)
-    return {20: m1, 21: e1, 22: m2, 23: e2, 24: mo, 25: eo, 28: int(a['in1_zp']), 29: int(a['in2_zp']), 31: int(a['out_zp']),
-            34: int(a['lo']), 35: int(a['hi'])}
-
-
-def pad_channels(L, cin=None, cout=None):
-    """A layer with phantom channels appended: input channels (consumers of a tensor stored wider than the model's) and output rows get
-    weights = the weight zero point and bias 0, so (a - za)(w - zw) = 0 on them and a phantom output row stores the output zero point."""
-    w = L['w']
-    pads = [(0, 0)] * 4
-    if cin is not None:
-        pads[2] = (0, cin - w.shape[2])
-    if cout is not None:
-        pads[3] = (0, cout - w.shape[3])
-    if not any(p[1] for p in pads):
-        return L
-    w = np.pad(w, pads, constant_values=int(L['w_zp']))
-    return dict(L, w=w, bias=np.pad(L['bias'], (0, w.shape[3] - len(L['bias']))))
 
 
 def compile_ssd_mobilenet_v2_quant(qm):
@@ -365,93 +451,22 @@ def compile_ssd_mobilenet_v2_quant(qm):
     v1's program, op by op: first layer (q_conv0_k), 1x1 expansions and projections (q_conv_k), depthwise layers (q_dwm_k / q_dw_k),
     the residual ADDs in the projections' epilogues (DD_Q_ADD_FUSE=0: OP_QADD, q_add_k).  Tensors of 24 channels are stored as 32
     (pad_channels: the phantom channels hold the zero point)."""
-    need = lambda cond, what: _model_need(cond, what, 'uint8 SSD-MobileNet-v2')
     size = int(qm['input']['size'])
     P = Program(size, size)
+    B = QBuilder(P, 'uint8 SSD-MobileNet-v2', pad=True)
+    need = B.need
     Ls = qm['layers']
     anchors, maps = nets.ssd_anchors(size)
     if qm.get('anchors') is not None:
         need(tuple(qm['anchors'].shape) == tuple(anchors.shape), 'anchors %s (this input size gives %s)' % (tuple(qm['anchors'].shape), tuple(anchors.shape)))
         anchors = np.ascontiguousarray(qm['anchors'], dtype=np.float32)
     n_anchors = len(anchors)
-
-    def geom(t, k, stride):
-        d = P.T(t)
-        ho, pt = same_pad(d['h'], k, stride)
-        wo, pl = same_pad(d['w'], k, stride)
-        return ho, wo, pt, pl
-
-    def info(kernel, flops, nbytes, wbytes, src_bytes=0):
-        P.info[-1] = dict(kernel=kernel, flops=flops, bytes=nbytes, wbytes=wbytes, src_bytes=src_bytes)
-
-    layer_t = {}                                             # layer (or block: its ADD's output) -> the tensor it writes
+    layer_t = B.layer_t                                      # layer (or block: its ADD's output) -> the tensor it writes
 
     L = Ls['conv0']
-    ho, pt = same_pad(size, 3, L['stride'])
-    wo, pl = same_pad(size, 3, L['stride'])
     need(L['w'].shape == (3, 3, 3, 32) and L['act'] == 'relu6', 'conv0: a 3x3 layer of 32 channels with ReLU6')
-    x = layer_t['conv0'] = P.qtensor(ho, wo, 32, L['out_zp'])
-    wp, wl, cb = pack_conv0(L)
-    raw = _req_words(L)
-    P.add_blob(np.zeros(16, np.uint8))
-    raw.update({38: 0 if wl is not None else 128 - int(L['w_zp']), 39: int(L['in_zp']), 46: P.add_blob(folded_addends(cb, raw))})
-    P._op(OP_QCONV0, dst=x, kh=3, kw=3, stride=L['stride'], pad_t=pt, pad_l=pl, cin=3, cout=32, cout_pad=32,
-          w_off=P.add_blob(wp), b_off=P.add_blob(cb), aff_off=P.add_blob(wl) if wl is not None else 0, ho=ho, wo=wo, raw=raw)
-    info('q_conv0_k', 2 * ho * wo * 27 * 32, 3 * size * size + ho * wo * 32, 27 * 32 + 4 * 32, 3 * size * size)
-
-    def conv(src, name, epi=None, res=-1, add=None, chan_map=None, cout_pad=None, dst=None, row_bytes=0, base_off=0, cout_store=0):
-        s = P.T(src)
-        L0 = Ls[name]
-        cout = L0['w'].shape[3]
-        L = pad_channels(L0, cin=s['c'], cout=(cout + 15) // 16 * 16 if epi != QEPI_ROWS else None)
-        kh = L['w'].shape[0]
-        ho, wo, pt, pl = geom(src, kh, L['stride'])
-        need(s['zp'] == L['in_zp'] and L0['w'].shape[2] <= s['c'] and L['w'].shape[2] == s['c'],
-                    '%s: input zero point %s / channels %s, its producer writes %s / %s' % (name, L['in_zp'], L0['w'].shape[2], s['zp'], s['c']))
-        if epi is None:                                      # bordered output: the 64-channel interleave where it fits (ReLU6, C % 64 == 0), else natural
-            epi = QEPI_Q16 if L['act'] == 'relu6' and res < 0 and L['w'].shape[3] % 64 == 0 else QEPI_Q16N
-        wp, cb, kcpt = pack_conv(L, epi, chan_map, cout_pad)
-        raw = _req_words(L)
-        if epi != QEPI_ROWS:
-            dst = P.qtensor(ho, wo, L['w'].shape[3], add['out_zp'] if add is not None else L['out_zp'])
-        raw.update({38: 128 - int(L['w_zp']), 39: int(L['in_zp']), 42: row_bytes, 43: base_off, 44: cout_store})
-        raw[46] = P.add_blob(folded_addends(cb, raw) if not raw[41] else np.array([int(v) * int(raw[32]) + (1 << 30) for v in cb], dtype=np.int64))
-        if add is not None:
-            r = P.T(res)
-            need(r['zp'] == add['in2_zp'] and L['out_zp'] == add['in1_zp'] and (r['h'], r['w'], r['c']) == (ho, wo, L['w'].shape[3]),
-                        '%s: the residual ADD reads tensors of other geometry or zero points' % name)
-            raw.update(add_words(add))
-        if epi != QEPI_ROWS and add is None:
-            layer_t[name] = dst
-        P._op(OP_QCONV, src=src, dst=dst, res=res, kh=kh, kw=kh, stride=L['stride'], pad_t=pt, pad_l=pl, cin=s['c'], cout=L['w'].shape[3],
-              cout_pad=len(cb), kpad=kcpt, epi=epi, w_off=P.add_blob(wp), b_off=P.add_blob(cb), ho=ho, wo=wo, raw=raw)
-        cin, cout = L0['w'].shape[2:]
-        info('q_conv_k', 2 * ho * wo * kh * kh * cin * cout, s['h'] * s['w'] * cin + ho * wo * cout, kh * kh * cin * cout + 4 * cout)
-        return dst
-
-    def dw(src, name):
-        L = Ls[name]
-        ho, wo, pt, pl = geom(src, 3, L['stride'])
-        s = P.T(src)
-        need(s['zp'] == L['in_zp'] and L['w'].shape[2] == s['c'], '%s: input zero point %s / channels %s, its producer writes %s / %s' % (name, L['in_zp'], L['w'].shape[2], s['zp'], s['c']))
-        w16, cb = pack_dw(L)
-        dst = layer_t[name] = P.qtensor(ho, wo, s['c'], L['out_zp'])
-        mf = pack_dw_mfma(L)
-        P._op(OP_QDW, src=src, dst=dst, kh=3, kw=3, stride=L['stride'], pad_t=pt, pad_l=pl, cin=s['c'], cout=s['c'], cout_pad=s['c'],
-              w_off=P.add_blob(w16), b_off=P.add_blob(cb), ho=ho, wo=wo, raw=_req_words(L),
-              p=[P.add_blob(mf[0]), P.add_blob(mf[1])] if mf is not None else [0, 0])
-        info('q_dw_k', 2 * ho * wo * 9 * s['c'], s['h'] * s['w'] * s['c'] + ho * wo * s['c'], 9 * s['c'] + 4 * s['c'])
-        return dst
-
-    def add_op(a_t, b_t, add):
-        t1, t2 = P.T(a_t), P.T(b_t)
-        need(t1['zp'] == add['in1_zp'] and t2['zp'] == add['in2_zp'] and (t1['h'], t1['w'], t1['c']) == (t2['h'], t2['w'], t2['c']),
-                    'ADD of tensors with other geometry or zero points')
-        dst = P.qtensor(t1['h'], t1['w'], t1['c'], add['out_zp'])
-        P._op(OP_QADD, src=a_t, dst=dst, res=b_t, cin=t1['c'], cout=t1['c'], ho=t1['h'], wo=t1['w'], raw=add_words(add))
-        nb = t1['h'] * t1['w'] * t1['c']
-        info('q_add_k', 0, 3 * nb, 0, 2 * nb)
-        return dst
+    x = layer_t['conv0'] = B.conv0(L)
+    conv = lambda src, name, **kw: B.conv(src, Ls[name], name, **kw)
 
     feats = {}
     blocks = []
@@ -463,14 +478,14 @@ def compile_ssd_mobilenet_v2_quant(qm):
         if b + '_expand' in Ls:
             h = conv(x, b + '_expand')
             feats[b + '_expand'] = h
-        h = dw(h, b + '_dw')
+        h = B.dw(h, Ls[b + '_dw'], b + '_dw')
         add = qm.get('add', {}).get(b)
         if add is None:
             x = conv(h, b + '_project')
         elif ADD_FUSE:
             x = layer_t[b] = conv(h, b + '_project', res=x, add=add)
         else:
-            x = layer_t[b] = add_op(conv(h, b + '_project'), x, add)
+            x = layer_t[b] = B.add_op(conv(h, b + '_project'), x, add)
         feats[b] = x
     x = conv(x, 'conv_last')
     feats['conv_last'] = x
@@ -478,9 +493,7 @@ def compile_ssd_mobilenet_v2_quant(qm):
         x = conv(conv(x, f'extra{j}_1'), f'extra{j}_2')
         feats[f'extra{j}_2'] = x
     n_cls = Ls['cls0']['w'].shape[3] // nets.SSD_ANCHORS_PER_MAP[0]
-    cls_row = (n_cls + 15) // 16 * 16
-    box_t = P.tensor(n_anchors, 1, 4, cs=4, dtype=DT_U8)
-    cls_t = P.tensor(n_anchors, 1, n_cls, cs=cls_row, dtype=DT_U8)
+    box_t, cls_t, cls_row = B.rows_tensors(n_anchors, n_cls)
     base = 0
     for k, (fname, a) in enumerate(zip(quantize.V2_FEATURE_LAYERS, nets.SSD_ANCHORS_PER_MAP)):
         ft = feats[fname]
@@ -488,20 +501,13 @@ def compile_ssd_mobilenet_v2_quant(qm):
         need(fm == maps[k], 'feature map %d is %dx%d (the anchors are laid out for %d)' % (k, fm, fm, maps[k]))
         for other in (f'box{k}', f'cls{k}'):
             need((Ls[other]['out_scale'], Ls[other]['out_zp']) == (Ls[other[:3] + '0']['out_scale'], Ls[other[:3] + '0']['out_zp']),
-                        'the six %s tensors are concatenated: they need one (scale, zero point)' % other[:3])
-        cmap = np.full(a * cls_row, -1, np.int64)
-        for an in range(a):
-            cmap[an * cls_row:an * cls_row + n_cls] = an * n_cls + np.arange(n_cls)
-        conv(ft, f'box{k}', epi=QEPI_ROWS, dst=box_t, row_bytes=4 * a, base_off=4 * base, cout_store=4 * a)
-        conv(ft, f'cls{k}', epi=QEPI_ROWS, dst=cls_t, chan_map=cmap, cout_pad=(a * cls_row + 15) // 16 * 16, row_bytes=a * cls_row,
-             base_off=cls_row * base, cout_store=a * cls_row)
+                 'the six %s tensors are concatenated: they need one (scale, zero point)' % other[:3])
+        box_args, cls_args = B.head_args(box_t, cls_t, a, n_cls, cls_row, base)
+        conv(ft, f'box{k}', epi=QEPI_ROWS, **box_args)
+        conv(ft, f'cls{k}', epi=QEPI_ROWS, **cls_args)
         base += fm * fm * a
     need(base == n_anchors, '%d anchors for predictors that emit %d rows' % (n_anchors, base))
-    Lb, Lc = Ls['box0'], Ls['cls0']
-    lut = quantize.logistic_table(Lc['out_scale'], Lc['out_zp'], qm['logistic']['out_scale'], qm['logistic']['out_zp'])
-    P._op(OP_QSSD_DECODE, src=box_t, res=cls_t, w_off=P.add_blob(lut), p=[n_cls, n_anchors],
-          rawf={32: float(Lb['out_scale']), 33: float(Lb['out_zp']), 34: float(qm['logistic']['out_scale']), 35: float(qm['logistic']['out_zp'])})
-    info('q_ssd_decode_k', 0, n_anchors * (4 + cls_row + 24), 256)
+    B.decode(box_t, cls_t, Ls['box0'], Ls['cls0'], qm['logistic'], n_cls, n_anchors, cls_row)
     P.out_tensor = cls_t
     P.meta = dict(kind='ssd_mobilenet_v2_uint8', anchors=anchors, n_classes=n_cls, box_tensor=box_t, cls_tensor=cls_t, cls_row=cls_row,
                   feats=feats, quant=True, layer_tensors=layer_t)

@@ -1,5 +1,6 @@
 """Measurement helpers for bench.py: per-kernel device time from HIP events on the launch stream
 and the roofline line of the dominant kernel (algorithmic FLOPs / bytes come from the op program)."""
+import collections
 import ctypes
 import numpy as np
 
@@ -54,6 +55,50 @@ def net_op_variants(net):
     check(lib().dd_net_op_variants(net._h, ptr(codes), n, ctypes.byref(cnt)), 'dd_net_op_variants')
     return [None if not c else (c & 15, c >> 4 & 15, c >> 8 & 15, c >> 12 & 15, (c >> 16 & 15) * 16, c >> 20 & 15, c >> 24 & 127)
             for c in (int(v) for v in codes)]
+
+
+QConvV = collections.namedtuple('QConvV', 'kernel MQ ROWSUM NPF PIPE SPLIT Q16N merged magic add launches')
+QPwsV = collections.namedtuple('QPwsV', 'kernel K MW epi ROWSUM SAT merged')
+QDwV = collections.namedtuple('QDwV', 'kernel SAT magic chunks')
+QDwpwV = collections.namedtuple('QDwpwV', 'kernel CIN COUT STRIDE QTT form SAT chunks')
+QConv0V = collections.namedtuple('QConv0V', 'kernel HL SAT chunks')
+QOtherV = collections.namedtuple('QOtherV', 'kernel chunks')
+Q_EPI_NAMES = {0: 'q16', 1: 'rows'}
+Q_DWPW_FORMS = {0: 'plain', 1: 'rowsum', 2: 'hilo', 3: 'dup'}
+
+
+def q_variant(c):
+    """One dd_net_op_variants word of a uint8 op -> named tuple (include/deepdish_hip.h has the packing); None for 0."""
+    c = int(c)
+    k = c & 15
+    if k == 1:
+        return QConvV('q_conv_k', c >> 4 & 7, bool(c >> 7 & 1), c >> 8 & 7, bool(c >> 11 & 1), c >> 12 & 3, bool(c >> 14 & 1), bool(c >> 15 & 1),
+                      bool(c >> 16 & 1), bool(c >> 17 & 1), c >> 18 & 3)
+    if k == 2:
+        return QPwsV('q_pws_k', 512 * (c >> 4 & 3), c >> 6 & 7, Q_EPI_NAMES[c >> 9 & 3], bool(c >> 11 & 1), c >> 12 & 3, bool(c >> 14 & 1))
+    if k == 3:
+        return QDwV('q_dw_k', 0, False, c >> 8 & 255)
+    if k == 4:
+        return QDwV('q_dwm_k', c >> 4 & 1, bool(c >> 5 & 1), c >> 8 & 255)
+    if k == 5:
+        return QDwpwV('q_dwpw_k', 32 * (c >> 4 & 31), 64 * (c >> 9 & 15), c >> 13 & 3, 64 * (c >> 15 & 3), Q_DWPW_FORMS[c >> 17 & 3], c >> 19 & 3, c >> 21 & 127)
+    if k == 6:
+        return QConv0V('q_conv0_k', bool(c >> 4 & 1), c >> 5 & 3, c >> 8 & 255)
+    if k == 7:
+        return QOtherV('q_add_k', c >> 8 & 255)
+    if k == 8:
+        return QOtherV('q_ssd_decode_k', 1)
+    return None
+
+
+def q_op_variants(net):
+    """Per op of the last forward of a uint8 program: which kernel instantiation ran it, as a named tuple (QConvV, QPwsV, QDwV, QDwpwV,
+    QConv0V, QOtherV), or None for an op that launched nothing of its own (a row pipeline ran it, or the decode nobody asked for)."""
+    n = len(net.program.ops)
+    codes = np.zeros(n, dtype=np.int32)
+    cnt = ctypes.c_int(0)
+    check(lib().dd_net_op_variants(net._h, ptr(codes), n, ctypes.byref(cnt)), 'dd_net_op_variants')
+    return [q_variant(c) for c in codes]
 
 
 def launches_of(net, ms, batch):

@@ -393,8 +393,26 @@ int dd_net_op_launches(dd_net *net, int32_t *codes_host, int cap, int *n_ops_hos
 /* Which variant of the generic convolution launcher ran each op of the last forward (read-only, beside dd_net_op_launches, which reports 0
  * for all of them): WM | WN << 4 | MI << 8 | NI << 12 | (BK / 16) << 16 | mode << 20 | splitk << 24 -- the block tile is WM*MI*16 pixels x
  * WN*NI*16 channels in steps of BK along K; mode 0 / 1 / 2 = conv_glds_k with the general / pointwise / whole-tap fill, 3 = conv_mfma_k;
- * splitk = slices of the K axis (1 = none; > 1: conv_splitk_finish_k ran behind it).  0 for an op that took any other kernel. */
+ * splitk = slices of the K axis (1 = none; > 1: conv_splitk_finish_k ran behind it).  0 for an op that took any other kernel.
+ * Ops of a uint8 program (every one that launched; 0 for an op a row pipeline ran): bits 0..3 the kernel, the rest its template arguments --
+ *   1 q_conv_k:       MQ << 4 (3 bits) | ROWSUM << 7 | NPF << 8 (3 bits) | PIPE << 11 | SPLIT << 12 (2 bits) | Q16N << 14 | merged heads << 15 |
+ *                     magic-number division << 16 | residual ADD << 17 | launches << 18 (2 bits; 2: the merged op as one launch per predictor,
+ *                     the word then describes the second)
+ *   2 q_pws_k:        (K / 512) << 4 (2 bits) | MW << 6 (3 bits) | epilogue << 9 (2 bits: 0 bordered interleaved, 1 rows) | ROWSUM << 11 |
+ *                     SAT << 12 (2 bits) | merged heads << 14
+ *   3 q_dw_k:         launches << 8 (8 bits)
+ *   4 q_dwm_k:        SAT << 4 | magic-number division << 5 | frame chunks << 8 (8 bits, saturating)
+ *   5 q_dwpw_k:       (CIN / 32) << 4 (5 bits) | (COUT / 64) << 9 (4 bits) | STRIDE << 13 (2 bits) | (QTT / 64) << 15 (2 bits) |
+ *                     filter form << 17 (2 bits: 0 plain, 1 row sums, 2 hi + lo, 3 dup) | SAT << 19 (2 bits) | frame chunks << 21 (7 bits, saturating)
+ *   6 q_conv0_k:      HL << 4 | SAT << 5 (2 bits) | frame chunks << 8 (8 bits, saturating)
+ *   7 q_add_k:        frame chunks << 8 (8 bits, saturating)
+ *   8 q_ssd_decode_k
+ * SAT: 0 the layer's own clamp, 1 the byte range by saturating packs, 2 also both shifts <= 8 (q_dwm_k: 0 / 1). */
 int dd_net_op_variants(dd_net *net, int32_t *codes_host, int cap, int *n_ops_host);
+/* Host only (no device, no context): *fits_host = 1 when a uint8 MobileNet block (3x3 depthwise of `stride` + 1x1 cin -> cout, SAME padding)
+ * on an h x w source runs as one fused launch (OP_QDWPW) -- the launcher's own acceptance rule, asked by the program compiler so that it
+ * never emits a fused op that dd_net_forward would refuse.  split_filter: the pointwise filter is packed as hi + lo parts. */
+int dd_netq_dwpw_fits(int cin, int cout, int stride, int h, int w, int split_filter, int *fits_host);
 
 /* TFLite_Detection_PostProcess (inside the reference's .tflite graph, tools/ssd_mobilenet.py:103-109):
  * anchor decode, sigmoid, per-class NMS, top max_det.  raw f32 [n_anchors][4+n_classes] ->
