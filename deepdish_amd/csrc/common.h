@@ -150,6 +150,9 @@ int yuv420_to_bgr(hipStream_t s, const uint8_t *src, int batch, int H, int W, in
                   int64_t frame_stride, uint8_t *dst);
 // the same + cv2.flip(frame, 0) + INTER_LINEAR stretch of n dense frames in one launch: the bytes of yuv420_to_bgr then crop_resize
 int yuv420_resize(hipStream_t s, const uint8_t *src, int n, int H, int W, int layout, int flip, int oh, int ow, uint8_t *out);
+// packed 4:2:2 YUV -> BGR (yuv.hip); order 4 YUY2, 5 UYVY; pitch / frame_stride 0 = dense; and its convert + flip + stretch of n dense frames
+int yuv422_to_bgr(hipStream_t s, const uint8_t *src, int batch, int H, int W, int order, int pitch, int64_t frame_stride, uint8_t *dst);
+int yuv422_resize(hipStream_t s, const uint8_t *src, int n, int H, int W, int order, int flip, int oh, int ow, uint8_t *out);
 // the JPEG decoder's two halves (jpeg_dec.hip), as the ingest ring drives them: a header into a record with the status a decoder of h x w
 // gives it (returned too; the reason is left in dd_last_error), and upload + kernels for n records without a host wait
 int jpegdec_parse(const uint8_t *file, size_t n, int h, int w, dd_jpeg_info *rec);

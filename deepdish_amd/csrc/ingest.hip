@@ -13,6 +13,10 @@
 // (yuv420_resize_k), or, with DD_INGEST_YUV_FUSED=0, as convert-into-a-staging-buffer then crop_resize (the same bytes, for A/B runs).
 // The consumer always receives BGR.
 //
+// A slot may also hold packed 4:2:2 YUV, what a UVC / V4L2 camera (YUY2) or a capture card (UYVY) delivers raw: 2 bytes per pixel, any
+// height, an even width.  The same three forms on the copy stream: yuv422_to_bgr straight into the slot's output without a transform,
+// yuv422_resize_k fused, or with DD_INGEST_YUV_FUSED=0 convert-into-the-staging-buffer then crop_resize.
+//
 // A slot may also hold baseline JPEG files, what a camera or the reference's frame_%06d.jpg sequence delivers (a tenth or less of the raw
 // bytes): put() copies a stream's file into the slot's pinned arena and parses its header on the calling thread, submit() uploads the
 // bytes in use and the records and decodes on the copy stream (csrc/jpeg_dec.hip) -- into the slot's output, or into a staging buffer
@@ -26,7 +30,7 @@
 struct dd_ingest {
     dd_ctx *ctx = nullptr;
     int slots = 0, S = 0, sh = 0, sw = 0, dh = 0, dw = 0, flip = 0;
-    int format = 0;                         // 0 BGR, 1 NV12, 2 I420, 3 JPEG files
+    int format = 0;                         // 0 BGR, 1 NV12, 2 I420, 3 JPEG files, 4 YUY2, 5 UYVY
     bool transform = false, own_out = false, fused = true;
     uint8_t *d_stage = nullptr;             // YUV, two-launch form only: the converted BGR frames [S][sh][sw][3]
     hipStream_t copy = nullptr;
@@ -45,16 +49,22 @@ struct dd_ingest {
     std::mutex mu;
 };
 
-constexpr int INGEST_JPEG = 3;
+constexpr int INGEST_JPEG = 3, INGEST_YUY2 = 4, INGEST_UYVY = 5;
+static bool ingest_is_422(int format) { return format == INGEST_YUY2 || format == INGEST_UYVY; }
 
 static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip,
                          int pixel_format, dd_ingest **out, size_t jpeg_slot_bytes = 0) {
     DD_REQUIRE(ctx && out && slots > 0 && n_streams > 0 && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0, DD_E_ARG,
                "%s: bad argument", who);
-    DD_REQUIRE((pixel_format >= 0 && pixel_format <= 2) || (pixel_format == INGEST_JPEG && jpeg_slot_bytes), DD_E_ARG, "%s: pixel_format %d is none of 0 (BGR), 1 (NV12), 2 (I420)", who, pixel_format);
+    DD_REQUIRE((pixel_format >= 0 && pixel_format <= 2) || ingest_is_422(pixel_format) || (pixel_format == INGEST_JPEG && jpeg_slot_bytes), DD_E_ARG,
+               "%s: pixel_format %d is none of 0 (BGR), 1 (NV12), 2 (I420), 4 (YUY2), 5 (UYVY)", who, pixel_format);
     if (pixel_format == 1 || pixel_format == 2) {
         DD_REQUIRE(src_w % 2 == 0, DD_E_ARG, "%s: src_w %d must be even for 4:2:0 frames", who, src_w);
         DD_REQUIRE(src_h % 2 == 0, DD_E_ARG, "%s: src_h %d must be even for 4:2:0 frames", who, src_h);
+        DD_REQUIRE(n_streams <= 65535, DD_E_ARG, "%s: n_streams %d above 65535", who, n_streams);
+    }
+    if (ingest_is_422(pixel_format)) {
+        DD_REQUIRE(src_w % 2 == 0, DD_E_ARG, "%s: src_w %d must be even for 4:2:2 frames", who, src_w);
         DD_REQUIRE(n_streams <= 65535, DD_E_ARG, "%s: n_streams %d above 65535", who, n_streams);
     }
     DD_HIP(hipSetDevice(ctx->device));
@@ -65,6 +75,7 @@ static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams,
     g->format = pixel_format;
     g->raw_bytes = pixel_format ? (size_t)n_streams * src_h * src_w * 3 / 2 : (size_t)n_streams * src_h * src_w * 3;
     if (pixel_format == INGEST_JPEG) g->raw_bytes = jpeg_slot_bytes;
+    if (ingest_is_422(pixel_format)) g->raw_bytes = (size_t)n_streams * src_h * src_w * 2;
     g->own_out = g->transform || pixel_format != 0;          // BGR without a transform: the uploaded frames are the output
     g->fused = !(getenv("DD_INGEST_YUV_FUSED") && atoi(getenv("DD_INGEST_YUV_FUSED")) == 0);
     if (pixel_format == INGEST_JPEG) g->fused = false;      // decode into the staging buffer, then crop_resize
@@ -231,13 +242,19 @@ int dd_ingest_submit(dd_ingest *g, int slot) {
     if (g->used[slot]) DD_HIP(hipStreamWaitEvent(g->copy, g->done[slot], 0));       // the previous consumer of this slot
     DD_HIP(hipMemcpyAsync(g->d_raw[slot], g->h_raw[slot], g->raw_bytes, hipMemcpyHostToDevice, g->copy));
     if (g->format) {
+        const bool packed = ingest_is_422(g->format);
+        auto convert = [&](uint8_t *dst) {
+            return packed ? ddk::yuv422_to_bgr(g->copy, g->d_raw[slot], g->S, g->sh, g->sw, g->format, 0, 0, dst)
+                          : ddk::yuv420_to_bgr(g->copy, g->d_raw[slot], g->S, g->sh, g->sw, g->format, 0, 0, 0, dst);
+        };
         int rc;
         if (!g->transform) {                                    // the converter writes straight into the slot's output
-            rc = ddk::yuv420_to_bgr(g->copy, g->d_raw[slot], g->S, g->sh, g->sw, g->format, 0, 0, 0, g->d_out[slot]);
+            rc = convert(g->d_out[slot]);
         } else if (g->fused) {
-            rc = ddk::yuv420_resize(g->copy, g->d_raw[slot], g->S, g->sh, g->sw, g->format, g->flip, g->dh, g->dw, g->d_out[slot]);
+            rc = packed ? ddk::yuv422_resize(g->copy, g->d_raw[slot], g->S, g->sh, g->sw, g->format, g->flip, g->dh, g->dw, g->d_out[slot])
+                        : ddk::yuv420_resize(g->copy, g->d_raw[slot], g->S, g->sh, g->sw, g->format, g->flip, g->dh, g->dw, g->d_out[slot]);
         } else {                                                // one staging buffer serves every slot: the copy stream runs them in order
-            rc = ddk::yuv420_to_bgr(g->copy, g->d_raw[slot], g->S, g->sh, g->sw, g->format, 0, 0, 0, g->d_stage);
+            rc = convert(g->d_stage);
             if (rc == DD_OK) rc = ddk::crop_resize(g->copy, g->d_stage, g->sh, g->sw, g->d_boxes, g->S, g->dh, g->dw, g->d_out[slot]);
         }
         if (rc != DD_OK) return rc;

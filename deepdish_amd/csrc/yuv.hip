@@ -5,13 +5,20 @@
 // it is unpinned like every other cv2 arithmetic here; tests/yuv_ref.py is the numpy restatement the kernels are held to bit for bit.
 //   NV12: H rows of luma, then H/2 rows of interleaved U,V pairs.   I420: H rows of luma, then the U plane, then the V plane.
 // The chroma sample of pixel (x, y) is that of block (x >> 1, y >> 1): no chroma interpolation.
+//
+// Packed 4:2:2 (YUY2 / UYVY), what a UVC / V4L2 camera or a capture card delivers raw, with the same per-pixel arithmetic:
+//   * yuv422_to_bgr_k   cv2.cvtColor(frame, COLOR_YUV2BGR_YUY2 / COLOR_YUV2BGR_UYVY); tests/yuv422_ref.py is its definition
+//   * yuv422_resize_k   convert + flip + resize in one launch, the lane of yuv420_resize_k over another tap fetch
+//   A row of W pixels is 2 W bytes of 4-byte macropixels, YUY2: Y0 U Y1 V, UYVY: U Y0 V Y1; both pixels of a macropixel share its chroma,
+//   every row carries its own (H may be odd).
+#include <climits>
 #include <cstdlib>
 #include "common.h"
 #include "resize_dev.h"
 
 namespace {
 
-constexpr int YUV_NV12 = 1, YUV_I420 = 2;
+constexpr int YUV_NV12 = 1, YUV_I420 = 2, YUV_YUY2 = 4, YUV_UYVY = 5;      // the ingest ring's pixel_format codes (3 is its JPEG ring)
 constexpr int YUV_SHIFT = 20;
 constexpr int YUV_CY = 1220542, YUV_CVR = 1673527, YUV_CVG = -852492, YUV_CUG = -409993, YUV_CUB = 2116026;
 // rounding term and the -128 of both chroma samples folded into one constant per channel: R = (c + CVR * V + KR) >> 20 ...
@@ -173,18 +180,56 @@ __device__ __forceinline__ void yuv_tap_pair(const uint8_t *__restrict__ f, int 
     t1 = second ? yuv_bgr(Y1, U1, V1) : t0;
 }
 
+// The taps of a dense NV12 / I420 frame at `f`.
+template <int LAYOUT>
+struct Yuv420Taps {
+    const uint8_t *__restrict__ f;
+    int H, W;
+    __device__ __forceinline__ void operator()(int r, int sx, bool second, uint32_t &t0, uint32_t &t1) const {
+        yuv_tap_pair<LAYOUT>(f, H, W, r, sx, second, t0, t1);
+    }
+};
+
+// Macropixel word (little-endian load of its four bytes) -> its samples.
+template <int ORDER> __device__ __forceinline__ int yuv422_y0(uint32_t w) { return (int)((ORDER == YUV_YUY2 ? w : w >> 8) & 255u); }
+template <int ORDER> __device__ __forceinline__ int yuv422_y1(uint32_t w) { return (int)((ORDER == YUV_YUY2 ? w >> 16 : w >> 24) & 255u); }
+template <int ORDER> __device__ __forceinline__ int yuv422_u(uint32_t w) { return (int)((ORDER == YUV_YUY2 ? w >> 8 : w) & 255u); }
+template <int ORDER> __device__ __forceinline__ int yuv422_v(uint32_t w) { return (int)((ORDER == YUV_YUY2 ? w >> 24 : w >> 16) & 255u); }
+
+// The taps of a dense YUY2 / UYVY frame at `f` (rows of 2 W bytes): pixels sx and sx + 1 are one macropixel when sx is even, else the second
+// half of one and the first half of the next -- which the row has whenever pixel sx + 1 exists (W is even).  Never a byte past the row.
+template <int ORDER>
+struct Yuv422Taps {
+    const uint8_t *__restrict__ f;
+    int W;
+    __device__ __forceinline__ void operator()(int r, int sx, bool second, uint32_t &t0, uint32_t &t1) const {
+        const uint8_t *mp = f + (size_t)r * (2 * (size_t)W) + 4 * (size_t)(sx >> 1);
+        const uint32_t w0 = *reinterpret_cast<const u32u *>(mp);
+        const int U0 = yuv422_u<ORDER>(w0), V0 = yuv422_v<ORDER>(w0);
+        if (!(sx & 1)) {
+            t0 = yuv_bgr(yuv422_y0<ORDER>(w0), U0, V0);
+            t1 = second ? yuv_bgr(yuv422_y1<ORDER>(w0), U0, V0) : t0;
+        } else {
+            t0 = yuv_bgr(yuv422_y1<ORDER>(w0), U0, V0);
+            if (second) {
+                const uint32_t w1 = *reinterpret_cast<const u32u *>(mp + 4);
+                t1 = yuv_bgr(yuv422_y0<ORDER>(w1), yuv422_u<ORDER>(w1), yuv422_v<ORDER>(w1));
+            } else t1 = t0;
+        }
+    }
+};
+
 // Convert + flip + stretch of whole dense frames: every source tap is converted to saturated BGR bytes first, then the arithmetic of
 // crop_resize_k / crop_resize4_k (image.hip) runs on those bytes -- lin_coeff, 11-bit coefficients, the exact-2x INTER_AREA shortcut --
-// so the result is what yuv420_to_bgr_k followed by crop_resize gives, byte for byte, without the BGR frame ever reaching HBM.
+// so the result is what the stand-alone converter followed by crop_resize gives, byte for byte, without the BGR frame ever reaching HBM.
 // grid (ceil(oh * (ow / NPX) / 256), n); a lane owns NPX (4: ow % 4 == 0, twelve bytes leave as three dwords; or 1) output pixels of a row.
-template <int LAYOUT, int NPX>
-__global__ __launch_bounds__(256) void yuv420_resize_k(const uint8_t *__restrict__ src, int H, int W, int flip, int oh, int ow,
-                                                       uint8_t *__restrict__ out) {
+// `tap(r, sx, second, t0, t1)` gives pixels (sx, r) and (sx + 1, r) of frame blockIdx.y, converted; `out` is [n][oh][ow][3].
+template <int NPX, class Taps>
+__device__ __forceinline__ void yuv_resize_lane(const Taps &tap, int H, int W, int flip, int oh, int ow, uint8_t *__restrict__ out) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
     const int qpr = ow / NPX;
     if (q >= oh * qpr) return;
     const int dy = q / qpr, dx0 = (q - dy * qpr) * NPX;
-    const uint8_t *f = src + (size_t)blockIdx.y * ((size_t)H * W * 3 / 2);
     uint8_t *o = out + (((size_t)blockIdx.y * oh + dy) * ow + dx0) * 3;
     const bool area = W == 2 * ow && H == 2 * oh;                // exact 2x decimation: INTER_AREA shortcut
     int sy, ya0 = 0, ya1 = 0, sy1;
@@ -200,8 +245,8 @@ __global__ __launch_bounds__(256) void yuv420_resize_k(const uint8_t *__restrict
         if (area) sx = 2 * (dx0 + i);
         else { lin_coeff(dx0 + i, ow, W, sx, xa0, xa1); second = sx + 1 <= W - 1; }      // at the right edge both taps are pixel sx
         uint32_t t00, t01, t10, t11;
-        yuv_tap_pair<LAYOUT>(f, H, W, r0, sx, second, t00, t01);
-        yuv_tap_pair<LAYOUT>(f, H, W, r1, sx, second, t10, t11);
+        tap(r0, sx, second, t00, t01);
+        tap(r1, sx, second, t10, t11);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const int p00 = (int)((t00 >> (8 * c)) & 255u), p01 = (int)((t01 >> (8 * c)) & 255u);
@@ -224,6 +269,67 @@ __global__ __launch_bounds__(256) void yuv420_resize_k(const uint8_t *__restrict
             ow32[w] = (uint32_t)b[4 * w] | ((uint32_t)b[4 * w + 1] << 8) | ((uint32_t)b[4 * w + 2] << 16) | ((uint32_t)b[4 * w + 3] << 24);
     } else {
         o[0] = px[0][0]; o[1] = px[0][1]; o[2] = px[0][2];
+    }
+}
+
+template <int LAYOUT, int NPX>
+__global__ __launch_bounds__(256) void yuv420_resize_k(const uint8_t *__restrict__ src, int H, int W, int flip, int oh, int ow,
+                                                       uint8_t *__restrict__ out) {
+    const Yuv420Taps<LAYOUT> tap{src + (size_t)blockIdx.y * ((size_t)H * W * 3 / 2), H, W};
+    yuv_resize_lane<NPX>(tap, H, W, flip, oh, ow, out);
+}
+
+template <int ORDER, int NPX>
+__global__ __launch_bounds__(256) void yuv422_resize_k(const uint8_t *__restrict__ src, int H, int W, int flip, int oh, int ow,
+                                                       uint8_t *__restrict__ out) {
+    const Yuv422Taps<ORDER> tap{src + (size_t)blockIdx.y * ((size_t)H * W * 2), W};
+    yuv_resize_lane<NPX>(tap, H, W, flip, oh, ow, out);
+}
+
+// grid (ceil(items / 256), batch).  WIDE: W % 16 == 0 and every row of both sides 16-byte aligned (the launcher checks) -- an item is 16
+// pixels of one row: two 16-byte loads (eight macropixels), three 16-byte stores; 5 bytes of traffic per pixel and nothing else.
+// Otherwise an item is one macropixel, byte by byte: any even W.  Rows and frames are addressed in 64 bits.
+template <int ORDER, bool WIDE>
+__global__ __launch_bounds__(256) void yuv422_to_bgr_k(const uint8_t *__restrict__ src, int H, int W, int pitch, int64_t frame_stride,
+                                                       uint8_t *__restrict__ dst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int ipr = WIDE ? W >> 4 : W >> 1;                      // items per row
+    if (i >= H * ipr) return;
+    const int y = i / ipr, bx = i - y * ipr;
+    const uint8_t *row = src + (size_t)blockIdx.y * (size_t)frame_stride + (size_t)y * (size_t)pitch;
+    uint8_t *o = dst + (((size_t)blockIdx.y * H + y) * W) * 3;
+    if constexpr (WIDE) {
+        const u4v *sp = reinterpret_cast<const u4v *>(row + 32 * (size_t)bx);
+        const u4v m0 = sp[0], m1 = sp[1];
+        int val[48];                                             // the 48 output values before the shift, in byte order
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t w = k < 4 ? m0[k & 3] : m1[k & 3];
+            const YuvChroma t = yuv_chroma(yuv422_u<ORDER>(w), yuv422_v<ORDER>(w));
+            const int c0 = yuv_luma(yuv422_y0<ORDER>(w)), c1 = yuv_luma(yuv422_y1<ORDER>(w));
+            val[6 * k] = c0 + t.b; val[6 * k + 1] = c0 + t.g; val[6 * k + 2] = c0 + t.r;
+            val[6 * k + 3] = c1 + t.b; val[6 * k + 4] = c1 + t.g; val[6 * k + 5] = c1 + t.r;
+        }
+        u4v *op = reinterpret_cast<u4v *>(o + 48 * (size_t)bx);
+#pragma unroll
+        for (int w = 0; w < 3; ++w) {
+            u4v q;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int b = 16 * w + 4 * j;
+                q[j] = yuv_pack4(val[b], val[b + 1], val[b + 2], val[b + 3]);
+            }
+            op[w] = q;
+        }
+    } else {
+        const uint8_t *mp = row + 4 * (size_t)bx;
+        const uint32_t w = (uint32_t)mp[0] | ((uint32_t)mp[1] << 8) | ((uint32_t)mp[2] << 16) | ((uint32_t)mp[3] << 24);
+        const YuvChroma t = yuv_chroma(yuv422_u<ORDER>(w), yuv422_v<ORDER>(w));
+        const int c0 = yuv_luma(yuv422_y0<ORDER>(w)), c1 = yuv_luma(yuv422_y1<ORDER>(w));
+        const uint32_t p0 = yuv_pack4(c0 + t.b, c0 + t.g, c0 + t.r, 0), p1 = yuv_pack4(c1 + t.b, c1 + t.g, c1 + t.r, 0);
+        uint8_t *q = o + 6 * (size_t)bx;
+        q[0] = (uint8_t)p0; q[1] = (uint8_t)(p0 >> 8); q[2] = (uint8_t)(p0 >> 16);
+        q[3] = (uint8_t)p1; q[4] = (uint8_t)(p1 >> 8); q[5] = (uint8_t)(p1 >> 16);
     }
 }
 
@@ -269,6 +375,41 @@ int yuv420_resize(hipStream_t s, const uint8_t *src, int n, int H, int W, int la
     return DD_OK;
 }
 
+// order 4 YUY2, 5 UYVY; pitch / frame_stride 0 = dense (see dd_yuv422_to_bgr).  The caller has checked order, sizes and pitch.
+int yuv422_to_bgr(hipStream_t s, const uint8_t *src, int batch, int H, int W, int order, int pitch, int64_t frame_stride, uint8_t *dst) {
+    if (batch <= 0) return DD_OK;
+    if (pitch == 0) pitch = 2 * W;
+    if (frame_stride == 0) frame_stride = (int64_t)pitch * H;
+    const bool wide = W % 16 == 0 && pitch % 16 == 0 && frame_stride % 16 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
+                      (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+    const dim3 grid(dd_ceil_div(H * (wide ? W / 16 : W / 2), 256), batch), block(256);
+    if (order == YUV_YUY2) {
+        if (wide) hipLaunchKernelGGL((yuv422_to_bgr_k<YUV_YUY2, true>), grid, block, 0, s, src, H, W, pitch, frame_stride, dst);
+        else hipLaunchKernelGGL((yuv422_to_bgr_k<YUV_YUY2, false>), grid, block, 0, s, src, H, W, pitch, frame_stride, dst);
+    } else {
+        if (wide) hipLaunchKernelGGL((yuv422_to_bgr_k<YUV_UYVY, true>), grid, block, 0, s, src, H, W, pitch, frame_stride, dst);
+        else hipLaunchKernelGGL((yuv422_to_bgr_k<YUV_UYVY, false>), grid, block, 0, s, src, H, W, pitch, frame_stride, dst);
+    }
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
+// n dense frames [H][W][2] -> BGR [n][oh][ow][3], rows read bottom-up when `flip`.
+int yuv422_resize(hipStream_t s, const uint8_t *src, int n, int H, int W, int order, int flip, int oh, int ow, uint8_t *out) {
+    if (n <= 0) return DD_OK;
+    const bool quad = ow % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0;
+    const dim3 grid(dd_ceil_div(oh * (quad ? ow / 4 : ow), 256), n), block(256);
+    if (order == YUV_YUY2) {
+        if (quad) hipLaunchKernelGGL((yuv422_resize_k<YUV_YUY2, 4>), grid, block, 0, s, src, H, W, flip, oh, ow, out);
+        else hipLaunchKernelGGL((yuv422_resize_k<YUV_YUY2, 1>), grid, block, 0, s, src, H, W, flip, oh, ow, out);
+    } else {
+        if (quad) hipLaunchKernelGGL((yuv422_resize_k<YUV_UYVY, 4>), grid, block, 0, s, src, H, W, flip, oh, ow, out);
+        else hipLaunchKernelGGL((yuv422_resize_k<YUV_UYVY, 1>), grid, block, 0, s, src, H, W, flip, oh, ow, out);
+    }
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
 }  // namespace ddk
 
 extern "C" {
@@ -293,6 +434,26 @@ int dd_yuv420_to_bgr(dd_ctx *ctx, const uint8_t *src, int batch, int H, int W, i
     if (batch == 0) return DD_OK;
     DD_REQUIRE(src && dst, DD_E_ARG, "dd_yuv420_to_bgr: NULL argument");
     return ddk::yuv420_to_bgr(dd_pick_stream(ctx, stream), src, batch, H, W, layout, pitch, chroma_offset, frame_stride, dst);
+}
+
+// Every argument is checked before ctx is touched: a bad call is answered with a code on a machine without a GPU.
+int dd_yuv422_to_bgr(dd_ctx *ctx, const uint8_t *src, int batch, int H, int W, int order, int pitch, int64_t frame_stride, uint8_t *dst,
+                     void *stream) {
+    DD_REQUIRE(order == YUV_YUY2 || order == YUV_UYVY, DD_E_ARG, "dd_yuv422_to_bgr: order %d is neither 4 (YUY2) nor 5 (UYVY)", order);
+    DD_REQUIRE(batch >= 0 && batch <= 65535, DD_E_ARG, "dd_yuv422_to_bgr: batch %d outside 0..65535", batch);
+    DD_REQUIRE(W >= 2 && W % 2 == 0, DD_E_ARG, "dd_yuv422_to_bgr: W %d must be even and positive (4:2:2 macropixels)", W);
+    DD_REQUIRE(H >= 1, DD_E_ARG, "dd_yuv422_to_bgr: H %d must be positive", H);
+    DD_REQUIRE((int64_t)H * (W / 2) <= INT_MAX - 256, DD_E_ARG, "dd_yuv422_to_bgr: H %d x W %d is more macropixels than a launch indexes", H, W);
+    DD_REQUIRE(pitch == 0 || pitch >= 2 * (int64_t)W, DD_E_ARG, "dd_yuv422_to_bgr: pitch %d below 2 W = %lld", pitch, 2 * (long long)W);
+    const int64_t p = pitch ? pitch : 2 * (int64_t)W, extent = p * (H - 1) + 2 * (int64_t)W;
+    DD_REQUIRE(p <= INT_MAX, DD_E_ARG, "dd_yuv422_to_bgr: W %d needs a pitch above INT_MAX", W);
+    DD_REQUIRE(frame_stride == 0 || frame_stride >= extent, DD_E_ARG, "dd_yuv422_to_bgr: frame_stride %lld below a frame's %lld bytes",
+               (long long)frame_stride, (long long)extent);
+    DD_REQUIRE(ctx, DD_E_ARG, "dd_yuv422_to_bgr: NULL ctx");
+    DD_DEVICE(ctx);
+    if (batch == 0) return DD_OK;
+    DD_REQUIRE(src && dst, DD_E_ARG, "dd_yuv422_to_bgr: NULL argument");
+    return ddk::yuv422_to_bgr(dd_pick_stream(ctx, stream), src, batch, H, W, order, pitch, frame_stride, dst);
 }
 
 }  // extern "C"

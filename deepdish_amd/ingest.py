@@ -9,6 +9,11 @@ With `pixel_format='nv12'` or `'i420'` a slot holds what a decoder produces itse
 cross the host link, and the conversion to BGR (csrc/yuv.hip, OpenCV's BT.601 fixed-point arithmetic restated) runs on the copy
 stream in front of the flip + resize.  `yuv420_to_bgr` is the same conversion for frames that are already in device memory.
 
+With `pixel_format='yuy2'` or `'uyvy'` a slot holds packed 4:2:2, what a UVC / V4L2 camera (YUY2: Y0 U Y1 V) or an SDI / HDMI capture card
+(UYVY: U Y0 V Y1) delivers raw: 2 bytes per pixel, two thirds of BGR, converted with the same arithmetic (cv2.cvtColor COLOR_YUV2BGR_YUY2 /
+_UYVY restated; tests/yuv422_ref.py is the definition, parity with OpenCV itself is unpinned).  `yuv422_to_bgr` is that conversion for
+frames already in device memory.
+
 With `pixel_format='jpeg'` a slot holds baseline JPEG files, what an IP camera's MJPEG stream or the reference's frame_%06d.jpg sequence
 (--input-cvat-dir) delivers -- a tenth or less of the raw bytes: `put(slot, stream, file)` copies a file into the slot's pinned arena and
 parses its header on the calling thread, `submit(slot)` uploads the bytes in use and decodes on the copy stream (csrc/jpeg_dec.hip,
@@ -19,22 +24,26 @@ import numpy as np
 from ._lib import lib, check, P
 from .runtime import default_context, ptr
 
-PIXEL_FORMATS = {'bgr': 0, 'nv12': 1, 'i420': 2, 'jpeg': 3}
+PIXEL_FORMATS = {'bgr': 0, 'nv12': 1, 'i420': 2, 'jpeg': 3, 'yuy2': 4, 'uyvy': 5}
+PACKED_422 = ('yuy2', 'uyvy')
 
 
 class FrameIngest:
     def __init__(self, n_streams, src_size, dst_size=None, slots=2, flip=False, context=None, pixel_format='bgr', jpeg_slot_bytes=None):
         """src_size / dst_size: (width, height) like the reference's `input_size`; dst defaults to src.
-        pixel_format: what a slot holds, 'bgr' | 'nv12' | 'i420' (YUV needs an even width and height) | 'jpeg'; the consumer always gets
-        BGR.  jpeg_slot_bytes: the size of a JPEG slot's arena, by default n_streams * width * height * 3 // 8."""
+        pixel_format: what a slot holds, 'bgr' | 'nv12' | 'i420' (4:2:0 needs an even width and height) | 'yuy2' | 'uyvy' (packed 4:2:2,
+        named by FOURCC: an even width, any height) | 'jpeg'; the consumer always gets BGR.  jpeg_slot_bytes: the size of a JPEG slot's arena, by default n_streams * width * height * 3 // 8."""
         self._h = None
         if pixel_format not in PIXEL_FORMATS:
-            raise ValueError("pixel_format %r is none of 'bgr', 'nv12', 'i420', 'jpeg'" % (pixel_format,))
+            raise ValueError("pixel_format %r is none of 'bgr', 'nv12', 'i420', 'yuy2', 'uyvy', 'jpeg'%s"
+                             % (pixel_format, " (packed Y0 U Y1 V is spelt 'yuy2', its FOURCC)" if pixel_format == 'yuyv' else ''))
         self.pixel_format = pixel_format
         self.sw, self.sh = src_size
         self.dw, self.dh = dst_size or src_size
         if pixel_format in ('nv12', 'i420') and (self.sw % 2 or self.sh % 2):
             raise ValueError('%s frames need an even width and height, got %dx%d' % (pixel_format, self.sw, self.sh))
+        if pixel_format in PACKED_422 and self.sw % 2:
+            raise ValueError('%s frames need an even width, got %dx%d' % (pixel_format, self.sw, self.sh))
         self.ctx = context or default_context()
         self.S, self.slots = int(n_streams), int(slots)
         h = P()
@@ -54,7 +63,12 @@ class FrameIngest:
             p, n = ctypes.c_void_p(), ctypes.c_int64()
             check(lib().dd_ingest_host_slot(self._h, i, ctypes.byref(p), ctypes.byref(n)), 'dd_ingest_host_slot')
             buf = (ctypes.c_uint8 * n.value).from_address(p.value)
-            shape = (self.S, self.sh, self.sw, 3) if pixel_format == 'bgr' else (self.S, self.sh * 3 // 2, self.sw)
+            if pixel_format == 'bgr':
+                shape = (self.S, self.sh, self.sw, 3)
+            elif pixel_format in PACKED_422:
+                shape = (self.S, self.sh, self.sw, 2)
+            else:
+                shape = (self.S, self.sh * 3 // 2, self.sw)
             self._host.append(np.frombuffer(buf, dtype=np.uint8).reshape(shape))
 
     def __del__(self):
@@ -67,8 +81,8 @@ class FrameIngest:
             pass
 
     def host(self, slot):
-        """Pinned numpy view of a slot, [S, src_h, src_w, 3] for BGR and [S, src_h * 3 // 2, src_w] for NV12 / I420 (the shape cv2 gives
-        such frames): fill it, then submit(slot).  Blocks until the slot's previous upload has left the host buffer."""
+        """Pinned numpy view of a slot, [S, src_h, src_w, 3] for BGR, [S, src_h * 3 // 2, src_w] for NV12 / I420 and [S, src_h, src_w, 2]
+        for YUY2 / UYVY (the shapes cv2 gives such frames): fill it, then submit(slot).  Blocks until the slot's previous upload has left the host buffer."""
         if self.pixel_format == 'jpeg':
             raise ValueError("a 'jpeg' ring has no raw slot to fill: hand each stream's file to put(slot, stream, data)")
         check(lib().dd_ingest_wait_uploaded(self._h, slot), 'dd_ingest_wait_uploaded')
@@ -146,4 +160,33 @@ def yuv420_to_bgr(src, height, width, layout, pitch=0, chroma_offset=0, frame_st
         raise ValueError('src holds %d bytes, %d frames need %d' % (src.numel(), batch, (batch - 1) * stride + extent))
     check(lib().dd_yuv420_to_bgr(ctx.handle, ptr(src), batch, height, width, PIXEL_FORMATS[layout], pitch, chroma_offset, frame_stride,
                                  ptr(out), stream), 'dd_yuv420_to_bgr')
+    return out
+
+
+def yuv422_to_bgr(src, height, width, order, pitch=0, frame_stride=0, out=None, context=None, stream=None):
+    """Packed 4:2:2 frames in device memory -> u8 [batch, height, width, 3] BGR device tensor (cv2.cvtColor COLOR_YUV2BGR_YUY2 / _UYVY
+    restated).  order: 'yuy2' (Y0 U Y1 V) or 'uyvy' (U Y0 V Y1).  src: u8 device tensor, [batch, height, width, 2] when dense; padded
+    surfaces are described by pitch (bytes per row, 0 = 2 * width) and frame_stride (0 = pitch * height) -- the batch is then what
+    fits.  out: a tensor to write into (the batch is then its first dimension).  The launch is queued on the context's stream (or
+    `stream`): `context.sync()` before torch reads the result on another stream."""
+    import torch
+    if order not in PACKED_422:
+        raise ValueError("order %r is neither 'yuy2' nor 'uyvy'" % (order,))
+    ctx = context or default_context()
+    p = pitch or 2 * width
+    extent = p * (height - 1) + 2 * width
+    stride = frame_stride or p * height
+    if out is not None:
+        batch = out.shape[0]
+    else:
+        batch = max(0, (src.numel() - extent) // stride + 1)
+        out = torch.empty((batch, height, width, 3), dtype=torch.uint8, device=src.device)
+    if tuple(out.shape[1:]) != (height, width, 3) or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError('out must be a contiguous u8 [batch, %d, %d, 3] tensor' % (height, width))
+    if src.dtype != torch.uint8 or not src.is_contiguous():
+        raise ValueError('src must be a contiguous u8 tensor')
+    if batch > 0 and src.numel() < (batch - 1) * stride + extent:
+        raise ValueError('src holds %d bytes, %d frames need %d' % (src.numel(), batch, (batch - 1) * stride + extent))
+    check(lib().dd_yuv422_to_bgr(ctx.handle, ptr(src), batch, height, width, PIXEL_FORMATS[order], pitch, frame_stride, ptr(out), stream),
+          'dd_yuv422_to_bgr')
     return out

@@ -143,3 +143,26 @@ def to_yuv420(frame_bgr, layout):
         c = out[H:].reshape(2, H // 2, W // 2)
         c[0], c[1] = cu, cv
     return out
+
+
+def to_yuv422(frame_bgr, order):
+    """BGR u8 [H, W, 3] (W even) -> packed 4:2:2 u8 [H, W, 2], the shape cv2 gives such frames; order 'yuy2' (Y0 U Y1 V) or 'uyvy'
+    (U Y0 V Y1).  For synthetic inputs only: the float forward transform of to_yuv420 with chroma averaged over each horizontal pair --
+    it pins nothing."""
+    if order not in ('yuy2', 'uyvy'):
+        raise ValueError("order %r is neither 'yuy2' nor 'uyvy'" % (order,))
+    f = np.asarray(frame_bgr, dtype=np.float64)
+    H, W = f.shape[:2]
+    if W % 2 or f.shape[2:] != (3,):
+        raise ValueError('to_yuv422 needs a BGR frame of even width, got %r' % (f.shape,))
+    b, g, r = f[..., 0], f[..., 1], f[..., 2]
+    y = 16.0 + (65.481 * r + 128.553 * g + 24.966 * b) / 255.0
+    u = 128.0 + (-37.797 * r - 74.203 * g + 112.0 * b) / 255.0
+    v = 128.0 + (112.0 * r - 93.786 * g - 18.214 * b) / 255.0
+    sub = lambda p: p.reshape(H, W // 2, 2).mean(axis=2)
+    q = lambda p: np.clip(np.rint(p), 0, 255).astype(np.uint8)
+    out = np.empty((H, W, 2), dtype=np.uint8)
+    luma, chroma = (0, 1) if order == 'yuy2' else (1, 0)
+    out[..., luma] = q(y)
+    out[:, 0::2, chroma], out[:, 1::2, chroma] = q(sub(u)), q(sub(v))
+    return out

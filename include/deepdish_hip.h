@@ -280,6 +280,15 @@ int dd_resize_bilinear(dd_ctx *ctx, const uint8_t *src, int H, int W, int c,
  * DD_E_ARG (the message names the argument) for another layout, an odd or non-positive size, a pitch below W. */
 int dd_yuv420_to_bgr(dd_ctx *ctx, const uint8_t *src, int batch, int H, int W, int layout, int pitch, int64_t chroma_offset,
                      int64_t frame_stride, uint8_t *dst, void *stream);
+/* Packed 4:2:2 YUV -> BGR: cv2.cvtColor(frame, COLOR_YUV2BGR_YUY2 / COLOR_YUV2BGR_UYVY) for frames already on the device, what a UVC / V4L2
+ * camera (YUY2) or an SDI / HDMI capture card (UYVY) delivers raw.  Per pixel the arithmetic of dd_yuv420_to_bgr (tests/yuv422_ref.py is the
+ * definition; parity with OpenCV itself is unpinned, the library is absent).  A row of W pixels (W even) is 2 W bytes of 4-byte macropixels,
+ * order 4 = YUY2: Y0 U Y1 V, order 5 = UYVY: U Y0 V Y1; the two pixels of a macropixel share its chroma, no interpolation, no vertical
+ * sub-sampling (H may be odd).  pitch: bytes per row, 0 = 2 W.  frame_stride: bytes between frames, 0 = dense (pitch * H).
+ * dst: u8 dense [batch][H][W][3] BGR.  DD_E_ARG (the message names the argument) for another order, an odd or non-positive W, a non-positive
+ * H, a pitch below 2 W; the arguments are checked before ctx is used. */
+int dd_yuv422_to_bgr(dd_ctx *ctx, const uint8_t *src, int batch, int H, int W, int order, int pitch, int64_t frame_stride, uint8_t *dst,
+                     void *stream);
 
 /* ---------------------------------------------------------------- frame ingest
  * The CPU side of Pipeline.capture (deepdish.py:837-878): cv2.flip(frame, 0) (:864) + cv2.resize(frame,
@@ -297,7 +306,10 @@ int dd_ingest_create(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w
  * n_streams * src_h * src_w * 3 / 2 bytes -- half the bytes per frame on the host link and in pinned memory; dd_ingest_submit converts on
  * the copy stream, then flips and stretches the BGR frame as above (one launch for all three; DD_INGEST_YUV_FUSED=0, read here, selects
  * convert-into-a-staging-buffer + the BGR ring's resize launch: the same bytes).  The consumer still receives BGR
- * [n_streams][dst_h][dst_w][3]; submit / acquire / release are unchanged. */
+ * [n_streams][dst_h][dst_w][3]; submit / acquire / release are unchanged.
+ * pixel_format 4 = YUY2, 5 = UYVY: packed 4:2:2 as dd_yuv422_to_bgr, dense (src_w even, else DD_E_ARG naming the value; src_h any positive
+ * value).  Such a slot and its device twin are n_streams * src_h * src_w * 2 bytes, two thirds of BGR; the conversion, the one-launch form
+ * and DD_INGEST_YUV_FUSED=0 are as for 4:2:0.  pixel_format 3 names the JPEG ring, which dd_ingest_create_jpeg makes: refused here. */
 int dd_ingest_create_format(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip,
                             int pixel_format, dd_ingest **out);
 /* The same ring for slots that hold baseline JPEG files (see the JPEG decoder below): a slot is one pinned arena of slot_bytes, into which
