@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdarg>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 #include "../../include/deepdish_hip.h"
@@ -93,6 +94,15 @@ struct dd_ctx {
 static inline hipStream_t dd_pick_stream(dd_ctx *ctx, void *stream) {
     return stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
 }
+
+// Switches from the environment.  dd_env_int: the number a variable holds, `def` when it is not set; dd_env_set: present at all.  A call site keeps
+// its own convention on top ("0 turns off": dd_env_int(X, 1) != 0; "non-zero turns on": dd_env_int(X, 0) != 0) and its own lifetime (`static` = once
+// per process).
+static inline int dd_env_int(const char *name, int def) {
+    const char *v = getenv(name);
+    return v ? atoi(v) : def;
+}
+static inline bool dd_env_set(const char *name) { return getenv(name) != nullptr; }
 
 static inline int dd_ceil_div(int a, int b) { return (a + b - 1) / b; }
 

@@ -27,15 +27,8 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 
-enum { OP_INPUT = 1, OP_CONV = 2, OP_DWCONV = 3, OP_MAXPOOL = 4, OP_UPSAMPLE = 5, OP_FC = 6, OP_L2NORM = 7, OP_STEM = 8, OP_DWPW = 9 };
-enum { ACT_NONE = 0, ACT_RELU6 = 1, ACT_ELU = 2, ACT_SILU = 3, ACT_RELU = 4, ACT_SIGMOID = 5 };
-enum { EPI_F16 = 0, EPI_F32 = 1, EPI_SSD_HEAD = 2, EPI_YOLO = 3 };
 // dd_net_op_launches: 0 = the op's own kernel, 1 = no launch (folded into the next op's), else the fused / special kernel
 enum { OPK_DEFAULT = 0, OPK_FOLDED = 1, OPK_POOL_ROWS = 2, OPK_POOL_ROWS_STEM = 3, OPK_RES_UNIT = 4, OPK_SSD_FRONT = 5, OPK_C64_ROWS = 6, OPK_S2_ROWS = 7, OPK_CONV_WS = 8, OPK_WS_DW = 9, OPK_DWPW_ROWS = 10, OPK_SSD_HEAD_DEC = 11, OPK_RES_PAIR = 12, OPK_YOLO_HEAD_DEC = 13, OPK_MARS_WS = 14, OPK_FOLDED_PREV = 15, OPK_MARS_PAIR = 16, OPK_C64_STRIPS = 18, OPK_Q_FRONT = 19, OPK_Q_MID = 20, OPK_STEM_WIDE = 23 };   // (17, 21, 22: q_dwm_k, q_conv_k<add>, q_add_k, csrc/netsq.hip; 19: q_front_k, csrc/netsq_front.hip; 20: q_mid_k, csrc/netsq_mid.hip)
-enum { DT_F16 = 0, DT_F32 = 1, DT_U8 = 2 };
-
-constexpr int OP_WORDS = 48;       // int32 words per op record (see deepdish_amd/nets.py)
-constexpr int TENSOR_WORDS = 8;
 
 // 1 / (1 + exp(-v)) with v_rcp_f32 (1 ulp) instead of the correctly rounded quotient hipcc makes of `1.f / x` (v_div_scale x 2, v_rcp, four
 // v_fma, v_div_fmas, v_div_fixup: eleven instructions per element -- 6 355 such sequences in this file before; every YOLOv5 layer ends in a SiLU
@@ -3878,7 +3871,7 @@ int launch_conv(hipStream_t s, ConvP &P, DevBuf &slab, int max_batch, int device
     if constexpr (GLDS) {
         const bool pw = P.kh == 1 && P.kw == 1 && P.stride == 1 && P.pad_t == 0 && P.pad_l == 0 && P.cin % 64 == 0 &&
                         P.ho == P.H && P.wo == P.W;
-        static const bool no_fm2 = getenv("DD_NO_FM2") != nullptr;                      // A/B switch
+        static const bool no_fm2 = dd_env_set("DD_NO_FM2");                      // A/B switch
         const bool tapu = P.cin % 64 == 0 && P.kh <= 3 && P.kw <= 3 && P.kpad == P.kh * P.kw * P.cin && !no_fm2;
         if (pw) hipLaunchKernelGGL((conv_glds_k<WM, WN, MI, NI, 1>), dim3(gx, gy, splitk), dim3(WM * WN * 64), lds_bytes, s, P);
         else if (tapu) hipLaunchKernelGGL((conv_glds_k<WM, WN, MI, NI, 2>), dim3(gx, gy, splitk), dim3(WM * WN * 64), lds_bytes, s, P);
@@ -3940,7 +3933,7 @@ void spatial_tile(int ho, int wo, int stride, int max_patch, ConvP &P) {
 
 // Can the pooled 3x3 layer P run as conv3x3_pool_rows_k on nimg images?  (P.p[0..1] = pooled height, width.)
 bool pool_rows_fusable(const ConvP &P, int nimg) {
-    static const bool tiled = getenv("DD_POOL_TILED") && atoi(getenv("DD_POOL_TILED")) != 0;
+    static const bool tiled = dd_env_int("DD_POOL_TILED", 0) != 0;
     return !tiled && nimg >= 160 && P.W == 32 && P.wo == 32 && P.H == P.ho && P.H % 2 == 0 && P.p[0] == P.H / 2 - 1 && P.p[1] == 15 &&
            P.pad_t == 1 && P.pad_l == 1 && P.cin == 32 && P.cout == 32 && P.act == ACT_ELU;
 }
@@ -3963,7 +3956,7 @@ int launch_stem_wide(hipStream_t s, ConvP &P, int nimg, int device) {
     const int strips = P.W / 32, cpw = 4 / strips;
     const int groups = dd_ceil_div(nimg, cpw);                     // workgroups' worth of crops
     // few crops: split the rows of a crop over several workgroups (a unit's first two steps only build its rings: ~2 recomputed rounds per extra unit)
-    static const int force_split = getenv("DD_STEM_WIDE_SPLIT") ? atoi(getenv("DD_STEM_WIDE_SPLIT")) : 0;
+    static const int force_split = dd_env_int("DD_STEM_WIDE_SPLIT", 0);
     const int split = force_split > 0 ? force_split : groups >= 512 ? 1 : groups >= 256 ? 2 : 4;
     const long long n_units = (long long)groups * split;
     DD_REQUIRE(n_units < (1ll << 31), DD_E_CAPACITY, "stem_wide: %lld units", n_units);
@@ -3993,8 +3986,8 @@ int launch_conv3x3_rw(hipStream_t s, ConvP &P, int nimg, bool pool, int device) 
                 return DD_OK;
             });
             if (rc != DD_OK) return rc;
-            static const int force_split = getenv("DD_POOL_SPLIT") ? atoi(getenv("DD_POOL_SPLIT")) : 0;
-            static const int dbg = getenv("DD_PR_DBG") ? atoi(getenv("DD_PR_DBG")) : 0;
+            static const int force_split = dd_env_int("DD_POOL_SPLIT", 0);
+            static const int dbg = dd_env_int("DD_PR_DBG", 0);
             const int split = force_split > 0 ? force_split : nimg >= 1536 ? 1 : nimg >= 768 ? 2 : 4;
             const int n_units = nimg * split;
             const int grid = std::min(dd_ceil_div(n_units, 4), 2 * 256);
@@ -4050,10 +4043,10 @@ int launch_conv3x3_rw(hipStream_t s, ConvP &P, int nimg, bool pool, int device) 
 
 // Residual unit (layer A then layer B reading only A's output) as one launch of res_unit_rows_k?
 bool res_unit_fusable(const ConvP &A, const ConvP &B, int nimg) {
-    static const bool off = getenv("DD_RES_UNIT_UNFUSED") && atoi(getenv("DD_RES_UNIT_UNFUSED")) != 0;
+    static const bool off = dd_env_int("DD_RES_UNIT_UNFUSED", 0) != 0;
     // one wave per image: both layers of a unit take 56-60 us whatever the batch up to 2048 images; the two tiled launches
     // take 34 / 52 / 58 / 77 us at 160 / 320 / 480 / 640 images (profiles/r02_res_unit_sweep.txt)
-    static const int min_img = getenv("DD_RES_UNIT_MIN") ? atoi(getenv("DD_RES_UNIT_MIN")) : 512;
+    static const int min_img = dd_env_int("DD_RES_UNIT_MIN", 512);
     auto plain = [](const ConvP &P) {
         return P.kh == 3 && P.kw == 3 && P.stride == 1 && P.pad_t == 1 && P.pad_l == 1 && P.cin == 32 && P.cout == 32 && P.cout_pad == 32 &&
                P.epi == EPI_F16 && P.W == 15 && P.wo == 15 && P.H == P.ho && P.splitk <= 1;
@@ -4082,8 +4075,8 @@ int launch_res_unit(hipStream_t s, const ConvP &A, const ConvP &B, int nimg, int
 // Two residual units in a row (A1, B1 then A2, B2; each pair res_unit_fusable) as one launch of res_pair_rows_k?  The caller
 // knows from the program (op flag 2 on B1) that B1's two outputs are read by the second unit only.
 bool res_pair_fusable(const ConvP &A1, const ConvP &B1, const ConvP &A2, const ConvP &B2, int nimg) {
-    static const bool off = getenv("DD_RES_PAIR_OFF") && atoi(getenv("DD_RES_PAIR_OFF")) != 0;
-    static const int min_img = getenv("DD_RES_PAIR_MIN") ? atoi(getenv("DD_RES_PAIR_MIN")) : 1024;    // four image pairs per CU
+    static const bool off = dd_env_int("DD_RES_PAIR_OFF", 0) != 0;
+    static const int min_img = dd_env_int("DD_RES_PAIR_MIN", 1024);    // four image pairs per CU
     return !off && nimg >= min_img && A1.H == 31 && A1.W == 15 &&
            B1.res == A1.in && B1.cs_res == A1.cs_in && B1.coff_res == A1.coff_in &&                  // first unit: skip tensor = its input
            A2.in == static_cast<const _Float16 *>(B1.out2) && A2.cs_in == B1.cs_out2 && !A2.coff_in && !B1.coff_out2 &&
@@ -4106,8 +4099,8 @@ int launch_res_pair(hipStream_t s, const ConvP &A1, const ConvP &B1, const ConvP
 }
 
 bool s2_rows_eligible(const ConvP &P, int nimg, int max_batch) {
-    static const bool off = getenv("DD_S2_ROWS_OFF") && atoi(getenv("DD_S2_ROWS_OFF")) != 0;
-    static const int min_img = getenv("DD_S2_ROWS_MIN") ? atoi(getenv("DD_S2_ROWS_MIN")) : 512;
+    static const bool off = dd_env_int("DD_S2_ROWS_OFF", 0) != 0;
+    static const int min_img = dd_env_int("DD_S2_ROWS_MIN", 512);
     return !off && nimg >= min_img && P.kh == 3 && P.kw == 3 && P.stride == 2 && P.pad_t == 1 && P.pad_l == 1 && P.cin == 32 && P.cout == 64 &&
            P.cout_pad == 64 && P.kpad >= 288 && P.epi == EPI_F16 && P.W == 15 && P.H == 31 && P.ho == 16 && P.wo == 8 && P.splitk <= 1 &&
            P.act == ACT_ELU && !P.res && !P.out2 && (long long)dd_ceil_div(max_batch * P.ho * P.wo, 64) >= 256;
@@ -4129,8 +4122,8 @@ int launch_conv3x3_s2_rows(hipStream_t s, const ConvP &P, int nimg, int device) 
 
 // YOLOv5's 3x3 64 -> 64 layers (80 x 80 maps, SiLU, with or without the bottleneck's shortcut) as 8-column strips of conv3x3_c64_rows_k
 bool c64_strips_eligible(const ConvP &P, int nimg, int max_batch) {
-    static const bool off = getenv("DD_C64_STRIPS_OFF") && atoi(getenv("DD_C64_STRIPS_OFF")) != 0;
-    static const int min_items = getenv("DD_C64_STRIPS_MIN") ? atoi(getenv("DD_C64_STRIPS_MIN")) : 1024;      // two items per wave slot of the chip
+    static const bool off = dd_env_int("DD_C64_STRIPS_OFF", 0) != 0;
+    static const int min_items = dd_env_int("DD_C64_STRIPS_MIN", 1024);      // two items per wave slot of the chip
     return !off && P.kh == 3 && P.kw == 3 && P.stride == 1 && P.pad_t == 1 && P.pad_l == 1 && P.cin == 64 && P.cout == 64 &&
            P.cout_pad == 64 && P.kpad == 576 && P.epi == EPI_F16 && P.W > 8 && P.W % 8 == 0 && P.wo == P.W && P.H == P.ho && P.H % 2 == 0 &&
            P.splitk <= 1 && P.act == ACT_SILU && !P.out2 && (!P.res || (P.cs_res % 8 == 0 && P.coff_res % 8 == 0)) &&
@@ -4157,8 +4150,8 @@ int launch_conv3x3_c64_strips(hipStream_t s, const ConvP &P, int nimg, int devic
 }
 
 bool c64_rows_eligible(const ConvP &P, int nimg, int max_batch) {
-    static const bool off = getenv("DD_C64_ROWS_OFF") && atoi(getenv("DD_C64_ROWS_OFF")) != 0;
-    static const int min_img = getenv("DD_C64_ROWS_MIN") ? atoi(getenv("DD_C64_ROWS_MIN")) : 512;
+    static const bool off = dd_env_int("DD_C64_ROWS_OFF", 0) != 0;
+    static const int min_img = dd_env_int("DD_C64_ROWS_MIN", 512);
     return !off && nimg >= min_img && P.kh == 3 && P.kw == 3 && P.stride == 1 && P.pad_t == 1 && P.pad_l == 1 && P.cin == 64 && P.cout == 64 &&
            P.cout_pad == 64 && P.kpad == 576 && P.epi == EPI_F16 && P.W == 8 && P.wo == 8 && P.H == P.ho && P.H % 2 == 0 && P.splitk <= 1 &&
            ((P.act == ACT_ELU && !P.res && !P.out2) || (P.act == ACT_NONE && P.res && P.out2 && P.cs_res % 8 == 0 && P.coff_res % 8 == 0)) &&
@@ -4183,9 +4176,9 @@ int launch_conv3x3_c64_rows(hipStream_t s, const ConvP &P, int nimg, int device)
 
 // First layer (S) + first MobileNet block (P, reading only S's output) as one launch of ssd_front_k?
 bool ssd_front_fusable(const ConvP &S, const ConvP &P, int nimg) {
-    static const bool off = getenv("DD_SSD_FRONT_UNFUSED") && atoi(getenv("DD_SSD_FRONT_UNFUSED")) != 0;
+    static const bool off = dd_env_int("DD_SSD_FRONT_UNFUSED", 0) != 0;
     // whole forward at 8 / 16 / 32 / 48 / 96 / 192 frames: fused 305 / 366 / 507 / 627 / 969 / 1662 us, two launches 293 / 376 / 515 / 652 / 1024 / 1740 us
-    static const int min_img = getenv("DD_SSD_FRONT_MIN") ? atoi(getenv("DD_SSD_FRONT_MIN")) : 16;
+    static const int min_img = dd_env_int("DD_SSD_FRONT_MIN", 16);
     return !off && nimg >= min_img && S.stride == 2 && S.cout == 32 && S.cout_pad == 32 && S.act == ACT_RELU6 && (S.W * 3) % 4 == 0 &&
            (reinterpret_cast<uintptr_t>(S.src8) & 3) == 0 && S.pad_t >= 0 && S.pad_l >= 0 && S.pad_t <= 1 && S.pad_l <= 1 &&
            P.cin == 32 && P.cout == 64 && P.cout_pad == 64 && P.kpad == 32 && P.stride == 1 && P.pad_t == 1 && P.pad_l == 1 &&
@@ -4202,7 +4195,7 @@ int launch_ssd_front(hipStream_t s, const ConvP &S, const ConvP &P, int nimg, in
     });
     if (rc != DD_OK) return rc;
     const int strips = dd_ceil_div(P.wo, SF_SW);
-    static const int force_parts = getenv("DD_SSD_FRONT_PARTS") ? atoi(getenv("DD_SSD_FRONT_PARTS")) : 0;
+    static const int force_parts = dd_env_int("DD_SSD_FRONT_PARTS", 0);
     // row parts per strip: 2048 wave slots (two per SIMD) are filled in rounds; a part costs its rows + 2 (the two stem rows above it)
     int parts = 1;
     long long best = -1;
@@ -4234,8 +4227,8 @@ int launch_stem(hipStream_t s, ConvP &P, int nimg) {
 }
 
 bool dwpw_rows_eligible(const ConvP &P, int nimg) {
-    static const bool off = getenv("DD_DWPW_ROWS_OFF") && atoi(getenv("DD_DWPW_ROWS_OFF")) != 0;
-    static const int min_img = getenv("DD_DWPW_ROWS_MIN") ? atoi(getenv("DD_DWPW_ROWS_MIN")) : 96;     // 64 frames: 745 vs 741 us for the whole forward; 384: 2767 vs 2859
+    static const bool off = dd_env_int("DD_DWPW_ROWS_OFF", 0) != 0;
+    static const int min_img = dd_env_int("DD_DWPW_ROWS_MIN", 96);     // 64 frames: 745 vs 741 us for the whole forward; 384: 2767 vs 2859
     return !off && nimg >= min_img && P.cin == 128 && P.cout == 128 && P.cout_pad == 128 && P.kpad == 128 && P.stride == 1 && P.pad_t == 1 && P.pad_l == 1 &&
            P.act == ACT_RELU6 && P.dw_act == ACT_RELU6 && P.ho == P.H && P.wo == P.W && !P.res && !P.out2 && P.cs_in % 8 == 0 && P.coff_in % 8 == 0;
 }
@@ -4249,7 +4242,7 @@ int launch_dwpw_rows(hipStream_t s, const ConvP &P, int nimg, int device) {
     });
     if (rc != DD_OK) return rc;
     const int strips = dd_ceil_div(P.W, DR_SW);
-    static const int force_parts = getenv("DD_DWPW_ROWS_PARTS") ? atoi(getenv("DD_DWPW_ROWS_PARTS")) : 0;
+    static const int force_parts = dd_env_int("DD_DWPW_ROWS_PARTS", 0);
     int parts = 1;                                               // row parts per strip, as in launch_ssd_front
     long long best = -1;
     for (int p = 1; p <= 8; ++p) {
@@ -4306,7 +4299,7 @@ bool ws_eligible(const ConvP &P) {
     // for its eligible layers, bit-identical: 48 / 64 frames +0.6 / +0.4 %, 96 / 128 / 160 / 192 / 256 frames -2.9 / -1.5 / -5.7 /
     // -2.3 / -2.9 %; end to end at 256 frames per launch (4 worker groups) 68.8 -> 72.4 k frames/s.  At the 96-frame launches of an
     // earlier default the persistent blocks lost to the other groups' kernels they cannot share a CU with (-1.5 % end to end).
-    static const int mode = getenv("DD_WS") ? atoi(getenv("DD_WS")) : -1;
+    static const int mode = dd_env_int("DD_WS", -1);
     const int nimg = P.m / std::max(1, P.ho * P.wo);
     return (mode > 0 || (mode < 0 && nimg >= 160)) && P.kh == 1 && P.kw == 1 && P.stride == 1 && P.pad_t == 0 && P.pad_l == 0 && P.ho == P.H && P.wo == P.W &&
            (P.cin == 256 || P.cin == 512) && P.kpad == P.cin && P.epi == EPI_F16 && !P.res && !P.out2 && P.m >= 16384 &&
@@ -4319,7 +4312,7 @@ int launch_conv_ws(hipStream_t s, ConvP &P, int device) {
                                                                  // one 8-wave block with a 128 KiB ring: 43.9 vs 46.8 us, 19x19x512 -> 512 at 192 frames)
     const int n_slices = P.cout_pad / (32 * NW);
     P.splitk = 1;
-    static const int dbg_mode = getenv("DD_WS_MODE") ? atoi(getenv("DD_WS_MODE")) : 0;
+    static const int dbg_mode = dd_env_int("DD_WS_MODE", 0);
     P.p[5] = dbg_mode;
     constexpr size_t lds_bytes = (size_t)D * WS_BM * 64 * sizeof(_Float16);
     DD_REQUIRE(n_slices >= 1 && (256 * 4 / NW / 4) % n_slices == 0, DD_E_ARG, "conv_ws: %d channel slices", n_slices);
@@ -4335,7 +4328,7 @@ int launch_conv_ws(hipStream_t s, ConvP &P, int device) {
     // DD_WSR=1: register-staged fills (conv_wsr_k), =2: that with 64 channels per wave (weights spill into AGPRs, one block per CU).
     // Same bits; measured at 384 frames: 19x19x512 94.5 (LDS-DMA ring) / 93.8 / 88.6 us, 38x38x256 119 / 119 / 126 us -- neither the
     // fills' issue cost nor the LDS read bandwidth is what holds the loop at 0.37 MFMA-busy, so the ring stays the default.
-    static const int wsr = getenv("DD_WSR") ? atoi(getenv("DD_WSR")) : 0;
+    static const int wsr = dd_env_int("DD_WSR", 0);
     if (wsr == 2 && P.cout_pad % 256 == 0) {                     // 64 channels per wave, one block per CU: half the LDS reads per MFMA
         constexpr size_t lds_r = (size_t)4 * WS_BM * 64 * sizeof(_Float16);
         const int ns = P.cout_pad / 256;
@@ -4354,7 +4347,7 @@ int launch_conv_ws(hipStream_t s, ConvP &P, int device) {
         DD_LAUNCH_CHECK();
         return DD_OK;
     }
-    static const int spb = getenv("DD_WS_SPB") ? atoi(getenv("DD_WS_SPB")) : 1;     // stages per barrier; 2 measured null (19x19x512 93.6 / 91.8 vs 94.5 / 92.0 us, same bits)
+    static const int spb = dd_env_int("DD_WS_SPB", 1);     // stages per barrier; 2 measured null (19x19x512 93.6 / 91.8 vs 94.5 / 92.0 us, same bits)
     if (spb == 2) {
         static DevOnce once2;
         const int rc2 = once2.run(device, [&]() -> int {
@@ -4379,7 +4372,7 @@ int launch_conv_ws(hipStream_t s, ConvP &P, int device) {
 
 // Pointwise layer P (conv_ws_k material) followed by the depthwise layer Q that alone reads its output: one launch of conv_ws_dw_k?
 bool ws_dw_fusable(const ConvP &P, const DwP &Q, int nimg) {
-    static const bool off = getenv("DD_WS_DW_OFF") && atoi(getenv("DD_WS_DW_OFF")) != 0;
+    static const bool off = dd_env_int("DD_WS_DW_OFF", 0) != 0;
     if (off || !ws_eligible(P) || P.act != ACT_RELU6 || Q.act != ACT_RELU6 || Q.stride != 1 || Q.pad_t != 1 || Q.pad_l != 1) return false;
     if (Q.in != static_cast<const _Float16 *>(P.out) || Q.coff_in || Q.cs_in != P.cs_out || P.coff_out || Q.H != P.ho || Q.W != P.wo ||
         Q.ho != Q.H || Q.wo != Q.W || Q.c != P.cout || P.cout != P.cout_pad || (Q.W != 19 && Q.W != 10) || (long long)nimg * Q.H * Q.W >= (1 << 23))
@@ -4402,7 +4395,7 @@ int launch_conv_ws_dw(hipStream_t s, ConvP &P, const DwP &Q, int nimg, int devic
         return DD_OK;
     });
     if (rc != DD_OK) return rc;
-    static const int dbg_mode = getenv("DD_WS_MODE") ? atoi(getenv("DD_WS_MODE")) : 0;
+    static const int dbg_mode = dd_env_int("DD_WS_MODE", 0);
     P.p[5] = dbg_mode;
     hipLaunchKernelGGL((conv_ws_dw_k<KS, WMAP, ACT_RELU6, ACT_RELU6>), dim3(512), dim3(NW * 64), lds_bytes, s, P, Q, n_slices, nimg);
     DD_LAUNCH_CHECK();
@@ -4438,7 +4431,7 @@ int launch_dwpw_big(hipStream_t s, ConvP &P, int device, int nimg) {
 // MARS conv4_x on the crop-resident weight-stationary kernels (csrc/mars_tail.hip).  They run at EVERY batch size (their K halves
 // meet at the end: not conv_glds_k's summation order), so a crop's feature does not depend on the launch shape.  DD_MARS_WS=0: off.
 bool mars_ws_on() {
-    static const bool on = !(getenv("DD_MARS_WS") && atoi(getenv("DD_MARS_WS")) == 0);
+    static const bool on = dd_env_int("DD_MARS_WS", 1) != 0;
     return on;
 }
 bool mars_ws_s1_eligible(const ConvP &P) {
@@ -4452,61 +4445,78 @@ bool mars_ws_s2_eligible(const ConvP &P) {                        // the 3x3 str
            P.cin == 64 && P.cout == 128 && P.cout_pad == 128 && P.kpad >= 576 && P.epi == EPI_F16 && P.act == ACT_ELU && !P.res && !P.out2 &&
            P.cs_in % 8 == 0 && P.coff_in % 8 == 0 && P.cs_out % 8 == 0 && P.coff_out % 8 == 0;
 }
+// ---- an op's tensors and weights, as the kernel-argument structs carry them
+// Tensor t: where it lies and how its channels are strided -- the (pointer, channel stride, channel offset) triple of ConvP, MarsWsP, MarsPairP, ...
+template <class Ptr>
+inline void bind_tensor(const dd_net *net, int t, Ptr &p, int &cs, int &coff) {
+    const TensorDesc &d = net->tensors[t];
+    p = static_cast<Ptr>(net->bufs[d.buf]); cs = d.cs; coff = d.coff;
+}
+template <class T> inline const T *blob(const dd_net *net, uint32_t off) { return reinterpret_cast<const T *>(net->d_weights + (size_t)off); }
+
+// ---- shapes the matchers share
+// 3x3, stride 1, 32 -> 32, pad 1, f16 epilogue: what conv3x3_rw_k takes (whole filter in registers, input patch staged once)
+inline bool rw_shape(int kh, int kw, int stride, int pad_t, int pad_l, int cin, int cout_pad, int epi) {
+    return kh == 3 && kw == 3 && stride == 1 && cin == 32 && cout_pad == 32 && epi == EPI_F16 && pad_t == 1 && pad_l == 1;
+}
+inline bool rw_shape(const ConvP &P) { return rw_shape(P.kh, P.kw, P.stride, P.pad_t, P.pad_l, P.cin, P.cout_pad, P.epi); }
+// ... as an op that reads tensor `src` and nothing else, writes one tensor and carries no pool
+inline bool rw_shape_plain(const OpView &q, int src, int act) {
+    return q.kind() == OP_CONV && q.src() == src && rw_shape(q.kh(), q.kw(), q.stride(), q.pad_t(), q.pad_l(), q.cin(), q.cout_pad(), q.epi()) &&
+           q.act() == act && q.res() < 0 && q.dst2() < 0 && !q.pool();
+}
+// a widening block's skip path: 1x1 stride 2, cin -> cout, unpadded, no activation, no residual, one output
+inline bool proj_shape(const OpView &q, int cin, int cout) {
+    return q.kind() == OP_CONV && q.kh() == 1 && q.kw() == 1 && q.stride() == 2 && q.pad_t() == 0 && q.pad_l() == 0 && q.cin() == cin && q.cout() == cout &&
+           q.cout_pad() == cout && q.act() == ACT_NONE && q.epi() == EPI_F16 && q.res() < 0 && q.dst2() < 0 && q.kpad() >= cin && q.src() >= 0 && q.dst() >= 0;
+}
+inline bool f16_map(const TensorDesc &d, int h, int w) { return d.h == h && d.w == w && d.cs % 8 == 0 && d.coff % 8 == 0; }
+
 bool mars_proj_follows(const dd_net *net, int i, const ConvP &P) {   // op i + 1: 1x1 stride 2, 64 -> 128, no activation, same map as op i's input
-    const int32_t *q = net->prog.data() + net->ops_off + (size_t)(i + 1) * OP_WORDS;
-    if (q[0] != OP_CONV || q[5] != 1 || q[6] != 1 || q[7] != 2 || q[8] != 0 || q[9] != 0 || q[10] != 64 || q[11] != 128 || q[12] != 128 ||
-        q[14] != ACT_NONE || q[15] != EPI_F16 || q[3] >= 0 || q[4] >= 0 || q[13] < 64 || q[1] < 0 || q[2] < 0) return false;
-    const TensorDesc &qs = net->tensors[q[1]], &qd = net->tensors[q[2]];
-    return qs.h == 16 && qs.w == 8 && qd.h == 8 && qd.w == 4 && qs.cs % 8 == 0 && qs.coff % 8 == 0 && qd.cs % 8 == 0 && qd.coff % 8 == 0 && qd.dtype == DT_F16;
+    const OpView q = op(net, i + 1);
+    if (!proj_shape(q, 64, 128)) return false;
+    const TensorDesc &qs = net->tensors[q.src()], &qd = net->tensors[q.dst()];
+    return f16_map(qs, 16, 8) && f16_map(qd, 8, 4) && qd.dtype == DT_F16;
 }
 // MARS conv3_x blocks as one launch each (csrc/mars_pair.hip), from DD_MARS_PAIR_MIN crops (default 256; the same bits as the layer-by-layer
 // kernels, so a crop's feature does not depend on which ran).  Ops i .. i + n - 1 must be: [3x3 stride-2 32 -> 64 ELU on a 31x15 map; 1x1
 // stride-2 projection of another 31x15 tensor;] or [3x3 64 -> 64 ELU on 16x8;] then 3x3 64 -> 64, no activation, residual = the projection /
 // a 16x8x64 tensor, second output with its affine.  Returns the number of ops (3 or 2) and fills Q, or 0.
 int mars_pair_match(const dd_net *net, int i, int nimg, MarsPairP &Q, bool &first) {
-    void *const *bufs = net->bufs.data();
-    static const bool off = getenv("DD_MARS_PAIR") && atoi(getenv("DD_MARS_PAIR")) == 0;
-    static const int min_crops = getenv("DD_MARS_PAIR_MIN") ? atoi(getenv("DD_MARS_PAIR_MIN")) : 256;
+    static const bool off = dd_env_int("DD_MARS_PAIR", 1) == 0;
+    static const int min_crops = dd_env_int("DD_MARS_PAIR_MIN", 256);
     if (off || nimg < min_crops) return 0;
-    auto op = [&](int k) { return net->prog.data() + net->ops_off + (size_t)k * OP_WORDS; };
-    auto W = [&](const int32_t *o, int word) { return net->d_weights + (size_t)(uint32_t)o[word]; };
-    auto conv3 = [&](const int32_t *o, int stride, int cin, int act) {
-        return o[0] == OP_CONV && o[5] == 3 && o[6] == 3 && o[7] == stride && o[10] == cin && o[11] == 64 && o[12] == 64 && o[14] == act && o[15] == EPI_F16 &&
-               o[8] == 1 && o[9] == 1 && o[13] >= 9 * cin && o[1] >= 0 && o[2] >= 0 && !o[29];
+    auto conv3 = [&](const OpView &o, int stride, int cin, int act) {
+        return o.kind() == OP_CONV && o.kh() == 3 && o.kw() == 3 && o.stride() == stride && o.cin() == cin && o.cout() == 64 && o.cout_pad() == 64 && o.act() == act &&
+               o.epi() == EPI_F16 && o.pad_t() == 1 && o.pad_l() == 1 && o.kpad() >= 9 * cin && o.src() >= 0 && o.dst() >= 0 && !o.pool();
     };
-    auto t16x8 = [&](int t, int c) { const TensorDesc &d = net->tensors[t]; return d.h == 16 && d.w == 8 && d.c == c && d.cs % 8 == 0 && d.coff % 8 == 0 && d.dtype == DT_F16; };
-    auto t31x15 = [&](int t) { const TensorDesc &d = net->tensors[t]; return d.h == 31 && d.w == 15 && d.c == 32 && d.cs % 8 == 0 && d.coff % 8 == 0 && d.dtype == DT_F16; };
+    auto t16x8 = [&](int t, int c) { const TensorDesc &d = net->tensors[t]; return f16_map(d, 16, 8) && d.c == c && d.dtype == DT_F16; };
+    auto t31x15 = [&](int t) { const TensorDesc &d = net->tensors[t]; return f16_map(d, 31, 15) && d.c == 32 && d.dtype == DT_F16; };
     memset(&Q, 0, sizeof(Q));
-    const int32_t *a = op(i);
+    const OpView a = op(net, i);
     int nb;                                                       // index of the block's second layer
-    if (i + 2 < net->n_ops && a[30] == 3 && conv3(a, 2, 32, ACT_ELU) && a[3] < 0 && a[4] < 0 && t31x15(a[1]) && t16x8(a[2], 64)) {
-        const int32_t *p = op(i + 1);
-        if (!(p[30] == 4 && p[0] == OP_CONV && p[5] == 1 && p[6] == 1 && p[7] == 2 && p[8] == 0 && p[9] == 0 && p[10] == 32 && p[11] == 64 && p[12] == 64 &&
-              p[14] == ACT_NONE && p[15] == EPI_F16 && p[3] < 0 && p[4] < 0 && p[13] >= 32 && p[1] >= 0 && p[2] >= 0 && t31x15(p[1]) && t16x8(p[2], 64))) return 0;
+    if (i + 2 < net->n_ops && a.hint() == HINT_NEXT_IS_PROJ && conv3(a, 2, 32, ACT_ELU) && a.res() < 0 && a.dst2() < 0 && t31x15(a.src()) && t16x8(a.dst(), 64)) {
+        const OpView p = op(net, i + 1);
+        if (!(p.hint() == HINT_PAIR_MEMBER && proj_shape(p, 32, 64) && t31x15(p.src()) && t16x8(p.dst(), 64))) return 0;
         first = true; nb = i + 2;
-        const TensorDesc &ti = net->tensors[a[1]], &tr = net->tensors[p[1]];
-        Q.in = reinterpret_cast<const _Float16 *>(bufs[ti.buf]); Q.cs_in = ti.cs; Q.coff_in = ti.coff;
-        Q.in2 = reinterpret_cast<const _Float16 *>(bufs[tr.buf]); Q.cs_in2 = tr.cs; Q.coff_in2 = tr.coff;
-        Q.wp = reinterpret_cast<const _Float16 *>(W(p, 16)); Q.kpad_p = p[13]; Q.bias_p = reinterpret_cast<const float *>(W(p, 17));
-        const int32_t *b = op(nb);
-        if (b[3] != p[2]) return 0;                               // the second layer adds the projection
-    } else if (i + 1 < net->n_ops && a[30] == 4 && conv3(a, 1, 64, ACT_ELU) && a[3] < 0 && a[4] < 0 && t16x8(a[1], 64) && t16x8(a[2], 64)) {
+        bind_tensor(net, a.src(), Q.in, Q.cs_in, Q.coff_in);
+        bind_tensor(net, p.src(), Q.in2, Q.cs_in2, Q.coff_in2);
+        Q.wp = blob<_Float16>(net, p.w_off()); Q.kpad_p = p.kpad(); Q.bias_p = blob<float>(net, p.bias_off());
+        if (op(net, nb).res() != p.dst()) return 0;               // the second layer adds the projection
+    } else if (i + 1 < net->n_ops && a.hint() == HINT_PAIR_MEMBER && conv3(a, 1, 64, ACT_ELU) && a.res() < 0 && a.dst2() < 0 && t16x8(a.src(), 64) && t16x8(a.dst(), 64)) {
         first = false; nb = i + 1;
-        const TensorDesc &ti = net->tensors[a[1]];
-        Q.in = reinterpret_cast<const _Float16 *>(bufs[ti.buf]); Q.cs_in = ti.cs; Q.coff_in = ti.coff;
-        const int32_t *b = op(nb);
-        if (b[3] < 0 || !t16x8(b[3], 64)) return 0;
-        const TensorDesc &tr = net->tensors[b[3]];
-        Q.res = reinterpret_cast<const _Float16 *>(bufs[tr.buf]); Q.cs_res = tr.cs; Q.coff_res = tr.coff;
+        bind_tensor(net, a.src(), Q.in, Q.cs_in, Q.coff_in);
+        const OpView b = op(net, nb);
+        if (b.res() < 0 || !t16x8(b.res(), 64)) return 0;
+        bind_tensor(net, b.res(), Q.res, Q.cs_res, Q.coff_res);
     } else return 0;
-    const int32_t *b = op(nb);
-    if (!(conv3(b, 1, 64, ACT_NONE) && b[1] == a[2] && b[3] >= 0 && b[4] >= 0 && b[19] && t16x8(b[2], 64) && t16x8(b[4], 64))) return 0;
-    Q.wa = reinterpret_cast<const _Float16 *>(W(a, 16)); Q.kpad_a = a[13]; Q.bias_a = reinterpret_cast<const float *>(W(a, 17));
-    Q.wb = reinterpret_cast<const _Float16 *>(W(b, 16)); Q.kpad_b = b[13]; Q.bias_b = reinterpret_cast<const float *>(W(b, 17));
-    const TensorDesc &to = net->tensors[b[2]], &t2 = net->tensors[b[4]];
-    Q.out = reinterpret_cast<_Float16 *>(bufs[to.buf]); Q.cs_out = to.cs; Q.coff_out = to.coff;
-    Q.out2 = reinterpret_cast<_Float16 *>(bufs[t2.buf]); Q.cs_out2 = t2.cs; Q.coff_out2 = t2.coff;
-    Q.aff2 = reinterpret_cast<const float *>(W(b, 18)); Q.cout_pad = b[12];
+    const OpView b = op(net, nb);
+    if (!(conv3(b, 1, 64, ACT_NONE) && b.src() == a.dst() && b.res() >= 0 && b.dst2() >= 0 && b.has_aff() && t16x8(b.dst(), 64) && t16x8(b.dst2(), 64))) return 0;
+    Q.wa = blob<_Float16>(net, a.w_off()); Q.kpad_a = a.kpad(); Q.bias_a = blob<float>(net, a.bias_off());
+    Q.wb = blob<_Float16>(net, b.w_off()); Q.kpad_b = b.kpad(); Q.bias_b = blob<float>(net, b.bias_off());
+    bind_tensor(net, b.dst(), Q.out, Q.cs_out, Q.coff_out);
+    bind_tensor(net, b.dst2(), Q.out2, Q.cs_out2, Q.coff_out2);
+    Q.aff2 = blob<float>(net, b.aff_off()); Q.cout_pad = b.cout_pad();
     Q.zero = net->d_zero; Q.n_img = nimg;
     return nb - i + 1;
 }
@@ -4573,14 +4583,14 @@ static int net_create(dd_ctx *ctx, const int32_t *program_host, int n_words, con
         std::vector<int> first(nb, -1), last(nb, -1);
         for (int t = 0; t < nt; ++t) DD_REQUIRE(n->tensors[t].buf >= 0 && n->tensors[t].buf < nb, DD_E_ARG, "dd_net_create_shared: tensor %d names buffer %d of %d", t, n->tensors[t].buf, nb);
         for (int i = 0; i < no; ++i)
-            DD_REQUIRE((ops + (size_t)i * OP_WORDS)[0] < 16, DD_E_ARG, "dd_net_create_shared: uint8 programs keep one buffer per tensor (their borders are set once)");
-        // An op flagged "only the next op reads my output" (word 30) may run inside that op's launch -- a first layer folded into the
+            DD_REQUIRE(OpView{ops + (size_t)i * OP_WORDS}.kind() < OP_QCONV0, DD_E_ARG, "dd_net_create_shared: uint8 programs keep one buffer per tensor (their borders are set once)");
+        // An op with a hint (W_HINT: "only the next op reads my output" and its kin) may run inside that op's launch -- a first layer folded into the
         // pooled layer behind it, a residual unit held back until its second layer, a pair of units until the fourth -- so every buffer
         // touched anywhere in such a chain of ops is live over the whole chain.
         std::vector<int> gs(no), ge(no);
         for (int i = 0; i < no;) {
             int j = i;
-            while (j + 1 < no && (ops + (size_t)j * OP_WORDS)[30] != 0) ++j;
+            while (j + 1 < no && OpView{ops + (size_t)j * OP_WORDS}.hint() != HINT_NONE) ++j;
             for (int k = i; k <= j; ++k) { gs[k] = i; ge[k] = j; }
             i = j + 1;
         }
@@ -4591,8 +4601,8 @@ static int net_create(dd_ctx *ctx, const int32_t *program_host, int n_words, con
             last[b] = std::max(last[b], ge[i]);
         };
         for (int i = 0; i < no; ++i) {
-            const int32_t *o = ops + (size_t)i * OP_WORDS;
-            touch2(o[1], i); touch2(o[2], i); touch2(o[3], i); touch2(o[4], i);
+            const OpView o{ops + (size_t)i * OP_WORDS};
+            touch2(o.src(), i); touch2(o.dst(), i); touch2(o.res(), i); touch2(o.dst2(), i);
         }
         if (n->out_tensor >= 0) last[n->tensors[n->out_tensor].buf] = no;
         std::vector<size_t> bytes(nb), off(nb, 0);
@@ -4637,19 +4647,19 @@ static int net_create(dd_ctx *ctx, const int32_t *program_host, int n_words, con
         // captured graphs, so it must never be reallocated by a forward
         size_t need = 0;
         for (int i = 0; i < no; ++i) {
-            const int32_t *o = p + (size_t)i * OP_WORDS;
-            if (o[0] != OP_CONV) continue;
-            const int bk = o[28] == 32 ? 32 : 64, sk = conv_splitk(o[26], o[27], o[12], o[13] / bk, max_batch);
-            if (sk > 1) need = std::max(need, (size_t)sk * max_batch * o[26] * o[27] * o[12] * sizeof(float));
+            const OpView o{p + (size_t)i * OP_WORDS};
+            if (o.kind() != OP_CONV) continue;
+            const int bk = o.bk() == 32 ? 32 : 64, sk = conv_splitk(o.ho(), o.wo(), o.cout_pad(), o.kpad() / bk, max_batch);
+            if (sk > 1) need = std::max(need, (size_t)sk * max_batch * o.ho() * o.wo() * o.cout_pad() * sizeof(float));
         }
         if (need) { const int rc = n->slab.reserve(need); if (rc != DD_OK) return rc; }
     }
     n->weight_bytes = n_weight_bytes;
     DD_HIP(hipMalloc(&n->d_zero, 256));
     DD_HIP(hipMemset(n->d_zero, 0, 256));
-    n->use_glds = getenv("DD_NO_GLDS") == nullptr;
-    n->use_rw = getenv("DD_NO_RW") == nullptr;
-    n->tile_mode = getenv("DD_TILE_MODE") ? atoi(getenv("DD_TILE_MODE")) : 0;
+    n->use_glds = !dd_env_set("DD_NO_GLDS");
+    n->use_rw = !dd_env_set("DD_NO_RW");
+    n->tile_mode = dd_env_int("DD_TILE_MODE", 0);
     DD_HIP(hipMalloc(&n->d_weights, (size_t)n_weight_bytes + 256));
     DD_HIP(hipMemcpy(n->d_weights, weights_host, (size_t)n_weight_bytes, hipMemcpyHostToDevice));
     guard.n = nullptr;
@@ -4769,14 +4779,14 @@ int dd_net_read(dd_net *n, int tensor, int n_img, void *dst, int dst_on_device, 
     // conv0 in ssd_front_k, the first layer of a residual unit, a pointwise layer in conv_ws_dw_k; batch dependent) was
     // never written: reading it would return stale or uninitialised data.
     for (int i = 0; i < n->n_ops && i < (int)n->op_launch.size(); ++i) {
-        const int32_t *o = n->prog.data() + n->ops_off + (size_t)i * OP_WORDS;
-        DD_REQUIRE(!(o[2] == t && n->op_launch[i] == OPK_SSD_HEAD_DEC), DD_E_STATE,
+        const OpView o = op(n, i);
+        DD_REQUIRE(!(o.dst() == t && n->op_launch[i] == OPK_SSD_HEAD_DEC), DD_E_STATE,
                    "dd_net_read: tensor %d (the SSD head matrix) was not written: the head layers decoded in their epilogue "
                    "(dd_net_ssd_decode); read dd_net_ssd_decoded instead", t);
-        DD_REQUIRE(!(o[2] == t && n->op_launch[i] == OPK_YOLO_HEAD_DEC), DD_E_STATE,
+        DD_REQUIRE(!(o.dst() == t && n->op_launch[i] == OPK_YOLO_HEAD_DEC), DD_E_STATE,
                    "dd_net_read: tensor %d (the Detect matrix) was not written: the head layers reduced their rows in their epilogue "
                    "(dd_net_yolo_decode); read dd_net_yolo_decoded instead", t);
-        DD_REQUIRE(!((o[2] == t || o[4] == t) && n->op_launch[i] == OPK_FOLDED), DD_E_STATE,
+        DD_REQUIRE(!((o.dst() == t || o.dst2() == t) && n->op_launch[i] == OPK_FOLDED), DD_E_STATE,
                    "dd_net_read: tensor %d was not written by the last forward (op %d ran inside the next op's launch at this batch "
                    "size and its output stayed on chip); run a smaller batch or a program compiled without the fusion flags", t, i);
     }
@@ -4809,14 +4819,14 @@ int dd_net_ssd_decode(dd_net *net, const float *anchors_host, int n_anchors, flo
     DD_REQUIRE(anchors_host && n_anchors > 0, DD_E_ARG, "dd_net_ssd_decode: anchors missing");
     int heads = 0;
     for (int i = 0; i < net->n_ops; ++i) {
-        const int32_t *o = net->prog.data() + net->ops_off + (size_t)i * OP_WORDS;
-        if (o[0] == OP_CONV && o[15] == EPI_SSD_HEAD) {
-            DD_REQUIRE(o[18] && o[21] == n_anchors && 4 + o[20] <= 96, DD_E_ARG,
-                       "dd_net_ssd_decode: head op %d has no per-anchor weight copy, or %d anchors / %d classes do not fit", i, o[21], o[20]);
+        const OpView o = op(net, i);
+        if (o.kind() == OP_CONV && o.epi() == EPI_SSD_HEAD) {
+            DD_REQUIRE(o.aff_off() && o.p(1) == n_anchors && 4 + o.p(0) <= 96, DD_E_ARG,
+                       "dd_net_ssd_decode: head op %d has no per-anchor weight copy, or %d anchors / %d classes do not fit", i, o.p(1), o.p(0));
             ++heads;
         }
-        if (o[0] == 20) {                                      // OP_QSSD_DECODE (uint8 programs decode in an op of their own)
-            DD_REQUIRE(o[21] == n_anchors, DD_E_ARG, "dd_net_ssd_decode: the program decodes %d anchors, %d given", o[21], n_anchors);
+        if (o.kind() == OP_QSSD_DECODE) {                      // (uint8 programs decode in an op of their own)
+            DD_REQUIRE(o[W_Q_DEC_ANCHORS] == n_anchors, DD_E_ARG, "dd_net_ssd_decode: the program decodes %d anchors, %d given", o[W_Q_DEC_ANCHORS], n_anchors);
             ++heads;
         }
     }
@@ -4848,12 +4858,12 @@ int dd_net_yolo_decode(dd_net *net, int enable) {
     DD_REQUIRE(!net->ssd_dec, DD_E_STATE, "dd_net_yolo_decode: the SSD decode is on for this network");
     int heads = 0, rows = 0;
     for (int i = 0; i < net->n_ops; ++i) {
-        const int32_t *o = net->prog.data() + net->ops_off + (size_t)i * OP_WORDS;
-        if (o[0] == OP_CONV && o[15] == EPI_YOLO) {
-            DD_REQUIRE(o[18] && !o[19] && o[20] >= 6 && o[20] <= 96, DD_E_ARG,
-                       "dd_net_yolo_decode: head op %d has no per-anchor weight copy, or %d columns per row do not fit", i, o[20]);
-            DD_REQUIRE(rows == 0 || rows == o[21], DD_E_ARG, "dd_net_yolo_decode: heads disagree on the rows per image");
-            rows = o[21];
+        const OpView o = op(net, i);
+        if (o.kind() == OP_CONV && o.epi() == EPI_YOLO) {
+            DD_REQUIRE(o.aff_off() && !o.has_aff() && o.p(0) >= 6 && o.p(0) <= 96, DD_E_ARG,
+                       "dd_net_yolo_decode: head op %d has no per-anchor weight copy, or %d columns per row do not fit", i, o.p(0));
+            DD_REQUIRE(rows == 0 || rows == o.p(1), DD_E_ARG, "dd_net_yolo_decode: heads disagree on the rows per image");
+            rows = o.p(1);
             ++heads;
         }
     }
@@ -4913,17 +4923,17 @@ int dd_net_ssd_heads_u8(dd_net *net, const uint8_t **box_q, const uint8_t **cls_
     DD_REQUIRE(!net->arena, DD_E_STATE, "dd_net_ssd_heads_u8: the engine's buffers share memory by lifetime (dd_net_create_shared): the head "
                "tensors do not outlive the forward");
     for (int i = 0; i < net->n_ops; ++i) {
-        const int32_t *o = net->prog.data() + net->ops_off + (size_t)i * OP_WORDS;
-        if (o[0] != 20) continue;                              // OP_QSSD_DECODE
-        DD_REQUIRE(o[1] >= 0 && o[1] < (int)net->tensors.size() && o[3] >= 0 && o[3] < (int)net->tensors.size(), DD_E_ARG, "dd_net_ssd_heads_u8: head tensors out of range");
-        const TensorDesc &tb = net->tensors[o[1]], &tc = net->tensors[o[3]];
-        DD_REQUIRE(tb.cs == 4 && tb.h == o[21] && tc.h == o[21] && tb.w == 1 && tc.w == 1 && o[20] <= tc.cs && !tb.pad && !tc.pad && !tb.coff && !tc.coff, DD_E_ARG,
-                   "dd_net_ssd_heads_u8: head tensors of %d anchors are not [anchors][4] / [anchors][>= %d] bytes", o[21], o[20]);
+        const OpView o = op(net, i);
+        if (o.kind() != OP_QSSD_DECODE) continue;
+        DD_REQUIRE(o.src() >= 0 && o.src() < (int)net->tensors.size() && o.res() >= 0 && o.res() < (int)net->tensors.size(), DD_E_ARG, "dd_net_ssd_heads_u8: head tensors out of range");
+        const TensorDesc &tb = net->tensors[o.src()], &tc = net->tensors[o.res()];
+        DD_REQUIRE(tb.cs == 4 && tb.h == o[W_Q_DEC_ANCHORS] && tc.h == o[W_Q_DEC_ANCHORS] && tb.w == 1 && tc.w == 1 && o[W_Q_DEC_CLASSES] <= tc.cs && !tb.pad && !tc.pad && !tb.coff && !tc.coff, DD_E_ARG,
+                   "dd_net_ssd_heads_u8: head tensors of %d anchors are not [anchors][4] / [anchors][>= %d] bytes", o[W_Q_DEC_ANCHORS], o[W_Q_DEC_CLASSES]);
         *box_q = static_cast<const uint8_t *>(net->bufs[tb.buf]); *cls_q = static_cast<const uint8_t *>(net->bufs[tc.buf]);
-        *cls_stride = tc.cs; *n_anchors = o[21]; *n_classes = o[20];
-        *lut = reinterpret_cast<const uint8_t *>(net->d_weights + (size_t)(uint32_t)o[16]);
-        const float *of = reinterpret_cast<const float *>(o);
-        for (int q = 0; q < 4; ++q) quant4_host[q] = of[32 + q];
+        *cls_stride = tc.cs; *n_anchors = o[W_Q_DEC_ANCHORS]; *n_classes = o[W_Q_DEC_CLASSES];
+        *lut = reinterpret_cast<const uint8_t *>(net->d_weights + (size_t)o.w_off());
+        quant4_host[0] = o.fw(W_Q_DEC_BOX_SCALE); quant4_host[1] = o.fw(W_Q_DEC_BOX_ZP);
+        quant4_host[2] = o.fw(W_Q_DEC_SCORE_SCALE); quant4_host[3] = o.fw(W_Q_DEC_SCORE_ZP);
         return DD_OK;
     }
     DD_REQUIRE(false, DD_E_ARG, "dd_net_ssd_heads_u8: the program has no uint8 SSD head");
@@ -4972,531 +4982,591 @@ int dd_net_forward(dd_net *net, const uint8_t *input, int nimg, void *stream) {
     return DD_OK;
 }
 
-static int net_run_ops(dd_net *net, const uint8_t *input, int nimg, hipStream_t s) {
-    auto base = [&](int t) -> char * {
-        const TensorDesc &d = net->tensors[t];
-        return static_cast<char *>(net->bufs[d.buf]);
-    };
-    net->op_launch.assign((size_t)net->n_ops, OPK_DEFAULT);
-    net->op_variant.assign((size_t)net->n_ops, 0);
-    ConvP stem_p;                                                 // a first layer waiting to be folded into the next op's launch
-    bool stem_pending = false;
-    bool wide_pending = false, wide_ready = false;               // ... into the launch of the NEXT TWO ops (3x3 layer, then max pool: stem_conv_pool_wide_k, launched at the pool op)
-    bool input_pending = false;                                   // a space-to-depth input op waiting to be folded into the 3x3 layer behind it
+}  // extern "C"
+
+// ---- the walk over the op list: one pass that decides and launches
+namespace {
+
+// Launches held back while the walk looks at the ops behind them: an op whose output only the next op reads may run inside that op's launch.
+enum HeldKind { HELD_STEM, HELD_PW, HELD_UNIT, HELD_PAIR };
+struct Held {
+    ConvP stem; int stem_op = -1; bool stem_on = false;           // a first layer waiting to be folded into the next op's launch
+    bool wide_conv = false, wide_pool = false;                    // ... into the launch of the NEXT TWO ops (3x3 layer, then max pool: stem_conv_pool_wide_k, launched at the pool op; `stem` then holds that launch)
+    bool input_on = false; int input_op = -1;                     // a space-to-depth input op waiting to be folded into the 3x3 layer behind it
     float input_mean = 0.f, input_scale = 1.f;
-    int input_op = -1;
-    ConvP unit_a;                                                 // first 3x3 layer of a residual unit, likewise
-    bool unit_pending = false;
-    ConvP pw_p;                                                   // pointwise layer whose only reader is the next (depthwise) op
-    bool pw_pending = false;
+    ConvP unit_a; int unit_op = -1; bool unit_on = false;         // first 3x3 layer of a residual unit, likewise
+    ConvP pw; int pw_op = -1; bool pw_on = false;                 // pointwise layer whose only reader is the next (depthwise) op
     bool proj_done = false;                                       // the previous op's launch also ran this op (a 1x1 stride-2 projection)
-    MarsPairP pair64;                                             // a conv3_x block whose ops run as one launch at its last op (mars_pair64_k)
-    bool pair64_first = false;
-    int pair_left = 0;
-    ConvP pair_a, pair_b;                                         // a whole residual unit held back: it may run with the next unit (res_pair_rows_k)
-    bool pair_pending = false;
-    int pair_op = -1;
-    auto flush_pair = [&]() -> int {                              // ... or on its own after all
-        pair_pending = false;
-        net->op_launch[pair_op] = OPK_RES_UNIT;
-        return launch_res_unit(s, pair_a, pair_b, nimg, net->ctx->device);
-    };
-    auto run_ws = [&](ConvP &P) { return P.cin == 256 ? launch_conv_ws<4>(s, P, net->ctx->device) : launch_conv_ws<8>(s, P, net->ctx->device); };
-    int first_op = 0;
-    bool mid_on = false;
-    {
-        // uint8 SSD: the first three launches (first layer, MobileNet blocks 1 and 2) over chunks of frames that REUSE the image slots 0 .. chunk - 1
-        // of the two tensors between them, so that 0.72 + 1.44 MB per frame of producer -> consumer traffic can stay in the 256 MB Infinity
-        // Cache instead of going to HBM and back (DD_Q_FRONT_CHUNK=n frames; 0 = off).  Same kernels, same bits: block 2 writes its own
-        // output where the whole-batch launch would.
-        static const int chunk_env = getenv("DD_Q_FRONT_CHUNK") ? atoi(getenv("DD_Q_FRONT_CHUNK")) : 0;
-        auto opw = [&](int k) { return net->prog.data() + net->ops_off + (size_t)k * OP_WORDS; };
-        // uint8 SSD: the same three ops as ONE launch, the two tensors between them in LDS rings (csrc/netsq_front.hip).  DD_Q_FRONT=0: the three
-        // launches; DD_Q_FRONT_MIN: frames per forward from which the row pipeline runs (a few frames spread better as three wide launches).  Read on
-        // every forward: a test flips them between two forwards of one engine.
-        const char *front_env = getenv("DD_Q_FRONT"), *front_min_env = getenv("DD_Q_FRONT_MIN");
-        const int front_min = front_min_env ? atoi(front_min_env) : 24;
-        {   // blocks 3 + 4 as one launch (csrc/netsq_mid.hip), taken in the op loop below: DD_Q_MID=0 the two launches; same batch threshold
-            const char *mid_env = getenv("DD_Q_MID");
-            mid_on = !(mid_env && atoi(mid_env) == 0) && nimg >= front_min;
-        }
-        if (!(front_env && atoi(front_env) == 0) && chunk_env <= 0 && nimg >= front_min && net->n_ops > 3 && opw(0)[0] == 16 && opw(1)[0] == 19 && opw(2)[0] == 19) {
-            if (net->profile) for (int k = 0; k < 3; ++k) DD_HIP(hipEventRecord(net->events[k], s));
-            int ran = 0;
-            const int rc = netq_run_front(net, opw(0), opw(1), opw(2), input, nimg, s, &ran);
-            if (rc != DD_OK) return rc;
-            if (ran) { first_op = 3; net->op_launch[0] = OPK_FOLDED; net->op_launch[1] = OPK_FOLDED; net->op_launch[2] = OPK_Q_FRONT; }
-        }
-        if (first_op == 0 && chunk_env > 0 && nimg > chunk_env && net->n_ops > 3 && opw(0)[0] == 16 && opw(1)[0] == 19 && opw(2)[0] == 19 && opw(1)[1] == opw(0)[2] && opw(2)[1] == opw(1)[2]) {
-            const TensorDesc &t2 = net->tensors[opw(2)[2]];
-            const size_t img_out = (size_t)(t2.h + 2) * (t2.w + 2) * t2.cs;          // bordered uint8 layout: bytes per image
-            void *&out_buf = net->bufs[t2.buf];
-            void *const out_base = out_buf;
-            if (net->profile) for (int k = 0; k < 3; ++k) DD_HIP(hipEventRecord(net->events[k], s));
-            for (int c0 = 0; c0 < nimg; c0 += chunk_env) {
-                const int nc = std::min(chunk_env, nimg - c0);
-                out_buf = static_cast<char *>(out_base) + (size_t)c0 * img_out;
-                for (int k = 0; k < 3; ++k) {
-                    int handled = 0;
-                    const int rc = netq_run_op(net, k, opw(k), input + (size_t)c0 * net->in_h * net->in_w * 3, nc, s, &handled);
-                    if (rc != DD_OK || !handled) { out_buf = out_base; return rc != DD_OK ? rc : DD_E_ARG; }
-                }
-            }
-            out_buf = out_base;
-            first_op = 3;
+    MarsPairP pair64; bool pair64_first = false; int pair64_left = 0;   // a conv3_x block whose ops run as one launch at its last op (mars_pair64_k)
+    ConvP pair_a, pair_b; int pair_op = -1; bool pair_on = false; // a whole residual unit held back: it may run with the next unit (res_pair_rows_k)
+};
+
+struct Run {                                                      // one forward
+    dd_net *net; const uint8_t *input; int nimg; hipStream_t s;
+    bool mid_on = false;                                          // uint8 blocks 3 + 4 as one launch (csrc/netsq_mid.hip)
+    Held held;
+    int device() const { return net->ctx->device; }
+};
+
+int launch_ws(Run &r, ConvP &P) { return P.cin == 256 ? launch_conv_ws<4>(r.s, P, r.device()) : launch_conv_ws<8>(r.s, P, r.device()); }
+
+// Run what is held on its own after all, and say so in op_launch of the op it belonged to.
+int flush(Run &r, HeldKind what) {
+    Held &h = r.held;
+    switch (what) {
+        case HELD_STEM: h.stem_on = false; r.net->op_launch[h.stem_op] = OPK_DEFAULT; return launch_stem(r.s, h.stem, r.nimg);
+        case HELD_PW: h.pw_on = false; r.net->op_launch[h.pw_op] = OPK_CONV_WS; return launch_ws(r, h.pw);
+        case HELD_UNIT: h.unit_on = false; r.net->op_launch[h.unit_op] = OPK_DEFAULT; return launch_conv3x3_rw(r.s, h.unit_a, r.nimg, false, r.device());
+        case HELD_PAIR: h.pair_on = false; r.net->op_launch[h.pair_op] = OPK_RES_UNIT; return launch_res_unit(r.s, h.pair_a, h.pair_b, r.nimg, r.device());
+    }
+    return DD_OK;
+}
+
+// In front of every op: what was held for an op of another kind than this one runs on its own (a program that sets a hint wrongly still computes
+// the right thing).
+int flush_unclaimed(Run &r, const OpView &o) {
+    const Held &h = r.held;
+    const int kind = o.kind();
+    int rc;
+    if (h.pair_on && kind != OP_CONV && (rc = flush(r, HELD_PAIR)) != DD_OK) return rc;
+    if (h.pw_on && kind != OP_DWCONV && (rc = flush(r, HELD_PW)) != DD_OK) return rc;
+    if (h.unit_on && kind != OP_CONV && (rc = flush(r, HELD_UNIT)) != DD_OK) return rc;
+    if (h.stem_on && !(kind == OP_CONV && o.pool()) && kind != OP_DWPW && (rc = flush(r, HELD_STEM)) != DD_OK) return rc;   // not followed by the layer it was meant for
+    return DD_OK;
+}
+
+// An op that runs inside a neighbouring launch returns before anything held is flushed: a program that puts a held residual unit, stem or pointwise
+// layer directly in front of a folded op is refused instead of silently never writing it.
+int refuse_fold_while_held(const Held &h, int i) {
+    DD_REQUIRE(!h.unit_on && !h.pair_on && !h.stem_on && !h.pw_on && !h.input_on, DD_E_STATE,
+               "dd_net_forward: op %d is folded into a neighbouring launch while an earlier op's launch is still held back", i);
+    return DD_OK;
+}
+
+// The kernel arguments an op states: tensors, weights, residual, second output and its affine, p / f.  A stem or dw + pw op adds its own on top.
+ConvP conv_params(const dd_net *net, const OpView &o, int nimg) {
+    ConvP P;
+    memset(&P, 0, sizeof(P));
+    if (o.src() >= 0) {
+        bind_tensor(net, o.src(), P.in, P.cs_in, P.coff_in);
+        P.H = net->tensors[o.src()].h; P.W = net->tensors[o.src()].w;
+    }
+    P.cin = o.cin();
+    P.kh = o.kh(); P.kw = o.kw(); P.stride = o.stride(); P.pad_t = o.pad_t(); P.pad_l = o.pad_l();
+    P.cout = o.cout(); P.cout_pad = o.cout_pad(); P.kpad = o.kpad(); P.act = o.act(); P.epi = o.epi();
+    P.w = blob<_Float16>(net, o.w_off());
+    P.bias = blob<float>(net, o.bias_off());
+    P.ho = o.ho(); P.wo = o.wo(); P.m = nimg * P.ho * P.wo;      // conv grid (dst may be a head matrix)
+    bind_tensor(net, o.dst(), P.out, P.cs_out, P.coff_out);
+    if (o.res() >= 0) bind_tensor(net, o.res(), P.res, P.cs_res, P.coff_res);
+    if (o.dst2() >= 0) {
+        bind_tensor(net, o.dst2(), P.out2, P.cs_out2, P.coff_out2);
+        P.aff2 = blob<float>(net, o.aff_off());
+    }
+    if (o.dst2() < 0 && o.has_aff()) {                            // EPI_F32 with a post-activation affine (MARS fc1 + "ball")
+        P.aff2 = blob<float>(net, o.aff_off());
+        P.post_aff = 1;
+    }
+    for (int q = 0; q < 6; ++q) P.p[q] = o.p(q);
+    for (int q = 0; q < 8; ++q) P.f[q] = o.f(q);
+    return P;
+}
+
+// the first layer's half of a launch that folds it in (conv3x3_pool_rows_k<STEM>, stem_conv_pool_wide_k)
+void take_stem(ConvP &P, const ConvP &stem) {
+    P.src8 = stem.src8; P.in_mean = stem.in_mean; P.in_scale = stem.in_scale;
+    P.dw_w = stem.w; P.dw_bias = stem.bias; P.dw_act = stem.act;
+}
+
+// first 3x3 layer of a residual unit (only the next op reads it) at a batch where the unit runs as one launch
+bool unit_first_layer(const Run &r, int i, const OpView &o, const ConvP &P) {
+    return o.hint() != HINT_NONE && !o.pool() && i + 1 < r.net->n_ops && r.nimg >= 160 && !P.res && !P.out2;
+}
+
+int run_input(Run &r, int i, const OpView &o) {
+    dd_net *net = r.net; Held &h = r.held; hipStream_t s = r.s;
+    const int dst = o.dst();
+    const TensorDesc *td = &net->tensors[dst];
+    _Float16 *out; int cs, coff;
+    bind_tensor(net, dst, out, cs, coff);
+    const int m = r.nimg * td->h * td->w;
+    if (o.s2d() && o.hint() != HINT_NONE && !o.swap_rb() && cs == 32 && !coff && i + 1 < net->n_ops && net->use_rw) {   // only the next op reads it: the Focus fold
+        static const bool off = dd_env_int("DD_FOCUS_UNFUSED", 0) != 0;
+        if (!off && rw_shape_plain(op(net, i + 1), dst, ACT_SILU) && td->w % 32 == 0) {
+            h.input_on = true; h.input_mean = o.f(0); h.input_scale = o.f(1); h.input_op = i;
+            net->op_launch[i] = OPK_FOLDED;
+            return DD_OK;
         }
     }
-    for (int i = first_op; i < net->n_ops; ++i) {
-        if (net->profile) DD_HIP(hipEventRecord(net->events[i], s));
-        const int32_t *o = net->prog.data() + net->ops_off + (size_t)i * OP_WORDS;
-        const float *of = reinterpret_cast<const float *>(o);
-        const int kind = o[0], src = o[1], dst = o[2], res = o[3], dst2 = o[4];
-        const TensorDesc *ts = src >= 0 ? &net->tensors[src] : nullptr;
-        const TensorDesc *td = dst >= 0 ? &net->tensors[dst] : nullptr;
-        DD_REQUIRE(!input_pending || (kind == OP_CONV && i == input_op + 1), DD_E_STATE, "dd_net_forward: input op %d was folded into an op that did not take it", input_op);
-        if (mid_on && kind == 19 && i + 1 < net->n_ops && net->prog[net->ops_off + (size_t)(i + 1) * OP_WORDS] == 19) {   // two uint8 block ops: blocks 3 + 4 as one launch?
-            const int32_t *o4 = net->prog.data() + net->ops_off + (size_t)(i + 1) * OP_WORDS;
-            if (net->profile) DD_HIP(hipEventRecord(net->events[i + 1], s));
-            int ran = 0;
-            const int rc = netq_run_mid(net, o, o4, nimg, s, &ran);
-            if (rc != DD_OK) return rc;
-            if (ran) { net->op_launch[i] = OPK_FOLDED; net->op_launch[i + 1] = OPK_Q_MID; ++i; continue; }
+    if (o.s2d() && cs >= 16 && cs % 8 == 0) {
+        const int cpp = cs / 8;
+        DD_REQUIRE((long long)m * cpp < (1ll << 31), DD_E_CAPACITY, "dd_net_forward: %d x %d input chunks", m, cpp);
+        hipLaunchKernelGGL(input_s2d_chunks_k, dim3(dd_ceil_div(m * cpp, 256)), dim3(256), 0, s, r.input, net->in_h, net->in_w, o.swap_rb(),
+                           o.f(0), o.f(1), m * cpp, cpp, out + coff, cs);
+    } else
+    hipLaunchKernelGGL(input_k, dim3(dd_ceil_div(m, 256)), dim3(256), 0, s, r.input, net->in_h, net->in_w, o.swap_rb(),
+                       o.f(0), o.f(1), o.s2d(), m, out + coff, cs);
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
+template <int WM, int WN, int MI, int NI, int BK, bool GLDS>
+int conv_tile(Run &r, int i, ConvP &P) {
+    return launch_conv<WM, WN, MI, NI, BK, GLDS>(r.s, P, r.net->slab, r.net->max_batch, r.device(), &r.net->slab_moved, &r.net->op_variant[i]);
+}
+
+// The generic implicit-GEMM kernels: tile from the layer and the batch of the call.
+int launch_conv_tiled(Run &r, int i, ConvP &P, bool bk32, bool glds) {
+    const dd_net *net = r.net;
+    if (P.cout_pad <= 32) {
+        // 32 output channels: 128 pixels per block (each wave 32 px x 32 ch) once there are enough pixels
+        return bk32 ? conv_tile<4, 1, 1, 2, 32, false>(r, i, P)
+             : (glds && P.m >= 16384) ? conv_tile<4, 1, 2, 2, 64, true>(r, i, P)
+             : glds ? conv_tile<4, 1, 1, 2, 64, true>(r, i, P)
+                    : conv_tile<4, 1, 1, 2, 64, false>(r, i, P);
+    } else if (glds && net->tile_mode != 1 && P.m >= 16384 && P.cout_pad >= 128) {
+        // plenty of pixels: 128 x 128 with 8 waves -- a third less L2->LDS traffic per FLOP than 64 x 128
+        // (24.3 us vs 26.6 us for 19x19x512 -> 512 at 64 frames; at 10x10 it halves the block count and loses).
+        // A K-capped run shows ~40 % of such a launch is per-round cost (prologue, epilogue, a partly filled
+        // last round of the 512 resident blocks), so 192 x 128 is taken when it saves rounds:
+        // 724 -> 484 tiles for 19x19x512 at 64 frames is one round instead of two (21.3 -> 18.0 us).
+        const int gy128 = dd_ceil_div(P.cout_pad, 128);
+        const int c128 = dd_ceil_div(dd_ceil_div(P.m, 128) * gy128, 512) * 128;
+        const int c192 = dd_ceil_div(dd_ceil_div(P.m, 192) * gy128, 512) * 192;
+        if (P.epi == EPI_F16 && c192 <= c128 && net->tile_mode != 2) return conv_tile<4, 2, 3, 4, 64, true>(r, i, P);
+        return conv_tile<4, 2, 2, 4, 64, true>(r, i, P);
+    } else if (glds && net->tile_mode != 1 && P.m >= 16384 && P.cout_pad == 64) {
+        return conv_tile<4, 2, 2, 2, 64, true>(r, i, P);      // 128 x 64, 8 waves
+    } else if (glds && net->tile_mode != 1 && P.m >= 4096 && P.cout_pad >= 128) {
+        // 64 pixels x 128 channels: each staged pixel row feeds twice the MFMAs; measured 31 us vs 38 us
+        // for 19x19x512 -> 512 at 64 frames (128 x 64 gave nothing, 128 x 128 was 2.5x slower: 2 blocks/CU)
+        return conv_tile<2, 2, 2, 4, 64, true>(r, i, P);
+    }
+    return bk32 ? conv_tile<2, 2, 2, 2, 32, false>(r, i, P)
+         : glds ? conv_tile<2, 2, 2, 2, 64, true>(r, i, P)
+                : conv_tile<2, 2, 2, 2, 64, false>(r, i, P);
+}
+
+// A 3x3 32 -> 32 layer on conv3x3_rw_k and the launches built on it: whole filter in registers, input patch staged once.
+int run_conv3x3_rw(Run &r, int i, const OpView &o, ConvP &P) {
+    dd_net *net = r.net; Held &h = r.held; const int nimg = r.nimg;
+    int rc;
+    if (h.input_on) { h.input_on = false; P.src8 = r.input; P.in_mean = h.input_mean; P.in_scale = h.input_scale; }
+    if (o.pool()) { P.p[0] = net->tensors[o.dst()].h; P.p[1] = net->tensors[o.dst()].w; }      // fused 3x3/2 max pool: dst is the pooled tensor
+    if (h.wide_conv) {                                         // first layer + this layer + the max pool behind it: one launch at the pool op (checked at the first layer's op)
+        h.wide_conv = false;
+        const int pooled = op(net, i + 1).dst();
+        take_stem(P, h.stem);
+        bind_tensor(net, pooled, P.out, P.cs_out, P.coff_out); P.p[0] = net->tensors[pooled].h; P.p[1] = net->tensors[pooled].w;
+        h.stem = P; h.wide_pool = true; net->op_launch[i] = OPK_FOLDED;
+        return DD_OK;
+    }
+    if (h.stem_on) {
+        if (o.pool() && pool_rows_fusable(P, nimg) && h.stem.out == static_cast<const void *>(P.in) && !P.coff_in) {
+            h.stem_on = false;
+            take_stem(P, h.stem);
+        } else if ((rc = flush(r, HELD_STEM)) != DD_OK) return rc;
+    }
+    if (unit_first_layer(r, i, o, P)) {
+        if (h.pair_on && P.in != static_cast<const _Float16 *>(h.pair_b.out2) && (rc = flush(r, HELD_PAIR)) != DD_OK) return rc;
+        h.unit_a = P; h.unit_op = i; h.unit_on = true;         // only the next op reads this layer's output
+        net->op_launch[i] = OPK_FOLDED;
+        return DD_OK;
+    }
+    if (o.pool() && pool_rows_fusable(P, nimg)) net->op_launch[i] = P.src8 ? OPK_POOL_ROWS_STEM : OPK_POOL_ROWS;
+    return launch_conv3x3_rw(r.s, P, nimg, o.pool(), r.device());
+}
+
+int run_conv(Run &r, int i, const OpView &o) {
+    dd_net *net = r.net; Held &h = r.held; const int nimg = r.nimg; hipStream_t s = r.s;
+    int rc;
+    if (h.proj_done) {
+        if ((rc = refuse_fold_while_held(h, i)) != DD_OK) return rc;
+        h.proj_done = false; net->op_launch[i] = OPK_FOLDED_PREV;
+        return DD_OK;
+    }
+    if (h.pair64_left > 0) {                                   // inside a conv3_x block that runs as one launch: at its last op
+        if ((rc = refuse_fold_while_held(h, i)) != DD_OK) return rc;
+        if (--h.pair64_left > 0) { net->op_launch[i] = OPK_FOLDED; return DD_OK; }
+        if ((rc = mars_pair64_launch(s, r.device(), h.pair64, h.pair64_first)) != DD_OK) return rc;
+        net->op_launch[i] = OPK_MARS_PAIR;
+        return DD_OK;
+    }
+    if (o.hint() == HINT_NEXT_IS_PROJ || o.hint() == HINT_PAIR_MEMBER) {
+        const int n_ops = mars_pair_match(net, i, nimg, h.pair64, h.pair64_first);
+        if (n_ops) {
+            if ((rc = refuse_fold_while_held(h, i)) != DD_OK) return rc;
+            h.pair64_left = n_ops - 1; net->op_launch[i] = OPK_FOLDED;
+            return DD_OK;
         }
-        DD_REQUIRE((!wide_pending || kind == OP_CONV) && (!wide_ready || kind == OP_MAXPOOL), DD_E_STATE, "dd_net_forward: op %d does not take the first layer folded into it", i);
-        if (pair_pending && kind != OP_CONV) { const int rc = flush_pair(); if (rc != DD_OK) return rc; }
-        if (pw_pending && kind != OP_DWCONV) {
-            pw_pending = false; net->op_launch[i - 1] = OPK_CONV_WS;
-            const int rc = run_ws(pw_p);
-            if (rc != DD_OK) return rc;
+    }
+    ConvP P = conv_params(net, o, nimg);
+    DD_REQUIRE(!o.pool() || (net->use_rw && P.kh == 3 && P.stride == 1 && P.cin == 32 && P.cout_pad == 32), DD_E_ARG,
+               "dd_net_forward: fused pooling is only built for the 3x3 32->32 kernel");
+    if (h.unit_on) {                                           // the previous op was a residual unit's first layer
+        if (res_unit_fusable(h.unit_a, P, nimg)) {
+            h.unit_on = false;
+            P.zero = net->d_zero;
+            if (h.pair_on) {                                   // ... and the unit before is waiting for this one
+                if (res_pair_fusable(h.pair_a, h.pair_b, h.unit_a, P, nimg)) {
+                    h.pair_on = false;
+                    if ((rc = launch_res_pair(s, h.pair_a, h.pair_b, h.unit_a, P, nimg, r.device())) != DD_OK) return rc;
+                    net->op_launch[i] = OPK_RES_PAIR;          // ops i - 3 .. i - 1 stay "in the next launch"
+                    return DD_OK;
+                }
+                if ((rc = flush(r, HELD_PAIR)) != DD_OK) return rc;
+            }
+            // this unit's outputs are read by the next residual unit only -- hold it back, the two may run as one launch
+            if (o.hint() == HINT_HOLD_UNIT && i + 2 < net->n_ops) {
+                h.pair_a = h.unit_a; h.pair_b = P; h.pair_on = true; h.pair_op = i;
+                net->op_launch[i] = OPK_FOLDED;
+                return DD_OK;
+            }
+            if ((rc = launch_res_unit(s, h.unit_a, P, nimg, r.device())) != DD_OK) return rc;
+            net->op_launch[i] = OPK_RES_UNIT;
+            return DD_OK;
         }
-        if (unit_pending && kind != OP_CONV) {                        // (a program that sets the flag wrongly still computes the right thing)
-            unit_pending = false; net->op_launch[i - 1] = OPK_DEFAULT;
-            const int rc = launch_conv3x3_rw(s, unit_a, nimg, false, net->ctx->device);
-            if (rc != DD_OK) return rc;
+        if (h.pair_on && (rc = flush(r, HELD_PAIR)) != DD_OK) return rc;
+        if ((rc = flush(r, HELD_UNIT)) != DD_OK) return rc;
+    }
+    if (h.pair_on) {                                           // a held unit waits only for the first layer of the unit that reads it
+        const bool next_a = net->use_rw && rw_shape(P) && unit_first_layer(r, i, o, P) && P.in == static_cast<const _Float16 *>(h.pair_b.out2);
+        if (!next_a && (rc = flush(r, HELD_PAIR)) != DD_OK) return rc;
+    }
+    if (P.epi == EPI_YOLO && net->yolo_dec && o.aff_off() && !o.has_aff()) {      // aff_off / aux_off: the per-anchor copy of weights / bias
+        DD_REQUIRE(P.p[1] == net->dec_anchors, DD_E_ARG, "dd_net_forward: head of %d rows, decode set up for %d", P.p[1], net->dec_anchors);
+        P.w = blob<_Float16>(net, o.aff_off());
+        P.bias = blob<float>(net, o.aux_off());
+        P.zero = net->d_zero;
+        P.dec_boxes = net->dec_boxes; P.dec_score = net->dec_score; P.dec_cls = net->dec_cls;
+        if ((rc = launch_yolo_head_dec(s, P)) != DD_OK) return rc;
+        net->op_launch[i] = OPK_YOLO_HEAD_DEC;
+        return DD_OK;
+    }
+    if (P.epi == EPI_SSD_HEAD && net->ssd_dec && o.aff_off() && !o.has_aff()) {   // aff_off / aux_off: the per-anchor copy of weights / bias
+        DD_REQUIRE(P.p[1] == net->dec_anchors, DD_E_ARG, "dd_net_forward: head of %d anchors, decode set up for %d", P.p[1], net->dec_anchors);
+        P.w = blob<_Float16>(net, o.aff_off());
+        P.bias = blob<float>(net, o.aux_off());
+        P.zero = net->d_zero;
+        P.anchors = net->d_anchors; P.dec_boxes = net->dec_boxes; P.dec_score = net->dec_score; P.dec_keys = net->dec_keys;
+        P.dec_cls = net->dec_cls; P.dec_thr = net->dec_thr;
+        if ((rc = launch_ssd_head_dec(s, P)) != DD_OK) return rc;
+        net->op_launch[i] = OPK_SSD_HEAD_DEC;
+        return DD_OK;
+    }
+    const bool bk32 = o.bk() == 32;                            // shallow K (<= 96): one or few 32-wide steps
+    const bool glds = !bk32 && net->use_glds;                  // K >= 97: direct-to-LDS fills, any Cin % 8 == 0
+    P.zero = net->d_zero;
+    if (net->use_rw && rw_shape(P)) return run_conv3x3_rw(r, i, o, P);
+    if (mars_ws_s1_eligible(P)) {
+        const MarsWsP Q = mars_ws_params(P, nimg);
+        net->op_launch[i] = OPK_MARS_WS;
+        return mars_ws128_launch(s, r.device(), Q, P.res ? MARS_WS_S1_RES : MARS_WS_S1, P.act, P.out2 != nullptr);
+    } else if (o.hint() == HINT_NEXT_IS_PROJ && i + 1 < net->n_ops && mars_ws_s2_eligible(P) && mars_proj_follows(net, i, P)) {
+        // 3x3 stride-2 layer of a widening residual block + the 1x1 stride-2 projection of the block's raw input (the next op): one launch
+        const OpView q = op(net, i + 1);
+        MarsWsP Q = mars_ws_params(P, nimg);
+        bind_tensor(net, q.src(), Q.in2, Q.cs_in2, Q.coff_in2);
+        Q.w2 = blob<_Float16>(net, q.w_off()); Q.kpad2 = q.kpad();
+        Q.bias2 = blob<float>(net, q.bias_off());
+        bind_tensor(net, q.dst(), Q.out2, Q.cs_out2, Q.coff_out2);
+        net->op_launch[i] = OPK_MARS_WS;
+        rc = mars_ws128_launch(s, r.device(), Q, MARS_WS_S2_PROJ, P.act, false);
+        h.proj_done = true;
+        return rc;
+    } else if (s2_rows_eligible(P, nimg, net->max_batch)) {
+        net->op_launch[i] = OPK_S2_ROWS;
+        return launch_conv3x3_s2_rows(s, P, nimg, r.device());
+    } else if (c64_rows_eligible(P, nimg, net->max_batch)) {
+        net->op_launch[i] = OPK_C64_ROWS;
+        return launch_conv3x3_c64_rows(s, P, nimg, r.device());
+    } else if (c64_strips_eligible(P, nimg, net->max_batch)) {
+        net->op_launch[i] = OPK_C64_STRIPS;
+        return launch_conv3x3_c64_strips(s, P, nimg, r.device());
+    } else if (ws_eligible(P) && o.hint() != HINT_NONE && i + 1 < net->n_ops && P.act == ACT_RELU6) {
+        h.pw = P; h.pw_op = i; h.pw_on = true; net->op_launch[i] = OPK_FOLDED;     // only the next (depthwise) op reads this output
+        return DD_OK;
+    } else if (ws_eligible(P)) {
+        net->op_launch[i] = OPK_CONV_WS;
+        return launch_ws(r, P);
+    }
+    return launch_conv_tiled(r, i, P, bk32, glds);
+}
+
+int run_stem(Run &r, int i, const OpView &o) {
+    dd_net *net = r.net; Held &h = r.held; const int nimg = r.nimg;
+    const int dst = o.dst();
+    const TensorDesc *td = &net->tensors[dst];
+    ConvP P = conv_params(net, o, nimg);
+    P.src8 = r.input; P.H = net->in_h; P.W = net->in_w; P.in_mean = o.f(0); P.in_scale = o.f(1);
+    P.zero = net->d_zero;
+    P.kh = P.kw = 3; P.epi = EPI_F16; P.splitk = 1;
+    DD_REQUIRE(P.cout_pad == 32 && (P.stride == 1 || P.stride == 2), DD_E_ARG, "dd_net_forward: stem needs 32 output channels, stride 1 or 2");
+    const bool aligned = (reinterpret_cast<uintptr_t>(r.input) & 3) == 0;
+    const bool hinted = o.hint() != HINT_NONE;
+    // hinted: the next op is the pooled 3x3 layer reading this tensor and nothing else does -- with enough images
+    // both run as one launch (conv3x3_pool_rows_k<STEM>) and this tensor is never written
+    static const bool unfused = dd_env_int("DD_STEM_UNFUSED", 0) != 0;
+    if (hinted && !unfused && i + 1 < net->n_ops && P.stride == 1 && P.pad_t == 1 && P.pad_l == 1 && P.cout == 32 && P.act == ACT_ELU && P.W == 32 && aligned) {
+        h.stem = P; h.stem_op = i; h.stem_on = true; net->op_launch[i] = OPK_FOLDED;
+        return DD_OK;
+    }
+    // widths 64 / 128 (the 128 x 64 and 256 x 128 encoders): the next two ops are the 3x3 layer and its VALID 3x3/2 max pool, each the only
+    // reader of the tensor in front of it (the hint here; the 3x3 layer's output is looked up in the op list) -- from DD_STEM_WIDE_MIN crops the three run as one launch
+    // (stem_conv_pool_wide_k) and neither full-resolution tensor is written.  DD_STEM_WIDE=1 / 0: the one launch / always the three launches
+    // (default: STEM_WIDE_DEFAULT).  Read on every forward: a test flips them between two forwards of one process.
+    auto sole_reader = [&](int t, int reader) {       // no op but `reader` reads tensor t's buffer, and it is not the network's output
+        if (t < 0 || t == net->out_tensor) return false;
+        for (int k = 0; k < net->n_ops; ++k) {
+            const OpView w = op(net, k);
+            for (int a : {w.src(), w.res()})
+                if (k != reader && a >= 0 && net->tensors[a].buf == net->tensors[t].buf) return false;
         }
-        if (stem_pending && !(kind == OP_CONV && o[29]) && kind != OP_DWPW) {   // not followed by the layer it was meant for: run it on its own
-            stem_pending = false; net->op_launch[i - 1] = OPK_DEFAULT;
-            const int rc = launch_stem(s, stem_p, nimg);
-            if (rc != DD_OK) return rc;
+        return true;
+    };
+    const bool wide_off = dd_env_int("DD_STEM_WIDE", STEM_WIDE_DEFAULT ? 1 : 0) == 0;
+    const int wide_min = dd_env_int("DD_STEM_WIDE_MIN", STEM_WIDE_MIN_CROPS);
+    if (hinted && !wide_off && nimg >= wide_min && i + 2 < net->n_ops && net->use_rw && stem_wide_geometry(P.H, P.W) && P.stride == 1 &&
+        P.pad_t == 1 && P.pad_l == 1 && P.cout == 32 && P.act == ACT_ELU && !td->coff && aligned) {
+        const OpView q = op(net, i + 1), p = op(net, i + 2);       // the 3x3 layer, the pool
+        if (rw_shape_plain(q, dst, ACT_ELU) && q.cout() == 32 && q.hint() == HINT_NONE &&
+            p.kind() == OP_MAXPOOL && p.src() == q.dst() && p.pool_k() == 3 && p.pool_cascade() <= 1 && p.stride() == 2 && p.pad_t() == 0 && p.dst() >= 0 && sole_reader(q.dst(), i + 2) &&
+            net->tensors[p.dst()].h == P.H / 2 - 1 && net->tensors[p.dst()].w == P.W / 2 - 1 && net->tensors[p.dst()].c == 32) {
+            h.stem = P; h.wide_conv = true; net->op_launch[i] = OPK_FOLDED;
+            return DD_OK;
         }
-        switch (kind) {
-            case OP_INPUT: {
-                const int s2d = o[5];
-                const int m = nimg * td->h * td->w;
-                if (s2d && o[30] && !o[6] && td->cs == 32 && !td->coff && i + 1 < net->n_ops && net->use_rw) {   // o[30]: only the next op reads it
-                    const int32_t *q = net->prog.data() + net->ops_off + (size_t)(i + 1) * OP_WORDS;
-                    static const bool off = getenv("DD_FOCUS_UNFUSED") && atoi(getenv("DD_FOCUS_UNFUSED")) != 0;
-                    if (!off && q[0] == OP_CONV && q[1] == dst && q[5] == 3 && q[6] == 3 && q[7] == 1 && q[8] == 1 && q[9] == 1 && q[10] == 32 &&
-                        q[12] == 32 && q[14] == ACT_SILU && q[15] == EPI_F16 && q[3] < 0 && q[4] < 0 && !q[29] && td->w % 32 == 0) {
-                        input_pending = true; input_mean = of[32]; input_scale = of[33]; input_op = i;
-                        net->op_launch[i] = OPK_FOLDED;
-                        break;
-                    }
-                }
-                if (s2d && td->cs >= 16 && td->cs % 8 == 0) {
-                    const int cpp = td->cs / 8;
-                    DD_REQUIRE((long long)m * cpp < (1ll << 31), DD_E_CAPACITY, "dd_net_forward: %d x %d input chunks", m, cpp);
-                    hipLaunchKernelGGL(input_s2d_chunks_k, dim3(dd_ceil_div(m * cpp, 256)), dim3(256), 0, s, input, net->in_h, net->in_w, o[6],
-                                       of[32], of[33], m * cpp, cpp, reinterpret_cast<_Float16 *>(base(dst)) + td->coff, td->cs);
-                } else
-                hipLaunchKernelGGL(input_k, dim3(dd_ceil_div(m, 256)), dim3(256), 0, s, input, net->in_h, net->in_w, o[6],
-                                   of[32], of[33], s2d, m, reinterpret_cast<_Float16 *>(base(dst)) + td->coff, td->cs);
-                DD_LAUNCH_CHECK();
-                break;
-            }
-            case OP_CONV: {
-                // (the early exits below skip the held-back launches' flush further down: a program that puts a held residual unit, stem or
-                // pointwise layer directly in front of a folded op is refused instead of silently never writing it)
-#define DD_NO_PENDING() DD_REQUIRE(!unit_pending && !pair_pending && !stem_pending && !pw_pending && !input_pending, DD_E_STATE, \
-                                   "dd_net_forward: op %d is folded into a neighbouring launch while an earlier op's launch is still held back", i)
-                if (proj_done) { DD_NO_PENDING(); proj_done = false; net->op_launch[i] = OPK_FOLDED_PREV; break; }
-                if (pair_left > 0) {                               // inside a conv3_x block that runs as one launch: at its last op
-                    DD_NO_PENDING();
-                    if (--pair_left > 0) { net->op_launch[i] = OPK_FOLDED; break; }
-                    const int rc = mars_pair64_launch(s, net->ctx->device, pair64, pair64_first);
-                    if (rc != DD_OK) return rc;
-                    net->op_launch[i] = OPK_MARS_PAIR;
-                    break;
-                }
-                if (o[30] == 3 || o[30] == 4) {
-                    const int n_ops = mars_pair_match(net, i, nimg, pair64, pair64_first);
-                    if (n_ops) { DD_NO_PENDING(); pair_left = n_ops - 1; net->op_launch[i] = OPK_FOLDED; break; }
-                }
-#undef DD_NO_PENDING
-                ConvP P;
-                memset(&P, 0, sizeof(P));
-                P.in = reinterpret_cast<const _Float16 *>(base(src)); P.H = ts->h; P.W = ts->w; P.cs_in = ts->cs;
-                P.coff_in = ts->coff; P.cin = o[10];
-                P.kh = o[5]; P.kw = o[6]; P.stride = o[7]; P.pad_t = o[8]; P.pad_l = o[9];
-                P.cout = o[11]; P.cout_pad = o[12]; P.kpad = o[13]; P.act = o[14]; P.epi = o[15];
-                P.w = reinterpret_cast<const _Float16 *>(net->d_weights + (size_t)(uint32_t)o[16]);
-                P.bias = reinterpret_cast<const float *>(net->d_weights + (size_t)(uint32_t)o[17]);
-                P.ho = o[26]; P.wo = o[27]; P.m = nimg * P.ho * P.wo;      // conv grid (dst may be a head matrix)
-                P.out = base(dst); P.cs_out = td->cs; P.coff_out = td->coff;
-                if (res >= 0) {
-                    const TensorDesc &tr = net->tensors[res];
-                    P.res = reinterpret_cast<const _Float16 *>(base(res)); P.cs_res = tr.cs; P.coff_res = tr.coff;
-                }
-                if (dst2 >= 0) {
-                    const TensorDesc &t2 = net->tensors[dst2];
-                    P.out2 = reinterpret_cast<_Float16 *>(base(dst2)); P.cs_out2 = t2.cs; P.coff_out2 = t2.coff;
-                    P.aff2 = reinterpret_cast<const float *>(net->d_weights + (size_t)(uint32_t)o[18]);
-                }
-                if (dst2 < 0 && o[19]) {                       // EPI_F32 with a post-activation affine (MARS fc1 + "ball")
-                    P.aff2 = reinterpret_cast<const float *>(net->d_weights + (size_t)(uint32_t)o[18]);
-                    P.post_aff = 1;
-                }
-                for (int q = 0; q < 6; ++q) P.p[q] = o[20 + q];
-                for (int q = 0; q < 8; ++q) P.f[q] = of[32 + q];
-                int rc;
-                DD_REQUIRE(!o[29] || (net->use_rw && P.kh == 3 && P.stride == 1 && P.cin == 32 && P.cout_pad == 32), DD_E_ARG,
-                           "dd_net_forward: fused pooling is only built for the 3x3 32->32 kernel");
-                if (unit_pending) {                            // the previous op was a residual unit's first layer
-                    unit_pending = false;
-                    if (res_unit_fusable(unit_a, P, nimg)) {
-                        P.zero = net->d_zero;
-                        if (pair_pending) {                        // ... and the unit before is waiting for this one
-                            if (res_pair_fusable(pair_a, pair_b, unit_a, P, nimg)) {
-                                pair_pending = false;
-                                rc = launch_res_pair(s, pair_a, pair_b, unit_a, P, nimg, net->ctx->device);
-                                if (rc != DD_OK) return rc;
-                                net->op_launch[i] = OPK_RES_PAIR;  // ops i - 3 .. i - 1 stay "in the next launch"
-                                break;
-                            }
-                            if ((rc = flush_pair()) != DD_OK) return rc;
-                        }
-                        // o[30] == 2: this unit's outputs are read by the next residual unit only -- hold it back, the two may run as one launch
-                        if (o[30] == 2 && i + 2 < net->n_ops) {
-                            pair_a = unit_a; pair_b = P; pair_pending = true; pair_op = i;
-                            net->op_launch[i] = OPK_FOLDED;
-                            break;
-                        }
-                        rc = launch_res_unit(s, unit_a, P, nimg, net->ctx->device);
-                        if (rc != DD_OK) return rc;
-                        net->op_launch[i] = OPK_RES_UNIT;
-                        break;
-                    }
-                    if (pair_pending && (rc = flush_pair()) != DD_OK) return rc;
-                    net->op_launch[i - 1] = OPK_DEFAULT;
-                    rc = launch_conv3x3_rw(s, unit_a, nimg, false, net->ctx->device);
-                    if (rc != DD_OK) return rc;
-                }
-                if (pair_pending) {                            // a held unit waits only for the first layer of the unit that reads it
-                    const bool next_a = net->use_rw && P.kh == 3 && P.kw == 3 && P.stride == 1 && P.cin == 32 && P.cout_pad == 32 && P.epi == EPI_F16 &&
-                                        P.pad_t == 1 && P.pad_l == 1 && o[30] && !o[29] && i + 1 < net->n_ops && nimg >= 160 && !P.res && !P.out2 &&
-                                        P.in == static_cast<const _Float16 *>(pair_b.out2);
-                    if (!next_a && (rc = flush_pair()) != DD_OK) return rc;
-                }
-                if (P.epi == EPI_YOLO && net->yolo_dec && o[18] && !o[19]) {      // o[18] / o[31]: the per-anchor copy of weights / bias
-                    DD_REQUIRE(P.p[1] == net->dec_anchors, DD_E_ARG, "dd_net_forward: head of %d rows, decode set up for %d", P.p[1], net->dec_anchors);
-                    P.w = reinterpret_cast<const _Float16 *>(net->d_weights + (size_t)(uint32_t)o[18]);
-                    P.bias = reinterpret_cast<const float *>(net->d_weights + (size_t)(uint32_t)o[31]);
-                    P.zero = net->d_zero;
-                    P.dec_boxes = net->dec_boxes; P.dec_score = net->dec_score; P.dec_cls = net->dec_cls;
-                    rc = launch_yolo_head_dec(s, P);
-                    if (rc != DD_OK) return rc;
-                    net->op_launch[i] = OPK_YOLO_HEAD_DEC;
-                    break;
-                }
-                if (P.epi == EPI_SSD_HEAD && net->ssd_dec && o[18] && !o[19]) {   // o[18] / o[31]: the per-anchor copy of weights / bias
-                    DD_REQUIRE(P.p[1] == net->dec_anchors, DD_E_ARG, "dd_net_forward: head of %d anchors, decode set up for %d", P.p[1], net->dec_anchors);
-                    P.w = reinterpret_cast<const _Float16 *>(net->d_weights + (size_t)(uint32_t)o[18]);
-                    P.bias = reinterpret_cast<const float *>(net->d_weights + (size_t)(uint32_t)o[31]);
-                    P.zero = net->d_zero;
-                    P.anchors = net->d_anchors; P.dec_boxes = net->dec_boxes; P.dec_score = net->dec_score; P.dec_keys = net->dec_keys;
-                    P.dec_cls = net->dec_cls; P.dec_thr = net->dec_thr;
-                    rc = launch_ssd_head_dec(s, P);
-                    if (rc != DD_OK) return rc;
-                    net->op_launch[i] = OPK_SSD_HEAD_DEC;
-                    break;
-                }
-                const bool bk32 = o[28] == 32;                 // shallow K (<= 96): one or few 32-wide steps
-                const bool glds = !bk32 && net->use_glds;          // K >= 97: direct-to-LDS fills, any Cin % 8 == 0
-                P.zero = net->d_zero;
-                if (net->use_rw && P.kh == 3 && P.kw == 3 && P.stride == 1 && P.cin == 32 && P.cout_pad == 32 &&
-                    P.epi == EPI_F16 && P.pad_t == 1 && P.pad_l == 1) {
-                    // whole filter in registers, input patch staged once (see conv3x3_rw_k)
-                    if (input_pending) { input_pending = false; P.src8 = input; P.in_mean = input_mean; P.in_scale = input_scale; }
-                    if (o[29]) { P.p[0] = td->h; P.p[1] = td->w; }      // fused 3x3/2 max pool: dst is the pooled tensor
-                    if (wide_pending) {                        // first layer + this layer + the max pool behind it: one launch at the pool op (checked at the first layer's op)
-                        wide_pending = false;
-                        const int32_t *r = o + OP_WORDS;
-                        const TensorDesc &tp = net->tensors[r[2]];
-                        P.src8 = stem_p.src8; P.in_mean = stem_p.in_mean; P.in_scale = stem_p.in_scale;
-                        P.dw_w = stem_p.w; P.dw_bias = stem_p.bias; P.dw_act = stem_p.act;
-                        P.out = base(r[2]); P.cs_out = tp.cs; P.coff_out = tp.coff; P.p[0] = tp.h; P.p[1] = tp.w;
-                        stem_p = P; wide_ready = true; net->op_launch[i] = OPK_FOLDED;
-                        break;
-                    }
-                    if (stem_pending) {
-                        stem_pending = false;
-                        if (o[29] && pool_rows_fusable(P, nimg) && stem_p.out == static_cast<const void *>(P.in) && !P.coff_in) {
-                            P.src8 = stem_p.src8; P.in_mean = stem_p.in_mean; P.in_scale = stem_p.in_scale;
-                            P.dw_w = stem_p.w; P.dw_bias = stem_p.bias; P.dw_act = stem_p.act;
-                        } else {
-                            net->op_launch[i - 1] = OPK_DEFAULT;
-                            rc = launch_stem(s, stem_p, nimg);
-                            if (rc != DD_OK) return rc;
-                        }
-                    }
-                    if (o[30] && !o[29] && i + 1 < net->n_ops && nimg >= 160 && !P.res && !P.out2) {
-                        if (pair_pending && P.in != static_cast<const _Float16 *>(pair_b.out2) && (rc = flush_pair()) != DD_OK) return rc;
-                        unit_a = P; unit_pending = true;       // o[30]: only the next op reads this layer's output
-                        net->op_launch[i] = OPK_FOLDED;
-                        break;
-                    }
-                    if (o[29] && pool_rows_fusable(P, nimg)) net->op_launch[i] = P.src8 ? OPK_POOL_ROWS_STEM : OPK_POOL_ROWS;
-                    rc = launch_conv3x3_rw(s, P, nimg, o[29] != 0, net->ctx->device);
-                } else if (mars_ws_s1_eligible(P)) {
-                    const MarsWsP Q = mars_ws_params(P, nimg);
-                    net->op_launch[i] = OPK_MARS_WS;
-                    rc = mars_ws128_launch(s, net->ctx->device, Q, P.res ? MARS_WS_S1_RES : MARS_WS_S1, P.act, P.out2 != nullptr);
-                } else if (o[30] == 3 && i + 1 < net->n_ops && mars_ws_s2_eligible(P) && mars_proj_follows(net, i, P)) {
-                    // 3x3 stride-2 layer of a widening residual block + the 1x1 stride-2 projection of the block's raw input (the next op): one launch
-                    const int32_t *q = net->prog.data() + net->ops_off + (size_t)(i + 1) * OP_WORDS;
-                    const TensorDesc &qs = net->tensors[q[1]], &qd = net->tensors[q[2]];
-                    MarsWsP Q = mars_ws_params(P, nimg);
-                    Q.in2 = reinterpret_cast<const _Float16 *>(base(q[1])); Q.cs_in2 = qs.cs; Q.coff_in2 = qs.coff;
-                    Q.w2 = reinterpret_cast<const _Float16 *>(net->d_weights + (size_t)(uint32_t)q[16]); Q.kpad2 = q[13];
-                    Q.bias2 = reinterpret_cast<const float *>(net->d_weights + (size_t)(uint32_t)q[17]);
-                    Q.out2 = reinterpret_cast<_Float16 *>(base(q[2])); Q.cs_out2 = qd.cs; Q.coff_out2 = qd.coff;
-                    net->op_launch[i] = OPK_MARS_WS;
-                    rc = mars_ws128_launch(s, net->ctx->device, Q, MARS_WS_S2_PROJ, P.act, false);
-                    proj_done = true;
-                } else if (s2_rows_eligible(P, nimg, net->max_batch)) {
-                    net->op_launch[i] = OPK_S2_ROWS;
-                    rc = launch_conv3x3_s2_rows(s, P, nimg, net->ctx->device);
-                } else if (c64_rows_eligible(P, nimg, net->max_batch)) {
-                    net->op_launch[i] = OPK_C64_ROWS;
-                    rc = launch_conv3x3_c64_rows(s, P, nimg, net->ctx->device);
-                } else if (c64_strips_eligible(P, nimg, net->max_batch)) {
-                    net->op_launch[i] = OPK_C64_STRIPS;
-                    rc = launch_conv3x3_c64_strips(s, P, nimg, net->ctx->device);
-                } else if (ws_eligible(P) && o[30] && i + 1 < net->n_ops && P.act == ACT_RELU6) {
-                    pw_p = P; pw_pending = true; net->op_launch[i] = OPK_FOLDED;     // o[30]: only the next (depthwise) op reads this output
-                    break;
-                } else if (ws_eligible(P)) {
-                    net->op_launch[i] = OPK_CONV_WS;
-                    rc = P.cin == 256 ? launch_conv_ws<4>(s, P, net->ctx->device) : launch_conv_ws<8>(s, P, net->ctx->device);
-                } else if (P.cout_pad <= 32) {
-                    // 32 output channels: 128 pixels per block (each wave 32 px x 32 ch) once there are enough pixels
-                    rc = bk32 ? launch_conv<4, 1, 1, 2, 32, false>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i])
-                       : (glds && P.m >= 16384) ? launch_conv<4, 1, 2, 2, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i])
-                       : glds ? launch_conv<4, 1, 1, 2, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i])
-                              : launch_conv<4, 1, 1, 2, 64, false>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i]);
-                } else if (glds && net->tile_mode != 1 && P.m >= 16384 && P.cout_pad >= 128) {
-                    // plenty of pixels: 128 x 128 with 8 waves -- a third less L2->LDS traffic per FLOP than 64 x 128
-                    // (24.3 us vs 26.6 us for 19x19x512 -> 512 at 64 frames; at 10x10 it halves the block count and loses).
-                    // A K-capped run shows ~40 % of such a launch is per-round cost (prologue, epilogue, a partly filled
-                    // last round of the 512 resident blocks), so 192 x 128 is taken when it saves rounds:
-                    // 724 -> 484 tiles for 19x19x512 at 64 frames is one round instead of two (21.3 -> 18.0 us).
-                    const int gy128 = dd_ceil_div(P.cout_pad, 128);
-                    const int c128 = dd_ceil_div(dd_ceil_div(P.m, 128) * gy128, 512) * 128;
-                    const int c192 = dd_ceil_div(dd_ceil_div(P.m, 192) * gy128, 512) * 192;
-                    if (P.epi == EPI_F16 && c192 <= c128 && net->tile_mode != 2)
-                        rc = launch_conv<4, 2, 3, 4, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i]);
-                    else
-                        rc = launch_conv<4, 2, 2, 4, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i]);
-                } else if (glds && net->tile_mode != 1 && P.m >= 16384 && P.cout_pad == 64) {
-                    rc = launch_conv<4, 2, 2, 2, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i]);      // 128 x 64, 8 waves
-                } else if (glds && net->tile_mode != 1 && P.m >= 4096 && P.cout_pad >= 128) {
-                    // 64 pixels x 128 channels: each staged pixel row feeds twice the MFMAs; measured 31 us vs 38 us
-                    // for 19x19x512 -> 512 at 64 frames (128 x 64 gave nothing, 128 x 128 was 2.5x slower: 2 blocks/CU)
-                    rc = launch_conv<2, 2, 2, 4, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i]);
-                } else {
-                    rc = bk32 ? launch_conv<2, 2, 2, 2, 32, false>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i])
-                       : glds ? launch_conv<2, 2, 2, 2, 64, true>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i])
-                              : launch_conv<2, 2, 2, 2, 64, false>(s, P, net->slab, net->max_batch, net->ctx->device, &net->slab_moved, &net->op_variant[i]);
-                }
-                if (rc != DD_OK) return rc;
-                break;
-            }
-            case OP_STEM: {
-                ConvP P;
-                memset(&P, 0, sizeof(P));
-                P.src8 = input; P.H = net->in_h; P.W = net->in_w; P.in_mean = of[32]; P.in_scale = of[33];
-                P.zero = net->d_zero;
-                P.kh = P.kw = 3; P.stride = o[7]; P.pad_t = o[8]; P.pad_l = o[9];
-                P.cout = o[11]; P.cout_pad = o[12]; P.act = o[14]; P.epi = EPI_F16; P.splitk = 1;
-                DD_REQUIRE(P.cout_pad == 32 && (P.stride == 1 || P.stride == 2), DD_E_ARG, "dd_net_forward: stem needs 32 output channels, stride 1 or 2");
-                P.w = reinterpret_cast<const _Float16 *>(net->d_weights + (size_t)(uint32_t)o[16]);
-                P.bias = reinterpret_cast<const float *>(net->d_weights + (size_t)(uint32_t)o[17]);
-                P.ho = td->h; P.wo = td->w; P.m = nimg * P.ho * P.wo;
-                P.out = base(dst); P.cs_out = td->cs; P.coff_out = td->coff;
-                // o[30]: the next op is the pooled 3x3 layer reading this tensor and nothing else does -- with enough images
-                // both run as one launch (conv3x3_pool_rows_k<STEM>) and this tensor is never written
-                static const bool unfused = getenv("DD_STEM_UNFUSED") && atoi(getenv("DD_STEM_UNFUSED")) != 0;
-                if (o[30] && !unfused && i + 1 < net->n_ops && P.stride == 1 && P.pad_t == 1 && P.pad_l == 1 && P.cout == 32 && P.act == ACT_ELU &&
-                    P.W == 32 && (reinterpret_cast<uintptr_t>(input) & 3) == 0) {
-                    stem_p = P; stem_pending = true; net->op_launch[i] = OPK_FOLDED;
-                    break;
-                }
-                // widths 64 / 128 (the 128 x 64 and 256 x 128 encoders): the next two ops are the 3x3 layer and its VALID 3x3/2 max pool, each the only
-                // reader of the tensor in front of it (o[30] here; the 3x3 layer's output is looked up in the op list) -- from DD_STEM_WIDE_MIN crops the three run as one launch
-                // (stem_conv_pool_wide_k) and neither full-resolution tensor is written.  DD_STEM_WIDE=1 / 0: the one launch / always the three launches
-                // (default: STEM_WIDE_DEFAULT).  Read on every forward: a test flips them between two forwards of one process.
-                auto sole_reader = [&](int t, int reader) {       // no op but `reader` reads tensor t's buffer, and it is not the network's output
-                    if (t < 0 || t == net->out_tensor) return false;
-                    for (int k = 0; k < net->n_ops; ++k) {
-                        const int32_t *w = net->prog.data() + net->ops_off + (size_t)k * OP_WORDS;
-                        for (int a : {w[1], w[3]})
-                            if (k != reader && a >= 0 && net->tensors[a].buf == net->tensors[t].buf) return false;
-                    }
-                    return true;
-                };
-                const char *wide_env = getenv("DD_STEM_WIDE"), *wide_min_env = getenv("DD_STEM_WIDE_MIN");
-                const bool wide_off = wide_env ? atoi(wide_env) == 0 : !STEM_WIDE_DEFAULT;
-                const int wide_min = wide_min_env ? atoi(wide_min_env) : STEM_WIDE_MIN_CROPS;
-                if (o[30] && !wide_off && nimg >= wide_min && i + 2 < net->n_ops && net->use_rw && stem_wide_geometry(P.H, P.W) && P.stride == 1 &&
-                    P.pad_t == 1 && P.pad_l == 1 && P.cout == 32 && P.act == ACT_ELU && !td->coff && (reinterpret_cast<uintptr_t>(input) & 3) == 0) {
-                    const int32_t *q = o + OP_WORDS, *r = o + 2 * OP_WORDS;
-                    if (q[0] == OP_CONV && q[1] == dst && q[5] == 3 && q[6] == 3 && q[7] == 1 && q[8] == 1 && q[9] == 1 && q[10] == 32 && q[11] == 32 && q[12] == 32 &&
-                        q[14] == ACT_ELU && q[15] == EPI_F16 && q[3] < 0 && q[4] < 0 && !q[29] && !q[30] &&
-                        r[0] == OP_MAXPOOL && r[1] == q[2] && r[5] == 3 && r[6] <= 1 && r[7] == 2 && r[8] == 0 && r[2] >= 0 && sole_reader(q[2], i + 2) &&
-                        net->tensors[r[2]].h == P.H / 2 - 1 && net->tensors[r[2]].w == P.W / 2 - 1 && net->tensors[r[2]].c == 32) {
-                        stem_p = P; wide_pending = true; net->op_launch[i] = OPK_FOLDED;
-                        break;
-                    }
-                }
-                if (o[30] && i + 1 < net->n_ops && P.stride == 2) {       // followed by the first MobileNet block (ssd_front_k)
-                    stem_p = P; stem_p.zero = net->d_zero; stem_pending = true; net->op_launch[i] = OPK_FOLDED;
-                    break;
-                }
-                int rc = launch_stem(s, P, nimg);
-                if (rc != DD_OK) return rc;
-                break;
-            }
-            case OP_DWPW: {
-                ConvP P;
-                memset(&P, 0, sizeof(P));
-                P.in = reinterpret_cast<const _Float16 *>(base(src)); P.H = ts->h; P.W = ts->w; P.cs_in = ts->cs;
-                P.coff_in = ts->coff; P.cin = o[10];
-                P.kh = P.kw = 1; P.stride = o[7]; P.pad_t = o[8]; P.pad_l = o[9];
-                P.cout = o[11]; P.cout_pad = o[12]; P.kpad = o[13]; P.act = o[14]; P.epi = EPI_F16; P.splitk = 1;
-                P.w = reinterpret_cast<const _Float16 *>(net->d_weights + (size_t)(uint32_t)o[16]);
-                P.bias = reinterpret_cast<const float *>(net->d_weights + (size_t)(uint32_t)o[17]);
-                P.dw_w = reinterpret_cast<const _Float16 *>(net->d_weights + (size_t)(uint32_t)o[20]);
-                P.dw_bias = reinterpret_cast<const float *>(net->d_weights + (size_t)(uint32_t)o[21]);
-                P.dw_act = o[22]; P.zero = net->d_zero;
-                P.ho = td->h; P.wo = td->w; P.m = nimg * P.ho * P.wo;
-                P.total_quads = nimg * P.ho * ((P.wo + 3) / 4);
-                P.out = base(dst); P.cs_out = td->cs; P.coff_out = td->coff;
-                int rc;
-                if (stem_pending) {
-                    stem_pending = false;
-                    if (ssd_front_fusable(stem_p, P, nimg)) {
-                        rc = launch_ssd_front(s, stem_p, P, nimg, net->ctx->device);
-                        if (rc != DD_OK) return rc;
-                        net->op_launch[i] = OPK_SSD_FRONT;
-                        break;
-                    }
-                    net->op_launch[i - 1] = OPK_DEFAULT;
-                    rc = launch_stem(s, stem_p, nimg);
-                    if (rc != DD_OK) return rc;
-                }
-                if (P.cin == 32 && P.cout_pad == 64 && P.stride == 1) rc = launch_dwpw<4, 1, 4, 32, 1>(s, P, net->ctx->device);
-                else if (P.cin == 64 && P.cout_pad == 128 && P.stride == 2) rc = launch_dwpw<2, 2, 4, 64, 2>(s, P, net->ctx->device);
-                else if (dwpw_rows_eligible(P, nimg)) { net->op_launch[i] = OPK_DWPW_ROWS; rc = launch_dwpw_rows(s, P, nimg, net->ctx->device); }
-                else if (P.cin == 128 && P.cout_pad == 128 && P.stride == 1) rc = launch_dwpw<2, 2, 2, 128, 1>(s, P, net->ctx->device);
-                else if (P.cin == 128 && P.cout_pad == 256 && P.stride == 2) rc = launch_dwpw<1, 4, 4, 128, 2>(s, P, net->ctx->device);
-                else if (P.cin >= 256 && P.cin % 64 == 0 && P.cin <= 1024 && P.cout_pad % DWB_BN == 0 && P.kpad == P.cin)
-                    rc = P.stride == 1 ? launch_dwpw_big<1>(s, P, net->ctx->device, nimg) : launch_dwpw_big<2>(s, P, net->ctx->device, nimg);
-                else DD_REQUIRE(false, DD_E_ARG, "dd_net_forward: no fused dw+pw kernel for %d -> %d stride %d", P.cin, P.cout_pad, P.stride);
-                if (rc != DD_OK) return rc;
-                break;
-            }
-            case OP_DWCONV: {
-                DwP P;
-                P.in = reinterpret_cast<const _Float16 *>(base(src)); P.H = ts->h; P.W = ts->w; P.cs_in = ts->cs; P.coff_in = ts->coff;
-                P.w = reinterpret_cast<const _Float16 *>(net->d_weights + (size_t)(uint32_t)o[16]);
-                P.bias = reinterpret_cast<const float *>(net->d_weights + (size_t)(uint32_t)o[17]);
-                P.stride = o[7]; P.pad_t = o[8]; P.pad_l = o[9]; P.ho = td->h; P.wo = td->w; P.c = o[12];
-                P.m = nimg * td->h * td->w; P.act = o[14];
-                P.out = reinterpret_cast<_Float16 *>(base(dst)); P.cs_out = td->cs; P.coff_out = td->coff;
-                P.zero = net->d_zero;
-                if (pw_pending) {
-                    pw_pending = false;
-                    if (ws_dw_fusable(pw_p, P, nimg)) {
-                        const int rc = P.W == 10 ? (pw_p.cin == 256 ? launch_conv_ws_dw<4, 10>(s, pw_p, P, nimg, net->ctx->device) : launch_conv_ws_dw<8, 10>(s, pw_p, P, nimg, net->ctx->device))
-                                                 : (pw_p.cin == 256 ? launch_conv_ws_dw<4, 19>(s, pw_p, P, nimg, net->ctx->device) : launch_conv_ws_dw<8, 19>(s, pw_p, P, nimg, net->ctx->device));
-                        if (rc != DD_OK) return rc;
-                        net->op_launch[i] = OPK_WS_DW;
-                        break;
-                    }
-                    net->op_launch[i - 1] = OPK_CONV_WS;
-                    const int rc = run_ws(pw_p);
-                    if (rc != DD_OK) return rc;
-                }
-                static const bool two_rows = getenv("DD_DW_ONE_ROW") == nullptr;              // A/B switch
-                const int ty = (P.stride == 1 && two_rows) ? 2 : 1;
-                const long long total = (long long)nimg * ((P.ho + ty - 1) / ty) * ((P.wo + 3) / 4) * (P.c >> 3);
-                DD_REQUIRE(total < (1LL << 31), DD_E_CAPACITY, "dd_net_forward: depthwise layer of %lld items exceeds 32-bit indexing", total);
-                DD_REQUIRE(P.stride == 1 || P.stride == 2, DD_E_ARG, "dd_net_forward: depthwise stride %d", P.stride);
-                const dim3 grid((unsigned)((total + 255) / 256));
+    }
+    if (hinted && i + 1 < net->n_ops && P.stride == 2) {       // followed by the first MobileNet block (ssd_front_k)
+        h.stem = P; h.stem_op = i; h.stem_on = true; net->op_launch[i] = OPK_FOLDED;
+        return DD_OK;
+    }
+    return launch_stem(r.s, P, nimg);
+}
+
+int run_dwpw(Run &r, int i, const OpView &o) {
+    dd_net *net = r.net; Held &h = r.held; const int nimg = r.nimg; hipStream_t s = r.s;
+    ConvP P = conv_params(net, o, nimg);
+    P.kh = P.kw = 1; P.epi = EPI_F16; P.splitk = 1;
+    P.dw_w = blob<_Float16>(net, (uint32_t)o.p(0));
+    P.dw_bias = blob<float>(net, (uint32_t)o.p(1));
+    P.dw_act = o.p(2); P.zero = net->d_zero;
+    P.total_quads = nimg * P.ho * ((P.wo + 3) / 4);
+    int rc;
+    if (h.stem_on) {
+        if (ssd_front_fusable(h.stem, P, nimg)) {
+            h.stem_on = false;
+            if ((rc = launch_ssd_front(s, h.stem, P, nimg, r.device())) != DD_OK) return rc;
+            net->op_launch[i] = OPK_SSD_FRONT;
+            return DD_OK;
+        }
+        if ((rc = flush(r, HELD_STEM)) != DD_OK) return rc;
+    }
+    if (P.cin == 32 && P.cout_pad == 64 && P.stride == 1) return launch_dwpw<4, 1, 4, 32, 1>(s, P, r.device());
+    if (P.cin == 64 && P.cout_pad == 128 && P.stride == 2) return launch_dwpw<2, 2, 4, 64, 2>(s, P, r.device());
+    if (dwpw_rows_eligible(P, nimg)) { net->op_launch[i] = OPK_DWPW_ROWS; return launch_dwpw_rows(s, P, nimg, r.device()); }
+    if (P.cin == 128 && P.cout_pad == 128 && P.stride == 1) return launch_dwpw<2, 2, 2, 128, 1>(s, P, r.device());
+    if (P.cin == 128 && P.cout_pad == 256 && P.stride == 2) return launch_dwpw<1, 4, 4, 128, 2>(s, P, r.device());
+    if (P.cin >= 256 && P.cin % 64 == 0 && P.cin <= 1024 && P.cout_pad % DWB_BN == 0 && P.kpad == P.cin)
+        return P.stride == 1 ? launch_dwpw_big<1>(s, P, r.device(), nimg) : launch_dwpw_big<2>(s, P, r.device(), nimg);
+    DD_REQUIRE(false, DD_E_ARG, "dd_net_forward: no fused dw+pw kernel for %d -> %d stride %d", P.cin, P.cout_pad, P.stride);
+    return DD_OK;
+}
+
+int run_dwconv(Run &r, int i, const OpView &o) {
+    dd_net *net = r.net; Held &h = r.held; const int nimg = r.nimg; hipStream_t s = r.s;
+    const TensorDesc *ts = &net->tensors[o.src()], *td = &net->tensors[o.dst()];
+    DwP P;
+    bind_tensor(net, o.src(), P.in, P.cs_in, P.coff_in); P.H = ts->h; P.W = ts->w;
+    P.w = blob<_Float16>(net, o.w_off());
+    P.bias = blob<float>(net, o.bias_off());
+    P.stride = o.stride(); P.pad_t = o.pad_t(); P.pad_l = o.pad_l(); P.ho = td->h; P.wo = td->w; P.c = o.cout_pad();
+    P.m = nimg * td->h * td->w; P.act = o.act();
+    bind_tensor(net, o.dst(), P.out, P.cs_out, P.coff_out);
+    P.zero = net->d_zero;
+    if (h.pw_on) {
+        if (ws_dw_fusable(h.pw, P, nimg)) {
+            h.pw_on = false;
+            const int rc = P.W == 10 ? (h.pw.cin == 256 ? launch_conv_ws_dw<4, 10>(s, h.pw, P, nimg, r.device()) : launch_conv_ws_dw<8, 10>(s, h.pw, P, nimg, r.device()))
+                                     : (h.pw.cin == 256 ? launch_conv_ws_dw<4, 19>(s, h.pw, P, nimg, r.device()) : launch_conv_ws_dw<8, 19>(s, h.pw, P, nimg, r.device()));
+            if (rc != DD_OK) return rc;
+            net->op_launch[i] = OPK_WS_DW;
+            return DD_OK;
+        }
+        const int rc = flush(r, HELD_PW);
+        if (rc != DD_OK) return rc;
+    }
+    static const bool two_rows = !dd_env_set("DD_DW_ONE_ROW");              // A/B switch
+    const int ty = (P.stride == 1 && two_rows) ? 2 : 1;
+    const long long total = (long long)nimg * ((P.ho + ty - 1) / ty) * ((P.wo + 3) / 4) * (P.c >> 3);
+    DD_REQUIRE(total < (1LL << 31), DD_E_CAPACITY, "dd_net_forward: depthwise layer of %lld items exceeds 32-bit indexing", total);
+    DD_REQUIRE(P.stride == 1 || P.stride == 2, DD_E_ARG, "dd_net_forward: depthwise stride %d", P.stride);
+    const dim3 grid((unsigned)((total + 255) / 256));
 #define DD_DW(S_, A_) hipLaunchKernelGGL((dwconv3_k<S_, A_>), grid, dim3(256), 0, s, P)
 #define DD_DW2(A_) hipLaunchKernelGGL((dwconv3_k<1, A_, 2>), grid, dim3(256), 0, s, P)
-                if (ty == 2) { if (P.act == ACT_RELU6) DD_DW2(ACT_RELU6); else if (P.act == ACT_SILU) DD_DW2(ACT_SILU); else DD_DW2(-1); }
-                else if (P.act == ACT_RELU6) { if (P.stride == 1) DD_DW(1, ACT_RELU6); else DD_DW(2, ACT_RELU6); }
-                else if (P.act == ACT_SILU) { if (P.stride == 1) DD_DW(1, ACT_SILU); else DD_DW(2, ACT_SILU); }
-                else { if (P.stride == 1) DD_DW(1, -1); else DD_DW(2, -1); }
+    if (ty == 2) { if (P.act == ACT_RELU6) DD_DW2(ACT_RELU6); else if (P.act == ACT_SILU) DD_DW2(ACT_SILU); else DD_DW2(-1); }
+    else if (P.act == ACT_RELU6) { if (P.stride == 1) DD_DW(1, ACT_RELU6); else DD_DW(2, ACT_RELU6); }
+    else if (P.act == ACT_SILU) { if (P.stride == 1) DD_DW(1, ACT_SILU); else DD_DW(2, ACT_SILU); }
+    else { if (P.stride == 1) DD_DW(1, -1); else DD_DW(2, -1); }
 #undef DD_DW2
 #undef DD_DW
-                DD_LAUNCH_CHECK();
-                break;
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
+int run_pool(Run &r, int i, const OpView &o) {
+    dd_net *net = r.net; Held &h = r.held; const int nimg = r.nimg; hipStream_t s = r.s;
+    if (h.wide_pool) {                                           // the first layer and the 3x3 layer in front of this pool were held back for this launch
+        h.wide_pool = false;
+        const int rc = launch_stem_wide(s, h.stem, nimg, r.device());
+        if (rc != DD_OK) return rc;
+        net->op_launch[i] = OPK_STEM_WIDE;
+        return DD_OK;
+    }
+    const TensorDesc *ts = &net->tensors[o.src()], *td = &net->tensors[o.dst()];
+    const int n_pools = o.pool_cascade();
+    PoolP P;
+    bind_tensor(net, o.src(), P.in, P.cs_in, P.coff_in); P.H = ts->h; P.W = ts->w;
+    P.k = o.pool_k(); P.stride = o.stride(); P.pad = o.pad_t(); P.ho = td->h; P.wo = td->w; P.c = o.cout_pad();
+    P.m = nimg * td->h * td->w;
+    bind_tensor(net, o.dst(), P.out, P.cs_out, P.coff_out);
+    if (n_pools > 1) {                                           // a cascade of stride-1 pools into consecutive channel slices (nets.py pool_cascade)
+        const size_t lds = (size_t)2 * ts->h * ts->w * 16 * PC_GROUPS;
+        DD_REQUIRE(P.stride == 1 && P.pad == P.k / 2 && (P.k & 1) && td->h == ts->h && td->w == ts->w && lds <= 64 * 1024 && ts->h * ts->w <= 4096 && P.coff_out + n_pools * P.c <= td->cs &&      /* (the kernel's p / W by float reciprocal is exact below 4 096 pixels) */
+                   (P.c >> 3) % PC_GROUPS == 0 && (long long)nimg * (P.c >> 3) < (1LL << 31), DD_E_ARG, "dd_net_forward: pool cascade %d: shape", i);
+        hipLaunchKernelGGL(pool_cascade_k, dim3((unsigned)(nimg * ((P.c >> 3) / PC_GROUPS))), dim3(256), lds, s, P, n_pools);
+        DD_LAUNCH_CHECK();
+        return DD_OK;
+    }
+    const long long total = (long long)P.m * (P.c >> 3);
+    DD_REQUIRE(total < (1LL << 31), DD_E_CAPACITY, "dd_net_forward: pooling layer of %lld items exceeds 32-bit indexing", total);
+    hipLaunchKernelGGL(maxpool_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, P);
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
+int run_upsample(Run &r, const OpView &o) {
+    const dd_net *net = r.net;
+    const TensorDesc *ts = &net->tensors[o.src()], *td = &net->tensors[o.dst()];
+    const int m = r.nimg * td->h * td->w;
+    const long long total = (long long)m * (o.cout_pad() >> 3);
+    DD_REQUIRE(total < (1LL << 31), DD_E_CAPACITY, "dd_net_forward: upsample layer of %lld items exceeds 32-bit indexing", total);
+    hipLaunchKernelGGL(upsample2_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, r.s,
+                       static_cast<const _Float16 *>(net->bufs[ts->buf]), ts->h, ts->w, ts->cs, ts->coff, o.cout_pad(), m,
+                       static_cast<_Float16 *>(net->bufs[td->buf]), td->cs, td->coff);
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
+int run_l2norm(Run &r, const OpView &o) {
+    const dd_net *net = r.net;
+    const TensorDesc *ts = &net->tensors[o.src()], *td = &net->tensors[o.dst()];
+    hipLaunchKernelGGL(l2norm_k, dim3(dd_ceil_div(r.nimg, 4)), dim3(256), 0, r.s,
+                       static_cast<const float *>(net->bufs[ts->buf]) + ts->coff, r.nimg, ts->c, o.f(0),
+                       static_cast<float *>(net->bufs[td->buf]) + td->coff);
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
+// uint8 SSD, in front of the walk: the first three ops (first layer, MobileNet blocks 1 and 2) as one launch, or over chunks of frames.  Sets the
+// op the walk starts at, and whether it takes blocks 3 + 4 as one launch.
+int run_q_front(Run &r, int *first_op) {
+    dd_net *net = r.net; const int nimg = r.nimg; hipStream_t s = r.s;
+    // The first three launches over chunks of frames that REUSE the image slots 0 .. chunk - 1
+    // of the two tensors between them, so that 0.72 + 1.44 MB per frame of producer -> consumer traffic can stay in the 256 MB Infinity
+    // Cache instead of going to HBM and back (DD_Q_FRONT_CHUNK=n frames; 0 = off).  Same kernels, same bits: block 2 writes its own
+    // output where the whole-batch launch would.
+    static const int chunk_env = dd_env_int("DD_Q_FRONT_CHUNK", 0);
+    // The same three ops as ONE launch, the two tensors between them in LDS rings (csrc/netsq_front.hip).  DD_Q_FRONT=0: the three
+    // launches; DD_Q_FRONT_MIN: frames per forward from which the row pipeline runs (a few frames spread better as three wide launches).  Read on
+    // every forward: a test flips them between two forwards of one engine.
+    const bool front_on = dd_env_int("DD_Q_FRONT", 1) != 0;
+    const int front_min = dd_env_int("DD_Q_FRONT_MIN", 24);
+    // blocks 3 + 4 as one launch (csrc/netsq_mid.hip), taken in the walk: DD_Q_MID=0 the two launches; same batch threshold
+    r.mid_on = dd_env_int("DD_Q_MID", 1) != 0 && nimg >= front_min;
+    *first_op = 0;
+    const bool front_ops = net->n_ops > 3 && op(net, 0).kind() == OP_QCONV0 && op(net, 1).kind() == OP_QDWPW && op(net, 2).kind() == OP_QDWPW;
+    if (front_on && chunk_env <= 0 && nimg >= front_min && front_ops) {
+        if (net->profile) for (int k = 0; k < 3; ++k) DD_HIP(hipEventRecord(net->events[k], s));
+        int ran = 0;
+        const int rc = netq_run_front(net, op(net, 0).w, op(net, 1).w, op(net, 2).w, r.input, nimg, s, &ran);
+        if (rc != DD_OK) return rc;
+        if (ran) { *first_op = 3; net->op_launch[0] = OPK_FOLDED; net->op_launch[1] = OPK_FOLDED; net->op_launch[2] = OPK_Q_FRONT; }
+    }
+    if (*first_op == 0 && chunk_env > 0 && nimg > chunk_env && front_ops && op(net, 1).src() == op(net, 0).dst() && op(net, 2).src() == op(net, 1).dst()) {
+        const TensorDesc &t2 = net->tensors[op(net, 2).dst()];
+        const size_t img_out = (size_t)(t2.h + 2) * (t2.w + 2) * t2.cs;          // bordered uint8 layout: bytes per image
+        void *&out_buf = net->bufs[t2.buf];
+        void *const out_base = out_buf;
+        if (net->profile) for (int k = 0; k < 3; ++k) DD_HIP(hipEventRecord(net->events[k], s));
+        for (int c0 = 0; c0 < nimg; c0 += chunk_env) {
+            const int nc = std::min(chunk_env, nimg - c0);
+            out_buf = static_cast<char *>(out_base) + (size_t)c0 * img_out;
+            for (int k = 0; k < 3; ++k) {
+                int handled = 0;
+                const int rc = netq_run_op(net, k, op(net, k).w, r.input + (size_t)c0 * net->in_h * net->in_w * 3, nc, s, &handled);
+                if (rc != DD_OK || !handled) { out_buf = out_base; return rc != DD_OK ? rc : DD_E_ARG; }
             }
-            case OP_MAXPOOL: {
-                if (wide_ready) {                                // the first layer and the 3x3 layer in front of this pool were held back for this launch
-                    wide_ready = false;
-                    const int rc = launch_stem_wide(s, stem_p, nimg, net->ctx->device);
-                    if (rc != DD_OK) return rc;
-                    net->op_launch[i] = OPK_STEM_WIDE;
-                    break;
-                }
-                PoolP P;
-                P.in = reinterpret_cast<const _Float16 *>(base(src)); P.H = ts->h; P.W = ts->w; P.cs_in = ts->cs; P.coff_in = ts->coff;
-                P.k = o[5]; P.stride = o[7]; P.pad = o[8]; P.ho = td->h; P.wo = td->w; P.c = o[12];
-                P.m = nimg * td->h * td->w;
-                P.out = reinterpret_cast<_Float16 *>(base(dst)); P.cs_out = td->cs; P.coff_out = td->coff;
-                if (o[6] > 1) {                                  // a cascade of o[6] stride-1 pools into consecutive channel slices (nets.py pool_cascade)
-                    const size_t lds = (size_t)2 * ts->h * ts->w * 16 * PC_GROUPS;
-                    DD_REQUIRE(P.stride == 1 && P.pad == P.k / 2 && (P.k & 1) && td->h == ts->h && td->w == ts->w && lds <= 64 * 1024 && ts->h * ts->w <= 4096 && P.coff_out + o[6] * P.c <= td->cs &&      /* (the kernel's p / W by float reciprocal is exact below 4 096 pixels) */
-                               (P.c >> 3) % PC_GROUPS == 0 && (long long)nimg * (P.c >> 3) < (1LL << 31), DD_E_ARG, "dd_net_forward: pool cascade %d: shape", i);
-                    hipLaunchKernelGGL(pool_cascade_k, dim3((unsigned)(nimg * ((P.c >> 3) / PC_GROUPS))), dim3(256), lds, s, P, o[6]);
-                    DD_LAUNCH_CHECK();
-                    break;
-                }
-                const long long total = (long long)P.m * (P.c >> 3);
-                DD_REQUIRE(total < (1LL << 31), DD_E_CAPACITY, "dd_net_forward: pooling layer of %lld items exceeds 32-bit indexing", total);
-                hipLaunchKernelGGL(maxpool_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, P);
-                DD_LAUNCH_CHECK();
-                break;
-            }
-            case OP_UPSAMPLE: {
-                const int m = nimg * td->h * td->w;
-                const long long total = (long long)m * (o[12] >> 3);
-                DD_REQUIRE(total < (1LL << 31), DD_E_CAPACITY, "dd_net_forward: upsample layer of %lld items exceeds 32-bit indexing", total);
-                hipLaunchKernelGGL(upsample2_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                                   reinterpret_cast<const _Float16 *>(base(src)), ts->h, ts->w, ts->cs, ts->coff, o[12], m,
-                                   reinterpret_cast<_Float16 *>(base(dst)), td->cs, td->coff);
-                DD_LAUNCH_CHECK();
-                break;
-            }
-            case OP_L2NORM: {
-                hipLaunchKernelGGL(l2norm_k, dim3(dd_ceil_div(nimg, 4)), dim3(256), 0, s,
-                                   reinterpret_cast<const float *>(base(src)) + ts->coff, nimg, ts->c, of[32],
-                                   reinterpret_cast<float *>(base(dst)) + td->coff);
-                DD_LAUNCH_CHECK();
-                break;
-            }
+        }
+        out_buf = out_base;
+        *first_op = 3;
+    }
+    return DD_OK;
+}
+
+// uint8 SSD: op i and the next are block ops -- blocks 3 + 4 as one launch?  *ran = 0: not those two
+int run_q_mid(Run &r, int i, int *ran) {
+    dd_net *net = r.net;
+    if (net->profile) DD_HIP(hipEventRecord(net->events[i + 1], r.s));
+    *ran = 0;
+    const int rc = netq_run_mid(net, op(net, i).w, op(net, i + 1).w, r.nimg, r.s, ran);
+    if (rc != DD_OK) return rc;
+    if (*ran) { net->op_launch[i] = OPK_FOLDED; net->op_launch[i + 1] = OPK_Q_MID; }
+    return DD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+static int net_run_ops(dd_net *net, const uint8_t *input, int nimg, hipStream_t s) {
+    net->op_launch.assign((size_t)net->n_ops, OPK_DEFAULT);
+    net->op_variant.assign((size_t)net->n_ops, 0);
+    Run r{net, input, nimg, s};
+    Held &h = r.held;
+    int first_op = 0;
+    int rc = run_q_front(r, &first_op);
+    if (rc != DD_OK) return rc;
+    for (int i = first_op; i < net->n_ops; ++i) {
+        if (net->profile) DD_HIP(hipEventRecord(net->events[i], s));
+        const OpView o = op(net, i);
+        const int kind = o.kind();
+        DD_REQUIRE(!h.input_on || (kind == OP_CONV && i == h.input_op + 1), DD_E_STATE, "dd_net_forward: input op %d was folded into an op that did not take it", h.input_op);
+        if (r.mid_on && kind == OP_QDWPW && i + 1 < net->n_ops && op(net, i + 1).kind() == OP_QDWPW) {   // two uint8 block ops
+            int ran = 0;
+            if ((rc = run_q_mid(r, i, &ran)) != DD_OK) return rc;
+            if (ran) { ++i; continue; }
+        }
+        DD_REQUIRE((!h.wide_conv || kind == OP_CONV) && (!h.wide_pool || kind == OP_MAXPOOL), DD_E_STATE, "dd_net_forward: op %d does not take the first layer folded into it", i);
+        if ((rc = flush_unclaimed(r, o)) != DD_OK) return rc;
+        switch (kind) {
+            case OP_INPUT: rc = run_input(r, i, o); break;
+            case OP_CONV: rc = run_conv(r, i, o); break;
+            case OP_STEM: rc = run_stem(r, i, o); break;
+            case OP_DWPW: rc = run_dwpw(r, i, o); break;
+            case OP_DWCONV: rc = run_dwconv(r, i, o); break;
+            case OP_MAXPOOL: rc = run_pool(r, i, o); break;
+            case OP_UPSAMPLE: rc = run_upsample(r, o); break;
+            case OP_L2NORM: rc = run_l2norm(r, o); break;
             default: {
                 int handled = 0;
-                const int rc = netq_run_op(net, i, o, input, nimg, s, &handled);       // csrc/netsq.hip: the uint8 programs' ops
+                rc = netq_run_op(net, i, o.w, input, nimg, s, &handled);       // csrc/netsq.hip: the uint8 programs' ops
                 if (rc != DD_OK) return rc;
                 DD_REQUIRE(handled, DD_E_ARG, "dd_net_forward: unknown op kind %d at %d", kind, i);
             }
         }
+        if (rc != DD_OK) return rc;
     }
-    if (pair_pending) { const int rc = flush_pair(); if (rc != DD_OK) return rc; }
+    if (h.pair_on && (rc = flush(r, HELD_PAIR)) != DD_OK) return rc;
     if (net->profile) {
         DD_HIP(hipEventRecord(net->events[net->n_ops], s));
         DD_HIP(hipEventRecord(net->events[net->n_ops + 1], s));

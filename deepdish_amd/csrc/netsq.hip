@@ -1133,7 +1133,7 @@ int launch_q_dwpw(hipStream_t s, QDwpwP &P, int nimg, int device, bool *ok, bool
     int lpt = 0;
     P.tiles_per_frame = dd_ceil_div(P.hw, QTT);
     dwpw_plan(P.H, P.W, P.ho, P.wo, STRIDE, P.off_y, CIN, NT, QTT, &P.NR, &lpt);
-    static const int extra_env = getenv("DD_Q_EXTRA") ? atoi(getenv("DD_Q_EXTRA")) : -1;
+    static const int extra_env = dd_env_int("DD_Q_EXTRA", -1);
     P.NR += extra_env >= 0 ? extra_env : EXTRA;                   // ring rows beyond one tile's span: the next tile's rows can be requested a stage earlier
     const int RB = (P.W + 2) * CIN;
     constexpr bool KEEP = ((CIN / 16) * (QTT / 64)) / NW <= 2;        // (as in the kernel) else the depthwise tables take LDS
@@ -1176,13 +1176,13 @@ int launch_q_dwpw(hipStream_t s, QDwpwP &P, int nimg, int device, bool *ok, bool
         per_cu = std::max(1, std::min(8, nb));
         per_cu_cache[device & 63].store(per_cu, std::memory_order_relaxed);
     }
-    static const int per_cu_env = getenv("DD_Q_PER_CU") ? atoi(getenv("DD_Q_PER_CU")) : 0;     // experiment: fewer blocks per CU than fit
+    static const int per_cu_env = dd_env_int("DD_Q_PER_CU", 0);     // experiment: fewer blocks per CU than fit
     if (per_cu_env > 0) per_cu = std::min(per_cu, per_cu_env);
     const int n_tiles = nimg * P.tiles_per_frame;
     const int blocks = std::min(n_tiles, per_cu * 256);
     const int tpb = dd_ceil_div(n_tiles, blocks);
     const dim3 grid((unsigned)dd_ceil_div(n_tiles, tpb));
-    static const bool stamps = getenv("DD_Q_STAMPS") && atoi(getenv("DD_Q_STAMPS")) != 0;
+    static const bool stamps = dd_env_int("DD_Q_STAMPS", 0) != 0;
     const size_t n_st = (size_t)grid.x * NW * 8;
     if (stamps) { DD_HIP(hipMalloc(&P.dbg, n_st * 8)); DD_HIP(hipMemsetAsync(P.dbg, 0, n_st * 8, s)); }
     hipLaunchKernelGGL(kern, grid, dim3(NT), lds, s, P, n_tiles, tpb);
@@ -1203,7 +1203,7 @@ int launch_q_dwpw(hipStream_t s, QDwpwP &P, int nimg, int device, bool *ok, bool
 
 // The fused kernels there are: (cin, cout, stride) -> instantiation.  *ok = false: none, or its launcher does not take the geometry.
 int dwpw_dispatch(hipStream_t s, QDwpwP &Q, int nc, int dev, int cin, int cout, int stride, bool *ok, bool dry, int *variant, bool dry_split = false) {
-    static const int qt128 = getenv("DD_Q_QT128") ? atoi(getenv("DD_Q_QT128")) : 1;   // block 1: 128-pixel tiles, four waves (0: 64-pixel tiles, two waves)
+    static const int qt128 = dd_env_int("DD_Q_QT128", 1);   // block 1: 128-pixel tiles, four waves (0: 64-pixel tiles, two waves)
     *ok = false;
 #define DD_QB(CIN_, COUT_, WP_, S_, LPT_) launch_q_dwpw<CIN_, COUT_, WP_, S_, LPT_>(s, Q, nc, dev, ok, dry, variant, dry_split)
     if (cin == 32 && cout == 64 && stride == 1) return qt128 ? launch_q_dwpw<32, 64, 4, 1, 6, 0, 4, 128>(s, Q, nc, dev, ok, dry, variant, dry_split) : DD_QB(32, 64, 2, 1, 8);
@@ -1527,7 +1527,7 @@ int dd_netq_dwpw_fits(int cin, int cout, int stride, int h, int w, int split_fil
 }
 
 int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int nimg, hipStream_t s, int *handled) {
-    const int kind = o[0], src = o[1], dst = o[2];
+    const int kind = o[W_KIND], src = o[W_SRC], dst = o[W_DST];
     *handled = kind >= OP_QCONV0 && kind <= OP_QADD;
     if (!*handled) return DD_OK;
     auto base = [&](int t) -> uint8_t * { return static_cast<uint8_t *>(net->bufs[net->tensors[t].buf]); };
@@ -1540,16 +1540,16 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
         case OP_QCONV0: {
             QConv0P P;
             P.src = input; P.H = net->in_h; P.W = net->in_w; P.total_bytes = (long long)nimg * P.H * P.W * 3;
-            P.stride = o[7]; P.pad_t = o[8]; P.pad_l = o[9]; P.ho = td->h; P.wo = td->w; P.m = nimg * P.ho * P.wo;
-            P.w = reinterpret_cast<const i4v *>(W + (size_t)(uint32_t)o[16]);
-            P.w2 = o[18] ? reinterpret_cast<const i4v *>(W + (size_t)(uint32_t)o[18]) : nullptr;
-            P.cq = reinterpret_cast<const long long *>(W + (size_t)(uint32_t)o[46]);
-            P.out = base(dst); P.in_zp = o[39]; P.zwc = o[38]; P.R = make_req(o);
+            P.stride = o[W_STRIDE]; P.pad_t = o[W_PAD_T]; P.pad_l = o[W_PAD_L]; P.ho = td->h; P.wo = td->w; P.m = nimg * P.ho * P.wo;
+            P.w = reinterpret_cast<const i4v *>(W + (size_t)(uint32_t)o[W_W_OFF]);
+            P.w2 = o[W_AFF_OFF] ? reinterpret_cast<const i4v *>(W + (size_t)(uint32_t)o[W_AFF_OFF]) : nullptr;
+            P.cq = reinterpret_cast<const long long *>(W + (size_t)(uint32_t)o[W_Q_CQ_OFF]);
+            P.out = base(dst); P.in_zp = o[W_Q_IN_ZP]; P.zwc = o[W_Q_ZWC]; P.R = make_req(o);
             P.out_bytes = (long long)nimg * (P.ho + 2) * 2 * (P.wo + 2) * 16;
             DD_REQUIRE(td->w >= 16, DD_E_ARG, "dd_net_forward: uint8 first layer: output narrower than a fragment");
-            DD_REQUIRE(td->pad == 1 && td->cs == 32 && o[11] == 32 && (reinterpret_cast<uintptr_t>(input) & 3) == 0 && (P.total_bytes & 3) == 0 && !P.R.linear && P.R.e >= 1,
+            DD_REQUIRE(td->pad == 1 && td->cs == 32 && o[W_COUT] == 32 && (reinterpret_cast<uintptr_t>(input) & 3) == 0 && (P.total_bytes & 3) == 0 && !P.R.linear && P.R.e >= 1,
                        DD_E_ARG, "dd_net_forward: uint8 first layer: 32 channels into a bordered tensor from a 4-byte aligned batch");
-            DD_REQUIRE(o[46] != 0, DD_E_ARG, "dd_net_forward: uint8 first layer: no folded requantisation constants in the program");
+            DD_REQUIRE(o[W_Q_CQ_OFF] != 0, DD_E_ARG, "dd_net_forward: uint8 first layer: no folded requantisation constants in the program");
             // The kernel's source and destination are 31-bit buffer ranges (2 904 frames of 300x300: 0.74 MB of bordered output each).  A bigger
             // batch runs as launches over chunks of frames -- the frames are independent, so a chunk is the same kernel on other base pointers.
             const long long in_img = (long long)P.H * P.W * 3, out_img = (long long)(P.ho + 2) * 2 * (P.wo + 2) * 16, lim31 = (1ll << 31) - 17;
@@ -1583,62 +1583,62 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
             memset(&P, 0, sizeof(P));
             DD_REQUIRE(ts->pad == 1 && ts->cs % 16 == 0, DD_E_ARG, "dd_net_forward: uint8 conv %d reads a tensor that is not in the bordered layout", i);
             P.in = base(src); P.H = ts->h; P.W = ts->w; P.c16_in = ts->cs / 16;
-            P.kh = o[5]; P.kw = o[6]; P.stride = o[7]; P.off_y = 1 - o[8]; P.off_x = 1 - o[9];
-            P.ho = o[26]; P.wo = o[27]; P.m = nimg * P.ho * P.wo;
-            P.w = reinterpret_cast<const i4v *>(W + (size_t)(uint32_t)o[16]);
-            P.cbias = reinterpret_cast<const int *>(W + (size_t)(uint32_t)o[17]);
-            P.kc_per_tap = o[13]; P.n_mfrag = o[12] / 16; P.epi = o[15];
-            P.out = base(dst); P.zwc = o[38]; P.R = make_req(o);
-            const int n_frag_a = o[14];                              // > 0: two predictors in one op (fragments [0, n_frag_a) the first: netsq.py conv_heads)
+            P.kh = o[W_KH]; P.kw = o[W_KW]; P.stride = o[W_STRIDE]; P.off_y = 1 - o[W_PAD_T]; P.off_x = 1 - o[W_PAD_L];
+            P.ho = o[W_HO]; P.wo = o[W_WO]; P.m = nimg * P.ho * P.wo;
+            P.w = reinterpret_cast<const i4v *>(W + (size_t)(uint32_t)o[W_W_OFF]);
+            P.cbias = reinterpret_cast<const int *>(W + (size_t)(uint32_t)o[W_B_OFF]);
+            P.kc_per_tap = o[W_KPAD]; P.n_mfrag = o[W_COUT_PAD] / 16; P.epi = o[W_EPI];
+            P.out = base(dst); P.zwc = o[W_Q_ZWC]; P.R = make_req(o);
+            const int n_frag_a = o[W_ACT];                              // > 0: two predictors in one op (fragments [0, n_frag_a) the first: netsq.py conv_heads)
             QReq Rb = P.R;
             if (n_frag_a) {
-                int32_t d[48] = {0}; d[32] = o[20]; d[33] = o[21]; d[40] = o[22]; d[36] = 0; d[37] = 255; d[41] = o[41]; Rb = make_req(d);
-                DD_REQUIRE(o[4] >= 0 && P.epi == QEPI_ROWS && n_frag_a < P.n_mfrag && !net->tensors[o[4]].pad && o[23] % 4 == 0 && o[24] % 4 == 0 && o[25] % 4 == 0 && o[25] <= o[23] &&
-                           (long long)o[24] + (long long)P.ho * P.wo * o[23] <= (long long)net->tensors[o[4]].h * net->tensors[o[4]].w * net->tensors[o[4]].cs, DD_E_ARG,
+                int32_t d[OP_WORDS] = {0}; d[W_Q_MULT] = o[W_Q_BOX_MULT]; d[W_Q_SHIFT] = o[W_Q_BOX_SHIFT]; d[W_Q_OUT_ZP] = o[W_Q_BOX_OUT_ZP]; d[W_Q_LO] = 0; d[W_Q_HI] = 255; d[W_Q_LINEAR] = o[W_Q_LINEAR]; Rb = make_req(d);
+                DD_REQUIRE(o[W_DST2] >= 0 && P.epi == QEPI_ROWS && n_frag_a < P.n_mfrag && !net->tensors[o[W_DST2]].pad && o[W_Q_BOX_ROW_BYTES] % 4 == 0 && o[W_Q_BOX_BASE_OFF] % 4 == 0 && o[W_Q_BOX_COUT_STORE] % 4 == 0 && o[W_Q_BOX_COUT_STORE] <= o[W_Q_BOX_ROW_BYTES] &&
+                           (long long)o[W_Q_BOX_BASE_OFF] + (long long)P.ho * P.wo * o[W_Q_BOX_ROW_BYTES] <= (long long)net->tensors[o[W_DST2]].h * net->tensors[o[W_DST2]].w * net->tensors[o[W_DST2]].cs, DD_E_ARG,
                            "dd_net_forward: uint8 conv %d: second predictor's row geometry", i);
             }
             DD_REQUIRE(P.off_y >= 0 && P.off_x >= 0 && (P.ho - 1) * P.stride + P.kh - 1 + P.off_y <= P.H + 1 && (P.wo - 1) * P.stride + P.kw - 1 + P.off_x <= P.W + 1,
                        DD_E_ARG, "dd_net_forward: uint8 conv %d reaches outside the one-pixel border", i);
-            DD_REQUIRE(o[3] < 0 || P.epi == QEPI_Q16N, DD_E_ARG, "dd_net_forward: uint8 conv %d: a residual operand needs the natural bordered epilogue", i);
+            DD_REQUIRE(o[W_RES] < 0 || P.epi == QEPI_Q16N, DD_E_ARG, "dd_net_forward: uint8 conv %d: a residual operand needs the natural bordered epilogue", i);
             if (P.epi == QEPI_Q16) {
-                DD_REQUIRE(td->pad == 1 && td->h == P.ho && td->w == P.wo && o[12] % 64 == 0 && td->cs == o[12] && !P.R.linear, DD_E_ARG,
+                DD_REQUIRE(td->pad == 1 && td->h == P.ho && td->w == P.wo && o[W_COUT_PAD] % 64 == 0 && td->cs == o[W_COUT_PAD] && !P.R.linear, DD_E_ARG,
                            "dd_net_forward: uint8 conv %d: bordered output needs a multiple of 64 channels and an activation", i);
                 P.Ho = td->h; P.Wo = td->w; P.c16_out = td->cs / 16; P.mq = 4;
             } else if (P.epi == QEPI_Q16N) {
                 // any multiple of 16 channels, with or without activation: one to three planes per wave item (natural filter order)
-                DD_REQUIRE(td->pad == 1 && td->h == P.ho && td->w == P.wo && o[12] % 16 == 0 && td->cs == o[12] && n_frag_a == 0 && (P.R.linear || P.R.lo >= P.R.zo) &&
+                DD_REQUIRE(td->pad == 1 && td->h == P.ho && td->w == P.wo && o[W_COUT_PAD] % 16 == 0 && td->cs == o[W_COUT_PAD] && n_frag_a == 0 && (P.R.linear || P.R.lo >= P.R.zo) &&
                            P.R.e >= 0 && P.R.e <= 30 && P.R.lo >= 0 && P.R.lo <= P.R.hi && P.R.hi <= 255, DD_E_ARG,
                            "dd_net_forward: uint8 conv %d: natural bordered output geometry / requantisation", i);
                 P.Ho = td->h; P.Wo = td->w; P.c16_out = td->cs / 16;
                 P.mq = P.n_mfrag % 3 == 0 ? 3 : P.n_mfrag % 2 == 0 ? 2 : std::min(3, P.n_mfrag);
-                if (o[3] >= 0) {
-                    DD_REQUIRE(o[3] < (int)net->tensors.size(), DD_E_ARG, "dd_net_forward: uint8 conv %d: residual tensor %d out of range", i, o[3]);
-                    const TensorDesc *tr = &net->tensors[o[3]];
-                    P.res = base(o[3]); P.A = make_add(o);
-                    DD_REQUIRE(tr->pad == 1 && tr->h == td->h && tr->w == td->w && tr->cs == td->cs && o[3] != dst && add_ok(P.A) && P.R.lo == 0 && P.R.hi == 255, DD_E_ARG,
+                if (o[W_RES] >= 0) {
+                    DD_REQUIRE(o[W_RES] < (int)net->tensors.size(), DD_E_ARG, "dd_net_forward: uint8 conv %d: residual tensor %d out of range", i, o[W_RES]);
+                    const TensorDesc *tr = &net->tensors[o[W_RES]];
+                    P.res = base(o[W_RES]); P.A = make_add(o);
+                    DD_REQUIRE(tr->pad == 1 && tr->h == td->h && tr->w == td->w && tr->cs == td->cs && o[W_RES] != dst && add_ok(P.A) && P.R.lo == 0 && P.R.hi == 255, DD_E_ARG,
                                "dd_net_forward: uint8 conv %d: residual operand geometry / ADD parameters", i);
                     if (i < (int)net->op_launch.size()) net->op_launch[i] = 21;      // dd_net_op_launches: q_conv_k with the residual ADD in its epilogue
                 }
             } else {
-                P.img_bytes_out = (long long)td->h * td->w * td->cs; P.row_bytes = o[42]; P.base_off = o[43]; P.cout_store = o[44];
+                P.img_bytes_out = (long long)td->h * td->w * td->cs; P.row_bytes = o[W_Q_ROW_BYTES]; P.base_off = o[W_Q_BASE_OFF]; P.cout_store = o[W_Q_COUT_STORE];
                 DD_REQUIRE(!td->pad && P.row_bytes % 4 == 0 && P.base_off % 4 == 0 && P.cout_store % 4 == 0 && P.cout_store <= P.row_bytes &&
                            (long long)P.base_off + (long long)P.ho * P.wo * P.row_bytes <= P.img_bytes_out, DD_E_ARG, "dd_net_forward: uint8 conv %d: row output geometry", i);
                 P.mq = std::min(4, P.n_mfrag);
             }
             // 1x1 stride-1 layers with 512 / 1024 input channels and pixels enough: the filter in registers, the pixels through LDS (q_pws_k)
-            static const int pws_env = getenv("DD_Q_PWS") ? atoi(getenv("DD_Q_PWS")) : 1;
+            static const int pws_env = dd_env_int("DD_Q_PWS", 1);
             if (pws_env && P.epi != QEPI_Q16N && P.kh == 1 && P.kw == 1 && P.stride == 1 && P.off_y == 1 && P.off_x == 1 && (ts->cs == 512 || ts->cs == 1024) && P.m >= 8192 && P.n_mfrag >= 8 &&
-                o[46] != 0 && (P.epi == QEPI_ROWS || (!P.R.linear && P.R.e >= 1))) {
+                o[W_Q_CQ_OFF] != 0 && (P.epi == QEPI_ROWS || (!P.R.linear && P.R.e >= 1))) {
                 QPwsP Q;
                 memset(&Q, 0, sizeof(Q));
                 Q.in = P.in; Q.H = P.H; Q.W = P.W; Q.c16_in = P.c16_in; Q.hw = P.ho * P.wo; Q.m = P.m;
-                Q.w = P.w; Q.cbias = P.cbias; Q.cq = reinterpret_cast<const long long *>(W + (size_t)(uint32_t)o[46]);
+                Q.w = P.w; Q.cbias = P.cbias; Q.cq = reinterpret_cast<const long long *>(W + (size_t)(uint32_t)o[W_Q_CQ_OFF]);
                 Q.n_mfrag = P.n_mfrag; Q.out = P.out; Q.c16_out = P.c16_out; Q.zwc = P.zwc; Q.R = P.R;
                 if (P.epi == QEPI_ROWS) { Q.img_bytes_out = P.img_bytes_out; Q.row_bytes = P.row_bytes; Q.base_off = P.base_off; Q.cout_store = P.cout_store; }
                 if (n_frag_a) {
-                    const TensorDesc *tb = &net->tensors[o[4]];
-                    Q.n_frag_a = n_frag_a; Q.out_b = base(o[4]); Q.img_bytes_b = (long long)tb->h * tb->w * tb->cs; Q.row_bytes_b = o[23]; Q.base_off_b = o[24]; Q.cout_store_b = o[25];
-                    Q.zwc_b = o[28]; Q.Rb = Rb;
+                    const TensorDesc *tb = &net->tensors[o[W_DST2]];
+                    Q.n_frag_a = n_frag_a; Q.out_b = base(o[W_DST2]); Q.img_bytes_b = (long long)tb->h * tb->w * tb->cs; Q.row_bytes_b = o[W_Q_BOX_ROW_BYTES]; Q.base_off_b = o[W_Q_BOX_BASE_OFF]; Q.cout_store_b = o[W_Q_BOX_COUT_STORE];
+                    Q.zwc_b = o[W_Q_BOX_ZWC]; Q.Rb = Rb;
                 }
                 bool ok = false;
                 // (the 19x19 class predictor has 18 fragments: six waves of three load the SIMDs 6 / 6 / 3 / 3, five of four 8 / 4 / 4 / 2)
@@ -1655,7 +1655,7 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
                 // few wave items anyway and pixels enough -- measured per layer at 384 frames: extras 48 -> 38, 63 -> 39 us, 5x5 class predictor
                 // 23 -> 16 us, but 53 -> 65, 86 -> 95, 68 -> 78 us on the layers with 19 k+ items (b12 / b13 pointwise, 19x19 class predictor).
                 const long long items2 = (long long)n_mgroups * dd_ceil_div(P.m, 32);
-                static const int npf_env = getenv("DD_Q_NPF") ? atoi(getenv("DD_Q_NPF")) : 0;
+                static const int npf_env = dd_env_int("DD_Q_NPF", 0);
                 // (end of round: with the register-filter kernel on the big 1x1 layers and the k split on the small 3x3 ones, two fragments win or tie on
                 // every layer left here -- 87 -> 78 us over the eleven small layers; the rule used to be four below 8 192 items)
                 const int npf = npf_env ? npf_env : 2;
@@ -1664,7 +1664,7 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
                 DD_REQUIRE(n_items < (1ll << 31), DD_E_CAPACITY, "dd_net_forward: uint8 conv %d: %lld wave items", i, n_items);
                 const bool rsum = P.zwc != 0 || (P.n_frag_a && P.zwc_b != 0);
                 const bool pipe = n_items < 8192;
-                static const int split_env = getenv("DD_Q_SPLITK") ? atoi(getenv("DD_Q_SPLITK")) : 1;
+                static const int split_env = dd_env_int("DD_Q_SPLITK", 1);
                 const bool split = split_env && P.kh * P.kw == 9 && n_items < 1024;       // (3x3: the k steps divide by the three filter rows; at 1 200 items the split costs: 40 -> 51 us)
                 const dim3 grid(split ? (unsigned)n_items : (unsigned)((n_items + 3) / 4)), block(split ? 192 : 256);
                 // (two launches of one op -- DD_Q_HEADS_ONE=0 -- report the second one's kernel and count 2 in bits 18..19)
@@ -1686,13 +1686,13 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
             if (n_frag_a == 0) return run_generic(P);
             // two predictors outside q_pws_k's shapes (small feature maps, small batches): one launch, the second one's fragments, constants and
             // destination rows chosen per wave item (DD_Q_HEADS_ONE=0: one launch each, the form until round 6 -- the same bits)
-            const TensorDesc *tb = &net->tensors[o[4]];
-            static const int heads_one = getenv("DD_Q_HEADS_ONE") ? atoi(getenv("DD_Q_HEADS_ONE")) : 1;
+            const TensorDesc *tb = &net->tensors[o[W_DST2]];
+            static const int heads_one = dd_env_int("DD_Q_HEADS_ONE", 1);
             if (heads_one) {
                 P.mq = std::min(4, n_frag_a);
                 P.n_frag_a = n_frag_a; P.groups_a = dd_ceil_div(n_frag_a, P.mq);
-                P.out_b = base(o[4]); P.img_bytes_b = (long long)tb->h * tb->w * tb->cs; P.row_bytes_b = o[23]; P.base_off_b = o[24]; P.cout_store_b = o[25];
-                P.zwc_b = o[28]; P.Rb = Rb;
+                P.out_b = base(o[W_DST2]); P.img_bytes_b = (long long)tb->h * tb->w * tb->cs; P.row_bytes_b = o[W_Q_BOX_ROW_BYTES]; P.base_off_b = o[W_Q_BOX_BASE_OFF]; P.cout_store_b = o[W_Q_BOX_COUT_STORE];
+                P.zwc_b = o[W_Q_BOX_ZWC]; P.Rb = Rb;
                 return run_generic(P);
             }
             QConvP P2 = P;
@@ -1701,24 +1701,24 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
             if (rc2 != DD_OK) return rc2;
             P2.w = P.w + (size_t)n_frag_a * (P.kh * P.kw * P.kc_per_tap) * 64; P2.cbias = P.cbias + 16 * n_frag_a;
             P2.n_mfrag -= n_frag_a; P2.mq = std::min(4, P2.n_mfrag);
-            P2.out = base(o[4]); P2.img_bytes_out = (long long)tb->h * tb->w * tb->cs; P2.row_bytes = o[23]; P2.base_off = o[24]; P2.cout_store = o[25];
-            P2.zwc = o[28]; P2.R = Rb;
+            P2.out = base(o[W_DST2]); P2.img_bytes_out = (long long)tb->h * tb->w * tb->cs; P2.row_bytes = o[W_Q_BOX_ROW_BYTES]; P2.base_off = o[W_Q_BOX_BASE_OFF]; P2.cout_store = o[W_Q_BOX_COUT_STORE];
+            P2.zwc = o[W_Q_BOX_ZWC]; P2.R = Rb;
             return run_generic(P2);
         }
         case OP_QDW: {
             QDwP P;
             DD_REQUIRE(ts->pad == 1 && td->pad == 1 && ts->cs == td->cs && ts->cs % 16 == 0, DD_E_ARG, "dd_net_forward: uint8 depthwise %d: tensor layouts", i);
             P.in = base(src); P.H = ts->h; P.W = ts->w; P.c16 = ts->cs / 16;
-            P.stride = o[7]; P.off_y = 1 - o[8]; P.off_x = 1 - o[9]; P.ho = td->h; P.wo = td->w;
-            P.w = reinterpret_cast<const short *>(W + (size_t)(uint32_t)o[16]);
-            P.cbias = reinterpret_cast<const int *>(W + (size_t)(uint32_t)o[17]);
+            P.stride = o[W_STRIDE]; P.off_y = 1 - o[W_PAD_T]; P.off_x = 1 - o[W_PAD_L]; P.ho = td->h; P.wo = td->w;
+            P.w = reinterpret_cast<const short *>(W + (size_t)(uint32_t)o[W_W_OFF]);
+            P.cbias = reinterpret_cast<const int *>(W + (size_t)(uint32_t)o[W_B_OFF]);
             P.out = base(dst); P.R = make_req(o);
             P.total = (long long)nimg * P.ho * P.c16 * P.wo;
             DD_REQUIRE(P.off_y >= 0 && P.off_x >= 0 && (P.ho - 1) * P.stride + 2 + P.off_y <= P.H + 1 && (P.wo - 1) * P.stride + 2 + P.off_x <= P.W + 1 && !P.R.linear,
                        DD_E_ARG, "dd_net_forward: uint8 depthwise %d reaches outside the one-pixel border", i);
             DD_REQUIRE(P.total < (1ll << 31) * 256, DD_E_CAPACITY, "dd_net_forward: uint8 depthwise %d: too many items", i);
-            static const bool no_mfma = getenv("DD_Q_DW_VALU") && atoi(getenv("DD_Q_DW_VALU")) != 0;       // A/B switch: the vector-ALU form
-            if (o[20] && P.R.e >= 1 && !no_mfma) {                  // o[20], o[21]: the block-diagonal operand table and its constants (netsq.pack_dw_mfma)
+            static const bool no_mfma = dd_env_int("DD_Q_DW_VALU", 0) != 0;       // A/B switch: the vector-ALU form
+            if (o[W_Q_DW_A_OFF] && P.R.e >= 1 && !no_mfma) {                  // o[W_Q_DW_A_OFF], o[W_Q_DW_CB_OFF]: the block-diagonal operand table and its constants (netsq.pack_dw_mfma)
                 // q_dwm_k's offsets are 32-bit ((n + 1) frames of source and of output; block 2's depthwise reads 1 478 656 bytes a frame:
                 // 2 903 frames).  A bigger batch runs as launches over chunks of frames on other base pointers (the frames are independent).
                 const long long in_img = (long long)(P.H + 2) * P.c16 * (P.W + 2) * 16, out_img = (long long)(P.ho + 2) * P.c16 * (P.wo + 2) * 16;
@@ -1733,8 +1733,8 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
                     QDwmP Q;
                     Q.in = P.in + c0 * in_img; Q.H = P.H; Q.W = P.W; Q.c16 = P.c16; Q.stride = P.stride; Q.off_y = P.off_y; Q.off_x = P.off_x; Q.ho = P.ho; Q.wo = P.wo;
                     Q.m = nc * P.ho * P.wo; Q.out = P.out + c0 * out_img; Q.R = P.R;
-                    Q.dw_a = reinterpret_cast<const uint2 *>(W + (size_t)(uint32_t)o[20]);
-                    Q.dw_cb = reinterpret_cast<const int *>(W + (size_t)(uint32_t)o[21]);
+                    Q.dw_a = reinterpret_cast<const uint2 *>(W + (size_t)(uint32_t)o[W_Q_DW_A_OFF]);
+                    Q.dw_cb = reinterpret_cast<const int *>(W + (size_t)(uint32_t)o[W_Q_DW_CB_OFF]);
                     const long long n_items = items(nc);
                     *variant = QV_DWM | (P.R.lo == 0 && P.R.hi == 255 ? 1 : 0) << 4 | 0 << 5 | (int)std::min(n_chunks, 255ll) << 8;
                     Q.hw_magic = (unsigned)((1ull << 32) / (unsigned)(P.ho * P.wo)) + 1u; Q.wo_magic = (unsigned)((1ull << 32) / (unsigned)P.wo) + 1u; Q.c16_magic = (unsigned)((1ull << 32) / (unsigned)P.c16) + 1u;
@@ -1756,20 +1756,20 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
             QDwpwP P;
             memset(&P, 0, sizeof(P));
             DD_REQUIRE(ts->pad == 1 && td->pad == 1 && ts->cs % 16 == 0 && td->cs % 64 == 0, DD_E_ARG, "dd_net_forward: uint8 block %d: tensor layouts", i);
-            const int stride = o[7], cin = o[10], cout = o[11];
+            const int stride = o[W_STRIDE], cin = o[W_CIN], cout = o[W_COUT];
             P.in = base(src); P.H = ts->h; P.W = ts->w;
-            P.off_y = 1 - o[8]; P.off_x = 1 - o[9]; P.ho = td->h; P.wo = td->w; P.hw = P.ho * P.wo; P.tiles_per_frame = dd_ceil_div(P.hw, QT);
+            P.off_y = 1 - o[W_PAD_T]; P.off_x = 1 - o[W_PAD_L]; P.ho = td->h; P.wo = td->w; P.hw = P.ho * P.wo; P.tiles_per_frame = dd_ceil_div(P.hw, QT);
             P.out = base(dst); P.c16_out = td->cs / 16;
-            P.dw_a = reinterpret_cast<const uint2 *>(W + (size_t)(uint32_t)o[20]);
-            P.dw_cq = reinterpret_cast<const long long *>(W + (size_t)(uint32_t)o[45]);      // o[21] (the 32-bit constants) serves the two-op form only
-            P.cq = reinterpret_cast<const long long *>(W + (size_t)(uint32_t)o[46]);
-            P.w = reinterpret_cast<const i4v *>(W + (size_t)(uint32_t)o[16]);
-            P.w2 = o[18] ? reinterpret_cast<const i4v *>(W + (size_t)(uint32_t)o[18]) : nullptr;       // o[18]: the lo part of a split pointwise filter
-            P.cbias = reinterpret_cast<const int *>(W + (size_t)(uint32_t)o[17]);
-            P.zwc = o[38]; P.Rp = make_req(o); P.dup = o[47];
-            { int32_t d[48] = {0}; d[32] = o[22]; d[33] = o[23]; d[36] = o[24]; d[37] = o[25]; d[40] = o[28]; P.Rd = make_req(d); }
+            P.dw_a = reinterpret_cast<const uint2 *>(W + (size_t)(uint32_t)o[W_Q_DW_A_OFF]);
+            P.dw_cq = reinterpret_cast<const long long *>(W + (size_t)(uint32_t)o[W_Q_DW_CQ_OFF]);      // o[W_Q_DW_CB_OFF] (the 32-bit constants) serves the two-op form only
+            P.cq = reinterpret_cast<const long long *>(W + (size_t)(uint32_t)o[W_Q_CQ_OFF]);
+            P.w = reinterpret_cast<const i4v *>(W + (size_t)(uint32_t)o[W_W_OFF]);
+            P.w2 = o[W_AFF_OFF] ? reinterpret_cast<const i4v *>(W + (size_t)(uint32_t)o[W_AFF_OFF]) : nullptr;       // o[W_AFF_OFF]: the lo part of a split pointwise filter
+            P.cbias = reinterpret_cast<const int *>(W + (size_t)(uint32_t)o[W_B_OFF]);
+            P.zwc = o[W_Q_ZWC]; P.Rp = make_req(o); P.dup = o[W_Q_DUP];
+            { int32_t d[OP_WORDS] = {0}; d[W_Q_MULT] = o[W_Q_DW_MULT]; d[W_Q_SHIFT] = o[W_Q_DW_SHIFT]; d[W_Q_LO] = o[W_Q_DW_LO]; d[W_Q_HI] = o[W_Q_DW_HI]; d[W_Q_OUT_ZP] = o[W_Q_DW_OUT_ZP]; P.Rd = make_req(d); }
             DD_REQUIRE(!P.dup || (cin == 32 && P.zwc == 0 && !P.w2), DD_E_ARG, "dd_net_forward: uint8 block %d: duplicated operand bytes are for 32 input channels", i);
-            DD_REQUIRE(o[45] != 0 && o[46] != 0, DD_E_ARG, "dd_net_forward: uint8 block %d: the program carries no folded requantisation constants (compiled by an older netsq.py?)", i);
+            DD_REQUIRE(o[W_Q_DW_CQ_OFF] != 0 && o[W_Q_CQ_OFF] != 0, DD_E_ARG, "dd_net_forward: uint8 block %d: the program carries no folded requantisation constants (compiled by an older netsq.py?)", i);
             DD_REQUIRE(cin == ts->cs && cout == td->cs && P.Rd.e >= 1 && P.Rp.e >= 1 && !P.Rd.linear && !P.Rp.linear && P.off_y >= 0 && P.off_x >= 0 &&
                        (P.ho - 1) * stride + 2 + P.off_y <= P.H + 1 && (P.wo - 1) * stride + 2 + P.off_x <= P.W + 1, DD_E_ARG,
                        "dd_net_forward: uint8 block %d: shapes / multipliers the fused kernel does not take", i);
@@ -1793,12 +1793,12 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
             return DD_OK;
         }
         case OP_QADD: {
-            DD_REQUIRE(ts && td && o[3] >= 0 && o[3] < (int)net->tensors.size(), DD_E_ARG, "dd_net_forward: uint8 ADD %d: operands", i);
-            const TensorDesc *tb = &net->tensors[o[3]];
+            DD_REQUIRE(ts && td && o[W_RES] >= 0 && o[W_RES] < (int)net->tensors.size(), DD_E_ARG, "dd_net_forward: uint8 ADD %d: operands", i);
+            const TensorDesc *tb = &net->tensors[o[W_RES]];
             QAddP P;
             P.A = make_add(o);
             DD_REQUIRE(ts->pad == 1 && td->pad == 1 && tb->pad == 1 && ts->h == td->h && ts->w == td->w && ts->cs == td->cs && tb->h == td->h && tb->w == td->w &&
-                       tb->cs == td->cs && td->cs % 16 == 0 && dst != src && dst != o[3] && add_ok(P.A), DD_E_ARG, "dd_net_forward: uint8 ADD %d: tensor layouts / parameters", i);
+                       tb->cs == td->cs && td->cs % 16 == 0 && dst != src && dst != o[W_RES] && add_ok(P.A), DD_E_ARG, "dd_net_forward: uint8 ADD %d: tensor layouts / parameters", i);
             P.H = td->h; P.W = td->w; P.c16 = td->cs / 16;
             // items below 2^31 per launch: a bigger batch runs as launches over chunks of frames on other base pointers (the frames are independent)
             const long long per_img = (long long)P.H * P.c16 * P.W, img_bytes = (long long)(P.H + 2) * (P.W + 2) * td->cs;
@@ -1806,7 +1806,7 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
             const long long chunk = ((1ll << 31) - 256) / per_img;
             for (long long c0 = 0; c0 < nimg; c0 += chunk) {
                 const long long nc = std::min(chunk, nimg - c0);
-                P.a = base(src) + c0 * img_bytes; P.b = base(o[3]) + c0 * img_bytes; P.out = base(dst) + c0 * img_bytes;
+                P.a = base(src) + c0 * img_bytes; P.b = base(o[W_RES]) + c0 * img_bytes; P.out = base(dst) + c0 * img_bytes;
                 P.n_items = (int)(nc * per_img);
                 *variant = QV_ADD | (int)std::min((nimg + chunk - 1) / chunk, 255ll) << 8;
                 hipLaunchKernelGGL(q_add_k, dim3((unsigned)dd_ceil_div(P.n_items, 256)), dim3(256), 0, s, P);
@@ -1818,14 +1818,14 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
         case OP_QSSD_DECODE: {
             if (!net->ssd_dec) return DD_OK;                     // nobody asked for the per-anchor arrays: the head tensors are the output
             QDecP P;
-            const TensorDesc &tb = net->tensors[o[1]], &tc = net->tensors[o[3]];
-            P.box = base(o[1]); P.cls = base(o[3]);
-            P.n_anchors = o[21]; P.n_classes = o[20]; P.cls_stride = tc.cs;
+            const TensorDesc &tb = net->tensors[o[W_SRC]], &tc = net->tensors[o[W_RES]];
+            P.box = base(o[W_SRC]); P.cls = base(o[W_RES]);
+            P.n_anchors = o[W_Q_DEC_ANCHORS]; P.n_classes = o[W_Q_DEC_CLASSES]; P.cls_stride = tc.cs;
             DD_REQUIRE(P.n_anchors == net->dec_anchors && tb.cs == 4 && tb.h == P.n_anchors && tc.h == P.n_anchors && P.n_classes <= tc.cs, DD_E_ARG,
                        "dd_net_forward: uint8 decode of %d anchors, set up for %d", P.n_anchors, net->dec_anchors);
-            P.lut = reinterpret_cast<const uint8_t *>(W + (size_t)(uint32_t)o[16]);
+            P.lut = reinterpret_cast<const uint8_t *>(W + (size_t)(uint32_t)o[W_W_OFF]);
             const float *of = reinterpret_cast<const float *>(o);
-            P.box_scale = of[32]; P.box_zp = of[33]; P.sc_scale = of[34]; P.sc_zp = of[35]; P.thr = net->dec_thr;
+            P.box_scale = of[W_Q_DEC_BOX_SCALE]; P.box_zp = of[W_Q_DEC_BOX_ZP]; P.sc_scale = of[W_Q_DEC_SCORE_SCALE]; P.sc_zp = of[W_Q_DEC_SCORE_ZP]; P.thr = net->dec_thr;
             P.anchors = net->d_anchors; P.boxes = net->dec_boxes; P.score = net->dec_score; P.keys = net->dec_keys; P.cls_out = net->dec_cls;
             DD_REQUIRE(P.cls_stride % 16 == 0 && P.n_classes <= 128, DD_E_ARG, "dd_net_forward: uint8 decode: %d classes in rows of %d bytes", P.n_classes, P.cls_stride);
             *variant = QV_DECODE;

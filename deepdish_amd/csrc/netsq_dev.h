@@ -2,6 +2,7 @@
 // parameters of one layer and the requantise-and-pack forms.  See the header comment of csrc/netsq.hip for the arithmetic.
 #pragma once
 #include "common.h"
+#include "net_priv.h"
 
 namespace {
 
@@ -11,7 +12,6 @@ typedef unsigned u4v __attribute__((ext_vector_type(4)));
 typedef short s2v __attribute__((ext_vector_type(2)));
 typedef const __attribute__((address_space(4))) int cint;      // read-only data at a wave-uniform address: s_load
 
-enum { OP_QCONV0 = 16, OP_QCONV = 17, OP_QDW = 18, OP_QDWPW = 19, OP_QSSD_DECODE = 20, OP_QADD = 21 };
 enum { QEPI_Q16 = 0, QEPI_ROWS = 1, QEPI_Q16N = 2 };     // Q16N: bordered output, filter rows in natural channel order (netsq.py QEPI_Q16N)
 
 struct QReq {            // requantisation of one layer (per-tensor parameters)
@@ -139,8 +139,8 @@ __device__ __forceinline__ int q_add_u8(int a, int b, const QAdd &A) {      // a
 
 inline QAdd make_add(const int32_t *o) {      // the op words of netsq.add_words
     QAdd A;
-    A.M1 = o[20]; A.e1 = o[21]; A.M2 = o[22]; A.e2 = o[23]; A.Mo = o[24]; A.eo = o[25];
-    A.z1 = o[28]; A.z2 = o[29]; A.zo = o[31]; A.lo = o[34]; A.hi = o[35];
+    A.M1 = o[W_Q_ADD_M1]; A.e1 = o[W_Q_ADD_E1]; A.M2 = o[W_Q_ADD_M2]; A.e2 = o[W_Q_ADD_E2]; A.Mo = o[W_Q_ADD_MO]; A.eo = o[W_Q_ADD_EO];
+    A.z1 = o[W_Q_ADD_Z1]; A.z2 = o[W_Q_ADD_Z2]; A.zo = o[W_Q_ADD_ZO]; A.lo = o[W_Q_ADD_LO]; A.hi = o[W_Q_ADD_HI];
     return A;
 }
 
@@ -160,8 +160,8 @@ __device__ __forceinline__ int sdot4(int a, int b, int c) {
 
 inline QReq make_req(const int32_t *o) {
     QReq R;
-    R.M = o[32]; R.e = o[33];
-    R.zo = o[40]; R.lo = o[36]; R.hi = o[37]; R.linear = o[41];
+    R.M = o[W_Q_MULT]; R.e = o[W_Q_SHIFT];
+    R.zo = o[W_Q_OUT_ZP]; R.lo = o[W_Q_LO]; R.hi = o[W_Q_HI]; R.linear = o[W_Q_LINEAR];
     R.C = (1ll << 30) + (R.e > 0 ? (1ll << (30 + R.e)) : 0) + ((long long)R.zo << (31 + R.e));
     return R;
 }

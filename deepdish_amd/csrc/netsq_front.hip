@@ -343,32 +343,32 @@ __global__ __launch_bounds__(256, 2) void q_front_k(const QFrontP P, const int r
 // program, the geometry or the quantisation parameters are not what the row pipeline is built for -- the caller runs the three launches.
 int netq_run_front(dd_net *net, const int32_t *o0, const int32_t *o1, const int32_t *o2, const uint8_t *input, int nimg, hipStream_t s, int *ran) {
     *ran = 0;
-    if (o0[0] != OP_QCONV0 || o1[0] != OP_QDWPW || o2[0] != OP_QDWPW || o1[1] != o0[2] || o2[1] != o1[2]) return DD_OK;
-    const TensorDesc &t0 = net->tensors[o0[2]], &t1 = net->tensors[o1[2]], &t2 = net->tensors[o2[2]];
+    if (o0[W_KIND] != OP_QCONV0 || o1[W_KIND] != OP_QDWPW || o2[W_KIND] != OP_QDWPW || o1[W_SRC] != o0[W_DST] || o2[W_SRC] != o1[W_DST]) return DD_OK;
+    const TensorDesc &t0 = net->tensors[o0[W_DST]], &t1 = net->tensors[o1[W_DST]], &t2 = net->tensors[o2[W_DST]];
     if (net->in_h != F_S0 || net->in_w != F_S0 || t0.h != F_S1 || t0.w != F_S1 || t0.cs != 32 || t1.h != F_S1 || t1.w != F_S1 || t1.cs != 64 ||
         t2.h != F_S2 || t2.w != F_S2 || t2.cs != 128 || !t0.pad || !t1.pad || !t2.pad) return DD_OK;
     // first layer 3x3 stride 2 without padding above / left; block 1 stride 1 padded by one; block 2 stride 2 without padding above / left
-    if (o0[7] != 2 || o0[8] != 0 || o0[9] != 0 || o1[7] != 1 || o1[8] != 1 || o1[9] != 1 || o1[10] != 32 || o1[11] != 64 ||
-        o2[7] != 2 || o2[8] != 0 || o2[9] != 0 || o2[10] != 64 || o2[11] != 128) return DD_OK;
+    if (o0[W_STRIDE] != 2 || o0[W_PAD_T] != 0 || o0[W_PAD_L] != 0 || o1[W_STRIDE] != 1 || o1[W_PAD_T] != 1 || o1[W_PAD_L] != 1 || o1[W_CIN] != 32 || o1[W_COUT] != 64 ||
+        o2[W_STRIDE] != 2 || o2[W_PAD_T] != 0 || o2[W_PAD_L] != 0 || o2[W_CIN] != 64 || o2[W_COUT] != 128) return DD_OK;
     // filters: all three split into hi + lo parts (no row sums), or none (weight zero points of 128: no row sums either)
-    const bool split = o0[18] != 0;
-    if ((o1[47] != 0) != split || (o2[18] != 0) != split || o0[38] != 0 || o1[38] != 0 || o2[38] != 0 || (!split && o1[18] != 0)) return DD_OK;
-    if (!o0[17] || !o1[17] || !o1[21] || !o2[17] || !o2[21] || !o1[20] || !o2[20]) return DD_OK;
+    const bool split = o0[W_AFF_OFF] != 0;
+    if ((o1[W_Q_DUP] != 0) != split || (o2[W_AFF_OFF] != 0) != split || o0[W_Q_ZWC] != 0 || o1[W_Q_ZWC] != 0 || o2[W_Q_ZWC] != 0 || (!split && o1[W_AFF_OFF] != 0)) return DD_OK;
+    if (!o0[W_B_OFF] || !o1[W_B_OFF] || !o1[W_Q_DW_CB_OFF] || !o2[W_B_OFF] || !o2[W_Q_DW_CB_OFF] || !o1[W_Q_DW_A_OFF] || !o2[W_Q_DW_A_OFF]) return DD_OK;
     char *W = net->d_weights;
     QFrontP P;
     memset(&P, 0, sizeof(P));
     P.src = input; P.src_bytes = (long long)nimg * F_S0 * F_S0 * 3;
     P.out = static_cast<uint8_t *>(net->bufs[t2.buf]);
     auto blob = [&](int32_t off) { return W + (size_t)(uint32_t)off; };
-    P.w0 = reinterpret_cast<const i4v *>(blob(o0[16])); P.w0l = split ? reinterpret_cast<const i4v *>(blob(o0[18])) : nullptr;
-    P.cb0 = reinterpret_cast<const int *>(blob(o0[17])); P.in_zp = o0[39]; P.R0 = make_req(o0); P.zp0 = (P.R0.zo ^ 0x80) & 0xff;
-    auto dwreq = [&](const int32_t *o) { int32_t d[48] = {0}; d[32] = o[22]; d[33] = o[23]; d[36] = o[24]; d[37] = o[25]; d[40] = o[28]; return make_req(d); };
-    P.dwa1 = reinterpret_cast<const uint2 *>(blob(o1[20])); P.dcb1 = reinterpret_cast<const int *>(blob(o1[21]));
-    P.w1 = reinterpret_cast<const i4v *>(blob(o1[16])); P.cb1 = reinterpret_cast<const int *>(blob(o1[17]));
+    P.w0 = reinterpret_cast<const i4v *>(blob(o0[W_W_OFF])); P.w0l = split ? reinterpret_cast<const i4v *>(blob(o0[W_AFF_OFF])) : nullptr;
+    P.cb0 = reinterpret_cast<const int *>(blob(o0[W_B_OFF])); P.in_zp = o0[W_Q_IN_ZP]; P.R0 = make_req(o0); P.zp0 = (P.R0.zo ^ 0x80) & 0xff;
+    auto dwreq = [&](const int32_t *o) { int32_t d[OP_WORDS] = {0}; d[W_Q_MULT] = o[W_Q_DW_MULT]; d[W_Q_SHIFT] = o[W_Q_DW_SHIFT]; d[W_Q_LO] = o[W_Q_DW_LO]; d[W_Q_HI] = o[W_Q_DW_HI]; d[W_Q_OUT_ZP] = o[W_Q_DW_OUT_ZP]; return make_req(d); };
+    P.dwa1 = reinterpret_cast<const uint2 *>(blob(o1[W_Q_DW_A_OFF])); P.dcb1 = reinterpret_cast<const int *>(blob(o1[W_Q_DW_CB_OFF]));
+    P.w1 = reinterpret_cast<const i4v *>(blob(o1[W_W_OFF])); P.cb1 = reinterpret_cast<const int *>(blob(o1[W_B_OFF]));
     P.Rd1 = dwreq(o1); P.Rp1 = make_req(o1); P.zp1 = (P.Rp1.zo ^ 0x80) & 0xff;
-    P.dwa2 = reinterpret_cast<const uint2 *>(blob(o2[20])); P.dcb2 = reinterpret_cast<const int *>(blob(o2[21]));
-    P.w2 = reinterpret_cast<const i4v *>(blob(o2[16])); P.w2l = split ? reinterpret_cast<const i4v *>(blob(o2[18])) : nullptr;
-    P.cb2 = reinterpret_cast<const int *>(blob(o2[17]));
+    P.dwa2 = reinterpret_cast<const uint2 *>(blob(o2[W_Q_DW_A_OFF])); P.dcb2 = reinterpret_cast<const int *>(blob(o2[W_Q_DW_CB_OFF]));
+    P.w2 = reinterpret_cast<const i4v *>(blob(o2[W_W_OFF])); P.w2l = split ? reinterpret_cast<const i4v *>(blob(o2[W_AFF_OFF])) : nullptr;
+    P.cb2 = reinterpret_cast<const int *>(blob(o2[W_B_OFF]));
     P.Rd2 = dwreq(o2); P.Rp2 = make_req(o2);
     const QReq *R[5] = {&P.R0, &P.Rd1, &P.Rp1, &P.Rd2, &P.Rp2};
     bool byte_clamp = true, small_shift = true;
@@ -396,7 +396,7 @@ int netq_run_front(dd_net *net, const int32_t *o0, const int32_t *o1, const int3
     const int blocks = std::max(1, std::min(2 * n_cu, rows_total / 15));
     const int rpb = dd_ceil_div(rows_total, blocks);
     const unsigned grid = (unsigned)dd_ceil_div(rows_total, rpb);
-    static const bool stamps = getenv("DD_Q_STAMPS") && atoi(getenv("DD_Q_STAMPS")) != 0;
+    static const bool stamps = dd_env_int("DD_Q_STAMPS", 0) != 0;
     const size_t n_st = (size_t)grid * 4 * 8;
     if (stamps) { DD_HIP(hipMalloc(&P.dbg, n_st * 8)); DD_HIP(hipMemsetAsync(P.dbg, 0, n_st * 8, s)); }
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), F_LDS, s, P, rows_total, rpb);

@@ -286,27 +286,27 @@ __global__ __launch_bounds__(1024) void q_mid_k(const QMidP P, const int rows_to
 // launch.  *ran = 0: not these shapes / quantisation parameters -- the caller runs the two launches.
 int netq_run_mid(dd_net *net, const int32_t *o3, const int32_t *o4, int nimg, hipStream_t s, int *ran) {
     *ran = 0;
-    if (o3[0] != OP_QDWPW || o4[0] != OP_QDWPW || o4[1] != o3[2] || o3[1] < 0) return DD_OK;
-    const TensorDesc &ti = net->tensors[o3[1]], &t3 = net->tensors[o3[2]], &t4 = net->tensors[o4[2]];
+    if (o3[W_KIND] != OP_QDWPW || o4[W_KIND] != OP_QDWPW || o4[W_SRC] != o3[W_DST] || o3[W_SRC] < 0) return DD_OK;
+    const TensorDesc &ti = net->tensors[o3[W_SRC]], &t3 = net->tensors[o3[W_DST]], &t4 = net->tensors[o4[W_DST]];
     if (ti.h != M_S3 || ti.w != M_S3 || ti.cs != 128 || t3.h != M_S3 || t3.w != M_S3 || t3.cs != 128 || t4.h != M_S4 || t4.w != M_S4 || t4.cs != 256 ||
         !ti.pad || !t3.pad || !t4.pad) return DD_OK;
-    if (o3[7] != 1 || o3[8] != 1 || o3[9] != 1 || o3[10] != 128 || o3[11] != 128 || o4[7] != 2 || o4[8] != 1 || o4[9] != 1 || o4[10] != 128 || o4[11] != 256) return DD_OK;
-    const bool split = o3[18] != 0;                                // both pointwise filters split into hi + lo parts (no row sums), or neither (zero points of 128)
-    if ((o4[18] != 0) != split || o3[38] != 0 || o4[38] != 0 || o3[47] != 0 || o4[47] != 0) return DD_OK;
-    if (!o3[17] || !o3[20] || !o3[21] || !o4[17] || !o4[20] || !o4[21]) return DD_OK;
+    if (o3[W_STRIDE] != 1 || o3[W_PAD_T] != 1 || o3[W_PAD_L] != 1 || o3[W_CIN] != 128 || o3[W_COUT] != 128 || o4[W_STRIDE] != 2 || o4[W_PAD_T] != 1 || o4[W_PAD_L] != 1 || o4[W_CIN] != 128 || o4[W_COUT] != 256) return DD_OK;
+    const bool split = o3[W_AFF_OFF] != 0;                                // both pointwise filters split into hi + lo parts (no row sums), or neither (zero points of 128)
+    if ((o4[W_AFF_OFF] != 0) != split || o3[W_Q_ZWC] != 0 || o4[W_Q_ZWC] != 0 || o3[W_Q_DUP] != 0 || o4[W_Q_DUP] != 0) return DD_OK;
+    if (!o3[W_B_OFF] || !o3[W_Q_DW_A_OFF] || !o3[W_Q_DW_CB_OFF] || !o4[W_B_OFF] || !o4[W_Q_DW_A_OFF] || !o4[W_Q_DW_CB_OFF]) return DD_OK;
     char *W = net->d_weights;
     QMidP P;
     memset(&P, 0, sizeof(P));
     P.in = static_cast<const uint8_t *>(net->bufs[ti.buf]);
     P.out = static_cast<uint8_t *>(net->bufs[t4.buf]);
     auto blob = [&](int32_t off) { return W + (size_t)(uint32_t)off; };
-    auto dwreq = [&](const int32_t *o) { int32_t d[48] = {0}; d[32] = o[22]; d[33] = o[23]; d[36] = o[24]; d[37] = o[25]; d[40] = o[28]; return make_req(d); };
-    P.dwa3 = reinterpret_cast<const uint2 *>(blob(o3[20])); P.dcb3 = reinterpret_cast<const int *>(blob(o3[21]));
-    P.w3 = reinterpret_cast<const i4v *>(blob(o3[16])); P.w3l = split ? reinterpret_cast<const i4v *>(blob(o3[18])) : nullptr;
-    P.cb3 = reinterpret_cast<const int *>(blob(o3[17])); P.Rd3 = dwreq(o3); P.Rp3 = make_req(o3); P.zp3 = (P.Rp3.zo ^ 0x80) & 0xff;
-    P.dwa4 = reinterpret_cast<const uint2 *>(blob(o4[20])); P.dcb4 = reinterpret_cast<const int *>(blob(o4[21]));
-    P.w4 = reinterpret_cast<const i4v *>(blob(o4[16])); P.w4l = split ? reinterpret_cast<const i4v *>(blob(o4[18])) : nullptr;
-    P.cb4 = reinterpret_cast<const int *>(blob(o4[17])); P.Rd4 = dwreq(o4); P.Rp4 = make_req(o4);
+    auto dwreq = [&](const int32_t *o) { int32_t d[OP_WORDS] = {0}; d[W_Q_MULT] = o[W_Q_DW_MULT]; d[W_Q_SHIFT] = o[W_Q_DW_SHIFT]; d[W_Q_LO] = o[W_Q_DW_LO]; d[W_Q_HI] = o[W_Q_DW_HI]; d[W_Q_OUT_ZP] = o[W_Q_DW_OUT_ZP]; return make_req(d); };
+    P.dwa3 = reinterpret_cast<const uint2 *>(blob(o3[W_Q_DW_A_OFF])); P.dcb3 = reinterpret_cast<const int *>(blob(o3[W_Q_DW_CB_OFF]));
+    P.w3 = reinterpret_cast<const i4v *>(blob(o3[W_W_OFF])); P.w3l = split ? reinterpret_cast<const i4v *>(blob(o3[W_AFF_OFF])) : nullptr;
+    P.cb3 = reinterpret_cast<const int *>(blob(o3[W_B_OFF])); P.Rd3 = dwreq(o3); P.Rp3 = make_req(o3); P.zp3 = (P.Rp3.zo ^ 0x80) & 0xff;
+    P.dwa4 = reinterpret_cast<const uint2 *>(blob(o4[W_Q_DW_A_OFF])); P.dcb4 = reinterpret_cast<const int *>(blob(o4[W_Q_DW_CB_OFF]));
+    P.w4 = reinterpret_cast<const i4v *>(blob(o4[W_W_OFF])); P.w4l = split ? reinterpret_cast<const i4v *>(blob(o4[W_AFF_OFF])) : nullptr;
+    P.cb4 = reinterpret_cast<const int *>(blob(o4[W_B_OFF])); P.Rd4 = dwreq(o4); P.Rp4 = make_req(o4);
     const QReq *R[4] = {&P.Rd3, &P.Rp3, &P.Rd4, &P.Rp4};
     bool byte_clamp = true, small_shift = true;
     for (const QReq *r : R) {

@@ -23,6 +23,25 @@ ACT_NONE, ACT_RELU6, ACT_ELU, ACT_SILU, ACT_RELU, ACT_SIGMOID = 0, 1, 2, 3, 4, 5
 EPI_F16, EPI_F32, EPI_SSD_HEAD, EPI_YOLO = 0, 1, 2, 3
 DT_F16, DT_F32, DT_U8 = 0, 1, 2
 OP_WORDS, TENSOR_WORDS = 48, 8
+# The op record: word index of every field, name for name the OpWord enum of csrc/net_priv.h (W_KIND = 0 is kind=0; tests/test_op_fields.py holds the
+# two together).  Words 5 / 6 and 20 .. 47 carry several meanings, one name each: kh / kw of a convolution are s2d / swap_rb of the input op and
+# pool_k / pool_cascade of a pool; p0 .. p5 and f0 .. f7 are the f16 ops' integer and float parameters; q_* are the uint8 ops' own (netsq.py).
+OP_FIELDS = dict(
+    kind=0, src=1, dst=2, res=3, dst2=4, kh=5, kw=6, stride=7, pad_t=8, pad_l=9, cin=10, cout=11, cout_pad=12, kpad=13, act=14, epi=15, w_off=16,
+    b_off=17, aff_off=18, has_aff=19, p0=20, p1=21, p2=22, p3=23, p4=24, p5=25, ho=26, wo=27, bk=28, pool=29, hint=30, aux_off=31, s2d=5, swap_rb=6,
+    pool_k=5, pool_cascade=6, f0=32, f1=33, f2=34, f3=35, f4=36, f5=37, f6=38, f7=39, q_mult=32, q_shift=33, q_lo=36, q_hi=37, q_zwc=38, q_in_zp=39,
+    q_out_zp=40, q_linear=41, q_row_bytes=42, q_base_off=43, q_cout_store=44, q_dw_cq_off=45, q_cq_off=46, q_dup=47, q_dw_a_off=20, q_dw_cb_off=21,
+    q_dw_mult=22, q_dw_shift=23, q_dw_lo=24, q_dw_hi=25, q_dw_out_zp=28, q_box_mult=20, q_box_shift=21, q_box_out_zp=22, q_box_row_bytes=23,
+    q_box_base_off=24, q_box_cout_store=25, q_box_zwc=28, q_add_m1=20, q_add_e1=21, q_add_m2=22, q_add_e2=23, q_add_mo=24, q_add_eo=25, q_add_z1=28,
+    q_add_z2=29, q_add_zo=31, q_add_lo=34, q_add_hi=35, q_dec_classes=20, q_dec_anchors=21, q_dec_box_scale=32, q_dec_box_zp=33, q_dec_score_scale=34,
+    q_dec_score_zp=35)
+KIND, SRC, DST, HINT = OP_FIELDS['kind'], OP_FIELDS['src'], OP_FIELDS['dst'], OP_FIELDS['hint']
+# the hint word: what the compiler knows about the ops behind an op (the executor still checks shapes, batch and balance before it folds anything)
+HINT_NONE = 0
+HINT_NEXT_ONLY = 1        # only the next op reads my output
+HINT_HOLD_UNIT = 2        # hold this residual unit for the next one
+HINT_NEXT_IS_PROJ = 3     # the next op is this block's projection
+HINT_PAIR_MEMBER = 4      # member of a conv3_x block launch
 MAGIC = 0x314E4444
 BN_EPS = 1e-3
 
@@ -101,21 +120,19 @@ class Program:
         w = np.zeros(OP_WORDS, dtype=np.int32)
         f = w.view(np.float32)
         w[0:5] = (kind, src, dst, res, dst2)
-        names = dict(kh=5, kw=6, stride=7, pad_t=8, pad_l=9, cin=10, cout=11, cout_pad=12, kpad=13, act=14, epi=15,
-                     w_off=16, b_off=17, aff_off=18, has_aff=19, ho=26, wo=27, bk=28, pool=29, fuse_next=30, aux_off=31)
         for k, v in kw.items():
             if k == 'p':
-                w[20:20 + len(v)] = v
+                w[OP_FIELDS['p0']:OP_FIELDS['p0'] + len(v)] = v
             elif k == 'f':
-                f[32:32 + len(v)] = v
-            elif k == 'raw':                      # {word index: int32} (uint8 programs, deepdish_amd/netsq.py)
-                for i, x in v.items():
-                    w[i] = x
-            elif k == 'rawf':
-                for i, x in v.items():
-                    f[i] = x
+                f[OP_FIELDS['f0']:OP_FIELDS['f0'] + len(v)] = v
+            elif k == 'raw':                      # {field name: int32} (uint8 programs, deepdish_amd/netsq.py)
+                for name, x in v.items():
+                    w[OP_FIELDS[name]] = x
+            elif k == 'rawf':                     # {field name: float32}
+                for name, x in v.items():
+                    f[OP_FIELDS[name]] = x
             else:
-                w[names[k]] = v
+                w[OP_FIELDS[k]] = v
         self.ops.append(w)
         self.info.append(dict(kernel='?', flops=0, bytes=0, wbytes=0))
 
@@ -124,7 +141,7 @@ class Program:
         """c_pad: channels of the output tensor (the real ones first, zeros behind them; 0 = 12 of 16 / 3 of 8)."""
         h, w = (self.in_h // 2, self.in_w // 2) if s2d else (self.in_h, self.in_w)
         t = self.tensor(h, w, c_pad if c_pad else 12 if s2d else 3, cs=c_pad if c_pad else 16 if s2d else 8)
-        self._op(OP_INPUT, dst=t, kh=int(s2d), kw=int(swap_rb), f=[mean, scale])
+        self._op(OP_INPUT, dst=t, s2d=int(s2d), swap_rb=int(swap_rb), f=[mean, scale])
         return t
 
     def stem(self, w_hwio, bias, stride, act, swap_rb, mean=0.0, scale=1.0):
@@ -271,9 +288,9 @@ class Program:
         if kernel is None or c % 8 or cout % 8:
             # the previous op is the previous block's pointwise layer and this depthwise layer is its only reader: from 160
             # frames both can run as one launch (csrc/nets.hip conv_ws_dw_k; the executor checks shapes, batch and balance)
-            if (self.PW_DW_FUSE and stride == 1 and self.ops and self.ops[-1][0] == OP_CONV and self.ops[-1][2] == src
-                    and tuple(self.ops[-1][5:8]) == (1, 1, 1) and src not in self.keep):
-                self.ops[-1][30] = 1
+            if (self.PW_DW_FUSE and stride == 1 and self.ops and self.ops[-1][KIND] == OP_CONV and self.ops[-1][DST] == src
+                    and tuple(self.ops[-1][k] for k in (OP_FIELDS['kh'], OP_FIELDS['kw'], OP_FIELDS['stride'])) == (1, 1, 1) and src not in self.keep):
+                self.ops[-1][HINT] = HINT_NEXT_ONLY
             x = self.dwconv(src, dw_hwc, dw_bias, stride, dw_act)
             return self.conv(x, pw_hwio, pw_bias, act=pw_act)
         assert dw_hwc.shape == (3, 3, c) and pw_hwio.shape[:3] == (1, 1, c)
@@ -295,7 +312,7 @@ class Program:
         wo = (s['w'] + 2 * pad - k) // stride + 1
         if dst is None:
             dst = self.tensor(ho, wo, s['c'])
-        self._op(OP_MAXPOOL, src=src, dst=dst, kh=k, stride=stride, pad_t=pad, cout_pad=rup(s['c'], 8))
+        self._op(OP_MAXPOOL, src=src, dst=dst, pool_k=k, stride=stride, pad_t=pad, cout_pad=rup(s['c'], 8))
         self.info[-1] = dict(kernel='maxpool_k', flops=0, bytes=2 * s['c'] * (s['h'] * s['w'] + ho * wo), wbytes=0)
         return dst
 
@@ -303,7 +320,7 @@ class Program:
         """n stride-1 k x k max pools of each other in one launch (csrc/nets.hip pool_cascade_k): result i goes to the channel slice i * c behind
         dst_first (a view of the concat tensor: YOLOv5's SPP)."""
         s = self.T(src)
-        self._op(OP_MAXPOOL, src=src, dst=dst_first, kh=k, kw=n, stride=1, pad_t=k // 2, cout_pad=rup(s['c'], 8))
+        self._op(OP_MAXPOOL, src=src, dst=dst_first, pool_k=k, pool_cascade=n, stride=1, pad_t=k // 2, cout_pad=rup(s['c'], 8))
         self.info[-1] = dict(kernel='pool_cascade_k', flops=0, bytes=2 * s['c'] * s['h'] * s['w'] * (1 + n), wbytes=0)
         return dst_first
 
@@ -326,8 +343,8 @@ class Program:
             op = self.ops[-1]
             a = np.zeros((2, rup(cout, 8)), dtype=np.float32)
             a[0, :cout], a[1, :cout] = aff2
-            op[18] = self.add_blob(a)
-            op[19] = 1
+            op[OP_FIELDS['aff_off']] = self.add_blob(a)
+            op[OP_FIELDS['has_aff']] = 1
         return dst
 
     def l2norm(self, src, eps):
@@ -432,14 +449,14 @@ def compile_mars(wd, in_h=64, in_w=32):
     w, b = fold_conv_bn(wd, 'conv1_1')
     x = c11 = P.stem(w, b, 1, ACT_ELU, swap_rb=bool(wd.get('__swap_rb__', True)))   # :175-177 BGR -> RGB, :101-105 (a .tflite graph says whether it reverses the channels)
     if Program.STEM_POOL_FUSE:       # conv1_1 is read by conv1_2 only: with >= 160 crops both run as one launch
-        P.ops[-1][30] = 1            # (conv3x3_pool_rows_k<STEM>) and the conv1_1 tensor is not written
+        P.ops[-1][HINT] = HINT_NEXT_ONLY   # (conv3x3_pool_rows_k<STEM>) and the conv1_1 tensor is not written
     w, b = fold_conv_bn(wd, 'conv1_2')
     if in_w == 32:
         x = pool = P.conv(x, w, b, act=ACT_ELU, pool=True)                     # :106-110 + :116 VALID pool, one launch (the fused kernel is 32 wide)
     else:                                                                      # other crop sizes: the pool as its own op
         wide = Program.STEM_POOL_FUSE and in_w in (64, 128) and in_h % 2 == 0   # stem_conv_pool_wide_k takes the three ops
         if not wide:
-            P.ops[-1][30] = 0
+            P.ops[-1][HINT] = HINT_NONE
         x = pool = P.maxpool(P.conv(x, w, b, act=ACT_ELU), 3, 2, 0)
     raw, pre = x, x                  # raw = block input (skip path), pre = what conv "1" reads
     for i, (name, c, inc, first) in enumerate(MARS_BLOCKS):
@@ -447,10 +464,10 @@ def compile_mars(wd, in_h=64, in_w=32):
         w, b = fold_conv_bn(wd, name + '/1')
         h1 = P.conv(pre, w, b, stride=stride, act=ACT_ELU)                      # :58-62
         if Program.RES_UNIT_FUSE and not inc and c == 32:
-            P.ops[-1][30] = 1        # h1 is read by conv "2" only: both layers of the unit run as one launch (res_unit_rows_k)
+            P.ops[-1][HINT] = HINT_NEXT_ONLY   # h1 is read by conv "2" only: both layers of the unit run as one launch (res_unit_rows_k)
         if inc:
             if Program.PROJ_FUSE:
-                P.ops[-1][30] = 3        # the next op is this block's 1x1 stride-2 projection of `raw`: both may run as one launch (csrc/mars_tail.hip)
+                P.ops[-1][HINT] = HINT_NEXT_IS_PROJ   # the next op is this block's 1x1 stride-2 projection of `raw`: both may run as one launch (csrc/mars_tail.hip)
             skip = P.conv(raw, wd[name + '/projection/weights'], np.zeros(c, np.float32), stride=2)   # :30-36
         else:
             skip = raw
@@ -459,7 +476,7 @@ def compile_mars(wd, in_h=64, in_w=32):
             # conv3_x: h1 (and the projection) are read by conv "2" only -- with enough crops the block's layers run as ONE launch
             # (csrc/mars_pair.hip) and neither tensor is written.  Marks the op in front of conv "2"; the widening block's stride-2 layer
             # already carries the projection marker (3), which chains it to the projection for the buffer lifetimes.
-            P.ops[-1][30] = 4
+            P.ops[-1][HINT] = HINT_PAIR_MEMBER
         s = P.T(h1)
         out = P.tensor(s['h'], s['w'], c)
         if nxt is not None:          # the next block's BN+ELU pre-activation is a second epilogue output (:17-21)
@@ -468,7 +485,7 @@ def compile_mars(wd, in_h=64, in_w=32):
                    aff2=bn_affine(wd, nxt + '/bn'))                             # :68-72 + :37/:39 skip add
             nb = MARS_BLOCKS[i + 1]
             if Program.RES_UNIT_FUSE and Program.RES_PAIR_FUSE and not inc and c == 32 and not nb[2] and nb[1] == 32:
-                P.ops[-1][30] = 2    # out / out2 are read by the next residual unit only (its skip and its first layer): with enough
+                P.ops[-1][HINT] = HINT_HOLD_UNIT   # out / out2 are read by the next residual unit only (its skip and its first layer): with enough
                                      # crops both units run as one launch (res_pair_rows_k) and neither tensor is written
             raw, pre = out, out2
         else:
@@ -568,8 +585,8 @@ def compile_ssd_mobilenet(wd, in_size=300, mean=127.5, std=127.5):
         s, t = bn_affine(wd, f'dw{i}/bn')
         w, b = fold_conv_bn(wd, f'pw{i}')
         x = P.dwpw(x, wd[f'dw{i}/weights'][:, :, :, 0] * s, t, st, ACT_RELU6, w, b, ACT_RELU6)
-        if i == 1 and Program.SSD_FRONT_FUSE and P.ops[-1][0] == OP_DWPW and P.ops[-2][0] == OP_STEM:
-            P.ops[-2][30] = 1        # conv0 is read by block 1 only: one launch (csrc/nets.hip ssd_front_k), conv0's tensor is not written
+        if i == 1 and Program.SSD_FRONT_FUSE and P.ops[-1][KIND] == OP_DWPW and P.ops[-2][KIND] == OP_STEM:
+            P.ops[-2][HINT] = HINT_NEXT_ONLY   # conv0 is read by block 1 only: one launch (csrc/nets.hip ssd_front_k), conv0's tensor is not written
         if i in (11, 13):
             feats.append(x)
             P.keep.add(x)
@@ -701,7 +718,7 @@ def compile_yolov5s(wd, in_size=640):
     if FOCUS32:
         x = P.input(swap_rb=False, s2d=True, c_pad=32)
         if FOCUS_FUSE:
-            P.ops[-1][30] = 1                                                 # only the conv behind it reads the sliced tensor: the executor folds the slicing into its patch fill
+            P.ops[-1][HINT] = HINT_NEXT_ONLY                                  # only the conv behind it reads the sliced tensor: the executor folds the slicing into its patch fill
         w, b = fold_conv_bn(wd, 'm0.focus')
         w32 = np.zeros((3, 3, 32, w.shape[3]), dtype=w.dtype)
         w32[:, :, :12] = w

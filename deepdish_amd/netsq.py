@@ -34,13 +34,13 @@ def _req_words(L):
     linear = int(L['act'] == 'none')
     if not linear and lo < L['out_zp']:
         raise ValueError('activation clamp below the zero point')
-    return {32: m, 33: -shift, 36: lo, 37: hi, 40: int(L['out_zp']), 41: linear}
+    return dict(q_mult=m, q_shift=-shift, q_lo=lo, q_hi=hi, q_out_zp=int(L['out_zp']), q_linear=linear)
 
 
 def folded_addends(cb, rw):
     """Per-channel 64-bit addend of the ReLU-type requantisation z = ((acc + cb) M + C) >> (31 + e)  ->  (acc M + [cb M + C]) >> (31 + e),
     C = 2^30 + 2^(30+e) + (zo << (31+e)) (csrc/netsq.hip make_req): accumulators start at zero and v_mad_i64_i32 adds the channel's constant."""
-    m, e, zo = int(rw[32]), int(rw[33]), int(rw[40])
+    m, e, zo = int(rw['q_mult']), int(rw['q_shift']), int(rw['q_out_zp'])
     c = (1 << 30) + ((1 << (30 + e)) if e > 0 else 0) + (zo << (31 + e))
     out = [int(v) * m + c for v in np.asarray(cb).reshape(-1)]
     _model_need(all(-(1 << 62) < v < (1 << 62) for v in out), 'a requantisation addend (folded bias x multiplier + zero point << %d) leaves 62 bits' % (31 + e), 'uint8 layer')
@@ -155,11 +155,11 @@ def _model_need(cond, what, model='uint8 SSD-MobileNet-v1'):
 
 
 def add_words(a):
-    """Op words of a uint8 ADD (OP_QADD, or OP_QCONV with a residual operand): 20..25 the three multipliers and right shifts
-    (quantize.add_multipliers), 28 / 29 the two input zero points, 31 the output zero point, 34 / 35 the clamp."""
+    """Op words of a uint8 ADD (OP_QADD, or OP_QCONV with a residual operand): the three multipliers and right shifts
+    (quantize.add_multipliers), the two input zero points, the output zero point, the clamp."""
     m1, e1, m2, e2, mo, eo = quantize.add_multipliers(a)
-    return {20: m1, 21: e1, 22: m2, 23: e2, 24: mo, 25: eo, 28: int(a['in1_zp']), 29: int(a['in2_zp']), 31: int(a['out_zp']),
-            34: int(a['lo']), 35: int(a['hi'])}
+    return dict(q_add_m1=m1, q_add_e1=e1, q_add_m2=m2, q_add_e2=e2, q_add_mo=mo, q_add_eo=eo, q_add_z1=int(a['in1_zp']), q_add_z2=int(a['in2_zp']),
+                q_add_zo=int(a['out_zp']), q_add_lo=int(a['lo']), q_add_hi=int(a['hi']))
 
 
 def pad_channels(L, cin=None, cout=None):
@@ -223,7 +223,7 @@ class QBuilder:
         wp, wl, cb = pack_conv0(L)
         raw = _req_words(L)
         P.add_blob(np.zeros(16, np.uint8))                      # (offset 0 means "absent" in the op words)
-        raw.update({38: 0 if wl is not None else 128 - int(L['w_zp']), 39: int(L['in_zp']), 46: P.add_blob(folded_addends(cb, raw))})
+        raw.update(q_zwc=0 if wl is not None else 128 - int(L['w_zp']), q_in_zp=int(L['in_zp']), q_cq_off=P.add_blob(folded_addends(cb, raw)))
         P._op(OP_QCONV0, dst=x, kh=3, kw=3, stride=L['stride'], pad_t=pt, pad_l=pl, cin=3, cout=32, cout_pad=32,
               w_off=P.add_blob(wp), b_off=P.add_blob(cb), aff_off=P.add_blob(wl) if wl is not None else 0, ho=ho, wo=wo, raw=raw)
         self.info('q_conv0_k', 2 * ho * wo * 27 * 32, 3 * P.in_h * P.in_w + ho * wo * 32, 27 * 32 + 4 * 32, 3 * P.in_h * P.in_w)
@@ -246,9 +246,9 @@ class QBuilder:
         if epi != QEPI_ROWS:                                 # a bordered output is this op's own tensor (the ADD's, where it has one); rows go to `dst`
             dst = P.qtensor(ho, wo, L['w'].shape[3], add['out_zp'] if add is not None else L['out_zp'])
         raw = _req_words(L)
-        raw.update({38: 128 - int(L['w_zp']), 39: int(L['in_zp']), 42: row_bytes, 43: base_off, 44: cout_store})
+        raw.update(q_zwc=128 - int(L['w_zp']), q_in_zp=int(L['in_zp']), q_row_bytes=row_bytes, q_base_off=base_off, q_cout_store=cout_store)
         # the per-channel 64-bit requantisation addends (q_pws_k): cbias * M + C of the ReLU form, or + 2^30 (the first rounding) without activation
-        raw[46] = P.add_blob(folded_addends(cb, raw) if not raw[41] else np.array([int(v) * int(raw[32]) + (1 << 30) for v in cb], dtype=np.int64))
+        raw['q_cq_off'] = P.add_blob(folded_addends(cb, raw) if not raw['q_linear'] else np.array([int(v) * int(raw['q_mult']) + (1 << 30) for v in cb], dtype=np.int64))
         if add is not None:
             r = P.T(res)
             self.need(r['zp'] == add['in2_zp'] and L['out_zp'] == add['in1_zp'] and (r['h'], r['w'], r['c']) == (ho, wo, L['w'].shape[3]),
@@ -266,7 +266,7 @@ class QBuilder:
 
     def conv_heads(self, src, Lc, Lb, cls_args, box_args, name='?'):
         """The class and box predictors of one feature map as ONE op (they read the same pixels; csrc/netsq.hip q_pws_k stores both, small
-        batches run one launch of q_conv_k): fragments of the class layer first, then the box layer's; its parameters in words 20..25, 28."""
+        batches run one launch of q_conv_k): fragments of the class layer first, then the box layer's; its parameters in the q_box_* words."""
         P = self.P
         s = P.T(src)
         ho, wo, pt, pl = self.geom(src, 1, 1)
@@ -274,12 +274,13 @@ class QBuilder:
         wc, cbc, kcpt = pack_conv(Lc, QEPI_ROWS, cls_args['chan_map'], cls_args['cout_pad'])
         wb, cbb, _ = pack_conv(Lb, QEPI_ROWS, None, None)
         rc, rb = _req_words(Lc), _req_words(Lb)
-        self.need(rc[41] and rb[41], '%s: predictors carry no activation' % name)
-        lin = lambda cb, r: np.array([int(v) * int(r[32]) + (1 << 30) for v in cb], dtype=np.int64)
+        self.need(rc['q_linear'] and rb['q_linear'], '%s: predictors carry no activation' % name)
+        lin = lambda cb, r: np.array([int(v) * int(r['q_mult']) + (1 << 30) for v in cb], dtype=np.int64)
         raw = dict(rc)
-        raw.update({38: 128 - int(Lc['w_zp']), 39: int(Lc['in_zp']), 42: cls_args['row_bytes'], 43: cls_args['base_off'], 44: cls_args['cout_store'],
-                    46: P.add_blob(np.concatenate([lin(cbc, rc), lin(cbb, rb)])),
-                    20: rb[32], 21: rb[33], 22: rb[40], 23: box_args['row_bytes'], 24: box_args['base_off'], 25: box_args['cout_store'], 28: 128 - int(Lb['w_zp'])})
+        raw.update(q_zwc=128 - int(Lc['w_zp']), q_in_zp=int(Lc['in_zp']), q_row_bytes=cls_args['row_bytes'], q_base_off=cls_args['base_off'], q_cout_store=cls_args['cout_store'],
+                   q_cq_off=P.add_blob(np.concatenate([lin(cbc, rc), lin(cbb, rb)])),
+                   q_box_mult=rb['q_mult'], q_box_shift=rb['q_shift'], q_box_out_zp=rb['q_out_zp'], q_box_row_bytes=box_args['row_bytes'], q_box_base_off=box_args['base_off'],
+                   q_box_cout_store=box_args['cout_store'], q_box_zwc=128 - int(Lb['w_zp']))
         P._op(OP_QCONV, src=src, dst=cls_args['dst'], dst2=box_args['dst'], kh=1, kw=1, stride=1, pad_t=pt, pad_l=pl, cin=s['c'], cout=Lc['w'].shape[3] + Lb['w'].shape[3],
               cout_pad=len(cbc) + len(cbb), kpad=kcpt, act=len(cbc) // 16, epi=QEPI_ROWS, w_off=P.add_blob(np.concatenate([wc, wb])), b_off=P.add_blob(np.concatenate([cbc, cbb])),
               ho=ho, wo=wo, raw=raw)
@@ -298,8 +299,8 @@ class QBuilder:
             self.layer_t[name] = dst
         mf = pack_dw_mfma(L)                                    # the matrix-pipe form's operand table (None: a weight needs w - zw = 255)
         P._op(OP_QDW, src=src, dst=dst, kh=3, kw=3, stride=L['stride'], pad_t=pt, pad_l=pl, cin=s['c'], cout=s['c'], cout_pad=s['c'],
-              w_off=P.add_blob(w16), b_off=P.add_blob(cb), ho=ho, wo=wo, raw=_req_words(L),
-              p=[P.add_blob(mf[0]), P.add_blob(mf[1])] if mf is not None else [0, 0])
+              w_off=P.add_blob(w16), b_off=P.add_blob(cb), ho=ho, wo=wo,
+              raw=dict(_req_words(L), q_dw_a_off=P.add_blob(mf[0]) if mf is not None else 0, q_dw_cb_off=P.add_blob(mf[1]) if mf is not None else 0))
         self.info('q_dw_k', 2 * ho * wo * 9 * s['c'], s['h'] * s['w'] * s['c'] + ho * wo * s['c'], 9 * s['c'] + 4 * s['c'])
         return dst
 
@@ -324,7 +325,7 @@ class QBuilder:
         self.need(s['zp'] == Ld['in_zp'] and Ld['out_zp'] == Lp['in_zp'] and Ld['w'].shape[2] == cin and Lp['w'].shape[2] == cin, '%s / %s: zero points and channel counts along the block do not agree' % (dname, pname))
         packed_dw = pack_dw_mfma(Ld)
         rd, rp = _req_words(Ld), _req_words(Lp)
-        if packed_dw is None or rd[33] < 1 or rp[33] < 1:
+        if packed_dw is None or rd['q_shift'] < 1 or rp['q_shift'] < 1:
             return self.conv(self.dw(src, Ld, dname), Lp, pname)           # w - zw = 255, or a multiplier >= 0.5: the two-op form handles it
         dwa, dcb = packed_dw
         wp, cb, kcpt = pack_conv(Lp, QEPI_Q16)
@@ -352,10 +353,11 @@ class QBuilder:
                 zwc = 0
         dst = P.qtensor(ho, wo, cout, Lp['out_zp'])
         raw = dict(rp)
-        raw.update({38: zwc, 39: int(Lp['in_zp']), 45: P.add_blob(folded_addends(dcb, rd)), 46: P.add_blob(folded_addends(cb, rp)), 47: dup})
+        raw.update(q_zwc=zwc, q_in_zp=int(Lp['in_zp']), q_dw_cq_off=P.add_blob(folded_addends(dcb, rd)), q_cq_off=P.add_blob(folded_addends(cb, rp)), q_dup=dup)
         P._op(OP_QDWPW, src=src, dst=dst, kh=1, kw=1, stride=stride, pad_t=pt, pad_l=pl, cin=cin, cout=cout, cout_pad=cout, kpad=kcpt,
               w_off=P.add_blob(wp), b_off=P.add_blob(cb), aff_off=w_lo, ho=ho, wo=wo,
-              p=[P.add_blob(dwa), P.add_blob(dcb), rd[32], rd[33], rd[36], rd[37]], bk=rd[40], raw=raw)
+              raw=dict(raw, q_dw_a_off=P.add_blob(dwa), q_dw_cb_off=P.add_blob(dcb), q_dw_mult=rd['q_mult'], q_dw_shift=rd['q_shift'], q_dw_lo=rd['q_lo'], q_dw_hi=rd['q_hi'],
+                       q_dw_out_zp=rd['q_out_zp']))
         self.info('q_dwpw_k', 2 * ho * wo * cin * (9 + cout), s['h'] * s['w'] * cin + ho * wo * cout, cin * (9 + cout) + 4 * (cin + cout), s['h'] * s['w'] * cin)
         return dst
 
@@ -391,8 +393,9 @@ class QBuilder:
     def decode(self, box_t, cls_t, Lb, Lc, logistic, n_cls, n_anchors, cls_row):
         P = self.P
         lut = quantize.logistic_table(Lc['out_scale'], Lc['out_zp'], logistic['out_scale'], logistic['out_zp'])
-        P._op(OP_QSSD_DECODE, src=box_t, res=cls_t, w_off=P.add_blob(lut), p=[n_cls, n_anchors],
-              rawf={32: float(Lb['out_scale']), 33: float(Lb['out_zp']), 34: float(logistic['out_scale']), 35: float(logistic['out_zp'])})
+        P._op(OP_QSSD_DECODE, src=box_t, res=cls_t, w_off=P.add_blob(lut), raw=dict(q_dec_classes=n_cls, q_dec_anchors=n_anchors),
+              rawf=dict(q_dec_box_scale=float(Lb['out_scale']), q_dec_box_zp=float(Lb['out_zp']), q_dec_score_scale=float(logistic['out_scale']),
+                        q_dec_score_zp=float(logistic['out_zp'])))
         self.info('q_ssd_decode_k', 0, n_anchors * (4 + cls_row + 24), 256)
 
 
