@@ -99,7 +99,8 @@ class MultiStreamPipeline:
                              '(mars-64x32x3, mars-128x64x3, mars-256x128x3)' % (encoder_model, self.enc_hw[0], self.enc_hw[1]))
         # crops per encoder forward: the activation arena per crop grows 4.8 x / 19 x with the crop (nets.MARS_ARENA_BYTES_PER_CROP), so the default
         # shrinks by that much -- the arena stays within what 64 x 32 takes at the same stream count (never below 16 crops).
-        # The pipeline forwards in chunks of this many and the forward is crop-independent: the same bits at any chunk size
+        # The pipeline forwards in chunks of this many and the forward is crop-independent: the same bits however the crops fall into chunks.
+        # (The number itself is the engine's max_batch, which fixes the K split of its convolutions: another value, other last bits.)
         if not encoder_max_batch:
             per_crop = nets.MARS_ARENA_BYTES_PER_CROP
             encoder_max_batch = max(16, max(64, 32 * self.S) * per_crop[(64, 32)] // per_crop[self.enc_hw])

@@ -91,6 +91,7 @@ def test_long_scene_unbounded_gallery():
             got, want = app[rows], g[f'cost_{f}']
             live = got < 1e4                                        # gated entries are 1e5 (linear_assignment.py:181-189)
             assert live.sum() >= min(got.shape) - 2, f                # (nearly) every track's own detection passes the gate
+            assert live[want <= 0.2].all(), f                         # and no pair the reference would match (its own track's) is gated away
             worst = max(worst, float(np.abs(got[live] - want[live]).max()))
             compared += int(live.sum())
     assert compared >= 30 and worst <= 2e-6, (compared, worst)      # stated cosine tolerance (f32 both sides)
