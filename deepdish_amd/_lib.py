@@ -141,8 +141,11 @@ SIGNATURES = {
     'dd_pipeline_overlay': [P, P, c_int, P, P, P, P, P, P, P, P, P],
     'dd_render_create': [P, c_int, c_int, POINTER(P)],
     'dd_render_destroy': [P],
+    'dd_render_record_set': [P, c_int],
     'dd_render_put_mask': [P, P, c_int, c_int, POINTER(c_int)],
     'dd_render_draw': [P, P, c_int, P, c_int, P, P, P, P],
+    'dd_ground_camera': [c_double, c_double, c_double, c_int, c_int, c_double, c_double, c_double, P],
+    'dd_ground_from_image': [P, P, c_int, P, P, ctypes.c_longlong, P, c_int, P],
     'dd_jpeg_create': [P, c_int, c_int, c_int, c_int, POINTER(P)],
     'dd_jpeg_destroy': [P],
     'dd_jpeg_header': [P, P, c_int, POINTER(c_int)],

@@ -2,8 +2,10 @@
 // boxes, text) painted over frames that live in HBM, one launch for all requested streams.
 //   rectangle   Pillow's ImageDraw.rectangle(outline=...), byte for byte: the two horizontal edges, and the two vertical edges over rows
 //               min(y0 + 1, y1) .. max(y0 + 1, y1) (Draw.c draws them from y0 + 1 to y1 as lines: a box with y1 == y0 also colours row y0 + 1)
-//   line        this build's rule, exact integers: a capsule of odd width w around the segment a-b -- with d = b - a, L2 = d.d, t = (p - a).d,
-//               c = (p - a) x d: t <= 0: 4 |p - a|^2 <= w^2;  t >= L2: 4 |p - b|^2 <= w^2;  else 4 c^2 <= w^2 L2
+//   fill        Pillow's ImageDraw.rectangle(fill=...) without outline, byte for byte: every pixel x0 <= x <= x1, y0 <= y <= y1
+//               (fills and lines of even width are accepted only after dd_render_record_set(r, DD_RENDER_RECORDS_2))
+//   line        this build's rule, exact integers: a capsule of width w (1 .. 15, odd or even) around the segment a-b -- with d = b - a,
+//               L2 = d.d, t = (p - a).d, c = (p - a) x d: t <= 0: 4 |p - a|^2 <= w^2;  t >= L2: 4 |p - b|^2 <= w^2;  else 4 c^2 <= w^2 L2
 //   mask        Pillow's ImageDraw.draw_bitmap (what ImageDraw.text ends in): per channel t = dst (255 - m) + ink m + 128, ((t >> 8) + t) >> 8,
 //               the coverage m read from a u8 atlas in HBM
 // Painter's order: a workgroup owns one 64 x 16 tile of one output frame, loads it once, walks that stream's records in order (staged
@@ -18,9 +20,9 @@ constexpr int RD_THREADS = 256;
 constexpr int RD_TILE_W = 64, RD_TILE_H = 16;       // 16 lanes x 4 pixels wide, 16 rows: one wave = 4 rows
 constexpr int RD_CHUNK = 256;                       // records staged in LDS at a time: one per thread
 constexpr int RD_COORD_MIN = -8192, RD_COORD_MAX = 8191, RD_MAX_SIDE = 8192, RD_MAX_WIDTH = 15;
-enum { RD_RECT = 0, RD_LINE = 1, RD_MASK = 2 };
+enum { RD_RECT = 0, RD_LINE = 1, RD_MASK = 2, RD_FILL = 3 };
 
-struct RdRec { int kind, x0, y0, x1, y1, arg, ink, pad; };      // rect: corners; line: a, b, arg = width; mask: x, y, w, h, arg = atlas offset; ink = B | G << 8 | R << 16
+struct RdRec { int kind, x0, y0, x1, y1, arg, ink, pad; };      // rect, fill: corners; line: a, b, arg = width; mask: x, y, w, h, arg = atlas offset; ink = B | G << 8 | R << 16
 
 struct RdP {
     const uint8_t *frames;     // [*][H][W][3]
@@ -68,6 +70,12 @@ __device__ __forceinline__ void rd_apply(const RdRec &r, const uint8_t *__restri
             else if (t >= L2) in = 4 * ((long long)qx * qx + (long long)qy * qy) <= w2;
             else { const long long c = (long long)pxx * dy - (long long)py * dx; in = 4 * c * c <= w2 * L2; }
             if (in) px[j] = (uint32_t)r.ink;
+        }
+    } else if (r.kind == RD_FILL) {
+        if (y >= r.y0 && y <= r.y1) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (x + j >= r.x0 && x + j <= r.x1) px[j] = (uint32_t)r.ink;
         }
     } else {
         const int my = y - r.y0;
@@ -118,7 +126,8 @@ __global__ __launch_bounds__(RD_THREADS) void render_k(const RdP P) {
             else if (r.kind == RD_LINE) {
                 const int e = (r.arg + 1) / 2;
                 bx0 = min(r.x0, r.x1) - e; bx1 = max(r.x0, r.x1) + e; by0 = min(r.y0, r.y1) - e; by1 = max(r.y0, r.y1) + e;
-            } else { bx0 = r.x0; by0 = r.y0; bx1 = r.x0 + r.x1 - 1; by1 = r.y0 + r.y1 - 1; }
+            } else if (r.kind == RD_FILL) { bx0 = r.x0; bx1 = r.x1; by0 = r.y0; by1 = r.y1; }
+            else { bx0 = r.x0; by0 = r.y0; bx1 = r.x0 + r.x1 - 1; by1 = r.y0 + r.y1 - 1; }
             hit = bx0 <= tx1 && bx1 >= tx0 && by0 <= ty1 && by1 >= ty0;
         }
         const unsigned long long m = __ballot(hit);
@@ -159,6 +168,7 @@ struct dd_render {
     PinBuf h_recs;                         // ... staged here
     hipEvent_t copied = nullptr;           // the last draw's copy out of h_recs
     bool copy_pending = false;
+    int record_set = DD_RENDER_RECORDS_1;  // what dd_render_draw accepts: kinds 0 .. 2 with odd widths, or (2) also kind 3 and even widths
     std::mutex mu;
 };
 
@@ -185,6 +195,16 @@ int dd_render_destroy(dd_render *r) {
     r->d_recs.release();
     r->h_recs.release();
     delete r;
+    return DD_OK;
+}
+
+// Which records dd_render_draw accepts from now on.  A renderer starts with DD_RENDER_RECORDS_1 (rectangle outlines, lines of odd width, masks) and
+// refuses everything else, as it always has; DD_RENDER_RECORDS_2 adds the filled rectangle (kind 3) and lines of even width.
+int dd_render_record_set(dd_render *r, int record_set) {
+    DD_REQUIRE(r, DD_E_ARG, "dd_render_record_set: NULL argument");
+    DD_REQUIRE(record_set == DD_RENDER_RECORDS_1 || record_set == DD_RENDER_RECORDS_2, DD_E_ARG, "dd_render_record_set: record set %d (1 or 2)", record_set);
+    std::lock_guard<std::mutex> lk(r->mu);
+    r->record_set = record_set;
     return DD_OK;
 }
 
@@ -233,9 +253,10 @@ int dd_render_draw(dd_render *r, const uint8_t *frames_dev, int n_frames, const 
     DD_REQUIRE(total == 0 || prims_host, DD_E_ARG, "dd_render_draw: %d records and no array", total);
     std::lock_guard<std::mutex> lk(r->mu);
     const size_t atlas_used = r->atlas_host.size();
+    const bool wide = r->record_set == DD_RENDER_RECORDS_2;
     for (int k = 0; k < total; ++k) {
         const int32_t *q = prims_host + (size_t)k * 8;
-        DD_REQUIRE(q[0] >= RD_RECT && q[0] <= RD_MASK, DD_E_ARG, "dd_render_draw: record %d has kind %d", k, q[0]);
+        DD_REQUIRE(q[0] >= RD_RECT && q[0] <= (wide ? RD_FILL : RD_MASK), DD_E_ARG, "dd_render_draw: record %d has kind %d", k, q[0]);
         if (q[0] == RD_MASK) {
             DD_REQUIRE(q[1] >= RD_COORD_MIN && q[1] <= RD_COORD_MAX && q[2] >= RD_COORD_MIN && q[2] <= RD_COORD_MAX, DD_E_ARG,
                        "dd_render_draw: record %d lies at (%d, %d), outside %d .. %d", k, q[1], q[2], RD_COORD_MIN, RD_COORD_MAX);
@@ -245,10 +266,11 @@ int dd_render_draw(dd_render *r, const uint8_t *frames_dev, int n_frames, const 
             for (int c = 1; c <= 4; ++c)
                 DD_REQUIRE(q[c] >= RD_COORD_MIN && q[c] <= RD_COORD_MAX, DD_E_ARG, "dd_render_draw: record %d has coordinate %d, outside %d .. %d", k, q[c],
                            RD_COORD_MIN, RD_COORD_MAX);
-            if (q[0] == RD_RECT)
+            if (q[0] == RD_RECT || q[0] == RD_FILL)
                 DD_REQUIRE(q[3] >= q[1] && q[4] >= q[2], DD_E_ARG, "dd_render_draw: record %d is a rectangle with x1 < x0 or y1 < y0 (%d, %d, %d, %d)", k, q[1], q[2], q[3], q[4]);
             if (q[0] == RD_LINE)
-                DD_REQUIRE(q[5] >= 1 && q[5] <= RD_MAX_WIDTH && (q[5] & 1), DD_E_ARG, "dd_render_draw: record %d has line width %d (odd, 1 .. %d)", k, q[5], RD_MAX_WIDTH);
+                DD_REQUIRE(q[5] >= 1 && q[5] <= RD_MAX_WIDTH && (wide || (q[5] & 1)), DD_E_ARG, "dd_render_draw: record %d has line width %d (%s1 .. %d)", k, q[5],
+                           wide ? "" : "odd, ", RD_MAX_WIDTH);
         }
     }
     DD_DEVICE(r->ctx);

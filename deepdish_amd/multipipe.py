@@ -43,8 +43,11 @@ class MultiStreamPipeline:
                  nms_max_overlap=0.6, max_iou_distance=0.7, max_age=60, n_init=3, context=None, run_detector=True,
                  encoder_max_batch=None, track_capacity=512, gallery_capacity=256, background_subtraction_ratio=None,
                  background_masking=False, graph=None, object_detector_skip_frames=None, metric='cosine',
-                 association='host', detector_letterbox=False):
+                 association='host', detector_letterbox=False, ground=None, topdownview_size_m=None):
         from .tools.yolov5 import letterbox_pad
+        from .ground import for_pipeline
+        # the reference's --3d mode (deepdish.py:592-611): a GroundPlane, or a list with one per stream; None: no top-down view
+        self.ground, self.topdown_scale = for_pipeline(ground, topdownview_size_m, input_size, int(n_streams))      # ValueError before anything is built
         self.detector_letterbox = letterbox_pad(detector_letterbox)      # None, or the pad value of the YOLOv5 detector's letterboxed input
         if self.detector_letterbox is not None and 'yolov5' not in model:      # before anything is built
             raise ValueError('%s: detector_letterbox is the YOLOv5 detector\'s option; the other detectors are trained on stretched input' % model)
@@ -263,7 +266,8 @@ class MultiStreamPipeline:
         """The reference's annotated output frame (deepdish.py:295-408, 1187-1207) of `streams` (default: all) after the last step, painted
         over frames_dev (the frames that step received) in one launch (csrc/render.hip) -> u8 [n, H, W, 3] BGR on the device, in the order
         of `streams`.  annotation = --object-annotation: 'label', 'id' or 'none'.  font: a PIL font (default: Pillow's default face at
-        int(24 / 640 * W)).  Nothing of this runs unless it is called."""
+        int(24 / 640 * W)).  With `ground` set the frame carries the top-down panel (deepdish.py:410-440).  Nothing of this runs unless it
+        is called."""
         from . import render as rd
         rd.annotation_kind(annotation)
         assert tuple(frames_dev.shape) == (self.S, self.H, self.W, 3)
@@ -272,12 +276,34 @@ class MultiStreamPipeline:
             self._renderers = {}
         key = id(font) if font is not None else None
         if key not in self._renderers:
-            self._renderers[key] = (rd.Renderer(self.H, self.W, font=font, context=self.ctx), font)      # (the font is kept alive with its id)
+            self._renderers[key] = (rd.Renderer(self.H, self.W, font=font, context=self.ctx, records=2 if self.ground is not None else 1), font)      # (the font is kept alive with its id)
         r = self._renderers[key][0]
+        overlays = self.overlay(streams)
+        topdown = [None] * len(streams)
+        if self.ground is not None:
+            topdown = [(self.W / 4, self.H / 4, g, self.topdown_scale) for g in self._ground_of(streams, overlays)]
         prims = [rd.overlay_primitives(r, o['line'], o['track_ids'], o['track_labels'], o['track_tlbr'], o['points'], o['path_counts'], o['crossings'],
-                                       o['det_tlbr'], [(l, int(c[1]), int(c[0])) for l, c in zip(self.wanted, o['counts'])], annotation)
-                 for o in self.overlay(streams)]
+                                       o['det_tlbr'], [(l, int(c[1]), int(c[0])) for l, c in zip(self.wanted, o['counts'])], annotation, topdown=t)
+                 for o, t in zip(overlays, topdown)]
         return r.draw(frames_dev, prims, streams=streams, out=out)
+
+    def _ground_of(self, streams, overlays):
+        """The path points of every overlay, unprojected with their stream's camera in one call -> f64 [points, 2] per overlay."""
+        counts = [len(o['points']) for o in overlays]
+        pts = np.concatenate([o['points'] for o in overlays], axis=0) if overlays else np.zeros((0, 2))
+        cam = np.repeat(np.asarray(streams, dtype=np.int32), counts) if len(self.ground) > 1 else None
+        g = self.ground.space_from_image(pts, cam)
+        return np.split(g, np.cumsum(counts)[:-1]) if overlays else []
+
+    def ground_paths(self, streams=None):
+        """Where the drawn tracks of the last step are, in metres on the ground: per stream of `streams` (default: all) a dict with
+        track_ids int64 [t], path_counts int64 [t] and points f64 [sum(path_counts), 2] -- overlay()'s bottom-centre paths behind one
+        another, each through its stream's camera (GroundPlane.space_from_image; NaN at or above the horizon)."""
+        if self.ground is None:
+            raise ValueError('ground_paths: the pipeline was built without ground=')
+        streams = list(range(self.S)) if streams is None else [int(z) for z in streams]
+        overlays = self.overlay(streams)
+        return [dict(track_ids=o['track_ids'], path_counts=o['path_counts'], points=g) for o, g in zip(overlays, self._ground_of(streams, overlays))]
 
     def render_jpeg(self, frames_dev, streams=None, annotation='label', quality=95, font=None):
         """render(...) and then csrc/jpeg.hip: the annotated output frames of `streams` as JPEG files, a list of bytes in the order of

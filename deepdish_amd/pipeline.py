@@ -77,7 +77,10 @@ class HotPath:
                  context=None, run_detector=True, disable_background_subtraction=True, background_subtraction_ratio=0.25,
                  enable_background_masking=False, log=None, restore_from_log=False, mqtt_publish=None, mqtt_topic='default/topic',
                  mqtt_acp_id=None, mqtt_verbosity=1, cpu_temp=None, annotations=None, object_detector_skip_frames=None,
-                 metric='cosine', association='host', detector_letterbox=False):
+                 metric='cosine', association='host', detector_letterbox=False, ground=None, topdownview_size_m=None):
+        from .ground import for_pipeline
+        # the reference's --3d mode (deepdish.py:592-611): a GroundPlane; None: no top-down view
+        self.ground, self.topdown_scale = for_pipeline(ground, topdownview_size_m, input_size, 1)      # ValueError before anything is built
         if detector_letterbox is not False and detector_letterbox is not None and 'yolov5' not in model:      # before anything is built
             raise ValueError('%s: detector_letterbox is the YOLOv5 detector\'s option; the other detectors are trained on stretched input' % model)
         nn_matching.metric_kind(metric)              # 'cosine' or 'euclidean' (nn_matching.py:126-132), else ValueError -- before anything is built
@@ -199,7 +202,8 @@ class HotPath:
     def render(self, frame_dev, annotation='label', font=None):
         """The reference's annotated output frame (deepdish.py:295-408, 1187-1207) after the last step, painted over frame_dev (the frame
         that step received) by csrc/render.hip -> u8 [1, H, W, 3] BGR on the device; MultiStreamPipeline.render for one stream, built from
-        this class's Python tracker objects.  annotation = --object-annotation: 'label', 'id' or 'none'."""
+        this class's Python tracker objects.  annotation = --object-annotation: 'label', 'id' or 'none'.  With `ground` set the frame
+        carries the top-down panel (deepdish.py:410-440)."""
         from . import render as rd
         rd.annotation_kind(annotation)
         H, W = int(frame_dev.shape[0]), int(frame_dev.shape[1])
@@ -207,18 +211,21 @@ class HotPath:
             self._renderers = {}
         key = (H, W, id(font) if font is not None else None)
         if key not in self._renderers:
-            self._renderers[key] = (rd.Renderer(H, W, font=font, context=self.ctx), font)
+            self._renderers[key] = (rd.Renderer(H, W, font=font, context=self.ctx, records=2 if self.ground is not None else 1), font)
         r = self._renderers[key][0]
         detections, events = getattr(self, '_overlay', ([], []))
         drawn = [t for t in self.tracker.tracks if t.is_confirmed() and t.time_since_update <= 1]      # :1053
         paths = [self.counter.db.get(t.track_id, []) for t in drawn]
         points = np.array([p for path in paths for p in path], dtype=np.float64).reshape(-1, 2)
+        topdown = None
+        if self.ground is not None:                                                              # :1088-1097, every path in one call
+            topdown = (W / 4, H / 4, self.ground.space_from_image(points), self.topdown_scale)
         crossings = [tuple(self.counter.db[tid][-2]) + tuple(self.counter.db[tid][-1]) for _, _, tid in events]      # :1078 pts[-4:]
         prims = rd.overlay_primitives(r, np.asarray(self.counter.line, np.float64).reshape(4), [t.track_id for t in drawn],
                                       [t.get_label() for t in drawn], np.array([t.to_tlbr() for t in drawn], dtype=np.float64).reshape(-1, 4),
                                       points, [len(p) for p in paths], np.array(crossings, dtype=np.float64).reshape(-1, 4),
                                       np.array([d.to_tlbr() for d in detections], dtype=np.float64).reshape(-1, 4),
-                                      [(l, self.counter.negcount[l], self.counter.poscount[l]) for l in self.counter.labels], annotation)
+                                      [(l, self.counter.negcount[l], self.counter.poscount[l]) for l in self.counter.labels], annotation, topdown=topdown)
         return r.draw(frame_dev, [prims])
 
     def render_jpeg(self, frame_dev, annotation='label', quality=95):

@@ -7,6 +7,11 @@ A frame's overlay is a list of primitive records, int32 [k, 8], painted in order
     polylines(points, counts, ...)      several polylines at once, segment by segment (round caps close the joints)
     Renderer.text(x, y, string, rgb)    Pillow's ImageDraw.text at the truncated position, byte for byte, through a coverage atlas
 
+Record set 2, which a Renderer(..., records=2) accepts (the default renderer refuses it, as it always has):
+
+    fills(tlbr, rgb)                    filled rectangles, Pillow's ImageDraw.rectangle(fill=...) byte for byte (corners inclusive)
+    lines(a, b, width, rgb, even=True)  the same capsule rule for widths 1 .. 15 of either parity
+
 Each returns such an array; np.concatenate them in paint order and hand one array per output frame to Renderer.draw:
 
     r = Renderer(480, 640)
@@ -23,7 +28,7 @@ import numpy as np
 
 from ._lib import lib, check, P
 
-KIND_RECT, KIND_LINE, KIND_MASK = 0, 1, 2
+KIND_RECT, KIND_LINE, KIND_MASK, KIND_FILL = 0, 1, 2, 3
 COORD_MIN, COORD_MAX, MAX_SIDE = -8192, 8191, 8192
 EMPTY = np.zeros((0, 8), dtype=np.int32)
 
@@ -56,17 +61,25 @@ def rects(tlbr, rgb):
     return _records(KIND_RECT, c[ok], 0, rgb)
 
 
-def _width(width):
+def fills(tlbr, rgb):
+    """Filled rectangles [x0, y0, x1, y1], both corners inclusive (deepdish.py:418-420, :437-438).  Pillow refuses x1 < x0 or y1 < y0; such
+    a box is dropped here.  Record set 2."""
+    c, ok = _coords(tlbr, 4)
+    ok &= (c[:, 2] >= c[:, 0]) & (c[:, 3] >= c[:, 1])
+    return _records(KIND_FILL, c[ok], 0, rgb)
+
+
+def _width(width, even=False):
     width = int(width)
-    if width < 1 or width > 15 or width % 2 == 0:
-        raise ValueError('line width %d: odd widths 1 .. 15' % width)
+    if width < 1 or width > 15 or (width % 2 == 0 and not even):
+        raise ValueError('line width %d: %swidths 1 .. 15' % (width, '' if even else 'odd '))
     return width
 
 
-def lines(a, b, width, rgb):
-    """Segments a[i] - b[i] ([k, 2] each); a zero-length segment is a disc."""
+def lines(a, b, width, rgb, even=False):
+    """Segments a[i] - b[i] ([k, 2] each); a zero-length segment is a disc.  even=True: a width of either parity (record set 2)."""
     c, ok = _coords(np.concatenate([np.asarray(a, np.float64).reshape(-1, 2), np.asarray(b, np.float64).reshape(-1, 2)], axis=1), 4)
-    return _records(KIND_LINE, c[ok], _width(width), rgb)
+    return _records(KIND_LINE, c[ok], _width(width, even), rgb)
 
 
 def polylines(points, counts, width, rgb):
@@ -115,7 +128,7 @@ class Renderer:
     """One canvas size, one font, one coverage atlas on the device.  A string is rasterised once (font.getmask2, or getmask for a bitmap
     font, as ImageDraw.text does) and lives in the atlas from then on."""
 
-    def __init__(self, H, W, font=None, context=None):
+    def __init__(self, H, W, font=None, context=None, records=1):
         from .runtime import default_context
         self.ctx = context or default_context()
         self.H, self.W = int(H), int(W)
@@ -123,6 +136,9 @@ class Renderer:
         h = P()
         check(lib().dd_render_create(self.ctx.handle, self.H, self.W, ctypes.byref(h)), 'dd_render_create')
         self._h = h
+        self.records = int(records)           # 1: outlines, odd-width lines, masks; 2: fills and even widths too (the top-down view needs them)
+        if self.records != 1:
+            check(lib().dd_render_record_set(self._h, self.records), 'dd_render_record_set')
         self._strings = {}                 # string -> (atlas offset, w, h, off_x, off_y), or None for a string without a pixel
         self.cache_hits = self.cache_misses = 0
 
@@ -198,15 +214,40 @@ def annotation_kind(annotation):
     return a
 
 
+def topdown_primitives(view_w, view_h, ground_points, point_counts, scale):
+    """The top-down panel of one frame (deepdish.py:410-440): the black panel [0, 0, int(view_w), int(view_h)], then per track its
+    marker -- a fill from trunc(q_last - 1) to trunc(q_last + 1) -- and its path, the polyline through trunc(q) in width 2, with
+    q = g * scale * (1, -1) + (view_w / 2, view_h) for ground points g (:429; view_w, view_h untruncated there).  Nothing is clipped to
+    the panel.  A non-finite ground point drops the marker or the segments that touch it.  -> (panel [1, 8], elements [k, 8])."""
+    g = np.asarray(ground_points, dtype=np.float64).reshape(-1, 2)
+    counts = np.asarray(point_counts, dtype=np.int64).reshape(-1)
+    assert counts.sum() == len(g)
+    q = g * np.asarray(scale, dtype=np.float64) * np.array([1.0, -1.0]) + np.array([view_w * 0.5, view_h * 1.0])
+    green = (0, 255, 0)
+    parts, at = [], 0
+    for n in counts:                                                  # per track: the marker lies under the track's own path
+        t = q[at:at + n]
+        at += n
+        if n:
+            parts.append(fills(np.concatenate([t[-1] - 1.0, t[-1] + 1.0]), green))
+            parts.append(lines(t[:-1], t[1:], 2, green, even=True))
+    panel = fills([0, 0, int(view_w), int(view_h)], (0, 0, 0))
+    return panel, (np.concatenate(parts, axis=0) if parts else EMPTY)
+
+
 def overlay_primitives(renderer, line, track_ids, track_labels, track_tlbr, points, point_counts, crossings, det_tlbr, counters,
-                       annotation='label'):
+                       annotation='label', topdown=None):
     """One frame's overlay in the reference's paint order (a stable sort by priority, deepdish.py:1194):
         2  count line, width 3, RGB (0, 0, 255)                                     :354-359, :972
         3  the whole path of every drawn track with >= 2 points, width 3, (255, 0, 255)      :340-345, :1066-1069
         4  this step's crossing segments, width 5, (0, 0, 255)                      :347-352, :1122
         5  the detections given to the tracker, outline (255, 0, 0)                 :295-305, :1125-1127
         6  per track: outline (255, 255, 255), then its text at the top-left, (0, 255, 0)    :307-326, :1086
+        9  with topdown: the black panel in the top-left corner                     :410-420
+        10 with topdown: per track its marker, then its ground path in width 2, (0, 255, 0)  :422-440, :1088-1097
         10 counters, from the bottom edge up, labels reversed                       :378-408
+    topdown = (view_w, view_h, ground_points, scale): the panel's size (W / 4, H / 4 upstream, not truncated), `points` unprojected to
+    the ground (GroundPlane.space_from_image) and the metres -> pixels factors; see topdown_primitives.
     track_*: the confirmed tracks with time_since_update <= 1, in track order; points / point_counts: their paths behind one another;
     counters: (label, negcount, poscount) in the order of the wanted labels."""
     annotation = annotation_kind(annotation)
@@ -220,6 +261,9 @@ def overlay_primitives(renderer, line, track_ids, track_labels, track_tlbr, poin
         txt = str(track_ids[k]) if annotation == 'id' else (track_labels[k] or '') if annotation == 'label' else ''
         parts.append(rects(track_tlbr[k], (255, 255, 255)))
         parts.append(renderer.text(track_tlbr[k, 0], track_tlbr[k, 1], txt, (0, 255, 0)))
+    if topdown is not None:
+        view_w, view_h, ground_points, scale = topdown
+        parts.extend(topdown_primitives(view_w, view_h, ground_points, point_counts, scale))
     cursor = H
     for label, neg, pos in reversed(list(counters)):
         cursor -= text_size(font, str(neg))[1]

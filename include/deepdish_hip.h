@@ -640,11 +640,17 @@ int dd_pipeline_overlay(dd_pipeline *p, const int *streams_host, int n, int *siz
  *   {0, x0, y0, x1, y1, 0, ink, 0}        rectangle outline, Pillow's ImageDraw.rectangle byte for byte (x1 >= x0, y1 >= y0)
  *   {1, ax, ay, bx, by, width, ink, 0}    line segment: the pixels within width / 2 of it (a capsule; exact integers; width odd, 1 .. 15)
  *   {2, x, y, w, h, offset, ink, 0}       mask blit: u8 coverage [h][w] at `offset` of the atlas, blended as Pillow's draw_bitmap does
+ *   {3, x0, y0, x1, y1, 0, ink, 0}        filled rectangle, Pillow's ImageDraw.rectangle(fill=...) byte for byte: x0 .. x1, y0 .. y1 inclusive (x1 >= x0, y1 >= y0)
+ * Kind 3 and lines of EVEN width (the same capsule rule) belong to record set 2: a renderer refuses them until dd_render_record_set(r, 2).
  * ink = B | G << 8 | R << 16; coordinates lie in -8192 .. 8191 and a canvas is at most 8192 either way (DD_E_ARG otherwise).  Records
  * are painted in the order given: a later one overwrites an earlier one. */
 typedef struct dd_render dd_render;
 int dd_render_create(dd_ctx *ctx, int frame_h, int frame_w, dd_render **out);
 int dd_render_destroy(dd_render *r);
+/* The records dd_render_draw accepts from now on: DD_RENDER_RECORDS_1 (how a renderer starts) or DD_RENDER_RECORDS_2. */
+#define DD_RENDER_RECORDS_1 1
+#define DD_RENDER_RECORDS_2 2
+int dd_render_record_set(dd_render *r, int record_set);
 /* Appends a coverage mask (host u8 [h][w]) to the atlas; offset_out is what a mask record names.  Complete on return. */
 int dd_render_put_mask(dd_render *r, const uint8_t *mask_host, int w, int h, int *offset_out);
 /* frames_dev: u8 [n_frames][H][W][3].  Output frame i of n is frame streams_host[i] under records prim_off_host[i] ..
@@ -653,6 +659,22 @@ int dd_render_put_mask(dd_render *r, const uint8_t *mask_host, int w, int h, int
  * `stream` (NULL: the context's); draws of one renderer go to one stream at a time. */
 int dd_render_draw(dd_render *r, const uint8_t *frames_dev, int n_frames, const int *streams_host, int n, const int32_t *prims_host,
                    const int *prim_off_host, uint8_t *out_dev, void *stream);
+
+/* ---------------------------------------------------------------- ground plane (csrc/ground.hip, csrc/ground_dev.h)
+ * The reference's --3d mode (deepdish.py:592-611, :1088-1097): a rectilinear camera at (0, 0, elevation), heading 0, tilt 0 = looking
+ * straight down, 90 degrees = at the horizon towards +Y; image pixels go to metres on the plane Z = 0.  A pixel whose ray does not reach
+ * the ground (at or above the horizon), or a non-finite one, yields (NaN, NaN).
+ * A camera is DD_GROUND_CAMERA_DOUBLES doubles: fx, fy, cx, cy, elevation, cos tilt, sin tilt, cos roll, sin roll. */
+#define DD_GROUND_CAMERA_DOUBLES 9
+/* Host only.  DD_E_ARG for a non-finite value and for a non-positive focal length, sensor side, image side or elevation. */
+int dd_ground_camera(double f_mm, double sensor_w_mm, double sensor_h_mm, int image_w, int image_h, double elevation_m, double tilt_deg,
+                     double roll_deg, double *out);
+/* cams: f64 [n_cams][9]; cam_index: int32 [n], or NULL for camera 0; points, out: f64 [n][2], sharing no byte.  on_device = 0: host
+ * arrays, computed in the call (ctx may be NULL); an index outside 0 .. n_cams - 1 is DD_E_ARG and nothing is written.  on_device = 1:
+ * all arrays on the device (points and out 16-byte aligned), one launch queued on `stream` (NULL: the context's); a point with an index
+ * outside the table yields NaN and reads no camera.  Host and device results agree bit for bit.  n == 0 is a no-op. */
+int dd_ground_from_image(dd_ctx *ctx, const double *cams, int n_cams, const int32_t *cam_index, const double *points, long long n, double *out,
+                         int on_device, void *stream);
 
 /* ---------------------------------------------------------------- JPEG encoder (csrc/jpeg.hip)
  * The exit of the render path: BGR frames in HBM -> whole baseline JFIF files in HBM, with no raw download and no CPU encode.  It serves
