@@ -21,6 +21,8 @@
 // bytes): put() copies a stream's file into the slot's pinned arena and parses its header on the calling thread, submit() uploads the
 // bytes in use and the records and decodes on the copy stream (csrc/jpeg_dec.hip) -- into the slot's output, or into a staging buffer
 // in front of crop_resize when a flip or a resize is asked.  Each stream carries a status; a bad file costs its neighbours nothing.
+// Such a ring may decode at 1/2, 1/4 or 1/8 scale (dd_ingest_create_jpeg_scaled): src_h x src_w stays what every file must state, the
+// decoder writes ceil(src_h / scale) x ceil(src_w / scale) frames, and it is that size the staging buffer has and crop_resize starts from.
 #include <cstddef>
 #include <cstdlib>
 #include <mutex>
@@ -31,6 +33,7 @@ struct dd_ingest {
     dd_ctx *ctx = nullptr;
     int slots = 0, S = 0, sh = 0, sw = 0, dh = 0, dw = 0, flip = 0;
     int format = 0;                         // 0 BGR, 1 NV12, 2 I420, 3 JPEG files, 4 YUY2, 5 UYVY
+    int jh = 0, jw = 0;                     // the frames in front of the flip + resize: sh x sw, or a JPEG ring's scaled decode
     bool transform = false, own_out = false, fused = true;
     uint8_t *d_stage = nullptr;             // YUV, two-launch form only: the converted BGR frames [S][sh][sw][3]
     hipStream_t copy = nullptr;
@@ -53,7 +56,7 @@ constexpr int INGEST_JPEG = 3, INGEST_YUY2 = 4, INGEST_UYVY = 5;
 static bool ingest_is_422(int format) { return format == INGEST_YUY2 || format == INGEST_UYVY; }
 
 static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip,
-                         int pixel_format, dd_ingest **out, size_t jpeg_slot_bytes = 0) {
+                         int pixel_format, dd_ingest **out, size_t jpeg_slot_bytes = 0, int jpeg_scale = 1) {
     DD_REQUIRE(ctx && out && slots > 0 && n_streams > 0 && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0, DD_E_ARG,
                "%s: bad argument", who);
     DD_REQUIRE((pixel_format >= 0 && pixel_format <= 2) || ingest_is_422(pixel_format) || (pixel_format == INGEST_JPEG && jpeg_slot_bytes), DD_E_ARG,
@@ -67,11 +70,13 @@ static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams,
         DD_REQUIRE(src_w % 2 == 0, DD_E_ARG, "%s: src_w %d must be even for 4:2:2 frames", who, src_w);
         DD_REQUIRE(n_streams <= 65535, DD_E_ARG, "%s: n_streams %d above 65535", who, n_streams);
     }
+    DD_REQUIRE(jpeg_scale == 1 || jpeg_scale == 2 || jpeg_scale == 4 || jpeg_scale == 8, DD_E_ARG, "%s: scale %d is none of 1, 2, 4, 8", who, jpeg_scale);
     DD_HIP(hipSetDevice(ctx->device));
     dd_ingest *g = new dd_ingest();
     g->ctx = ctx; g->slots = slots; g->S = n_streams; g->sh = src_h; g->sw = src_w; g->dh = dst_h; g->dw = dst_w;
     g->flip = flip != 0;
-    g->transform = g->flip || src_h != dst_h || src_w != dst_w;
+    g->jh = (src_h + jpeg_scale - 1) / jpeg_scale, g->jw = (src_w + jpeg_scale - 1) / jpeg_scale;
+    g->transform = g->flip || g->jh != dst_h || g->jw != dst_w;
     g->format = pixel_format;
     g->raw_bytes = pixel_format ? (size_t)n_streams * src_h * src_w * 3 / 2 : (size_t)n_streams * src_h * src_w * 3;
     if (pixel_format == INGEST_JPEG) g->raw_bytes = jpeg_slot_bytes;
@@ -94,18 +99,18 @@ static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams,
         g->ready.push_back(r); g->done.push_back(dn); g->used.push_back(0); g->submitted.push_back(0);
     }
     if (g->format && g->transform && !g->fused)
-        DD_HIP(hipMalloc(reinterpret_cast<void **>(&g->d_stage), (size_t)n_streams * src_h * src_w * 3 + 64));
+        DD_HIP(hipMalloc(reinterpret_cast<void **>(&g->d_stage), (size_t)n_streams * g->jh * g->jw * 3 + 64));
     if (g->transform && !(g->format && g->fused)) {
         std::vector<int> boxes((size_t)n_streams * 8, 0);
         for (int z = 0; z < n_streams; ++z) {
             int *b = boxes.data() + (size_t)z * 8;
-            b[0] = 0; b[1] = 0; b[2] = src_w; b[3] = src_h; b[4] = z; b[5] = g->flip;
+            b[0] = 0; b[1] = 0; b[2] = g->jw; b[3] = g->jh; b[4] = z; b[5] = g->flip;
         }
         DD_HIP(hipMalloc(&g->d_boxes, boxes.size() * sizeof(int)));
         DD_HIP(hipMemcpy(g->d_boxes, boxes.data(), boxes.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     if (pixel_format == INGEST_JPEG) {
-        if (int rc = dd_jpegdec_create(ctx, src_h, src_w, n_streams, (int64_t)jpeg_slot_bytes, &g->dec)) return rc;
+        if (int rc = dd_jpegdec_create_scaled(ctx, src_h, src_w, jpeg_scale, n_streams, (int64_t)jpeg_slot_bytes, &g->dec)) return rc;
         for (int i = 0; i < slots; ++i) {
             dd_jpeg_info *r = nullptr;
             int *hs = nullptr, *ds = nullptr;
@@ -139,6 +144,12 @@ int dd_ingest_create_jpeg(dd_ctx *ctx, int slots, int n_streams, int src_h, int 
                           dd_ingest **out) {
     DD_REQUIRE(slot_bytes >= 1, DD_E_ARG, "dd_ingest_create_jpeg: slot_bytes %lld", (long long)slot_bytes);
     return ingest_create("dd_ingest_create_jpeg", ctx, slots, n_streams, src_h, src_w, dst_h, dst_w, flip, INGEST_JPEG, out, (size_t)slot_bytes);
+}
+
+int dd_ingest_create_jpeg_scaled(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip, int scale, int64_t slot_bytes,
+                                 dd_ingest **out) {
+    DD_REQUIRE(slot_bytes >= 1, DD_E_ARG, "dd_ingest_create_jpeg_scaled: slot_bytes %lld", (long long)slot_bytes);
+    return ingest_create("dd_ingest_create_jpeg_scaled", ctx, slots, n_streams, src_h, src_w, dst_h, dst_w, flip, INGEST_JPEG, out, (size_t)slot_bytes, scale);
 }
 
 int dd_ingest_jpeg_put(dd_ingest *g, int slot, int stream, const uint8_t *data_host, int64_t n) {
@@ -231,7 +242,7 @@ int dd_ingest_submit(dd_ingest *g, int slot) {
         if (g->used[slot]) DD_HIP(hipStreamWaitEvent(g->copy, g->done[slot], 0));
         uint8_t *dst = g->transform ? g->d_stage : g->d_out[slot];
         int rc = ddk::jpegdec_launch(g->dec, g->h_recs[slot], g->h_raw[slot], g->fill[slot], g->S, dst, g->d_status[slot], g->copy, nullptr);
-        if (rc == DD_OK && g->transform) rc = ddk::crop_resize(g->copy, g->d_stage, g->sh, g->sw, g->d_boxes, g->S, g->dh, g->dw, g->d_out[slot]);
+        if (rc == DD_OK && g->transform) rc = ddk::crop_resize(g->copy, g->d_stage, g->jh, g->jw, g->d_boxes, g->S, g->dh, g->dw, g->d_out[slot]);
         if (rc != DD_OK) return rc;
         DD_HIP(hipMemcpyAsync(g->h_status[slot], g->d_status[slot], (size_t)g->S * sizeof(int), hipMemcpyDeviceToHost, g->copy));
         DD_HIP(hipEventRecord(g->ready[slot], g->copy));

@@ -13,6 +13,11 @@
 // A band too wide for LDS (DD_JPEGDEC_PLANES) takes its planes through HBM: jpeg_planes_k transforms, jpeg_pixels_k reads them back.
 // Files of one call may differ in tables, sampling and restart interval; a file that is refused or damaged sets its own status and
 // writes nothing outside its own frame.
+//
+// A decoder made with a scale denominator of 2, 4 or 8 (libjpeg's scale_denom, Pillow's Image.draft; tests/jpeg_scaled_ref.py) runs the
+// same markers and entropy kernels and then jpeg_pixels_scaled_k<S> (jpeg_planes_scaled_k<S>) in place of the last: every block goes
+// straight to 4x4, 2x2 or 1x1 samples (csrc/jpeg_dec_dev.h), the band's planes shrink with it, 4:2:0 chroma is not up-sampled at all, and
+// the frame written is ceil(H / S) x ceil(W / S).  The coefficient buffer keeps its full-size layout.
 #include "common.h"
 #include "jpeg_dec_dev.h"
 #include <cstdlib>
@@ -42,6 +47,21 @@ __host__ __device__ inline JdBand jd_band(int W, int ncomp, int hs, int vs) {
     b.yrows = 8 * vs;
     b.halo = ncomp == 3 && vs == 2 ? 1 : 0;
     b.crows = ncomp == 3 ? 8 + 2 * b.halo : 0;
+    b.lds = (size_t)b.yrows * b.Wy + 2 * (size_t)b.crows * b.Wc;
+    return b;
+}
+
+// The same at scale 1 / s.  At s >= 2 a band is still one MCU row, 8 * vs / s output rows; every component's rows coincide with the
+// luma's (4:2:0 chroma keeps blocks of twice the luma's side, csrc/jpeg_dec_dev.h jpd_plane), so there is no halo.
+__host__ __device__ inline JdBand jd_band(int W, int ncomp, int hs, int vs, int s) {
+    if (s == 1) return jd_band(W, ncomp, hs, vs);
+    JdBand b;
+    const int mx = (W + 8 * hs - 1) / (8 * hs);
+    const int ny = 8 / s, nc = jpd_plane(1, 1, 1, 1, hs, vs, s).n;
+    b.Wy = mx * hs * ny, b.Wc = mx * nc;
+    b.yrows = vs * ny;
+    b.halo = 0;
+    b.crows = ncomp == 3 ? nc : 0;
     b.lds = (size_t)b.yrows * b.Wy + 2 * (size_t)b.crows * b.Wc;
     return b;
 }
@@ -297,6 +317,164 @@ __global__ __launch_bounds__(JD_T) void jpeg_pixels_k(const dd_jpeg_info *__rest
     }
 }
 
+// ---- 1/2, 1/4 and 1/8 scale: the two kernels above specialised on the scale denominator S.  The full-size kernels stay as they are.
+
+// Block `blk` of a frame to N x N samples at dst, rows `stride` bytes apart.  N = 8 is the full transform (4:2:0 chroma at S = 2).  dst is
+// aligned to N bytes: every plane starts at a multiple of its block side and is a whole number of blocks wide.
+template <int N>
+__device__ __forceinline__ void jd_block_scaled(const int16_t *__restrict__ coef, size_t blk, const uint16_t *__restrict__ q, uint8_t *dst, int stride) {
+    if constexpr (N == 8) {
+        jd_block(coef, blk, q, dst, stride, -1);
+    } else if constexpr (N == 1) {
+        *dst = (uint8_t)jpd_idct1((int32_t)coef[blk * 64] * (int32_t)q[0]);
+    } else {
+        int32_t d[64];
+        const uint4 *c4 = reinterpret_cast<const uint4 *>(coef + blk * 64);
+        const uint4 *q4 = reinterpret_cast<const uint4 *>(q);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            if (N == 4 ? i == 4 : (i != 0 && !(i & 1))) continue;          // rows the transform does not read
+            const uint4 c = c4[i], v = q4[i];
+            const uint32_t cw[4] = {c.x, c.y, c.z, c.w}, qw[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                d[8 * i + 2 * j] = (int32_t)(int16_t)(cw[j] & 0xffffu) * (int32_t)(qw[j] & 0xffffu);
+                d[8 * i + 2 * j + 1] = (int32_t)(int16_t)(cw[j] >> 16) * (int32_t)(qw[j] >> 16);
+            }
+        }
+        int o[N * N];
+        if constexpr (N == 4) {
+            jpd_idct4(d, o);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                *reinterpret_cast<uint32_t *>(dst + (size_t)r * stride) = (uint32_t)o[4 * r] | ((uint32_t)o[4 * r + 1] << 8) | ((uint32_t)o[4 * r + 2] << 16) | ((uint32_t)o[4 * r + 3] << 24);
+        } else {
+            jpd_idct2(d, o);
+#pragma unroll
+            for (int r = 0; r < 2; ++r) *reinterpret_cast<uint16_t *>(dst + (size_t)r * stride) = (uint16_t)(o[2 * r] | (o[2 * r + 1] << 8));
+        }
+    }
+}
+
+// The blocks of MCU row `band` into planes Y [b.yrows][Wy], Cb and Cr [b.crows][Wc], whose row 0 is the band's first.
+template <int S>
+__device__ __forceinline__ void jd_transform_band_scaled(const dd_jpeg_info &r, const int16_t *__restrict__ coef, int band, const JdBand &b, uint8_t *Y, uint8_t *Cb,
+                                                         uint8_t *Cr) {
+    constexpr int NY = 8 / S;
+    const int mx = r.mcus_x, bpm = r.blocks_per_mcu, ny = bpm == 1 ? 1 : bpm - 2, hs = r.hmax;
+    for (int t = threadIdx.x; t < mx * bpm; t += JD_T) {
+        const int m = t / bpm, k = t - m * bpm;
+        const size_t blk = ((size_t)band * mx + m) * bpm + k;
+        if (k < ny) {
+            jd_block_scaled<NY>(coef, blk, r.quant[r.tq[0]], Y + (size_t)(k / hs) * NY * b.Wy + (size_t)(m * hs + k % hs) * NY, b.Wy);
+        } else {
+            const int c = k - ny + 1;
+            uint8_t *dst = (c == 1 ? Cb : Cr) + (size_t)m * b.crows;
+            if (b.crows == NY) jd_block_scaled<NY>(coef, blk, r.quant[r.tq[c]], dst, b.Wc);
+            else jd_block_scaled<2 * NY>(coef, blk, r.quant[r.tq[c]], dst, b.Wc);           // 4:2:0
+        }
+    }
+}
+
+// Pixel x of plane row `row` (the components' rows coincide).  Only 4:2:2 chroma is up-sampled: jdsample.c's h2v1 fancy filter over the
+// plane's true width cw, plain replication at cw <= 2 and at S = 8, where libjpeg turns the filter off.  Packed B | G << 8 | R << 16.
+template <int S>
+__device__ __forceinline__ uint32_t jd_pixel_scaled(const dd_jpeg_info &r, const JdBand &b, const uint8_t *Y, const uint8_t *Cb, const uint8_t *Cr, int row, int x, int cw) {
+    const int yy = Y[(size_t)row * b.Wy + x];
+    if (r.ncomp == 1) return (uint32_t)yy * 0x010101u;
+    const size_t o = (size_t)row * b.Wc;
+    int cb, cr;
+    if (b.Wc == b.Wy) {
+        cb = Cb[o + x], cr = Cr[o + x];
+    } else {
+        const int cx = x >> 1;
+        if (S == 8 || cw <= 2) {
+            cb = Cb[o + cx], cr = Cr[o + cx];
+        } else {
+            const int nx = (x & 1) ? min(cx + 1, cw - 1) : max(cx - 1, 0), bias = (x & 1) ? 2 : 1;
+            cb = (3 * Cb[o + cx] + Cb[o + nx] + bias) >> 2;
+            cr = (3 * Cr[o + cx] + Cr[o + nx] + bias) >> 2;
+        }
+    }
+    return jpd_bgr(yy, cb, cr);
+}
+
+// Rows [y_first, y_first + rows) of the oh x ow frame `out` from planes whose row `row0` is output row y_first.
+template <int S>
+__device__ __forceinline__ void jd_paint_scaled(const dd_jpeg_info &r, const JdBand &b, const uint8_t *Y, const uint8_t *Cb, const uint8_t *Cr, int row0, int y_first, int rows,
+                                                int ow, uint8_t *__restrict__ out, bool vec) {
+    const int cw = r.ncomp == 3 ? jpd_plane(r.height, r.width, 1, 1, r.hmax, r.vmax, S).cols : 0;
+    if (vec) {
+        const int qw = ow >> 2;
+        for (int i = threadIdx.x; i < rows * qw; i += JD_T) {
+            const int row = i / qw, x = (i - row * qw) * 4;
+            uint32_t p[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) p[j] = jd_pixel_scaled<S>(r, b, Y, Cb, Cr, row0 + row, x + j, cw);
+            uint32_t *o = reinterpret_cast<uint32_t *>(out + ((size_t)(y_first + row) * ow + x) * 3);
+            o[0] = p[0] | (p[1] << 24);
+            o[1] = (p[1] >> 8) | (p[2] << 16);
+            o[2] = (p[2] >> 16) | (p[3] << 8);
+        }
+    } else {
+        for (int i = threadIdx.x; i < rows * ow; i += JD_T) {
+            const int row = i / ow, x = i - row * ow;
+            const uint32_t p = jd_pixel_scaled<S>(r, b, Y, Cb, Cr, row0 + row, x, cw);
+            uint8_t *o = out + ((size_t)(y_first + row) * ow + x) * 3;
+            o[0] = (uint8_t)p, o[1] = (uint8_t)(p >> 8), o[2] = (uint8_t)(p >> 16);
+        }
+    }
+}
+
+template <int S>
+__global__ __launch_bounds__(JD_T) void jpeg_planes_scaled_k(const dd_jpeg_info *__restrict__ recs, JdGeom g, const int *__restrict__ mark, const int16_t *__restrict__ coef,
+                                                             uint8_t *__restrict__ planes) {
+    const int f = blockIdx.x / g.max_bands, band = blockIdx.x - f * g.max_bands;
+    const dd_jpeg_info &r = recs[f];
+    if (mark[f] != DD_JPEG_ST_OK || r.path != DD_JPEGDEC_PLANES || band >= r.mcus_y) return;
+    const JdBand b = jd_band(r.width, r.ncomp, r.hmax, r.vmax, S);
+    uint8_t *Y = planes + (size_t)f * g.plane_stride, *Cb = Y + (size_t)r.mcus_y * b.yrows * b.Wy, *Cr = Cb + (size_t)r.mcus_y * b.crows * b.Wc;
+    jd_transform_band_scaled<S>(r, coef + (size_t)f * g.coef_stride, band, b, Y + (size_t)band * b.yrows * b.Wy, Cb + (size_t)band * b.crows * b.Wc,
+                                Cr + (size_t)band * b.crows * b.Wc);
+}
+
+// One workgroup per band of a frame; the frames are ceil(H / S) x ceil(W / S), dense.
+template <int S>
+__global__ __launch_bounds__(JD_T) void jpeg_pixels_scaled_k(const dd_jpeg_info *__restrict__ recs, JdGeom g, const int *__restrict__ mark, const int16_t *__restrict__ coef,
+                                                             const uint8_t *__restrict__ planes, uint8_t *__restrict__ out, int vec) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t jd_lds[];
+    const int f = blockIdx.x / g.max_bands, band = blockIdx.x - f * g.max_bands;
+    const dd_jpeg_info &r = recs[f];
+    if (mark[f] != DD_JPEG_ST_OK || band >= r.mcus_y) return;
+    const JdBand b = jd_band(r.width, r.ncomp, r.hmax, r.vmax, S);
+    const int oh = (g.H + S - 1) / S, ow = (g.W + S - 1) / S;
+    const int y_first = band * b.yrows, rows = min(b.yrows, oh - y_first);
+    if (rows <= 0) return;
+    uint8_t *frame = out + (size_t)f * oh * ow * 3;
+    if (r.path == DD_JPEGDEC_LDS) {
+        uint8_t *Y = jd_lds, *Cb = Y + (size_t)b.yrows * b.Wy, *Cr = Cb + (size_t)b.crows * b.Wc;
+        jd_transform_band_scaled<S>(r, coef + (size_t)f * g.coef_stride, band, b, Y, Cb, Cr);
+        __syncthreads();
+        jd_paint_scaled<S>(r, b, Y, Cb, Cr, 0, y_first, rows, ow, frame, vec != 0);
+    } else {
+        const uint8_t *Y = planes + (size_t)f * g.plane_stride, *Cb = Y + (size_t)r.mcus_y * b.yrows * b.Wy, *Cr = Cb + (size_t)r.mcus_y * b.crows * b.Wc;
+        jd_paint_scaled<S>(r, b, Y, Cb, Cr, y_first, y_first, rows, ow, frame, vec != 0);
+    }
+}
+
+template <int S>
+int jd_launch_pixels_scaled(unsigned grid, size_t lds, hipStream_t s, bool any_planes, const dd_jpeg_info *recs, const JdGeom &g, const int *mark, const int16_t *coef,
+                            uint8_t *planes, uint8_t *out_dev) {
+    if (any_planes) {
+        hipLaunchKernelGGL(jpeg_planes_scaled_k<S>, dim3(grid), dim3(JD_T), 0, s, recs, g, mark, coef, planes);
+        DD_LAUNCH_CHECK();
+    }
+    const int vec = (((g.W + S - 1) / S) & 3) == 0 && (reinterpret_cast<uintptr_t>(out_dev) & 3) == 0;
+    hipLaunchKernelGGL(jpeg_pixels_scaled_k<S>, dim3(grid), dim3(JD_T), lds, s, recs, g, mark, coef, planes, out_dev, vec);
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
 // ------------------------------------------------------------------------------------------------ host
 
 int jd_geometry(int h, int w, const char *who, JdGeom *g) {
@@ -317,6 +495,7 @@ int jd_geometry(int h, int w, const char *who, JdGeom *g) {
 struct dd_jpegdec {
     dd_ctx *ctx = nullptr;
     JdGeom g{};
+    int scale = 1, oh = 0, ow = 0;          // the scale denominator; the frames a decode writes are oh x ow
     int max_frames = 0, lanes = 0;
     size_t max_bytes = 0;
     DevBuf recs, bytes, coef, starts, mark, planes;
@@ -366,7 +545,7 @@ int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, const uint8_t *bytes_
         }
         DD_REQUIRE(r.file_offset >= 0 && (size_t)r.file_offset + (size_t)r.scan_offset + (size_t)r.scan_length <= n_bytes, DD_E_ARG,
                    "jpeg decoder: file %d lies outside the %zu bytes given", i, n_bytes);
-        const JdBand b = jd_band(r.width, r.ncomp, r.hmax, r.vmax);
+        const JdBand b = jd_band(r.width, r.ncomp, r.hmax, r.vmax, d->scale);
         r.path = b.lds <= (size_t)JD_LDS_MAX ? DD_JPEGDEC_LDS : DD_JPEGDEC_PLANES;
         if (r.path == DD_JPEGDEC_LDS) lds = b.lds > lds ? b.lds : lds;
         else any_planes = true;
@@ -403,6 +582,20 @@ int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, const uint8_t *bytes_
     DD_LAUNCH_CHECK();
     if (d->profile) DD_HIP(hipEventRecord(d->ev[3], s));
     const unsigned grid = (unsigned)n * (unsigned)g.max_bands;
+    if (d->scale != 1) {
+        int rc = DD_OK;
+        switch (d->scale) {
+            case 2: rc = jd_launch_pixels_scaled<2>(grid, lds, s, any_planes, recs, g, mark, coef, d->planes.as<uint8_t>(), out_dev); break;
+            case 4: rc = jd_launch_pixels_scaled<4>(grid, lds, s, any_planes, recs, g, mark, coef, d->planes.as<uint8_t>(), out_dev); break;
+            default: rc = jd_launch_pixels_scaled<8>(grid, lds, s, any_planes, recs, g, mark, coef, d->planes.as<uint8_t>(), out_dev); break;
+        }
+        if (rc != DD_OK) return rc;
+        if (d->profile) {
+            DD_HIP(hipEventRecord(d->ev[4], s));
+            d->profiled = true;
+        }
+        return DD_OK;
+    }
     if (any_planes) {
         hipLaunchKernelGGL(jpeg_planes_k, dim3(grid), dim3(JD_T), 0, s, recs, g, mark, coef, d->planes.as<uint8_t>());
         DD_LAUNCH_CHECK();
@@ -431,28 +624,46 @@ int dd_jpeg_parse(const uint8_t *file_host, int64_t n, dd_jpeg_info *info) {
     return DD_OK;
 }
 
-int dd_jpegdec_plan(int h, int w, int ncomp, int hs, int vs, int *path_host, int *band_rows_host, int *bands_host) {
+static int jd_plan(const char *who, int h, int w, int ncomp, int hs, int vs, int scale, int *path_host, int *band_rows_host, int *bands_host) {
     JdGeom g;
-    if (int rc = jd_geometry(h, w, "dd_jpegdec_plan", &g)) return rc;
+    if (int rc = jd_geometry(h, w, who, &g)) return rc;
+    DD_REQUIRE(jpd_scale_ok(scale), DD_E_ARG, "%s: scale %d is none of 1, 2, 4, 8", who, scale);
     DD_REQUIRE((ncomp == 1 && hs == 1 && vs == 1) || (ncomp == 3 && ((hs == 1 && vs == 1) || (hs == 2 && (vs == 1 || vs == 2)))), DD_E_ARG,
-               "dd_jpegdec_plan: %d components with luma sampling %dx%d (1 component, or 3 with 1x1, 2x1 or 2x2)", ncomp, hs, vs);
-    const JdBand b = jd_band(w, ncomp, hs, vs);
+               "%s: %d components with luma sampling %dx%d (1 component, or 3 with 1x1, 2x1 or 2x2)", who, ncomp, hs, vs);
+    const JdBand b = jd_band(w, ncomp, hs, vs, scale);
+    const int oh = (h + scale - 1) / scale;
     if (path_host) *path_host = b.lds <= (size_t)JD_LDS_MAX ? DD_JPEGDEC_LDS : DD_JPEGDEC_PLANES;
     if (band_rows_host) *band_rows_host = b.yrows;
-    if (bands_host) *bands_host = (h + b.yrows - 1) / b.yrows;
+    if (bands_host) *bands_host = (oh + b.yrows - 1) / b.yrows;
     return DD_OK;
 }
 
-int dd_jpegdec_create(dd_ctx *ctx, int h, int w, int max_frames, int64_t max_bytes, dd_jpegdec **out) {
-    DD_REQUIRE(ctx && out, DD_E_ARG, "dd_jpegdec_create: NULL argument");
+int dd_jpegdec_plan(int h, int w, int ncomp, int hs, int vs, int *path_host, int *band_rows_host, int *bands_host) {
+    return jd_plan("dd_jpegdec_plan", h, w, ncomp, hs, vs, 1, path_host, band_rows_host, bands_host);
+}
+
+int dd_jpegdec_plan_scaled(int h, int w, int ncomp, int hs, int vs, int scale, int *path_host, int *band_rows_host, int *bands_host) {
+    return jd_plan("dd_jpegdec_plan_scaled", h, w, ncomp, hs, vs, scale, path_host, band_rows_host, bands_host);
+}
+
+int dd_jpeg_draft_scale(int src_w, int src_h, int dst_w, int dst_h) {
+    DD_REQUIRE(src_w >= 1 && src_h >= 1 && dst_w >= 1 && dst_h >= 1, DD_E_ARG, "dd_jpeg_draft_scale: %d x %d for %d x %d", src_w, src_h, dst_w, dst_h);
+    const int k = src_w / dst_w < src_h / dst_h ? src_w / dst_w : src_h / dst_h;
+    return k >= 8 ? 8 : k >= 4 ? 4 : k >= 2 ? 2 : 1;
+}
+
+static int jd_create(const char *who, dd_ctx *ctx, int h, int w, int scale, int max_frames, int64_t max_bytes, dd_jpegdec **out) {
+    DD_REQUIRE(ctx && out, DD_E_ARG, "%s: NULL argument", who);
     JdGeom g;
-    if (int rc = jd_geometry(h, w, "dd_jpegdec_create", &g)) return rc;
-    DD_REQUIRE(max_frames >= 1 && (long long)max_frames * g.max_bands <= 0x7fffffffll, DD_E_ARG, "dd_jpegdec_create: max_frames %d", max_frames);
-    DD_REQUIRE(max_bytes >= 1, DD_E_ARG, "dd_jpegdec_create: max_bytes %lld", (long long)max_bytes);
+    if (int rc = jd_geometry(h, w, who, &g)) return rc;
+    DD_REQUIRE(jpd_scale_ok(scale), DD_E_ARG, "%s: scale %d is none of 1, 2, 4, 8", who, scale);
+    DD_REQUIRE(max_frames >= 1 && (long long)max_frames * g.max_bands <= 0x7fffffffll, DD_E_ARG, "%s: max_frames %d", who, max_frames);
+    DD_REQUIRE(max_bytes >= 1, DD_E_ARG, "%s: max_bytes %lld", who, (long long)max_bytes);
     DD_DEVICE(ctx);
     dd_jpegdec *d = new (std::nothrow) dd_jpegdec();
-    DD_REQUIRE(d, DD_E_HIP, "dd_jpegdec_create: out of host memory");
+    DD_REQUIRE(d, DD_E_HIP, "%s: out of host memory", who);
     d->ctx = ctx, d->g = g, d->max_frames = max_frames, d->max_bytes = (size_t)max_bytes;
+    d->scale = scale, d->oh = (h + scale - 1) / scale, d->ow = (w + scale - 1) / scale;
     const char *lanes = getenv("DD_JPEGDEC_LANES");                 // intervals per wave of jpeg_entropy_k, for A/B runs: 1 .. 64
     if (lanes && atoi(lanes) >= 1 && atoi(lanes) <= 64) d->lanes = atoi(lanes);
     int rc = d->recs.reserve((size_t)max_frames * sizeof(dd_jpeg_info));
@@ -461,7 +672,7 @@ int dd_jpegdec_create(dd_ctx *ctx, int h, int w, int max_frames, int64_t max_byt
     if (rc == DD_OK) rc = d->mark.reserve((size_t)max_frames * sizeof(int));
     if (rc == DD_OK) rc = d->recs_host.reserve((size_t)max_frames * sizeof(dd_jpeg_info));
     if (rc == DD_OK && hipEventCreateWithFlags(&d->uploaded, hipEventDisableTiming) != hipSuccess) {
-        dd_set_error("dd_jpegdec_create: hipEventCreateWithFlags failed");
+        dd_set_error("%s: hipEventCreateWithFlags failed", who);
         rc = DD_E_HIP;
     }
     if (rc != DD_OK) {
@@ -469,6 +680,20 @@ int dd_jpegdec_create(dd_ctx *ctx, int h, int w, int max_frames, int64_t max_byt
         return rc;
     }
     *out = d;
+    return DD_OK;
+}
+
+int dd_jpegdec_create(dd_ctx *ctx, int h, int w, int max_frames, int64_t max_bytes, dd_jpegdec **out) {
+    return jd_create("dd_jpegdec_create", ctx, h, w, 1, max_frames, max_bytes, out);
+}
+
+int dd_jpegdec_create_scaled(dd_ctx *ctx, int h, int w, int scale, int max_frames, int64_t max_bytes, dd_jpegdec **out) {
+    return jd_create("dd_jpegdec_create_scaled", ctx, h, w, scale, max_frames, max_bytes, out);
+}
+
+int dd_jpegdec_output_size(dd_jpegdec *d, int *out_h, int *out_w) {
+    DD_REQUIRE(d && out_h && out_w, DD_E_ARG, "dd_jpegdec_output_size: NULL argument");
+    *out_h = d->oh, *out_w = d->ow;
     return DD_OK;
 }
 

@@ -204,3 +204,88 @@ JPD_HD uint32_t jpd_bgr(int y, int cb, int cr) {
     b = b < 0 ? 0 : b > 255 ? 255 : b;
     return (uint32_t)b | ((uint32_t)g << 8) | ((uint32_t)r << 16);
 }
+
+// ---- decoding at 1/2, 1/4 and 1/8 scale (libjpeg's scale_num / scale_denom, Pillow's Image.draft; tests/jpeg_scaled_ref.py is the
+// definition).  The entropy decoder and the coefficients are the full-size ones; every 8 x 8 block is transformed straight to n x n
+// samples, n chosen per component.
+
+JPD_HD bool jpd_scale_ok(int s) { return s == 1 || s == 2 || s == 4 || s == 8; }
+
+// jdmaster.c: a component sampled hs x vs below hmax x vmax turns its blocks into n x n samples at scale 1 / s -- 8 / s, doubled while
+// that still divides what the most densely sampled component gets, so that 4:2:0 chroma needs no up-sampling at any s >= 2 -- and its
+// plane, before cropping to the output, holds rows x cols samples of an h x w file.
+struct JpdPlane {
+    int n, rows, cols;
+};
+
+JPD_HD JpdPlane jpd_plane(int h, int w, int hs, int vs, int hmax, int vmax, int s) {
+    const int m = 8 / s;
+    JpdPlane p;
+    p.n = m;
+    while (p.n < 8 && (hmax * m) % (hs * p.n * 2) == 0 && (vmax * m) % (vs * p.n * 2) == 0) p.n *= 2;
+    p.rows = (int)(((long long)h * vs * p.n + vmax * 8 - 1) / (vmax * 8));
+    p.cols = (int)(((long long)w * hs * p.n + hmax * 8 - 1) / (hmax * 8));
+    return p;
+}
+
+// jidctred.c (CONST_BITS 13, PASS1_BITS 2).  The column pass is exact in 64 bits for every int16 coefficient times an 8-bit quantiser, so
+// what it hands to the row pass fits 32 bits; the row pass wraps like jpd_idct8, which the range limit's & 1023 does not see.
+
+// jpeg_idct_4x4: terms 0, 1, 2, 3, 5, 6, 7 of rows and columns; term 4 is not read.  Descaled by 12, then by 19.
+JPD_HD void jpd_idct4(const int32_t (&d)[64], int (&o)[16]) {
+    typedef int64_t L;
+    typedef uint32_t U;
+    int32_t ws[4][8];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int c = 0; c < 8; ++c) {
+        if (c == 4) continue;
+        const L t0 = (L)d[c] * 16384, t2 = (L)d[16 + c] * 15137 - (L)d[48 + c] * 6270;
+        const L z1 = d[56 + c], z2 = d[40 + c], z3 = d[24 + c], z4 = d[8 + c];
+        const L o0 = z2 * 11893 + z4 * 8697 - z1 * 1730 - z3 * 17799;
+        const L o2 = z3 * 7373 + z4 * 20995 - z1 * 4176 - z2 * 4926;
+        ws[0][c] = (int32_t)((t0 + t2 + o2 + 2048) >> 12), ws[3][c] = (int32_t)((t0 + t2 - o2 + 2048) >> 12);
+        ws[1][c] = (int32_t)((t0 - t2 + o0 + 2048) >> 12), ws[2][c] = (int32_t)((t0 - t2 - o0 + 2048) >> 12);
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int r = 0; r < 4; ++r) {
+        const U t0 = (U)ws[r][0] << 14, t2 = (U)ws[r][2] * 15137u - (U)ws[r][6] * 6270u;
+        const U z1 = (U)ws[r][7], z2 = (U)ws[r][5], z3 = (U)ws[r][3], z4 = (U)ws[r][1];
+        const U o0 = z2 * 11893u + z4 * 8697u - z1 * 1730u - z3 * 17799u;
+        const U o2 = z3 * 7373u + z4 * 20995u - z1 * 4176u - z2 * 4926u;
+        const U k = 1u << 18;
+        o[4 * r] = jpd_range_limit(jpd_sar(t0 + t2 + o2 + k, 19)), o[4 * r + 3] = jpd_range_limit(jpd_sar(t0 + t2 - o2 + k, 19));
+        o[4 * r + 1] = jpd_range_limit(jpd_sar(t0 - t2 + o0 + k, 19)), o[4 * r + 2] = jpd_range_limit(jpd_sar(t0 - t2 - o0 + k, 19));
+    }
+}
+
+// jpeg_idct_2x2: terms 0, 1, 3, 5, 7.  Descaled by 13, then by 20.
+JPD_HD void jpd_idct2(const int32_t (&d)[64], int (&o)[4]) {
+    typedef int64_t L;
+    typedef uint32_t U;
+    int32_t ws[2][8];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int c = 0; c < 8; ++c) {
+        if (c != 0 && !(c & 1)) continue;
+        const L t10 = (L)d[c] * 32768;
+        const L t0 = (L)d[40 + c] * 6967 + (L)d[8 + c] * 29692 - (L)d[56 + c] * 5906 - (L)d[24 + c] * 10426;
+        ws[0][c] = (int32_t)((t10 + t0 + 4096) >> 13), ws[1][c] = (int32_t)((t10 - t0 + 4096) >> 13);
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int r = 0; r < 2; ++r) {
+        const U t10 = (U)ws[r][0] << 15;
+        const U t0 = (U)ws[r][5] * 6967u + (U)ws[r][1] * 29692u - (U)ws[r][7] * 5906u - (U)ws[r][3] * 10426u;
+        const U k = 1u << 19;
+        o[2 * r] = jpd_range_limit(jpd_sar(t10 + t0 + k, 20)), o[2 * r + 1] = jpd_range_limit(jpd_sar(t10 - t0 + k, 20));
+    }
+}
+
+// jpeg_idct_1x1: the dequantised DC term, descaled by 3.
+JPD_HD int jpd_idct1(int32_t dc) { return jpd_range_limit(jpd_sar((uint32_t)dc + 4u, 3)); }

@@ -17,7 +17,9 @@ frames already in device memory.
 With `pixel_format='jpeg'` a slot holds baseline JPEG files, what an IP camera's MJPEG stream or the reference's frame_%06d.jpg sequence
 (--input-cvat-dir) delivers -- a tenth or less of the raw bytes: `put(slot, stream, file)` copies a file into the slot's pinned arena and
 parses its header on the calling thread, `submit(slot)` uploads the bytes in use and decodes on the copy stream (csrc/jpeg_dec.hip,
-libjpeg's arithmetic restated), and `status(slot)` tells per stream whether its frame is good (deepdish_amd.jpeg.ST_*)."""
+libjpeg's arithmetic restated), and `status(slot)` tells per stream whether its frame is good (deepdish_amd.jpeg.ST_*).  `jpeg_scale=2`, 4, 8
+or 'auto' decodes at that fraction (libjpeg's scale_denom, deepdish_amd.jpeg.JpegDecoder(scale=...)) in front of the resize: megapixel
+cameras feeding a 640 x 480 pipeline never have their full-size frames written."""
 import ctypes
 import numpy as np
 
@@ -29,10 +31,13 @@ PACKED_422 = ('yuy2', 'uyvy')
 
 
 class FrameIngest:
-    def __init__(self, n_streams, src_size, dst_size=None, slots=2, flip=False, context=None, pixel_format='bgr', jpeg_slot_bytes=None):
+    def __init__(self, n_streams, src_size, dst_size=None, slots=2, flip=False, context=None, pixel_format='bgr', jpeg_slot_bytes=None, jpeg_scale=1):
         """src_size / dst_size: (width, height) like the reference's `input_size`; dst defaults to src.
         pixel_format: what a slot holds, 'bgr' | 'nv12' | 'i420' (4:2:0 needs an even width and height) | 'yuy2' | 'uyvy' (packed 4:2:2,
-        named by FOURCC: an even width, any height) | 'jpeg'; the consumer always gets BGR.  jpeg_slot_bytes: the size of a JPEG slot's arena, by default n_streams * width * height * 3 // 8."""
+        named by FOURCC: an even width, any height) | 'jpeg'; the consumer always gets BGR.  jpeg_slot_bytes: the size of a JPEG slot's arena, by default n_streams * width * height * 3 // 8.
+        jpeg_scale ('jpeg' only; anything but 1 with another format is a ValueError): 1, 2, 4, 8 or 'auto' = deepdish_amd.jpeg.draft_scale(src_size,
+        dst_size), Pillow's draft rule.  src_size stays what every file must state; the ring decodes ceil(height / scale) x ceil(width / scale)
+        frames and resizes from there -- or decodes straight into the slot when that is dst_size and no flip is asked."""
         self._h = None
         if pixel_format not in PIXEL_FORMATS:
             raise ValueError("pixel_format %r is none of 'bgr', 'nv12', 'i420', 'yuy2', 'uyvy', 'jpeg'%s"
@@ -44,6 +49,14 @@ class FrameIngest:
             raise ValueError('%s frames need an even width and height, got %dx%d' % (pixel_format, self.sw, self.sh))
         if pixel_format in PACKED_422 and self.sw % 2:
             raise ValueError('%s frames need an even width, got %dx%d' % (pixel_format, self.sw, self.sh))
+        if pixel_format != 'jpeg' and jpeg_scale != 1:
+            raise ValueError("jpeg_scale %r: only a 'jpeg' ring decodes, a %r ring has nothing to scale" % (jpeg_scale, pixel_format))
+        if jpeg_scale == 'auto':
+            from .jpeg import draft_scale
+            jpeg_scale = draft_scale((self.sw, self.sh), (self.dw, self.dh))
+        if isinstance(jpeg_scale, bool) or jpeg_scale not in (1, 2, 4, 8):
+            raise ValueError("jpeg_scale %r is none of 1, 2, 4, 8, 'auto'" % (jpeg_scale,))
+        self.jpeg_scale = int(jpeg_scale)
         self.ctx = context or default_context()
         self.S, self.slots = int(n_streams), int(slots)
         h = P()
@@ -52,8 +65,12 @@ class FrameIngest:
                                          ctypes.byref(h)), 'dd_ingest_create')
         elif pixel_format == 'jpeg':
             self.jpeg_slot_bytes = int(jpeg_slot_bytes) if jpeg_slot_bytes else self.S * self.sw * self.sh * 3 // 8
-            check(lib().dd_ingest_create_jpeg(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
-                                              self.jpeg_slot_bytes, ctypes.byref(h)), 'dd_ingest_create_jpeg')
+            if self.jpeg_scale == 1:
+                check(lib().dd_ingest_create_jpeg(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
+                                                  self.jpeg_slot_bytes, ctypes.byref(h)), 'dd_ingest_create_jpeg')
+            else:
+                check(lib().dd_ingest_create_jpeg_scaled(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
+                                                         self.jpeg_scale, self.jpeg_slot_bytes, ctypes.byref(h)), 'dd_ingest_create_jpeg_scaled')
         else:
             check(lib().dd_ingest_create_format(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
                                                 PIXEL_FORMATS[pixel_format], ctypes.byref(h)), 'dd_ingest_create_format')

@@ -14,7 +14,9 @@ decoder honours: a restart interval is the unit of parallel work.  Parity with O
 
 The way in is the mirror (csrc/jpeg_parse.h, csrc/jpeg_dec.hip): `parse(file)` reads a baseline file's header on the host, and
 `JpegDecoder(H, W).decode(files)` turns files in host memory into BGR frames in HBM, byte for byte libjpeg's pixels (tests/jpeg_dec_ref.py,
-tests/test_gpu_jpeg_decode.py); the ingest ring's `pixel_format='jpeg'` slots (deepdish_amd/ingest.py) are built on it."""
+tests/test_gpu_jpeg_decode.py); the ingest ring's `pixel_format='jpeg'` slots (deepdish_amd/ingest.py) are built on it.  With `scale=2`, 4
+or 8 the decoder transforms every 8 x 8 block straight to 4 x 4, 2 x 2 or 1 x 1 samples, libjpeg's scale_denom and Pillow's Image.draft
+(tests/jpeg_scaled_ref.py), and `draft_scale(src, want)` picks the scale as Pillow does."""
 import ctypes
 
 import numpy as np
@@ -161,12 +163,28 @@ def parse(file):
     return out
 
 
-def decoder_plan(H, W, ncomp=3, hs=2, vs=2):
+def decoder_plan(H, W, ncomp=3, hs=2, vs=2, scale=1):
     """-> (path, rows of a band, bands): DEC_PATH_LDS keeps a band's sample planes in LDS, DEC_PATH_PLANES takes them through HBM.
+    H x W is the file's size; at scale 2, 4 or 8 the rows and bands are those of the scaled frame, and a band needs less LDS.
     Needs no device."""
     path, rows, bands = ctypes.c_int(-1), ctypes.c_int(-1), ctypes.c_int(-1)
-    check(lib().dd_jpegdec_plan(int(H), int(W), int(ncomp), int(hs), int(vs), ctypes.byref(path), ctypes.byref(rows), ctypes.byref(bands)), 'dd_jpegdec_plan')
+    if scale == 1:
+        check(lib().dd_jpegdec_plan(int(H), int(W), int(ncomp), int(hs), int(vs), ctypes.byref(path), ctypes.byref(rows), ctypes.byref(bands)), 'dd_jpegdec_plan')
+    else:
+        check(lib().dd_jpegdec_plan_scaled(int(H), int(W), int(ncomp), int(hs), int(vs), int(scale), ctypes.byref(path), ctypes.byref(rows), ctypes.byref(bands)),
+              'dd_jpegdec_plan_scaled')
     return path.value, rows.value, bands.value
+
+
+def draft_scale(src_size, want_size):
+    """Pillow's Image.draft rule for files of src_size = (width, height) wanted at want_size = (width, height): the largest of 8, 4, 2, 1
+    that is <= min(sw // dw, sh // dh), and 1 when that is 0 -- the cheapest decode that is still at least as large as what is wanted.
+    Needs no device."""
+    (sw, sh), (dw, dh) = src_size, want_size
+    s = lib().dd_jpeg_draft_scale(int(sw), int(sh), int(dw), int(dh))
+    if s < 1:
+        check(s, 'dd_jpeg_draft_scale')
+    return s
 
 
 class JpegDecoder:
@@ -178,17 +196,31 @@ class JpegDecoder:
         frames, status = dec.decode(files)           # u8 [n, 480, 640, 3] and int32 [n] on the device
 
     status: ST_OK; ST_HEADER (refused: parse(file) says why) and ST_SIZE (not H x W) leave the frame untouched; ST_DATA (corrupt or
-    truncated entropy data) leaves unspecified bytes in that frame alone; ST_NO_FRAME for an empty file."""
+    truncated entropy data) leaves unspecified bytes in that frame alone; ST_NO_FRAME for an empty file.
 
-    def __init__(self, H, W, max_frames=16, max_bytes=None, context=None):
+    scale=2, 4 or 8 decodes at that fraction, as libjpeg's scale_denom does (Pillow's im.draft(mode, (W // scale, H // scale)), byte for
+    byte; parity with cv2.IMREAD_REDUCED_COLOR_* is not pinned): H x W stays what a file must state, and the frames are
+    [n, out_H, out_W, 3] with out_H = ceil(H / scale), out_W = ceil(W / scale)."""
+
+    def __init__(self, H, W, max_frames=16, max_bytes=None, context=None, scale=1):
         from .runtime import default_context
         self.ctx = context or default_context()
         self.H, self.W, self.max_frames = int(H), int(W), int(max_frames)
         self.max_bytes = int(max_bytes) if max_bytes else self.max_frames * (self.H * self.W * 3 + 4096)
         self._h = None
+        self.scale = scale
         h = P()
-        check(lib().dd_jpegdec_create(self.ctx.handle, self.H, self.W, self.max_frames, self.max_bytes, ctypes.byref(h)), 'dd_jpegdec_create')
+        if scale == 1:
+            check(lib().dd_jpegdec_create(self.ctx.handle, self.H, self.W, self.max_frames, self.max_bytes, ctypes.byref(h)), 'dd_jpegdec_create')
+        else:
+            if not isinstance(scale, int) or isinstance(scale, bool):
+                raise ValueError('scale %r is none of 1, 2, 4, 8' % (scale,))
+            check(lib().dd_jpegdec_create_scaled(self.ctx.handle, self.H, self.W, scale, self.max_frames, self.max_bytes, ctypes.byref(h)),
+                  'dd_jpegdec_create_scaled')
         self._h = h
+        oh, ow = ctypes.c_int(), ctypes.c_int()
+        check(lib().dd_jpegdec_output_size(self._h, ctypes.byref(oh), ctypes.byref(ow)), 'dd_jpegdec_output_size')
+        self.out_H, self.out_W = oh.value, ow.value
 
     def __del__(self):
         try:
@@ -209,7 +241,7 @@ class JpegDecoder:
         return dict(zip(('upload', 'markers', 'entropy', 'pixels'), (float(v) for v in ms)))
 
     def decode(self, files, out=None, status=None, stream=None):
-        """files: a list of bytes objects.  out / status: tensors to write instead of new ones.  Queued on the context's stream (or
+        """files: a list of bytes objects -> (u8 [n, out_H, out_W, 3], int32 [n]).  out / status: tensors to write instead of new ones.  Queued on the context's stream (or
         `stream`): `context.sync()` before torch reads the result on another stream."""
         import torch
         n = len(files)
@@ -223,10 +255,10 @@ class JpegDecoder:
         buf = (ctypes.c_uint8 * max(1, len(blob))).from_buffer(blob)
         dev = torch.device('cuda', self.ctx.device)
         if out is None:
-            out = torch.empty((n, self.H, self.W, 3), dtype=torch.uint8, device=dev)
+            out = torch.empty((n, self.out_H, self.out_W, 3), dtype=torch.uint8, device=dev)
         if status is None:
             status = torch.empty(n, dtype=torch.int32, device=dev)
-        assert tuple(out.shape) == (n, self.H, self.W, 3) and out.dtype == torch.uint8 and out.is_contiguous()
+        assert tuple(out.shape) == (n, self.out_H, self.out_W, 3) and out.dtype == torch.uint8 and out.is_contiguous()
         assert tuple(status.shape) == (n,) and status.dtype == torch.int32
         torch.cuda.current_stream(out.device).synchronize()
         check(lib().dd_jpegdec_decode(self._h, buf, offs.ctypes.data_as(P), lens.ctypes.data_as(P), n, P(out.data_ptr()), P(status.data_ptr()), stream),

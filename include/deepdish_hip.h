@@ -323,6 +323,12 @@ int dd_ingest_create_format(dd_ctx *ctx, int slots, int n_streams, int src_h, in
  * must have returned before that slot's submit; a second put for a stream replaces the first (its bytes stay in the arena until the submit). */
 int dd_ingest_create_jpeg(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip, int64_t slot_bytes,
                           dd_ingest **out);
+/* The same ring decoding at 1 / scale (1, 2, 4 or 8; anything else is DD_E_ARG naming the value; see dd_jpegdec_create_scaled).  src_h x
+ * src_w stays the size every file must state (DD_JPEG_ST_SIZE otherwise).  The decoder writes frames of ceil(src_h / scale) x ceil(src_w /
+ * scale): straight into the slot's output when that is dst_h x dst_w and no flip is asked, otherwise into the staging buffer, which has
+ * that size, followed by the ring's crop_resize launch from there to dst_h x dst_w.  scale 1 is dd_ingest_create_jpeg. */
+int dd_ingest_create_jpeg_scaled(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip, int scale,
+                                 int64_t slot_bytes, dd_ingest **out);
 int dd_ingest_jpeg_put(dd_ingest *g, int slot, int stream, const uint8_t *data_host, int64_t n);
 int dd_ingest_status(dd_ingest *g, int slot, int *status_host);
 int dd_ingest_destroy(dd_ingest *g);
@@ -782,6 +788,22 @@ int dd_jpegdec_decode(dd_jpegdec *dec, const uint8_t *files_host, const int64_t 
  * jpeg_entropy_k, jpeg_planes_k + jpeg_pixels_k.  DD_E_STATE without a profiled decode. */
 int dd_jpegdec_profile(dd_jpegdec *dec, int on);
 int dd_jpegdec_profile_read(dd_jpegdec *dec, float *ms_host);
+/* Decoding at 1/2, 1/4 or 1/8 scale: libjpeg's scale_num / scale_denom = 1 / scale, what Pillow's Image.draft and cv2's
+ * IMREAD_REDUCED_COLOR_2 / 4 / 8 select.  A file of h x w decodes to ceil(h / scale) x ceil(w / scale), byte for byte Pillow's
+ * im.draft(mode, (w // scale, h // scale)); im.convert('RGB') with the channels swapped (tests/jpeg_scaled_ref.py; parity with OpenCV's
+ * reduced decode is not pinned).  Markers and entropy decoding are the full-size ones; every 8 x 8 block is transformed straight to n x n
+ * samples (jidctred.c), n = 8 / scale, except 4:2:0 chroma, which keeps 2 * n and so needs no up-sampling; 4:2:2 chroma goes through the
+ * h2v1 filter (replicated at scale 8).  h x w stays the size a file must state, and the status contract is dd_jpegdec_decode's; out_dev
+ * is u8 [n][ceil(h / scale)][ceil(w / scale)][3], and a frame is written only inside its own bytes of it, whatever its status.
+ * scale 1 is dd_jpegdec_create / dd_jpegdec_plan exactly; a scale other than 1, 2, 4, 8 is DD_E_ARG naming the value.  A band of
+ * jpeg_pixels_k is 8 * vs / scale output rows and needs less LDS, so widths that take DD_JPEGDEC_PLANES at full size stay in LDS here. */
+int dd_jpegdec_create_scaled(dd_ctx *ctx, int h, int w, int scale, int max_frames, int64_t max_bytes, dd_jpegdec **out);
+int dd_jpegdec_plan_scaled(int h, int w, int ncomp, int hs, int vs, int scale, int *path_host, int *band_rows_host, int *bands_host);
+/* The size of the frames this decoder writes: h x w, or the scaled size. */
+int dd_jpegdec_output_size(dd_jpegdec *dec, int *out_h_host, int *out_w_host);
+/* Pillow's draft rule: the largest of 8, 4, 2, 1 that is <= min(src_w / dst_w, src_h / dst_h) in whole numbers, 1 when that is 0: the
+ * decode that is still at least dst_w x dst_h.  Returns the scale; DD_E_ARG for a side below 1.  Host only. */
+int dd_jpeg_draft_scale(int src_w, int src_h, int dst_w, int dst_h);
 
 /* ---------------------------------------------------------------- multi-GPU
  * Sum of the per-stream count vectors (pos, neg, int, del per label; deepdish.py:1141-1145).
