@@ -939,8 +939,7 @@ int crop_box_host_f64(const double *b, int ph, int pw, int H, int W, int *sx, in
 int crop_resize(hipStream_t s, const uint8_t *frames, int H, int W, const void *d_boxes, int n, int oh, int ow,
                 uint8_t *out) {
     if (n <= 0) return DD_OK;
-    static const bool quad_off = getenv("DD_CROP_QUADS") && atoi(getenv("DD_CROP_QUADS")) == 0;
-    if (!quad_off && ow % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0)
+    if (ow % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0)
         hipLaunchKernelGGL(crop_resize4_k, dim3(dd_ceil_div(oh * (ow / 4), 256), n), dim3(256), 0, s, frames, H, W,
                            static_cast<const CropBox *>(d_boxes), oh, ow, out);
     else

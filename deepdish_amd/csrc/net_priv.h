@@ -30,9 +30,6 @@ struct dd_net {
     float *d_anchors = nullptr, *dec_boxes = nullptr, *dec_score = nullptr, *dec_keys = nullptr; int *dec_cls = nullptr;
     bool slab_moved = false;                 // the slab was reallocated during the last eager forward: captured graphs hold a dead pointer
     _Float16 *d_zero = nullptr;              // 256 bytes of zeros (padding taps of the direct-to-LDS fills)
-    bool use_glds = true;
-    bool use_rw = true;                      // DD_NO_RW=1: 3x3x32x32 layers fall back to the implicit-GEMM kernels (A/B measurements)
-    int tile_mode = 0;                       // DD_TILE_MODE=1 forces the 64 x 64 tile everywhere (A/B measurements)
     std::vector<hipEvent_t> events;           // n_ops + 1 when profiling
     std::vector<int32_t> op_launch;           // per op of the last forward: DD_OPK_* (which launch ran it)
     std::vector<int32_t> op_variant;          // per op of the last forward: tile / fill mode / K split of the generic conv launcher, 0 = another kernel

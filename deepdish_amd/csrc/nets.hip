@@ -3116,9 +3116,9 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ws_k(const ConvP P, const int
         for (int b = 0; b < MI; ++b)
             x[b] = *reinterpret_cast<const h8 *>(xs + (b * 16 + fr) * 64 + (((kk << 2) + fq) ^ sw) * 8);
     };
-    // SPB stages per barrier (DD_WS_SPB).  SPB = 2 = one wait + barrier per TWO K slabs, 32 MFMAs per wave between barriers instead of
-    // 16 (fills D - 2 .. D - 1 stages ahead, D - 5 stages left in flight by the wait): built to test whether barrier skew between the
-    // four waves of a block is what a stage pays for -- it is not: no change on either layer (round 3, same-box A/B).  Default 1.
+    // SPB stages per barrier; only 1 is instantiated.  (2 = one wait + barrier per TWO K slabs, 32 MFMAs per wave between barriers instead
+    // of 16, changed nothing on either layer: barrier skew between the four waves of a block is not what a stage pays for.  The parameter
+    // stays because the compiler emits other code for the same loop written with literals.)
     for (int st = 0; st < D - SPB; ++st) fill(st);
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("s_waitcnt vmcnt(%0)" ::"i"(G * (D - SPB - 1)) : "memory");
@@ -3178,136 +3178,6 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_ws_k(const ConvP P, const int
 #if defined(__HIP_DEVICE_COMPILE__)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the look-ahead fills past the last tile
 #endif
-}
-
-// conv_ws_k with the pixel tiles staged THROUGH REGISTERS instead of by LDS-DMA.  In-kernel stamps (round 3, -DDD_KERNEL_STAMP build
-// of conv_ws_k: scripts/stamp_conv_ws.sh) put the two global_load_lds of a stage at 336 of its 876 cycles per wave -- with the
-// address chain hoisted out of the loop still 233: an LDS-DMA costs the issuing wave ~115 cycles here, and a weight-stationary wave
-// issues two of them per 16 MFMAs.  A global_load_dwordx4 to registers costs the wave a few cycles to issue and a ds_write_b128 13;
-// the price is 32 VGPRs for four stages in flight.  Stage s is loaded LA + 2 = 6 stages before its MFMAs, written to LDS two
-// stages before them (behind that stage's barrier: the buffer's last reader is two barriers back), read like conv_ws_k reads it.
-// hipcc counts these loads itself (no LDS-DMA in the kernel), so the waits in front of the ds_writes are exact.  Same LDS image,
-// same fragment reads, same MFMA order, same epilogue: the same bits.
-template <int KS, int NW, int ACT, int NG = 1>
-__global__ __launch_bounds__(NW * 64) void conv_wsr_k(const ConvP P, const int n_slices) {
-    constexpr int BM = WS_BM, MI = 4, NI = 2 * NG, G = 8 / NW, D = 4, LA = 4;
-    static_assert(KS % LA == 0 && 8 % NW == 0, "register sets rotate with the unrolled K loop");
-    extern __shared__ __attribute__((aligned(16))) _Float16 lds[];         // [D][64 pixels][64 halves]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fr = lane & 15, fq = lane >> 4, sw = fr & 7;
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    const int slice = j % n_slices, worker = (j / n_slices) * 8 + xcd;
-    const int n_workers = ((int)(gridDim.x >> 3) / n_slices) * 8;
-    const int T = (P.m + BM - 1) / BM;
-    const int ntiles = worker < T ? (T - worker + n_workers - 1) / n_workers : 0;
-    const int cbase = slice * (32 * NG * NW) + wave * (32 * NG);
-
-    h8 wf[KS * 2][NI];
-#pragma unroll
-    for (int k = 0; k < KS * 2; ++k)
-#pragma unroll
-        for (int a = 0; a < NI; ++a)
-            wf[k][a] = *reinterpret_cast<const h8 *>(P.w + (size_t)(cbase + rw_weight_row(a, fr)) * P.kpad + k * 32 + fq * 8);
-    Epi8 E[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) E[g] = epi8_load(P, cbase + g * 32 + fq * 8);
-    f4 acc[NI][MI];
-#pragma unroll
-    for (int a = 0; a < NI; ++a)
-#pragma unroll
-        for (int b = 0; b < MI; ++b) acc[a][b] = f4{0.f, 0.f, 0.f, 0.f};
-
-    const int rr = lane >> 3, pp = lane & 7;
-    const int gch = (pp ^ rr) * 8;
-    // per-lane source pointers of a tile's G row groups (K chunk gch of pixel row grp * 8 + rr), once per tile; a load is then the
-    // pointer plus an immediate K-slab offset.  Rows past the tensor / tiles past the last one read pixel 0 (never stored).
-    auto tile_base = [&](int ti, const _Float16 *(&tb)[G]) {
-        const int m0 = (worker + ti * n_workers) * BM;
-#pragma unroll
-        for (int i = 0; i < G; ++i) {
-            const int m = m0 + (wave * G + i) * 8 + rr;
-            tb[i] = P.in + (size_t)((ti < ntiles && m < P.m) ? m : 0) * P.cs_in + P.coff_in + gch;
-        }
-    };
-    h8 rs[LA][G];                                                // stages in flight: set s % LA holds stage s between its load and its LDS write
-    auto load_stage = [&](const _Float16 *const (&tb)[G], int ksp, h8 (&r)[G]) {
-#pragma unroll
-        for (int i = 0; i < G; ++i) r[i] = *reinterpret_cast<const h8 *>(tb[i] + ksp * 64);
-    };
-    auto write_stage = [&](int buf, const h8 (&r)[G]) {
-        _Float16 *dst = lds + (size_t)buf * (BM * 64);
-#pragma unroll
-        for (int i = 0; i < G; ++i) *reinterpret_cast<h8 *>(dst + ((wave * G + i) * 8 + rr) * 64 + pp * 8) = r[i];
-    };
-    h8 xa[MI], xb[MI];
-    auto read_frags = [&](int st, int kk, h8 (&x)[MI]) {
-        const _Float16 *xs = lds + (size_t)(st & (D - 1)) * (BM * 64);
-#pragma unroll
-        for (int b = 0; b < MI; ++b)
-            x[b] = *reinterpret_cast<const h8 *>(xs + (b * 16 + fr) * 64 + (((kk << 2) + fq) ^ sw) * 8);
-    };
-    constexpr int AH = LA + 2;                                   // a stage is loaded AH stages ahead: tile ti + OA or ti + OA + 1
-    constexpr int OA = AH / KS;
-    const _Float16 *tbA[G], *tbB[G];
-    {   // stages 0, 1 -> LDS; stages 2 .. AH - 1 -> their register sets
-        const _Float16 *t[G];
-#pragma unroll
-        for (int tt = 0; tt * KS < AH; ++tt) {
-            tile_base(tt, t);
-#pragma unroll
-            for (int st = tt * KS; st < (tt + 1) * KS && st < AH; ++st) {
-                load_stage(t, st - tt * KS, rs[st % LA]);
-                if (st < 2) write_stage(st, rs[st % LA]);
-            }
-        }
-    }
-    tile_base(OA, tbA);
-    tile_base(OA + 1, tbB);
-    __syncthreads();
-    read_frags(0, 0, xa);
-    for (int ti = 0; ti < ntiles; ++ti) {
-        const int m0 = (worker + ti * n_workers) * BM;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const int st = ti * KS + ks;
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // my writes of stage st + 1 (last stage) and my reads of stage st - 1 are done ...
-            __builtin_amdgcn_s_barrier();                        // ... everybody's are
-            asm volatile("" ::: "memory");
-#endif
-            write_stage((st + 2) & (D - 1), rs[(ks + 2) % LA]);  // stage st + 2 (its loads were issued LA stages ago)
-            if ((ks + AH) / KS == OA) load_stage(tbA, (ks + AH) % KS, rs[(ks + 2) % LA]);   // stage st + AH into the set just written out
-            else load_stage(tbB, (ks + AH) % KS, rs[(ks + 2) % LA]);
-            read_frags(st, 1, xb);
-#pragma unroll
-            for (int a = 0; a < NI; ++a)
-#pragma unroll
-                for (int b = 0; b < MI; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[ks * 2][a], xa[b], acc[a][b], 0, 0, 0);
-            read_frags(st + 1, 0, xa);
-#pragma unroll
-            for (int a = 0; a < NI; ++a)
-#pragma unroll
-                for (int b = 0; b < MI; ++b)
-                    acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[ks * 2 + 1][a], xb[b], acc[a][b], 0, 0, 0);
-        }
-#pragma unroll
-        for (int b = 0; b < MI; ++b) {
-            const int m = m0 + b * 16 + fr;
-#pragma unroll
-            for (int g = 0; g < NG; ++g) {
-                float o[8];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { o[r] = acc[2 * g][b][r]; o[4 + r] = acc[2 * g + 1][b][r]; }
-                if (m < P.m) conv_epilogue_f16x8<ACT, true, 0>(P, E[g], m, cbase + g * 32 + fq * 8, o);
-                acc[2 * g][b] = acc[2 * g + 1][b] = f4{0.f, 0.f, 0.f, 0.f};
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < G; ++i) tbA[i] = tbB[i];
-        tile_base(ti + OA + 2, tbB);
-    }
 }
 
 struct DwP {
@@ -3871,8 +3741,7 @@ int launch_conv(hipStream_t s, ConvP &P, DevBuf &slab, int max_batch, int device
     if constexpr (GLDS) {
         const bool pw = P.kh == 1 && P.kw == 1 && P.stride == 1 && P.pad_t == 0 && P.pad_l == 0 && P.cin % 64 == 0 &&
                         P.ho == P.H && P.wo == P.W;
-        static const bool no_fm2 = dd_env_set("DD_NO_FM2");                      // A/B switch
-        const bool tapu = P.cin % 64 == 0 && P.kh <= 3 && P.kw <= 3 && P.kpad == P.kh * P.kw * P.cin && !no_fm2;
+        const bool tapu = P.cin % 64 == 0 && P.kh <= 3 && P.kw <= 3 && P.kpad == P.kh * P.kw * P.cin;
         if (pw) hipLaunchKernelGGL((conv_glds_k<WM, WN, MI, NI, 1>), dim3(gx, gy, splitk), dim3(WM * WN * 64), lds_bytes, s, P);
         else if (tapu) hipLaunchKernelGGL((conv_glds_k<WM, WN, MI, NI, 2>), dim3(gx, gy, splitk), dim3(WM * WN * 64), lds_bytes, s, P);
         else hipLaunchKernelGGL((conv_glds_k<WM, WN, MI, NI, 0>), dim3(gx, gy, splitk), dim3(WM * WN * 64), lds_bytes, s, P);
@@ -4325,44 +4194,8 @@ int launch_conv_ws(hipStream_t s, ConvP &P, int device) {
     });
     if (rc != DD_OK) return rc;
     const dim3 grid(2 * 256 * 4 / NW);                           // persistent: 8 waves per CU
-    // DD_WSR=1: register-staged fills (conv_wsr_k), =2: that with 64 channels per wave (weights spill into AGPRs, one block per CU).
-    // Same bits; measured at 384 frames: 19x19x512 94.5 (LDS-DMA ring) / 93.8 / 88.6 us, 38x38x256 119 / 119 / 126 us -- neither the
-    // fills' issue cost nor the LDS read bandwidth is what holds the loop at 0.37 MFMA-busy, so the ring stays the default.
-    static const int wsr = dd_env_int("DD_WSR", 0);
-    if (wsr == 2 && P.cout_pad % 256 == 0) {                     // 64 channels per wave, one block per CU: half the LDS reads per MFMA
-        constexpr size_t lds_r = (size_t)4 * WS_BM * 64 * sizeof(_Float16);
-        const int ns = P.cout_pad / 256;
-        if (P.act == ACT_RELU6) hipLaunchKernelGGL((conv_wsr_k<KS, NW, ACT_RELU6, 2>), dim3(256), dim3(NW * 64), lds_r, s, P, ns);
-        else if (P.act == ACT_SILU) hipLaunchKernelGGL((conv_wsr_k<KS, NW, ACT_SILU, 2>), dim3(256), dim3(NW * 64), lds_r, s, P, ns);
-        else hipLaunchKernelGGL((conv_wsr_k<KS, NW, ACT_NONE, 2>), dim3(256), dim3(NW * 64), lds_r, s, P, ns);
-        DD_LAUNCH_CHECK();
-        return DD_OK;
-    }
-    if (wsr) {
-        constexpr size_t lds_r = (size_t)4 * WS_BM * 64 * sizeof(_Float16);
-        const dim3 grid_r(2 * 256 * 4 / NW);
-        if (P.act == ACT_RELU6) hipLaunchKernelGGL((conv_wsr_k<KS, NW, ACT_RELU6>), grid_r, dim3(NW * 64), lds_r, s, P, n_slices);
-        else if (P.act == ACT_SILU) hipLaunchKernelGGL((conv_wsr_k<KS, NW, ACT_SILU>), grid_r, dim3(NW * 64), lds_r, s, P, n_slices);
-        else hipLaunchKernelGGL((conv_wsr_k<KS, NW, ACT_NONE>), grid_r, dim3(NW * 64), lds_r, s, P, n_slices);
-        DD_LAUNCH_CHECK();
-        return DD_OK;
-    }
-    static const int spb = dd_env_int("DD_WS_SPB", 1);     // stages per barrier; 2 measured null (19x19x512 93.6 / 91.8 vs 94.5 / 92.0 us, same bits)
-    if (spb == 2) {
-        static DevOnce once2;
-        const int rc2 = once2.run(device, [&]() -> int {
-            DD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_ws_k<KS, NW, D, ACT_RELU6, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            DD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_ws_k<KS, NW, D, ACT_SILU, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            DD_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_ws_k<KS, NW, D, ACT_NONE, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            return DD_OK;
-        });
-        if (rc2 != DD_OK) return rc2;
-        if (P.act == ACT_RELU6) hipLaunchKernelGGL((conv_ws_k<KS, NW, D, ACT_RELU6, 2>), grid, dim3(NW * 64), lds_bytes, s, P, n_slices);
-        else if (P.act == ACT_SILU) hipLaunchKernelGGL((conv_ws_k<KS, NW, D, ACT_SILU, 2>), grid, dim3(NW * 64), lds_bytes, s, P, n_slices);
-        else hipLaunchKernelGGL((conv_ws_k<KS, NW, D, ACT_NONE, 2>), grid, dim3(NW * 64), lds_bytes, s, P, n_slices);
-        DD_LAUNCH_CHECK();
-        return DD_OK;
-    }
+    // (Register-staged fills, with 32 or 64 channels per wave, ran within 6 % either way at the same bits: neither the fills' issue
+    // cost nor the LDS read bandwidth is what holds the loop at 0.37 MFMA-busy.)
     if (P.act == ACT_RELU6) hipLaunchKernelGGL((conv_ws_k<KS, NW, D, ACT_RELU6>), grid, dim3(NW * 64), lds_bytes, s, P, n_slices);
     else if (P.act == ACT_SILU) hipLaunchKernelGGL((conv_ws_k<KS, NW, D, ACT_SILU>), grid, dim3(NW * 64), lds_bytes, s, P, n_slices);
     else hipLaunchKernelGGL((conv_ws_k<KS, NW, D, ACT_NONE>), grid, dim3(NW * 64), lds_bytes, s, P, n_slices);
@@ -4657,9 +4490,6 @@ static int net_create(dd_ctx *ctx, const int32_t *program_host, int n_words, con
     n->weight_bytes = n_weight_bytes;
     DD_HIP(hipMalloc(&n->d_zero, 256));
     DD_HIP(hipMemset(n->d_zero, 0, 256));
-    n->use_glds = !dd_env_set("DD_NO_GLDS");
-    n->use_rw = !dd_env_set("DD_NO_RW");
-    n->tile_mode = dd_env_int("DD_TILE_MODE", 0);
     DD_HIP(hipMalloc(&n->d_weights, (size_t)n_weight_bytes + 256));
     DD_HIP(hipMemcpy(n->d_weights, weights_host, (size_t)n_weight_bytes, hipMemcpyHostToDevice));
     guard.n = nullptr;
@@ -5090,7 +4920,7 @@ int run_input(Run &r, int i, const OpView &o) {
     _Float16 *out; int cs, coff;
     bind_tensor(net, dst, out, cs, coff);
     const int m = r.nimg * td->h * td->w;
-    if (o.s2d() && o.hint() != HINT_NONE && !o.swap_rb() && cs == 32 && !coff && i + 1 < net->n_ops && net->use_rw) {   // only the next op reads it: the Focus fold
+    if (o.s2d() && o.hint() != HINT_NONE && !o.swap_rb() && cs == 32 && !coff && i + 1 < net->n_ops) {   // only the next op reads it: the Focus fold
         static const bool off = dd_env_int("DD_FOCUS_UNFUSED", 0) != 0;
         if (!off && rw_shape_plain(op(net, i + 1), dst, ACT_SILU) && td->w % 32 == 0) {
             h.input_on = true; h.input_mean = o.f(0); h.input_scale = o.f(1); h.input_op = i;
@@ -5116,15 +4946,13 @@ int conv_tile(Run &r, int i, ConvP &P) {
 }
 
 // The generic implicit-GEMM kernels: tile from the layer and the batch of the call.
-int launch_conv_tiled(Run &r, int i, ConvP &P, bool bk32, bool glds) {
-    const dd_net *net = r.net;
+int launch_conv_tiled(Run &r, int i, ConvP &P, bool bk32) {
     if (P.cout_pad <= 32) {
         // 32 output channels: 128 pixels per block (each wave 32 px x 32 ch) once there are enough pixels
         return bk32 ? conv_tile<4, 1, 1, 2, 32, false>(r, i, P)
-             : (glds && P.m >= 16384) ? conv_tile<4, 1, 2, 2, 64, true>(r, i, P)
-             : glds ? conv_tile<4, 1, 1, 2, 64, true>(r, i, P)
-                    : conv_tile<4, 1, 1, 2, 64, false>(r, i, P);
-    } else if (glds && net->tile_mode != 1 && P.m >= 16384 && P.cout_pad >= 128) {
+             : P.m >= 16384 ? conv_tile<4, 1, 2, 2, 64, true>(r, i, P)
+                            : conv_tile<4, 1, 1, 2, 64, true>(r, i, P);
+    } else if (!bk32 && P.m >= 16384 && P.cout_pad >= 128) {
         // plenty of pixels: 128 x 128 with 8 waves -- a third less L2->LDS traffic per FLOP than 64 x 128
         // (24.3 us vs 26.6 us for 19x19x512 -> 512 at 64 frames; at 10x10 it halves the block count and loses).
         // A K-capped run shows ~40 % of such a launch is per-round cost (prologue, epilogue, a partly filled
@@ -5133,18 +4961,16 @@ int launch_conv_tiled(Run &r, int i, ConvP &P, bool bk32, bool glds) {
         const int gy128 = dd_ceil_div(P.cout_pad, 128);
         const int c128 = dd_ceil_div(dd_ceil_div(P.m, 128) * gy128, 512) * 128;
         const int c192 = dd_ceil_div(dd_ceil_div(P.m, 192) * gy128, 512) * 192;
-        if (P.epi == EPI_F16 && c192 <= c128 && net->tile_mode != 2) return conv_tile<4, 2, 3, 4, 64, true>(r, i, P);
+        if (P.epi == EPI_F16 && c192 <= c128) return conv_tile<4, 2, 3, 4, 64, true>(r, i, P);
         return conv_tile<4, 2, 2, 4, 64, true>(r, i, P);
-    } else if (glds && net->tile_mode != 1 && P.m >= 16384 && P.cout_pad == 64) {
+    } else if (!bk32 && P.m >= 16384 && P.cout_pad == 64) {
         return conv_tile<4, 2, 2, 2, 64, true>(r, i, P);      // 128 x 64, 8 waves
-    } else if (glds && net->tile_mode != 1 && P.m >= 4096 && P.cout_pad >= 128) {
+    } else if (!bk32 && P.m >= 4096 && P.cout_pad >= 128) {
         // 64 pixels x 128 channels: each staged pixel row feeds twice the MFMAs; measured 31 us vs 38 us
         // for 19x19x512 -> 512 at 64 frames (128 x 64 gave nothing, 128 x 128 was 2.5x slower: 2 blocks/CU)
         return conv_tile<2, 2, 2, 4, 64, true>(r, i, P);
     }
-    return bk32 ? conv_tile<2, 2, 2, 2, 32, false>(r, i, P)
-         : glds ? conv_tile<2, 2, 2, 2, 64, true>(r, i, P)
-                : conv_tile<2, 2, 2, 2, 64, false>(r, i, P);
+    return bk32 ? conv_tile<2, 2, 2, 2, 32, false>(r, i, P) : conv_tile<2, 2, 2, 2, 64, true>(r, i, P);
 }
 
 // A 3x3 32 -> 32 layer on conv3x3_rw_k and the launches built on it: whole filter in registers, input patch staged once.
@@ -5201,7 +5027,7 @@ int run_conv(Run &r, int i, const OpView &o) {
         }
     }
     ConvP P = conv_params(net, o, nimg);
-    DD_REQUIRE(!o.pool() || (net->use_rw && P.kh == 3 && P.stride == 1 && P.cin == 32 && P.cout_pad == 32), DD_E_ARG,
+    DD_REQUIRE(!o.pool() || (P.kh == 3 && P.stride == 1 && P.cin == 32 && P.cout_pad == 32), DD_E_ARG,
                "dd_net_forward: fused pooling is only built for the 3x3 32->32 kernel");
     if (h.unit_on) {                                           // the previous op was a residual unit's first layer
         if (res_unit_fusable(h.unit_a, P, nimg)) {
@@ -5230,7 +5056,7 @@ int run_conv(Run &r, int i, const OpView &o) {
         if ((rc = flush(r, HELD_UNIT)) != DD_OK) return rc;
     }
     if (h.pair_on) {                                           // a held unit waits only for the first layer of the unit that reads it
-        const bool next_a = net->use_rw && rw_shape(P) && unit_first_layer(r, i, o, P) && P.in == static_cast<const _Float16 *>(h.pair_b.out2);
+        const bool next_a = rw_shape(P) && unit_first_layer(r, i, o, P) && P.in == static_cast<const _Float16 *>(h.pair_b.out2);
         if (!next_a && (rc = flush(r, HELD_PAIR)) != DD_OK) return rc;
     }
     if (P.epi == EPI_YOLO && net->yolo_dec && o.aff_off() && !o.has_aff()) {      // aff_off / aux_off: the per-anchor copy of weights / bias
@@ -5254,10 +5080,9 @@ int run_conv(Run &r, int i, const OpView &o) {
         net->op_launch[i] = OPK_SSD_HEAD_DEC;
         return DD_OK;
     }
-    const bool bk32 = o.bk() == 32;                            // shallow K (<= 96): one or few 32-wide steps
-    const bool glds = !bk32 && net->use_glds;                  // K >= 97: direct-to-LDS fills, any Cin % 8 == 0
+    const bool bk32 = o.bk() == 32;                            // shallow K (<= 96): one or few 32-wide steps; K >= 97: direct-to-LDS fills, any Cin % 8 == 0
     P.zero = net->d_zero;
-    if (net->use_rw && rw_shape(P)) return run_conv3x3_rw(r, i, o, P);
+    if (rw_shape(P)) return run_conv3x3_rw(r, i, o, P);
     if (mars_ws_s1_eligible(P)) {
         const MarsWsP Q = mars_ws_params(P, nimg);
         net->op_launch[i] = OPK_MARS_WS;
@@ -5290,7 +5115,7 @@ int run_conv(Run &r, int i, const OpView &o) {
         net->op_launch[i] = OPK_CONV_WS;
         return launch_ws(r, P);
     }
-    return launch_conv_tiled(r, i, P, bk32, glds);
+    return launch_conv_tiled(r, i, P, bk32);
 }
 
 int run_stem(Run &r, int i, const OpView &o) {
@@ -5326,7 +5151,7 @@ int run_stem(Run &r, int i, const OpView &o) {
     };
     const bool wide_off = dd_env_int("DD_STEM_WIDE", STEM_WIDE_DEFAULT ? 1 : 0) == 0;
     const int wide_min = dd_env_int("DD_STEM_WIDE_MIN", STEM_WIDE_MIN_CROPS);
-    if (hinted && !wide_off && nimg >= wide_min && i + 2 < net->n_ops && net->use_rw && stem_wide_geometry(P.H, P.W) && P.stride == 1 &&
+    if (hinted && !wide_off && nimg >= wide_min && i + 2 < net->n_ops && stem_wide_geometry(P.H, P.W) && P.stride == 1 &&
         P.pad_t == 1 && P.pad_l == 1 && P.cout == 32 && P.act == ACT_ELU && !td->coff && aligned) {
         const OpView q = op(net, i + 1), p = op(net, i + 2);       // the 3x3 layer, the pool
         if (rw_shape_plain(q, dst, ACT_ELU) && q.cout() == 32 && q.hint() == HINT_NONE &&
@@ -5395,19 +5220,14 @@ int run_dwconv(Run &r, int i, const OpView &o) {
         const int rc = flush(r, HELD_PW);
         if (rc != DD_OK) return rc;
     }
-    static const bool two_rows = !dd_env_set("DD_DW_ONE_ROW");              // A/B switch
-    const int ty = (P.stride == 1 && two_rows) ? 2 : 1;
+    const int ty = P.stride == 1 ? 2 : 1;                       // stride 1: two output rows per item
     const long long total = (long long)nimg * ((P.ho + ty - 1) / ty) * ((P.wo + 3) / 4) * (P.c >> 3);
     DD_REQUIRE(total < (1LL << 31), DD_E_CAPACITY, "dd_net_forward: depthwise layer of %lld items exceeds 32-bit indexing", total);
     DD_REQUIRE(P.stride == 1 || P.stride == 2, DD_E_ARG, "dd_net_forward: depthwise stride %d", P.stride);
     const dim3 grid((unsigned)((total + 255) / 256));
-#define DD_DW(S_, A_) hipLaunchKernelGGL((dwconv3_k<S_, A_>), grid, dim3(256), 0, s, P)
-#define DD_DW2(A_) hipLaunchKernelGGL((dwconv3_k<1, A_, 2>), grid, dim3(256), 0, s, P)
-    if (ty == 2) { if (P.act == ACT_RELU6) DD_DW2(ACT_RELU6); else if (P.act == ACT_SILU) DD_DW2(ACT_SILU); else DD_DW2(-1); }
-    else if (P.act == ACT_RELU6) { if (P.stride == 1) DD_DW(1, ACT_RELU6); else DD_DW(2, ACT_RELU6); }
-    else if (P.act == ACT_SILU) { if (P.stride == 1) DD_DW(1, ACT_SILU); else DD_DW(2, ACT_SILU); }
-    else { if (P.stride == 1) DD_DW(1, -1); else DD_DW(2, -1); }
-#undef DD_DW2
+#define DD_DW(A_) do { if (P.stride == 1) hipLaunchKernelGGL((dwconv3_k<1, A_, 2>), grid, dim3(256), 0, s, P); \
+                       else hipLaunchKernelGGL((dwconv3_k<2, A_, 1>), grid, dim3(256), 0, s, P); } while (0)
+    if (P.act == ACT_RELU6) DD_DW(ACT_RELU6); else if (P.act == ACT_SILU) DD_DW(ACT_SILU); else DD_DW(-1);
 #undef DD_DW
     DD_LAUNCH_CHECK();
     return DD_OK;
@@ -5467,16 +5287,11 @@ int run_l2norm(Run &r, const OpView &o) {
     return DD_OK;
 }
 
-// uint8 SSD, in front of the walk: the first three ops (first layer, MobileNet blocks 1 and 2) as one launch, or over chunks of frames.  Sets the
+// uint8 SSD, in front of the walk: the first three ops (first layer, MobileNet blocks 1 and 2) as one launch.  Sets the
 // op the walk starts at, and whether it takes blocks 3 + 4 as one launch.
 int run_q_front(Run &r, int *first_op) {
     dd_net *net = r.net; const int nimg = r.nimg; hipStream_t s = r.s;
-    // The first three launches over chunks of frames that REUSE the image slots 0 .. chunk - 1
-    // of the two tensors between them, so that 0.72 + 1.44 MB per frame of producer -> consumer traffic can stay in the 256 MB Infinity
-    // Cache instead of going to HBM and back (DD_Q_FRONT_CHUNK=n frames; 0 = off).  Same kernels, same bits: block 2 writes its own
-    // output where the whole-batch launch would.
-    static const int chunk_env = dd_env_int("DD_Q_FRONT_CHUNK", 0);
-    // The same three ops as ONE launch, the two tensors between them in LDS rings (csrc/netsq_front.hip).  DD_Q_FRONT=0: the three
+    // The three ops as ONE launch, the two tensors between them in LDS rings (csrc/netsq_front.hip).  DD_Q_FRONT=0: the three
     // launches; DD_Q_FRONT_MIN: frames per forward from which the row pipeline runs (a few frames spread better as three wide launches).  Read on
     // every forward: a test flips them between two forwards of one engine.
     const bool front_on = dd_env_int("DD_Q_FRONT", 1) != 0;
@@ -5485,30 +5300,12 @@ int run_q_front(Run &r, int *first_op) {
     r.mid_on = dd_env_int("DD_Q_MID", 1) != 0 && nimg >= front_min;
     *first_op = 0;
     const bool front_ops = net->n_ops > 3 && op(net, 0).kind() == OP_QCONV0 && op(net, 1).kind() == OP_QDWPW && op(net, 2).kind() == OP_QDWPW;
-    if (front_on && chunk_env <= 0 && nimg >= front_min && front_ops) {
+    if (front_on && nimg >= front_min && front_ops) {
         if (net->profile) for (int k = 0; k < 3; ++k) DD_HIP(hipEventRecord(net->events[k], s));
         int ran = 0;
         const int rc = netq_run_front(net, op(net, 0).w, op(net, 1).w, op(net, 2).w, r.input, nimg, s, &ran);
         if (rc != DD_OK) return rc;
         if (ran) { *first_op = 3; net->op_launch[0] = OPK_FOLDED; net->op_launch[1] = OPK_FOLDED; net->op_launch[2] = OPK_Q_FRONT; }
-    }
-    if (*first_op == 0 && chunk_env > 0 && nimg > chunk_env && front_ops && op(net, 1).src() == op(net, 0).dst() && op(net, 2).src() == op(net, 1).dst()) {
-        const TensorDesc &t2 = net->tensors[op(net, 2).dst()];
-        const size_t img_out = (size_t)(t2.h + 2) * (t2.w + 2) * t2.cs;          // bordered uint8 layout: bytes per image
-        void *&out_buf = net->bufs[t2.buf];
-        void *const out_base = out_buf;
-        if (net->profile) for (int k = 0; k < 3; ++k) DD_HIP(hipEventRecord(net->events[k], s));
-        for (int c0 = 0; c0 < nimg; c0 += chunk_env) {
-            const int nc = std::min(chunk_env, nimg - c0);
-            out_buf = static_cast<char *>(out_base) + (size_t)c0 * img_out;
-            for (int k = 0; k < 3; ++k) {
-                int handled = 0;
-                const int rc = netq_run_op(net, k, op(net, k).w, r.input + (size_t)c0 * net->in_h * net->in_w * 3, nc, s, &handled);
-                if (rc != DD_OK || !handled) { out_buf = out_base; return rc != DD_OK ? rc : DD_E_ARG; }
-            }
-        }
-        out_buf = out_base;
-        *first_op = 3;
     }
     return DD_OK;
 }

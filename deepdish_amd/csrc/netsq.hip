@@ -1058,7 +1058,7 @@ __global__ __launch_bounds__((COUT / (16 * MW)) * WP * 64, (COUT / (16 * MW)) * 
         // tile; the launcher adds rows where LDS allows) are requested now and fly through both stages; the others wait for barrier A, when
         // the depthwise stage has read the rows they replace.  One tile's worth of requests in flight during the matrix stage only left HBM
         // idle half of the time.  (Measured: neutral -- with the stores or the requests removed the stride-2 blocks run in 124 / 132 us against 208 with
-        // both: they move their 829 MB at the 4.0-4.2 TB/s every streaming kernel of this network reaches, extra ring rows (DD_Q_EXTRA) change nothing.)
+        // both: they move their 829 MB at the 4.0-4.2 TB/s every streaming kernel of this network reaches, extra ring rows change nothing.)
         int lo = 0, hi = -1, e_hi = -1;
         int n2 = 0, q02 = 0, q12 = 0, ga2 = 0, gb2 = 0;
         if (t + 1 < t_end) {
@@ -1133,8 +1133,7 @@ int launch_q_dwpw(hipStream_t s, QDwpwP &P, int nimg, int device, bool *ok, bool
     int lpt = 0;
     P.tiles_per_frame = dd_ceil_div(P.hw, QTT);
     dwpw_plan(P.H, P.W, P.ho, P.wo, STRIDE, P.off_y, CIN, NT, QTT, &P.NR, &lpt);
-    static const int extra_env = dd_env_int("DD_Q_EXTRA", -1);
-    P.NR += extra_env >= 0 ? extra_env : EXTRA;                   // ring rows beyond one tile's span: the next tile's rows can be requested a stage earlier
+    P.NR += EXTRA;                                                // ring rows beyond one tile's span: the next tile's rows can be requested a stage earlier
     const int RB = (P.W + 2) * CIN;
     constexpr bool KEEP = ((CIN / 16) * (QTT / 64)) / NW <= 2;        // (as in the kernel) else the depthwise tables take LDS
     const size_t lds = (size_t)P.NR * RB + (size_t)QTT * CINP + (size_t)2 * QTT * sizeof(int) + 2 * QTT * 16 + COUT * sizeof(int) + (KEEP ? 0 : (CIN / 16) * 64 * 8 + CIN * 8);
@@ -1176,8 +1175,6 @@ int launch_q_dwpw(hipStream_t s, QDwpwP &P, int nimg, int device, bool *ok, bool
         per_cu = std::max(1, std::min(8, nb));
         per_cu_cache[device & 63].store(per_cu, std::memory_order_relaxed);
     }
-    static const int per_cu_env = dd_env_int("DD_Q_PER_CU", 0);     // experiment: fewer blocks per CU than fit
-    if (per_cu_env > 0) per_cu = std::min(per_cu, per_cu_env);
     const int n_tiles = nimg * P.tiles_per_frame;
     const int blocks = std::min(n_tiles, per_cu * 256);
     const int tpb = dd_ceil_div(n_tiles, blocks);
@@ -1651,15 +1648,9 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
                 P.hw_magic = P.wo > 1 && (long long)P.m * (P.ho * P.wo) < (1ll << 32) ? (unsigned)((1ull << 32) / (unsigned)(P.ho * P.wo)) + 1u : 0u;   // (a divisor of 1 has no 32-bit magic)
                 P.wo_magic = (unsigned)((1ull << 32) / (unsigned)P.wo) + 1u;
                 const int n_mgroups = P.n_frag_a ? P.groups_a + dd_ceil_div(P.n_mfrag - P.n_frag_a, P.mq) : dd_ceil_div(P.n_mfrag, P.mq);
-                // Pixel fragments per wave item.  Two by default; four (half the weight fetches per MFMA, twice the registers) where the launch has
-                // few wave items anyway and pixels enough -- measured per layer at 384 frames: extras 48 -> 38, 63 -> 39 us, 5x5 class predictor
-                // 23 -> 16 us, but 53 -> 65, 86 -> 95, 68 -> 78 us on the layers with 19 k+ items (b12 / b13 pointwise, 19x19 class predictor).
-                const long long items2 = (long long)n_mgroups * dd_ceil_div(P.m, 32);
-                static const int npf_env = dd_env_int("DD_Q_NPF", 0);
-                // (end of round: with the register-filter kernel on the big 1x1 layers and the k split on the small 3x3 ones, two fragments win or tie on
-                // every layer left here -- 87 -> 78 us over the eleven small layers; the rule used to be four below 8 192 items)
-                const int npf = npf_env ? npf_env : 2;
-                (void)items2;
+                // Pixel fragments per wave item: with the register-filter kernel on the big 1x1 layers and the k split on the small 3x3 ones, two
+                // win or tie against four on every layer left here (87 -> 78 us over the eleven small layers at 384 frames).
+                constexpr int npf = 2;
                 const long long n_items = (long long)n_mgroups * dd_ceil_div(P.m, 16 * npf);
                 DD_REQUIRE(n_items < (1ll << 31), DD_E_CAPACITY, "dd_net_forward: uint8 conv %d: %lld wave items", i, n_items);
                 const bool rsum = P.zwc != 0 || (P.n_frag_a && P.zwc_b != 0);
@@ -1668,13 +1659,11 @@ int netq_run_op(dd_net *net, int i, const int32_t *o, const uint8_t *input, int 
                 const bool split = split_env && P.kh * P.kw == 9 && n_items < 1024;       // (3x3: the k steps divide by the three filter rows; at 1 200 items the split costs: 40 -> 51 us)
                 const dim3 grid(split ? (unsigned)n_items : (unsigned)((n_items + 3) / 4)), block(split ? 192 : 256);
                 // (two launches of one op -- DD_Q_HEADS_ONE=0 -- report the second one's kernel and count 2 in bits 18..19)
-                *variant = QV_CONV | P.mq << 4 | (int)rsum << 7 | npf << 8 | (int)(npf != 4 && (split || pipe)) << 11 | (split ? 3 : 1) << 12 | (P.epi == QEPI_Q16N ? 1 : 0) << 14 |
+                *variant = QV_CONV | P.mq << 4 | (int)rsum << 7 | npf << 8 | (int)(split || pipe) << 11 | (split ? 3 : 1) << 12 | (P.epi == QEPI_Q16N ? 1 : 0) << 14 |
                            (P.n_frag_a ? 1 : 0) << 15 | (P.hw_magic ? 1 : 0) << 16 | (P.res ? 1 : 0) << 17 | (((*variant & 15) == QV_CONV ? (*variant >> 18 & 3) : 0) + 1) << 18;
-#define DD_QC2(MQ_, R_, N_) do { if (npf == 4 && split) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 4, false, 3, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
-                                 else if (npf == 4) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 4, false, 1, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
-                                 else if (split) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 2, true, 3, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
-                                 else if (pipe) hipLaunchKernelGGL((q_conv_k<MQ_, R_, 2, true, 1, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
-                                 else hipLaunchKernelGGL((q_conv_k<MQ_, R_, 2, false, 1, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); } while (0)
+#define DD_QC2(MQ_, R_, N_) do { if (split) hipLaunchKernelGGL((q_conv_k<MQ_, R_, npf, true, 3, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
+                                 else if (pipe) hipLaunchKernelGGL((q_conv_k<MQ_, R_, npf, true, 1, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); \
+                                 else hipLaunchKernelGGL((q_conv_k<MQ_, R_, npf, false, 1, N_>), grid, block, 0, s, P, (int)n_items, n_mgroups); } while (0)
 #define DD_QC(MQ_, N_) do { if (rsum) DD_QC2(MQ_, true, N_); else DD_QC2(MQ_, false, N_); } while (0)
                 if (P.epi == QEPI_Q16N) { if (P.mq == 3) DD_QC(3, true); else if (P.mq == 2) DD_QC(2, true); else DD_QC(1, true); }
                 else if (P.mq == 4) DD_QC(4, false); else if (P.mq == 3) DD_QC(3, false); else if (P.mq == 2) DD_QC(2, false); else DD_QC(1, false);

@@ -245,13 +245,7 @@ int dd_pipeline_create(dd_ctx *ctx, int n_streams, int frame_h, int frame_w, dd_
         if ((rc = dd_net_input_size(detector, &p->det_in, &p->det_in_w)) != DD_OK) return rc;
         p->det_kind = anchors_host ? DET_SSD : DET_YOLOV5;
         if (p->det_kind == DET_YOLOV5) { p->label_offset = 0; p->det_conf = 0.25; }          // yolov5.py:38,134
-        {   // the look-ahead detector run yields to the main stream's short kernels (see dd_ctx_create)
-            int least = 0, greatest = 0;
-            const char *e = getenv("DD_STREAM_PRIO");
-            DD_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            if (e && atoi(e) == 1 && greatest != least) DD_HIP(hipStreamCreateWithPriority(&p->det_stream, hipStreamNonBlocking, least));
-            else DD_HIP(hipStreamCreateWithFlags(&p->det_stream, hipStreamNonBlocking));
-        }
+        DD_HIP(hipStreamCreateWithFlags(&p->det_stream, hipStreamNonBlocking));
         DD_HIP(hipEventCreateWithFlags(&p->det_done, hipEventDisableTiming));
         DD_HIP(hipEventCreateWithFlags(&p->main_mark, hipEventDisableTiming));
         DD_HIP(hipEventCreateWithFlags(&p->skip_mark, hipEventDisableTiming));
