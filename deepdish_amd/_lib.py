@@ -85,6 +85,7 @@ SIGNATURES = {
     'dd_mog2_destroy': [P],
     'dd_mog2_state': [P, c_int, P, P, P, P],
     'dd_mog2_apply': [P, P, c_double, P, P, P],
+    'dd_mog2_apply_streams': [P, P, P, c_double, P, P, P],
     'dd_mask_box_count': [P, P, c_int, c_int, c_int, P, P, c_int, P, P],
     'dd_net_create': [P, P, c_int, P, c_int64, c_int, POINTER(P)],
     'dd_net_create_shared': [P, P, c_int, P, c_int64, c_int, POINTER(P)],
@@ -131,6 +132,10 @@ SIGNATURES = {
     'dd_pipeline_association': [P, c_int],
     'dd_pipeline_step': [P, P, P, P, P, P],
     'dd_pipeline_step2': [P, P, P, P, P, P, P],
+    'dd_pipeline_step3': [P, P, P, P, P, P, P, P, P],
+    'dd_pipeline_frames_seen': [P, P],
+    'dd_pipeline_present_stats': [P, P],
+    'dd_gather_frames': [P, P, c_int, c_int64, P, c_int, P, P],
     'dd_pipeline_background_subtraction': [P, c_double, c_int],
     'dd_pipeline_motion_mask': [P, P, c_int, POINTER(ctypes.c_longlong)],
     'dd_pipeline_counts': [P, P],

@@ -56,15 +56,25 @@ class BackgroundSubtractorMOG2:
         except Exception:
             pass
 
-    def apply_device(self, frames_dev, learningRate=-1, masked_out=None):
+    def apply_device(self, frames_dev, learningRate=-1, masked_out=None, present=None):
         """frames_dev: device u8 [S, H, W, 3] (torch tensor or anything with .shape/.data_ptr()).  Queues the update
-        on the context's stream and returns the device mask [S, H, W] (valid in stream order)."""
+        on the context's stream and returns the device mask [S, H, W] (valid in stream order).
+        present: None, or S values of 0 / 1 -- only those subtractors see a frame (dd_mog2_apply_streams): model, mask plane and
+        masked_out of the others stay as they are, and each stream's automatic learning rate follows its own frame count."""
         s, h, w, c = frames_dev.shape
         if (s, c) != (self.S, 3):
             raise ValueError('frames must be [%d, H, W, 3] u8, got %r' % (self.S, tuple(frames_dev.shape)))
         self._ensure(h, w)
-        check(lib().dd_mog2_apply(self._h, ptr(frames_dev), float(learningRate), ptr(self.mask),
-                                  ptr(masked_out) if masked_out is not None else None, None), 'dd_mog2_apply')
+        if present is None:
+            check(lib().dd_mog2_apply(self._h, ptr(frames_dev), float(learningRate), ptr(self.mask),
+                                      ptr(masked_out) if masked_out is not None else None, None), 'dd_mog2_apply')
+            return self.mask
+        m = np.asarray(present)
+        if m.shape != (self.S,) or not np.all((m == 0) | (m == 1)):
+            raise ValueError('present: %d values of 0 / 1, got %r' % (self.S, present))
+        m = np.ascontiguousarray(m != 0, dtype=np.uint8)
+        check(lib().dd_mog2_apply_streams(self._h, ptr(frames_dev), ptr(m), float(learningRate), ptr(self.mask),
+                                          ptr(masked_out) if masked_out is not None else None, None), 'dd_mog2_apply_streams')
         return self.mask
 
     def apply(self, image, fgmask=None, learningRate=-1):

@@ -37,11 +37,14 @@ struct Mode { float w, var, mu0, mu1, mu2; };
 
 __device__ __forceinline__ void mode_swap(Mode &a, Mode &b) { const Mode t = a; a = b; b = t; }
 
-__global__ __launch_bounds__(256) void mog2_apply_k(const Mog2P P) {
+// One entry of mog2_apply_list_k's table: a stream to advance and the three rates of ITS frame count (OpenCV counts nframes per subtractor)
+struct Mog2Entry { int stream; float alphaT, alpha1, prune; };
+
+// One pixel of stream z through one apply(): the whole arithmetic of both kernels below, so that it exists once.  g, the pixel's modes,
+// is the CALLER's array: declared in here it costs four registers (65 instead of 61) and one wave per SIMD of occupancy once the function is inlined.
+__device__ __forceinline__ void mog2_pixel(const Mog2P &P, const size_t z, const int px, const float alphaT, const float alpha1, const float prune,
+                                           Mode (&g)[NMIX]) {
 #pragma clang fp contract(off)
-    const int px = blockIdx.x * 256 + threadIdx.x;
-    if (px >= P.hw) return;
-    const size_t z = blockIdx.y;
     const size_t gp = z * (size_t)P.hw + px;
     const uint8_t *src = P.frames + gp * 3;
     const uint8_t b0 = src[0], b1 = src[1], b2 = src[2];
@@ -49,7 +52,6 @@ __global__ __launch_bounds__(256) void mog2_apply_k(const Mog2P P) {
     int nmodes = P.nm[gp];
     float4 *rec = P.rec + z * NMIX * (size_t)P.hw + px;
     float *m2 = P.m2 + z * NMIX * (size_t)P.hw + px;
-    Mode g[NMIX];
 #pragma unroll
     for (int m = 0; m < NMIX; ++m) {
         g[m] = Mode{0.f, 0.f, 0.f, 0.f, 0.f};
@@ -65,7 +67,7 @@ __global__ __launch_bounds__(256) void mog2_apply_k(const Mog2P P) {
 #pragma unroll
     for (int m = 0; m < NMIX; ++m) {
         if (m < nmodes) {                                   // nmodes shrinks inside the loop, as upstream
-            float weight = P.alpha1 * g[m].w + P.prune;
+            float weight = alpha1 * g[m].w + prune;
             int pos = m;
             if (!fits) {
                 const float var = g[m].var;
@@ -74,8 +76,8 @@ __global__ __launch_bounds__(256) void mog2_apply_k(const Mog2P P) {
                 if (total < P.TB && dist2 < P.Tb * var) background = true;
                 if (dist2 < P.Tg * var) {
                     fits = true;
-                    weight += P.alphaT;
-                    const float k = P.alphaT / weight;
+                    weight += alphaT;
+                    const float k = alphaT / weight;
                     g[m].mu0 -= k * e0; g[m].mu1 -= k * e1; g[m].mu2 -= k * e2;
                     float vn = var + k * (dist2 - var);
                     vn = vn < P.var_min ? P.var_min : vn;
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(256) void mog2_apply_k(const Mog2P P) {
                         }
                 }
             }
-            if (weight < -P.prune) { weight = 0.f; nmodes--; }
+            if (weight < -prune) { weight = 0.f; nmodes--; }
 #pragma unroll
             for (int j = 0; j <= m; ++j) if (j == pos) g[j].w = weight;
             total += weight;
@@ -100,19 +102,19 @@ __global__ __launch_bounds__(256) void mog2_apply_k(const Mog2P P) {
 #pragma unroll
     for (int m = 0; m < NMIX; ++m) if (m < nmodes) g[m].w *= inv;
 
-    if (!fits && P.alphaT > 0.f) {                          // replace the weakest mode or add one
+    if (!fits && alphaT > 0.f) {                          // replace the weakest mode or add one
         int mode;
         if (nmodes == NMIX) mode = NMIX - 1; else { mode = nmodes; nmodes++; }
 #pragma unroll
         for (int j = 0; j < NMIX; ++j) {
-            if (j == mode) g[j] = Mode{nmodes == 1 ? 1.f : P.alphaT, P.var_init, d0, d1, d2};
-            else if (nmodes != 1 && j < nmodes - 1) g[j].w *= P.alpha1;
+            if (j == mode) g[j] = Mode{nmodes == 1 ? 1.f : alphaT, P.var_init, d0, d1, d2};
+            else if (nmodes != 1 && j < nmodes - 1) g[j].w *= alpha1;
         }
         bool stop = false;
 #pragma unroll
         for (int i = NMIX - 1; i > 0; --i)
             if (i <= nmodes - 1 && !stop) {
-                if (P.alphaT < g[i - 1].w) stop = true;
+                if (alphaT < g[i - 1].w) stop = true;
                 else mode_swap(g[i], g[i - 1]);
             }
     }
@@ -158,6 +160,23 @@ __global__ __launch_bounds__(256) void mog2_apply_k(const Mog2P P) {
     }
 }
 
+__global__ __launch_bounds__(256) void mog2_apply_k(const Mog2P P) {
+    const int px = blockIdx.x * 256 + threadIdx.x;
+    if (px >= P.hw) return;
+    Mode g[NMIX];
+    mog2_pixel(P, blockIdx.y, px, P.alphaT, P.alpha1, P.prune, g);
+}
+
+// The same for the n streams of a table (grid.y = n): model, mask plane and masked frame of the listed streams only; every other
+// stream's state and planes are neither read nor written.  P.alphaT / alpha1 / prune are unused here.
+__global__ __launch_bounds__(256) void mog2_apply_list_k(const Mog2P P, const Mog2Entry *__restrict__ tab) {
+    const int px = blockIdx.x * 256 + threadIdx.x;
+    if (px >= P.hw) return;
+    const Mog2Entry e = tab[blockIdx.y];
+    Mode g[NMIX];
+    mog2_pixel(P, (size_t)e.stream, px, e.alphaT, e.alpha1, e.prune, g);
+}
+
 // np.count_nonzero(fgMask[y:y+h, x:x+w]) (deepdish.py:957), one block per box.
 __global__ __launch_bounds__(256) void mask_box_count_k(const uint8_t *__restrict__ mask, int H, int W, const int *__restrict__ boxes,
                                                         const int *__restrict__ box_stream, int *__restrict__ counts) {
@@ -184,32 +203,74 @@ struct dd_mog2 {
     int S = 0, H = 0, W = 0;
     int history = 500, detect_shadows = 1;
     float var_threshold = 16.f;
-    long long nframes = 0;
+    std::vector<long long> nframes;            // per stream: frames its model has seen (OpenCV's nframes of one subtractor)
     float4 *rec = nullptr;
     float *m2 = nullptr;
     uint8_t *nm = nullptr;
+    // mog2_apply_list_k's table: built in pinned memory, copied on the stream of the call; `tab_copied` guards the next call's rewrite
+    PinBuf h_tab;
+    DevBuf d_tab;
+    hipEvent_t tab_copied = nullptr;
+    std::vector<int> list;
 };
 
 namespace ddk {
 
-int mog2_apply(dd_mog2 *m, hipStream_t s, const uint8_t *frames, double learning_rate, uint8_t *mask, uint8_t *masked) {
-    // BackgroundSubtractorMOG2Impl::apply: ++nframes; learningRate < 0 (or first frame) -> 1 / min(2 nframes, history)
-    ++m->nframes;
-    const double lr = (learning_rate >= 0 && m->nframes > 1) ? learning_rate
-                                                              : 1.0 / (double)std::min<long long>(2 * m->nframes, m->history);
-    DD_REQUIRE(lr >= 0 && lr <= 1, DD_E_ARG, "dd_mog2_apply: learning rate %g outside [0, 1]", lr);
+// BackgroundSubtractorMOG2Impl::apply for the streams with present_host[z] != 0 (NULL: every stream): ++nframes of that stream;
+// learningRate < 0 (or its first frame) -> 1 / min(2 nframes, history).  While every stream is listed and all counts are equal this is
+// the one launch of mog2_apply_k; otherwise mog2_apply_list_k over a table of the listed streams, each with the rates of its own count.
+int mog2_apply_streams(dd_mog2 *m, hipStream_t s, const uint8_t *frames, const uint8_t *present_host, double learning_rate, uint8_t *mask,
+                       uint8_t *masked) {
+    DD_REQUIRE(!(learning_rate > 1), DD_E_ARG, "dd_mog2_apply: learning rate %g outside [0, 1]", learning_rate);
+    std::vector<int> &list = m->list;
+    list.clear();
+    for (int z = 0; z < m->S; ++z) if (!present_host || present_host[z]) list.push_back(z);
+    const int n = (int)list.size();
+    if (n == 0) return DD_OK;
+    bool uniform = n == m->S;
+    for (int z = 1; z < m->S && uniform; ++z) uniform = m->nframes[z] == m->nframes[0];
+    auto rate = [&](long long nframes) {
+        return (learning_rate >= 0 && nframes > 1) ? learning_rate : 1.0 / (double)std::min<long long>(2 * nframes, m->history);
+    };
     Mog2P P;
     P.frames = frames; P.rec = m->rec; P.m2 = m->m2; P.nm = m->nm; P.mask = mask; P.masked = masked;
     P.hw = m->H * m->W;
-    P.alphaT = (float)lr; P.alpha1 = 1.f - P.alphaT;
     const float fCT = 0.05f;
-    P.prune = -P.alphaT * fCT;
+    P.alphaT = 0.f; P.alpha1 = 1.f; P.prune = 0.f;
     P.Tb = m->var_threshold; P.TB = 0.9f; P.Tg = 3.0f * 3.0f;
     P.var_init = 15.0f; P.var_min = 4.0f; P.var_max = 5 * 15.0f; P.tau = 0.5f;
     P.detect_shadows = m->detect_shadows; P.shadow_val = 127;
-    hipLaunchKernelGGL(mog2_apply_k, dim3((unsigned)dd_ceil_div(P.hw, 256), (unsigned)m->S), dim3(256), 0, s, P);
+    const dim3 grid((unsigned)dd_ceil_div(P.hw, 256), (unsigned)n);
+    if (uniform) {
+        for (long long &c : m->nframes) ++c;
+        P.alphaT = (float)rate(m->nframes[0]); P.alpha1 = 1.f - P.alphaT;
+        P.prune = -P.alphaT * fCT;
+        hipLaunchKernelGGL(mog2_apply_k, grid, dim3(256), 0, s, P);
+        DD_LAUNCH_CHECK();
+        return DD_OK;
+    }
+    int rc;
+    if (!m->tab_copied) DD_HIP(hipEventCreateWithFlags(&m->tab_copied, hipEventDisableTiming));
+    else DD_HIP(hipEventSynchronize(m->tab_copied));          // the previous call's copy out of h_tab (long complete in a running pipeline)
+    if ((rc = m->h_tab.reserve((size_t)m->S * sizeof(Mog2Entry))) != DD_OK) return rc;
+    if ((rc = m->d_tab.reserve((size_t)m->S * sizeof(Mog2Entry))) != DD_OK) return rc;
+    Mog2Entry *h = m->h_tab.as<Mog2Entry>();
+    for (int i = 0; i < n; ++i) {
+        const int z = list[i];
+        Mog2Entry &e = h[i];
+        e.stream = z;
+        e.alphaT = (float)rate(++m->nframes[z]); e.alpha1 = 1.f - e.alphaT;
+        e.prune = -e.alphaT * fCT;
+    }
+    DD_HIP(hipMemcpyAsync(m->d_tab.p, h, (size_t)n * sizeof(Mog2Entry), hipMemcpyHostToDevice, s));
+    DD_HIP(hipEventRecord(m->tab_copied, s));
+    hipLaunchKernelGGL(mog2_apply_list_k, grid, dim3(256), 0, s, P, m->d_tab.as<Mog2Entry>());
     DD_LAUNCH_CHECK();
     return DD_OK;
+}
+
+int mog2_apply(dd_mog2 *m, hipStream_t s, const uint8_t *frames, double learning_rate, uint8_t *mask, uint8_t *masked) {
+    return mog2_apply_streams(m, s, frames, nullptr, learning_rate, mask, masked);
 }
 
 int mask_box_count(hipStream_t s, const uint8_t *mask, int H, int W, const int *d_boxes, const int *d_box_stream, int K, int *d_counts) {
@@ -232,6 +293,7 @@ int dd_mog2_create(dd_ctx *ctx, int n_streams, int height, int width, int histor
     dd_mog2 *m = new dd_mog2();
     m->ctx = ctx; m->S = n_streams; m->H = height; m->W = width;
     m->history = history; m->var_threshold = (float)var_threshold; m->detect_shadows = detect_shadows != 0;
+    m->nframes.assign(n_streams, 0);
     const size_t px = (size_t)n_streams * height * width;
     hipError_t e = hipMalloc(reinterpret_cast<void **>(&m->rec), px * NMIX * sizeof(float4));
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&m->m2), px * NMIX * sizeof(float));
@@ -251,6 +313,8 @@ int dd_mog2_create(dd_ctx *ctx, int n_streams, int height, int width, int histor
 int dd_mog2_destroy(dd_mog2 *m) {
     if (!m) return DD_OK;
     (void)hipFree(m->rec); (void)hipFree(m->m2); (void)hipFree(m->nm);
+    if (m->tab_copied) (void)hipEventDestroy(m->tab_copied);
+    m->h_tab.release(); m->d_tab.release();
     delete m;
     return DD_OK;
 }
@@ -259,6 +323,15 @@ int dd_mog2_apply(dd_mog2 *m, const uint8_t *frames, double learning_rate, uint8
     DD_REQUIRE(m && frames && mask, DD_E_ARG, "dd_mog2_apply: NULL argument");
     DD_DEVICE(m->ctx);
     return ddk::mog2_apply(m, dd_pick_stream(m->ctx, stream), frames, learning_rate, mask, masked_frames);
+}
+
+int dd_mog2_apply_streams(dd_mog2 *m, const uint8_t *frames, const uint8_t *present_host, double learning_rate, uint8_t *mask,
+                          uint8_t *masked_frames, void *stream) {
+    DD_REQUIRE(m && frames && mask, DD_E_ARG, "dd_mog2_apply_streams: NULL argument");
+    for (int z = 0; present_host && z < m->S; ++z)
+        DD_REQUIRE(present_host[z] <= 1, DD_E_ARG, "dd_mog2_apply_streams: present[%d] = %d (0 or 1)", z, (int)present_host[z]);
+    DD_DEVICE(m->ctx);
+    return ddk::mog2_apply_streams(m, dd_pick_stream(m->ctx, stream), frames, present_host, learning_rate, mask, masked_frames);
 }
 
 int dd_mog2_state(dd_mog2 *m, int stream_index, float *weight_host, float *variance_host, float *mean_host, uint8_t *nmodes_host) {

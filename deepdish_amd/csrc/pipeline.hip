@@ -19,7 +19,9 @@
 struct dd_tracker;
 struct dd_mog2;
 namespace ddk {
-int mog2_apply(dd_mog2 *m, hipStream_t s, const uint8_t *frames, double learning_rate, uint8_t *mask, uint8_t *masked);
+int mog2_apply_streams(dd_mog2 *m, hipStream_t s, const uint8_t *frames, const uint8_t *present_host, double learning_rate, uint8_t *mask,
+                       uint8_t *masked);
+int gather_frames(hipStream_t s, const uint8_t *src, long long frame_bytes, const int *d_idx, int n, uint8_t *dst);
 int mask_box_count(hipStream_t s, const uint8_t *mask, int H, int W, const int *d_boxes, const int *d_box_stream, int K, int *d_counts);
 int yolov5_decode(hipStream_t s, const float *raw, int n_rows, int n_cls, float thr, float img_w, float img_h, float *out_boxes,
                   float *out_scores, int *out_cls, int cap, int *out_n, int batch, void *scratch);
@@ -96,6 +98,8 @@ struct StreamState {
     std::vector<int> ic, keep;
     std::vector<int64_t> ints;                                       // count line: track table rows
     std::vector<double> means;
+    std::vector<double> det_tlwh;                                    // the rows that went into the tracker in this stream's last step (overlay)
+    long long seen = 0;                                              // steps this stream was present in: its own frame number
 };
 
 using ddhost::cross2;
@@ -164,10 +168,53 @@ struct dd_pipeline {
     DevBuf d_feats_skip, d_gather;             // a skip step's tracker input rows; their per-stream offsets on the device
     PinBuf h_gather;
     hipEvent_t skip_mark = nullptr;            // a skip step's main stream waits here for what the detector stream holds at step entry
+    // Presence masks (dd_pipeline_step3): a step advances the streams of `act` only -- all S of them without a mask.  Every per-step
+    // array of the step (detector output blocks, off, doff, tlwh, the tracker pointer list) is indexed by POSITION in act.
+    std::vector<int> act, act_next, det_pending_act;     // this step's streams, the look-ahead's, those of the queued detector run
+    std::vector<dd_tracker *> atrks;           // trks of act
+    DevBuf d_gframes;                          // the detector's input frames compacted (frames_gather_k): S * H * W * 3 bytes, allocated by the
+                                               // first masked step that needs them
+    // index lists for kernels on the detector stream (frames_gather_k's list, the generic adaptor's box table): a ring of pinned / device
+    // slots, each guarded by the event of its last copy -- a queued run that is discarded may still be reading the slot before
+    static constexpr int LIST_SLOTS = 4;
+    PinBuf h_lists;
+    DevBuf d_lists;
+    hipEvent_t list_copied[LIST_SLOTS] = {};
+    int list_next = 0;
+    std::vector<int> list_build;
+    long long masked_steps = 0, gather_launches = 0, streams_stepped = 0;      // dd_pipeline_present_stats
 };
 
 namespace {
 int flush_stage_events(dd_pipeline *p);
+
+// n_ints <= 8 S ints from the host to the device in the order of stream s -> where they will be.  `host` is free when this returns.
+int stage_list(dd_pipeline *p, hipStream_t s, const int *host, size_t n_ints, const int **dev) {
+    const size_t slot_ints = (size_t)p->S * 8;
+    int rc;
+    if ((rc = p->h_lists.reserve(slot_ints * dd_pipeline::LIST_SLOTS * sizeof(int))) != DD_OK) return rc;
+    if ((rc = p->d_lists.reserve(slot_ints * dd_pipeline::LIST_SLOTS * sizeof(int))) != DD_OK) return rc;
+    DD_REQUIRE(n_ints <= slot_ints, DD_E_CAPACITY, "dd_pipeline_step3: a list of %zu ints, room for %zu", n_ints, slot_ints);
+    const int k = p->list_next;
+    p->list_next = (k + 1) % dd_pipeline::LIST_SLOTS;
+    if (!p->list_copied[k]) DD_HIP(hipEventCreateWithFlags(&p->list_copied[k], hipEventDisableTiming));
+    else DD_HIP(hipEventSynchronize(p->list_copied[k]));      // four lists ago: complete unless the detector stream is that far behind
+    int *h = p->h_lists.as<int>() + k * slot_ints, *d = p->d_lists.as<int>() + k * slot_ints;
+    memcpy(h, host, n_ints * sizeof(int));
+    DD_HIP(hipMemcpyAsync(d, h, n_ints * sizeof(int), hipMemcpyHostToDevice, s));
+    DD_HIP(hipEventRecord(p->list_copied[k], s));
+    *dev = d;
+    return DD_OK;
+}
+
+// present_host (u8 [S], 0 / 1, or NULL = every stream) -> the ascending list of present streams
+int present_list(const dd_pipeline *p, const uint8_t *present_host, const char *what, std::vector<int> &act) {
+    for (int z = 0; present_host && z < p->S; ++z)
+        DD_REQUIRE(present_host[z] <= 1, DD_E_ARG, "dd_pipeline_step3: %s[%d] = %d (0 or 1)", what, z, (int)present_host[z]);
+    act.clear();
+    for (int z = 0; z < p->S; ++z) if (!present_host || present_host[z]) act.push_back(z);
+    return DD_OK;
+}
 
 int wanted_index(const dd_pipeline *p, const std::string &name) {
     for (size_t i = 0; i < p->wanted.size(); ++i) if (p->wanted[i] == name) return (int)i;
@@ -308,12 +355,13 @@ int dd_pipeline_destroy(dd_pipeline *p) {
     if (p->det_done) (void)hipEventDestroy(p->det_done);
     if (p->main_mark) (void)hipEventDestroy(p->main_mark);
     if (p->skip_mark) (void)hipEventDestroy(p->skip_mark);
+    for (hipEvent_t e : p->list_copied) if (e) (void)hipEventDestroy(e);
     for (auto &s : p->st) dd_tracker_destroy(s.trk);
     (void)hipFree(p->d_anchors);
     dd_mog2_destroy(p->mog2);
     for (DevBuf *b : {&p->d_resized, &p->d_tmp, &p->d_post, &p->d_det, &p->d_fin, &p->d_pack, &p->d_tfl_boxes, &p->d_nms, &p->d_crop, &p->d_patches, &p->d_feats,
-                      &p->d_mask, &p->d_masked, &p->d_mbox, &p->d_feats_skip, &p->d_gather}) b->release();
-    for (PinBuf *b : {&p->h_fin, &p->h_nms, &p->h_crop, &p->h_mbox, &p->h_gather}) b->release();
+                      &p->d_mask, &p->d_masked, &p->d_mbox, &p->d_feats_skip, &p->d_gather, &p->d_gframes, &p->d_lists}) b->release();
+    for (PinBuf *b : {&p->h_fin, &p->h_nms, &p->h_crop, &p->h_mbox, &p->h_gather, &p->h_lists}) b->release();
     delete p;
     return DD_OK;
 }
@@ -499,8 +547,20 @@ int dd_pipeline_detections(dd_pipeline *p, int stream, double *boxes_host, doubl
     return DD_OK;
 }
 
+int dd_pipeline_frames_seen(dd_pipeline *p, int64_t *seen_host) {
+    DD_REQUIRE(p && seen_host, DD_E_ARG, "dd_pipeline_frames_seen: NULL argument");
+    for (int z = 0; z < p->S; ++z) seen_host[z] = p->st[z].seen;
+    return DD_OK;
+}
+
+int dd_pipeline_present_stats(dd_pipeline *p, long long *out3_host) {
+    DD_REQUIRE(p && out3_host, DD_E_ARG, "dd_pipeline_present_stats: NULL argument");
+    out3_host[0] = p->masked_steps; out3_host[1] = p->gather_launches; out3_host[2] = p->streams_stepped;
+    return DD_OK;
+}
+
 // The overlay elements of the last step, read off the state the step left: the tracker's host mirror, StreamState::db and votes, the
-// tracker input rows (tlwh, doff) and the counters.  Nothing here is kept by the step for this call's sake.
+// tracker input rows (StreamState::det_tlwh) and the counters.  A stream absent from the last step shows its own last step.
 int dd_pipeline_overlay(dd_pipeline *p, const int *streams_host, int n, int *sizes_host, const int *caps_host, int64_t *track_ints_host,
                         double *track_tlbr_host, double *points_host, double *cross_host, double *det_tlbr_host, int64_t *counts_host,
                         double *line_host) {
@@ -509,20 +569,20 @@ int dd_pipeline_overlay(dd_pipeline *p, const int *streams_host, int n, int *siz
         DD_REQUIRE(streams_host[i] >= 0 && streams_host[i] < p->S, DD_E_ARG, "dd_pipeline_overlay: stream %d of %d", streams_host[i], p->S);
     const bool fill = track_ints_host && track_tlbr_host && points_host && cross_host && det_tlbr_host && counts_host && line_host;
     DD_REQUIRE(!fill || caps_host, DD_E_ARG, "dd_pipeline_overlay: arrays without their capacities");
-    const bool stepped = p->steps > 0 && (int)p->doff.size() == p->S + 1;
     size_t nt = 0, np = 0, nc = 0, nd = 0;
     std::vector<int64_t> ints;
     std::vector<double> means;
     for (int i = 0; i < n; ++i) {
         const int z = streams_host[i];
         StreamState &st = p->st[z];
+        const bool stepped = st.seen > 0;
         int nl = 0, rc;
         if ((rc = dd_tracker_count(st.trk, 0, &nl)) != DD_OK) return rc;
         ints.resize((size_t)nl * 6); means.resize((size_t)nl * 8);
         if (nl && stepped && (rc = ddk::tracker_read_host(st.trk, 0, ints.data(), means.data())) != DD_OK) return rc;
         int *sz = sizes_host + (size_t)i * 4;
         sz[0] = sz[1] = sz[2] = 0;
-        sz[3] = stepped ? p->doff[z + 1] - p->doff[z] : 0;
+        sz[3] = (int)(st.det_tlwh.size() / 4);
         for (int k = 0; stepped && k < nl; ++k) {
             const int64_t *r = ints.data() + (size_t)k * 6;
             if (r[1] != CONFIRMED || r[2] > 1) continue;                // deepdish.py:1053
@@ -558,7 +618,7 @@ int dd_pipeline_overlay(dd_pipeline *p, const int *streams_host, int n, int *siz
         if (fill) {
             DD_REQUIRE(nd + sz[3] <= (size_t)caps_host[3], DD_E_CAPACITY, "dd_pipeline_overlay: more detections than the array has room for");
             for (int j = 0; j < sz[3]; ++j) {                            // detection.py to_tlbr
-                const double *b = p->tlwh.data() + (size_t)(p->doff[z] + j) * 4;
+                const double *b = st.det_tlwh.data() + (size_t)j * 4;
                 double *o = det_tlbr_host + (nd + j) * 4;
                 o[0] = b[0]; o[1] = b[1]; o[2] = b[0] + b[2]; o[3] = b[1] + b[3];
             }
@@ -606,88 +666,112 @@ static const bool g_stage_events = !(getenv("DD_STAGE_EVENTS") && atoi(getenv("D
 #define DD_STAGE_END(k) do { if (g_stage_events) { DD_HIP(hipEventRecord(p->ev_main[2 * (k) + 1], s)); p->ev_pair[k] = true; } } while (0)
 #define DD_TIMED_WAIT(expr) do { const double w0_ = now_s(); DD_HIP(expr); p->step_wait += now_s() - w0_; } while (0)
 
-int enqueue_detector(dd_pipeline *p, const uint8_t *frames) {
+// `act`: the streams whose frames the run takes, ascending (dd_pipeline_step3's present streams; all S of them without a mask).  The
+// batch is n = act.size(): every block of the run's output is indexed by POSITION in act.  With n < S the resize launches, which take a
+// dense batch, read the n frames compacted into d_gframes by one frames_gather_k launch; the generic adaptor's crop_resize carries a
+// stream index per box, so its box table is built over act instead.
+int enqueue_detector(dd_pipeline *p, const uint8_t *frames, const std::vector<int> &act) {
     hipStream_t s = p->det_stream;
-    const int S = p->S, MAX_DET = p->max_det;
+    const int n = (int)act.size(), MAX_DET = p->max_det;
     int rc;
+    const uint8_t *src = frames;               // what the resize reads: n dense frames
+    const int *d_tfl = p->d_tfl_boxes.as<int>(), *d_idx_gather = nullptr;
+    if (n < p->S && p->det_kind == DET_TFLITE) {
+        std::vector<int> &hb = p->list_build;
+        hb.assign((size_t)n * 8, 0);
+        for (int i = 0; i < n; ++i) { int *b = hb.data() + (size_t)i * 8; b[2] = p->W; b[3] = p->H; b[4] = act[i]; b[6] = 1; }   // whole frame, swap_rb
+        if ((rc = stage_list(p, s, hb.data(), hb.size(), &d_tfl)) != DD_OK) return rc;
+    } else if (n < p->S) {
+        const size_t frame_bytes = (size_t)p->H * p->W * 3;
+        if (!p->d_gframes.p) {                 // the first masked step that needs it: S frames, exactly (DevBuf::reserve would add a quarter)
+            DD_HIP(hipMalloc(&p->d_gframes.p, (size_t)p->S * frame_bytes));
+            p->d_gframes.cap = (size_t)p->S * frame_bytes;
+        }
+        if ((rc = stage_list(p, s, act.data(), act.size(), &d_idx_gather)) != DD_OK) return rc;
+        src = p->d_gframes.as<uint8_t>();
+    }
     // order after whatever the caller has queued on the main stream so far (e.g. the ingest ring's wait for the
     // upload of these frames)
     DD_HIP(hipEventRecord(p->main_mark, p->ctx->stream));
     DD_HIP(hipStreamWaitEvent(s, p->main_mark, 0));
     if (g_stage_events) DD_HIP(hipEventRecord(p->ev_det[0], s));
+    if (src != frames) {
+        if ((rc = ddk::gather_frames(s, frames, (long long)p->H * p->W * 3, d_idx_gather, n, p->d_gframes.as<uint8_t>())) != DD_OK) return rc;
+        p->gather_launches += 1;
+    }
     if (p->det_kind == DET_TFLITE) {                           // tflite_object_detector.py:207-211: cv2.resize (INTER_LINEAR) of the RGB frame
-        if ((rc = ddk::crop_resize(s, frames, p->H, p->W, p->d_tfl_boxes.p, S, p->det_in, p->det_in_w, p->d_resized.as<uint8_t>())) != DD_OK) return rc;
-    } else if (p->letterbox_pad >= 0) {                        // dd_pipeline_detector_letterbox: d_tmp holds S * H * det_in_w * 3 >= S * H * new_w * 3 bytes
-        if ((rc = ddk::resize_lanczos_letterbox(s, p->ctx->device, frames, S, p->H, p->W, 3, 1, p->d_resized.as<uint8_t>(), p->det_in, p->det_in_w,
+        if ((rc = ddk::crop_resize(s, frames, p->H, p->W, d_tfl, n, p->det_in, p->det_in_w, p->d_resized.as<uint8_t>())) != DD_OK) return rc;
+    } else if (p->letterbox_pad >= 0) {                        // dd_pipeline_detector_letterbox: d_tmp holds n * H * det_in_w * 3 >= n * H * new_w * 3 bytes
+        if ((rc = ddk::resize_lanczos_letterbox(s, p->ctx->device, src, n, p->H, p->W, 3, 1, p->d_resized.as<uint8_t>(), p->det_in, p->det_in_w,
                                                 p->letterbox_pad, p->d_tmp.as<uint8_t>())) != DD_OK) return rc;
-    } else if ((rc = ddk::resize_lanczos(s, p->ctx->device, frames, p->H, p->W, 3, 1, p->d_resized.as<uint8_t>(), p->det_in,
-                                         p->det_in_w, p->d_tmp.as<uint8_t>(), S)) != DD_OK) return rc;    // ssd_mobilenet.py:54-57, yolov5.py:99
-    if ((rc = dd_net_forward(p->det, p->d_resized.as<uint8_t>(), S, s)) != DD_OK) return rc;       // :102-103 / yolov5.py:107-109
+    } else if ((rc = ddk::resize_lanczos(s, p->ctx->device, src, p->H, p->W, 3, 1, p->d_resized.as<uint8_t>(), p->det_in,
+                                         p->det_in_w, p->d_tmp.as<uint8_t>(), n)) != DD_OK) return rc;    // ssd_mobilenet.py:54-57, yolov5.py:99
+    if ((rc = dd_net_forward(p->det, p->d_resized.as<uint8_t>(), n, s)) != DD_OK) return rc;       // :102-103 / yolov5.py:107-109
     void *raw = nullptr;
     if ((rc = dd_net_output(p->det, -1, &raw, nullptr, nullptr, nullptr, nullptr, nullptr)) != DD_OK) return rc;
     if (p->det_kind == DET_YOLOV5) {                                                               // yolov5.py:120-131
         const size_t cap = (size_t)p->n_anchors;
-        float *yb = p->d_fin.as<float>(), *ys = yb + S * cap * 4;
-        int *yc = reinterpret_cast<int *>(ys + S * cap), *yn = yc + S * cap;
+        float *yb = p->d_fin.as<float>(), *ys = yb + n * cap * 4;
+        int *yc = reinterpret_cast<int *>(ys + n * cap), *yn = yc + n * cap;
         if (p->yolo_dec) {                                       // :126-128 ran in the Detect layers' epilogues
             float *b4 = nullptr, *cf = nullptr; int *cl = nullptr;
             if ((rc = dd_net_yolo_decoded(p->det, &b4, &cf, &cl, nullptr)) != DD_OK) return rc;
             if (p->letterbox_pad >= 0) {
                 if ((rc = ddk::yolov5_select_letterbox(s, b4, cf, cl, p->n_anchors, (float)p->det_conf, p->W, p->H, p->det_in_w, p->det_in, yb, ys, yc,
-                                                       p->n_anchors, yn, S)) != DD_OK) return rc;
+                                                       p->n_anchors, yn, n)) != DD_OK) return rc;
             } else
             if ((rc = ddk::yolov5_select(s, b4, cf, cl, p->n_anchors, (float)p->det_conf, (float)p->W, (float)p->H, yb, ys, yc,
-                                         p->n_anchors, yn, S)) != DD_OK) return rc;
+                                         p->n_anchors, yn, n)) != DD_OK) return rc;
         } else if (p->letterbox_pad >= 0) {
             if ((rc = ddk::yolov5_decode_letterbox(s, static_cast<const float *>(raw), p->n_anchors, p->n_classes, (float)p->det_conf, p->W, p->H,
-                                                   p->det_in_w, p->det_in, yb, ys, yc, p->n_anchors, yn, S, p->d_post.p)) != DD_OK) return rc;
+                                                   p->det_in_w, p->det_in, yb, ys, yc, p->n_anchors, yn, n, p->d_post.p)) != DD_OK) return rc;
         } else
         if ((rc = ddk::yolov5_decode(s, static_cast<const float *>(raw), p->n_anchors, p->n_classes, (float)p->det_conf, (float)p->W,
-                                     (float)p->H, yb, ys, yc, p->n_anchors, yn, S, p->d_post.p)) != DD_OK) return rc;
-        // the passing rows of all streams packed behind one another; the host block is [S counts | pad to 64 B | rows x 24 B]: the
+                                     (float)p->H, yb, ys, yc, p->n_anchors, yn, n, p->d_post.p)) != DD_OK) return rc;
+        // the passing rows of all streams packed behind one another; the host block is [n counts | pad to 64 B | rows x 24 B]: the
         // counts and the first yolo_host_rows rows now, whatever lies beyond them when the step consumes the block
-        if ((rc = ddk::yolov5_pack(s, yb, ys, yc, yn, p->n_anchors, S, p->d_pack.as<float>())) != DD_OK) return rc;
-        const size_t head = ((size_t)S * 4 + 63) / 64 * 64;
-        DD_HIP(hipMemcpyAsync(p->h_fin.p, yn, (size_t)S * 4, hipMemcpyDeviceToHost, s));
+        if ((rc = ddk::yolov5_pack(s, yb, ys, yc, yn, p->n_anchors, n, p->d_pack.as<float>())) != DD_OK) return rc;
+        const size_t head = ((size_t)n * 4 + 63) / 64 * 64;
+        DD_HIP(hipMemcpyAsync(p->h_fin.p, yn, (size_t)n * 4, hipMemcpyDeviceToHost, s));
         DD_HIP(hipMemcpyAsync(p->h_fin.as<char>() + head, p->d_pack.p, p->yolo_host_rows * 24, hipMemcpyDeviceToHost, s));
         if (g_stage_events) DD_HIP(hipEventRecord(p->ev_det[1], s));
         DD_HIP(hipEventRecord(p->det_done, s));
-        p->det_pending = frames;
+        p->det_pending = frames; p->det_pending_act = act;
         return DD_OK;
     }
-    float *db = p->d_det.as<float>(), *dc = db + (size_t)S * MAX_DET * 4, *ds = dc + (size_t)S * MAX_DET;
-    int *dn = reinterpret_cast<int *>(ds + (size_t)S * MAX_DET);
+    float *db = p->d_det.as<float>(), *dc = db + (size_t)n * MAX_DET * 4, *ds = dc + (size_t)n * MAX_DET;
+    int *dn = reinterpret_cast<int *>(ds + (size_t)n * MAX_DET);
     if (p->ssd_per_class > 0) {                                 // use_regular_nms = true: per-class NMS, straight from the head
         if (p->q8.cls) rc = ddk::ssd_regular_nms_u8(s, p->q8.box, p->q8.cls, p->q8.stride, p->q8.lut, p->q8.quant, p->d_anchors, p->n_anchors, p->n_classes,
-                                                    MAX_DET, p->ssd_per_class, p->ssd_score_thr, p->ssd_iou_thr, db, dc, ds, dn, S);
+                                                    MAX_DET, p->ssd_per_class, p->ssd_score_thr, p->ssd_iou_thr, db, dc, ds, dn, n);
         else rc = ddk::ssd_regular_nms_raw(s, static_cast<const float *>(raw), p->d_anchors, p->n_anchors, p->n_classes, MAX_DET, p->ssd_per_class,
-                                           p->ssd_score_thr, p->ssd_iou_thr, db, dc, ds, dn, S);
+                                           p->ssd_score_thr, p->ssd_iou_thr, db, dc, ds, dn, n);
         if (rc != DD_OK) return rc;
     } else if (p->ssd_dec) {
         float *eb = nullptr, *es = nullptr, *ek = nullptr;
         int *ec = nullptr;
         if ((rc = dd_net_ssd_decoded(p->det, &eb, &es, &ec, &ek)) != DD_OK) return rc;
-        if ((rc = ddk::ssd_postprocess_decoded(s, eb, es, ec, ek, p->n_anchors, MAX_DET, p->ssd_score_thr, p->ssd_iou_thr, db, dc, ds, dn, S,
+        if ((rc = ddk::ssd_postprocess_decoded(s, eb, es, ec, ek, p->n_anchors, MAX_DET, p->ssd_score_thr, p->ssd_iou_thr, db, dc, ds, dn, n,
                                                p->d_post.p, p->d_post.cap)) != DD_OK) return rc;
     } else if ((rc = ddk::ssd_postprocess(s, static_cast<const float *>(raw), p->d_anchors, p->n_anchors, p->n_classes, MAX_DET,
-                                          p->ssd_score_thr, p->ssd_iou_thr, db, dc, ds, dn, S, p->d_post.p, p->d_post.cap)) != DD_OK) return rc;
+                                          p->ssd_score_thr, p->ssd_iou_thr, db, dc, ds, dn, n, p->d_post.p, p->d_post.cap)) != DD_OK) return rc;
     if (p->det_kind == DET_TFLITE) {                           // the generic adaptor's tail is a few integer truncations: on the host (step2)
-        const size_t dbytes = (size_t)S * MAX_DET * 6 * sizeof(float) + (size_t)S * sizeof(int);
+        const size_t dbytes = (size_t)n * MAX_DET * 6 * sizeof(float) + (size_t)n * sizeof(int);
         DD_HIP(hipMemcpyAsync(p->h_fin.p, p->d_det.p, dbytes, hipMemcpyDeviceToHost, s));
         if (g_stage_events) DD_HIP(hipEventRecord(p->ev_det[1], s));
         DD_HIP(hipEventRecord(p->det_done, s));
-        p->det_pending = frames;
+        p->det_pending = frames; p->det_pending_act = act;
         return DD_OK;
     }
-    double *fb = p->d_fin.as<double>(), *fs = fb + (size_t)S * MAX_DET * 4;
-    int *fc = reinterpret_cast<int *>(fs + (size_t)S * MAX_DET), *fn = fc + (size_t)S * MAX_DET;
-    if ((rc = ddk::ssd_finish(s, db, dc, ds, S, MAX_DET, p->det_conf, 0.5, (double)p->W, (double)p->H, fb, fc, fs, fn)) != DD_OK)
+    double *fb = p->d_fin.as<double>(), *fs = fb + (size_t)n * MAX_DET * 4;
+    int *fc = reinterpret_cast<int *>(fs + (size_t)n * MAX_DET), *fn = fc + (size_t)n * MAX_DET;
+    if ((rc = ddk::ssd_finish(s, db, dc, ds, n, MAX_DET, p->det_conf, 0.5, (double)p->W, (double)p->H, fb, fc, fs, fn)) != DD_OK)
         return rc;                                                                                    // :111-150
-    const size_t fbytes = (size_t)S * (MAX_DET * (4 * 8 + 8 + 4) + 4);
+    const size_t fbytes = (size_t)n * (MAX_DET * (4 * 8 + 8 + 4) + 4);
     DD_HIP(hipMemcpyAsync(p->h_fin.p, p->d_fin.p, fbytes, hipMemcpyDeviceToHost, s));
     if (g_stage_events) DD_HIP(hipEventRecord(p->ev_det[1], s));
     DD_HIP(hipEventRecord(p->det_done, s));
-    p->det_pending = frames;
+    p->det_pending = frames; p->det_pending_act = act;
     return DD_OK;
 }
 
@@ -780,23 +864,54 @@ extern "C" {
 // frames_next is queued only when the next step is a detector step.
 int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames, const uint8_t *frames_next, const double *inj_boxes_host,
                       const double *inj_scores_host, const int *inj_cls_host, const int *inj_offsets_host);
+// The same step for the streams with present_host[z] != 0 only (u8 [S]; NULL = every stream): for the others this step does not exist --
+// no predict, no update, no count-line pass, no vote, no MOG2 update, nothing of their frame slot or injected rows read, nothing of
+// their state written.  present_next_host belongs to frames_next.  The queued look-ahead run remembers its stream list: a next step
+// that arrives with other frames or another list discards it and runs the detector itself, with the same result.
+int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames, const uint8_t *present_host, const uint8_t *frames_next,
+                      const uint8_t *present_next_host, const double *inj_boxes_host, const double *inj_scores_host,
+                      const int *inj_cls_host, const int *inj_offsets_host);
 
 int dd_pipeline_step(dd_pipeline *p, const uint8_t *frames, const double *inj_boxes_host, const double *inj_scores_host,
                      const int *inj_cls_host, const int *inj_offsets_host) {
     return dd_pipeline_step2(p, frames, nullptr, inj_boxes_host, inj_scores_host, inj_cls_host, inj_offsets_host);
 }
 
-int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *frames_next, const double *inj_boxes_host,
+int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames, const uint8_t *frames_next, const double *inj_boxes_host,
                       const double *inj_scores_host, const int *inj_cls_host, const int *inj_offsets_host) {
+    return dd_pipeline_step3(p, frames, nullptr, frames_next, nullptr, inj_boxes_host, inj_scores_host, inj_cls_host, inj_offsets_host);
+}
+
+int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *present_host, const uint8_t *frames_next,
+                      const uint8_t *present_next_host, const double *inj_boxes_host, const double *inj_scores_host,
+                      const int *inj_cls_host, const int *inj_offsets_host) {
     DD_REQUIRE(p && frames_in, DD_E_ARG, "dd_pipeline_step: NULL argument");
     DD_REQUIRE(frames_next != frames_in, DD_E_ARG,
                "dd_pipeline_step2: frames_next must be a different buffer from frames (its detector run is queued while "
                "this step still reads frames, and the next step consumes it by address)");
+    DD_REQUIRE(!present_next_host || frames_next, DD_E_ARG, "dd_pipeline_step3: present_next without frames_next");
+    // the skip phase is one counter per pipeline; under masks it would have to be one per stream
+    DD_REQUIRE(!(present_host || present_next_host) || p->skip_n <= 0, DD_E_STATE,
+               "dd_pipeline_step3: a presence mask on a pipeline with object_detector_skip_frames set (dd_pipeline_detector_skip_frames)");
+    int rc;
+    const std::vector<int> &act = p->act, &act_next = p->act_next;
+    if ((rc = present_list(p, present_host, "present", p->act)) != DD_OK) return rc;
+    if ((rc = present_list(p, present_next_host, "present_next", p->act_next)) != DD_OK) return rc;
     DD_DEVICE(p->ctx);
     const uint8_t *frames = frames_in;
     hipStream_t s = p->ctx->stream;
-    const int S = p->S, MAX_DET = p->max_det;
-    int rc;
+    const int S = p->S, n = (int)act.size(), MAX_DET = p->max_det;
+    p->masked_steps += present_host != nullptr;
+    p->streams_stepped += n;
+    if (n == 0) {                                  // a legal step: nothing is launched and no state changes (a queued look-ahead run was
+        p->det_pending = nullptr;                  // announced for other streams than arrived: dropped)
+        p->steps += 1;
+        return DD_OK;
+    }
+    if (act_next.empty()) frames_next = nullptr;
+    std::vector<dd_tracker *> &atrks = p->atrks;
+    atrks.resize(n);
+    for (int i = 0; i < n; ++i) atrks[i] = p->trks[act[i]];
     if ((rc = flush_stage_events(p)) != DD_OK) return rc;
     // deepdish.py:929-938: the first step detects; then N skip steps follow every detector step
     const bool skip = p->skip_rem > 0 && p->steps > 0;
@@ -811,11 +926,11 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
         DD_HIP(hipStreamWaitEvent(s, p->skip_mark, 0));
     }
     DD_STAGE_BEGIN(0);
-    if ((rc = ddk::trackers_predict(p->trks.data(), S)) != DD_OK) return rc;            // deepdish.py:1028
+    if ((rc = ddk::trackers_predict(atrks.data(), n)) != DD_OK) return rc;              // deepdish.py:1028
     DD_STAGE_END(0);
     if (p->mog2) {                                                                      // :920-924
-        if ((rc = ddk::mog2_apply(p->mog2, s, frames_in, -1.0, p->d_mask.as<uint8_t>(),
-                                  p->bg_masking ? p->d_masked.as<uint8_t>() : nullptr)) != DD_OK) return rc;
+        if ((rc = ddk::mog2_apply_streams(p->mog2, s, frames_in, present_host, -1.0, p->d_mask.as<uint8_t>(),
+                                          p->bg_masking ? p->d_masked.as<uint8_t>() : nullptr)) != DD_OK) return rc;
         if (p->bg_masking) { frames = p->d_masked.as<uint8_t>(); frames_next = nullptr; p->det_pending = nullptr; }
     }
 
@@ -825,9 +940,9 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
     std::vector<StreamState> &st = p->st;
     if (skip) {
         // every stream keeps the adaptor output of the last detector step; the early look-ahead form queues the next frames here
-        if (p->det && frames_next && !p->det_late && (rc = enqueue_detector(p, frames_next)) != DD_OK) return rc;
+        if (p->det && frames_next && !p->det_late && (rc = enqueue_detector(p, frames_next, act_next)) != DD_OK) return rc;
     } else if (p->det) {
-        if (p->det_pending != frames && (rc = enqueue_detector(p, frames)) != DD_OK) return rc;       // not queued ahead: run it now
+        if ((p->det_pending != frames || p->det_pending_act != act) && (rc = enqueue_detector(p, frames, act)) != DD_OK) return rc;   // not queued ahead (or for other streams): run it now
         DD_TIMED_WAIT(hipEventSynchronize(p->det_done));                                               // round trip 1
         p->det_pending = nullptr;
         if (g_stage_events) {   // the detector chain of these frames on its stream: resize, forward, post-process, adaptor tail, host copy
@@ -836,13 +951,13 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
             p->g_det += (double)ms;
         }
         if (p->det_kind == DET_YOLOV5) {
-            const size_t head = ((size_t)S * 4 + 63) / 64 * 64;
+            const size_t head = ((size_t)n * 4 + 63) / 64 * 64;
             const int *yn = p->h_fin.as<int>();
             std::vector<size_t> &ybase = p->ybase;
-            ybase.assign(S + 1, 0);
-            for (int z = 0; z < S; ++z) ybase[z + 1] = ybase[z] + (size_t)std::min(yn[z], p->n_anchors);
-            if (ybase[S] > p->yolo_host_rows) {                    // a busy step: fetch the rest (the detector stream is idle here) and
-                const size_t have = p->yolo_host_rows, total = ybase[S];      // make room for twice as many from now on
+            ybase.assign(n + 1, 0);
+            for (int i = 0; i < n; ++i) ybase[i + 1] = ybase[i] + (size_t)std::min(yn[i], p->n_anchors);
+            if (ybase[n] > p->yolo_host_rows) {                    // a busy step: fetch the rest (the detector stream is idle here) and
+                const size_t have = p->yolo_host_rows, total = ybase[n];      // make room for twice as many from now on
                 // ... but never more than the packed block holds (S * n_anchors rows): the first copy of every later step reads that many
                 const size_t grown = std::min(2 * total, (size_t)S * (size_t)p->n_anchors);
                 PinBuf bigger;
@@ -858,13 +973,13 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
                 yn = p->h_fin.as<int>();
             }
             const float *rows = reinterpret_cast<const float *>(p->h_fin.as<char>() + head);
-            ddk::parallel_for(S, GRAIN, [&](int z0, int z1) {
-                for (int z = z0; z < z1; ++z) {
-                    StreamState &q = st[z];
+            ddk::parallel_for(n, GRAIN, [&](int i0, int i1) {
+                for (int i = i0; i < i1; ++i) {
+                    StreamState &q = st[act[i]];
                     q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
-                    const int n = (int)(ybase[z + 1] - ybase[z]);
-                    for (int i = 0; i < n; ++i) {                                                      // yolov5.py:137-145
-                        const float *b = rows + (ybase[z] + i) * 6;
+                    const int nr = (int)(ybase[i + 1] - ybase[i]);
+                    for (int r = 0; r < nr; ++r) {                                                     // yolov5.py:137-145
+                        const float *b = rows + (ybase[i] + r) * 6;
                         int c;
                         memcpy(&c, b + 5, 4);
                         const float sc = b[4];
@@ -878,17 +993,18 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
         } else if (p->det_kind == DET_TFLITE) {
             // tflite_object_detector.py:234-295 (_postprocess) + tools/tflite.py:26-41: score >= threshold, int() of the scaled
             // corners (f32 arithmetic, truncation), label = label_list[class], stable sort by descending score, wanted labels only
-            const float *hb = p->h_fin.as<float>(), *hc = hb + (size_t)S * MAX_DET * 4, *hs = hc + (size_t)S * MAX_DET;
-            const int *hn = reinterpret_cast<const int *>(hs + (size_t)S * MAX_DET);
-            ddk::parallel_for(S, GRAIN, [&](int z0, int z1) {
+            // (the run's blocks hold n = act.size() frames: z below is the POSITION of a stream in act)
+            const float *hb = p->h_fin.as<float>(), *hc = hb + (size_t)n * MAX_DET * 4, *hs = hc + (size_t)n * MAX_DET;
+            const int *hn = reinterpret_cast<const int *>(hs + (size_t)n * MAX_DET);
+            ddk::parallel_for(n, GRAIN, [&](int z0, int z1) {
                 for (int z = z0; z < z1; ++z) {
-                    StreamState &q = st[z];
+                    StreamState &q = st[act[z]];
                     q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
-                    int order[MAX_DET_CAP], n = 0;
+                    int order[MAX_DET_CAP], no = 0;
                     for (int i = 0; i < hn[z] && i < MAX_DET; ++i)
-                        if ((double)hs[z * MAX_DET + i] >= p->det_conf) order[n++] = i;      // np.float32 >= python float: compared in float64
-                    std::stable_sort(order, order + n, [&](int a, int b) { return hs[z * MAX_DET + a] > hs[z * MAX_DET + b]; });
-                    for (int k = 0; k < n; ++k) {
+                        if ((double)hs[z * MAX_DET + i] >= p->det_conf) order[no++] = i;     // np.float32 >= python float: compared in float64
+                    std::stable_sort(order, order + no, [&](int a, int b) { return hs[z * MAX_DET + a] > hs[z * MAX_DET + b]; });
+                    for (int k = 0; k < no; ++k) {
                         const int i = order[k], c = (int)hc[z * MAX_DET + i];
                         if (c < 0 || c >= (int)p->tfl_labels.size() || wanted_index(p, p->tfl_labels[c]) < 0) continue;
                         // the class stored for the vote is resolved through class_name() = labels[c + label_offset]: the same line of the
@@ -907,11 +1023,11 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
                 }
             });
         } else {
-            const double *hb = p->h_fin.as<double>(), *hs = hb + (size_t)S * MAX_DET * 4;
-            const int *hc = reinterpret_cast<const int *>(hs + (size_t)S * MAX_DET), *hn = hc + (size_t)S * MAX_DET;
-            ddk::parallel_for(S, GRAIN, [&](int z0, int z1) {
+            const double *hb = p->h_fin.as<double>(), *hs = hb + (size_t)n * MAX_DET * 4;       // (z: position in act, as above)
+            const int *hc = reinterpret_cast<const int *>(hs + (size_t)n * MAX_DET), *hn = hc + (size_t)n * MAX_DET;
+            ddk::parallel_for(n, GRAIN, [&](int z0, int z1) {
                 for (int z = z0; z < z1; ++z) {
-                    StreamState &q = st[z];
+                    StreamState &q = st[act[z]];
                     q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
                     for (int i = 0; i < hn[z]; ++i) {                                                  // :204-212
                         const double sc = hs[z * MAX_DET + i];
@@ -925,19 +1041,21 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
             });
         }
         // the host block has been consumed: the detector buffers are free for the next frames
-        if (frames_next && !p->det_late && (rc = enqueue_detector(p, frames_next)) != DD_OK) return rc;
+        if (frames_next && !p->det_late && (rc = enqueue_detector(p, frames_next, act_next)) != DD_OK) return rc;
     } else {
-        for (auto &q : st) { q.boxes0.clear(); q.scores0.clear(); q.cls0.clear(); }
+        for (int z : act) { StreamState &q = st[z]; q.boxes0.clear(); q.scores0.clear(); q.cls0.clear(); }
     }
     if (inj_offsets_host)
         DD_REQUIRE(inj_boxes_host && inj_scores_host && inj_cls_host, DD_E_ARG, "dd_pipeline_step: injected arrays missing");
     const double t1 = now_s();
 
     // ---------------- box hygiene (deepdish.py:940-960, background subtraction off) + batched NMS (:995)
+    // (from here on i is a position in act and z = act[i] the stream: off, doff, tlwh, keep counts and the NMS problems are per position)
     std::vector<int> &off = p->off;
-    off.assign(S + 1, 0);
-    ddk::parallel_for(S, GRAIN, [&](int z0, int z1) {
-        for (int z = z0; z < z1; ++z) {
+    off.assign(n + 1, 0);
+    ddk::parallel_for(n, GRAIN, [&](int i0, int i1) {
+        for (int i = i0; i < i1; ++i) {
+            const int z = act[i];
             StreamState &q = st[z];
             if (inj_offsets_host && !skip) {
                 const int a = inj_offsets_host[z], b = inj_offsets_host[z + 1];
@@ -949,56 +1067,58 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
             ddhost::clean_boxes(q.boxes0, q.scores0, q.cls0, p->W, p->H, q.ib, q.is, q.ic);
         }
     });
-    for (int z = 0; z < S; ++z) off[z + 1] = off[z] + (int)st[z].is.size();
-    if (p->mog2 && off[S] > 0) {                                                        // :957 motion test on every candidate
-        const int K0 = off[S];
+    for (int i = 0; i < n; ++i) off[i + 1] = off[i] + (int)st[act[i]].is.size();
+    if (p->mog2 && off[n] > 0) {                                                        // :957 motion test on every candidate
+        const int K0 = off[n];
         const size_t in_bytes = (size_t)K0 * 5 * sizeof(int), all_bytes = in_bytes + (size_t)K0 * sizeof(int);
         if ((rc = p->h_mbox.reserve(all_bytes)) != DD_OK) return rc;
         if ((rc = p->d_mbox.reserve(all_bytes)) != DD_OK) return rc;
         int *hm = p->h_mbox.as<int>(), *dm = p->d_mbox.as<int>();
-        for (int z = 0; z < S; ++z)
-            for (size_t i = 0; i < st[z].is.size(); ++i) {
-                for (int q = 0; q < 4; ++q) hm[(size_t)(off[z] + i) * 4 + q] = (int)st[z].ib[i * 4 + q];
-                hm[(size_t)K0 * 4 + off[z] + i] = z;
+        for (int i = 0; i < n; ++i) {
+            const StreamState &q = st[act[i]];
+            for (size_t k = 0; k < q.is.size(); ++k) {
+                for (int c = 0; c < 4; ++c) hm[(size_t)(off[i] + k) * 4 + c] = (int)q.ib[k * 4 + c];
+                hm[(size_t)K0 * 4 + off[i] + k] = act[i];                 // the mask plane is the stream's own
             }
+        }
         DD_HIP(hipMemcpyAsync(dm, hm, in_bytes, hipMemcpyHostToDevice, s));
         if ((rc = ddk::mask_box_count(s, p->d_mask.as<uint8_t>(), p->H, p->W, dm, dm + (size_t)K0 * 4, K0, dm + (size_t)K0 * 5)) != DD_OK) return rc;
         DD_HIP(hipMemcpyAsync(hm + (size_t)K0 * 5, dm + (size_t)K0 * 5, (size_t)K0 * sizeof(int), hipMemcpyDeviceToHost, s));
         DD_TIMED_WAIT(hipStreamSynchronize(s));                                                        // extra round trip
         const int *cnt = hm + (size_t)K0 * 5;
         std::vector<int> off0 = off;
-        for (int z = 0; z < S; ++z) {
-            StreamState &q = st[z];
-            size_t n = 0;
-            for (size_t i = 0; i < q.is.size(); ++i) {
-                const int64_t w = q.ib[i * 4 + 2], h = q.ib[i * 4 + 3];
-                if (!((double)cnt[off0[z] + i] >= p->motion_ratio * (double)w * (double)h)) { p->motion_rejected++; continue; }
-                for (int c = 0; c < 4; ++c) q.ib[n * 4 + c] = q.ib[i * 4 + c];
-                q.is[n] = q.is[i]; q.ic[n] = q.ic[i];
-                ++n;
+        for (int i = 0; i < n; ++i) {
+            StreamState &q = st[act[i]];
+            size_t nk = 0;
+            for (size_t k = 0; k < q.is.size(); ++k) {
+                const int64_t w = q.ib[k * 4 + 2], h = q.ib[k * 4 + 3];
+                if (!((double)cnt[off0[i] + k] >= p->motion_ratio * (double)w * (double)h)) { p->motion_rejected++; continue; }
+                for (int c = 0; c < 4; ++c) q.ib[nk * 4 + c] = q.ib[k * 4 + c];
+                q.is[nk] = q.is[k]; q.ic[nk] = q.ic[k];
+                ++nk;
             }
-            q.ib.resize(n * 4); q.is.resize(n); q.ic.resize(n);
-            off[z + 1] = off[z] + (int)n;
+            q.ib.resize(nk * 4); q.is.resize(nk); q.ic.resize(nk);
+            off[i + 1] = off[i] + (int)nk;
         }
     }
-    const int K = off[S];
+    const int K = off[n];
     if (K > 0) {
         bool small = true;
-        for (int z = 0; z < S; ++z) if (off[z + 1] - off[z] > 64) small = false;
-        const size_t in_bytes = (size_t)K * 5 * sizeof(double) + (size_t)(S + 1) * sizeof(int);
-        const size_t out_bytes = (size_t)(K + S) * sizeof(int);
+        for (int i = 0; i < n; ++i) if (off[i + 1] - off[i] > 64) small = false;
+        const size_t in_bytes = (size_t)K * 5 * sizeof(double) + (size_t)(n + 1) * sizeof(int);
+        const size_t out_bytes = (size_t)(K + n) * sizeof(int);
         if ((rc = p->h_nms.reserve(in_bytes + out_bytes + 256)) != DD_OK) return rc;
         if ((rc = p->d_nms.reserve(in_bytes + out_bytes + 256 + (small ? 0 : ddk::nms_scratch_bytes(4096)))) != DD_OK) return rc;
         double *hb = p->h_nms.as<double>(), *hk = hb + (size_t)K * 4;
         int *ho = reinterpret_cast<int *>(hk + K);
-        ddk::parallel_for(S, GRAIN, [&](int z0, int z1) {
-            for (int z = z0; z < z1; ++z) {
-                const StreamState &q = st[z];
-                for (size_t i = 0; i < q.ib.size(); ++i) hb[(size_t)off[z] * 4 + i] = (double)q.ib[i];   // astype(np.float)
-                for (size_t i = 0; i < q.is.size(); ++i) hk[off[z] + i] = q.is[i];
+        ddk::parallel_for(n, GRAIN, [&](int i0, int i1) {
+            for (int i = i0; i < i1; ++i) {
+                const StreamState &q = st[act[i]];
+                for (size_t k = 0; k < q.ib.size(); ++k) hb[(size_t)off[i] * 4 + k] = (double)q.ib[k];   // astype(np.float)
+                for (size_t k = 0; k < q.is.size(); ++k) hk[off[i] + k] = q.is[k];
             }
         });
-        memcpy(ho, off.data(), (size_t)(S + 1) * sizeof(int));
+        memcpy(ho, off.data(), (size_t)(n + 1) * sizeof(int));
         char *d = p->d_nms.as<char>();
         DD_STAGE_BEGIN(1);
         DD_HIP(hipMemcpyAsync(d, hb, in_bytes, hipMemcpyHostToDevice, s));
@@ -1006,12 +1126,12 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
         const int *doff = reinterpret_cast<const int *>(dk + K);
         int *didx = reinterpret_cast<int *>(d + ((in_bytes + 63) / 64) * 64), *dnk = didx + K;
         if (small) {
-            if ((rc = ddk::nms_batched_small(s, dbx, dk, doff, S, p->nms_overlap, 0, didx, dnk)) != DD_OK) return rc;
+            if ((rc = ddk::nms_batched_small(s, dbx, dk, doff, n, p->nms_overlap, 0, didx, dnk)) != DD_OK) return rc;
         } else {
             void *scr = d + ((in_bytes + 63) / 64) * 64 + ((out_bytes + 63) / 64) * 64;
-            for (int z = 0; z < S; ++z) {
-                const int k = off[z + 1] - off[z];
-                if ((rc = ddk::nms_ex(s, dbx + (size_t)off[z] * 4, dk + off[z], k, p->nms_overlap, 0, 0, didx + off[z], dnk + z,
+            for (int i = 0; i < n; ++i) {
+                const int k = off[i + 1] - off[i];
+                if ((rc = ddk::nms_ex(s, dbx + (size_t)off[i] * 4, dk + off[i], k, p->nms_overlap, 0, 0, didx + off[i], dnk + i,
                                       scr, ddk::nms_scratch_bytes(4096))) != DD_OK) return rc;
             }
         }
@@ -1020,19 +1140,21 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
         DD_STAGE_END(1);
         DD_TIMED_WAIT(hipStreamSynchronize(s));                                                        // round trip 2
         const int *hnk = hidx + K;
-        for (int z = 0; z < S; ++z) st[z].keep.assign(hidx + off[z], hidx + off[z] + hnk[z]);
+        for (int i = 0; i < n; ++i) st[act[i]].keep.assign(hidx + off[i], hidx + off[i] + hnk[i]);
     } else {
-        for (auto &q : st) q.keep.clear();
+        for (int z : act) st[z].keep.clear();
     }
     const double t2 = now_s();
 
     // ---------------- crops + MARS for every kept box of every stream (deepdish.py:1008).  A skip step runs neither (:1003-1014): stream
     // z's first n_z = min(kept boxes, feature rows of the last encoder run) boxes pair with those rows, as zip() truncates
     std::vector<int> &doff = p->doff;
-    doff.assign(S + 1, 0);
-    for (int z = 0; z < S; ++z)
-        doff[z + 1] = doff[z] + (skip ? std::min((int)st[z].keep.size(), p->foff[z + 1] - p->foff[z]) : (int)st[z].keep.size());
-    const int D = doff[S];
+    doff.assign(n + 1, 0);
+    for (int i = 0; i < n; ++i) {                   // (a skip step is never masked: i is the stream there, as in foff)
+        const int kept = (int)st[act[i]].keep.size();
+        doff[i + 1] = doff[i] + (skip ? std::min(kept, p->foff[i + 1] - p->foff[i]) : kept);
+    }
+    const int D = doff[n];
     std::vector<double> &tlwh = p->tlwh;
     tlwh.resize((size_t)D * 4);
     if (D > 0) {
@@ -1043,22 +1165,24 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
             if ((rc = p->d_feats.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
         }
         int *hc = skip ? nullptr : p->h_crop.as<int>();
-        ddk::parallel_for(S, GRAIN, [&](int z0, int z1) {
-            for (int z = z0; z < z1; ++z) {
+        ddk::parallel_for(n, GRAIN, [&](int i0, int i1) {
+            for (int i = i0; i < i1; ++i) {
+                const int z = act[i];
                 StreamState &q = st[z];
                 q.det_cls.clear(); q.det_conf.clear();
-                for (int j = 0; j < doff[z + 1] - doff[z]; ++j) {
-                    const int i = q.keep[j];
-                    const int64_t *b = q.ib.data() + (size_t)i * 4;
+                for (int j = 0; j < doff[i + 1] - doff[i]; ++j) {
+                    const int k = q.keep[j];
+                    const int64_t *b = q.ib.data() + (size_t)k * 4;
                     if (hc) {
-                        int *c = hc + (size_t)(doff[z] + j) * 8;
+                        int *c = hc + (size_t)(doff[i] + j) * 8;
                         ddk::crop_box_host(b, p->enc_h, p->enc_w, p->H, p->W, c, c + 1, c + 2, c + 3);     // generate_detections.py:63-80
-                        c[4] = z; c[5] = c[6] = c[7] = 0;
+                        c[4] = z; c[5] = c[6] = c[7] = 0;             // the crop reads the stream's own frame slot
                     }
-                    for (int c4 = 0; c4 < 4; ++c4) tlwh[(size_t)(doff[z] + j) * 4 + c4] = (double)b[c4];
-                    q.det_cls.push_back(q.ic[i]);
-                    q.det_conf.push_back(q.is[i]);
+                    for (int c4 = 0; c4 < 4; ++c4) tlwh[(size_t)(doff[i] + j) * 4 + c4] = (double)b[c4];
+                    q.det_cls.push_back(q.ic[k]);
+                    q.det_conf.push_back(q.is[k]);
                 }
+                q.det_tlwh.assign(tlwh.begin() + (size_t)doff[i] * 4, tlwh.begin() + (size_t)doff[i + 1] * 4);
             }
         });
         if (!skip) {
@@ -1066,14 +1190,14 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
             DD_HIP(hipMemcpyAsync(p->d_crop.p, hc, (size_t)D * 32, hipMemcpyHostToDevice, s));
             if ((rc = ddk::crop_resize(s, frames, p->H, p->W, p->d_crop.p, D, p->enc_h, p->enc_w, p->d_patches.as<uint8_t>())) != DD_OK) return rc;
             for (int a = 0; a < D; a += p->enc_batch) {
-                const int n = std::min(p->enc_batch, D - a);
-                if ((rc = dd_net_forward(p->enc, p->d_patches.as<uint8_t>() + (size_t)a * p->enc_h * p->enc_w * 3, n, s)) != DD_OK) return rc;
-                if ((rc = dd_net_read(p->enc, -1, n, p->d_feats.as<float>() + (size_t)a * 128, 1, s)) != DD_OK) return rc;
+                const int nb = std::min(p->enc_batch, D - a);
+                if ((rc = dd_net_forward(p->enc, p->d_patches.as<uint8_t>() + (size_t)a * p->enc_h * p->enc_w * 3, nb, s)) != DD_OK) return rc;
+                if ((rc = dd_net_read(p->enc, -1, nb, p->d_feats.as<float>() + (size_t)a * 128, 1, s)) != DD_OK) return rc;
             }
             DD_STAGE_END(2);
         }
     } else {
-        for (auto &q : st) { q.det_cls.clear(); q.det_conf.clear(); }
+        for (int z : act) { StreamState &q = st[z]; q.det_cls.clear(); q.det_conf.clear(); q.det_tlwh.clear(); }
     }
     if (!skip) p->foff = doff;                      // the rows d_feats now holds: what the skip steps up to the next detector step pair with
     const double t3 = now_s();
@@ -1081,6 +1205,7 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
     // ---------------- deep_sort update, phase-split so all streams share two round trips (:1029)
     DD_STAGE_BEGIN(3);
     if (skip && D > 0) {                            // the skip step's tracker input rows, gathered on the device (the trak stage)
+        // (n == S here: a skip step is never masked)
         if ((rc = p->h_gather.reserve((size_t)(2 * S + 1) * sizeof(int))) != DD_OK) return rc;
         if ((rc = p->d_gather.reserve((size_t)(2 * S + 1) * sizeof(int))) != DD_OK) return rc;
         if ((rc = p->d_feats_skip.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
@@ -1093,24 +1218,24 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *f
         DD_LAUNCH_CHECK();
     }
     const float *feats = D == 0 ? nullptr : skip ? p->d_feats_skip.as<float>() : p->d_feats.as<float>();
-    if ((rc = ddk::trackers_update_begin(p->trks.data(), S, tlwh.data(), feats, 1, doff.data())) != DD_OK) return rc;
+    if ((rc = ddk::trackers_update_begin(atrks.data(), n, tlwh.data(), feats, 1, doff.data())) != DD_OK) return rc;
     DD_STAGE_END(3);
     // Look-ahead, late form (default): the detector run of the next frames is queued HERE, behind this step's NMS / crops / encoder /
     // association kernels (enqueue_detector orders the detector stream after what the main stream holds so far).  Queued at the
     // consume point instead (DD_DET_LATE=0) it shares the GPU with the encoder from the start, the chain the host waits for takes
     // twice as long, and then the GPU idles through the host's matching / count-line tail: one worker group ran 6.3 ms per
     // 384-frame step for 5.0 ms of kernels.  Here the chain runs alone, and the detector fills the tail.
-    if (p->det && frames_next && p->det_late && (rc = enqueue_detector(p, frames_next)) != DD_OK) return rc;
+    if (p->det && frames_next && p->det_late && (rc = enqueue_detector(p, frames_next, act_next)) != DD_OK) return rc;
     DD_TIMED_WAIT(hipStreamSynchronize(s));                                                            // round trip 3
     DD_STAGE_BEGIN(4);
-    if ((rc = ddk::trackers_update_match(p->trks.data(), S)) != DD_OK) return rc;
+    if ((rc = ddk::trackers_update_match(atrks.data(), n)) != DD_OK) return rc;
     DD_STAGE_END(4);
     DD_TIMED_WAIT(hipStreamSynchronize(s));                                                            // round trip 4
     DD_STAGE_BEGIN(5);
-    if ((rc = ddk::trackers_update_end(p->trks.data(), S)) != DD_OK) return rc;
+    if ((rc = ddk::trackers_update_end(atrks.data(), n)) != DD_OK) return rc;
     DD_STAGE_END(5);
-    ddk::parallel_for(S, GRAIN, [&](int z0, int z1) {
-        for (int z = z0; z < z1; ++z) count_line_one_stream(p, st[z]);
+    ddk::parallel_for(n, GRAIN, [&](int i0, int i1) {
+        for (int i = i0; i < i1; ++i) { count_line_one_stream(p, st[act[i]]); st[act[i]].seen += 1; }
     });
     const double t4 = now_s();
     p->t_det += t1 - t0; p->t_nms += t2 - t1; p->t_enc += t3 - t2; p->t_trk += t4 - t3;

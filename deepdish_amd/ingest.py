@@ -120,6 +120,14 @@ class FrameIngest:
         check(lib().dd_ingest_status(self._h, int(slot), out.ctypes.data_as(P)), 'dd_ingest_status')
         return out
 
+    def present(self, slot):
+        """uint8 [S]: the mask MultiStreamPipeline.step(..., present=) takes for this slot's frames -- status(slot) == 0 on a 'jpeg' ring
+        (a stream whose file was refused, of another size, damaged or missing is absent from the step, as a failed cap.read() is
+        dropped), all ones on the raw rings.  Like status() it waits for the slot's decode on a 'jpeg' ring."""
+        if self.pixel_format != 'jpeg':
+            return np.ones(self.S, np.uint8)
+        return (self.status(slot) == 0).astype(np.uint8)
+
     def submit(self, slot):
         check(lib().dd_ingest_submit(self._h, slot), 'dd_ingest_submit')
 

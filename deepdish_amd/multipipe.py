@@ -185,17 +185,52 @@ class MultiStreamPipeline:
         return (np.ascontiguousarray(np.array(b, dtype=np.float64).reshape(-1, 4)), np.array(sc, dtype=np.float64),
                 np.array(cl, dtype=np.int32), off)
 
-    def step(self, frames_dev, injected=None, frames_next=None):
+    def _mask(self, present, what):
+        """present= of step(): None, or S values of 0 / 1 -> contiguous uint8 [S] (ValueError otherwise)."""
+        if present is None:
+            return None
+        a = np.asarray(present)
+        if a.ndim != 1 or a.shape[0] != self.S:
+            raise ValueError('%s: one value per stream, shape (%d,), got %r' % (what, self.S, a.shape))
+        if a.dtype != np.bool_ and not (a.dtype.kind in 'iuf' and np.all((a == 0) | (a == 1))):
+            raise ValueError('%s: values must be 0 or 1 (bool, uint8 or a list of them)' % what)
+        return np.ascontiguousarray(a != 0, dtype=np.uint8)
+
+    def step(self, frames_dev, injected=None, frames_next=None, present=None, present_next=None):
         """frames_dev: u8 [S, H, W, 3] BGR torch tensor in HBM; injected: pack_injected(...) or None.
         frames_next: the frames of the following step (same shape): their detector run is queued on the
         detector stream and overlaps this step's NMS / encoder / tracker; the next step() must receive them.
         With object_detector_skip_frames, a skip step ignores `injected` (it stands for the detector's output, and the
-        detector does not run), and frames_next is queued only when the next step is a detector step."""
+        detector does not run), and frames_next is queued only when the next step is a detector step.
+        present: None (every stream), or S values of 0 / 1: the streams that have a frame in this step.  For the others the step does
+        not exist -- their slot of frames_dev and their rows of `injected` may hold anything, nothing of their state moves, and the
+        detector runs on the present frames only.  present_next belongs to frames_next; a next step that arrives with another mask than
+        announced runs its detector itself, with the same result.  An all-zero mask is a legal step.  Not with
+        object_detector_skip_frames (its phase is one counter per pipeline)."""
         assert tuple(frames_dev.shape) == (self.S, self.H, self.W, 3)
         assert frames_next is None or tuple(frames_next.shape) == (self.S, self.H, self.W, 3)
+        present, present_next = self._mask(present, 'present'), self._mask(present_next, 'present_next')
+        if present_next is not None and frames_next is None:
+            raise ValueError('present_next belongs to frames_next, which is missing')
+        if (present is not None or present_next is not None) and self.object_detector_skip_frames is not None \
+                and int(self.object_detector_skip_frames) > 0:
+            raise ValueError('object_detector_skip_frames with a presence mask: the skip phase is one counter per pipeline, '
+                             'under masks it would have to be one per stream')
         b, sc, cl, off = injected if injected is not None else (None, None, None, None)
-        check(lib().dd_pipeline_step2(self._h, ptr(frames_dev), ptr(frames_next), ptr(b), ptr(sc), ptr(cl), ptr(off)),
-              'dd_pipeline_step')
+        check(lib().dd_pipeline_step3(self._h, ptr(frames_dev), ptr(present), ptr(frames_next), ptr(present_next), ptr(b), ptr(sc), ptr(cl),
+                                      ptr(off)), 'dd_pipeline_step')
+
+    def frames_seen(self):
+        """int64 [S]: the number of steps each stream was present in -- every stream has its own frame number."""
+        out = np.zeros(self.S, dtype=np.int64)
+        check(lib().dd_pipeline_frames_seen(self._h, ptr(out)), 'dd_pipeline_frames_seen')
+        return out
+
+    def present_stats(self):
+        """Which path the steps took: steps that carried a mask, frames_gather_k launches, streams advanced summed over the steps."""
+        out = np.zeros(3, dtype=np.int64)
+        check(lib().dd_pipeline_present_stats(self._h, ptr(out)), 'dd_pipeline_present_stats')
+        return dict(masked_steps=int(out[0]), gather_launches=int(out[1]), streams_stepped=int(out[2]))
 
     def detector_stream(self):
         """The stream the look-ahead detector run is queued on (None without a detector): the consumer to name when acquiring the NEXT

@@ -353,6 +353,13 @@ int dd_mog2_create(dd_ctx *ctx, int n_streams, int height, int width, int histor
                    dd_mog2 **out);
 int dd_mog2_destroy(dd_mog2 *m);
 int dd_mog2_apply(dd_mog2 *m, const uint8_t *frames, double learning_rate, uint8_t *mask, uint8_t *masked_frames, void *stream);
+/* dd_mog2_apply for the streams with present_host[z] != 0 only (u8 [n_streams], values 0 / 1; NULL = every stream): model, mask plane
+ * and masked frame of the others are neither read nor written.  OpenCV counts nframes per subtractor, so the handle keeps one frame
+ * count per stream and the automatic learning rate is 1/min(2 nframes, history) of EACH listed stream.  While all counts are equal and
+ * every stream is listed this is dd_mog2_apply's one launch; otherwise one launch of mog2_apply_list_k over a table of {stream, alphaT,
+ * 1 - alphaT, prune} entries whose floats the host computes as dd_mog2_apply does -- the same per-pixel arithmetic either way. */
+int dd_mog2_apply_streams(dd_mog2 *m, const uint8_t *frames, const uint8_t *present_host, double learning_rate, uint8_t *mask,
+                          uint8_t *masked_frames, void *stream);
 /* Test aid: the model of one stream as host arrays -- weight, variance f32 [5][H*W], mean f32 [5][3][H*W]
  * (zero past a pixel's mode count), nmodes u8 [H*W].  Synchronises. */
 int dd_mog2_state(dd_mog2 *m, int stream_index, float *weight_host, float *variance_host, float *mean_host, uint8_t *nmodes_host);
@@ -362,6 +369,14 @@ int dd_mog2_state(dd_mog2 *m, int stream_index, float *weight_host, float *varia
  * [n_boxes].  Synchronises the stream. */
 int dd_mask_box_count(dd_ctx *ctx, const uint8_t *mask, int n_streams, int height, int width, const int *boxes_xywh_host,
                       const int *box_stream_host, int n_boxes, int *counts_host, void *stream);
+
+/* Frame compaction (csrc/gather.hip): dst frame i = src frame idx[i] for i < n, frames of frame_bytes bytes behind one another; src_dev
+ * holds n_src frames.  idx_host int32 [n] must be strictly increasing and < n_src (DD_E_ARG otherwise: checked on the host, never by a
+ * faulting kernel); n = 0 is legal and launches nothing.  One launch of frames_gather_k, grid (chunks, n), 64-bit offsets; 16-byte
+ * loads and stores per lane when src_dev, dst_dev and frame_bytes are multiples of 16, 4-byte ones when multiples of 4, bytes otherwise.
+ * The buffers must not overlap.  Synchronises the stream. */
+int dd_gather_frames(dd_ctx *ctx, const uint8_t *src_dev, int n_src, int64_t frame_bytes, const int *idx_host, int n, uint8_t *dst_dev,
+                     void *stream);
 
 /* ---------------------------------------------------------------- networks
  * Replaces tflite_runtime.Interpreter(model_path).invoke() at tools/ssd_mobilenet.py:35-38,102-109,
@@ -597,6 +612,23 @@ int dd_pipeline_step(dd_pipeline *p, const uint8_t *frames, const double *inj_bo
  * not be handed in here (pass NULL instead).  frames_next == frames is rejected (DD_E_ARG). */
 int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames, const uint8_t *frames_next, const double *inj_boxes_host,
                       const double *inj_scores_host, const int *inj_cls_host, const int *inj_offsets_host);
+/* dd_pipeline_step2 under per-stream presence masks: present_host u8 [n_streams] of 0 / 1 (other values: DD_E_ARG, before anything is
+ * queued); NULL = every stream, and then this IS dd_pipeline_step2.  For a stream with present[z] = 0 the step does not exist: no predict,
+ * no update, no count-line pass, no vote, no MOG2 update; nothing of its frame slot or of its injected rows is read and nothing of its
+ * state is written -- every stream is in the state of a pipeline stepped only when it was present.  The detector's resize and forward
+ * run on the present frames alone, compacted by dd_gather_frames' kernel into a buffer of n_streams frames that the first masked step
+ * needing it allocates (an all-ones mask gathers nothing).  present_next_host belongs to frames_next (without frames_next: DD_E_ARG;
+ * NULL = all present).  The queued look-ahead run remembers its stream list: when the next call arrives with other frames or another
+ * list than announced, the run is discarded and the detector runs in that call, with the same result.  An all-zero mask is a legal
+ * step that launches nothing and changes no state.  A mask on a pipeline with dd_pipeline_detector_skip_frames set is DD_E_STATE: the
+ * skip phase is one counter per pipeline, and under masks it would have to be one per stream. */
+int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames, const uint8_t *present_host, const uint8_t *frames_next,
+                      const uint8_t *present_next_host, const double *inj_boxes_host, const double *inj_scores_host,
+                      const int *inj_cls_host, const int *inj_offsets_host);
+/* seen_host int64 [n_streams]: the number of steps each stream was present in -- its own frame number. */
+int dd_pipeline_frames_seen(dd_pipeline *p, int64_t *seen_host);
+/* out3_host = {steps that carried a mask, frames_gather_k launches, streams advanced summed over all steps}: which path the steps took. */
+int dd_pipeline_present_stats(dd_pipeline *p, long long *out3_host);
 /* The stream the look-ahead detector run of dd_pipeline_step2 is queued on (NULL for a pipeline without a detector).  A caller whose
  * `frames_next` are still on their way to the device hands it to dd_ingest_acquire as the consumer of THAT slot: the upload of frame
  * t + 1 is then waited for by the detector run of frame t + 1 alone, not by step t's own kernels -- the reference's capture thread fills
