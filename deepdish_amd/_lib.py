@@ -135,6 +135,9 @@ SIGNATURES = {
     'dd_pipeline_step3': [P, P, P, P, P, P, P, P, P],
     'dd_pipeline_frames_seen': [P, P],
     'dd_pipeline_present_stats': [P, P],
+    'dd_pipeline_detector_skip_streams': [P, P, P],
+    'dd_pipeline_skip_stats': [P, P, P],
+    'dd_feature_rows_carry': [P, P, c_int64, P, c_int64, P, c_int64, P, c_int64, P, c_int, P],
     'dd_gather_frames': [P, P, c_int, c_int64, P, c_int, P, P],
     'dd_pipeline_background_subtraction': [P, c_double, c_int],
     'dd_pipeline_motion_mask': [P, P, c_int, POINTER(ctypes.c_longlong)],

@@ -19,6 +19,7 @@
 struct dd_tracker;
 struct dd_mog2;
 namespace ddk {
+int feature_rows_carry(hipStream_t s, const float *fresh, const float *store, float *out, float *store_new, const int *d_table, int n_entries);
 int mog2_apply_streams(dd_mog2 *m, hipStream_t s, const uint8_t *frames, const uint8_t *present_host, double learning_rate, uint8_t *mask,
                        uint8_t *masked);
 int gather_frames(hipStream_t s, const uint8_t *src, long long frame_bytes, const int *d_idx, int n, uint8_t *dst);
@@ -168,6 +169,19 @@ struct dd_pipeline {
     DevBuf d_feats_skip, d_gather;             // a skip step's tracker input rows; their per-stream offsets on the device
     PinBuf h_gather;
     hipEvent_t skip_mark = nullptr;            // a skip step's main stream waits here for what the detector stream holds at step entry
+    // One skip counter per stream (dd_pipeline_detector_skip_streams): a step is a detector step for some of its streams (det_list) and a
+    // skip step for the others.  Every stream's last encoder rows are kept in a store of their own (csrc/featrows.hip): d_feats is
+    // overwritten by the next encoder run of ANY stream.  The store is compact in stream order and double-buffered: a step that ran the
+    // encoder writes the other buffer (fresh rows replace, everything else is carried) in the launch that assembles the tracker's input.
+    bool skip_streams = false, last_skip = false;
+    std::vector<int> sk_n, sk_phase, sk_rem, sk_rem_next;      // N[z]; phase[z] (-1: none); skip steps left; the counters after this step
+    std::vector<uint8_t> sk_has, sk_has_next, sk_last;         // stream has a detector result (now, after this step); its last step was a skip step
+    std::vector<uint8_t> skp;                                  // per POSITION in act: this step is a skip step for that stream
+    std::vector<int> det_list, det_next, eoff;                 // this step's detector streams, the next step's; prefix sums of their kept boxes
+    std::vector<int> ret_off, ret_n, ret_off_new;              // rows [ret_off[z], + ret_n[z]) of the current store are stream z's
+    DevBuf d_store[2];
+    int store_cur = 0;
+    long long det_stream_steps = 0, skip_stream_steps = 0, carry_launches = 0, rows_retained = 0;      // dd_pipeline_skip_stats
     // Presence masks (dd_pipeline_step3): a step advances the streams of `act` only -- all S of them without a mask.  Every per-step
     // array of the step (detector output blocks, off, doff, tlwh, the tracker pointer list) is indexed by POSITION in act.
     std::vector<int> act, act_next, det_pending_act;     // this step's streams, the look-ahead's, those of the queued detector run
@@ -360,7 +374,7 @@ int dd_pipeline_destroy(dd_pipeline *p) {
     (void)hipFree(p->d_anchors);
     dd_mog2_destroy(p->mog2);
     for (DevBuf *b : {&p->d_resized, &p->d_tmp, &p->d_post, &p->d_det, &p->d_fin, &p->d_pack, &p->d_tfl_boxes, &p->d_nms, &p->d_crop, &p->d_patches, &p->d_feats,
-                      &p->d_mask, &p->d_masked, &p->d_mbox, &p->d_feats_skip, &p->d_gather, &p->d_gframes, &p->d_lists}) b->release();
+                      &p->d_mask, &p->d_masked, &p->d_mbox, &p->d_feats_skip, &p->d_gather, &p->d_gframes, &p->d_lists, &p->d_store[0], &p->d_store[1]}) b->release();
     for (PinBuf *b : {&p->h_fin, &p->h_nms, &p->h_crop, &p->h_mbox, &p->h_gather, &p->h_lists}) b->release();
     delete p;
     return DD_OK;
@@ -436,8 +450,50 @@ int dd_pipeline_detector_adaptor(dd_pipeline *p, int adaptor) {
 int dd_pipeline_detector_skip_frames(dd_pipeline *p, int n) {
     DD_REQUIRE(p, DD_E_ARG, "dd_pipeline_detector_skip_frames: NULL pipeline");
     DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, "dd_pipeline_detector_skip_frames: call before the first step");
+    DD_REQUIRE(!p->skip_streams || n <= 0, DD_E_STATE,
+               "dd_pipeline_detector_skip_frames: the pipeline has per-stream counters (dd_pipeline_detector_skip_streams); one form per pipeline");
     p->skip_n = n;
     p->skip_rem = 0;
+    return DD_OK;
+}
+
+// The same option with one counter per stream -- what the reference, one process per camera, has (its skip_rem is per camera).  n_host[z]
+// >= 0 is stream z's N; on a step in which z is present: rem[z] > 0 and z has a detector result -> a skip step for z, rem[z] -= 1;
+// otherwise a detector step for z, then rem[z] = N[z].  A step without z moves nothing of z, its counter included.  phase_host (NULL:
+// none; this build's addition, the reference has no such option) shortens the FIRST cycle only: after z's first detector step rem[z] =
+// phase_host[z] in 0 .. N[z] instead of N[z], so that streams with equal N detect on different steps (phase z mod (N + 1): S / (N + 1)
+// detector runs on every step after the first).  A mixed step runs predict, MOG2, box hygiene, the motion test, NMS, the tracker update
+// and the count line for every present stream, the detector chain and crops + encoder for the streams on a detector step only; a stream
+// on a skip step pairs its boxes with the rows of its own last encoder run, kept in a store of retained rows (csrc/featrows.hip).
+// Presence masks are allowed in this form.  Call before the first step; not together with dd_pipeline_detector_skip_frames(n > 0).
+int dd_pipeline_detector_skip_streams(dd_pipeline *p, const int *n_host, const int *phase_host) {
+    DD_REQUIRE(p && n_host, DD_E_ARG, "dd_pipeline_detector_skip_streams: NULL argument");
+    DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, "dd_pipeline_detector_skip_streams: call before the first step");
+    DD_REQUIRE(p->skip_n <= 0, DD_E_STATE,
+               "dd_pipeline_detector_skip_streams: the pipeline has the pipeline-wide counter (dd_pipeline_detector_skip_frames); one form per pipeline");
+    for (int z = 0; z < p->S; ++z) {
+        DD_REQUIRE(n_host[z] >= 0, DD_E_ARG, "dd_pipeline_detector_skip_streams: n[%d] = %d (>= 0)", z, n_host[z]);
+        DD_REQUIRE(!phase_host || (phase_host[z] >= 0 && phase_host[z] <= n_host[z]), DD_E_ARG,
+                   "dd_pipeline_detector_skip_streams: phase[%d] = %d (0 .. n[%d] = %d)", z, phase_host[z], z, n_host[z]);
+    }
+    const size_t S = p->S;
+    p->skip_streams = true;
+    p->sk_n.assign(n_host, n_host + S);
+    if (phase_host) p->sk_phase.assign(phase_host, phase_host + S); else p->sk_phase.assign(S, -1);
+    p->sk_rem.assign(S, 0); p->sk_rem_next.assign(S, 0);
+    p->sk_has.assign(S, 0); p->sk_has_next.assign(S, 0); p->sk_last.assign(S, 0);
+    p->ret_off.assign(S, 0); p->ret_n.assign(S, 0); p->ret_off_new.assign(S, 0);
+    return DD_OK;
+}
+
+// out5_host: detector stream-steps and skip stream-steps summed over the steps, feature_rows_carry_k launches, feature rows retained now,
+// bytes allocated for the store (both halves) -- the last three are 0 without dd_pipeline_detector_skip_streams.  skipped_host (u8 [S],
+// may be NULL): 1 where the stream's last step was a skip step (counted in both forms of the option).
+int dd_pipeline_skip_stats(dd_pipeline *p, long long *out5_host, uint8_t *skipped_host) {
+    DD_REQUIRE(p && out5_host, DD_E_ARG, "dd_pipeline_skip_stats: NULL argument");
+    out5_host[0] = p->det_stream_steps; out5_host[1] = p->skip_stream_steps; out5_host[2] = p->carry_launches;
+    out5_host[3] = p->rows_retained; out5_host[4] = (long long)(p->d_store[0].cap + p->d_store[1].cap);
+    for (int z = 0; skipped_host && z < p->S; ++z) skipped_host[z] = p->skip_streams ? p->sk_last[z] : (uint8_t)(p->last_skip && p->st[z].seen > 0);
     return DD_OK;
 }
 
@@ -917,9 +973,32 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
     const bool skip = p->skip_rem > 0 && p->steps > 0;
     const int skip_rem_next = skip ? p->skip_rem - 1 : p->skip_n;
     if (skip_rem_next > 0) frames_next = nullptr;          // the next step is a skip step: no detector run to queue for its frames
+    // One counter per stream (dd_pipeline_detector_skip_streams): `dl` = the streams of act on a detector step, skp[i] = 1 where position
+    // i of act is on a skip step.  The counters after this step follow from those at its entry, so the next step's detector list -- what
+    // the look-ahead queues -- is known here.  Without per-stream counters dl is act and skp is all zero (`skip` covers that form).
+    const bool per_stream = p->skip_streams;
+    std::vector<uint8_t> &skp = p->skp;
+    skp.assign(n, 0);
+    if (per_stream) {
+        p->det_list.clear(); p->det_next.clear();
+        p->sk_rem_next = p->sk_rem; p->sk_has_next = p->sk_has;
+        for (int i = 0; i < n; ++i) {
+            const int z = act[i];
+            if (p->sk_rem[z] > 0 && p->sk_has[z]) { skp[i] = 1; p->sk_rem_next[z] = p->sk_rem[z] - 1; }
+            else {
+                p->det_list.push_back(z);
+                p->sk_rem_next[z] = !p->sk_has[z] && p->sk_phase[z] >= 0 ? p->sk_phase[z] : p->sk_n[z];
+                p->sk_has_next[z] = 1;
+            }
+        }
+        for (int z : act_next) if (!(p->sk_rem_next[z] > 0 && p->sk_has_next[z])) p->det_next.push_back(z);
+        if (p->det_next.empty()) frames_next = nullptr;    // a step of skip steps only: no detector run to queue
+    }
+    const std::vector<int> &dl = per_stream ? p->det_list : act, &dl_next = per_stream ? p->det_next : act_next;
+    const int nd = (int)dl.size();                         // the detector run's batch: its blocks are indexed by POSITION in dl
     const double t0 = now_s();
     p->step_wait = 0;
-    if (skip && p->det) {
+    if ((skip || nd == 0) && p->det) {
         // no detector run reads these frames: the main stream takes over what the detector stream holds for them (the wait an ingest
         // ring queued there for their upload, dd_pipeline_detector_stream) before MOG2 reads them
         DD_HIP(hipEventRecord(p->skip_mark, p->det_stream));
@@ -938,11 +1017,12 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
     // (host phases below: one parallel_for over the streams each -- they share nothing; hostpool.h)
     constexpr int GRAIN = 16;
     std::vector<StreamState> &st = p->st;
-    if (skip) {
+    if (skip || (nd == 0 && p->det)) {
         // every stream keeps the adaptor output of the last detector step; the early look-ahead form queues the next frames here
-        if (p->det && frames_next && !p->det_late && (rc = enqueue_detector(p, frames_next, act_next)) != DD_OK) return rc;
+        if (per_stream) p->det_pending = nullptr;  // (a run queued for a step that turns out to have no detector stream: dropped)
+        if (p->det && frames_next && !p->det_late && (rc = enqueue_detector(p, frames_next, dl_next)) != DD_OK) return rc;
     } else if (p->det) {
-        if ((p->det_pending != frames || p->det_pending_act != act) && (rc = enqueue_detector(p, frames, act)) != DD_OK) return rc;   // not queued ahead (or for other streams): run it now
+        if ((p->det_pending != frames || p->det_pending_act != dl) && (rc = enqueue_detector(p, frames, dl)) != DD_OK) return rc;   // not queued ahead (or for other streams): run it now
         DD_TIMED_WAIT(hipEventSynchronize(p->det_done));                                               // round trip 1
         p->det_pending = nullptr;
         if (g_stage_events) {   // the detector chain of these frames on its stream: resize, forward, post-process, adaptor tail, host copy
@@ -951,13 +1031,13 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
             p->g_det += (double)ms;
         }
         if (p->det_kind == DET_YOLOV5) {
-            const size_t head = ((size_t)n * 4 + 63) / 64 * 64;
+            const size_t head = ((size_t)nd * 4 + 63) / 64 * 64;
             const int *yn = p->h_fin.as<int>();
             std::vector<size_t> &ybase = p->ybase;
-            ybase.assign(n + 1, 0);
-            for (int i = 0; i < n; ++i) ybase[i + 1] = ybase[i] + (size_t)std::min(yn[i], p->n_anchors);
-            if (ybase[n] > p->yolo_host_rows) {                    // a busy step: fetch the rest (the detector stream is idle here) and
-                const size_t have = p->yolo_host_rows, total = ybase[n];      // make room for twice as many from now on
+            ybase.assign(nd + 1, 0);
+            for (int i = 0; i < nd; ++i) ybase[i + 1] = ybase[i] + (size_t)std::min(yn[i], p->n_anchors);
+            if (ybase[nd] > p->yolo_host_rows) {                    // a busy step: fetch the rest (the detector stream is idle here) and
+                const size_t have = p->yolo_host_rows, total = ybase[nd];      // make room for twice as many from now on
                 // ... but never more than the packed block holds (S * n_anchors rows): the first copy of every later step reads that many
                 const size_t grown = std::min(2 * total, (size_t)S * (size_t)p->n_anchors);
                 PinBuf bigger;
@@ -973,9 +1053,9 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
                 yn = p->h_fin.as<int>();
             }
             const float *rows = reinterpret_cast<const float *>(p->h_fin.as<char>() + head);
-            ddk::parallel_for(n, GRAIN, [&](int i0, int i1) {
+            ddk::parallel_for(nd, GRAIN, [&](int i0, int i1) {
                 for (int i = i0; i < i1; ++i) {
-                    StreamState &q = st[act[i]];
+                    StreamState &q = st[dl[i]];
                     q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
                     const int nr = (int)(ybase[i + 1] - ybase[i]);
                     for (int r = 0; r < nr; ++r) {                                                     // yolov5.py:137-145
@@ -993,12 +1073,12 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
         } else if (p->det_kind == DET_TFLITE) {
             // tflite_object_detector.py:234-295 (_postprocess) + tools/tflite.py:26-41: score >= threshold, int() of the scaled
             // corners (f32 arithmetic, truncation), label = label_list[class], stable sort by descending score, wanted labels only
-            // (the run's blocks hold n = act.size() frames: z below is the POSITION of a stream in act)
-            const float *hb = p->h_fin.as<float>(), *hc = hb + (size_t)n * MAX_DET * 4, *hs = hc + (size_t)n * MAX_DET;
-            const int *hn = reinterpret_cast<const int *>(hs + (size_t)n * MAX_DET);
-            ddk::parallel_for(n, GRAIN, [&](int z0, int z1) {
+            // (the run's blocks hold nd = dl.size() frames: z below is the POSITION of a stream in dl)
+            const float *hb = p->h_fin.as<float>(), *hc = hb + (size_t)nd * MAX_DET * 4, *hs = hc + (size_t)nd * MAX_DET;
+            const int *hn = reinterpret_cast<const int *>(hs + (size_t)nd * MAX_DET);
+            ddk::parallel_for(nd, GRAIN, [&](int z0, int z1) {
                 for (int z = z0; z < z1; ++z) {
-                    StreamState &q = st[act[z]];
+                    StreamState &q = st[dl[z]];
                     q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
                     int order[MAX_DET_CAP], no = 0;
                     for (int i = 0; i < hn[z] && i < MAX_DET; ++i)
@@ -1023,11 +1103,11 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
                 }
             });
         } else {
-            const double *hb = p->h_fin.as<double>(), *hs = hb + (size_t)n * MAX_DET * 4;       // (z: position in act, as above)
-            const int *hc = reinterpret_cast<const int *>(hs + (size_t)n * MAX_DET), *hn = hc + (size_t)n * MAX_DET;
-            ddk::parallel_for(n, GRAIN, [&](int z0, int z1) {
+            const double *hb = p->h_fin.as<double>(), *hs = hb + (size_t)nd * MAX_DET * 4;       // (z: position in dl, as above)
+            const int *hc = reinterpret_cast<const int *>(hs + (size_t)nd * MAX_DET), *hn = hc + (size_t)nd * MAX_DET;
+            ddk::parallel_for(nd, GRAIN, [&](int z0, int z1) {
                 for (int z = z0; z < z1; ++z) {
-                    StreamState &q = st[act[z]];
+                    StreamState &q = st[dl[z]];
                     q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
                     for (int i = 0; i < hn[z]; ++i) {                                                  // :204-212
                         const double sc = hs[z * MAX_DET + i];
@@ -1041,9 +1121,9 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
             });
         }
         // the host block has been consumed: the detector buffers are free for the next frames
-        if (frames_next && !p->det_late && (rc = enqueue_detector(p, frames_next, act_next)) != DD_OK) return rc;
+        if (frames_next && !p->det_late && (rc = enqueue_detector(p, frames_next, dl_next)) != DD_OK) return rc;
     } else {
-        for (int z : act) { StreamState &q = st[z]; q.boxes0.clear(); q.scores0.clear(); q.cls0.clear(); }
+        for (int z : dl) { StreamState &q = st[z]; q.boxes0.clear(); q.scores0.clear(); q.cls0.clear(); }
     }
     if (inj_offsets_host)
         DD_REQUIRE(inj_boxes_host && inj_scores_host && inj_cls_host, DD_E_ARG, "dd_pipeline_step: injected arrays missing");
@@ -1057,7 +1137,7 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
         for (int i = i0; i < i1; ++i) {
             const int z = act[i];
             StreamState &q = st[z];
-            if (inj_offsets_host && !skip) {
+            if (inj_offsets_host && !skip && !skp[i]) {
                 const int a = inj_offsets_host[z], b = inj_offsets_host[z + 1];
                 q.boxes0.assign(inj_boxes_host + (size_t)a * 4, inj_boxes_host + (size_t)b * 4);
                 q.scores0.assign(inj_scores_host + a, inj_scores_host + b);
@@ -1150,31 +1230,36 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
     // z's first n_z = min(kept boxes, feature rows of the last encoder run) boxes pair with those rows, as zip() truncates
     std::vector<int> &doff = p->doff;
     doff.assign(n + 1, 0);
-    for (int i = 0; i < n; ++i) {                   // (a skip step is never masked: i is the stream there, as in foff)
+    // per-stream counters: a stream on a skip step pairs with its own retained rows; eoff = the encoder's rows, the detector streams' only
+    std::vector<int> &eoff = p->eoff;
+    eoff.assign(n + 1, 0);
+    for (int i = 0; i < n; ++i) {                   // (a lock-step skip step is never masked: i is the stream there, as in foff)
         const int kept = (int)st[act[i]].keep.size();
-        doff[i + 1] = doff[i] + (skip ? std::min(kept, p->foff[i + 1] - p->foff[i]) : kept);
+        doff[i + 1] = doff[i] + (skip ? std::min(kept, p->foff[i + 1] - p->foff[i]) : skp[i] ? std::min(kept, p->ret_n[act[i]]) : kept);
+        eoff[i + 1] = eoff[i] + (skip || skp[i] ? 0 : kept);
     }
-    const int D = doff[n];
+    const int D = doff[n], E = eoff[n];             // tracker input rows; rows the encoder makes in this step (E == D unless streams skip)
     std::vector<double> &tlwh = p->tlwh;
     tlwh.resize((size_t)D * 4);
     if (D > 0) {
-        if (!skip) {
-            if ((rc = p->h_crop.reserve((size_t)D * 32)) != DD_OK) return rc;
-            if ((rc = p->d_crop.reserve((size_t)D * 32)) != DD_OK) return rc;
-            if ((rc = p->d_patches.reserve((size_t)D * p->enc_h * p->enc_w * 3)) != DD_OK) return rc;
-            if ((rc = p->d_feats.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
+        if (E > 0) {
+            if ((rc = p->h_crop.reserve((size_t)E * 32)) != DD_OK) return rc;
+            if ((rc = p->d_crop.reserve((size_t)E * 32)) != DD_OK) return rc;
+            if ((rc = p->d_patches.reserve((size_t)E * p->enc_h * p->enc_w * 3)) != DD_OK) return rc;
+            if ((rc = p->d_feats.reserve((size_t)E * 128 * sizeof(float))) != DD_OK) return rc;
         }
-        int *hc = skip ? nullptr : p->h_crop.as<int>();
+        int *hc0 = E > 0 ? p->h_crop.as<int>() : nullptr;
         ddk::parallel_for(n, GRAIN, [&](int i0, int i1) {
             for (int i = i0; i < i1; ++i) {
                 const int z = act[i];
                 StreamState &q = st[z];
                 q.det_cls.clear(); q.det_conf.clear();
+                int *hc = skp[i] ? nullptr : hc0;
                 for (int j = 0; j < doff[i + 1] - doff[i]; ++j) {
                     const int k = q.keep[j];
                     const int64_t *b = q.ib.data() + (size_t)k * 4;
                     if (hc) {
-                        int *c = hc + (size_t)(doff[i] + j) * 8;
+                        int *c = hc + (size_t)(eoff[i] + j) * 8;
                         ddk::crop_box_host(b, p->enc_h, p->enc_w, p->H, p->W, c, c + 1, c + 2, c + 3);     // generate_detections.py:63-80
                         c[4] = z; c[5] = c[6] = c[7] = 0;             // the crop reads the stream's own frame slot
                     }
@@ -1185,12 +1270,12 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
                 q.det_tlwh.assign(tlwh.begin() + (size_t)doff[i] * 4, tlwh.begin() + (size_t)doff[i + 1] * 4);
             }
         });
-        if (!skip) {
+        if (E > 0) {
             DD_STAGE_BEGIN(2);
-            DD_HIP(hipMemcpyAsync(p->d_crop.p, hc, (size_t)D * 32, hipMemcpyHostToDevice, s));
-            if ((rc = ddk::crop_resize(s, frames, p->H, p->W, p->d_crop.p, D, p->enc_h, p->enc_w, p->d_patches.as<uint8_t>())) != DD_OK) return rc;
-            for (int a = 0; a < D; a += p->enc_batch) {
-                const int nb = std::min(p->enc_batch, D - a);
+            DD_HIP(hipMemcpyAsync(p->d_crop.p, hc0, (size_t)E * 32, hipMemcpyHostToDevice, s));
+            if ((rc = ddk::crop_resize(s, frames, p->H, p->W, p->d_crop.p, E, p->enc_h, p->enc_w, p->d_patches.as<uint8_t>())) != DD_OK) return rc;
+            for (int a = 0; a < E; a += p->enc_batch) {
+                const int nb = std::min(p->enc_batch, E - a);
                 if ((rc = dd_net_forward(p->enc, p->d_patches.as<uint8_t>() + (size_t)a * p->enc_h * p->enc_w * 3, nb, s)) != DD_OK) return rc;
                 if ((rc = dd_net_read(p->enc, -1, nb, p->d_feats.as<float>() + (size_t)a * 128, 1, s)) != DD_OK) return rc;
             }
@@ -1199,7 +1284,7 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
     } else {
         for (int z : act) { StreamState &q = st[z]; q.det_cls.clear(); q.det_conf.clear(); q.det_tlwh.clear(); }
     }
-    if (!skip) p->foff = doff;                      // the rows d_feats now holds: what the skip steps up to the next detector step pair with
+    if (!skip && !per_stream) p->foff = doff;       // the rows d_feats now holds: what the skip steps up to the next detector step pair with
     const double t3 = now_s();
 
     // ---------------- deep_sort update, phase-split so all streams share two round trips (:1029)
@@ -1218,6 +1303,51 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
         DD_LAUNCH_CHECK();
     }
     const float *feats = D == 0 ? nullptr : skip ? p->d_feats_skip.as<float>() : p->d_feats.as<float>();
+    if (per_stream) {
+        // One launch (csrc/featrows.hip): the tracker's input rows in act order -- fresh encoder rows for the streams of dl, retained rows
+        // for the others -- and, when an encoder run changed what is retained, the next store: fresh rows replace, the rest is carried,
+        // absent streams included.  With no stream on a skip step that has rows to pair, d_feats already is the tracker's input.
+        bool gather = false;
+        for (int i = 0; i < n; ++i) gather = gather || (skp[i] && doff[i + 1] > doff[i]);
+        const bool refresh = nd > 0;
+        std::vector<int> &tb = p->list_build, &noff = p->ret_off_new;
+        tb.clear();
+        int total = 0;
+        for (int z = 0, i = 0; z < S; ++z) {
+            const bool here = i < n && act[i] == z;
+            const bool fresh = here && !skp[i];
+            const int kept = here ? (fresh ? eoff[i + 1] - eoff[i] : doff[i + 1] - doff[i]) : 0;
+            const int n_out = here && gather ? kept : 0, n_store = !refresh ? 0 : fresh ? kept : p->ret_n[z];
+            if (n_out > 0 || n_store > 0) {
+                const int e[8] = {fresh ? 0 : 1, fresh ? eoff[i] : p->ret_off[z], n_out, here ? doff[i] : 0, n_store, total, 0, 0};
+                tb.insert(tb.end(), e, e + 8);
+            }
+            noff[z] = total;
+            total += n_store;
+            i += here;
+        }
+        if (!tb.empty()) {
+            DevBuf &next = p->d_store[1 - p->store_cur];
+            if (gather && (rc = p->d_feats_skip.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
+            if (refresh && (rc = next.reserve((size_t)total * 128 * sizeof(float))) != DD_OK) return rc;
+            const int *d_table = nullptr;
+            if ((rc = stage_list(p, s, tb.data(), tb.size(), &d_table)) != DD_OK) return rc;
+            if ((rc = ddk::feature_rows_carry(s, p->d_feats.as<float>(), p->d_store[p->store_cur].as<float>(), p->d_feats_skip.as<float>(),
+                                              next.as<float>(), d_table, (int)(tb.size() / 8))) != DD_OK) return rc;
+            p->carry_launches += 1;
+        }
+        if (refresh) {
+            for (int z = 0, i = 0; z < S; ++z) {
+                const bool here = i < n && act[i] == z;
+                if (here && !skp[i]) p->ret_n[z] = eoff[i + 1] - eoff[i];
+                i += here;
+            }
+            p->ret_off = noff;
+            p->store_cur = 1 - p->store_cur;
+            p->rows_retained = total;
+        }
+        feats = D == 0 ? nullptr : gather ? p->d_feats_skip.as<float>() : p->d_feats.as<float>();
+    }
     if ((rc = ddk::trackers_update_begin(atrks.data(), n, tlwh.data(), feats, 1, doff.data())) != DD_OK) return rc;
     DD_STAGE_END(3);
     // Look-ahead, late form (default): the detector run of the next frames is queued HERE, behind this step's NMS / crops / encoder /
@@ -1225,7 +1355,7 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
     // consume point instead (DD_DET_LATE=0) it shares the GPU with the encoder from the start, the chain the host waits for takes
     // twice as long, and then the GPU idles through the host's matching / count-line tail: one worker group ran 6.3 ms per
     // 384-frame step for 5.0 ms of kernels.  Here the chain runs alone, and the detector fills the tail.
-    if (p->det && frames_next && p->det_late && (rc = enqueue_detector(p, frames_next, act_next)) != DD_OK) return rc;
+    if (p->det && frames_next && p->det_late && (rc = enqueue_detector(p, frames_next, dl_next)) != DD_OK) return rc;
     DD_TIMED_WAIT(hipStreamSynchronize(s));                                                            // round trip 3
     DD_STAGE_BEGIN(4);
     if ((rc = ddk::trackers_update_match(atrks.data(), n)) != DD_OK) return rc;
@@ -1243,6 +1373,14 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
     p->ev_pending = true;
     p->steps += 1;
     p->skip_rem = skip_rem_next;
+    p->last_skip = skip;
+    if (per_stream) {
+        p->sk_rem.swap(p->sk_rem_next); p->sk_has.swap(p->sk_has_next);
+        for (int i = 0; i < n; ++i) p->sk_last[act[i]] = skp[i];
+        p->det_stream_steps += nd; p->skip_stream_steps += n - nd;
+    } else {
+        (skip ? p->skip_stream_steps : p->det_stream_steps) += n;
+    }
     return DD_OK;
 }
 

@@ -37,13 +37,44 @@ class _TrackerView:
         return v.value
 
 
+def _skip_streams(skip_frames, skip_phase, S):
+    """object_detector_skip_frames / object_detector_skip_phase -> (N int32 [S], phase int32 [S] or None) for the per-stream form,
+    (None, None) for the int form or no option; ValueError for what neither form takes."""
+    def per_stream(v, what):
+        a = np.asarray(v)
+        if a.ndim == 0:
+            a = np.full(S, a)
+        if a.ndim != 1 or a.shape[0] != S:
+            raise ValueError('%s: one value per stream, %d of them, got shape %r' % (what, S, a.shape))
+        if a.dtype.kind not in 'iu':
+            raise ValueError('%s: integers, got %s' % (what, a.dtype))
+        return np.ascontiguousarray(a, dtype=np.int32)
+    seq = skip_frames is not None and np.ndim(skip_frames) > 0
+    if not seq and skip_phase is None:
+        return None, None
+    if skip_frames is None:
+        raise ValueError('object_detector_skip_phase without object_detector_skip_frames: a phase shortens the first cycle of a stream\'s N')
+    if not seq:
+        raise ValueError('object_detector_skip_phase with object_detector_skip_frames=%r: an int is the pipeline-wide counter, which has no '
+                         'phase; pass object_detector_skip_frames=[%r] * %d for one counter per stream' % (skip_frames, skip_frames, S))
+    n = per_stream(skip_frames, 'object_detector_skip_frames')
+    if (n < 0).any():
+        raise ValueError('object_detector_skip_frames: N >= 0 for every stream, got %r' % (n.tolist(),))
+    phase = None
+    if skip_phase is not None:
+        phase = per_stream(skip_phase, 'object_detector_skip_phase')
+        if ((phase < 0) | (phase > n)).any():
+            raise ValueError('object_detector_skip_phase: 0 .. N[z] for every stream, got %r for N = %r' % (phase.tolist(), n.tolist()))
+    return n, phase
+
+
 class MultiStreamPipeline:
     def __init__(self, n_streams, model='synthetic-ssd_mobilenet_v1', encoder_model='synthetic-mars-64x32x3',
                  labels=None, wanted_labels=('person',), input_size=(640, 480), line=None, max_cosine_distance=0.2,
                  nms_max_overlap=0.6, max_iou_distance=0.7, max_age=60, n_init=3, context=None, run_detector=True,
                  encoder_max_batch=None, track_capacity=512, gallery_capacity=256, background_subtraction_ratio=None,
                  background_masking=False, graph=None, object_detector_skip_frames=None, metric='cosine',
-                 association='host', detector_letterbox=False, ground=None, topdownview_size_m=None):
+                 association='host', detector_letterbox=False, ground=None, topdownview_size_m=None, object_detector_skip_phase=None):
         from .tools.yolov5 import letterbox_pad
         from .ground import for_pipeline
         # the reference's --3d mode (deepdish.py:592-611): a GroundPlane, or a list with one per stream; None: no top-down view
@@ -51,6 +82,8 @@ class MultiStreamPipeline:
         self.detector_letterbox = letterbox_pad(detector_letterbox)      # None, or the pad value of the YOLOv5 detector's letterboxed input
         if self.detector_letterbox is not None and 'yolov5' not in model:      # before anything is built
             raise ValueError('%s: detector_letterbox is the YOLOv5 detector\'s option; the other detectors are trained on stretched input' % model)
+        # an int: one counter per pipeline (lock-step); S ints, or any phase: one counter per stream -- ValueError before anything is built
+        skip_n, skip_phase = _skip_streams(object_detector_skip_frames, object_detector_skip_phase, int(n_streams))
         self.metric = metric
         metric_kind = _metric_kind(metric)   # 'cosine' or 'euclidean' (nn_matching.py:126-132), else ValueError -- before anything is built
         self.association = association
@@ -148,8 +181,14 @@ class MultiStreamPipeline:
         if background_subtraction_ratio is not None:
             self.background_subtraction(background_subtraction_ratio, background_masking)
         # --object-detector-skip-frames (deepdish.py:892-893,929-938,1003-1014): detector + encoder on one step in N + 1 (None: every step)
+        # An int is the pipeline-wide counter: all streams detect on the same steps.  A sequence of S ints (and / or
+        # object_detector_skip_phase) gives every stream its own counter, the reference's rule per camera; that form takes presence masks.
         self.object_detector_skip_frames = object_detector_skip_frames
-        if object_detector_skip_frames is not None:
+        self.object_detector_skip_phase = object_detector_skip_phase
+        self.skip_per_stream = skip_n is not None
+        if self.skip_per_stream:
+            check(lib().dd_pipeline_detector_skip_streams(self._h, ptr(skip_n), ptr(skip_phase)), 'dd_pipeline_detector_skip_streams')
+        elif object_detector_skip_frames is not None:
             check(lib().dd_pipeline_detector_skip_frames(self._h, int(object_detector_skip_frames)), 'dd_pipeline_detector_skip_frames')
 
     def background_subtraction(self, ratio, masking=False):
@@ -205,17 +244,19 @@ class MultiStreamPipeline:
         present: None (every stream), or S values of 0 / 1: the streams that have a frame in this step.  For the others the step does
         not exist -- their slot of frames_dev and their rows of `injected` may hold anything, nothing of their state moves, and the
         detector runs on the present frames only.  present_next belongs to frames_next; a next step that arrives with another mask than
-        announced runs its detector itself, with the same result.  An all-zero mask is a legal step.  Not with
-        object_detector_skip_frames (its phase is one counter per pipeline)."""
+        announced runs its detector itself, with the same result.  An all-zero mask is a legal step.  Not with the int form of
+        object_detector_skip_frames (one counter per pipeline: all streams in lock-step); the per-stream form (a sequence of S ints)
+        takes masks: a stream's counter moves only on the steps it is present in."""
         assert tuple(frames_dev.shape) == (self.S, self.H, self.W, 3)
         assert frames_next is None or tuple(frames_next.shape) == (self.S, self.H, self.W, 3)
         present, present_next = self._mask(present, 'present'), self._mask(present_next, 'present_next')
         if present_next is not None and frames_next is None:
             raise ValueError('present_next belongs to frames_next, which is missing')
-        if (present is not None or present_next is not None) and self.object_detector_skip_frames is not None \
+        if (present is not None or present_next is not None) and not self.skip_per_stream and self.object_detector_skip_frames is not None \
                 and int(self.object_detector_skip_frames) > 0:
-            raise ValueError('object_detector_skip_frames with a presence mask: the skip phase is one counter per pipeline, '
-                             'under masks it would have to be one per stream')
+            raise ValueError('object_detector_skip_frames=%d with a presence mask: an int is one counter per pipeline (all streams in '
+                             'lock-step); pass a sequence, object_detector_skip_frames=[%d] * %d, for one counter per stream'
+                             % (int(self.object_detector_skip_frames), int(self.object_detector_skip_frames), self.S))
         b, sc, cl, off = injected if injected is not None else (None, None, None, None)
         check(lib().dd_pipeline_step3(self._h, ptr(frames_dev), ptr(present), ptr(frames_next), ptr(present_next), ptr(b), ptr(sc), ptr(cl),
                                       ptr(off)), 'dd_pipeline_step')
@@ -231,6 +272,15 @@ class MultiStreamPipeline:
         out = np.zeros(3, dtype=np.int64)
         check(lib().dd_pipeline_present_stats(self._h, ptr(out)), 'dd_pipeline_present_stats')
         return dict(masked_steps=int(out[0]), gather_launches=int(out[1]), streams_stepped=int(out[2]))
+
+    def skip_stats(self):
+        """Detector stream-steps and skip stream-steps summed over the steps; with per-stream counters also the launches of the retained-rows
+        kernel (csrc/featrows.hip), the feature rows retained now and the bytes allocated for their store (all 0 otherwise); `skipped`:
+        bool [S], whether each stream's last step was a skip step."""
+        out, sk = np.zeros(5, dtype=np.int64), np.zeros(self.S, dtype=np.uint8)
+        check(lib().dd_pipeline_skip_stats(self._h, ptr(out), ptr(sk)), 'dd_pipeline_skip_stats')
+        return dict(detector_stream_steps=int(out[0]), skip_stream_steps=int(out[1]), carry_launches=int(out[2]), rows_retained=int(out[3]),
+                    store_bytes=int(out[4]), skipped=sk.astype(bool))
 
     def detector_stream(self):
         """The stream the look-ahead detector run is queued on (None without a detector): the consumer to name when acquiring the NEXT

@@ -378,6 +378,18 @@ int dd_mask_box_count(dd_ctx *ctx, const uint8_t *mask, int n_streams, int heigh
 int dd_gather_frames(dd_ctx *ctx, const uint8_t *src_dev, int n_src, int64_t frame_bytes, const int *idx_host, int n, uint8_t *dst_dev,
                      void *stream);
 
+/* Retained feature rows (csrc/featrows.hip; what dd_pipeline_detector_skip_streams launches once per step, deepdish.py:1003-1014): a row
+ * is 128 f32.  table_host int32 [n_streams][6] = {sel, src_row, n_out, dst_out_row, n_store, dst_store_row}: stream z reads rows
+ * [src_row, src_row + max(n_out, n_store)) of fresh_dev (sel 0: the encoder's output) or store_dev (sel 1: the store), and writes the
+ * first n_out of them to rows_out_dev at dst_out_row (the tracker's input) and the first n_store to store_out_dev at dst_store_row (the
+ * next store).  *_rows = the rows each buffer holds: every range is checked against them on the host (DD_E_ARG; never by a faulting
+ * kernel), as are overlapping destination ranges and buffers that are not 16-byte aligned.  One launch of feature_rows_carry_k, one
+ * block per stream that has rows (a stream with none costs nothing), 16-byte loads and stores, 64-bit offsets; n_streams = 0 is legal
+ * and launches nothing.  Sources and destinations must not overlap.  Synchronises the stream. */
+int dd_feature_rows_carry(dd_ctx *ctx, const float *fresh_dev, int64_t fresh_rows, const float *store_dev, int64_t store_rows,
+                          float *rows_out_dev, int64_t out_rows, float *store_out_dev, int64_t store_out_rows, const int *table_host,
+                          int n_streams, void *stream);
+
 /* ---------------------------------------------------------------- networks
  * Replaces tflite_runtime.Interpreter(model_path).invoke() at tools/ssd_mobilenet.py:35-38,102-109,
  * tools/yolov5.py:71-79,107-109 and tools/generate_detections.py:153-154,169-171.  A model is an op
@@ -587,6 +599,28 @@ int dd_pipeline_ssd_regular_nms(dd_pipeline *p, int detections_per_class);
  * motion test and NMS, and its first min(kept boxes, feature rows of that step) boxes pair with those feature rows in order, as the
  * reference's zip() does.  Stage events add nothing to objd / feat on a skip step.  Before the first step. */
 int dd_pipeline_detector_skip_frames(dd_pipeline *p, int n);
+/* The same option with one counter per stream (deepdish.py:892-893,929-938,1003-1014 -- the reference is one process per camera, so its
+ * skip_rem IS per camera).  n_host int32 [n_streams], every value >= 0; phase_host int32 [n_streams] with 0 <= phase[z] <= n[z], or NULL
+ * (other values: DD_E_ARG).  Stream z keeps rem[z] (starts at 0) and "has a detector result" (starts false).  On a step in which z is
+ * present: rem[z] > 0 and z has a result -> a skip step for z, rem[z] -= 1; otherwise a detector step for z, then rem[z] = phase[z] if
+ * this was z's first detector step and a phase was given, else n[z].  A step without z moves nothing of z, its counter included.  Without
+ * phase this is the reference's rule applied to each stream's own present frames.  phase is this build's addition (the reference has no
+ * such option): it shortens the first cycle only, so that streams with equal n detect on different steps -- with phase[z] = z mod (n + 1)
+ * every unmasked step after the first runs the detector for n_streams / (n + 1) streams instead of all or none.
+ * In a step, predict, MOG2, box hygiene, the motion test (against this frame's mask), NMS, the tracker update and the count line run for
+ * every present stream; the detector chain, crops and encoder for the streams on a detector step only (through the compaction of
+ * dd_pipeline_step3 when those are not all streams); injected rows replace the detector's output for these and are ignored for the
+ * others.  A stream on a skip step pairs its first min(kept boxes, retained rows) boxes with the rows of ITS OWN last encoder run, which
+ * a store of retained rows keeps across other streams' encoder runs and steps without the stream (dd_feature_rows_carry's kernel, one
+ * launch per step; the store holds the rows actually retained, twice: it is double-buffered).  The look-ahead queues the detector run
+ * of the next step's detector streams, known when this step starts; nothing when there are none.  Presence masks are allowed in this
+ * form.  Before the first step (DD_E_STATE after); a pipeline takes this form or dd_pipeline_detector_skip_frames(n > 0), not both
+ * (DD_E_STATE). */
+int dd_pipeline_detector_skip_streams(dd_pipeline *p, const int *n_host, const int *phase_host);
+/* out5_host = {detector stream-steps, skip stream-steps (both summed over the steps, in either form of the option), feature_rows_carry_k
+ * launches, feature rows retained now, bytes allocated for the store}: the last three are 0 without dd_pipeline_detector_skip_streams.
+ * skipped_host u8 [n_streams] (may be NULL): 1 where the stream's last step was a skip step. */
+int dd_pipeline_skip_stats(dd_pipeline *p, long long *out5_host, uint8_t *skipped_host);
 /* Letterboxed detector input for a YOLOv5 pipeline (other detectors: DD_E_ARG -- SSD-MobileNet is trained on stretched input): the step's
  * Lanczos stretch becomes dd_resize_lanczos_letterbox with this pad value (0 .. 255; 114 is YOLOv5's own, 128 the reference's YOLOv3 canvas)
  * on the detector stream, and both decode forms un-map their boxes as dd_yolov5_decode_letterbox does.  Everything downstream sees frame
@@ -620,8 +654,9 @@ int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames, const uint8_t *fram
  * needing it allocates (an all-ones mask gathers nothing).  present_next_host belongs to frames_next (without frames_next: DD_E_ARG;
  * NULL = all present).  The queued look-ahead run remembers its stream list: when the next call arrives with other frames or another
  * list than announced, the run is discarded and the detector runs in that call, with the same result.  An all-zero mask is a legal
- * step that launches nothing and changes no state.  A mask on a pipeline with dd_pipeline_detector_skip_frames set is DD_E_STATE: the
- * skip phase is one counter per pipeline, and under masks it would have to be one per stream. */
+ * step that launches nothing and changes no state.  A mask on a pipeline with dd_pipeline_detector_skip_frames set is DD_E_STATE: that
+ * form's skip phase is one counter per pipeline (all streams in lock-step); dd_pipeline_detector_skip_streams has one per stream and
+ * takes masks. */
 int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames, const uint8_t *present_host, const uint8_t *frames_next,
                       const uint8_t *present_next_host, const double *inj_boxes_host, const double *inj_scores_host,
                       const int *inj_cls_host, const int *inj_offsets_host);
