@@ -74,6 +74,7 @@ SIGNATURES = {
     'dd_ingest_create_jpeg': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, P],
     'dd_ingest_create_jpeg_scaled': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, P],
     'dd_ingest_jpeg_put': [P, c_int, c_int, P, c_int64],
+    'dd_ingest_create_jpeg_ex': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, P],
     'dd_ingest_status': [P, c_int, P],
     'dd_ingest_destroy': [P],
     'dd_ingest_host_slot': [P, c_int, P, P],
@@ -171,6 +172,9 @@ SIGNATURES = {
     'dd_jpegdec_plan_scaled': [c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)],
     'dd_jpegdec_output_size': [P, POINTER(c_int), POINTER(c_int)],
     'dd_jpeg_draft_scale': [c_int, c_int, c_int, c_int],
+    'dd_jpeg_parse_scans': [P, c_int64, P, P],
+    'dd_jpegdec_create_ex': [P, c_int, c_int, c_int, c_int, c_int, c_int64, POINTER(P)],
+    'dd_jpegdec_profile_levels': [P, P, POINTER(c_int)],
     'dd_counts_accumulate': [P, P, P, c_int, P],
 }
 _RESTYPE = {'dd_last_error': c_char_p}

@@ -165,9 +165,10 @@ int yuv422_to_bgr(hipStream_t s, const uint8_t *src, int batch, int H, int W, in
 int yuv422_resize(hipStream_t s, const uint8_t *src, int n, int H, int W, int order, int flip, int oh, int ow, uint8_t *out);
 // the JPEG decoder's two halves (jpeg_dec.hip), as the ingest ring drives them: a header into a record with the status a decoder of h x w
 // gives it (returned too; the reason is left in dd_last_error), and upload + kernels for n records without a host wait
-int jpegdec_parse(const uint8_t *file, size_t n, int h, int w, dd_jpeg_info *rec);
-int jpegdec_launch(dd_jpegdec *dec, dd_jpeg_info *recs_host, const uint8_t *bytes_host, size_t n_bytes, int n, uint8_t *out_dev, int *status_dev, hipStream_t s,
-                   hipEvent_t uploaded);
+// scans / scans_host: NULL, or (a decoder made with DD_JPEGDEC_PROGRESSIVE) where each file's scan script goes, kept like the records
+int jpegdec_parse(const uint8_t *file, size_t n, int h, int w, dd_jpeg_info *rec, dd_jpeg_scans *scans);
+int jpegdec_launch(dd_jpegdec *dec, dd_jpeg_info *recs_host, dd_jpeg_scans *scans_host, const uint8_t *bytes_host, size_t n_bytes, int n, uint8_t *out_dev, int *status_dev,
+                   hipStream_t s, hipEvent_t uploaded);
 int resize_lanczos(hipStream_t s, int device, const uint8_t *src, int H, int W, int src_c, int swap_rb, uint8_t *dst,
                    int h, int w, uint8_t *tmp, int batch);
 size_t ssd_post_scratch_bytes(int n_anchors, int batch);

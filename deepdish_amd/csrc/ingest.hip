@@ -46,6 +46,7 @@ struct dd_ingest {
     // fill and whether the slot was submitted since it was last reset
     dd_jpegdec *dec = nullptr;
     std::vector<dd_jpeg_info *> h_recs;
+    std::vector<dd_jpeg_scans *> h_scans;     // beside the records, in a ring that takes progressive files (dd_ingest_create_jpeg_ex); else empty
     std::vector<int *> h_status, d_status;
     std::vector<size_t> fill;
     std::vector<char> stale;
@@ -56,7 +57,7 @@ constexpr int INGEST_JPEG = 3, INGEST_YUY2 = 4, INGEST_UYVY = 5;
 static bool ingest_is_422(int format) { return format == INGEST_YUY2 || format == INGEST_UYVY; }
 
 static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip,
-                         int pixel_format, dd_ingest **out, size_t jpeg_slot_bytes = 0, int jpeg_scale = 1) {
+                         int pixel_format, dd_ingest **out, size_t jpeg_slot_bytes = 0, int jpeg_scale = 1, int jpeg_flags = 0) {
     DD_REQUIRE(ctx && out && slots > 0 && n_streams > 0 && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0, DD_E_ARG,
                "%s: bad argument", who);
     DD_REQUIRE((pixel_format >= 0 && pixel_format <= 2) || ingest_is_422(pixel_format) || (pixel_format == INGEST_JPEG && jpeg_slot_bytes), DD_E_ARG,
@@ -110,7 +111,7 @@ static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams,
         DD_HIP(hipMemcpy(g->d_boxes, boxes.data(), boxes.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     if (pixel_format == INGEST_JPEG) {
-        if (int rc = dd_jpegdec_create_scaled(ctx, src_h, src_w, jpeg_scale, n_streams, (int64_t)jpeg_slot_bytes, &g->dec)) return rc;
+        if (int rc = dd_jpegdec_create_ex(ctx, src_h, src_w, jpeg_scale, jpeg_flags, n_streams, (int64_t)jpeg_slot_bytes, &g->dec)) return rc;
         for (int i = 0; i < slots; ++i) {
             dd_jpeg_info *r = nullptr;
             int *hs = nullptr, *ds = nullptr;
@@ -118,6 +119,12 @@ static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams,
             DD_HIP(hipHostMalloc(reinterpret_cast<void **>(&hs), (size_t)n_streams * sizeof(int), hipHostMallocDefault));
             DD_HIP(hipMalloc(reinterpret_cast<void **>(&ds), (size_t)n_streams * sizeof(int)));
             g->h_recs.push_back(r); g->h_status.push_back(hs); g->d_status.push_back(ds);
+            if (jpeg_flags & DD_JPEGDEC_PROGRESSIVE) {
+                dd_jpeg_scans *sc = nullptr;
+                DD_HIP(hipHostMalloc(reinterpret_cast<void **>(&sc), (size_t)n_streams * sizeof(dd_jpeg_scans), hipHostMallocDefault));
+                memset(sc, 0, (size_t)n_streams * sizeof(dd_jpeg_scans));
+                g->h_scans.push_back(sc);
+            }
             g->fill.push_back(0); g->stale.push_back(1);
         }
     }
@@ -152,6 +159,12 @@ int dd_ingest_create_jpeg_scaled(dd_ctx *ctx, int slots, int n_streams, int src_
     return ingest_create("dd_ingest_create_jpeg_scaled", ctx, slots, n_streams, src_h, src_w, dst_h, dst_w, flip, INGEST_JPEG, out, (size_t)slot_bytes, scale);
 }
 
+int dd_ingest_create_jpeg_ex(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip, int scale, int flags, int64_t slot_bytes,
+                             dd_ingest **out) {
+    DD_REQUIRE(slot_bytes >= 1, DD_E_ARG, "dd_ingest_create_jpeg_ex: slot_bytes %lld", (long long)slot_bytes);
+    return ingest_create("dd_ingest_create_jpeg_ex", ctx, slots, n_streams, src_h, src_w, dst_h, dst_w, flip, INGEST_JPEG, out, (size_t)slot_bytes, scale, flags);
+}
+
 int dd_ingest_jpeg_put(dd_ingest *g, int slot, int stream, const uint8_t *data_host, int64_t n) {
     DD_REQUIRE(g && data_host && slot >= 0 && slot < g->slots && stream >= 0 && stream < g->S && n >= 1 && n <= 0x7fffffffll, DD_E_ARG,
                "dd_ingest_jpeg_put: bad argument");
@@ -169,7 +182,7 @@ int dd_ingest_jpeg_put(dd_ingest *g, int slot, int stream, const uint8_t *data_h
     // the copy and the parse run outside the lock: decoder threads share that work.  A stream's record belongs to the thread that puts it.
     memcpy(g->h_raw[slot] + at, data_host, (size_t)n);
     dd_jpeg_info *rec = &g->h_recs[slot][stream];
-    ddk::jpegdec_parse(g->h_raw[slot] + at, (size_t)n, g->sh, g->sw, rec);
+    ddk::jpegdec_parse(g->h_raw[slot] + at, (size_t)n, g->sh, g->sw, rec, g->h_scans.empty() ? nullptr : &g->h_scans[slot][stream]);
     rec->file_offset = (int64_t)at;
     return DD_OK;
 }
@@ -206,6 +219,7 @@ int dd_ingest_destroy(dd_ingest *g) {
     }
     if (g->d_boxes) (void)hipFree(g->d_boxes);
     if (g->d_stage) (void)hipFree(g->d_stage);
+    for (dd_jpeg_scans *sc : g->h_scans) (void)hipHostFree(sc);
     for (size_t i = 0; i < g->h_recs.size(); ++i) {
         (void)hipHostFree(g->h_recs[i]);
         (void)hipHostFree(g->h_status[i]);
@@ -241,7 +255,8 @@ int dd_ingest_submit(dd_ingest *g, int slot) {
         if (int rc = ingest_jpeg_reset(g, slot)) return rc;                         // a submit without a put: every stream reports "no frame"
         if (g->used[slot]) DD_HIP(hipStreamWaitEvent(g->copy, g->done[slot], 0));
         uint8_t *dst = g->transform ? g->d_stage : g->d_out[slot];
-        int rc = ddk::jpegdec_launch(g->dec, g->h_recs[slot], g->h_raw[slot], g->fill[slot], g->S, dst, g->d_status[slot], g->copy, nullptr);
+        int rc = ddk::jpegdec_launch(g->dec, g->h_recs[slot], g->h_scans.empty() ? nullptr : g->h_scans[slot], g->h_raw[slot], g->fill[slot], g->S, dst, g->d_status[slot],
+                                     g->copy, nullptr);
         if (rc == DD_OK && g->transform) rc = ddk::crop_resize(g->copy, g->d_stage, g->jh, g->jw, g->d_boxes, g->S, g->dh, g->dw, g->d_out[slot]);
         if (rc != DD_OK) return rc;
         DD_HIP(hipMemcpyAsync(g->h_status[slot], g->d_status[slot], (size_t)g->S * sizeof(int), hipMemcpyDeviceToHost, g->copy));

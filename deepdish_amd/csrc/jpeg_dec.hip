@@ -18,6 +18,16 @@
 // same markers and entropy kernels and then jpeg_pixels_scaled_k<S> (jpeg_planes_scaled_k<S>) in place of the last: every block goes
 // straight to 4x4, 2x2 or 1x1 samples (csrc/jpeg_dec_dev.h), the band's planes shrink with it, 4:2:0 chroma is not up-sampled at all, and
 // the frame written is ceil(H / S) x ceil(W / S).  The coefficient buffer keeps its full-size layout.
+//
+// A decoder made with DD_JPEGDEC_PROGRESSIVE takes progressive (SOF2) files as well, beside baseline ones in the same call.  Such a file
+// ends in the same coefficients in the same blocks, so everything behind the entropy stage stays as it is.  The host walks the whole file
+// into a scan script (csrc/jpeg_parse.h jpd_parse_scans: dd_jpeg_scans, uploaded beside the records) and gives every scan a level, one
+// more than the highest level of an earlier scan of the same component whose band overlaps its own; then
+//   jpeg_prog_markers_k   one workgroup per scan finds its RSTn markers;
+//   jpeg_prog_entropy_k   launched once per level, one lane per (scan, restart interval) of that level over all files of the call
+//                         (libjpeg's default script: 10 scans, 3 launches): jdphuff.c's four scan kinds (csrc/jpeg_dec_dev.h) into the same
+//                         zeroed coefficient buffer, in the same MCU-interleaved block order.  Scans of one level write different words.
+// A decoder made without the flag hands no such file on (DD_JPEG_ST_HEADER, as ever) and launches neither.
 #include "common.h"
 #include "jpeg_dec_dev.h"
 #include <cstdlib>
@@ -103,6 +113,10 @@ __global__ __launch_bounds__(JD_T) void jpeg_markers_k(const dd_jpeg_info *__res
         if (tid == 0) mark[f] = r.status, status[f] = r.status;
         return;
     }
+    if (r.sof == 0xC2) {                                        // only a decoder that takes progressive files hands one on: jpeg_prog_markers_k walks its scans
+        if (tid == 0) mark[f] = DD_JPEG_ST_OK, status[f] = DD_JPEG_ST_OK;
+        return;
+    }
     const uint8_t *scan = bytes + r.file_offset + r.scan_offset;
     const uint32_t len = (uint32_t)r.scan_length;
     const int n_int = r.n_intervals;
@@ -156,6 +170,85 @@ __global__ __launch_bounds__(64) void jpeg_entropy_k(const dd_jpeg_info *__restr
     const uint32_t len = (uint32_t)r.scan_length;
     const uint32_t s = min(iv_start[idx], len), e = min(iv_end[idx], len);
     if (jpd_decode_interval(r, scan, s, e, m0, nm, coef + (size_t)f * coef_stride) != DD_JPEG_ST_OK) status[f] = DD_JPEG_ST_DATA;
+}
+
+// ---- progressive files (SOF2): only a decoder made with DD_JPEGDEC_PROGRESSIVE launches these two.
+
+// jpeg_markers_k for the scans of progressive files: one workgroup per (file, scan), `max_scans` of them a file.  iv_start / iv_end: per
+// restart interval of the scan, offsets into the scan's bytes, at the scan's interval_base.  A wrong marker count or sequence in any scan
+// sets the file's mark and status to DD_JPEG_ST_DATA (jpeg_markers_k has set them to OK).
+__global__ __launch_bounds__(JD_T) void jpeg_prog_markers_k(const dd_jpeg_info *__restrict__ recs, const dd_jpeg_scans *__restrict__ scans, int max_scans,
+                                                            const uint8_t *__restrict__ bytes, uint32_t *__restrict__ iv_start, uint32_t *__restrict__ iv_end,
+                                                            int *__restrict__ mark, int *__restrict__ status) {
+    __shared__ int sc[4];
+    __shared__ int bad;
+    const int f = blockIdx.x / max_scans, si = blockIdx.x - f * max_scans, tid = threadIdx.x;
+    const dd_jpeg_info &r = recs[f];
+    if (r.status != DD_JPEG_ST_OK || r.sof != 0xC2 || si >= scans[f].n_scans) return;
+    const dd_jpeg_scan &s = scans[f].scan[si];
+    const uint8_t *scan = bytes + r.file_offset + s.offset;
+    const uint32_t len = (uint32_t)s.length;
+    const int n_int = s.n_intervals;
+    uint32_t *st = iv_start + s.interval_base, *en = iv_end + s.interval_base;
+    if (tid == 0) bad = 0, st[0] = 0;
+    int found = 0;
+    for (uint32_t w0 = 0; w0 + 1 < len; w0 += JD_T * JD_CHUNK) {
+        const uint32_t p0 = w0 + (uint32_t)tid * JD_CHUNK;
+        int cnt = 0;
+        for (uint32_t p = p0; p < p0 + JD_CHUNK && p + 1 < len; ++p) cnt += jpd_rst_at(scan, p) >= 0 ? 1 : 0;
+        int all;
+        int k = found + jd_scan(cnt, sc, all);
+        if (cnt)
+            for (uint32_t p = p0; p < p0 + JD_CHUNK && p + 1 < len; ++p) {
+                const int m = jpd_rst_at(scan, p);
+                if (m < 0) continue;
+                if (m != (k & 7) || k + 1 >= n_int) bad = 1;
+                else en[k] = p, st[k + 1] = p + 2;
+                ++k;
+            }
+        found += all;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        en[n_int - 1] = len;
+        if (bad || found != n_int - 1) mark[f] = DD_JPEG_ST_DATA, status[f] = DD_JPEG_ST_DATA;
+    }
+}
+
+// One lane per (scan, restart interval) of level `level`, `per` of them in a wave; `total` lanes over all files of the call.  A file's
+// lanes of this level start at its level_base[level], its scans of the level following each other in file order.  Scans of one level write
+// different int16 words of the frame's coefficients (csrc/jpeg_parse.h gives the levels), so the lanes of a launch do not race; what a
+// scan refines was written by an earlier launch.  Files whose mark is set are not decoded.
+__global__ __launch_bounds__(64) void jpeg_prog_entropy_k(const dd_jpeg_info *__restrict__ recs, const dd_jpeg_scans *__restrict__ scans, int n, int level, int total, int per,
+                                                          const uint8_t *__restrict__ bytes, const uint32_t *__restrict__ iv_start, const uint32_t *__restrict__ iv_end,
+                                                          const int *__restrict__ mark, int16_t *__restrict__ coef, long long coef_stride, int *__restrict__ status) {
+    if ((int)threadIdx.x >= per) return;
+    const long long idx = (long long)blockIdx.x * per + threadIdx.x;
+    if (idx >= total) return;
+    int lo = 0, hi = n - 1;                                     // the last file whose lanes of this level start at or before idx
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (scans[mid].level_base[level] <= idx) lo = mid;
+        else hi = mid - 1;
+    }
+    const int f = lo;
+    const dd_jpeg_info &r = recs[f];
+    const dd_jpeg_scans &S = scans[f];
+    if (r.status != DD_JPEG_ST_OK || r.sof != 0xC2 || mark[f] != DD_JPEG_ST_OK) return;
+    int iv = (int)(idx - S.level_base[level]), si = 0;
+    const int n_scans = min(S.n_scans, DD_JPEG_MAX_SCANS);
+    for (; si < n_scans; ++si) {
+        if (S.scan[si].level != level) continue;
+        if (iv < S.scan[si].n_intervals) break;
+        iv -= S.scan[si].n_intervals;
+    }
+    if (si >= n_scans) return;
+    const dd_jpeg_scan &sc = S.scan[si];
+    const int units = sc.blocks_x * sc.blocks_y, ri = sc.restart_interval ? sc.restart_interval : units;
+    const int u0 = iv * ri, nu = min(ri, units - u0);
+    const uint32_t len = (uint32_t)sc.length;
+    const uint32_t s = min(iv_start[sc.interval_base + iv], len), e = min(iv_end[sc.interval_base + iv], len);
+    if (jpd_prog_decode_interval(r, sc, S.pool, bytes + r.file_offset + sc.offset, s, e, u0, nu, coef + (size_t)f * coef_stride) != DD_JPEG_ST_OK) status[f] = DD_JPEG_ST_DATA;
 }
 
 // Block `blk` of a frame: dequantise and transform.  rows: -1 all eight to dst (stride bytes apart), else that one row to dst.
@@ -503,19 +596,27 @@ struct dd_jpegdec {
     hipEvent_t uploaded = nullptr;
     bool profile = false, profiled = false;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};       // profile: call start, uploads done, markers, entropy, pixels
+    // DD_JPEGDEC_PROGRESSIVE only: the scan scripts beside the records, the scans' interval bounds, and the profile's events around each level
+    bool progressive = false;
+    DevBuf scans, pstarts;
+    PinBuf scans_host;
+    int levels_run = 0;
+    hipEvent_t lev[DD_JPEG_MAX_LEVELS + 1] = {};
 };
 
 namespace ddk {
 
-// The header of one file into *rec, with the status a decoder of h x w gives it (a NULL or empty file: DD_JPEG_ST_NO_FRAME).
-int jpegdec_parse(const uint8_t *file, size_t n, int h, int w, dd_jpeg_info *rec) {
+// The header of one file into *rec, with the status a decoder of h x w gives it (a NULL or empty file: DD_JPEG_ST_NO_FRAME).  scans: NULL,
+// or where a decoder that takes progressive files keeps this file's scan script (n_scans 0 for every other file).
+int jpegdec_parse(const uint8_t *file, size_t n, int h, int w, dd_jpeg_info *rec, dd_jpeg_scans *scans) {
     char msg[320];
+    if (scans) scans->n_scans = scans->n_tables = scans->n_levels = 0;
     if (!file || n == 0) {
         memset(rec, 0, sizeof(*rec));
         rec->status = DD_JPEG_ST_NO_FRAME;
         return rec->status;
     }
-    if (jpd_parse(file, n, rec, msg, sizeof(msg)) != DD_JPEG_R_OK) {
+    if ((scans ? jpd_parse_scans(file, n, rec, scans, msg, sizeof(msg)) : jpd_parse(file, n, rec, msg, sizeof(msg))) != DD_JPEG_R_OK) {
         dd_set_error("%s", msg);
         rec->status = DD_JPEG_ST_HEADER;
     } else if (rec->height != h || rec->width != w) {
@@ -528,20 +629,46 @@ int jpegdec_parse(const uint8_t *file, size_t n, int h, int w, dd_jpeg_info *rec
 // recs_host: n records from jpegdec_parse, in memory that stays as it is until the stream has run the upload (pinned: the copy is then
 // asynchronous); file i lies at bytes_host + recs_host[i].file_offset, all within n_bytes.  Fills the records' decoder fields, uploads
 // records and bytes in one copy each (then records `uploaded`, if given), and queues the kernels on s.  No host wait.
-int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, const uint8_t *bytes_host, size_t n_bytes, int n, uint8_t *out_dev, int *status_dev, hipStream_t s,
-                   hipEvent_t uploaded) {
+// scans_host: NULL, or n scan scripts from jpegdec_parse, kept like the records (a decoder that takes progressive files).
+int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, dd_jpeg_scans *scans_host, const uint8_t *bytes_host, size_t n_bytes, int n, uint8_t *out_dev, int *status_dev,
+                   hipStream_t s, hipEvent_t uploaded) {
     DD_REQUIRE(n >= 1 && n <= d->max_frames, DD_E_CAPACITY, "jpeg decoder: %d frames in a call (1 .. %d)", n, d->max_frames);
     DD_REQUIRE(n_bytes <= d->max_bytes, DD_E_CAPACITY, "jpeg decoder: %zu bytes of files in a call (at most %zu)", n_bytes, d->max_bytes);
     const JdGeom &g = d->g;
-    long long total = 0;
+    DD_REQUIRE(!scans_host || d->progressive, DD_E_STATE, "jpeg decoder: scan scripts for a decoder that was not made to take progressive files");
+    long long total = 0, ptotal = 0, level_total[DD_JPEG_MAX_LEVELS] = {};
+    int max_scans = 0, n_levels = 0;
     size_t lds = 0;
     bool any = false, any_planes = false;
     for (int i = 0; i < n; ++i) {
         dd_jpeg_info &r = recs_host[i];
         r.interval_base = (int32_t)total;
+        if (scans_host) {
+            dd_jpeg_scans &S = scans_host[i];
+            for (int l = 0; l < DD_JPEG_MAX_LEVELS; ++l) S.level_base[l] = (int32_t)level_total[l];
+            if (r.status != DD_JPEG_ST_OK || r.sof != 0xC2) S.n_scans = S.n_levels = 0;
+        }
         if (r.status != DD_JPEG_ST_OK) {
             r.n_intervals = 0;
             continue;
+        }
+        if (scans_host && scans_host[i].n_scans) {
+            dd_jpeg_scans &S = scans_host[i];
+            DD_REQUIRE(S.n_scans <= DD_JPEG_MAX_SCANS && S.n_levels <= DD_JPEG_MAX_LEVELS, DD_E_ARG, "jpeg decoder: file %d: %d scans at %d levels", i, S.n_scans, S.n_levels);
+            for (int k = 0; k < S.n_scans; ++k) {
+                dd_jpeg_scan &sc = S.scan[k];
+                DD_REQUIRE(r.file_offset >= 0 && sc.offset >= 0 && sc.length >= 0 && (size_t)r.file_offset + (size_t)sc.offset + (size_t)sc.length <= n_bytes, DD_E_ARG,
+                           "jpeg decoder: scan %d of file %d lies outside the %zu bytes given", k, i, n_bytes);
+                DD_REQUIRE(sc.level >= 0 && sc.level < S.n_levels && sc.n_intervals >= 1, DD_E_ARG, "jpeg decoder: scan %d of file %d: level %d, %d intervals", k, i, sc.level,
+                           sc.n_intervals);
+                sc.interval_base = (int32_t)ptotal;
+                ptotal += sc.n_intervals;
+                level_total[sc.level] += sc.n_intervals;
+            }
+            DD_REQUIRE(ptotal <= 0x7fffffffll, DD_E_CAPACITY, "jpeg decoder: more than 2^31 restart intervals in a call");
+            max_scans = S.n_scans > max_scans ? S.n_scans : max_scans;
+            n_levels = S.n_levels > n_levels ? S.n_levels : n_levels;
+            r.n_intervals = 0, r.restart_interval = 0, r.scan_offset = 0, r.scan_length = 0;          // nothing for jpeg_entropy_k
         }
         DD_REQUIRE(r.file_offset >= 0 && (size_t)r.file_offset + (size_t)r.scan_offset + (size_t)r.scan_length <= n_bytes, DD_E_ARG,
                    "jpeg decoder: file %d lies outside the %zu bytes given", i, n_bytes);
@@ -554,6 +681,8 @@ int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, const uint8_t *bytes_
         DD_REQUIRE(total <= 0x7fffffffll, DD_E_CAPACITY, "jpeg decoder: more than 2^31 restart intervals in a call");
     }
     if (int rc = d->starts.reserve((size_t)(total + 1) * 2 * sizeof(uint32_t))) return rc;
+    if (max_scans)
+        if (int rc = d->pstarts.reserve((size_t)(ptotal + 1) * 2 * sizeof(uint32_t))) return rc;
     if (any_planes)
         if (int rc = d->planes.reserve((size_t)n * (size_t)g.plane_stride)) return rc;
     dd_jpeg_info *recs = d->recs.as<dd_jpeg_info>();
@@ -565,11 +694,19 @@ int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, const uint8_t *bytes_
     if (d->profile) DD_HIP(hipEventRecord(d->ev[0], s));
     DD_HIP(hipMemcpyAsync(recs, recs_host, (size_t)n * sizeof(dd_jpeg_info), hipMemcpyHostToDevice, s));
     if (n_bytes) DD_HIP(hipMemcpyAsync(bytes, bytes_host, n_bytes, hipMemcpyHostToDevice, s));
+    if (max_scans) DD_HIP(hipMemcpyAsync(d->scans.as<dd_jpeg_scans>(), scans_host, (size_t)n * sizeof(dd_jpeg_scans), hipMemcpyHostToDevice, s));
     if (uploaded) DD_HIP(hipEventRecord(uploaded, s));
     if (d->profile) DD_HIP(hipEventRecord(d->ev[1], s));
     hipLaunchKernelGGL(jpeg_markers_k, dim3((unsigned)n), dim3(JD_T), 0, s, recs, bytes, iv_start, iv_end, mark, status_dev);
     DD_LAUNCH_CHECK();
+    const dd_jpeg_scans *scans = d->scans.as<dd_jpeg_scans>();
+    uint32_t *piv_start = max_scans ? d->pstarts.as<uint32_t>() : nullptr, *piv_end = max_scans ? piv_start + ptotal + 1 : nullptr;
+    if (max_scans) {
+        hipLaunchKernelGGL(jpeg_prog_markers_k, dim3((unsigned)n * (unsigned)max_scans), dim3(JD_T), 0, s, recs, scans, max_scans, bytes, piv_start, piv_end, mark, status_dev);
+        DD_LAUNCH_CHECK();
+    }
     if (d->profile) DD_HIP(hipEventRecord(d->ev[2], s));
+    d->levels_run = 0;
     if (!any) return DD_OK;
     DD_HIP(hipMemsetAsync(coef, 0, (size_t)n * (size_t)g.coef_stride * sizeof(int16_t), s));
     // intervals per wave: a lane decodes serially, so few intervals are spread over many waves (one per SIMD and more: 256 CUs of 4 SIMDs),
@@ -577,9 +714,26 @@ int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, const uint8_t *bytes_
     int per = 64;
     while (per > 1 && total / per < 2048) per >>= 1;
     if (d->lanes) per = d->lanes;
-    hipLaunchKernelGGL(jpeg_entropy_k, dim3((unsigned)((total + per - 1) / per)), dim3(64), 0, s, recs, n, (int)total, per, bytes, iv_start, iv_end, mark, coef,
-                       g.coef_stride, status_dev);
-    DD_LAUNCH_CHECK();
+    if (total || !max_scans) {                                  // a call of progressive files alone has nothing for it
+        hipLaunchKernelGGL(jpeg_entropy_k, dim3((unsigned)((total + per - 1) / per)), dim3(64), 0, s, recs, n, (int)total, per, bytes, iv_start, iv_end, mark, coef,
+                           g.coef_stride, status_dev);
+        DD_LAUNCH_CHECK();
+    }
+    if (max_scans) {
+        if (d->profile) DD_HIP(hipEventRecord(d->lev[0], s));
+        for (int l = 0; l < n_levels; ++l) {
+            const long long lt = level_total[l];
+            int lper = 64;
+            while (lper > 1 && lt / lper < 2048) lper >>= 1;
+            if (d->lanes) lper = d->lanes;
+            if (lt)
+                hipLaunchKernelGGL(jpeg_prog_entropy_k, dim3((unsigned)((lt + lper - 1) / lper)), dim3(64), 0, s, recs, scans, n, l, (int)lt, lper, bytes, piv_start, piv_end, mark,
+                                   coef, g.coef_stride, status_dev);
+            DD_LAUNCH_CHECK();
+            if (d->profile) DD_HIP(hipEventRecord(d->lev[l + 1], s));
+        }
+        d->levels_run = n_levels;
+    }
     if (d->profile) DD_HIP(hipEventRecord(d->ev[3], s));
     const unsigned grid = (unsigned)n * (unsigned)g.max_bands;
     if (d->scale != 1) {
@@ -613,6 +767,16 @@ int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, const uint8_t *bytes_
 }  // namespace ddk
 
 extern "C" {
+
+int dd_jpeg_parse_scans(const uint8_t *file_host, int64_t n, dd_jpeg_info *info, dd_jpeg_scans *scans) {
+    DD_REQUIRE(file_host && info && scans && n >= 0, DD_E_ARG, "dd_jpeg_parse_scans: NULL argument or a negative length");
+    char msg[320];
+    if (jpd_parse_scans(file_host, (size_t)n, info, scans, msg, sizeof(msg)) != DD_JPEG_R_OK) {
+        dd_set_error("%s", msg);
+        return DD_E_FORMAT;
+    }
+    return DD_OK;
+}
 
 int dd_jpeg_parse(const uint8_t *file_host, int64_t n, dd_jpeg_info *info) {
     DD_REQUIRE(file_host && info && n >= 0, DD_E_ARG, "dd_jpeg_parse: NULL argument or a negative length");
@@ -652,11 +816,12 @@ int dd_jpeg_draft_scale(int src_w, int src_h, int dst_w, int dst_h) {
     return k >= 8 ? 8 : k >= 4 ? 4 : k >= 2 ? 2 : 1;
 }
 
-static int jd_create(const char *who, dd_ctx *ctx, int h, int w, int scale, int max_frames, int64_t max_bytes, dd_jpegdec **out) {
+static int jd_create(const char *who, dd_ctx *ctx, int h, int w, int scale, int flags, int max_frames, int64_t max_bytes, dd_jpegdec **out) {
     DD_REQUIRE(ctx && out, DD_E_ARG, "%s: NULL argument", who);
     JdGeom g;
     if (int rc = jd_geometry(h, w, who, &g)) return rc;
     DD_REQUIRE(jpd_scale_ok(scale), DD_E_ARG, "%s: scale %d is none of 1, 2, 4, 8", who, scale);
+    DD_REQUIRE((flags & ~DD_JPEGDEC_PROGRESSIVE) == 0, DD_E_ARG, "%s: flags 0x%x (DD_JPEGDEC_PROGRESSIVE or 0)", who, flags);
     DD_REQUIRE(max_frames >= 1 && (long long)max_frames * g.max_bands <= 0x7fffffffll, DD_E_ARG, "%s: max_frames %d", who, max_frames);
     DD_REQUIRE(max_bytes >= 1, DD_E_ARG, "%s: max_bytes %lld", who, (long long)max_bytes);
     DD_DEVICE(ctx);
@@ -671,6 +836,9 @@ static int jd_create(const char *who, dd_ctx *ctx, int h, int w, int scale, int 
     if (rc == DD_OK) rc = d->coef.reserve((size_t)max_frames * (size_t)g.coef_stride * sizeof(int16_t));
     if (rc == DD_OK) rc = d->mark.reserve((size_t)max_frames * sizeof(int));
     if (rc == DD_OK) rc = d->recs_host.reserve((size_t)max_frames * sizeof(dd_jpeg_info));
+    d->progressive = (flags & DD_JPEGDEC_PROGRESSIVE) != 0;
+    if (rc == DD_OK && d->progressive) rc = d->scans.reserve((size_t)max_frames * sizeof(dd_jpeg_scans));
+    if (rc == DD_OK && d->progressive) rc = d->scans_host.reserve((size_t)max_frames * sizeof(dd_jpeg_scans));
     if (rc == DD_OK && hipEventCreateWithFlags(&d->uploaded, hipEventDisableTiming) != hipSuccess) {
         dd_set_error("%s: hipEventCreateWithFlags failed", who);
         rc = DD_E_HIP;
@@ -684,11 +852,15 @@ static int jd_create(const char *who, dd_ctx *ctx, int h, int w, int scale, int 
 }
 
 int dd_jpegdec_create(dd_ctx *ctx, int h, int w, int max_frames, int64_t max_bytes, dd_jpegdec **out) {
-    return jd_create("dd_jpegdec_create", ctx, h, w, 1, max_frames, max_bytes, out);
+    return jd_create("dd_jpegdec_create", ctx, h, w, 1, 0, max_frames, max_bytes, out);
 }
 
 int dd_jpegdec_create_scaled(dd_ctx *ctx, int h, int w, int scale, int max_frames, int64_t max_bytes, dd_jpegdec **out) {
-    return jd_create("dd_jpegdec_create_scaled", ctx, h, w, scale, max_frames, max_bytes, out);
+    return jd_create("dd_jpegdec_create_scaled", ctx, h, w, scale, 0, max_frames, max_bytes, out);
+}
+
+int dd_jpegdec_create_ex(dd_ctx *ctx, int h, int w, int scale, int flags, int max_frames, int64_t max_bytes, dd_jpegdec **out) {
+    return jd_create("dd_jpegdec_create_ex", ctx, h, w, scale, flags, max_frames, max_bytes, out);
 }
 
 int dd_jpegdec_output_size(dd_jpegdec *d, int *out_h, int *out_w) {
@@ -702,8 +874,11 @@ int dd_jpegdec_destroy(dd_jpegdec *d) {
     if (d->ctx) (void)hipSetDevice(d->ctx->device);
     d->recs.release(), d->bytes.release(), d->coef.release(), d->starts.release(), d->mark.release(), d->planes.release();
     d->recs_host.release();
+    d->scans.release(), d->pstarts.release(), d->scans_host.release();
     if (d->uploaded) (void)hipEventDestroy(d->uploaded);
     for (hipEvent_t e : d->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : d->lev)
         if (e) (void)hipEventDestroy(e);
     delete d;
     return DD_OK;
@@ -714,6 +889,9 @@ int dd_jpegdec_profile(dd_jpegdec *d, int on) {
     DD_DEVICE(d->ctx);
     if (on)
         for (hipEvent_t &e : d->ev)
+            if (!e) DD_HIP(hipEventCreate(&e));
+    if (on && d->progressive)
+        for (hipEvent_t &e : d->lev)
             if (!e) DD_HIP(hipEventCreate(&e));
     d->profile = on != 0;
     d->profiled = false;
@@ -729,23 +907,35 @@ int dd_jpegdec_profile_read(dd_jpegdec *d, float *ms_host) {
     return DD_OK;
 }
 
+int dd_jpegdec_profile_levels(dd_jpegdec *d, float *ms_host, int *n_levels_host) {
+    DD_REQUIRE(d && ms_host && n_levels_host, DD_E_ARG, "dd_jpegdec_profile_levels: NULL argument");
+    DD_REQUIRE(d->profiled, DD_E_STATE, "dd_jpegdec_profile_levels: no profiled decode (dd_jpegdec_profile(dec, 1), then a decode with a frame to decode)");
+    DD_DEVICE(d->ctx);
+    DD_HIP(hipEventSynchronize(d->ev[4]));
+    for (int i = 0; i < DD_JPEG_MAX_LEVELS; ++i) ms_host[i] = 0.f;
+    for (int i = 0; i < d->levels_run; ++i) DD_HIP(hipEventElapsedTime(&ms_host[i], d->lev[i], d->lev[i + 1]));
+    *n_levels_host = d->levels_run;
+    return DD_OK;
+}
+
 int dd_jpegdec_decode(dd_jpegdec *d, const uint8_t *files_host, const int64_t *offsets, const int64_t *lengths, int n, uint8_t *out_dev, int *status_dev, void *stream) {
     DD_REQUIRE(d && files_host && offsets && lengths && out_dev && status_dev, DD_E_ARG, "dd_jpegdec_decode: NULL argument");
     DD_REQUIRE(n >= 1 && n <= d->max_frames, DD_E_CAPACITY, "dd_jpegdec_decode: %d frames (1 .. %d)", n, d->max_frames);
     DD_DEVICE(d->ctx);
     hipStream_t s = dd_pick_stream(d->ctx, stream);
     dd_jpeg_info *recs = d->recs_host.as<dd_jpeg_info>();
+    dd_jpeg_scans *scans = d->progressive ? d->scans_host.as<dd_jpeg_scans>() : nullptr;
     size_t n_bytes = 0;
     for (int i = 0; i < n; ++i) {
         DD_REQUIRE(offsets[i] >= 0 && lengths[i] >= 0 && lengths[i] <= 0x7fffffffll, DD_E_ARG, "dd_jpegdec_decode: file %d at offset %lld, length %lld", i,
                    (long long)offsets[i], (long long)lengths[i]);
         const size_t end = (size_t)offsets[i] + (size_t)lengths[i];
         DD_REQUIRE(end <= d->max_bytes, DD_E_CAPACITY, "dd_jpegdec_decode: file %d ends at byte %zu, the decoder holds %zu", i, end, d->max_bytes);
-        ddk::jpegdec_parse(files_host + offsets[i], (size_t)lengths[i], d->g.H, d->g.W, &recs[i]);
+        ddk::jpegdec_parse(files_host + offsets[i], (size_t)lengths[i], d->g.H, d->g.W, &recs[i], scans ? &scans[i] : nullptr);
         recs[i].file_offset = offsets[i];
         if (lengths[i] && end > n_bytes) n_bytes = end;
     }
-    const int rc = ddk::jpegdec_launch(d, recs, files_host, n_bytes, n, out_dev, status_dev, s, d->uploaded);
+    const int rc = ddk::jpegdec_launch(d, recs, scans, files_host, n_bytes, n, out_dev, status_dev, s, d->uploaded);
     // the records' staging and the caller's bytes are free again once the two copies have run
     if (rc != DD_OK) {
         (void)hipStreamSynchronize(s);

@@ -1,7 +1,8 @@
 // The statements of the baseline JPEG decoder that run on the card, as __host__ __device__ code: the bit reader, the Huffman decoder,
 // one restart interval's MCUs, and jidctint.c's accurate-integer IDCT.  csrc/jpeg_dec.hip runs them in its kernels;
 // scripts/jpeg_decode_check.cpp runs the same statements on the host under the address and undefined-behaviour sanitizers, over
-// truncated and damaged files, before the card sees any.
+// truncated and damaged files, before the card sees any.  The progressive scans' statements (jdphuff.c) stand at the end, with their own
+// bounds; scripts/jpeg_prog_check.cpp runs those.
 //
 // The bounds are part of the design:
 //   - the bit reader never reads at or beyond the interval's end: it yields zero bits there and counts them (`phantom`);
@@ -289,3 +290,153 @@ JPD_HD void jpd_idct2(const int32_t (&d)[64], int (&o)[4]) {
 
 // jpeg_idct_1x1: the dequantised DC term, descaled by 3.
 JPD_HD int jpd_idct1(int32_t dc) { return jpd_range_limit(jpd_sar((uint32_t)dc + 4u, 3)); }
+
+// ---- progressive scans (libjpeg's jdphuff.c; tests/jpeg_prog_ref.py is the definition).  One restart interval of one scan: its units
+// [unit0, unit0 + n_units) -- MCUs of the frame for a scan of several components, the component's own blocks in raster order for a scan of
+// one -- from bytes[start .. end) into the frame's coefficient buffer, which keeps the baseline layout.  The bounds, beside the bit reader's:
+//   - the unit loop runs n_units, the block loop the unit's block count; every pass of a coefficient loop advances k, which stops at Se <= 63;
+//   - a block's address comes from the record alone (parsed and checked on the host), never from the entropy-coded bytes;
+//   - an EOB run only ever counts down, once per block.
+// What no valid file holds is defined all the same: a first scan stores the low 16 bits of v << Al, a DC predictor wraps at 32 bits, a
+// refinement adds or subtracts 1 << Al in 16 bits, wrapping.  Shifts by Al (0 .. 13) are done in uint32_t.
+
+JPD_HD int jpd_bit(JpdBits &b) {
+    if (b.n < 16) jpd_bits_fill(b);
+    return (int)jpd_take(b, 1);
+}
+
+// An EOBn symbol's run: 2^r blocks and r more bits, 1 .. 32767.
+JPD_HD int jpd_eobrun(JpdBits &b, int r) {
+    int run = 1 << r;
+    if (r) {
+        if (b.n < 16) jpd_bits_fill(b);
+        run += (int)jpd_take(b, r);
+    }
+    return run;
+}
+
+// A coefficient that is already non-zero, passed over by an AC refinement scan: one correction bit, and the coefficient is only read
+// when that bit is set.
+JPD_HD void jpd_refine_nonzero(JpdBits &b, int16_t *at, int p1) {
+    if (!jpd_bit(b)) return;
+    const int v = *at;
+    if (!(v & p1)) *at = (int16_t)(uint16_t)((uint32_t)v + (uint32_t)(v >= 0 ? p1 : -p1));
+}
+
+// Bit k: the block's coefficient at zigzag index k (1 .. 63) is non-zero.  An AC refinement scan asks this of every coefficient it passes;
+// 63 loads that do not depend on each other, in front of the block's serial walk, in place of one dependent load per coefficient.
+JPD_HD uint64_t jpd_nonzero_mask(const int16_t *blk) {
+    uint64_t nz = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+    for (int k = 1; k < 64; ++k) nz |= (uint64_t)(blk[JPD_ZIGZAG[k]] != 0) << k;
+    return nz;
+}
+
+// One block of the scan.  dc, ac: the tables the scan kind reads (the others may be NULL).  Returns DD_JPEG_ST_OK or DD_JPEG_ST_DATA.
+JPD_HD int jpd_prog_block(JpdBits &b, int ss, int se, int ah, int al, const dd_jpeg_huff *dc, const dd_jpeg_huff *ac, int16_t *blk, uint32_t &pred, int &eobrun) {
+    const int p1 = 1 << al;
+    if (ss == 0) {
+        if (ah == 0) {                                                      // DC, first scan
+            const int s = jpd_symbol(b, *dc);
+            if (s < 0 || s > 11) return DD_JPEG_ST_DATA;
+            if (s) pred += (uint32_t)jpd_extend(b, s);
+            blk[0] = (int16_t)(uint16_t)(pred << al);
+        } else if (jpd_bit(b))                                              // DC, refinement
+            blk[0] = (int16_t)((uint16_t)blk[0] | (uint16_t)p1);
+        return DD_JPEG_ST_OK;
+    }
+    if (ah == 0) {                                                          // AC, first scan
+        if (eobrun > 0) {
+            --eobrun;
+            return DD_JPEG_ST_OK;
+        }
+        for (int k = ss; k <= se; ++k) {
+            const int rs = jpd_symbol(b, *ac);
+            if (rs < 0) return DD_JPEG_ST_DATA;
+            const int r = rs >> 4, s = rs & 15;
+            if (s) {
+                k += r;
+                const uint32_t v = (uint32_t)jpd_extend(b, s);
+                if (k > se) return DD_JPEG_ST_DATA;
+                blk[JPD_ZIGZAG[k]] = (int16_t)(uint16_t)(v << al);
+            } else if (r == 15)
+                k += 15;
+            else {
+                eobrun = jpd_eobrun(b, r) - 1;
+                break;
+            }
+        }
+        return DD_JPEG_ST_OK;
+    }
+    int k = ss;                                                             // AC, refinement
+    const uint64_t nz = jpd_nonzero_mask(blk);                              // as the scan found the block: what it adds it does not pass again
+    if (eobrun == 0) {
+        for (; k <= se; ++k) {
+            const int rs = jpd_symbol(b, *ac);
+            if (rs < 0) return DD_JPEG_ST_DATA;
+            int r = rs >> 4, s = rs & 15;
+            if (s) {
+                if (s != 1) return DD_JPEG_ST_DATA;
+                s = jpd_bit(b) ? p1 : -p1;                                  // the new coefficient's sign comes in front of the correction bits
+            } else if (r != 15) {
+                eobrun = jpd_eobrun(b, r);
+                break;                                                      // the rest of this block is the run's first
+            }
+            for (; k <= se; ++k) {                                          // pass r coefficients that are still zero, refining the others on the way
+                if ((nz >> k) & 1) jpd_refine_nonzero(b, blk + JPD_ZIGZAG[k], p1);
+                else if (--r < 0) break;
+            }
+            if (s) {
+                if (k > se) return DD_JPEG_ST_DATA;
+                blk[JPD_ZIGZAG[k]] = (int16_t)(uint16_t)(uint32_t)s;                          // at the position the run lands on
+            }
+        }
+    }
+    if (eobrun > 0) {
+        for (; k <= se; ++k)
+            if ((nz >> k) & 1) jpd_refine_nonzero(b, blk + JPD_ZIGZAG[k], p1);
+        --eobrun;
+    }
+    return DD_JPEG_ST_OK;
+}
+
+// Where block (bx, by) of component c lies in the MCU-interleaved coefficient buffer (chroma is sampled 1 x 1: csrc/jpeg_parse.h).
+JPD_HD size_t jpd_block_at(const dd_jpeg_info &r, int c, int bx, int by) {
+    const int hs = c ? 1 : r.hmax, vs = c ? 1 : r.vmax;
+    const int base = c ? r.hmax * r.vmax + c - 1 : 0;
+    return ((size_t)(by / vs) * r.mcus_x + bx / hs) * r.blocks_per_mcu + base + (by % vs) * hs + bx % hs;
+}
+
+JPD_HD int jpd_prog_decode_interval(const dd_jpeg_info &r, const dd_jpeg_scan &sc, const dd_jpeg_huff *pool, const uint8_t *bytes, uint32_t start, uint32_t end, int unit0,
+                                    int n_units, int16_t *coef) {
+    JpdBits b;
+    jpd_bits_open(b, bytes, start, end);
+    uint32_t pred[3] = {0, 0, 0};
+    int eobrun = 0;
+    const int ss = sc.ss & 63, se = sc.se & 63, ah = sc.ah & 15, al = sc.al & 15;
+    if (sc.blocks_x < 1) return DD_JPEG_ST_DATA;
+    const dd_jpeg_huff *ac = sc.ac >= 0 && sc.ac < DD_JPEG_MAX_TABLES ? pool + sc.ac : nullptr;
+    if (ss > 0 && !ac) return DD_JPEG_ST_DATA;
+    const bool mcus = sc.ncomp > 1;
+    for (int u = 0; u < n_units; ++u) {
+        const int ux = (unit0 + u) % sc.blocks_x, uy = (unit0 + u) / sc.blocks_x;
+        for (int k = 0; k < (mcus ? sc.ncomp : 1) && k < 3; ++k) {
+            const int c = sc.comp[k] >= 0 && sc.comp[k] < 3 ? sc.comp[k] : 0;
+            const dd_jpeg_huff *dc = sc.dc[k] >= 0 && sc.dc[k] < DD_JPEG_MAX_TABLES ? pool + sc.dc[k] : nullptr;
+            if (ss == 0 && ah == 0 && !dc) return DD_JPEG_ST_DATA;
+            const int hs = mcus && c == 0 ? r.hmax : 1, vs = mcus && c == 0 ? r.vmax : 1;
+            for (int y = 0; y < vs; ++y)
+                for (int x = 0; x < hs; ++x) {
+                    int16_t *blk = coef + jpd_block_at(r, c, ux * hs + x, uy * vs + y) * 64;
+                    if (jpd_prog_block(b, ss, se, ah, al, dc, ac, blk, pred[c], eobrun) != DD_JPEG_ST_OK) return DD_JPEG_ST_DATA;
+                    if (b.n < b.phantom) return DD_JPEG_ST_DATA;          // bits were taken from beyond the interval's end
+                }
+        }
+    }
+    if (eobrun) return DD_JPEG_ST_DATA;                                     // an EOB run that outlives its interval
+    if (b.n - b.phantom >= 8) return DD_JPEG_ST_DATA;
+    if (b.pos < b.end && !(b.p[b.pos] == 0xFF && (b.pos + 1 >= b.end || b.p[b.pos + 1] != 0))) return DD_JPEG_ST_DATA;
+    return DD_JPEG_ST_OK;
+}

@@ -16,7 +16,12 @@ The way in is the mirror (csrc/jpeg_parse.h, csrc/jpeg_dec.hip): `parse(file)` r
 `JpegDecoder(H, W).decode(files)` turns files in host memory into BGR frames in HBM, byte for byte libjpeg's pixels (tests/jpeg_dec_ref.py,
 tests/test_gpu_jpeg_decode.py); the ingest ring's `pixel_format='jpeg'` slots (deepdish_amd/ingest.py) are built on it.  With `scale=2`, 4
 or 8 the decoder transforms every 8 x 8 block straight to 4 x 4, 2 x 2 or 1 x 1 samples, libjpeg's scale_denom and Pillow's Image.draft
-(tests/jpeg_scaled_ref.py), and `draft_scale(src, want)` picks the scale as Pillow does."""
+(tests/jpeg_scaled_ref.py), and `draft_scale(src, want)` picks the scale as Pillow does.
+
+Progressive (SOF2) files -- what cv2.imread reads without being asked, and what a CVAT directory re-saved by a tool usually holds -- are an
+option: `parse(file, progressive=True)`, `JpegDecoder(H, W, progressive=True)` and `FrameIngest(..., jpeg_progressive=True)`
+(tests/jpeg_prog_ref.py is the definition; jpeg_prog_entropy_k runs once per level of the scan script).  Without the option such a file is
+refused as before (reason 'progressive', ST_HEADER)."""
 import ctypes
 
 import numpy as np
@@ -123,7 +128,10 @@ DEC_PATH_LDS, DEC_PATH_PLANES = 0, 1
 E_FORMAT = -5
 ST_OK, ST_HEADER, ST_SIZE, ST_DATA, ST_NO_FRAME = 0, 1, 2, 3, 4
 REASONS = {0: 'ok', 1: 'truncated', 2: 'progressive', 3: 'arithmetic', 4: 'lossless', 5: 'precision', 6: 'components', 7: 'sampling',
-           8: 'scans', 9: 'huffman', 10: 'undefined', 11: 'size', 12: 'segment'}
+           8: 'scans', 9: 'huffman', 10: 'undefined', 11: 'size', 12: 'segment',
+           13: 'ac_components', 14: 'ac_before_dc', 15: 'first_ah', 16: 'refinement', 17: 'incomplete', 18: 'capacity'}
+MAX_SCANS, MAX_TABLES, MAX_LEVELS = 64, 32, 16
+DEC_PROGRESSIVE = 1
 
 
 class _Huff(ctypes.Structure):
@@ -142,15 +150,35 @@ class JpegInfo(ctypes.Structure):
                 + [('file_offset', ctypes.c_int64), ('quant', (ctypes.c_uint16 * 64) * 4), ('huff', _Huff * 4)])
 
 
-def parse(file):
+class JpegScan(ctypes.Structure):
+    """dd_jpeg_scan of include/deepdish_hip.h."""
+    _fields_ = ([('offset', ctypes.c_int32), ('length', ctypes.c_int32), ('ncomp', ctypes.c_int32), ('comp', ctypes.c_int32 * 3), ('dc', ctypes.c_int32 * 3)]
+                + [(k, ctypes.c_int32) for k in ('ac', 'ss', 'se', 'ah', 'al', 'restart_interval', 'blocks_x', 'blocks_y', 'n_intervals', 'level', 'interval_base')])
+
+
+class JpegScans(ctypes.Structure):
+    """dd_jpeg_scans of include/deepdish_hip.h."""
+    _fields_ = [('n_scans', ctypes.c_int32), ('n_tables', ctypes.c_int32), ('n_levels', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('level_base', ctypes.c_int32 * MAX_LEVELS), ('scan', JpegScan * MAX_SCANS), ('pool', _Huff * MAX_TABLES)]
+
+
+def parse(file, progressive=False):
     """The header of a baseline JPEG file, SOI .. the first SOS, as dd_jpeg_parse reads it -> dict.  Needs no device.  A file that is
-    refused raises DeepDishHipError with .reason (a word of REASONS) and the reason spelt out in the message."""
+    refused raises DeepDishHipError with .reason (a word of REASONS) and the reason spelt out in the message.
+
+    progressive=True reads progressive (SOF2) files as well (dd_jpeg_parse_scans, which walks the whole file): the dict then holds the frame
+    ('sof' 0xC2, no 'td' / 'ta' / 'huff', 'n_intervals' 0) and 'scans', one dict per SOS in file order -- 'comps', 'ss', 'se', 'ah', 'al',
+    'restart_interval' (the DRI in force: MCUs for a scan of several components, the component's blocks for one), 'blocks_x', 'blocks_y',
+    'n_intervals', 'level', 'offset', 'length' and 'dc' / 'ac', the (bits, vals) of the tables it reads -- with 'n_levels' and 'n_tables'.  A
+    baseline file gives the same dict as without the option."""
     data = bytes(file)
     info = JpegInfo()
-    rc = lib().dd_jpeg_parse(data, len(data), ctypes.byref(info))
+    scans = JpegScans() if progressive else None
+    who = 'dd_jpeg_parse_scans' if progressive else 'dd_jpeg_parse'
+    rc = lib().dd_jpeg_parse_scans(data, len(data), ctypes.byref(info), ctypes.byref(scans)) if progressive else lib().dd_jpeg_parse(data, len(data), ctypes.byref(info))
     if rc != 0:
         msg = lib().dd_last_error()
-        err = DeepDishHipError('dd_jpeg_parse failed (%d): %s' % (rc, msg.decode() if msg else '?'))
+        err = DeepDishHipError('%s failed (%d): %s' % (who, rc, msg.decode() if msg else '?'))
         err.code, err.reason = rc, REASONS.get(info.reason, '?') if rc == E_FORMAT else None
         raise err
     nc = info.ncomp
@@ -160,6 +188,17 @@ def parse(file):
     out['td'], out['ta'] = list(info.td[:nc]), list(info.ta[:nc])
     out['quant'] = {t: np.array(info.quant[t][:], np.int64) for t in range(4) if info.quant_defined[t]}
     out['huff'] = {(t >> 1, t & 1): (list(info.huff[t].bits), list(info.huff[t].vals[:info.huff[t].nvals])) for t in range(4) if info.huff[t].defined}
+    if progressive and scans.n_scans:
+        def table(i):
+            return (list(scans.pool[i].bits), list(scans.pool[i].vals[:scans.pool[i].nvals])) if i >= 0 else None
+        out['scans'] = []
+        for k in range(scans.n_scans):
+            sc = scans.scan[k]
+            d = {f: getattr(sc, f) for f in ('ss', 'se', 'ah', 'al', 'restart_interval', 'blocks_x', 'blocks_y', 'n_intervals', 'level', 'offset', 'length')}
+            d['comps'] = list(sc.comp[:sc.ncomp])
+            d['dc'], d['ac'] = [table(sc.dc[j]) for j in range(sc.ncomp)], table(sc.ac)
+            out['scans'].append(d)
+        out['n_levels'], out['n_tables'] = scans.n_levels, scans.n_tables
     return out
 
 
@@ -200,21 +239,30 @@ class JpegDecoder:
 
     scale=2, 4 or 8 decodes at that fraction, as libjpeg's scale_denom does (Pillow's im.draft(mode, (W // scale, H // scale)), byte for
     byte; parity with cv2.IMREAD_REDUCED_COLOR_* is not pinned): H x W stays what a file must state, and the frames are
-    [n, out_H, out_W, 3] with out_H = ceil(H / scale), out_W = ceil(W / scale)."""
+    [n, out_H, out_W, 3] with out_H = ceil(H / scale), out_W = ceil(W / scale).
 
-    def __init__(self, H, W, max_frames=16, max_bytes=None, context=None, scale=1):
+    progressive=True makes the decoder take progressive (SOF2) files too, at any scale, beside baseline files in the same call: byte for
+    byte libjpeg's pixels for a complete file (tests/jpeg_prog_ref.py).  parse(file, progressive=True) says what is refused: among it a
+    script that leaves coefficients undelivered, which libjpeg would smooth or zero-fill.  A decoder without the option gives such files
+    ST_HEADER and launches exactly what it always did."""
+
+    def __init__(self, H, W, max_frames=16, max_bytes=None, context=None, scale=1, progressive=False):
         from .runtime import default_context
         self.ctx = context or default_context()
         self.H, self.W, self.max_frames = int(H), int(W), int(max_frames)
         self.max_bytes = int(max_bytes) if max_bytes else self.max_frames * (self.H * self.W * 3 + 4096)
         self._h = None
         self.scale = scale
+        self.progressive = bool(progressive)
         h = P()
-        if scale == 1:
+        if scale != 1 and (not isinstance(scale, int) or isinstance(scale, bool)):
+            raise ValueError('scale %r is none of 1, 2, 4, 8' % (scale,))
+        if self.progressive:
+            check(lib().dd_jpegdec_create_ex(self.ctx.handle, self.H, self.W, scale, DEC_PROGRESSIVE, self.max_frames, self.max_bytes, ctypes.byref(h)),
+                  'dd_jpegdec_create_ex')
+        elif scale == 1:
             check(lib().dd_jpegdec_create(self.ctx.handle, self.H, self.W, self.max_frames, self.max_bytes, ctypes.byref(h)), 'dd_jpegdec_create')
         else:
-            if not isinstance(scale, int) or isinstance(scale, bool):
-                raise ValueError('scale %r is none of 1, 2, 4, 8' % (scale,))
             check(lib().dd_jpegdec_create_scaled(self.ctx.handle, self.H, self.W, scale, self.max_frames, self.max_bytes, ctypes.byref(h)),
                   'dd_jpegdec_create_scaled')
         self._h = h
@@ -239,6 +287,13 @@ class JpegDecoder:
         ms = (ctypes.c_float * 4)()
         check(lib().dd_jpegdec_profile_read(self._h, ms), 'dd_jpegdec_profile_read')
         return dict(zip(('upload', 'markers', 'entropy', 'pixels'), (float(v) for v in ms)))
+
+    def level_ms(self):
+        """progressive=True: milliseconds of jpeg_prog_entropy_k per level in the last profiled decode (waits for it); [] when the call held
+        no progressive file.  kernel_ms()['entropy'] covers them and jpeg_entropy_k."""
+        ms, n = (ctypes.c_float * MAX_LEVELS)(), ctypes.c_int()
+        check(lib().dd_jpegdec_profile_levels(self._h, ms, ctypes.byref(n)), 'dd_jpegdec_profile_levels')
+        return [float(v) for v in ms[:n.value]]
 
     def decode(self, files, out=None, status=None, stream=None):
         """files: a list of bytes objects -> (u8 [n, out_H, out_W, 3], int32 [n]).  out / status: tensors to write instead of new ones.  Queued on the context's stream (or

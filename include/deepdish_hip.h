@@ -872,6 +872,64 @@ int dd_jpegdec_output_size(dd_jpegdec *dec, int *out_h_host, int *out_w_host);
  * decode that is still at least dst_w x dst_h.  Returns the scale; DD_E_ARG for a side below 1.  Host only. */
 int dd_jpeg_draft_scale(int src_w, int src_h, int dst_w, int dst_h);
 
+/* ---- progressive files (SOF2), an option of the decoder.  cv2.imread, which the reference calls on images/frame_%06d.jpg
+ * (deepdish.py:685-689, :727), reads them without being asked, and a CVAT directory that a tool has re-saved holds them more often than
+ * not.  A progressive file ends in the same quantised coefficients as a baseline file, so only the entropy stage differs
+ * (jpeg_prog_entropy_k, libjpeg's jdphuff.c restated; tests/jpeg_prog_ref.py is the definition): the pixels are libjpeg's for a complete
+ * file, byte for byte Pillow's.  Nothing here changes what dd_jpeg_parse, dd_jpegdec_create(_scaled) or dd_ingest_create_jpeg(_scaled)
+ * do: they refuse such a file as before (DD_JPEG_R_PROGRESSIVE, DD_JPEG_ST_HEADER).
+ * Accepted: SOF2 at 8 bits with the components and samplings above; up to DD_JPEG_MAX_SCANS scans and DD_JPEG_MAX_TABLES DHT tables
+ * (slots 0 .. 3 of each class, redefined between scans at will); DC scans of any subset of the components in frame order; AC scans of one
+ * component; any DRI in front of any scan.  Refused by name, beside everything dd_jpeg_parse refuses: */
+#define DD_JPEG_R_AC_COMPONENTS 13  /* an AC scan (Ss > 0) of more than one component */
+#define DD_JPEG_R_AC_BEFORE_DC  14  /* an AC scan of a component whose DC scan has not come */
+#define DD_JPEG_R_FIRST_AH      15  /* the first scan of a band with Ah other than 0 */
+#define DD_JPEG_R_REFINEMENT    16  /* a refinement whose Ah is not the band's previous Al or whose Al is not Ah - 1; a band whose
+                                       coefficients stand at different bits; a band sent again */
+#define DD_JPEG_R_INCOMPLETE    17  /* the scans end with a coefficient of a component not delivered to bit 0: libjpeg would smooth or
+                                       zero-fill such a file, this build does not imitate that */
+#define DD_JPEG_R_CAPACITY      18  /* more scans or more Huffman tables than dd_jpeg_scans holds */
+/* DD_JPEG_R_PROGRESSIVE stays the reason for SOF6 (differential progressive, a hierarchical mode). */
+#define DD_JPEG_MAX_SCANS   64      /* libjpeg's and mozjpeg's scripts need at most 12 */
+#define DD_JPEG_MAX_TABLES  32
+#define DD_JPEG_MAX_LEVELS  16      /* a level lowers a band's Al by one, and Al is at most 13 */
+typedef struct dd_jpeg_scan {
+    int32_t offset, length;                      /* the entropy-coded bytes within the file: behind the SOS segment to the next marker that
+                                                    is neither RSTn nor a stuffed FF 00 */
+    int32_t ncomp, comp[3];                      /* indices into the frame's components, ascending */
+    int32_t dc[3], ac;                           /* indices into dd_jpeg_scans.pool; -1 where the scan reads no such table */
+    int32_t ss, se, ah, al;
+    int32_t restart_interval;                    /* the DRI in force at this SOS: MCUs for a scan of several components, blocks for one; 0: none */
+    int32_t blocks_x, blocks_y;                  /* the units the scan walks: the MCU grid, or one component's own ceil(w_c / 8) x ceil(h_c / 8) */
+    int32_t n_intervals;
+    int32_t level;                               /* one more than the highest level of an earlier scan of the same component whose band
+                                                    overlaps this one; scans of one level write different coefficients */
+    int32_t interval_base;                       /* filled by the decoder; 0 from dd_jpeg_parse_scans */
+} dd_jpeg_scan;
+typedef struct dd_jpeg_scans {
+    int32_t n_scans, n_tables, n_levels, reserved;        /* n_scans 0: a baseline file, all of it in dd_jpeg_info */
+    int32_t level_base[DD_JPEG_MAX_LEVELS];               /* filled by the decoder; 0 from dd_jpeg_parse_scans */
+    dd_jpeg_scan scan[DD_JPEG_MAX_SCANS];
+    dd_jpeg_huff pool[DD_JPEG_MAX_TABLES];                /* every DHT table of the file, in file order */
+} dd_jpeg_scans;
+/* dd_jpeg_parse for baseline and progressive files.  A baseline file gives exactly dd_jpeg_parse's *info and scans->n_scans 0.  For SOF2 the
+ * whole file is walked (entropy-coded bytes are skipped to the next marker, every read checked against n): *info holds the frame
+ * (sof 0xC2, no scan fields, no tables) and *scans the scan script.  Host only. */
+int dd_jpeg_parse_scans(const uint8_t *file_host, int64_t n, dd_jpeg_info *info, dd_jpeg_scans *scans);
+/* dd_jpegdec_create_scaled with flags: DD_JPEGDEC_PROGRESSIVE makes the decoder take SOF2 files too.  After jpeg_markers_k,
+ * jpeg_prog_markers_k finds every scan's RSTn markers, and jpeg_prog_entropy_k runs once per level over all files of the call, one lane per
+ * (scan, restart interval), into the same zeroed coefficient buffer; baseline files of the same call go through jpeg_entropy_k as ever, and
+ * the pixel kernels follow unchanged.  An error in any scan is DD_JPEG_ST_DATA for that file.  flags 0 is dd_jpegdec_create_scaled
+ * exactly; an unknown flag is DD_E_ARG. */
+#define DD_JPEGDEC_PROGRESSIVE 1
+int dd_jpegdec_create_ex(dd_ctx *ctx, int h, int w, int scale, int flags, int max_frames, int64_t max_bytes, dd_jpegdec **out);
+/* After a profiled decode on such a decoder: ms_host[DD_JPEG_MAX_LEVELS] = jpeg_prog_entropy_k per level, *n_levels_host how many ran
+ * (0: no progressive file in the call); dd_jpegdec_profile_read's third figure then covers both entropy kernels. */
+int dd_jpegdec_profile_levels(dd_jpegdec *dec, float *ms_host, int *n_levels_host);
+/* dd_ingest_create_jpeg_scaled with the same flags: a ring whose slots take progressive files as well (deepdish.py:685-689). */
+int dd_ingest_create_jpeg_ex(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip, int scale, int flags,
+                             int64_t slot_bytes, dd_ingest **out);
+
 /* ---------------------------------------------------------------- multi-GPU
  * Sum of the per-stream count vectors (pos, neg, int, del per label; deepdish.py:1141-1145).
  * The collective itself is issued by the host through torch.distributed (RCCL); this entry
