@@ -175,6 +175,7 @@ SIGNATURES = {
     'dd_jpeg_parse_scans': [P, c_int64, P, P],
     'dd_jpegdec_create_ex': [P, c_int, c_int, c_int, c_int, c_int, c_int64, POINTER(P)],
     'dd_jpegdec_profile_levels': [P, P, POINTER(c_int)],
+    'dd_jpegdec_split_stats': [P, P],
     'dd_counts_accumulate': [P, P, P, c_int, P],
 }
 _RESTYPE = {'dd_last_error': c_char_p}

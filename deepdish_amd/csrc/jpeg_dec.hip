@@ -28,6 +28,13 @@
 //                         (libjpeg's default script: 10 scans, 3 launches): jdphuff.c's four scan kinds (csrc/jpeg_dec_dev.h) into the same
 //                         zeroed coefficient buffer, in the same MCU-interleaved block order.  Scans of one level write different words.
 // A decoder made without the flag hands no such file on (DD_JPEG_ST_HEADER, as ever) and launches neither.
+//
+// A decoder made with DD_JPEGDEC_SPLIT gives a baseline file that is a single restart interval -- no restart markers: what cameras and
+// cv2.imencode write -- to a workgroup, not to one lane of jpeg_entropy_k:
+//   jpeg_split_entropy_k  one workgroup per such file cuts its scan into subsequences that the lanes decode from guessed states and then from
+//                         their predecessors' end states until none changes (Huffman data re-synchronises by itself), scans the blocks
+//                         begun and the DC sums, and decodes once more to store the coefficients: the sequential decode, cut into pieces.
+// Everything in front of and behind the entropy stage stays as it is; a decoder made without the flag does not launch it.
 #include "common.h"
 #include "jpeg_dec_dev.h"
 #include <cstdlib>
@@ -164,12 +171,152 @@ __global__ __launch_bounds__(64) void jpeg_entropy_k(const dd_jpeg_info *__restr
     const dd_jpeg_info &r = recs[f];
     const int iv = (int)(idx - r.interval_base);
     if (iv >= r.n_intervals || mark[f] != DD_JPEG_ST_OK) return;
+    if (r.reserved) return;                                     // DD_JPEGDEC_SPLIT: jpeg_split_entropy_k decodes this file
     const int mcus = r.mcus_x * r.mcus_y, ri = r.restart_interval ? r.restart_interval : mcus;
     const int m0 = iv * ri, nm = min(ri, mcus - m0);
     const uint8_t *scan = bytes + r.file_offset + r.scan_offset;
     const uint32_t len = (uint32_t)r.scan_length;
     const uint32_t s = min(iv_start[idx], len), e = min(iv_end[idx], len);
     if (jpd_decode_interval(r, scan, s, e, m0, nm, coef + (size_t)f * coef_stride) != DD_JPEG_ST_OK) status[f] = DD_JPEG_ST_DATA;
+}
+
+// ---- DD_JPEGDEC_SPLIT: only a decoder made with the flag launches this one.
+
+constexpr int JD_SPLIT_MAX_SUB = 2048;         // subsequences of a file: 28 bytes of LDS each, beside the file's four Huffman tables
+constexpr int JD_SPLIT_WORDS = 7;              // 32-bit words of LDS per subsequence
+
+// One workgroup per file whose record names a subsequence size (reserved = its log2; the host's routing, jpegdec_launch): a baseline file
+// without restart intervals, which jpeg_entropy_k would give to a single lane.  The lanes stride over the file's subsequences
+// (csrc/jpeg_dec_dev.h jpd_decode_span).  Round 0 decodes every subsequence from its guess; in round r every lane first reads its
+// predecessor's end state and, behind a barrier, decodes again where that is known and is not the start it used last -- so a round reads only
+// what the round before wrote, and the outcome does not depend on the order the lanes run in.  Subsequence 0 starts from the truth, so after
+// round r subsequences 0 .. r are final and the loop is over after at most n_sub + 1 rounds, which is also its hard limit.  Then one
+// exclusive scan gives every subsequence its first block and its DC predictors (kept to 16 bits: all that is ever stored of them), and a
+// last decode writes the coefficients.  Only a lane in front of which every end state is known can end the frame well; when none does, the
+// file is DD_JPEG_ST_DATA.  An error met from a guess is not an error: that lane's successor keeps its own start.
+// LDS: per subsequence the start used last, the end state, the blocks begun and the DC sums, JD_SPLIT_WORDS words, max_sub of each.
+// stats: subsequences, the most rounds a file took, decodes of a subsequence in the rounds (jpegdec_launch zeroes them).
+__global__ __launch_bounds__(JD_T) void jpeg_split_entropy_k(const dd_jpeg_info *__restrict__ recs, const uint8_t *__restrict__ bytes, const int *__restrict__ mark,
+                                                             int16_t *__restrict__ coef, long long coef_stride, int *__restrict__ status, int max_sub,
+                                                             unsigned int *__restrict__ stats) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t jd_lds[];
+    __shared__ dd_jpeg_huff huff[4];
+    __shared__ int sc[4];
+    __shared__ uint32_t s_end, s_first_bad, s_decodes;
+    __shared__ int s_ok;
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const dd_jpeg_info &r = recs[f];
+    const int log2b = r.reserved;
+    if (log2b < 4 || log2b > 30 || r.status != DD_JPEG_ST_OK || mark[f] != DD_JPEG_ST_OK) return;
+    const uint8_t *scan = bytes + r.file_offset + r.scan_offset;
+    const uint32_t len = (uint32_t)r.scan_length;
+    uint32_t *used_pos = reinterpret_cast<uint32_t *>(jd_lds), *used_kj = used_pos + max_sub, *end_pos = used_kj + max_sub, *end_kj = end_pos + max_sub;
+    uint32_t *blocks = end_kj + max_sub, *dc01 = blocks + max_sub, *dc2 = dc01 + max_sub;          // dc2: bit 31 marks a decode due in this round
+    {
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(r.huff);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(huff);
+        for (int i = tid; i < (int)(sizeof(huff) / 4); i += JD_T) dst[i] = src[i];
+    }
+    if (tid == 0) s_end = len, s_first_bad = 0xFFFFFFFFu, s_decodes = 0, s_ok = 0;
+    __syncthreads();
+    // where the data ends: the first 0xFF that no 0x00 follows
+    {
+        uint32_t e = len;
+        for (uint32_t p = (uint32_t)tid * 4; p < len && e == len; p += JD_T * 4) {
+            bool look = true;
+            if (p + 4 <= len) {
+                uint32_t w;
+                __builtin_memcpy(&w, scan + p, 4);
+                look = ((~w - 0x01010101u) & w & 0x80808080u) != 0;
+            }
+            if (look)
+                for (uint32_t q = p; q < p + 4 && q < len; ++q)
+                    if (jpd_marker_at(scan, q, len)) {
+                        e = q;
+                        break;
+                    }
+        }
+        if (e < len) atomicMin(&s_end, e);
+    }
+    __syncthreads();
+    const uint32_t end = s_end;
+    const int n_sub = (int)min((unsigned long long)max_sub, ((unsigned long long)end + (1ull << log2b) - 1) >> log2b);
+    const uint32_t n_blocks = (uint32_t)r.mcus_x * (uint32_t)r.mcus_y * (uint32_t)r.blocks_per_mcu;
+    int decodes = 0;
+    for (int i = tid; i < n_sub; i += JD_T) {                                   // round 0
+        JpdState st = jpd_span_guess(scan, (uint32_t)i, log2b, end);
+        JpdSpanSums sums;
+        used_pos[i] = st.pos, used_kj[i] = st.kj;
+        jpd_decode_span(r, huff, scan, end, (uint32_t)min((unsigned long long)end, ((unsigned long long)i + 1) << log2b), st, JPD_SPAN_COUNT, sums, nullptr, 0, 0, nullptr);
+        end_pos[i] = st.pos, end_kj[i] = st.kj;
+        blocks[i] = sums.blocks, dc01[i] = (uint32_t)sums.dc[0] | (uint32_t)sums.dc[1] << 16, dc2[i] = sums.dc[2];
+        ++decodes;
+    }
+    __syncthreads();
+    int rounds = 1;
+    for (int round = 1; round <= n_sub; ++round) {
+        int due = 0;
+        for (int i = tid; i < n_sub; i += JD_T) {
+            if (i == 0) continue;
+            JpdState p, u;
+            p.pos = end_pos[i - 1], p.kj = end_kj[i - 1];
+            u.pos = used_pos[i], u.kj = used_kj[i];
+            if (p.kj == JPD_STATE_UNKNOWN || jpd_state_eq(p, u)) continue;
+            used_pos[i] = p.pos, used_kj[i] = p.kj;
+            dc2[i] |= 0x80000000u;
+            due = 1;
+        }
+        ++rounds;
+        if (!__syncthreads_or(due)) break;
+        for (int i = tid; i < n_sub; i += JD_T) {
+            if (!(dc2[i] & 0x80000000u)) continue;
+            JpdState st;
+            JpdSpanSums sums;
+            st.pos = used_pos[i], st.kj = used_kj[i];
+            jpd_decode_span(r, huff, scan, end, (uint32_t)min((unsigned long long)end, ((unsigned long long)i + 1) << log2b), st, JPD_SPAN_COUNT, sums, nullptr, 0, 0, nullptr);
+            end_pos[i] = st.pos, end_kj[i] = st.kj;
+            blocks[i] = sums.blocks, dc01[i] = (uint32_t)sums.dc[0] | (uint32_t)sums.dc[1] << 16, dc2[i] = sums.dc[2];
+            ++decodes;
+        }
+        __syncthreads();
+    }
+    // the first subsequence whose end is not known, and every subsequence's first block and predictors
+    for (int i = tid; i < n_sub; i += JD_T)
+        if (end_kj[i] == JPD_STATE_UNKNOWN) atomicMin(&s_first_bad, (uint32_t)i);
+    int carry[4] = {0, 0, 0, 0};
+    for (int base = 0; base < n_sub; base += JD_T) {
+        const int i = base + tid;
+        const bool in = i < n_sub;
+        const int v[4] = {in ? (int)blocks[i] : 0, in ? (int)(dc01[i] & 0xFFFFu) : 0, in ? (int)(dc01[i] >> 16) : 0, in ? (int)(dc2[i] & 0xFFFFu) : 0};
+        int x[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            int all;
+            x[q] = carry[q] + jd_scan(v[q], sc, all);
+            carry[q] += all;
+        }
+        if (in) blocks[i] = (uint32_t)x[0], dc01[i] = ((uint32_t)x[1] & 0xFFFFu) | (uint32_t)x[2] << 16, dc2[i] = (uint32_t)x[3] & 0xFFFFu;
+    }
+    __syncthreads();
+    const uint32_t first_bad = s_first_bad;
+    int16_t *out = coef + (size_t)f * coef_stride;
+    for (int i = tid; i < n_sub; i += JD_T) {
+        JpdState st;
+        JpdSpanSums sums;
+        st.pos = used_pos[i], st.kj = used_kj[i];
+        const uint32_t pred[3] = {dc01[i] & 0xFFFFu, dc01[i] >> 16, dc2[i]};
+        const bool done = jpd_decode_span(r, huff, scan, end, (uint32_t)min((unsigned long long)end, ((unsigned long long)i + 1) << log2b), st, JPD_SPAN_WRITE, sums, out, blocks[i],
+                                          n_blocks, pred);
+        if (done && (uint32_t)i <= first_bad) s_ok = 1;
+    }
+    if (decodes) atomicAdd(&s_decodes, (uint32_t)decodes);
+    __syncthreads();
+    if (tid == 0) {
+        if (!s_ok) status[f] = DD_JPEG_ST_DATA;
+        atomicAdd(&stats[0], (unsigned int)n_sub);
+        atomicMax(&stats[1], (unsigned int)rounds);
+        atomicAdd(&stats[2], s_decodes);
+    }
 }
 
 // ---- progressive files (SOF2): only a decoder made with DD_JPEGDEC_PROGRESSIVE launches these two.
@@ -602,6 +749,13 @@ struct dd_jpegdec {
     PinBuf scans_host;
     int levels_run = 0;
     hipEvent_t lev[DD_JPEG_MAX_LEVELS + 1] = {};
+    // DD_JPEGDEC_SPLIT only: log2 of the subsequence size, jpeg_split_entropy_k's counters, their copy in pinned memory, the event behind that
+    // copy, and how many files the last decode routed to the kernel
+    bool split = false, split_auto = true, split_queued = false;
+    int split_log2 = 0, split_files = 0;
+    DevBuf split_stats;
+    PinBuf split_stats_host;
+    hipEvent_t split_done = nullptr;
 };
 
 namespace ddk {
@@ -637,12 +791,13 @@ int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, dd_jpeg_scans *scans_
     const JdGeom &g = d->g;
     DD_REQUIRE(!scans_host || d->progressive, DD_E_STATE, "jpeg decoder: scan scripts for a decoder that was not made to take progressive files");
     long long total = 0, ptotal = 0, level_total[DD_JPEG_MAX_LEVELS] = {};
-    int max_scans = 0, n_levels = 0;
+    int max_scans = 0, n_levels = 0, n_split = 0, max_sub = 0;
     size_t lds = 0;
     bool any = false, any_planes = false;
     for (int i = 0; i < n; ++i) {
         dd_jpeg_info &r = recs_host[i];
         r.interval_base = (int32_t)total;
+        r.reserved = 0;
         if (scans_host) {
             dd_jpeg_scans &S = scans_host[i];
             for (int l = 0; l < DD_JPEG_MAX_LEVELS; ++l) S.level_base[l] = (int32_t)level_total[l];
@@ -676,6 +831,20 @@ int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, dd_jpeg_scans *scans_
         r.path = b.lds <= (size_t)JD_LDS_MAX ? DD_JPEGDEC_LDS : DD_JPEGDEC_PLANES;
         if (r.path == DD_JPEGDEC_LDS) lds = b.lds > lds ? b.lds : lds;
         else any_planes = true;
+        // DD_JPEGDEC_SPLIT: a baseline file that is one restart interval (no DRI, DRI 0, or a DRI of the MCU count or more) and longer than a
+        // subsequence goes to jpeg_split_entropy_k, in subsequences of the decoder's size -- doubled, where DD_JPEGDEC_SPLIT_BYTES did not
+        // fix it, until every lane of the workgroup has at most one, and in any case until the file's states fit the kernel's LDS;
+        // jpeg_entropy_k passes over it
+        if (d->split && r.sof != 0xC2 && r.n_intervals == 1 && (long long)r.scan_length > (1ll << d->split_log2)) {
+            int lg = d->split_log2;
+            if (d->split_auto)                                              // one subsequence per lane of the file's workgroup: see the README's table
+                while ((((long long)r.scan_length + (1ll << lg) - 1) >> lg) > JD_T) ++lg;
+            while ((((long long)r.scan_length + (1ll << lg) - 1) >> lg) > JD_SPLIT_MAX_SUB) ++lg;
+            r.reserved = lg;
+            const int subs = (int)(((long long)r.scan_length + (1ll << lg) - 1) >> lg);
+            max_sub = subs > max_sub ? subs : max_sub;
+            ++n_split;
+        }
         total += r.n_intervals;
         any = true;
         DD_REQUIRE(total <= 0x7fffffffll, DD_E_CAPACITY, "jpeg decoder: more than 2^31 restart intervals in a call");
@@ -707,14 +876,36 @@ int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, dd_jpeg_scans *scans_
     }
     if (d->profile) DD_HIP(hipEventRecord(d->ev[2], s));
     d->levels_run = 0;
-    if (!any) return DD_OK;
+    unsigned int *split_stats = d->split ? d->split_stats.as<unsigned int>() : nullptr;
+    if (d->split) {
+        d->split_files = n_split;
+        DD_HIP(hipMemsetAsync(split_stats, 0, 4 * sizeof(unsigned int), s));
+    }
+    if (!any) {
+        if (d->split) {
+            DD_HIP(hipMemcpyAsync(d->split_stats_host.as<unsigned int>(), split_stats, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+            DD_HIP(hipEventRecord(d->split_done, s));
+            d->split_queued = true;
+        }
+        return DD_OK;
+    }
     DD_HIP(hipMemsetAsync(coef, 0, (size_t)n * (size_t)g.coef_stride * sizeof(int16_t), s));
+    if (n_split) {
+        const size_t split_lds = (size_t)max_sub * JD_SPLIT_WORDS * sizeof(uint32_t);
+        hipLaunchKernelGGL(jpeg_split_entropy_k, dim3((unsigned)n), dim3(JD_T), split_lds, s, recs, bytes, mark, coef, g.coef_stride, status_dev, max_sub, split_stats);
+        DD_LAUNCH_CHECK();
+    }
+    if (d->split) {
+        DD_HIP(hipMemcpyAsync(d->split_stats_host.as<unsigned int>(), split_stats, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+        DD_HIP(hipEventRecord(d->split_done, s));
+        d->split_queued = true;
+    }
     // intervals per wave: a lane decodes serially, so few intervals are spread over many waves (one per SIMD and more: 256 CUs of 4 SIMDs),
     // and only a call with very many intervals fills its waves
     int per = 64;
     while (per > 1 && total / per < 2048) per >>= 1;
     if (d->lanes) per = d->lanes;
-    if (total || !max_scans) {                                  // a call of progressive files alone has nothing for it
+    if ((total || !max_scans) && !(n_split && total == n_split)) {          // a call of progressive files alone, or of split files alone, has nothing for it
         hipLaunchKernelGGL(jpeg_entropy_k, dim3((unsigned)((total + per - 1) / per)), dim3(64), 0, s, recs, n, (int)total, per, bytes, iv_start, iv_end, mark, coef,
                            g.coef_stride, status_dev);
         DD_LAUNCH_CHECK();
@@ -821,7 +1012,15 @@ static int jd_create(const char *who, dd_ctx *ctx, int h, int w, int scale, int 
     JdGeom g;
     if (int rc = jd_geometry(h, w, who, &g)) return rc;
     DD_REQUIRE(jpd_scale_ok(scale), DD_E_ARG, "%s: scale %d is none of 1, 2, 4, 8", who, scale);
-    DD_REQUIRE((flags & ~DD_JPEGDEC_PROGRESSIVE) == 0, DD_E_ARG, "%s: flags 0x%x (DD_JPEGDEC_PROGRESSIVE or 0)", who, flags);
+    DD_REQUIRE((flags & ~(DD_JPEGDEC_PROGRESSIVE | DD_JPEGDEC_SPLIT)) == 0, DD_E_ARG, "%s: flags 0x%x (DD_JPEGDEC_PROGRESSIVE, DD_JPEGDEC_SPLIT, both or 0)", who, flags);
+    int split_log2 = 6;                                             // 64 bytes, doubled per file until a lane has one subsequence: see the README's table
+    const char *sb = (flags & DD_JPEGDEC_SPLIT) ? getenv("DD_JPEGDEC_SPLIT_BYTES") : nullptr;
+    if (sb) {                                                       // the subsequence size of jpeg_split_entropy_k: a power of two, 16 .. 4096
+        char *tail = nullptr;
+        const long v = strtol(sb, &tail, 10);
+        DD_REQUIRE(tail != sb && *tail == 0 && v >= 16 && v <= 4096 && (v & (v - 1)) == 0, DD_E_ARG, "%s: DD_JPEGDEC_SPLIT_BYTES=%s (a power of two, 16 .. 4096)", who, sb);
+        for (split_log2 = 4; (1l << split_log2) < v; ++split_log2) {}
+    }
     DD_REQUIRE(max_frames >= 1 && (long long)max_frames * g.max_bands <= 0x7fffffffll, DD_E_ARG, "%s: max_frames %d", who, max_frames);
     DD_REQUIRE(max_bytes >= 1, DD_E_ARG, "%s: max_bytes %lld", who, (long long)max_bytes);
     DD_DEVICE(ctx);
@@ -839,6 +1038,13 @@ static int jd_create(const char *who, dd_ctx *ctx, int h, int w, int scale, int 
     d->progressive = (flags & DD_JPEGDEC_PROGRESSIVE) != 0;
     if (rc == DD_OK && d->progressive) rc = d->scans.reserve((size_t)max_frames * sizeof(dd_jpeg_scans));
     if (rc == DD_OK && d->progressive) rc = d->scans_host.reserve((size_t)max_frames * sizeof(dd_jpeg_scans));
+    d->split = (flags & DD_JPEGDEC_SPLIT) != 0, d->split_log2 = split_log2, d->split_auto = sb == nullptr;
+    if (rc == DD_OK && d->split) rc = d->split_stats.reserve(4 * sizeof(unsigned int));
+    if (rc == DD_OK && d->split) rc = d->split_stats_host.reserve(4 * sizeof(unsigned int));
+    if (rc == DD_OK && d->split && hipEventCreateWithFlags(&d->split_done, hipEventDisableTiming) != hipSuccess) {
+        dd_set_error("%s: hipEventCreateWithFlags failed", who);
+        rc = DD_E_HIP;
+    }
     if (rc == DD_OK && hipEventCreateWithFlags(&d->uploaded, hipEventDisableTiming) != hipSuccess) {
         dd_set_error("%s: hipEventCreateWithFlags failed", who);
         rc = DD_E_HIP;
@@ -876,6 +1082,8 @@ int dd_jpegdec_destroy(dd_jpegdec *d) {
     d->recs_host.release();
     d->scans.release(), d->pstarts.release(), d->scans_host.release();
     if (d->uploaded) (void)hipEventDestroy(d->uploaded);
+    d->split_stats.release(), d->split_stats_host.release();
+    if (d->split_done) (void)hipEventDestroy(d->split_done);
     for (hipEvent_t e : d->ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : d->lev)
@@ -915,6 +1123,17 @@ int dd_jpegdec_profile_levels(dd_jpegdec *d, float *ms_host, int *n_levels_host)
     for (int i = 0; i < DD_JPEG_MAX_LEVELS; ++i) ms_host[i] = 0.f;
     for (int i = 0; i < d->levels_run; ++i) DD_HIP(hipEventElapsedTime(&ms_host[i], d->lev[i], d->lev[i + 1]));
     *n_levels_host = d->levels_run;
+    return DD_OK;
+}
+
+int dd_jpegdec_split_stats(dd_jpegdec *d, int64_t *out_host) {
+    DD_REQUIRE(d && out_host, DD_E_ARG, "dd_jpegdec_split_stats: NULL argument");
+    for (int i = 0; i < 4; ++i) out_host[i] = 0;
+    if (!d->split || !d->split_queued) return DD_OK;
+    DD_DEVICE(d->ctx);
+    DD_HIP(hipEventSynchronize(d->split_done));
+    const unsigned int *st = d->split_stats_host.as<unsigned int>();
+    out_host[0] = d->split_files, out_host[1] = st[0], out_host[2] = st[1], out_host[3] = st[2];
     return DD_OK;
 }
 

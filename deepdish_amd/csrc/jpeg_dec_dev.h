@@ -141,6 +141,195 @@ JPD_HD int jpd_decode_interval(const dd_jpeg_info &r, const uint8_t *scan, uint3
     return DD_JPEG_ST_OK;
 }
 
+// ---- one entropy-coded segment decoded by several lanes (DD_JPEGDEC_SPLIT; jpeg_split_entropy_k and scripts/jpeg_split_check.cpp run these
+// statements).  The segment's bytes are cut into subsequences of 1 << log2b bytes; subsequence i owns the symbols (a Huffman code with its
+// extra bits) whose first bit lies in bytes [i << log2b, (i + 1) << log2b).  A lane decodes its subsequence from a start state -- a guess
+// at first, its predecessor's end state later -- and the rounds repeat until no end state changes: Huffman data falls into step by itself.
+// The bounds, beside the bit reader's:
+//   - a span's loop takes one symbol per pass and ends at the first symbol boundary at or behind its limit, which is at most the data's end;
+//   - a block index at or above the frame's block count is never stored;
+//   - a speculative decode (JPD_SPAN_COUNT) stores no coefficient at all.
+
+// Where a decode stands: the first unread bit is bit `bit` (0: the most significant) of the data byte at `pos` of the stuffed stream (the
+// 0xFF of a stuffed pair, never its 0x00), in block k of the MCU, before coefficient j (0: the block's DC symbol comes next).
+struct JpdState {
+    uint32_t pos;
+    uint32_t kj;             // bit | k << 3 | j << 8, or JPD_STATE_UNKNOWN: the decode that should have led here met an error
+};
+constexpr uint32_t JPD_STATE_UNKNOWN = 0xFFFFFFFFu;
+constexpr int JPD_SPAN_COUNT = 0, JPD_SPAN_WRITE = 1;
+
+JPD_HD bool jpd_state_eq(const JpdState &a, const JpdState &b) { return a.pos == b.pos && a.kj == b.kj; }
+
+// Where the entropy-coded data of scan[0 .. len) ends for jpd_bits_fill: at the first 0xFF that no 0x00 follows, else at len.  In front of
+// that every 0xFF starts a stuffed pair.  (A lane of jpeg_split_entropy_k asks this of its own bytes; the least answer is the segment's.)
+JPD_HD bool jpd_marker_at(const uint8_t *scan, uint32_t p, uint32_t len) { return scan[p] == 0xFF && !(p + 1 < len && scan[p + 1] == 0); }
+
+// The first data byte at or behind p (p >= 1 or p == 0): p itself unless it is the 0x00 of a stuffed pair.
+JPD_HD uint32_t jpd_data_byte(const uint8_t *scan, uint32_t p, uint32_t end) { return p > 0 && p < end && scan[p] == 0 && scan[p - 1] == 0xFF ? p + 1 : p; }
+
+// The guess subsequence i starts from: its first byte, bit 0, the DC symbol of an MCU's first block.
+JPD_HD JpdState jpd_span_guess(const uint8_t *scan, uint32_t i, int log2b, uint32_t end) {
+    JpdState s;
+    s.pos = jpd_data_byte(scan, i << log2b, end), s.kj = 0;
+    return s;
+}
+
+// JpdBits with a limit: `over` counts how many of the unread bits came from bytes at or behind `lim` (they are the lowest; phantom bits are
+// among them), so the next unread bit lies in front of lim exactly when b.n > over.  lim <= b.end.
+struct JpdSpanBits {
+    JpdBits b;
+    uint32_t lim;
+    int over;
+};
+
+// jpd_bits_fill, keeping `over`: at least 33 unread bits afterwards, so that jpd_symbol and jpd_extend behind it never fill themselves.
+JPD_HD void jpd_span_fill(JpdSpanBits &s) {
+    JpdBits &b = s.b;
+    while (b.n <= 32) {
+        if (b.pos + 4 <= b.end && b.pos + 4 > b.pos) {
+            uint32_t w;
+            __builtin_memcpy(&w, b.p + b.pos, 4);
+            w = __builtin_bswap32(w);
+            if (((~w - 0x01010101u) & w & 0x80808080u) == 0) {          // no byte of w is 0xFF
+                const uint32_t front = b.pos >= s.lim ? 0u : s.lim - b.pos >= 4u ? 4u : s.lim - b.pos;
+                b.acc = (b.acc << 32) | w;
+                b.n += 32;
+                s.over += 8 * (4 - (int)front);
+                b.pos += 4;
+                continue;
+            }
+        }
+        uint32_t v = 0;
+        const bool behind = b.pos >= s.lim;
+        if (b.pos < b.end) {
+            v = b.p[b.pos];
+            if (v == 0xFF) {
+                if (b.pos + 1 < b.end && b.p[b.pos + 1] == 0) b.pos += 2;
+                else {
+                    b.pos = b.end;
+                    v = 0;
+                    b.phantom += 8;
+                }
+            } else
+                ++b.pos;
+        } else
+            b.phantom += 8;
+        b.acc = (b.acc << 8) | v;
+        b.n += 8;
+        if (behind) s.over += 8;
+    }
+}
+
+// What one decode of a subsequence found (JPD_SPAN_COUNT): how many blocks begin in it, and the wrap-around sum of the DC differences it
+// holds per component -- associative, and what jpd_decode_interval's (int16_t)(uint16_t)pred keeps of its 32-bit predictor.
+struct JpdSpanSums {
+    uint32_t blocks;
+    uint16_t dc[3];
+};
+
+// Decodes from state `st` to the first symbol boundary at or behind byte `lim` (lim <= end, the data's end as jpd_marker_at gives it) and
+// leaves that state in st; JPD_STATE_UNKNOWN after a code the table does not hold, a DC category above 11 or a coefficient behind 63.
+//   JPD_SPAN_COUNT  fills `sums`, also in front of an error; stores nothing.
+//   JPD_SPAN_WRITE  the caller knows the truth: `blk` is the index of the first block that begins here (a block under way at st is
+//                   blk - 1), pred the DC predictors in front of it, n_blocks the frame's block count.  Stores into coef, which the caller
+//                   has zeroed, what jpd_decode_interval stores.  Returns true when block n_blocks - 1 ends here and what is left behind it
+//                   is the padding of the last byte -- jpd_decode_interval's DD_JPEG_ST_OK -- and stops there; nothing is stored at or
+//                   behind block n_blocks.
+// The statements are jpd_decode_interval's, one symbol per pass: ZRL adds 16, a run is checked against 63 only where a coefficient follows,
+// a block without EOB ends at j = 64.
+JPD_HD bool jpd_decode_span(const dd_jpeg_info &r, const dd_jpeg_huff *huff, const uint8_t *scan, uint32_t end, uint32_t lim, JpdState &st, const int mode, JpdSpanSums &sums,
+                            int16_t *coef, uint32_t blk, uint32_t n_blocks, const uint32_t *pred) {
+    sums.blocks = 0, sums.dc[0] = sums.dc[1] = sums.dc[2] = 0;
+    if (st.kj == JPD_STATE_UNKNOWN || st.pos >= lim) return false;          // nothing of this subsequence is left: the state passes through
+    const int bpm = r.blocks_per_mcu, ny = bpm == 1 ? 1 : bpm - 2;
+    int k = (int)((st.kj >> 3) & 31), j = (int)(st.kj >> 8);
+    if (k >= bpm || j > 63) return false;
+    const uint32_t tsel = (uint32_t)(r.td[0] & 1) | (uint32_t)(r.ta[0] & 1) << 1 | (uint32_t)(r.td[1] & 1) << 2 | (uint32_t)(r.ta[1] & 1) << 3 | (uint32_t)(r.td[2] & 1) << 4 |
+                          (uint32_t)(r.ta[2] & 1) << 5;                      // the record is read here, not once a symbol
+    JpdSpanBits s;
+    jpd_bits_open(s.b, scan, st.pos, end);
+    s.lim = lim, s.over = 0;
+    jpd_span_fill(s);
+    s.b.n -= (int)(st.kj & 7);
+    JpdBits &b = s.b;
+    // per component: the DC predictor (JPD_SPAN_WRITE) or the sum of the differences met (JPD_SPAN_COUNT), in scalars, not in an indexed array
+    uint32_t a0 = 0, a1 = 0, a2 = 0, begun = 0;
+    if (mode == JPD_SPAN_WRITE) a0 = pred[0], a1 = pred[1], a2 = pred[2];
+    int16_t *cur = nullptr;                                                 // the block under way, where it may be stored
+    if (mode == JPD_SPAN_WRITE && j > 0 && blk >= 1 && blk - 1 < n_blocks) cur = coef + (size_t)(blk - 1) * 64;
+    bool known = true, done = false;
+    for (;;) {
+        jpd_span_fill(s);
+        if (b.n <= s.over) break;                                           // the next symbol belongs to the subsequence behind
+        const int c = k < ny ? 0 : k - ny + 1;
+        if (j == 0) {
+            if (mode == JPD_SPAN_WRITE && blk >= n_blocks) {                // surplus bits: jpd_decode_interval has stopped in front of them
+                known = false;
+                break;
+            }
+            const int sy = jpd_symbol(b, huff[(tsel >> (2 * c)) & 1]);
+            if (sy < 0 || sy > 11) {
+                known = false;
+                break;
+            }
+            const uint32_t diff = sy ? (uint32_t)jpd_extend(b, sy) : 0u;
+            const uint32_t a = (c == 0 ? a0 : c == 1 ? a1 : a2) + diff;
+            if (c == 0) a0 = a;
+            else if (c == 1) a1 = a;
+            else a2 = a;
+            if (mode == JPD_SPAN_WRITE) {
+                cur = coef + (size_t)blk * 64;
+                cur[0] = (int16_t)(uint16_t)a;
+                ++blk;
+            } else
+                ++begun;
+            j = 1;
+        } else {
+            const int rs = jpd_symbol(b, huff[2 + ((tsel >> (2 * c + 1)) & 1)]);
+            if (rs < 0) {
+                known = false;
+                break;
+            }
+            const int run = rs >> 4, sz = rs & 15;
+            if (sz == 0) {
+                j = run != 15 ? 64 : j + 16;
+            } else {
+                j += run;
+                const int v = jpd_extend(b, sz);
+                if (j > 63) {
+                    known = false;
+                    break;
+                }
+                if (mode == JPD_SPAN_WRITE && cur) cur[JPD_ZIGZAG[j]] = (int16_t)v;
+                ++j;
+            }
+        }
+        if (j >= 64) {                                                      // the block ends
+            if (mode == JPD_SPAN_WRITE && blk == n_blocks) {                // it was the frame's last: jpd_decode_interval's closing tests
+                known = false;
+                // bits from beyond the end; more than the last byte's padding; data bytes not yet taken (in front of `end` there is no marker)
+                done = !(b.n < b.phantom) && !(b.n - b.phantom >= 8) && !(b.pos < b.end);
+                break;
+            }
+            j = 0;
+            if (++k == bpm) k = 0;
+        }
+    }
+    if (mode == JPD_SPAN_COUNT) sums.blocks = begun, sums.dc[0] = (uint16_t)a0, sums.dc[1] = (uint16_t)a1, sums.dc[2] = (uint16_t)a2;
+    if (!known) {
+        st.kj = JPD_STATE_UNKNOWN;
+        return done;
+    }
+    // the cursor: over - n bits behind the first data byte at or behind lim
+    uint32_t q = jpd_data_byte(scan, lim, end);
+    int behind = s.over - b.n;
+    for (; behind >= 8 && q < end; behind -= 8) q += scan[q] == 0xFF ? 2 : 1;
+    if (q >= end) q = end, behind = 0;                                      // past the data: no subsequence starts there
+    st.pos = q, st.kj = (uint32_t)behind | ((uint32_t)k << 3) | ((uint32_t)j << 8);
+    return false;
+}
+
 // The RSTn marker (0 .. 7) at scan[p], p + 1 < len, or -1.
 JPD_HD int jpd_rst_at(const uint8_t *scan, uint32_t p) { return scan[p] == 0xFF && scan[p + 1] >= 0xD0 && scan[p + 1] <= 0xD7 ? scan[p + 1] - 0xD0 : -1; }
 

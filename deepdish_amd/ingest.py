@@ -31,7 +31,8 @@ PACKED_422 = ('yuy2', 'uyvy')
 
 
 class FrameIngest:
-    def __init__(self, n_streams, src_size, dst_size=None, slots=2, flip=False, context=None, pixel_format='bgr', jpeg_slot_bytes=None, jpeg_scale=1, jpeg_progressive=False):
+    def __init__(self, n_streams, src_size, dst_size=None, slots=2, flip=False, context=None, pixel_format='bgr', jpeg_slot_bytes=None, jpeg_scale=1, jpeg_progressive=False,
+                 jpeg_split=False):
         """src_size / dst_size: (width, height) like the reference's `input_size`; dst defaults to src.
         pixel_format: what a slot holds, 'bgr' | 'nv12' | 'i420' (4:2:0 needs an even width and height) | 'yuy2' | 'uyvy' (packed 4:2:2,
         named by FOURCC: an even width, any height) | 'jpeg'; the consumer always gets BGR.  jpeg_slot_bytes: the size of a JPEG slot's arena, by default n_streams * width * height * 3 // 8.
@@ -39,7 +40,9 @@ class FrameIngest:
         dst_size), Pillow's draft rule.  src_size stays what every file must state; the ring decodes ceil(height / scale) x ceil(width / scale)
         frames and resizes from there -- or decodes straight into the slot when that is dst_size and no flip is asked.
         jpeg_progressive ('jpeg' only): take progressive (SOF2) files as well as baseline ones, at any jpeg_scale
-        (deepdish_amd.jpeg.JpegDecoder(progressive=True)); without it such a file is ST_HEADER, as ever."""
+        (deepdish_amd.jpeg.JpegDecoder(progressive=True)); without it such a file is ST_HEADER, as ever.
+        jpeg_split ('jpeg' only): files without restart markers are decoded by a workgroup each, not by one lane
+        (deepdish_amd.jpeg.JpegDecoder(split=True)); the frames are the same."""
         self._h = None
         if pixel_format not in PIXEL_FORMATS:
             raise ValueError("pixel_format %r is none of 'bgr', 'nv12', 'i420', 'yuy2', 'uyvy', 'jpeg'%s"
@@ -62,6 +65,9 @@ class FrameIngest:
         if pixel_format != 'jpeg' and jpeg_progressive:
             raise ValueError("jpeg_progressive: only a 'jpeg' ring decodes, a %r ring has no files to take" % (pixel_format,))
         self.jpeg_progressive = bool(jpeg_progressive)
+        if pixel_format != 'jpeg' and jpeg_split:
+            raise ValueError("jpeg_split: only a 'jpeg' ring decodes, a %r ring has no files to split" % (pixel_format,))
+        self.jpeg_split = bool(jpeg_split)
         self.ctx = context or default_context()
         self.S, self.slots = int(n_streams), int(slots)
         h = P()
@@ -70,9 +76,10 @@ class FrameIngest:
                                          ctypes.byref(h)), 'dd_ingest_create')
         elif pixel_format == 'jpeg':
             self.jpeg_slot_bytes = int(jpeg_slot_bytes) if jpeg_slot_bytes else self.S * self.sw * self.sh * 3 // 8
-            if self.jpeg_progressive:
+            if self.jpeg_progressive or self.jpeg_split:
+                flags = (1 if self.jpeg_progressive else 0) | (2 if self.jpeg_split else 0)
                 check(lib().dd_ingest_create_jpeg_ex(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
-                                                     self.jpeg_scale, 1, self.jpeg_slot_bytes, ctypes.byref(h)), 'dd_ingest_create_jpeg_ex')
+                                                     self.jpeg_scale, flags, self.jpeg_slot_bytes, ctypes.byref(h)), 'dd_ingest_create_jpeg_ex')
             elif self.jpeg_scale == 1:
                 check(lib().dd_ingest_create_jpeg(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
                                                   self.jpeg_slot_bytes, ctypes.byref(h)), 'dd_ingest_create_jpeg')

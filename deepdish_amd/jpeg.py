@@ -21,7 +21,12 @@ or 8 the decoder transforms every 8 x 8 block straight to 4 x 4, 2 x 2 or 1 x 1 
 Progressive (SOF2) files -- what cv2.imread reads without being asked, and what a CVAT directory re-saved by a tool usually holds -- are an
 option: `parse(file, progressive=True)`, `JpegDecoder(H, W, progressive=True)` and `FrameIngest(..., jpeg_progressive=True)`
 (tests/jpeg_prog_ref.py is the definition; jpeg_prog_entropy_k runs once per level of the scan script).  Without the option such a file is
-refused as before (reason 'progressive', ST_HEADER)."""
+refused as before (reason 'progressive', ST_HEADER).
+
+Files without restart markers -- what an MJPEG camera, cv2.imencode and Pillow write by default -- are one entropy-coded segment, which the
+decoder gives to a single lane.  `JpegDecoder(H, W, split=True)` and `FrameIngest(..., jpeg_split=True)` cut such a scan into subsequences
+of DD_JPEGDEC_SPLIT_BYTES (by default 64, doubled per file until a workgroup's lanes have one each) that many lanes decode from guessed states until they agree (jpeg_split_entropy_k); the frames
+are the same bytes.  `split_stats()` says what the last decode took."""
 import ctypes
 
 import numpy as np
@@ -131,7 +136,7 @@ REASONS = {0: 'ok', 1: 'truncated', 2: 'progressive', 3: 'arithmetic', 4: 'lossl
            8: 'scans', 9: 'huffman', 10: 'undefined', 11: 'size', 12: 'segment',
            13: 'ac_components', 14: 'ac_before_dc', 15: 'first_ah', 16: 'refinement', 17: 'incomplete', 18: 'capacity'}
 MAX_SCANS, MAX_TABLES, MAX_LEVELS = 64, 32, 16
-DEC_PROGRESSIVE = 1
+DEC_PROGRESSIVE, DEC_SPLIT = 1, 2
 
 
 class _Huff(ctypes.Structure):
@@ -244,9 +249,13 @@ class JpegDecoder:
     progressive=True makes the decoder take progressive (SOF2) files too, at any scale, beside baseline files in the same call: byte for
     byte libjpeg's pixels for a complete file (tests/jpeg_prog_ref.py).  parse(file, progressive=True) says what is refused: among it a
     script that leaves coefficients undelivered, which libjpeg would smooth or zero-fill.  A decoder without the option gives such files
-    ST_HEADER and launches exactly what it always did."""
+    ST_HEADER and launches exactly what it always did.
 
-    def __init__(self, H, W, max_frames=16, max_bytes=None, context=None, scale=1, progressive=False):
+    split=True, with any scale and with or without progressive: a baseline file that is a single restart interval and whose scan is longer
+    than DD_JPEGDEC_SPLIT_BYTES (read here; a power of two, 16 .. 4096; 64 when not set) is decoded by a workgroup, not by one lane; every
+    other file of the call goes the usual way.  Frames and statuses are the same; split_stats() counts what the last decode did."""
+
+    def __init__(self, H, W, max_frames=16, max_bytes=None, context=None, scale=1, progressive=False, split=False):
         from .runtime import default_context
         self.ctx = context or default_context()
         self.H, self.W, self.max_frames = int(H), int(W), int(max_frames)
@@ -254,11 +263,13 @@ class JpegDecoder:
         self._h = None
         self.scale = scale
         self.progressive = bool(progressive)
+        self.split = bool(split)
         h = P()
         if scale != 1 and (not isinstance(scale, int) or isinstance(scale, bool)):
             raise ValueError('scale %r is none of 1, 2, 4, 8' % (scale,))
-        if self.progressive:
-            check(lib().dd_jpegdec_create_ex(self.ctx.handle, self.H, self.W, scale, DEC_PROGRESSIVE, self.max_frames, self.max_bytes, ctypes.byref(h)),
+        if self.progressive or self.split:
+            flags = (DEC_PROGRESSIVE if self.progressive else 0) | (DEC_SPLIT if self.split else 0)
+            check(lib().dd_jpegdec_create_ex(self.ctx.handle, self.H, self.W, scale, flags, self.max_frames, self.max_bytes, ctypes.byref(h)),
                   'dd_jpegdec_create_ex')
         elif scale == 1:
             check(lib().dd_jpegdec_create(self.ctx.handle, self.H, self.W, self.max_frames, self.max_bytes, ctypes.byref(h)), 'dd_jpegdec_create')
@@ -294,6 +305,14 @@ class JpegDecoder:
         ms, n = (ctypes.c_float * MAX_LEVELS)(), ctypes.c_int()
         check(lib().dd_jpegdec_profile_levels(self._h, ms, ctypes.byref(n)), 'dd_jpegdec_profile_levels')
         return [float(v) for v in ms[:n.value]]
+
+    def split_stats(self):
+        """-> {'files', 'subsequences', 'max_rounds', 'lane_decodes'} of the last decode (waits for it): files that went to
+        jpeg_split_entropy_k, the subsequences they were cut into, the most rounds one of them took (at most its subsequences + 1) and how
+        often a subsequence was decoded in the rounds (the storing decode not counted).  All zeros on a decoder made without split=True."""
+        out = (ctypes.c_int64 * 4)()
+        check(lib().dd_jpegdec_split_stats(self._h, out), 'dd_jpegdec_split_stats')
+        return dict(zip(('files', 'subsequences', 'max_rounds', 'lane_decodes'), (int(v) for v in out)))
 
     def decode(self, files, out=None, status=None, stream=None):
         """files: a list of bytes objects -> (u8 [n, out_H, out_W, 3], int32 [n]).  out / status: tensors to write instead of new ones.  Queued on the context's stream (or

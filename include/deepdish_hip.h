@@ -929,6 +929,22 @@ int dd_jpegdec_profile_levels(dd_jpegdec *dec, float *ms_host, int *n_levels_hos
 /* dd_ingest_create_jpeg_scaled with the same flags: a ring whose slots take progressive files as well (deepdish.py:685-689). */
 int dd_ingest_create_jpeg_ex(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip, int scale, int flags,
                              int64_t slot_bytes, dd_ingest **out);
+/* A flag for dd_jpegdec_create_ex and dd_ingest_create_jpeg_ex, alone or beside DD_JPEGDEC_PROGRESSIVE, at any scale: several lanes decode
+ * one entropy-coded segment.  A baseline file that is a single restart interval (no DRI, DRI 0, or a DRI of the MCU count or more: what an
+ * MJPEG camera, cv2.imencode and Pillow write by default) and whose scan is longer than one subsequence goes to jpeg_split_entropy_k, one
+ * workgroup per file, in place of one lane of jpeg_entropy_k: the scan is cut into subsequences of DD_JPEGDEC_SPLIT_BYTES (read when the
+ * handle is made: a power of two, 16 .. 4096, anything else DD_E_ARG naming the value; kept as given, only doubled for a file with more
+ * than 2048 of them.  Not set: 64, doubled per file until it has at most 256 subsequences, one per lane of its workgroup), every lane
+ * decodes its subsequences from a guessed state and then from its predecessor's end state until no end state changes, and a last decode
+ * stores the coefficients.  The result is the sequential decode, exact on every input, and the status contract
+ * is unchanged.  Files with real restart intervals, scans no longer than a subsequence and progressive files take jpeg_entropy_k and
+ * jpeg_prog_entropy_k in the same call as ever; without the flag nothing changes.  dd_jpeg_info.reserved holds the log2 of a routed
+ * file's subsequence size on the device (0: not routed). */
+#define DD_JPEGDEC_SPLIT 2
+/* Waits for the decoder's last decode; out_host[4] = files routed to jpeg_split_entropy_k in it, their subsequences, the most rounds a
+ * file took (at most its subsequences + 1), and decodes of a subsequence in the rounds (the storing decode not counted).  All zeros for a
+ * decoder made without DD_JPEGDEC_SPLIT. */
+int dd_jpegdec_split_stats(dd_jpegdec *dec, int64_t *out_host);
 
 /* ---------------------------------------------------------------- multi-GPU
  * Sum of the per-stream count vectors (pos, neg, int, del per label; deepdish.py:1141-1145).
