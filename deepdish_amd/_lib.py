@@ -138,6 +138,16 @@ SIGNATURES = {
     'dd_pipeline_present_stats': [P, P],
     'dd_pipeline_detector_skip_streams': [P, P, P],
     'dd_pipeline_skip_stats': [P, P, P],
+    'dd_pipeline_stream_lines': [P, P],
+    'dd_pipeline_lines': [P, P, c_int, P],
+    'dd_pipeline_stream_wanted': [P, P],
+    'dd_pipeline_stream_tracker_params': [P, P, P, P, P],
+    'dd_pipeline_stream_nms_overlap': [P, P],
+    'dd_pipeline_stream_motion_ratio': [P, P],
+    'dd_pipeline_reset_streams': [P, P, c_int],
+    'dd_pipeline_stream_param_stats': [P, P],
+    'dd_pipeline_mog2': [P, POINTER(P)],
+    'dd_mog2_reset_streams': [P, P, c_int, P],
     'dd_feature_rows_carry': [P, P, c_int64, P, c_int64, P, c_int64, P, c_int64, P, c_int, P],
     'dd_gather_frames': [P, P, c_int, c_int64, P, c_int, P, P],
     'dd_pipeline_background_subtraction': [P, c_double, c_int],

@@ -77,6 +77,15 @@ class BackgroundSubtractorMOG2:
                                           ptr(masked_out) if masked_out is not None else None, None), 'dd_mog2_apply_streams')
         return self.mask
 
+    def reset(self, streams):
+        """The listed streams' subtractors start over (dd_mog2_reset_streams): no modes, frame count 0 -- a new
+        cv2.createBackgroundSubtractorMOG2() for those streams; the others are untouched."""
+        a = np.ascontiguousarray(list(streams), dtype=np.int32)
+        if a.ndim != 1 or ((a < 0) | (a >= self.S)).any():
+            raise ValueError('streams: indices 0 .. %d, got %r' % (self.S - 1, streams))
+        if self._h and a.size:
+            check(lib().dd_mog2_reset_streams(self._h, ptr(a), int(a.size), None), 'dd_mog2_reset_streams')
+
     def apply(self, image, fgmask=None, learningRate=-1):
         """cv2 signature: image u8 [H, W, 3] (or [S, H, W, 3] for a multi-stream subtractor) -> fgmask u8 ndarray."""
         a = np.ascontiguousarray(image, dtype=np.uint8)

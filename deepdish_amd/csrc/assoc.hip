@@ -400,9 +400,9 @@ __device__ int min_cost_matching_wave(LsapLds &L, MatchLds &M, const double *ful
 // One wave per stream with T > 0 and n > 0.  desc[5 b ..]: row base (into state / tsu), T, n, cost base (appearance [T][n], then IoU
 // [T][n]), output base.  out + output base: status, #matches, #unmatched rows, #unmatched detections, then the matches ((row, det) pairs,
 // room for min(T, n)), the unmatched rows (room for T) and the unmatched detections (room for n).
-__global__ __launch_bounds__(64) void assoc_match_k(const double *__restrict__ cost, const int *__restrict__ row_state,
-                                                    const int *__restrict__ row_tsu, const int *__restrict__ desc, double max_cos,
-                                                    double max_iou, int max_age, int *__restrict__ out) {
+__device__ __forceinline__ void assoc_match_body(const double *__restrict__ cost, const int *__restrict__ row_state,
+                                                 const int *__restrict__ row_tsu, const int *__restrict__ desc, double max_cos,
+                                                 double max_iou, int max_age, int *__restrict__ out) {
     __shared__ LsapLds L;
     __shared__ MatchLds M;
     __shared__ SetLds S;
@@ -487,6 +487,22 @@ __global__ __launch_bounds__(64) void assoc_match_k(const double *__restrict__ c
     }
 }
 
+__global__ __launch_bounds__(64) void assoc_match_k(const double *__restrict__ cost, const int *__restrict__ row_state,
+                                                    const int *__restrict__ row_tsu, const int *__restrict__ desc, double max_cos,
+                                                    double max_iou, int max_age, int *__restrict__ out) {
+    assoc_match_body(cost, row_state, row_tsu, desc, max_cos, max_iou, max_age, out);
+}
+
+// The same with --max-cosine-distance, --max-iou-distance and --max-age of each decided stream's own tracker: par_d[2 b], par_d[2 b + 1]
+// and par_age[b] lie beside desc in the block the update uploads.
+__global__ __launch_bounds__(64) void assoc_match_streams_k(const double *__restrict__ cost, const int *__restrict__ row_state,
+                                                            const int *__restrict__ row_tsu, const int *__restrict__ desc,
+                                                            const double *__restrict__ par_d, const int *__restrict__ par_age,
+                                                            int *__restrict__ out) {
+    const int b = blockIdx.x;
+    assoc_match_body(cost, row_state, row_tsu, desc, par_d[2 * b], par_d[2 * b + 1], par_age[b], out);
+}
+
 }  // namespace
 
 namespace ddk {
@@ -498,6 +514,14 @@ int assoc_match(hipStream_t s, const double *cost, const int *row_state, const i
                 double max_cos, double max_iou, int max_age, int *out) {
     if (n_streams <= 0) return DD_OK;
     hipLaunchKernelGGL(assoc_match_k, dim3(n_streams), dim3(64), 0, s, cost, row_state, row_tsu, desc, max_cos, max_iou, max_age, out);
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
+int assoc_match_streams(hipStream_t s, const double *cost, const int *row_state, const int *row_tsu, const int *desc, int n_streams,
+                        const double *par_d, const int *par_age, int *out) {
+    if (n_streams <= 0) return DD_OK;
+    hipLaunchKernelGGL(assoc_match_streams_k, dim3(n_streams), dim3(64), 0, s, cost, row_state, row_tsu, desc, par_d, par_age, out);
     DD_LAUNCH_CHECK();
     return DD_OK;
 }

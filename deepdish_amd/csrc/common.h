@@ -150,6 +150,8 @@ int nms_ex(hipStream_t s, const void *boxes, const void *keys, int k, double thr
            int *out_n, void *scratch, size_t scratch_bytes);
 int nms_batched_small(hipStream_t s, const double *boxes, const double *keys, const int *d_offsets, int n_problems,
                       double thr, int mode, int *out_idx, int *out_n);
+int nms_batched_small_streams(hipStream_t s, const double *boxes, const double *keys, const int *d_offsets, int n_problems,
+                              const double *d_thrs, int mode, int *out_idx, int *out_n);   // one threshold per problem
 // tracker fused kernels
 int crop_box_host(const int64_t *b, int ph, int pw, int H, int W, int *sx, int *sy, int *cw, int *ch);
 int crop_box_host_f64(const double *b, int ph, int pw, int H, int W, int *sx, int *sy, int *cw, int *ch);
@@ -186,4 +188,7 @@ void match_decide_host(const double *app, const double *iou, int T, int n, const
 size_t assoc_out_ints(int T, int n);   // ints one stream's decision takes in assoc_match's output
 int assoc_match(hipStream_t s, const double *cost, const int *row_state, const int *row_tsu, const int *desc, int n_streams,
                 double max_cos, double max_iou, int max_age, int *out);
+// the same with the three values per decided stream: par_d f64 [n_streams][2] = max_cos, max_iou; par_age int [n_streams] (device)
+int assoc_match_streams(hipStream_t s, const double *cost, const int *row_state, const int *row_tsu, const int *desc, int n_streams,
+                        const double *par_d, const int *par_age, int *out);
 }  // namespace ddk

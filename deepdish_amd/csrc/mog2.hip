@@ -273,6 +273,19 @@ int mog2_apply(dd_mog2 *m, hipStream_t s, const uint8_t *frames, double learning
     return mog2_apply_streams(m, s, frames, nullptr, learning_rate, mask, masked);
 }
 
+// The listed streams' models as dd_mog2_create leaves them: creation clears the mode-count plane with a memset and nothing else (planes
+// past a pixel's mode count are never read), so this is one hipMemsetAsync per listed stream on s, and the frame count back to 0.
+int mog2_reset_streams(dd_mog2 *m, hipStream_t s, const int *streams_host, int n) {
+    for (int i = 0; i < n; ++i)
+        DD_REQUIRE(streams_host[i] >= 0 && streams_host[i] < m->S, DD_E_ARG, "dd_mog2_reset_streams: stream %d of %d", streams_host[i], m->S);
+    const size_t hw = (size_t)m->H * m->W;
+    for (int i = 0; i < n; ++i) {
+        DD_HIP(hipMemsetAsync(m->nm + (size_t)streams_host[i] * hw, 0, hw, s));
+        m->nframes[streams_host[i]] = 0;
+    }
+    return DD_OK;
+}
+
 int mask_box_count(hipStream_t s, const uint8_t *mask, int H, int W, const int *d_boxes, const int *d_box_stream, int K, int *d_counts) {
     if (K <= 0) return DD_OK;
     hipLaunchKernelGGL(mask_box_count_k, dim3((unsigned)K), dim3(256), 0, s, mask, H, W, d_boxes, d_box_stream, d_counts);
@@ -332,6 +345,12 @@ int dd_mog2_apply_streams(dd_mog2 *m, const uint8_t *frames, const uint8_t *pres
         DD_REQUIRE(present_host[z] <= 1, DD_E_ARG, "dd_mog2_apply_streams: present[%d] = %d (0 or 1)", z, (int)present_host[z]);
     DD_DEVICE(m->ctx);
     return ddk::mog2_apply_streams(m, dd_pick_stream(m->ctx, stream), frames, present_host, learning_rate, mask, masked_frames);
+}
+
+int dd_mog2_reset_streams(dd_mog2 *m, const int *streams_host, int n, void *stream) {
+    DD_REQUIRE(m && n >= 0 && (n == 0 || streams_host), DD_E_ARG, "dd_mog2_reset_streams: bad argument");
+    DD_DEVICE(m->ctx);
+    return ddk::mog2_reset_streams(m, dd_pick_stream(m->ctx, stream), streams_host, n);
 }
 
 int dd_mog2_state(dd_mog2 *m, int stream_index, float *weight_host, float *variance_host, float *mean_host, uint8_t *nmodes_host) {

@@ -68,9 +68,9 @@ __device__ __forceinline__ bool suppresses(const SBox &pi, const SBox &pj, doubl
 // ---------------------------------------------------------------- k <= 64: one wave, one launch
 // blockIdx.x selects an independent problem (batched form: offsets[p] .. offsets[p+1]).
 template <typename TB>
-__global__ __launch_bounds__(64) void nms_small_k(const TB *__restrict__ boxes, const TB *__restrict__ keys,
-                                                  const int *__restrict__ offsets, int k_single, double thr, int mode,
-                                                  int max_keep, int *__restrict__ out_idx, int *__restrict__ out_n) {
+__device__ __forceinline__ void nms_small_body(const TB *__restrict__ boxes, const TB *__restrict__ keys,
+                                               const int *__restrict__ offsets, int k_single, double thr, int mode,
+                                               int max_keep, int *__restrict__ out_idx, int *__restrict__ out_n) {
     __shared__ SBox sb[64];
     __shared__ int sid[64];
     const int lane = threadIdx.x;
@@ -105,6 +105,20 @@ __global__ __launch_bounds__(64) void nms_small_k(const TB *__restrict__ boxes, 
     if (lane < k && ((keep >> lane) & 1ull))
         out_idx[o0 + __popcll(keep & ((1ull << lane) - 1ull))] = sid[lane];
     if (lane == 0) out_n[p] = __popcll(keep);
+}
+
+template <typename TB>
+__global__ __launch_bounds__(64) void nms_small_k(const TB *__restrict__ boxes, const TB *__restrict__ keys,
+                                                  const int *__restrict__ offsets, int k_single, double thr, int mode,
+                                                  int max_keep, int *__restrict__ out_idx, int *__restrict__ out_n) {
+    nms_small_body(boxes, keys, offsets, k_single, thr, mode, max_keep, out_idx, out_n);
+}
+
+// The batched form with one threshold per problem (thrs[blockIdx.x]): streams with their own --nms-max-overlap in one launch.
+__global__ __launch_bounds__(64) void nms_small_streams_k(const double *__restrict__ boxes, const double *__restrict__ keys,
+                                                          const int *__restrict__ offsets, const double *__restrict__ thrs, int mode,
+                                                          int *__restrict__ out_idx, int *__restrict__ out_n) {
+    nms_small_body(boxes, keys, offsets, 0, thrs[blockIdx.x], mode, 0, out_idx, out_n);
 }
 
 // ---------------------------------------------------------------- general path
@@ -533,6 +547,15 @@ int nms_batched_small(hipStream_t s, const double *boxes, const double *keys, co
     if (n_problems <= 0) return DD_OK;
     hipLaunchKernelGGL(nms_small_k<double>, dim3(n_problems), dim3(64), 0, s, boxes, keys, d_offsets, 0, thr, mode, 0,
                        out_idx, out_n);
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
+// The same with one threshold per problem: d_thrs f64 [n_problems] on the device.
+int nms_batched_small_streams(hipStream_t s, const double *boxes, const double *keys, const int *d_offsets, int n_problems,
+                              const double *d_thrs, int mode, int *out_idx, int *out_n) {
+    if (n_problems <= 0) return DD_OK;
+    hipLaunchKernelGGL(nms_small_streams_k, dim3(n_problems), dim3(64), 0, s, boxes, keys, d_offsets, d_thrs, mode, out_idx, out_n);
     DD_LAUNCH_CHECK();
     return DD_OK;
 }

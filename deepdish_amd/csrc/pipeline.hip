@@ -49,6 +49,10 @@ int ssd_finish(hipStream_t s, const float *boxes, const float *cls, const float 
 int tracker_group_create(dd_ctx *ctx, int n, double max_cos, double max_iou, int max_age, int n_init, int budget, int tcap,
                          int gcap, dd_tracker **out);
 int tracker_group_set_metric(dd_tracker *any, int metric);
+int tracker_set_params(dd_tracker *t, const double *max_cos, const double *max_iou, const int *max_age, const int *n_init);
+int tracker_reset(dd_tracker *t);
+long long tracker_group_stream_param_launches(const dd_tracker *any);
+int mog2_reset_streams(dd_mog2 *m, hipStream_t s, const int *streams_host, int n);
 int tracker_group_set_association(dd_tracker *any, int where);
 int trackers_predict(dd_tracker **ts, int S);
 int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const float *feats, int feats_on_device,
@@ -115,11 +119,17 @@ struct dd_pipeline {
     int det_kind = DET_SSD, det_in = 300, det_in_w = 300, n_anchors = 0, n_classes = 0, enc_batch = 0, enc_h = 64, enc_w = 32;   // enc_h x enc_w: the encoder's crop size (its engine's input)
     int label_offset = 1;                      // class id c is line c + label_offset of the label file (SSD 1, YOLOv5 0)
     float *d_anchors = nullptr;
-    double nms_overlap = 0.6, det_conf = 0.5;
+    double det_conf = 0.5;
     int max_det = MAX_DET_DEFAULT; float ssd_score_thr = SSD_SCORE_THR, ssd_iou_thr = SSD_IOU_THR;   // TFLite_Detection_PostProcess options (dd_pipeline_ssd_options)
-    double line[4] = {0, 0, 0, 0};
     std::vector<std::string> labels;           // label file lines (index = class id + 1, ssd_mobilenet.py:142-147)
     std::vector<std::string> wanted;
+    // What the reference takes per process, per stream (dd_pipeline_stream_*; dd_pipeline_create's one value for every stream until then):
+    std::vector<double> lines;                 // [S][4] --line
+    std::vector<uint8_t> wanted_of;            // [S][n_wanted] --wanted-labels as a mask over `wanted`
+    std::vector<double> nms_of;                // [S] --nms-max-overlap; nms_differ: not all equal
+    std::vector<double> ratio_of;              // [S] --background-subtraction-ratio (while mog2 is set)
+    bool nms_differ = false;
+    long long nms_streams_launches = 0, reset_calls = 0, streams_reset = 0;      // dd_pipeline_stream_param_stats
     std::vector<StreamState> st;
     std::vector<dd_tracker *> trks;
     DevBuf d_resized, d_tmp, d_post, d_det, d_fin, d_pack, d_nms, d_crop, d_patches, d_feats;
@@ -230,8 +240,10 @@ int present_list(const dd_pipeline *p, const uint8_t *present_host, const char *
     return DD_OK;
 }
 
-int wanted_index(const dd_pipeline *p, const std::string &name) {
-    for (size_t i = 0; i < p->wanted.size(); ++i) if (p->wanted[i] == name) return (int)i;
+// index of `name` in the wanted list if stream z wants it, else -1
+int wanted_index(const dd_pipeline *p, int z, const std::string &name) {
+    const uint8_t *m = p->wanted_of.data() + (size_t)z * p->wanted.size();
+    for (size_t i = 0; i < p->wanted.size(); ++i) if (m[i] && p->wanted[i] == name) return (int)i;
     return -1;
 }
 
@@ -286,8 +298,9 @@ int dd_pipeline_create(dd_ctx *ctx, int n_streams, int frame_h, int frame_w, dd_
     dd_pipeline *p = new dd_pipeline();
     p->ctx = ctx; p->S = n_streams; p->H = frame_h; p->W = frame_w;
     p->det = detector; p->enc = encoder; p->n_anchors = n_anchors; p->n_classes = n_classes;
-    p->nms_overlap = nms_max_overlap;
-    for (int i = 0; i < 4; ++i) p->line[i] = line_host[i];
+    p->lines.resize((size_t)n_streams * 4);
+    for (size_t i = 0; i < p->lines.size(); ++i) p->lines[i] = line_host[i % 4];
+    p->nms_of.assign(n_streams, nms_max_overlap);
     auto split = [](const char *s, std::vector<std::string> &out) {
         std::string cur;
         for (const char *c = s; *c; ++c) { if (*c == '\n') { out.push_back(cur); cur.clear(); } else cur.push_back(*c); }
@@ -295,6 +308,7 @@ int dd_pipeline_create(dd_ctx *ctx, int n_streams, int frame_h, int frame_w, dd_
     };
     split(labels_nl, p->labels);
     split(wanted_nl, p->wanted);
+    p->wanted_of.assign((size_t)n_streams * p->wanted.size(), 1);
     DD_HIP(hipSetDevice(ctx->device));
     int rc;
     if ((rc = dd_net_max_batch(encoder, &p->enc_batch)) != DD_OK) return rc;
@@ -528,6 +542,142 @@ int dd_pipeline_association(dd_pipeline *p, int where) {
     return ddk::tracker_group_set_association(p->trks[0], where);
 }
 
+// ---------------- per-stream parameters (the reference's flags are per process, i.e. per camera; deepdish.py:1394-1460)
+#define DD_BEFORE_FIRST_STEP(name) DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, name ": call before the first step")
+
+// --line (deepdish.py:739-744) per stream
+int dd_pipeline_stream_lines(dd_pipeline *p, const double *lines_host) {
+    DD_REQUIRE(p && lines_host, DD_E_ARG, "dd_pipeline_stream_lines: NULL argument");
+    DD_BEFORE_FIRST_STEP("dd_pipeline_stream_lines");
+    for (int i = 0; i < p->S * 4; ++i)
+        DD_REQUIRE(std::isfinite(lines_host[i]), DD_E_ARG, "dd_pipeline_stream_lines: lines[%d][%d] is not finite", i / 4, i % 4);
+    p->lines.assign(lines_host, lines_host + (size_t)p->S * 4);
+    return DD_OK;
+}
+
+int dd_pipeline_lines(dd_pipeline *p, const int *streams_host, int n, double *out_host) {
+    DD_REQUIRE(p && n >= 0 && (n == 0 || (streams_host && out_host)), DD_E_ARG, "dd_pipeline_lines: bad argument");
+    for (int i = 0; i < n; ++i)
+        DD_REQUIRE(streams_host[i] >= 0 && streams_host[i] < p->S, DD_E_ARG, "dd_pipeline_lines: stream %d of %d", streams_host[i], p->S);
+    for (int i = 0; i < n; ++i) memcpy(out_host + (size_t)i * 4, p->lines.data() + (size_t)streams_host[i] * 4, 4 * sizeof(double));
+    return DD_OK;
+}
+
+// --wanted-labels (deepdish.py:460-461) per stream, as a 0 / 1 mask over the pipeline's wanted list
+int dd_pipeline_stream_wanted(dd_pipeline *p, const uint8_t *mask_host) {
+    DD_REQUIRE(p && mask_host, DD_E_ARG, "dd_pipeline_stream_wanted: NULL argument");
+    DD_BEFORE_FIRST_STEP("dd_pipeline_stream_wanted");
+    const size_t nw = p->wanted.size();
+    for (size_t i = 0; i < (size_t)p->S * nw; ++i)
+        DD_REQUIRE(mask_host[i] <= 1, DD_E_ARG, "dd_pipeline_stream_wanted: mask[%zu][%zu] = %d (0 or 1)", i / nw, i % nw, (int)mask_host[i]);
+    p->wanted_of.assign(mask_host, mask_host + (size_t)p->S * nw);
+    return DD_OK;
+}
+
+// --max-cosine-distance, --max-iou-distance, --max-age (deepdish.py:516-517), n_init (tracker.py:40-49) per stream's tracker
+int dd_pipeline_stream_tracker_params(dd_pipeline *p, const double *max_cos_host, const double *max_iou_host, const int *max_age_host,
+                                      const int *n_init_host) {
+    DD_REQUIRE(p, DD_E_ARG, "dd_pipeline_stream_tracker_params: NULL pipeline");
+    DD_BEFORE_FIRST_STEP("dd_pipeline_stream_tracker_params");
+    for (int z = 0; z < p->S; ++z) {
+        DD_REQUIRE(!max_cos_host || (std::isfinite(max_cos_host[z]) && max_cos_host[z] >= 0), DD_E_ARG,
+                   "dd_pipeline_stream_tracker_params: max_cos[%d] = %g (finite, >= 0)", z, max_cos_host[z]);
+        DD_REQUIRE(!max_iou_host || (std::isfinite(max_iou_host[z]) && max_iou_host[z] >= 0), DD_E_ARG,
+                   "dd_pipeline_stream_tracker_params: max_iou[%d] = %g (finite, >= 0)", z, max_iou_host[z]);
+        DD_REQUIRE(!max_age_host || max_age_host[z] >= 0, DD_E_ARG, "dd_pipeline_stream_tracker_params: max_age[%d] = %d (>= 0)", z, max_age_host[z]);
+        DD_REQUIRE(!n_init_host || n_init_host[z] >= 0, DD_E_ARG, "dd_pipeline_stream_tracker_params: n_init[%d] = %d (>= 0)", z, n_init_host[z]);
+    }
+    for (int z = 0; z < p->S; ++z) {
+        const int rc = ddk::tracker_set_params(p->trks[z], max_cos_host ? max_cos_host + z : nullptr, max_iou_host ? max_iou_host + z : nullptr,
+                                               max_age_host ? max_age_host + z : nullptr, n_init_host ? n_init_host + z : nullptr);
+        if (rc != DD_OK) return rc;
+    }
+    return DD_OK;
+}
+
+// --nms-max-overlap (deepdish.py:995) per stream
+int dd_pipeline_stream_nms_overlap(dd_pipeline *p, const double *overlap_host) {
+    DD_REQUIRE(p && overlap_host, DD_E_ARG, "dd_pipeline_stream_nms_overlap: NULL argument");
+    DD_BEFORE_FIRST_STEP("dd_pipeline_stream_nms_overlap");
+    for (int z = 0; z < p->S; ++z)
+        DD_REQUIRE(std::isfinite(overlap_host[z]), DD_E_ARG, "dd_pipeline_stream_nms_overlap: overlap[%d] is not finite", z);
+    p->nms_of.assign(overlap_host, overlap_host + p->S);
+    p->nms_differ = false;
+    for (int z = 1; z < p->S; ++z) p->nms_differ = p->nms_differ || p->nms_of[z] != p->nms_of[0];
+    return DD_OK;
+}
+
+// --background-subtraction-ratio (deepdish.py:957) per stream; subtraction itself is on or off for the whole pipeline
+int dd_pipeline_stream_motion_ratio(dd_pipeline *p, const double *ratio_host) {
+    DD_REQUIRE(p && ratio_host, DD_E_ARG, "dd_pipeline_stream_motion_ratio: NULL argument");
+    DD_REQUIRE(p->mog2, DD_E_STATE, "dd_pipeline_stream_motion_ratio: background subtraction is off (dd_pipeline_background_subtraction first)");
+    DD_BEFORE_FIRST_STEP("dd_pipeline_stream_motion_ratio");
+    for (int z = 0; z < p->S; ++z)
+        DD_REQUIRE(ratio_host[z] >= 0.0 && ratio_host[z] <= 1.0, DD_E_ARG,
+                   "dd_pipeline_stream_motion_ratio: ratio[%d] = %g (0 .. 1; subtraction cannot be off for some streams only)", z, ratio_host[z]);
+    p->ratio_of.assign(ratio_host, ratio_host + p->S);
+    return DD_OK;
+}
+
+// The listed streams start over (the reference restarts the camera's process): every piece of per-stream state back to what
+// dd_pipeline_create, dd_pipeline_background_subtraction and dd_pipeline_detector_skip_streams left.  Host state, plus the memsets of the
+// MOG2 mode-count plane and the motion-mask plane on the main stream, which the next step's launches follow.
+int dd_pipeline_reset_streams(dd_pipeline *p, const int *streams_host, int n) {
+    DD_REQUIRE(p && n >= 0 && (n == 0 || streams_host), DD_E_ARG, "dd_pipeline_reset_streams: bad argument");
+    std::vector<uint8_t> listed(p->S, 0);
+    for (int i = 0; i < n; ++i) {
+        const int z = streams_host[i];
+        DD_REQUIRE(z >= 0 && z < p->S, DD_E_ARG, "dd_pipeline_reset_streams: stream %d of %d", z, p->S);
+        DD_REQUIRE(!listed[z], DD_E_ARG, "dd_pipeline_reset_streams: stream %d is listed twice", z);
+        listed[z] = 1;
+    }
+    // one counter for all streams cannot give one stream a fresh first detector step
+    DD_REQUIRE(p->skip_n <= 0, DD_E_STATE, "dd_pipeline_reset_streams: the pipeline has the pipeline-wide object_detector_skip_frames counter "
+               "(dd_pipeline_detector_skip_frames); dd_pipeline_detector_skip_streams has one per stream and takes a reset");
+    if (n == 0) return DD_OK;
+    DD_DEVICE(p->ctx);
+    int rc;
+    for (int i = 0; i < n; ++i) if ((rc = ddk::tracker_reset(p->trks[streams_host[i]])) != DD_OK) return rc;
+    if (p->mog2) {
+        hipStream_t s = p->ctx->stream;
+        if ((rc = ddk::mog2_reset_streams(p->mog2, s, streams_host, n)) != DD_OK) return rc;
+        const size_t hw = (size_t)p->H * p->W;
+        for (int i = 0; i < n; ++i) DD_HIP(hipMemsetAsync(p->d_mask.as<uint8_t>() + (size_t)streams_host[i] * hw, 0, hw, s));
+    }
+    for (int i = 0; i < n; ++i) {
+        const int z = streams_host[i];
+        StreamState &q = p->st[z];
+        q.db.clear(); q.votes.clear();
+        q.counts.assign(p->wanted.size() * 4, 0);
+        q.det_cls.clear(); q.det_conf.clear();
+        q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
+        q.ib.clear(); q.is.clear(); q.ic.clear(); q.keep.clear();
+        q.det_tlwh.clear();
+        q.seen = 0;
+        if (p->skip_streams) {                     // counter and phase as at construction; the retained rows leave the store at its next refresh
+            p->sk_rem[z] = 0; p->sk_has[z] = 0; p->sk_last[z] = 0;
+            p->rows_retained -= p->ret_n[z];
+            p->ret_n[z] = 0;
+        }
+    }
+    p->det_pending = nullptr;                      // a queued look-ahead run is discarded: the next step runs the detector itself
+    p->reset_calls += 1; p->streams_reset += n;
+    return DD_OK;
+}
+
+int dd_pipeline_stream_param_stats(dd_pipeline *p, long long *out4_host) {
+    DD_REQUIRE(p && out4_host, DD_E_ARG, "dd_pipeline_stream_param_stats: NULL argument");
+    out4_host[0] = p->nms_streams_launches; out4_host[1] = ddk::tracker_group_stream_param_launches(p->trks[0]);
+    out4_host[2] = p->reset_calls; out4_host[3] = p->streams_reset;
+    return DD_OK;
+}
+
+int dd_pipeline_mog2(dd_pipeline *p, dd_mog2 **out) {
+    DD_REQUIRE(p && out, DD_E_ARG, "dd_pipeline_mog2: NULL argument");
+    *out = p->mog2;
+    return DD_OK;
+}
+
 // deepdish.py:512,889: background subtraction on (ratio = --background-subtraction-ratio, default 0.25) or off
 // (ratio < 0 = --disable-background-subtraction).  Turning it on starts a fresh model; masking =
 // --enable-background-masking (the detector and the encoder then see cv2.bitwise_and(frame, frame, mask=fgMask)).
@@ -545,6 +695,7 @@ int dd_pipeline_background_subtraction(dd_pipeline *p, double ratio, int masking
     if ((rc = p->d_mask.reserve((size_t)p->S * p->H * p->W)) != DD_OK) return rc;
     if (masking && (rc = p->d_masked.reserve((size_t)p->S * p->H * p->W * 3)) != DD_OK) return rc;
     p->motion_ratio = ratio; p->bg_masking = masking != 0;
+    p->ratio_of.assign(p->S, ratio);
     return DD_OK;
 }
 
@@ -632,6 +783,7 @@ int dd_pipeline_overlay(dd_pipeline *p, const int *streams_host, int n, int *siz
         const int z = streams_host[i];
         StreamState &st = p->st[z];
         const bool stepped = st.seen > 0;
+        const double *line = p->lines.data() + (size_t)z * 4;
         int nl = 0, rc;
         if ((rc = dd_tracker_count(st.trk, 0, &nl)) != DD_OK) return rc;
         ints.resize((size_t)nl * 6); means.resize((size_t)nl * 8);
@@ -648,7 +800,7 @@ int dd_pipeline_overlay(dd_pipeline *p, const int *streams_host, int n, int *siz
             if (npts > 1) {                                               // :1071-1078
                 const double a[2] = {it->second[npts - 1].first, it->second[npts - 1].second};
                 const double b[2] = {it->second[npts - 2].first, it->second[npts - 2].second};
-                crossed = seg_intersect(p->line, p->line + 2, a, b);
+                crossed = seg_intersect(line, line + 2, a, b);
             }
             if (fill) {
                 DD_REQUIRE(nt < (size_t)caps_host[0] && np + npts <= (size_t)caps_host[1] && nc + crossed <= (size_t)caps_host[2], DD_E_CAPACITY,
@@ -683,7 +835,7 @@ int dd_pipeline_overlay(dd_pipeline *p, const int *streams_host, int n, int *siz
         }
         nd += sz[3];
     }
-    if (fill) for (int i = 0; i < 4; ++i) line_host[i] = p->line[i];
+    if (fill) for (int i = 0; i < 4; ++i) line_host[i] = p->lines[(size_t)streams_host[0] * 4 + i];
     return DD_OK;
 }
 
@@ -844,7 +996,9 @@ __global__ void __launch_bounds__(256) skip_gather_rows_k(const float4 *__restri
 }
 
 // Count-line logic of one stream after its tracker update (deepdish.py:1035-1114, 1303-1312); host only.
-void count_line_one_stream(dd_pipeline *p, StreamState &st) {
+void count_line_one_stream(dd_pipeline *p, int z) {
+    StreamState &st = p->st[z];
+    const double *line = p->lines.data() + (size_t)z * 4;
     int nd = 0, nl = 0;
     dd_tracker_count(st.trk, 1, &nd);
     dd_tracker_count(st.trk, 0, &nl);
@@ -863,7 +1017,7 @@ void count_line_one_stream(dd_pipeline *p, StreamState &st) {
                 for (size_t q = 0; q + 1 < it->second.size() && !hit; ++q) {
                     const double a[2] = {it->second[q].first, it->second[q].second};
                     const double b[2] = {it->second[q + 1].first, it->second[q + 1].second};
-                    hit = seg_intersect(p->line, p->line + 2, a, b);
+                    hit = seg_intersect(line, line + 2, a, b);
                 }
                 if (hit) delcounts[vote_label(p, st.votes[id])] += 1;
                 it->second.clear();
@@ -891,18 +1045,18 @@ void count_line_one_stream(dd_pipeline *p, StreamState &st) {
         if (pts.size() > 1) {
             const double p2[2] = {pts.back().first, pts.back().second};
             const double q2[2] = {pts[pts.size() - 2].first, pts[pts.size() - 2].second};
-            const double cp = cross2(p->line[2] - p->line[0], p->line[3] - p->line[1], q2[0] - p2[0], q2[1] - p2[1]);
-            if (seg_intersect(p->line, p->line + 2, p2, q2)) events.emplace_back(vote_label(p, st.votes[id]), cp);
+            const double cp = cross2(line[2] - line[0], line[3] - line[1], q2[0] - p2[0], q2[1] - p2[1]);
+            if (seg_intersect(line, line + 2, p2, q2)) events.emplace_back(vote_label(p, st.votes[id]), cp);
         }
     }
     for (auto &e : events) {
-        const int wi = wanted_index(p, e.first);
+        const int wi = wanted_index(p, z, e.first);
         if (wi < 0) continue;
         st.counts[wi * 4 + (e.second >= 0 ? 0 : 1)] += 1;
         st.counts[wi * 4 + 2] += 1;
     }
     for (auto &d : delcounts) {
-        const int wi = wanted_index(p, d.first);
+        const int wi = wanted_index(p, z, d.first);
         if (wi >= 0) st.counts[wi * 4 + 3] += d.second;
     }
 }
@@ -1063,7 +1217,7 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
                         int c;
                         memcpy(&c, b + 5, 4);
                         const float sc = b[4];
-                        if (wanted_index(p, class_name(p, c)) < 0 || !(sc >= (float)p->det_conf)) continue;
+                        if (wanted_index(p, dl[i], class_name(p, c)) < 0 || !(sc >= (float)p->det_conf)) continue;
                         q.boxes0.insert(q.boxes0.end(), {(double)b[0], (double)b[1], (double)(b[2] - b[0]), (double)(b[3] - b[1])});   // f32 arithmetic, :140-142
                         q.scores0.push_back((double)sc);
                         q.cls0.push_back(c);
@@ -1086,7 +1240,7 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
                     std::stable_sort(order, order + no, [&](int a, int b) { return hs[z * MAX_DET + a] > hs[z * MAX_DET + b]; });
                     for (int k = 0; k < no; ++k) {
                         const int i = order[k], c = (int)hc[z * MAX_DET + i];
-                        if (c < 0 || c >= (int)p->tfl_labels.size() || wanted_index(p, p->tfl_labels[c]) < 0) continue;
+                        if (c < 0 || c >= (int)p->tfl_labels.size() || wanted_index(p, dl[z], p->tfl_labels[c]) < 0) continue;
                         // the class stored for the vote is resolved through class_name() = labels[c + label_offset]: the same line of the
                         // label file only while no blank line precedes it -- store the index class_name() maps back to this very label
                         int cs = -1;
@@ -1111,7 +1265,7 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
                     q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
                     for (int i = 0; i < hn[z]; ++i) {                                                  // :204-212
                         const double sc = hs[z * MAX_DET + i];
-                        if (!(sc >= p->det_conf) || wanted_index(p, class_name(p, hc[z * MAX_DET + i])) < 0) continue;
+                        if (!(sc >= p->det_conf) || wanted_index(p, dl[z], class_name(p, hc[z * MAX_DET + i])) < 0) continue;
                         const double *b = hb + ((size_t)z * MAX_DET + i) * 4;
                         q.boxes0.insert(q.boxes0.end(), {b[0], b[1], b[2] - b[0], b[3] - b[1]});
                         q.scores0.push_back(sc);
@@ -1172,7 +1326,7 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
             size_t nk = 0;
             for (size_t k = 0; k < q.is.size(); ++k) {
                 const int64_t w = q.ib[k * 4 + 2], h = q.ib[k * 4 + 3];
-                if (!((double)cnt[off0[i] + k] >= p->motion_ratio * (double)w * (double)h)) { p->motion_rejected++; continue; }
+                if (!((double)cnt[off0[i] + k] >= p->ratio_of[act[i]] * (double)w * (double)h)) { p->motion_rejected++; continue; }
                 for (int c = 0; c < 4; ++c) q.ib[nk * 4 + c] = q.ib[k * 4 + c];
                 q.is[nk] = q.is[k]; q.ic[nk] = q.ic[k];
                 ++nk;
@@ -1185,12 +1339,18 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
     if (K > 0) {
         bool small = true;
         for (int i = 0; i < n; ++i) if (off[i + 1] - off[i] > 64) small = false;
-        const size_t in_bytes = (size_t)K * 5 * sizeof(double) + (size_t)(n + 1) * sizeof(int);
+        // one --nms-max-overlap per stream: when this step's streams do not agree, their thresholds ride in the same upload, in front
+        // of the offsets, for the per-problem launch
+        bool thr_differ = false;
+        for (int i = 1; i < n && p->nms_differ && !thr_differ; ++i) thr_differ = p->nms_of[act[i]] != p->nms_of[act[0]];
+        const size_t n_thr = small && thr_differ ? (size_t)n : 0;
+        const size_t in_bytes = ((size_t)K * 5 + n_thr) * sizeof(double) + (size_t)(n + 1) * sizeof(int);
         const size_t out_bytes = (size_t)(K + n) * sizeof(int);
         if ((rc = p->h_nms.reserve(in_bytes + out_bytes + 256)) != DD_OK) return rc;
         if ((rc = p->d_nms.reserve(in_bytes + out_bytes + 256 + (small ? 0 : ddk::nms_scratch_bytes(4096)))) != DD_OK) return rc;
         double *hb = p->h_nms.as<double>(), *hk = hb + (size_t)K * 4;
-        int *ho = reinterpret_cast<int *>(hk + K);
+        for (size_t i = 0; i < n_thr; ++i) hk[K + i] = p->nms_of[act[i]];
+        int *ho = reinterpret_cast<int *>(hk + K + n_thr);
         ddk::parallel_for(n, GRAIN, [&](int i0, int i1) {
             for (int i = i0; i < i1; ++i) {
                 const StreamState &q = st[act[i]];
@@ -1203,15 +1363,18 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
         DD_STAGE_BEGIN(1);
         DD_HIP(hipMemcpyAsync(d, hb, in_bytes, hipMemcpyHostToDevice, s));
         const double *dbx = reinterpret_cast<const double *>(d), *dk = dbx + (size_t)K * 4;
-        const int *doff = reinterpret_cast<const int *>(dk + K);
+        const int *doff = reinterpret_cast<const int *>(dk + K + n_thr);
         int *didx = reinterpret_cast<int *>(d + ((in_bytes + 63) / 64) * 64), *dnk = didx + K;
-        if (small) {
-            if ((rc = ddk::nms_batched_small(s, dbx, dk, doff, n, p->nms_overlap, 0, didx, dnk)) != DD_OK) return rc;
+        if (n_thr) {
+            if ((rc = ddk::nms_batched_small_streams(s, dbx, dk, doff, n, dk + K, 0, didx, dnk)) != DD_OK) return rc;
+            p->nms_streams_launches += 1;
+        } else if (small) {
+            if ((rc = ddk::nms_batched_small(s, dbx, dk, doff, n, p->nms_of[act[0]], 0, didx, dnk)) != DD_OK) return rc;
         } else {
             void *scr = d + ((in_bytes + 63) / 64) * 64 + ((out_bytes + 63) / 64) * 64;
             for (int i = 0; i < n; ++i) {
                 const int k = off[i + 1] - off[i];
-                if ((rc = ddk::nms_ex(s, dbx + (size_t)off[i] * 4, dk + off[i], k, p->nms_overlap, 0, 0, didx + off[i], dnk + i,
+                if ((rc = ddk::nms_ex(s, dbx + (size_t)off[i] * 4, dk + off[i], k, p->nms_of[act[i]], 0, 0, didx + off[i], dnk + i,
                                       scr, ddk::nms_scratch_bytes(4096))) != DD_OK) return rc;
             }
         }
@@ -1365,7 +1528,7 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
     if ((rc = ddk::trackers_update_end(atrks.data(), n)) != DD_OK) return rc;
     DD_STAGE_END(5);
     ddk::parallel_for(n, GRAIN, [&](int i0, int i1) {
-        for (int i = i0; i < i1; ++i) { count_line_one_stream(p, st[act[i]]); st[act[i]].seen += 1; }
+        for (int i = i0; i < i1; ++i) { count_line_one_stream(p, act[i]); st[act[i]].seen += 1; }
     });
     const double t4 = now_s();
     p->t_det += t1 - t0; p->t_nms += t2 - t1; p->t_enc += t3 - t2; p->t_trk += t4 - t3;

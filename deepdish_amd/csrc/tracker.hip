@@ -165,6 +165,7 @@ struct TrackerPool {
     std::vector<int> assoc_base;                          // per stream: where its decision sits in h_assoc, -1 = none (T or n is 0)
     long long n_dev_updates = 0, n_host_updates = 0, n_fallback_streams = 0;
     long long assoc_d2h_bytes = 0;                        // what the decisions brought to the host: cost matrices, or lists + handed-back matrices
+    long long n_stream_param_launches = 0;                // group updates decided by assoc_match_streams_k (their trackers' settings differ)
     // phase state of the current group update
     std::vector<dd_tracker *> cur;
     std::vector<int> det_off, cost_base;
@@ -365,6 +366,38 @@ int tracker_group_create(dd_ctx *ctx, int n, double max_cos, double max_iou, int
     return DD_OK;
 }
 
+// --max-cosine-distance, --max-iou-distance, --max-age (deepdish.py:516-517) and n_init (tracker.py:40-49) of ONE tracker of a group; a
+// NULL leaves the value as it is.  The host decision reads them per tracker; trackers_update_begin picks the device launch that fits.
+int tracker_set_params(dd_tracker *t, const double *max_cos, const double *max_iou, const int *max_age, const int *n_init) {
+    DD_REQUIRE(t, DD_E_ARG, "tracker_set_params: NULL tracker");
+    DD_REQUIRE(!t->pool->upd_inflight, DD_E_STATE, "tracker parameters: an update of the group is in flight");
+    if (max_cos) t->max_cos = *max_cos;
+    if (max_iou) t->max_iou = *max_iou;
+    if (max_age) t->max_age = *max_age;
+    if (n_init) t->n_init = *n_init;
+    return DD_OK;
+}
+
+// One tracker of a group back to what tracker_new made (tracker.py:40-49: no tracks, _next_id = 1); the others are not touched.  Host
+// state only: every slot's gallery chunks go back to the pool, and stale rows of the chunk table are never read (a slot's gallery count
+// is 0 until gallery_place hands it a chunk, which rewrites its row).
+int tracker_reset(dd_tracker *t) {
+    DD_REQUIRE(t, DD_E_ARG, "tracker_reset: NULL tracker");
+    TrackerPool *p = t->pool;
+    DD_REQUIRE(!p->upd_inflight, DD_E_STATE, "tracker reset: an update of the group is in flight");
+    for (int sl : t->pending_free) gallery_free_slot(p, sl);
+    for (auto &tr : t->tracks) gallery_free_slot(p, tr.slot);
+    t->pending_free.clear(); t->tracks.clear(); t->deleted.clear();
+    t->live_means.clear(); t->dead_means.clear(); t->last_pairs.clear(); t->m_upd.clear(); t->m_new.clear();
+    t->next_id = 1;
+    t->ph_n = t->ph_T = 0; t->ph_cost_base = -1;
+    t->free_slots.resize(t->tcap);
+    for (int i = 0; i < t->tcap; ++i) t->free_slots[i] = t->slot_base + t->tcap - 1 - i;
+    return DD_OK;
+}
+
+long long tracker_group_stream_param_launches(const dd_tracker *any) { return any ? any->pool->n_stream_param_launches : 0; }
+
 // nn_matching.py:126-132: the metric of the whole group (its trackers share the gallery and the association launch).  Only while the
 // group has seen no detection: the gallery rows of the two metrics are not interchangeable.
 int tracker_group_set_metric(dd_tracker *any, int metric) {
@@ -456,10 +489,17 @@ int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const
         p->upd_inflight = true;
         return DD_OK;
     }
+    // the device decision takes max_cos, max_iou, max_age as launch arguments while the update's trackers agree on them; otherwise they
+    // are staged per decided stream behind the descriptors, in the same copy, for assoc_match_streams_k
+    bool par_differ = false;
+    for (int z = 1; z < S && use_dev && !par_differ; ++z)
+        par_differ = ts[z]->max_cos != ts[0]->max_cos || ts[z]->max_iou != ts[0]->max_iou || ts[z]->max_age != ts[0]->max_age;
     // ---- stage inputs: [det tlwh f64 D*4][8 int arrays of R rows][5 ints per stream the device decides]
+    //      (+ [pad to 8 bytes][2 f64 per such stream][1 int per such stream] when their settings differ)
     const size_t off_rows = (size_t)D * 4 * sizeof(double);
     const size_t off_desc = off_rows + (size_t)8 * R * sizeof(int);
-    const size_t in_bytes = off_desc + (use_dev ? (size_t)5 * S * sizeof(int) : 0);
+    const size_t off_par = (off_desc + (size_t)5 * S * sizeof(int) + 7) / 8 * 8, off_age = off_par + (size_t)2 * S * sizeof(double);
+    const size_t in_bytes = !use_dev ? off_desc : par_differ ? off_age + (size_t)S * sizeof(int) : off_desc + (size_t)5 * S * sizeof(int);
     if ((rc = p->h_in.reserve(in_bytes + 64)) != DD_OK) return rc;
     if ((rc = p->d_in.reserve(in_bytes + 64)) != DD_OK) return rc;
     char *h = p->h_in.as<char>();
@@ -485,10 +525,13 @@ int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const
     size_t out_ints = 0;
     if (use_dev) {                                              // (row base, T, n, cost base, output base) per stream with T > 0 && n > 0
         int *hd = reinterpret_cast<int *>(h + off_desc);
+        double *hpd = reinterpret_cast<double *>(h + off_par);
+        int *hpa = reinterpret_cast<int *>(h + off_age);
         int row_base = 0;
         for (int z = 0; z < S; ++z) {
             const dd_tracker *t = ts[z];
             if (t->ph_T > 0 && t->ph_n > 0) {
+                if (par_differ) { hpd[2 * n_dec] = t->max_cos; hpd[2 * n_dec + 1] = t->max_iou; hpa[n_dec] = t->max_age; }
                 int *e = hd + 5 * n_dec++;
                 e[0] = row_base; e[1] = t->ph_T; e[2] = t->ph_n; e[3] = p->cost_base[z]; e[4] = (int)out_ints;
                 p->assoc_base[z] = (int)out_ints;
@@ -526,6 +569,12 @@ int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const
         if (use_dev) {                                          // the decision itself; its lists and status words come back, the matrices stay
             if ((rc = p->d_assoc.reserve(out_ints * sizeof(int))) != DD_OK) return rc;
             if ((rc = p->h_assoc.reserve(out_ints * sizeof(int))) != DD_OK) return rc;
+            if (par_differ) {
+                if ((rc = ddk::assoc_match_streams(s, p->d_cost.as<double>(), dr + R, dr + 2 * R, reinterpret_cast<const int *>(d + off_desc), n_dec,
+                                                   reinterpret_cast<const double *>(d + off_par), reinterpret_cast<const int *>(d + off_age),
+                                                   p->d_assoc.as<int>())) != DD_OK) return rc;
+                p->n_stream_param_launches += n_dec > 0;
+            } else
             if ((rc = ddk::assoc_match(s, p->d_cost.as<double>(), dr + R, dr + 2 * R, reinterpret_cast<const int *>(d + off_desc), n_dec,
                                        ts[0]->max_cos, ts[0]->max_iou, ts[0]->max_age, p->d_assoc.as<int>())) != DD_OK) return rc;
             DD_HIP(hipMemcpyAsync(p->h_assoc.p, p->d_assoc.p, out_ints * sizeof(int), hipMemcpyDeviceToHost, s));

@@ -68,6 +68,114 @@ def _skip_streams(skip_frames, skip_phase, S):
     return n, phase
 
 
+def _stream_values(v, what, S, integer=False):
+    """A parameter the reference takes per process (max_age, n_init, max_cosine_distance, max_iou_distance, nms_max_overlap): a Python or
+    NumPy scalar, for all streams, or a sequence of exactly S values -> contiguous [S], int32 (integer=True) or float64.  ValueError
+    naming the parameter for a str, another rank or length, a non-integer in an integer parameter, a non-finite value."""
+    if isinstance(v, (str, bytes)) or v is None:
+        raise ValueError('%s: a number, or one per stream (%d of them), got %r' % (what, S, v))
+    a = np.asarray(v)
+    if a.dtype.kind not in 'iuf':
+        raise ValueError('%s: a number, or one per stream (%d of them), got %r' % (what, S, v))
+    if a.ndim == 0:
+        a = np.full(S, int(a) if integer else float(a))           # (an integer parameter given as one float is truncated, as int(max_age) always did)
+    elif a.ndim != 1 or a.shape[0] != S:
+        raise ValueError('%s: one value, or one per stream with shape (%d,), got shape %r' % (what, S, a.shape))
+    elif integer and a.dtype.kind not in 'iu':
+        raise ValueError('%s: integers, got %s' % (what, a.dtype))
+    if not np.all(np.isfinite(a)):
+        raise ValueError('%s: finite values, got %r' % (what, a.tolist()))
+    if (a < 0).any():
+        raise ValueError('%s: >= 0 for every stream, got %r' % (what, a.tolist()))
+    return np.ascontiguousarray(a, dtype=np.int32 if integer else np.float64)
+
+
+def _stream_lines(line, S, W, H):
+    """line= -> float64 [S, 4] (x1, y1, x2, y2 per stream).  None: the reference's default [[W/2, 0], [W/2, H]] (deepdish.py:739-741) for
+    every stream; a value of size 4: the pipeline's line, as always; shape (S, 4) or (S, 2, 2): one line per stream.  ValueError naming
+    `line` for anything else and for a coordinate that is not finite."""
+    if line is None:
+        line = np.array([[W / 2, 0], [W / 2, H]], dtype=int)        # deepdish.py:739-741
+    try:
+        a = np.asarray(line, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError('line: 4 numbers, or an array of shape (%d, 4) or (%d, 2, 2), got %r' % (S, S, line)) from None
+    if a.size == 4:
+        a = np.tile(a.reshape(1, 4), (S, 1))
+    elif a.shape in ((S, 4), (S, 2, 2)):
+        a = a.reshape(S, 4)
+    else:
+        raise ValueError('line: 4 numbers, or one line per stream with shape (%d, 4) or (%d, 2, 2), got shape %r' % (S, S, a.shape))
+    if not np.all(np.isfinite(a)):
+        raise ValueError('line: finite coordinates, got %r' % (a.tolist(),))
+    return np.ascontiguousarray(a)
+
+
+def _stream_wanted(wanted_labels, S):
+    """wanted_labels= -> (wanted, per_stream).  A sequence of str: the list of every stream -> (that list, None).  A sequence of S
+    sequences of str: one list per stream (an empty one is legal) -> (their union in order of first appearance, scanning streams
+    0 .. S - 1, the S lists).  ValueError naming `wanted_labels` for a bare str, a mix of both forms, another number of lists, or a list
+    entry that is not a str."""
+    if isinstance(wanted_labels, (str, bytes)) or wanted_labels is None:
+        raise ValueError('wanted_labels: a sequence of label names (or one such sequence per stream), got %r' % (wanted_labels,))
+    top = list(wanted_labels)
+    if all(isinstance(l, str) for l in top):
+        return top, None
+    if any(isinstance(l, (str, bytes)) for l in top):
+        raise ValueError('wanted_labels: label names, or one list of label names per stream, not a mix of both: %r' % (top,))
+    if len(top) != S:
+        raise ValueError('wanted_labels: one list per stream, %d of them, got %d' % (S, len(top)))
+    per = []
+    for z, lst in enumerate(top):
+        try:
+            lst = list(lst)
+        except TypeError:
+            raise ValueError('wanted_labels[%d]: a list of label names, got %r' % (z, lst)) from None
+        if not all(isinstance(l, str) for l in lst):
+            raise ValueError('wanted_labels[%d]: label names must be str, got %r' % (z, lst))
+        per.append(lst)
+    union = []
+    for lst in per:
+        union += [l for l in lst if l not in union]
+    return union, per
+
+
+def _stream_ratio(ratio, S):
+    """background_subtraction_ratio= -> None (subtraction off: None or one negative value, --disable-background-subtraction) or float64
+    [S].  One value holds for all streams; a sequence gives S values, each in [0, 1] -- subtraction cannot be off for some streams only,
+    so a None or negative entry inside a sequence is a ValueError, as are another length, rank or type."""
+    if ratio is None:
+        return None
+    if isinstance(ratio, (str, bytes)):
+        raise ValueError('background_subtraction_ratio: a number, None, or one number per stream, got %r' % (ratio,))
+    if np.ndim(ratio) == 0:
+        return None if float(ratio) < 0 else np.full(S, float(ratio))
+    seq = list(ratio) if np.ndim(ratio) == 1 else None
+    if seq is None or len(seq) != S:
+        raise ValueError('background_subtraction_ratio: one value, or one per stream with shape (%d,), got shape %r' % (S, np.shape(ratio)))
+    if any(r is None for r in seq):
+        raise ValueError('background_subtraction_ratio: None inside a sequence -- subtraction is on or off for the whole pipeline, got %r' % (seq,))
+    a = np.asarray(seq)
+    if a.dtype.kind not in 'iuf' or not np.all((a >= 0) & (a <= 1)):
+        raise ValueError('background_subtraction_ratio: every stream\'s value in [0, 1] (subtraction cannot be off for some streams only), '
+                         'got %r' % (seq,))
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _reset_streams(streams, S):
+    """reset(streams) -> contiguous int32 list; ValueError for an index outside 0 .. S - 1 or listed twice."""
+    a = np.asarray(list(streams))
+    if a.size == 0:
+        return np.zeros(0, np.int32)
+    if a.ndim != 1 or a.dtype.kind not in 'iu':
+        raise ValueError('streams: a list of stream indices, got %r' % (streams,))
+    if ((a < 0) | (a >= S)).any():
+        raise ValueError('streams: indices 0 .. %d, got %r' % (S - 1, a.tolist()))
+    if len(set(a.tolist())) != a.size:
+        raise ValueError('streams: a stream is listed twice in %r' % (a.tolist(),))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 class MultiStreamPipeline:
     def __init__(self, n_streams, model='synthetic-ssd_mobilenet_v1', encoder_model='synthetic-mars-64x32x3',
                  labels=None, wanted_labels=('person',), input_size=(640, 480), line=None, max_cosine_distance=0.2,
@@ -84,6 +192,14 @@ class MultiStreamPipeline:
             raise ValueError('%s: detector_letterbox is the YOLOv5 detector\'s option; the other detectors are trained on stretched input' % model)
         # an int: one counter per pipeline (lock-step); S ints, or any phase: one counter per stream -- ValueError before anything is built
         skip_n, skip_phase = _skip_streams(object_detector_skip_frames, object_detector_skip_phase, int(n_streams))
+        # what the reference takes per process -- one value for all streams, or one per stream (ValueError before anything is built)
+        S = int(n_streams)
+        lines = _stream_lines(line, S, input_size[0], input_size[1])
+        wanted, wanted_per = _stream_wanted(wanted_labels, S)
+        v_age, v_init = _stream_values(max_age, 'max_age', S, integer=True), _stream_values(n_init, 'n_init', S, integer=True)
+        v_cos, v_iou = _stream_values(max_cosine_distance, 'max_cosine_distance', S), _stream_values(max_iou_distance, 'max_iou_distance', S)
+        v_nms = _stream_values(nms_max_overlap, 'nms_max_overlap', S)
+        _stream_ratio(background_subtraction_ratio, S)
         self.metric = metric
         metric_kind = _metric_kind(metric)   # 'cosine' or 'euclidean' (nn_matching.py:126-132), else ValueError -- before anything is built
         self.association = association
@@ -91,7 +207,8 @@ class MultiStreamPipeline:
         self.ctx = context or default_context()
         self.S = int(n_streams)
         self.W, self.H = input_size
-        self.wanted = list(wanted_labels)
+        self.wanted = wanted                  # all streams' labels: the layout of counts(); wanted_of(z) is stream z's own list
+        self._wanted_per = wanted_per
         self.model_name = str(model)
         # the reference picks the detector plugin by a substring of --model (deepdish.py:482-502)
         self.kind = ('yolov5' if 'yolov5' in model else None if ('yolo' in model or 'saved_model' in model) else
@@ -152,17 +269,27 @@ class MultiStreamPipeline:
             self.enc.use_graph(True)
             if self.det is not None:
                 self.det.use_graph(True)
-        if line is None:
-            line = np.array([[self.W / 2, 0], [self.W / 2, self.H]], dtype=int)        # deepdish.py:739-741
-        self.line = np.ascontiguousarray(np.asarray(line, dtype=np.float64).reshape(4))
+        self.lines = lines                    # [S, 4]; self.line: the pipeline's line (stream 0's, when every stream has its own)
+        self.line = np.ascontiguousarray(lines[0])
         h = P()
         check(lib().dd_pipeline_create(self.ctx.handle, self.S, self.H, self.W, self.det._h if self.det else None,
                                        ptr(anchors), n_anchors, n_classes, self.enc._h,
                                        '\n'.join(self.label_lines).encode(), '\n'.join(self.wanted).encode(),
-                                       float(max_cosine_distance), float(nms_max_overlap), float(max_iou_distance),
-                                       int(max_age), int(n_init), ptr(self.line), int(track_capacity),
+                                       float(v_cos[0]), float(v_nms[0]), float(v_iou[0]),
+                                       int(v_age[0]), int(v_init[0]), ptr(self.line), int(track_capacity),
                                        int(gallery_capacity), ctypes.byref(h)), 'dd_pipeline_create')
         self._h = h
+        # only values that really differ between streams reach the per-stream setters: S equal values are the scalar pipeline exactly
+        if (lines != lines[0]).any():
+            check(lib().dd_pipeline_stream_lines(self._h, ptr(lines)), 'dd_pipeline_stream_lines')
+        if wanted_per is not None and any(set(l) != set(wanted) for l in wanted_per):
+            mask = np.ascontiguousarray([[int(l in own) for l in wanted] for own in wanted_per], dtype=np.uint8).reshape(self.S, len(wanted))
+            check(lib().dd_pipeline_stream_wanted(self._h, ptr(mask)), 'dd_pipeline_stream_wanted')
+        differ = [a if (a != a[0]).any() else None for a in (v_cos, v_iou, v_age, v_init)]
+        if any(a is not None for a in differ):
+            check(lib().dd_pipeline_stream_tracker_params(self._h, *[ptr(a) for a in differ]), 'dd_pipeline_stream_tracker_params')
+        if (v_nms != v_nms[0]).any():
+            check(lib().dd_pipeline_stream_nms_overlap(self._h, ptr(v_nms)), 'dd_pipeline_stream_nms_overlap')
         if metric_kind:         # NearestNeighborDistanceMetric("euclidean", max_cosine_distance, None) for every stream's tracker
             check(lib().dd_pipeline_metric(self._h, metric_kind), 'dd_pipeline_metric')
         if association_where:   # every stream's matching cascade and assignments on the device, one wave per stream (csrc/assoc.hip)
@@ -193,9 +320,14 @@ class MultiStreamPipeline:
 
     def background_subtraction(self, ratio, masking=False):
         """deepdish.py:512,889,957: ratio = --background-subtraction-ratio (reference default 0.25); None or a negative
-        value = --disable-background-subtraction (how a pipeline starts, and how the reference's benchmarks run)."""
-        check(lib().dd_pipeline_background_subtraction(self._h, -1.0 if ratio is None else float(ratio), int(bool(masking))),
+        value = --disable-background-subtraction (how a pipeline starts, and how the reference's benchmarks run).  ratio may also be a
+        sequence of S values, each in [0, 1]: every stream's motion test then compares against its own.  Turning subtraction off for
+        some streams only is not offered: a None or negative entry inside a sequence is a ValueError.  masking is one bool."""
+        r = _stream_ratio(ratio, self.S)
+        check(lib().dd_pipeline_background_subtraction(self._h, -1.0 if r is None else float(r[0]), int(bool(masking))),
               'dd_pipeline_background_subtraction')
+        if r is not None and (r != r[0]).any():
+            check(lib().dd_pipeline_stream_motion_ratio(self._h, ptr(r)), 'dd_pipeline_stream_motion_ratio')
 
     def motion_mask(self, read=True):
         """-> (fgMask of the last step as ndarray u8 [S, H, W], boxes rejected by the motion test so far)."""
@@ -261,6 +393,48 @@ class MultiStreamPipeline:
         check(lib().dd_pipeline_step3(self._h, ptr(frames_dev), ptr(present), ptr(frames_next), ptr(present_next), ptr(b), ptr(sc), ptr(cl),
                                       ptr(off)), 'dd_pipeline_step')
 
+    def wanted_of(self, stream):
+        """Stream z's own wanted labels in its own order (self.wanted is the union over the streams, the layout of counts())."""
+        if not 0 <= int(stream) < self.S:
+            raise ValueError('stream %r of %d' % (stream, self.S))
+        return list(self.wanted if self._wanted_per is None else self._wanted_per[int(stream)])
+
+    def reset(self, streams):
+        """The listed streams start over -- what restarting the camera's process is to the reference; for a camera that was swapped or
+        reconnects after a long gap.  Between steps, at any time.  Afterwards every listed stream is in the state of a stream of a freshly
+        built pipeline with the same parameters: no tracks and ids from 1 again, its gallery back in the pool, empty paths and votes,
+        counts zero, no detections, frames_seen() 0, an overlay that reports "never stepped", the MOG2 model, its frame count and the
+        motion-mask plane as at creation, the per-stream skip counter and phase as at construction with the retained detector output
+        and encoder rows dropped.  Every other stream is untouched.  A queued look-ahead detector run is discarded: the next step runs
+        the detector itself.  An empty list does nothing; an index out of range or listed twice is a ValueError.  Not with the int form
+        of object_detector_skip_frames (one counter for all streams cannot give one stream a fresh first detector step): pass a
+        sequence."""
+        a = _reset_streams(streams, self.S)
+        if not self.skip_per_stream and self.object_detector_skip_frames is not None and int(self.object_detector_skip_frames) > 0:
+            raise ValueError('object_detector_skip_frames=%d with reset(): an int is one counter per pipeline (all streams in lock-step); '
+                             'pass a sequence, object_detector_skip_frames=[%d] * %d, for one counter per stream'
+                             % (int(self.object_detector_skip_frames), int(self.object_detector_skip_frames), self.S))
+        check(lib().dd_pipeline_reset_streams(self._h, ptr(a) if a.size else None, int(a.size)), 'dd_pipeline_reset_streams')
+
+    def stream_param_stats(self):
+        """Which kernels per-stream parameters selected: launches of the per-problem NMS variant and of the per-stream association
+        variant (both 0 while all streams share their values), reset() calls that reset a stream and the streams they reset."""
+        out = np.zeros(4, dtype=np.int64)
+        check(lib().dd_pipeline_stream_param_stats(self._h, ptr(out)), 'dd_pipeline_stream_param_stats')
+        return dict(nms_stream_launches=int(out[0]), association_stream_launches=int(out[1]), resets=int(out[2]), streams_reset=int(out[3]))
+
+    def mog2_state(self, stream):
+        """Test aid: the background model of one stream (dd_mog2_state) -> (weight [5, P], variance [5, P], mean [5, 3, P], nmodes [P])."""
+        h = P()
+        check(lib().dd_pipeline_mog2(self._h, ctypes.byref(h)), 'dd_pipeline_mog2')
+        if not h.value:
+            raise ValueError('mog2_state: background subtraction is off')
+        n = self.H * self.W
+        wt, var, mu = np.zeros((5, n), np.float32), np.zeros((5, n), np.float32), np.zeros((5, 3, n), np.float32)
+        nm = np.zeros(n, np.uint8)
+        check(lib().dd_mog2_state(h, int(stream), ptr(wt), ptr(var), ptr(mu), ptr(nm)), 'dd_mog2_state')
+        return wt, var, mu, nm
+
     def frames_seen(self):
         """int64 [S]: the number of steps each stream was present in -- every stream has its own frame number."""
         out = np.zeros(self.S, dtype=np.int64)
@@ -323,7 +497,7 @@ class MultiStreamPipeline:
 
     def overlay(self, streams=None):
         """The overlay elements of the last step (dd_pipeline_overlay) for `streams` (default: all): a list with one dict per stream --
-        line f64 [4]; track_ids int64 [t], track_labels (voted label names), track_tlbr f64 [t, 4] and path_counts int64 [t] for the
+        line f64 [4], the stream's own count line; track_ids int64 [t], track_labels (voted label names), track_tlbr f64 [t, 4] and path_counts int64 [t] for the
         confirmed tracks with time_since_update <= 1 in track order; points f64 [sum(path_counts), 2], their bottom-centre paths behind
         one another; crossings f64 [c, 4], the segments that crossed the line in this step; det_tlbr f64 [d, 4], the detections that
         went into the tracker; counts int64 [n_wanted, 4] = pos, neg, int, del."""
@@ -338,11 +512,13 @@ class MultiStreamPipeline:
         counts, line = np.zeros((n, len(self.wanted), 4), np.int64), np.zeros(4, np.float64)
         check(lib().dd_pipeline_overlay(self._h, ptr(streams), n, ptr(sizes), ptr(caps), ptr(ti), ptr(tb), ptr(pts), ptr(cr), ptr(dt), ptr(counts),
                                         ptr(line)), 'dd_pipeline_overlay')
+        lines = np.zeros((n, 4), np.float64)
+        check(lib().dd_pipeline_lines(self._h, ptr(streams), n, ptr(lines)), 'dd_pipeline_lines')
         end = np.concatenate([np.zeros((1, 4), np.int64), np.cumsum(sizes, axis=0)])
         out = []
         for i in range(n):
             (t0, p0, c0, d0), (t1, p1, c1, d1) = end[i], end[i + 1]
-            out.append(dict(line=line, track_ids=ti[t0:t1, 0], track_labels=[self.label_lines[k] if k >= 0 else '' for k in ti[t0:t1, 1]],
+            out.append(dict(line=lines[i], track_ids=ti[t0:t1, 0], track_labels=[self.label_lines[k] if k >= 0 else '' for k in ti[t0:t1, 1]],
                             track_tlbr=tb[t0:t1], path_counts=ti[t0:t1, 2], points=pts[p0:p1], crossings=cr[c0:c1], det_tlbr=dt[d0:d1],
                             counts=counts[i]))
         return out
@@ -368,9 +544,16 @@ class MultiStreamPipeline:
         if self.ground is not None:
             topdown = [(self.W / 4, self.H / 4, g, self.topdown_scale) for g in self._ground_of(streams, overlays)]
         prims = [rd.overlay_primitives(r, o['line'], o['track_ids'], o['track_labels'], o['track_tlbr'], o['points'], o['path_counts'], o['crossings'],
-                                       o['det_tlbr'], [(l, int(c[1]), int(c[0])) for l, c in zip(self.wanted, o['counts'])], annotation, topdown=t)
-                 for o, t in zip(overlays, topdown)]
+                                       o['det_tlbr'], self._counters(z, o['counts']), annotation, topdown=t)
+                 for z, o, t in zip(streams, overlays, topdown)]
         return r.draw(frames_dev, prims, streams=streams, out=out)
+
+    def _counters(self, stream, counts):
+        """(label, negcount, poscount) of the counters the reference process of this stream's camera draws (deepdish.py:1142): its own
+        wanted labels, in its own order."""
+        if self._wanted_per is None:
+            return [(l, int(c[1]), int(c[0])) for l, c in zip(self.wanted, counts)]
+        return [(l, int(counts[self.wanted.index(l)][1]), int(counts[self.wanted.index(l)][0])) for l in self._wanted_per[stream]]
 
     def _ground_of(self, streams, overlays):
         """The path points of every overlay, unprojected with their stream's camera in one call -> f64 [points, 2] per overlay."""

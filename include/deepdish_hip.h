@@ -363,6 +363,11 @@ int dd_mog2_apply_streams(dd_mog2 *m, const uint8_t *frames, const uint8_t *pres
 /* Test aid: the model of one stream as host arrays -- weight, variance f32 [5][H*W], mean f32 [5][3][H*W]
  * (zero past a pixel's mode count), nmodes u8 [H*W].  Synchronises. */
 int dd_mog2_state(dd_mog2 *m, int stream_index, float *weight_host, float *variance_host, float *mean_host, uint8_t *nmodes_host);
+/* The listed streams' subtractors start over, as cv2.createBackgroundSubtractorMOG2() (deepdish.py:889) leaves them in a restarted
+ * process: no modes at any pixel (the plane dd_mog2_create clears, cleared again on `stream`, NULL = the context's) and a frame count
+ * of 0, so the automatic learning rate 1/min(2 nframes, history) starts over too.  The other streams' models are neither read nor
+ * written.  streams_host int32 [n], each 0 .. n_streams - 1 (DD_E_ARG otherwise, before anything is queued); n = 0 does nothing. */
+int dd_mog2_reset_streams(dd_mog2 *m, const int *streams_host, int n, void *stream);
 /* np.count_nonzero(fgMask[y:y+h, x:x+w]) (deepdish.py:957) for n_boxes boxes: mask device u8
  * [n_streams][height][width]; boxes_xywh_host int32 [n_boxes][4], already clipped to the frame as
  * deepdish.py:951-952 does (anything else is DD_E_ARG); box_stream_host int32 [n_boxes]; counts_host int32
@@ -633,6 +638,51 @@ int dd_pipeline_metric(dd_pipeline *p, int metric);
 /* dd_tracker_set_association for the pipeline's tracker group (deep_sort/tracker.py:95-133, deep_sort/linear_assignment.py:11-141 decided on
  * the host, 0, the default, or on the device, 1; other values: DD_E_ARG).  Between steps. */
 int dd_pipeline_association(dd_pipeline *p, int where);
+/* Per-stream parameters.  The reference is one process per camera, and each process has its own flags (deepdish.py:1394-1460); the
+ * values dd_pipeline_create takes once hold for every stream until one of these setters gives every stream its own.  All of them: before
+ * the first step (DD_E_STATE after), arrays of n_streams entries on the host, checked as a whole before anything changes (DD_E_ARG).
+ * A pipeline whose entries are all equal launches exactly the kernels, with the arguments, of one built from the scalar.
+ *
+ * --line (deepdish.py:739-744): lines_host f64 [n_streams][4] = x1, y1, x2, y2 of each stream's count line, finite.  The crossing tests
+ * of the count-line pass (:1071-1078, :1303-1312) and of dd_pipeline_overlay use the stream's own line. */
+int dd_pipeline_stream_lines(dd_pipeline *p, const double *lines_host);
+/* The count lines of `n` streams, out_host f64 [n][4] in the order of streams_host. */
+int dd_pipeline_lines(dd_pipeline *p, const int *streams_host, int n, double *out_host);
+/* --wanted-labels (deepdish.py:460-461; the adaptors' label filter, tools/ssd_mobilenet.py:204-212, tools/yolov5.py:137-145,
+ * tools/tflite.py:26-41; the counters, deepdish.py:525-528): mask_host u8 [n_streams][n_wanted] of 0 / 1 over the wanted_nl list given to
+ * dd_pipeline_create -- stream z detects, tracks and counts label i only where mask[z][i] = 1.  A row of zeros is legal: that stream
+ * tracks and counts nothing.  The shape of dd_pipeline_counts stays [n_streams][n_wanted][4]; rows a stream does not want stay zero. */
+int dd_pipeline_stream_wanted(dd_pipeline *p, const uint8_t *mask_host);
+/* --max-cosine-distance, --max-iou-distance, --max-age (deepdish.py:516-517) and deep_sort's n_init (tracker.py:40-49) per stream's
+ * tracker; each array is NULL (unchanged) or [n_streams].  max_cos >= 0 and max_iou >= 0, finite; max_age >= 0; n_init >= 0.  The host
+ * decision reads them per tracker as it always did; decided on the device (dd_pipeline_association), a group update whose trackers do
+ * not all agree launches assoc_match_streams_k, which reads the three association values per decided stream from the staging block the
+ * update already uploads (no further copy), instead of assoc_match_k. */
+int dd_pipeline_stream_tracker_params(dd_pipeline *p, const double *max_cos_host, const double *max_iou_host, const int *max_age_host,
+                                      const int *n_init_host);
+/* --nms-max-overlap (deepdish.py:995) per stream, f64 [n_streams], finite.  While every stream of a step has at most 64 candidates and
+ * the step's streams do not all agree, the batched NMS launch is nms_small_streams_k, which reads one threshold per problem from the
+ * block the step already uploads; beyond 64 candidates the one-call-per-stream form passes that stream's value. */
+int dd_pipeline_stream_nms_overlap(dd_pipeline *p, const double *overlap_host);
+/* --background-subtraction-ratio (deepdish.py:957) per stream, f64 [n_streams], each in [0, 1]: the motion test of stream z's boxes
+ * compares against ratio[z].  Only after dd_pipeline_background_subtraction turned subtraction on (DD_E_STATE otherwise); turning it
+ * on again resets every stream to that call's ratio.  Subtraction cannot be off for some streams only. */
+int dd_pipeline_stream_motion_ratio(dd_pipeline *p, const double *ratio_host);
+/* The listed streams start over; the reference restarts the camera's process.  Between steps, at any time.  Afterwards each listed stream
+ * is in the state of a stream of a pipeline just built with the same parameters: no tracks, no deleted list, next id 1
+ * (tracker.py:40-49), its gallery chunks back in the pool; empty path store and votes (deepdish.py:519), counters zero (:525-528); no
+ * detections, frame number 0, an overlay that reports "never stepped"; MOG2 model, frame count and motion-mask plane as at creation
+ * (dd_mog2_reset_streams on the pipeline's stream); per-stream skip counter and phase as dd_pipeline_detector_skip_streams left them,
+ * the retained detector output and encoder rows dropped.  Nothing of any other stream is read or written.  A queued look-ahead detector
+ * run is discarded: the next step runs the detector itself.  streams_host int32 [n]: an index outside 0 .. n_streams - 1 or listed twice
+ * is DD_E_ARG, before anything changes; n = 0 does nothing.  With dd_pipeline_detector_skip_frames(n > 0) it is DD_E_STATE, as masks are:
+ * one counter for all streams cannot give one stream a fresh first detector step -- dd_pipeline_detector_skip_streams can. */
+int dd_pipeline_reset_streams(dd_pipeline *p, const int *streams_host, int n);
+/* out4_host = {launches of nms_small_streams_k, launches of assoc_match_streams_k, dd_pipeline_reset_streams calls that reset at least one
+ * stream, streams reset}: whether the per-stream kernel variants ran. */
+int dd_pipeline_stream_param_stats(dd_pipeline *p, long long *out4_host);
+/* The pipeline's background subtractor (NULL while subtraction is off), for dd_mog2_state; it is the pipeline's: do not apply or destroy. */
+int dd_pipeline_mog2(dd_pipeline *p, dd_mog2 **out);
 /* frames: device u8 [n_streams][H][W][3] BGR.  inj_*: optional detections that REPLACE the detector's
  * output (it still runs): tlwh f64 rows, scores, class ids; stream s owns rows
  * [inj_offsets[s], inj_offsets[s+1]).  Blocks until the step is complete. */
@@ -703,7 +753,8 @@ int dd_pipeline_detections(dd_pipeline *p, int stream, double *boxes_host, doubl
  * of each kind in all (DD_E_CAPACITY otherwise): track_ints int64 rows {track id, line of the label file that holds the voted label or
  * -1, points of its path}; track_tlbr f64 [tracks][4] (to_tlbr()); points f64 [points][2], the bottom-centre path of each track in turn;
  * cross f64 [crossings][4], the last two path points of a track that crossed the line in this step; det_tlbr f64 [detections][4];
- * counts int64 [n][n_wanted][4] as dd_pipeline_counts; line f64 [4].  Host work only; between steps. */
+ * counts int64 [n][n_wanted][4] as dd_pipeline_counts; line f64 [4], the count line of stream streams_host[0] (with per-stream lines,
+ * dd_pipeline_lines has the others).  Host work only; between steps. */
 int dd_pipeline_overlay(dd_pipeline *p, const int *streams_host, int n, int *sizes_host, const int *caps_host, int64_t *track_ints_host,
                         double *track_tlbr_host, double *points_host, double *cross_host, double *det_tlbr_host, int64_t *counts_host,
                         double *line_host);
