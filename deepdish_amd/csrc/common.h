@@ -177,6 +177,50 @@ size_t ssd_post_scratch_bytes(int n_anchors, int batch);
 int ssd_postprocess(hipStream_t s, const float *raw, const float *anchors, int n_anchors, int n_classes, int max_det,
                     float score_thr, float iou_thr, float *boxes, float *classes, float *scores, int *count, int batch,
                     void *scratch, size_t scratch_bytes);
+size_t ssd_post_decoded_scratch_bytes(int n_anchors, int batch);
+int ssd_postprocess_decoded(hipStream_t s, const float *d_boxes, const float *d_score, const int *d_cls, const float *d_keys,
+                            int n_anchors, int max_det, float score_thr, float iou_thr, float *boxes, float *classes, float *scores,
+                            int *count, int batch, void *scratch, size_t scratch_bytes);
+int ssd_regular_nms_raw(hipStream_t s, const float *raw, const float *anchors, int n_anchors, int n_classes, int max_det, int per_class,
+                        float score_thr, float iou_thr, float *boxes, float *classes, float *scores, int *count, int batch);
+int ssd_regular_nms_u8(hipStream_t s, const uint8_t *box_q, const uint8_t *cls_q, int cls_stride, const uint8_t *lut, const float *quant4,
+                       const float *anchors, int n_anchors, int n_classes, int max_det, int per_class, float score_thr, float iou_thr,
+                       float *boxes, float *classes, float *scores, int *count, int batch);
+int ssd_finish(hipStream_t s, const float *boxes, const float *cls, const float *scores, int batch, int max_det, double conf,
+               double iou_thr, double img_w, double img_h, double *out_boxes, int *out_cls, double *out_scores, int *out_n);
+// YOLOv5 (post.hip): rows over the threshold per image, from the raw head or from the Detect layers' decoded rows; stretch or letterbox
+int yolov5_decode(hipStream_t s, const float *raw, int n_rows, int n_cls, float thr, float img_w, float img_h, float *out_boxes,
+                  float *out_scores, int *out_cls, int cap, int *out_n, int batch, void *scratch);
+int yolov5_select(hipStream_t s, const float *boxes4, const float *conf, const int *cls, int n_rows, float thr, float img_w, float img_h,
+                  float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch);
+int yolov5_decode_letterbox(hipStream_t s, const float *raw, int n_rows, int n_cls, float thr, int img_w, int img_h, int net_w, int net_h,
+                            float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch, void *scratch);
+int yolov5_select_letterbox(hipStream_t s, const float *boxes4, const float *conf, const int *cls, int n_rows, float thr, int img_w, int img_h,
+                            int net_w, int net_h, float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch);
+int yolov5_pack(hipStream_t s, const float *boxes, const float *scores, const int *cls, const int *n_rows, int cap, int batch, float *packed);
+int resize_lanczos_letterbox(hipStream_t s, int device, const uint8_t *src, int batch, int H, int W, int src_c, int swap_rb, uint8_t *dst, int h, int w,
+                             int pad, uint8_t *tmp);
+// what the batched pipeline launches on streams of its own: retained feature rows (featrows.hip), frame compaction (gather.hip), MOG2 (mog2.hip)
+int feature_rows_carry(hipStream_t s, const float *fresh, const float *store, float *out, float *store_new, const int *d_table, int n_entries);
+int gather_frames(hipStream_t s, const uint8_t *src, long long frame_bytes, const int *d_idx, int n, uint8_t *dst);
+int mog2_apply_streams(dd_mog2 *m, hipStream_t s, const uint8_t *frames, const uint8_t *present_host, double learning_rate, uint8_t *mask,
+                       uint8_t *masked);
+int mog2_reset_streams(dd_mog2 *m, hipStream_t s, const int *streams_host, int n);
+int mask_box_count(hipStream_t s, const uint8_t *mask, int H, int W, const int *d_boxes, const int *d_box_stream, int K, int *d_counts);
+// a group of trackers sharing one pool (tracker.hip): every stream's tracker of a pipeline, stepped together in three phases
+int tracker_group_create(dd_ctx *ctx, int n, double max_cos, double max_iou, int max_age, int n_init, int budget, int tcap,
+                         int gcap, dd_tracker **out);
+int tracker_group_set_metric(dd_tracker *any, int metric);
+int tracker_group_set_association(dd_tracker *any, int where);
+long long tracker_group_stream_param_launches(const dd_tracker *any);
+int tracker_set_params(dd_tracker *t, const double *max_cos, const double *max_iou, const int *max_age, const int *n_init);
+int tracker_reset(dd_tracker *t);
+int trackers_predict(dd_tracker **ts, int S);
+int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const float *feats, int feats_on_device,
+                          const int *det_off);
+int trackers_update_match(dd_tracker **ts, int S);
+int trackers_update_end(dd_tracker **ts, int S);
+int tracker_read_host(dd_tracker *t, int which, int64_t *ints6_host, double *means_host);
 void pyset_difference_order(const std::vector<int> &a, const std::vector<int> &b, std::vector<int> &out);
 int lsap(const double *cost, int nr, int nc, int *rows, int *cols);   // host; returns pair count or -1
 int gather_state(hipStream_t s, const double *means, const double *covs, const int *slots, int n,

@@ -48,7 +48,9 @@ __global__ __launch_bounds__(256) void feature_rows_carry_k(const uint4 *__restr
 
 namespace ddk {
 
-// d_table: device, n_entries x 8 ints as above, every range checked by the caller; entries with no rows are not in it.
+// d_table: device, n_entries x 8 ints as above; entries with no rows are not in it.  No range is checked here or by the kernel: the
+// pipeline's tables come from ddhost::feature_row_table (host_phases.h), whose every range the sanitizer harness holds to its buffer
+// (tests/sanitize/host_harness.cpp); dd_feature_rows_carry below checks a caller's own table.
 int feature_rows_carry(hipStream_t s, const float *fresh, const float *store, float *out, float *store_new, const int *d_table, int n_entries) {
     if (n_entries <= 0) return DD_OK;
     hipLaunchKernelGGL(feature_rows_carry_k, dim3((unsigned)n_entries), dim3(256), 0, s, reinterpret_cast<const uint4 *>(fresh),

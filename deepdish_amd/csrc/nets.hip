@@ -4375,7 +4375,6 @@ extern "C" {
 // n_ops * 48 words.  See deepdish_amd/nets.py (Program.serialize) for the field order.
 static int net_create(dd_ctx *ctx, const int32_t *program_host, int n_words, const void *weights_host,
                       int64_t n_weight_bytes, int max_batch, dd_net **out, bool share);
-int dd_net_destroy(dd_net *n);
 
 int dd_net_create(dd_ctx *ctx, const int32_t *program_host, int n_words, const void *weights_host,
                   int64_t n_weight_bytes, int max_batch, dd_net **out) {

@@ -16,60 +16,6 @@
 #include "hostpool.h"
 #include "host_phases.h"
 
-struct dd_tracker;
-struct dd_mog2;
-namespace ddk {
-int feature_rows_carry(hipStream_t s, const float *fresh, const float *store, float *out, float *store_new, const int *d_table, int n_entries);
-int mog2_apply_streams(dd_mog2 *m, hipStream_t s, const uint8_t *frames, const uint8_t *present_host, double learning_rate, uint8_t *mask,
-                       uint8_t *masked);
-int gather_frames(hipStream_t s, const uint8_t *src, long long frame_bytes, const int *d_idx, int n, uint8_t *dst);
-int mask_box_count(hipStream_t s, const uint8_t *mask, int H, int W, const int *d_boxes, const int *d_box_stream, int K, int *d_counts);
-int yolov5_decode(hipStream_t s, const float *raw, int n_rows, int n_cls, float thr, float img_w, float img_h, float *out_boxes,
-                  float *out_scores, int *out_cls, int cap, int *out_n, int batch, void *scratch);
-int yolov5_select(hipStream_t s, const float *boxes4, const float *conf, const int *cls, int n_rows, float thr, float img_w, float img_h,
-                  float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch);
-int yolov5_decode_letterbox(hipStream_t s, const float *raw, int n_rows, int n_cls, float thr, int img_w, int img_h, int net_w, int net_h,
-                            float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch, void *scratch);
-int yolov5_select_letterbox(hipStream_t s, const float *boxes4, const float *conf, const int *cls, int n_rows, float thr, int img_w, int img_h,
-                            int net_w, int net_h, float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch);
-int resize_lanczos_letterbox(hipStream_t s, int device, const uint8_t *src, int batch, int H, int W, int src_c, int swap_rb, uint8_t *dst, int h, int w,
-                             int pad, uint8_t *tmp);
-size_t ssd_post_decoded_scratch_bytes(int n_anchors, int batch);
-int ssd_postprocess_decoded(hipStream_t s, const float *d_boxes, const float *d_score, const int *d_cls, const float *d_keys,
-                            int n_anchors, int max_det, float score_thr, float iou_thr, float *boxes, float *classes, float *scores,
-                            int *count, int batch, void *scratch, size_t scratch_bytes);
-int yolov5_pack(hipStream_t s, const float *boxes, const float *scores, const int *cls, const int *n_rows, int cap, int batch, float *packed);
-int ssd_regular_nms_raw(hipStream_t s, const float *raw, const float *anchors, int n_anchors, int n_classes, int max_det, int per_class,
-                        float score_thr, float iou_thr, float *boxes, float *classes, float *scores, int *count, int batch);
-int ssd_regular_nms_u8(hipStream_t s, const uint8_t *box_q, const uint8_t *cls_q, int cls_stride, const uint8_t *lut, const float *quant4,
-                       const float *anchors, int n_anchors, int n_classes, int max_det, int per_class, float score_thr, float iou_thr,
-                       float *boxes, float *classes, float *scores, int *count, int batch);
-int ssd_finish(hipStream_t s, const float *boxes, const float *cls, const float *scores, int batch, int max_det, double conf,
-               double iou_thr, double img_w, double img_h, double *out_boxes, int *out_cls, double *out_scores, int *out_n);
-int tracker_group_create(dd_ctx *ctx, int n, double max_cos, double max_iou, int max_age, int n_init, int budget, int tcap,
-                         int gcap, dd_tracker **out);
-int tracker_group_set_metric(dd_tracker *any, int metric);
-int tracker_set_params(dd_tracker *t, const double *max_cos, const double *max_iou, const int *max_age, const int *n_init);
-int tracker_reset(dd_tracker *t);
-long long tracker_group_stream_param_launches(const dd_tracker *any);
-int mog2_reset_streams(dd_mog2 *m, hipStream_t s, const int *streams_host, int n);
-int tracker_group_set_association(dd_tracker *any, int where);
-int trackers_predict(dd_tracker **ts, int S);
-int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const float *feats, int feats_on_device,
-                          const int *det_off);
-int trackers_update_match(dd_tracker **ts, int S);
-int trackers_update_end(dd_tracker **ts, int S);
-int tracker_read_host(dd_tracker *t, int which, int64_t *ints6_host, double *means_host);
-}
-extern "C" int dd_net_max_batch(dd_net *net, int *out_host);
-extern "C" int dd_net_ssd_decode(dd_net *net, const float *anchors_host, int n_anchors, float score_thr, int enable);
-extern "C" int dd_net_ssd_decoded(dd_net *net, float **boxes, float **scores, int **classes, float **keys);
-extern "C" int dd_net_ssd_heads_u8(dd_net *net, const uint8_t **box_q, const uint8_t **cls_q, int *cls_stride, const uint8_t **lut, float *quant4_host,
-                                   int *n_anchors, int *n_classes);
-extern "C" int dd_net_yolo_decode(dd_net *net, int enable);
-extern "C" int dd_net_yolo_decoded(dd_net *net, float **boxes, float **conf, int **classes, int *rows);
-extern "C" int dd_net_input_size(dd_net *net, int *h_host, int *w_host);
-
 namespace {
 
 constexpr int MAX_DET_DEFAULT = 10, MAX_DET_CAP = 64;          // max_detections of the stock SSD post-process op; what csrc/post.hip takes
@@ -77,6 +23,59 @@ constexpr float SSD_SCORE_THR = 1e-8f, SSD_IOU_THR = 0.6f;    // its score / NMS
 constexpr int YOLO_HOST_ROWS = 128;      // YOLOv5 rows per stream the first device-to-host copy of a step has room for (the rest, if any, follows)
 enum { DET_SSD = 0, DET_YOLOV5 = 1, DET_TFLITE = 2 };
 enum { CONFIRMED = 2, DELETED = 3 };
+constexpr int GRAIN = 16;                // host phases: one parallel_for over the streams each -- they share nothing (hostpool.h)
+
+// The blocks a detector run fills and the step consumes, one description each: at(base, n, max_det) = the typed pointers into a block
+// of n images (on the device or in its pinned host copy), bytes(n, max_det) = what it takes.  enqueue_detector writes them and sizes its
+// copy to the host by them, the step's adaptor tails read them, dd_pipeline_create reserves them.
+// TFLite_Detection_PostProcess's output, which the generic TFLite adaptor takes as it is: per image max_det boxes f32 x4 (ymin, xmin,
+// ymax, xmax, normalised), classes f32, scores f32; then a count per image
+struct TfliteBlock {
+    float *boxes, *classes, *scores;
+    int *count;
+    static TfliteBlock at(void *base, size_t n, size_t max_det) {
+        float *b = static_cast<float *>(base), *s = b + n * max_det * 5;
+        return {b, b + n * max_det * 4, s, reinterpret_cast<int *>(s + n * max_det)};
+    }
+    static size_t bytes(size_t n, size_t max_det) { return n * max_det * 6 * sizeof(float) + n * sizeof(int); }
+};
+// the SSD adaptor's tail (ssd_finish, tools/ssd_mobilenet.py:111-150): per image max_det boxes f64 x4 (tlbr, pixels), scores f64, class
+// i32; then a count per image
+struct SsdBlock {
+    double *boxes, *scores;
+    int *cls, *count;
+    static SsdBlock at(void *base, size_t n, size_t max_det) {
+        double *b = static_cast<double *>(base), *s = b + n * max_det * 4;
+        int *c = reinterpret_cast<int *>(s + n * max_det);
+        return {b, s, c, c + n * max_det};
+    }
+    static size_t bytes(size_t n, size_t max_det) { return n * (max_det * (4 * 8 + 8 + 4) + 4); }
+};
+// YOLOv5 on the device: every row of the head may pass the threshold (yolov5.py:120-145 has no limit), so max_det is the head's row
+// count -- per image max_det boxes f32 x4, scores f32, classes i32; then a count per image
+struct YoloBlock {
+    float *boxes, *scores;
+    int *cls, *count;
+    static YoloBlock at(void *base, size_t n, size_t max_det) {
+        float *b = static_cast<float *>(base), *s = b + n * max_det * 4;
+        int *c = reinterpret_cast<int *>(s + n * max_det);
+        return {b, s, c, c + n * max_det};
+    }
+    static size_t bytes(size_t n, size_t max_det) { return n * (max_det * 24 + 4); }
+};
+// YOLOv5 on the host: [n counts | pad to 64 B | rows x 24 B], the passing rows of all images packed behind one another (yolov5_pack: box
+// f32 x4, score f32, class i32).  max_det = the packed rows the block has room for, over all images.  bytes() is counts + rows: the pad is
+// less than the 64 B of slack its reservation adds.
+struct YoloHostBlock {
+    static constexpr size_t ROW = 24;
+    int *count;
+    float *rows;
+    static size_t head(size_t n) { return (n * 4 + 63) / 64 * 64; }
+    static YoloHostBlock at(void *base, size_t n, size_t /*max_det*/) {
+        return {static_cast<int *>(base), reinterpret_cast<float *>(static_cast<char *>(base) + head(n))};
+    }
+    static size_t bytes(size_t n, size_t max_det) { return n * 4 + max_det * ROW; }
+};
 
 struct Votes {                         // track.py:78-81,147-151: label -> confidences, in first-seen order
     std::vector<int> cls;
@@ -105,10 +104,18 @@ struct StreamState {
     std::vector<double> means;
     std::vector<double> det_tlwh;                                    // the rows that went into the tracker in this stream's last step (overlay)
     long long seen = 0;                                              // steps this stream was present in: its own frame number
+    // the stream starts over (dd_pipeline_reset_streams): as a new StreamState has it, but for its tracker handle, reset in place
+    void restart(size_t n_wanted) {
+        dd_tracker *keep_trk = trk;
+        *this = StreamState();
+        trk = keep_trk;
+        counts.assign(n_wanted * 4, 0);
+    }
 };
 
 using ddhost::cross2;
 using ddhost::seg_intersect;
+using ddhost::StepPlan;
 
 }  // namespace
 
@@ -169,33 +176,30 @@ struct dd_pipeline {
     DevBuf d_mask, d_masked, d_mbox;
     PinBuf h_mbox;
     long long motion_rejected = 0;
-    std::vector<int> off, doff;                // per-step prefix sums (candidates, kept detections) over the streams
+    std::vector<int> off, doff, eoff;          // per-step prefix sums over the positions of act: candidates, tracker input rows, encoder rows
     std::vector<double> tlwh;
-    // --object-detector-skip-frames (deepdish.py:892-893,929-938,1003-1014; dd_pipeline_detector_skip_frames): a skip step reuses the
-    // last detector step's adaptor output (StreamState::boxes0/scores0/cls0) and its feature rows (d_feats, per-stream offsets foff)
-    int skip_n = 0;                            // N; <= 0 = every step a detector step
-    int skip_rem = 0;                          // skip steps left before the next detector step (the reference's skip_rem)
+    // --object-detector-skip-frames (deepdish.py:892-893,929-938,1003-1014): one set of counters (host_phases.h) drives both forms.  On
+    // a skip step a stream keeps the adaptor output of its last detector step (StreamState::boxes0/scores0/cls0) and pairs its boxes with
+    // the feature rows of its last encoder run.  Where those rows are kept is what differs:
+    //  * dd_pipeline_detector_skip_frames (skip_lockstep; also a pipeline without the option): all streams step together, so the rows
+    //    simply stay in d_feats, per-stream offsets foff, and a skip step gathers them with skip_gather_rows_k.  No store.
+    //  * dd_pipeline_detector_skip_streams (skip_streams): d_feats is overwritten by the next encoder run of ANY stream, so every stream's
+    //    rows are kept in a store of their own (csrc/featrows.hip), compact in stream order and double-buffered: a step that ran the
+    //    encoder writes the other buffer (fresh rows replace, everything else is carried) in the launch that assembles the tracker's input.
+    ddhost::SkipCounters sk;
+    bool skip_lockstep = false, skip_streams = false;
     std::vector<int> foff;                     // row offsets of the last encoder run's features in d_feats, [S + 1]
     DevBuf d_feats_skip, d_gather;             // a skip step's tracker input rows; their per-stream offsets on the device
     PinBuf h_gather;
-    hipEvent_t skip_mark = nullptr;            // a skip step's main stream waits here for what the detector stream holds at step entry
-    // One skip counter per stream (dd_pipeline_detector_skip_streams): a step is a detector step for some of its streams (det_list) and a
-    // skip step for the others.  Every stream's last encoder rows are kept in a store of their own (csrc/featrows.hip): d_feats is
-    // overwritten by the next encoder run of ANY stream.  The store is compact in stream order and double-buffered: a step that ran the
-    // encoder writes the other buffer (fresh rows replace, everything else is carried) in the launch that assembles the tracker's input.
-    bool skip_streams = false, last_skip = false;
-    std::vector<int> sk_n, sk_phase, sk_rem, sk_rem_next;      // N[z]; phase[z] (-1: none); skip steps left; the counters after this step
-    std::vector<uint8_t> sk_has, sk_has_next, sk_last;         // stream has a detector result (now, after this step); its last step was a skip step
-    std::vector<uint8_t> skp;                                  // per POSITION in act: this step is a skip step for that stream
-    std::vector<int> det_list, det_next, eoff;                 // this step's detector streams, the next step's; prefix sums of their kept boxes
-    std::vector<int> ret_off, ret_n, ret_off_new;              // rows [ret_off[z], + ret_n[z]) of the current store are stream z's
+    hipEvent_t skip_mark = nullptr;            // a step without a detector run: its main stream waits here for what the detector stream holds at step entry
+    std::vector<int> ret_off, ret_n, ret_off_new, ret_n_new;   // rows [ret_off[z], + ret_n[z]) of the current store are stream z's; the next store's
     DevBuf d_store[2];
     int store_cur = 0;
     long long det_stream_steps = 0, skip_stream_steps = 0, carry_launches = 0, rows_retained = 0;      // dd_pipeline_skip_stats
-    // Presence masks (dd_pipeline_step3): a step advances the streams of `act` only -- all S of them without a mask.  Every per-step
-    // array of the step (detector output blocks, off, doff, tlwh, the tracker pointer list) is indexed by POSITION in act.
-    std::vector<int> act, act_next, det_pending_act;     // this step's streams, the look-ahead's, those of the queued detector run
-    std::vector<dd_tracker *> atrks;           // trks of act
+    // Presence masks (dd_pipeline_step3): a step advances the streams of plan.act only -- all S of them without a mask.
+    ddhost::StepPlan plan;
+    std::vector<int> det_pending_act;          // the streams of the queued detector run
+    std::vector<dd_tracker *> atrks;           // trks of plan.act
     DevBuf d_gframes;                          // the detector's input frames compacted (frames_gather_k): S * H * W * 3 bytes, allocated by the
                                                // first masked step that needs them
     // index lists for kernels on the detector stream (frames_gather_k's list, the generic adaptor's box table): a ring of pinned / device
@@ -210,7 +214,21 @@ struct dd_pipeline {
 };
 
 namespace {
-int flush_stage_events(dd_pipeline *p);
+// Stage events of the previous step -> the accumulated GPU milliseconds (they completed long ago unless the caller asks right after a step).
+int flush_stage_events(dd_pipeline *p) {
+    if (!p->ev_pending) return DD_OK;
+    p->ev_pending = false;
+    double *into[6] = {&p->g_trk, &p->g_nms, &p->g_enc, &p->g_trk, &p->g_trk, &p->g_trk};
+    for (int k = 0; k < 6; ++k) {
+        if (!p->ev_pair[k]) continue;
+        p->ev_pair[k] = false;
+        float ms = 0.f;
+        DD_HIP(hipEventSynchronize(p->ev_main[2 * k + 1]));
+        DD_HIP(hipEventElapsedTime(&ms, p->ev_main[2 * k], p->ev_main[2 * k + 1]));
+        *into[k] += (double)ms;
+    }
+    return DD_OK;
+}
 
 // n_ints <= 8 S ints from the host to the device in the order of stream s -> where they will be.  `host` is free when this returns.
 int stage_list(dd_pipeline *p, hipStream_t s, const int *host, size_t n_ints, const int **dev) {
@@ -238,6 +256,12 @@ int present_list(const dd_pipeline *p, const uint8_t *present_host, const char *
     act.clear();
     for (int z = 0; z < p->S; ++z) if (!present_host || present_host[z]) act.push_back(z);
     return DD_OK;
+}
+
+// One whole-frame CropBox per listed stream (the generic adaptor's bilinear stretch, BGR -> RGB): streams == NULL = 0 .. n - 1
+void whole_frame_boxes(const dd_pipeline *p, const int *streams, int n, std::vector<int> &hb) {
+    hb.assign((size_t)n * 8, 0);
+    for (int i = 0; i < n; ++i) { int *b = hb.data() + (size_t)i * 8; b[2] = p->W; b[3] = p->H; b[4] = streams ? streams[i] : i; b[6] = 1; }   // whole frame, swap_rb
 }
 
 // index of `name` in the wanted list if stream z wants it, else -1
@@ -275,17 +299,9 @@ double now_s() {
 
 }  // namespace
 
-extern "C" {
+#define DD_BEFORE_FIRST_STEP(name) DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, name ": call before the first step")
 
-int dd_tracker_create(dd_ctx *, double, double, int, int, int, int, int, dd_tracker **);
-int dd_tracker_destroy(dd_tracker *);
-int dd_tracker_count(dd_tracker *, int, int *);
-int dd_tracker_read(dd_tracker *, int, int64_t *, double *, double *);
-int dd_net_forward(dd_net *, const uint8_t *, int, void *);
-int dd_net_output(dd_net *, int, void **, int *, int *, int *, int *, int *);
-int dd_net_read(dd_net *, int, int, void *, int, void *);
-int dd_mog2_create(dd_ctx *, int, int, int, int, double, int, dd_mog2 **);
-int dd_mog2_destroy(dd_mog2 *);
+extern "C" {
 
 int dd_pipeline_create(dd_ctx *ctx, int n_streams, int frame_h, int frame_w, dd_net *detector,
                        const float *anchors_host, int n_anchors, int n_classes, dd_net *encoder,
@@ -338,9 +354,9 @@ int dd_pipeline_create(dd_ctx *ctx, int n_streams, int frame_h, int frame_w, dd_
             p->ssd_dec = !(e && atoi(e) == 0);
             if (p->ssd_dec && (rc = dd_net_ssd_decode(detector, anchors_host, n_anchors, SSD_SCORE_THR, 1)) != DD_OK) return rc;
             // sized for the largest max_detections the post-process kernels take: dd_pipeline_ssd_options may raise it before the first step
-            if ((rc = p->d_det.reserve(S * MAX_DET_CAP * 6 * sizeof(float) + S * sizeof(int) + 256)) != DD_OK) return rc;
-            if ((rc = p->d_fin.reserve(S * (MAX_DET_CAP * (4 * 8 + 4 + 8) + 4) + 256)) != DD_OK) return rc;
-            if ((rc = p->h_fin.reserve(S * (MAX_DET_CAP * (4 * 8 + 4 + 8) + 4) + 256)) != DD_OK) return rc;
+            if ((rc = p->d_det.reserve(TfliteBlock::bytes(S, MAX_DET_CAP) + 256)) != DD_OK) return rc;
+            if ((rc = p->d_fin.reserve(SsdBlock::bytes(S, MAX_DET_CAP) + 256)) != DD_OK) return rc;
+            if ((rc = p->h_fin.reserve(SsdBlock::bytes(S, MAX_DET_CAP) + 256)) != DD_OK) return rc;
         } else {
             if ((rc = p->d_post.reserve(S * n_anchors * 8 + 256)) != DD_OK) return rc;              // per-row confidence + class
             // yolov5.py:126-128 (cls *= obj, argmax, confidence) runs in the Detect layers' epilogues when the program carries their
@@ -349,13 +365,11 @@ int dd_pipeline_create(dd_ctx *ctx, int n_streams, int frame_h, int frame_w, dd_
                 const char *e = getenv("DD_YOLO_DEC");
                 p->yolo_dec = !(e && atoi(e) == 0) && dd_net_yolo_decode(detector, 1) == DD_OK;
             }
-            // every row of the head may pass the threshold: yolov5.py:120-145 has no limit, so neither has this (device: per image
-            // n_anchors rows of boxes f32x4, score, class + a count; then the same rows packed over the images)
-            const size_t fin = S * ((size_t)n_anchors * 24 + 4) + 256;
-            if ((rc = p->d_fin.reserve(fin)) != DD_OK) return rc;
-            if ((rc = p->d_pack.reserve(S * (size_t)n_anchors * 24 + 256)) != DD_OK) return rc;
+            // every row of the head may pass the threshold: then the same rows packed over the images
+            if ((rc = p->d_fin.reserve(YoloBlock::bytes(S, n_anchors) + 256)) != DD_OK) return rc;
+            if ((rc = p->d_pack.reserve(S * (size_t)n_anchors * YoloHostBlock::ROW + 256)) != DD_OK) return rc;
             p->yolo_host_rows = (size_t)S * YOLO_HOST_ROWS;
-            if ((rc = p->h_fin.reserve(S * 4 + 64 + p->yolo_host_rows * 24)) != DD_OK) return rc;
+            if ((rc = p->h_fin.reserve(YoloHostBlock::bytes(S, p->yolo_host_rows) + 64)) != DD_OK) return rc;
         }
     }
     // late look-ahead (dd_pipeline_step2) when a step's kernels fill the GPU; with a handful of streams they do not, and the detector of
@@ -364,6 +378,7 @@ int dd_pipeline_create(dd_ctx *ctx, int n_streams, int frame_h, int frame_w, dd_
     p->st.resize(n_streams);
     p->trks.resize(n_streams);
     p->foff.assign(n_streams + 1, 0);
+    p->sk.start(n_streams, 0);
     if ((rc = ddk::tracker_group_create(ctx, n_streams, max_cosine_distance, max_iou_distance, max_age, n_init, 0,
                                         track_capacity, gallery_capacity, p->trks.data())) != DD_OK) return rc;
     for (int z = 0; z < n_streams; ++z) {
@@ -404,7 +419,7 @@ int dd_pipeline_ssd_options(dd_pipeline *p, int max_detections, float nms_score_
     DD_REQUIRE(p && p->det && p->det_kind != DET_YOLOV5, DD_E_ARG, "dd_pipeline_ssd_options: needs a pipeline with an SSD-type detector");
     DD_REQUIRE(max_detections >= 1 && max_detections <= MAX_DET_CAP && nms_iou_threshold > 0.f && nms_iou_threshold <= 1.f, DD_E_ARG,
                "dd_pipeline_ssd_options: max_detections %d (1 .. %d), nms_iou_threshold %g (0 < t <= 1)", max_detections, MAX_DET_CAP, (double)nms_iou_threshold);
-    DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, "dd_pipeline_ssd_options: call before the first step");
+    DD_BEFORE_FIRST_STEP("dd_pipeline_ssd_options");
     DD_DEVICE(p->ctx);
     if (p->ssd_dec && nms_score_threshold != p->ssd_score_thr) {   // the head layers' decode epilogue carries the score threshold
         std::vector<float> anchors((size_t)p->n_anchors * 4);
@@ -419,7 +434,7 @@ int dd_pipeline_ssd_options(dd_pipeline *p, int max_detections, float nms_score_
 int dd_pipeline_ssd_regular_nms(dd_pipeline *p, int detections_per_class) {
     DD_REQUIRE(p && p->det && p->det_kind != DET_YOLOV5, DD_E_ARG, "dd_pipeline_ssd_regular_nms: needs a pipeline with an SSD-type detector");
     DD_REQUIRE(detections_per_class >= 1, DD_E_ARG, "dd_pipeline_ssd_regular_nms: detections_per_class %d (>= 1)", detections_per_class);
-    DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, "dd_pipeline_ssd_regular_nms: call before the first step");
+    DD_BEFORE_FIRST_STEP("dd_pipeline_ssd_regular_nms");
     DD_DEVICE(p->ctx);
     int rc, dtype = 0;
     if ((rc = dd_net_output(p->det, -1, nullptr, nullptr, nullptr, nullptr, nullptr, &dtype)) != DD_OK) return rc;
@@ -440,14 +455,14 @@ int dd_pipeline_ssd_regular_nms(dd_pipeline *p, int detections_per_class) {
 int dd_pipeline_detector_adaptor(dd_pipeline *p, int adaptor) {
     DD_REQUIRE(p && p->det && p->det_kind != DET_YOLOV5 && (adaptor == DET_SSD || adaptor == DET_TFLITE), DD_E_ARG,
                "dd_pipeline_detector_adaptor: needs a pipeline with an SSD-type detector; adaptor 0 (ssd_mobilenet) or 2 (tflite)");
-    DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, "dd_pipeline_detector_adaptor: call before the first step");
+    DD_BEFORE_FIRST_STEP("dd_pipeline_detector_adaptor");
     DD_DEVICE(p->ctx);
     p->det_kind = adaptor;
     if (adaptor == DET_TFLITE) {
         p->tfl_labels.clear();
         for (size_t i = 1; i < p->labels.size(); ++i) if (!p->labels[i].empty()) p->tfl_labels.push_back(p->labels[i]);
-        std::vector<int> hb((size_t)p->S * 8, 0);
-        for (int z = 0; z < p->S; ++z) { int *b = hb.data() + (size_t)z * 8; b[2] = p->W; b[3] = p->H; b[4] = z; b[6] = 1; }   // whole frame, swap_rb
+        std::vector<int> hb;
+        whole_frame_boxes(p, nullptr, p->S, hb);
         int rc;
         if ((rc = p->d_tfl_boxes.reserve(hb.size() * sizeof(int))) != DD_OK) return rc;
         DD_HIP(hipMemcpy(p->d_tfl_boxes.p, hb.data(), hb.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -463,15 +478,16 @@ int dd_pipeline_detector_adaptor(dd_pipeline *p, int adaptor) {
 // that step's feature rows as zip() does: the first min(kept boxes now, feature rows then) of each.  Call before the first step.
 int dd_pipeline_detector_skip_frames(dd_pipeline *p, int n) {
     DD_REQUIRE(p, DD_E_ARG, "dd_pipeline_detector_skip_frames: NULL pipeline");
-    DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, "dd_pipeline_detector_skip_frames: call before the first step");
+    DD_BEFORE_FIRST_STEP("dd_pipeline_detector_skip_frames");
     DD_REQUIRE(!p->skip_streams || n <= 0, DD_E_STATE,
                "dd_pipeline_detector_skip_frames: the pipeline has per-stream counters (dd_pipeline_detector_skip_streams); one form per pipeline");
-    p->skip_n = n;
-    p->skip_rem = 0;
+    if (p->skip_streams) return DD_OK;         // n <= 0 beside per-stream counters: nothing to turn off
+    p->skip_lockstep = n > 0;
+    p->sk.start(p->S, std::max(n, 0));          // the same N for every stream, no phase
     return DD_OK;
 }
 
-// The same option with one counter per stream -- what the reference, one process per camera, has (its skip_rem is per camera).  n_host[z]
+// The same option with one counter per stream -- what the reference, one process per camera, has (its counter is per camera).  n_host[z]
 // >= 0 is stream z's N; on a step in which z is present: rem[z] > 0 and z has a detector result -> a skip step for z, rem[z] -= 1;
 // otherwise a detector step for z, then rem[z] = N[z].  A step without z moves nothing of z, its counter included.  phase_host (NULL:
 // none; this build's addition, the reference has no such option) shortens the FIRST cycle only: after z's first detector step rem[z] =
@@ -482,8 +498,8 @@ int dd_pipeline_detector_skip_frames(dd_pipeline *p, int n) {
 // Presence masks are allowed in this form.  Call before the first step; not together with dd_pipeline_detector_skip_frames(n > 0).
 int dd_pipeline_detector_skip_streams(dd_pipeline *p, const int *n_host, const int *phase_host) {
     DD_REQUIRE(p && n_host, DD_E_ARG, "dd_pipeline_detector_skip_streams: NULL argument");
-    DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, "dd_pipeline_detector_skip_streams: call before the first step");
-    DD_REQUIRE(p->skip_n <= 0, DD_E_STATE,
+    DD_BEFORE_FIRST_STEP("dd_pipeline_detector_skip_streams");
+    DD_REQUIRE(!p->skip_lockstep, DD_E_STATE,
                "dd_pipeline_detector_skip_streams: the pipeline has the pipeline-wide counter (dd_pipeline_detector_skip_frames); one form per pipeline");
     for (int z = 0; z < p->S; ++z) {
         DD_REQUIRE(n_host[z] >= 0, DD_E_ARG, "dd_pipeline_detector_skip_streams: n[%d] = %d (>= 0)", z, n_host[z]);
@@ -492,11 +508,10 @@ int dd_pipeline_detector_skip_streams(dd_pipeline *p, const int *n_host, const i
     }
     const size_t S = p->S;
     p->skip_streams = true;
-    p->sk_n.assign(n_host, n_host + S);
-    if (phase_host) p->sk_phase.assign(phase_host, phase_host + S); else p->sk_phase.assign(S, -1);
-    p->sk_rem.assign(S, 0); p->sk_rem_next.assign(S, 0);
-    p->sk_has.assign(S, 0); p->sk_has_next.assign(S, 0); p->sk_last.assign(S, 0);
-    p->ret_off.assign(S, 0); p->ret_n.assign(S, 0); p->ret_off_new.assign(S, 0);
+    p->sk.start(S, 0);
+    p->sk.n.assign(n_host, n_host + S);
+    if (phase_host) p->sk.phase.assign(phase_host, phase_host + S);
+    p->ret_off.assign(S, 0); p->ret_n.assign(S, 0);
     return DD_OK;
 }
 
@@ -507,7 +522,7 @@ int dd_pipeline_skip_stats(dd_pipeline *p, long long *out5_host, uint8_t *skippe
     DD_REQUIRE(p && out5_host, DD_E_ARG, "dd_pipeline_skip_stats: NULL argument");
     out5_host[0] = p->det_stream_steps; out5_host[1] = p->skip_stream_steps; out5_host[2] = p->carry_launches;
     out5_host[3] = p->rows_retained; out5_host[4] = (long long)(p->d_store[0].cap + p->d_store[1].cap);
-    for (int z = 0; skipped_host && z < p->S; ++z) skipped_host[z] = p->skip_streams ? p->sk_last[z] : (uint8_t)(p->last_skip && p->st[z].seen > 0);
+    for (int z = 0; skipped_host && z < p->S; ++z) skipped_host[z] = p->sk.last[z];
     return DD_OK;
 }
 
@@ -516,7 +531,7 @@ int dd_pipeline_skip_stats(dd_pipeline *p, long long *out5_host, uint8_t *skippe
 int dd_pipeline_detector_letterbox(dd_pipeline *p, int pad) {
     DD_REQUIRE(p && p->det && p->det_kind == DET_YOLOV5, DD_E_ARG, "dd_pipeline_detector_letterbox: needs a pipeline with a YOLOv5 detector");
     DD_REQUIRE(pad >= 0 && pad <= 255, DD_E_ARG, "dd_pipeline_detector_letterbox: pad %d (0 .. 255)", pad);
-    DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, "dd_pipeline_detector_letterbox: call before the first step");
+    DD_BEFORE_FIRST_STEP("dd_pipeline_detector_letterbox");
     int rc;
     if ((rc = dd_letterbox_geometry(p->W, p->H, p->det_in_w, p->det_in, nullptr, nullptr, nullptr, nullptr)) != DD_OK) return rc;
     p->letterbox_pad = pad;
@@ -530,7 +545,7 @@ int dd_pipeline_detector_letterbox(dd_pipeline *p, int pad) {
 int dd_pipeline_metric(dd_pipeline *p, int metric) {
     DD_REQUIRE(p, DD_E_ARG, "dd_pipeline_metric: NULL pipeline");
     DD_REQUIRE(metric == 0 || metric == 1, DD_E_ARG, "dd_pipeline_metric: metric must be 0 (cosine) or 1 (euclidean), got %d", metric);
-    DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, "dd_pipeline_metric: call before the first step");
+    DD_BEFORE_FIRST_STEP("dd_pipeline_metric");
     return ddk::tracker_group_set_metric(p->trks[0], metric);
 }
 
@@ -543,7 +558,6 @@ int dd_pipeline_association(dd_pipeline *p, int where) {
 }
 
 // ---------------- per-stream parameters (the reference's flags are per process, i.e. per camera; deepdish.py:1394-1460)
-#define DD_BEFORE_FIRST_STEP(name) DD_REQUIRE(p->steps == 0 && !p->det_pending, DD_E_STATE, name ": call before the first step")
 
 // --line (deepdish.py:739-744) per stream
 int dd_pipeline_stream_lines(dd_pipeline *p, const double *lines_host) {
@@ -632,7 +646,7 @@ int dd_pipeline_reset_streams(dd_pipeline *p, const int *streams_host, int n) {
         listed[z] = 1;
     }
     // one counter for all streams cannot give one stream a fresh first detector step
-    DD_REQUIRE(p->skip_n <= 0, DD_E_STATE, "dd_pipeline_reset_streams: the pipeline has the pipeline-wide object_detector_skip_frames counter "
+    DD_REQUIRE(!p->skip_lockstep, DD_E_STATE, "dd_pipeline_reset_streams: the pipeline has the pipeline-wide object_detector_skip_frames counter "
                "(dd_pipeline_detector_skip_frames); dd_pipeline_detector_skip_streams has one per stream and takes a reset");
     if (n == 0) return DD_OK;
     DD_DEVICE(p->ctx);
@@ -646,16 +660,9 @@ int dd_pipeline_reset_streams(dd_pipeline *p, const int *streams_host, int n) {
     }
     for (int i = 0; i < n; ++i) {
         const int z = streams_host[i];
-        StreamState &q = p->st[z];
-        q.db.clear(); q.votes.clear();
-        q.counts.assign(p->wanted.size() * 4, 0);
-        q.det_cls.clear(); q.det_conf.clear();
-        q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
-        q.ib.clear(); q.is.clear(); q.ic.clear(); q.keep.clear();
-        q.det_tlwh.clear();
-        q.seen = 0;
-        if (p->skip_streams) {                     // counter and phase as at construction; the retained rows leave the store at its next refresh
-            p->sk_rem[z] = 0; p->sk_has[z] = 0; p->sk_last[z] = 0;
+        p->st[z].restart(p->wanted.size());
+        p->sk.restart(z);                          // counter and phase as at construction
+        if (p->skip_streams) {                     // the retained rows leave the store at its next refresh
             p->rows_retained -= p->ret_n[z];
             p->ret_n[z] = 0;
         }
@@ -852,21 +859,6 @@ namespace {
 
 // resize -> forward -> post-process -> adaptor tail -> pinned host block, all streams at once, on the
 // detector stream; det_done fires when the host block is complete.
-// Stage events of the previous step -> the accumulated GPU milliseconds (they completed long ago unless the caller asks right after a step).
-int flush_stage_events(dd_pipeline *p) {
-    if (!p->ev_pending) return DD_OK;
-    p->ev_pending = false;
-    double *into[6] = {&p->g_trk, &p->g_nms, &p->g_enc, &p->g_trk, &p->g_trk, &p->g_trk};
-    for (int k = 0; k < 6; ++k) {
-        if (!p->ev_pair[k]) continue;
-        p->ev_pair[k] = false;
-        float ms = 0.f;
-        DD_HIP(hipEventSynchronize(p->ev_main[2 * k + 1]));
-        DD_HIP(hipEventElapsedTime(&ms, p->ev_main[2 * k], p->ev_main[2 * k + 1]));
-        *into[k] += (double)ms;
-    }
-    return DD_OK;
-}
 // DD_STAGE_EVENTS=0: no stage events (dd_pipeline_stage_gpu_ms then reports zeros for the GPU stages); fourteen event records and seven
 // reads per step are ~10 us of host time -- noise against a multi-millisecond batched step, a few % of a single stream's 0.45 ms frame
 static const bool g_stage_events = !(getenv("DD_STAGE_EVENTS") && atoi(getenv("DD_STAGE_EVENTS")) == 0);
@@ -885,10 +877,8 @@ int enqueue_detector(dd_pipeline *p, const uint8_t *frames, const std::vector<in
     const uint8_t *src = frames;               // what the resize reads: n dense frames
     const int *d_tfl = p->d_tfl_boxes.as<int>(), *d_idx_gather = nullptr;
     if (n < p->S && p->det_kind == DET_TFLITE) {
-        std::vector<int> &hb = p->list_build;
-        hb.assign((size_t)n * 8, 0);
-        for (int i = 0; i < n; ++i) { int *b = hb.data() + (size_t)i * 8; b[2] = p->W; b[3] = p->H; b[4] = act[i]; b[6] = 1; }   // whole frame, swap_rb
-        if ((rc = stage_list(p, s, hb.data(), hb.size(), &d_tfl)) != DD_OK) return rc;
+        whole_frame_boxes(p, act.data(), n, p->list_build);
+        if ((rc = stage_list(p, s, p->list_build.data(), p->list_build.size(), &d_tfl)) != DD_OK) return rc;
     } else if (n < p->S) {
         const size_t frame_bytes = (size_t)p->H * p->W * 3;
         if (!p->d_gframes.p) {                 // the first masked step that needs it: S frames, exactly (DevBuf::reserve would add a quarter)
@@ -917,70 +907,58 @@ int enqueue_detector(dd_pipeline *p, const uint8_t *frames, const std::vector<in
     if ((rc = dd_net_forward(p->det, p->d_resized.as<uint8_t>(), n, s)) != DD_OK) return rc;       // :102-103 / yolov5.py:107-109
     void *raw = nullptr;
     if ((rc = dd_net_output(p->det, -1, &raw, nullptr, nullptr, nullptr, nullptr, nullptr)) != DD_OK) return rc;
-    if (p->det_kind == DET_YOLOV5) {                                                               // yolov5.py:120-131
-        const size_t cap = (size_t)p->n_anchors;
-        float *yb = p->d_fin.as<float>(), *ys = yb + n * cap * 4;
-        int *yc = reinterpret_cast<int *>(ys + n * cap), *yn = yc + n * cap;
-        if (p->yolo_dec) {                                       // :126-128 ran in the Detect layers' epilogues
-            float *b4 = nullptr, *cf = nullptr; int *cl = nullptr;
-            if ((rc = dd_net_yolo_decoded(p->det, &b4, &cf, &cl, nullptr)) != DD_OK) return rc;
-            if (p->letterbox_pad >= 0) {
-                if ((rc = ddk::yolov5_select_letterbox(s, b4, cf, cl, p->n_anchors, (float)p->det_conf, p->W, p->H, p->det_in_w, p->det_in, yb, ys, yc,
-                                                       p->n_anchors, yn, n)) != DD_OK) return rc;
-            } else
-            if ((rc = ddk::yolov5_select(s, b4, cf, cl, p->n_anchors, (float)p->det_conf, (float)p->W, (float)p->H, yb, ys, yc,
-                                         p->n_anchors, yn, n)) != DD_OK) return rc;
-        } else if (p->letterbox_pad >= 0) {
-            if ((rc = ddk::yolov5_decode_letterbox(s, static_cast<const float *>(raw), p->n_anchors, p->n_classes, (float)p->det_conf, p->W, p->H,
-                                                   p->det_in_w, p->det_in, yb, ys, yc, p->n_anchors, yn, n, p->d_post.p)) != DD_OK) return rc;
-        } else
-        if ((rc = ddk::yolov5_decode(s, static_cast<const float *>(raw), p->n_anchors, p->n_classes, (float)p->det_conf, (float)p->W,
-                                     (float)p->H, yb, ys, yc, p->n_anchors, yn, n, p->d_post.p)) != DD_OK) return rc;
-        // the passing rows of all streams packed behind one another; the host block is [n counts | pad to 64 B | rows x 24 B]: the
-        // counts and the first yolo_host_rows rows now, whatever lies beyond them when the step consumes the block
-        if ((rc = ddk::yolov5_pack(s, yb, ys, yc, yn, p->n_anchors, n, p->d_pack.as<float>())) != DD_OK) return rc;
-        const size_t head = ((size_t)n * 4 + 63) / 64 * 64;
-        DD_HIP(hipMemcpyAsync(p->h_fin.p, yn, (size_t)n * 4, hipMemcpyDeviceToHost, s));
-        DD_HIP(hipMemcpyAsync(p->h_fin.as<char>() + head, p->d_pack.p, p->yolo_host_rows * 24, hipMemcpyDeviceToHost, s));
+    // every adaptor ends the same way: its block to the pinned host copy, then the run is the pending one
+    auto finish = [&](const void *d_block, size_t bytes, size_t h_offset) -> int {
+        DD_HIP(hipMemcpyAsync(p->h_fin.as<char>() + h_offset, d_block, bytes, hipMemcpyDeviceToHost, s));
         if (g_stage_events) DD_HIP(hipEventRecord(p->ev_det[1], s));
         DD_HIP(hipEventRecord(p->det_done, s));
         p->det_pending = frames; p->det_pending_act = act;
         return DD_OK;
+    };
+    if (p->det_kind == DET_YOLOV5) {                                                               // yolov5.py:120-131
+        const YoloBlock y = YoloBlock::at(p->d_fin.p, n, p->n_anchors);
+        if (p->yolo_dec) {                                       // :126-128 ran in the Detect layers' epilogues
+            float *b4 = nullptr, *cf = nullptr; int *cl = nullptr;
+            if ((rc = dd_net_yolo_decoded(p->det, &b4, &cf, &cl, nullptr)) != DD_OK) return rc;
+            if (p->letterbox_pad >= 0) {
+                if ((rc = ddk::yolov5_select_letterbox(s, b4, cf, cl, p->n_anchors, (float)p->det_conf, p->W, p->H, p->det_in_w, p->det_in, y.boxes, y.scores, y.cls,
+                                                       p->n_anchors, y.count, n)) != DD_OK) return rc;
+            } else
+            if ((rc = ddk::yolov5_select(s, b4, cf, cl, p->n_anchors, (float)p->det_conf, (float)p->W, (float)p->H, y.boxes, y.scores, y.cls,
+                                         p->n_anchors, y.count, n)) != DD_OK) return rc;
+        } else if (p->letterbox_pad >= 0) {
+            if ((rc = ddk::yolov5_decode_letterbox(s, static_cast<const float *>(raw), p->n_anchors, p->n_classes, (float)p->det_conf, p->W, p->H,
+                                                   p->det_in_w, p->det_in, y.boxes, y.scores, y.cls, p->n_anchors, y.count, n, p->d_post.p)) != DD_OK) return rc;
+        } else
+        if ((rc = ddk::yolov5_decode(s, static_cast<const float *>(raw), p->n_anchors, p->n_classes, (float)p->det_conf, (float)p->W,
+                                     (float)p->H, y.boxes, y.scores, y.cls, p->n_anchors, y.count, n, p->d_post.p)) != DD_OK) return rc;
+        // the passing rows of all streams packed behind one another; of the host block the counts and the first yolo_host_rows rows
+        // now, whatever lies beyond them when the step consumes the block
+        if ((rc = ddk::yolov5_pack(s, y.boxes, y.scores, y.cls, y.count, p->n_anchors, n, p->d_pack.as<float>())) != DD_OK) return rc;
+        DD_HIP(hipMemcpyAsync(p->h_fin.p, y.count, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        return finish(p->d_pack.p, p->yolo_host_rows * YoloHostBlock::ROW, YoloHostBlock::head(n));
     }
-    float *db = p->d_det.as<float>(), *dc = db + (size_t)n * MAX_DET * 4, *ds = dc + (size_t)n * MAX_DET;
-    int *dn = reinterpret_cast<int *>(ds + (size_t)n * MAX_DET);
+    const TfliteBlock d = TfliteBlock::at(p->d_det.p, n, MAX_DET);
     if (p->ssd_per_class > 0) {                                 // use_regular_nms = true: per-class NMS, straight from the head
         if (p->q8.cls) rc = ddk::ssd_regular_nms_u8(s, p->q8.box, p->q8.cls, p->q8.stride, p->q8.lut, p->q8.quant, p->d_anchors, p->n_anchors, p->n_classes,
-                                                    MAX_DET, p->ssd_per_class, p->ssd_score_thr, p->ssd_iou_thr, db, dc, ds, dn, n);
+                                                    MAX_DET, p->ssd_per_class, p->ssd_score_thr, p->ssd_iou_thr, d.boxes, d.classes, d.scores, d.count, n);
         else rc = ddk::ssd_regular_nms_raw(s, static_cast<const float *>(raw), p->d_anchors, p->n_anchors, p->n_classes, MAX_DET, p->ssd_per_class,
-                                           p->ssd_score_thr, p->ssd_iou_thr, db, dc, ds, dn, n);
+                                           p->ssd_score_thr, p->ssd_iou_thr, d.boxes, d.classes, d.scores, d.count, n);
         if (rc != DD_OK) return rc;
     } else if (p->ssd_dec) {
         float *eb = nullptr, *es = nullptr, *ek = nullptr;
         int *ec = nullptr;
         if ((rc = dd_net_ssd_decoded(p->det, &eb, &es, &ec, &ek)) != DD_OK) return rc;
-        if ((rc = ddk::ssd_postprocess_decoded(s, eb, es, ec, ek, p->n_anchors, MAX_DET, p->ssd_score_thr, p->ssd_iou_thr, db, dc, ds, dn, n,
+        if ((rc = ddk::ssd_postprocess_decoded(s, eb, es, ec, ek, p->n_anchors, MAX_DET, p->ssd_score_thr, p->ssd_iou_thr, d.boxes, d.classes, d.scores, d.count, n,
                                                p->d_post.p, p->d_post.cap)) != DD_OK) return rc;
     } else if ((rc = ddk::ssd_postprocess(s, static_cast<const float *>(raw), p->d_anchors, p->n_anchors, p->n_classes, MAX_DET,
-                                          p->ssd_score_thr, p->ssd_iou_thr, db, dc, ds, dn, n, p->d_post.p, p->d_post.cap)) != DD_OK) return rc;
-    if (p->det_kind == DET_TFLITE) {                           // the generic adaptor's tail is a few integer truncations: on the host (step2)
-        const size_t dbytes = (size_t)n * MAX_DET * 6 * sizeof(float) + (size_t)n * sizeof(int);
-        DD_HIP(hipMemcpyAsync(p->h_fin.p, p->d_det.p, dbytes, hipMemcpyDeviceToHost, s));
-        if (g_stage_events) DD_HIP(hipEventRecord(p->ev_det[1], s));
-        DD_HIP(hipEventRecord(p->det_done, s));
-        p->det_pending = frames; p->det_pending_act = act;
-        return DD_OK;
-    }
-    double *fb = p->d_fin.as<double>(), *fs = fb + (size_t)n * MAX_DET * 4;
-    int *fc = reinterpret_cast<int *>(fs + (size_t)n * MAX_DET), *fn = fc + (size_t)n * MAX_DET;
-    if ((rc = ddk::ssd_finish(s, db, dc, ds, n, MAX_DET, p->det_conf, 0.5, (double)p->W, (double)p->H, fb, fc, fs, fn)) != DD_OK)
+                                          p->ssd_score_thr, p->ssd_iou_thr, d.boxes, d.classes, d.scores, d.count, n, p->d_post.p, p->d_post.cap)) != DD_OK) return rc;
+    if (p->det_kind == DET_TFLITE)                             // the generic adaptor's tail is a few integer truncations: on the host (consume_tflite)
+        return finish(p->d_det.p, TfliteBlock::bytes(n, MAX_DET), 0);
+    const SsdBlock f = SsdBlock::at(p->d_fin.p, n, MAX_DET);
+    if ((rc = ddk::ssd_finish(s, d.boxes, d.classes, d.scores, n, MAX_DET, p->det_conf, 0.5, (double)p->W, (double)p->H, f.boxes, f.cls, f.scores, f.count)) != DD_OK)
         return rc;                                                                                    // :111-150
-    const size_t fbytes = (size_t)n * (MAX_DET * (4 * 8 + 8 + 4) + 4);
-    DD_HIP(hipMemcpyAsync(p->h_fin.p, p->d_fin.p, fbytes, hipMemcpyDeviceToHost, s));
-    if (g_stage_events) DD_HIP(hipEventRecord(p->ev_det[1], s));
-    DD_HIP(hipEventRecord(p->det_done, s));
-    p->det_pending = frames; p->det_pending_act = act;
-    return DD_OK;
+    return finish(p->d_fin.p, SsdBlock::bytes(n, MAX_DET), 0);
 }
 
 // A skip step's tracker input (deepdish.py:1003-1014: zip(boxes, labels, scores, features) with the last encoder run's features):
@@ -1063,344 +1041,322 @@ void count_line_one_stream(dd_pipeline *p, int z) {
 
 }  // namespace
 
-extern "C" {
+// ---------------- the phases of one step, in the order dd_pipeline_step3 calls them.  i is a position in pl.act and z = pl.act[i] the
+// stream, except in the adaptor tails, where i is a position in pl.dl (the detector run's blocks hold dl.size() images).
 
-// frames: device u8 [S][H][W][3] BGR.  inj_*: optional injected detections that REPLACE the detector's
-// output (the detector still runs): boxes tlwh as the detector adaptor would return them (f64),
-// scores, class ids, stream s owns rows [inj_offsets[s], inj_offsets[s+1]).
-// frames_next (optional): the frames of the following step; their detector run is queued on the detector
-// stream as soon as this step has read its own detections, and overlaps this step's NMS / encoder / tracker.
-// With dd_pipeline_detector_skip_frames a skip step ignores inj_* (they stand for the detector's output, and it does not run), and
-// frames_next is queued only when the next step is a detector step.
-int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames, const uint8_t *frames_next, const double *inj_boxes_host,
-                      const double *inj_scores_host, const int *inj_cls_host, const int *inj_offsets_host);
-// The same step for the streams with present_host[z] != 0 only (u8 [S]; NULL = every stream): for the others this step does not exist --
-// no predict, no update, no count-line pass, no vote, no MOG2 update, nothing of their frame slot or injected rows read, nothing of
-// their state written.  present_next_host belongs to frames_next.  The queued look-ahead run remembers its stream list: a next step
-// that arrives with other frames or another list discards it and runs the detector itself, with the same result.
-int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames, const uint8_t *present_host, const uint8_t *frames_next,
-                      const uint8_t *present_next_host, const double *inj_boxes_host, const double *inj_scores_host,
-                      const int *inj_cls_host, const int *inj_offsets_host);
-
-int dd_pipeline_step(dd_pipeline *p, const uint8_t *frames, const double *inj_boxes_host, const double *inj_scores_host,
-                     const int *inj_cls_host, const int *inj_offsets_host) {
-    return dd_pipeline_step2(p, frames, nullptr, inj_boxes_host, inj_scores_host, inj_cls_host, inj_offsets_host);
-}
-
-int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames, const uint8_t *frames_next, const double *inj_boxes_host,
-                      const double *inj_scores_host, const int *inj_cls_host, const int *inj_offsets_host) {
-    return dd_pipeline_step3(p, frames, nullptr, frames_next, nullptr, inj_boxes_host, inj_scores_host, inj_cls_host, inj_offsets_host);
-}
-
-int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *present_host, const uint8_t *frames_next,
-                      const uint8_t *present_next_host, const double *inj_boxes_host, const double *inj_scores_host,
-                      const int *inj_cls_host, const int *inj_offsets_host) {
-    DD_REQUIRE(p && frames_in, DD_E_ARG, "dd_pipeline_step: NULL argument");
-    DD_REQUIRE(frames_next != frames_in, DD_E_ARG,
-               "dd_pipeline_step2: frames_next must be a different buffer from frames (its detector run is queued while "
-               "this step still reads frames, and the next step consumes it by address)");
-    DD_REQUIRE(!present_next_host || frames_next, DD_E_ARG, "dd_pipeline_step3: present_next without frames_next");
-    // the skip phase is one counter per pipeline; under masks it would have to be one per stream
-    DD_REQUIRE(!(present_host || present_next_host) || p->skip_n <= 0, DD_E_STATE,
-               "dd_pipeline_step3: a presence mask on a pipeline with object_detector_skip_frames set (dd_pipeline_detector_skip_frames)");
+// 1. Which streams step, which of them run the detector, what the counters will be, which frames are read, whether a look-ahead run is
+// queued: everything the step decides, before it launches anything.
+static int phase_plan(dd_pipeline *p, StepPlan &pl, const uint8_t *frames_in, const uint8_t *present_host, const uint8_t *frames_next,
+                      const uint8_t *present_next_host, const double *inj_boxes_host, const double *inj_scores_host, const int *inj_cls_host,
+                      const int *inj_offsets_host) {
     int rc;
-    const std::vector<int> &act = p->act, &act_next = p->act_next;
-    if ((rc = present_list(p, present_host, "present", p->act)) != DD_OK) return rc;
-    if ((rc = present_list(p, present_next_host, "present_next", p->act_next)) != DD_OK) return rc;
-    DD_DEVICE(p->ctx);
-    const uint8_t *frames = frames_in;
+    if ((rc = present_list(p, present_host, "present", pl.act)) != DD_OK) return rc;
+    if ((rc = present_list(p, present_next_host, "present_next", pl.act_next)) != DD_OK) return rc;
+    ddhost::plan_skip(p->sk, pl);              // deepdish.py:929-938: a stream's first step detects; then N skip steps follow every detector step
+    const bool masking = p->mog2 && p->bg_masking;          // the detector and the encoder then read the masked copy, which a look-ahead run cannot
+    pl.frames_in = frames_in; pl.present = present_host;
+    pl.frames = masking ? p->d_masked.as<uint8_t>() : frames_in;
+    pl.frames_next = pl.dl_next.empty() || masking ? nullptr : frames_next;   // no stream of the next step on a detector step: nothing to queue
+    pl.inj_boxes = inj_boxes_host; pl.inj_scores = inj_scores_host; pl.inj_cls = inj_cls_host; pl.inj_offsets = inj_offsets_host;
+    return DD_OK;
+}
+
+// 2. tracker predict for the step's streams; MOG2 over their frames
+static int phase_predict_mog2(dd_pipeline *p, const StepPlan &pl) {
     hipStream_t s = p->ctx->stream;
-    const int S = p->S, n = (int)act.size(), MAX_DET = p->max_det;
-    p->masked_steps += present_host != nullptr;
-    p->streams_stepped += n;
-    if (n == 0) {                                  // a legal step: nothing is launched and no state changes (a queued look-ahead run was
-        p->det_pending = nullptr;                  // announced for other streams than arrived: dropped)
-        p->steps += 1;
-        return DD_OK;
-    }
-    if (act_next.empty()) frames_next = nullptr;
-    std::vector<dd_tracker *> &atrks = p->atrks;
-    atrks.resize(n);
-    for (int i = 0; i < n; ++i) atrks[i] = p->trks[act[i]];
-    if ((rc = flush_stage_events(p)) != DD_OK) return rc;
-    // deepdish.py:929-938: the first step detects; then N skip steps follow every detector step
-    const bool skip = p->skip_rem > 0 && p->steps > 0;
-    const int skip_rem_next = skip ? p->skip_rem - 1 : p->skip_n;
-    if (skip_rem_next > 0) frames_next = nullptr;          // the next step is a skip step: no detector run to queue for its frames
-    // One counter per stream (dd_pipeline_detector_skip_streams): `dl` = the streams of act on a detector step, skp[i] = 1 where position
-    // i of act is on a skip step.  The counters after this step follow from those at its entry, so the next step's detector list -- what
-    // the look-ahead queues -- is known here.  Without per-stream counters dl is act and skp is all zero (`skip` covers that form).
-    const bool per_stream = p->skip_streams;
-    std::vector<uint8_t> &skp = p->skp;
-    skp.assign(n, 0);
-    if (per_stream) {
-        p->det_list.clear(); p->det_next.clear();
-        p->sk_rem_next = p->sk_rem; p->sk_has_next = p->sk_has;
-        for (int i = 0; i < n; ++i) {
-            const int z = act[i];
-            if (p->sk_rem[z] > 0 && p->sk_has[z]) { skp[i] = 1; p->sk_rem_next[z] = p->sk_rem[z] - 1; }
-            else {
-                p->det_list.push_back(z);
-                p->sk_rem_next[z] = !p->sk_has[z] && p->sk_phase[z] >= 0 ? p->sk_phase[z] : p->sk_n[z];
-                p->sk_has_next[z] = 1;
-            }
-        }
-        for (int z : act_next) if (!(p->sk_rem_next[z] > 0 && p->sk_has_next[z])) p->det_next.push_back(z);
-        if (p->det_next.empty()) frames_next = nullptr;    // a step of skip steps only: no detector run to queue
-    }
-    const std::vector<int> &dl = per_stream ? p->det_list : act, &dl_next = per_stream ? p->det_next : act_next;
-    const int nd = (int)dl.size();                         // the detector run's batch: its blocks are indexed by POSITION in dl
-    const double t0 = now_s();
-    p->step_wait = 0;
-    if ((skip || nd == 0) && p->det) {
+    int rc;
+    if (pl.dl.empty() && p->det) {
         // no detector run reads these frames: the main stream takes over what the detector stream holds for them (the wait an ingest
         // ring queued there for their upload, dd_pipeline_detector_stream) before MOG2 reads them
         DD_HIP(hipEventRecord(p->skip_mark, p->det_stream));
         DD_HIP(hipStreamWaitEvent(s, p->skip_mark, 0));
     }
     DD_STAGE_BEGIN(0);
-    if ((rc = ddk::trackers_predict(atrks.data(), n)) != DD_OK) return rc;              // deepdish.py:1028
+    if ((rc = ddk::trackers_predict(p->atrks.data(), (int)pl.act.size())) != DD_OK) return rc;      // deepdish.py:1028
     DD_STAGE_END(0);
     if (p->mog2) {                                                                      // :920-924
-        if ((rc = ddk::mog2_apply_streams(p->mog2, s, frames_in, present_host, -1.0, p->d_mask.as<uint8_t>(),
+        if ((rc = ddk::mog2_apply_streams(p->mog2, s, pl.frames_in, pl.present, -1.0, p->d_mask.as<uint8_t>(),
                                           p->bg_masking ? p->d_masked.as<uint8_t>() : nullptr)) != DD_OK) return rc;
-        if (p->bg_masking) { frames = p->d_masked.as<uint8_t>(); frames_next = nullptr; p->det_pending = nullptr; }
+        if (p->bg_masking) p->det_pending = nullptr;           // a run queued on the unmasked frames: dropped
     }
+    return DD_OK;
+}
 
-    // ---------------- detector: resize -> forward -> post-process -> adaptor tail, all streams at once
-    // (host phases below: one parallel_for over the streams each -- they share nothing; hostpool.h)
-    constexpr int GRAIN = 16;
-    std::vector<StreamState> &st = p->st;
-    if (skip || (nd == 0 && p->det)) {
-        // every stream keeps the adaptor output of the last detector step; the early look-ahead form queues the next frames here
-        if (per_stream) p->det_pending = nullptr;  // (a run queued for a step that turns out to have no detector stream: dropped)
-        if (p->det && frames_next && !p->det_late && (rc = enqueue_detector(p, frames_next, dl_next)) != DD_OK) return rc;
-    } else if (p->det) {
-        if ((p->det_pending != frames || p->det_pending_act != dl) && (rc = enqueue_detector(p, frames, dl)) != DD_OK) return rc;   // not queued ahead (or for other streams): run it now
-        DD_TIMED_WAIT(hipEventSynchronize(p->det_done));                                               // round trip 1
-        p->det_pending = nullptr;
-        if (g_stage_events) {   // the detector chain of these frames on its stream: resize, forward, post-process, adaptor tail, host copy
-            float ms = 0.f;
-            DD_HIP(hipEventElapsedTime(&ms, p->ev_det[0], p->ev_det[1]));
-            p->g_det += (double)ms;
-        }
-        if (p->det_kind == DET_YOLOV5) {
-            const size_t head = ((size_t)nd * 4 + 63) / 64 * 64;
-            const int *yn = p->h_fin.as<int>();
-            std::vector<size_t> &ybase = p->ybase;
-            ybase.assign(nd + 1, 0);
-            for (int i = 0; i < nd; ++i) ybase[i + 1] = ybase[i] + (size_t)std::min(yn[i], p->n_anchors);
-            if (ybase[nd] > p->yolo_host_rows) {                    // a busy step: fetch the rest (the detector stream is idle here) and
-                const size_t have = p->yolo_host_rows, total = ybase[nd];      // make room for twice as many from now on
-                // ... but never more than the packed block holds (S * n_anchors rows): the first copy of every later step reads that many
-                const size_t grown = std::min(2 * total, (size_t)S * (size_t)p->n_anchors);
-                PinBuf bigger;
-                if ((rc = bigger.reserve(head + grown * 24)) != DD_OK) return rc;
-                memcpy(bigger.p, p->h_fin.p, head + have * 24);
-                hipError_t he = hipMemcpyAsync(bigger.as<char>() + head + have * 24, p->d_pack.as<char>() + have * 24, (total - have) * 24,
-                                               hipMemcpyDeviceToHost, p->det_stream);
-                if (he == hipSuccess) he = hipStreamSynchronize(p->det_stream);
-                if (he != hipSuccess) { bigger.release(); DD_HIP(he); }
-                p->h_fin.release();
-                p->h_fin = bigger;
-                p->yolo_host_rows = grown;
-                yn = p->h_fin.as<int>();
+// 3a. YOLOv5's tail (yolov5.py:137-145) over the packed host block; a busy step fetches the rows its first copy had no room for
+static int consume_yolov5(dd_pipeline *p, const StepPlan &pl) {
+    const std::vector<int> &dl = pl.dl;
+    const int nd = (int)dl.size();
+    int rc;
+    const size_t head = YoloHostBlock::head(nd), ROW = YoloHostBlock::ROW;
+    const int *yn = YoloHostBlock::at(p->h_fin.p, nd, p->yolo_host_rows).count;
+    std::vector<size_t> &ybase = p->ybase;
+    ybase.assign(nd + 1, 0);
+    for (int i = 0; i < nd; ++i) ybase[i + 1] = ybase[i] + (size_t)std::min(yn[i], p->n_anchors);
+    if (ybase[nd] > p->yolo_host_rows) {                    // a busy step: fetch the rest (the detector stream is idle here) and
+        const size_t have = p->yolo_host_rows, total = ybase[nd];      // make room for twice as many from now on
+        // ... but never more than the packed block holds (S * n_anchors rows): the first copy of every later step reads that many
+        const size_t grown = std::min(2 * total, (size_t)p->S * (size_t)p->n_anchors);
+        PinBuf bigger;
+        if ((rc = bigger.reserve(head + grown * ROW)) != DD_OK) return rc;
+        memcpy(bigger.p, p->h_fin.p, head + have * ROW);
+        hipError_t he = hipMemcpyAsync(bigger.as<char>() + head + have * ROW, p->d_pack.as<char>() + have * ROW, (total - have) * ROW,
+                                       hipMemcpyDeviceToHost, p->det_stream);
+        if (he == hipSuccess) he = hipStreamSynchronize(p->det_stream);
+        if (he != hipSuccess) { bigger.release(); DD_HIP(he); }
+        p->h_fin.release();
+        p->h_fin = bigger;
+        p->yolo_host_rows = grown;
+    }
+    const float *rows = YoloHostBlock::at(p->h_fin.p, nd, p->yolo_host_rows).rows;
+    ddk::parallel_for(nd, GRAIN, [&](int i0, int i1) {
+        for (int i = i0; i < i1; ++i) {
+            StreamState &q = p->st[dl[i]];
+            q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
+            const int nr = (int)(ybase[i + 1] - ybase[i]);
+            for (int r = 0; r < nr; ++r) {
+                const float *b = rows + (ybase[i] + r) * 6;
+                int c;
+                memcpy(&c, b + 5, 4);
+                const float sc = b[4];
+                if (wanted_index(p, dl[i], class_name(p, c)) < 0 || !(sc >= (float)p->det_conf)) continue;
+                q.boxes0.insert(q.boxes0.end(), {(double)b[0], (double)b[1], (double)(b[2] - b[0]), (double)(b[3] - b[1])});   // f32 arithmetic, :140-142
+                q.scores0.push_back((double)sc);
+                q.cls0.push_back(c);
             }
-            const float *rows = reinterpret_cast<const float *>(p->h_fin.as<char>() + head);
-            ddk::parallel_for(nd, GRAIN, [&](int i0, int i1) {
-                for (int i = i0; i < i1; ++i) {
-                    StreamState &q = st[dl[i]];
-                    q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
-                    const int nr = (int)(ybase[i + 1] - ybase[i]);
-                    for (int r = 0; r < nr; ++r) {                                                     // yolov5.py:137-145
-                        const float *b = rows + (ybase[i] + r) * 6;
-                        int c;
-                        memcpy(&c, b + 5, 4);
-                        const float sc = b[4];
-                        if (wanted_index(p, dl[i], class_name(p, c)) < 0 || !(sc >= (float)p->det_conf)) continue;
-                        q.boxes0.insert(q.boxes0.end(), {(double)b[0], (double)b[1], (double)(b[2] - b[0]), (double)(b[3] - b[1])});   // f32 arithmetic, :140-142
-                        q.scores0.push_back((double)sc);
-                        q.cls0.push_back(c);
-                    }
-                }
-            });
-        } else if (p->det_kind == DET_TFLITE) {
-            // tflite_object_detector.py:234-295 (_postprocess) + tools/tflite.py:26-41: score >= threshold, int() of the scaled
-            // corners (f32 arithmetic, truncation), label = label_list[class], stable sort by descending score, wanted labels only
-            // (the run's blocks hold nd = dl.size() frames: z below is the POSITION of a stream in dl)
-            const float *hb = p->h_fin.as<float>(), *hc = hb + (size_t)nd * MAX_DET * 4, *hs = hc + (size_t)nd * MAX_DET;
-            const int *hn = reinterpret_cast<const int *>(hs + (size_t)nd * MAX_DET);
-            ddk::parallel_for(nd, GRAIN, [&](int z0, int z1) {
-                for (int z = z0; z < z1; ++z) {
-                    StreamState &q = st[dl[z]];
-                    q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
-                    int order[MAX_DET_CAP], no = 0;
-                    for (int i = 0; i < hn[z] && i < MAX_DET; ++i)
-                        if ((double)hs[z * MAX_DET + i] >= p->det_conf) order[no++] = i;     // np.float32 >= python float: compared in float64
-                    std::stable_sort(order, order + no, [&](int a, int b) { return hs[z * MAX_DET + a] > hs[z * MAX_DET + b]; });
-                    for (int k = 0; k < no; ++k) {
-                        const int i = order[k], c = (int)hc[z * MAX_DET + i];
-                        if (c < 0 || c >= (int)p->tfl_labels.size() || wanted_index(p, dl[z], p->tfl_labels[c]) < 0) continue;
-                        // the class stored for the vote is resolved through class_name() = labels[c + label_offset]: the same line of the
-                        // label file only while no blank line precedes it -- store the index class_name() maps back to this very label
-                        int cs = -1;
-                        for (int li = p->label_offset; li < (int)p->labels.size() && cs < 0; ++li) if (p->labels[li] == p->tfl_labels[c]) cs = li - p->label_offset;
-                        if (cs < 0) continue;
-                        const float *b = hb + ((size_t)z * MAX_DET + i) * 4;                          // ymin, xmin, ymax, xmax (normalised)
-                        // int(np.float32 * python int): the reference's pinned NumPy promotes the product to float64 (exact), then truncates
-                        const int top = (int)((double)b[0] * (double)p->H), left = (int)((double)b[1] * (double)p->W);
-                        const int bottom = (int)((double)b[2] * (double)p->H), right = (int)((double)b[3] * (double)p->W);
-                        q.boxes0.insert(q.boxes0.end(), {(double)left, (double)top, (double)(right - left), (double)(bottom - top)});
-                        q.scores0.push_back((double)hs[z * MAX_DET + i]);
-                        q.cls0.push_back(cs);
-                    }
-                }
-            });
-        } else {
-            const double *hb = p->h_fin.as<double>(), *hs = hb + (size_t)nd * MAX_DET * 4;       // (z: position in dl, as above)
-            const int *hc = reinterpret_cast<const int *>(hs + (size_t)nd * MAX_DET), *hn = hc + (size_t)nd * MAX_DET;
-            ddk::parallel_for(nd, GRAIN, [&](int z0, int z1) {
-                for (int z = z0; z < z1; ++z) {
-                    StreamState &q = st[dl[z]];
-                    q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
-                    for (int i = 0; i < hn[z]; ++i) {                                                  // :204-212
-                        const double sc = hs[z * MAX_DET + i];
-                        if (!(sc >= p->det_conf) || wanted_index(p, dl[z], class_name(p, hc[z * MAX_DET + i])) < 0) continue;
-                        const double *b = hb + ((size_t)z * MAX_DET + i) * 4;
-                        q.boxes0.insert(q.boxes0.end(), {b[0], b[1], b[2] - b[0], b[3] - b[1]});
-                        q.scores0.push_back(sc);
-                        q.cls0.push_back(hc[z * MAX_DET + i]);
-                    }
-                }
-            });
         }
-        // the host block has been consumed: the detector buffers are free for the next frames
-        if (frames_next && !p->det_late && (rc = enqueue_detector(p, frames_next, dl_next)) != DD_OK) return rc;
-    } else {
-        for (int z : dl) { StreamState &q = st[z]; q.boxes0.clear(); q.scores0.clear(); q.cls0.clear(); }
-    }
-    if (inj_offsets_host)
-        DD_REQUIRE(inj_boxes_host && inj_scores_host && inj_cls_host, DD_E_ARG, "dd_pipeline_step: injected arrays missing");
-    const double t1 = now_s();
+    });
+    return DD_OK;
+}
 
-    // ---------------- box hygiene (deepdish.py:940-960, background subtraction off) + batched NMS (:995)
-    // (from here on i is a position in act and z = act[i] the stream: off, doff, tlwh, keep counts and the NMS problems are per position)
+// 3b. The generic TFLite adaptor's tail: tflite_object_detector.py:234-295 (_postprocess) + tools/tflite.py:26-41 -- score >= threshold,
+// int() of the scaled corners (f32 arithmetic, truncation), label = label_list[class], stable sort by descending score, wanted labels only
+static int consume_tflite(dd_pipeline *p, const StepPlan &pl) {
+    const std::vector<int> &dl = pl.dl;
+    const int nd = (int)dl.size(), MAX_DET = p->max_det;
+    const TfliteBlock h = TfliteBlock::at(p->h_fin.p, nd, MAX_DET);
+    const float *hb = h.boxes, *hc = h.classes, *hs = h.scores;
+    const int *hn = h.count;
+    ddk::parallel_for(nd, GRAIN, [&](int z0, int z1) {
+        for (int z = z0; z < z1; ++z) {
+            StreamState &q = p->st[dl[z]];
+            q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
+            int order[MAX_DET_CAP], no = 0;
+            for (int i = 0; i < hn[z] && i < MAX_DET; ++i)
+                if ((double)hs[z * MAX_DET + i] >= p->det_conf) order[no++] = i;     // np.float32 >= python float: compared in float64
+            std::stable_sort(order, order + no, [&](int a, int b) { return hs[z * MAX_DET + a] > hs[z * MAX_DET + b]; });
+            for (int k = 0; k < no; ++k) {
+                const int i = order[k], c = (int)hc[z * MAX_DET + i];
+                if (c < 0 || c >= (int)p->tfl_labels.size() || wanted_index(p, dl[z], p->tfl_labels[c]) < 0) continue;
+                // the class stored for the vote is resolved through class_name() = labels[c + label_offset]: the same line of the
+                // label file only while no blank line precedes it -- store the index class_name() maps back to this very label
+                int cs = -1;
+                for (int li = p->label_offset; li < (int)p->labels.size() && cs < 0; ++li) if (p->labels[li] == p->tfl_labels[c]) cs = li - p->label_offset;
+                if (cs < 0) continue;
+                const float *b = hb + ((size_t)z * MAX_DET + i) * 4;                          // ymin, xmin, ymax, xmax (normalised)
+                // int(np.float32 * python int): the reference's pinned NumPy promotes the product to float64 (exact), then truncates
+                const int top = (int)((double)b[0] * (double)p->H), left = (int)((double)b[1] * (double)p->W);
+                const int bottom = (int)((double)b[2] * (double)p->H), right = (int)((double)b[3] * (double)p->W);
+                q.boxes0.insert(q.boxes0.end(), {(double)left, (double)top, (double)(right - left), (double)(bottom - top)});
+                q.scores0.push_back((double)hs[z * MAX_DET + i]);
+                q.cls0.push_back(cs);
+            }
+        }
+    });
+    return DD_OK;
+}
+
+// 3c. The SSD adaptor's tail (ssd_mobilenet.py:204-212) over what ssd_finish left
+static int consume_ssd(dd_pipeline *p, const StepPlan &pl) {
+    const std::vector<int> &dl = pl.dl;
+    const int nd = (int)dl.size(), MAX_DET = p->max_det;
+    const SsdBlock h = SsdBlock::at(p->h_fin.p, nd, MAX_DET);
+    const double *hb = h.boxes, *hs = h.scores;
+    const int *hc = h.cls, *hn = h.count;
+    ddk::parallel_for(nd, GRAIN, [&](int z0, int z1) {
+        for (int z = z0; z < z1; ++z) {
+            StreamState &q = p->st[dl[z]];
+            q.boxes0.clear(); q.scores0.clear(); q.cls0.clear();
+            for (int i = 0; i < hn[z]; ++i) {
+                const double sc = hs[z * MAX_DET + i];
+                if (!(sc >= p->det_conf) || wanted_index(p, dl[z], class_name(p, hc[z * MAX_DET + i])) < 0) continue;
+                const double *b = hb + ((size_t)z * MAX_DET + i) * 4;
+                q.boxes0.insert(q.boxes0.end(), {b[0], b[1], b[2] - b[0], b[3] - b[1]});
+                q.scores0.push_back(sc);
+                q.cls0.push_back(hc[z * MAX_DET + i]);
+            }
+        }
+    });
+    return DD_OK;
+}
+
+// 3. The detector's block for the streams of dl -> their adaptor output (StreamState::boxes0 / scores0 / cls0); the streams on a skip
+// step keep theirs.  The early look-ahead form queues the next frames here.
+static int phase_consume_detector(dd_pipeline *p, const StepPlan &pl) {
+    int rc;
+    if (pl.dl.empty()) {
+        p->det_pending = nullptr;                  // (a run queued for a step that turns out to have no detector stream: dropped)
+        if (p->det && pl.frames_next && !p->det_late && (rc = enqueue_detector(p, pl.frames_next, pl.dl_next)) != DD_OK) return rc;
+        return DD_OK;
+    }
+    if (!p->det) {                                 // injected detections only
+        for (int z : pl.dl) { StreamState &q = p->st[z]; q.boxes0.clear(); q.scores0.clear(); q.cls0.clear(); }
+        return DD_OK;
+    }
+    if ((p->det_pending != pl.frames || p->det_pending_act != pl.dl) && (rc = enqueue_detector(p, pl.frames, pl.dl)) != DD_OK) return rc;   // not queued ahead (or for other streams): run it now
+    DD_TIMED_WAIT(hipEventSynchronize(p->det_done));                                               // round trip 1
+    p->det_pending = nullptr;
+    if (g_stage_events) {   // the detector chain of these frames on its stream: resize, forward, post-process, adaptor tail, host copy
+        float ms = 0.f;
+        DD_HIP(hipEventElapsedTime(&ms, p->ev_det[0], p->ev_det[1]));
+        p->g_det += (double)ms;
+    }
+    rc = p->det_kind == DET_YOLOV5 ? consume_yolov5(p, pl) : p->det_kind == DET_TFLITE ? consume_tflite(p, pl) : consume_ssd(p, pl);
+    if (rc != DD_OK) return rc;
+    // the host block has been consumed: the detector buffers are free for the next frames
+    if (pl.frames_next && !p->det_late && (rc = enqueue_detector(p, pl.frames_next, pl.dl_next)) != DD_OK) return rc;
+    return DD_OK;
+}
+
+// 4. Injected detections replace the adaptor output of the streams on a detector step; box hygiene (deepdish.py:940-960) for every
+// stream; off = the candidates per position
+static void phase_inject_hygiene(dd_pipeline *p, const StepPlan &pl) {
+    const std::vector<int> &act = pl.act;
+    const int n = (int)act.size();
     std::vector<int> &off = p->off;
     off.assign(n + 1, 0);
     ddk::parallel_for(n, GRAIN, [&](int i0, int i1) {
         for (int i = i0; i < i1; ++i) {
             const int z = act[i];
-            StreamState &q = st[z];
-            if (inj_offsets_host && !skip && !skp[i]) {
-                const int a = inj_offsets_host[z], b = inj_offsets_host[z + 1];
-                q.boxes0.assign(inj_boxes_host + (size_t)a * 4, inj_boxes_host + (size_t)b * 4);
-                q.scores0.assign(inj_scores_host + a, inj_scores_host + b);
-                q.cls0.assign(inj_cls_host + a, inj_cls_host + b);
+            StreamState &q = p->st[z];
+            if (pl.inj_offsets && !pl.skp[i]) {
+                const int a = pl.inj_offsets[z], b = pl.inj_offsets[z + 1];
+                q.boxes0.assign(pl.inj_boxes + (size_t)a * 4, pl.inj_boxes + (size_t)b * 4);
+                q.scores0.assign(pl.inj_scores + a, pl.inj_scores + b);
+                q.cls0.assign(pl.inj_cls + a, pl.inj_cls + b);
             }
             q.ib.clear(); q.is.clear(); q.ic.clear();
             ddhost::clean_boxes(q.boxes0, q.scores0, q.cls0, p->W, p->H, q.ib, q.is, q.ic);
         }
     });
-    for (int i = 0; i < n; ++i) off[i + 1] = off[i] + (int)st[act[i]].is.size();
-    if (p->mog2 && off[n] > 0) {                                                        // :957 motion test on every candidate
-        const int K0 = off[n];
-        const size_t in_bytes = (size_t)K0 * 5 * sizeof(int), all_bytes = in_bytes + (size_t)K0 * sizeof(int);
-        if ((rc = p->h_mbox.reserve(all_bytes)) != DD_OK) return rc;
-        if ((rc = p->d_mbox.reserve(all_bytes)) != DD_OK) return rc;
-        int *hm = p->h_mbox.as<int>(), *dm = p->d_mbox.as<int>();
-        for (int i = 0; i < n; ++i) {
-            const StreamState &q = st[act[i]];
-            for (size_t k = 0; k < q.is.size(); ++k) {
-                for (int c = 0; c < 4; ++c) hm[(size_t)(off[i] + k) * 4 + c] = (int)q.ib[k * 4 + c];
-                hm[(size_t)K0 * 4 + off[i] + k] = act[i];                 // the mask plane is the stream's own
-            }
-        }
-        DD_HIP(hipMemcpyAsync(dm, hm, in_bytes, hipMemcpyHostToDevice, s));
-        if ((rc = ddk::mask_box_count(s, p->d_mask.as<uint8_t>(), p->H, p->W, dm, dm + (size_t)K0 * 4, K0, dm + (size_t)K0 * 5)) != DD_OK) return rc;
-        DD_HIP(hipMemcpyAsync(hm + (size_t)K0 * 5, dm + (size_t)K0 * 5, (size_t)K0 * sizeof(int), hipMemcpyDeviceToHost, s));
-        DD_TIMED_WAIT(hipStreamSynchronize(s));                                                        // extra round trip
-        const int *cnt = hm + (size_t)K0 * 5;
-        std::vector<int> off0 = off;
-        for (int i = 0; i < n; ++i) {
-            StreamState &q = st[act[i]];
-            size_t nk = 0;
-            for (size_t k = 0; k < q.is.size(); ++k) {
-                const int64_t w = q.ib[k * 4 + 2], h = q.ib[k * 4 + 3];
-                if (!((double)cnt[off0[i] + k] >= p->ratio_of[act[i]] * (double)w * (double)h)) { p->motion_rejected++; continue; }
-                for (int c = 0; c < 4; ++c) q.ib[nk * 4 + c] = q.ib[k * 4 + c];
-                q.is[nk] = q.is[k]; q.ic[nk] = q.ic[k];
-                ++nk;
-            }
-            q.ib.resize(nk * 4); q.is.resize(nk); q.ic.resize(nk);
-            off[i + 1] = off[i] + (int)nk;
-        }
-    }
-    const int K = off[n];
-    if (K > 0) {
-        bool small = true;
-        for (int i = 0; i < n; ++i) if (off[i + 1] - off[i] > 64) small = false;
-        // one --nms-max-overlap per stream: when this step's streams do not agree, their thresholds ride in the same upload, in front
-        // of the offsets, for the per-problem launch
-        bool thr_differ = false;
-        for (int i = 1; i < n && p->nms_differ && !thr_differ; ++i) thr_differ = p->nms_of[act[i]] != p->nms_of[act[0]];
-        const size_t n_thr = small && thr_differ ? (size_t)n : 0;
-        const size_t in_bytes = ((size_t)K * 5 + n_thr) * sizeof(double) + (size_t)(n + 1) * sizeof(int);
-        const size_t out_bytes = (size_t)(K + n) * sizeof(int);
-        if ((rc = p->h_nms.reserve(in_bytes + out_bytes + 256)) != DD_OK) return rc;
-        if ((rc = p->d_nms.reserve(in_bytes + out_bytes + 256 + (small ? 0 : ddk::nms_scratch_bytes(4096)))) != DD_OK) return rc;
-        double *hb = p->h_nms.as<double>(), *hk = hb + (size_t)K * 4;
-        for (size_t i = 0; i < n_thr; ++i) hk[K + i] = p->nms_of[act[i]];
-        int *ho = reinterpret_cast<int *>(hk + K + n_thr);
-        ddk::parallel_for(n, GRAIN, [&](int i0, int i1) {
-            for (int i = i0; i < i1; ++i) {
-                const StreamState &q = st[act[i]];
-                for (size_t k = 0; k < q.ib.size(); ++k) hb[(size_t)off[i] * 4 + k] = (double)q.ib[k];   // astype(np.float)
-                for (size_t k = 0; k < q.is.size(); ++k) hk[off[i] + k] = q.is[k];
-            }
-        });
-        memcpy(ho, off.data(), (size_t)(n + 1) * sizeof(int));
-        char *d = p->d_nms.as<char>();
-        DD_STAGE_BEGIN(1);
-        DD_HIP(hipMemcpyAsync(d, hb, in_bytes, hipMemcpyHostToDevice, s));
-        const double *dbx = reinterpret_cast<const double *>(d), *dk = dbx + (size_t)K * 4;
-        const int *doff = reinterpret_cast<const int *>(dk + K + n_thr);
-        int *didx = reinterpret_cast<int *>(d + ((in_bytes + 63) / 64) * 64), *dnk = didx + K;
-        if (n_thr) {
-            if ((rc = ddk::nms_batched_small_streams(s, dbx, dk, doff, n, dk + K, 0, didx, dnk)) != DD_OK) return rc;
-            p->nms_streams_launches += 1;
-        } else if (small) {
-            if ((rc = ddk::nms_batched_small(s, dbx, dk, doff, n, p->nms_of[act[0]], 0, didx, dnk)) != DD_OK) return rc;
-        } else {
-            void *scr = d + ((in_bytes + 63) / 64) * 64 + ((out_bytes + 63) / 64) * 64;
-            for (int i = 0; i < n; ++i) {
-                const int k = off[i + 1] - off[i];
-                if ((rc = ddk::nms_ex(s, dbx + (size_t)off[i] * 4, dk + off[i], k, p->nms_of[act[i]], 0, 0, didx + off[i], dnk + i,
-                                      scr, ddk::nms_scratch_bytes(4096))) != DD_OK) return rc;
-            }
-        }
-        int *hidx = reinterpret_cast<int *>(p->h_nms.as<char>() + ((in_bytes + 63) / 64) * 64);
-        DD_HIP(hipMemcpyAsync(hidx, didx, out_bytes, hipMemcpyDeviceToHost, s));
-        DD_STAGE_END(1);
-        DD_TIMED_WAIT(hipStreamSynchronize(s));                                                        // round trip 2
-        const int *hnk = hidx + K;
-        for (int i = 0; i < n; ++i) st[act[i]].keep.assign(hidx + off[i], hidx + off[i] + hnk[i]);
-    } else {
-        for (int z : act) st[z].keep.clear();
-    }
-    const double t2 = now_s();
+    for (int i = 0; i < n; ++i) off[i + 1] = off[i] + (int)p->st[act[i]].is.size();
+}
 
-    // ---------------- crops + MARS for every kept box of every stream (deepdish.py:1008).  A skip step runs neither (:1003-1014): stream
-    // z's first n_z = min(kept boxes, feature rows of the last encoder run) boxes pair with those rows, as zip() truncates
-    std::vector<int> &doff = p->doff;
-    doff.assign(n + 1, 0);
-    // per-stream counters: a stream on a skip step pairs with its own retained rows; eoff = the encoder's rows, the detector streams' only
-    std::vector<int> &eoff = p->eoff;
-    eoff.assign(n + 1, 0);
-    for (int i = 0; i < n; ++i) {                   // (a lock-step skip step is never masked: i is the stream there, as in foff)
-        const int kept = (int)st[act[i]].keep.size();
-        doff[i + 1] = doff[i] + (skip ? std::min(kept, p->foff[i + 1] - p->foff[i]) : skp[i] ? std::min(kept, p->ret_n[act[i]]) : kept);
-        eoff[i + 1] = eoff[i] + (skip || skp[i] ? 0 : kept);
+// 5. deepdish.py:957: the motion test on every candidate, against its stream's own mask plane (the extra round trip)
+static int phase_motion_test(dd_pipeline *p, const StepPlan &pl) {
+    const std::vector<int> &act = pl.act;
+    const int n = (int)act.size();
+    std::vector<int> &off = p->off;
+    if (!p->mog2 || off[n] == 0) return DD_OK;
+    hipStream_t s = p->ctx->stream;
+    int rc;
+    const int K0 = off[n];
+    const size_t in_bytes = (size_t)K0 * 5 * sizeof(int), all_bytes = in_bytes + (size_t)K0 * sizeof(int);
+    if ((rc = p->h_mbox.reserve(all_bytes)) != DD_OK) return rc;
+    if ((rc = p->d_mbox.reserve(all_bytes)) != DD_OK) return rc;
+    int *hm = p->h_mbox.as<int>(), *dm = p->d_mbox.as<int>();
+    for (int i = 0; i < n; ++i) {
+        const StreamState &q = p->st[act[i]];
+        for (size_t k = 0; k < q.is.size(); ++k) {
+            for (int c = 0; c < 4; ++c) hm[(size_t)(off[i] + k) * 4 + c] = (int)q.ib[k * 4 + c];
+            hm[(size_t)K0 * 4 + off[i] + k] = act[i];                 // the mask plane is the stream's own
+        }
     }
+    DD_HIP(hipMemcpyAsync(dm, hm, in_bytes, hipMemcpyHostToDevice, s));
+    if ((rc = ddk::mask_box_count(s, p->d_mask.as<uint8_t>(), p->H, p->W, dm, dm + (size_t)K0 * 4, K0, dm + (size_t)K0 * 5)) != DD_OK) return rc;
+    DD_HIP(hipMemcpyAsync(hm + (size_t)K0 * 5, dm + (size_t)K0 * 5, (size_t)K0 * sizeof(int), hipMemcpyDeviceToHost, s));
+    DD_TIMED_WAIT(hipStreamSynchronize(s));                                                        // extra round trip
+    const int *cnt = hm + (size_t)K0 * 5;
+    std::vector<int> off0 = off;
+    for (int i = 0; i < n; ++i) {
+        StreamState &q = p->st[act[i]];
+        size_t nk = 0;
+        for (size_t k = 0; k < q.is.size(); ++k) {
+            const int64_t w = q.ib[k * 4 + 2], h = q.ib[k * 4 + 3];
+            if (!((double)cnt[off0[i] + k] >= p->ratio_of[act[i]] * (double)w * (double)h)) { p->motion_rejected++; continue; }
+            for (int c = 0; c < 4; ++c) q.ib[nk * 4 + c] = q.ib[k * 4 + c];
+            q.is[nk] = q.is[k]; q.ic[nk] = q.ic[k];
+            ++nk;
+        }
+        q.ib.resize(nk * 4); q.is.resize(nk); q.ic.resize(nk);
+        off[i + 1] = off[i] + (int)nk;
+    }
+    return DD_OK;
+}
+
+// 6. batched NMS (deepdish.py:995), one problem per position -> StreamState::keep
+static int phase_nms(dd_pipeline *p, const StepPlan &pl) {
+    const std::vector<int> &act = pl.act, &off = p->off;
+    const int n = (int)act.size(), K = off[n];
+    std::vector<StreamState> &st = p->st;
+    if (K == 0) {
+        for (int z : act) st[z].keep.clear();
+        return DD_OK;
+    }
+    hipStream_t s = p->ctx->stream;
+    int rc;
+    bool small = true;
+    for (int i = 0; i < n; ++i) if (off[i + 1] - off[i] > 64) small = false;
+    // one --nms-max-overlap per stream: when this step's streams do not agree, their thresholds ride in the same upload, in front
+    // of the offsets, for the per-problem launch
+    bool thr_differ = false;
+    for (int i = 1; i < n && p->nms_differ && !thr_differ; ++i) thr_differ = p->nms_of[act[i]] != p->nms_of[act[0]];
+    const size_t n_thr = small && thr_differ ? (size_t)n : 0;
+    const size_t in_bytes = ((size_t)K * 5 + n_thr) * sizeof(double) + (size_t)(n + 1) * sizeof(int);
+    const size_t out_bytes = (size_t)(K + n) * sizeof(int);
+    if ((rc = p->h_nms.reserve(in_bytes + out_bytes + 256)) != DD_OK) return rc;
+    if ((rc = p->d_nms.reserve(in_bytes + out_bytes + 256 + (small ? 0 : ddk::nms_scratch_bytes(4096)))) != DD_OK) return rc;
+    double *hb = p->h_nms.as<double>(), *hk = hb + (size_t)K * 4;
+    for (size_t i = 0; i < n_thr; ++i) hk[K + i] = p->nms_of[act[i]];
+    int *ho = reinterpret_cast<int *>(hk + K + n_thr);
+    ddk::parallel_for(n, GRAIN, [&](int i0, int i1) {
+        for (int i = i0; i < i1; ++i) {
+            const StreamState &q = st[act[i]];
+            for (size_t k = 0; k < q.ib.size(); ++k) hb[(size_t)off[i] * 4 + k] = (double)q.ib[k];   // astype(np.float)
+            for (size_t k = 0; k < q.is.size(); ++k) hk[off[i] + k] = q.is[k];
+        }
+    });
+    memcpy(ho, off.data(), (size_t)(n + 1) * sizeof(int));
+    char *d = p->d_nms.as<char>();
+    DD_STAGE_BEGIN(1);
+    DD_HIP(hipMemcpyAsync(d, hb, in_bytes, hipMemcpyHostToDevice, s));
+    const double *dbx = reinterpret_cast<const double *>(d), *dk = dbx + (size_t)K * 4;
+    const int *doff = reinterpret_cast<const int *>(dk + K + n_thr);
+    int *didx = reinterpret_cast<int *>(d + ((in_bytes + 63) / 64) * 64), *dnk = didx + K;
+    if (n_thr) {
+        if ((rc = ddk::nms_batched_small_streams(s, dbx, dk, doff, n, dk + K, 0, didx, dnk)) != DD_OK) return rc;
+        p->nms_streams_launches += 1;
+    } else if (small) {
+        if ((rc = ddk::nms_batched_small(s, dbx, dk, doff, n, p->nms_of[act[0]], 0, didx, dnk)) != DD_OK) return rc;
+    } else {
+        void *scr = d + ((in_bytes + 63) / 64) * 64 + ((out_bytes + 63) / 64) * 64;
+        for (int i = 0; i < n; ++i) {
+            const int k = off[i + 1] - off[i];
+            if ((rc = ddk::nms_ex(s, dbx + (size_t)off[i] * 4, dk + off[i], k, p->nms_of[act[i]], 0, 0, didx + off[i], dnk + i,
+                                  scr, ddk::nms_scratch_bytes(4096))) != DD_OK) return rc;
+        }
+    }
+    int *hidx = reinterpret_cast<int *>(p->h_nms.as<char>() + ((in_bytes + 63) / 64) * 64);
+    DD_HIP(hipMemcpyAsync(hidx, didx, out_bytes, hipMemcpyDeviceToHost, s));
+    DD_STAGE_END(1);
+    DD_TIMED_WAIT(hipStreamSynchronize(s));                                                        // round trip 2
+    const int *hnk = hidx + K;
+    for (int i = 0; i < n; ++i) st[act[i]].keep.assign(hidx + off[i], hidx + off[i] + hnk[i]);
+    return DD_OK;
+}
+
+// 7. Pair every stream's kept boxes with feature rows (doff; eoff = the rows made now), then crops + MARS for the boxes of the streams
+// on a detector step (deepdish.py:1008).  A stream on a skip step runs neither (:1003-1014): it pairs with the rows of its last run.
+static int phase_pair_crops_encoder(dd_pipeline *p, const StepPlan &pl) {
+    const std::vector<int> &act = pl.act;
+    const std::vector<uint8_t> &skp = pl.skp;
+    const int n = (int)act.size();
+    hipStream_t s = p->ctx->stream;
+    int rc;
+    std::vector<StreamState> &st = p->st;
+    std::vector<int> &doff = p->doff, &eoff = p->eoff;
+    // (the rows of a stream's last run: retained in the store, or -- all streams stepping together, i is the stream -- still in d_feats)
+    ddhost::pair_counts(skp, [&](int i) { return (int)st[act[i]].keep.size(); },
+                        [&](int i) { return p->skip_streams ? p->ret_n[act[i]] : p->foff[i + 1] - p->foff[i]; }, doff, eoff);
     const int D = doff[n], E = eoff[n];             // tracker input rows; rows the encoder makes in this step (E == D unless streams skip)
     std::vector<double> &tlwh = p->tlwh;
     tlwh.resize((size_t)D * 4);
@@ -1436,7 +1392,7 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
         if (E > 0) {
             DD_STAGE_BEGIN(2);
             DD_HIP(hipMemcpyAsync(p->d_crop.p, hc0, (size_t)E * 32, hipMemcpyHostToDevice, s));
-            if ((rc = ddk::crop_resize(s, frames, p->H, p->W, p->d_crop.p, E, p->enc_h, p->enc_w, p->d_patches.as<uint8_t>())) != DD_OK) return rc;
+            if ((rc = ddk::crop_resize(s, pl.frames, p->H, p->W, p->d_crop.p, E, p->enc_h, p->enc_w, p->d_patches.as<uint8_t>())) != DD_OK) return rc;
             for (int a = 0; a < E; a += p->enc_batch) {
                 const int nb = std::min(p->enc_batch, E - a);
                 if ((rc = dd_net_forward(p->enc, p->d_patches.as<uint8_t>() + (size_t)a * p->enc_h * p->enc_w * 3, nb, s)) != DD_OK) return rc;
@@ -1447,52 +1403,44 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
     } else {
         for (int z : act) { StreamState &q = st[z]; q.det_cls.clear(); q.det_conf.clear(); q.det_tlwh.clear(); }
     }
-    if (!skip && !per_stream) p->foff = doff;       // the rows d_feats now holds: what the skip steps up to the next detector step pair with
-    const double t3 = now_s();
+    if (!p->skip_streams && !pl.dl.empty()) p->foff = doff;   // the rows d_feats now holds: what the skip steps up to the next detector step pair with
+    return DD_OK;
+}
 
-    // ---------------- deep_sort update, phase-split so all streams share two round trips (:1029)
+// 8. The tracker's feature rows, in act order (opens stage pair 3, which phase 9 closes).  d_feats already is that input unless a stream
+// on a skip step has rows to pair; then they are assembled in d_feats_skip --
+//  * all streams stepping together: skip_gather_rows_k out of d_feats (n == S: such a pipeline takes no mask);
+//  * per-stream counters: one feature_rows_carry launch (csrc/featrows.hip) -- fresh encoder rows for the streams of dl, retained rows
+//    for the others -- which also writes the next store when an encoder run changed what is retained.
+static int phase_feature_rows(dd_pipeline *p, const StepPlan &pl, const float **feats_out) {
+    hipStream_t s = p->ctx->stream;
+    const int S = p->S, n = (int)pl.act.size(), D = p->doff[n];
+    int rc;
+    bool gathered = false;
     DD_STAGE_BEGIN(3);
-    if (skip && D > 0) {                            // the skip step's tracker input rows, gathered on the device (the trak stage)
-        // (n == S here: a skip step is never masked)
-        if ((rc = p->h_gather.reserve((size_t)(2 * S + 1) * sizeof(int))) != DD_OK) return rc;
-        if ((rc = p->d_gather.reserve((size_t)(2 * S + 1) * sizeof(int))) != DD_OK) return rc;
-        if ((rc = p->d_feats_skip.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
-        int *hg = p->h_gather.as<int>();           // the previous step's copy out of it completed at that step's last stream wait
-        memcpy(hg, doff.data(), (size_t)(S + 1) * sizeof(int));
-        memcpy(hg + S + 1, p->foff.data(), (size_t)S * sizeof(int));
-        DD_HIP(hipMemcpyAsync(p->d_gather.p, hg, (size_t)(2 * S + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-        const int *dg = p->d_gather.as<int>();
-        hipLaunchKernelGGL(skip_gather_rows_k, dim3(S), dim3(256), 0, s, p->d_feats.as<float4>(), p->d_feats_skip.as<float4>(), dg, dg + S + 1);
-        DD_LAUNCH_CHECK();
-    }
-    const float *feats = D == 0 ? nullptr : skip ? p->d_feats_skip.as<float>() : p->d_feats.as<float>();
-    if (per_stream) {
-        // One launch (csrc/featrows.hip): the tracker's input rows in act order -- fresh encoder rows for the streams of dl, retained rows
-        // for the others -- and, when an encoder run changed what is retained, the next store: fresh rows replace, the rest is carried,
-        // absent streams included.  With no stream on a skip step that has rows to pair, d_feats already is the tracker's input.
-        bool gather = false;
-        for (int i = 0; i < n; ++i) gather = gather || (skp[i] && doff[i + 1] > doff[i]);
-        const bool refresh = nd > 0;
-        std::vector<int> &tb = p->list_build, &noff = p->ret_off_new;
-        tb.clear();
-        int total = 0;
-        for (int z = 0, i = 0; z < S; ++z) {
-            const bool here = i < n && act[i] == z;
-            const bool fresh = here && !skp[i];
-            const int kept = here ? (fresh ? eoff[i + 1] - eoff[i] : doff[i + 1] - doff[i]) : 0;
-            const int n_out = here && gather ? kept : 0, n_store = !refresh ? 0 : fresh ? kept : p->ret_n[z];
-            if (n_out > 0 || n_store > 0) {
-                const int e[8] = {fresh ? 0 : 1, fresh ? eoff[i] : p->ret_off[z], n_out, here ? doff[i] : 0, n_store, total, 0, 0};
-                tb.insert(tb.end(), e, e + 8);
-            }
-            noff[z] = total;
-            total += n_store;
-            i += here;
+    if (!p->skip_streams) {
+        if (pl.dl.empty() && D > 0) {
+            if ((rc = p->h_gather.reserve((size_t)(2 * S + 1) * sizeof(int))) != DD_OK) return rc;
+            if ((rc = p->d_gather.reserve((size_t)(2 * S + 1) * sizeof(int))) != DD_OK) return rc;
+            if ((rc = p->d_feats_skip.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
+            int *hg = p->h_gather.as<int>();           // the previous step's copy out of it completed at that step's last stream wait
+            memcpy(hg, p->doff.data(), (size_t)(S + 1) * sizeof(int));
+            memcpy(hg + S + 1, p->foff.data(), (size_t)S * sizeof(int));
+            DD_HIP(hipMemcpyAsync(p->d_gather.p, hg, (size_t)(2 * S + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+            const int *dg = p->d_gather.as<int>();
+            hipLaunchKernelGGL(skip_gather_rows_k, dim3(S), dim3(256), 0, s, p->d_feats.as<float4>(), p->d_feats_skip.as<float4>(), dg, dg + S + 1);
+            DD_LAUNCH_CHECK();
+            gathered = true;
         }
+    } else {
+        const bool refresh = !pl.dl.empty();
+        std::vector<int> &tb = p->list_build;
+        const ddhost::RowTable rt = ddhost::feature_row_table(S, pl.act, pl.skp, p->doff, p->eoff, p->ret_off, p->ret_n, refresh, tb,
+                                                              p->ret_off_new, p->ret_n_new);
         if (!tb.empty()) {
             DevBuf &next = p->d_store[1 - p->store_cur];
-            if (gather && (rc = p->d_feats_skip.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
-            if (refresh && (rc = next.reserve((size_t)total * 128 * sizeof(float))) != DD_OK) return rc;
+            if (rt.gather && (rc = p->d_feats_skip.reserve((size_t)D * 128 * sizeof(float))) != DD_OK) return rc;
+            if (refresh && (rc = next.reserve((size_t)rt.total * 128 * sizeof(float))) != DD_OK) return rc;
             const int *d_table = nullptr;
             if ((rc = stage_list(p, s, tb.data(), tb.size(), &d_table)) != DD_OK) return rc;
             if ((rc = ddk::feature_rows_carry(s, p->d_feats.as<float>(), p->d_store[p->store_cur].as<float>(), p->d_feats_skip.as<float>(),
@@ -1500,50 +1448,130 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
             p->carry_launches += 1;
         }
         if (refresh) {
-            for (int z = 0, i = 0; z < S; ++z) {
-                const bool here = i < n && act[i] == z;
-                if (here && !skp[i]) p->ret_n[z] = eoff[i + 1] - eoff[i];
-                i += here;
-            }
-            p->ret_off = noff;
+            p->ret_off.swap(p->ret_off_new); p->ret_n.swap(p->ret_n_new);
             p->store_cur = 1 - p->store_cur;
-            p->rows_retained = total;
+            p->rows_retained = rt.total;
         }
-        feats = D == 0 ? nullptr : gather ? p->d_feats_skip.as<float>() : p->d_feats.as<float>();
+        gathered = rt.gather;
     }
-    if ((rc = ddk::trackers_update_begin(atrks.data(), n, tlwh.data(), feats, 1, doff.data())) != DD_OK) return rc;
+    *feats_out = D == 0 ? nullptr : gathered ? p->d_feats_skip.as<float>() : p->d_feats.as<float>();
+    return DD_OK;
+}
+
+// 9. deep_sort update, phase-split so all streams share two round trips (deepdish.py:1029), with the late look-ahead between its
+// first launches and its first wait
+static int phase_tracker_update(dd_pipeline *p, const StepPlan &pl, const float *feats) {
+    hipStream_t s = p->ctx->stream;
+    const int n = (int)pl.act.size();
+    dd_tracker **atrks = p->atrks.data();
+    int rc;
+    if ((rc = ddk::trackers_update_begin(atrks, n, p->tlwh.data(), feats, 1, p->doff.data())) != DD_OK) return rc;
     DD_STAGE_END(3);
     // Look-ahead, late form (default): the detector run of the next frames is queued HERE, behind this step's NMS / crops / encoder /
     // association kernels (enqueue_detector orders the detector stream after what the main stream holds so far).  Queued at the
     // consume point instead (DD_DET_LATE=0) it shares the GPU with the encoder from the start, the chain the host waits for takes
     // twice as long, and then the GPU idles through the host's matching / count-line tail: one worker group ran 6.3 ms per
     // 384-frame step for 5.0 ms of kernels.  Here the chain runs alone, and the detector fills the tail.
-    if (p->det && frames_next && p->det_late && (rc = enqueue_detector(p, frames_next, dl_next)) != DD_OK) return rc;
+    if (p->det && pl.frames_next && p->det_late && (rc = enqueue_detector(p, pl.frames_next, pl.dl_next)) != DD_OK) return rc;
     DD_TIMED_WAIT(hipStreamSynchronize(s));                                                            // round trip 3
     DD_STAGE_BEGIN(4);
-    if ((rc = ddk::trackers_update_match(atrks.data(), n)) != DD_OK) return rc;
+    if ((rc = ddk::trackers_update_match(atrks, n)) != DD_OK) return rc;
     DD_STAGE_END(4);
     DD_TIMED_WAIT(hipStreamSynchronize(s));                                                            // round trip 4
     DD_STAGE_BEGIN(5);
-    if ((rc = ddk::trackers_update_end(atrks.data(), n)) != DD_OK) return rc;
+    if ((rc = ddk::trackers_update_end(atrks, n)) != DD_OK) return rc;
     DD_STAGE_END(5);
-    ddk::parallel_for(n, GRAIN, [&](int i0, int i1) {
-        for (int i = i0; i < i1; ++i) { count_line_one_stream(p, act[i]); st[act[i]].seen += 1; }
+    return DD_OK;
+}
+
+// 10. the count line of every stream of the step; its frame number moves on
+static void phase_count_line(dd_pipeline *p, const StepPlan &pl) {
+    ddk::parallel_for((int)pl.act.size(), GRAIN, [&](int i0, int i1) {
+        for (int i = i0; i < i1; ++i) { count_line_one_stream(p, pl.act[i]); p->st[pl.act[i]].seen += 1; }
     });
+}
+
+// 11. the step has succeeded: the plan's counters become the pipeline's
+static void phase_commit(dd_pipeline *p, const StepPlan &pl) {
+    const int n = (int)pl.act.size(), nd = (int)pl.dl.size();
+    p->ev_pending = true;
+    p->steps += 1;
+    p->sk.rem = pl.rem_next; p->sk.has = pl.has_next;
+    for (int i = 0; i < n; ++i) p->sk.last[pl.act[i]] = pl.skp[i];
+    p->det_stream_steps += nd; p->skip_stream_steps += n - nd;
+}
+
+extern "C" {
+
+// frames: device u8 [S][H][W][3] BGR.  inj_*: optional injected detections that REPLACE the detector's
+// output (the detector still runs): boxes tlwh as the detector adaptor would return them (f64),
+// scores, class ids, stream s owns rows [inj_offsets[s], inj_offsets[s+1]).
+// frames_next (optional): the frames of the following step; their detector run is queued on the detector
+// stream as soon as this step has read its own detections, and overlaps this step's NMS / encoder / tracker.
+// With dd_pipeline_detector_skip_frames a skip step ignores inj_* (they stand for the detector's output, and it does not run), and
+// frames_next is queued only when the next step is a detector step.
+int dd_pipeline_step(dd_pipeline *p, const uint8_t *frames, const double *inj_boxes_host, const double *inj_scores_host,
+                     const int *inj_cls_host, const int *inj_offsets_host) {
+    return dd_pipeline_step2(p, frames, nullptr, inj_boxes_host, inj_scores_host, inj_cls_host, inj_offsets_host);
+}
+
+int dd_pipeline_step2(dd_pipeline *p, const uint8_t *frames, const uint8_t *frames_next, const double *inj_boxes_host,
+                      const double *inj_scores_host, const int *inj_cls_host, const int *inj_offsets_host) {
+    return dd_pipeline_step3(p, frames, nullptr, frames_next, nullptr, inj_boxes_host, inj_scores_host, inj_cls_host, inj_offsets_host);
+}
+
+// The same step for the streams with present_host[z] != 0 only (u8 [S]; NULL = every stream): for the others this step does not exist --
+// no predict, no update, no count-line pass, no vote, no MOG2 update, nothing of their frame slot or injected rows read, nothing of
+// their state written.  present_next_host belongs to frames_next.  The queued look-ahead run remembers its stream list: a next step
+// that arrives with other frames or another list discards it and runs the detector itself, with the same result.
+int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *present_host, const uint8_t *frames_next,
+                      const uint8_t *present_next_host, const double *inj_boxes_host, const double *inj_scores_host,
+                      const int *inj_cls_host, const int *inj_offsets_host) {
+    DD_REQUIRE(p && frames_in, DD_E_ARG, "dd_pipeline_step: NULL argument");
+    DD_REQUIRE(frames_next != frames_in, DD_E_ARG,
+               "dd_pipeline_step2: frames_next must be a different buffer from frames (its detector run is queued while "
+               "this step still reads frames, and the next step consumes it by address)");
+    DD_REQUIRE(!present_next_host || frames_next, DD_E_ARG, "dd_pipeline_step3: present_next without frames_next");
+    // all streams of that form step together: it keeps their rows in d_feats by stream, not in a store
+    DD_REQUIRE(!(present_host || present_next_host) || !p->skip_lockstep, DD_E_STATE,
+               "dd_pipeline_step3: a presence mask on a pipeline with object_detector_skip_frames set (dd_pipeline_detector_skip_frames)");
+    int rc;
+    if ((rc = phase_plan(p, p->plan, frames_in, present_host, frames_next, present_next_host, inj_boxes_host, inj_scores_host, inj_cls_host,
+                         inj_offsets_host)) != DD_OK) return rc;
+    const StepPlan &pl = p->plan;
+    DD_DEVICE(p->ctx);
+    const int n = (int)pl.act.size();
+    p->masked_steps += present_host != nullptr;
+    p->streams_stepped += n;
+    if (n == 0) {                                  // a legal step: nothing is launched and no state changes (a queued look-ahead run was
+        p->det_pending = nullptr;                  // announced for other streams than arrived: dropped)
+        p->steps += 1;
+        return DD_OK;
+    }
+    p->atrks.resize(n);
+    for (int i = 0; i < n; ++i) p->atrks[i] = p->trks[pl.act[i]];
+    if ((rc = flush_stage_events(p)) != DD_OK) return rc;
+    const double t0 = now_s();
+    p->step_wait = 0;
+    if ((rc = phase_predict_mog2(p, pl)) != DD_OK) return rc;
+    if ((rc = phase_consume_detector(p, pl)) != DD_OK) return rc;
+    if (inj_offsets_host)
+        DD_REQUIRE(inj_boxes_host && inj_scores_host && inj_cls_host, DD_E_ARG, "dd_pipeline_step: injected arrays missing");
+    const double t1 = now_s();
+    phase_inject_hygiene(p, pl);
+    if ((rc = phase_motion_test(p, pl)) != DD_OK) return rc;
+    if ((rc = phase_nms(p, pl)) != DD_OK) return rc;
+    const double t2 = now_s();
+    if ((rc = phase_pair_crops_encoder(p, pl)) != DD_OK) return rc;
+    const double t3 = now_s();
+    const float *feats = nullptr;
+    if ((rc = phase_feature_rows(p, pl, &feats)) != DD_OK) return rc;
+    if ((rc = phase_tracker_update(p, pl, feats)) != DD_OK) return rc;
+    phase_count_line(p, pl);
     const double t4 = now_s();
     p->t_det += t1 - t0; p->t_nms += t2 - t1; p->t_enc += t3 - t2; p->t_trk += t4 - t3;
     p->g_wall += 1e3 * (t4 - t0); p->g_host += 1e3 * ((t4 - t0) - p->step_wait);
-    p->ev_pending = true;
-    p->steps += 1;
-    p->skip_rem = skip_rem_next;
-    p->last_skip = skip;
-    if (per_stream) {
-        p->sk_rem.swap(p->sk_rem_next); p->sk_has.swap(p->sk_has_next);
-        for (int i = 0; i < n; ++i) p->sk_last[act[i]] = skp[i];
-        p->det_stream_steps += nd; p->skip_stream_steps += n - nd;
-    } else {
-        (skip ? p->skip_stream_steps : p->det_stream_steps) += n;
-    }
+    phase_commit(p, pl);
     return DD_OK;
 }
 

@@ -697,17 +697,6 @@ void match_decide_host(const double *app, const double *iou, int T, int n, const
 }
 
 namespace {
-int update_match(dd_tracker **ts, int S);
-}
-
-// (an update that fails here is over: trackers_update_end will not be called for it)
-int trackers_update_match(dd_tracker **ts, int S) {
-    const int rc = update_match(ts, S);
-    if (rc != DD_OK) ts[0]->pool->upd_inflight = false;
-    return rc;
-}
-
-namespace {
 int update_match(dd_tracker **ts, int S) {
     TrackerPool *p = ts[0]->pool;
     hipStream_t s = p->ctx->stream;
@@ -799,6 +788,13 @@ int update_match(dd_tracker **ts, int S) {
     return DD_OK;
 }
 }  // namespace
+
+// (an update that fails here is over: trackers_update_end will not be called for it)
+int trackers_update_match(dd_tracker **ts, int S) {
+    const int rc = update_match(ts, S);
+    if (rc != DD_OK) ts[0]->pool->upd_inflight = false;
+    return rc;
+}
 
 // phase 3 (the means have landed): mirror them for dd_tracker_read.
 int trackers_update_end(dd_tracker **ts, int S) {

@@ -3,7 +3,8 @@
 // through ddk::parallel_for for a few hundred steps; a stream's body runs the phases csrc/pipeline.hip runs on the pool: box hygiene
 // (host_phases.h clean_boxes), a cascade-sized assignment problem (lsap.cpp), the CPython-set iteration order of the IoU stage's
 // candidates (pyset.cpp) and the count-line segment test (host_phases.h seg_intersect).  Every stream's results are checked
-// against a serial replay, so a lost or doubled chunk shows as a mismatch as well as a race report.
+// against a serial replay, so a lost or doubled chunk shows as a mismatch as well as a race report.  Before that, on the main thread, the
+// step's index arithmetic (host_phases.h: step plan, pairing counts, feature-row table) is driven and checked -- see check_step_plans.
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
@@ -57,9 +58,142 @@ static Result one_stream(int group, int z, int step) {
     return out;
 }
 
+// ---------------- the step's index arithmetic (host_phases.h plan_skip, pair_counts, feature_row_table), driven as dd_pipeline_step3
+// drives it: random presence masks, one skip counter per stream, random kept counts; checked against a serial replay per stream and
+// against host vectors of tagged rows moved exactly as feature_rows_carry_k moves them.
+
+// tests/skip_streams_ref.py::schedule: true where the detector runs, over `frames` present frames of one stream (phase < 0: none)
+static std::vector<bool> schedule(int n, int phase, int frames) {
+    int rem = 0;
+    bool has = false;
+    std::vector<bool> out;
+    for (int f = 0; f < frames; ++f) {
+        if (rem > 0 && has) { rem -= 1; out.push_back(false); }
+        else { rem = !has && phase >= 0 ? phase : n; has = true; out.push_back(true); }
+    }
+    return out;
+}
+
+struct Row { int z, run, j; bool operator==(const Row &o) const { return z == o.z && run == o.run && j == o.j; } };   // (stream, encoder run, row)
+struct Seen { long long all_absent = 0, returned = 0, empty_dl = 0, retained_zero = 0, kept_over_retained = 0, gathers = 0, refreshes = 0; };
+
+static long long check_step_plans(int S, unsigned long long seed, int steps, Seen &seen) {
+    Rng r{seed};
+    long long bad = 0;
+    auto fail = [&](const char *what, int step) { if (bad++ < 5) fprintf(stderr, "host harness: S = %d, step %d: %s\n", S, step, what); };
+    ddhost::SkipCounters sk;
+    sk.start(S, 0);
+    for (int z = 0; z < S; ++z) { sk.n[z] = r.next() % 4; sk.phase[z] = r.next() % 2 ? -1 : (int)(r.next() % (sk.n[z] + 1)); }
+    std::vector<std::vector<bool>> seq(S);                 // per stream: detector step (true) or skip step, one per present frame
+    std::vector<int> away(S, 0), gone_for(S, 0);
+    auto draw = [&](std::vector<int> &act) {               // the next step's presence mask
+        act.clear();
+        const unsigned mode = r.next() % 12;
+        for (int z = 0; z < S; ++z) {
+            if (away[z] == 0 && r.next() % 40 == 0) away[z] = 20 + r.next() % 40;       // a camera drops out for a while
+            bool here = mode == 0 ? false : mode == 1 ? true : r.next() % 5 < 3;
+            if (away[z] > 0) { away[z] -= 1; here = false; }
+            if (here) { seen.returned += gone_for[z] >= 20; gone_for[z] = 0; act.push_back(z); } else gone_for[z] += 1;
+        }
+        seen.all_absent += act.empty();
+    };
+    std::vector<int> ret_off(S, 0), ret_n(S, 0), ret_off_new, ret_n_new, last_run(S, -1), last_n(S, 0), doff, eoff, table, kept, expect_dl, cur, nxt;
+    std::vector<Row> store, store_new, fresh, out;
+    std::vector<char> w_out, w_store;
+    ddhost::StepPlan pl;
+    draw(cur);
+    for (int step = 0; step < steps; ++step) {
+        draw(nxt);
+        pl.act = cur; pl.act_next = nxt;
+        ddhost::plan_skip(sk, pl);
+        const std::vector<int> &act = pl.act;
+        const int n = (int)act.size();
+        if (step > 0 && pl.dl != expect_dl) fail("the detector streams are not those the step before announced (dl_next)", step);
+        std::vector<int> dl;
+        for (int i = 0; i < n; ++i) { if (!pl.skp[i]) dl.push_back(act[i]); seq[act[i]].push_back(!pl.skp[i]); }
+        if (dl != pl.dl) fail("dl is not the streams of act with skp 0", step);
+        seen.empty_dl += n > 0 && pl.dl.empty();
+
+        kept.resize(n);
+        for (int i = 0; i < n; ++i) kept[i] = r.next() % 6;
+        ddhost::pair_counts(pl.skp, [&](int i) { return kept[i]; }, [&](int i) { return ret_n[act[i]]; }, doff, eoff);
+        const int D = doff[n], E = eoff[n];
+        fresh.assign(E, Row{-1, -1, -1});
+        for (int i = 0; i < n; ++i) if (!pl.skp[i]) for (int j = 0; j < kept[i]; ++j) fresh[eoff[i] + j] = Row{act[i], step, j};
+        const bool refresh = !pl.dl.empty();
+        const ddhost::RowTable rt = ddhost::feature_row_table(S, act, pl.skp, doff, eoff, ret_off, ret_n, refresh, table, ret_off_new, ret_n_new);
+        seen.gathers += rt.gather; seen.refreshes += refresh;
+        if (!refresh && rt.total != 0) fail("a store is written without an encoder run", step);
+        out.assign(D, Row{-1, -1, -1}); store_new.assign(rt.total, Row{-1, -1, -1});
+        w_out.assign(D, 0); w_store.assign(rt.total, 0);
+        for (size_t e = 0; e + 8 <= table.size(); e += 8) {                    // one block of feature_rows_carry_k per entry
+            const int *t = table.data() + e;
+            const int sel = t[0], src = t[1], n_out = t[2], dst = t[3], n_store = t[4], dst2 = t[5], nr = std::max(n_out, n_store);
+            const std::vector<Row> &from = sel ? store : fresh;
+            const bool ok = (sel == 0 || sel == 1) && n_out >= 0 && n_store >= 0 && nr > 0 && src >= 0 && (size_t)src + nr <= from.size() &&
+                            (n_out == 0 || (rt.gather && dst >= 0 && dst + n_out <= D)) && (n_store == 0 || (refresh && dst2 >= 0 && dst2 + n_store <= rt.total));
+            if (!ok) { fail("a table entry's range lies outside its buffer", step); continue; }
+            for (int j = 0; j < n_out; ++j) { if (w_out[dst + j]++) fail("two entries write the same tracker input row", step); out[dst + j] = from[src + j]; }
+            for (int j = 0; j < n_store; ++j) { if (w_store[dst2 + j]++) fail("two entries write the same store row", step); store_new[dst2 + j] = from[src + j]; }
+        }
+        // the tracker's input: the assembled rows, or the encoder's output as it stands
+        const std::vector<Row> &input = rt.gather ? out : fresh;
+        if (!rt.gather && D != E) fail("no gather, but the tracker's rows are not the encoder's", step);
+        for (int i = 0; i < n; ++i) {
+            const int z = act[i], want = pl.skp[i] ? std::min(kept[i], last_n[z]) : kept[i];
+            if (pl.skp[i]) { seen.retained_zero += last_n[z] == 0; seen.kept_over_retained += kept[i] > last_n[z]; }
+            if (doff[i + 1] - doff[i] != want) { fail("a stream's tracker row count", step); continue; }
+            for (int j = 0; j < want; ++j)
+                if (!(input[doff[i] + j] == Row{z, pl.skp[i] ? last_run[z] : step, j})) { fail("a tracker input row is not the stream's own", step); break; }
+        }
+        for (int i = 0; i < n; ++i) if (!pl.skp[i]) { last_run[act[i]] = step; last_n[act[i]] = kept[i]; }
+        if (refresh) { store.swap(store_new); ret_off.swap(ret_off_new); ret_n.swap(ret_n_new); }
+        // the store now: every stream's last run, compact, in stream order
+        size_t pos = 0;
+        for (int z = 0; z < S; ++z) {
+            if (ret_n[z] != last_n[z] || (ret_n[z] > 0 && ret_off[z] != (int)pos) || pos + last_n[z] > store.size()) { fail("the store's offsets", step); break; }
+            for (int j = 0; j < last_n[z]; ++j) if (!(store[pos + j] == Row{z, last_run[z], j})) { fail("a store row is not the stream's last run", step); break; }
+            pos += last_n[z];
+        }
+        if (pos != store.size()) fail("the store's size", step);
+        // commit, as the step does when it has succeeded
+        sk.rem = pl.rem_next; sk.has = pl.has_next;
+        for (int i = 0; i < n; ++i) sk.last[act[i]] = pl.skp[i];
+        expect_dl = pl.dl_next;
+        cur = nxt;
+    }
+    for (int z = 0; z < S; ++z)
+        if (seq[z] != schedule(sk.n[z], sk.phase[z], (int)seq[z].size())) fail("a stream's detector / skip sequence differs from its serial replay", z);
+    return bad;
+}
+
+// dd_pipeline_detector_skip_frames: the same N for every stream, no phase, no mask -- every step is a detector step or a skip step for all
+static long long check_lockstep(int S, int N, int steps) {
+    long long bad = 0;
+    ddhost::SkipCounters sk;
+    sk.start(S, N);
+    ddhost::StepPlan pl;
+    for (int z = 0; z < S; ++z) { pl.act.push_back(z); pl.act_next.push_back(z); }
+    for (int step = 0; step < steps; ++step) {
+        ddhost::plan_skip(sk, pl);
+        const bool det = step % (N + 1) == 0, det_next = (step + 1) % (N + 1) == 0;
+        bad += pl.dl.size() != (det ? (size_t)S : 0) || pl.dl_next.size() != (det_next ? (size_t)S : 0);
+        for (int z = 0; z < S; ++z) bad += pl.skp[z] != !det;
+        sk.rem = pl.rem_next; sk.has = pl.has_next;
+    }
+    return bad;
+}
+
 int main(int argc, char **argv) {
     const int groups = 4, S = 384, steps = argc > 1 ? atoi(argv[1]) : 300;
     std::atomic<long long> bad{0};
+    Seen seen;
+    for (int s : {1, 3, 7}) for (int rep = 0; rep < 4; ++rep) bad += check_step_plans(s, 977 * s + rep, 400, seen);
+    for (int N = 0; N < 4; ++N) bad += check_lockstep(5, N, 40);
+    if (!(seen.all_absent && seen.returned && seen.empty_dl && seen.retained_zero && seen.kept_over_retained && seen.gathers && seen.refreshes)) {
+        fprintf(stderr, "host harness: a case the step-plan check is there for never occurred\n");
+        bad++;
+    }
     std::vector<std::thread> th;
     for (int g = 0; g < groups; ++g)
         th.emplace_back([&, g] {
