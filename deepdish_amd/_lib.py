@@ -146,6 +146,13 @@ SIGNATURES = {
     'dd_pipeline_stream_motion_ratio': [P, P],
     'dd_pipeline_reset_streams': [P, P, c_int],
     'dd_pipeline_stream_param_stats': [P, P],
+    'dd_pipeline_snapshot_bytes': [P, P, c_int, c_int, POINTER(c_int64)],
+    'dd_pipeline_snapshot': [P, P, c_int, c_int, P, c_int64, POINTER(c_int64)],
+    'dd_pipeline_restore': [P, P, c_int64, P, c_int],
+    'dd_snapshot_info': [P, c_int64, POINTER(c_int), P, c_int],
+    'dd_tracker_gallery_read': [P, c_int64, P, c_int, POINTER(c_int), POINTER(c_int)],
+    'dd_chunk_rows_gather': [P, P, c_int, c_int64, P, c_int, P, c_int, P, c_int64, P],
+    'dd_chunk_rows_scatter': [P, P, c_int, c_int64, P, c_int, P, c_int, P, c_int64, P],
     'dd_pipeline_mog2': [P, POINTER(P)],
     'dd_mog2_reset_streams': [P, P, c_int, P],
     'dd_feature_rows_carry': [P, P, c_int64, P, c_int64, P, c_int64, P, c_int64, P, c_int, P],

@@ -221,6 +221,27 @@ int trackers_update_begin(dd_tracker **ts, int S, const double *tlwh_host, const
 int trackers_update_match(dd_tracker **ts, int S);
 int trackers_update_end(dd_tracker **ts, int S);
 int tracker_read_host(dd_tracker *t, int which, int64_t *ints6_host, double *means_host);
+// stream snapshots: one tracker's tables out (tracker_export) and in (reserve, then import, then flush), and the gallery kernels (snapshot.hip)
+struct TrackerPoolView {
+    float *const *d_arenas;
+    double *d_means, *d_covs, max_cos, max_iou;
+    int arena_shift, metric, budget, tcap, max_age, n_init;
+    bool upd_inflight;
+};
+struct TrackView { int64_t id; int state, tsu, hits, age, last_det, slot, slot_total, n_rows, n_chunks; const int *chunks; };
+struct TrackLoad { int64_t id; int state, tsu, hits, age, last_det, slot_total, n_rows; const double *mean; };
+void tracker_pool_view(dd_tracker *t, TrackerPoolView *v);
+int tracker_export(dd_tracker *t, int64_t *next_id, std::vector<TrackView> &live, std::vector<TrackView> &dead);
+int tracker_pool_reserve_chunks(dd_tracker *any, size_t n);
+int tracker_import(dd_tracker *t, int64_t next_id, const TrackLoad *tracks, int n_live, int n_dead, std::vector<int> &slots_out,
+                   std::vector<int> &chunks_out);
+int tracker_gallery_flush(dd_tracker *any, hipStream_t s);
+int chunk_rows_gather(hipStream_t s, float *const *d_arenas, int arena_shift, const int *d_chunks, const int *d_table, int n_entries,
+                      float *dense, const double *means, const double *covs, double *state);
+int chunk_rows_scatter(hipStream_t s, float *const *d_arenas, int arena_shift, const int *d_chunks, const int *d_table, int n_entries,
+                       const float *dense, double *means, double *covs, const double *state);
+int mog2_stream_planes(dd_mog2 *m, int stream, void **rec, void **m2, void **nm, long long **nframes, int *history, float *var_threshold,
+                       int *detect_shadows);
 void pyset_difference_order(const std::vector<int> &a, const std::vector<int> &b, std::vector<int> &out);
 int lsap(const double *cost, int nr, int nc, int *rows, int *cols);   // host; returns pair count or -1
 int gather_state(hipStream_t s, const double *means, const double *covs, const int *slots, int n,

@@ -286,6 +286,22 @@ int mog2_reset_streams(dd_mog2 *m, hipStream_t s, const int *streams_host, int n
     return DD_OK;
 }
 
+// One stream's model for a snapshot: its rec [5][P] float4, m2 [5][P] f32 and nm [P] u8 planes (each contiguous per stream), its frame
+// count and the settings of the subtractor.
+int mog2_stream_planes(dd_mog2 *m, int stream, void **rec, void **m2, void **nm, long long **nframes, int *history, float *var_threshold,
+                       int *detect_shadows) {
+    DD_REQUIRE(m && stream >= 0 && stream < m->S, DD_E_ARG, "mog2_stream_planes: stream %d", stream);
+    const size_t hw = (size_t)m->H * m->W;
+    if (rec) *rec = m->rec + (size_t)stream * NMIX * hw;
+    if (m2) *m2 = m->m2 + (size_t)stream * NMIX * hw;
+    if (nm) *nm = m->nm + (size_t)stream * hw;
+    if (nframes) *nframes = &m->nframes[stream];
+    if (history) *history = m->history;
+    if (var_threshold) *var_threshold = m->var_threshold;
+    if (detect_shadows) *detect_shadows = m->detect_shadows;
+    return DD_OK;
+}
+
 int mask_box_count(hipStream_t s, const uint8_t *mask, int H, int W, const int *d_boxes, const int *d_box_stream, int K, int *d_counts) {
     if (K <= 0) return DD_OK;
     hipLaunchKernelGGL(mask_box_count_k, dim3((unsigned)K), dim3(256), 0, s, mask, H, W, d_boxes, d_box_stream, d_counts);

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "hostpool.h"
 #include "host_phases.h"
+#include "snapshot_fmt.h"
 
 namespace {
 
@@ -1573,6 +1574,397 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
     p->g_wall += 1e3 * (t4 - t0); p->g_host += 1e3 * ((t4 - t0) - p->step_wait);
     phase_commit(p, pl);
     return DD_OK;
+}
+
+}  // extern "C"
+
+// ---------------- stream snapshots (include/deepdish_hip.h; the blob: csrc/snapshot_fmt.h; the gallery kernels: csrc/snapshot.hip)
+namespace {
+
+// What a stream's entry records of its parameters, and what restore compares the destination's with
+ddsnap::Params stream_params(const dd_pipeline *p, int z) {
+    ddsnap::Params q;
+    ddk::TrackerPoolView tv;
+    ddk::tracker_pool_view(p->trks[z], &tv);
+    q.H = p->H; q.W = p->W; q.feat_len = 128; q.metric = tv.metric; q.nn_budget = tv.budget;
+    q.det_kind = p->det_kind; q.max_det = p->max_det; q.n_labels = (int32_t)p->labels.size(); q.label_offset = p->label_offset;
+    uint64_t h = ddsnap::fnv1a(nullptr, 0);
+    for (const std::string &l : p->labels) { h = ddsnap::fnv1a(l.data(), l.size(), h); h = ddsnap::fnv1a("\n", 1, h); }
+    q.labels_hash = h;
+    memcpy(q.line, p->lines.data() + (size_t)z * 4, sizeof q.line);
+    q.max_age = tv.max_age; q.n_init = tv.n_init; q.max_cos = tv.max_cos; q.max_iou = tv.max_iou; q.nms = p->nms_of[z];
+    if (p->mog2) {
+        q.mog_on = 1; q.ratio = p->ratio_of[z]; q.masking = p->bg_masking;
+        ddk::mog2_stream_planes(p->mog2, z, nullptr, nullptr, nullptr, nullptr, &q.mog_history, &q.mog_var_thr, &q.mog_shadows);
+    }
+    q.skip_form = p->skip_streams; q.skip_n = p->sk.n[z]; q.skip_phase = p->sk.phase[z];
+    for (size_t i = 0; i < p->wanted.size(); ++i) if (p->wanted_of[(size_t)z * p->wanted.size() + i]) q.wanted.push_back(p->wanted[i]);
+    return q;
+}
+
+// the first parameter of the source stream (a) that differs from the destination's (b); NULL: none.  Floats by bit pattern.
+const char *params_differ(const ddsnap::Params &a, const ddsnap::Params &b) {
+    const auto bits = [](const void *x, const void *y, size_t n) { return memcmp(x, y, n) != 0; };
+    if (a.H != b.H) return "H";
+    if (a.W != b.W) return "W";
+    if (a.feat_len != b.feat_len) return "feature length";
+    if (a.metric != b.metric) return "metric";
+    if (a.nn_budget != b.nn_budget) return "nn_budget";
+    if (a.det_kind != b.det_kind) return "detector kind";
+    if (a.max_det != b.max_det) return "max_det";
+    if (a.labels_hash != b.labels_hash || a.n_labels != b.n_labels || a.label_offset != b.label_offset) return "labels";
+    {
+        std::vector<std::string> x = a.wanted, y = b.wanted;
+        std::sort(x.begin(), x.end()); std::sort(y.begin(), y.end());
+        if (x != y) return "wanted labels";
+    }
+    if (bits(a.line, b.line, sizeof a.line)) return "line";
+    if (a.max_age != b.max_age) return "max_age";
+    if (a.n_init != b.n_init) return "n_init";
+    if (bits(&a.max_cos, &b.max_cos, 8)) return "max_cosine_distance";
+    if (bits(&a.max_iou, &b.max_iou, 8)) return "max_iou_distance";
+    if (bits(&a.nms, &b.nms, 8)) return "nms_max_overlap";
+    if (a.mog_on != b.mog_on || bits(&a.ratio, &b.ratio, 8)) return "background_subtraction_ratio";
+    if (a.masking != b.masking) return "background_masking";
+    if (a.mog_history != b.mog_history) return "MOG2 history";
+    if (bits(&a.mog_var_thr, &b.mog_var_thr, 4)) return "MOG2 varThreshold";
+    if (a.mog_shadows != b.mog_shadows) return "MOG2 detect_shadows";
+    if (a.skip_form != b.skip_form || a.skip_n != b.skip_n) return "object_detector_skip_frames";
+    if (a.skip_phase != b.skip_phase) return "object_detector_skip_phase";
+    return nullptr;
+}
+
+int snapshot_streams(const dd_pipeline *p, const char *name, const int *streams_host, int n, std::vector<int> &zs) {
+    DD_REQUIRE(p && n >= 0 && n <= p->S, DD_E_ARG, "%s: bad argument (n = %d)", name, n);
+    zs.resize(n);
+    std::vector<uint8_t> listed(p->S, 0);
+    for (int i = 0; i < n; ++i) {
+        const int z = streams_host ? streams_host[i] : i;
+        DD_REQUIRE(z >= 0 && z < p->S, DD_E_ARG, "%s: stream %d of %d", name, z, p->S);
+        DD_REQUIRE(!listed[z], DD_E_ARG, "%s: stream %d is listed twice", name, z);
+        listed[z] = 1;
+        zs[i] = z;
+    }
+    DD_REQUIRE(!p->skip_lockstep, DD_E_STATE, "%s: the pipeline has the pipeline-wide object_detector_skip_frames counter (dd_pipeline_detector_skip_frames): "
+               "one counter for all streams cannot continue one stream's cycle; dd_pipeline_detector_skip_streams (a sequence of N) has one per stream", name);
+    ddk::TrackerPoolView tv;
+    ddk::tracker_pool_view(p->trks[0], &tv);
+    DD_REQUIRE(!tv.upd_inflight, DD_E_STATE, "%s: an update of the tracker group is in flight", name);
+    return DD_OK;
+}
+
+// The host half of a snapshot: every listed stream's entry but for means, covariances and the bulk sections, and the track views
+// (slots and chunk lists) the gather table is built from.
+int snapshot_collect(dd_pipeline *p, const std::vector<int> &zs, int background, std::vector<ddsnap::Entry> &es, std::vector<std::vector<ddk::TrackView>> &views) {
+    es.assign(zs.size(), ddsnap::Entry());
+    views.assign(zs.size(), std::vector<ddk::TrackView>());
+    std::vector<ddk::TrackView> dead;
+    for (size_t i = 0; i < zs.size(); ++i) {
+        const int z = zs[i];
+        const StreamState &st = p->st[z];
+        ddsnap::Entry &e = es[i];
+        e.par = stream_params(p, z);
+        for (const std::string &w : e.par.wanted) {
+            const int wi = wanted_index(p, z, w);
+            e.counts.insert(e.counts.end(), st.counts.begin() + (size_t)wi * 4, st.counts.begin() + (size_t)wi * 4 + 4);
+        }
+        e.seen = st.seen; e.rem = p->sk.rem[z]; e.has = p->sk.has[z]; e.last = p->sk.last[z];
+        e.det_cls.assign(st.det_cls.begin(), st.det_cls.end()); e.det_conf = st.det_conf; e.det_tlwh = st.det_tlwh;
+        e.boxes0 = st.boxes0; e.scores0 = st.scores0; e.cls0.assign(st.cls0.begin(), st.cls0.end());
+        int rc;
+        if ((rc = ddk::tracker_export(st.trk, &e.next_id, views[i], dead)) != DD_OK) return rc;
+        e.n_live = (int32_t)views[i].size(); e.n_dead = (int32_t)dead.size();
+        views[i].insert(views[i].end(), dead.begin(), dead.end());
+        e.tracks.resize(views[i].size());
+        for (size_t k = 0; k < views[i].size(); ++k) {
+            const ddk::TrackView &v = views[i][k];
+            ddsnap::Track &t = e.tracks[k];
+            t.id = v.id; t.state = v.state; t.tsu = v.tsu; t.hits = v.hits; t.age = v.age; t.last_det = v.last_det; t.slot_total = v.slot_total; t.n_rows = v.n_rows;
+            e.gallery_rows += (uint64_t)v.n_rows;
+        }
+        for (const auto &kv : st.db) {
+            if (kv.second.empty()) continue;
+            ddsnap::Path q;
+            q.id = kv.first;
+            for (const auto &pt : kv.second) { q.xy.push_back(pt.first); q.xy.push_back(pt.second); }
+            e.paths.push_back(std::move(q));
+        }
+        for (const auto &kv : st.votes) {
+            if (kv.second.cls.empty()) continue;
+            ddsnap::Vote v;
+            v.id = kv.first; v.cls.assign(kv.second.cls.begin(), kv.second.cls.end()); v.cnt.assign(kv.second.cnt.begin(), kv.second.cnt.end()); v.sum = kv.second.sum;
+            e.votes.push_back(std::move(v));
+        }
+        e.n_ret = p->skip_streams ? p->ret_n[z] : 0;
+        e.has_bg = background && p->mog2;
+        if (e.has_bg) {
+            long long *nf = nullptr;
+            ddk::mog2_stream_planes(p->mog2, z, nullptr, nullptr, nullptr, &nf, nullptr, nullptr, nullptr);
+            e.nframes = *nf;
+        }
+    }
+    return DD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dd_pipeline_snapshot_bytes(dd_pipeline *p, const int *streams_host, int n, int background, int64_t *bytes_host) {
+    DD_REQUIRE(p && bytes_host, DD_E_ARG, "dd_pipeline_snapshot_bytes: NULL argument");
+    std::vector<int> zs;
+    int rc;
+    if ((rc = snapshot_streams(p, "dd_pipeline_snapshot_bytes", streams_host, n, zs)) != DD_OK) return rc;
+    std::vector<ddsnap::Entry> es;
+    std::vector<std::vector<ddk::TrackView>> views;
+    if ((rc = snapshot_collect(p, zs, background, es, views)) != DD_OK) return rc;
+    uint64_t total = ddsnap::header_bytes((uint32_t)n);
+    for (const ddsnap::Entry &e : es) total += ddsnap::write_entry(e, nullptr);
+    *bytes_host = (int64_t)total;
+    return DD_OK;
+}
+
+int dd_pipeline_snapshot(dd_pipeline *p, const int *streams_host, int n, int background, uint8_t *blob_host, int64_t cap, int64_t *bytes_host) {
+    DD_REQUIRE(p && blob_host && bytes_host, DD_E_ARG, "dd_pipeline_snapshot: NULL argument");
+    std::vector<int> zs;
+    int rc;
+    if ((rc = snapshot_streams(p, "dd_pipeline_snapshot", streams_host, n, zs)) != DD_OK) return rc;
+    std::vector<ddsnap::Entry> es;
+    std::vector<std::vector<ddk::TrackView>> views;
+    if ((rc = snapshot_collect(p, zs, background, es, views)) != DD_OK) return rc;
+    std::vector<uint64_t> sizes(n);
+    uint64_t total = ddsnap::header_bytes((uint32_t)n);
+    for (int i = 0; i < n; ++i) { sizes[i] = ddsnap::write_entry(es[i], nullptr); total += sizes[i]; }
+    DD_REQUIRE((uint64_t)cap >= total, DD_E_CAPACITY, "dd_pipeline_snapshot: %llu bytes, room for %lld", (unsigned long long)total, (long long)cap);
+    DD_DEVICE(p->ctx);
+    hipStream_t s = p->ctx->stream;
+    DD_HIP(hipStreamSynchronize(s));                              // between steps: the main stream is idle from here on, the detector stream is not touched
+    // ---- the gather table: one entry per track {offset of its chunk list, rows, first dense row, slot}; dense = [rows][36 units per track]
+    std::vector<int> table, chunks;
+    uint64_t rows = 0;
+    for (int i = 0; i < n; ++i)
+        for (const ddk::TrackView &v : views[i]) {
+            const int e[4] = {(int)chunks.size(), v.n_rows, (int)rows, v.slot};
+            table.insert(table.end(), e, e + 4);
+            chunks.insert(chunks.end(), v.chunks, v.chunks + v.n_chunks);
+            rows += (uint64_t)v.n_rows;
+        }
+    DD_REQUIRE(rows < (1ull << 31), DD_E_CAPACITY, "dd_pipeline_snapshot: %llu gallery rows in one snapshot; list fewer streams", (unsigned long long)rows);
+    const size_t nt = table.size() / 4;
+    DevBuf d_dense, d_tab;
+    PinBuf h_tab;
+    const auto done = [&](int r) { d_dense.release(); d_tab.release(); h_tab.release(); return r; };
+    if (nt > 0) {
+        ddk::TrackerPoolView tv;
+        ddk::tracker_pool_view(p->trks[0], &tv);
+        const size_t b_tab = table.size() * sizeof(int), b_ch = chunks.size() * sizeof(int), b_rows = (size_t)rows * 512, b_state = nt * 576;
+        if ((rc = d_dense.reserve(b_rows + b_state)) != DD_OK || (rc = d_tab.reserve(b_tab + b_ch)) != DD_OK ||
+            (rc = h_tab.reserve(std::max(b_tab + b_ch, b_state))) != DD_OK) return done(rc);
+        memcpy(h_tab.p, table.data(), b_tab);
+        if (b_ch) memcpy(h_tab.as<char>() + b_tab, chunks.data(), b_ch);
+        hipError_t he = hipMemcpyAsync(d_tab.p, h_tab.p, b_tab + b_ch, hipMemcpyHostToDevice, s);
+        if (he != hipSuccess) { dd_set_error("dd_pipeline_snapshot: table upload -> %s", hipGetErrorString(he)); return done(DD_E_HIP); }
+        double *d_state = reinterpret_cast<double *>(d_dense.as<char>() + b_rows);
+        if ((rc = ddk::chunk_rows_gather(s, tv.d_arenas, tv.arena_shift, reinterpret_cast<const int *>(d_tab.as<char>() + b_tab), d_tab.as<int>(), (int)nt,
+                                         d_dense.as<float>(), tv.d_means, tv.d_covs, d_state)) != DD_OK) return done(rc);
+        he = hipStreamSynchronize(s);                             // (the table has been read: h_tab now takes the state block)
+        if (he == hipSuccess) he = hipMemcpyAsync(h_tab.p, d_state, b_state, hipMemcpyDeviceToHost, s);
+        if (he == hipSuccess) he = hipStreamSynchronize(s);
+        if (he != hipSuccess) { dd_set_error("dd_pipeline_snapshot: gather -> %s", hipGetErrorString(he)); return done(DD_E_HIP); }
+        const double *hs = h_tab.as<double>();
+        size_t k = 0;
+        for (int i = 0; i < n; ++i)
+            for (ddsnap::Track &t : es[i].tracks) { memcpy(t.mean, hs + k * 72, sizeof t.mean); memcpy(t.cov, hs + k * 72 + 8, sizeof t.cov); ++k; }
+    }
+    // ---- the blob: header, then per entry its host part; the bulk sections come straight from the device
+    ddsnap::write_header(blob_host, sizes);
+    uint64_t at = ddsnap::header_bytes((uint32_t)n), row0 = 0;
+    const size_t hw = (size_t)p->H * p->W;
+    hipError_t he = hipSuccess;
+    for (int i = 0; i < n && he == hipSuccess; ++i) {
+        uint64_t off[3] = {0, 0, 0};
+        ddsnap::write_entry(es[i], blob_host + at, off);
+        const ddsnap::Entry &e = es[i];
+        const int z = zs[i];
+        if (e.gallery_rows) he = hipMemcpyAsync(blob_host + at + off[0], d_dense.as<char>() + row0 * 512, e.gallery_rows * 512, hipMemcpyDeviceToHost, s);
+        row0 += e.gallery_rows;
+        if (e.n_ret && he == hipSuccess)
+            he = hipMemcpyAsync(blob_host + at + off[1], p->d_store[p->store_cur].as<char>() + (size_t)p->ret_off[z] * 512, (size_t)e.n_ret * 512, hipMemcpyDeviceToHost, s);
+        if (e.has_bg) {
+            void *rec = nullptr, *m2 = nullptr, *nm = nullptr;
+            ddk::mog2_stream_planes(p->mog2, z, &rec, &m2, &nm, nullptr, nullptr, nullptr, nullptr);
+            uint8_t *o = blob_host + at + off[2];
+            const void *src[4] = {rec, m2, nm, p->d_mask.as<uint8_t>() + (size_t)z * hw};
+            const size_t len[4] = {hw * 80, hw * 20, hw, hw};
+            for (int k = 0; k < 4 && he == hipSuccess; ++k) { he = hipMemcpyAsync(o, src[k], len[k], hipMemcpyDeviceToHost, s); o += len[k]; }
+        }
+        at += sizes[i];
+    }
+    if (he == hipSuccess) he = hipStreamSynchronize(s);
+    if (he != hipSuccess) { dd_set_error("dd_pipeline_snapshot: copy to the host -> %s", hipGetErrorString(he)); return done(DD_E_HIP); }
+    *bytes_host = (int64_t)total;
+    return done(DD_OK);
+}
+
+int dd_snapshot_info(const uint8_t *blob_host, int64_t n_bytes, int *n_entries_host, int64_t *info_host, int cap_entries) {
+    DD_REQUIRE(blob_host && n_bytes >= 0 && n_entries_host, DD_E_ARG, "dd_snapshot_info: bad argument");
+    std::vector<ddsnap::Entry> es;
+    std::vector<std::pair<uint64_t, uint64_t>> table;
+    std::string err;
+    DD_REQUIRE(ddsnap::parse_blob(blob_host, (uint64_t)n_bytes, es, table, err), DD_E_ARG, "dd_snapshot_info: the blob is refused: %s", err.c_str());
+    *n_entries_host = (int)es.size();
+    if (!info_host) return DD_OK;
+    DD_REQUIRE(cap_entries >= (int)es.size(), DD_E_ARG, "dd_snapshot_info: %zu entries, room for %d", es.size(), cap_entries);
+    for (size_t i = 0; i < es.size(); ++i) {
+        int64_t *o = info_host + i * 8;
+        o[0] = es[i].seen; o[1] = es[i].n_live + es[i].n_dead; o[2] = es[i].next_id; o[3] = (int64_t)es[i].gallery_rows; o[4] = es[i].has_bg;
+        o[5] = (int64_t)table[i].second; o[6] = (int64_t)table[i].first; o[7] = 0;
+    }
+    return DD_OK;
+}
+
+int dd_pipeline_restore(dd_pipeline *p, const uint8_t *blob_host, int64_t n_bytes, const int *streams_host, int n) {
+    DD_REQUIRE(p && blob_host && n_bytes >= 0, DD_E_ARG, "dd_pipeline_restore: bad argument");
+    // ---- everything that can be refused, before anything changes
+    std::vector<ddsnap::Entry> es;
+    std::vector<std::pair<uint64_t, uint64_t>> table;
+    std::string err;
+    DD_REQUIRE(ddsnap::parse_blob(blob_host, (uint64_t)n_bytes, es, table, err), DD_E_ARG, "dd_pipeline_restore: the blob is refused: %s", err.c_str());
+    DD_REQUIRE(n == (int)es.size(), DD_E_ARG, "dd_pipeline_restore: %d streams for a snapshot of %zu entries", n, es.size());
+    std::vector<int> zs;
+    int rc;
+    if ((rc = snapshot_streams(p, "dd_pipeline_restore", streams_host, n, zs)) != DD_OK) return rc;
+    size_t need_chunks = 0, nt = 0, ret_add = 0;
+    uint64_t rows = 0;
+    for (int i = 0; i < n; ++i) {
+        const ddsnap::Entry &e = es[i];
+        const ddsnap::Params dst = stream_params(p, zs[i]);
+        const char *what = params_differ(e.par, dst);
+        DD_REQUIRE(!what, DD_E_ARG, "dd_pipeline_restore: entry %d -> stream %d: %s differs between the snapshot's stream and the destination "
+                   "(parameters are checked, not carried)", i, zs[i], what);
+        DD_REQUIRE(!e.has_bg || p->mog2, DD_E_ARG, "dd_pipeline_restore: entry %d carries a background model and subtraction is off", i);
+        ddk::TrackerPoolView tv;
+        ddk::tracker_pool_view(p->trks[zs[i]], &tv);
+        DD_REQUIRE(e.n_live + e.n_dead <= tv.tcap, DD_E_CAPACITY, "dd_pipeline_restore: entry %d has %d tracks, track_capacity of stream %d is %d", i,
+                   e.n_live + e.n_dead, zs[i], tv.tcap);
+        for (const ddsnap::Track &t : e.tracks) need_chunks += (size_t)((t.n_rows + 31) / 32);
+        nt += e.tracks.size();
+        rows += e.gallery_rows;
+        ret_add += (size_t)e.n_ret;
+    }
+    DD_REQUIRE(rows < (1ull << 31), DD_E_CAPACITY, "dd_pipeline_restore: %llu gallery rows in one call; restore fewer entries at a time", (unsigned long long)rows);
+    if (n == 0) return DD_OK;
+    DD_DEVICE(p->ctx);
+    hipStream_t s = p->ctx->stream;
+    // ---- reserve: gallery chunks, staging, the retained-rows store -- a failure here gives back what it took
+    if ((rc = ddk::tracker_pool_reserve_chunks(p->trks[0], need_chunks)) != DD_OK) return rc;
+    DevBuf d_dense, d_tab, d_store_new;
+    PinBuf h_tab;
+    const auto done = [&](int r) { d_dense.release(); d_tab.release(); h_tab.release(); d_store_new.release(); return r; };
+    const size_t b_tab = nt * 4 * sizeof(int), b_ch = need_chunks * sizeof(int), b_rows = (size_t)rows * 512, b_state = nt * 576;
+    const size_t o_state = (b_tab + b_ch + 15) / 16 * 16;
+    if (nt > 0 && ((rc = d_dense.reserve(b_rows + b_state)) != DD_OK || (rc = d_tab.reserve(b_tab + b_ch)) != DD_OK ||
+                   (rc = h_tab.reserve(o_state + b_state)) != DD_OK)) return done(rc);
+    std::vector<uint8_t> listed(p->S, 0);
+    for (int z : zs) listed[z] = 1;
+    int ret_end = 0;                                             // rows of the current store the other streams use
+    if (p->skip_streams) for (int z = 0; z < p->S; ++z) if (!listed[z] && p->ret_n[z] > 0) ret_end = std::max(ret_end, p->ret_off[z] + p->ret_n[z]);
+    const bool store_grows = ret_add > 0 && ((size_t)ret_end + ret_add) * 512 > p->d_store[p->store_cur].cap;
+    if (store_grows && (rc = d_store_new.reserve(((size_t)ret_end + ret_add) * 512)) != DD_OK) return done(rc);
+    DD_HIP(hipStreamSynchronize(s));
+    // ---- commit: as dd_pipeline_reset_streams, then the state
+    hipError_t he = hipSuccess;
+    if (store_grows) {
+        if (ret_end) he = hipMemcpyAsync(d_store_new.p, p->d_store[p->store_cur].p, (size_t)ret_end * 512, hipMemcpyDeviceToDevice, s);
+        if (he == hipSuccess) he = hipStreamSynchronize(s);
+        if (he != hipSuccess) { dd_set_error("dd_pipeline_restore: store copy -> %s", hipGetErrorString(he)); return done(DD_E_HIP); }
+        std::swap(p->d_store[p->store_cur], d_store_new);         // (the old buffer is released with d_store_new)
+    }
+    if (p->mog2) {
+        if ((rc = ddk::mog2_reset_streams(p->mog2, s, zs.data(), n)) != DD_OK) return done(rc);
+        const size_t hw = (size_t)p->H * p->W;
+        for (int z : zs) if (hipMemsetAsync(p->d_mask.as<uint8_t>() + (size_t)z * hw, 0, hw, s) != hipSuccess) { dd_set_error("dd_pipeline_restore: memset failed"); return done(DD_E_HIP); }
+    }
+    std::vector<int> slots, chunks;
+    std::vector<ddk::TrackLoad> loads;
+    for (int i = 0; i < n; ++i) {
+        const ddsnap::Entry &e = es[i];
+        loads.clear();
+        for (const ddsnap::Track &t : e.tracks) loads.push_back({t.id, t.state, t.tsu, t.hits, t.age, t.last_det, t.slot_total, t.n_rows, t.mean});
+        if ((rc = ddk::tracker_import(p->trks[zs[i]], e.next_id, loads.data(), e.n_live, e.n_dead, slots, chunks)) != DD_OK) return done(rc);
+    }
+    if (nt > 0) {
+        int *ht = h_tab.as<int>(), *hc = ht + nt * 4;
+        double *hs = reinterpret_cast<double *>(h_tab.as<char>() + o_state);
+        size_t k = 0, c0 = 0, r0 = 0;
+        for (int i = 0; i < n; ++i)
+            for (const ddsnap::Track &t : es[i].tracks) {
+                int *e4 = ht + k * 4;
+                e4[0] = (int)c0; e4[1] = t.n_rows; e4[2] = (int)r0; e4[3] = slots[k];
+                memcpy(hs + k * 72, t.mean, sizeof t.mean); memcpy(hs + k * 72 + 8, t.cov, sizeof t.cov);
+                c0 += (size_t)((t.n_rows + 31) / 32); r0 += (size_t)t.n_rows; ++k;
+            }
+        if (b_ch) memcpy(hc, chunks.data(), b_ch);
+        double *d_state = reinterpret_cast<double *>(d_dense.as<char>() + b_rows);
+        he = hipMemcpyAsync(d_tab.p, ht, b_tab + b_ch, hipMemcpyHostToDevice, s);
+        if (he == hipSuccess) he = hipMemcpyAsync(d_state, hs, b_state, hipMemcpyHostToDevice, s);
+        size_t at_row = 0;
+        for (int i = 0; i < n && he == hipSuccess; ++i) {
+            if (es[i].gallery_rows) he = hipMemcpyAsync(d_dense.as<char>() + at_row * 512, es[i].gallery, es[i].gallery_rows * 512, hipMemcpyHostToDevice, s);
+            at_row += es[i].gallery_rows;
+        }
+        if (he != hipSuccess) { dd_set_error("dd_pipeline_restore: upload -> %s", hipGetErrorString(he)); return done(DD_E_HIP); }
+        ddk::TrackerPoolView tv;
+        ddk::tracker_pool_view(p->trks[0], &tv);
+        if ((rc = ddk::chunk_rows_scatter(s, tv.d_arenas, tv.arena_shift, reinterpret_cast<const int *>(d_tab.as<char>() + b_tab), d_tab.as<int>(), (int)nt,
+                                          d_dense.as<float>(), tv.d_means, tv.d_covs, d_state)) != DD_OK) return done(rc);
+    }
+    if ((rc = ddk::tracker_gallery_flush(p->trks[0], s)) != DD_OK) return done(rc);
+    const size_t hw = (size_t)p->H * p->W;
+    int ret_at = ret_end;
+    for (int i = 0; i < n; ++i) {
+        const ddsnap::Entry &e = es[i];
+        const int z = zs[i];
+        StreamState &st = p->st[z];
+        st.restart(p->wanted.size());
+        for (size_t k = 0; k < e.par.wanted.size(); ++k) {
+            const int wi = wanted_index(p, z, e.par.wanted[k]);
+            for (int c = 0; c < 4; ++c) st.counts[(size_t)wi * 4 + c] = e.counts[k * 4 + c];
+        }
+        st.seen = e.seen;
+        st.det_cls.assign(e.det_cls.begin(), e.det_cls.end()); st.det_conf = e.det_conf; st.det_tlwh = e.det_tlwh;
+        st.boxes0 = e.boxes0; st.scores0 = e.scores0; st.cls0.assign(e.cls0.begin(), e.cls0.end());
+        for (const ddsnap::Path &q : e.paths) {
+            auto &pts = st.db[q.id];
+            for (size_t k = 0; k + 1 < q.xy.size(); k += 2) pts.emplace_back(q.xy[k], q.xy[k + 1]);
+        }
+        for (const ddsnap::Vote &v : e.votes) {
+            Votes &w = st.votes[v.id];
+            w.cls.assign(v.cls.begin(), v.cls.end()); w.cnt.assign(v.cnt.begin(), v.cnt.end()); w.sum = v.sum;
+        }
+        p->sk.rem[z] = e.rem; p->sk.has[z] = e.has; p->sk.last[z] = e.last;
+        if (p->skip_streams) {
+            p->rows_retained += e.n_ret - p->ret_n[z];
+            p->ret_off[z] = e.n_ret ? ret_at : 0; p->ret_n[z] = e.n_ret;
+            if (e.n_ret && he == hipSuccess)
+                he = hipMemcpyAsync(p->d_store[p->store_cur].as<char>() + (size_t)ret_at * 512, e.ret_rows, (size_t)e.n_ret * 512, hipMemcpyHostToDevice, s);
+            ret_at += e.n_ret;
+        }
+        if (e.has_bg) {
+            void *rec = nullptr, *m2 = nullptr, *nm = nullptr;
+            long long *nf = nullptr;
+            ddk::mog2_stream_planes(p->mog2, z, &rec, &m2, &nm, &nf, nullptr, nullptr, nullptr);
+            *nf = e.nframes;
+            const uint8_t *o = e.bg;
+            void *dst[4] = {rec, m2, nm, p->d_mask.as<uint8_t>() + (size_t)z * hw};
+            const size_t len[4] = {hw * 80, hw * 20, hw, hw};
+            for (int k = 0; k < 4 && he == hipSuccess; ++k) { he = hipMemcpyAsync(dst[k], o, len[k], hipMemcpyHostToDevice, s); o += len[k]; }
+        }
+    }
+    p->det_pending = nullptr;                                     // as after a reset: the next step runs the detector itself
+    if (he == hipSuccess) he = hipStreamSynchronize(s);           // the blob and the staging buffers are the caller's / released below
+    if (he != hipSuccess) { dd_set_error("dd_pipeline_restore: copy to the device -> %s", hipGetErrorString(he)); return done(DD_E_HIP); }
+    return done(DD_OK);
 }
 
 }  // extern "C"

@@ -831,9 +831,130 @@ int tracker_read_host(dd_tracker *t, int which, int64_t *ints6_host, double *mea
     return DD_OK;
 }
 
+// ---- stream snapshots (dd_pipeline_snapshot / dd_pipeline_restore): one tracker's tables out, and in again.  Slot and chunk numbers are
+// not state: an import hands out fresh ones, and only the ORDER of tracks, of the rows inside a gallery and the sample count are kept.
+
+void tracker_pool_view(dd_tracker *t, TrackerPoolView *v) {
+    TrackerPool *p = t->pool;
+    v->d_arenas = p->d_arenas; v->d_means = p->d_means; v->d_covs = p->d_covs;
+    v->arena_shift = GAL_ARENA_SHIFT; v->metric = p->metric; v->budget = t->budget; v->tcap = t->tcap;
+    v->max_cos = t->max_cos; v->max_iou = t->max_iou; v->max_age = t->max_age; v->n_init = t->n_init;
+    v->upd_inflight = p->upd_inflight;
+}
+
+// live tracks, then the deleted list of the last update (their slots and chunk lists are intact until the next predict)
+int tracker_export(dd_tracker *t, int64_t *next_id, std::vector<TrackView> &live, std::vector<TrackView> &dead) {
+    TrackerPool *p = t->pool;
+    DD_REQUIRE(t->live_means.size() == t->tracks.size() * 8 && t->dead_means.size() == t->deleted.size() * 8, DD_E_STATE,
+               "snapshot: the tracker's means are not mirrored (between a per-track call and the next update)");
+    *next_id = t->next_id;
+    for (int which = 0; which < 2; ++which) {
+        const std::vector<TrackRec> &v = which == 0 ? t->tracks : t->deleted;
+        std::vector<TrackView> &out = which == 0 ? live : dead;
+        out.clear();
+        for (const TrackRec &tr : v) {
+            TrackView w;
+            w.id = tr.id; w.state = tr.state; w.tsu = tr.tsu; w.hits = tr.hits; w.age = tr.age; w.last_det = tr.last_det; w.slot = tr.slot;
+            w.slot_total = p->slot_total[tr.slot];
+            w.n_rows = gallery_count(p, tr.slot, t->budget);
+            w.chunks = p->slot_chunks[tr.slot].data();
+            w.n_chunks = dd_ceil_div(w.n_rows, GAL_CH);
+            DD_REQUIRE(w.n_chunks <= (int)p->slot_chunks[tr.slot].size(), DD_E_STATE, "snapshot: track %lld has %d rows in %zu chunks", (long long)tr.id,
+                       w.n_rows, p->slot_chunks[tr.slot].size());
+            out.push_back(w);
+        }
+    }
+    return DD_OK;
+}
+
+// The first half of an import: the pool holds n free chunks afterwards, or nothing has changed but the number of (empty) arenas.
+int tracker_pool_reserve_chunks(dd_tracker *any, size_t n) {
+    TrackerPool *p = any->pool;
+    while (p->free_chunks.size() < n) {
+        const int rc = pool_add_arena(p);
+        if (rc != DD_OK) return rc;
+    }
+    return DD_OK;
+}
+
+// The second half, which cannot fail once the caller has checked n_live + n_dead <= tcap and reserved the chunks: tracker_reset, then
+// the listed tracks with fresh slots and chunk lists.  slots_out[i] / chunks_out (ceil(n_rows / 32) per track, behind one another): where
+// the caller's scatter launch puts means, covariances and gallery rows; tracker_gallery_flush then brings the chunk table up to date.
+int tracker_import(dd_tracker *t, int64_t next_id, const TrackLoad *tr_in, int n_live, int n_dead, std::vector<int> &slots_out,
+                   std::vector<int> &chunks_out) {
+    TrackerPool *p = t->pool;
+    DD_REQUIRE(n_live >= 0 && n_dead >= 0 && n_live + n_dead <= t->tcap, DD_E_CAPACITY, "restore: %d tracks, track_capacity %d", n_live + n_dead, t->tcap);
+    int rc = tracker_reset(t);
+    if (rc != DD_OK) return rc;
+    size_t need = 0;
+    for (int i = 0; i < n_live + n_dead; ++i) need += (size_t)dd_ceil_div(tr_in[i].n_rows, GAL_CH);
+    DD_REQUIRE(p->free_chunks.size() >= need, DD_E_STATE, "restore: %zu gallery chunks were not reserved", need);
+    t->next_id = next_id;
+    t->live_means.resize((size_t)n_live * 8); t->dead_means.resize((size_t)n_dead * 8);
+    for (int i = 0; i < n_live + n_dead; ++i) {
+        const TrackLoad &in = tr_in[i];
+        TrackRec tr;
+        tr.id = in.id; tr.state = in.state; tr.tsu = in.tsu; tr.hits = in.hits; tr.age = in.age; tr.last_det = in.last_det;
+        tr.slot = t->free_slots.back();
+        t->free_slots.pop_back();
+        const bool live = i < n_live;
+        (live ? t->tracks : t->deleted).push_back(tr);
+        if (!live) t->pending_free.push_back(tr.slot);
+        memcpy((live ? t->live_means.data() + (size_t)i * 8 : t->dead_means.data() + (size_t)(i - n_live) * 8), in.mean, 8 * sizeof(double));
+        std::vector<int> &chs = p->slot_chunks[tr.slot];
+        const int nc = dd_ceil_div(in.n_rows, GAL_CH);
+        p->tab_need = std::max(p->tab_need, nc);
+        for (int ci = 0; ci < nc; ++ci) {
+            const int c = p->free_chunks.back();
+            p->free_chunks.pop_back();
+            chs.push_back(c);
+            p->tab_upd.push_back(tr.slot); p->tab_upd.push_back(ci); p->tab_upd.push_back(c);
+            chunks_out.push_back(c);
+        }
+        p->slot_total[tr.slot] = in.slot_total;
+        slots_out.push_back(tr.slot);
+    }
+    return DD_OK;
+}
+
+int tracker_gallery_flush(dd_tracker *any, hipStream_t s) { return gallery_flush(any->pool, s); }
+
 }  // namespace ddk
 
 extern "C" {
+
+// Test aid: one live track's gallery rows in storage order (chunk_rows_gather_k over its chunk list) and its sample count.
+int dd_tracker_gallery_read(dd_tracker *t, int64_t track_id, float *rows_host, int cap_rows, int *n_rows_host, int *slot_total_host) {
+    DD_REQUIRE(t && n_rows_host, DD_E_ARG, "dd_tracker_gallery_read: NULL argument");
+    int i = -1;
+    for (size_t k = 0; k < t->tracks.size() && i < 0; ++k) if (t->tracks[k].id == track_id) i = (int)k;
+    DD_REQUIRE(i >= 0, DD_E_ARG, "dd_tracker_gallery_read: no live track with id %lld", (long long)track_id);
+    TrackerPool *p = t->pool;
+    const int slot = t->tracks[i].slot, n = gallery_count(p, slot, t->budget), nc = dd_ceil_div(n, GAL_CH);
+    *n_rows_host = n;
+    if (slot_total_host) *slot_total_host = p->slot_total[slot];
+    if (!rows_host || n == 0) return DD_OK;
+    DD_REQUIRE(cap_rows >= n, DD_E_CAPACITY, "dd_tracker_gallery_read: %d rows, room for %d", n, cap_rows);
+    DD_REQUIRE(nc <= (int)p->slot_chunks[slot].size(), DD_E_STATE, "dd_tracker_gallery_read: %d rows in %zu chunks", n, p->slot_chunks[slot].size());
+    DD_DEVICE(p->ctx);
+    hipStream_t s = p->ctx->stream;
+    DD_HIP(hipStreamSynchronize(s));                              // the staging buffers below are the group's
+    int rc;
+    const size_t head = ((size_t)(4 + nc) * sizeof(int) + 15) / 16 * 16, bytes = head + (size_t)n * 128 * sizeof(float);
+    if ((rc = p->h_gather.reserve(bytes)) != DD_OK) return rc;
+    if ((rc = p->d_gather.reserve(bytes)) != DD_OK) return rc;
+    int *h = p->h_gather.as<int>();
+    h[0] = 4; h[1] = n; h[2] = 0; h[3] = -1;                      // the chunk list lies behind the table, in the same array
+    memcpy(h + 4, p->slot_chunks[slot].data(), (size_t)nc * sizeof(int));
+    char *d = p->d_gather.as<char>();
+    DD_HIP(hipMemcpyAsync(d, h, head, hipMemcpyHostToDevice, s));
+    if ((rc = ddk::chunk_rows_gather(s, p->d_arenas, GAL_ARENA_SHIFT, reinterpret_cast<const int *>(d), reinterpret_cast<const int *>(d), 1,
+                                     reinterpret_cast<float *>(d + head), nullptr, nullptr, nullptr)) != DD_OK) return rc;
+    DD_HIP(hipMemcpyAsync(p->h_gather.as<char>() + head, d + head, bytes - head, hipMemcpyDeviceToHost, s));
+    DD_HIP(hipStreamSynchronize(s));
+    memcpy(rows_host, p->h_gather.as<char>() + head, bytes - head);
+    return DD_OK;
+}
 
 int dd_tracker_create(dd_ctx *ctx, double max_cosine_distance, double max_iou_distance, int max_age, int n_init,
                       int nn_budget, int track_capacity, int gallery_capacity, dd_tracker **out) {

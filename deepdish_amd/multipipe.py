@@ -30,6 +30,15 @@ class _TrackerView:
             check(lib().dd_tracker_read(self._h, 0, ptr(ints), ptr(means), None))
         return ints, means
 
+    def gallery(self, track_id):
+        """Test aid: (rows f32 [n, 128] of one live track's gallery in storage order, samples appended so far)."""
+        n, total = ctypes.c_int(), ctypes.c_int()
+        check(lib().dd_tracker_gallery_read(self._h, int(track_id), None, 0, ctypes.byref(n), ctypes.byref(total)), 'dd_tracker_gallery_read')
+        rows = np.zeros((n.value, 128), dtype=np.float32)
+        if n.value:
+            check(lib().dd_tracker_gallery_read(self._h, int(track_id), ptr(rows), n.value, ctypes.byref(n), ctypes.byref(total)), 'dd_tracker_gallery_read')
+        return rows, total.value
+
     @property
     def next_id(self):
         v = ctypes.c_int64()
@@ -415,6 +424,45 @@ class MultiStreamPipeline:
                              'pass a sequence, object_detector_skip_frames=[%d] * %d, for one counter per stream'
                              % (int(self.object_detector_skip_frames), int(self.object_detector_skip_frames), self.S))
         check(lib().dd_pipeline_reset_streams(self._h, ptr(a) if a.size else None, int(a.size)), 'dd_pipeline_reset_streams')
+
+    def snapshot(self, streams=None, background=True):
+        """The state of `streams` (default: all) as a StreamSnapshot (host bytes: deepdish_amd/snapshot.py), between steps.  A pure read:
+        it waits for the main stream and changes nothing, a queued look-ahead detector run stays queued, and the pipeline steps on
+        exactly as one that was never asked.  Per stream it carries the tracker (tracks and deleted list, ids, means, covariances, every
+        gallery in storage order), paths, votes, counts by label name, frames_seen, the last step's detections, the per-stream skip
+        counter with the retained detector output and encoder rows, and -- background=True and subtraction on -- the MOG2 model with its
+        frame count and the motion-mask plane (about 31 MB per 640 x 480 stream).  Parameters are recorded to be checked by restore(),
+        not carried; stage timers, the *_stats() counters, the tracker's last cost matrices and matches, the Python-side `ground`
+        cameras and fonts are not stream state.  Not with the int form of object_detector_skip_frames (N > 0)."""
+        from .snapshot import StreamSnapshot
+        a = np.arange(self.S, dtype=np.int32) if streams is None else _reset_streams(streams, self.S)
+        n = ctypes.c_int64()
+        check(lib().dd_pipeline_snapshot_bytes(self._h, ptr(a) if a.size else None, int(a.size), int(bool(background)), ctypes.byref(n)),
+              'dd_pipeline_snapshot_bytes')
+        blob = np.empty(n.value, dtype=np.uint8)
+        check(lib().dd_pipeline_snapshot(self._h, ptr(a) if a.size else None, int(a.size), int(bool(background)), ptr(blob), n.value, ctypes.byref(n)),
+              'dd_pipeline_snapshot')
+        return StreamSnapshot(blob)
+
+    def restore(self, snapshot, streams=None):
+        """Entry i of `snapshot` becomes stream streams[i] (default: streams 0 .. len(snapshot) - 1): reset([z]) followed by loading the
+        state, every other stream untouched, a queued look-ahead run discarded.  From its next step on the stream is bit for bit the
+        stream the snapshot was taken from -- in this pipeline, in another process, in a pipeline with another number of streams, on
+        another GPU (with the same encoder_max_batch: the engine's max_batch fixes the last bits of the features).  Everything is checked
+        before anything changes, and a restore that raises leaves the pipeline exactly as it was.  ValueError: a stream out of range or
+        listed twice, len(streams) != len(snapshot), a parameter of the source stream that differs from the destination's (named),
+        a snapshot with background into a pipeline with subtraction off, a blob the validator refuses.  DeepDishHipError: more tracks
+        than track_capacity (DD_E_CAPACITY), the int form of object_detector_skip_frames with N > 0 (DD_E_STATE: pass a sequence, as
+        for reset())."""
+        from ._lib import DeepDishHipError
+        a = np.arange(len(snapshot), dtype=np.int32) if streams is None else _reset_streams(streams, self.S)
+        if a.size != len(snapshot):
+            raise ValueError('streams: %d streams for a snapshot of %d entries' % (a.size, len(snapshot)))
+        blob = snapshot._blob
+        rc = lib().dd_pipeline_restore(self._h, ptr(blob), int(blob.size), ptr(a) if a.size else None, int(a.size))
+        if rc == -1:                               # DD_E_ARG
+            raise ValueError(lib().dd_last_error().decode())
+        check(rc, 'dd_pipeline_restore')
 
     def stream_param_stats(self):
         """Which kernels per-stream parameters selected: launches of the per-problem NMS variant and of the per-stream association

@@ -681,6 +681,42 @@ int dd_pipeline_reset_streams(dd_pipeline *p, const int *streams_host, int n);
 /* out4_host = {launches of nms_small_streams_k, launches of assoc_match_streams_k, dd_pipeline_reset_streams calls that reset at least one
  * stream, streams reset}: whether the per-stream kernel variants ran. */
 int dd_pipeline_stream_param_stats(dd_pipeline *p, long long *out4_host);
+/* ---- stream snapshots (csrc/snapshot_fmt.h: the blob; csrc/snapshot.hip: the gallery kernels).  A stream restored from a snapshot is,
+ * from its next step on, bit for bit the stream the snapshot was taken from: in the same pipeline, in another process, in a pipeline with
+ * another number of streams, on another device.  Carried per stream: the tracker (tracks and deleted list in order, next id, every mean
+ * and covariance, every gallery in storage order with its sample count), paths, votes, counts (by label name), frame number, the last
+ * step's detections and retained adaptor output, the skip counter with the stream's retained encoder rows, and -- background != 0 and
+ * subtraction on -- the MOG2 planes, frame count and motion-mask plane.  NOT carried: parameters (recorded and compared), stage timers and
+ * the *_stats counters, dd_tracker_last_cost / dd_tracker_last_matches.  Slot and chunk numbers are not state: restore hands out fresh ones.
+ *
+ * dd_pipeline_snapshot_bytes: what dd_pipeline_snapshot of the listed streams (streams_host NULL: 0 .. n - 1) will write.
+ * dd_pipeline_snapshot: a pure read between steps -- it waits for the main stream and changes nothing; a queued look-ahead run stays queued.
+ * One chunk_rows_gather_k launch packs every listed gallery, mean and covariance; one copy brings them to the host. */
+int dd_pipeline_snapshot_bytes(dd_pipeline *p, const int *streams_host, int n, int background, int64_t *bytes_host);
+int dd_pipeline_snapshot(dd_pipeline *p, const int *streams_host, int n, int background, uint8_t *blob_host, int64_t cap, int64_t *bytes_host);
+/* Entry i of the blob goes to stream streams_host[i] (NULL: stream i); n must be the blob's entry count.  Equal to dd_pipeline_reset_streams
+ * of those streams followed by loading the state; a queued look-ahead run is discarded.  Everything is checked before anything changes, and
+ * a restore that returns an error leaves the pipeline exactly as it was: DD_E_ARG for a stream out of range or listed twice, another n
+ * than the blob has, a blob its validator refuses, a background section while subtraction is off, or a parameter of the source stream
+ * that differs from the destination's (the message names the first: H, W, feature length, metric, nn_budget, detector kind, max_det,
+ * labels, wanted labels, line, max_age, n_init, max_cosine_distance, max_iou_distance, nms_max_overlap, motion ratio, masking, the MOG2
+ * settings, skip N and phase; floats by bit pattern); DD_E_CAPACITY for more tracks than track_capacity; DD_E_STATE with
+ * dd_pipeline_detector_skip_frames(n > 0) (see dd_pipeline_reset_streams) or an update in flight. */
+int dd_pipeline_restore(dd_pipeline *p, const uint8_t *blob_host, int64_t n_bytes, const int *streams_host, int n);
+/* Host only: validates the blob and describes it.  info_host (may be NULL) int64 [cap_entries][8] = frames seen, tracks (live + deleted),
+ * next id, gallery rows, has background, bytes, offset of the entry in the blob, 0. */
+int dd_snapshot_info(const uint8_t *blob_host, int64_t n_bytes, int *n_entries_host, int64_t *info_host, int cap_entries);
+/* Test aid: the gallery of one live track, rows in STORAGE order (under nn_budget the ring as it lies), and the samples appended so far. */
+int dd_tracker_gallery_read(dd_tracker *t, int64_t track_id, float *rows_host, int cap_rows, int *n_rows_host, int *slot_total_host);
+/* The two gallery kernels alone.  arenas_host: n_arenas device pointers, each to arena_rows rows of 128 f32 (arena_rows = 32 x a power of two);
+ * chunk c is rows [32 (c mod chunks per arena), + 32) of arena c div chunks per arena.  chunks_host int32 [n_chunks]: chunk lists behind
+ * one another.  table_host int64 [n_entries][3] = {offset of the entry's list in chunks_host, row count, first row in dense_dev}: row r of
+ * an entry is row r mod 32 of chunk list[r div 32].  gather packs the rows into dense_dev (dense_rows rows), scatter is the inverse.
+ * Every range is checked here against the stated sizes; destinations must not overlap.  Synchronous. */
+int dd_chunk_rows_gather(dd_ctx *ctx, const void *const *arenas_host, int n_arenas, int64_t arena_rows, const int *chunks_host, int n_chunks,
+                         const int64_t *table_host, int n_entries, float *dense_dev, int64_t dense_rows, void *stream);
+int dd_chunk_rows_scatter(dd_ctx *ctx, void *const *arenas_host, int n_arenas, int64_t arena_rows, const int *chunks_host, int n_chunks,
+                          const int64_t *table_host, int n_entries, const float *dense_dev, int64_t dense_rows, void *stream);
 /* The pipeline's background subtractor (NULL while subtraction is off), for dd_mog2_state; it is the pipeline's: do not apply or destroy. */
 int dd_pipeline_mog2(dd_pipeline *p, dd_mog2 **out);
 /* frames: device u8 [n_streams][H][W][3] BGR.  inj_*: optional detections that REPLACE the detector's
