@@ -193,6 +193,9 @@ SIGNATURES = {
     'dd_jpegdec_create_ex': [P, c_int, c_int, c_int, c_int, c_int, c_int64, POINTER(P)],
     'dd_jpegdec_profile_levels': [P, P, POINTER(c_int)],
     'dd_jpegdec_split_stats': [P, P],
+    'dd_jpegdec_decode_scales': [P, P, P, P, P, c_int, P, P, P],
+    'dd_ingest_source_sizes': [P, c_int, P],
+    'dd_jpeg_parse_flags': [P, c_int64, c_int, P, P],
     'dd_counts_accumulate': [P, P, P, c_int, P],
 }
 _RESTYPE = {'dd_last_error': c_char_p}

@@ -168,9 +168,14 @@ int yuv422_resize(hipStream_t s, const uint8_t *src, int n, int H, int W, int or
 // the JPEG decoder's two halves (jpeg_dec.hip), as the ingest ring drives them: a header into a record with the status a decoder of h x w
 // gives it (returned too; the reason is left in dd_last_error), and upload + kernels for n records without a host wait
 // scans / scans_host: NULL, or (a decoder made with DD_JPEGDEC_PROGRESSIVE) where each file's scan script goes, kept like the records
-int jpegdec_parse(const uint8_t *file, size_t n, int h, int w, dd_jpeg_info *rec, dd_jpeg_scans *scans);
+// flags: the decoder's DD_JPEGDEC_* (0: every file must be h x w and define its tables); scales: NULL, or one scale denominator per file
+// (a decoder made with DD_JPEGDEC_ANY_SIZE)
+int jpegdec_parse(const uint8_t *file, size_t n, int h, int w, dd_jpeg_info *rec, dd_jpeg_scans *scans, int flags = 0);
 int jpegdec_launch(dd_jpegdec *dec, dd_jpeg_info *recs_host, dd_jpeg_scans *scans_host, const uint8_t *bytes_host, size_t n_bytes, int n, uint8_t *out_dev, int *status_dev,
-                   hipStream_t s, hipEvent_t uploaded);
+                   hipStream_t s, hipEvent_t uploaded, const int *scales = nullptr);
+// csrc/jpeg_dec_any.hip: the pixel stage of a DD_JPEGDEC_ANY_SIZE decoder, per log2 of the scale the LDS, whether a file has it, whether one takes the planes path
+int jpegdec_pixels_any(hipStream_t s, int n, int max_bands, long long coef_stride, long long plane_stride, const size_t *lds_at, const bool *any_at, const bool *planes_at,
+                       const dd_jpeg_info *recs, const int *mark, const int16_t *coef, uint8_t *planes, uint8_t *out_dev, int OH, int OW);
 int resize_lanczos(hipStream_t s, int device, const uint8_t *src, int H, int W, int src_c, int swap_rb, uint8_t *dst,
                    int h, int w, uint8_t *tmp, int batch);
 size_t ssd_post_scratch_bytes(int n_anchors, int batch);

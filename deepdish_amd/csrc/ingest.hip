@@ -23,6 +23,11 @@
 // in front of crop_resize when a flip or a resize is asked.  Each stream carries a status; a bad file costs its neighbours nothing.
 // Such a ring may decode at 1/2, 1/4 or 1/8 scale (dd_ingest_create_jpeg_scaled): src_h x src_w stays what every file must state, the
 // decoder writes ceil(src_h / scale) x ceil(src_w / scale) frames, and it is that size the staging buffer has and crop_resize starts from.
+// A ring made with DD_JPEGDEC_ANY_SIZE takes files of any size up to src_h x src_w, each at its own scale (the ring's, or Pillow's draft rule
+// per file): put() records the file's size and scale, and submit() always decodes into the staging buffer -- uniform slots of the largest
+// frame, each file in its slot's top-left corner -- builds one crop box per stream from its record, uploads the boxes through the slot's
+// pinned memory and lets crop_resize stretch each to dst, as the reference's cv2.resize(frame, self.input_size) does whatever the camera sent.
+#include <algorithm>
 #include <cstddef>
 #include <cstdlib>
 #include <mutex>
@@ -50,6 +55,12 @@ struct dd_ingest {
     std::vector<int *> h_status, d_status;
     std::vector<size_t> fill;
     std::vector<char> stale;
+    // DD_JPEGDEC_ANY_SIZE: per slot and stream what put() learnt, (width, height, scale) and the scale alone as the decoder takes it, and the
+    // crop boxes in pinned memory on their way to d_boxes
+    int jflags = 0, jscale = 1;
+    bool any_size = false, auto_scale = false;
+    std::vector<std::vector<int>> sizes, scales;
+    std::vector<int *> h_boxes;
     std::mutex mu;
 };
 
@@ -71,13 +82,17 @@ static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams,
         DD_REQUIRE(src_w % 2 == 0, DD_E_ARG, "%s: src_w %d must be even for 4:2:2 frames", who, src_w);
         DD_REQUIRE(n_streams <= 65535, DD_E_ARG, "%s: n_streams %d above 65535", who, n_streams);
     }
+    const bool any_size = pixel_format == INGEST_JPEG && (jpeg_flags & DD_JPEGDEC_ANY_SIZE) != 0;
+    const bool auto_scale = any_size && jpeg_scale == 0;        // the draft rule per file; the slots are sized for scale 1
+    if (auto_scale) jpeg_scale = 1;
     DD_REQUIRE(jpeg_scale == 1 || jpeg_scale == 2 || jpeg_scale == 4 || jpeg_scale == 8, DD_E_ARG, "%s: scale %d is none of 1, 2, 4, 8", who, jpeg_scale);
     DD_HIP(hipSetDevice(ctx->device));
     dd_ingest *g = new dd_ingest();
     g->ctx = ctx; g->slots = slots; g->S = n_streams; g->sh = src_h; g->sw = src_w; g->dh = dst_h; g->dw = dst_w;
     g->flip = flip != 0;
     g->jh = (src_h + jpeg_scale - 1) / jpeg_scale, g->jw = (src_w + jpeg_scale - 1) / jpeg_scale;
-    g->transform = g->flip || g->jh != dst_h || g->jw != dst_w;
+    g->transform = g->flip || g->jh != dst_h || g->jw != dst_w || any_size;      // any size: always through the staging buffer and crop_resize
+    g->jflags = jpeg_flags, g->jscale = jpeg_scale, g->any_size = any_size, g->auto_scale = auto_scale;
     g->format = pixel_format;
     g->raw_bytes = pixel_format ? (size_t)n_streams * src_h * src_w * 3 / 2 : (size_t)n_streams * src_h * src_w * 3;
     if (pixel_format == INGEST_JPEG) g->raw_bytes = jpeg_slot_bytes;
@@ -126,6 +141,13 @@ static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams,
                 g->h_scans.push_back(sc);
             }
             g->fill.push_back(0); g->stale.push_back(1);
+            if (any_size) {
+                int *hb = nullptr;
+                DD_HIP(hipHostMalloc(reinterpret_cast<void **>(&hb), (size_t)n_streams * 8 * sizeof(int), hipHostMallocDefault));
+                g->h_boxes.push_back(hb);
+                g->sizes.emplace_back((size_t)n_streams * 3, 0);
+                g->scales.emplace_back((size_t)n_streams, jpeg_scale);
+            }
         }
     }
     *out = g;
@@ -140,6 +162,7 @@ static int ingest_jpeg_reset(dd_ingest *g, int slot) {
         memset(&g->h_recs[slot][z], 0, offsetof(dd_jpeg_info, quant));      // the scalar fields; the next parse rewrites the tables
         g->h_recs[slot][z].status = DD_JPEG_ST_NO_FRAME;
     }
+    if (g->any_size) std::fill(g->sizes[slot].begin(), g->sizes[slot].end(), 0);
     g->fill[slot] = 0;
     g->stale[slot] = 0;
     return DD_OK;
@@ -182,8 +205,24 @@ int dd_ingest_jpeg_put(dd_ingest *g, int slot, int stream, const uint8_t *data_h
     // the copy and the parse run outside the lock: decoder threads share that work.  A stream's record belongs to the thread that puts it.
     memcpy(g->h_raw[slot] + at, data_host, (size_t)n);
     dd_jpeg_info *rec = &g->h_recs[slot][stream];
-    ddk::jpegdec_parse(g->h_raw[slot] + at, (size_t)n, g->sh, g->sw, rec, g->h_scans.empty() ? nullptr : &g->h_scans[slot][stream]);
+    ddk::jpegdec_parse(g->h_raw[slot] + at, (size_t)n, g->sh, g->sw, rec, g->h_scans.empty() ? nullptr : &g->h_scans[slot][stream], g->jflags);
     rec->file_offset = (int64_t)at;
+    if (g->any_size) {                                          // a refused header leaves zeros; a file too large keeps what it stated
+        int *sz = &g->sizes[slot][(size_t)stream * 3];
+        sz[0] = sz[1] = sz[2] = 0;
+        if (rec->status == DD_JPEG_ST_OK || rec->status == DD_JPEG_ST_SIZE) {
+            const int sc = g->auto_scale ? dd_jpeg_draft_scale(rec->width, rec->height, g->dw, g->dh) : g->jscale;
+            sz[0] = rec->width, sz[1] = rec->height, sz[2] = sc;
+            g->scales[slot][stream] = sc;
+        }
+    }
+    return DD_OK;
+}
+
+int dd_ingest_source_sizes(dd_ingest *g, int slot, int *sizes_host) {
+    DD_REQUIRE(g && sizes_host && slot >= 0 && slot < g->slots, DD_E_ARG, "dd_ingest_source_sizes: bad argument");
+    DD_REQUIRE(g->any_size, DD_E_STATE, "dd_ingest_source_sizes: the ring was not made with DD_JPEGDEC_ANY_SIZE");
+    memcpy(sizes_host, g->sizes[slot].data(), (size_t)g->S * 3 * sizeof(int));
     return DD_OK;
 }
 
@@ -220,6 +259,7 @@ int dd_ingest_destroy(dd_ingest *g) {
     if (g->d_boxes) (void)hipFree(g->d_boxes);
     if (g->d_stage) (void)hipFree(g->d_stage);
     for (dd_jpeg_scans *sc : g->h_scans) (void)hipHostFree(sc);
+    for (int *hb : g->h_boxes) (void)hipHostFree(hb);
     for (size_t i = 0; i < g->h_recs.size(); ++i) {
         (void)hipHostFree(g->h_recs[i]);
         (void)hipHostFree(g->h_status[i]);
@@ -255,8 +295,19 @@ int dd_ingest_submit(dd_ingest *g, int slot) {
         if (int rc = ingest_jpeg_reset(g, slot)) return rc;                         // a submit without a put: every stream reports "no frame"
         if (g->used[slot]) DD_HIP(hipStreamWaitEvent(g->copy, g->done[slot], 0));
         uint8_t *dst = g->transform ? g->d_stage : g->d_out[slot];
+        if (g->any_size) {                                      // one box per stream from its record: the file's own frame in its staging slot
+            int *hb = g->h_boxes[slot];
+            for (int z = 0; z < g->S; ++z) {
+                const dd_jpeg_info &r = g->h_recs[slot][z];
+                const int sc = g->scales[slot][z], ok = r.status == DD_JPEG_ST_OK && sc >= 1;
+                const int ow = ok ? (r.width + sc - 1) / sc : 0, oh = ok ? (r.height + sc - 1) / sc : 0;
+                int *b = hb + (size_t)z * 8;
+                b[0] = 0, b[1] = g->flip ? g->jh - oh : 0, b[2] = ow, b[3] = oh, b[4] = z, b[5] = g->flip, b[6] = 0, b[7] = 0;      // crop_resize flips within the slot
+            }
+            DD_HIP(hipMemcpyAsync(g->d_boxes, hb, (size_t)g->S * 8 * sizeof(int), hipMemcpyHostToDevice, g->copy));
+        }
         int rc = ddk::jpegdec_launch(g->dec, g->h_recs[slot], g->h_scans.empty() ? nullptr : g->h_scans[slot], g->h_raw[slot], g->fill[slot], g->S, dst, g->d_status[slot],
-                                     g->copy, nullptr);
+                                     g->copy, nullptr, g->any_size ? g->scales[slot].data() : nullptr);
         if (rc == DD_OK && g->transform) rc = ddk::crop_resize(g->copy, g->d_stage, g->jh, g->jw, g->d_boxes, g->S, g->dh, g->dw, g->d_out[slot]);
         if (rc != DD_OK) return rc;
         DD_HIP(hipMemcpyAsync(g->h_status[slot], g->d_status[slot], (size_t)g->S * sizeof(int), hipMemcpyDeviceToHost, g->copy));

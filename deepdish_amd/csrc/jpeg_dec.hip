@@ -35,53 +35,20 @@
 //                         their predecessors' end states until none changes (Huffman data re-synchronises by itself), scans the blocks
 //                         begun and the DC sums, and decodes once more to store the coefficients: the sequential decode, cut into pieces.
 // Everything in front of and behind the entropy stage stays as it is; a decoder made without the flag does not launch it.
+//
+// A decoder made with DD_JPEGDEC_ANY_SIZE takes files of any size up to its H x W, each at its own scale (dd_jpegdec_decode_scales): the
+// kernels up to here are per record and run as they are, jpegdec_launch decides path and scale per file, holds every record to the
+// decoder's buffers, and hands the pixel stage to jpeg_pixels_any_k<S> / jpeg_planes_any_k<S> (csrc/jpeg_dec_any.hip), which write each
+// frame into the top-left corner of a uniform slot.  DD_JPEGDEC_STD_TABLES goes to the parser alone (csrc/jpeg_parse.h).
 #include "common.h"
 #include "jpeg_dec_dev.h"
+#include "jpeg_dec_pix.h"
 #include <cstdlib>
 #include <new>
 
 namespace {
 
-constexpr int JD_T = 256;                      // threads per workgroup (markers, pixels)
 constexpr int JD_CHUNK = 16;                   // scan bytes per thread and pass of jpeg_markers_k
-constexpr int JD_LDS_MAX = 64 * 1024;          // a band's planes; what every kernel may use without asking
-
-struct JdGeom {
-    int H, W, max_bands;
-    long long coef_stride;                     // int16 per frame: the largest accepted sampling's blocks
-    long long plane_stride;                    // bytes per frame of the HBM planes
-};
-
-struct JdBand {
-    int Wy, Wc, yrows, crows, halo;
-    size_t lds;
-};
-
-__host__ __device__ inline JdBand jd_band(int W, int ncomp, int hs, int vs) {
-    JdBand b;
-    const int mx = (W + 8 * hs - 1) / (8 * hs);
-    b.Wy = mx * 8 * hs, b.Wc = mx * 8;
-    b.yrows = 8 * vs;
-    b.halo = ncomp == 3 && vs == 2 ? 1 : 0;
-    b.crows = ncomp == 3 ? 8 + 2 * b.halo : 0;
-    b.lds = (size_t)b.yrows * b.Wy + 2 * (size_t)b.crows * b.Wc;
-    return b;
-}
-
-// The same at scale 1 / s.  At s >= 2 a band is still one MCU row, 8 * vs / s output rows; every component's rows coincide with the
-// luma's (4:2:0 chroma keeps blocks of twice the luma's side, csrc/jpeg_dec_dev.h jpd_plane), so there is no halo.
-__host__ __device__ inline JdBand jd_band(int W, int ncomp, int hs, int vs, int s) {
-    if (s == 1) return jd_band(W, ncomp, hs, vs);
-    JdBand b;
-    const int mx = (W + 8 * hs - 1) / (8 * hs);
-    const int ny = 8 / s, nc = jpd_plane(1, 1, 1, 1, hs, vs, s).n;
-    b.Wy = mx * hs * ny, b.Wc = mx * nc;
-    b.yrows = vs * ny;
-    b.halo = 0;
-    b.crows = ncomp == 3 ? nc : 0;
-    b.lds = (size_t)b.yrows * b.Wy + 2 * (size_t)b.crows * b.Wc;
-    return b;
-}
 
 // ------------------------------------------------------------------------------------------------ device
 
@@ -398,133 +365,6 @@ __global__ __launch_bounds__(64) void jpeg_prog_entropy_k(const dd_jpeg_info *__
     if (jpd_prog_decode_interval(r, sc, S.pool, bytes + r.file_offset + sc.offset, s, e, u0, nu, coef + (size_t)f * coef_stride) != DD_JPEG_ST_OK) status[f] = DD_JPEG_ST_DATA;
 }
 
-// Block `blk` of a frame: dequantise and transform.  rows: -1 all eight to dst (stride bytes apart), else that one row to dst.
-__device__ __forceinline__ void jd_block(const int16_t *__restrict__ coef, size_t blk, const uint16_t *__restrict__ q, uint8_t *dst, int stride, int row) {
-    int32_t d[64];
-    const uint4 *c4 = reinterpret_cast<const uint4 *>(coef + blk * 64);
-    const uint4 *q4 = reinterpret_cast<const uint4 *>(q);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint4 c = c4[i], v = q4[i];
-        const uint32_t cw[4] = {c.x, c.y, c.z, c.w}, qw[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            d[8 * i + 2 * j] = (int32_t)(int16_t)(cw[j] & 0xffffu) * (int32_t)(qw[j] & 0xffffu);
-            d[8 * i + 2 * j + 1] = (int32_t)(int16_t)(cw[j] >> 16) * (int32_t)(qw[j] >> 16);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 8; ++c) jpd_idct8<8, 11>(&d[c]);
-    if (row < 0) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            jpd_idct8<1, 18>(&d[8 * r]);
-            uint32_t lo = 0, hi = 0;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                lo |= (uint32_t)jpd_range_limit(d[8 * r + i]) << (8 * i);
-                hi |= (uint32_t)jpd_range_limit(d[8 * r + 4 + i]) << (8 * i);
-            }
-            *reinterpret_cast<uint2 *>(dst + (size_t)r * stride) = make_uint2(lo, hi);
-        }
-    } else {
-        int32_t e[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) e[i] = row == 0 ? d[i] : d[56 + i];            // the halo rows: a block's first or last
-        jpd_idct8<1, 18>(e);
-        uint32_t lo = 0, hi = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            lo |= (uint32_t)jpd_range_limit(e[i]) << (8 * i);
-            hi |= (uint32_t)jpd_range_limit(e[4 + i]) << (8 * i);
-        }
-        *reinterpret_cast<uint2 *>(dst) = make_uint2(lo, hi);
-    }
-}
-
-// The blocks of MCU row `band` into planes Y [.. ][Wy], Cb and Cr [.. ][Wc]: Y's row 0 is the band's first luma row; the chroma planes'
-// row 0 is the band's first chroma row when halo is 0, else the last chroma row of the band above, and row 9 the first of the band below.
-__device__ __forceinline__ void jd_transform_band(const dd_jpeg_info &r, const int16_t *__restrict__ coef, int band, const JdBand &b, uint8_t *Y, uint8_t *Cb, uint8_t *Cr,
-                                                  bool halo) {
-    const int mx = r.mcus_x, bpm = r.blocks_per_mcu, ny = bpm == 1 ? 1 : bpm - 2, hs = r.hmax;
-    const int per_mcu = bpm + (halo ? 4 : 0);
-    for (int t = threadIdx.x; t < mx * per_mcu; t += JD_T) {
-        const int m = t / per_mcu, k = t - m * per_mcu;
-        const size_t mcu = (size_t)band * mx + m;
-        if (k < ny) {
-            jd_block(coef, mcu * bpm + k, r.quant[r.tq[0]], Y + (size_t)(k / hs) * 8 * b.Wy + (size_t)(m * hs + k % hs) * 8, b.Wy, -1);
-        } else if (k < bpm) {
-            const int c = k - ny + 1;
-            jd_block(coef, mcu * bpm + k, r.quant[r.tq[c]], (c == 1 ? Cb : Cr) + (size_t)(halo ? 1 : 0) * b.Wc + (size_t)m * 8, b.Wc, -1);
-        } else {
-            const int h = k - bpm, c = 1 + (h & 1), below = h >> 1;
-            if (below ? band + 1 >= r.mcus_y : band == 0) continue;          // the frame's edge: the filter repeats the band's own row
-            const size_t nb = ((size_t)(below ? band + 1 : band - 1) * mx + m) * bpm + ny + (c - 1);
-            jd_block(coef, nb, r.quant[r.tq[c]], (c == 1 ? Cb : Cr) + (size_t)(below ? 9 : 0) * b.Wc + (size_t)m * 8, b.Wc, below ? 0 : 7);
-        }
-    }
-}
-
-// Pixel (y, x) of the frame from planes whose row 0 is luma row y0 / chroma row c0: libjpeg's fancy up-sampling over the component's
-// true size cw x ch (plain replication at cw <= 2, as jdsample.c chooses), then jdcolor.c.  Packed B | G << 8 | R << 16.
-__device__ __forceinline__ uint32_t jd_pixel(const dd_jpeg_info &r, const JdBand &b, const uint8_t *Y, const uint8_t *Cb, const uint8_t *Cr, int y0, int c0, int y, int x,
-                                             int cw, int ch) {
-    const int yy = Y[(size_t)(y - y0) * b.Wy + x];
-    if (r.ncomp == 1) return (uint32_t)yy * 0x010101u;
-    int cb, cr;
-    if (r.hmax == 1) {
-        const size_t o = (size_t)(y - c0) * b.Wc + x;
-        cb = Cb[o], cr = Cr[o];
-    } else {
-        const int cx = x >> 1, cy = r.vmax == 2 ? y >> 1 : y;
-        const size_t near = (size_t)(cy - c0) * b.Wc;
-        if (cw <= 2) {
-            cb = Cb[near + cx], cr = Cr[near + cx];
-        } else {
-            const int nx = (x & 1) ? min(cx + 1, cw - 1) : max(cx - 1, 0);
-            if (r.vmax == 1) {
-                const int bias = (x & 1) ? 2 : 1;
-                cb = (3 * Cb[near + cx] + Cb[near + nx] + bias) >> 2;
-                cr = (3 * Cr[near + cx] + Cr[near + nx] + bias) >> 2;
-            } else {
-                const int fy = (y & 1) ? min(cy + 1, ch - 1) : max(cy - 1, 0);
-                const size_t far = (size_t)(fy - c0) * b.Wc;
-                const int bias = (x & 1) ? 7 : 8;
-                cb = (3 * (3 * Cb[near + cx] + Cb[far + cx]) + 3 * Cb[near + nx] + Cb[far + nx] + bias) >> 4;
-                cr = (3 * (3 * Cr[near + cx] + Cr[far + cx]) + 3 * Cr[near + nx] + Cr[far + nx] + bias) >> 4;
-            }
-        }
-    }
-    return jpd_bgr(yy, cb, cr);
-}
-
-// Rows [y_first, y_first + rows) of frame `out` from the planes.  Four pixels a thread, three dword stores, where rows are dword-aligned.
-__device__ __forceinline__ void jd_paint(const dd_jpeg_info &r, const JdBand &b, const uint8_t *Y, const uint8_t *Cb, const uint8_t *Cr, int y0, int c0, int y_first, int rows,
-                                         uint8_t *__restrict__ out, bool vec) {
-    const int W = r.width, H = r.height;
-    const int cw = (W + r.hmax - 1) / r.hmax, ch = (H + r.vmax - 1) / r.vmax;
-    if (vec) {
-        const int qw = W >> 2;
-        for (int i = threadIdx.x; i < rows * qw; i += JD_T) {
-            const int row = i / qw, x = (i - row * qw) * 4, y = y_first + row;
-            uint32_t p[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) p[j] = jd_pixel(r, b, Y, Cb, Cr, y0, c0, y, x + j, cw, ch);
-            uint32_t *o = reinterpret_cast<uint32_t *>(out + ((size_t)y * W + x) * 3);
-            o[0] = p[0] | (p[1] << 24);
-            o[1] = (p[1] >> 8) | (p[2] << 16);
-            o[2] = (p[2] >> 16) | (p[3] << 8);
-        }
-    } else {
-        for (int i = threadIdx.x; i < rows * W; i += JD_T) {
-            const int row = i / W, x = i - row * W, y = y_first + row;
-            const uint32_t p = jd_pixel(r, b, Y, Cb, Cr, y0, c0, y, x, cw, ch);
-            uint8_t *o = out + ((size_t)y * W + x) * 3;
-            o[0] = (uint8_t)p, o[1] = (uint8_t)(p >> 8), o[2] = (uint8_t)(p >> 16);
-        }
-    }
-}
-
 // DD_JPEGDEC_PLANES only: one workgroup per band transforms it into the frame's planes in HBM.
 __global__ __launch_bounds__(JD_T) void jpeg_planes_k(const dd_jpeg_info *__restrict__ recs, JdGeom g, const int *__restrict__ mark, const int16_t *__restrict__ coef,
                                                       uint8_t *__restrict__ planes) {
@@ -554,115 +394,6 @@ __global__ __launch_bounds__(JD_T) void jpeg_pixels_k(const dd_jpeg_info *__rest
     } else {
         const uint8_t *Y = planes + (size_t)f * g.plane_stride, *Cb = Y + (size_t)r.mcus_y * b.yrows * b.Wy, *Cr = Cb + (size_t)r.mcus_y * 8 * b.Wc;
         jd_paint(r, b, Y, Cb, Cr, 0, 0, y_first, rows, frame, vec != 0);
-    }
-}
-
-// ---- 1/2, 1/4 and 1/8 scale: the two kernels above specialised on the scale denominator S.  The full-size kernels stay as they are.
-
-// Block `blk` of a frame to N x N samples at dst, rows `stride` bytes apart.  N = 8 is the full transform (4:2:0 chroma at S = 2).  dst is
-// aligned to N bytes: every plane starts at a multiple of its block side and is a whole number of blocks wide.
-template <int N>
-__device__ __forceinline__ void jd_block_scaled(const int16_t *__restrict__ coef, size_t blk, const uint16_t *__restrict__ q, uint8_t *dst, int stride) {
-    if constexpr (N == 8) {
-        jd_block(coef, blk, q, dst, stride, -1);
-    } else if constexpr (N == 1) {
-        *dst = (uint8_t)jpd_idct1((int32_t)coef[blk * 64] * (int32_t)q[0]);
-    } else {
-        int32_t d[64];
-        const uint4 *c4 = reinterpret_cast<const uint4 *>(coef + blk * 64);
-        const uint4 *q4 = reinterpret_cast<const uint4 *>(q);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            if (N == 4 ? i == 4 : (i != 0 && !(i & 1))) continue;          // rows the transform does not read
-            const uint4 c = c4[i], v = q4[i];
-            const uint32_t cw[4] = {c.x, c.y, c.z, c.w}, qw[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                d[8 * i + 2 * j] = (int32_t)(int16_t)(cw[j] & 0xffffu) * (int32_t)(qw[j] & 0xffffu);
-                d[8 * i + 2 * j + 1] = (int32_t)(int16_t)(cw[j] >> 16) * (int32_t)(qw[j] >> 16);
-            }
-        }
-        int o[N * N];
-        if constexpr (N == 4) {
-            jpd_idct4(d, o);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                *reinterpret_cast<uint32_t *>(dst + (size_t)r * stride) = (uint32_t)o[4 * r] | ((uint32_t)o[4 * r + 1] << 8) | ((uint32_t)o[4 * r + 2] << 16) | ((uint32_t)o[4 * r + 3] << 24);
-        } else {
-            jpd_idct2(d, o);
-#pragma unroll
-            for (int r = 0; r < 2; ++r) *reinterpret_cast<uint16_t *>(dst + (size_t)r * stride) = (uint16_t)(o[2 * r] | (o[2 * r + 1] << 8));
-        }
-    }
-}
-
-// The blocks of MCU row `band` into planes Y [b.yrows][Wy], Cb and Cr [b.crows][Wc], whose row 0 is the band's first.
-template <int S>
-__device__ __forceinline__ void jd_transform_band_scaled(const dd_jpeg_info &r, const int16_t *__restrict__ coef, int band, const JdBand &b, uint8_t *Y, uint8_t *Cb,
-                                                         uint8_t *Cr) {
-    constexpr int NY = 8 / S;
-    const int mx = r.mcus_x, bpm = r.blocks_per_mcu, ny = bpm == 1 ? 1 : bpm - 2, hs = r.hmax;
-    for (int t = threadIdx.x; t < mx * bpm; t += JD_T) {
-        const int m = t / bpm, k = t - m * bpm;
-        const size_t blk = ((size_t)band * mx + m) * bpm + k;
-        if (k < ny) {
-            jd_block_scaled<NY>(coef, blk, r.quant[r.tq[0]], Y + (size_t)(k / hs) * NY * b.Wy + (size_t)(m * hs + k % hs) * NY, b.Wy);
-        } else {
-            const int c = k - ny + 1;
-            uint8_t *dst = (c == 1 ? Cb : Cr) + (size_t)m * b.crows;
-            if (b.crows == NY) jd_block_scaled<NY>(coef, blk, r.quant[r.tq[c]], dst, b.Wc);
-            else jd_block_scaled<2 * NY>(coef, blk, r.quant[r.tq[c]], dst, b.Wc);           // 4:2:0
-        }
-    }
-}
-
-// Pixel x of plane row `row` (the components' rows coincide).  Only 4:2:2 chroma is up-sampled: jdsample.c's h2v1 fancy filter over the
-// plane's true width cw, plain replication at cw <= 2 and at S = 8, where libjpeg turns the filter off.  Packed B | G << 8 | R << 16.
-template <int S>
-__device__ __forceinline__ uint32_t jd_pixel_scaled(const dd_jpeg_info &r, const JdBand &b, const uint8_t *Y, const uint8_t *Cb, const uint8_t *Cr, int row, int x, int cw) {
-    const int yy = Y[(size_t)row * b.Wy + x];
-    if (r.ncomp == 1) return (uint32_t)yy * 0x010101u;
-    const size_t o = (size_t)row * b.Wc;
-    int cb, cr;
-    if (b.Wc == b.Wy) {
-        cb = Cb[o + x], cr = Cr[o + x];
-    } else {
-        const int cx = x >> 1;
-        if (S == 8 || cw <= 2) {
-            cb = Cb[o + cx], cr = Cr[o + cx];
-        } else {
-            const int nx = (x & 1) ? min(cx + 1, cw - 1) : max(cx - 1, 0), bias = (x & 1) ? 2 : 1;
-            cb = (3 * Cb[o + cx] + Cb[o + nx] + bias) >> 2;
-            cr = (3 * Cr[o + cx] + Cr[o + nx] + bias) >> 2;
-        }
-    }
-    return jpd_bgr(yy, cb, cr);
-}
-
-// Rows [y_first, y_first + rows) of the oh x ow frame `out` from planes whose row `row0` is output row y_first.
-template <int S>
-__device__ __forceinline__ void jd_paint_scaled(const dd_jpeg_info &r, const JdBand &b, const uint8_t *Y, const uint8_t *Cb, const uint8_t *Cr, int row0, int y_first, int rows,
-                                                int ow, uint8_t *__restrict__ out, bool vec) {
-    const int cw = r.ncomp == 3 ? jpd_plane(r.height, r.width, 1, 1, r.hmax, r.vmax, S).cols : 0;
-    if (vec) {
-        const int qw = ow >> 2;
-        for (int i = threadIdx.x; i < rows * qw; i += JD_T) {
-            const int row = i / qw, x = (i - row * qw) * 4;
-            uint32_t p[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) p[j] = jd_pixel_scaled<S>(r, b, Y, Cb, Cr, row0 + row, x + j, cw);
-            uint32_t *o = reinterpret_cast<uint32_t *>(out + ((size_t)(y_first + row) * ow + x) * 3);
-            o[0] = p[0] | (p[1] << 24);
-            o[1] = (p[1] >> 8) | (p[2] << 16);
-            o[2] = (p[2] >> 16) | (p[3] << 8);
-        }
-    } else {
-        for (int i = threadIdx.x; i < rows * ow; i += JD_T) {
-            const int row = i / ow, x = i - row * ow;
-            const uint32_t p = jd_pixel_scaled<S>(r, b, Y, Cb, Cr, row0 + row, x, cw);
-            uint8_t *o = out + ((size_t)(y_first + row) * ow + x) * 3;
-            o[0] = (uint8_t)p, o[1] = (uint8_t)(p >> 8), o[2] = (uint8_t)(p >> 16);
-        }
     }
 }
 
@@ -756,23 +487,34 @@ struct dd_jpegdec {
     DevBuf split_stats;
     PinBuf split_stats_host;
     hipEvent_t split_done = nullptr;
+    // DD_JPEGDEC_ANY_SIZE: g.H x g.W is the largest file accepted and `scale` the smallest denominator of a call; DD_JPEGDEC_STD_TABLES goes
+    // to the parser with the rest of the flags
+    bool any_size = false;
+    int flags = 0;
 };
 
 namespace ddk {
 
 // The header of one file into *rec, with the status a decoder of h x w gives it (a NULL or empty file: DD_JPEG_ST_NO_FRAME).  scans: NULL,
 // or where a decoder that takes progressive files keeps this file's scan script (n_scans 0 for every other file).
-int jpegdec_parse(const uint8_t *file, size_t n, int h, int w, dd_jpeg_info *rec, dd_jpeg_scans *scans) {
+// flags: the decoder's.  DD_JPEGDEC_STD_TABLES goes to the parser; with DD_JPEGDEC_ANY_SIZE h x w is the largest size accepted.
+int jpegdec_parse(const uint8_t *file, size_t n, int h, int w, dd_jpeg_info *rec, dd_jpeg_scans *scans, int flags) {
     char msg[320];
+    const int pf = flags & DD_JPEGDEC_STD_TABLES;
     if (scans) scans->n_scans = scans->n_tables = scans->n_levels = 0;
     if (!file || n == 0) {
         memset(rec, 0, sizeof(*rec));
         rec->status = DD_JPEG_ST_NO_FRAME;
         return rec->status;
     }
-    if ((scans ? jpd_parse_scans(file, n, rec, scans, msg, sizeof(msg)) : jpd_parse(file, n, rec, msg, sizeof(msg))) != DD_JPEG_R_OK) {
+    if ((scans ? jpd_parse_scans(file, n, rec, scans, msg, sizeof(msg), pf) : jpd_parse(file, n, rec, msg, sizeof(msg), pf)) != DD_JPEG_R_OK) {
         dd_set_error("%s", msg);
         rec->status = DD_JPEG_ST_HEADER;
+    } else if (flags & DD_JPEGDEC_ANY_SIZE) {
+        if (rec->height > h || rec->width > w) {
+            dd_set_error("jpeg decoder: a %d x %d file for a decoder of at most %d x %d", rec->width, rec->height, w, h);
+            rec->status = DD_JPEG_ST_SIZE;
+        }
     } else if (rec->height != h || rec->width != w) {
         dd_set_error("jpeg decoder: a %d x %d file for a decoder of %d x %d", rec->width, rec->height, w, h);
         rec->status = DD_JPEG_ST_SIZE;
@@ -784,12 +526,16 @@ int jpegdec_parse(const uint8_t *file, size_t n, int h, int w, dd_jpeg_info *rec
 // asynchronous); file i lies at bytes_host + recs_host[i].file_offset, all within n_bytes.  Fills the records' decoder fields, uploads
 // records and bytes in one copy each (then records `uploaded`, if given), and queues the kernels on s.  No host wait.
 // scans_host: NULL, or n scan scripts from jpegdec_parse, kept like the records (a decoder that takes progressive files).
+// scales: NULL, or (a decoder made with DD_JPEGDEC_ANY_SIZE) one scale denominator per file, none below the decoder's own.
 int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, dd_jpeg_scans *scans_host, const uint8_t *bytes_host, size_t n_bytes, int n, uint8_t *out_dev, int *status_dev,
-                   hipStream_t s, hipEvent_t uploaded) {
+                   hipStream_t s, hipEvent_t uploaded, const int *scales) {
     DD_REQUIRE(n >= 1 && n <= d->max_frames, DD_E_CAPACITY, "jpeg decoder: %d frames in a call (1 .. %d)", n, d->max_frames);
     DD_REQUIRE(n_bytes <= d->max_bytes, DD_E_CAPACITY, "jpeg decoder: %zu bytes of files in a call (at most %zu)", n_bytes, d->max_bytes);
     const JdGeom &g = d->g;
     DD_REQUIRE(!scans_host || d->progressive, DD_E_STATE, "jpeg decoder: scan scripts for a decoder that was not made to take progressive files");
+    DD_REQUIRE(!scales || d->any_size, DD_E_STATE, "jpeg decoder: a scale per file for a decoder that was not made with DD_JPEGDEC_ANY_SIZE");
+    size_t lds_at[4] = {0, 0, 0, 0};                            // DD_JPEGDEC_ANY_SIZE: per log2 of the scale, the LDS, whether a file takes it
+    bool any_at[4] = {false, false, false, false}, planes_at[4] = {false, false, false, false};
     long long total = 0, ptotal = 0, level_total[DD_JPEG_MAX_LEVELS] = {};
     int max_scans = 0, n_levels = 0, n_split = 0, max_sub = 0;
     size_t lds = 0;
@@ -827,10 +573,31 @@ int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, dd_jpeg_scans *scans_
         }
         DD_REQUIRE(r.file_offset >= 0 && (size_t)r.file_offset + (size_t)r.scan_offset + (size_t)r.scan_length <= n_bytes, DD_E_ARG,
                    "jpeg decoder: file %d lies outside the %zu bytes given", i, n_bytes);
-        const JdBand b = jd_band(r.width, r.ncomp, r.hmax, r.vmax, d->scale);
+        const int fs = scales ? scales[i] : d->scale;
+        DD_REQUIRE(jpd_scale_ok(fs) && fs >= d->scale, DD_E_ARG, "jpeg decoder: file %d at scale %d (1, 2, 4 or 8, and at least the decoder's %d)", i, fs, d->scale);
+        const JdBand b = jd_band(r.width, r.ncomp, r.hmax, r.vmax, fs);
         r.path = b.lds <= (size_t)JD_LDS_MAX ? DD_JPEGDEC_LDS : DD_JPEGDEC_PLANES;
         if (r.path == DD_JPEGDEC_LDS) lds = b.lds > lds ? b.lds : lds;
         else any_planes = true;
+        if (d->any_size) {
+            // these records came from put on other threads: everything the kernels index with is held to the decoder's buffers here,
+            // before anything is queued.  jd_geometry's strides are monotone in h and w, so a file that fits the sides fits them.
+            const long long blocks = (long long)r.mcus_x * r.mcus_y * r.blocks_per_mcu;
+            const long long crows = fs == 1 ? 8 : b.crows;
+            const long long plane_bytes = (long long)r.mcus_y * ((long long)b.yrows * b.Wy + (r.ncomp == 3 ? 2 * crows * b.Wc : 0));
+            DD_REQUIRE(r.height >= 1 && r.height <= g.H && r.width >= 1 && r.width <= g.W, DD_E_ARG, "jpeg decoder: file %d is %d x %d, the decoder holds at most %d x %d", i,
+                       r.width, r.height, g.W, g.H);
+            DD_REQUIRE(r.mcus_x == (r.width + 8 * r.hmax - 1) / (8 * r.hmax) && r.mcus_y == (r.height + 8 * r.vmax - 1) / (8 * r.vmax) && r.mcus_y <= g.max_bands, DD_E_ARG,
+                       "jpeg decoder: file %d: %d x %d MCUs for %d x %d pixels", i, r.mcus_x, r.mcus_y, r.width, r.height);
+            DD_REQUIRE(blocks * 64 <= g.coef_stride, DD_E_ARG, "jpeg decoder: file %d has %lld blocks, a frame's coefficients hold %lld", i, blocks, g.coef_stride / 64);
+            DD_REQUIRE(r.path == DD_JPEGDEC_LDS || plane_bytes <= g.plane_stride, DD_E_ARG, "jpeg decoder: file %d needs %lld bytes of planes, a frame holds %lld", i, plane_bytes,
+                       g.plane_stride);
+            const int lg = fs == 1 ? 0 : fs == 2 ? 1 : fs == 4 ? 2 : 3;
+            any_at[lg] = true;
+            if (r.path == DD_JPEGDEC_LDS) lds_at[lg] = b.lds > lds_at[lg] ? b.lds : lds_at[lg];
+            else planes_at[lg] = true;
+            r.path |= lg << 8;
+        }
         // DD_JPEGDEC_SPLIT: a baseline file that is one restart interval (no DRI, DRI 0, or a DRI of the MCU count or more) and longer than a
         // subsequence goes to jpeg_split_entropy_k, in subsequences of the decoder's size -- doubled, where DD_JPEGDEC_SPLIT_BYTES did not
         // fix it, until every lane of the workgroup has at most one, and in any case until the file's states fit the kernel's LDS;
@@ -927,6 +694,15 @@ int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, dd_jpeg_scans *scans_
     }
     if (d->profile) DD_HIP(hipEventRecord(d->ev[3], s));
     const unsigned grid = (unsigned)n * (unsigned)g.max_bands;
+    if (d->any_size) {                                          // one launch per scale that occurs; each passes over the other scales' files
+        const int rc = jpegdec_pixels_any(s, n, g.max_bands, g.coef_stride, g.plane_stride, lds_at, any_at, planes_at, recs, mark, coef, d->planes.as<uint8_t>(), out_dev, d->oh, d->ow);
+        if (rc != DD_OK) return rc;
+        if (d->profile) {
+            DD_HIP(hipEventRecord(d->ev[4], s));
+            d->profiled = true;
+        }
+        return DD_OK;
+    }
     if (d->scale != 1) {
         int rc = DD_OK;
         switch (d->scale) {
@@ -963,6 +739,17 @@ int dd_jpeg_parse_scans(const uint8_t *file_host, int64_t n, dd_jpeg_info *info,
     DD_REQUIRE(file_host && info && scans && n >= 0, DD_E_ARG, "dd_jpeg_parse_scans: NULL argument or a negative length");
     char msg[320];
     if (jpd_parse_scans(file_host, (size_t)n, info, scans, msg, sizeof(msg)) != DD_JPEG_R_OK) {
+        dd_set_error("%s", msg);
+        return DD_E_FORMAT;
+    }
+    return DD_OK;
+}
+
+int dd_jpeg_parse_flags(const uint8_t *file_host, int64_t n, int flags, dd_jpeg_info *info, dd_jpeg_scans *scans) {
+    DD_REQUIRE(file_host && info && n >= 0, DD_E_ARG, "dd_jpeg_parse_flags: NULL argument or a negative length");
+    DD_REQUIRE((flags & ~DD_JPEGDEC_STD_TABLES) == 0, DD_E_ARG, "dd_jpeg_parse_flags: flags 0x%x (DD_JPEGDEC_STD_TABLES or 0)", flags);
+    char msg[320];
+    if ((scans ? jpd_parse_scans(file_host, (size_t)n, info, scans, msg, sizeof(msg), flags) : jpd_parse(file_host, (size_t)n, info, msg, sizeof(msg), flags)) != DD_JPEG_R_OK) {
         dd_set_error("%s", msg);
         return DD_E_FORMAT;
     }
@@ -1012,7 +799,8 @@ static int jd_create(const char *who, dd_ctx *ctx, int h, int w, int scale, int 
     JdGeom g;
     if (int rc = jd_geometry(h, w, who, &g)) return rc;
     DD_REQUIRE(jpd_scale_ok(scale), DD_E_ARG, "%s: scale %d is none of 1, 2, 4, 8", who, scale);
-    DD_REQUIRE((flags & ~(DD_JPEGDEC_PROGRESSIVE | DD_JPEGDEC_SPLIT)) == 0, DD_E_ARG, "%s: flags 0x%x (DD_JPEGDEC_PROGRESSIVE, DD_JPEGDEC_SPLIT, both or 0)", who, flags);
+    DD_REQUIRE((flags & ~(DD_JPEGDEC_PROGRESSIVE | DD_JPEGDEC_SPLIT | DD_JPEGDEC_ANY_SIZE | DD_JPEGDEC_STD_TABLES)) == 0, DD_E_ARG,
+               "%s: flags 0x%x (DD_JPEGDEC_PROGRESSIVE, DD_JPEGDEC_SPLIT, DD_JPEGDEC_ANY_SIZE, DD_JPEGDEC_STD_TABLES, any of them or 0)", who, flags);
     int split_log2 = 6;                                             // 64 bytes, doubled per file until a lane has one subsequence: see the README's table
     const char *sb = (flags & DD_JPEGDEC_SPLIT) ? getenv("DD_JPEGDEC_SPLIT_BYTES") : nullptr;
     if (sb) {                                                       // the subsequence size of jpeg_split_entropy_k: a power of two, 16 .. 4096
@@ -1028,6 +816,7 @@ static int jd_create(const char *who, dd_ctx *ctx, int h, int w, int scale, int 
     DD_REQUIRE(d, DD_E_HIP, "%s: out of host memory", who);
     d->ctx = ctx, d->g = g, d->max_frames = max_frames, d->max_bytes = (size_t)max_bytes;
     d->scale = scale, d->oh = (h + scale - 1) / scale, d->ow = (w + scale - 1) / scale;
+    d->flags = flags, d->any_size = (flags & DD_JPEGDEC_ANY_SIZE) != 0;
     const char *lanes = getenv("DD_JPEGDEC_LANES");                 // intervals per wave of jpeg_entropy_k, for A/B runs: 1 .. 64
     if (lanes && atoi(lanes) >= 1 && atoi(lanes) <= 64) d->lanes = atoi(lanes);
     int rc = d->recs.reserve((size_t)max_frames * sizeof(dd_jpeg_info));
@@ -1137,24 +926,28 @@ int dd_jpegdec_split_stats(dd_jpegdec *d, int64_t *out_host) {
     return DD_OK;
 }
 
-int dd_jpegdec_decode(dd_jpegdec *d, const uint8_t *files_host, const int64_t *offsets, const int64_t *lengths, int n, uint8_t *out_dev, int *status_dev, void *stream) {
-    DD_REQUIRE(d && files_host && offsets && lengths && out_dev && status_dev, DD_E_ARG, "dd_jpegdec_decode: NULL argument");
-    DD_REQUIRE(n >= 1 && n <= d->max_frames, DD_E_CAPACITY, "dd_jpegdec_decode: %d frames (1 .. %d)", n, d->max_frames);
+static int jd_decode(const char *who, dd_jpegdec *d, const uint8_t *files_host, const int64_t *offsets, const int64_t *lengths, const int *scales, int n, uint8_t *out_dev,
+                     int *status_dev, void *stream) {
+    DD_REQUIRE(d && files_host && offsets && lengths && out_dev && status_dev, DD_E_ARG, "%s: NULL argument", who);
+    DD_REQUIRE(n >= 1 && n <= d->max_frames, DD_E_CAPACITY, "%s: %d frames (1 .. %d)", who, n, d->max_frames);
+    DD_REQUIRE(!scales || d->any_size, DD_E_STATE, "%s: a scale per file needs a decoder made with DD_JPEGDEC_ANY_SIZE", who);
+    for (int i = 0; scales && i < n; ++i)
+        DD_REQUIRE(jpd_scale_ok(scales[i]) && scales[i] >= d->scale, DD_E_ARG, "%s: file %d at scale %d (1, 2, 4 or 8, and at least the decoder's %d)", who, i, scales[i], d->scale);
     DD_DEVICE(d->ctx);
     hipStream_t s = dd_pick_stream(d->ctx, stream);
     dd_jpeg_info *recs = d->recs_host.as<dd_jpeg_info>();
     dd_jpeg_scans *scans = d->progressive ? d->scans_host.as<dd_jpeg_scans>() : nullptr;
     size_t n_bytes = 0;
     for (int i = 0; i < n; ++i) {
-        DD_REQUIRE(offsets[i] >= 0 && lengths[i] >= 0 && lengths[i] <= 0x7fffffffll, DD_E_ARG, "dd_jpegdec_decode: file %d at offset %lld, length %lld", i,
+        DD_REQUIRE(offsets[i] >= 0 && lengths[i] >= 0 && lengths[i] <= 0x7fffffffll, DD_E_ARG, "%s: file %d at offset %lld, length %lld", who, i,
                    (long long)offsets[i], (long long)lengths[i]);
         const size_t end = (size_t)offsets[i] + (size_t)lengths[i];
-        DD_REQUIRE(end <= d->max_bytes, DD_E_CAPACITY, "dd_jpegdec_decode: file %d ends at byte %zu, the decoder holds %zu", i, end, d->max_bytes);
-        ddk::jpegdec_parse(files_host + offsets[i], (size_t)lengths[i], d->g.H, d->g.W, &recs[i], scans ? &scans[i] : nullptr);
+        DD_REQUIRE(end <= d->max_bytes, DD_E_CAPACITY, "%s: file %d ends at byte %zu, the decoder holds %zu", who, i, end, d->max_bytes);
+        ddk::jpegdec_parse(files_host + offsets[i], (size_t)lengths[i], d->g.H, d->g.W, &recs[i], scans ? &scans[i] : nullptr, d->flags);
         recs[i].file_offset = offsets[i];
         if (lengths[i] && end > n_bytes) n_bytes = end;
     }
-    const int rc = ddk::jpegdec_launch(d, recs, scans, files_host, n_bytes, n, out_dev, status_dev, s, d->uploaded);
+    const int rc = ddk::jpegdec_launch(d, recs, scans, files_host, n_bytes, n, out_dev, status_dev, s, d->uploaded, scales);
     // the records' staging and the caller's bytes are free again once the two copies have run
     if (rc != DD_OK) {
         (void)hipStreamSynchronize(s);
@@ -1162,6 +955,15 @@ int dd_jpegdec_decode(dd_jpegdec *d, const uint8_t *files_host, const int64_t *o
     }
     DD_HIP(hipEventSynchronize(d->uploaded));
     return DD_OK;
+}
+
+int dd_jpegdec_decode(dd_jpegdec *d, const uint8_t *files_host, const int64_t *offsets, const int64_t *lengths, int n, uint8_t *out_dev, int *status_dev, void *stream) {
+    return jd_decode("dd_jpegdec_decode", d, files_host, offsets, lengths, nullptr, n, out_dev, status_dev, stream);
+}
+
+int dd_jpegdec_decode_scales(dd_jpegdec *d, const uint8_t *files_host, const int64_t *offsets, const int64_t *lengths, const int *scales, int n, uint8_t *out_dev,
+                             int *status_dev, void *stream) {
+    return jd_decode("dd_jpegdec_decode_scales", d, files_host, offsets, lengths, scales, n, out_dev, status_dev, stream);
 }
 
 }  // extern "C"

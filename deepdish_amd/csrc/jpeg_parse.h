@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstring>
 #include "../../include/deepdish_hip.h"
+#include "jpeg_tables.h"
 
 constexpr int JPD_MAX_SIDE = 8192;
 
@@ -86,8 +87,23 @@ static inline size_t jpd_huffman(const uint8_t *d, size_t p, size_t e, dd_jpeg_i
     return jpd_huffman_build(d, p, e, &o->huff[tc * 2 + th], o, msg, msgcap);
 }
 
-// Returns DD_JPEG_R_OK or the reason (also o->reason); msg gets the text.
-static inline int jpd_parse(const uint8_t *d, size_t n, dd_jpeg_info *o, char *msg, size_t msgcap) {
+// DD_JPEGDEC_STD_TABLES: ITU-T T.81 Annex K.3's table for class tc (0 DC, 1 AC) and slot th (0 luminance, 1 chrominance) into *h, in the
+// same look-up form a DHT segment gives -- what libjpeg-turbo's jstdhuff.c puts into every slot 0 / 1 a file leaves undefined (UVC cameras
+// in MJPG mode and MJPG AVI frames carry no DHT at all).
+static inline void jpd_huffman_std(int tc, int th, dd_jpeg_huff *h, dd_jpeg_info *o, char *msg, size_t msgcap) {
+    uint8_t seg[1 + 16 + 162];
+    const uint8_t *bits = tc ? (th ? JP_AC_CHROMA_BITS : JP_AC_LUMA_BITS) : (th ? JP_DC_CHROMA_BITS : JP_DC_LUMA_BITS);
+    const uint8_t *vals = tc ? (th ? JP_AC_CHROMA_VALS : JP_AC_LUMA_VALS) : JP_DC_VALS;
+    const size_t nv = tc ? 162 : 12;
+    seg[0] = (uint8_t)(tc << 4 | th);
+    std::memcpy(seg + 1, bits, 16);
+    std::memcpy(seg + 17, vals, nv);
+    (void)jpd_huffman_build(seg, 0, 17 + nv, h, o, msg, msgcap);
+}
+
+// Returns DD_JPEG_R_OK or the reason (also o->reason); msg gets the text.  flags: 0, or DD_JPEGDEC_STD_TABLES: at the SOS every DC / AC slot
+// 0 or 1 that a component references and the file has not defined receives the Annex K.3 table of that slot; defined slots are untouched.
+static inline int jpd_parse(const uint8_t *d, size_t n, dd_jpeg_info *o, char *msg, size_t msgcap, int flags = 0) {
     std::memset(o, 0, sizeof(*o));
     if (msgcap) msg[0] = 0;
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) JPD_REFUSE(DD_JPEG_R_TRUNCATED, "dd_jpeg_parse: truncated or not a JPEG file: no SOI marker in %zu bytes", n);
@@ -173,6 +189,10 @@ static inline int jpd_parse(const uint8_t *d, size_t n, dd_jpeg_info *o, char *m
             if (ss != 0 || se != 63 || a != 0) JPD_REFUSE(DD_JPEG_R_PROGRESSIVE, "dd_jpeg_parse: a scan with Ss %d, Se %d, Ah/Al 0x%02X: progressive parameters are refused", ss, se, a);
             for (int c = 0; c < ns; ++c) {
                 if (o->td[c] > 1 || o->ta[c] > 1) JPD_REFUSE(DD_JPEG_R_HUFFMAN, "dd_jpeg_parse: component %d names Huffman tables %d / %d (0 and 1 only)", c, o->td[c], o->ta[c]);
+                if (flags & DD_JPEGDEC_STD_TABLES) {
+                    if (!o->huff[o->td[c]].defined) jpd_huffman_std(0, o->td[c], &o->huff[o->td[c]], o, msg, msgcap);
+                    if (!o->huff[2 + o->ta[c]].defined) jpd_huffman_std(1, o->ta[c], &o->huff[2 + o->ta[c]], o, msg, msgcap);
+                }
                 if (!o->huff[o->td[c]].defined || !o->huff[2 + o->ta[c]].defined)
                     JPD_REFUSE(DD_JPEG_R_UNDEFINED, "dd_jpeg_parse: component %d references a Huffman table the file does not define", c);
                 if (!o->quant_defined[o->tq[c]]) JPD_REFUSE(DD_JPEG_R_UNDEFINED, "dd_jpeg_parse: component %d references quant table %d, which the file does not define", c, o->tq[c]);
@@ -207,10 +227,11 @@ static inline int jpd_parse(const uint8_t *d, size_t n, dd_jpeg_info *o, char *m
         return (code);                             \
     } while (0)
 
-static inline int jpd_parse_scans(const uint8_t *d, size_t n, dd_jpeg_info *o, dd_jpeg_scans *S, char *msg, size_t msgcap) {
+// flags: jpd_parse's, for the baseline files only; a progressive file with an undefined table is refused whatever they say.
+static inline int jpd_parse_scans(const uint8_t *d, size_t n, dd_jpeg_info *o, dd_jpeg_scans *S, char *msg, size_t msgcap, int flags = 0) {
     S->n_scans = S->n_tables = S->n_levels = S->reserved = 0;
     std::memset(S->level_base, 0, sizeof(S->level_base));
-    if (jpd_parse(d, n, o, msg, msgcap) != DD_JPEG_R_PROGRESSIVE) return o->reason;
+    if (jpd_parse(d, n, o, msg, msgcap, flags) != DD_JPEG_R_PROGRESSIVE) return o->reason;
     // jpd_parse has checked SOI and every segment in front of the SOF2 (or of the scan with progressive parameters in a baseline frame)
     char base_msg[320];
     std::snprintf(base_msg, sizeof(base_msg), "%s", msg);

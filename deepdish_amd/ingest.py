@@ -19,7 +19,9 @@ With `pixel_format='jpeg'` a slot holds baseline JPEG files, what an IP camera's
 parses its header on the calling thread, `submit(slot)` uploads the bytes in use and decodes on the copy stream (csrc/jpeg_dec.hip,
 libjpeg's arithmetic restated), and `status(slot)` tells per stream whether its frame is good (deepdish_amd.jpeg.ST_*).  `jpeg_scale=2`, 4, 8
 or 'auto' decodes at that fraction (libjpeg's scale_denom, deepdish_amd.jpeg.JpegDecoder(scale=...)) in front of the resize: megapixel
-cameras feeding a 640 x 480 pipeline never have their full-size frames written."""
+cameras feeding a 640 x 480 pipeline never have their full-size frames written.  `jpeg_any_size=True` makes src_size the largest file
+accepted, not the only one: cameras of every mode share one ring, each file stretched to dst_size as the reference's
+cv2.resize(frame, self.input_size) does (deepdish.py:867), and `source_sizes(slot)` says what each stream sent."""
 import ctypes
 import numpy as np
 
@@ -32,7 +34,7 @@ PACKED_422 = ('yuy2', 'uyvy')
 
 class FrameIngest:
     def __init__(self, n_streams, src_size, dst_size=None, slots=2, flip=False, context=None, pixel_format='bgr', jpeg_slot_bytes=None, jpeg_scale=1, jpeg_progressive=False,
-                 jpeg_split=False):
+                 jpeg_split=False, jpeg_any_size=False, jpeg_std_tables=False):
         """src_size / dst_size: (width, height) like the reference's `input_size`; dst defaults to src.
         pixel_format: what a slot holds, 'bgr' | 'nv12' | 'i420' (4:2:0 needs an even width and height) | 'yuy2' | 'uyvy' (packed 4:2:2,
         named by FOURCC: an even width, any height) | 'jpeg'; the consumer always gets BGR.  jpeg_slot_bytes: the size of a JPEG slot's arena, by default n_streams * width * height * 3 // 8.
@@ -42,7 +44,16 @@ class FrameIngest:
         jpeg_progressive ('jpeg' only): take progressive (SOF2) files as well as baseline ones, at any jpeg_scale
         (deepdish_amd.jpeg.JpegDecoder(progressive=True)); without it such a file is ST_HEADER, as ever.
         jpeg_split ('jpeg' only): files without restart markers are decoded by a workgroup each, not by one lane
-        (deepdish_amd.jpeg.JpegDecoder(split=True)); the frames are the same."""
+        (deepdish_amd.jpeg.JpegDecoder(split=True)); the frames are the same.
+        jpeg_any_size ('jpeg' only, a ValueError otherwise): src_size is the largest file accepted.  A file with 1 <= height <= src height and
+        1 <= width <= src width is ST_OK and is stretched to dst_size (a file of exactly twice dst_size takes the 2 x INTER_AREA shortcut); one
+        with either side larger is ST_SIZE and absent.  A camera may change its size from one frame to the next.  jpeg_scale='auto' then means
+        the draft rule per file, draft_scale((file_w, file_h), dst_size), worked out in put(); an integer is that denominator for every file.
+        Every submit decodes into a staging buffer of uniform slots, n_streams * ceil(height / scale) * ceil(width / scale) * 3 bytes -- with
+        'auto' or 1 that is n_streams * height * width * 3: 9.6 GB for 1 536 streams accepting up to 1920 x 1080.  It is the price of uniform
+        slots and the caller's to size.
+        jpeg_std_tables ('jpeg' only): baseline files that leave a Huffman table slot 0 / 1 undefined (MJPG cameras send no DHT segment) decode
+        with the Annex K.3 tables (deepdish_amd.jpeg.JpegDecoder(std_tables=True)); without it such a file is ST_HEADER, as ever."""
         self._h = None
         if pixel_format not in PIXEL_FORMATS:
             raise ValueError("pixel_format %r is none of 'bgr', 'nv12', 'i420', 'yuy2', 'uyvy', 'jpeg'%s"
@@ -56,6 +67,14 @@ class FrameIngest:
             raise ValueError('%s frames need an even width, got %dx%d' % (pixel_format, self.sw, self.sh))
         if pixel_format != 'jpeg' and jpeg_scale != 1:
             raise ValueError("jpeg_scale %r: only a 'jpeg' ring decodes, a %r ring has nothing to scale" % (jpeg_scale, pixel_format))
+        if pixel_format != 'jpeg' and jpeg_any_size:
+            raise ValueError("jpeg_any_size: only a 'jpeg' ring decodes, a %r ring has no files to take" % (pixel_format,))
+        if pixel_format != 'jpeg' and jpeg_std_tables:
+            raise ValueError("jpeg_std_tables: only a 'jpeg' ring decodes, a %r ring has no files to take" % (pixel_format,))
+        self.jpeg_any_size, self.jpeg_std_tables = bool(jpeg_any_size), bool(jpeg_std_tables)
+        self.jpeg_scale_auto = self.jpeg_any_size and jpeg_scale == 'auto'          # per file, in put(); the slots are sized for scale 1
+        if self.jpeg_scale_auto:
+            jpeg_scale = 1
         if jpeg_scale == 'auto':
             from .jpeg import draft_scale
             jpeg_scale = draft_scale((self.sw, self.sh), (self.dw, self.dh))
@@ -76,10 +95,10 @@ class FrameIngest:
                                          ctypes.byref(h)), 'dd_ingest_create')
         elif pixel_format == 'jpeg':
             self.jpeg_slot_bytes = int(jpeg_slot_bytes) if jpeg_slot_bytes else self.S * self.sw * self.sh * 3 // 8
-            if self.jpeg_progressive or self.jpeg_split:
-                flags = (1 if self.jpeg_progressive else 0) | (2 if self.jpeg_split else 0)
+            if self.jpeg_progressive or self.jpeg_split or self.jpeg_any_size or self.jpeg_std_tables:
+                flags = (1 if self.jpeg_progressive else 0) | (2 if self.jpeg_split else 0) | (4 if self.jpeg_any_size else 0) | (8 if self.jpeg_std_tables else 0)
                 check(lib().dd_ingest_create_jpeg_ex(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
-                                                     self.jpeg_scale, flags, self.jpeg_slot_bytes, ctypes.byref(h)), 'dd_ingest_create_jpeg_ex')
+                                                     0 if self.jpeg_scale_auto else self.jpeg_scale, flags, self.jpeg_slot_bytes, ctypes.byref(h)), 'dd_ingest_create_jpeg_ex')
             elif self.jpeg_scale == 1:
                 check(lib().dd_ingest_create_jpeg(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
                                                   self.jpeg_slot_bytes, ctypes.byref(h)), 'dd_ingest_create_jpeg')
@@ -133,6 +152,13 @@ class FrameIngest:
         non-zero status has unspecified pixels in its own frame and costs the others nothing."""
         out = np.empty(self.S, np.int32)
         check(lib().dd_ingest_status(self._h, int(slot), out.ctypes.data_as(P)), 'dd_ingest_status')
+        return out
+
+    def source_sizes(self, slot):
+        """jpeg_any_size rings: int32 [S, 3] = (width, height, scale) of the file each stream put into the slot, zeros where nothing was put
+        or the header was refused (a file too large keeps the size it stated).  What put() learnt on the host: it does not wait."""
+        out = np.zeros((self.S, 3), np.int32)
+        check(lib().dd_ingest_source_sizes(self._h, int(slot), out.ctypes.data_as(P)), 'dd_ingest_source_sizes')
         return out
 
     def present(self, slot):

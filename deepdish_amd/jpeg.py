@@ -26,7 +26,14 @@ refused as before (reason 'progressive', ST_HEADER).
 Files without restart markers -- what an MJPEG camera, cv2.imencode and Pillow write by default -- are one entropy-coded segment, which the
 decoder gives to a single lane.  `JpegDecoder(H, W, split=True)` and `FrameIngest(..., jpeg_split=True)` cut such a scan into subsequences
 of DD_JPEGDEC_SPLIT_BYTES (by default 64, doubled per file until a workgroup's lanes have one each) that many lanes decode from guessed states until they agree (jpeg_split_entropy_k); the frames
-are the same bytes.  `split_stats()` says what the last decode took."""
+are the same bytes.  `split_stats()` says what the last decode took.
+
+A camera fleet delivers VGA, 720p, 1080p and 4K side by side, and the reference stretches whatever arrives to its input size (deepdish.py:867).
+`JpegDecoder(H, W, any_size=True)` and `FrameIngest(..., jpeg_any_size=True)` take every file of at most H x W, each at its own scale
+(`decode(files, scales=[...])`; on the ring `jpeg_scale='auto'` is then Pillow's draft rule per file), into the top-left corner of uniform
+slots.  UVC webcams in MJPG mode and MJPG AVI frames carry no DHT segment: `parse(file, std_tables=True)`, `JpegDecoder(..., std_tables=True)`
+and `FrameIngest(..., jpeg_std_tables=True)` give every undefined table slot 0 / 1 of a baseline file its ITU-T T.81 Annex K.3 table, as
+libjpeg-turbo does.  Both are off unless asked for."""
 import ctypes
 
 import numpy as np
@@ -136,7 +143,7 @@ REASONS = {0: 'ok', 1: 'truncated', 2: 'progressive', 3: 'arithmetic', 4: 'lossl
            8: 'scans', 9: 'huffman', 10: 'undefined', 11: 'size', 12: 'segment',
            13: 'ac_components', 14: 'ac_before_dc', 15: 'first_ah', 16: 'refinement', 17: 'incomplete', 18: 'capacity'}
 MAX_SCANS, MAX_TABLES, MAX_LEVELS = 64, 32, 16
-DEC_PROGRESSIVE, DEC_SPLIT = 1, 2
+DEC_PROGRESSIVE, DEC_SPLIT, DEC_ANY_SIZE, DEC_STD_TABLES = 1, 2, 4, 8
 
 
 class _Huff(ctypes.Structure):
@@ -167,7 +174,7 @@ class JpegScans(ctypes.Structure):
                 ('level_base', ctypes.c_int32 * MAX_LEVELS), ('scan', JpegScan * MAX_SCANS), ('pool', _Huff * MAX_TABLES)]
 
 
-def parse(file, progressive=False):
+def parse(file, progressive=False, std_tables=False):
     """The header of a baseline JPEG file, SOI .. the first SOS, as dd_jpeg_parse reads it -> dict.  Needs no device.  A file that is
     refused raises DeepDishHipError with .reason (a word of REASONS) and the reason spelt out in the message.
 
@@ -175,12 +182,21 @@ def parse(file, progressive=False):
     ('sof' 0xC2, no 'td' / 'ta' / 'huff', 'n_intervals' 0) and 'scans', one dict per SOS in file order -- 'comps', 'ss', 'se', 'ah', 'al',
     'restart_interval' (the DRI in force: MCUs for a scan of several components, the component's blocks for one), 'blocks_x', 'blocks_y',
     'n_intervals', 'level', 'offset', 'length' and 'dc' / 'ac', the (bits, vals) of the tables it reads -- with 'n_levels' and 'n_tables'.  A
-    baseline file gives the same dict as without the option."""
+    baseline file gives the same dict as without the option.
+
+    std_tables=True (dd_jpeg_parse_flags): every DC / AC table slot 0 or 1 that a component of a baseline file references and the file does
+    not define is the Annex K.3 table of that slot (0 luminance, 1 chrominance), in 'huff' like a table the file carries; without it such a
+    file is refused with reason 'undefined'.  A table id above 1 and a progressive file with an undefined table stay refused."""
     data = bytes(file)
     info = JpegInfo()
     scans = JpegScans() if progressive else None
-    who = 'dd_jpeg_parse_scans' if progressive else 'dd_jpeg_parse'
-    rc = lib().dd_jpeg_parse_scans(data, len(data), ctypes.byref(info), ctypes.byref(scans)) if progressive else lib().dd_jpeg_parse(data, len(data), ctypes.byref(info))
+    who = 'dd_jpeg_parse_flags' if std_tables else 'dd_jpeg_parse_scans' if progressive else 'dd_jpeg_parse'
+    if std_tables:
+        rc = lib().dd_jpeg_parse_flags(data, len(data), DEC_STD_TABLES, ctypes.byref(info), ctypes.byref(scans) if progressive else None)
+    elif progressive:
+        rc = lib().dd_jpeg_parse_scans(data, len(data), ctypes.byref(info), ctypes.byref(scans))
+    else:
+        rc = lib().dd_jpeg_parse(data, len(data), ctypes.byref(info))
     if rc != 0:
         msg = lib().dd_last_error()
         err = DeepDishHipError('%s failed (%d): %s' % (who, rc, msg.decode() if msg else '?'))
@@ -253,9 +269,18 @@ class JpegDecoder:
 
     split=True, with any scale and with or without progressive: a baseline file that is a single restart interval and whose scan is longer
     than DD_JPEGDEC_SPLIT_BYTES (read here; a power of two, 16 .. 4096; 64 when not set) is decoded by a workgroup, not by one lane; every
-    other file of the call goes the usual way.  Frames and statuses are the same; split_stats() counts what the last decode did."""
+    other file of the call goes the usual way.  Frames and statuses are the same; split_stats() counts what the last decode did.
 
-    def __init__(self, H, W, max_frames=16, max_bytes=None, context=None, scale=1, progressive=False, split=False):
+    any_size=True, with any of the above: H x W is the largest file accepted, not the only one.  A file with 1 <= height <= H and
+    1 <= width <= W is ST_OK, one with either side larger ST_SIZE.  The frames stay [n, out_H, out_W, 3]: frame i is the top-left
+    ceil(h_i / s_i) x ceil(w_i / s_i) of its slot -- the pixels a decoder of that file's own size and scale gives -- and no other byte of the
+    slot is written.  decode(files, scales=[...]) gives each file its own denominator; `scale` is then the smallest a call may use (it fixes
+    out_H x out_W), and a smaller entry raises (DD_E_ARG).
+
+    std_tables=True: a baseline file that leaves a Huffman table slot 0 / 1 undefined (MJPG cameras send no DHT segment) decodes with the
+    Annex K.3 table there, as libjpeg-turbo does; see parse(file, std_tables=True).  Without it such a file is ST_HEADER."""
+
+    def __init__(self, H, W, max_frames=16, max_bytes=None, context=None, scale=1, progressive=False, split=False, any_size=False, std_tables=False):
         from .runtime import default_context
         self.ctx = context or default_context()
         self.H, self.W, self.max_frames = int(H), int(W), int(max_frames)
@@ -264,11 +289,14 @@ class JpegDecoder:
         self.scale = scale
         self.progressive = bool(progressive)
         self.split = bool(split)
+        self.any_size = bool(any_size)
+        self.std_tables = bool(std_tables)
         h = P()
         if scale != 1 and (not isinstance(scale, int) or isinstance(scale, bool)):
             raise ValueError('scale %r is none of 1, 2, 4, 8' % (scale,))
-        if self.progressive or self.split:
-            flags = (DEC_PROGRESSIVE if self.progressive else 0) | (DEC_SPLIT if self.split else 0)
+        if self.progressive or self.split or self.any_size or self.std_tables:
+            flags = ((DEC_PROGRESSIVE if self.progressive else 0) | (DEC_SPLIT if self.split else 0) | (DEC_ANY_SIZE if self.any_size else 0)
+                     | (DEC_STD_TABLES if self.std_tables else 0))
             check(lib().dd_jpegdec_create_ex(self.ctx.handle, self.H, self.W, scale, flags, self.max_frames, self.max_bytes, ctypes.byref(h)),
                   'dd_jpegdec_create_ex')
         elif scale == 1:
@@ -314,9 +342,10 @@ class JpegDecoder:
         check(lib().dd_jpegdec_split_stats(self._h, out), 'dd_jpegdec_split_stats')
         return dict(zip(('files', 'subsequences', 'max_rounds', 'lane_decodes'), (int(v) for v in out)))
 
-    def decode(self, files, out=None, status=None, stream=None):
+    def decode(self, files, out=None, status=None, stream=None, scales=None):
         """files: a list of bytes objects -> (u8 [n, out_H, out_W, 3], int32 [n]).  out / status: tensors to write instead of new ones.  Queued on the context's stream (or
-        `stream`): `context.sync()` before torch reads the result on another stream."""
+        `stream`): `context.sync()` before torch reads the result on another stream.  scales (any_size=True only): one of 1, 2, 4, 8 per
+        file, none below the decoder's `scale`."""
         import torch
         n = len(files)
         lens = np.array([len(f) for f in files], np.int64)
@@ -335,6 +364,13 @@ class JpegDecoder:
         assert tuple(out.shape) == (n, self.out_H, self.out_W, 3) and out.dtype == torch.uint8 and out.is_contiguous()
         assert tuple(status.shape) == (n,) and status.dtype == torch.int32
         torch.cuda.current_stream(out.device).synchronize()
+        if scales is not None:
+            sc = np.ascontiguousarray(scales, np.int32)
+            if sc.shape != (n,):
+                raise ValueError('scales: %d entries for %d files' % (sc.size, n))
+            check(lib().dd_jpegdec_decode_scales(self._h, buf, offs.ctypes.data_as(P), lens.ctypes.data_as(P), sc.ctypes.data_as(P), n, P(out.data_ptr()),
+                                                 P(status.data_ptr()), stream), 'dd_jpegdec_decode_scales')
+            return out, status
         check(lib().dd_jpegdec_decode(self._h, buf, offs.ctypes.data_as(P), lens.ctypes.data_as(P), n, P(out.data_ptr()), P(status.data_ptr()), stream),
               'dd_jpegdec_decode')
         return out, status

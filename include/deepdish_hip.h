@@ -870,7 +870,10 @@ int dd_jpeg_encode(dd_jpeg *enc, const uint8_t *frames_dev, int n, uint8_t *out_
  * Image.open(f).convert('RGB') with the channels swapped, byte for byte (tests/jpeg_dec_ref.py).  Parity with OpenCV's own decode is
  * not pinned.
  * Accepted: SOF0, and SOF1 at 8 bits; 1 component, or 3 with luma sampled 1x1, 2x1 or 2x2 over 1x1 chroma; one interleaved scan; DC / AC
- * tables 0 and 1; any DRI.  Everything else is refused by name (DD_JPEG_R_*). */
+ * tables 0 and 1; any DRI.  Everything else is refused by name (DD_JPEG_R_*).
+ * Options of dd_jpegdec_create_ex / dd_ingest_create_jpeg_ex, all off unless asked for (below): DD_JPEGDEC_PROGRESSIVE (SOF2 files),
+ * DD_JPEGDEC_SPLIT (marker-less scans over many lanes), DD_JPEGDEC_ANY_SIZE (files of any size up to the decoder's, each at its own scale),
+ * DD_JPEGDEC_STD_TABLES (the Annex K.3 tables where a file defines none). */
 #define DD_E_FORMAT     -5   /* input data (a file) is malformed or of a kind that is refused; the message names the reason */
 /* why dd_jpeg_parse refused a file (dd_jpeg_info.reason) */
 #define DD_JPEG_R_OK           0
@@ -883,13 +886,13 @@ int dd_jpeg_encode(dd_jpeg *enc, const uint8_t *frames_dev, int n, uint8_t *out_
 #define DD_JPEG_R_SAMPLING     7   /* 4:4:0, 4:1:1, sub-sampled luma ... */
 #define DD_JPEG_R_SCANS        8   /* a scan that does not hold every component in order */
 #define DD_JPEG_R_HUFFMAN      9   /* a DHT that over-subscribes the code space, names more than 256 symbols or a table id above 1 */
-#define DD_JPEG_R_UNDEFINED   10   /* a component references a table the file does not define */
+#define DD_JPEG_R_UNDEFINED   10   /* a component references a table the file does not define (a Huffman slot 0 / 1: unless DD_JPEGDEC_STD_TABLES) */
 #define DD_JPEG_R_SIZE        11   /* height or width of 0 or above 8192 */
 #define DD_JPEG_R_SEGMENT     12   /* a segment whose content contradicts its length */
 /* per-frame status of a decode (int32) */
 #define DD_JPEG_ST_OK          0
 #define DD_JPEG_ST_HEADER      1   /* the header was refused (dd_jpeg_parse says why); nothing is written for the frame */
-#define DD_JPEG_ST_SIZE        2   /* the SOF size is not the decoder's H x W; nothing is written */
+#define DD_JPEG_ST_SIZE        2   /* the SOF size is not the decoder's H x W (DD_JPEGDEC_ANY_SIZE: a side is larger than it); nothing is written */
 #define DD_JPEG_ST_DATA        3   /* corrupt or truncated entropy-coded data: the frame holds unspecified bytes, inside its own H x W x 3 */
 #define DD_JPEG_ST_NO_FRAME    4   /* ingest ring: no file was put for this stream since the last submit; nothing is written */
 /* One Huffman table: Annex C's bits / vals, and what the kernel reads: look[b] = length << 8 | symbol for the code of at most 8 bits that
@@ -1032,6 +1035,45 @@ int dd_ingest_create_jpeg_ex(dd_ctx *ctx, int slots, int n_streams, int src_h, i
  * file took (at most its subsequences + 1), and decodes of a subsequence in the rounds (the storing decode not counted).  All zeros for a
  * decoder made without DD_JPEGDEC_SPLIT. */
 int dd_jpegdec_split_stats(dd_jpegdec *dec, int64_t *out_host);
+
+/* ---- files of any size up to the decoder's, each at its own scale: a flag for dd_jpegdec_create_ex and dd_ingest_create_jpeg_ex, beside
+ * the others, at any scale.  A camera fleet delivers VGA, 720p, 1080p and 4K side by side, and a camera that reconnects changes mode; the
+ * reference stretches whatever arrives to its input size (cv2.resize(frame, self.input_size), deepdish.py:867).  With the flag h x w is
+ * the largest file accepted: a file with 1 <= height <= h and 1 <= width <= w is DD_JPEG_ST_OK, one with either side larger is
+ * DD_JPEG_ST_SIZE, writes nothing, and both sizes stand in dd_last_error().  Path (DD_JPEGDEC_LDS / _PLANES) and dword stores are
+ * decided per file.  out_dev stays u8 [n][OH][OW][3], OH = ceil(h / scale), OW = ceil(w / scale), rows OW * 3 bytes apart: frame i is
+ * the top-left ceil(h_i / s_i) x ceil(w_i / s_i) of its slot, and no other byte of the slot is written.  The pixels are those of a
+ * decoder made for that file's own size and scale, byte for byte: jpeg_pixels_any_k<S> and jpeg_planes_any_k<S> are jpeg_pixels(_scaled)_k
+ * and jpeg_planes(_scaled)_k with the pitch, the frame stride and the output size taken from the slot and the record; one launch per
+ * scale that occurs in the call, each passing over the files of another scale.  The markers and entropy kernels are per record as ever.
+ * On the device dd_jpeg_info.path holds the path in bits 0 .. 7 and the log2 of the file's scale in bits 8 .. 15 (only with this flag);
+ * dd_jpeg_info.reserved stays the split log2.  Without the flag nothing changes. */
+#define DD_JPEGDEC_ANY_SIZE 4
+/* dd_jpegdec_decode with one scale denominator per file: scales int32 [n] of 1, 2, 4, 8, or NULL for the decoder's own scale in every
+ * file (then this is dd_jpegdec_decode).  The decoder's own scale is the smallest a call may use -- it fixes OH x OW -- and a smaller
+ * entry, or one that is none of 1, 2, 4, 8, is DD_E_ARG.  A scales array needs a decoder made with DD_JPEGDEC_ANY_SIZE (DD_E_STATE). */
+int dd_jpegdec_decode_scales(dd_jpegdec *dec, const uint8_t *files_host, const int64_t *offsets, const int64_t *lengths, const int *scales, int n,
+                             uint8_t *out_dev, int *status_dev, void *stream);
+/* The ring made with DD_JPEGDEC_ANY_SIZE: src_h x src_w is the largest file accepted.  dd_ingest_jpeg_put parses, records the file's size
+ * and scale -- `scale` for every file, or, with scale 0 (accepted with this flag only), Pillow's draft rule per file,
+ * dd_jpeg_draft_scale(file_w, file_h, dst_w, dst_h), the slots then being sized for scale 1 -- and dd_ingest_submit always decodes into
+ * the staging buffer, n_streams * OH * OW * 3 bytes (n_streams * src_h * src_w * 3 with scale 0 or 1: the caller's to size), builds one
+ * crop box per stream from its record, (0, 0, w_out, h_out) with the ring's flip, empty where the host knows the status is not OK,
+ * uploads the boxes through the slot's pinned memory without a host wait and launches crop_resize from there to dst_h x dst_w.  A file of
+ * exactly twice dst takes crop_resize's INTER_AREA shortcut.  dd_ingest_source_sizes: sizes_host int32 [n_streams][3] = (width, height,
+ * scale) of what was put into the slot since its last submit was taken up, zeros where nothing was put or the header was refused; host
+ * knowledge, no wait.  DD_E_STATE on a ring made without the flag. */
+int dd_ingest_source_sizes(dd_ingest *g, int slot, int *sizes_host);
+
+/* ---- default Huffman tables: a flag for dd_jpegdec_create_ex, dd_ingest_create_jpeg_ex and dd_jpeg_parse_flags.  UVC webcams in MJPG mode
+ * and MJPG AVI frames carry no DHT segment and rely on the Annex K.3 tables; libjpeg-turbo fills every undefined slot 0 / 1 with them
+ * (jstdhuff.c).  With the flag, at the SOS of a baseline file (SOF0, SOF1 at 8 bits) every DC / AC slot 0 or 1 that a component references
+ * and the file has not defined receives the table of that slot -- 0 luminance, 1 chrominance -- in dd_jpeg_info.huff[], look-up form and
+ * `defined` included; defined slots are untouched, and behind the parser nothing knows the difference.  Still refused as ever: a table id
+ * above 1, a progressive file with an undefined table, everything else.  Without the flag such a file is DD_JPEG_R_UNDEFINED. */
+#define DD_JPEGDEC_STD_TABLES 8
+/* dd_jpeg_parse (scans NULL) or dd_jpeg_parse_scans (scans given) with flags: 0 or DD_JPEGDEC_STD_TABLES; anything else is DD_E_ARG. */
+int dd_jpeg_parse_flags(const uint8_t *file_host, int64_t n, int flags, dd_jpeg_info *info, dd_jpeg_scans *scans);
 
 /* ---------------------------------------------------------------- multi-GPU
  * Sum of the per-stream count vectors (pos, neg, int, del per label; deepdish.py:1141-1145).
