@@ -126,6 +126,8 @@ __device__ __forceinline__ unsigned dd_xcd_remap(unsigned id, unsigned n) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
 }
 
+struct JdPerScale;                              // csrc/jpeg_dec_plan.h
+
 // ---- kernel launchers shared between the flat C ABI and the tracker / pipeline handles ----
 namespace ddk {
 int kf_initiate(hipStream_t s, double *means, double *covs, const int *slots, const double *xyah, int n);
@@ -173,9 +175,9 @@ int yuv422_resize(hipStream_t s, const uint8_t *src, int n, int H, int W, int or
 int jpegdec_parse(const uint8_t *file, size_t n, int h, int w, dd_jpeg_info *rec, dd_jpeg_scans *scans, int flags = 0);
 int jpegdec_launch(dd_jpegdec *dec, dd_jpeg_info *recs_host, dd_jpeg_scans *scans_host, const uint8_t *bytes_host, size_t n_bytes, int n, uint8_t *out_dev, int *status_dev,
                    hipStream_t s, hipEvent_t uploaded, const int *scales = nullptr);
-// csrc/jpeg_dec_any.hip: the pixel stage of a DD_JPEGDEC_ANY_SIZE decoder, per log2 of the scale the LDS, whether a file has it, whether one takes the planes path
-int jpegdec_pixels_any(hipStream_t s, int n, int max_bands, long long coef_stride, long long plane_stride, const size_t *lds_at, const bool *any_at, const bool *planes_at,
-                       const dd_jpeg_info *recs, const int *mark, const int16_t *coef, uint8_t *planes, uint8_t *out_dev, int OH, int OW);
+// csrc/jpeg_dec_any.hip: the pixel stage of a DD_JPEGDEC_ANY_SIZE decoder; per_scale: the call plan's (csrc/jpeg_dec_plan.h)
+int jpegdec_pixels_any(hipStream_t s, int n, int max_bands, long long coef_stride, long long plane_stride, const JdPerScale &per_scale, const dd_jpeg_info *recs,
+                       const int *mark, const int16_t *coef, uint8_t *planes, uint8_t *out_dev, int OH, int OW);
 int resize_lanczos(hipStream_t s, int device, const uint8_t *src, int H, int W, int src_c, int swap_rb, uint8_t *dst,
                    int h, int w, uint8_t *tmp, int batch);
 size_t ssd_post_scratch_bytes(int n_anchors, int batch);

@@ -1,48 +1,39 @@
-// Baseline JPEG decoder for files that arrive in host memory: BGR frames in HBM, byte for byte what libjpeg gives for them (Pillow's
-// Image.open(f).convert('RGB'), channels swapped; tests/jpeg_dec_ref.py is the definition).  Serves the frame_%06d.jpg sequence the
-// reference reads under --input-cvat-dir (deepdish.py:685-689, :727) and MJPEG cameras, through the ingest ring (csrc/ingest.hip) or on
-// its own.  All integer arithmetic.
+// JPEG decoder for files that arrive in host memory: BGR frames in HBM, byte for byte what libjpeg gives for them (Pillow's
+// Image.open(f).convert('RGB'), channels swapped; tests/jpeg_dec_ref.py, jpeg_scaled_ref.py and jpeg_prog_ref.py are the definition).
+// Serves the frame_%06d.jpg sequence the reference reads under --input-cvat-dir (deepdish.py:685-689, :727) and MJPEG cameras, through the
+// ingest ring (csrc/ingest.hip) or on its own.  All integer arithmetic.  Files of one call may differ in tables, sampling, restart
+// interval and kind; a file that is refused or damaged sets its own status and writes nothing outside its own frame.
 //
-// The host parses each header (csrc/jpeg_parse.h, bounded by the header) and uploads the records and the file bytes; then
-//   jpeg_markers_k   one workgroup per file finds the RSTn markers in its scan bytes and writes each restart interval's start and end;
-//   jpeg_entropy_k   one lane per restart interval decodes it (csrc/jpeg_dec_dev.h; Huffman decoding is serial inside an interval) and
-//                    stores the non-zero quantised coefficients, int16, natural order, into a zeroed buffer in HBM;
-//   jpeg_pixels_k    one workgroup per band (one MCU row) of a frame: dequantisation and the IDCT, one 8x8 block per thread, into sample
-//                    planes in LDS; then fancy up-sampling and colour conversion, BGR rows stored in order.  The h2v2 filter's one
-//                    chroma row above and below the band comes from transforming those neighbouring chroma blocks again.
-// A band too wide for LDS (DD_JPEGDEC_PLANES) takes its planes through HBM: jpeg_planes_k transforms, jpeg_pixels_k reads them back.
-// Files of one call may differ in tables, sampling and restart interval; a file that is refused or damaged sets its own status and
-// writes nothing outside its own frame.
-//
-// A decoder made with a scale denominator of 2, 4 or 8 (libjpeg's scale_denom, Pillow's Image.draft; tests/jpeg_scaled_ref.py) runs the
-// same markers and entropy kernels and then jpeg_pixels_scaled_k<S> (jpeg_planes_scaled_k<S>) in place of the last: every block goes
-// straight to 4x4, 2x2 or 1x1 samples (csrc/jpeg_dec_dev.h), the band's planes shrink with it, 4:2:0 chroma is not up-sampled at all, and
-// the frame written is ceil(H / S) x ceil(W / S).  The coefficient buffer keeps its full-size layout.
-//
-// A decoder made with DD_JPEGDEC_PROGRESSIVE takes progressive (SOF2) files as well, beside baseline ones in the same call.  Such a file
-// ends in the same coefficients in the same blocks, so everything behind the entropy stage stays as it is.  The host walks the whole file
-// into a scan script (csrc/jpeg_parse.h jpd_parse_scans: dd_jpeg_scans, uploaded beside the records) and gives every scan a level, one
-// more than the highest level of an earlier scan of the same component whose band overlaps its own; then
-//   jpeg_prog_markers_k   one workgroup per scan finds its RSTn markers;
-//   jpeg_prog_entropy_k   launched once per level, one lane per (scan, restart interval) of that level over all files of the call
-//                         (libjpeg's default script: 10 scans, 3 launches): jdphuff.c's four scan kinds (csrc/jpeg_dec_dev.h) into the same
-//                         zeroed coefficient buffer, in the same MCU-interleaved block order.  Scans of one level write different words.
-// A decoder made without the flag hands no such file on (DD_JPEG_ST_HEADER, as ever) and launches neither.
-//
-// A decoder made with DD_JPEGDEC_SPLIT gives a baseline file that is a single restart interval -- no restart markers: what cameras and
-// cv2.imencode write -- to a workgroup, not to one lane of jpeg_entropy_k:
-//   jpeg_split_entropy_k  one workgroup per such file cuts its scan into subsequences that the lanes decode from guessed states and then from
-//                         their predecessors' end states until none changes (Huffman data re-synchronises by itself), scans the blocks
-//                         begun and the DC sums, and decodes once more to store the coefficients: the sequential decode, cut into pieces.
-// Everything in front of and behind the entropy stage stays as it is; a decoder made without the flag does not launch it.
-//
-// A decoder made with DD_JPEGDEC_ANY_SIZE takes files of any size up to its H x W, each at its own scale (dd_jpegdec_decode_scales): the
-// kernels up to here are per record and run as they are, jpegdec_launch decides path and scale per file, holds every record to the
-// decoder's buffers, and hands the pixel stage to jpeg_pixels_any_k<S> / jpeg_planes_any_k<S> (csrc/jpeg_dec_any.hip), which write each
-// frame into the top-left corner of a uniform slot.  DD_JPEGDEC_STD_TABLES goes to the parser alone (csrc/jpeg_parse.h).
+// One call, in order (jpegdec_launch; nothing waits on the host):
+//   parse     csrc/jpeg_parse.h, on the host, bounded by the header: one dd_jpeg_info per file, and for a DD_JPEGDEC_PROGRESSIVE decoder
+//             the file walked into a scan script (dd_jpeg_scans), every scan at a level one above the highest earlier scan of the same
+//             component whose band overlaps its own.  DD_JPEGDEC_STD_TABLES stops here: the Annex K tables where a file has none.
+//             DD_JPEGDEC_ANY_SIZE makes the decoder's h x w the largest size accepted and no longer the only one.
+//   plan      csrc/jpeg_dec_plan.h jd_plan_call, on the host: every live file's place in the interval arrays, its pixel path and scale,
+//             its route through the entropy stage, and the sizes of every launch below (JdCall).  It holds every record to the decoder's
+//             buffers, so after it the kernels index with the records' fields as they are; it is the only stage that can refuse a call.
+//   upload    records, file bytes and (progressive files in the call) scan scripts, one copy each.
+//   markers   jpeg_markers_k        one workgroup per file finds the RSTn markers in its scan and writes each restart interval's bounds,
+//                                   and sets mark[f], the status the later kernels go by;
+//             jpeg_prog_markers_k   the same per (file, scan) of the progressive files.
+//   entropy   into the zeroed coefficient buffer: int16, natural order, MCU-interleaved blocks, a frame coef_stride apart.
+//             jpeg_split_entropy_k  DD_JPEGDEC_SPLIT: one workgroup per baseline file that is a single restart interval longer than a
+//                                   subsequence (no restart markers: what cameras and cv2.imencode write).  The lanes decode its
+//                                   subsequences from guessed states, then from their predecessors' end states until none changes;
+//             jpeg_entropy_k        one lane per restart interval of every other baseline file (Huffman decoding is serial inside one);
+//             jpeg_prog_entropy_k   once per level, one lane per (scan, restart interval) of that level over all files of the call
+//                                   (libjpeg's default script: 10 scans, 3 launches): jdphuff.c's four scan kinds.  Scans of one level
+//                                   write different words; what a scan refines was written by an earlier launch.
+//   pixels    one workgroup per band (one MCU row) of a frame (csrc/jpeg_dec_pix.h): jpeg_pixels_k at scale 1, jpeg_pixels_scaled_k<S> at
+//             1/2, 1/4, 1/8 (the frames are ceil(H / S) x ceil(W / S)), in front of either jpeg_planes_k / jpeg_planes_scaled_k<S> where a
+//             file of the call is too wide for a band in LDS (DD_JPEGDEC_PLANES); a DD_JPEGDEC_ANY_SIZE decoder runs
+//             jpeg_pixels_any_k<S> / jpeg_planes_any_k<S> (csrc/jpeg_dec_any.hip) once per scale that occurs in the call.
+// The statements the entropy kernels run are csrc/jpeg_dec_dev.h, __host__ __device__, so that the scripts/jpeg_*_check.cpp programs run
+// them over hostile files on the host.
 #include "common.h"
 #include "jpeg_dec_dev.h"
 #include "jpeg_dec_pix.h"
+#include "jpeg_dec_plan.h"
 #include <cstdlib>
 #include <new>
 
@@ -149,10 +140,9 @@ __global__ __launch_bounds__(64) void jpeg_entropy_k(const dd_jpeg_info *__restr
 
 // ---- DD_JPEGDEC_SPLIT: only a decoder made with the flag launches this one.
 
-constexpr int JD_SPLIT_MAX_SUB = 2048;         // subsequences of a file: 28 bytes of LDS each, beside the file's four Huffman tables
 constexpr int JD_SPLIT_WORDS = 7;              // 32-bit words of LDS per subsequence
 
-// One workgroup per file whose record names a subsequence size (reserved = its log2; the host's routing, jpegdec_launch): a baseline file
+// One workgroup per file whose record names a subsequence size (reserved = its log2; the call plan's routing): a baseline file
 // without restart intervals, which jpeg_entropy_k would give to a single lane.  The lanes stride over the file's subsequences
 // (csrc/jpeg_dec_dev.h jpd_decode_span).  Round 0 decodes every subsequence from its guess; in round r every lane first reads its
 // predecessor's end state and, behind a barrier, decodes again where that is known and is not the start it used last -- so a round reads only
@@ -162,7 +152,7 @@ constexpr int JD_SPLIT_WORDS = 7;              // 32-bit words of LDS per subseq
 // last decode writes the coefficients.  Only a lane in front of which every end state is known can end the frame well; when none does, the
 // file is DD_JPEG_ST_DATA.  An error met from a guess is not an error: that lane's successor keeps its own start.
 // LDS: per subsequence the start used last, the end state, the blocks begun and the DC sums, JD_SPLIT_WORDS words, max_sub of each.
-// stats: subsequences, the most rounds a file took, decodes of a subsequence in the rounds (jpegdec_launch zeroes them).
+// stats: subsequences, the most rounds a file took, decodes of a subsequence in the rounds (the entropy stage zeroes them).
 __global__ __launch_bounds__(JD_T) void jpeg_split_entropy_k(const dd_jpeg_info *__restrict__ recs, const uint8_t *__restrict__ bytes, const int *__restrict__ mark,
                                                              int16_t *__restrict__ coef, long long coef_stride, int *__restrict__ status, int max_sub,
                                                              unsigned int *__restrict__ stats) {
@@ -433,65 +423,173 @@ __global__ __launch_bounds__(JD_T) void jpeg_pixels_scaled_k(const dd_jpeg_info 
     }
 }
 
-template <int S>
-int jd_launch_pixels_scaled(unsigned grid, size_t lds, hipStream_t s, bool any_planes, const dd_jpeg_info *recs, const JdGeom &g, const int *mark, const int16_t *coef,
-                            uint8_t *planes, uint8_t *out_dev) {
-    if (any_planes) {
-        hipLaunchKernelGGL(jpeg_planes_scaled_k<S>, dim3(grid), dim3(JD_T), 0, s, recs, g, mark, coef, planes);
-        DD_LAUNCH_CHECK();
-    }
-    const int vec = (((g.W + S - 1) / S) & 3) == 0 && (reinterpret_cast<uintptr_t>(out_dev) & 3) == 0;
-    hipLaunchKernelGGL(jpeg_pixels_scaled_k<S>, dim3(grid), dim3(JD_T), lds, s, recs, g, mark, coef, planes, out_dev, vec);
-    DD_LAUNCH_CHECK();
-    return DD_OK;
-}
-
 // ------------------------------------------------------------------------------------------------ host
 
-int jd_geometry(int h, int w, const char *who, JdGeom *g) {
-    DD_REQUIRE(h >= 1 && w >= 1 && h <= JPD_MAX_SIDE && w <= JPD_MAX_SIDE, DD_E_ARG, "%s: a %d x %d frame (h, w: 1 .. %d either way)", who, w, h, JPD_MAX_SIDE);
-    g->H = h, g->W = w;
-    g->max_bands = (h + 7) / 8;
-    const long long b8w = (w + 7) / 8, b8h = (h + 7) / 8, b16w = (w + 15) / 16, b16h = (h + 15) / 16;
-    long long blocks = 3 * b8w * b8h;                                            // 4:4:4
-    if (4 * b16w * b8h > blocks) blocks = 4 * b16w * b8h;                       // 4:2:2
-    if (6 * b16w * b16h > blocks) blocks = 6 * b16w * b16h;                     // 4:2:0
-    g->coef_stride = blocks * 64;
-    g->plane_stride = 3 * (16 * b16w) * (16 * b16h);                            // every sampling's planes fit in three padded ones
-    return DD_OK;
+// A refusal of csrc/jpeg_dec_plan.h, which knows no dd_set_error, into the library's last error.
+int jd_fail(int rc, const char *msg) {
+    if (rc != DD_OK) dd_set_error("%s", msg);
+    return rc;
 }
 
 }  // namespace
 
 struct dd_jpegdec {
     dd_ctx *ctx = nullptr;
-    JdGeom g{};
-    int scale = 1, oh = 0, ow = 0;          // the scale denominator; the frames a decode writes are oh x ow
-    int max_frames = 0, lanes = 0;
-    size_t max_bytes = 0;
+    JdConfig cfg{};                         // what the call plan goes by: geometry, scale, flags, capacities
+    int oh = 0, ow = 0;                     // the frames (DD_JPEGDEC_ANY_SIZE: the slots) a decode writes are oh x ow
     DevBuf recs, bytes, coef, starts, mark, planes;
     PinBuf recs_host;
     hipEvent_t uploaded = nullptr;
-    bool profile = false, profiled = false;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};       // profile: call start, uploads done, markers, entropy, pixels
-    // DD_JPEGDEC_PROGRESSIVE only: the scan scripts beside the records, the scans' interval bounds, and the profile's events around each level
-    bool progressive = false;
-    DevBuf scans, pstarts;
-    PinBuf scans_host;
-    int levels_run = 0;
-    hipEvent_t lev[DD_JPEG_MAX_LEVELS + 1] = {};
-    // DD_JPEGDEC_SPLIT only: log2 of the subsequence size, jpeg_split_entropy_k's counters, their copy in pinned memory, the event behind that
-    // copy, and how many files the last decode routed to the kernel
-    bool split = false, split_auto = true, split_queued = false;
-    int split_log2 = 0, split_files = 0;
-    DevBuf split_stats;
-    PinBuf split_stats_host;
-    hipEvent_t split_done = nullptr;
-    // DD_JPEGDEC_ANY_SIZE: g.H x g.W is the largest file accepted and `scale` the smallest denominator of a call; DD_JPEGDEC_STD_TABLES goes
-    // to the parser with the rest of the flags
-    bool any_size = false;
-    int flags = 0;
+    struct {                                // DD_JPEGDEC_PROGRESSIVE: the scan scripts beside the records, and the scans' interval bounds
+        DevBuf scans, starts;
+        PinBuf scans_host;
+    } prog;
+    struct {                                // DD_JPEGDEC_SPLIT: jpeg_split_entropy_k's counters, their copy in pinned memory, the event behind
+        DevBuf stats;                       // that copy, whether a decode has queued one, and how many files the last decode routed to the kernel
+        PinBuf stats_host;
+        hipEvent_t done = nullptr;
+        bool queued = false;
+        int files = 0;
+    } split;
+    struct {                                // dd_jpegdec_profile: events at call start, uploads done, markers, entropy, pixels, and around
+        bool on = false, done = false;      // each level of jpeg_prog_entropy_k; done: the last decode recorded them all
+        hipEvent_t ev[5] = {};
+        hipEvent_t lev[DD_JPEG_MAX_LEVELS + 1] = {};
+        int levels_run = 0;
+    } profile;
 };
+
+namespace {
+
+// One call on its way through the stages: the plan, the stream, and where the kernels read and write.
+struct JdRun {
+    dd_jpegdec *d;
+    const JdCall &c;
+    int n;
+    hipStream_t s;
+    dd_jpeg_info *recs;
+    dd_jpeg_scans *scans;
+    uint8_t *bytes;
+    uint32_t *iv_start, *iv_end, *piv_start, *piv_end;      // the bounds of the baseline files' intervals, and of the progressive scans'
+    int *mark;
+    int16_t *coef;
+    uint8_t *planes, *out;
+    int *status;
+};
+
+int jd_profile_mark(const JdRun &r, hipEvent_t e) {
+    if (r.d->profile.on) DD_HIP(hipEventRecord(e, r.s));
+    return DD_OK;
+}
+
+int jd_stage_reserve(dd_jpegdec *d, const JdCall &c, int n) {
+    if (int rc = d->starts.reserve((size_t)(c.total + 1) * 2 * sizeof(uint32_t))) return rc;
+    if (jd_call_has_progressive(c))
+        if (int rc = d->prog.starts.reserve((size_t)(c.ptotal + 1) * 2 * sizeof(uint32_t))) return rc;
+    if (c.any_planes)
+        if (int rc = d->planes.reserve((size_t)n * (size_t)d->cfg.g.plane_stride)) return rc;
+    return DD_OK;
+}
+
+// Records and bytes in one copy each, the scan scripts where a file of the call has one; then `uploaded`, if given.
+int jd_stage_upload(const JdRun &r, const dd_jpeg_info *recs_host, const dd_jpeg_scans *scans_host, const uint8_t *bytes_host, size_t n_bytes, hipEvent_t uploaded) {
+    DD_HIP(hipMemcpyAsync(r.recs, recs_host, (size_t)r.n * sizeof(dd_jpeg_info), hipMemcpyHostToDevice, r.s));
+    if (n_bytes) DD_HIP(hipMemcpyAsync(r.bytes, bytes_host, n_bytes, hipMemcpyHostToDevice, r.s));
+    if (jd_call_has_progressive(r.c)) DD_HIP(hipMemcpyAsync(r.scans, scans_host, (size_t)r.n * sizeof(dd_jpeg_scans), hipMemcpyHostToDevice, r.s));
+    if (uploaded) DD_HIP(hipEventRecord(uploaded, r.s));
+    return DD_OK;
+}
+
+int jd_stage_markers(const JdRun &r) {
+    hipLaunchKernelGGL(jpeg_markers_k, dim3((unsigned)r.n), dim3(JD_T), 0, r.s, r.recs, r.bytes, r.iv_start, r.iv_end, r.mark, r.status);
+    DD_LAUNCH_CHECK();
+    if (jd_call_has_progressive(r.c)) {
+        hipLaunchKernelGGL(jpeg_prog_markers_k, dim3((unsigned)r.n * (unsigned)r.c.max_scans), dim3(JD_T), 0, r.s, r.recs, r.scans, r.c.max_scans, r.bytes, r.piv_start, r.piv_end,
+                           r.mark, r.status);
+        DD_LAUNCH_CHECK();
+    }
+    return DD_OK;
+}
+
+// Split files, then the other baseline files, then the progressive files level by level, into the zeroed coefficients.  A
+// DD_JPEGDEC_SPLIT decoder reads the split kernel's counters back behind it in every call, also one with nothing to decode.
+int jd_stage_entropy(const JdRun &r) {
+    dd_jpegdec *d = r.d;
+    const JdCall &c = r.c;
+    const long long coef_stride = d->cfg.g.coef_stride;
+    unsigned int *stats = d->cfg.has(DD_JPEGDEC_SPLIT) ? d->split.stats.as<unsigned int>() : nullptr;
+    d->profile.levels_run = 0;
+    if (stats) {
+        d->split.files = c.n_split;
+        DD_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(unsigned int), r.s));
+    }
+    if (c.any) DD_HIP(hipMemsetAsync(r.coef, 0, (size_t)r.n * (size_t)coef_stride * sizeof(int16_t), r.s));
+    if (jd_call_has_split(c)) {
+        const size_t split_lds = (size_t)c.max_sub * JD_SPLIT_WORDS * sizeof(uint32_t);
+        hipLaunchKernelGGL(jpeg_split_entropy_k, dim3((unsigned)r.n), dim3(JD_T), split_lds, r.s, r.recs, r.bytes, r.mark, r.coef, coef_stride, r.status, c.max_sub, stats);
+        DD_LAUNCH_CHECK();
+    }
+    if (stats) {
+        DD_HIP(hipMemcpyAsync(d->split.stats_host.as<unsigned int>(), stats, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, r.s));
+        DD_HIP(hipEventRecord(d->split.done, r.s));
+        d->split.queued = true;
+    }
+    if (!c.any) return DD_OK;
+    if (jd_call_has_baseline_lanes(c)) {
+        const int per = jd_lanes_per_wave(c.total, d->cfg.lanes);
+        hipLaunchKernelGGL(jpeg_entropy_k, dim3((unsigned)((c.total + per - 1) / per)), dim3(64), 0, r.s, r.recs, r.n, (int)c.total, per, r.bytes, r.iv_start, r.iv_end, r.mark, r.coef,
+                           coef_stride, r.status);
+        DD_LAUNCH_CHECK();
+    }
+    if (jd_call_has_progressive(c)) {
+        if (int rc = jd_profile_mark(r, d->profile.lev[0])) return rc;
+        for (int l = 0; l < c.n_levels; ++l) {
+            const long long lt = c.level_total[l];
+            const int per = jd_lanes_per_wave(lt, d->cfg.lanes);
+            if (lt) {
+                hipLaunchKernelGGL(jpeg_prog_entropy_k, dim3((unsigned)((lt + per - 1) / per)), dim3(64), 0, r.s, r.recs, r.scans, r.n, l, (int)lt, per, r.bytes, r.piv_start, r.piv_end,
+                                   r.mark, r.coef, coef_stride, r.status);
+                DD_LAUNCH_CHECK();
+            }
+            if (int rc = jd_profile_mark(r, d->profile.lev[l + 1])) return rc;
+        }
+        d->profile.levels_run = c.n_levels;
+    }
+    return DD_OK;
+}
+
+// One workgroup per band of every frame: the planes kernel first where a file of the call takes DD_JPEGDEC_PLANES.  A DD_JPEGDEC_ANY_SIZE
+// decoder does that once per scale that occurs (csrc/jpeg_dec_any.hip); every other decoder has one scale, and dense frames of oh x ow.
+int jd_stage_pixels(const JdRun &r) {
+    const dd_jpegdec *d = r.d;
+    const JdGeom &g = d->cfg.g;
+    if (d->cfg.has(DD_JPEGDEC_ANY_SIZE))
+        return ddk::jpegdec_pixels_any(r.s, r.n, g.max_bands, g.coef_stride, g.plane_stride, r.c.per_scale, r.recs, r.mark, r.coef, r.planes, r.out, d->oh, d->ow);
+    const unsigned grid = (unsigned)r.n * (unsigned)g.max_bands;
+    const int vec = (d->ow & 3) == 0 && (reinterpret_cast<uintptr_t>(r.out) & 3) == 0;
+    return jd_with_scale(d->cfg.scale, [&](auto scale) -> int {
+        constexpr int S = decltype(scale)::value;
+        if (r.c.any_planes) {
+            if constexpr (S == 1) hipLaunchKernelGGL(jpeg_planes_k, dim3(grid), dim3(JD_T), 0, r.s, r.recs, g, r.mark, r.coef, r.planes);
+            else hipLaunchKernelGGL(jpeg_planes_scaled_k<S>, dim3(grid), dim3(JD_T), 0, r.s, r.recs, g, r.mark, r.coef, r.planes);
+            DD_LAUNCH_CHECK();
+        }
+        if constexpr (S == 1) hipLaunchKernelGGL(jpeg_pixels_k, dim3(grid), dim3(JD_T), r.c.lds, r.s, r.recs, g, r.mark, r.coef, r.planes, r.out, vec);
+        else hipLaunchKernelGGL(jpeg_pixels_scaled_k<S>, dim3(grid), dim3(JD_T), r.c.lds, r.s, r.recs, g, r.mark, r.coef, r.planes, r.out, vec);
+        DD_LAUNCH_CHECK();
+        return DD_OK;
+    });
+}
+
+// What the three parsers of the C API share.  flags: 0 or DD_JPEGDEC_STD_TABLES.
+int jd_parse_api(const uint8_t *file_host, int64_t n, int flags, dd_jpeg_info *info, dd_jpeg_scans *scans) {
+    char msg[320];
+    if ((scans ? jpd_parse_scans(file_host, (size_t)n, info, scans, msg, sizeof(msg), flags) : jpd_parse(file_host, (size_t)n, info, msg, sizeof(msg), flags)) != DD_JPEG_R_OK)
+        return jd_fail(DD_E_FORMAT, msg);
+    return DD_OK;
+}
+
+}  // namespace
 
 namespace ddk {
 
@@ -523,211 +621,35 @@ int jpegdec_parse(const uint8_t *file, size_t n, int h, int w, dd_jpeg_info *rec
 }
 
 // recs_host: n records from jpegdec_parse, in memory that stays as it is until the stream has run the upload (pinned: the copy is then
-// asynchronous); file i lies at bytes_host + recs_host[i].file_offset, all within n_bytes.  Fills the records' decoder fields, uploads
-// records and bytes in one copy each (then records `uploaded`, if given), and queues the kernels on s.  No host wait.
+// asynchronous); file i lies at bytes_host + recs_host[i].file_offset, all within n_bytes.  Plans the call (which fills the records'
+// decoder fields, or refuses), uploads (then records `uploaded`, if given), and queues the kernels on s.  No host wait.
 // scans_host: NULL, or n scan scripts from jpegdec_parse, kept like the records (a decoder that takes progressive files).
 // scales: NULL, or (a decoder made with DD_JPEGDEC_ANY_SIZE) one scale denominator per file, none below the decoder's own.
 int jpegdec_launch(dd_jpegdec *d, dd_jpeg_info *recs_host, dd_jpeg_scans *scans_host, const uint8_t *bytes_host, size_t n_bytes, int n, uint8_t *out_dev, int *status_dev,
                    hipStream_t s, hipEvent_t uploaded, const int *scales) {
-    DD_REQUIRE(n >= 1 && n <= d->max_frames, DD_E_CAPACITY, "jpeg decoder: %d frames in a call (1 .. %d)", n, d->max_frames);
-    DD_REQUIRE(n_bytes <= d->max_bytes, DD_E_CAPACITY, "jpeg decoder: %zu bytes of files in a call (at most %zu)", n_bytes, d->max_bytes);
-    const JdGeom &g = d->g;
-    DD_REQUIRE(!scans_host || d->progressive, DD_E_STATE, "jpeg decoder: scan scripts for a decoder that was not made to take progressive files");
-    DD_REQUIRE(!scales || d->any_size, DD_E_STATE, "jpeg decoder: a scale per file for a decoder that was not made with DD_JPEGDEC_ANY_SIZE");
-    size_t lds_at[4] = {0, 0, 0, 0};                            // DD_JPEGDEC_ANY_SIZE: per log2 of the scale, the LDS, whether a file takes it
-    bool any_at[4] = {false, false, false, false}, planes_at[4] = {false, false, false, false};
-    long long total = 0, ptotal = 0, level_total[DD_JPEG_MAX_LEVELS] = {};
-    int max_scans = 0, n_levels = 0, n_split = 0, max_sub = 0;
-    size_t lds = 0;
-    bool any = false, any_planes = false;
-    for (int i = 0; i < n; ++i) {
-        dd_jpeg_info &r = recs_host[i];
-        r.interval_base = (int32_t)total;
-        r.reserved = 0;
-        if (scans_host) {
-            dd_jpeg_scans &S = scans_host[i];
-            for (int l = 0; l < DD_JPEG_MAX_LEVELS; ++l) S.level_base[l] = (int32_t)level_total[l];
-            if (r.status != DD_JPEG_ST_OK || r.sof != 0xC2) S.n_scans = S.n_levels = 0;
-        }
-        if (r.status != DD_JPEG_ST_OK) {
-            r.n_intervals = 0;
-            continue;
-        }
-        if (scans_host && scans_host[i].n_scans) {
-            dd_jpeg_scans &S = scans_host[i];
-            DD_REQUIRE(S.n_scans <= DD_JPEG_MAX_SCANS && S.n_levels <= DD_JPEG_MAX_LEVELS, DD_E_ARG, "jpeg decoder: file %d: %d scans at %d levels", i, S.n_scans, S.n_levels);
-            for (int k = 0; k < S.n_scans; ++k) {
-                dd_jpeg_scan &sc = S.scan[k];
-                DD_REQUIRE(r.file_offset >= 0 && sc.offset >= 0 && sc.length >= 0 && (size_t)r.file_offset + (size_t)sc.offset + (size_t)sc.length <= n_bytes, DD_E_ARG,
-                           "jpeg decoder: scan %d of file %d lies outside the %zu bytes given", k, i, n_bytes);
-                DD_REQUIRE(sc.level >= 0 && sc.level < S.n_levels && sc.n_intervals >= 1, DD_E_ARG, "jpeg decoder: scan %d of file %d: level %d, %d intervals", k, i, sc.level,
-                           sc.n_intervals);
-                sc.interval_base = (int32_t)ptotal;
-                ptotal += sc.n_intervals;
-                level_total[sc.level] += sc.n_intervals;
-            }
-            DD_REQUIRE(ptotal <= 0x7fffffffll, DD_E_CAPACITY, "jpeg decoder: more than 2^31 restart intervals in a call");
-            max_scans = S.n_scans > max_scans ? S.n_scans : max_scans;
-            n_levels = S.n_levels > n_levels ? S.n_levels : n_levels;
-            r.n_intervals = 0, r.restart_interval = 0, r.scan_offset = 0, r.scan_length = 0;          // nothing for jpeg_entropy_k
-        }
-        DD_REQUIRE(r.file_offset >= 0 && (size_t)r.file_offset + (size_t)r.scan_offset + (size_t)r.scan_length <= n_bytes, DD_E_ARG,
-                   "jpeg decoder: file %d lies outside the %zu bytes given", i, n_bytes);
-        const int fs = scales ? scales[i] : d->scale;
-        DD_REQUIRE(jpd_scale_ok(fs) && fs >= d->scale, DD_E_ARG, "jpeg decoder: file %d at scale %d (1, 2, 4 or 8, and at least the decoder's %d)", i, fs, d->scale);
-        const JdBand b = jd_band(r.width, r.ncomp, r.hmax, r.vmax, fs);
-        r.path = b.lds <= (size_t)JD_LDS_MAX ? DD_JPEGDEC_LDS : DD_JPEGDEC_PLANES;
-        if (r.path == DD_JPEGDEC_LDS) lds = b.lds > lds ? b.lds : lds;
-        else any_planes = true;
-        if (d->any_size) {
-            // these records came from put on other threads: everything the kernels index with is held to the decoder's buffers here,
-            // before anything is queued.  jd_geometry's strides are monotone in h and w, so a file that fits the sides fits them.
-            const long long blocks = (long long)r.mcus_x * r.mcus_y * r.blocks_per_mcu;
-            const long long crows = fs == 1 ? 8 : b.crows;
-            const long long plane_bytes = (long long)r.mcus_y * ((long long)b.yrows * b.Wy + (r.ncomp == 3 ? 2 * crows * b.Wc : 0));
-            DD_REQUIRE(r.height >= 1 && r.height <= g.H && r.width >= 1 && r.width <= g.W, DD_E_ARG, "jpeg decoder: file %d is %d x %d, the decoder holds at most %d x %d", i,
-                       r.width, r.height, g.W, g.H);
-            DD_REQUIRE(r.mcus_x == (r.width + 8 * r.hmax - 1) / (8 * r.hmax) && r.mcus_y == (r.height + 8 * r.vmax - 1) / (8 * r.vmax) && r.mcus_y <= g.max_bands, DD_E_ARG,
-                       "jpeg decoder: file %d: %d x %d MCUs for %d x %d pixels", i, r.mcus_x, r.mcus_y, r.width, r.height);
-            DD_REQUIRE(blocks * 64 <= g.coef_stride, DD_E_ARG, "jpeg decoder: file %d has %lld blocks, a frame's coefficients hold %lld", i, blocks, g.coef_stride / 64);
-            DD_REQUIRE(r.path == DD_JPEGDEC_LDS || plane_bytes <= g.plane_stride, DD_E_ARG, "jpeg decoder: file %d needs %lld bytes of planes, a frame holds %lld", i, plane_bytes,
-                       g.plane_stride);
-            const int lg = fs == 1 ? 0 : fs == 2 ? 1 : fs == 4 ? 2 : 3;
-            any_at[lg] = true;
-            if (r.path == DD_JPEGDEC_LDS) lds_at[lg] = b.lds > lds_at[lg] ? b.lds : lds_at[lg];
-            else planes_at[lg] = true;
-            r.path |= lg << 8;
-        }
-        // DD_JPEGDEC_SPLIT: a baseline file that is one restart interval (no DRI, DRI 0, or a DRI of the MCU count or more) and longer than a
-        // subsequence goes to jpeg_split_entropy_k, in subsequences of the decoder's size -- doubled, where DD_JPEGDEC_SPLIT_BYTES did not
-        // fix it, until every lane of the workgroup has at most one, and in any case until the file's states fit the kernel's LDS;
-        // jpeg_entropy_k passes over it
-        if (d->split && r.sof != 0xC2 && r.n_intervals == 1 && (long long)r.scan_length > (1ll << d->split_log2)) {
-            int lg = d->split_log2;
-            if (d->split_auto)                                              // one subsequence per lane of the file's workgroup: see the README's table
-                while ((((long long)r.scan_length + (1ll << lg) - 1) >> lg) > JD_T) ++lg;
-            while ((((long long)r.scan_length + (1ll << lg) - 1) >> lg) > JD_SPLIT_MAX_SUB) ++lg;
-            r.reserved = lg;
-            const int subs = (int)(((long long)r.scan_length + (1ll << lg) - 1) >> lg);
-            max_sub = subs > max_sub ? subs : max_sub;
-            ++n_split;
-        }
-        total += r.n_intervals;
-        any = true;
-        DD_REQUIRE(total <= 0x7fffffffll, DD_E_CAPACITY, "jpeg decoder: more than 2^31 restart intervals in a call");
-    }
-    if (int rc = d->starts.reserve((size_t)(total + 1) * 2 * sizeof(uint32_t))) return rc;
-    if (max_scans)
-        if (int rc = d->pstarts.reserve((size_t)(ptotal + 1) * 2 * sizeof(uint32_t))) return rc;
-    if (any_planes)
-        if (int rc = d->planes.reserve((size_t)n * (size_t)g.plane_stride)) return rc;
-    dd_jpeg_info *recs = d->recs.as<dd_jpeg_info>();
-    uint8_t *bytes = d->bytes.as<uint8_t>();
-    int16_t *coef = d->coef.as<int16_t>();
-    uint32_t *iv_start = d->starts.as<uint32_t>(), *iv_end = iv_start + total + 1;
-    int *mark = d->mark.as<int>();
-    d->profiled = false;
-    if (d->profile) DD_HIP(hipEventRecord(d->ev[0], s));
-    DD_HIP(hipMemcpyAsync(recs, recs_host, (size_t)n * sizeof(dd_jpeg_info), hipMemcpyHostToDevice, s));
-    if (n_bytes) DD_HIP(hipMemcpyAsync(bytes, bytes_host, n_bytes, hipMemcpyHostToDevice, s));
-    if (max_scans) DD_HIP(hipMemcpyAsync(d->scans.as<dd_jpeg_scans>(), scans_host, (size_t)n * sizeof(dd_jpeg_scans), hipMemcpyHostToDevice, s));
-    if (uploaded) DD_HIP(hipEventRecord(uploaded, s));
-    if (d->profile) DD_HIP(hipEventRecord(d->ev[1], s));
-    hipLaunchKernelGGL(jpeg_markers_k, dim3((unsigned)n), dim3(JD_T), 0, s, recs, bytes, iv_start, iv_end, mark, status_dev);
-    DD_LAUNCH_CHECK();
-    const dd_jpeg_scans *scans = d->scans.as<dd_jpeg_scans>();
-    uint32_t *piv_start = max_scans ? d->pstarts.as<uint32_t>() : nullptr, *piv_end = max_scans ? piv_start + ptotal + 1 : nullptr;
-    if (max_scans) {
-        hipLaunchKernelGGL(jpeg_prog_markers_k, dim3((unsigned)n * (unsigned)max_scans), dim3(JD_T), 0, s, recs, scans, max_scans, bytes, piv_start, piv_end, mark, status_dev);
-        DD_LAUNCH_CHECK();
-    }
-    if (d->profile) DD_HIP(hipEventRecord(d->ev[2], s));
-    d->levels_run = 0;
-    unsigned int *split_stats = d->split ? d->split_stats.as<unsigned int>() : nullptr;
-    if (d->split) {
-        d->split_files = n_split;
-        DD_HIP(hipMemsetAsync(split_stats, 0, 4 * sizeof(unsigned int), s));
-    }
-    if (!any) {
-        if (d->split) {
-            DD_HIP(hipMemcpyAsync(d->split_stats_host.as<unsigned int>(), split_stats, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-            DD_HIP(hipEventRecord(d->split_done, s));
-            d->split_queued = true;
-        }
-        return DD_OK;
-    }
-    DD_HIP(hipMemsetAsync(coef, 0, (size_t)n * (size_t)g.coef_stride * sizeof(int16_t), s));
-    if (n_split) {
-        const size_t split_lds = (size_t)max_sub * JD_SPLIT_WORDS * sizeof(uint32_t);
-        hipLaunchKernelGGL(jpeg_split_entropy_k, dim3((unsigned)n), dim3(JD_T), split_lds, s, recs, bytes, mark, coef, g.coef_stride, status_dev, max_sub, split_stats);
-        DD_LAUNCH_CHECK();
-    }
-    if (d->split) {
-        DD_HIP(hipMemcpyAsync(d->split_stats_host.as<unsigned int>(), split_stats, 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-        DD_HIP(hipEventRecord(d->split_done, s));
-        d->split_queued = true;
-    }
-    // intervals per wave: a lane decodes serially, so few intervals are spread over many waves (one per SIMD and more: 256 CUs of 4 SIMDs),
-    // and only a call with very many intervals fills its waves
-    int per = 64;
-    while (per > 1 && total / per < 2048) per >>= 1;
-    if (d->lanes) per = d->lanes;
-    if ((total || !max_scans) && !(n_split && total == n_split)) {          // a call of progressive files alone, or of split files alone, has nothing for it
-        hipLaunchKernelGGL(jpeg_entropy_k, dim3((unsigned)((total + per - 1) / per)), dim3(64), 0, s, recs, n, (int)total, per, bytes, iv_start, iv_end, mark, coef,
-                           g.coef_stride, status_dev);
-        DD_LAUNCH_CHECK();
-    }
-    if (max_scans) {
-        if (d->profile) DD_HIP(hipEventRecord(d->lev[0], s));
-        for (int l = 0; l < n_levels; ++l) {
-            const long long lt = level_total[l];
-            int lper = 64;
-            while (lper > 1 && lt / lper < 2048) lper >>= 1;
-            if (d->lanes) lper = d->lanes;
-            if (lt)
-                hipLaunchKernelGGL(jpeg_prog_entropy_k, dim3((unsigned)((lt + lper - 1) / lper)), dim3(64), 0, s, recs, scans, n, l, (int)lt, lper, bytes, piv_start, piv_end, mark,
-                                   coef, g.coef_stride, status_dev);
-            DD_LAUNCH_CHECK();
-            if (d->profile) DD_HIP(hipEventRecord(d->lev[l + 1], s));
-        }
-        d->levels_run = n_levels;
-    }
-    if (d->profile) DD_HIP(hipEventRecord(d->ev[3], s));
-    const unsigned grid = (unsigned)n * (unsigned)g.max_bands;
-    if (d->any_size) {                                          // one launch per scale that occurs; each passes over the other scales' files
-        const int rc = jpegdec_pixels_any(s, n, g.max_bands, g.coef_stride, g.plane_stride, lds_at, any_at, planes_at, recs, mark, coef, d->planes.as<uint8_t>(), out_dev, d->oh, d->ow);
-        if (rc != DD_OK) return rc;
-        if (d->profile) {
-            DD_HIP(hipEventRecord(d->ev[4], s));
-            d->profiled = true;
-        }
-        return DD_OK;
-    }
-    if (d->scale != 1) {
-        int rc = DD_OK;
-        switch (d->scale) {
-            case 2: rc = jd_launch_pixels_scaled<2>(grid, lds, s, any_planes, recs, g, mark, coef, d->planes.as<uint8_t>(), out_dev); break;
-            case 4: rc = jd_launch_pixels_scaled<4>(grid, lds, s, any_planes, recs, g, mark, coef, d->planes.as<uint8_t>(), out_dev); break;
-            default: rc = jd_launch_pixels_scaled<8>(grid, lds, s, any_planes, recs, g, mark, coef, d->planes.as<uint8_t>(), out_dev); break;
-        }
-        if (rc != DD_OK) return rc;
-        if (d->profile) {
-            DD_HIP(hipEventRecord(d->ev[4], s));
-            d->profiled = true;
-        }
-        return DD_OK;
-    }
-    if (any_planes) {
-        hipLaunchKernelGGL(jpeg_planes_k, dim3(grid), dim3(JD_T), 0, s, recs, g, mark, coef, d->planes.as<uint8_t>());
-        DD_LAUNCH_CHECK();
-    }
-    const int vec = (g.W & 3) == 0 && (reinterpret_cast<uintptr_t>(out_dev) & 3) == 0;
-    hipLaunchKernelGGL(jpeg_pixels_k, dim3(grid), dim3(JD_T), lds, s, recs, g, mark, coef, d->planes.as<uint8_t>(), out_dev, vec);
-    DD_LAUNCH_CHECK();
-    if (d->profile) {
-        DD_HIP(hipEventRecord(d->ev[4], s));
-        d->profiled = true;
-    }
+    JdCall c;
+    char msg[320];
+    if (int rc = jd_plan_call(d->cfg, recs_host, scans_host, n_bytes, n, scales, &c, msg, sizeof(msg))) return jd_fail(rc, msg);
+    if (int rc = jd_stage_reserve(d, c, n)) return rc;
+    const bool prog = jd_call_has_progressive(c);
+    uint32_t *iv = d->starts.as<uint32_t>(), *piv = prog ? d->prog.starts.as<uint32_t>() : nullptr;
+    const JdRun r = {d, c, n, s,
+                     d->recs.as<dd_jpeg_info>(), d->prog.scans.as<dd_jpeg_scans>(), d->bytes.as<uint8_t>(),
+                     iv, iv + c.total + 1, piv, prog ? piv + c.ptotal + 1 : nullptr,
+                     d->mark.as<int>(), d->coef.as<int16_t>(), d->planes.as<uint8_t>(), out_dev, status_dev};
+    auto &ev = d->profile.ev;
+    d->profile.done = false;
+    if (int rc = jd_profile_mark(r, ev[0])) return rc;
+    if (int rc = jd_stage_upload(r, recs_host, scans_host, bytes_host, n_bytes, uploaded)) return rc;
+    if (int rc = jd_profile_mark(r, ev[1])) return rc;
+    if (int rc = jd_stage_markers(r)) return rc;
+    if (int rc = jd_profile_mark(r, ev[2])) return rc;
+    if (int rc = jd_stage_entropy(r)) return rc;
+    if (!c.any) return DD_OK;                                   // every file refused or missing: the statuses are set, no frame is written
+    if (int rc = jd_profile_mark(r, ev[3])) return rc;
+    if (int rc = jd_stage_pixels(r)) return rc;
+    if (int rc = jd_profile_mark(r, ev[4])) return rc;
+    d->profile.done = d->profile.on;
     return DD_OK;
 }
 
@@ -737,38 +659,24 @@ extern "C" {
 
 int dd_jpeg_parse_scans(const uint8_t *file_host, int64_t n, dd_jpeg_info *info, dd_jpeg_scans *scans) {
     DD_REQUIRE(file_host && info && scans && n >= 0, DD_E_ARG, "dd_jpeg_parse_scans: NULL argument or a negative length");
-    char msg[320];
-    if (jpd_parse_scans(file_host, (size_t)n, info, scans, msg, sizeof(msg)) != DD_JPEG_R_OK) {
-        dd_set_error("%s", msg);
-        return DD_E_FORMAT;
-    }
-    return DD_OK;
+    return jd_parse_api(file_host, n, 0, info, scans);
 }
 
 int dd_jpeg_parse_flags(const uint8_t *file_host, int64_t n, int flags, dd_jpeg_info *info, dd_jpeg_scans *scans) {
     DD_REQUIRE(file_host && info && n >= 0, DD_E_ARG, "dd_jpeg_parse_flags: NULL argument or a negative length");
     DD_REQUIRE((flags & ~DD_JPEGDEC_STD_TABLES) == 0, DD_E_ARG, "dd_jpeg_parse_flags: flags 0x%x (DD_JPEGDEC_STD_TABLES or 0)", flags);
-    char msg[320];
-    if ((scans ? jpd_parse_scans(file_host, (size_t)n, info, scans, msg, sizeof(msg), flags) : jpd_parse(file_host, (size_t)n, info, msg, sizeof(msg), flags)) != DD_JPEG_R_OK) {
-        dd_set_error("%s", msg);
-        return DD_E_FORMAT;
-    }
-    return DD_OK;
+    return jd_parse_api(file_host, n, flags, info, scans);
 }
 
 int dd_jpeg_parse(const uint8_t *file_host, int64_t n, dd_jpeg_info *info) {
     DD_REQUIRE(file_host && info && n >= 0, DD_E_ARG, "dd_jpeg_parse: NULL argument or a negative length");
-    char msg[320];
-    if (jpd_parse(file_host, (size_t)n, info, msg, sizeof(msg)) != DD_JPEG_R_OK) {
-        dd_set_error("%s", msg);
-        return DD_E_FORMAT;
-    }
-    return DD_OK;
+    return jd_parse_api(file_host, n, 0, info, nullptr);
 }
 
 static int jd_plan(const char *who, int h, int w, int ncomp, int hs, int vs, int scale, int *path_host, int *band_rows_host, int *bands_host) {
     JdGeom g;
-    if (int rc = jd_geometry(h, w, who, &g)) return rc;
+    char msg[320];
+    if (int rc = jd_geometry(h, w, who, &g, msg, sizeof(msg))) return jd_fail(rc, msg);
     DD_REQUIRE(jpd_scale_ok(scale), DD_E_ARG, "%s: scale %d is none of 1, 2, 4, 8", who, scale);
     DD_REQUIRE((ncomp == 1 && hs == 1 && vs == 1) || (ncomp == 3 && ((hs == 1 && vs == 1) || (hs == 2 && (vs == 1 || vs == 2)))), DD_E_ARG,
                "%s: %d components with luma sampling %dx%d (1 component, or 3 with 1x1, 2x1 or 2x2)", who, ncomp, hs, vs);
@@ -796,41 +704,41 @@ int dd_jpeg_draft_scale(int src_w, int src_h, int dst_w, int dst_h) {
 
 static int jd_create(const char *who, dd_ctx *ctx, int h, int w, int scale, int flags, int max_frames, int64_t max_bytes, dd_jpegdec **out) {
     DD_REQUIRE(ctx && out, DD_E_ARG, "%s: NULL argument", who);
-    JdGeom g;
-    if (int rc = jd_geometry(h, w, who, &g)) return rc;
+    JdConfig cfg{};
+    char msg[320];
+    if (int rc = jd_geometry(h, w, who, &cfg.g, msg, sizeof(msg))) return jd_fail(rc, msg);
     DD_REQUIRE(jpd_scale_ok(scale), DD_E_ARG, "%s: scale %d is none of 1, 2, 4, 8", who, scale);
     DD_REQUIRE((flags & ~(DD_JPEGDEC_PROGRESSIVE | DD_JPEGDEC_SPLIT | DD_JPEGDEC_ANY_SIZE | DD_JPEGDEC_STD_TABLES)) == 0, DD_E_ARG,
                "%s: flags 0x%x (DD_JPEGDEC_PROGRESSIVE, DD_JPEGDEC_SPLIT, DD_JPEGDEC_ANY_SIZE, DD_JPEGDEC_STD_TABLES, any of them or 0)", who, flags);
-    int split_log2 = 6;                                             // 64 bytes, doubled per file until a lane has one subsequence: see the README's table
-    const char *sb = (flags & DD_JPEGDEC_SPLIT) ? getenv("DD_JPEGDEC_SPLIT_BYTES") : nullptr;
+    cfg.scale = scale, cfg.flags = flags, cfg.max_frames = max_frames, cfg.max_bytes = (size_t)max_bytes;
+    cfg.split_log2 = 6, cfg.split_auto = true;                      // 64 bytes, doubled per file until a lane has one subsequence: see the README's table
+    const char *sb = cfg.has(DD_JPEGDEC_SPLIT) ? getenv("DD_JPEGDEC_SPLIT_BYTES") : nullptr;
     if (sb) {                                                       // the subsequence size of jpeg_split_entropy_k: a power of two, 16 .. 4096
         char *tail = nullptr;
         const long v = strtol(sb, &tail, 10);
         DD_REQUIRE(tail != sb && *tail == 0 && v >= 16 && v <= 4096 && (v & (v - 1)) == 0, DD_E_ARG, "%s: DD_JPEGDEC_SPLIT_BYTES=%s (a power of two, 16 .. 4096)", who, sb);
-        for (split_log2 = 4; (1l << split_log2) < v; ++split_log2) {}
+        for (cfg.split_log2 = 4; (1l << cfg.split_log2) < v; ++cfg.split_log2) {}
+        cfg.split_auto = false;
     }
-    DD_REQUIRE(max_frames >= 1 && (long long)max_frames * g.max_bands <= 0x7fffffffll, DD_E_ARG, "%s: max_frames %d", who, max_frames);
+    const char *lanes = getenv("DD_JPEGDEC_LANES");                 // intervals per wave of the entropy kernels, for A/B runs: 1 .. 64
+    if (lanes && atoi(lanes) >= 1 && atoi(lanes) <= 64) cfg.lanes = atoi(lanes);
+    DD_REQUIRE(max_frames >= 1 && (long long)max_frames * cfg.g.max_bands <= 0x7fffffffll, DD_E_ARG, "%s: max_frames %d", who, max_frames);
     DD_REQUIRE(max_bytes >= 1, DD_E_ARG, "%s: max_bytes %lld", who, (long long)max_bytes);
     DD_DEVICE(ctx);
     dd_jpegdec *d = new (std::nothrow) dd_jpegdec();
     DD_REQUIRE(d, DD_E_HIP, "%s: out of host memory", who);
-    d->ctx = ctx, d->g = g, d->max_frames = max_frames, d->max_bytes = (size_t)max_bytes;
-    d->scale = scale, d->oh = (h + scale - 1) / scale, d->ow = (w + scale - 1) / scale;
-    d->flags = flags, d->any_size = (flags & DD_JPEGDEC_ANY_SIZE) != 0;
-    const char *lanes = getenv("DD_JPEGDEC_LANES");                 // intervals per wave of jpeg_entropy_k, for A/B runs: 1 .. 64
-    if (lanes && atoi(lanes) >= 1 && atoi(lanes) <= 64) d->lanes = atoi(lanes);
+    d->ctx = ctx, d->cfg = cfg, d->oh = (h + scale - 1) / scale, d->ow = (w + scale - 1) / scale;
+    const bool prog = cfg.has(DD_JPEGDEC_PROGRESSIVE), split = cfg.has(DD_JPEGDEC_SPLIT);
     int rc = d->recs.reserve((size_t)max_frames * sizeof(dd_jpeg_info));
     if (rc == DD_OK) rc = d->bytes.reserve((size_t)max_bytes + 16);
-    if (rc == DD_OK) rc = d->coef.reserve((size_t)max_frames * (size_t)g.coef_stride * sizeof(int16_t));
+    if (rc == DD_OK) rc = d->coef.reserve((size_t)max_frames * (size_t)cfg.g.coef_stride * sizeof(int16_t));
     if (rc == DD_OK) rc = d->mark.reserve((size_t)max_frames * sizeof(int));
     if (rc == DD_OK) rc = d->recs_host.reserve((size_t)max_frames * sizeof(dd_jpeg_info));
-    d->progressive = (flags & DD_JPEGDEC_PROGRESSIVE) != 0;
-    if (rc == DD_OK && d->progressive) rc = d->scans.reserve((size_t)max_frames * sizeof(dd_jpeg_scans));
-    if (rc == DD_OK && d->progressive) rc = d->scans_host.reserve((size_t)max_frames * sizeof(dd_jpeg_scans));
-    d->split = (flags & DD_JPEGDEC_SPLIT) != 0, d->split_log2 = split_log2, d->split_auto = sb == nullptr;
-    if (rc == DD_OK && d->split) rc = d->split_stats.reserve(4 * sizeof(unsigned int));
-    if (rc == DD_OK && d->split) rc = d->split_stats_host.reserve(4 * sizeof(unsigned int));
-    if (rc == DD_OK && d->split && hipEventCreateWithFlags(&d->split_done, hipEventDisableTiming) != hipSuccess) {
+    if (rc == DD_OK && prog) rc = d->prog.scans.reserve((size_t)max_frames * sizeof(dd_jpeg_scans));
+    if (rc == DD_OK && prog) rc = d->prog.scans_host.reserve((size_t)max_frames * sizeof(dd_jpeg_scans));
+    if (rc == DD_OK && split) rc = d->split.stats.reserve(4 * sizeof(unsigned int));
+    if (rc == DD_OK && split) rc = d->split.stats_host.reserve(4 * sizeof(unsigned int));
+    if (rc == DD_OK && split && hipEventCreateWithFlags(&d->split.done, hipEventDisableTiming) != hipSuccess) {
         dd_set_error("%s: hipEventCreateWithFlags failed", who);
         rc = DD_E_HIP;
     }
@@ -869,13 +777,13 @@ int dd_jpegdec_destroy(dd_jpegdec *d) {
     if (d->ctx) (void)hipSetDevice(d->ctx->device);
     d->recs.release(), d->bytes.release(), d->coef.release(), d->starts.release(), d->mark.release(), d->planes.release();
     d->recs_host.release();
-    d->scans.release(), d->pstarts.release(), d->scans_host.release();
+    d->prog.scans.release(), d->prog.starts.release(), d->prog.scans_host.release();
     if (d->uploaded) (void)hipEventDestroy(d->uploaded);
-    d->split_stats.release(), d->split_stats_host.release();
-    if (d->split_done) (void)hipEventDestroy(d->split_done);
-    for (hipEvent_t e : d->ev)
+    d->split.stats.release(), d->split.stats_host.release();
+    if (d->split.done) (void)hipEventDestroy(d->split.done);
+    for (hipEvent_t e : d->profile.ev)
         if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : d->lev)
+    for (hipEvent_t e : d->profile.lev)
         if (e) (void)hipEventDestroy(e);
     delete d;
     return DD_OK;
@@ -885,65 +793,65 @@ int dd_jpegdec_profile(dd_jpegdec *d, int on) {
     DD_REQUIRE(d, DD_E_ARG, "dd_jpegdec_profile: NULL decoder");
     DD_DEVICE(d->ctx);
     if (on)
-        for (hipEvent_t &e : d->ev)
+        for (hipEvent_t &e : d->profile.ev)
             if (!e) DD_HIP(hipEventCreate(&e));
-    if (on && d->progressive)
-        for (hipEvent_t &e : d->lev)
+    if (on && d->cfg.has(DD_JPEGDEC_PROGRESSIVE))
+        for (hipEvent_t &e : d->profile.lev)
             if (!e) DD_HIP(hipEventCreate(&e));
-    d->profile = on != 0;
-    d->profiled = false;
+    d->profile.on = on != 0;
+    d->profile.done = false;
     return DD_OK;
 }
 
 int dd_jpegdec_profile_read(dd_jpegdec *d, float *ms_host) {
     DD_REQUIRE(d && ms_host, DD_E_ARG, "dd_jpegdec_profile_read: NULL argument");
-    DD_REQUIRE(d->profiled, DD_E_STATE, "dd_jpegdec_profile_read: no profiled decode (dd_jpegdec_profile(dec, 1), then a decode with a frame to decode)");
+    DD_REQUIRE(d->profile.done, DD_E_STATE, "dd_jpegdec_profile_read: no profiled decode (dd_jpegdec_profile(dec, 1), then a decode with a frame to decode)");
     DD_DEVICE(d->ctx);
-    DD_HIP(hipEventSynchronize(d->ev[4]));
-    for (int i = 0; i < 4; ++i) DD_HIP(hipEventElapsedTime(&ms_host[i], d->ev[i], d->ev[i + 1]));
+    DD_HIP(hipEventSynchronize(d->profile.ev[4]));
+    for (int i = 0; i < 4; ++i) DD_HIP(hipEventElapsedTime(&ms_host[i], d->profile.ev[i], d->profile.ev[i + 1]));
     return DD_OK;
 }
 
 int dd_jpegdec_profile_levels(dd_jpegdec *d, float *ms_host, int *n_levels_host) {
     DD_REQUIRE(d && ms_host && n_levels_host, DD_E_ARG, "dd_jpegdec_profile_levels: NULL argument");
-    DD_REQUIRE(d->profiled, DD_E_STATE, "dd_jpegdec_profile_levels: no profiled decode (dd_jpegdec_profile(dec, 1), then a decode with a frame to decode)");
+    DD_REQUIRE(d->profile.done, DD_E_STATE, "dd_jpegdec_profile_levels: no profiled decode (dd_jpegdec_profile(dec, 1), then a decode with a frame to decode)");
     DD_DEVICE(d->ctx);
-    DD_HIP(hipEventSynchronize(d->ev[4]));
+    DD_HIP(hipEventSynchronize(d->profile.ev[4]));
     for (int i = 0; i < DD_JPEG_MAX_LEVELS; ++i) ms_host[i] = 0.f;
-    for (int i = 0; i < d->levels_run; ++i) DD_HIP(hipEventElapsedTime(&ms_host[i], d->lev[i], d->lev[i + 1]));
-    *n_levels_host = d->levels_run;
+    for (int i = 0; i < d->profile.levels_run; ++i) DD_HIP(hipEventElapsedTime(&ms_host[i], d->profile.lev[i], d->profile.lev[i + 1]));
+    *n_levels_host = d->profile.levels_run;
     return DD_OK;
 }
 
 int dd_jpegdec_split_stats(dd_jpegdec *d, int64_t *out_host) {
     DD_REQUIRE(d && out_host, DD_E_ARG, "dd_jpegdec_split_stats: NULL argument");
     for (int i = 0; i < 4; ++i) out_host[i] = 0;
-    if (!d->split || !d->split_queued) return DD_OK;
+    if (!d->split.queued) return DD_OK;
     DD_DEVICE(d->ctx);
-    DD_HIP(hipEventSynchronize(d->split_done));
-    const unsigned int *st = d->split_stats_host.as<unsigned int>();
-    out_host[0] = d->split_files, out_host[1] = st[0], out_host[2] = st[1], out_host[3] = st[2];
+    DD_HIP(hipEventSynchronize(d->split.done));
+    const unsigned int *st = d->split.stats_host.as<unsigned int>();
+    out_host[0] = d->split.files, out_host[1] = st[0], out_host[2] = st[1], out_host[3] = st[2];
     return DD_OK;
 }
 
 static int jd_decode(const char *who, dd_jpegdec *d, const uint8_t *files_host, const int64_t *offsets, const int64_t *lengths, const int *scales, int n, uint8_t *out_dev,
                      int *status_dev, void *stream) {
     DD_REQUIRE(d && files_host && offsets && lengths && out_dev && status_dev, DD_E_ARG, "%s: NULL argument", who);
-    DD_REQUIRE(n >= 1 && n <= d->max_frames, DD_E_CAPACITY, "%s: %d frames (1 .. %d)", who, n, d->max_frames);
-    DD_REQUIRE(!scales || d->any_size, DD_E_STATE, "%s: a scale per file needs a decoder made with DD_JPEGDEC_ANY_SIZE", who);
+    DD_REQUIRE(n >= 1 && n <= d->cfg.max_frames, DD_E_CAPACITY, "%s: %d frames (1 .. %d)", who, n, d->cfg.max_frames);
+    DD_REQUIRE(!scales || d->cfg.has(DD_JPEGDEC_ANY_SIZE), DD_E_STATE, "%s: a scale per file needs a decoder made with DD_JPEGDEC_ANY_SIZE", who);
     for (int i = 0; scales && i < n; ++i)
-        DD_REQUIRE(jpd_scale_ok(scales[i]) && scales[i] >= d->scale, DD_E_ARG, "%s: file %d at scale %d (1, 2, 4 or 8, and at least the decoder's %d)", who, i, scales[i], d->scale);
+        DD_REQUIRE(jpd_scale_ok(scales[i]) && scales[i] >= d->cfg.scale, DD_E_ARG, "%s: file %d at scale %d (1, 2, 4 or 8, and at least the decoder's %d)", who, i, scales[i], d->cfg.scale);
     DD_DEVICE(d->ctx);
     hipStream_t s = dd_pick_stream(d->ctx, stream);
     dd_jpeg_info *recs = d->recs_host.as<dd_jpeg_info>();
-    dd_jpeg_scans *scans = d->progressive ? d->scans_host.as<dd_jpeg_scans>() : nullptr;
+    dd_jpeg_scans *scans = d->cfg.has(DD_JPEGDEC_PROGRESSIVE) ? d->prog.scans_host.as<dd_jpeg_scans>() : nullptr;
     size_t n_bytes = 0;
     for (int i = 0; i < n; ++i) {
         DD_REQUIRE(offsets[i] >= 0 && lengths[i] >= 0 && lengths[i] <= 0x7fffffffll, DD_E_ARG, "%s: file %d at offset %lld, length %lld", who, i,
                    (long long)offsets[i], (long long)lengths[i]);
         const size_t end = (size_t)offsets[i] + (size_t)lengths[i];
-        DD_REQUIRE(end <= d->max_bytes, DD_E_CAPACITY, "%s: file %d ends at byte %zu, the decoder holds %zu", who, i, end, d->max_bytes);
-        ddk::jpegdec_parse(files_host + offsets[i], (size_t)lengths[i], d->g.H, d->g.W, &recs[i], scans ? &scans[i] : nullptr, d->flags);
+        DD_REQUIRE(end <= d->cfg.max_bytes, DD_E_CAPACITY, "%s: file %d ends at byte %zu, the decoder holds %zu", who, i, end, d->cfg.max_bytes);
+        ddk::jpegdec_parse(files_host + offsets[i], (size_t)lengths[i], d->cfg.g.H, d->cfg.g.W, &recs[i], scans ? &scans[i] : nullptr, d->cfg.flags);
         recs[i].file_offset = offsets[i];
         if (lengths[i] && end > n_bytes) n_bytes = end;
     }

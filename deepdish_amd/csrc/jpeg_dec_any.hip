@@ -1,23 +1,23 @@
-// The pixel stage of the JPEG decoder for files of any size up to the decoder's, each at its own scale (DD_JPEGDEC_ANY_SIZE;
-// csrc/jpeg_dec.hip jpegdec_launch decides the path and the scale of every file, holds its record to the decoder's buffers and calls
-// jpegdec_pixels_any).  The device functions are those of the existing pixel kernels (csrc/jpeg_dec_pix.h); these kernels are in a file of
-// their own so that the existing ones compile to what they compiled to.
+// The pixel stage of the JPEG decoder for a DD_JPEGDEC_ANY_SIZE decoder: files of any size up to the decoder's, each at its own scale, each
+// written into the top-left corner of a uniform slot.  csrc/jpeg_dec.hip describes the stages in front of this one; the call plan
+// (csrc/jpeg_dec_plan.h) has decided every file's path and scale, has held its record to the decoder's strides, and says which scales
+// occur (JdPerScale).  The kernels here are those of csrc/jpeg_dec.hip's pixel stage with the scale a template argument at 1 as well, a
+// slot pitch, and a test that passes over the files of another scale; the device functions are shared (csrc/jpeg_dec_pix.h).  They have
+// a translation unit of their own because they are a separate family of eight kernels that only this option launches.
 #include "common.h"
 #include "jpeg_dec_dev.h"
 #include "jpeg_dec_pix.h"
+#include "jpeg_dec_plan.h"
 
 namespace {
 
-// Only a decoder made with DD_JPEGDEC_ANY_SIZE launches these.  The four pixel kernels of csrc/jpeg_dec.hip for files of any size up to the
-// decoder's, each at its own scale: a record's path holds the path in bits 0 .. 7 and the log2 of the file's scale in bits 8 .. 15, the frame
-// is the top-left ceil(h / S) x ceil(w / S) of a slot of OH x OW whose rows are OW * 3 bytes apart, and a launch passes over the files of
-// another scale.  The planes and the coefficients keep the file's own dense layout inside the decoder's strides, which bound every accepted
-// file's (jpegdec_launch checks that on the host).
+// A record's path holds the path and the log2 of the file's scale (jd_path_pack); the frame is the top-left ceil(h / S) x ceil(w / S) of a
+// slot of OH x OW whose rows are OW * 3 bytes apart.  The planes and the coefficients keep the file's own dense layout inside the
+// decoder's strides, which bound every accepted file's (the plan checks that on the host).
 
 template <int S>
 __device__ __forceinline__ bool jd_any_mine(const dd_jpeg_info &r, int path) {
-    constexpr int LOG2 = S == 1 ? 0 : S == 2 ? 1 : S == 4 ? 2 : 3;
-    return r.path == (path | LOG2 << 8);
+    return r.path == jd_path_pack(path, jd_scale_log2(S));
 }
 
 // Rows [y_first, y_first + rows) of the file's ow pixels wide frame at `out`, rows `pitch` bytes apart, from planes whose row 0 is output
@@ -97,36 +97,34 @@ __global__ __launch_bounds__(JD_T) void jpeg_pixels_any_k(const dd_jpeg_info *__
     }
 }
 
-template <int S>
-int jd_launch_pixels_any(unsigned grid, size_t lds, hipStream_t s, bool any_planes, const dd_jpeg_info *recs, const JdGeom &g, const int *mark, const int16_t *coef,
-                         uint8_t *planes, uint8_t *out_dev, int OH, int OW) {
-    if (any_planes) {
-        hipLaunchKernelGGL(jpeg_planes_any_k<S>, dim3(grid), dim3(JD_T), 0, s, recs, g, mark, coef, planes);
-        DD_LAUNCH_CHECK();
-    }
-    const int vec = (OW & 3) == 0 && (reinterpret_cast<uintptr_t>(out_dev) & 3) == 0;
-    hipLaunchKernelGGL(jpeg_pixels_any_k<S>, dim3(grid), dim3(JD_T), lds, s, recs, g, mark, coef, planes, out_dev, OH, OW, vec);
-    DD_LAUNCH_CHECK();
-    return DD_OK;
-}
-
 }  // namespace
 
 namespace ddk {
 
-// One launch pair per scale that occurs (log2 0 .. 3): jpeg_planes_any_k<S> where a file of that scale takes DD_JPEGDEC_PLANES, then
-// jpeg_pixels_any_k<S> with the largest LDS a file of that scale needs.  n files, max_bands workgroups each.
-int jpegdec_pixels_any(hipStream_t s, int n, int max_bands, long long coef_stride, long long plane_stride, const size_t *lds_at, const bool *any_at, const bool *planes_at,
-                       const dd_jpeg_info *recs, const int *mark, const int16_t *coef, uint8_t *planes, uint8_t *out_dev, int OH, int OW) {
+// One launch pair per scale that occurs in the call: jpeg_planes_any_k<S> where a file of that scale takes DD_JPEGDEC_PLANES, then
+// jpeg_pixels_any_k<S> with the most LDS a file of that scale needs.  n files, max_bands workgroups each; each launch passes over the
+// other scales' files.  OH x OW: the slot.
+int jpegdec_pixels_any(hipStream_t s, int n, int max_bands, long long coef_stride, long long plane_stride, const JdPerScale &per_scale, const dd_jpeg_info *recs,
+                       const int *mark, const int16_t *coef, uint8_t *planes, uint8_t *out_dev, int OH, int OW) {
     JdGeom g{};
     g.max_bands = max_bands, g.coef_stride = coef_stride, g.plane_stride = plane_stride;
     const unsigned grid = (unsigned)n * (unsigned)max_bands;
-    int rc = DD_OK;
-    if (rc == DD_OK && any_at[0]) rc = jd_launch_pixels_any<1>(grid, lds_at[0], s, planes_at[0], recs, g, mark, coef, planes, out_dev, OH, OW);
-    if (rc == DD_OK && any_at[1]) rc = jd_launch_pixels_any<2>(grid, lds_at[1], s, planes_at[1], recs, g, mark, coef, planes, out_dev, OH, OW);
-    if (rc == DD_OK && any_at[2]) rc = jd_launch_pixels_any<4>(grid, lds_at[2], s, planes_at[2], recs, g, mark, coef, planes, out_dev, OH, OW);
-    if (rc == DD_OK && any_at[3]) rc = jd_launch_pixels_any<8>(grid, lds_at[3], s, planes_at[3], recs, g, mark, coef, planes, out_dev, OH, OW);
-    return rc;
+    const int vec = (OW & 3) == 0 && (reinterpret_cast<uintptr_t>(out_dev) & 3) == 0;
+    for (int lg = 0; lg < 4; ++lg) {
+        if (!per_scale.any_at[lg]) continue;
+        const int rc = jd_with_scale(1 << lg, [&](auto scale) -> int {
+            constexpr int S = decltype(scale)::value;
+            if (per_scale.planes_at[lg]) {
+                hipLaunchKernelGGL(jpeg_planes_any_k<S>, dim3(grid), dim3(JD_T), 0, s, recs, g, mark, coef, planes);
+                DD_LAUNCH_CHECK();
+            }
+            hipLaunchKernelGGL(jpeg_pixels_any_k<S>, dim3(grid), dim3(JD_T), per_scale.lds_at[lg], s, recs, g, mark, coef, planes, out_dev, OH, OW, vec);
+            DD_LAUNCH_CHECK();
+            return DD_OK;
+        });
+        if (rc != DD_OK) return rc;
+    }
+    return DD_OK;
 }
 
 }  // namespace ddk

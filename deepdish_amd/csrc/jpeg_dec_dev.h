@@ -13,13 +13,7 @@
 // Arithmetic is 32-bit; what can wrap on hostile coefficients is computed in uint32_t.
 #pragma once
 #include <cstdint>
-#include "jpeg_parse.h"
-
-#if defined(__HIPCC__)
-#define JPD_HD __host__ __device__ __forceinline__
-#else
-#define JPD_HD inline
-#endif
+#include "jpeg_dec_plan.h"                     // JPD_HD; the scales and jpd_plane, which the call plan needs as well
 
 struct JpdBits {
     const uint8_t *p;
@@ -395,28 +389,8 @@ JPD_HD uint32_t jpd_bgr(int y, int cb, int cr) {
     return (uint32_t)b | ((uint32_t)g << 8) | ((uint32_t)r << 16);
 }
 
-// ---- decoding at 1/2, 1/4 and 1/8 scale (libjpeg's scale_num / scale_denom, Pillow's Image.draft; tests/jpeg_scaled_ref.py is the
-// definition).  The entropy decoder and the coefficients are the full-size ones; every 8 x 8 block is transformed straight to n x n
-// samples, n chosen per component.
-
-JPD_HD bool jpd_scale_ok(int s) { return s == 1 || s == 2 || s == 4 || s == 8; }
-
-// jdmaster.c: a component sampled hs x vs below hmax x vmax turns its blocks into n x n samples at scale 1 / s -- 8 / s, doubled while
-// that still divides what the most densely sampled component gets, so that 4:2:0 chroma needs no up-sampling at any s >= 2 -- and its
-// plane, before cropping to the output, holds rows x cols samples of an h x w file.
-struct JpdPlane {
-    int n, rows, cols;
-};
-
-JPD_HD JpdPlane jpd_plane(int h, int w, int hs, int vs, int hmax, int vmax, int s) {
-    const int m = 8 / s;
-    JpdPlane p;
-    p.n = m;
-    while (p.n < 8 && (hmax * m) % (hs * p.n * 2) == 0 && (vmax * m) % (vs * p.n * 2) == 0) p.n *= 2;
-    p.rows = (int)(((long long)h * vs * p.n + vmax * 8 - 1) / (vmax * 8));
-    p.cols = (int)(((long long)w * hs * p.n + hmax * 8 - 1) / (hmax * 8));
-    return p;
-}
+// ---- decoding at 1/2, 1/4 and 1/8 scale: jpd_scale_ok and jpd_plane (csrc/jpeg_dec_plan.h) say what n x n samples a block becomes; these are
+// the transforms.
 
 // jidctred.c (CONST_BITS 13, PASS1_BITS 2).  The column pass is exact in 64 bits for every int16 coefficient times an 8-bit quantiser, so
 // what it hands to the row pass fits 32 bits; the row pass wraps like jpd_idct8, which the range limit's & 1023 does not see.

@@ -1,51 +1,15 @@
-// Device-side pieces of the JPEG decoder's pixel stage, shared by its two translation units: csrc/jpeg_dec.hip (jpeg_pixels_k, jpeg_planes_k,
-// jpeg_pixels_scaled_k<S>, jpeg_planes_scaled_k<S>) and csrc/jpeg_dec_any.hip (jpeg_pixels_any_k<S>, jpeg_planes_any_k<S>, which only a
-// decoder made with DD_JPEGDEC_ANY_SIZE launches).  The band geometry, the block transforms at every scale, up-sampling and colour conversion.
-// The new kernels live in a file of their own so that the code the compiler makes of the existing ones stays what it was.
+// The pixel stage of the JPEG decoder on the device: what its kernels do to one band (one MCU row) of one file.  A band's blocks are
+// dequantised and transformed (jd_block, jd_block_scaled<N>) into sample planes Y, Cb, Cr laid out as the plan's JdBand says
+// (csrc/jpeg_dec_plan.h), in LDS or -- a band too wide for LDS, DD_JPEGDEC_PLANES -- in HBM; then every output pixel is up-sampled and
+// colour-converted from the planes (jd_pixel, jd_pixel_scaled<S>) and the rows are stored in order (jd_paint, jd_paint_scaled<S>).  At scale 1 the
+// h2v2 filter's chroma row above and below the band comes from transforming those neighbouring chroma blocks again (the halo); at 1/2, 1/4
+// and 1/8 every block goes straight to 4 x 4, 2 x 2 or 1 x 1 samples, 4:2:0 chroma is not up-sampled at all and there is no halo.
+// Two translation units include this: csrc/jpeg_dec.hip, whose kernels write dense frames of the decoder's one size and scale, and
+// csrc/jpeg_dec_any.hip, whose kernels write every file at its own size and scale into a slot (DD_JPEGDEC_ANY_SIZE).
 #pragma once
 #include "jpeg_dec_dev.h"
 
 namespace {
-
-constexpr int JD_T = 256;                      // threads per workgroup (markers, pixels)
-constexpr int JD_LDS_MAX = 64 * 1024;          // a band's planes; what every kernel may use without asking
-
-struct JdGeom {
-    int H, W, max_bands;
-    long long coef_stride;                     // int16 per frame: the largest accepted sampling's blocks
-    long long plane_stride;                    // bytes per frame of the HBM planes
-};
-
-struct JdBand {
-    int Wy, Wc, yrows, crows, halo;
-    size_t lds;
-};
-
-__host__ __device__ inline JdBand jd_band(int W, int ncomp, int hs, int vs) {
-    JdBand b;
-    const int mx = (W + 8 * hs - 1) / (8 * hs);
-    b.Wy = mx * 8 * hs, b.Wc = mx * 8;
-    b.yrows = 8 * vs;
-    b.halo = ncomp == 3 && vs == 2 ? 1 : 0;
-    b.crows = ncomp == 3 ? 8 + 2 * b.halo : 0;
-    b.lds = (size_t)b.yrows * b.Wy + 2 * (size_t)b.crows * b.Wc;
-    return b;
-}
-
-// The same at scale 1 / s.  At s >= 2 a band is still one MCU row, 8 * vs / s output rows; every component's rows coincide with the
-// luma's (4:2:0 chroma keeps blocks of twice the luma's side, csrc/jpeg_dec_dev.h jpd_plane), so there is no halo.
-__host__ __device__ inline JdBand jd_band(int W, int ncomp, int hs, int vs, int s) {
-    if (s == 1) return jd_band(W, ncomp, hs, vs);
-    JdBand b;
-    const int mx = (W + 8 * hs - 1) / (8 * hs);
-    const int ny = 8 / s, nc = jpd_plane(1, 1, 1, 1, hs, vs, s).n;
-    b.Wy = mx * hs * ny, b.Wc = mx * nc;
-    b.yrows = vs * ny;
-    b.halo = 0;
-    b.crows = ncomp == 3 ? nc : 0;
-    b.lds = (size_t)b.yrows * b.Wy + 2 * (size_t)b.crows * b.Wc;
-    return b;
-}
 
 // Block `blk` of a frame: dequantise and transform.  rows: -1 all eight to dst (stride bytes apart), else that one row to dst.
 __device__ __forceinline__ void jd_block(const int16_t *__restrict__ coef, size_t blk, const uint16_t *__restrict__ q, uint8_t *dst, int stride, int row) {
@@ -174,7 +138,7 @@ __device__ __forceinline__ void jd_paint(const dd_jpeg_info &r, const JdBand &b,
     }
 }
 
-// ---- 1/2, 1/4 and 1/8 scale: the two kernels above specialised on the scale denominator S.  The full-size kernels stay as they are.
+// ---- 1/2, 1/4 and 1/8 scale: the same, specialised on the scale denominator S.
 
 // Block `blk` of a frame to N x N samples at dst, rows `stride` bytes apart.  N = 8 is the full transform (4:2:0 chroma at S = 2).  dst is
 // aligned to N bytes: every plane starts at a multiple of its block side and is a whole number of blocks wide.
