@@ -121,6 +121,9 @@ SIGNATURES = {
     'dd_ssd_detections': [P, P, P, P, c_int, c_int, c_double, c_double, c_double, c_double, P, P, P, P, P],
     'dd_yolov5_decode': [P, P, c_int, c_int, c_float, c_float, c_float, P, P, P, c_int, P, P],
     'dd_yolov5_decode_letterbox': [P, P, c_int, c_int, c_float, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P],
+    'dd_yolov5_decode_batch': [P, P, c_int, c_int, c_float, c_float, c_float, c_int, c_int, P, P, P, c_int, P, c_int, P],
+    'dd_yolov5_select_batch': [P, P, P, P, c_int, c_float, c_float, c_float, c_int, c_int, P, P, P, c_int, P, c_int, P],
+    'dd_yolov5_pack': [P, P, P, P, P, c_int, c_int, P, P],
     'dd_pipeline_create': [P, c_int, c_int, c_int, P, P, c_int, c_int, P, c_char_p, c_char_p, c_double, c_double,
                            c_double, c_int, c_int, P, c_int, c_int, POINTER(P)],
     'dd_pipeline_destroy': [P],

@@ -13,6 +13,8 @@
 // scan stops early once `max_keep` survivors exist (greedy prefix property).
 // Ties in the key are resolved "higher original index first" (what a stable ascending argsort read
 // from the back gives); the reference's own order under ties is unspecified (unstable sort).
+// A NaN key (modes 0 and 1) ranks as the largest key, as np.argsort places it; among NaN keys -- and between a NaN and a +inf key,
+// which are one level here -- the higher original index comes first.
 #include "common.h"
 
 namespace {
@@ -21,6 +23,11 @@ constexpr int MAXK = 4096;
 typedef unsigned long long u64;
 
 struct SBox { double a, b, c, d, area; };   // mode 0: x1,y1,x2,y2,area ; mode 1: x,y,w,h,area ; mode 2: ymin,xmin,ymax,xmax,area
+
+// A NaN key is the largest key (np.argsort places it last, so the reference picks it first): it is made +inf where the key is loaded,
+// and the comparisons below stay a total order.  A NaN and a +inf key then tie and go by index like any other tie.
+template <typename T>
+__device__ __forceinline__ T canon_key(T k) { return k != k ? (T)__builtin_inf() : k; }
 
 __device__ __forceinline__ bool before(double ka, int ia, double kb, int ib) {
     return ka > kb || (ka == kb && ia > ib);
@@ -80,7 +87,7 @@ __device__ __forceinline__ void nms_small_body(const TB *__restrict__ boxes, con
     double key = -__builtin_inf();
     SBox mine = {0, 0, 0, 0, 0};
     if (lane < k) {
-        key = (double)keys[o0 + lane];
+        key = canon_key((double)keys[o0 + lane]);
         mine = make_sbox(boxes + (size_t)(o0 + lane) * 4, mode);
     }
     int rank = 0;
@@ -132,7 +139,7 @@ __global__ __launch_bounds__(256) void nms_rank_k(const TB *__restrict__ boxes, 
     boxes += (size_t)blockIdx.z * k * 4; keys += (size_t)blockIdx.z * k;     // blockIdx.z = image of a batch
     sorted += (size_t)blockIdx.z * k; sidx += (size_t)blockIdx.z * k;
     const int kp = (k + V - 1) / V * V;
-    for (int i = threadIdx.x; i < kp; i += blockDim.x) skey[i] = i < k ? keys[i] : (TB)(-__builtin_inf());
+    for (int i = threadIdx.x; i < kp; i += blockDim.x) skey[i] = i < k ? canon_key(keys[i]) : (TB)(-__builtin_inf());
     __syncthreads();
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= k) return;

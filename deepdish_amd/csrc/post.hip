@@ -59,6 +59,7 @@ __global__ __launch_bounds__(256) void ssd_decode_k(const float *__restrict__ ra
         const int oi = __shfl_xor(bi, o, 64);
         if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
     }
+    if (bi == 0x7fffffff) bi = 0;                             // no class won (every logit -inf or NaN: a NaN logit never wins): class 0, score sigmoid(-inf) = 0
     if (live && sub == 0) {
         const float rr[4] = {r[0], r[1], r[2], r[3]};
         const float an[4] = {anchors[a * 4 + 0], anchors[a * 4 + 1], anchors[a * 4 + 2], anchors[a * 4 + 3]};
@@ -547,6 +548,48 @@ int dd_yolov5_decode_letterbox(dd_ctx *ctx, const float *raw, int n_rows, int n_
     if ((rc = ctx->scratch[2].reserve((size_t)n_rows * 8 + 256)) != DD_OK) return rc;
     return ddk::yolov5_decode_letterbox(s, raw, n_rows, n_cls, thr, img_w, img_h, net_w, net_h, out_boxes, out_scores, out_cls, cap, out_n, 1,
                                         ctx->scratch[2].p);
+}
+
+// dd_yolov5_decode / dd_yolov5_decode_letterbox (net_w > 0) for `batch` images in one call: the two launches of the batched pipeline.
+int dd_yolov5_decode_batch(dd_ctx *ctx, const float *raw, int n_rows, int n_cls, float thr, float img_w, float img_h, int net_w, int net_h,
+                           float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch, void *stream) {
+    DD_REQUIRE(ctx && raw && out_boxes && out_scores && out_cls && out_n && n_rows >= 0 && n_cls > 0 && cap >= 0 && batch > 0,
+               DD_E_ARG, "dd_yolov5_decode_batch: bad argument");
+    DD_REQUIRE(net_w <= 0 || (img_w == (float)(int)img_w && img_h == (float)(int)img_h), DD_E_ARG,
+               "dd_yolov5_decode_batch: a letterboxed frame has a whole number of pixels");
+    DD_DEVICE(ctx);
+    hipStream_t s = dd_pick_stream(ctx, stream);
+    if (n_rows == 0) { DD_HIP(hipMemsetAsync(out_n, 0, sizeof(int) * (size_t)batch, s)); return DD_OK; }
+    int rc;
+    if ((rc = ctx->scratch[2].reserve((size_t)batch * n_rows * 8 + 256)) != DD_OK) return rc;
+    if (net_w > 0)
+        return ddk::yolov5_decode_letterbox(s, raw, n_rows, n_cls, thr, (int)img_w, (int)img_h, net_w, net_h, out_boxes, out_scores, out_cls, cap,
+                                            out_n, batch, ctx->scratch[2].p);
+    return ddk::yolov5_decode(s, raw, n_rows, n_cls, thr, img_w, img_h, out_boxes, out_scores, out_cls, cap, out_n, batch, ctx->scratch[2].p);
+}
+
+// The second half alone (ddk::yolov5_select, with net_w > 0 ddk::yolov5_select_letterbox) on per-row boxes, confidences and classes.
+int dd_yolov5_select_batch(dd_ctx *ctx, const float *boxes4, const float *conf, const int *cls, int n_rows, float thr, float img_w, float img_h,
+                           int net_w, int net_h, float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch, void *stream) {
+    DD_REQUIRE(ctx && boxes4 && conf && cls && out_boxes && out_scores && out_cls && out_n && n_rows >= 0 && cap >= 0 && batch > 0,
+               DD_E_ARG, "dd_yolov5_select_batch: bad argument");
+    DD_REQUIRE(net_w <= 0 || (img_w == (float)(int)img_w && img_h == (float)(int)img_h), DD_E_ARG,
+               "dd_yolov5_select_batch: a letterboxed frame has a whole number of pixels");
+    DD_DEVICE(ctx);
+    hipStream_t s = dd_pick_stream(ctx, stream);
+    if (n_rows == 0) { DD_HIP(hipMemsetAsync(out_n, 0, sizeof(int) * (size_t)batch, s)); return DD_OK; }
+    if (net_w > 0)
+        return ddk::yolov5_select_letterbox(s, boxes4, conf, cls, n_rows, thr, (int)img_w, (int)img_h, net_w, net_h, out_boxes, out_scores, out_cls,
+                                            cap, out_n, batch);
+    return ddk::yolov5_select(s, boxes4, conf, cls, n_rows, thr, img_w, img_h, out_boxes, out_scores, out_cls, cap, out_n, batch);
+}
+
+// ddk::yolov5_pack: the per-image [cap] outputs of the calls above -> packed rows of all images behind one another.
+int dd_yolov5_pack(dd_ctx *ctx, const float *boxes, const float *scores, const int *cls, const int *n_rows, int cap, int batch, float *packed,
+                   void *stream) {
+    DD_REQUIRE(ctx && boxes && scores && cls && n_rows && packed && cap >= 0 && batch > 0, DD_E_ARG, "dd_yolov5_pack: bad argument");
+    DD_DEVICE(ctx);
+    return ddk::yolov5_pack(dd_pick_stream(ctx, stream), boxes, scores, cls, n_rows, cap, batch, packed);
 }
 
 int dd_counts_accumulate(dd_ctx *ctx, int64_t *acc, const int64_t *counts_host, int n, void *stream) {

@@ -91,7 +91,9 @@ int dd_euclidean_nn_cost(dd_ctx *ctx, const float *gallery, const int *offsets_h
 
 /* deep_sort/preprocessing.py:6-73 non_max_suppression (greedy, +1 pixel, inter/area_other > thr).
  * `keys` is the sort key (scores, or y2 when the reference is called with scores=None).
- * out_idx[k] receives the surviving indices in pick order, *out_n their number (both device). */
+ * out_idx[k] receives the surviving indices in pick order, *out_n their number (both device).
+ * Equal keys: the higher original index first.  A NaN key ranks as the largest key (np.argsort places it last, so the reference
+ * picks it first); it is treated as +inf, so NaN keys -- and a NaN beside a +inf key -- tie and go by index.  k <= 4096. */
 int dd_nms(dd_ctx *ctx, const double *tlwh, const double *keys, int k, double max_overlap,
            int *out_idx, int *out_n, void *stream);
 
@@ -473,7 +475,8 @@ int dd_ssd_postprocess(dd_ctx *ctx, const float *raw, const float *anchors, int 
 
 /* The op's first stage alone, `batch` images: raw f32 [batch][n_anchors][4+n_classes] -> per anchor boxes f32 [.][4]
  * (ymin,xmin,ymax,xmax), scores (sigmoid of the best class logit, background excluded), classes int32 (id - 1, lowest
- * on ties), keys f32 (score, or -1 below score_thr) -- and its second stage (class-agnostic NMS, top max_det) from
+ * on ties; a NaN logit never wins, and an anchor no class wins -- every logit -inf or NaN -- gives class 0 with score 0, so the
+ * class is always in [0, n_classes - 2]), keys f32 (score, or -1 below score_thr) -- and its second stage (class-agnostic NMS, top max_det) from
  * those arrays.  dd_ssd_postprocess = the two in one call for one image. */
 int dd_ssd_decode(dd_ctx *ctx, const float *raw, const float *anchors, int n_anchors, int n_classes, float score_thr,
                   float *boxes, float *scores, int *classes, float *keys, int batch, void *stream);
@@ -539,7 +542,7 @@ int dd_net_yolo_decoded_read(dd_net *net, int n, float *boxes_host, float *conf_
 /* tools/ssd_mobilenet.py:111-150, SSDMobileNet.predict after its four get_tensor calls, for `batch` images at once:
  * NaN scrub (:111-116), score >= confidence (:119), reorder [1,0,3,2] and scale by (w,h,w,h) in f64 (:121-127),
  * per-class nms_boxes (:59-98, see dd_nms_ssd).  Inputs are the outputs of dd_ssd_postprocess (device):
- * boxes f32 [batch][max_det][4], classes f32, scores f32 [batch][max_det], max_det <= 16.  Outputs (device):
+ * boxes f32 [batch][max_det][4], classes f32, scores f32 [batch][max_det], max_det <= 64.  Outputs (device):
  * out_boxes f64 [batch][max_det][4] xyxy pixels, out_cls int32 (class id = label-file line - 1, :142-147),
  * out_scores f64, out_n int32 [batch].  Rows come class by class in ascending id (the reference walks a Python
  * set) and inside a class in nms_boxes' pick order. */
@@ -560,6 +563,25 @@ int dd_yolov5_decode(dd_ctx *ctx, const float *raw, int n_rows, int n_cls, float
  * are).  No int(), no clipping: boxes in the padding come out negative.  A frame with the canvas's aspect gives dd_yolov5_decode's bits. */
 int dd_yolov5_decode_letterbox(dd_ctx *ctx, const float *raw, int n_rows, int n_cls, float thr, int img_w, int img_h, int net_w, int net_h,
                                float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, void *stream);
+
+/* The forms of the two calls above that the batched pipeline launches, reachable on their own.
+ * dd_yolov5_decode_batch: raw f32 [batch][n_rows][5 + n_cls] -> per image out_boxes f32 [batch][cap][4], out_scores, out_cls
+ * [batch][cap], out_n [batch].  out_n[z] counts EVERY row of image z with confidence >= thr; the first min(out_n[z], cap) of them, in
+ * row order, are written and nothing behind them is touched.  net_w <= 0: the stretch arithmetic of dd_yolov5_decode; net_w > 0: the
+ * un-mapping of dd_yolov5_decode_letterbox (img_w, img_h whole numbers).  n_rows == 0 zeroes out_n and launches nothing.  Per-row
+ * scratch (confidence and class, batch * n_rows * 8 bytes plus alignment) comes from the context.
+ * dd_yolov5_select_batch: the second half alone on boxes4 f32 [batch][n_rows][4] (x, y, w, h), conf f32 and cls int32
+ * [batch][n_rows] (what dd_net_yolo_decoded hands out): same outputs, same geometry switch, no scratch.
+ * dd_yolov5_pack: those per-image outputs -> packed f32 rows {x1, y1, x2, y2, score, class bits} of all images behind one another,
+ * image z's min(n_rows[z], cap) rows starting at the sum over the images before it; n_rows int32 [batch] (device) as out_n above.
+ * Nothing is written past the total. */
+int dd_yolov5_decode_batch(dd_ctx *ctx, const float *raw, int n_rows, int n_cls, float thr, float img_w, float img_h, int net_w, int net_h,
+                           float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n, int batch, void *stream);
+int dd_yolov5_select_batch(dd_ctx *ctx, const float *boxes4, const float *conf, const int *cls, int n_rows, float thr, float img_w,
+                           float img_h, int net_w, int net_h, float *out_boxes, float *out_scores, int *out_cls, int cap, int *out_n,
+                           int batch, void *stream);
+int dd_yolov5_pack(dd_ctx *ctx, const float *boxes, const float *scores, const int *cls, const int *n_rows, int cap, int batch,
+                   float *packed, void *stream);
 
 /* ---------------------------------------------------------------- multi-stream hot path
  * The per-frame call sequence of the reference's Pipeline (deepdish.py:880-885 run_object_detector,

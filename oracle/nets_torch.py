@@ -153,7 +153,11 @@ def ssd_postprocess(raw, anchors, max_det=10, score_thr=1e-8, iou_thr=0.6):
     hh = f(0.5) * np.exp(raw[:, 2] / f(5)) * a[:, 2]
     hw = f(0.5) * np.exp(raw[:, 3] / f(5)) * a[:, 3]
     boxes = np.stack([yc - hh, xc - hw, yc + hh, xc + hw], axis=1).astype(np.float32)
-    sc = (f(1) / (f(1) + np.exp(-raw[:, 5:]))).astype(np.float32)        # class 0 = background
+    # class 0 = background.  A NaN logit never wins (the op's treatment of NaN is pinned to nothing; the kernels scan with a strict `>`):
+    # it counts as -inf, and an anchor whose logits are all -inf or NaN gets class 0 with score sigmoid(-inf) = 0.
+    logits = np.where(np.isnan(raw[:, 5:]), f(-np.inf), raw[:, 5:])
+    with np.errstate(over='ignore'):
+        sc = (f(1) / (f(1) + np.exp(-logits))).astype(np.float32)
     best_c = sc.argmax(axis=1)
     best = sc[np.arange(len(sc)), best_c]
     return ssd_postprocess_decoded(boxes, best, best_c, max_det, score_thr, iou_thr)
