@@ -69,6 +69,8 @@ SIGNATURES = {
     'dd_resize_bilinear': [P, P, c_int, c_int, c_int, P, c_int, c_int, P],
     'dd_yuv420_to_bgr': [P, P, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, P, P],
     'dd_yuv422_to_bgr': [P, P, c_int, c_int, c_int, c_int, c_int, c_int64, P, P],
+    'dd_raw8_to_bgr': [P, P, c_int, c_int, c_int, c_int, c_int, c_int64, P, P],
+    'dd_ingest_create_raw8': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
     'dd_ingest_create': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
     'dd_ingest_create_format': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P],
     'dd_ingest_create_jpeg': [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, P],

@@ -167,6 +167,10 @@ int yuv420_resize(hipStream_t s, const uint8_t *src, int n, int H, int W, int la
 // packed 4:2:2 YUV -> BGR (yuv.hip); order 4 YUY2, 5 UYVY; pitch / frame_stride 0 = dense; and its convert + flip + stretch of n dense frames
 int yuv422_to_bgr(hipStream_t s, const uint8_t *src, int batch, int H, int W, int order, int pitch, int64_t frame_stride, uint8_t *dst);
 int yuv422_resize(hipStream_t s, const uint8_t *src, int n, int H, int W, int order, int flip, int oh, int ow, uint8_t *out);
+// 8-bit raw sensor frames -> BGR (bayer.hip); layout 6 RGGB, 7 GRBG, 8 GBRG, 9 BGGR, 10 gray; pitch / frame_stride 0 = dense; and its convert +
+// flip + stretch of n dense frames
+int raw8_to_bgr(hipStream_t s, const uint8_t *src, int batch, int H, int W, int layout, int pitch, int64_t frame_stride, uint8_t *dst);
+int raw8_resize(hipStream_t s, const uint8_t *src, int n, int H, int W, int layout, int flip, int oh, int ow, uint8_t *out);
 // the JPEG decoder's two halves (jpeg_dec.hip), as the ingest ring drives them: a header into a record with the status a decoder of h x w
 // gives it (returned too; the reason is left in dd_last_error), and upload + kernels for n records without a host wait
 // scans / scans_host: NULL, or (a decoder made with DD_JPEGDEC_PROGRESSIVE) where each file's scan script goes, kept like the records

@@ -17,6 +17,11 @@
 // height, an even width.  The same three forms on the copy stream: yuv422_to_bgr straight into the slot's output without a transform,
 // yuv422_resize_k fused, or with DD_INGEST_YUV_FUSED=0 convert-into-the-staging-buffer then crop_resize.
 //
+// A slot may also hold 8-bit raw sensor frames, what a machine-vision or CSI camera delivers before any colour processing: a Bayer mosaic
+// (RGGB, GRBG, GBRG, BGGR) or monochrome, 1 byte per pixel, a third of BGR (dd_ingest_create_raw8).  The same three forms on the copy stream
+// (csrc/bayer.hip): raw8_to_bgr straight into the slot's output without a transform, raw8_resize_k fused, or with DD_INGEST_YUV_FUSED=0
+// convert-into-the-staging-buffer then crop_resize.
+//
 // A slot may also hold baseline JPEG files, what a camera or the reference's frame_%06d.jpg sequence delivers (a tenth or less of the raw
 // bytes): put() copies a stream's file into the slot's pinned arena and parses its header on the calling thread, submit() uploads the
 // bytes in use and the records and decodes on the copy stream (csrc/jpeg_dec.hip) -- into the slot's output, or into a staging buffer
@@ -28,6 +33,7 @@
 // frame, each file in its slot's top-left corner -- builds one crop box per stream from its record, uploads the boxes through the slot's
 // pinned memory and lets crop_resize stretch each to dst, as the reference's cv2.resize(frame, self.input_size) does whatever the camera sent.
 #include <algorithm>
+#include <climits>
 #include <cstddef>
 #include <cstdlib>
 #include <mutex>
@@ -37,7 +43,7 @@
 struct dd_ingest {
     dd_ctx *ctx = nullptr;
     int slots = 0, S = 0, sh = 0, sw = 0, dh = 0, dw = 0, flip = 0;
-    int format = 0;                         // 0 BGR, 1 NV12, 2 I420, 3 JPEG files, 4 YUY2, 5 UYVY
+    int format = 0;                         // 0 BGR, 1 NV12, 2 I420, 3 JPEG files, 4 YUY2, 5 UYVY, 6 .. 9 Bayer RGGB GRBG GBRG BGGR, 10 gray
     int jh = 0, jw = 0;                     // the frames in front of the flip + resize: sh x sw, or a JPEG ring's scaled decode
     bool transform = false, own_out = false, fused = true;
     uint8_t *d_stage = nullptr;             // YUV, two-launch form only: the converted BGR frames [S][sh][sw][3]
@@ -65,13 +71,16 @@ struct dd_ingest {
 };
 
 constexpr int INGEST_JPEG = 3, INGEST_YUY2 = 4, INGEST_UYVY = 5;
+constexpr int INGEST_RGGB = 6, INGEST_GRAY = 10;         // raw 8-bit: 6 .. 9 the Bayer mosaics, 10 monochrome
 static bool ingest_is_422(int format) { return format == INGEST_YUY2 || format == INGEST_UYVY; }
+static bool ingest_is_raw8(int format) { return format >= INGEST_RGGB && format <= INGEST_GRAY; }
 
 static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip,
-                         int pixel_format, dd_ingest **out, size_t jpeg_slot_bytes = 0, int jpeg_scale = 1, int jpeg_flags = 0) {
+                         int pixel_format, dd_ingest **out, size_t jpeg_slot_bytes = 0, int jpeg_scale = 1, int jpeg_flags = 0, bool raw8 = false) {
     DD_REQUIRE(ctx && out && slots > 0 && n_streams > 0 && src_h > 0 && src_w > 0 && dst_h > 0 && dst_w > 0, DD_E_ARG,
                "%s: bad argument", who);
-    DD_REQUIRE((pixel_format >= 0 && pixel_format <= 2) || ingest_is_422(pixel_format) || (pixel_format == INGEST_JPEG && jpeg_slot_bytes), DD_E_ARG,
+    DD_REQUIRE((pixel_format >= 0 && pixel_format <= 2) || ingest_is_422(pixel_format) || (pixel_format == INGEST_JPEG && jpeg_slot_bytes) ||
+               (raw8 && ingest_is_raw8(pixel_format)), DD_E_ARG,
                "%s: pixel_format %d is none of 0 (BGR), 1 (NV12), 2 (I420), 4 (YUY2), 5 (UYVY)", who, pixel_format);
     if (pixel_format == 1 || pixel_format == 2) {
         DD_REQUIRE(src_w % 2 == 0, DD_E_ARG, "%s: src_w %d must be even for 4:2:0 frames", who, src_w);
@@ -82,6 +91,7 @@ static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams,
         DD_REQUIRE(src_w % 2 == 0, DD_E_ARG, "%s: src_w %d must be even for 4:2:2 frames", who, src_w);
         DD_REQUIRE(n_streams <= 65535, DD_E_ARG, "%s: n_streams %d above 65535", who, n_streams);
     }
+    if (ingest_is_raw8(pixel_format)) DD_REQUIRE(n_streams <= 65535, DD_E_ARG, "%s: n_streams %d above 65535", who, n_streams);
     const bool any_size = pixel_format == INGEST_JPEG && (jpeg_flags & DD_JPEGDEC_ANY_SIZE) != 0;
     const bool auto_scale = any_size && jpeg_scale == 0;        // the draft rule per file; the slots are sized for scale 1
     if (auto_scale) jpeg_scale = 1;
@@ -97,6 +107,7 @@ static int ingest_create(const char *who, dd_ctx *ctx, int slots, int n_streams,
     g->raw_bytes = pixel_format ? (size_t)n_streams * src_h * src_w * 3 / 2 : (size_t)n_streams * src_h * src_w * 3;
     if (pixel_format == INGEST_JPEG) g->raw_bytes = jpeg_slot_bytes;
     if (ingest_is_422(pixel_format)) g->raw_bytes = (size_t)n_streams * src_h * src_w * 2;
+    if (ingest_is_raw8(pixel_format)) g->raw_bytes = (size_t)n_streams * src_h * src_w;
     g->own_out = g->transform || pixel_format != 0;          // BGR without a transform: the uploaded frames are the output
     g->fused = !(getenv("DD_INGEST_YUV_FUSED") && atoi(getenv("DD_INGEST_YUV_FUSED")) == 0);
     if (pixel_format == INGEST_JPEG) g->fused = false;      // decode into the staging buffer, then crop_resize
@@ -246,6 +257,20 @@ int dd_ingest_create_format(dd_ctx *ctx, int slots, int n_streams, int src_h, in
     return ingest_create("dd_ingest_create_format", ctx, slots, n_streams, src_h, src_w, dst_h, dst_w, flip, pixel_format, out);
 }
 
+// Layout and sizes are checked before ctx is touched: a bad call is answered with a code on a machine without a GPU.
+int dd_ingest_create_raw8(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip, int layout,
+                          dd_ingest **out) {
+    DD_REQUIRE(ingest_is_raw8(layout), DD_E_ARG, "dd_ingest_create_raw8: layout %d is none of 6 (RGGB), 7 (GRBG), 8 (GBRG), 9 (BGGR), 10 (gray)",
+               layout);
+    if (layout != INGEST_GRAY) {
+        DD_REQUIRE(src_w >= 3, DD_E_ARG, "dd_ingest_create_raw8: src_w %d below 3 (a demosaiced site needs both neighbours)", src_w);
+        DD_REQUIRE(src_h >= 3, DD_E_ARG, "dd_ingest_create_raw8: src_h %d below 3 (a demosaiced site needs both neighbours)", src_h);
+    }
+    DD_REQUIRE((int64_t)src_h * src_w <= INT_MAX - 256, DD_E_ARG, "dd_ingest_create_raw8: src_h %d x src_w %d is more pixels than a launch indexes",
+               src_h, src_w);
+    return ingest_create("dd_ingest_create_raw8", ctx, slots, n_streams, src_h, src_w, dst_h, dst_w, flip, layout, out, 0, 1, 0, true);
+}
+
 int dd_ingest_destroy(dd_ingest *g) {
     if (!g) return DD_OK;
     (void)hipStreamSynchronize(g->copy);
@@ -319,14 +344,17 @@ int dd_ingest_submit(dd_ingest *g, int slot) {
     if (g->used[slot]) DD_HIP(hipStreamWaitEvent(g->copy, g->done[slot], 0));       // the previous consumer of this slot
     DD_HIP(hipMemcpyAsync(g->d_raw[slot], g->h_raw[slot], g->raw_bytes, hipMemcpyHostToDevice, g->copy));
     if (g->format) {
-        const bool packed = ingest_is_422(g->format);
+        const bool packed = ingest_is_422(g->format), raw8 = ingest_is_raw8(g->format);
         auto convert = [&](uint8_t *dst) {
+            if (raw8) return ddk::raw8_to_bgr(g->copy, g->d_raw[slot], g->S, g->sh, g->sw, g->format, 0, 0, dst);
             return packed ? ddk::yuv422_to_bgr(g->copy, g->d_raw[slot], g->S, g->sh, g->sw, g->format, 0, 0, dst)
                           : ddk::yuv420_to_bgr(g->copy, g->d_raw[slot], g->S, g->sh, g->sw, g->format, 0, 0, 0, dst);
         };
         int rc;
         if (!g->transform) {                                    // the converter writes straight into the slot's output
             rc = convert(g->d_out[slot]);
+        } else if (g->fused && raw8) {
+            rc = ddk::raw8_resize(g->copy, g->d_raw[slot], g->S, g->sh, g->sw, g->format, g->flip, g->dh, g->dw, g->d_out[slot]);
         } else if (g->fused) {
             rc = packed ? ddk::yuv422_resize(g->copy, g->d_raw[slot], g->S, g->sh, g->sw, g->format, g->flip, g->dh, g->dw, g->d_out[slot])
                         : ddk::yuv420_resize(g->copy, g->d_raw[slot], g->S, g->sh, g->sw, g->format, g->flip, g->dh, g->dw, g->d_out[slot]);

@@ -14,6 +14,15 @@ With `pixel_format='yuy2'` or `'uyvy'` a slot holds packed 4:2:2, what a UVC / V
 _UYVY restated; tests/yuv422_ref.py is the definition, parity with OpenCV itself is unpinned).  `yuv422_to_bgr` is that conversion for
 frames already in device memory.
 
+With `pixel_format='bayer_rggb'`, `'bayer_grbg'`, `'bayer_gbrg'` or `'bayer_bggr'` a slot holds the 8-bit Bayer mosaic a machine-vision (GigE / USB3
+Vision BayerRG8 and its siblings) or CSI camera delivers before any colour processing, named by the sensor's top-left 2 x 2 block read row
+by row; with `'gray'` 8-bit monochrome (GREY / Y800, infrared cameras).  One byte per pixel, a third of BGR.  The mosaic is demosaiced on the
+copy stream by OpenCV's published bilinear rule restated (csrc/bayer.hip; cv2.cvtColor COLOR_BayerBG2BGR for RGGB, _BayerGB2BGR for GRBG,
+_BayerGR2BGR for GBRG, _BayerRG2BGR for BGGR -- OpenCV names the block at (1, 1); tests/bayer_ref.py is the definition, parity with OpenCV
+itself is unpinned), in one launch with the flip + resize.  `raw8_to_bgr` is that conversion for frames already in device memory.  Not
+built: 10 / 12 / 16-bit and packed RAW10 mosaics; white balance, gamma or colour matrices (a camera that sends 8-bit Bayer has applied its
+own before the mosaic leaves it); edge-aware / VNG demosaicing.
+
 With `pixel_format='jpeg'` a slot holds baseline JPEG files, what an IP camera's MJPEG stream or the reference's frame_%06d.jpg sequence
 (--input-cvat-dir) delivers -- a tenth or less of the raw bytes: `put(slot, stream, file)` copies a file into the slot's pinned arena and
 parses its header on the calling thread, `submit(slot)` uploads the bytes in use and decodes on the copy stream (csrc/jpeg_dec.hip,
@@ -28,8 +37,11 @@ import numpy as np
 from ._lib import lib, check, P
 from .runtime import default_context, ptr
 
-PIXEL_FORMATS = {'bgr': 0, 'nv12': 1, 'i420': 2, 'jpeg': 3, 'yuy2': 4, 'uyvy': 5}
+PIXEL_FORMATS = {'bgr': 0, 'nv12': 1, 'i420': 2, 'jpeg': 3, 'yuy2': 4, 'uyvy': 5, 'bayer_rggb': 6, 'bayer_grbg': 7, 'bayer_gbrg': 8, 'bayer_bggr': 9,
+                 'gray': 10}
 PACKED_422 = ('yuy2', 'uyvy')
+BAYER = ('bayer_rggb', 'bayer_grbg', 'bayer_gbrg', 'bayer_bggr')
+RAW8 = BAYER + ('gray',)
 
 
 class FrameIngest:
@@ -37,7 +49,8 @@ class FrameIngest:
                  jpeg_split=False, jpeg_any_size=False, jpeg_std_tables=False):
         """src_size / dst_size: (width, height) like the reference's `input_size`; dst defaults to src.
         pixel_format: what a slot holds, 'bgr' | 'nv12' | 'i420' (4:2:0 needs an even width and height) | 'yuy2' | 'uyvy' (packed 4:2:2,
-        named by FOURCC: an even width, any height) | 'jpeg'; the consumer always gets BGR.  jpeg_slot_bytes: the size of a JPEG slot's arena, by default n_streams * width * height * 3 // 8.
+        named by FOURCC: an even width, any height) | 'bayer_rggb' | 'bayer_grbg' | 'bayer_gbrg' | 'bayer_bggr' (an 8-bit mosaic named by its top-left
+        2 x 2 block: both sides at least 3, either may be odd) | 'gray' (8-bit monochrome, any size) | 'jpeg'; the consumer always gets BGR.  jpeg_slot_bytes: the size of a JPEG slot's arena, by default n_streams * width * height * 3 // 8.
         jpeg_scale ('jpeg' only; anything but 1 with another format is a ValueError): 1, 2, 4, 8 or 'auto' = deepdish_amd.jpeg.draft_scale(src_size,
         dst_size), Pillow's draft rule.  src_size stays what every file must state; the ring decodes ceil(height / scale) x ceil(width / scale)
         frames and resizes from there -- or decodes straight into the slot when that is dst_size and no flip is asked.
@@ -56,8 +69,9 @@ class FrameIngest:
         with the Annex K.3 tables (deepdish_amd.jpeg.JpegDecoder(std_tables=True)); without it such a file is ST_HEADER, as ever."""
         self._h = None
         if pixel_format not in PIXEL_FORMATS:
-            raise ValueError("pixel_format %r is none of 'bgr', 'nv12', 'i420', 'yuy2', 'uyvy', 'jpeg'%s"
-                             % (pixel_format, " (packed Y0 U Y1 V is spelt 'yuy2', its FOURCC)" if pixel_format == 'yuyv' else ''))
+            raise ValueError("pixel_format %r is none of 'bgr', 'nv12', 'i420', 'yuy2', 'uyvy', 'jpeg', 'bayer_rggb', 'bayer_grbg', 'bayer_gbrg', 'bayer_bggr', 'gray'%s"
+                             % (pixel_format, " (packed Y0 U Y1 V is spelt 'yuy2', its FOURCC)" if pixel_format == 'yuyv'
+                                else " (8-bit monochrome is spelt 'gray')" if pixel_format == 'grey' else ''))
         self.pixel_format = pixel_format
         self.sw, self.sh = src_size
         self.dw, self.dh = dst_size or src_size
@@ -65,6 +79,8 @@ class FrameIngest:
             raise ValueError('%s frames need an even width and height, got %dx%d' % (pixel_format, self.sw, self.sh))
         if pixel_format in PACKED_422 and self.sw % 2:
             raise ValueError('%s frames need an even width, got %dx%d' % (pixel_format, self.sw, self.sh))
+        if pixel_format in BAYER and (self.sw < 3 or self.sh < 3):
+            raise ValueError('%s frames need a width and height of at least 3, got %dx%d' % (pixel_format, self.sw, self.sh))
         if pixel_format != 'jpeg' and jpeg_scale != 1:
             raise ValueError("jpeg_scale %r: only a 'jpeg' ring decodes, a %r ring has nothing to scale" % (jpeg_scale, pixel_format))
         if pixel_format != 'jpeg' and jpeg_any_size:
@@ -105,6 +121,9 @@ class FrameIngest:
             else:
                 check(lib().dd_ingest_create_jpeg_scaled(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
                                                          self.jpeg_scale, self.jpeg_slot_bytes, ctypes.byref(h)), 'dd_ingest_create_jpeg_scaled')
+        elif pixel_format in RAW8:
+            check(lib().dd_ingest_create_raw8(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
+                                              PIXEL_FORMATS[pixel_format], ctypes.byref(h)), 'dd_ingest_create_raw8')
         else:
             check(lib().dd_ingest_create_format(self.ctx.handle, self.slots, self.S, self.sh, self.sw, self.dh, self.dw, int(bool(flip)),
                                                 PIXEL_FORMATS[pixel_format], ctypes.byref(h)), 'dd_ingest_create_format')
@@ -118,6 +137,8 @@ class FrameIngest:
                 shape = (self.S, self.sh, self.sw, 3)
             elif pixel_format in PACKED_422:
                 shape = (self.S, self.sh, self.sw, 2)
+            elif pixel_format in RAW8:
+                shape = (self.S, self.sh, self.sw)
             else:
                 shape = (self.S, self.sh * 3 // 2, self.sw)
             self._host.append(np.frombuffer(buf, dtype=np.uint8).reshape(shape))
@@ -132,8 +153,8 @@ class FrameIngest:
             pass
 
     def host(self, slot):
-        """Pinned numpy view of a slot, [S, src_h, src_w, 3] for BGR, [S, src_h * 3 // 2, src_w] for NV12 / I420 and [S, src_h, src_w, 2]
-        for YUY2 / UYVY (the shapes cv2 gives such frames): fill it, then submit(slot).  Blocks until the slot's previous upload has left the host buffer."""
+        """Pinned numpy view of a slot, [S, src_h, src_w, 3] for BGR, [S, src_h * 3 // 2, src_w] for NV12 / I420, [S, src_h, src_w, 2]
+        for YUY2 / UYVY and [S, src_h, src_w] for a Bayer mosaic or gray (the shapes cv2 gives such frames): fill it, then submit(slot).  Blocks until the slot's previous upload has left the host buffer."""
         if self.pixel_format == 'jpeg':
             raise ValueError("a 'jpeg' ring has no raw slot to fill: hand each stream's file to put(slot, stream, data)")
         check(lib().dd_ingest_wait_uploaded(self._h, slot), 'dd_ingest_wait_uploaded')
@@ -255,4 +276,36 @@ def yuv422_to_bgr(src, height, width, order, pitch=0, frame_stride=0, out=None, 
         raise ValueError('src holds %d bytes, %d frames need %d' % (src.numel(), batch, (batch - 1) * stride + extent))
     check(lib().dd_yuv422_to_bgr(ctx.handle, ptr(src), batch, height, width, PIXEL_FORMATS[order], pitch, frame_stride, ptr(out), stream),
           'dd_yuv422_to_bgr')
+    return out
+
+
+def raw8_to_bgr(src, height, width, layout, pitch=0, frame_stride=0, out=None, context=None, stream=None):
+    """8-bit raw sensor frames in device memory -> u8 [batch, height, width, 3] BGR device tensor.  layout: 'bayer_rggb', 'bayer_grbg',
+    'bayer_gbrg' or 'bayer_bggr' (cv2.cvtColor COLOR_BayerBG2BGR / _BayerGB2BGR / _BayerGR2BGR / _BayerRG2BGR restated: bilinear, the outer
+    ring of pixels repeats its inner neighbour; width and height at least 3) or 'gray' (COLOR_GRAY2BGR).  src: u8 device tensor,
+    [batch, height, width] when dense; padded surfaces are described by pitch (bytes per row, 0 = width) and frame_stride (0 = pitch *
+    height) -- the batch is then what fits.  out: a tensor to write into (the batch is then its first dimension).  The launch is queued on
+    the context's stream (or `stream`): `context.sync()` before torch reads the result on another stream."""
+    import torch
+    if layout not in RAW8:
+        raise ValueError("layout %r is none of 'bayer_rggb', 'bayer_grbg', 'bayer_gbrg', 'bayer_bggr', 'gray'" % (layout,))
+    if layout in BAYER and (width < 3 or height < 3):
+        raise ValueError('%s frames need a width and height of at least 3, got %dx%d' % (layout, width, height))
+    ctx = context or default_context()
+    p = pitch or width
+    extent = p * (height - 1) + width
+    stride = frame_stride or p * height
+    if out is not None:
+        batch = out.shape[0]
+    else:
+        batch = max(0, (src.numel() - extent) // stride + 1)
+        out = torch.empty((batch, height, width, 3), dtype=torch.uint8, device=src.device)
+    if tuple(out.shape[1:]) != (height, width, 3) or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError('out must be a contiguous u8 [batch, %d, %d, 3] tensor' % (height, width))
+    if src.dtype != torch.uint8 or not src.is_contiguous():
+        raise ValueError('src must be a contiguous u8 tensor')
+    if batch > 0 and src.numel() < (batch - 1) * stride + extent:
+        raise ValueError('src holds %d bytes, %d frames need %d' % (src.numel(), batch, (batch - 1) * stride + extent))
+    check(lib().dd_raw8_to_bgr(ctx.handle, ptr(src), batch, height, width, PIXEL_FORMATS[layout], pitch, frame_stride, ptr(out), stream),
+          'dd_raw8_to_bgr')
     return out

@@ -166,3 +166,33 @@ def to_yuv422(frame_bgr, order):
     out[..., luma] = q(y)
     out[:, 0::2, chroma], out[:, 1::2, chroma] = q(sub(u)), q(sub(v))
     return out
+
+
+BAYER_PATTERNS = ('rggb', 'grbg', 'gbrg', 'bggr')
+
+
+def to_bayer(frame_bgr, pattern):
+    """BGR u8 [H, W, 3] -> the 8-bit mosaic u8 [H, W] a sensor with that colour filter delivers: pattern 'rggb', 'grbg', 'gbrg' or 'bggr'
+    (a leading 'bayer_' is accepted) names the top-left 2 x 2 block read row by row, and every site keeps the sample of its own colour.
+    Plain sampling, no filtering: for synthetic inputs only, it pins nothing."""
+    name = pattern[6:] if isinstance(pattern, str) and pattern.startswith('bayer_') else pattern
+    if name not in BAYER_PATTERNS:
+        raise ValueError("pattern %r is none of 'rggb', 'grbg', 'gbrg', 'bggr'" % (pattern,))
+    f = np.asarray(frame_bgr, dtype=np.uint8)
+    if f.ndim != 3 or f.shape[2] != 3:
+        raise ValueError('to_bayer needs a BGR frame, got %r' % (f.shape,))
+    out = np.empty(f.shape[:2], dtype=np.uint8)
+    for k, colour in enumerate(name):
+        y, x = k >> 1, k & 1
+        out[y::2, x::2] = f[y::2, x::2, 'bgr'.index(colour)]
+    return out
+
+
+def to_gray(frame_bgr):
+    """BGR u8 [H, W, 3] -> 8-bit monochrome u8 [H, W]: Y = (1868 B + 9617 G + 4899 R + 8192) >> 14, the BT.601 luma weights 0.114, 0.587,
+    0.299 in 14 fractional bits (they sum to 16384, so a grey pixel keeps its level).  For synthetic inputs only: it pins nothing."""
+    f = np.asarray(frame_bgr, dtype=np.uint8)
+    if f.ndim != 3 or f.shape[2] != 3:
+        raise ValueError('to_gray needs a BGR frame, got %r' % (f.shape,))
+    f = f.astype(np.int32)
+    return ((1868 * f[..., 0] + 9617 * f[..., 1] + 4899 * f[..., 2] + 8192) >> 14).astype(np.uint8)

@@ -291,6 +291,19 @@ int dd_yuv420_to_bgr(dd_ctx *ctx, const uint8_t *src, int batch, int H, int W, i
  * H, a pitch below 2 W; the arguments are checked before ctx is used. */
 int dd_yuv422_to_bgr(dd_ctx *ctx, const uint8_t *src, int batch, int H, int W, int order, int pitch, int64_t frame_stride, uint8_t *dst,
                      void *stream);
+/* 8-bit raw sensor frames -> BGR for frames already on the device: one byte per pixel, what a machine-vision (GigE / USB3 Vision BayerRG8 and
+ * its siblings) or CSI camera delivers before any colour processing, and 8-bit monochrome.  layout 6 = RGGB, 7 = GRBG, 8 = GBRG, 9 = BGGR: the
+ * sensor's top-left 2 x 2 block read row by row (cv2.cvtColor COLOR_BayerBG2BGR, _BayerGB2BGR, _BayerGR2BGR, _BayerRG2BGR in that order:
+ * OpenCV names the block at (1, 1)); layout 10 = gray (COLOR_GRAY2BGR: B = G = R = the sample).  The mosaic is demosaiced by OpenCV's
+ * published bilinear rule restated (csrc/bayer.hip; tests/bayer_ref.py is the definition; parity with OpenCV itself is unpinned, the library
+ * is absent): out(x, y) = D(clamp(x, 1, W - 2), clamp(y, 1, H - 2)), and at an interior R or B site its own colour is the sample,
+ * G = (N + S + W + E + 2) >> 2, the opposite colour (NW + NE + SW + SE + 2) >> 2; at a G site G is the sample, the colour of its horizontal
+ * neighbours (W + E + 1) >> 1, of its vertical ones (N + S + 1) >> 1.  No white balance, gamma or colour matrix is applied.
+ * src: `batch` frames of W x H u8 (Bayer: both >= 3, either may be odd; gray: both >= 1).  pitch: bytes per row, 0 = W.  frame_stride: bytes
+ * between frames, 0 = dense (pitch * H).  dst: u8 dense [batch][H][W][3] BGR.  DD_E_ARG (the message names the argument) for another layout,
+ * a size too small, a pitch below W; the arguments are checked before ctx is used. */
+int dd_raw8_to_bgr(dd_ctx *ctx, const uint8_t *src, int batch, int H, int W, int layout, int pitch, int64_t frame_stride, uint8_t *dst,
+                   void *stream);
 
 /* ---------------------------------------------------------------- frame ingest
  * The CPU side of Pipeline.capture (deepdish.py:837-878): cv2.flip(frame, 0) (:864) + cv2.resize(frame,
@@ -314,6 +327,15 @@ int dd_ingest_create(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w
  * and DD_INGEST_YUV_FUSED=0 are as for 4:2:0.  pixel_format 3 names the JPEG ring, which dd_ingest_create_jpeg makes: refused here. */
 int dd_ingest_create_format(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip,
                             int pixel_format, dd_ingest **out);
+/* The same ring for slots that hold 8-bit raw sensor frames, dense: layout 6 .. 9 a Bayer mosaic, 10 monochrome, as dd_raw8_to_bgr (the
+ * ring's format codes continued; dd_ingest_create_format refuses them as it always has).  A slot and its device twin are
+ * n_streams * src_h * src_w bytes, a third of BGR.  dd_ingest_submit converts on the copy stream: straight into the slot's output without
+ * a flip or a resize, otherwise convert + flip + stretch in one launch (the mosaic is demosaiced in the stored frame, then flipped), or,
+ * with DD_INGEST_YUV_FUSED=0 (read here), convert-into-a-staging-buffer + the BGR ring's resize launch: the same bytes.  DD_E_ARG naming
+ * the value for another layout or a Bayer src_h / src_w below 3, checked before ctx is used.  dd_ingest_status and dd_ingest_jpeg_put on
+ * such a ring are DD_E_STATE.  The consumer receives BGR [n_streams][dst_h][dst_w][3]. */
+int dd_ingest_create_raw8(dd_ctx *ctx, int slots, int n_streams, int src_h, int src_w, int dst_h, int dst_w, int flip, int layout,
+                          dd_ingest **out);
 /* The same ring for slots that hold baseline JPEG files (see the JPEG decoder below): a slot is one pinned arena of slot_bytes, into which
  * dd_ingest_jpeg_put copies stream `stream`'s file at the next 64-byte-aligned offset (after waiting for the slot's previous upload, as
  * dd_ingest_wait_uploaded does) and parses its header on the calling thread; it may be called from several threads at once.  A full arena
