@@ -90,6 +90,9 @@ SIGNATURES = {
     'dd_mog2_apply': [P, P, c_double, P, P, P],
     'dd_mog2_apply_streams': [P, P, P, c_double, P, P, P],
     'dd_mask_box_count': [P, P, c_int, c_int, c_int, P, P, c_int, P, P],
+    'dd_mask_stream_count': [P, P, c_int, c_int, c_int, P, c_int, P],
+    'dd_pipeline_motion_gate': [P, P],
+    'dd_pipeline_gate_stats': [P, P, P, P],
     'dd_net_create': [P, P, c_int, P, c_int64, c_int, POINTER(P)],
     'dd_net_create_shared': [P, P, c_int, P, c_int64, c_int, POINTER(P)],
     'dd_net_activation_bytes': [P, POINTER(c_int64)],

@@ -125,6 +125,29 @@ def createBackgroundSubtractorMOG2(history=500, varThreshold=16, detectShadows=T
     return BackgroundSubtractorMOG2(history, varThreshold, detectShadows, n_streams, context)
 
 
+def mask_stream_count(mask_dev, streams=None, context=None):
+    """np.count_nonzero of whole mask planes (csrc/gate.hip): mask_dev device u8 [S, H, W], contiguous -> int32 [n], the non-zero
+    bytes of the planes `streams` lists (None: all S, in order).  Any byte value counts, MOG2's 127 (shadow) as its 255.  Planes that
+    are not listed are not read.  ValueError for another shape or dtype or an index outside 0 .. S - 1."""
+    if len(mask_dev.shape) != 3 or mask_dev.dtype != torch.uint8 or not mask_dev.is_contiguous():
+        raise ValueError('mask_dev: a contiguous u8 [S, H, W] device tensor, got %s %r' % (mask_dev.dtype, tuple(mask_dev.shape)))
+    S, h, w = (int(v) for v in mask_dev.shape)
+    if streams is None:
+        z, n = None, S
+    else:
+        z = np.asarray(list(streams))
+        if z.size and (z.ndim != 1 or z.dtype.kind not in 'iu' or ((z < 0) | (z >= S)).any()):
+            raise ValueError('streams: indices 0 .. %d, got %r' % (S - 1, streams))
+        z = np.ascontiguousarray(z.reshape(-1), dtype=np.int32)
+        n = int(z.size)
+    out = np.zeros(n, np.int32)
+    if n:
+        ctx = context or default_context()
+        check(lib().dd_mask_stream_count(ctx.handle, ptr(mask_dev), S, h, w, None if z is None else z.ctypes.data_as(P), n,
+                                         out.ctypes.data_as(P)), 'dd_mask_stream_count')
+    return out
+
+
 def motion_filter(counts, boxes_xywh, ratio):
     """deepdish.py:957: box k survives iff count_k >= ratio * w * h."""
     return [bool(c >= ratio * w * h) for c, (_, _, w, h) in zip(counts, boxes_xywh)]

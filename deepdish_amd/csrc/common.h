@@ -218,6 +218,8 @@ int mog2_apply_streams(dd_mog2 *m, hipStream_t s, const uint8_t *frames, const u
                        uint8_t *masked);
 int mog2_reset_streams(dd_mog2 *m, hipStream_t s, const int *streams_host, int n);
 int mask_box_count(hipStream_t s, const uint8_t *mask, int H, int W, const int *d_boxes, const int *d_box_stream, int K, int *d_counts);
+// non-zero bytes of whole mask planes (gate.hip): d_streams int32 [n] or NULL = planes 0 .. n - 1; d_counts int32 [n]
+int mask_stream_count(hipStream_t s, const uint8_t *mask, int H, int W, const int *d_streams, int n, int *d_counts);
 // a group of trackers sharing one pool (tracker.hip): every stream's tracker of a pipeline, stepped together in three phases
 int tracker_group_create(dd_ctx *ctx, int n, double max_cos, double max_iou, int max_age, int n_init, int budget, int tcap,
                          int gcap, dd_tracker **out);

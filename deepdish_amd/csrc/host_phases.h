@@ -70,6 +70,10 @@ struct StepPlan {
     std::vector<uint8_t> skp;                  // per position in act: a skip step for that stream (all ones = a lock-step skip step: dl empty)
     std::vector<int> rem_next;                 // the counters after this step (committed when it has succeeded)
     std::vector<uint8_t> has_next;
+    // the motion gate (gate_streams, below): empty / zero in a pipeline without it.  A gated stream is a third state of a position:
+    // not on a skip step (skp 0), yet without a block in the detector run (not in dl).
+    std::vector<uint8_t> gat;                  // per position in act: gated in this step
+    std::vector<int> dl_elig, cnt_elig;        // dl as plan_skip left it (the streams the gate counted), and their foreground pixels
     // the step's arguments.  frames: what the detector and the crops read (the masked copy under --enable-background-masking).
     // frames_next: NULL = no look-ahead run is queued (none given, no stream of it on a detector step, or masking).
     const uint8_t *frames_in = nullptr, *frames = nullptr, *frames_next = nullptr, *present = nullptr;
@@ -83,7 +87,8 @@ struct StepPlan {
 inline void plan_skip(const SkipCounters &c, StepPlan &pl) {
     const int n = (int)pl.act.size();
     pl.skp.assign(n, 0);
-    pl.dl.clear(); pl.dl_next.clear();
+    pl.gat.assign(n, 0);
+    pl.dl.clear(); pl.dl_next.clear(); pl.dl_elig.clear(); pl.cnt_elig.clear();
     pl.rem_next = c.rem; pl.has_next = c.has;
     for (int i = 0; i < n; ++i) {
         const int z = pl.act[i];
@@ -97,8 +102,48 @@ inline void plan_skip(const SkipCounters &c, StepPlan &pl) {
     for (int z : pl.act_next) if (!(pl.rem_next[z] > 0 && pl.has_next[z])) pl.dl_next.push_back(z);
 }
 
+// The motion gate (dd_pipeline_motion_gate): "nothing moved on this stream, so whatever the detector finds fails the motion test".
+// thr[z] = T[z] >= 0.  After MOG2 the step counts the foreground pixels of every stream of dl; counts[j] belongs to pl.dl[j].  A
+// stream with counts <= T leaves dl and is marked in gat: this step runs no detector chain, crops or encoder rows for it, its adaptor
+// output is empty, and the rest of the step sees a present stream with zero candidates.  dl stays ascending.  Returns the number gated.
+inline int gate_streams(const std::vector<int> &thr, const int *counts, StepPlan &pl) {
+    pl.dl_elig = pl.dl;
+    pl.cnt_elig.assign(counts, counts + pl.dl.size());
+    pl.dl.clear();
+    int gated = 0;
+    for (size_t i = 0, j = 0; i < pl.act.size() && j < pl.dl_elig.size(); ++i) {
+        if (pl.act[i] != pl.dl_elig[j]) continue;
+        const int z = pl.dl_elig[j];
+        if (pl.cnt_elig[j] <= thr[z]) { pl.gat[i] = 1; ++gated; }
+        else pl.dl.push_back(z);
+        ++j;
+    }
+    return gated;
+}
+
+// What dd_pipeline_gate_stats reports: steps on which the gate ran, gated stream-steps, and per stream the count of its last
+// detector-eligible step (-1: none yet) and whether that step was gated.  A step's plan enters when the step has succeeded.
+struct GateStats {
+    long long steps = 0, gated = 0;
+    std::vector<int> last_count;
+    std::vector<uint8_t> last_gated;
+    void start(size_t S) { steps = gated = 0; last_count.assign(S, -1); last_gated.assign(S, 0); }
+    void restart(int z) { last_count[z] = -1; last_gated[z] = 0; }
+    void commit(const std::vector<int> &thr, const StepPlan &pl) {
+        if (pl.dl_elig.empty()) return;
+        steps += 1;
+        for (size_t j = 0; j < pl.dl_elig.size(); ++j) {
+            const int z = pl.dl_elig[j];
+            last_count[z] = pl.cnt_elig[j];
+            last_gated[z] = pl.cnt_elig[j] <= thr[z];
+            gated += last_gated[z];
+        }
+    }
+};
+
 // Prefix sums per position in act.  doff: the tracker's input rows -- a stream on a detector step brings its kept boxes, one on a skip
-// step the first min(kept boxes now, feature rows of its last encoder run) of them, as zip() truncates (deepdish.py:1003-1014).
+// step the first min(kept boxes now, feature rows of its last encoder run) of them, as zip() truncates (deepdish.py:1003-1014); a gated
+// stream has no candidates, so kept(i) is 0 and it takes no row of either kind.
 // eoff: the rows the encoder makes in this step, the detector streams' only.  kept(i), retained(i): per position.
 template <class Kept, class Retained>
 inline void pair_counts(const std::vector<uint8_t> &skp, Kept kept, Retained retained, std::vector<int> &doff, std::vector<int> &eoff) {

@@ -177,6 +177,12 @@ struct dd_pipeline {
     DevBuf d_mask, d_masked, d_mbox;
     PinBuf h_mbox;
     long long motion_rejected = 0;
+    // The motion gate (dd_pipeline_motion_gate): after MOG2 a step counts the foreground pixels of its detector streams (csrc/gate.hip)
+    // and takes those with count <= gate_thr[z] out of the detector run.  gate_thr empty = no gate: nothing of it runs.
+    std::vector<int> gate_thr;
+    ddhost::GateStats gate;
+    DevBuf d_gate;
+    PinBuf h_gate;
     std::vector<int> off, doff, eoff;          // per-step prefix sums over the positions of act: candidates, tracker input rows, encoder rows
     std::vector<double> tlwh;
     // --object-detector-skip-frames (deepdish.py:892-893,929-938,1003-1014): one set of counters (host_phases.h) drives both forms.  On
@@ -404,8 +410,8 @@ int dd_pipeline_destroy(dd_pipeline *p) {
     (void)hipFree(p->d_anchors);
     dd_mog2_destroy(p->mog2);
     for (DevBuf *b : {&p->d_resized, &p->d_tmp, &p->d_post, &p->d_det, &p->d_fin, &p->d_pack, &p->d_tfl_boxes, &p->d_nms, &p->d_crop, &p->d_patches, &p->d_feats,
-                      &p->d_mask, &p->d_masked, &p->d_mbox, &p->d_feats_skip, &p->d_gather, &p->d_gframes, &p->d_lists, &p->d_store[0], &p->d_store[1]}) b->release();
-    for (PinBuf *b : {&p->h_fin, &p->h_nms, &p->h_crop, &p->h_mbox, &p->h_gather, &p->h_lists}) b->release();
+                      &p->d_mask, &p->d_masked, &p->d_mbox, &p->d_feats_skip, &p->d_gather, &p->d_gframes, &p->d_lists, &p->d_store[0], &p->d_store[1], &p->d_gate}) b->release();
+    for (PinBuf *b : {&p->h_fin, &p->h_nms, &p->h_crop, &p->h_mbox, &p->h_gather, &p->h_lists, &p->h_gate}) b->release();
     delete p;
     return DD_OK;
 }
@@ -482,6 +488,8 @@ int dd_pipeline_detector_skip_frames(dd_pipeline *p, int n) {
     DD_BEFORE_FIRST_STEP("dd_pipeline_detector_skip_frames");
     DD_REQUIRE(!p->skip_streams || n <= 0, DD_E_STATE,
                "dd_pipeline_detector_skip_frames: the pipeline has per-stream counters (dd_pipeline_detector_skip_streams); one form per pipeline");
+    DD_REQUIRE(p->gate_thr.empty() || n <= 0, DD_E_STATE, "dd_pipeline_detector_skip_frames: n = %d on a pipeline with a motion gate "
+               "(dd_pipeline_motion_gate): not built -- a gated step leaves no detector output for the skip steps after it to reuse", n);
     if (p->skip_streams) return DD_OK;         // n <= 0 beside per-stream counters: nothing to turn off
     p->skip_lockstep = n > 0;
     p->sk.start(p->S, std::max(n, 0));          // the same N for every stream, no phase
@@ -504,6 +512,8 @@ int dd_pipeline_detector_skip_streams(dd_pipeline *p, const int *n_host, const i
                "dd_pipeline_detector_skip_streams: the pipeline has the pipeline-wide counter (dd_pipeline_detector_skip_frames); one form per pipeline");
     for (int z = 0; z < p->S; ++z) {
         DD_REQUIRE(n_host[z] >= 0, DD_E_ARG, "dd_pipeline_detector_skip_streams: n[%d] = %d (>= 0)", z, n_host[z]);
+        DD_REQUIRE(p->gate_thr.empty() || n_host[z] == 0, DD_E_STATE, "dd_pipeline_detector_skip_streams: n[%d] = %d on a pipeline with a motion gate "
+                   "(dd_pipeline_motion_gate): not built -- a gated step leaves no detector output for the skip steps after it to reuse", z, n_host[z]);
         DD_REQUIRE(!phase_host || (phase_host[z] >= 0 && phase_host[z] <= n_host[z]), DD_E_ARG,
                    "dd_pipeline_detector_skip_streams: phase[%d] = %d (0 .. n[%d] = %d)", z, phase_host[z], z, n_host[z]);
     }
@@ -630,7 +640,47 @@ int dd_pipeline_stream_motion_ratio(dd_pipeline *p, const double *ratio_host) {
     for (int z = 0; z < p->S; ++z)
         DD_REQUIRE(ratio_host[z] >= 0.0 && ratio_host[z] <= 1.0, DD_E_ARG,
                    "dd_pipeline_stream_motion_ratio: ratio[%d] = %g (0 .. 1; subtraction cannot be off for some streams only)", z, ratio_host[z]);
+    for (int z = 0; z < p->S; ++z)
+        DD_REQUIRE(p->gate_thr.empty() || ratio_host[z] > 0.0, DD_E_STATE, "dd_pipeline_stream_motion_ratio: ratio[%d] = 0 on a pipeline with a motion "
+                   "gate (dd_pipeline_motion_gate): every box passes count >= 0, so an empty mask decides nothing", z);
     p->ratio_of.assign(ratio_host, ratio_host + p->S);
+    return DD_OK;
+}
+
+// The motion gate.  threshold_host int32 [S], T[z] >= 0.  On every step, after MOG2 and before the detector is consumed, the foreground
+// pixels (non-zero mask bytes, shadows included) of every stream on a detector step are counted by one launch of mask_stream_count_k
+// and one wait; a stream with count <= T[z] is GATED for this step: no detector chain, no crops, no encoder rows, an empty adaptor
+// output (injected rows for it are ignored: they stand for a detector output that was not made), and otherwise the step of a present
+// stream with zero candidates.  With T = 0 that is the ungated result: an empty mask fails every box of positive area at any ratio > 0
+// (deepdish.py:957).  Needs subtraction on with every ratio > 0 and no object_detector_skip_frames N > 0 (not built: a gated step
+// leaves nothing for the following skip steps to reuse, and the reference would test the retained boxes against the next mask).  No
+// frames_next run is queued ahead by a gated pipeline: the next step's detector list is not known before its mask is.
+int dd_pipeline_motion_gate(dd_pipeline *p, const int *threshold_host) {
+    DD_REQUIRE(p && threshold_host, DD_E_ARG, "dd_pipeline_motion_gate: NULL argument");
+    DD_BEFORE_FIRST_STEP("dd_pipeline_motion_gate");
+    DD_REQUIRE(p->mog2, DD_E_STATE, "dd_pipeline_motion_gate: background subtraction is off (dd_pipeline_background_subtraction first)");
+    for (int z = 0; z < p->S; ++z) {
+        DD_REQUIRE(threshold_host[z] >= 0, DD_E_ARG, "dd_pipeline_motion_gate: threshold[%d] = %d (>= 0)", z, threshold_host[z]);
+        DD_REQUIRE(p->ratio_of[z] > 0.0, DD_E_STATE, "dd_pipeline_motion_gate: background_subtraction_ratio[%d] = 0 -- every box passes "
+                   "count >= 0, so an empty mask decides nothing", z);
+        DD_REQUIRE(p->sk.n[z] == 0, DD_E_STATE, "dd_pipeline_motion_gate: object_detector_skip_frames N[%d] = %d -- gating together with skip "
+                   "frames is not built: a gated step leaves no detector output for the skip steps after it to reuse", z, p->sk.n[z]);
+    }
+    p->gate_thr.assign(threshold_host, threshold_host + p->S);
+    p->gate.start(p->S);
+    return DD_OK;
+}
+
+// out2_host = {steps on which the gate ran (some stream was on a detector step), gated stream-steps}; count_host int32 [S] (may be
+// NULL): the foreground pixels measured on each stream's last detector-eligible step, -1 before its first (and after its reset);
+// gated_host u8 [S] (may be NULL): whether that step was gated.  All zero / -1 for a pipeline without the gate.
+int dd_pipeline_gate_stats(dd_pipeline *p, long long *out2_host, int *count_host, uint8_t *gated_host) {
+    DD_REQUIRE(p && out2_host, DD_E_ARG, "dd_pipeline_gate_stats: NULL argument");
+    out2_host[0] = p->gate.steps; out2_host[1] = p->gate.gated;
+    for (int z = 0; z < p->S; ++z) {
+        if (count_host) count_host[z] = p->gate_thr.empty() ? -1 : p->gate.last_count[z];
+        if (gated_host) gated_host[z] = p->gate_thr.empty() ? 0 : p->gate.last_gated[z];
+    }
     return DD_OK;
 }
 
@@ -663,6 +713,7 @@ int dd_pipeline_reset_streams(dd_pipeline *p, const int *streams_host, int n) {
         const int z = streams_host[i];
         p->st[z].restart(p->wanted.size());
         p->sk.restart(z);                          // counter and phase as at construction
+        if (!p->gate_thr.empty()) p->gate.restart(z);
         if (p->skip_streams) {                     // the retained rows leave the store at its next refresh
             p->rows_retained -= p->ret_n[z];
             p->ret_n[z] = 0;
@@ -691,6 +742,8 @@ int dd_pipeline_mog2(dd_pipeline *p, dd_mog2 **out) {
 // --enable-background-masking (the detector and the encoder then see cv2.bitwise_and(frame, frame, mask=fgMask)).
 int dd_pipeline_background_subtraction(dd_pipeline *p, double ratio, int masking) {
     DD_REQUIRE(p && !(ratio > 1.0), DD_E_ARG, "dd_pipeline_background_subtraction: ratio must be <= 1 (negative = off)");
+    DD_REQUIRE(p->gate_thr.empty() || ratio > 0.0, DD_E_STATE, "dd_pipeline_background_subtraction: ratio %g on a pipeline with a motion gate "
+               "(dd_pipeline_motion_gate), which needs subtraction on and a ratio above 0", ratio);
     DD_DEVICE(p->ctx);
     DD_HIP(hipStreamSynchronize(p->ctx->stream));
     if (p->det_stream) DD_HIP(hipStreamSynchronize(p->det_stream));
@@ -1057,7 +1110,9 @@ static int phase_plan(dd_pipeline *p, StepPlan &pl, const uint8_t *frames_in, co
     const bool masking = p->mog2 && p->bg_masking;          // the detector and the encoder then read the masked copy, which a look-ahead run cannot
     pl.frames_in = frames_in; pl.present = present_host;
     pl.frames = masking ? p->d_masked.as<uint8_t>() : frames_in;
-    pl.frames_next = pl.dl_next.empty() || masking ? nullptr : frames_next;   // no stream of the next step on a detector step: nothing to queue
+    // no stream of the next step on a detector step: nothing to queue; under the motion gate the next step's list is not known before
+    // its mask is
+    pl.frames_next = pl.dl_next.empty() || masking || !p->gate_thr.empty() ? nullptr : frames_next;
     pl.inj_boxes = inj_boxes_host; pl.inj_scores = inj_scores_host; pl.inj_cls = inj_cls_host; pl.inj_offsets = inj_offsets_host;
     return DD_OK;
 }
@@ -1066,8 +1121,8 @@ static int phase_plan(dd_pipeline *p, StepPlan &pl, const uint8_t *frames_in, co
 static int phase_predict_mog2(dd_pipeline *p, const StepPlan &pl) {
     hipStream_t s = p->ctx->stream;
     int rc;
-    if (pl.dl.empty() && p->det) {
-        // no detector run reads these frames: the main stream takes over what the detector stream holds for them (the wait an ingest
+    if ((pl.dl.empty() || !p->gate_thr.empty()) && p->det) {
+        // no detector run reads these frames (or, under the motion gate, none was queued ahead and none may follow): the main stream takes over what the detector stream holds for them (the wait an ingest
         // ring queued there for their upload, dd_pipeline_detector_stream) before MOG2 reads them
         DD_HIP(hipEventRecord(p->skip_mark, p->det_stream));
         DD_HIP(hipStreamWaitEvent(s, p->skip_mark, 0));
@@ -1080,6 +1135,27 @@ static int phase_predict_mog2(dd_pipeline *p, const StepPlan &pl) {
                                           p->bg_masking ? p->d_masked.as<uint8_t>() : nullptr)) != DD_OK) return rc;
         if (p->bg_masking) p->det_pending = nullptr;           // a run queued on the unmasked frames: dropped
     }
+    return DD_OK;
+}
+
+// 2b. The motion gate: the foreground pixels of every stream of dl, one launch and one wait; the streams with nothing (at most T[z]
+// pixels) moving leave dl -- the third state of a position: not on a skip step, no block in the detector run -- with an empty adaptor
+// output.  The index arithmetic is ddhost::gate_streams.
+static int phase_motion_gate(dd_pipeline *p, StepPlan &pl) {
+    if (p->gate_thr.empty() || pl.dl.empty()) return DD_OK;
+    hipStream_t s = p->ctx->stream;
+    const int nd = (int)pl.dl.size();
+    int rc;
+    if ((rc = p->d_gate.reserve((size_t)p->S * sizeof(int))) != DD_OK) return rc;
+    if ((rc = p->h_gate.reserve((size_t)p->S * sizeof(int))) != DD_OK) return rc;
+    const int *d_list = nullptr;               // every stream: the planes in order, no list
+    if (nd < p->S && (rc = stage_list(p, s, pl.dl.data(), pl.dl.size(), &d_list)) != DD_OK) return rc;
+    if ((rc = ddk::mask_stream_count(s, p->d_mask.as<uint8_t>(), p->H, p->W, d_list, nd, p->d_gate.as<int>())) != DD_OK) return rc;
+    DD_HIP(hipMemcpyAsync(p->h_gate.p, p->d_gate.p, (size_t)nd * sizeof(int), hipMemcpyDeviceToHost, s));
+    DD_TIMED_WAIT(hipStreamSynchronize(s));                                                        // the gate's round trip
+    ddhost::gate_streams(p->gate_thr, p->h_gate.as<int>(), pl);
+    for (size_t i = 0; i < pl.act.size(); ++i)
+        if (pl.gat[i]) { StreamState &q = p->st[pl.act[i]]; q.boxes0.clear(); q.scores0.clear(); q.cls0.clear(); }
     return DD_OK;
 }
 
@@ -1218,7 +1294,7 @@ static int phase_consume_detector(dd_pipeline *p, const StepPlan &pl) {
     return DD_OK;
 }
 
-// 4. Injected detections replace the adaptor output of the streams on a detector step; box hygiene (deepdish.py:940-960) for every
+// 4. Injected detections replace the adaptor output of the streams on a detector step (not of a gated one: there was no such output); box hygiene (deepdish.py:940-960) for every
 // stream; off = the candidates per position
 static void phase_inject_hygiene(dd_pipeline *p, const StepPlan &pl) {
     const std::vector<int> &act = pl.act;
@@ -1229,7 +1305,7 @@ static void phase_inject_hygiene(dd_pipeline *p, const StepPlan &pl) {
         for (int i = i0; i < i1; ++i) {
             const int z = act[i];
             StreamState &q = p->st[z];
-            if (pl.inj_offsets && !pl.skp[i]) {
+            if (pl.inj_offsets && !pl.skp[i] && !pl.gat[i]) {
                 const int a = pl.inj_offsets[z], b = pl.inj_offsets[z + 1];
                 q.boxes0.assign(pl.inj_boxes + (size_t)a * 4, pl.inj_boxes + (size_t)b * 4);
                 q.scores0.assign(pl.inj_scores + a, pl.inj_scores + b);
@@ -1499,7 +1575,10 @@ static void phase_commit(dd_pipeline *p, const StepPlan &pl) {
     p->steps += 1;
     p->sk.rem = pl.rem_next; p->sk.has = pl.has_next;
     for (int i = 0; i < n; ++i) p->sk.last[pl.act[i]] = pl.skp[i];
-    p->det_stream_steps += nd; p->skip_stream_steps += n - nd;
+    int n_skp = 0;
+    for (int i = 0; i < n; ++i) n_skp += pl.skp[i];
+    p->det_stream_steps += nd; p->skip_stream_steps += n_skp;      // (a gated stream-step is neither)
+    if (!p->gate_thr.empty()) p->gate.commit(p->gate_thr, pl);
 }
 
 extern "C" {
@@ -1539,7 +1618,7 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
     int rc;
     if ((rc = phase_plan(p, p->plan, frames_in, present_host, frames_next, present_next_host, inj_boxes_host, inj_scores_host, inj_cls_host,
                          inj_offsets_host)) != DD_OK) return rc;
-    const StepPlan &pl = p->plan;
+    StepPlan &pl = p->plan;
     DD_DEVICE(p->ctx);
     const int n = (int)pl.act.size();
     p->masked_steps += present_host != nullptr;
@@ -1555,6 +1634,7 @@ int dd_pipeline_step3(dd_pipeline *p, const uint8_t *frames_in, const uint8_t *p
     const double t0 = now_s();
     p->step_wait = 0;
     if ((rc = phase_predict_mog2(p, pl)) != DD_OK) return rc;
+    if ((rc = phase_motion_gate(p, pl)) != DD_OK) return rc;
     if ((rc = phase_consume_detector(p, pl)) != DD_OK) return rc;
     if (inj_offsets_host)
         DD_REQUIRE(inj_boxes_host && inj_scores_host && inj_cls_host, DD_E_ARG, "dd_pipeline_step: injected arrays missing");

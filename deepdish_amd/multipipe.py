@@ -171,6 +171,36 @@ def _stream_ratio(ratio, S):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _stream_gate(motion_gate, S, ratio, skip_frames):
+    """motion_gate= -> None (no gate) or int32 [S] thresholds, each >= 0: an int holds for all streams, a sequence gives S ints.
+    `ratio`: _stream_ratio's result, `skip_frames`: object_detector_skip_frames as given.  ValueError naming the parameter for a
+    wrong type, rank, length or sign, and for what the gate does not go with: subtraction off, a stream's ratio equal to 0, either
+    form of object_detector_skip_frames with some N > 0."""
+    if motion_gate is None:
+        return None
+    if isinstance(motion_gate, (str, bytes, bool)):
+        raise ValueError('motion_gate: None, an int, or one int per stream (%d of them), got %r' % (S, motion_gate))
+    a = np.asarray(motion_gate)
+    if a.dtype.kind not in 'iu':
+        raise ValueError('motion_gate: integers (foreground pixels), got %r' % (motion_gate,))
+    if a.ndim == 0:
+        a = np.full(S, int(a))
+    elif a.ndim != 1 or a.shape[0] != S:
+        raise ValueError('motion_gate: one value, or one per stream with shape (%d,), got shape %r' % (S, a.shape))
+    if (a < 0).any() or (a > np.iinfo(np.int32).max).any():
+        raise ValueError('motion_gate: 0 <= threshold < 2**31 for every stream, got %r' % (a.tolist(),))
+    if ratio is None:
+        raise ValueError('motion_gate with background_subtraction_ratio off: the gate reads the foreground mask')
+    if (ratio == 0).any():
+        raise ValueError('motion_gate with background_subtraction_ratio = 0 (%r): every box passes count >= 0, so an empty mask '
+                         'decides nothing' % (ratio.tolist(),))
+    if skip_frames is not None and (np.asarray(skip_frames) > 0).any():
+        raise ValueError('motion_gate with object_detector_skip_frames=%r: not built -- a gated step leaves no detector output for the '
+                         'skip steps after it to reuse (the reference would test the retained boxes against the next frame\'s mask)'
+                         % (skip_frames,))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
 def _reset_streams(streams, S):
     """reset(streams) -> contiguous int32 list; ValueError for an index outside 0 .. S - 1 or listed twice."""
     a = np.asarray(list(streams))
@@ -191,7 +221,8 @@ class MultiStreamPipeline:
                  nms_max_overlap=0.6, max_iou_distance=0.7, max_age=60, n_init=3, context=None, run_detector=True,
                  encoder_max_batch=None, track_capacity=512, gallery_capacity=256, background_subtraction_ratio=None,
                  background_masking=False, graph=None, object_detector_skip_frames=None, metric='cosine',
-                 association='host', detector_letterbox=False, ground=None, topdownview_size_m=None, object_detector_skip_phase=None):
+                 association='host', detector_letterbox=False, ground=None, topdownview_size_m=None, object_detector_skip_phase=None,
+                 motion_gate=None):
         from .tools.yolov5 import letterbox_pad
         from .ground import for_pipeline
         # the reference's --3d mode (deepdish.py:592-611): a GroundPlane, or a list with one per stream; None: no top-down view
@@ -208,7 +239,8 @@ class MultiStreamPipeline:
         v_age, v_init = _stream_values(max_age, 'max_age', S, integer=True), _stream_values(n_init, 'n_init', S, integer=True)
         v_cos, v_iou = _stream_values(max_cosine_distance, 'max_cosine_distance', S), _stream_values(max_iou_distance, 'max_iou_distance', S)
         v_nms = _stream_values(nms_max_overlap, 'nms_max_overlap', S)
-        _stream_ratio(background_subtraction_ratio, S)
+        # the motion gate: None, one threshold (foreground pixels) for all streams or one per stream -- and what it does not go with
+        gate = _stream_gate(motion_gate, S, _stream_ratio(background_subtraction_ratio, S), object_detector_skip_frames)
         self.metric = metric
         metric_kind = _metric_kind(metric)   # 'cosine' or 'euclidean' (nn_matching.py:126-132), else ValueError -- before anything is built
         self.association = association
@@ -326,6 +358,11 @@ class MultiStreamPipeline:
             check(lib().dd_pipeline_detector_skip_streams(self._h, ptr(skip_n), ptr(skip_phase)), 'dd_pipeline_detector_skip_streams')
         elif object_detector_skip_frames is not None:
             check(lib().dd_pipeline_detector_skip_frames(self._h, int(object_detector_skip_frames)), 'dd_pipeline_detector_skip_frames')
+        # the motion gate (dd_pipeline_motion_gate): a stream whose foreground mask holds at most motion_gate[z] pixels runs no detector
+        # and no encoder in that step and hands its tracker zero detections; None: every stream runs both, as always
+        self.motion_gate = None if gate is None else gate.copy()
+        if gate is not None:
+            check(lib().dd_pipeline_motion_gate(self._h, ptr(gate)), 'dd_pipeline_motion_gate')
 
     def background_subtraction(self, ratio, masking=False):
         """deepdish.py:512,889,957: ratio = --background-subtraction-ratio (reference default 0.25); None or a negative
@@ -387,7 +424,9 @@ class MultiStreamPipeline:
         detector runs on the present frames only.  present_next belongs to frames_next; a next step that arrives with another mask than
         announced runs its detector itself, with the same result.  An all-zero mask is a legal step.  Not with the int form of
         object_detector_skip_frames (one counter per pipeline: all streams in lock-step); the per-stream form (a sequence of S ints)
-        takes masks: a stream's counter moves only on the steps it is present in."""
+        takes masks: a stream's counter moves only on the steps it is present in.
+        With motion_gate set no frames_next run is queued ahead (the next step's detector list is not known before its mask is): the
+        argument stays legal, the next step runs its detector itself, and `injected` rows of a gated stream are ignored."""
         assert tuple(frames_dev.shape) == (self.S, self.H, self.W, 3)
         assert frames_next is None or tuple(frames_next.shape) == (self.S, self.H, self.W, 3)
         present, present_next = self._mask(present, 'present'), self._mask(present_next, 'present_next')
@@ -503,6 +542,14 @@ class MultiStreamPipeline:
         check(lib().dd_pipeline_skip_stats(self._h, ptr(out), ptr(sk)), 'dd_pipeline_skip_stats')
         return dict(detector_stream_steps=int(out[0]), skip_stream_steps=int(out[1]), carry_launches=int(out[2]), rows_retained=int(out[3]),
                     store_bytes=int(out[4]), skipped=sk.astype(bool))
+
+    def gate_stats(self):
+        """The motion gate's counters: `steps` on which it ran (some stream was on a detector step), `gated_stream_steps` summed over
+        the steps, and per stream `count` int32 [S] -- the foreground pixels measured on its last detector-eligible step, -1 before its
+        first and after its reset -- and `gated` bool [S], whether that step was gated.  A step without the stream keeps its entry."""
+        out, cnt, g = np.zeros(2, dtype=np.int64), np.zeros(self.S, dtype=np.int32), np.zeros(self.S, dtype=np.uint8)
+        check(lib().dd_pipeline_gate_stats(self._h, ptr(out), ptr(cnt), ptr(g)), 'dd_pipeline_gate_stats')
+        return dict(steps=int(out[0]), gated_stream_steps=int(out[1]), count=cnt, gated=g.astype(bool))
 
     def detector_stream(self):
         """The stream the look-ahead detector run is queued on (None without a detector): the consumer to name when acquiring the NEXT

@@ -11,7 +11,7 @@ from time import time
 import numpy as np
 import torch
 
-from .background import createBackgroundSubtractorMOG2, motion_filter
+from .background import createBackgroundSubtractorMOG2, motion_filter, mask_stream_count
 from .deep_sort import nn_matching, preprocessing
 from .deep_sort.detection import Detection
 from .deep_sort.tracker import Tracker, association_kind
@@ -77,12 +77,26 @@ class HotPath:
                  context=None, run_detector=True, disable_background_subtraction=True, background_subtraction_ratio=0.25,
                  enable_background_masking=False, log=None, restore_from_log=False, mqtt_publish=None, mqtt_topic='default/topic',
                  mqtt_acp_id=None, mqtt_verbosity=1, cpu_temp=None, annotations=None, object_detector_skip_frames=None,
-                 metric='cosine', association='host', detector_letterbox=False, ground=None, topdownview_size_m=None):
+                 metric='cosine', association='host', detector_letterbox=False, ground=None, topdownview_size_m=None, motion_gate=None):
         from .ground import for_pipeline
         # the reference's --3d mode (deepdish.py:592-611): a GroundPlane; None: no top-down view
         self.ground, self.topdown_scale = for_pipeline(ground, topdownview_size_m, input_size, 1)      # ValueError before anything is built
         if detector_letterbox is not False and detector_letterbox is not None and 'yolov5' not in model:      # before anything is built
             raise ValueError('%s: detector_letterbox is the YOLOv5 detector\'s option; the other detectors are trained on stretched input' % model)
+        # the motion gate (MultiStreamPipeline's, for one stream): None, or a threshold in foreground pixels -- before anything is built
+        if motion_gate is not None:
+            if isinstance(motion_gate, bool) or not isinstance(motion_gate, (int, np.integer)) or motion_gate < 0:
+                raise ValueError('motion_gate: None or an int >= 0 (foreground pixels), got %r' % (motion_gate,))
+            if disable_background_subtraction:
+                raise ValueError('motion_gate with disable_background_subtraction: the gate reads the foreground mask')
+            if not background_subtraction_ratio > 0:
+                raise ValueError('motion_gate with background_subtraction_ratio=%r: every box passes count >= 0, so an empty mask '
+                                 'decides nothing' % (background_subtraction_ratio,))
+            if object_detector_skip_frames:
+                raise ValueError('motion_gate with object_detector_skip_frames=%r: not built -- a gated frame leaves no detector output '
+                                 'for the skipped frames after it to reuse' % (object_detector_skip_frames,))
+        self.motion_gate = None if motion_gate is None else int(motion_gate)
+        self.gated_frames = 0
         nn_matching.metric_kind(metric)              # 'cosine' or 'euclidean' (nn_matching.py:126-132), else ValueError -- before anything is built
         association_kind(association)                # 'host' or 'device', else ValueError -- likewise
         self.ctx = context or default_context()
@@ -140,8 +154,14 @@ class HotPath:
             self.backSub.apply_device(frame_dev[None], masked_out=masked[None] if masked is not None else None)
             if masked is not None:
                 frame_dev = masked
+        # the motion gate: at most motion_gate foreground pixels (the mask MOG2 just wrote, counted by csrc/gate.hip) -- every box the
+        # detector could return fails the motion test, so neither it nor the encoder runs and `injected` is ignored
+        gated = self.motion_gate is not None and int(mask_stream_count(self.backSub.mask, context=self.ctx)[0]) <= self.motion_gate
+        self.gated_frames += gated
         skipped = self._skip_rem > 0 and self._prev_objd is not None                             # :929-938
-        if skipped:
+        if gated:
+            boxes0, labels0, scores0 = [], [], []
+        elif skipped:
             boxes0, labels0, scores0 = self._prev_objd
             self._skip_rem -= 1
         else:
@@ -195,7 +215,7 @@ class HotPath:
         if self.sink is not None:
             self.sink.crossings(events, t0 if t_frame is None else t_frame, self.frame_count)            # :1116-1123
         self.timings = dict(objd=t1 - t0, feat=t2 - t1, trak=t3 - t2, proc=t4 - t3, e2e=t4 - t0)
-        if skipped:                                                                                     # :980, :1019
+        if skipped or gated:                                                                            # :980, :1019
             del self.timings['objd'], self.timings['feat']
         return events
 

@@ -398,6 +398,13 @@ int dd_mog2_reset_streams(dd_mog2 *m, const int *streams_host, int n, void *stre
  * [n_boxes].  Synchronises the stream. */
 int dd_mask_box_count(dd_ctx *ctx, const uint8_t *mask, int n_streams, int height, int width, const int *boxes_xywh_host,
                       const int *box_stream_host, int n_boxes, int *counts_host, void *stream);
+/* np.count_nonzero of whole mask planes (csrc/gate.hip, mask_stream_count_k): mask_dev device u8 [n_streams][height][width], planes
+ * dense; streams_host int32 [n], each 0 .. n_streams - 1, or NULL = all of them in order (then n must be n_streams); counts_host int32
+ * [n], counts_host[i] = the non-zero bytes of plane streams_host[i].  Any byte value counts: MOG2's 127 (shadow) as its 255.  Planes
+ * that are not listed are not read.  An integer sum: the same ints on every call.  n = 0 does nothing; n <= 65 535.  Anything else
+ * is DD_E_ARG before a launch.  Runs on the context's stream and synchronises it. */
+int dd_mask_stream_count(dd_ctx *ctx, const uint8_t *mask_dev, int n_streams, int height, int width, const int *streams_host, int n,
+                         int *counts_host);
 
 /* Frame compaction (csrc/gather.hip): dst frame i = src frame idx[i] for i < n, frames of frame_bytes bytes behind one another; src_dev
  * holds n_src frames.  idx_host int32 [n] must be strictly increasing and < n_src (DD_E_ARG otherwise: checked on the host, never by a
@@ -712,6 +719,34 @@ int dd_pipeline_stream_nms_overlap(dd_pipeline *p, const double *overlap_host);
  * compares against ratio[z].  Only after dd_pipeline_background_subtraction turned subtraction on (DD_E_STATE otherwise); turning it
  * on again resets every stream to that call's ratio.  Subtraction cannot be off for some streams only. */
 int dd_pipeline_stream_motion_ratio(dd_pipeline *p, const double *ratio_host);
+/* The motion gate (opt-in; this build's addition -- the reference has none, its nearest relative is the power-saving delay of
+ * deepdish.py:963-969): skip the detector and the encoder for the streams where nothing moved.  threshold_host int32 [n_streams],
+ * T[z] >= 0.  From then on every step, after tracker predict and MOG2 and before the detector's output is consumed, counts the
+ * foreground pixels of each stream on a detector step (mask_stream_count_k, one launch, one more host wait per step) and GATES the
+ * streams with count <= T[z] for this step: no detector chain (resize, forward, post-process, adaptor tail), no crops, no encoder
+ * rows; the adaptor output dd_pipeline_detections returns is empty; injected rows of the stream are ignored (they stand for a detector
+ * output that was not made); everything else runs as for any present stream -- box hygiene, motion test and NMS over zero candidates,
+ * the tracker update with zero detections, the count line, its frame number.  The contract: with T[z] = 0 the pipeline is, step by
+ * step, bit for bit the ungated one (tracks, galleries, counts, frames seen, motion mask), because an empty mask fails every box of
+ * positive area at any ratio > 0 (deepdish.py:957) -- with these differences: (1) a box that the hygiene clips to w * h == 0 passes
+ * the reference's test on any mask (0 >= ratio * 0) and is a detection ungated; on a gated step it does not exist; (2) the adaptor
+ * output of a gated step is empty instead of holding boxes that would all have been rejected; (3) the motion test's rejected counter
+ * does not count what was never made, and dd_pipeline_skip_stats' detector stream-steps exclude gated ones (they are no skip
+ * stream-steps either).  T[z] > 0 is a stated approximation for noisy sensors: a stream with at most T[z] foreground pixels hands
+ * its tracker nothing, whatever the detector would have found there.  No frames_next run is queued ahead by a gated pipeline (the next
+ * step's detector list is not known before its mask is): the argument stays legal and the next step runs its detector itself.
+ * Presence masks, background masking and dd_pipeline_reset_streams are allowed (after a reset MOG2 starts over for the stream; the
+ * counts that yields decide).  The gate is a parameter of the pipeline, not stream state: snapshots do not carry it.
+ * DD_E_STATE: after the first step; subtraction off; a stream's ratio equal to 0 (every box passes count >= 0, so an empty mask decides
+ * nothing); either form of object_detector_skip_frames with some N > 0 -- not built: a gated step leaves no detector output for the
+ * following skip steps to reuse, and the reference tests the retained boxes against the NEXT frame's mask.  The same combinations are
+ * refused by the other setters once the gate is set.  DD_E_ARG: NULL, a negative threshold. */
+int dd_pipeline_motion_gate(dd_pipeline *p, const int *threshold_host);
+/* out2_host = {steps on which the gate ran (some stream was on a detector step), gated stream-steps summed over the steps}; count_host
+ * int32 [n_streams] (may be NULL): the foreground pixels measured on the stream's last detector-eligible step, -1 before its first
+ * and after its reset; gated_host u8 [n_streams] (may be NULL): whether that step was gated.  A step without the stream keeps its
+ * entry.  Zeros and -1 for a pipeline without the gate. */
+int dd_pipeline_gate_stats(dd_pipeline *p, long long *out2_host, int *count_host, uint8_t *gated_host);
 /* The listed streams start over; the reference restarts the camera's process.  Between steps, at any time.  Afterwards each listed stream
  * is in the state of a stream of a pipeline just built with the same parameters: no tracks, no deleted list, next id 1
  * (tracker.py:40-49), its gallery chunks back in the pool; empty path store and votes (deepdish.py:519), counters zero (:525-528); no
