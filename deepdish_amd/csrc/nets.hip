@@ -3801,9 +3801,12 @@ void spatial_tile(int ho, int wo, int stride, int max_patch, ConvP &P) {
 }
 
 // Can the pooled 3x3 layer P run as conv3x3_pool_rows_k on nimg images?  (P.p[0..1] = pooled height, width.)
+// At least four pooled rows (H >= 10): the launcher splits a crop into up to four units of pooled rows, and the kernel stores a unit's last
+// pooled row after its round loop without asking whether the unit has one -- a unit with no rows (fewer pooled rows than units) would store
+// an unset row in front of its crop's tensor.
 bool pool_rows_fusable(const ConvP &P, int nimg) {
     static const bool tiled = dd_env_int("DD_POOL_TILED", 0) != 0;
-    return !tiled && nimg >= 160 && P.W == 32 && P.wo == 32 && P.H == P.ho && P.H % 2 == 0 && P.p[0] == P.H / 2 - 1 && P.p[1] == 15 &&
+    return !tiled && nimg >= 160 && P.W == 32 && P.wo == 32 && P.H == P.ho && P.H % 2 == 0 && P.p[0] == P.H / 2 - 1 && P.p[0] >= 4 && P.p[1] == 15 &&
            P.pad_t == 1 && P.pad_l == 1 && P.cin == 32 && P.cout == 32 && P.act == ACT_ELU;
 }
 
@@ -3994,7 +3997,7 @@ bool c64_strips_eligible(const ConvP &P, int nimg, int max_batch) {
     static const bool off = dd_env_int("DD_C64_STRIPS_OFF", 0) != 0;
     static const int min_items = dd_env_int("DD_C64_STRIPS_MIN", 1024);      // two items per wave slot of the chip
     return !off && P.kh == 3 && P.kw == 3 && P.stride == 1 && P.pad_t == 1 && P.pad_l == 1 && P.cin == 64 && P.cout == 64 &&
-           P.cout_pad == 64 && P.kpad == 576 && P.epi == EPI_F16 && P.W > 8 && P.W % 8 == 0 && P.wo == P.W && P.H == P.ho && P.H % 2 == 0 &&
+           P.cout_pad == 64 && P.kpad == 576 && P.epi == EPI_F16 && P.W > 8 && P.W % 8 == 0 && P.wo == P.W && P.H == P.ho && P.H % 2 == 0 && P.H >= 6 &&
            P.splitk <= 1 && P.act == ACT_SILU && !P.out2 && (!P.res || (P.cs_res % 8 == 0 && P.coff_res % 8 == 0)) &&
            P.cs_in % 8 == 0 && P.coff_in % 8 == 0 && (long long)nimg * (P.W >> 3) >= min_items &&
            (long long)dd_ceil_div(max_batch * P.ho * P.wo, 64) >= 256;    // launch_conv would not split K for this engine: same summation order
@@ -4018,11 +4021,14 @@ int launch_conv3x3_c64_strips(hipStream_t s, const ConvP &P, int nimg, int devic
     return DD_OK;
 }
 
+// H >= 6 (here and for the strips): the kernel's ring of C64_SLOTS = 11 row slots holds the 4 rows a round reads and the rows of C64_LEAD = 3
+// rounds of look-ahead -- 7 when one of the three rounds opens an image (2 + 2 + 3).  With H = 4 or 2 two or all three of them do (8 or 9
+// rows), and the look-ahead DMAs would land in slots the round has yet to read.
 bool c64_rows_eligible(const ConvP &P, int nimg, int max_batch) {
     static const bool off = dd_env_int("DD_C64_ROWS_OFF", 0) != 0;
     static const int min_img = dd_env_int("DD_C64_ROWS_MIN", 512);
     return !off && nimg >= min_img && P.kh == 3 && P.kw == 3 && P.stride == 1 && P.pad_t == 1 && P.pad_l == 1 && P.cin == 64 && P.cout == 64 &&
-           P.cout_pad == 64 && P.kpad == 576 && P.epi == EPI_F16 && P.W == 8 && P.wo == 8 && P.H == P.ho && P.H % 2 == 0 && P.splitk <= 1 &&
+           P.cout_pad == 64 && P.kpad == 576 && P.epi == EPI_F16 && P.W == 8 && P.wo == 8 && P.H == P.ho && P.H % 2 == 0 && P.H >= 6 && P.splitk <= 1 &&
            ((P.act == ACT_ELU && !P.res && !P.out2) || (P.act == ACT_NONE && P.res && P.out2 && P.cs_res % 8 == 0 && P.coff_res % 8 == 0)) &&
            (long long)dd_ceil_div(max_batch * P.ho * P.wo, 64) >= 256;    // launch_conv would not split K for this engine: same summation order
 }
